@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the TLS grid-search hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config k2_90d]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config k2_90d] [--dump-outputs DIR]
 
 N > 1 runs one process per GPU: either under `python -m torch.distributed.run --nproc-per-node N
 ... bench.py --gpus N` (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment) or started
@@ -317,8 +317,40 @@ class Harness(object):
         return elapsed, kernel_ms
 
 
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: at most this much in all (a fixed, seeded sample beyond it)
+
+
+def _host_gathered_results(h, ctx):
+    """Every rank's fetched (chi2, row, depth) of its last search, all-gathered over the host channel, rank after rank
+    (the layout of the RCCL gather).  Collective: every rank calls it."""
+    c, r, d = ctx.fetch()
+    parts = h.channel.allgather_bytes(c.tobytes() + r.tobytes() + d.tobytes())
+    n = [len(b) // 24 for b in parts]
+    return (numpy.concatenate([numpy.frombuffer(b[:8 * k], dtype=numpy.float64) for b, k in zip(parts, n)]),
+            numpy.concatenate([numpy.frombuffer(b[8 * k:16 * k], dtype=numpy.int64) for b, k in zip(parts, n)]),
+            numpy.concatenate([numpy.frombuffer(b[16 * k:], dtype=numpy.float64) for b, k in zip(parts, n)]))
+
+
+def dump_outputs(out_dir, outputs):
+    """Writes each array as out_dir/<name>.npy in float64 (the row index is exact in it).  Past DUMP_LIMIT_BYTES in all,
+    every array keeps the same fixed, seeded sample of its entries (in grid order) and index.npy says which."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: numpy.asarray(v, dtype=numpy.float64) for k, v in outputs.items()}
+    n = len(next(iter(arrays.values())))
+    assert all(len(a) == n for a in arrays.values())
+    per_entry = 8 * (len(arrays) + 1)
+    if n * 8 * len(arrays) > DUMP_LIMIT_BYTES:
+        keep = numpy.sort(numpy.random.RandomState(0).choice(n, DUMP_LIMIT_BYTES // per_entry, replace=False))
+        arrays = {k: a[keep] for k, a in arrays.items()}
+        arrays["index"] = keep.astype(numpy.float64)
+    for k, a in arrays.items():
+        numpy.save(os.path.join(out_dir, k + ".npy"), a)
+    return sorted(arrays)
+
+
 def run_survey(h, args, inp):
-    """Survey layout: one full-grid search of this rank's light curve per step."""
+    """Survey layout: one full-grid search of this rank's light curve per step.  With --dump-outputs, h.outputs holds what
+    the last timed step handed its caller: every rank's per-period (chi2, row, depth), rank after rank."""
     ctx = h.ctx
     periods = inp["periods"]
     ctx.prepare(inp["t"], inp["y"], inp["dy"], periods, inp["table"], inp["params"])
@@ -346,6 +378,11 @@ def run_survey(h, args, inp):
     if staged:  # outside the timed region: one gathered slot on the host
         g_chi2, g_row, g_depth = ctx.comm_fetch_staged(count_per_rank, n_slots, n_slots - 1, h.world)
         assert len(g_chi2) == count_per_rank * h.world
+        if args.dump_outputs:
+            h.outputs = {"chi2": g_chi2, "row": g_row, "depth": g_depth}
+    elif args.dump_outputs:
+        c, r, d = ctx.fetch() if h.channel is None else _host_gathered_results(h, ctx)
+        h.outputs = {"chi2": c, "row": r, "depth": d}
     return elapsed, kernel_ms
 
 
@@ -585,7 +622,14 @@ def main():
                          "(default: fail with a non-zero status)")
     ap.add_argument("--force-collective", action="store_true",
                     help="1-GPU runs: go through the RCCL code path with a one-rank communicator")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed survey steps handed their caller in the last one "
+                         "(every rank's per-period chi2, row, depth) as DIR/<name>.npy, float64, at most 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.gpus > 1 and args.mode == "shard":
+        ap.error("--dump-outputs writes the survey layout's outputs: not with --mode shard")
 
     # Started plainly (`python bench.py --gpus N`, no launcher): become the launcher.  N rank
     # processes of this same command line, one per GPU, with the environment contract of
@@ -615,6 +659,9 @@ def main():
             kernel_ms = shard_out[0]["kernel_ms_max_rank"]
 
     out = None
+    if rank == 0 and args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, h.outputs)
+        sys.stderr.write("bench: wrote %s to %s\n" % (", ".join(k + ".npy" for k in dumped), args.dump_outputs))
     if rank == 0:
         extras = world == 1 and not args.no_extras
         # one counted pass (outside the timed region) for the work statistics
