@@ -179,6 +179,8 @@ int tls_debug_poison_lds(tls_ctx *ctx, uint32_t word);
  * tls_search_batch call (a stall in one group -- a transfer, a wait, a T0-fit launch -- shows here; bench.py prints the
  * largest and the median).  Returns the number of groups; out may be NULL. */
 int tls_debug_batch_group_ms(const tls_ctx *ctx, double *out, int64_t capacity);
+/* developer instrumentation: bytes of device memory the context holds, in all and in the final T0 fit's HBM scratch */
+int tls_debug_device_bytes(const tls_ctx *ctx, int64_t *total, int64_t *t0_fit_scratch);
 /* block until the stream is idle */
 int tls_synchronize(tls_ctx *ctx);
 /* fetch: copy results (and counters, may be NULL) back; synchronises. */
@@ -251,6 +253,16 @@ int tls_power_batch(tls_ctx *ctx, const double *t, const double *y, const double
 /* (ABI 5: out_SR / out_power_raw.  With n_curves = 1 and all arrays this is the device part of the drop-in power() call:
  * search, spectra, pick, the final T0 fit's trial epochs and scaled template formed on the device, all fits of a group in one
  * launch, ONE wait per group of 32 light curves.) */
+/* developer/test entry: the post-search chain of tls_power_batch -- spectra, pick, trial epochs and scaled template, final
+ * T0 fit, first minimum, the same code -- on search results the caller supplies: chi2 / row / depth [n_curves][n_periods]
+ * and flux y [n_curves][n] of light curves on the prepared plan (tls_prepare: time stamps, periods, template and
+ * T0_fit_margin).  n_curves in [1, 1024], all in one group.  TLS_E_ARG when the row at a curve's chi2 minimum is not the
+ * first row of a template duration.  Optional (NULL: not returned): every fit's trial epochs and residuals
+ * [n_curves][n] (the first out_n_epochs[c] of a row are set), its number of trial epochs, and whether the rotation path
+ * handed it back to the general kernel (1), kept it (0), or did not run (-1). */
+int tls_debug_post_search(tls_ctx *ctx, const double *y, int64_t n_curves, const double *chi2, const int64_t *row,
+                          const double *depth, int64_t median_kernel, tls_power_summary *out_summary,
+                          double *out_epochs, double *out_residuals, int64_t *out_n_epochs, int64_t *out_handed_back);
 
 /* ---- host-only planning (no GPU needed) ------------------------------------------ */
 /* Trial cells (duration x T0 positions) each period will enumerate: the data-independent

@@ -289,3 +289,38 @@ def test_pink_noise_dispatch_keeps_small_inputs_on_the_host():
     transit_times = [5.0, 15.0, 25.0]
     snr, snr_pink = stats.snr_stats(t, y, 10.0, 0.01, 5.0, transit_times, 0.3, numpy.array([14, 15, 14]), pink_noise_fn=fn)
     assert calls and calls[0][1] == 14 and len(snr) == len(snr_pink) == 3
+
+
+def test_batch_inputs_reject_what_cleaning_would_drop_from_any_curve():
+    """survey._batch_inputs: the first curve goes through validate.py; every other curve is checked the way cleaned_array
+    would clean it (a NaN, infinite or non-positive flux or dy), the error names the curve, a clean batch passes unchanged."""
+    from tls_amd.survey import _batch_inputs
+    t = numpy.linspace(1.0, 11.0, 300)
+    rng = numpy.random.RandomState(3)
+    flux = 1 + rng.normal(0, 1e-3, (9, len(t)))
+    dy = rng.uniform(0.5, 1.5, flux.shape) * 1e-3
+    kw = dict(period_min=1.0, period_max=3.0, oversampling_factor=1)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        inp, y_rows, dy_rows = _batch_inputs(t, flux, None, kw)
+        numpy.testing.assert_array_equal(y_rows, flux)
+        numpy.testing.assert_array_equal(dy_rows[7], numpy.std(flux[7]))
+        inp, y_rows, dy_rows = _batch_inputs(t, flux, dy, kw)
+        numpy.testing.assert_array_equal(dy_rows[7], dy[7] / numpy.mean(dy[7]))
+        for bad in (numpy.nan, numpy.inf, -numpy.inf, 0.0, -1e-3):
+            f = flux.copy()
+            f[7, 123] = bad
+            for d in (None, dy):
+                with pytest.raises(ValueError, match="light curve 7"):
+                    _batch_inputs(t, f, d, kw)
+            d = dy.copy()
+            d[7, 5] = bad
+            with pytest.raises(ValueError, match="light curve 7"):
+                _batch_inputs(t, flux, d, kw)
+        with pytest.raises(ValueError, match="light curve 2"):
+            _batch_inputs(t, flux, [dy[0], dy[1], dy[2][:-1]] + list(dy[3:]), kw)
+        # (curve 0 is cleaned by validate.py: a dropped point no longer matches the shared time stamps)
+        f = flux.copy()
+        f[0, 9] = numpy.nan
+        with pytest.raises(ValueError, match="cleaned"):
+            _batch_inputs(t, f, None, kw)

@@ -24,6 +24,7 @@ SYMBOLS = (
     "tls_device_count", "tls_ctx_create", "tls_ctx_destroy", "tls_last_error", "tls_version", "tls_abi_version",
     "tls_device_name", "tls_get_options", "tls_set_options", "tls_debug_set_switch", "tls_debug_get_switches", "tls_search", "tls_search_batch", "tls_power_batch", "tls_prepare", "tls_update_flux", "tls_execute",
     "tls_synchronize", "tls_fetch", "tls_execute_timed", "tls_plan_info", "tls_last_kernel", "tls_grid_cells", "tls_period_costs", "tls_t0_fit", "tls_pink_noise", "tls_spectra", "tls_kernel_timing", "tls_debug_phase_cycles", "tls_debug_cumsum", "tls_debug_folded", "tls_debug_prefix", "tls_debug_check_counts", "tls_debug_poison_lds", "tls_debug_period_cycles", "tls_debug_batch_group_ms",
+    "tls_debug_post_search", "tls_debug_device_bytes",
     "tls_comm_unique_id", "tls_comm_init", "tls_comm_destroy", "tls_comm_info", "tls_comm_allgather_results", "tls_comm_allgather_device", "tls_comm_fetch_gathered",
     "tls_comm_stage_results", "tls_comm_allgather_staged", "tls_comm_fetch_staged",
     "tls_comm_barrier", "tls_comm_max",
@@ -174,6 +175,11 @@ def load():
     lib.tls_debug_period_cycles.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), i64]
     lib.tls_debug_batch_group_ms.restype = ci
     lib.tls_debug_batch_group_ms.argtypes = [vp, _c_double_p, i64]
+    lib.tls_debug_post_search.restype = ci
+    lib.tls_debug_post_search.argtypes = [vp, _c_double_p, i64, _c_double_p, _c_int64_p, _c_double_p, i64, ctypes.c_void_p,
+                                          _c_double_p, _c_double_p, _c_int64_p, _c_int64_p]
+    lib.tls_debug_device_bytes.restype = ci
+    lib.tls_debug_device_bytes.argtypes = [vp, _c_int64_p, _c_int64_p]
     lib.tls_debug_cumsum.restype = ci
     lib.tls_debug_cumsum.argtypes = [vp, _c_double_p, i64, _c_double_p, ci]
     lib.tls_grid_cells.restype = ci
@@ -452,6 +458,36 @@ class Context(object):
         out = numpy.empty(len(v) + 1, dtype=numpy.float64)
         self._check(self._lib.tls_debug_cumsum(self._h, _dp(v), len(v), _dp(out), int(threads)))
         return out
+
+    def debug_post_search(self, y_batch, chi2, row, depth, median_kernel, with_fits=False):
+        """Developer/test entry: tls_power_batch's post-search chain (spectra, pick, final T0 fit) on the prepared plan (prepare())
+        with injected search results chi2 / row / depth [n_curves, n_periods] and flux y_batch [n_curves, n]; the summaries.
+        with_fits: also (epochs, residuals) -- lists of every fit's trial epochs and residuals -- and handed_back [n_curves]
+        (1: the rotation path handed the fit to the general kernel, 0: it did not, -1: it did not run)."""
+        y_batch = numpy.ascontiguousarray(y_batch, dtype=numpy.float64)
+        chi2 = numpy.ascontiguousarray(chi2, dtype=numpy.float64)
+        row = numpy.ascontiguousarray(row, dtype=numpy.int64)
+        depth = numpy.ascontiguousarray(depth, dtype=numpy.float64)
+        if y_batch.ndim != 2 or chi2.ndim != 2 or chi2.shape != row.shape or chi2.shape != depth.shape \
+                or len(chi2) != len(y_batch) or chi2.shape[1] != self._n_periods:
+            raise ValueError("chi2, row, depth must have shape [n_curves, n_periods] of the prepared plan, y_batch [n_curves, n]")
+        summary = numpy.zeros(len(chi2), dtype=POWER_SUMMARY_DTYPE)
+        n_c = len(chi2)
+        ep, res = numpy.empty(y_batch.shape), numpy.empty(y_batch.shape)
+        n_ep, back = numpy.empty(n_c, dtype=numpy.int64), numpy.empty(n_c, dtype=numpy.int64)
+        self._invalidate_results()
+        self._check(self._lib.tls_debug_post_search(self._h, _dp(y_batch), n_c, _dp(chi2), _ip(row), _dp(depth),
+                                                    int(median_kernel), summary.ctypes.data_as(ctypes.c_void_p),
+                                                    *((_dp(ep), _dp(res), _ip(n_ep), _ip(back)) if with_fits else (None,) * 4)))
+        if with_fits:
+            return summary, [ep[c, :n_ep[c]] for c in range(n_c)], [res[c, :n_ep[c]] for c in range(n_c)], back
+        return summary
+
+    def device_bytes(self):
+        """(total, t0_fit_scratch): bytes of device memory the context holds, in all and as the final T0 fit's HBM scratch."""
+        total, scratch = ctypes.c_int64(0), ctypes.c_int64(0)
+        self._check(self._lib.tls_debug_device_bytes(self._h, ctypes.byref(total), ctypes.byref(scratch)))
+        return int(total.value), int(scratch.value)
 
     def folded(self, n_periods, n):
         """Developer/test entry: the folded flux of every period of the prepared plan, (n_periods, n), as the

@@ -973,11 +973,13 @@ int enqueue(tls_ctx* ctx, bool count_work, bool phase_clock = false, double* deb
 }
 
 // T0-fit launch shared by tls_t0_fit and tls_power_batch: every pointer on the device, nothing waited for.
-// One fit (d_params == nullptr: period, dur, roll, n_epochs from the host) or `n_fits` fits in ONE launch (blockIdx.y = fit;
-// their parameters, epochs and signals written on the device by tls_power_prep, the arrays `*_stride` doubles apart).
+// One fit (d_params == nullptr: period, dur, roll, n_epochs from the host) or `n_fits` fits in ONE launch (their parameters,
+// epochs and signals written on the device by tls_power_prep, the arrays `*_stride` doubles apart).
 // Three launches (round 6): the base order of every fit (one workgroup a fit), the epochs as rotations of it (one wavefront
 // an epoch: tls_t0fit_rot), and the general kernel for the fits the rotation path handed back (ties, gaps the folds' rounding
-// could close: its workgroups leave at once otherwise).  Switch t0_rot = 0: the general kernel alone.
+// could close: its workgroups pass over the other fits).  Switch t0_rot = 0: the general kernel alone.  The general kernel's
+// `blocks` workgroups go through the fits one after the other: HBM scratch (series that do not fit the LDS) is one slab per
+// workgroup, max(blocks, n_fits) slabs in all (mode 1 has one workgroup per fit), whatever the number of fits.
 int launch_t0_fit(tls_ctx* ctx, const double* d_t, const double* d_y, const double* d_signal, const double* d_epochs,
                   double* d_residuals, unsigned int* d_queue, int64_t n, double period, int64_t dur, int64_t n_epochs,
                   int64_t roll, double t_lo, double t_hi, const tlsdev::T0FitParams* d_params = nullptr, int64_t n_fits = 1,
@@ -987,13 +989,14 @@ int launch_t0_fit(tls_ctx* ctx, const double* d_t, const double* d_y, const doub
     a.residuals = d_residuals; a.queue = d_queue; a.scratch = nullptr; a.scratch_stride = 0;
     a.period = period; a.n = (int)n; a.dur = (int)dur; a.roll = (int)(roll % n); a.n_epochs = (int)n_epochs;
     a.params = d_params; a.y_stride = y_stride; a.signal_stride = signal_stride; a.epoch_stride = epoch_stride;
+    a.n_fits = d_params ? (int)n_fits : 1;
     a.mode = 0; a.rot = nullptr; a.rot_perm = nullptr; a.rot_stride = 0; a.t_lo = t_lo; a.t_hi = t_hi;
     const size_t hdr = 272;
     const size_t resident_bytes = hdr + 16 * (size_t)n;
     const bool resident = resident_bytes <= kLdsPerCU && n <= 65535;
     size_t lds; int threads, blocks;
     // (a batched launch does not know its fits' epoch counts on the host: every fit gets the full set of workgroups, those
-    // beyond its epochs leave at once)
+    // beyond its epochs pass it over)
     const int64_t epochs_cap = d_params ? n : n_epochs;
     if (resident) {
         a.nb = (int)n; lds = resident_bytes;
@@ -1005,7 +1008,7 @@ int launch_t0_fit(tls_ctx* ctx, const double* d_t, const double* d_y, const doub
         a.nb = (int)std::min<int64_t>(n, 16384); lds = hdr + 4 * (size_t)a.nb;
         threads = 512; blocks = (int)std::min<int64_t>(epochs_cap, (int64_t)2 * ctx->n_cu);
         a.scratch_stride = 3 * n;
-        TLS_HIP(ctx, ctx->d_fscratch.reserve((size_t)blocks * (size_t)n_fits * (size_t)a.scratch_stride));
+        TLS_HIP(ctx, ctx->d_fscratch.reserve((size_t)std::max<int64_t>(blocks, n_fits) * (size_t)a.scratch_stride));
         a.scratch = ctx->d_fscratch.ptr;
     }
     if (blocks < 1) return TLS_OK;
@@ -1020,7 +1023,7 @@ int launch_t0_fit(tls_ctx* ctx, const double* d_t, const double* d_y, const doub
     auto launch = [&](int mode, unsigned grid_x) -> hipError_t {
         tlsdev::T0FitArgs b = a;
         b.mode = mode;
-        const dim3 grid(grid_x, fits);
+        const dim3 grid(grid_x, mode == 1 ? fits : 1u);
         hipError_t e;
         if (resident) {
             auto kernel = tlsdev::tls_t0fit_kernel<true, unsigned short>;
@@ -1047,6 +1050,97 @@ int launch_t0_fit(tls_ctx* ctx, const double* d_t, const double* d_y, const doub
         e = launch(0, (unsigned)blocks);
     }
     if (e != hipSuccess) return fail(ctx, TLS_E_HIP, std::string("t0 fit launch: ") + hipGetErrorString(e));
+    return TLS_OK;
+}
+
+// ---- the post-search chain of survey-mode power() (tls_power_batch; tls_debug_post_search feeds it injected search results):
+// spectra (stats.py:105-132), the pick of main.py:198-212,269-272, trial epochs and scaled template (tls_power_prep), the
+// final T0 fit of every curve in one set of launches (stats.py:135-204) and its first minimum, nothing waited for
+struct PostSearchBufs {
+    size_t spec_stride = 0, fit_stride = 0;   // SR | power_raw | power of one curve; epochs / residuals of one fit
+    int64_t max_len = 1;                       // longest template row: the stride of the scaled signals
+    double *sde = nullptr, *pick = nullptr, *T0 = nullptr;   // [group][2] | [group][8] | [group], side by side (ONE copy out)
+    int* n_epochs = nullptr;
+    tlsdev::T0FitParams* fit = nullptr;
+};
+
+int reserve_post_search(tls_ctx* ctx, int64_t group, int64_t n_periods, int64_t n, int64_t max_len, PostSearchBufs& b) {
+    const size_t np = (size_t)n_periods, g = (size_t)group;
+    b.max_len = std::max<int64_t>(max_len, 1);
+    b.spec_stride = 3 * np;
+    TLS_HIP(ctx, ctx->d_spec.reserve(g * b.spec_stride + 2 * g + 8 * g + g));
+    b.sde = ctx->d_spec.ptr + g * b.spec_stride;
+    b.pick = b.sde + 2 * g;
+    b.T0 = b.pick + 8 * g;
+    b.fit_stride = (size_t)n;
+    TLS_HIP(ctx, ctx->d_fep.reserve(g * b.fit_stride));
+    TLS_HIP(ctx, ctx->d_fres.reserve(g * b.fit_stride));
+    // signals | n_epochs (ints) | fit parameters (T0FitParams, 24 B each)
+    TLS_HIP(ctx, ctx->d_fsig.reserve(g * (size_t)b.max_len + g + 3 * g));
+    b.n_epochs = reinterpret_cast<int*>(ctx->d_fsig.ptr + g * (size_t)b.max_len);
+    b.fit = reinterpret_cast<tlsdev::T0FitParams*>(ctx->d_fsig.ptr + g * (size_t)b.max_len + g);
+    static_assert(sizeof(tlsdev::T0FitParams) == 24, "three doubles of device scratch per fit");
+    return TLS_OK;
+}
+
+// `gc` curves: chi2 / row / depth [gc][n_periods], flux [gc][n] on the device; the plan's time stamps, periods and template
+int enqueue_post_search(tls_ctx* ctx, const PostSearchBufs& b, int64_t gc, const double* d_chi2, const long long* d_row,
+                        const double* d_depth, const double* d_y, int64_t n, int64_t n_periods, int64_t median_kernel,
+                        double t_min, double t_max, double margin) {
+    const size_t np = (size_t)n_periods;
+    int64_t kernel = median_kernel;
+    if (kernel % 2 == 0) kernel += 1;                                   // stats.py:115-117
+    tlsdev::SpectraArgs sa;
+    sa.chi2 = d_chi2; sa.SR = ctx->d_spec.ptr; sa.power_raw = ctx->d_spec.ptr + np; sa.power = ctx->d_spec.ptr + 2 * np;
+    sa.sde = b.sde; sa.n = (int)n_periods; sa.kernel = (int)kernel; sa.detrend = n_periods > 2 * kernel ? 1 : 0;   // stats.py:118
+    sa.chi2_stride = (long long)np; sa.out_stride = (long long)b.spec_stride; sa.sde_stride = 2;
+    hipLaunchKernelGGL(tlsdev::tls_spectra_head, dim3(1, (unsigned)gc), dim3(1024), 0, ctx->stream, sa);
+    if (sa.detrend) {
+        const int n_med = (int)(n_periods - kernel + 1), per = tlsdev::kMedianWindows;
+        const size_t lds = (size_t)(2 * per + kernel) * 8;
+        hipLaunchKernelGGL(tlsdev::tls_spectra_median, dim3((unsigned)((n_med + per - 1) / per), (unsigned)gc), dim3(256), lds,
+                           ctx->stream, sa);
+        hipLaunchKernelGGL(tlsdev::tls_spectra_tail, dim3(1, (unsigned)gc), dim3(1024), 0, ctx->stream, sa);
+    }
+    tlsdev::PickArgs pa;
+    pa.chi2 = d_chi2; pa.row = d_row; pa.depth = d_depth; pa.power = ctx->d_spec.ptr + 2 * np;
+    pa.periods = ctx->d_periods.ptr; pa.out = b.pick; pa.power_stride = (long long)b.spec_stride; pa.n = (int)n_periods;
+    hipLaunchKernelGGL(tlsdev::tls_power_pick, dim3((unsigned)gc), dim3(1024), 0, ctx->stream, pa);
+    // (WITHOUT a host round trip, round 6: trial epochs, the depth-scaled template and the fit's parameters are formed on the
+    // device from the pick, all fits run in ONE set of launches, the first minimum is taken on the device)
+    tlsdev::PrepArgs pr;
+    pr.pick = b.pick; pr.widths = ctx->d_widths.ptr; pr.n_widths = ctx->n_widths; pr.q = ctx->d_q.ptr;
+    pr.signal = ctx->d_fsig.ptr; pr.signal_stride = (long long)b.max_len; pr.epochs = ctx->d_fep.ptr; pr.epoch_stride = (long long)b.fit_stride;
+    pr.params = b.fit; pr.n_epochs = b.n_epochs; pr.t_min = t_min; pr.margin = margin; pr.n = (int)n;
+    hipLaunchKernelGGL(tlsdev::tls_power_prep, dim3((unsigned)gc), dim3(256), 0, ctx->stream, pr);
+    TLS_HIP(ctx, hipGetLastError());
+    int rc = launch_t0_fit(ctx, ctx->d_t.ptr, d_y, ctx->d_fsig.ptr, ctx->d_fep.ptr, ctx->d_fres.ptr, nullptr, n, 1.0, 0, 0, 0,
+                           t_min, t_max, b.fit, gc, n, b.max_len, (int64_t)b.fit_stride);
+    if (rc) return rc;
+    tlsdev::FirstMinArgs fa;
+    fa.residuals = ctx->d_fres.ptr; fa.epochs = ctx->d_fep.ptr; fa.n_epochs = b.n_epochs;
+    fa.T0 = b.T0; fa.stride = (long long)b.fit_stride;
+    hipLaunchKernelGGL(tlsdev::tls_first_min, dim3((unsigned)gc), dim3(1024), 0, ctx->stream, fa);
+    TLS_HIP(ctx, hipGetLastError());
+    return TLS_OK;
+}
+
+// the summary of curve c from the chain's results on the host (sde | pick | T0 of `group` curves, as reserve_post_search
+// lays them out); TLS_E_ARG when tls_power_prep found no template width starting at the picked row
+int read_summary(tls_ctx* ctx, const double* h_sde, int64_t group, int64_t c, int64_t curve, tls_power_summary& os) {
+    const double* pk = h_sde + 2 * group + 8 * c;
+    const double T0 = h_sde[10 * group + c];
+    if (pk[7] != 0.0)
+        return fail(ctx, TLS_E_ARG, "template row " + std::to_string((long long)pk[5]) + " at the chi2 minimum of light curve " +
+                                    std::to_string((long long)curve) + " is not the first row of a duration");
+    const bool no_fit = pk[6] != 0.0;
+    os.chi2_min = pk[0]; os.index_best = (int64_t)pk[1]; os.index_power = (int64_t)pk[2];
+    os.best_row = (int64_t)pk[5]; os.no_fit = no_fit ? 1 : 0;
+    if (no_fit) {   // main.py:216-267: flat spectra
+        os.SDE = 0; os.SDE_raw = 0; os.period = std::nan(""); os.T0 = 0; os.depth = 1;
+    } else {
+        os.SDE_raw = h_sde[2 * c]; os.SDE = h_sde[2 * c + 1]; os.period = pk[3]; os.depth = pk[4]; os.T0 = T0;
+    }
     return TLS_OK;
 }
 
@@ -1898,6 +1992,82 @@ int tls_debug_batch_group_ms(const tls_ctx* ctx, double* out, int64_t capacity) 
     return (int)std::min<int64_t>(n, 0x7fffffff);
 }
 
+int tls_debug_post_search(tls_ctx* ctx, const double* y, int64_t n_curves, const double* chi2, const int64_t* row,
+                          const double* depth, int64_t median_kernel, tls_power_summary* out_summary, double* out_epochs,
+                          double* out_residuals, int64_t* out_n_epochs, int64_t* out_handed_back) {
+    if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
+    if (!ctx->prepared || !ctx->key.valid) return fail(ctx, TLS_E_STATE, "tls_debug_post_search before tls_prepare");
+    if (!y || !chi2 || !row || !depth || !out_summary) return fail(ctx, TLS_E_ARG, "null argument");
+    if (n_curves < 1 || n_curves > 1024) return fail(ctx, TLS_E_ARG, "n_curves out of range [1, 1024]");
+    if (median_kernel < 1 || median_kernel > 8000) return fail(ctx, TLS_E_ARG, "median kernel out of range [1, 8000]");
+    TLS_HIP(ctx, hipSetDevice(ctx->device));
+    const PlanKey& k = ctx->key;
+    const int64_t n = k.n, n_periods = k.n_periods;
+    if (n_periods < 1) return fail(ctx, TLS_E_ARG, "tls_debug_post_search needs at least one period");
+    const double t_min = *std::min_element(k.t.begin(), k.t.end()), t_max = *std::max_element(k.t.begin(), k.t.end());
+    const int64_t max_len = *std::max_element(k.length.begin(), k.length.end());
+    const size_t np = (size_t)n_periods, nn = (size_t)n, gc = (size_t)n_curves;
+    auto& sl = ctx->slot[0];
+    TLS_HIP(ctx, sl.d_y.reserve(gc * nn));
+    TLS_HIP(ctx, sl.d_chi2.reserve(gc * np));
+    TLS_HIP(ctx, sl.d_row.reserve(gc * np));
+    TLS_HIP(ctx, sl.d_depth.reserve(gc * np));
+    PostSearchBufs pb;
+    int rc = reserve_post_search(ctx, n_curves, n_periods, n, max_len, pb);
+    if (rc) return rc;
+    TLS_HIP(ctx, hipMemcpyAsync(sl.d_y.ptr, y, gc * nn * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(sl.d_chi2.ptr, chi2, gc * np * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(sl.d_row.ptr, row, gc * np * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(sl.d_depth.ptr, depth, gc * np * 8, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = enqueue_post_search(ctx, pb, n_curves, sl.d_chi2.ptr, sl.d_row.ptr, sl.d_depth.ptr, sl.d_y.ptr, n, n_periods,
+                                  median_kernel, t_min, t_max, k.params.T0_fit_margin))) {
+        (void)hipStreamSynchronize(ctx->stream);
+        return rc;
+    }
+    std::vector<double> h(11 * gc);
+    TLS_HIP(ctx, hipMemcpyAsync(h.data(), pb.sde, 11 * gc * 8, hipMemcpyDeviceToHost, ctx->stream));
+    std::vector<int> nep(gc);
+    TLS_HIP(ctx, hipMemcpyAsync(nep.data(), pb.n_epochs, gc * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    if (out_epochs) TLS_HIP(ctx, hipMemcpyAsync(out_epochs, ctx->d_fep.ptr, gc * nn * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (out_residuals) TLS_HIP(ctx, hipMemcpyAsync(out_residuals, ctx->d_fres.ptr, gc * nn * 8, hipMemcpyDeviceToHost, ctx->stream));
+    // (the rotation path's flag of every fit: state[1] behind the base order's three arrays, launch_t0_fit's layout)
+    const bool rotation = ctx->opt.t0_rot != 0 && n >= tlsdev::kT0RotMinPoints;
+    std::vector<double> flag(gc, -1.0);
+    if (out_handed_back && rotation)
+        TLS_HIP(ctx, hipMemcpy2DAsync(flag.data(), 8, ctx->d_frot.ptr + 3 * nn + 1, (3 * nn + 4) * 8, 8, gc, hipMemcpyDeviceToHost, ctx->stream));
+    TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (size_t c = 0; c < gc; ++c) {
+        if (out_n_epochs) out_n_epochs[c] = nep[c];
+        // (a fit with no trial epoch never ran: its slot of the rotation path holds nothing of it)
+        if (out_handed_back) out_handed_back[c] = !rotation ? -1 : nep[c] < 1 ? 0 : flag[c] != 0.0 ? 1 : 0;
+    }
+    ctx->executed = false;   // (the batch slot's buffers were written: as after tls_power_batch)
+    for (int64_t c = 0; c < n_curves; ++c)
+        if ((rc = read_summary(ctx, h.data(), n_curves, c, c, out_summary[c]))) return rc;
+    return TLS_OK;
+}
+
+int tls_debug_device_bytes(const tls_ctx* ctx, int64_t* total, int64_t* t0_fit_scratch) {
+    if (!ctx || !total || !t0_fit_scratch) return TLS_E_ARG;
+    size_t sum = 0;
+    auto add = [&](const auto& b) { sum += b.cap * sizeof(*b.ptr); };
+    add(ctx->d_plan); add(ctx->d_out);
+    add(ctx->d_scratch); add(ctx->d_pack); add(ctx->d_gather); add(ctx->d_scalar); add(ctx->d_stage);
+    add(ctx->d_phase); add(ctx->d_check);
+    add(ctx->d_queue); add(ctx->d_squeue); add(ctx->d_lists); add(ctx->d_perm); add(ctx->d_pqueues);
+    add(ctx->d_curve_S0); add(ctx->d_curve_w0);
+    for (const auto& sl : ctx->slot) {
+        add(sl.d_y); add(sl.d_w); add(sl.d_S0); add(sl.d_w0); add(sl.d_chi2); add(sl.d_depth); add(sl.d_row);
+    }
+    add(ctx->d_ft); add(ctx->d_fy); add(ctx->d_fsig); add(ctx->d_fep); add(ctx->d_fres); add(ctx->d_fscratch);
+    add(ctx->d_pink); add(ctx->d_frot); add(ctx->d_frperm); add(ctx->d_spec);
+    add(ctx->d_partials); add(ctx->d_tiles_done);
+    add(ctx->d_split); add(ctx->d_park); add(ctx->d_band);
+    *total = (int64_t)sum;
+    *t0_fit_scratch = (int64_t)(ctx->d_fscratch.cap * sizeof(double));
+    return TLS_OK;
+}
+
 int tls_debug_check_counts(tls_ctx* ctx, uint64_t* counts, int n) {
     if (!ctx || !counts || n < 1) return fail(ctx, TLS_E_ARG, "bad argument");
     for (int i = 0; i < n; ++i) counts[i] = 0;
@@ -2190,16 +2360,11 @@ static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, cons
         return fail(ctx, TLS_E_ARG, "out_chi2, out_row and out_depth go together (all or none)");
     int rc = tls_prepare(ctx, t, y, dy, n, periods, n_periods, tmpl, params);   // the plan, from the first curve
     if (rc) return rc;
-    int64_t kernel = median_kernel;
-    if (kernel % 2 == 0) kernel += 1;                                   // stats.py:115-117
     const int64_t group = std::min<int64_t>(32, n_curves);              // (one light curve: the drop-in power() call)
     const size_t np = (size_t)n_periods, nn = (size_t)n;
     const bool uni = ctx->uniform_w;
-    const int detrend = n_periods > 2 * kernel ? 1 : 0;
     double t_min = t[0], t_max = t[0];
     for (int64_t i = 1; i < n; ++i) { t_min = std::min(t_min, t[i]); t_max = std::max(t_max, t[i]); }
-    int64_t max_len = 1;
-    for (int64_t r = 0; r < tmpl->n_rows; ++r) max_len = std::max(max_len, tmpl->length[r]);
     // device buffers of one group: flux (weights), per-curve constants, search results, spectra, summaries, T0-fit inputs
     auto& sl = ctx->slot[0];
     TLS_HIP(ctx, sl.d_y.reserve((size_t)group * nn));
@@ -2210,19 +2375,11 @@ static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, cons
     TLS_HIP(ctx, sl.d_row.reserve((size_t)group * np));
     TLS_HIP(ctx, sl.d_depth.reserve((size_t)group * np));
     TLS_HIP(ctx, ctx->d_perm.reserve((size_t)std::max(ctx->blocks, ctx->slim_blocks) * nn));
-    const size_t spec_stride = 3 * np;                                  // SR | power_raw | power of one curve
-    TLS_HIP(ctx, ctx->d_spec.reserve((size_t)group * spec_stride + 2 * (size_t)group + 8 * (size_t)group + (size_t)group));
-    double* d_sde = ctx->d_spec.ptr + (size_t)group * spec_stride;      // [group][2]
-    double* d_pick = d_sde + 2 * (size_t)group;                         // [group][8]
-    double* d_T0 = d_pick + 8 * (size_t)group;                          // [group]
-    const size_t fit_stride = nn;                                       // epochs / residuals of one curve (<= n each)
-    TLS_HIP(ctx, ctx->d_fep.reserve((size_t)group * fit_stride));
-    TLS_HIP(ctx, ctx->d_fres.reserve((size_t)group * fit_stride));
-    // signals | n_epochs (ints) | fit parameters (T0FitParams, 24 B each)
-    TLS_HIP(ctx, ctx->d_fsig.reserve((size_t)group * (size_t)max_len + (size_t)group + 3 * (size_t)group));
-    int* d_nep = reinterpret_cast<int*>(ctx->d_fsig.ptr + (size_t)group * (size_t)max_len);
-    tlsdev::T0FitParams* d_fit = reinterpret_cast<tlsdev::T0FitParams*>(ctx->d_fsig.ptr + (size_t)group * (size_t)max_len + (size_t)group);
-    static_assert(sizeof(tlsdev::T0FitParams) == 24, "three doubles of device scratch per fit");
+    int64_t max_len = 1;
+    for (int64_t r = 0; r < tmpl->n_rows; ++r) max_len = std::max(max_len, tmpl->length[r]);
+    PostSearchBufs pb;
+    if ((rc = reserve_post_search(ctx, group, n_periods, n, max_len, pb))) return rc;
+    const size_t spec_stride = pb.spec_stride;
     // pinned staging: flux in; summaries, T0 and (on request) the per-period arrays out.  TWO sets (the device buffers are
     // one: the stream runs the groups in order): while the device works on group g the host forms group g + 1 in the other
     // set and enqueues it, THEN waits for g -- the device never waits for the host between two groups (round 6)
@@ -2328,43 +2485,13 @@ static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, cons
         ctx->over_y = ctx->over_w = ctx->over_S0 = ctx->over_w0 = nullptr;
         ctx->over_chi2 = nullptr; ctx->over_row = nullptr; ctx->over_depth = nullptr;
         if (rc2) return rc2;
-        // ---- spectra of every curve of the group (stats.py:105-132), then what main.py:198-212,269-272 read off them
-        tlsdev::SpectraArgs sa;
-        sa.chi2 = sl.d_chi2.ptr; sa.SR = ctx->d_spec.ptr; sa.power_raw = ctx->d_spec.ptr + np; sa.power = ctx->d_spec.ptr + 2 * np;
-        sa.sde = d_sde; sa.n = (int)n_periods; sa.kernel = (int)kernel; sa.detrend = detrend;
-        sa.chi2_stride = (long long)np; sa.out_stride = (long long)spec_stride; sa.sde_stride = 2;
-        hipLaunchKernelGGL(tlsdev::tls_spectra_head, dim3(1, (unsigned)gc), dim3(1024), 0, ctx->stream, sa);
-        if (detrend) {
-            const int n_med = (int)(n_periods - kernel + 1), per = tlsdev::kMedianWindows;
-            const size_t lds = (size_t)(2 * per + kernel) * 8;
-            hipLaunchKernelGGL(tlsdev::tls_spectra_median, dim3((unsigned)((n_med + per - 1) / per), (unsigned)gc), dim3(256), lds,
-                               ctx->stream, sa);
-            hipLaunchKernelGGL(tlsdev::tls_spectra_tail, dim3(1, (unsigned)gc), dim3(1024), 0, ctx->stream, sa);
-        }
-        tlsdev::PickArgs pa;
-        pa.chi2 = sl.d_chi2.ptr; pa.row = sl.d_row.ptr; pa.depth = sl.d_depth.ptr; pa.power = ctx->d_spec.ptr + 2 * np;
-        pa.periods = ctx->d_periods.ptr; pa.out = d_pick; pa.power_stride = (long long)spec_stride; pa.n = (int)n_periods;
-        hipLaunchKernelGGL(tlsdev::tls_power_pick, dim3((unsigned)gc), dim3(1024), 0, ctx->stream, pa);
-        // ---- final T0 fit of every curve (stats.py:135-204), WITHOUT a host round trip (round 6): trial epochs, the depth-scaled
-        // template and the fit's parameters are formed on the device from the pick (tls_power_prep), all fits of the group run
-        // in ONE set of launches (blockIdx.y = light curve), the first minimum is taken on the device
-        tlsdev::PrepArgs pr;
-        pr.pick = d_pick; pr.widths = ctx->d_widths.ptr; pr.n_widths = ctx->n_widths; pr.q = ctx->d_q.ptr;
-        pr.signal = ctx->d_fsig.ptr; pr.signal_stride = (long long)max_len; pr.epochs = ctx->d_fep.ptr; pr.epoch_stride = (long long)fit_stride;
-        pr.params = d_fit; pr.n_epochs = d_nep; pr.t_min = t_min; pr.margin = params->T0_fit_margin; pr.n = (int)n;
-        hipLaunchKernelGGL(tlsdev::tls_power_prep, dim3((unsigned)gc), dim3(256), 0, ctx->stream, pr);
-        TLS_HIP(ctx, hipGetLastError());
-        rc2 = launch_t0_fit(ctx, ctx->d_t.ptr, sl.d_y.ptr, ctx->d_fsig.ptr, ctx->d_fep.ptr, ctx->d_fres.ptr, nullptr, n, 1.0, 0, 0, 0,
-                            t_min, t_max, d_fit, gc, (int64_t)nn, max_len, (int64_t)fit_stride);
+        // ---- spectra, pick and final T0 fit of every curve of the group
+        rc2 = enqueue_post_search(ctx, pb, gc, sl.d_chi2.ptr, sl.d_row.ptr, sl.d_depth.ptr, sl.d_y.ptr, n, n_periods, median_kernel,
+                                  t_min, t_max, params->T0_fit_margin);
         if (rc2) return rc2;
-        tlsdev::FirstMinArgs fa;
-        fa.residuals = ctx->d_fres.ptr; fa.epochs = ctx->d_fep.ptr; fa.n_epochs = d_nep;
-        fa.T0 = d_T0; fa.stride = (long long)fit_stride;
-        hipLaunchKernelGGL(tlsdev::tls_first_min, dim3((unsigned)gc), dim3(1024), 0, ctx->stream, fa);
-        TLS_HIP(ctx, hipGetLastError());
         // (sde | pick | T0 lie side by side behind the spectra on the device: ONE copy, the host keeps the layout)
         const OutLayout o = out_layout(g);
-        TLS_HIP(ctx, hipMemcpyAsync(o.sde, d_sde, 11 * (size_t)group * 8, hipMemcpyDeviceToHost, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(o.sde, pb.sde, 11 * (size_t)group * 8, hipMemcpyDeviceToHost, ctx->stream));
         if (out_chi2) {
             TLS_HIP(ctx, hipMemcpyAsync(o.chi2, sl.d_chi2.ptr, (size_t)gc * np * 8, hipMemcpyDeviceToHost, ctx->stream));
             TLS_HIP(ctx, hipMemcpyAsync(o.chi2 + (size_t)group * np, sl.d_row.ptr, (size_t)gc * np * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -2407,16 +2534,8 @@ static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, cons
         }
         const OutLayout o = out_layout(g);
         for (int64_t c = 0; c < gc; ++c) {
-            const double* pk = o.pick + 8 * c;
-            tls_power_summary& os = out_summary[c0 + c];
-            const bool no_fit = pk[6] != 0.0;
-            os.chi2_min = pk[0]; os.index_best = (int64_t)pk[1]; os.index_power = (int64_t)pk[2];
-            os.best_row = (int64_t)pk[5]; os.no_fit = no_fit ? 1 : 0;
-            if (no_fit) {   // main.py:216-267: flat spectra
-                os.SDE = 0; os.SDE_raw = 0; os.period = std::nan(""); os.T0 = 0; os.depth = 1;
-            } else {
-                os.SDE_raw = o.sde[2 * c]; os.SDE = o.sde[2 * c + 1]; os.period = pk[3]; os.depth = pk[4]; os.T0 = o.T0[c];
-            }
+            const int rc2 = read_summary(ctx, o.sde, group, c, c0 + c, out_summary[c0 + c]);
+            if (rc2) return rc2;
         }
         if (out_chi2) {
             std::memcpy(out_chi2 + c0 * n_periods, o.chi2, (size_t)gc * np * 8);

@@ -3107,7 +3107,8 @@ struct T0FitArgs {
     long long scratch_stride;
     double period;
     int n, dur, roll, n_epochs, nb;
-    // survey batches / the fused power() chain: fit c = blockIdx.y takes period, dur, roll and n_epochs from params[c] (written
+    int n_fits;             // fits of the launch (1 without params)
+    // survey batches / the fused power() chain: fit c takes period, dur, roll and n_epochs from params[c] (written
     // on the device by tls_power_prep: no host round trip between the search and the fit) and its arrays at y + c * y_stride,
     // signal + c * signal_stride, epochs / residuals + c * epoch_stride.  nullptr: one fit, the scalars above.
     const struct T0FitParams* params;
@@ -3126,18 +3127,19 @@ struct T0FitArgs {
 struct T0FitParams { double period; int dur, roll, n_epochs, pad_; };
 constexpr int kT0RotMinPoints = 16;   // (the rotation path looks at eight neighbours of the wrap)
 
+// Fit c of a launch: this workgroup's share of its epochs (every gridDim.x-th one from blockIdx.x).  What skips the fit is
+// uniform for the workgroup.
 template <bool RESIDENT, typename IdxT>
-__global__ void __launch_bounds__(1024) tls_t0fit_kernel(const T0FitArgs a0) {
+__device__ __forceinline__ void t0fit_one(const T0FitArgs& a0, long long c) {
     T0FitArgs a = a0;
     if (a0.params != nullptr) {
-        const long long c = blockIdx.y;
         const T0FitParams fp = a0.params[c];
         a.period = fp.period; a.dur = fp.dur; a.roll = fp.roll; a.n_epochs = fp.n_epochs;
         a.y = a0.y + c * a0.y_stride; a.signal = a0.signal + c * a0.signal_stride;
         a.epochs = a0.epochs + c * a0.epoch_stride; a.residuals = a0.residuals + c * a0.epoch_stride;
-        if ((int)blockIdx.x >= a.n_epochs) return;   // (uniform for the workgroup)
+        if ((int)blockIdx.x >= a.n_epochs) return;
     }
-    double* const rot_fit = a.rot ? a.rot + (long long)blockIdx.y * a.rot_stride : nullptr;
+    double* const rot_fit = a.rot ? a.rot + c * a.rot_stride : nullptr;
     if (a.mode == 2 && rot_fit[3LL * a.n + 1] == 0.0) return;   // (the rotation path has done this fit)
     if (a.mode == 1) a.n_epochs = a.n_epochs > 0 ? 1 : 0;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -3156,7 +3158,7 @@ __global__ void __launch_bounds__(1024) tls_t0fit_kernel(const T0FitArgs a0) {
         regB = regA + n;                                 // sort scratch
         cnt = reinterpret_cast<unsigned int*>(regB);
     } else {
-        regA = a.scratch + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * a.scratch_stride;
+        regA = a.scratch + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * a.scratch_stride;   // (one of the two is 1)
         regB = regA + n;
         cnt = reinterpret_cast<unsigned int*>(smem + kHdr);
     }
@@ -3250,7 +3252,7 @@ __global__ void __launch_bounds__(1024) tls_t0fit_kernel(const T0FitArgs a0) {
             // quotients; the smallest gap between neighbouring phases around the cycle (a gap the folds' rounding could close
             // under another epoch, or a tie, sends the fit through every epoch's own check: mode 2)
             double* Fb = rot_fit; double* phb = Fb + n; double* cq = phb + n; double* state = cq + n;
-            int* order = a.rot_perm + (long long)blockIdx.y * n;
+            int* order = a.rot_perm + c * n;
             const int r1 = a.roll % n;
             double c_sum = 0.0, gap_min = INFINITY;
             for (int k = tid; k < n; k += nt) {
@@ -3307,6 +3309,29 @@ __global__ void __launch_bounds__(1024) tls_t0fit_kernel(const T0FitArgs a0) {
             a.residuals[work] = tot;
         }
         wg_sync();
+    }
+}
+
+// Mode 1: grid (1, n_fits), fit c = blockIdx.y.  Otherwise grid (blocks, 1): EVERY workgroup takes its share of every fit's
+// epochs, one fit after the other -- a workgroup needs one slab of HBM scratch however many fits the launch has, and a lone
+// fit the rotation path hands back still gets every workgroup.
+// (Which fits have work for this workgroup is read 64 fits at a time, one per lane: a mode-2 launch with no fit handed back
+// costs each workgroup one load per lane, not one dependent load per fit.)
+template <bool RESIDENT, typename IdxT>
+__global__ void __launch_bounds__(1024) tls_t0fit_kernel(const T0FitArgs a) {
+    if (a.mode == 1) { t0fit_one<RESIDENT, IdxT>(a, blockIdx.y); return; }
+    const int lane = threadIdx.x & (kWave - 1);
+    for (int c0 = 0; c0 < a.n_fits; c0 += kWave) {
+        const int c = c0 + lane;
+        bool todo = c < a.n_fits;
+        if (todo && a.params != nullptr) todo = (int)blockIdx.x < a.params[c].n_epochs;
+        if (todo && a.mode == 2) todo = a.rot[c * a.rot_stride + 3LL * a.n + 1] != 0.0;
+        unsigned long long m = ballot64(todo);   // (the same in every wave: the same words)
+        while (m) {
+            const int k = __builtin_ctzll(m);
+            m &= m - 1;
+            t0fit_one<RESIDENT, IdxT>(a, c0 + k);
+        }
     }
 }
 
@@ -3519,7 +3544,8 @@ __global__ void __launch_bounds__(1024) tls_spectra_tail(const SpectraArgs a0) {
 // Survey-mode power(): what main.py:198-212,269-272 read off the spectra of one light curve -- one workgroup per
 // light curve (blockIdx.x).  out[c][0..7] = chi2_min, index of the FIRST minimum of chi2 (numpy.argmin), index of the
 // FIRST maximum of the detrended power (numpy.argmax), period and depth at the power peak, template row at the chi2
-// minimum, max(chi2) == min(chi2) ("no transit was fit", main.py:203), reserved.
+// minimum, max(chi2) == min(chi2) ("no transit was fit", main.py:203), 0 (tls_power_prep sets it to 1 when the row is not
+// the first row of any template width: the host reports an error).
 struct PickArgs {
     const double* chi2; const long long* row; const double* depth;   // [n_curves][n] (stride n)
     const double* power;                                             // [n_curves] stride power_stride
@@ -3619,7 +3645,7 @@ __global__ void __launch_bounds__(1024) tls_first_min(const FirstMinArgs a) {
 // start, two roundings, the end point set exactly) and the template scaled to the fitted depth, 1 - (1 - signal) / (SIGNAL_DEPTH
 // / (1 - depth)).  One workgroup per light curve.  No host round trip: the fit is enqueued right behind.
 struct PrepArgs {
-    const double* pick;             // [n_curves][8] (tls_power_pick)
+    double* pick;                   // [n_curves][8] (tls_power_pick; [7] raised here on an unknown row)
     const WidthEntry* widths; int n_widths;
     const double* q;                // 1 - template rows, the plan's layout
     double* signal; long long signal_stride;
@@ -3636,10 +3662,12 @@ __global__ void __launch_bounds__(256) tls_power_prep(const PrepArgs a) {
     const long long c = blockIdx.x;
     const double* pk = a.pick + 8 * c;
     if (tid == 0) {
-        int points = 0, k_row = 0;
+        int points = 0, k_row = -1;
         if (pk[6] == 0.0) {   // a transit was fit (main.py:203-216 otherwise: T0 = 0)
-            const int best_row = (int)pk[5];
-            for (int k = 0; k < a.n_widths; ++k) if (a.widths[k].row == best_row) { k_row = k; break; }   // (reported rows are the first row of their width)
+            const double best_row = pk[5];
+            for (int k = 0; k < a.n_widths; ++k) if ((double)a.widths[k].row == best_row) { k_row = k; break; }   // (reported rows are the first row of their width)
+        }
+        if (k_row >= 0) {
             const int dur = a.widths[k_row].q_len;
             if (a.margin == 0) points = a.n;
             else points = (int)((double)a.n / (a.margin * (double)dur));   // stats.py:150
@@ -3653,6 +3681,7 @@ __global__ void __launch_bounds__(256) tls_power_prep(const PrepArgs a) {
             fp.period = period; fp.dur = dur; fp.roll = (dur / 2 + 1) % a.n; fp.n_epochs = points; fp.pad_ = 0;
             a.params[c] = fp;
         } else {
+            if (pk[6] == 0.0) a.pick[8 * c + 7] = 1.0;   // no width starts at this row: no fit, an error on the host
             T0FitParams fp;
             fp.period = 1.0; fp.dur = 0; fp.roll = 0; fp.n_epochs = 0; fp.pad_ = 0;
             a.params[c] = fp;

@@ -277,7 +277,9 @@ def fused_power(t, y, dy, periods, table, params, oversampling_factor, context=N
     search, SDE spectra (stats.py:105-132), the pick of main.py:198-212,269-272 and the final T0 fit (stats.py:135-204) -- trial
     epochs and scaled template formed on the device, first minimum taken on the device -- with ONE wait at the end instead of
     three (search fetch, spectra fetch, T0-fit fetch).  Returns (context, summary record, chi2, row, depth, SR, power_raw,
-    power); every value equals what search_periods + spectra + final_T0_fit return for the same light curve."""
+    power).  Against search_periods + spectra + final_T0_fit on the same light curve: the search results are equal, the
+    T0-fit residuals agree to 1e-12 relative (the rotation path of the fit sums in another order), and T0 is equal except
+    where two trial epochs' residuals lie that close (a near-tie may pick the other one)."""
     from . import constants as C
     kernel = oversampling_factor * C.SDE_MEDIAN_KERNEL_SIZE
     if kernel != int(kernel):

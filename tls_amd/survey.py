@@ -26,10 +26,15 @@ def _batch_inputs(t, flux_batch, dy_batch, power_kwargs):
     dy_rows = numpy.empty_like(flux_batch)
     dy_rows[0] = inp["dy"]
     for k in range(1, len(flux_batch)):
+        # (the first curve went through validate.py; a point cleaned_array would drop from any other is an error here)
+        if not numpy.all(numpy.isfinite(flux_batch[k]) & (flux_batch[k] > 0)):
+            raise ValueError("light curve %d has a NaN, infinite or non-positive flux: clean it before a batched search" % k)
         if dy_batch is None:
             dy_rows[k] = numpy.std(flux_batch[k])
         else:
             dy = numpy.asarray(dy_batch[k], dtype=numpy.float64)
+            if dy.shape != (len(t),) or not numpy.all(numpy.isfinite(dy) & (dy > 0)):
+                raise ValueError("dy of light curve %d is not %d finite positive values" % (k, len(t)))
             dy_rows[k] = dy / numpy.mean(dy)
     y_rows = flux_batch.copy()
     y_rows[0] = inp["y"]
