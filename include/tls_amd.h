@@ -33,8 +33,9 @@ extern "C" {
 /* Bumped whenever a struct of this header changes its layout or an entry point its signature (3: tls_counters has
  * five fields, tls_period_costs / tls_power_batch exist; 4: tls_options, tls_get_options / tls_set_options; 5: tls_options
  * keeps the two caller-facing switches, the developer switches moved behind tls_debug_set_switch, tls_period_costs takes
- * them as text).  A binding compares it with tls_abi_version(). */
-#define TLS_AMD_ABI_VERSION 5
+ * them as text; 6: tls_transit_stats, tls_power_batch_stats, tls_debug_transit_stats).  A binding compares it with
+ * tls_abi_version(). */
+#define TLS_AMD_ABI_VERSION 6
 
 #define TLS_OK 0
 #define TLS_E_ARG (-1)      /* invalid argument */
@@ -253,6 +254,39 @@ int tls_power_batch(tls_ctx *ctx, const double *t, const double *y, const double
 /* (ABI 5: out_SR / out_power_raw.  With n_curves = 1 and all arrays this is the device part of the drop-in power() call:
  * search, spectra, pick, the final T0 fit's trial epochs and scaled template formed on the device, all fits of a group in one
  * launch, ONE wait per group of 32 light curves.) */
+/* The per-transit vetting statistics of power() (api.py:175-241) for one light curve, every field the results key of the
+ * same name (the tuples split into _std fields; duration_days is results.duration, in days).  Counts are doubles: a
+ * curve without a fit carries NaN in every field but period_uncertainty, like the results object. */
+typedef struct tls_transit_stats {
+    double period_uncertainty, duration_days;
+    double depth_mean, depth_mean_std, depth_mean_even, depth_mean_even_std, depth_mean_odd, depth_mean_odd_std;
+    double snr, odd_even_mismatch;
+    double transit_count, distinct_transit_count, empty_transit_count;
+    double in_transit_count, after_transit_count, before_transit_count;
+} tls_transit_stats;
+/* tls_power_batch plus the statistics of every light curve, computed on the device behind the final T0 fit of each group
+ * and copied back with the group's summaries (still one wait per group).  row_duration: lc_cache_overview["duration"] of
+ * every template row (tmpl->n_rows entries); fill_factor: calculate_fill_factor(t); root[k] = float(k) ** 0.5 as Python
+ * forms it, k = 0 .. n_root - 1 with n_root > n.  out_per_transit (NULL: not returned): [n_curves][6][max_epochs] --
+ * transit_times, per_transit_count, transit_depths, transit_depths_uncertainties, snr_per_transit, snr_pink_per_transit --
+ * NaN past a curve's epochs; out_n_epochs (NULL: not returned): epochs of every curve (0 without a fit).  TLS_E_ARG when t
+ * is not non-decreasing, or when a curve has more than max_epochs transit epochs. */
+int tls_power_batch_stats(tls_ctx *ctx, const double *t, const double *y, const double *dy, int64_t n,
+                          int64_t n_curves, const double *periods, int64_t n_periods,
+                          const tls_template *tmpl, const tls_params *params, int64_t median_kernel,
+                          tls_power_summary *out_summary, double *out_chi2, int64_t *out_row, double *out_depth,
+                          double *out_power, double *out_SR, double *out_power_raw,
+                          const double *row_duration, double fill_factor, const double *root, int64_t n_root,
+                          tls_transit_stats *out_stats, int64_t max_epochs, double *out_per_transit,
+                          int64_t *out_n_epochs);
+/* developer/test entry: the statistics stage of tls_power_batch_stats, the same kernel, on picks the caller supplies for
+ * light curves y [n_curves][n] on the prepared plan: period, T0, best_row, depth, no_fit, index_power per curve and the
+ * detrended power [n_curves][n_periods].  n_curves in [1, 1024]; the other arguments as tls_power_batch_stats. */
+int tls_debug_transit_stats(tls_ctx *ctx, const double *y, int64_t n_curves, const double *period, const double *T0,
+                            const int64_t *best_row, const double *depth, const int64_t *no_fit, const int64_t *index_power,
+                            const double *power, const double *row_duration, int64_t n_rows, double fill_factor,
+                            const double *root, int64_t n_root, int64_t max_epochs, tls_transit_stats *out_stats,
+                            double *out_per_transit, int64_t *out_n_epochs);
 /* developer/test entry: the post-search chain of tls_power_batch -- spectra, pick, trial epochs and scaled template, final
  * T0 fit, first minimum, the same code -- on search results the caller supplies: chi2 / row / depth [n_curves][n_periods]
  * and flux y [n_curves][n] of light curves on the prepared plan (tls_prepare: time stamps, periods, template and

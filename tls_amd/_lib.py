@@ -17,14 +17,14 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtls_amd.so")
 if os.environ.get("TLS_AMD_DEBUG") == "1" and os.environ.get("TLS_AMD_LIB"):
     LIB_PATH = os.environ["TLS_AMD_LIB"]
-ABI_VERSION = 5   # include/tls_amd.h TLS_AMD_ABI_VERSION: checked against the library at load time
+ABI_VERSION = 6   # include/tls_amd.h TLS_AMD_ABI_VERSION: checked against the library at load time
 
 # every symbol include/tls_amd.h declares (tests check the export list against the header)
 SYMBOLS = (
     "tls_device_count", "tls_ctx_create", "tls_ctx_destroy", "tls_last_error", "tls_version", "tls_abi_version",
     "tls_device_name", "tls_get_options", "tls_set_options", "tls_debug_set_switch", "tls_debug_get_switches", "tls_search", "tls_search_batch", "tls_power_batch", "tls_prepare", "tls_update_flux", "tls_execute",
     "tls_synchronize", "tls_fetch", "tls_execute_timed", "tls_plan_info", "tls_last_kernel", "tls_grid_cells", "tls_period_costs", "tls_t0_fit", "tls_pink_noise", "tls_spectra", "tls_kernel_timing", "tls_debug_phase_cycles", "tls_debug_cumsum", "tls_debug_folded", "tls_debug_prefix", "tls_debug_check_counts", "tls_debug_poison_lds", "tls_debug_period_cycles", "tls_debug_batch_group_ms",
-    "tls_debug_post_search", "tls_debug_device_bytes",
+    "tls_debug_post_search", "tls_debug_device_bytes", "tls_power_batch_stats", "tls_debug_transit_stats",
     "tls_comm_unique_id", "tls_comm_init", "tls_comm_destroy", "tls_comm_info", "tls_comm_allgather_results", "tls_comm_allgather_device", "tls_comm_fetch_gathered",
     "tls_comm_stage_results", "tls_comm_allgather_staged", "tls_comm_fetch_staged",
     "tls_comm_barrier", "tls_comm_max",
@@ -76,6 +76,23 @@ class PowerSummary(ctypes.Structure):
 POWER_SUMMARY_DTYPE = numpy.dtype([("SDE", "f8"), ("SDE_raw", "f8"), ("chi2_min", "f8"), ("period", "f8"), ("T0", "f8"),
                                    ("depth", "f8"), ("index_best", "i8"), ("index_power", "i8"), ("best_row", "i8"),
                                    ("no_fit", "i8")])
+
+
+TRANSIT_STATS_FIELDS = ("period_uncertainty", "duration_days", "depth_mean", "depth_mean_std", "depth_mean_even",
+                        "depth_mean_even_std", "depth_mean_odd", "depth_mean_odd_std", "snr", "odd_even_mismatch",
+                        "transit_count", "distinct_transit_count", "empty_transit_count", "in_transit_count",
+                        "after_transit_count", "before_transit_count")
+
+
+class TransitStats(ctypes.Structure):
+    """tls_transit_stats: the per-transit vetting statistics of power() (api.py:175-241) for one light curve."""
+    _fields_ = [(k, ctypes.c_double) for k in TRANSIT_STATS_FIELDS]
+
+
+TRANSIT_STATS_DTYPE = numpy.dtype([(k, "f8") for k in TRANSIT_STATS_FIELDS])
+# rows of the per-transit output [n_curves][6][max_epochs]
+PER_TRANSIT_FIELDS = ("transit_times", "per_transit_count", "transit_depths", "transit_depths_uncertainties",
+                      "snr_per_transit", "snr_pink_per_transit")
 
 
 class Counters(ctypes.Structure):
@@ -178,6 +195,15 @@ def load():
     lib.tls_debug_post_search.restype = ci
     lib.tls_debug_post_search.argtypes = [vp, _c_double_p, i64, _c_double_p, _c_int64_p, _c_double_p, i64, ctypes.c_void_p,
                                           _c_double_p, _c_double_p, _c_int64_p, _c_int64_p]
+    lib.tls_power_batch_stats.restype = ci
+    lib.tls_power_batch_stats.argtypes = [vp, _c_double_p, _c_double_p, _c_double_p, i64, i64, _c_double_p, i64,
+                                          tp, pp, i64, ctypes.c_void_p, _c_double_p, _c_int64_p, _c_double_p, _c_double_p,
+                                          _c_double_p, _c_double_p, _c_double_p, dbl, _c_double_p, i64, ctypes.c_void_p, i64,
+                                          _c_double_p, _c_int64_p]
+    lib.tls_debug_transit_stats.restype = ci
+    lib.tls_debug_transit_stats.argtypes = [vp, _c_double_p, i64, _c_double_p, _c_double_p, _c_int64_p, _c_double_p, _c_int64_p,
+                                            _c_int64_p, _c_double_p, _c_double_p, i64, dbl, _c_double_p, i64, i64, ctypes.c_void_p,
+                                            _c_double_p, _c_int64_p]
     lib.tls_debug_device_bytes.restype = ci
     lib.tls_debug_device_bytes.argtypes = [vp, _c_int64_p, _c_int64_p]
     lib.tls_debug_cumsum.restype = ci
@@ -383,6 +409,62 @@ class Context(object):
         if with_spectra:
             return summary, chi2, row, depth, power, SR, power_raw
         return summary, chi2, row, depth, power
+
+    def power_batch_stats(self, t, y_batch, dy_batch, periods, table, params, median_kernel, fill_factor, root, max_epochs,
+                          per_transit=False, with_arrays=False):
+        """power_batch plus the per-transit statistics of every light curve (tls_power_batch_stats): (summary, stats
+        (TRANSIT_STATS_DTYPE), per_transit [n_curves, 6, max_epochs] or None, n_epochs or None, chi2, row, depth, power).
+        table.duration is the fractional duration of every template row; root[k] = float(k) ** 0.5, k = 0 .. len(t)."""
+        t, periods = _f8(t), _f8(periods)
+        y_batch = numpy.ascontiguousarray(y_batch, dtype=numpy.float64)
+        dy_batch = numpy.ascontiguousarray(dy_batch, dtype=numpy.float64)
+        if y_batch.ndim != 2 or y_batch.shape != dy_batch.shape or y_batch.shape[1] != len(t):
+            raise ValueError("y_batch and dy_batch must both have shape [n_curves, len(t)]")
+        arrays, tm, pr = self._pack(table, params)
+        row_duration, root = _f8(table.duration), _f8(root)
+        n_c, n_p, max_epochs = y_batch.shape[0], len(periods), int(max_epochs)
+        summary = numpy.zeros(n_c, dtype=POWER_SUMMARY_DTYPE)
+        stats = numpy.zeros(n_c, dtype=TRANSIT_STATS_DTYPE)
+        assert stats.dtype.itemsize == ctypes.sizeof(TransitStats)
+        rows = numpy.empty((n_c, len(PER_TRANSIT_FIELDS), max_epochs)) if per_transit else None
+        n_epochs = numpy.empty(n_c, dtype=numpy.int64) if per_transit else None
+        chi2 = row = depth = power = None
+        if with_arrays:
+            chi2, depth, power = (numpy.empty((n_c, n_p)) for _ in range(3))
+            row = numpy.empty((n_c, n_p), dtype=numpy.int64)
+        self._invalidate_results()
+        self._check(self._lib.tls_power_batch_stats(
+            self._h, _dp(t), _dp(y_batch), _dp(dy_batch), len(t), n_c, _dp(periods), n_p, ctypes.byref(tm),
+            ctypes.byref(pr), int(median_kernel), summary.ctypes.data_as(ctypes.c_void_p),
+            None if chi2 is None else _dp(chi2), None if row is None else _ip(row),
+            None if depth is None else _dp(depth), None if power is None else _dp(power), None, None,
+            _dp(row_duration), float(fill_factor), _dp(root), len(root), stats.ctypes.data_as(ctypes.c_void_p), max_epochs,
+            None if rows is None else _dp(rows), None if n_epochs is None else _ip(n_epochs)))
+        self._n_periods = n_p
+        return summary, stats, rows, n_epochs, chi2, row, depth, power
+
+    def debug_transit_stats(self, y_batch, period, T0, best_row, depth, no_fit, index_power, power, row_duration,
+                            fill_factor, root, max_epochs):
+        """Developer/test entry: the statistics kernel of power_batch_stats on the prepared plan (prepare()) with injected
+        picks -- period, T0, best_row, depth, no_fit, index_power per curve, power [n_curves, n_periods] -- and flux
+        y_batch [n_curves, n]; (stats, per_transit [n_curves, 6, max_epochs], n_epochs)."""
+        y_batch = numpy.ascontiguousarray(y_batch, dtype=numpy.float64)
+        power = numpy.ascontiguousarray(power, dtype=numpy.float64)
+        n_c = len(y_batch)
+        if y_batch.ndim != 2 or power.shape != (n_c, self._n_periods):
+            raise ValueError("power must have shape [n_curves, n_periods] of the prepared plan, y_batch [n_curves, n]")
+        period, T0, depth = (_f8(numpy.broadcast_to(v, (n_c,))) for v in (period, T0, depth))
+        best_row, no_fit, index_power = (_i8(numpy.broadcast_to(v, (n_c,))) for v in (best_row, no_fit, index_power))
+        row_duration, root, max_epochs = _f8(row_duration), _f8(root), int(max_epochs)
+        stats = numpy.zeros(n_c, dtype=TRANSIT_STATS_DTYPE)
+        rows = numpy.empty((n_c, len(PER_TRANSIT_FIELDS), max_epochs))
+        n_epochs = numpy.empty(n_c, dtype=numpy.int64)
+        self._invalidate_results()
+        self._check(self._lib.tls_debug_transit_stats(
+            self._h, _dp(y_batch), n_c, _dp(period), _dp(T0), _ip(best_row), _dp(depth), _ip(no_fit), _ip(index_power),
+            _dp(power), _dp(row_duration), len(row_duration), float(fill_factor), _dp(root), len(root), max_epochs,
+            stats.ctypes.data_as(ctypes.c_void_p), _dp(rows), _ip(n_epochs)))
+        return stats, rows, n_epochs
 
     def _invalidate_results(self):
         """Every call that launches a search, replaces its inputs or reuses the result buffers: the chi2 array an

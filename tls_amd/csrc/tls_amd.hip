@@ -229,6 +229,8 @@ struct tls_ctx {
     DevBuf<double> d_frot;          // ... its rotation path: per fit flux | phases | quotients of the base order, state
     DevBuf<int> d_frperm;           // ... and the base order itself
     DevBuf<double> d_spec;                                         // SDE spectra: SR | power_raw | power | sde[2] | chi2 copy
+    DevBuf<double> d_tstats;        // tls_power_batch_stats: row durations | root table | per-curve scratch of one group
+    DevBuf<int> d_tranges;          // ... and every epoch's chunk start | stop | offset
     size_t list_stride = 0;
     // two-kernel slab path (series in HBM, one light curve): fold kernel + search kernel per batch of periods
     bool split = false;                      // the plan supports it (enqueue uses it for single-curve launches)
@@ -1060,18 +1062,24 @@ struct PostSearchBufs {
     size_t spec_stride = 0, fit_stride = 0;   // SR | power_raw | power of one curve; epochs / residuals of one fit
     int64_t max_len = 1;                       // longest template row: the stride of the scaled signals
     double *sde = nullptr, *pick = nullptr, *T0 = nullptr;   // [group][2] | [group][8] | [group], side by side (ONE copy out)
+    double* stats = nullptr;                   // tls_power_batch_stats: [group][16] | per-transit [group][6][max_epochs], behind T0
+    int64_t group = 0;
     int* n_epochs = nullptr;
     tlsdev::T0FitParams* fit = nullptr;
 };
 
-int reserve_post_search(tls_ctx* ctx, int64_t group, int64_t n_periods, int64_t n, int64_t max_len, PostSearchBufs& b) {
+// stats_words: doubles of the statistics stage per curve behind T0 (0: no statistics requested)
+int reserve_post_search(tls_ctx* ctx, int64_t group, int64_t n_periods, int64_t n, int64_t max_len, PostSearchBufs& b,
+                        size_t stats_words = 0) {
     const size_t np = (size_t)n_periods, g = (size_t)group;
     b.max_len = std::max<int64_t>(max_len, 1);
     b.spec_stride = 3 * np;
-    TLS_HIP(ctx, ctx->d_spec.reserve(g * b.spec_stride + 2 * g + 8 * g + g));
+    b.group = group;
+    TLS_HIP(ctx, ctx->d_spec.reserve(g * b.spec_stride + 2 * g + 8 * g + g + stats_words * g));
     b.sde = ctx->d_spec.ptr + g * b.spec_stride;
     b.pick = b.sde + 2 * g;
     b.T0 = b.pick + 8 * g;
+    b.stats = stats_words ? b.T0 + g : nullptr;
     b.fit_stride = (size_t)n;
     TLS_HIP(ctx, ctx->d_fep.reserve(g * b.fit_stride));
     TLS_HIP(ctx, ctx->d_fres.reserve(g * b.fit_stride));
@@ -1122,6 +1130,78 @@ int enqueue_post_search(tls_ctx* ctx, const PostSearchBufs& b, int64_t gc, const
     fa.T0 = b.T0; fa.stride = (long long)b.fit_stride;
     hipLaunchKernelGGL(tlsdev::tls_first_min, dim3((unsigned)gc), dim3(1024), 0, ctx->stream, fa);
     TLS_HIP(ctx, hipGetLastError());
+    return TLS_OK;
+}
+
+// ---- the per-transit statistics stage (tls_power_batch_stats; tls_debug_transit_stats feeds it injected picks)
+struct StatsRequest {
+    const double* row_duration = nullptr; int64_t n_rows = 0;   // lc_cache_overview["duration"] of every template row
+    double fill_factor = 0;
+    const double* root = nullptr; int64_t n_root = 0;           // float(k) ** 0.5, k < n_root (n_root > n)
+    int64_t max_epochs = 1;
+    tls_transit_stats* out = nullptr; double* out_per_transit = nullptr; int64_t* out_n_epochs = nullptr;
+    size_t words() const { return (size_t)tlsdev::kTransitStats + (size_t)tlsdev::kPerTransitRows * (size_t)max_epochs; }
+};
+static_assert(sizeof(tls_transit_stats) == tlsdev::kTransitStats * 8, "tls_transit_stats is the kernel's record");
+
+struct StatsBufs { double *row_duration = nullptr, *root = nullptr, *scratch = nullptr; int* ranges = nullptr; size_t scratch_stride = 0; };
+
+// device inputs of a request (uploaded once per call) and the O(group x n) scratch of one group
+int reserve_transit_stats(tls_ctx* ctx, const StatsRequest& sr, int64_t group, int64_t n, StatsBufs& sb) {
+    sb.scratch_stride = 4 * (size_t)n + 1;   // flux_ootr | concat(odd, even) | pink terms | running sums
+    const size_t ins = (size_t)sr.n_rows + (size_t)sr.n_root;
+    TLS_HIP(ctx, ctx->d_tstats.reserve(ins + (size_t)group * sb.scratch_stride));
+    TLS_HIP(ctx, ctx->d_tranges.reserve((size_t)group * 3 * (size_t)sr.max_epochs));
+    sb.row_duration = ctx->d_tstats.ptr; sb.root = sb.row_duration + sr.n_rows; sb.scratch = sb.root + sr.n_root;
+    sb.ranges = ctx->d_tranges.ptr;
+    TLS_HIP(ctx, hipMemcpyAsync(sb.row_duration, sr.row_duration, (size_t)sr.n_rows * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(sb.root, sr.root, (size_t)sr.n_root * 8, hipMemcpyHostToDevice, ctx->stream));
+    return TLS_OK;
+}
+
+// the statistics of `gc` curves from the chain's pick, T0 and detrended power (enqueue_post_search), nothing waited for
+int enqueue_transit_stats(tls_ctx* ctx, const PostSearchBufs& b, const StatsBufs& sb, const StatsRequest& sr, int64_t gc,
+                          const double* d_y, int64_t n, int64_t n_periods, double t_min, double t_max) {
+    tlsdev::TransitStatsArgs a;
+    a.t = ctx->d_t.ptr; a.y = d_y; a.pick = b.pick; a.T0 = b.T0;
+    a.power = ctx->d_spec.ptr + 2 * (size_t)n_periods; a.power_stride = (long long)b.spec_stride;
+    a.periods = ctx->d_periods.ptr; a.n_periods = (int)n_periods;
+    a.row_duration = sb.row_duration; a.root = sb.root; a.n_root = (int)sr.n_root;
+    a.fill_factor = sr.fill_factor; a.t_min = t_min; a.t_max = t_max;
+    a.stats = b.stats; a.per_transit = b.stats + (size_t)tlsdev::kTransitStats * (size_t)b.group;
+    a.ranges = sb.ranges; a.scratch = sb.scratch; a.scratch_stride = (long long)sb.scratch_stride;
+    a.n = (int)n; a.max_epochs = (int)sr.max_epochs;
+    hipLaunchKernelGGL(tlsdev::tls_transit_stats, dim3((unsigned)gc), dim3(256), 0, ctx->stream, a);
+    TLS_HIP(ctx, hipGetLastError());
+    return TLS_OK;
+}
+
+// curve c's statistics from the group's host copy (records of `group` curves, then their per-transit rows when copied)
+int read_transit_stats(tls_ctx* ctx, const StatsRequest& sr, const double* h_stats, int64_t group, int64_t c, int64_t curve,
+                       bool with_rows) {
+    const double* rec = h_stats + (size_t)tlsdev::kTransitStats * c;
+    const double epochs = rec[10];
+    if (epochs > (double)sr.max_epochs)
+        return fail(ctx, TLS_E_ARG, "light curve " + std::to_string((long long)curve) + " has more than max_epochs = " +
+                                    std::to_string((long long)sr.max_epochs) + " transit epochs");
+    std::memcpy(&sr.out[curve], rec, sizeof(tls_transit_stats));
+    if (sr.out_n_epochs) sr.out_n_epochs[curve] = std::isnan(epochs) ? 0 : (int64_t)epochs;
+    if (sr.out_per_transit && with_rows) {
+        const size_t rows = (size_t)tlsdev::kPerTransitRows * (size_t)sr.max_epochs;
+        std::memcpy(sr.out_per_transit + (size_t)curve * rows, h_stats + (size_t)tlsdev::kTransitStats * group + (size_t)c * rows, rows * 8);
+    }
+    return TLS_OK;
+}
+
+// what the statistics stage requires beyond tls_power_batch's arguments
+int check_stats_request(tls_ctx* ctx, const StatsRequest& sr, const double* t, int64_t n, int64_t n_rows) {
+    if (!sr.row_duration || !sr.root || !sr.out) return fail(ctx, TLS_E_ARG, "null statistics argument");
+    if (sr.n_rows != n_rows) return fail(ctx, TLS_E_ARG, "one fractional duration per template row wanted");
+    if (sr.n_root < n + 1) return fail(ctx, TLS_E_ARG, "the k ** 0.5 table must cover k = 0 .. n");
+    if (sr.max_epochs < 1 || sr.max_epochs > 100000000) return fail(ctx, TLS_E_ARG, "max_epochs out of range [1, 1e8]");
+    if (n > 0x3fffffff) return fail(ctx, TLS_E_ARG, "n too large for the statistics stage");
+    for (int64_t i = 1; i < n; ++i)
+        if (!(t[i] >= t[i - 1])) return fail(ctx, TLS_E_ARG, "the statistics need non-decreasing time stamps");
     return TLS_OK;
 }
 
@@ -1267,6 +1347,7 @@ void tls_ctx_destroy(tls_ctx* ctx) {
     ctx->d_gather.release(); ctx->d_scalar.release(); ctx->d_stage.release();
     ctx->d_partials.release(); ctx->d_tiles_done.release(); ctx->d_check.release(); ctx->d_spec.release(); ctx->d_queue.release(); ctx->d_squeue.release(); ctx->d_pqueues.release(); ctx->d_phase.release(); ctx->d_lists.release(); ctx->d_perm.release(); ctx->d_curve_S0.release(); ctx->d_curve_w0.release();
     ctx->d_ft.release(); ctx->d_fy.release(); ctx->d_fsig.release(); ctx->d_fep.release(); ctx->d_fres.release(); ctx->d_fscratch.release(); ctx->d_frot.release(); ctx->d_frperm.release(); ctx->d_pink.release();
+    ctx->d_tstats.release(); ctx->d_tranges.release();
     ctx->d_split.release(); ctx->d_park.release(); ctx->d_band.release();
     if (ctx->h_band) (void)hipHostFree(ctx->h_band);
     for (auto& ev : ctx->ev_band) if (ev) (void)hipEventDestroy(ev);
@@ -2047,6 +2128,60 @@ int tls_debug_post_search(tls_ctx* ctx, const double* y, int64_t n_curves, const
     return TLS_OK;
 }
 
+int tls_debug_transit_stats(tls_ctx* ctx, const double* y, int64_t n_curves, const double* period, const double* T0,
+                            const int64_t* best_row, const double* depth, const int64_t* no_fit, const int64_t* index_power,
+                            const double* power, const double* row_duration, int64_t n_rows, double fill_factor,
+                            const double* root, int64_t n_root, int64_t max_epochs, tls_transit_stats* out_stats,
+                            double* out_per_transit, int64_t* out_n_epochs) {
+    if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
+    if (!ctx->prepared || !ctx->key.valid) return fail(ctx, TLS_E_STATE, "tls_debug_transit_stats before tls_prepare");
+    if (!y || !period || !T0 || !best_row || !depth || !no_fit || !index_power || !power) return fail(ctx, TLS_E_ARG, "null argument");
+    if (n_curves < 1 || n_curves > 1024) return fail(ctx, TLS_E_ARG, "n_curves out of range [1, 1024]");
+    TLS_HIP(ctx, hipSetDevice(ctx->device));
+    const PlanKey& k = ctx->key;
+    const int64_t n = k.n, n_periods = k.n_periods;
+    if (n_periods < 1) return fail(ctx, TLS_E_ARG, "tls_debug_transit_stats needs at least one period");
+    StatsRequest sr;
+    sr.row_duration = row_duration; sr.n_rows = n_rows; sr.fill_factor = fill_factor; sr.root = root; sr.n_root = n_root;
+    sr.max_epochs = max_epochs; sr.out = out_stats; sr.out_per_transit = out_per_transit; sr.out_n_epochs = out_n_epochs;
+    int rc = check_stats_request(ctx, sr, k.t.data(), n, k.n_rows);
+    if (rc) return rc;
+    const size_t np = (size_t)n_periods, nn = (size_t)n, gc = (size_t)n_curves;
+    for (size_t c = 0; c < gc; ++c) {
+        if (index_power[c] < 0 || index_power[c] >= n_periods) return fail(ctx, TLS_E_ARG, "index_power out of range");
+        if (!no_fit[c] && (best_row[c] < 0 || best_row[c] >= n_rows)) return fail(ctx, TLS_E_ARG, "best_row out of range");
+    }
+    const double t_min = *std::min_element(k.t.begin(), k.t.end()), t_max = *std::max_element(k.t.begin(), k.t.end());
+    auto& sl = ctx->slot[0];
+    TLS_HIP(ctx, sl.d_y.reserve(gc * nn));
+    PostSearchBufs pb;
+    if ((rc = reserve_post_search(ctx, n_curves, n_periods, n, 1, pb, sr.words()))) return rc;
+    StatsBufs sb;
+    if ((rc = reserve_transit_stats(ctx, sr, n_curves, n, sb))) return rc;
+    // the pick record of tls_power_pick ([2] index_power, [3] period, [4] depth, [5] best_row, [6] no_fit) and T0
+    std::vector<double> pick(8 * gc + gc, 0.0);
+    for (size_t c = 0; c < gc; ++c) {
+        double* pk = pick.data() + 8 * c;
+        pk[2] = (double)index_power[c]; pk[3] = period[c]; pk[4] = depth[c]; pk[5] = (double)(no_fit[c] ? 0 : best_row[c]);
+        pk[6] = no_fit[c] ? 1.0 : 0.0;
+        pick[8 * gc + c] = T0[c];
+    }
+    TLS_HIP(ctx, hipMemcpyAsync(sl.d_y.ptr, y, gc * nn * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpy2DAsync(ctx->d_spec.ptr + 2 * np, pb.spec_stride * 8, power, np * 8, np * 8, gc, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(pb.pick, pick.data(), pick.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = enqueue_transit_stats(ctx, pb, sb, sr, n_curves, sl.d_y.ptr, n, n_periods, t_min, t_max))) {
+        (void)hipStreamSynchronize(ctx->stream);
+        return rc;
+    }
+    std::vector<double> h(gc * sr.words());
+    TLS_HIP(ctx, hipMemcpyAsync(h.data(), pb.stats, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->executed = false;   // (the batch slot's buffers were written: as after tls_power_batch)
+    for (int64_t c = 0; c < n_curves; ++c)
+        if ((rc = read_transit_stats(ctx, sr, h.data(), n_curves, c, c, true))) return rc;
+    return TLS_OK;
+}
+
 int tls_debug_device_bytes(const tls_ctx* ctx, int64_t* total, int64_t* t0_fit_scratch) {
     if (!ctx || !total || !t0_fit_scratch) return TLS_E_ARG;
     size_t sum = 0;
@@ -2060,7 +2195,7 @@ int tls_debug_device_bytes(const tls_ctx* ctx, int64_t* total, int64_t* t0_fit_s
         add(sl.d_y); add(sl.d_w); add(sl.d_S0); add(sl.d_w0); add(sl.d_chi2); add(sl.d_depth); add(sl.d_row);
     }
     add(ctx->d_ft); add(ctx->d_fy); add(ctx->d_fsig); add(ctx->d_fep); add(ctx->d_fres); add(ctx->d_fscratch);
-    add(ctx->d_pink); add(ctx->d_frot); add(ctx->d_frperm); add(ctx->d_spec);
+    add(ctx->d_pink); add(ctx->d_frot); add(ctx->d_frperm); add(ctx->d_spec); add(ctx->d_tstats); add(ctx->d_tranges);
     add(ctx->d_partials); add(ctx->d_tiles_done);
     add(ctx->d_split); add(ctx->d_park); add(ctx->d_band);
     *total = (int64_t)sum;
@@ -2325,14 +2460,37 @@ int tls_search_batch(tls_ctx* ctx, const double* t, const double* y, const doubl
 static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, const double* dy, int64_t n, int64_t n_curves,
                             const double* periods, int64_t n_periods, const tls_template* tmpl, const tls_params* params,
                             int64_t median_kernel, tls_power_summary* out_summary, double* out_chi2, int64_t* out_row,
-                            double* out_depth, double* out_power, double* out_SR, double* out_power_raw);
+                            double* out_depth, double* out_power, double* out_SR, double* out_power_raw,
+                            const StatsRequest* sr);
+
+static int power_batch_finish(tls_ctx* ctx, int rc);
 
 int tls_power_batch(tls_ctx* ctx, const double* t, const double* y, const double* dy, int64_t n, int64_t n_curves,
                     const double* periods, int64_t n_periods, const tls_template* tmpl, const tls_params* params,
                     int64_t median_kernel, tls_power_summary* out_summary, double* out_chi2, int64_t* out_row,
                     double* out_depth, double* out_power, double* out_SR, double* out_power_raw) {
-    const int rc = power_batch_impl(ctx, t, y, dy, n, n_curves, periods, n_periods, tmpl, params, median_kernel, out_summary,
-                                    out_chi2, out_row, out_depth, out_power, out_SR, out_power_raw);
+    return power_batch_finish(ctx, power_batch_impl(ctx, t, y, dy, n, n_curves, periods, n_periods, tmpl, params, median_kernel,
+                                                    out_summary, out_chi2, out_row, out_depth, out_power, out_SR, out_power_raw, nullptr));
+}
+
+int tls_power_batch_stats(tls_ctx* ctx, const double* t, const double* y, const double* dy, int64_t n, int64_t n_curves,
+                          const double* periods, int64_t n_periods, const tls_template* tmpl, const tls_params* params,
+                          int64_t median_kernel, tls_power_summary* out_summary, double* out_chi2, int64_t* out_row,
+                          double* out_depth, double* out_power, double* out_SR, double* out_power_raw,
+                          const double* row_duration, double fill_factor, const double* root, int64_t n_root,
+                          tls_transit_stats* out_stats, int64_t max_epochs, double* out_per_transit, int64_t* out_n_epochs) {
+    if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
+    if (!t || !tmpl) return fail(ctx, TLS_E_ARG, "null argument");
+    StatsRequest sr;
+    sr.row_duration = row_duration; sr.n_rows = tmpl->n_rows; sr.fill_factor = fill_factor; sr.root = root; sr.n_root = n_root;
+    sr.max_epochs = max_epochs; sr.out = out_stats; sr.out_per_transit = out_per_transit; sr.out_n_epochs = out_n_epochs;
+    const int rc = check_stats_request(ctx, sr, t, n, tmpl->n_rows);
+    if (rc) return rc;
+    return power_batch_finish(ctx, power_batch_impl(ctx, t, y, dy, n, n_curves, periods, n_periods, tmpl, params, median_kernel,
+                                                    out_summary, out_chi2, out_row, out_depth, out_power, out_SR, out_power_raw, &sr));
+}
+
+static int power_batch_finish(tls_ctx* ctx, int rc) {
     if (ctx && rc != TLS_OK) {
         // EVERY failure leaves through here: nothing is still copying into or out of the pinned staging buffers or the
         // caller's arrays, and the context does not keep pointing at a batch slot
@@ -2349,7 +2507,8 @@ int tls_power_batch(tls_ctx* ctx, const double* t, const double* y, const double
 static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, const double* dy, int64_t n, int64_t n_curves,
                             const double* periods, int64_t n_periods, const tls_template* tmpl, const tls_params* params,
                             int64_t median_kernel, tls_power_summary* out_summary, double* out_chi2, int64_t* out_row,
-                            double* out_depth, double* out_power, double* out_SR, double* out_power_raw) {
+                            double* out_depth, double* out_power, double* out_SR, double* out_power_raw,
+                            const StatsRequest* sr) {
     if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
     if (n_curves < 0) return fail(ctx, TLS_E_ARG, "negative number of light curves");
     if (n_curves == 0) return TLS_OK;
@@ -2378,14 +2537,18 @@ static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, cons
     int64_t max_len = 1;
     for (int64_t r = 0; r < tmpl->n_rows; ++r) max_len = std::max(max_len, tmpl->length[r]);
     PostSearchBufs pb;
-    if ((rc = reserve_post_search(ctx, group, n_periods, n, max_len, pb))) return rc;
+    if ((rc = reserve_post_search(ctx, group, n_periods, n, max_len, pb, sr ? sr->words() : 0))) return rc;
     const size_t spec_stride = pb.spec_stride;
+    // (statistics requested: their records -- and the per-transit rows when asked for -- ride in the group's one copy out)
+    StatsBufs sb;
+    if (sr && (rc = reserve_transit_stats(ctx, *sr, group, n, sb))) return rc;
+    const size_t stats_out = !sr ? 0 : sr->out_per_transit ? sr->words() : (size_t)tlsdev::kTransitStats;
     // pinned staging: flux in; summaries, T0 and (on request) the per-period arrays out.  TWO sets (the device buffers are
     // one: the stream runs the groups in order): while the device works on group g the host forms group g + 1 in the other
     // set and enqueues it, THEN waits for g -- the device never waits for the host between two groups (round 6)
     const size_t in_doubles = (size_t)group * nn * (uni ? 1 : 2) + 2 * (size_t)group;
     const size_t arrays = (out_chi2 ? 3 : 0) + (out_power ? 1 : 0) + (out_SR ? 1 : 0) + (out_power_raw ? 1 : 0);
-    const size_t out_doubles = 11 * (size_t)group + arrays * (size_t)group * np;
+    const size_t out_doubles = (11 + stats_out) * (size_t)group + arrays * (size_t)group * np;
     for (auto& hs : ctx->slot) {
         if (!hs.ev_out) {
             TLS_HIP(ctx, hipEventCreateWithFlags(&hs.ev_in, hipEventDisableTiming));
@@ -2439,12 +2602,13 @@ static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, cons
         return TLS_OK;
     };
     // host layout of a group's results (the same in both sets)
-    struct OutLayout { double *sde, *pick, *T0, *chi2, *power, *SR, *praw, *spec3; };
+    struct OutLayout { double *sde, *pick, *T0, *stats, *chi2, *power, *SR, *praw, *spec3; };
     auto out_layout = [&](int64_t g) -> OutLayout {
         OutLayout o{};
         double* base = ctx->slot[g & 1].h_out;
         o.sde = base; o.pick = o.sde + 2 * (size_t)group; o.T0 = o.pick + 8 * (size_t)group;
-        double* h_next = o.T0 + group;                   // chi2 | row | depth | power | SR | power_raw, on request
+        o.stats = o.T0 + group;                          // statistics records (and rows), on request
+        double* h_next = o.stats + stats_out * (size_t)group;   // chi2 | row | depth | power | SR | power_raw, on request
         if (out_chi2) { o.chi2 = h_next; h_next += 3 * (size_t)group * np; }
         if (out_power && out_SR && out_power_raw) { o.spec3 = h_next; h_next += 3 * (size_t)group * np; }
         else {
@@ -2489,9 +2653,10 @@ static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, cons
         rc2 = enqueue_post_search(ctx, pb, gc, sl.d_chi2.ptr, sl.d_row.ptr, sl.d_depth.ptr, sl.d_y.ptr, n, n_periods, median_kernel,
                                   t_min, t_max, params->T0_fit_margin);
         if (rc2) return rc2;
-        // (sde | pick | T0 lie side by side behind the spectra on the device: ONE copy, the host keeps the layout)
+        if (sr && (rc2 = enqueue_transit_stats(ctx, pb, sb, *sr, gc, sl.d_y.ptr, n, n_periods, t_min, t_max))) return rc2;
+        // (sde | pick | T0 [| statistics] lie side by side behind the spectra on the device: ONE copy, the host keeps the layout)
         const OutLayout o = out_layout(g);
-        TLS_HIP(ctx, hipMemcpyAsync(o.sde, pb.sde, 11 * (size_t)group * 8, hipMemcpyDeviceToHost, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(o.sde, pb.sde, (11 + stats_out) * (size_t)group * 8, hipMemcpyDeviceToHost, ctx->stream));
         if (out_chi2) {
             TLS_HIP(ctx, hipMemcpyAsync(o.chi2, sl.d_chi2.ptr, (size_t)gc * np * 8, hipMemcpyDeviceToHost, ctx->stream));
             TLS_HIP(ctx, hipMemcpyAsync(o.chi2 + (size_t)group * np, sl.d_row.ptr, (size_t)gc * np * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -2537,6 +2702,11 @@ static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, cons
             const int rc2 = read_summary(ctx, o.sde, group, c, c0 + c, out_summary[c0 + c]);
             if (rc2) return rc2;
         }
+        if (sr)
+            for (int64_t c = 0; c < gc; ++c) {
+                const int rc2 = read_transit_stats(ctx, *sr, o.stats, group, c, c0 + c, true);
+                if (rc2) return rc2;
+            }
         if (out_chi2) {
             std::memcpy(out_chi2 + c0 * n_periods, o.chi2, (size_t)gc * np * 8);
             std::memcpy(out_row + c0 * n_periods, o.chi2 + (size_t)group * np, (size_t)gc * np * 8);

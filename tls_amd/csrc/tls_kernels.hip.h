@@ -3778,4 +3778,281 @@ __global__ void __launch_bounds__(1024) tls_cumsum_kernel(const double* f, doubl
     else exact_sequential_cumsum(f, out, count, reinterpret_cast<CumsumScratch*>(scratch));
 }
 
+// ---- survey-mode power()'s per-transit vetting statistics (api.py:175-241 over the host functions of stats.py), one workgroup
+// of 256 threads per light curve of a group, enqueued behind tls_first_min: transit times, duration in days, the in-transit
+// chunk of every epoch (two binary searches on ascending t), per-epoch count / mean / population std, the odd and even
+// concatenations, the out-of-transit flux (transit_mask's order kept by a ballot compaction), pink noise, SNR, counts and
+// the period uncertainty.  Every numpy.mean / numpy.std is numpy_pairwise_sum in numpy's association, squares rounded before
+// they are summed; every `k ** 0.5` Python forms from a count is root[k], a table the caller built with Python's pow.
+constexpr int kTransitStats = 16;      // doubles of one tls_transit_stats record
+constexpr int kPerTransitRows = 6;     // transit_times | per_transit_count | transit_depths | ..._uncertainties | snr | snr_pink
+constexpr int kExactSegments = 512;    // stats._EXACT_SEGMENTS: non-empty epochs up to which power() sums each chunk on its own
+struct TransitStatsArgs {
+    const double* t; const double* y;              // [n] ascending, [n_curves][n]
+    const double* pick; const double* T0;          // [n_curves][8] (tls_power_pick), [n_curves] (tls_first_min)
+    const double* power; long long power_stride;   // detrended power of curve c at power + c * power_stride
+    const double* periods; int n_periods;
+    const double* row_duration;                    // lc_cache_overview["duration"] of every template row
+    const double* root; int n_root;                // root[k] = float(k) ** 0.5
+    double fill_factor, t_min, t_max;
+    double* stats;                                 // [n_curves][kTransitStats]
+    double* per_transit;                           // [n_curves][kPerTransitRows][max_epochs]
+    int* ranges;                                   // [n_curves][3][max_epochs]: chunk start | stop | offset in concat(odd, even)
+    double* scratch;                               // [n_curves][scratch_stride]: flux_ootr | concat(odd, even) | pink terms | sums
+    long long scratch_stride;
+    int n, max_epochs;
+};
+
+// numpy's float remainder (npy_divmod): fmod, then the result takes the divisor's sign
+__device__ __forceinline__ double numpy_remainder(double a, double b) {
+    double m = fmod(a, b);
+    if (b == 0.0) return m;
+    if (m != 0.0) { if ((b < 0.0) != (m < 0.0)) m += b; }
+    else m = copysign(0.0, b);
+    return m;
+}
+
+// stats.period_uncertainty from the peak `peak`: the upper walk past the end is inf, the lower walk and periods[lower] wrap
+// through negative indices like Python's, and below -n_periods they are inf too.  flat: the zero power of a curve without fit.
+__device__ double period_uncertainty_walk(const double* power, const double* periods, int np, int peak, bool flat) {
+    auto pw = [&](int i) { return flat ? 0.0 : power[i]; };
+    const double half = 0.5 * pw(peak);
+    int upper = peak + 1;
+    for (;; ++upper) {
+        if (upper >= np) return INFINITY;
+        if (!(pw(upper) > half)) break;
+    }
+    int lower = peak - 1;
+    for (;; --lower) {
+        if (lower < -np) return INFINITY;
+        if (!(pw(lower < 0 ? lower + np : lower) > half)) break;
+    }
+    return 0.5 * (periods[upper] - periods[lower < 0 ? lower + np : lower]);
+}
+
+__global__ void __launch_bounds__(256) tls_transit_stats(const TransitStatsArgs a) {
+#pragma clang fp contract(off)
+    __shared__ __attribute__((aligned(16))) unsigned char cs_lds[kCumsumScratchBytes];
+    __shared__ int s_mode, s_E, s_width, s_L, s_empty, s_nonfinite, s_wcount[kMaxWaves];
+    __shared__ long long s_M_odd, s_M_all;
+    __shared__ unsigned long long s_in, s_after, s_before;
+    __shared__ double s_d, s_dur, s_period, s_T0, s_pink, s_sum[8];
+    const int tid = threadIdx.x, nt = blockDim.x, n = a.n, maxE = a.max_epochs;
+    const int lane = tid & (kWave - 1), wave = tid / kWave, nw = nt / kWave;
+    const long long c = blockIdx.x;
+    const double* t = a.t;
+    const double* y = a.y + c * n;
+    const double* pk = a.pick + 8 * c;
+    double* st = a.stats + c * kTransitStats;
+    double* times = a.per_transit + c * (long long)kPerTransitRows * maxE;
+    double* cnt = times + maxE; double* means = cnt + maxE; double* unc = means + maxE;
+    double* snr_w = unc + maxE; double* snr_p = snr_w + maxE;
+    int* r_start = a.ranges + c * 3LL * maxE; int* r_stop = r_start + maxE; int* r_off = r_stop + maxE;
+    double* ootr = a.scratch + c * a.scratch_stride; double* cat = ootr + n; double* terms = cat + n; double* sums = terms + n;
+    if (tid == 0) {
+        const bool flat = pk[6] != 0.0 || pk[7] != 0.0;
+        const double period = pk[3], T0 = a.T0[c];
+        st[0] = period_uncertainty_walk(a.power + c * a.power_stride, a.periods, a.n_periods, flat ? 0 : (int)pk[2], flat);
+        int mode = flat ? 1 : 0, E = 0;
+        double d = NAN, dur = NAN;
+        if (!flat) {
+            // all_transit_times: one period added at a time, the first epoch one period on when T0 < min(t)
+            const double end = a.t_min + (a.t_max - a.t_min);
+            double tt = T0 < a.t_min ? T0 + period : T0;
+            times[0] = tt; E = 1;
+            while (tt + period < end) {
+                if (E >= maxE) { mode = 2; E = maxE + 1; break; }
+                tt = tt + period;
+                times[E++] = tt;
+            }
+            // calculate_transit_duration_in_days: duration * stretch * period, then * fill_factor
+            dur = a.row_duration[(long long)pk[5]];
+            const double stretch = ((a.t_max - a.t_min) / period) / (double)E;
+            d = dur * stretch * period;
+            d = d * a.fill_factor;
+        }
+        s_mode = mode; s_E = E; s_d = d; s_dur = dur; s_period = period; s_T0 = T0;
+        s_in = 0; s_after = 0; s_before = 0; s_empty = 0;
+    }
+    wg_sync();
+    const int mode = s_mode, E = s_E;
+    if (mode != 0) {   // no fit (api._results_without_fit: NaN), or more epochs than max_epochs (the host reports it)
+        for (int k = tid; k < kPerTransitRows * maxE; k += nt) times[k] = NAN;
+        if (tid == 0) {
+            for (int f = 1; f < kTransitStats; ++f) st[f] = NAN;
+            if (mode == 2) st[10] = (double)E;
+        }
+        return;
+    }
+    const double d = s_d;
+    // searchsorted(t, v, "right") / searchsorted(t, v, "left"); open interval (lo, hi) as [s, e), NaN bounds empty
+    auto count_le = [&](double v) { int lo = 0, hi = n; while (lo < hi) { const int m = (lo + hi) >> 1; if (t[m] <= v) lo = m + 1; else hi = m; } return lo; };
+    auto count_lt = [&](double v) { int lo = 0, hi = n; while (lo < hi) { const int m = (lo + hi) >> 1; if (t[m] < v) lo = m + 1; else hi = m; } return lo; };
+    auto open_range = [&](double lo, double hi, int& s, int& e) {
+        s = count_le(lo); e = count_lt(hi);
+        if (isnan(lo) || isnan(hi)) e = s; else e = e > s ? e : s;
+    };
+    unsigned long long my_in = 0, my_after = 0, my_before = 0;
+    int my_empty = 0;
+    for (int k = tid; k < E; k += nt) {
+        const double mid = times[k];
+        const double lo = mid - 0.5 * d, hi = mid + 0.5 * d;
+        int s, e;
+        open_range(lo, hi, s, e);   // _intransit_fluxes
+        r_start[k] = s; r_stop[k] = e;
+        cnt[k] = (double)(e - s);
+        if (e == s) ++my_empty;
+        const double e0 = mid - 1.5 * d, e3 = mid + 1.5 * d;   // count_stats: epochs fully inside the data
+        if (e0 > a.t_min && e3 < a.t_max) {
+            int s2, e2;
+            open_range(e0, lo, s2, e2); my_before += (unsigned long long)(e2 - s2);
+            my_in += (unsigned long long)(e - s);
+            open_range(hi, e3, s2, e2); my_after += (unsigned long long)(e2 - s2);
+        }
+    }
+    atomicAdd(&s_in, my_in); atomicAdd(&s_after, my_after); atomicAdd(&s_before, my_before); atomicAdd(&s_empty, my_empty);
+    // flux_ootr = y[~transit_mask(t, period, 2 * duration, T0)] (the fractional duration used as days), in order
+    {
+        const double period = s_period, T0 = s_T0, dur2 = 2.0 * s_dur;
+        int base_out = 0;
+        for (int base = 0; base < n; base += nt) {
+            const int i = base + tid;
+            bool keep = false;
+            if (i < n) keep = !(fabs(numpy_remainder(t[i] - T0 + 0.5 * period, period) - 0.5 * period) < 0.5 * dur2);
+            const unsigned long long m = __ballot(keep);
+            const int below = __popcll(m & ((1ull << lane) - 1ull));
+            if (lane == 0) s_wcount[wave] = __popcll(m);
+            wg_sync();
+            int off = base_out, total = 0;
+            for (int w = 0; w < nw; ++w) { if (w < wave) off += s_wcount[w]; total += s_wcount[w]; }
+            if (keep) ootr[off + below] = y[i];
+            base_out += total;
+            wg_sync();
+        }
+        if (tid == 0) s_L = base_out;
+    }
+    wg_sync();
+    if (tid == 0) {
+        // offsets of every chunk in concat(chunks[1::2], chunks[0::2]), and int(numpy.mean(per_transit_count))
+        long long off = 0;
+        for (int k = 1; k < E; k += 2) { r_off[k] = (int)(off < 0x7fffffff ? off : 0x7fffffff); off += r_stop[k] - r_start[k]; }
+        s_M_odd = off;
+        for (int k = 0; k < E; k += 2) { r_off[k] = (int)(off < 0x7fffffff ? off : 0x7fffffff); off += r_stop[k] - r_start[k]; }
+        s_M_all = off;
+        const double mean_count = numpy_pairwise_sum([cnt](int k) { return cnt[k]; }, 0, E) / (double)E;
+        s_width = mean_count < 2147483647.0 ? (int)mean_count : 0x7fffffff;
+    }
+    wg_sync();
+    const long long M_odd = s_M_odd, M_all = s_M_all;
+    const bool cat_ok = M_all <= n;             // (chunks overlap only when the duration in days exceeds the period)
+    const bool exact = E - s_empty <= kExactSegments;
+    for (int k = tid; k < E; k += nt) {
+        const int s = r_start[k], m = r_stop[k] - s;
+        if (m == 0) { means[k] = NAN; unc[k] = NAN; continue; }
+        const double* ch = y + s;
+        const double dm = (double)m;
+        double mean, var;
+        auto sq_dev = [ch](int j, double mu) { const double dv = ch[j] - mu; double sq = dv * dv; asm volatile("" : "+v"(sq)); return sq; };
+        if (exact) {   // numpy.mean / numpy.std of the chunk
+            mean = numpy_pairwise_sum([ch](int j) { return ch[j]; }, 0, m) / dm;
+            var = numpy_pairwise_sum([&](int j) { return sq_dev(j, mean); }, 0, m) / dm;
+        } else {       // numpy.add.reduceat: the segment's first element plus the pairwise sum of the rest
+            mean = (m > 1 ? ch[0] + numpy_pairwise_sum([ch](int j) { return ch[j]; }, 1, m - 1) : ch[0]) / dm;
+            const double mu = mean;
+            var = (m > 1 ? sq_dev(0, mu) + numpy_pairwise_sum([&](int j) { return sq_dev(j, mu); }, 1, m - 1) : sq_dev(0, mu)) / dm;
+        }
+        means[k] = mean;
+        unc[k] = sqrt(var) / sqrt(dm);
+        if (cat_ok) { double* dst = cat + r_off[k]; for (int j = 0; j < m; ++j) dst[j] = ch[j]; }
+    }
+    // pink noise (snr_stats -> stats.pink_noise): tls_pink_terms' windows over flux_ootr, the exact sequential sum of the terms
+    wg_sync();
+    const int L = s_L, width = s_width;
+    const int n_windows = L - width + 1;
+    if (tid == 0) s_nonfinite = 0;
+    wg_sync();
+    if (width >= 1 && n_windows >= 1) {
+        const double wd = (double)width, rw = a.root[width];
+        for (int i = tid; i < n_windows; i += nt) {
+            const double* w = ootr + i;
+            const double mu = numpy_pairwise_sum([w](int k) { return w[k]; }, 0, width) / wd;
+            const double var = numpy_pairwise_sum([w, mu](int k) { const double dv = w[k] - mu; double sq = dv * dv; asm volatile("" : "+v"(sq)); return sq; }, 0, width) / wd;
+            terms[i] = sqrt(var) / rw;
+            if (!isfinite(terms[i])) s_nonfinite = 1;   // (the exact scan wants finite terms: those add one by one below)
+        }
+        wg_sync();
+        if (s_nonfinite == 0) {
+            const double total = exact_cumsum<false, false>(terms, sums, n_windows, reinterpret_cast<Cumsum2Scratch*>(cs_lds));
+            if (tid == 0) s_pink = total / (double)n_windows;
+        } else if (tid == 0) {
+            double total = 0.0;
+            for (int i = 0; i < n_windows; ++i) total += terms[i];
+            s_pink = total / (double)n_windows;
+        }
+    } else if (tid == 0) {
+        s_pink = NAN;   // (the host's pink_noise raises: snr_stats' except)
+    }
+    wg_sync();
+    // mean and population std of the odd, even and all concatenations and of flux_ootr: one wave each
+    if (lane == 0 && wave < 4) {
+        const int n_odd = E / 2;
+        auto cat_at = [&](long long j) -> double {
+            if (cat_ok) return cat[j];
+            // (overlapping chunks: the chunk that holds element j of the concatenation, epochs 1, 3, ... then 0, 2, ...)
+            auto epoch = [&](int q) { return q < n_odd ? 2 * q + 1 : 2 * (q - n_odd); };
+            int lo = 0, hi = E - 1;
+            while (lo < hi) { const int q = (lo + hi + 1) >> 1; if ((long long)r_off[epoch(q)] <= j) lo = q; else hi = q - 1; }
+            const int k = epoch(lo);
+            return y[r_start[k] + (j - r_off[k])];
+        };
+        long long lo = 0, m = 0;
+        if (wave == 0) { lo = 0; m = M_odd; }
+        else if (wave == 1) { lo = M_odd; m = M_all - M_odd; }
+        else if (wave == 2) { lo = 0; m = M_all; }
+        else m = L;
+        double mean = NAN, sd = NAN;
+        if (m > 0) {
+            const double dm = (double)m;
+            if (wave < 3) {
+                mean = numpy_pairwise_sum([&](int j) { return cat_at(j); }, (int)lo, (int)m) / dm;
+                const double mu = mean;
+                sd = sqrt(numpy_pairwise_sum([&](int j) { const double dv = cat_at(j) - mu; double sq = dv * dv; asm volatile("" : "+v"(sq)); return sq; }, (int)lo, (int)m) / dm);
+            } else {
+                mean = numpy_pairwise_sum([ootr](int j) { return ootr[j]; }, 0, (int)m) / dm;
+                const double mu = mean;
+                sd = sqrt(numpy_pairwise_sum([ootr, mu](int j) { const double dv = ootr[j] - mu; double sq = dv * dv; asm volatile("" : "+v"(sq)); return sq; }, 0, (int)m) / dm);
+            }
+        }
+        s_sum[2 * wave] = mean; s_sum[2 * wave + 1] = sd;
+    }
+    wg_sync();
+    auto root = [&](long long k) { return k < a.n_root ? a.root[k] : sqrt((double)k); };
+    const double std_ootr = s_sum[7], pink = s_pink;
+    const double std_snr = L > 0 ? std_ootr : NAN;
+    for (int k = tid; k < maxE; k += nt) {
+        if (k < E) {
+            const double m = cnt[k];
+            const bool usable = m > 0.0 && !isnan(std_snr);
+            snr_w[k] = usable ? (1 - means[k]) / (std_snr / sqrt(m)) : 0.0;
+            snr_p[k] = usable ? (1 - means[k]) / pink : 0.0;
+        } else {
+            times[k] = NAN; cnt[k] = NAN; means[k] = NAN; unc[k] = NAN; snr_w[k] = NAN; snr_p[k] = NAN;
+        }
+    }
+    if (tid == 0) {
+        const long long M_even = M_all - M_odd;
+        const double mean_odd = s_sum[0], mean_even = s_sum[2], depth_mean = s_sum[4];
+        const double err_odd = M_odd > 0 ? s_sum[1] / root(M_odd) : NAN;
+        const double err_even = M_even > 0 ? s_sum[3] / root(M_even) : NAN;
+        st[1] = d;
+        st[2] = depth_mean; st[3] = s_sum[5] / root(M_all);
+        st[4] = mean_even; st[5] = err_even; st[6] = mean_odd; st[7] = err_odd;
+        st[8] = ((1 - depth_mean) / std_ootr) * root(M_all);
+        st[9] = fabs(mean_odd - mean_even) / (err_odd + err_even);
+        const int empty = s_empty;
+        st[10] = (double)E; st[11] = (double)(E - empty); st[12] = (double)empty;
+        st[13] = (double)s_in; st[14] = (double)s_after; st[15] = (double)s_before;
+    }
+}
+
 }  // namespace tlsdev

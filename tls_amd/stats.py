@@ -39,6 +39,11 @@ def FAP(SDE):
 def rp_rs_from_depth(depth, law, params):
     """Planet-to-star radius ratio from the maximum transit depth for a given
     limb-darkening law (Heller 2019, arXiv:1901.01730; reference stats.py:21-69)."""
+    return (depth * limb_darkening_factor(law, params)) ** (1 / 2)
+
+
+def limb_darkening_factor(law, params):
+    """The factor rp_rs_from_depth applies to the depth of `law` (validated as the reference does)."""
     if len(params) == 1:
         params = float(params[0])
     if not isinstance(params, (float, int)) and not all(
@@ -64,7 +69,7 @@ def rp_rs_from_depth(depth, law, params):
         factor = 1 + 2 * params[1] / 9 - params[0] / 3
     else:
         factor = 1 - params[0] / 5 - params[1] / 3 - 3 * params[2] / 7 - params[3] / 2
-    return (depth * factor) ** (1 / 2)
+    return factor
 
 
 def _window_sums(cols):

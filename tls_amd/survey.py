@@ -77,15 +77,48 @@ def _on_devices(group, call, n_curves):
     return [p for p in parts if p is not None]
 
 
-def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_arrays=False, devices=None, **power_kwargs):
+def _max_epochs(t, periods):
+    """Most transit epochs any pick on this grid can have (all_transit_times from a T0 in [min t, min t + period])."""
+    return int(numpy.ceil((numpy.max(t) - numpy.min(t)) / numpy.min(periods))) + 2
+
+
+def _fap(sde):
+    """stats.FAP of every entry of `sde`, vectorised: fap[argmax(threshold > SDE)]."""
+    from .stats import _fap_table
+    fap, thr = _fap_table()
+    sde = numpy.asarray(sde, dtype=numpy.float64)
+    if numpy.all(thr[1:] >= thr[:-1]):
+        # (ascending thresholds: the first one above SDE is a binary search; none above -- inf or NaN SDE -- gives 0, like argmax)
+        idx = numpy.searchsorted(thr, sde, side="right")
+        idx[(idx >= len(thr)) | numpy.isnan(sde)] = 0
+    else:
+        idx = numpy.argmax(thr[None, :] > sde[:, None], axis=1)
+    return fap[idx]
+
+
+def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_arrays=False, devices=None, statistics=False,
+                per_transit=False, **power_kwargs):
     """Survey-mode power(): for every light curve of `flux_batch` what `transitleastsquares(t, flux).power(**kwargs)`
     reports as SDE, SDE_raw, chi2_min, period, T0, depth and duration (fractional, lc_cache_overview["duration"] of
     the template row at the chi^2 minimum, main.py:199-200) -- search, SDE spectra and final T0 fit all on the
     device (tls_power_batch), one record of 80 bytes back per light curve.
 
-    Returns (summary, periods[, chi2, row, depth, power]): summary is a numpy structured array with the fields of
-    tls_power_summary plus "duration".  The per-transit statistics of power() (SNR, odd/even, counts) are host work
-    on a handful of candidates and are not part of the batch call."""
+    statistics=True adds power()'s per-transit vetting statistics, computed on the device behind the final T0 fit
+    (tls_power_batch_stats): the fields of tls_transit_stats (period_uncertainty, duration_days = results.duration in
+    days, depth_mean[_std], depth_mean_even[_std], depth_mean_odd[_std], snr, odd_even_mismatch and the transit counts),
+    plus rp_rs, FAP and chi2red_min formed on the host.  Every field equals the results key of the same name (the tuples
+    split into _std fields); a curve without a fit reports what power() reports then.  per_transit=True (implies
+    statistics) also returns a dict of [n_curves, max_epochs] arrays -- transit_times, per_transit_count, transit_depths,
+    transit_depths_uncertainties, snr_per_transit, snr_pink_per_transit, NaN past a curve's epochs -- and n_epochs.
+    The statistics need ascending t.
+
+    Returns (summary, periods[, chi2, row, depth, power][, per_transit]): summary is a numpy structured array with the
+    fields of tls_power_summary plus "duration" (and the statistics on request)."""
+    statistics = bool(statistics or per_transit)
+    if statistics:
+        t_check = numpy.asarray(t, dtype=numpy.float64)
+        if t_check.ndim != 1 or not numpy.all(t_check[1:] >= t_check[:-1]):
+            raise ValueError("statistics=True needs ascending time stamps t")
     inp, y_rows, dy_rows = _batch_inputs(t, flux_batch, dy_batch, power_kwargs)
     from . import constants as C
     osf = power_kwargs.get("oversampling_factor", C.OVERSAMPLING_FACTOR)
@@ -93,27 +126,61 @@ def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_ar
     if kernel != int(kernel):
         raise ValueError("oversampling_factor * %d must be an integer" % C.SDE_MEDIAN_KERNEL_SIZE)
 
-    def call(ctx, lo, hi):
-        return ctx.power_batch(inp["t"], y_rows[lo:hi], dy_rows[lo:hi], inp["periods"], inp["table"], inp["params"],
-                               int(kernel), with_arrays=with_arrays, with_power=with_arrays)
+    if statistics:
+        from .stats import calculate_fill_factor
+        fill_factor = calculate_fill_factor(inp["t"])
+        root = numpy.array([float(k) ** 0.5 for k in range(len(inp["t"]) + 1)])   # (Python's pow, as power() forms k ** 0.5)
+        max_epochs = _max_epochs(inp["t"], inp["periods"])
+
+        def call(ctx, lo, hi):
+            return ctx.power_batch_stats(inp["t"], y_rows[lo:hi], dy_rows[lo:hi], inp["periods"], inp["table"], inp["params"],
+                                         int(kernel), fill_factor, root, max_epochs, per_transit=per_transit,
+                                         with_arrays=with_arrays)
+    else:
+        def call(ctx, lo, hi):
+            return ctx.power_batch(inp["t"], y_rows[lo:hi], dy_rows[lo:hi], inp["periods"], inp["table"], inp["params"],
+                                   int(kernel), with_arrays=with_arrays, with_power=with_arrays)
 
     kind, what = _resolve(devices, device, context, len(y_rows))
     if kind == "group":
         parts = _on_devices(what, call, len(y_rows))
-        raw = numpy.concatenate([p[0] for p in parts])
-        chi2, row, depth, power = (numpy.concatenate([p[k] for p in parts]) if with_arrays else None for k in (1, 2, 3, 4))
     else:
         ctx = context if context is not None else _search.default_context(what)
-        raw, chi2, row, depth, power = call(ctx, 0, len(y_rows))
+        parts = [call(ctx, 0, len(y_rows))]
+    out = [None if parts[0][k] is None else numpy.concatenate([p[k] for p in parts]) for k in range(len(parts[0]))]
+    if statistics:
+        raw, tstats, rows, n_epochs, chi2, row, depth, power = out
+    else:
+        raw, chi2, row, depth, power = out
     names = list(raw.dtype.names) + ["duration"]
-    summary = numpy.zeros(len(raw), dtype=[(k, raw.dtype[k]) for k in raw.dtype.names] + [("duration", "f8")])
+    fields = [(k, raw.dtype[k]) for k in raw.dtype.names] + [("duration", "f8")]
+    if statistics:
+        fields += [(k, "f8") for k in tstats.dtype.names] + [("rp_rs", "f8"), ("FAP", "f8"), ("chi2red_min", "f8")]
+    summary = numpy.zeros(len(raw), dtype=fields)
     for k in raw.dtype.names:
         summary[k] = raw[k]
     summary["duration"] = numpy.where(raw["no_fit"] != 0, numpy.nan, inp["table"].duration[raw["best_row"]])
-    assert names == list(summary.dtype.names)
+    assert names == list(summary.dtype.names)[:len(names)]
+    if statistics:
+        from .stats import limb_darkening_factor
+        for k in tstats.dtype.names:
+            summary[k] = tstats[k]
+        # rp_rs_from_depth(1 - depth) curve by curve (numpy's scalar ** 0.5, as power() takes it); NaN without a fit
+        factor = limb_darkening_factor(inp["limb_dark"], inp["u"])
+        fit = raw["no_fit"] == 0
+        summary["rp_rs"] = numpy.nan
+        summary["rp_rs"][fit] = [x ** (1 / 2) for x in (1 - raw["depth"][fit]) * factor]
+        summary["FAP"] = _fap(raw["SDE"])
+        summary["chi2red_min"] = raw["chi2_min"] / (len(inp["t"]) - 4)
+    result = (summary, inp["periods"])
     if with_arrays:
-        return summary, inp["periods"], chi2, row, depth, power
-    return summary, inp["periods"]
+        result += (chi2, row, depth, power)
+    if per_transit:
+        from ._lib import PER_TRANSIT_FIELDS
+        pt = {k: rows[:, i, :] for i, k in enumerate(PER_TRANSIT_FIELDS)}
+        pt["n_epochs"] = n_epochs
+        result += (pt,)
+    return result
 
 
 def search_batch(t, flux_batch, dy_batch=None, context=None, device=None, devices=None, **power_kwargs):
