@@ -33,9 +33,9 @@ extern "C" {
 /* Bumped whenever a struct of this header changes its layout or an entry point its signature (3: tls_counters has
  * five fields, tls_period_costs / tls_power_batch exist; 4: tls_options, tls_get_options / tls_set_options; 5: tls_options
  * keeps the two caller-facing switches, the developer switches moved behind tls_debug_set_switch, tls_period_costs takes
- * them as text; 6: tls_transit_stats, tls_power_batch_stats, tls_debug_transit_stats).  A binding compares it with
- * tls_abi_version(). */
-#define TLS_AMD_ABI_VERSION 6
+ * them as text; 6: tls_transit_stats, tls_power_batch_stats, tls_debug_transit_stats; 7: tls_power_batch_models,
+ * tls_debug_transit_models).  A binding compares it with tls_abi_version(). */
+#define TLS_AMD_ABI_VERSION 7
 
 #define TLS_OK 0
 #define TLS_E_ARG (-1)      /* invalid argument */
@@ -287,6 +287,37 @@ int tls_debug_transit_stats(tls_ctx *ctx, const double *y, int64_t n_curves, con
                             const double *power, const double *row_duration, int64_t n_rows, double fill_factor,
                             const double *root, int64_t n_root, int64_t max_epochs, tls_transit_stats *out_stats,
                             double *out_per_transit, int64_t *out_n_epochs);
+/* tls_power_batch_stats plus the arrays power() returns for plotting (api.py:175-203), computed on the device behind the
+ * statistics of each group and copied back with them (still one wait per group):
+ *   out_folded [n_curves][3][n]: folded_phase, folded_y and the order (indices into t, as doubles) that sorts the phases
+ *     fold(t, period, T0 + period / 2) ascending.  The order is the stable one: equal phases by index (power()'s
+ *     numpy.argsort leaves their order open; for distinct phases the two agree).  folded_dy is dy gathered by that order.
+ *   out_model_folded [n_curves][n]: model_folded_model.
+ *   out_lc [n_curves][2][lc_cap]: model_lightcurve_time, then model_lightcurve_model, NaN past out_lc_len[c] entries.
+ * curve_t / curve_f: the in-transit slice of the supersampled template curve (template.py:52-53, curve_n >= 2 ascending
+ * time stamps); curve_lo / curve_hi: the ends of reference_transit's linspace (t[first], t[-first - 1]); maxw:
+ * int(max(durations) * n), not rounded up to even (api.py:140).  Every row of a curve without a fit is NaN, its length 0.
+ * TLS_E_ARG as tls_power_batch_stats, when lc_cap is below a curve's model light curve, and where power() itself raises
+ * (fewer than two model samples, a squeezed transit wider than its window).  out_per_transit may be NULL. */
+int tls_power_batch_models(tls_ctx *ctx, const double *t, const double *y, const double *dy, int64_t n,
+                           int64_t n_curves, const double *periods, int64_t n_periods,
+                           const tls_template *tmpl, const tls_params *params, int64_t median_kernel,
+                           tls_power_summary *out_summary, double *out_chi2, int64_t *out_row, double *out_depth,
+                           double *out_power, double *out_SR, double *out_power_raw,
+                           const double *row_duration, double fill_factor, const double *root, int64_t n_root,
+                           tls_transit_stats *out_stats, int64_t max_epochs, double *out_per_transit,
+                           int64_t *out_n_epochs, const double *curve_t, const double *curve_f, int64_t curve_n,
+                           double curve_lo, double curve_hi, double maxw, int64_t lc_cap, double *out_folded,
+                           double *out_model_folded, double *out_lc, int64_t *out_lc_len);
+/* developer/test entry: the statistics and model stages of tls_power_batch_models on injected picks, as
+ * tls_debug_transit_stats; the model arguments as tls_power_batch_models. */
+int tls_debug_transit_models(tls_ctx *ctx, const double *y, int64_t n_curves, const double *period, const double *T0,
+                             const int64_t *best_row, const double *depth, const int64_t *no_fit, const int64_t *index_power,
+                             const double *power, const double *row_duration, int64_t n_rows, double fill_factor,
+                             const double *root, int64_t n_root, int64_t max_epochs, tls_transit_stats *out_stats,
+                             double *out_per_transit, int64_t *out_n_epochs, const double *curve_t, const double *curve_f,
+                             int64_t curve_n, double curve_lo, double curve_hi, double maxw, int64_t lc_cap,
+                             double *out_folded, double *out_model_folded, double *out_lc, int64_t *out_lc_len);
 /* developer/test entry: the post-search chain of tls_power_batch -- spectra, pick, trial epochs and scaled template, final
  * T0 fit, first minimum, the same code -- on search results the caller supplies: chi2 / row / depth [n_curves][n_periods]
  * and flux y [n_curves][n] of light curves on the prepared plan (tls_prepare: time stamps, periods, template and

@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtls_amd.so")
 if os.environ.get("TLS_AMD_DEBUG") == "1" and os.environ.get("TLS_AMD_LIB"):
     LIB_PATH = os.environ["TLS_AMD_LIB"]
-ABI_VERSION = 6   # include/tls_amd.h TLS_AMD_ABI_VERSION: checked against the library at load time
+ABI_VERSION = 7   # include/tls_amd.h TLS_AMD_ABI_VERSION: checked against the library at load time
 
 # every symbol include/tls_amd.h declares (tests check the export list against the header)
 SYMBOLS = (
@@ -25,6 +25,7 @@ SYMBOLS = (
     "tls_device_name", "tls_get_options", "tls_set_options", "tls_debug_set_switch", "tls_debug_get_switches", "tls_search", "tls_search_batch", "tls_power_batch", "tls_prepare", "tls_update_flux", "tls_execute",
     "tls_synchronize", "tls_fetch", "tls_execute_timed", "tls_plan_info", "tls_last_kernel", "tls_grid_cells", "tls_period_costs", "tls_t0_fit", "tls_pink_noise", "tls_spectra", "tls_kernel_timing", "tls_debug_phase_cycles", "tls_debug_cumsum", "tls_debug_folded", "tls_debug_prefix", "tls_debug_check_counts", "tls_debug_poison_lds", "tls_debug_period_cycles", "tls_debug_batch_group_ms",
     "tls_debug_post_search", "tls_debug_device_bytes", "tls_power_batch_stats", "tls_debug_transit_stats",
+    "tls_power_batch_models", "tls_debug_transit_models",
     "tls_comm_unique_id", "tls_comm_init", "tls_comm_destroy", "tls_comm_info", "tls_comm_allgather_results", "tls_comm_allgather_device", "tls_comm_fetch_gathered",
     "tls_comm_stage_results", "tls_comm_allgather_staged", "tls_comm_fetch_staged",
     "tls_comm_barrier", "tls_comm_max",
@@ -93,6 +94,28 @@ TRANSIT_STATS_DTYPE = numpy.dtype([(k, "f8") for k in TRANSIT_STATS_FIELDS])
 # rows of the per-transit output [n_curves][6][max_epochs]
 PER_TRANSIT_FIELDS = ("transit_times", "per_transit_count", "transit_depths", "transit_depths_uncertainties",
                       "snr_per_transit", "snr_pink_per_transit")
+# rows of the folded output [n_curves][3][n] and of the model light curve output [n_curves][2][lc_cap]
+FOLDED_FIELDS = ("folded_phase", "folded_y", "order")
+LIGHTCURVE_FIELDS = ("model_lightcurve_time", "model_lightcurve_model")
+
+
+class ModelTemplate(object):
+    """What tls_power_batch_models needs of the template shape: the in-transit slice of the supersampled curve
+    (template.py:52-53) and the ends of reference_transit's linspace; maxw = int(max(durations) * n) (api.py:140)."""
+
+    def __init__(self, curve_t, curve_f, lo, hi, maxw):
+        self.curve_t, self.curve_f = _f8(curve_t), _f8(curve_f)
+        self.lo, self.hi, self.maxw = float(lo), float(hi), float(maxw)
+
+    def args(self, lc_cap, out):
+        folded, model, lc, lc_len = out
+        return [_dp(self.curve_t), _dp(self.curve_f), len(self.curve_t), self.lo, self.hi, self.maxw, int(lc_cap),
+                _dp(folded), _dp(model), _dp(lc), _ip(lc_len)]
+
+
+def _model_outputs(n_c, n, lc_cap):
+    return (numpy.empty((n_c, len(FOLDED_FIELDS), n)), numpy.empty((n_c, n)),
+            numpy.empty((n_c, len(LIGHTCURVE_FIELDS), int(lc_cap))), numpy.empty(n_c, dtype=numpy.int64))
 
 
 class Counters(ctypes.Structure):
@@ -204,6 +227,11 @@ def load():
     lib.tls_debug_transit_stats.argtypes = [vp, _c_double_p, i64, _c_double_p, _c_double_p, _c_int64_p, _c_double_p, _c_int64_p,
                                             _c_int64_p, _c_double_p, _c_double_p, i64, dbl, _c_double_p, i64, i64, ctypes.c_void_p,
                                             _c_double_p, _c_int64_p]
+    models = [_c_double_p, _c_double_p, i64, dbl, dbl, dbl, i64, _c_double_p, _c_double_p, _c_double_p, _c_int64_p]
+    lib.tls_power_batch_models.restype = ci
+    lib.tls_power_batch_models.argtypes = lib.tls_power_batch_stats.argtypes + models
+    lib.tls_debug_transit_models.restype = ci
+    lib.tls_debug_transit_models.argtypes = lib.tls_debug_transit_stats.argtypes + models
     lib.tls_debug_device_bytes.restype = ci
     lib.tls_debug_device_bytes.argtypes = [vp, _c_int64_p, _c_int64_p]
     lib.tls_debug_cumsum.restype = ci
@@ -411,10 +439,12 @@ class Context(object):
         return summary, chi2, row, depth, power
 
     def power_batch_stats(self, t, y_batch, dy_batch, periods, table, params, median_kernel, fill_factor, root, max_epochs,
-                          per_transit=False, with_arrays=False):
+                          per_transit=False, with_arrays=False, with_spectra=False, models=None, lc_cap=0):
         """power_batch plus the per-transit statistics of every light curve (tls_power_batch_stats): (summary, stats
         (TRANSIT_STATS_DTYPE), per_transit [n_curves, 6, max_epochs] or None, n_epochs or None, chi2, row, depth, power).
-        table.duration is the fractional duration of every template row; root[k] = float(k) ** 0.5, k = 0 .. len(t)."""
+        table.duration is the fractional duration of every template row; root[k] = float(k) ** 0.5, k = 0 .. len(t).
+        with_spectra: SR and power_raw [n_curves, n_periods] follow.  models (a ModelTemplate): tls_power_batch_models, and
+        (folded [n_curves, 3, n], model_folded [n_curves, n], lightcurve [n_curves, 2, lc_cap], lc_len [n_curves]) follow."""
         t, periods = _f8(t), _f8(periods)
         y_batch = numpy.ascontiguousarray(y_batch, dtype=numpy.float64)
         dy_batch = numpy.ascontiguousarray(dy_batch, dtype=numpy.float64)
@@ -428,20 +458,32 @@ class Context(object):
         assert stats.dtype.itemsize == ctypes.sizeof(TransitStats)
         rows = numpy.empty((n_c, len(PER_TRANSIT_FIELDS), max_epochs)) if per_transit else None
         n_epochs = numpy.empty(n_c, dtype=numpy.int64) if per_transit else None
-        chi2 = row = depth = power = None
+        chi2 = row = depth = power = SR = power_raw = None
         if with_arrays:
             chi2, depth, power = (numpy.empty((n_c, n_p)) for _ in range(3))
             row = numpy.empty((n_c, n_p), dtype=numpy.int64)
+        if with_spectra:
+            SR, power_raw = numpy.empty((n_c, n_p)), numpy.empty((n_c, n_p))
+        args = [self._h, _dp(t), _dp(y_batch), _dp(dy_batch), len(t), n_c, _dp(periods), n_p, ctypes.byref(tm),
+                ctypes.byref(pr), int(median_kernel), summary.ctypes.data_as(ctypes.c_void_p),
+                None if chi2 is None else _dp(chi2), None if row is None else _ip(row),
+                None if depth is None else _dp(depth), None if power is None else _dp(power),
+                None if SR is None else _dp(SR), None if power_raw is None else _dp(power_raw),
+                _dp(row_duration), float(fill_factor), _dp(root), len(root), stats.ctypes.data_as(ctypes.c_void_p), max_epochs,
+                None if rows is None else _dp(rows), None if n_epochs is None else _ip(n_epochs)]
         self._invalidate_results()
-        self._check(self._lib.tls_power_batch_stats(
-            self._h, _dp(t), _dp(y_batch), _dp(dy_batch), len(t), n_c, _dp(periods), n_p, ctypes.byref(tm),
-            ctypes.byref(pr), int(median_kernel), summary.ctypes.data_as(ctypes.c_void_p),
-            None if chi2 is None else _dp(chi2), None if row is None else _ip(row),
-            None if depth is None else _dp(depth), None if power is None else _dp(power), None, None,
-            _dp(row_duration), float(fill_factor), _dp(root), len(root), stats.ctypes.data_as(ctypes.c_void_p), max_epochs,
-            None if rows is None else _dp(rows), None if n_epochs is None else _ip(n_epochs)))
+        if models is None:
+            self._check(self._lib.tls_power_batch_stats(*args))
+        else:
+            out = _model_outputs(n_c, len(t), lc_cap)
+            self._check(self._lib.tls_power_batch_models(*(args + models.args(lc_cap, out))))
         self._n_periods = n_p
-        return summary, stats, rows, n_epochs, chi2, row, depth, power
+        result = (summary, stats, rows, n_epochs, chi2, row, depth, power)
+        if with_spectra:
+            result += (SR, power_raw)
+        if models is not None:
+            result += out
+        return result
 
     def debug_transit_stats(self, y_batch, period, T0, best_row, depth, no_fit, index_power, power, row_duration,
                             fill_factor, root, max_epochs):
@@ -465,6 +507,29 @@ class Context(object):
             _dp(power), _dp(row_duration), len(row_duration), float(fill_factor), _dp(root), len(root), max_epochs,
             stats.ctypes.data_as(ctypes.c_void_p), _dp(rows), _ip(n_epochs)))
         return stats, rows, n_epochs
+
+    def debug_transit_models(self, y_batch, period, T0, best_row, depth, no_fit, index_power, power, row_duration,
+                             fill_factor, root, max_epochs, models, lc_cap):
+        """Developer/test entry: the statistics and model stages of power_batch_stats(models=...) on injected picks, as
+        debug_transit_stats; (stats, per_transit, n_epochs, folded, model_folded, lightcurve, lc_len)."""
+        y_batch = numpy.ascontiguousarray(y_batch, dtype=numpy.float64)
+        power = numpy.ascontiguousarray(power, dtype=numpy.float64)
+        n_c = len(y_batch)
+        if y_batch.ndim != 2 or power.shape != (n_c, self._n_periods):
+            raise ValueError("power must have shape [n_curves, n_periods] of the prepared plan, y_batch [n_curves, n]")
+        period, T0, depth = (_f8(numpy.broadcast_to(v, (n_c,))) for v in (period, T0, depth))
+        best_row, no_fit, index_power = (_i8(numpy.broadcast_to(v, (n_c,))) for v in (best_row, no_fit, index_power))
+        row_duration, root, max_epochs = _f8(row_duration), _f8(root), int(max_epochs)
+        stats = numpy.zeros(n_c, dtype=TRANSIT_STATS_DTYPE)
+        rows = numpy.empty((n_c, len(PER_TRANSIT_FIELDS), max_epochs))
+        n_epochs = numpy.empty(n_c, dtype=numpy.int64)
+        out = _model_outputs(n_c, y_batch.shape[1], lc_cap)
+        self._invalidate_results()
+        self._check(self._lib.tls_debug_transit_models(
+            self._h, _dp(y_batch), n_c, _dp(period), _dp(T0), _ip(best_row), _dp(depth), _ip(no_fit), _ip(index_power),
+            _dp(power), _dp(row_duration), len(row_duration), float(fill_factor), _dp(root), len(root), max_epochs,
+            stats.ctypes.data_as(ctypes.c_void_p), _dp(rows), _ip(n_epochs), *models.args(lc_cap, out)))
+        return (stats, rows, n_epochs) + out
 
     def _invalidate_results(self):
         """Every call that launches a search, replaces its inputs or reuses the result buffers: the chi2 array an

@@ -231,6 +231,7 @@ struct tls_ctx {
     DevBuf<double> d_spec;                                         // SDE spectra: SR | power_raw | power | sde[2] | chi2 copy
     DevBuf<double> d_tstats;        // tls_power_batch_stats: row durations | root table | per-curve scratch of one group
     DevBuf<int> d_tranges;          // ... and every epoch's chunk start | stop | offset
+    DevBuf<double> d_models;        // tls_power_batch_models: template curve | per-curve scratch of one group | results of one group
     size_t list_stride = 0;
     // two-kernel slab path (series in HBM, one light curve): fold kernel + search kernel per batch of periods
     bool split = false;                      // the plan supports it (enqueue uses it for single-curve launches)
@@ -1205,6 +1206,106 @@ int check_stats_request(tls_ctx* ctx, const StatsRequest& sr, const double* t, i
     return TLS_OK;
 }
 
+// ---- the plotted arrays of power() (tls_power_batch_models; tls_debug_transit_models feeds it injected picks): behind the
+// statistics stage, whose transit times and epoch counts it reads
+struct ModelsRequest {
+    const double* curve_t = nullptr; const double* curve_f = nullptr; int64_t curve_n = 0;   // in-transit supersampled curve
+    double curve_lo = 0, curve_hi = 0, maxw = 0;
+    int64_t lc_cap = 0;                                          // entries of a model light curve row
+    double* out_folded = nullptr; double* out_model_folded = nullptr; double* out_lc = nullptr; int64_t* out_lc_len = nullptr;
+    size_t stride(int64_t n) const { return (size_t)tlsdev::kModelsHeader + 4 * (size_t)n + 2 * (size_t)lc_cap; }
+};
+
+struct ModelsBufs { double *curve = nullptr, *scratch = nullptr, *out = nullptr; size_t scratch_stride = 0, out_stride = 0; bool resident = false; int nb = 0; size_t lds = 0; };
+
+int check_models_request(tls_ctx* ctx, const ModelsRequest& mr, int64_t n) {
+    if (!mr.curve_t || !mr.curve_f || !mr.out_folded || !mr.out_model_folded || !mr.out_lc || !mr.out_lc_len)
+        return fail(ctx, TLS_E_ARG, "null model argument");
+    if (mr.curve_n < 2 || mr.curve_n > 100000000) return fail(ctx, TLS_E_ARG, "the template curve needs at least two samples");
+    for (int64_t i = 1; i < mr.curve_n; ++i)
+        if (!(mr.curve_t[i] > mr.curve_t[i - 1])) return fail(ctx, TLS_E_ARG, "the template curve's time stamps must ascend");
+    if (mr.lc_cap < 1 || mr.lc_cap > 16 * n + 64) return fail(ctx, TLS_E_ARG, "lc_cap out of range [1, 16 n + 64]");
+    if (!(mr.maxw >= 1.0) || n > 100000000) return fail(ctx, TLS_E_ARG, "maxw must be at least 1, n at most 1e8");
+    return TLS_OK;
+}
+
+// the template curve (uploaded once per call), the O(group x n) scratch and results of one group, and the launch shape
+int reserve_transit_models(tls_ctx* ctx, const ModelsRequest& mr, int64_t group, int64_t n, ModelsBufs& mb) {
+    const size_t hdr = 272, resident_bytes = hdr + 16 * (size_t)n;   // (tls_t0fit_kernel's layout)
+    mb.resident = resident_bytes <= kLdsPerCU && n <= 65535;
+    mb.nb = mb.resident ? (int)n : (int)std::min<int64_t>(n, 16384);
+    mb.lds = mb.resident ? resident_bytes : hdr + 4 * (size_t)mb.nb;
+    mb.scratch_stride = (mb.resident ? 0 : 3 * (size_t)n) + 2 * (size_t)tlsdev::kModelsOversample * (size_t)n;
+    mb.out_stride = mr.stride(n);
+    const size_t g = (size_t)group, curve = 2 * (size_t)mr.curve_n;
+    TLS_HIP(ctx, ctx->d_models.reserve(curve + g * mb.scratch_stride + g * mb.out_stride));
+    mb.curve = ctx->d_models.ptr; mb.scratch = mb.curve + curve; mb.out = mb.scratch + g * mb.scratch_stride;
+    TLS_HIP(ctx, hipMemcpyAsync(mb.curve, mr.curve_t, (size_t)mr.curve_n * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(mb.curve + mr.curve_n, mr.curve_f, (size_t)mr.curve_n * 8, hipMemcpyHostToDevice, ctx->stream));
+    return TLS_OK;
+}
+
+// the arrays of `gc` curves from the chain's pick and T0 and the statistics stage's epochs, nothing waited for
+int enqueue_transit_models(tls_ctx* ctx, const PostSearchBufs& b, const StatsBufs& sb, const StatsRequest& sr,
+                           const ModelsRequest& mr, const ModelsBufs& mb, int64_t gc, const double* d_y, int64_t n,
+                           double t_min, double t_max) {
+    tlsdev::ModelsArgs a;
+    a.t = ctx->d_t.ptr; a.y = d_y; a.pick = b.pick; a.T0 = b.T0;
+    a.stats = b.stats; a.per_transit = b.stats + (size_t)tlsdev::kTransitStats * (size_t)b.group; a.max_epochs = (int)sr.max_epochs;
+    a.row_duration = sb.row_duration;
+    a.curve_t = mb.curve; a.curve_f = mb.curve + mr.curve_n; a.curve_n = (int)mr.curve_n;
+    a.curve_lo = mr.curve_lo; a.curve_hi = mr.curve_hi;
+    a.fill_factor = sr.fill_factor; a.t_min = t_min; a.t_max = t_max; a.maxw = mr.maxw;
+    a.out = mb.out; a.out_stride = (long long)mb.out_stride; a.lc_cap = mr.lc_cap;
+    a.scratch = mb.scratch; a.scratch_stride = (long long)mb.scratch_stride;
+    a.n = (int)n; a.nb = mb.nb;
+    hipError_t e;
+    if (mb.resident) {
+        auto kernel = tlsdev::tls_transit_models<true, unsigned short>;
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mb.lds);
+        if (e == hipSuccess) { hipLaunchKernelGGL(kernel, dim3((unsigned)gc), dim3(512), mb.lds, ctx->stream, a); e = hipGetLastError(); }
+    } else {
+        auto kernel = tlsdev::tls_transit_models<false, unsigned int>;
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mb.lds);
+        if (e == hipSuccess) { hipLaunchKernelGGL(kernel, dim3((unsigned)gc), dim3(512), mb.lds, ctx->stream, a); e = hipGetLastError(); }
+    }
+    if (e != hipSuccess) return fail(ctx, TLS_E_HIP, std::string("model launch: ") + hipGetErrorString(e));
+    return TLS_OK;
+}
+
+// curve c's arrays from the group's host copy (h: `stride` doubles a curve) into the caller's rows; NaN past the model light
+// curve's length and in every row of a curve without a fit
+int read_transit_models(tls_ctx* ctx, const ModelsRequest& mr, const double* h, size_t stride, int64_t c, int64_t curve,
+                        int64_t n) {
+    const double* rec = h + stride * (size_t)c;
+    const size_t nn = (size_t)n, cap = (size_t)mr.lc_cap;
+    double* folded = mr.out_folded + 3 * nn * (size_t)curve;
+    double* model = mr.out_model_folded + nn * (size_t)curve;
+    double* lc = mr.out_lc + 2 * cap * (size_t)curve;
+    const double code = rec[0];
+    if (code == tlsdev::kModelsRaises)
+        return fail(ctx, TLS_E_ARG, "light curve " + std::to_string((long long)curve) + ": power() raises for its model (" +
+                                    std::to_string((long long)rec[1]) + " model samples, or a transit wider than the window)");
+    if (code == tlsdev::kModelsTooLong)
+        return fail(ctx, TLS_E_ARG, "light curve " + std::to_string((long long)curve) + ": model light curve longer than lc_cap = " +
+                                    std::to_string((long long)mr.lc_cap));
+    if (code < 0) {
+        std::fill(folded, folded + 3 * nn, std::nan("")); std::fill(model, model + nn, std::nan(""));
+        std::fill(lc, lc + 2 * cap, std::nan(""));
+        mr.out_lc_len[curve] = 0;
+        return TLS_OK;
+    }
+    const size_t len = (size_t)code;
+    std::memcpy(folded, rec + tlsdev::kModelsHeader, 3 * nn * 8);
+    std::memcpy(model, rec + tlsdev::kModelsHeader + 3 * nn, nn * 8);
+    for (int r = 0; r < 2; ++r) {
+        std::memcpy(lc + r * cap, rec + tlsdev::kModelsHeader + 4 * nn + r * cap, len * 8);
+        std::fill(lc + r * cap + len, lc + (r + 1) * cap, std::nan(""));
+    }
+    mr.out_lc_len[curve] = (int64_t)len;
+    return TLS_OK;
+}
+
 // the summary of curve c from the chain's results on the host (sde | pick | T0 of `group` curves, as reserve_post_search
 // lays them out); TLS_E_ARG when tls_power_prep found no template width starting at the picked row
 int read_summary(tls_ctx* ctx, const double* h_sde, int64_t group, int64_t c, int64_t curve, tls_power_summary& os) {
@@ -1347,7 +1448,7 @@ void tls_ctx_destroy(tls_ctx* ctx) {
     ctx->d_gather.release(); ctx->d_scalar.release(); ctx->d_stage.release();
     ctx->d_partials.release(); ctx->d_tiles_done.release(); ctx->d_check.release(); ctx->d_spec.release(); ctx->d_queue.release(); ctx->d_squeue.release(); ctx->d_pqueues.release(); ctx->d_phase.release(); ctx->d_lists.release(); ctx->d_perm.release(); ctx->d_curve_S0.release(); ctx->d_curve_w0.release();
     ctx->d_ft.release(); ctx->d_fy.release(); ctx->d_fsig.release(); ctx->d_fep.release(); ctx->d_fres.release(); ctx->d_fscratch.release(); ctx->d_frot.release(); ctx->d_frperm.release(); ctx->d_pink.release();
-    ctx->d_tstats.release(); ctx->d_tranges.release();
+    ctx->d_tstats.release(); ctx->d_tranges.release(); ctx->d_models.release();
     ctx->d_split.release(); ctx->d_park.release(); ctx->d_band.release();
     if (ctx->h_band) (void)hipHostFree(ctx->h_band);
     for (auto& ev : ctx->ev_band) if (ev) (void)hipEventDestroy(ev);
@@ -2128,11 +2229,12 @@ int tls_debug_post_search(tls_ctx* ctx, const double* y, int64_t n_curves, const
     return TLS_OK;
 }
 
-int tls_debug_transit_stats(tls_ctx* ctx, const double* y, int64_t n_curves, const double* period, const double* T0,
-                            const int64_t* best_row, const double* depth, const int64_t* no_fit, const int64_t* index_power,
-                            const double* power, const double* row_duration, int64_t n_rows, double fill_factor,
-                            const double* root, int64_t n_root, int64_t max_epochs, tls_transit_stats* out_stats,
-                            double* out_per_transit, int64_t* out_n_epochs) {
+// tls_debug_transit_stats, and with `mr` tls_debug_transit_models: the statistics stage (then the models) on injected picks
+static int debug_transit_impl(tls_ctx* ctx, const double* y, int64_t n_curves, const double* period, const double* T0,
+                              const int64_t* best_row, const double* depth, const int64_t* no_fit, const int64_t* index_power,
+                              const double* power, const double* row_duration, int64_t n_rows, double fill_factor,
+                              const double* root, int64_t n_root, int64_t max_epochs, tls_transit_stats* out_stats,
+                              double* out_per_transit, int64_t* out_n_epochs, const ModelsRequest* mr) {
     if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
     if (!ctx->prepared || !ctx->key.valid) return fail(ctx, TLS_E_STATE, "tls_debug_transit_stats before tls_prepare");
     if (!y || !period || !T0 || !best_row || !depth || !no_fit || !index_power || !power) return fail(ctx, TLS_E_ARG, "null argument");
@@ -2145,7 +2247,7 @@ int tls_debug_transit_stats(tls_ctx* ctx, const double* y, int64_t n_curves, con
     sr.row_duration = row_duration; sr.n_rows = n_rows; sr.fill_factor = fill_factor; sr.root = root; sr.n_root = n_root;
     sr.max_epochs = max_epochs; sr.out = out_stats; sr.out_per_transit = out_per_transit; sr.out_n_epochs = out_n_epochs;
     int rc = check_stats_request(ctx, sr, k.t.data(), n, k.n_rows);
-    if (rc) return rc;
+    if (rc || (mr && (rc = check_models_request(ctx, *mr, n)))) return rc;
     const size_t np = (size_t)n_periods, nn = (size_t)n, gc = (size_t)n_curves;
     for (size_t c = 0; c < gc; ++c) {
         if (index_power[c] < 0 || index_power[c] >= n_periods) return fail(ctx, TLS_E_ARG, "index_power out of range");
@@ -2158,6 +2260,8 @@ int tls_debug_transit_stats(tls_ctx* ctx, const double* y, int64_t n_curves, con
     if ((rc = reserve_post_search(ctx, n_curves, n_periods, n, 1, pb, sr.words()))) return rc;
     StatsBufs sb;
     if ((rc = reserve_transit_stats(ctx, sr, n_curves, n, sb))) return rc;
+    ModelsBufs mb;
+    if (mr && (rc = reserve_transit_models(ctx, *mr, n_curves, n, mb))) return rc;
     // the pick record of tls_power_pick ([2] index_power, [3] period, [4] depth, [5] best_row, [6] no_fit) and T0
     std::vector<double> pick(8 * gc + gc, 0.0);
     for (size_t c = 0; c < gc; ++c) {
@@ -2173,13 +2277,45 @@ int tls_debug_transit_stats(tls_ctx* ctx, const double* y, int64_t n_curves, con
         (void)hipStreamSynchronize(ctx->stream);
         return rc;
     }
-    std::vector<double> h(gc * sr.words());
+    if (mr && (rc = enqueue_transit_models(ctx, pb, sb, sr, *mr, mb, n_curves, sl.d_y.ptr, n, t_min, t_max))) {
+        (void)hipStreamSynchronize(ctx->stream);
+        return rc;
+    }
+    std::vector<double> h(gc * sr.words()), hm(mr ? gc * mb.out_stride : 0);
     TLS_HIP(ctx, hipMemcpyAsync(h.data(), pb.stats, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (mr) TLS_HIP(ctx, hipMemcpyAsync(hm.data(), mb.out, hm.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
     TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->executed = false;   // (the batch slot's buffers were written: as after tls_power_batch)
     for (int64_t c = 0; c < n_curves; ++c)
         if ((rc = read_transit_stats(ctx, sr, h.data(), n_curves, c, c, true))) return rc;
+    if (mr)
+        for (int64_t c = 0; c < n_curves; ++c)
+            if ((rc = read_transit_models(ctx, *mr, hm.data(), mb.out_stride, c, c, n))) return rc;
     return TLS_OK;
+}
+
+int tls_debug_transit_stats(tls_ctx* ctx, const double* y, int64_t n_curves, const double* period, const double* T0,
+                            const int64_t* best_row, const double* depth, const int64_t* no_fit, const int64_t* index_power,
+                            const double* power, const double* row_duration, int64_t n_rows, double fill_factor,
+                            const double* root, int64_t n_root, int64_t max_epochs, tls_transit_stats* out_stats,
+                            double* out_per_transit, int64_t* out_n_epochs) {
+    return debug_transit_impl(ctx, y, n_curves, period, T0, best_row, depth, no_fit, index_power, power, row_duration, n_rows,
+                              fill_factor, root, n_root, max_epochs, out_stats, out_per_transit, out_n_epochs, nullptr);
+}
+
+int tls_debug_transit_models(tls_ctx* ctx, const double* y, int64_t n_curves, const double* period, const double* T0,
+                             const int64_t* best_row, const double* depth, const int64_t* no_fit, const int64_t* index_power,
+                             const double* power, const double* row_duration, int64_t n_rows, double fill_factor,
+                             const double* root, int64_t n_root, int64_t max_epochs, tls_transit_stats* out_stats,
+                             double* out_per_transit, int64_t* out_n_epochs, const double* curve_t, const double* curve_f,
+                             int64_t curve_n, double curve_lo, double curve_hi, double maxw, int64_t lc_cap,
+                             double* out_folded, double* out_model_folded, double* out_lc, int64_t* out_lc_len) {
+    ModelsRequest mr;
+    mr.curve_t = curve_t; mr.curve_f = curve_f; mr.curve_n = curve_n; mr.curve_lo = curve_lo; mr.curve_hi = curve_hi;
+    mr.maxw = maxw; mr.lc_cap = lc_cap;
+    mr.out_folded = out_folded; mr.out_model_folded = out_model_folded; mr.out_lc = out_lc; mr.out_lc_len = out_lc_len;
+    return debug_transit_impl(ctx, y, n_curves, period, T0, best_row, depth, no_fit, index_power, power, row_duration, n_rows,
+                              fill_factor, root, n_root, max_epochs, out_stats, out_per_transit, out_n_epochs, &mr);
 }
 
 int tls_debug_device_bytes(const tls_ctx* ctx, int64_t* total, int64_t* t0_fit_scratch) {
@@ -2195,7 +2331,7 @@ int tls_debug_device_bytes(const tls_ctx* ctx, int64_t* total, int64_t* t0_fit_s
         add(sl.d_y); add(sl.d_w); add(sl.d_S0); add(sl.d_w0); add(sl.d_chi2); add(sl.d_depth); add(sl.d_row);
     }
     add(ctx->d_ft); add(ctx->d_fy); add(ctx->d_fsig); add(ctx->d_fep); add(ctx->d_fres); add(ctx->d_fscratch);
-    add(ctx->d_pink); add(ctx->d_frot); add(ctx->d_frperm); add(ctx->d_spec); add(ctx->d_tstats); add(ctx->d_tranges);
+    add(ctx->d_pink); add(ctx->d_frot); add(ctx->d_frperm); add(ctx->d_spec); add(ctx->d_tstats); add(ctx->d_tranges); add(ctx->d_models);
     add(ctx->d_partials); add(ctx->d_tiles_done);
     add(ctx->d_split); add(ctx->d_park); add(ctx->d_band);
     *total = (int64_t)sum;
@@ -2461,7 +2597,7 @@ static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, cons
                             const double* periods, int64_t n_periods, const tls_template* tmpl, const tls_params* params,
                             int64_t median_kernel, tls_power_summary* out_summary, double* out_chi2, int64_t* out_row,
                             double* out_depth, double* out_power, double* out_SR, double* out_power_raw,
-                            const StatsRequest* sr);
+                            const StatsRequest* sr, const ModelsRequest* mr = nullptr);
 
 static int power_batch_finish(tls_ctx* ctx, int rc);
 
@@ -2490,6 +2626,31 @@ int tls_power_batch_stats(tls_ctx* ctx, const double* t, const double* y, const 
                                                     out_summary, out_chi2, out_row, out_depth, out_power, out_SR, out_power_raw, &sr));
 }
 
+int tls_power_batch_models(tls_ctx* ctx, const double* t, const double* y, const double* dy, int64_t n, int64_t n_curves,
+                           const double* periods, int64_t n_periods, const tls_template* tmpl, const tls_params* params,
+                           int64_t median_kernel, tls_power_summary* out_summary, double* out_chi2, int64_t* out_row,
+                           double* out_depth, double* out_power, double* out_SR, double* out_power_raw,
+                           const double* row_duration, double fill_factor, const double* root, int64_t n_root,
+                           tls_transit_stats* out_stats, int64_t max_epochs, double* out_per_transit, int64_t* out_n_epochs,
+                           const double* curve_t, const double* curve_f, int64_t curve_n, double curve_lo, double curve_hi,
+                           double maxw, int64_t lc_cap, double* out_folded, double* out_model_folded, double* out_lc,
+                           int64_t* out_lc_len) {
+    if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
+    if (!t || !tmpl) return fail(ctx, TLS_E_ARG, "null argument");
+    StatsRequest sr;
+    sr.row_duration = row_duration; sr.n_rows = tmpl->n_rows; sr.fill_factor = fill_factor; sr.root = root; sr.n_root = n_root;
+    sr.max_epochs = max_epochs; sr.out = out_stats; sr.out_per_transit = out_per_transit; sr.out_n_epochs = out_n_epochs;
+    ModelsRequest mr;
+    mr.curve_t = curve_t; mr.curve_f = curve_f; mr.curve_n = curve_n; mr.curve_lo = curve_lo; mr.curve_hi = curve_hi;
+    mr.maxw = maxw; mr.lc_cap = lc_cap;
+    mr.out_folded = out_folded; mr.out_model_folded = out_model_folded; mr.out_lc = out_lc; mr.out_lc_len = out_lc_len;
+    int rc = check_stats_request(ctx, sr, t, n, tmpl->n_rows);
+    if (rc || (rc = check_models_request(ctx, mr, n))) return rc;
+    return power_batch_finish(ctx, power_batch_impl(ctx, t, y, dy, n, n_curves, periods, n_periods, tmpl, params, median_kernel,
+                                                    out_summary, out_chi2, out_row, out_depth, out_power, out_SR, out_power_raw,
+                                                    &sr, &mr));
+}
+
 static int power_batch_finish(tls_ctx* ctx, int rc) {
     if (ctx && rc != TLS_OK) {
         // EVERY failure leaves through here: nothing is still copying into or out of the pinned staging buffers or the
@@ -2508,7 +2669,7 @@ static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, cons
                             const double* periods, int64_t n_periods, const tls_template* tmpl, const tls_params* params,
                             int64_t median_kernel, tls_power_summary* out_summary, double* out_chi2, int64_t* out_row,
                             double* out_depth, double* out_power, double* out_SR, double* out_power_raw,
-                            const StatsRequest* sr) {
+                            const StatsRequest* sr, const ModelsRequest* mr) {
     if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
     if (n_curves < 0) return fail(ctx, TLS_E_ARG, "negative number of light curves");
     if (n_curves == 0) return TLS_OK;
@@ -2543,12 +2704,16 @@ static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, cons
     StatsBufs sb;
     if (sr && (rc = reserve_transit_stats(ctx, *sr, group, n, sb))) return rc;
     const size_t stats_out = !sr ? 0 : sr->out_per_transit ? sr->words() : (size_t)tlsdev::kTransitStats;
+    // (models requested: the folded light curve, the folded model and the padded model light curve of every curve, behind them)
+    ModelsBufs mb;
+    if (mr && (rc = reserve_transit_models(ctx, *mr, group, n, mb))) return rc;
+    const size_t models_out = mr ? mb.out_stride : 0;
     // pinned staging: flux in; summaries, T0 and (on request) the per-period arrays out.  TWO sets (the device buffers are
     // one: the stream runs the groups in order): while the device works on group g the host forms group g + 1 in the other
     // set and enqueues it, THEN waits for g -- the device never waits for the host between two groups (round 6)
     const size_t in_doubles = (size_t)group * nn * (uni ? 1 : 2) + 2 * (size_t)group;
     const size_t arrays = (out_chi2 ? 3 : 0) + (out_power ? 1 : 0) + (out_SR ? 1 : 0) + (out_power_raw ? 1 : 0);
-    const size_t out_doubles = (11 + stats_out) * (size_t)group + arrays * (size_t)group * np;
+    const size_t out_doubles = (11 + stats_out + models_out) * (size_t)group + arrays * (size_t)group * np;
     for (auto& hs : ctx->slot) {
         if (!hs.ev_out) {
             TLS_HIP(ctx, hipEventCreateWithFlags(&hs.ev_in, hipEventDisableTiming));
@@ -2602,7 +2767,7 @@ static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, cons
         return TLS_OK;
     };
     // host layout of a group's results (the same in both sets)
-    struct OutLayout { double *sde, *pick, *T0, *stats, *chi2, *power, *SR, *praw, *spec3; };
+    struct OutLayout { double *sde, *pick, *T0, *stats, *chi2, *power, *SR, *praw, *spec3, *models; };
     auto out_layout = [&](int64_t g) -> OutLayout {
         OutLayout o{};
         double* base = ctx->slot[g & 1].h_out;
@@ -2616,6 +2781,7 @@ static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, cons
             if (out_SR) { o.SR = h_next; h_next += (size_t)group * np; }
             if (out_power_raw) { o.praw = h_next; h_next += (size_t)group * np; }
         }
+        if (mr) o.models = h_next;                       // the models' rows, on request
         return o;
     };
     // ---- device side of group g, nothing waited for: flux up, search (tls_search_batch's launch: fold + sort shared by the
@@ -2654,6 +2820,7 @@ static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, cons
                                   t_min, t_max, params->T0_fit_margin);
         if (rc2) return rc2;
         if (sr && (rc2 = enqueue_transit_stats(ctx, pb, sb, *sr, gc, sl.d_y.ptr, n, n_periods, t_min, t_max))) return rc2;
+        if (mr && (rc2 = enqueue_transit_models(ctx, pb, sb, *sr, *mr, mb, gc, sl.d_y.ptr, n, t_min, t_max))) return rc2;
         // (sde | pick | T0 [| statistics] lie side by side behind the spectra on the device: ONE copy, the host keeps the layout)
         const OutLayout o = out_layout(g);
         TLS_HIP(ctx, hipMemcpyAsync(o.sde, pb.sde, (11 + stats_out) * (size_t)group * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -2670,6 +2837,7 @@ static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, cons
         if (o.power) TLS_HIP(ctx, fetch_spec(o.power, 2));
         if (o.SR) TLS_HIP(ctx, fetch_spec(o.SR, 0));
         if (o.praw) TLS_HIP(ctx, fetch_spec(o.praw, 1));
+        if (o.models) TLS_HIP(ctx, hipMemcpyAsync(o.models, mb.out, (size_t)gc * mb.out_stride * 8, hipMemcpyDeviceToHost, ctx->stream));
         TLS_HIP(ctx, hipEventRecord(hs.ev_out, ctx->stream));
         return TLS_OK;
     };
@@ -2705,6 +2873,11 @@ static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, cons
         if (sr)
             for (int64_t c = 0; c < gc; ++c) {
                 const int rc2 = read_transit_stats(ctx, *sr, o.stats, group, c, c0 + c, true);
+                if (rc2) return rc2;
+            }
+        if (mr)
+            for (int64_t c = 0; c < gc; ++c) {
+                const int rc2 = read_transit_models(ctx, *mr, o.models, mb.out_stride, c, c0 + c, n);
                 if (rc2) return rc2;
             }
         if (out_chi2) {

@@ -4055,4 +4055,199 @@ __global__ void __launch_bounds__(256) tls_transit_stats(const TransitStatsArgs 
     }
 }
 
+
+// ---------------------------------------------------------------------------------------
+// The plotted arrays of power() (api.py:175-203) for one light curve, behind tls_transit_stats (it reads that kernel's
+// transit times and epoch count):
+//   folded light curve   phase = x - floor(x), x = (t - T0') / period, T0' = T0 + period / 2; ascending phase, y gathered,
+//                        the order itself returned (the caller gathers dy with it).  The order is the STABLE one -- equal
+//                        phases by index -- from fold_and_sort, the sort of the T0 fit (LDS-resident series, or HBM scratch
+//                        beyond that); power()'s numpy.argsort leaves the order of equal phases open, for distinct phases the
+//                        two are the same.
+//   model_folded_model   fractional_transit(duration * maxw * fill_half, maxw / stretch, 1 - depth, samples = n)
+//   model_lightcurve     fractional_transit(duration * maxw, maxw / stretch, 1 - depth, samples = int(n / E) * 5) tiled over
+//                        the epochs plus one before and after, the grids numpy.linspace(e - P / 2, e + P / 2, samples), cropped
+//                        to [first x > min t, first x > max t)
+// fractional_transit (template.py:63-80) and reference_transit (template.py:44-60) are restated operation by operation:
+// numpy.linspace as k * step + start with the end point set (step 0: k / div * delta + start), interp1d's bracket
+// (searchsorted(x, z, "right") - 1 clamped to [0, len - 2]) and blend, the exact min.  One workgroup (512 threads) a curve.
+constexpr int kModelsHeader = 2;          // per curve: [0] model light curve length (< 0: no output, see kModels*), [1] samples
+constexpr double kModelsNoFit = -1.0;     // no fit (or no statistics): nothing written
+constexpr double kModelsRaises = -2.0;    // power() raises here (occupied > samples, one sample, no samples)
+constexpr double kModelsTooLong = -3.0;   // the model light curve is longer than the row the caller gave it
+constexpr int kModelsOversample = 5;      // OVERSAMPLE_MODEL_LIGHT_CURVE
+struct ModelsArgs {
+    const double* t; const double* y;             // [n] ascending, [n_curves][n]
+    const double* pick; const double* T0;         // tls_power_pick records, tls_first_min
+    const double* stats; const double* per_transit; int max_epochs;   // tls_transit_stats: records, rows (transit times first)
+    const double* row_duration;                   // lc_cache_overview["duration"] of every template row
+    const double* curve_t; const double* curve_f; int curve_n;   // the in-transit slice of the supersampled template curve
+    double curve_lo, curve_hi;                    // the ends of reference_transit's linspace: t[first], t[-first - 1]
+    double fill_factor, t_min, t_max, maxw;       // maxw = int(max(durations) * n), not rounded up to even
+    double* out; long long out_stride, lc_cap;    // [n_curves][out_stride]: header | phase | y | order | folded model | lc time | lc model
+    double* scratch; long long scratch_stride;    // [n_curves][...]: sort slab (3 n, HBM series) | reference transit | single transit
+    int n, nb;
+};
+
+// numpy.linspace(start, stop, num)[k]
+__device__ __forceinline__ double numpy_linspace_at(long long k, long long num, double start, double stop) {
+#pragma clang fp contract(off)
+    if (num > 1 && k == num - 1) return stop;
+    const double delta = stop - start;
+    double v;
+    if (num > 1) {
+        const double div = (double)(num - 1), step = delta / div;
+        v = step == 0.0 ? ((double)k / div) * delta : (double)k * step;
+    } else {
+        v = (double)k * delta;
+    }
+    return v + start;
+}
+
+// interp1d(z, x)(f) at one z: x ascending, len >= 2; x(i) gives the grid
+template <typename X, typename F>
+__device__ __forceinline__ double interp_at(double z, long long len, const X& x, const F& f) {
+#pragma clang fp contract(off)
+    long long lo = 0, hi = len;   // searchsorted "right": the number of entries <= z
+    while (lo < hi) { const long long m = (lo + hi) >> 1; if (x(m) <= z) lo = m + 1; else hi = m; }
+    long long j = lo - 1;
+    j = j < 0 ? 0 : (j > len - 2 ? len - 2 : j);
+    const double xj = x(j);
+    const double theta = (z - xj) / (x(j + 1) - xj);
+    return (1 - theta) * f(j) + theta * f(j + 1);
+}
+
+// fractional_transit(duration, maxwidth, depth, samples) into dst[samples]; ref: scratch of `samples` doubles for
+// reference_transit(samples).  All threads of the workgroup call it; false (uniform) where the reference raises.
+__device__ bool fractional_transit_dev(const ModelsArgs& a, double duration, double maxwidth, double depth, long long samples,
+                                       double* ref, double* dst, double* wred) {
+#pragma clang fp contract(off)
+    const int tid = threadIdx.x, nt = blockDim.x, lane = tid & (kWave - 1), wave = tid / kWave, nw = nt / kWave;
+    if (samples < 2) return false;   // numpy.min of nothing, interp1d's assert
+    // reference_transit: the in-transit curve at linspace(curve_lo, curve_hi, samples), (lo - down) / (lo - 1)
+    auto ct = [&](long long i) { return a.curve_t[i]; };
+    auto cf = [&](long long i) { return a.curve_f[i]; };
+    double lo = INFINITY;
+    for (long long i = tid; i < samples; i += nt) {
+        const double v = interp_at(numpy_linspace_at(i, samples, a.curve_lo, a.curve_hi), a.curve_n, ct, cf);
+        ref[i] = v;
+        lo = fmin(lo, v);
+    }
+#pragma unroll
+    for (int dlt = kWave / 2; dlt > 0; dlt >>= 1) lo = fmin(lo, __shfl_down(lo, dlt, kWave));
+    if (lane == 0) wred[wave] = lo;
+    wg_sync();
+    lo = wred[0];
+    for (int v = 1; v < nw; ++v) lo = fmin(lo, wred[v]);
+    for (long long i = tid; i < samples; i += nt) ref[i] = (lo - ref[i]) / (lo - 1);
+    wg_sync();
+    const double q = (duration / maxwidth) * (double)samples;
+    if (!(q >= 0.0 && q < (double)(samples + 1))) return false;   // (negative or more than samples: numpy raises)
+    const long long occupied = (long long)q;
+    if (occupied > samples) return false;
+    const long long pad = (long long)((double)(samples - occupied) * 0.5);
+    auto grid = [&](long long k) { return numpy_linspace_at(k, samples, -0.5, 0.5); };
+    auto shape = [&](long long k) { return ref[k]; };
+    for (long long i = tid; i < samples; i += nt) {
+        double r = 1.0;   // the padding, and the one appended on the right when the result is short
+        if (i >= pad && i < pad + occupied)
+            r = interp_at(numpy_linspace_at(i - pad, occupied, -0.5, 0.5), samples, grid, shape);
+        dst[i] = 1 - ((1 - r) * depth);
+    }
+    wg_sync();
+    return true;
+}
+
+template <bool RESIDENT, typename IdxT>
+__global__ void __launch_bounds__(512) tls_transit_models(const ModelsArgs a) {
+#pragma clang fp contract(off)
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int tid = threadIdx.x, nt = blockDim.x, n = a.n;
+    const long long c = blockIdx.x;
+    unsigned int* wsum = reinterpret_cast<unsigned int*>(smem);       // 32 words
+    double* wred = reinterpret_cast<double*>(smem + 128);             // kMaxWaves doubles
+    int* s_work = reinterpret_cast<int*>(smem + 256);
+    constexpr int kHdr = 272;   // (the T0 fit's layout: fold_and_sort sees the same workspace)
+    const double* pk = a.pick + 8 * c;
+    const double* st = a.stats + c * kTransitStats;
+    double* out = a.out + c * a.out_stride;
+    double* o_phase = out + kModelsHeader; double* o_y = o_phase + n; double* o_order = o_y + n; double* o_model = o_order + n;
+    double* o_time = o_model + n; double* o_lc = o_time + a.lc_cap;
+    double* slab = a.scratch + c * a.scratch_stride;
+    double* ref = slab + (RESIDENT ? 0 : 3LL * n);
+    double* single = ref + (long long)kModelsOversample * n;
+    const double E_d = st[10];
+    if (pk[6] != 0.0 || pk[7] != 0.0 || !(E_d >= 1.0 && E_d <= (double)a.max_epochs)) {
+        if (tid == 0) { out[0] = kModelsNoFit; out[1] = 0.0; }
+        return;
+    }
+    const int E = (int)E_d;
+    const double period = pk[3], depth = pk[4], T0 = a.T0[c];
+    // ---- folded light curve: fold(t, period, T0 + period / 2), stable order, y gathered
+    {
+        double* regA; double* regB; unsigned int* cnt;
+        if constexpr (RESIDENT) {
+            regA = reinterpret_cast<double*>(smem + kHdr); regB = regA + n; cnt = reinterpret_cast<unsigned int*>(regB);
+        } else {
+            regA = slab; regB = regA + n; cnt = reinterpret_cast<unsigned int*>(smem + kHdr);
+        }
+        IdxT* idx_tmp = RESIDENT ? reinterpret_cast<IdxT*>(cnt + a.nb) : reinterpret_cast<IdxT*>(regB);
+        IdxT* perm = idx_tmp + n;
+        PhaseClock pc; pc.start(nullptr);
+        fold_and_sort<IdxT>(a.t, n, period, T0 + period / 2, regA, cnt, a.nb, idx_tmp, perm, wsum, pc,
+                            reinterpret_cast<unsigned int*>(wred), 2 * kMaxWaves);
+        const double* y = a.y + c * n;
+        for (int k = tid; k < n; k += nt) {
+            const int i = (int)perm[k];
+            o_phase[k] = regA[i]; o_y[k] = y[i]; o_order[k] = (double)i;
+        }
+        wg_sync();
+    }
+    // ---- the two template models (calculate_stretch with the device's own epoch count)
+    const double duration = a.row_duration[(long long)pk[5]];
+    const double stretch = ((a.t_max - a.t_min) / period) / (double)E;
+    const double fill_half = 1 - ((1 - a.fill_factor) * 0.5);
+    const double maxwidth = a.maxw / stretch;
+    const long long samples = (long long)((double)n / (double)E) * kModelsOversample;
+    bool ok = fractional_transit_dev(a, duration * a.maxw * fill_half, maxwidth, 1 - depth, n, ref, o_model, wred);
+    ok = ok && fractional_transit_dev(a, duration * a.maxw, maxwidth, 1 - depth, samples, ref, single, wred);
+    if (!ok) {
+        if (tid == 0) { out[0] = kModelsRaises; out[1] = (double)samples; }
+        return;
+    }
+    // ---- model_lightcurve: (E + 2) grids of `samples`, the first x above min(t) and the first above max(t)
+    const double* times = a.per_transit + c * (long long)kPerTransitRows * a.max_epochs;
+    const double first_e = times[0] - period, last_e = times[E - 1] + period, half = period / 2;
+    auto x_at = [&](long long i) {
+        const long long j = i / samples, k = i - j * samples;
+        const double e = j == 0 ? first_e : (j == E + 1 ? last_e : times[j - 1]);
+        return numpy_linspace_at(k, samples, e - half, e + half);
+    };
+    const long long total = (long long)(E + 2) * samples;
+    if (tid == 0) { s_work[0] = 0x7fffffff; s_work[1] = 0x7fffffff; }
+    wg_sync();
+    int my_lo = 0x7fffffff, my_hi = 0x7fffffff;
+    for (long long i = tid; i < total; i += nt) {
+        const double x = x_at(i);
+        if (x > a.t_min && (int)i < my_lo) my_lo = (int)i;
+        if (x > a.t_max && (int)i < my_hi) my_hi = (int)i;
+    }
+    if (my_lo != 0x7fffffff) atomicMin(&s_work[0], my_lo);
+    if (my_hi != 0x7fffffff) atomicMin(&s_work[1], my_hi);
+    wg_sync();
+    // (numpy.nanargmax of an all-False mask is 0)
+    const long long start = s_work[0] == 0x7fffffff ? 0 : s_work[0], stop = s_work[1] == 0x7fffffff ? 0 : s_work[1];
+    const long long len = stop > start ? stop - start : 0;
+    if (len > a.lc_cap) {
+        if (tid == 0) { out[0] = kModelsTooLong; out[1] = (double)samples; }
+        return;
+    }
+    for (long long m = tid; m < len; m += nt) {
+        const long long i = start + m;
+        o_time[m] = x_at(i);
+        o_lc[m] = single[i % samples];
+    }
+    if (tid == 0) { out[0] = (double)len; out[1] = (double)samples; }
+}
+
 }  // namespace tlsdev

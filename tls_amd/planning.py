@@ -20,4 +20,6 @@ def search_inputs(t, flux, dy=None, **kwargs):
                   M_star_max=model.M_star_max, T0_fit_margin=model.T0_fit_margin)
     return dict(t=model.t, y=model.y, dy=model.dy, periods=periods_sorted.copy(),
                 table=table, params=params, overview=overview,
-                rows=rows, durations=durations, limb_dark=model.limb_dark, u=model.u)
+                rows=rows, durations=durations, limb_dark=model.limb_dark, u=model.u,
+                shape=dict(per=model.per, rp=model.rp, a=model.a, inc=model.inc, ecc=model.ecc, w=model.w, u=model.u,
+                           limb_dark=model.limb_dark))

@@ -96,8 +96,29 @@ def _fap(sde):
     return fap[idx]
 
 
+def _lc_cap(n, max_epochs):
+    """Entries of a model light curve row that no curve of this grid exceeds.  With E epochs and s = int(n / E) * 5 samples a
+    grid, the crop to (min t, max t] keeps at most (E + 1) s + 1 grid points (the span is at most E + 1 periods, T0 lies in
+    [min t, min t + period]), a few more where rounding makes neighbouring grids overlap; never more than the (E + 2) s of all
+    grids."""
+    from . import constants as C
+    E = numpy.arange(1, max(int(max_epochs), 1) + 1)
+    s = (n / E).astype(numpy.int64) * C.OVERSAMPLE_MODEL_LIGHT_CURVE
+    return max(1, int(numpy.max(numpy.minimum((E + 2) * s, (E + 1) * s + 2 * E + 8))))
+
+
+def _model_template(inp):
+    """_lib.ModelTemplate of the search's template shape: the in-transit slice of the supersampled curve, as
+    template.reference_transit takes it (cached per shape), and maxw = int(max(durations) * n) (api.py:140)."""
+    from ._lib import ModelTemplate
+    from .template import _supersampled_curve
+    t_s, f_s, first = _supersampled_curve(**inp["shape"])
+    maxw = int(numpy.max(inp["durations"]) * numpy.size(inp["t"]))
+    return ModelTemplate(t_s[first: -first + 1], f_s[first: -first + 1], t_s[first], t_s[-first - 1], maxw)
+
+
 def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_arrays=False, devices=None, statistics=False,
-                per_transit=False, **power_kwargs):
+                per_transit=False, models=False, **power_kwargs):
     """Survey-mode power(): for every light curve of `flux_batch` what `transitleastsquares(t, flux).power(**kwargs)`
     reports as SDE, SDE_raw, chi2_min, period, T0, depth and duration (fractional, lc_cache_overview["duration"] of
     the template row at the chi^2 minimum, main.py:199-200) -- search, SDE spectra and final T0 fit all on the
@@ -112,8 +133,24 @@ def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_ar
     transit_depths_uncertainties, snr_per_transit, snr_pink_per_transit, NaN past a curve's epochs -- and n_epochs.
     The statistics need ascending t.
 
-    Returns (summary, periods[, chi2, row, depth, power][, per_transit]): summary is a numpy structured array with the
-    fields of tls_power_summary plus "duration" (and the statistics on request)."""
+    models=True (implies statistics and per_transit) also returns the arrays power() returns for plotting, computed on the
+    device behind the statistics (tls_power_batch_models), as a dict: folded_phase, folded_y, folded_dy and model_folded_model
+    [n_curves, n]; model_lightcurve_time and model_lightcurve_model [n_curves, lc_cap], NaN past lc_len[k] entries; lc_len;
+    model_folded_phase [n] (one numpy.linspace, shared).  The phases are sorted in the STABLE order (equal phases by index);
+    power()'s numpy.argsort leaves the order of equal phases open, for distinct phases the two are the same.  A curve without
+    a fit has NaN rows and lc_len 0.
+
+    Returns (summary, periods[, chi2, row, depth, power][, per_transit][, models]): summary is a numpy structured array with
+    the fields of tls_power_summary plus "duration" (and the statistics on request)."""
+    return _power_batch(t, flux_batch, dy_batch, context, device, with_arrays, devices, statistics, per_transit, models,
+                        False, power_kwargs)
+
+
+def _power_batch(t, flux_batch, dy_batch, context, device, with_arrays, devices, statistics, per_transit, models, spectra,
+                 power_kwargs):
+    """power_batch; spectra=True (power_results) also returns SR and power_raw [n_curves, n_periods] behind the arrays."""
+    models = bool(models)
+    per_transit = bool(per_transit or models)
     statistics = bool(statistics or per_transit)
     if statistics:
         t_check = numpy.asarray(t, dtype=numpy.float64)
@@ -131,11 +168,13 @@ def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_ar
         fill_factor = calculate_fill_factor(inp["t"])
         root = numpy.array([float(k) ** 0.5 for k in range(len(inp["t"]) + 1)])   # (Python's pow, as power() forms k ** 0.5)
         max_epochs = _max_epochs(inp["t"], inp["periods"])
+        template = _model_template(inp) if models else None
+        lc_cap = _lc_cap(len(inp["t"]), max_epochs) if models else 0
 
         def call(ctx, lo, hi):
             return ctx.power_batch_stats(inp["t"], y_rows[lo:hi], dy_rows[lo:hi], inp["periods"], inp["table"], inp["params"],
                                          int(kernel), fill_factor, root, max_epochs, per_transit=per_transit,
-                                         with_arrays=with_arrays)
+                                         with_arrays=with_arrays, with_spectra=spectra, models=template, lc_cap=lc_cap)
     else:
         def call(ctx, lo, hi):
             return ctx.power_batch(inp["t"], y_rows[lo:hi], dy_rows[lo:hi], inp["periods"], inp["table"], inp["params"],
@@ -147,9 +186,15 @@ def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_ar
     else:
         ctx = context if context is not None else _search.default_context(what)
         parts = [call(ctx, 0, len(y_rows))]
-    out = [None if parts[0][k] is None else numpy.concatenate([p[k] for p in parts]) for k in range(len(parts[0]))]
+    # (one part: its arrays as they are -- the padded model rows of a large batch run to hundreds of MB)
+    out = [None if parts[0][k] is None else parts[0][k] if len(parts) == 1 else numpy.concatenate([p[k] for p in parts])
+           for k in range(len(parts[0]))]
     if statistics:
-        raw, tstats, rows, n_epochs, chi2, row, depth, power = out
+        raw, tstats, rows, n_epochs, chi2, row, depth, power = out[:8]
+        extra = out[8:]
+        if spectra:
+            SR, power_raw = extra[:2]
+            extra = extra[2:]
     else:
         raw, chi2, row, depth, power = out
     names = list(raw.dtype.names) + ["duration"]
@@ -180,7 +225,71 @@ def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_ar
         pt = {k: rows[:, i, :] for i, k in enumerate(PER_TRANSIT_FIELDS)}
         pt["n_epochs"] = n_epochs
         result += (pt,)
+    if models:
+        folded, model_folded, lightcurve, lc_len = extra
+        n = len(inp["t"])
+        m = dict(folded_phase=folded[:, 0], folded_y=folded[:, 1], model_folded_model=model_folded,
+                 model_lightcurve_time=lightcurve[:, 0], model_lightcurve_model=lightcurve[:, 1], lc_len=lc_len,
+                 model_folded_phase=numpy.linspace(0 + 1 / n / 2, 1 + 1 / n / 2, n))   # (api.py: half a cadence on)
+        # folded_dy: dy gathered by the device's order (NaN without a fit)
+        order = folded[:, 2]
+        no_fit = numpy.isnan(order[:, 0])
+        m["folded_dy"] = numpy.take_along_axis(dy_rows, numpy.where(no_fit[:, None], 0, order).astype(numpy.int64), axis=1)
+        m["folded_dy"][no_fit] = numpy.nan
+        result += (m,)
+    if spectra:
+        result += (SR, power_raw)
     return result
+
+
+def power_results(t, flux_batch, dy_batch=None, context=None, device=None, devices=None, **power_kwargs):
+    """power()'s results object for every light curve of `flux_batch` (shape [n_curves, len(t)], shared ascending time
+    stamps): a list of transitleastsquaresresults, element k equal to
+    transitleastsquares(t, flux_batch[k], dy_batch[k]).power(**power_kwargs) key for key and in key order (41 keys).  Search,
+    spectra, final T0 fit, statistics, the folded light curve and the model light curves all come from the device
+    (power_batch(models=True, with_arrays=True)); tuples are rebuilt from the _std fields, chi2red = chi2 / (n - 4),
+    `periods` is one array shared by all objects, and a curve without a fit gets exactly what power() returns then
+    (api.transitleastsquares._results_without_fit).  The folded light curve is sorted in the stable order: for equal
+    phases (duplicate time stamps) power()'s numpy.argsort may order them otherwise.
+
+    Memory: every object holds O(n_periods + n) doubles -- power, power_raw, SR, chi2, chi2red and the folded and model
+    arrays, about 0.7 MB for the k2_90d configuration (90 days at 48 cadences a day), so 1024 curves take about 0.7 GB, and
+    the call's own staging as much again while it runs.  Callers with large batches pass them in chunks.
+    devices=[...] deals the batch out over several GPUs, as the other survey calls."""
+    from .api import transitleastsquares
+    from .results import transitleastsquaresresults
+    if len(numpy.shape(flux_batch)) != 2 or numpy.shape(flux_batch)[1] != len(t):
+        raise ValueError("flux_batch must have shape [n_curves, len(t)]")
+    if dy_batch is not None and numpy.shape(dy_batch) != numpy.shape(flux_batch):
+        raise ValueError("dy_batch must have the shape of flux_batch")
+    summary, periods, chi2, row, depth, power, pt, m, SR, power_raw = _power_batch(
+        t, flux_batch, dy_batch, context, device, True, devices, True, True, True, True, power_kwargs)
+    n = len(m["model_folded_phase"])
+    chi2red = chi2 / (n - 4)   # (main.py:210-212)
+    out = []
+    for k in range(len(summary)):
+        rec = summary[k]
+        if rec["no_fit"]:
+            out.append(transitleastsquares._results_without_fit(None, periods, chi2[k], chi2red[k], numpy.min(chi2[k]),
+                                                                 numpy.min(chi2red[k])))
+            continue
+        e = int(pt["n_epochs"][k])
+        cnt = int(m["lc_len"][k])
+        row_of = {key: pt[key][k, :e] for key in ("per_transit_count", "transit_depths", "transit_depths_uncertainties",
+                                                   "snr_per_transit", "snr_pink_per_transit")}
+        out.append(transitleastsquaresresults(
+            float(rec["SDE"]), float(rec["SDE_raw"]), numpy.min(chi2[k]), numpy.min(chi2red[k]), periods[rec["index_power"]],
+            rec["period_uncertainty"], float(rec["T0"]), rec["duration_days"], depth[k][rec["index_power"]],
+            (rec["depth_mean"], rec["depth_mean_std"]), (rec["depth_mean_even"], rec["depth_mean_even_std"]),
+            (rec["depth_mean_odd"], rec["depth_mean_odd_std"]), row_of["transit_depths"],
+            row_of["transit_depths_uncertainties"], rec["rp_rs"], rec["snr"], row_of["snr_per_transit"],
+            row_of["snr_pink_per_transit"], rec["odd_even_mismatch"], pt["transit_times"][k, :e].tolist(),
+            row_of["per_transit_count"], e, int(rec["distinct_transit_count"]), int(rec["empty_transit_count"]),
+            rec["FAP"], int(rec["in_transit_count"]), int(rec["after_transit_count"]), int(rec["before_transit_count"]),
+            periods, power[k], power_raw[k], SR[k], chi2[k], chi2red[k], m["model_lightcurve_time"][k, :cnt],
+            m["model_lightcurve_model"][k, :cnt], m["model_folded_phase"], m["folded_y"][k], m["folded_dy"][k],
+            m["folded_phase"][k], m["model_folded_model"][k]))
+    return out
 
 
 def search_batch(t, flux_batch, dy_batch=None, context=None, device=None, devices=None, **power_kwargs):
