@@ -34,7 +34,8 @@ extern "C" {
  * five fields, tls_period_costs / tls_power_batch exist; 4: tls_options, tls_get_options / tls_set_options; 5: tls_options
  * keeps the two caller-facing switches, the developer switches moved behind tls_debug_set_switch, tls_period_costs takes
  * them as text; 6: tls_transit_stats, tls_power_batch_stats, tls_debug_transit_stats; 7: tls_power_batch_models,
- * tls_debug_transit_models).  A binding compares it with tls_abi_version(). */
+ * tls_debug_transit_models).  A binding compares it with tls_abi_version().  Entries added without changing a layout or
+ * signature keep the version (7: tls_inject_transits). */
 #define TLS_AMD_ABI_VERSION 7
 
 #define TLS_OK 0
@@ -328,6 +329,25 @@ int tls_debug_transit_models(tls_ctx *ctx, const double *y, int64_t n_curves, co
 int tls_debug_post_search(tls_ctx *ctx, const double *y, int64_t n_curves, const double *chi2, const int64_t *row,
                           const double *depth, int64_t median_kernel, tls_power_summary *out_summary,
                           double *out_epochs, double *out_residuals, int64_t *out_n_epochs, int64_t *out_handed_back);
+
+/* ---- survey-mode injection-recovery: transits injected on the device ---------------------------------------------- */
+/* Constants of one injected planet on a circular orbit, formed by the caller as transit_model's _true_anomaly (ecc < 1e-5
+ * branch) and projected_separation form them: tp = T0 - period * (pi/2 - omega) / (2 pi), sin_inc = sin(radians(inc)),
+ * omega = radians(90); rp = Rp/R*, a = a/R*. */
+typedef struct tls_injection {
+    double tp, period, rp, a, sin_inc, omega;
+} tls_injection;
+/* out_flux[k][i] = flux[k or 0][i] * transit_model.light_curve(t[i]) of injection k (quadratic law u1, u2; linear: u2 = 0;
+ * uniform: u1 = u2 = 0).  flux_rows: 1 (one base row shared by every injection) or n_inj.  out_in_transit[k] (may be NULL):
+ * points with z < 1 + rp, 0 for a planet whose transits all fall into gaps.  A point out of contact keeps its base flux bit
+ * for bit.  TLS_E_ARG for n < 1, another flux_rows, a non-finite constant, period <= 0, a <= 0 or rp < 0; n_inj == 0 is a
+ * no-op. */
+int tls_inject_transits(tls_ctx *ctx, const double *t, int64_t n,
+                        const double *flux, int64_t flux_rows,
+                        const tls_injection *inj, int64_t n_inj,
+                        double u1, double u2,
+                        double *out_flux,
+                        int64_t *out_in_transit);
 
 /* ---- host-only planning (no GPU needed) ------------------------------------------ */
 /* Trial cells (duration x T0 positions) each period will enumerate: the data-independent

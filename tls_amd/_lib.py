@@ -26,6 +26,7 @@ SYMBOLS = (
     "tls_synchronize", "tls_fetch", "tls_execute_timed", "tls_plan_info", "tls_last_kernel", "tls_grid_cells", "tls_period_costs", "tls_t0_fit", "tls_pink_noise", "tls_spectra", "tls_kernel_timing", "tls_debug_phase_cycles", "tls_debug_cumsum", "tls_debug_folded", "tls_debug_prefix", "tls_debug_check_counts", "tls_debug_poison_lds", "tls_debug_period_cycles", "tls_debug_batch_group_ms",
     "tls_debug_post_search", "tls_debug_device_bytes", "tls_power_batch_stats", "tls_debug_transit_stats",
     "tls_power_batch_models", "tls_debug_transit_models",
+    "tls_inject_transits",
     "tls_comm_unique_id", "tls_comm_init", "tls_comm_destroy", "tls_comm_info", "tls_comm_allgather_results", "tls_comm_allgather_device", "tls_comm_fetch_gathered",
     "tls_comm_stage_results", "tls_comm_allgather_staged", "tls_comm_fetch_staged",
     "tls_comm_barrier", "tls_comm_max",
@@ -116,6 +117,17 @@ class ModelTemplate(object):
 def _model_outputs(n_c, n, lc_cap):
     return (numpy.empty((n_c, len(FOLDED_FIELDS), n)), numpy.empty((n_c, n)),
             numpy.empty((n_c, len(LIGHTCURVE_FIELDS), int(lc_cap))), numpy.empty(n_c, dtype=numpy.int64))
+
+
+INJECTION_FIELDS = ("tp", "period", "rp", "a", "sin_inc", "omega")
+
+
+class Injection(ctypes.Structure):
+    """tls_injection: the constants of one injected planet on a circular orbit (include/tls_amd.h), 48 bytes."""
+    _fields_ = [(k, ctypes.c_double) for k in INJECTION_FIELDS]
+
+
+INJECTION_DTYPE = numpy.dtype([(k, "f8") for k in INJECTION_FIELDS])
 
 
 class Counters(ctypes.Structure):
@@ -232,6 +244,9 @@ def load():
     lib.tls_power_batch_models.argtypes = lib.tls_power_batch_stats.argtypes + models
     lib.tls_debug_transit_models.restype = ci
     lib.tls_debug_transit_models.argtypes = lib.tls_debug_transit_stats.argtypes + models
+    lib.tls_inject_transits.restype = ci
+    lib.tls_inject_transits.argtypes = [vp, _c_double_p, i64, _c_double_p, i64, ctypes.POINTER(Injection), i64, dbl, dbl,
+                                        _c_double_p, _c_int64_p]
     lib.tls_debug_device_bytes.restype = ci
     lib.tls_debug_device_bytes.argtypes = [vp, _c_int64_p, _c_int64_p]
     lib.tls_debug_cumsum.restype = ci
@@ -598,6 +613,27 @@ class Context(object):
         out = numpy.empty(1, dtype=numpy.float64)
         self._check(self._lib.tls_pink_noise(self._h, _dp(d), len(d), int(width), float(int(width) ** 0.5), _dp(out)))
         return float(out[0])
+
+    def inject_transits(self, t, flux, constants, u1, u2):
+        """(rows [n_inj, n], n_in_transit [n_inj]): flux (one row [n] shared by every injection, or [n_inj, n]) times the
+        transit model of every injection (tls_inject_transits); `constants` an INJECTION_DTYPE array (or anything with its
+        fields), u1 / u2 the quadratic law's coefficients (u2 = 0 for the linear law, both 0 for the uniform one)."""
+        t = _f8(t)
+        f = _f8(flux)
+        c = numpy.zeros(numpy.size(constants["tp"]), dtype=INJECTION_DTYPE)
+        for k in INJECTION_FIELDS:
+            c[k] = numpy.ravel(constants[k])
+        n, n_inj = len(t), len(c)
+        if f.ndim == 1:
+            f = f[None, :]
+        if f.ndim != 2 or f.shape[1] != n:
+            raise ValueError("flux must have shape [len(t)] or [n_injections, len(t)]")
+        rows = numpy.empty((n_inj, n), dtype=numpy.float64)
+        count = numpy.zeros(n_inj, dtype=numpy.int64)
+        self._check(self._lib.tls_inject_transits(self._h, _dp(t), n, _dp(f), f.shape[0],
+                                                  c.ctypes.data_as(ctypes.POINTER(Injection)), n_inj, float(u1), float(u2),
+                                                  _dp(rows), _ip(count)))
+        return rows, count
 
     def debug_cumsum(self, values, threads=512):
         """[0, cumsum(values)] computed by the kernel's exact parallel sequential-order scan."""

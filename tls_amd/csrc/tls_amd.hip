@@ -232,6 +232,8 @@ struct tls_ctx {
     DevBuf<double> d_tstats;        // tls_power_batch_stats: row durations | root table | per-curve scratch of one group
     DevBuf<int> d_tranges;          // ... and every epoch's chunk start | stop | offset
     DevBuf<double> d_models;        // tls_power_batch_models: template curve | per-curve scratch of one group | results of one group
+    DevBuf<double> d_inject;        // tls_inject_transits: t | base rows | injected rows | constants of one slab
+    DevBuf<unsigned long long> d_inject_count;   // ... and its points in contact per injection
     size_t list_stride = 0;
     // two-kernel slab path (series in HBM, one light curve): fold kernel + search kernel per batch of periods
     bool split = false;                      // the plan supports it (enqueue uses it for single-curve launches)
@@ -1448,7 +1450,7 @@ void tls_ctx_destroy(tls_ctx* ctx) {
     ctx->d_gather.release(); ctx->d_scalar.release(); ctx->d_stage.release();
     ctx->d_partials.release(); ctx->d_tiles_done.release(); ctx->d_check.release(); ctx->d_spec.release(); ctx->d_queue.release(); ctx->d_squeue.release(); ctx->d_pqueues.release(); ctx->d_phase.release(); ctx->d_lists.release(); ctx->d_perm.release(); ctx->d_curve_S0.release(); ctx->d_curve_w0.release();
     ctx->d_ft.release(); ctx->d_fy.release(); ctx->d_fsig.release(); ctx->d_fep.release(); ctx->d_fres.release(); ctx->d_fscratch.release(); ctx->d_frot.release(); ctx->d_frperm.release(); ctx->d_pink.release();
-    ctx->d_tstats.release(); ctx->d_tranges.release(); ctx->d_models.release();
+    ctx->d_tstats.release(); ctx->d_tranges.release(); ctx->d_models.release(); ctx->d_inject.release(); ctx->d_inject_count.release();
     ctx->d_split.release(); ctx->d_park.release(); ctx->d_band.release();
     if (ctx->h_band) (void)hipHostFree(ctx->h_band);
     for (auto& ev : ctx->ev_band) if (ev) (void)hipEventDestroy(ev);
@@ -1985,6 +1987,65 @@ int tls_pink_noise(tls_ctx* ctx, const double* data, int64_t n, int64_t width, d
     TLS_HIP(ctx, hipMemcpyAsync(&last, d_sums + n_windows, 8, hipMemcpyDeviceToHost, ctx->stream));
     TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     *out = last / (double)n_windows;
+    return TLS_OK;
+}
+
+static_assert(sizeof(tls_injection) == 6 * sizeof(double), "tls_injection is six doubles");
+
+int tls_inject_transits(tls_ctx* ctx, const double* t, int64_t n, const double* flux, int64_t flux_rows,
+                        const tls_injection* inj, int64_t n_inj, double u1, double u2, double* out_flux,
+                        int64_t* out_in_transit) {
+    if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
+    if (n < 1 || n > 100000000) return fail(ctx, TLS_E_ARG, "inject: n out of range [1, 1e8]");
+    if (n_inj < 0) return fail(ctx, TLS_E_ARG, "inject: n_inj < 0");
+    if (n_inj == 0) return TLS_OK;
+    if (flux_rows != 1 && flux_rows != n_inj) return fail(ctx, TLS_E_ARG, "inject: flux_rows must be 1 or n_inj");
+    if (!t || !flux || !inj || !out_flux) return fail(ctx, TLS_E_ARG, "null argument");
+    if (!std::isfinite(u1) || !std::isfinite(u2)) return fail(ctx, TLS_E_ARG, "inject: non-finite limb darkening");
+    for (int64_t k = 0; k < n_inj; ++k) {
+        const tls_injection& c = inj[k];
+        if (!std::isfinite(c.tp) || !std::isfinite(c.period) || !std::isfinite(c.rp) || !std::isfinite(c.a)
+            || !std::isfinite(c.sin_inc) || !std::isfinite(c.omega))
+            return fail(ctx, TLS_E_ARG, "inject: injection " + std::to_string(k) + " has a non-finite constant");
+        if (!(c.period > 0.0) || !(c.a > 0.0) || !(c.rp >= 0.0))
+            return fail(ctx, TLS_E_ARG, "inject: injection " + std::to_string(k) + " needs period > 0, a > 0 and rp >= 0");
+    }
+    TLS_HIP(ctx, hipSetDevice(ctx->device));
+    // rows per launch: the slab's injected rows stay within 256 MB (and gridDim.y within its limit)
+    const size_t nn = (size_t)n;
+    const int64_t slab = std::max<int64_t>(1, std::min<int64_t>({n_inj, (int64_t)65535, (int64_t)((256u << 20) / (8 * nn))}));
+    const size_t base_len = flux_rows == 1 ? nn : (size_t)slab * nn;
+    // t | base rows | injected rows | constants
+    TLS_HIP(ctx, ctx->d_inject.reserve(nn + base_len + (size_t)slab * nn + 6 * (size_t)slab));
+    TLS_HIP(ctx, ctx->d_inject_count.reserve((size_t)slab));
+    double* d_t = ctx->d_inject.ptr;
+    double* d_base = d_t + nn;
+    double* d_out = d_base + base_len;
+    double* d_consts = d_out + (size_t)slab * nn;
+    TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (flux_rows == 1) TLS_HIP(ctx, hipMemcpyAsync(d_base, flux, nn * 8, hipMemcpyHostToDevice, ctx->stream));
+    for (int64_t k0 = 0; k0 < n_inj; k0 += slab) {
+        const int64_t rows = std::min<int64_t>(slab, n_inj - k0);
+        if (flux_rows != 1)
+            TLS_HIP(ctx, hipMemcpyAsync(d_base, flux + (size_t)k0 * nn, (size_t)rows * nn * 8, hipMemcpyHostToDevice, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(d_consts, inj + k0, (size_t)rows * sizeof(tls_injection), hipMemcpyHostToDevice, ctx->stream));
+        TLS_HIP(ctx, hipMemsetAsync(ctx->d_inject_count.ptr, 0, (size_t)rows * sizeof(unsigned long long), ctx->stream));
+        tlsdev::InjectArgs a;
+        a.t = d_t; a.flux = d_base; a.consts = d_consts; a.u1 = u1; a.u2 = u2; a.out = d_out;
+        a.count = ctx->d_inject_count.ptr; a.n = (long long)n; a.flux_stride = flux_rows == 1 ? 0 : (long long)n;
+        hipLaunchKernelGGL(tlsdev::tls_inject_transits, dim3((unsigned)((n + 255) / 256), (unsigned)rows), dim3(256), 0,
+                           ctx->stream, a);
+        TLS_HIP(ctx, hipGetLastError());
+        ctx->last_kernel = "tls_inject_transits";
+        TLS_HIP(ctx, hipMemcpyAsync(out_flux + (size_t)k0 * nn, d_out, (size_t)rows * nn * 8, hipMemcpyDeviceToHost, ctx->stream));
+        if (out_in_transit) {
+            static_assert(sizeof(unsigned long long) == sizeof(int64_t), "count width");
+            TLS_HIP(ctx, hipMemcpyAsync(out_in_transit + k0, ctx->d_inject_count.ptr, (size_t)rows * 8, hipMemcpyDeviceToHost,
+                                        ctx->stream));
+        }
+        // (the next slab overwrites the device rows: the copies above have to be done first)
+        TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
     return TLS_OK;
 }
 

@@ -4250,4 +4250,7 @@ __global__ void __launch_bounds__(512) tls_transit_models(const ModelsArgs a) {
     if (tid == 0) { out[0] = (double)len; out[1] = (double)samples; }
 }
 
+// survey-mode injection (tls_inject_transits)
+#include "tls_inject.hip.h"
+
 }  // namespace tlsdev

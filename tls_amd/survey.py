@@ -313,3 +313,252 @@ def search_batch(t, flux_batch, dy_batch=None, context=None, device=None, device
         ctx = context if context is not None else _search.default_context(what)
         chi2, row, depth = call(ctx, 0, len(y_rows))
     return inp["periods"], chi2, row, depth
+
+
+# ---- injection-recovery ---------------------------------------------------------------------------------------------------
+INJECTION_FIELDS = ("T0", "period", "rp_rs", "a", "inc")
+INJECTION_LAWS = ("quadratic", "linear", "uniform")
+
+
+def _injection_table(injections):
+    """The injections as a structured float64 array with the fields T0, period (days), rp_rs, a (a/R*) and inc (degrees),
+    from a structured array or a dict of arrays; ValueError for anything the device model does not cover."""
+    if isinstance(injections, dict):
+        names = tuple(injections.keys())
+    else:
+        injections = numpy.asarray(injections)
+        names = injections.dtype.names or ()
+        if not names:
+            raise ValueError("injections must be a structured array or a dict with fields %s" % (INJECTION_FIELDS,))
+    for k in ("ecc", "w"):
+        if k in names:
+            raise ValueError("injections carry an %r field: injection-recovery injects circular orbits only (ecc = 0, w = 90)"
+                             % k)
+    missing = [k for k in INJECTION_FIELDS if k not in names]
+    if missing:
+        raise ValueError("injections lack the fields %s (wanted: %s)" % (missing, INJECTION_FIELDS))
+    cols = [numpy.atleast_1d(numpy.asarray(injections[k], dtype=numpy.float64)) for k in INJECTION_FIELDS]
+    if any(c.ndim != 1 for c in cols) or len({len(c) for c in cols}) != 1:
+        raise ValueError("the injection fields must be 1-d arrays of one length")
+    table = numpy.zeros(len(cols[0]), dtype=[(k, "f8") for k in INJECTION_FIELDS])
+    for k, c in zip(INJECTION_FIELDS, cols):
+        if not numpy.all(numpy.isfinite(c)):
+            raise ValueError("injection field %r has a non-finite value" % k)
+        table[k] = c
+    if numpy.any(table["period"] <= 0):
+        raise ValueError("injection periods must be > 0")
+    if numpy.any(table["a"] <= 0):
+        raise ValueError("injection a/R* must be > 0")
+    if numpy.any(table["rp_rs"] < 0):
+        raise ValueError("injection rp_rs must be >= 0")
+    return table
+
+
+def injection_constants(injections):
+    """The tls_injection constants of every injection (_lib.INJECTION_DTYPE), formed by numpy as transit_model's
+    _true_anomaly (ecc < 1e-5) and projected_separation form them for light_curve(t, T0, period, rp_rs, a, inc, 0, 90, ...)."""
+    from ._lib import INJECTION_DTYPE
+    table = _injection_table(injections)
+    c = numpy.zeros(len(table), dtype=INJECTION_DTYPE)
+    omega = numpy.radians(90)
+    f_conj = numpy.pi / 2.0 - omega
+    for k in range(len(table)):
+        t0, per, inc = float(table["T0"][k]), float(table["period"][k]), float(table["inc"][k])
+        c["tp"][k] = t0 - per * f_conj / (2.0 * numpy.pi)
+        c["sin_inc"][k] = numpy.sin(numpy.radians(inc))   # (a scalar, as projected_separation takes it)
+    c["period"], c["rp"], c["a"], c["omega"] = table["period"], table["rp_rs"], table["a"], omega
+    return c
+
+
+def _injection_law(inject_u, inject_limb_dark, power_kwargs):
+    """(law, u1, u2) of the injected planet: inject_u / inject_limb_dark, else the search template's u / limb_dark, else the
+    TLS defaults; u2 = 0 for the linear law, u1 = u2 = 0 for the uniform one (as transit_model.light_curve takes them)."""
+    from . import constants as C
+    law = inject_limb_dark if inject_limb_dark is not None else power_kwargs.get("limb_dark", C.DEFAULT_LIMB_DARK)
+    if law not in INJECTION_LAWS:
+        raise ValueError("injection limb darkening law %r has no closed form on the device: use one of %s"
+                         % (law, INJECTION_LAWS))
+    u = inject_u if inject_u is not None else power_kwargs.get("u", C.DEFAULT_U)
+    u = [float(v) for v in numpy.atleast_1d(u)] if u is not None else []
+    need = {"quadratic": 2, "linear": 1, "uniform": 0}[law]
+    if len(u) < need:
+        raise ValueError("limb darkening law %r needs %d coefficients, got %d" % (law, need, len(u)))
+    if law == "quadratic":
+        return law, u[0], u[1]
+    if law == "linear":
+        return law, u[0], 0.0
+    return law, 0.0, 0.0
+
+
+def injected_duration(injections):
+    """T14 (days) of every injection on its circular orbit: b = a cos i,
+    T14 = P / pi * arcsin(min(1, sqrt(max((1 + rp)^2 - b^2, 0)) / (a sin i)))."""
+    table = _injection_table(injections)
+    inc = numpy.radians(table["inc"])
+    b = table["a"] * numpy.cos(inc)
+    chord = numpy.sqrt(numpy.maximum((1.0 + table["rp_rs"]) ** 2 - b ** 2, 0.0)) / (table["a"] * numpy.sin(inc))
+    return table["period"] / numpy.pi * numpy.arcsin(numpy.minimum(1.0, chord))
+
+
+def classify_recovery(injections, summary, n_in_transit=None, sde_threshold=7.0, period_tolerance=0.01, aliases=(1.0,),
+                      epoch_tolerance=None):
+    """The recovery record of every injection from the search summary of its injected light curve (power_batch's summary:
+    SDE, period, T0, no_fit).  period_match: the first factor m of `aliases` with |P_found - m P| <= period_tolerance m P,
+    else 0; epoch_offset: the found T0 minus the nearest injected mid-time, these spaced min(m, 1) P (NaN without a match);
+    recovered: no_fit == 0, SDE >= sde_threshold, a period match and |epoch_offset| <= epoch_tolerance (default 0.5 T14)."""
+    table = _injection_table(injections)
+    summary = numpy.asarray(summary)
+    if len(summary) != len(table):
+        raise ValueError("summary has %d records for %d injections" % (len(summary), len(table)))
+    aliases = tuple(float(m) for m in aliases)
+    if not aliases or any(not (m > 0) for m in aliases):
+        raise ValueError("aliases must be positive period factors")
+    fields = [(k, "f8") for k in INJECTION_FIELDS] + [("T14", "f8"), ("n_in_transit", "i8"), ("period_match", "f8"),
+                                                       ("epoch_offset", "f8"), ("recovered", "?")]
+    rec = numpy.zeros(len(table), dtype=fields)
+    for k in INJECTION_FIELDS:
+        rec[k] = table[k]
+    rec["T14"] = injected_duration(table)
+    rec["n_in_transit"] = -1 if n_in_transit is None else numpy.asarray(n_in_transit, dtype=numpy.int64)
+    P, found_P, found_T0 = table["period"], summary["period"], summary["T0"]
+    match = numpy.zeros(len(table))
+    with numpy.errstate(invalid="ignore"):
+        for m in aliases[::-1]:   # (the first factor that matches wins)
+            ok = numpy.abs(found_P - m * P) <= period_tolerance * (m * P)
+            match = numpy.where(ok, m, match)
+        spacing = numpy.minimum(match, 1.0) * P
+        offset = numpy.full(len(table), numpy.nan)
+        has = match > 0
+        d = found_T0[has] - table["T0"][has]
+        offset[has] = d - numpy.rint(d / spacing[has]) * spacing[has]
+        tol = 0.5 * rec["T14"] if epoch_tolerance is None else numpy.broadcast_to(float(epoch_tolerance), len(table))
+        rec["period_match"] = match
+        rec["epoch_offset"] = offset
+        rec["recovered"] = ((summary["no_fit"] == 0) & (summary["SDE"] >= sde_threshold) & has
+                            & (numpy.abs(offset) <= tol))
+    return rec
+
+
+def _default_chunk(n):
+    """Injections per chunk: the chunk's rows stay at or below about 256 MB, whole launch groups of 32 where that allows."""
+    rows = max(1, (256 << 20) // (8 * max(int(n), 1)))
+    return rows - rows % 32 if rows >= 32 else rows
+
+
+def injection_recovery(t, flux, injections, dy=None, inject_u=None, inject_limb_dark=None, sde_threshold=7.0,
+                       period_tolerance=0.01, aliases=(1.0,), epoch_tolerance=None, chunk=None, return_rows=False,
+                       statistics=False, context=None, device=None, devices=None, **power_kwargs):
+    """Injection-recovery in survey mode: inject every planet of `injections` into `flux` on the device
+    (tls_inject_transits: flux * transit_model.light_curve(t, T0, period, rp_rs, a, inc, 0, 90, u, law)), search every
+    injected light curve with power_batch, and classify each injection (classify_recovery).
+
+    flux: [n] (every injection into the same base curve) or [n_injections, n]; dy: None (std of each injected row, as
+    power() takes it), [n] or [n_injections, n].  injections: a structured array or dict with T0, period, rp_rs, a (a/R*)
+    and inc (degrees); circular orbits only.  inject_u / inject_limb_dark set the injected planet's limb darkening
+    (quadratic, linear or uniform), by default the search template's u / limb_dark of power_kwargs, else the TLS defaults;
+    power_kwargs (u, limb_dark, ecc, w included) go to the search unchanged.
+
+    Per chunk of `chunk` injections (default: about 256 MB of rows, a multiple of 32): the rows are formed on the call's
+    device (the given context or device, or the group's first one), copied to the host, searched by power_batch (with
+    `statistics` and `devices` passed through) and classified.  The round trip makes the search's inputs exactly
+    power_batch's, so `summary` equals power_batch(t, rows, dy) on the same rows.
+
+    Returns (recovery, summary[, rows]): recovery a structured array -- the injected fields, T14, n_in_transit (points
+    with z < 1 + rp_rs: 0 where every transit falls into a gap), period_match, epoch_offset, recovered -- and summary
+    power_batch's summary; rows [n_injections, n] with return_rows=True."""
+    table = _injection_table(injections)
+    n_inj = len(table)
+    t = numpy.asarray(t, dtype=numpy.float64)
+    if t.ndim != 1:
+        raise ValueError("t must be 1-d")
+    n = len(t)
+    flux = numpy.asarray(flux, dtype=numpy.float64)
+    if flux.shape not in ((n,), (n_inj, n)):
+        raise ValueError("flux must have shape [len(t)] or [n_injections, len(t)], got %s" % (flux.shape,))
+    if dy is not None:
+        dy = numpy.asarray(dy, dtype=numpy.float64)
+        if dy.shape not in ((n,), (n_inj, n)):
+            raise ValueError("dy must be None or have shape [len(t)] or [n_injections, len(t)], got %s" % (dy.shape,))
+    _, u1, u2 = _injection_law(inject_u, inject_limb_dark, power_kwargs)
+    chunk = _default_chunk(n) if chunk is None else int(chunk)
+    if chunk < 1:
+        raise ValueError("chunk must be >= 1")
+    # (checked before any device work)
+    classify_recovery(table[:0], numpy.zeros(0, dtype=[("period", "f8"), ("T0", "f8"), ("SDE", "f8"), ("no_fit", "i8")]),
+                      None, sde_threshold, period_tolerance, aliases, epoch_tolerance)
+    consts = injection_constants(table)
+
+    kind, what = _resolve(devices, device, context, n_inj)
+    if kind == "group":
+        inject_ctx, lock = what.contexts[0], what._lock
+    else:
+        inject_ctx, lock = (context if context is not None else _search.default_context(what)), None
+
+    summaries, counts, all_rows = [], [], []
+    for lo in range(0, n_inj, chunk):
+        hi = min(n_inj, lo + chunk)
+        base = flux if flux.ndim == 1 else flux[lo:hi]
+        if lock is not None:
+            with lock:
+                rows, count = inject_ctx.inject_transits(t, base, consts[lo:hi], u1, u2)
+        else:
+            rows, count = inject_ctx.inject_transits(t, base, consts[lo:hi], u1, u2)
+        dy_rows = None if dy is None else (numpy.broadcast_to(dy, rows.shape) if dy.ndim == 1 else dy[lo:hi])
+        summaries.append(_power_batch(t, rows, dy_rows, context, device, False, devices, statistics, False, False, False,
+                                      power_kwargs)[0])
+        counts.append(count)
+        if return_rows:
+            all_rows.append(rows)
+    if summaries:
+        summary = numpy.concatenate(summaries)
+        count = numpy.concatenate(counts)
+    else:
+        raise ValueError("no injections")
+    recovery = classify_recovery(table, summary, count, sde_threshold, period_tolerance, aliases, epoch_tolerance)
+    if return_rows:
+        return recovery, summary, numpy.concatenate(all_rows)
+    return recovery, summary
+
+
+def injection_grid(t, periods, rp_rs, per_cell=1, b_max=0.0, seed=0, R_star=1.0, M_star=1.0):
+    """Deterministic injections on a (period, rp_rs) grid, `per_cell` of each pair (periods outermost): T0 = min(t) + U(0, 1) P,
+    a/R* from Kepler's third law (tls_amd.constants G, R_sun, M_sun; R_star, M_star in solar units), b ~ U(0, b_max) and
+    inc = degrees(arccos(b / a)).  The draws come from numpy.random.RandomState(seed) (T0 of all injections, then b), never
+    from the global generator.  Returns the structured array injection_recovery takes."""
+    from . import constants as C
+    periods = numpy.atleast_1d(numpy.asarray(periods, dtype=numpy.float64))
+    rp_rs = numpy.atleast_1d(numpy.asarray(rp_rs, dtype=numpy.float64))
+    per_cell = int(per_cell)
+    if periods.ndim != 1 or rp_rs.ndim != 1 or per_cell < 1:
+        raise ValueError("periods and rp_rs must be 1-d, per_cell >= 1")
+    if not (0.0 <= float(b_max)):
+        raise ValueError("b_max must be >= 0")
+    P = numpy.repeat(periods, len(rp_rs) * per_cell)
+    rp = numpy.tile(numpy.repeat(rp_rs, per_cell), len(periods))
+    rng = numpy.random.RandomState(seed)
+    T0 = numpy.min(t) + rng.uniform(0.0, 1.0, len(P)) * P
+    b = rng.uniform(0.0, float(b_max), len(P))
+    P_s = P * C.SECONDS_PER_DAY
+    a = (C.G * (M_star * C.M_sun) * P_s ** 2 / (4.0 * numpy.pi ** 2)) ** (1.0 / 3.0) / (R_star * C.R_sun)
+    out = numpy.zeros(len(P), dtype=[(k, "f8") for k in INJECTION_FIELDS])
+    out["T0"], out["period"], out["rp_rs"], out["a"] = T0, P, rp, a
+    out["inc"] = numpy.degrees(numpy.arccos(b / a))
+    _injection_table(out)
+    return out
+
+
+def completeness(recovery, period_edges, rp_edges, exclude_untransiting=True):
+    """Recovered fraction per (period, rp_rs) cell: (fraction, recovered, total), each [len(period_edges) - 1,
+    len(rp_edges) - 1] (numpy.histogram2d bins; fraction NaN in an empty cell).  exclude_untransiting leaves out the
+    injections without a point in transit (n_in_transit == 0)."""
+    rec = numpy.asarray(recovery)
+    keep = numpy.ones(len(rec), dtype=bool)
+    if exclude_untransiting:
+        keep &= rec["n_in_transit"] != 0
+    bins = (numpy.asarray(period_edges, dtype=numpy.float64), numpy.asarray(rp_edges, dtype=numpy.float64))
+    total = numpy.histogram2d(rec["period"][keep], rec["rp_rs"][keep], bins=bins)[0].astype(numpy.int64)
+    hit = keep & rec["recovered"]
+    recovered = numpy.histogram2d(rec["period"][hit], rec["rp_rs"][hit], bins=bins)[0].astype(numpy.int64)
+    with numpy.errstate(invalid="ignore", divide="ignore"):
+        fraction = numpy.where(total > 0, recovered / numpy.maximum(total, 1), numpy.nan)
+    return fraction, recovered, total
