@@ -35,7 +35,7 @@ extern "C" {
  * keeps the two caller-facing switches, the developer switches moved behind tls_debug_set_switch, tls_period_costs takes
  * them as text; 6: tls_transit_stats, tls_power_batch_stats, tls_debug_transit_stats; 7: tls_power_batch_models,
  * tls_debug_transit_models).  A binding compares it with tls_abi_version().  Entries added without changing a layout or
- * signature keep the version (7: tls_inject_transits). */
+ * signature keep the version (7: tls_inject_transits, tls_null_rows, tls_debug_null_words). */
 #define TLS_AMD_ABI_VERSION 7
 
 #define TLS_OK 0
@@ -183,6 +183,11 @@ int tls_debug_poison_lds(tls_ctx *ctx, uint32_t word);
 int tls_debug_batch_group_ms(const tls_ctx *ctx, double *out, int64_t capacity);
 /* developer instrumentation: bytes of device memory the context holds, in all and in the final T0 fit's HBM scratch */
 int tls_debug_device_bytes(const tls_ctx *ctx, int64_t *total, int64_t *t0_fit_scratch);
+/* Test entry: the raw Philox words tls_null_rows draws for trials first_trial .. first_trial + n_rows - 1 with the same
+ * (n, seed, mode, block): out [n_rows][W], W = the mode's words per trial rounded up to a multiple of 4 (the last W - words
+ * of a row are drawn but not used).  The arguments are checked as tls_null_rows checks them. */
+int tls_debug_null_words(tls_ctx *ctx, int64_t n, int64_t n_rows, uint64_t seed, int64_t first_trial, int mode,
+                         int64_t block, uint64_t *out);
 /* block until the stream is idle */
 int tls_synchronize(tls_ctx *ctx);
 /* fetch: copy results (and counters, may be NULL) back; synchronises. */
@@ -348,6 +353,25 @@ int tls_inject_transits(tls_ctx *ctx, const double *t, int64_t n,
                         double u1, double u2,
                         double *out_flux,
                         int64_t *out_in_transit);
+
+/* ---- survey-mode false-alarm calibration: null (noise-only) light curves on the device ----------------------------- */
+/* out[r][i] for trials R = first_trial + r (r < n_rows), points i < n.  The random stream is Philox4x64-10 under key
+ * (seed, 0), word j at counter (j / 4 + 1, 0, 0, 0) as numpy.random.Philox(key=seed).random_raw() orders it; trial R takes
+ * words [R W, R W + words), W = words rounded up to a multiple of 4 (numpy.random.Philox(key=seed, counter=R W / 4)
+ * .random_raw(W)), so a row depends on (seed, R) alone, not on how the trials are split into calls.
+ * mode 0, white noise (words = 2n): u_a = (w[2i] >> 11) 2^-53, u_b = (w[2i+1] >> 11) 2^-53 (numpy Generator.random()),
+ *   out = 1 + sigma[r or 0] sqrt(-2 log(1 - u_a)) cos(2 pi u_b) without contraction; n_sigma 1 or n_rows, every sigma in
+ *   (0, 0.1].  src, n_src and block are not read.
+ * mode 1, block bootstrap (words = ceil(n / block)): trial R copies source row s = R mod n_src of src [n_src][n]; bootstrap
+ *   block b (points b block .. min(n, (b+1) block) - 1) starts at start_b = floor(w[b] (n - block + 1) / 2^64), out[i] =
+ *   src[s][start_b + i - b block]: copies only, bit-exact.  block in [1, n], every source value finite and > 0.  sigma and
+ *   n_sigma are not read.
+ * TLS_E_ARG for n outside [1, 1e8], n_rows < 0, first_trial < 0, another mode, a bad sigma, n_sigma, block, n_src or
+ * source value, and for trials whose counters would pass 2^64 - 1; n_rows == 0 is a no-op. */
+int tls_null_rows(tls_ctx *ctx, int64_t n, int64_t n_rows, uint64_t seed, int64_t first_trial, int mode,
+                  const double *sigma, int64_t n_sigma,
+                  const double *src, int64_t n_src, int64_t block,
+                  double *out);
 
 /* ---- host-only planning (no GPU needed) ------------------------------------------ */
 /* Trial cells (duration x T0 positions) each period will enumerate: the data-independent

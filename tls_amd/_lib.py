@@ -26,7 +26,7 @@ SYMBOLS = (
     "tls_synchronize", "tls_fetch", "tls_execute_timed", "tls_plan_info", "tls_last_kernel", "tls_grid_cells", "tls_period_costs", "tls_t0_fit", "tls_pink_noise", "tls_spectra", "tls_kernel_timing", "tls_debug_phase_cycles", "tls_debug_cumsum", "tls_debug_folded", "tls_debug_prefix", "tls_debug_check_counts", "tls_debug_poison_lds", "tls_debug_period_cycles", "tls_debug_batch_group_ms",
     "tls_debug_post_search", "tls_debug_device_bytes", "tls_power_batch_stats", "tls_debug_transit_stats",
     "tls_power_batch_models", "tls_debug_transit_models",
-    "tls_inject_transits",
+    "tls_inject_transits", "tls_null_rows", "tls_debug_null_words",
     "tls_comm_unique_id", "tls_comm_init", "tls_comm_destroy", "tls_comm_info", "tls_comm_allgather_results", "tls_comm_allgather_device", "tls_comm_fetch_gathered",
     "tls_comm_stage_results", "tls_comm_allgather_staged", "tls_comm_fetch_staged",
     "tls_comm_barrier", "tls_comm_max",
@@ -247,6 +247,11 @@ def load():
     lib.tls_inject_transits.restype = ci
     lib.tls_inject_transits.argtypes = [vp, _c_double_p, i64, _c_double_p, i64, ctypes.POINTER(Injection), i64, dbl, dbl,
                                         _c_double_p, _c_int64_p]
+    u64 = ctypes.c_uint64
+    lib.tls_null_rows.restype = ci
+    lib.tls_null_rows.argtypes = [vp, i64, i64, u64, i64, ci, _c_double_p, i64, _c_double_p, i64, i64, _c_double_p]
+    lib.tls_debug_null_words.restype = ci
+    lib.tls_debug_null_words.argtypes = [vp, i64, i64, u64, i64, ci, i64, ctypes.POINTER(u64)]
     lib.tls_debug_device_bytes.restype = ci
     lib.tls_debug_device_bytes.argtypes = [vp, _c_int64_p, _c_int64_p]
     lib.tls_debug_cumsum.restype = ci
@@ -634,6 +639,39 @@ class Context(object):
                                                   c.ctypes.data_as(ctypes.POINTER(Injection)), n_inj, float(u1), float(u2),
                                                   _dp(rows), _ip(count)))
         return rows, count
+
+    def null_rows(self, n, n_rows, seed, first_trial=0, sigma=None, source=None, block=None):
+        """Null light curves [n_rows, n] for trials first_trial .. first_trial + n_rows - 1 (tls_null_rows): white noise
+        1 + sigma z (mode 0, `sigma` a scalar or [n_rows]) when `source` is None, else a block bootstrap of the rows of
+        `source` ([n] or [n_src, n], mode 1; trial R copies row R mod n_src in blocks of `block` points)."""
+        n, n_rows = int(n), int(n_rows)
+        out = numpy.empty((n_rows, n), dtype=numpy.float64)
+        if source is None:
+            s = _f8(numpy.atleast_1d(sigma))
+            if s.ndim != 1:
+                raise ValueError("sigma must be a scalar or [n_rows]")
+            self._check(self._lib.tls_null_rows(self._h, n, n_rows, int(seed), int(first_trial), 0, _dp(s), len(s), None, 0,
+                                                0, _dp(out)))
+        else:
+            src = _f8(source)
+            if src.ndim == 1:
+                src = src[None, :]
+            if src.ndim != 2 or src.shape[1] != n:
+                raise ValueError("source must have shape [n] or [n_src, n]")
+            self._check(self._lib.tls_null_rows(self._h, n, n_rows, int(seed), int(first_trial), 1, None, 0, _dp(src),
+                                                src.shape[0], int(block), _dp(out)))
+        return out
+
+    def debug_null_words(self, n, n_rows, seed, first_trial=0, block=None):
+        """The raw Philox words [n_rows, W] tls_null_rows draws for these trials (tls_debug_null_words): white-noise
+        layout when `block` is None, the bootstrap's otherwise."""
+        n, n_rows = int(n), int(n_rows)
+        words = 2 * n if block is None else -(-n // int(block)) if int(block) >= 1 else 1
+        out = numpy.empty((n_rows, 4 * (-(-words // 4))), dtype=numpy.uint64)
+        self._check(self._lib.tls_debug_null_words(self._h, n, n_rows, int(seed), int(first_trial), 0 if block is None else 1,
+                                                   0 if block is None else int(block),
+                                                   out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
+        return out
 
     def debug_cumsum(self, values, threads=512):
         """[0, cumsum(values)] computed by the kernel's exact parallel sequential-order scan."""

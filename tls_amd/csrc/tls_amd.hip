@@ -234,6 +234,8 @@ struct tls_ctx {
     DevBuf<double> d_models;        // tls_power_batch_models: template curve | per-curve scratch of one group | results of one group
     DevBuf<double> d_inject;        // tls_inject_transits: t | base rows | injected rows | constants of one slab
     DevBuf<unsigned long long> d_inject_count;   // ... and its points in contact per injection
+    DevBuf<double> d_null;          // tls_null_rows: source rows | sigma | rows of one slab
+    DevBuf<unsigned long long> d_null_words;     // tls_debug_null_words: the words of one slab
     size_t list_stride = 0;
     // two-kernel slab path (series in HBM, one light curve): fold kernel + search kernel per batch of periods
     bool split = false;                      // the plan supports it (enqueue uses it for single-curve launches)
@@ -1451,6 +1453,7 @@ void tls_ctx_destroy(tls_ctx* ctx) {
     ctx->d_partials.release(); ctx->d_tiles_done.release(); ctx->d_check.release(); ctx->d_spec.release(); ctx->d_queue.release(); ctx->d_squeue.release(); ctx->d_pqueues.release(); ctx->d_phase.release(); ctx->d_lists.release(); ctx->d_perm.release(); ctx->d_curve_S0.release(); ctx->d_curve_w0.release();
     ctx->d_ft.release(); ctx->d_fy.release(); ctx->d_fsig.release(); ctx->d_fep.release(); ctx->d_fres.release(); ctx->d_fscratch.release(); ctx->d_frot.release(); ctx->d_frperm.release(); ctx->d_pink.release();
     ctx->d_tstats.release(); ctx->d_tranges.release(); ctx->d_models.release(); ctx->d_inject.release(); ctx->d_inject_count.release();
+    ctx->d_null.release(); ctx->d_null_words.release();
     ctx->d_split.release(); ctx->d_park.release(); ctx->d_band.release();
     if (ctx->h_band) (void)hipHostFree(ctx->h_band);
     for (auto& ev : ctx->ev_band) if (ev) (void)hipEventDestroy(ev);
@@ -2044,6 +2047,117 @@ int tls_inject_transits(tls_ctx* ctx, const double* t, int64_t n, const double* 
                                         ctx->stream));
         }
         // (the next slab overwrites the device rows: the copies above have to be done first)
+        TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return TLS_OK;
+}
+
+// Checks shared by tls_null_rows and tls_debug_null_words; *blocks = Philox blocks per trial (W / 4).
+static int null_check(tls_ctx* ctx, int64_t n, int64_t n_rows, int64_t first_trial, int mode, int64_t block, int64_t* blocks) {
+    if (n < 1 || n > 100000000) return fail(ctx, TLS_E_ARG, "null rows: n out of range [1, 1e8]");
+    if (n_rows < 0) return fail(ctx, TLS_E_ARG, "null rows: n_rows < 0");
+    if (first_trial < 0) return fail(ctx, TLS_E_ARG, "null rows: first_trial < 0");
+    int64_t words;
+    if (mode == 0) {
+        words = 2 * n;
+    } else if (mode == 1) {
+        if (block < 1 || block > n) return fail(ctx, TLS_E_ARG, "null rows: block out of range [1, n]");
+        words = (n + block - 1) / block;
+    } else {
+        return fail(ctx, TLS_E_ARG, "null rows: mode must be 0 (white noise) or 1 (block bootstrap)");
+    }
+    *blocks = (words + 3) / 4;
+    // the last block's counter, (first_trial + n_rows) W / 4, must stay below 2^64 (counter words 1..3 stay 0)
+    if (first_trial > INT64_MAX - n_rows || (uint64_t)(first_trial + n_rows) > (UINT64_MAX - 1) / (uint64_t)*blocks)
+        return fail(ctx, TLS_E_ARG, "null rows: trial indices past the 64-bit Philox counter");
+    return TLS_OK;
+}
+
+// rows per launch: at most 256 MB of rows, and gridDim.y within its limit
+static int64_t null_slab(int64_t n_rows, size_t row_bytes) {
+    return std::max<int64_t>(1, std::min<int64_t>({n_rows, (int64_t)65535, (int64_t)((256u << 20) / row_bytes)}));
+}
+
+int tls_null_rows(tls_ctx* ctx, int64_t n, int64_t n_rows, uint64_t seed, int64_t first_trial, int mode,
+                  const double* sigma, int64_t n_sigma, const double* src, int64_t n_src, int64_t block, double* out) {
+    if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
+    int64_t blocks = 0;
+    if (int rc = null_check(ctx, n, n_rows, first_trial, mode, block, &blocks)) return rc;
+    if (mode == 0) {
+        if (n_sigma != 1 && n_sigma != n_rows) return fail(ctx, TLS_E_ARG, "null rows: n_sigma must be 1 or n_rows");
+        if (!sigma) return fail(ctx, TLS_E_ARG, "null argument");
+        for (int64_t k = 0; k < n_sigma; ++k)
+            if (!(sigma[k] > 0.0 && sigma[k] <= 0.1))
+                return fail(ctx, TLS_E_ARG, "null rows: sigma " + std::to_string(k) + " outside (0, 0.1]");
+    } else {
+        if (n_src < 1) return fail(ctx, TLS_E_ARG, "null rows: n_src < 1");
+        if (!src) return fail(ctx, TLS_E_ARG, "null argument");
+        if ((uint64_t)n_src > (uint64_t)(SIZE_MAX / 8) / (uint64_t)n) return fail(ctx, TLS_E_ARG, "null rows: source too large");
+        for (size_t k = 0; k < (size_t)n_src * (size_t)n; ++k)
+            if (!(std::isfinite(src[k]) && src[k] > 0.0))
+                return fail(ctx, TLS_E_ARG, "null rows: source row " + std::to_string(k / (size_t)n)
+                                            + " has a non-finite or non-positive value");
+    }
+    if (n_rows == 0) return TLS_OK;
+    if (!out) return fail(ctx, TLS_E_ARG, "null argument");
+    TLS_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t nn = (size_t)n;
+    const int64_t slab = null_slab(n_rows, 8 * nn);
+    const size_t src_len = mode == 1 ? (size_t)n_src * nn : 0;
+    const size_t sigma_len = mode == 0 ? (size_t)n_sigma : 0;
+    // source rows | sigma | rows of one slab
+    TLS_HIP(ctx, ctx->d_null.reserve(src_len + sigma_len + (size_t)slab * nn));
+    double* d_src = ctx->d_null.ptr;
+    double* d_sigma = d_src + src_len;
+    double* d_out = d_sigma + sigma_len;
+    if (src_len) TLS_HIP(ctx, hipMemcpyAsync(d_src, src, src_len * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (sigma_len) TLS_HIP(ctx, hipMemcpyAsync(d_sigma, sigma, sigma_len * 8, hipMemcpyHostToDevice, ctx->stream));
+    for (int64_t k0 = 0; k0 < n_rows; k0 += slab) {
+        const int64_t rows = std::min<int64_t>(slab, n_rows - k0);
+        tlsdev::NullArgs a;
+        a.out = d_out; a.src = d_src; a.seed = (unsigned long long)seed; a.first_trial = (long long)(first_trial + k0);
+        a.blocks = (long long)blocks; a.n_src = (long long)n_src; a.n = (unsigned int)n; a.L = (unsigned int)block;
+        a.sigma_stride = n_sigma == 1 ? 0 : 1;
+        a.sigma = mode == 0 ? d_sigma + (n_sigma == 1 ? 0 : k0) : nullptr;
+        if (mode == 0) {
+            hipLaunchKernelGGL(tlsdev::tls_null_white, dim3((unsigned)((blocks + 255) / 256), (unsigned)rows), dim3(256), 0,
+                               ctx->stream, a);
+            ctx->last_kernel = "tls_null_white";
+        } else {
+            hipLaunchKernelGGL(tlsdev::tls_null_bootstrap, dim3((unsigned)((n + 255) / 256), (unsigned)rows), dim3(256), 0,
+                               ctx->stream, a);
+            ctx->last_kernel = "tls_null_bootstrap";
+        }
+        TLS_HIP(ctx, hipGetLastError());
+        TLS_HIP(ctx, hipMemcpyAsync(out + (size_t)k0 * nn, d_out, (size_t)rows * nn * 8, hipMemcpyDeviceToHost, ctx->stream));
+        // (the next slab overwrites the device rows: the copy above has to be done first)
+        TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return TLS_OK;
+}
+
+int tls_debug_null_words(tls_ctx* ctx, int64_t n, int64_t n_rows, uint64_t seed, int64_t first_trial, int mode,
+                         int64_t block, uint64_t* out) {
+    if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
+    int64_t blocks = 0;
+    if (int rc = null_check(ctx, n, n_rows, first_trial, mode, block, &blocks)) return rc;
+    if (n_rows == 0) return TLS_OK;
+    if (!out) return fail(ctx, TLS_E_ARG, "null argument");
+    TLS_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t W = 4 * (size_t)blocks;
+    const int64_t slab = null_slab(n_rows, 8 * W);
+    TLS_HIP(ctx, ctx->d_null_words.reserve((size_t)slab * W));
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "word width");
+    for (int64_t k0 = 0; k0 < n_rows; k0 += slab) {
+        const int64_t rows = std::min<int64_t>(slab, n_rows - k0);
+        tlsdev::NullArgs a{};
+        a.seed = (unsigned long long)seed; a.first_trial = (long long)(first_trial + k0); a.blocks = (long long)blocks;
+        hipLaunchKernelGGL(tlsdev::tls_null_words, dim3((unsigned)((blocks + 255) / 256), (unsigned)rows), dim3(256), 0,
+                           ctx->stream, a, ctx->d_null_words.ptr);
+        TLS_HIP(ctx, hipGetLastError());
+        ctx->last_kernel = "tls_null_words";
+        TLS_HIP(ctx, hipMemcpyAsync(out + (size_t)k0 * W, ctx->d_null_words.ptr, (size_t)rows * W * 8, hipMemcpyDeviceToHost,
+                                    ctx->stream));
         TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     return TLS_OK;

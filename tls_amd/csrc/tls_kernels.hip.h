@@ -4253,4 +4253,7 @@ __global__ void __launch_bounds__(512) tls_transit_models(const ModelsArgs a) {
 // survey-mode injection (tls_inject_transits)
 #include "tls_inject.hip.h"
 
+// survey-mode null light curves (tls_null_rows)
+#include "tls_null.hip.h"
+
 }  // namespace tlsdev

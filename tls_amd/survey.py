@@ -7,6 +7,8 @@ Across GPUs the light curves are simply dealt out: one process per GPU (bench.py
 (every visible GPU) on the calls below -- contiguous slices of the batch to the contexts of a `tls_amd.search.DeviceGroup`, one host thread each, no
 collective (every light curve's results come back over its own GPU's copy engine).
 """
+import operator
+
 import numpy
 
 from . import search as _search
@@ -562,3 +564,175 @@ def completeness(recovery, period_edges, rp_edges, exclude_untransiting=True):
     with numpy.errstate(invalid="ignore", divide="ignore"):
         fraction = numpy.where(total > 0, recovered / numpy.maximum(total, 1), numpy.nan)
     return fraction, recovered, total
+
+
+# ---- false-alarm calibration: SDE of searches on noise alone --------------------------------------------------------------
+NULL_SIGMA_MAX = 0.1   # (tls_null_rows' bound on the white-noise sigma)
+
+
+def _integer(name, value, lo, hi=None):
+    """int(value) for an integral `value` in [lo, hi); ValueError otherwise."""
+    try:
+        v = operator.index(value)
+    except TypeError:
+        raise ValueError("%s must be an integer, got %r" % (name, value))
+    if v < lo or (hi is not None and v >= hi):
+        raise ValueError("%s must lie in [%d, %s), got %d" % (name, lo, "inf" if hi is None else hi, v))
+    return v
+
+
+def _null_arguments(t, n_trials, sigma, source, block, seed, first_trial):
+    """(t, mode, sigma, source, block, seed, first_trial) checked as tls_null_rows checks them, plus the Philox counter bound
+    of the last trial; sigma a float64 array ([1] or [n_trials]) in mode 0, source [n_src, n] in mode 1."""
+    t = numpy.asarray(t, dtype=numpy.float64)
+    if t.ndim != 1 or len(t) < 1:
+        raise ValueError("t must be a non-empty 1-d array")
+    n = len(t)
+    n_trials = _integer("n_trials", n_trials, 1)
+    seed = _integer("seed", seed, 0, 2 ** 64)
+    first_trial = _integer("first_trial", first_trial, 0)
+    if source is None:
+        if block is not None:
+            raise ValueError("block is the bootstrap's: it needs a source")
+        if sigma is None:
+            raise ValueError("white noise (no source) needs sigma")
+        sigma = numpy.asarray(sigma, dtype=numpy.float64)
+        if sigma.shape not in ((), (n_trials,)):
+            raise ValueError("sigma must be a scalar or have shape [n_trials], got %s" % (sigma.shape,))
+        if not numpy.all((sigma > 0) & (sigma <= NULL_SIGMA_MAX)):
+            raise ValueError("sigma must lie in (0, %g]" % NULL_SIGMA_MAX)
+        sigma = numpy.atleast_1d(sigma)
+        words = 2 * n
+    else:
+        if sigma is not None:
+            raise ValueError("sigma is the white noise's: a bootstrap (source given) takes none")
+        if block is None:
+            raise ValueError("a bootstrap (source given) needs block")
+        block = _integer("block", block, 1, n + 1)
+        source = numpy.asarray(source, dtype=numpy.float64)
+        if source.ndim == 1:
+            source = source[None, :]
+        if source.ndim != 2 or source.shape[1] != n or len(source) < 1:
+            raise ValueError("source must have shape [len(t)] or [n_sources, len(t)], got %s" % (numpy.shape(source),))
+        if not numpy.all(numpy.isfinite(source) & (source > 0)):
+            raise ValueError("source has a non-finite or non-positive value")
+        words = -(-n // block)
+    if first_trial + n_trials > (2 ** 64 - 2) // (-(-words // 4)):
+        raise ValueError("trials first_trial .. first_trial + n_trials - 1 run past the 64-bit Philox counter")
+    return t, (0 if source is None else 1), sigma, source, block, seed, first_trial
+
+
+def null_sde(t, n_trials, sigma=None, source=None, block=None, seed=0, first_trial=0, dy=None, chunk=None, return_rows=False,
+             statistics=False, context=None, device=None, devices=None, **power_kwargs):
+    """Search `n_trials` null (noise-only) light curves formed on the device and return their power_batch summary: the
+    SDE of every search of noise alone, the input of fap_table.
+
+    White noise (source None): row R is 1 + sigma_R z, z standard normals (Box-Muller on numpy's Philox4x64-10 stream);
+    sigma a scalar or [n_trials], each in (0, 0.1].  Block bootstrap (source [n] or [n_sources, n], block L in [1, n]):
+    row R copies source row R mod n_sources in blocks of L points taken from uniformly drawn starts, which keeps the
+    sources' correlated noise on time scales below L and breaks any periodicity.  Row R depends on (seed, R) alone
+    (tls_null_rows: trial R takes its own stretch of the stream), trials being R = first_trial .. first_trial + n_trials
+    - 1, so splitting a calibration into calls over consecutive first_trial gives the same rows.
+
+    Per chunk of `chunk` trials (default: about 256 MB of rows, a multiple of 32) the rows are formed on the call's device
+    (the given context or device, or the group's first one), copied to the host and searched by power_batch (`dy`,
+    `statistics`, `devices` and power_kwargs passed through), so `summary` equals power_batch(t, rows, dy) on the same
+    rows.  dy: None (std of each row, as power() takes it), [n] or [n_trials, n].
+
+    Returns summary, or (summary, rows [n_trials, n]) with return_rows=True."""
+    t, mode, sigma, source, block, seed, first_trial = _null_arguments(t, n_trials, sigma, source, block, seed, first_trial)
+    n_trials, n = int(n_trials), len(t)
+    if dy is not None:
+        dy = numpy.asarray(dy, dtype=numpy.float64)
+        if dy.shape not in ((n,), (n_trials, n)):
+            raise ValueError("dy must be None or have shape [len(t)] or [n_trials, len(t)], got %s" % (dy.shape,))
+        if not numpy.all(numpy.isfinite(dy) & (dy > 0)):
+            raise ValueError("dy must be finite and positive")
+    chunk = _default_chunk(n) if chunk is None else _integer("chunk", chunk, 1)
+    if statistics and not numpy.all(t[1:] >= t[:-1]):
+        raise ValueError("statistics=True needs ascending time stamps t")
+
+    kind, what = _resolve(devices, device, context, n_trials)
+    if kind == "group":
+        null_ctx, lock = what.contexts[0], what._lock
+    else:
+        null_ctx, lock = (context if context is not None else _search.default_context(what)), None
+
+    def rows_of(lo, hi):
+        sig = None if mode == 1 else sigma if len(sigma) == 1 else sigma[lo:hi]
+        return null_ctx.null_rows(n, hi - lo, seed, first_trial + lo, sigma=sig, source=source, block=block)
+
+    summaries, all_rows = [], []
+    for lo in range(0, n_trials, chunk):
+        hi = min(n_trials, lo + chunk)
+        if lock is not None:
+            with lock:
+                rows = rows_of(lo, hi)
+        else:
+            rows = rows_of(lo, hi)
+        dy_rows = None if dy is None else (numpy.broadcast_to(dy, rows.shape) if dy.ndim == 1 else dy[lo:hi])
+        summaries.append(_power_batch(t, rows, dy_rows, context, device, False, devices, statistics, False, False, False,
+                                      power_kwargs)[0])
+        if return_rows:
+            all_rows.append(rows)
+    summary = numpy.concatenate(summaries)
+    if return_rows:
+        return summary, numpy.concatenate(all_rows)
+    return summary
+
+
+def fap_table(null_sde, max_fap=0.1):
+    """A false-alarm table from the SDE of n null searches, in the format of the reference's fap.csv (stats._fap_table):
+    (fap [m + 1], thresholds [m + 1], n) with m = min(n, ceil(max_fap n) + 1), thresholds the m largest SDE ascending and
+    then inf, fap[k] = max(m - k, 1) / n and fap[0] = NaN.  For n = 12495 and max_fap = 0.1 that is the reference's shape
+    (m = 1251).  Every value must be finite (a search without a fit reports SDE 0 and counts as 0)."""
+    x = numpy.asarray(null_sde, dtype=numpy.float64)
+    if x.ndim != 1 or len(x) < 1:
+        raise ValueError("null_sde must be a non-empty 1-d array")
+    if not numpy.all(numpy.isfinite(x)):
+        raise ValueError("null_sde has a non-finite value")
+    max_fap = float(max_fap)
+    if not (0.0 < max_fap <= 1.0):
+        raise ValueError("max_fap must lie in (0, 1]")
+    n = len(x)
+    m = min(n, int(numpy.ceil(max_fap * n)) + 1)
+    thresholds = numpy.append(numpy.sort(x)[n - m:], numpy.inf)
+    fap = numpy.maximum(m - numpy.arange(m + 1), 1) / n
+    fap[0] = numpy.nan
+    return fap, thresholds, n
+
+
+def _fap_of(table):
+    """(fap, thresholds, n) of a fap_table result, checked."""
+    fap, thr, n = table
+    fap, thr, n = numpy.asarray(fap, dtype=numpy.float64), numpy.asarray(thr, dtype=numpy.float64), int(n)
+    if fap.ndim != 1 or fap.shape != thr.shape or len(fap) < 2 or n < 1:
+        raise ValueError("not a fap_table: (fap [m + 1], thresholds [m + 1], n)")
+    if numpy.any(numpy.isnan(thr)) or not numpy.all(thr[1:] >= thr[:-1]) or thr[-1] != numpy.inf:
+        raise ValueError("not a fap_table: the thresholds must ascend and end with inf")
+    return fap, thr, n
+
+
+def empirical_fap(sde, table):
+    """The false-alarm probability of every entry of `sde` under a fap_table, by the reference's rule
+    fap[argmax(thresholds > SDE)] (stats.FAP): NaN below the smallest kept SDE (and for NaN or inf), 1 / n at the top."""
+    fap, thr, _ = _fap_of(table)
+    sde = numpy.asarray(sde, dtype=numpy.float64)
+    flat = sde.ravel()
+    # (ascending thresholds: the first one above SDE is a binary search; none above -- inf or NaN SDE -- gives 0, like argmax)
+    idx = numpy.searchsorted(thr, flat, side="right")
+    idx[(idx >= len(thr)) | numpy.isnan(flat)] = 0
+    out = fap[idx].reshape(sde.shape)
+    return out if out.ndim else out[()]
+
+
+def sde_threshold(table, target_fap):
+    """The smallest SDE x with empirical_fap(x, table) <= target_fap: thresholds[k - 1] for the smallest k >= 1 with
+    fap[k] <= target_fap.  ValueError for a target outside [1 / n, fap[1]] (fap[1] = (m - 1) / n, at least the table's
+    max_fap)."""
+    fap, thr, n = _fap_of(table)
+    target = float(target_fap)
+    if not (1.0 / n <= target <= fap[1]):
+        raise ValueError("target_fap must lie in [1/n, max_fap] = [%.6g, %.6g] of this table, got %r" % (1.0 / n, fap[1], target_fap))
+    k = 1 + int(numpy.argmax(fap[1:] <= target))
+    return float(thr[k - 1])
