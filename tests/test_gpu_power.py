@@ -347,3 +347,35 @@ def test_pink_noise_on_the_device_returns_the_bits_of_the_reference_loop():
     assert search.pink_noise(data[:500], 10, context=ctx) == stats.pink_noise(data[:500], 10)
     with pytest.raises(RuntimeError):
         ctx.pink_noise(data[:10], 11)
+
+
+def test_a_failed_batch_leaves_the_context_as_a_fresh_one():
+    """The failure exit of both batch entries: curve 35 (the second launch group) has per-point dy and every other curve
+    uniform dy, so tls_search_batch and tls_power_batch stop with the mixed-weights error -- tls_power_batch while group 0
+    is still in flight (group g + 1 is formed before group g is consumed).  The same context then gives for a valid batch
+    bit for bit what a fresh context gives, for both calls."""
+    from tls_amd import _lib
+    t, f0, kw = synthetic.config("k2_90d", seed=0)
+    inp = synthetic.search_inputs(t, f0, None, **dict(kw, period_min=5.0, period_max=20.0))
+    y = numpy.stack([inp["y"]] + [synthetic.config("k2_90d", seed=s)[1] for s in range(1, 40)])
+    dy = numpy.tile(inp["dy"], (40, 1))
+    mixed = dy.copy()
+    mixed[35] *= 1.0 + 0.1 * numpy.sin(numpy.arange(len(t)))
+    args = (inp["periods"], inp["table"], inp["params"])
+    ctx, fresh = _lib.Context(0), None
+    try:
+        with pytest.raises(RuntimeError, match="must all have uniform or all have per-point dy"):
+            ctx.search_batch(inp["t"], y, mixed, *args)
+        with pytest.raises(RuntimeError, match="must all have uniform or all have per-point dy"):
+            ctx.power_batch(inp["t"], y, mixed, *args, 30, with_arrays=True, with_power=True)
+        got = ctx.search_batch(inp["t"], y, dy, *args)
+        got_power = ctx.power_batch(inp["t"], y, dy, *args, 30, with_arrays=True, with_power=True, with_spectra=True)
+        fresh = _lib.Context(0)
+        want = fresh.search_batch(inp["t"], y, dy, *args)
+        want_power = fresh.power_batch(inp["t"], y, dy, *args, 30, with_arrays=True, with_power=True, with_spectra=True)
+    finally:
+        ctx.close()
+        if fresh is not None:
+            fresh.close()
+    for a, b in zip(got + got_power, want + want_power):
+        assert a.tobytes() == b.tobytes()

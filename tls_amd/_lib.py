@@ -114,6 +114,11 @@ class ModelTemplate(object):
                 _dp(folded), _dp(model), _dp(lc), _ip(lc_len)]
 
 
+# the per-period arrays of the power-batch entries, in the order of their C arguments, and the arrays of the models stage
+PER_PERIOD_OUTPUTS = ("chi2", "row", "depth", "power", "SR", "power_raw")
+MODEL_OUTPUTS = ("folded", "model_folded", "lightcurve", "lc_len")
+
+
 def _model_outputs(n_c, n, lc_cap):
     return (numpy.empty((n_c, len(FOLDED_FIELDS), n)), numpy.empty((n_c, n)),
             numpy.empty((n_c, len(LIGHTCURVE_FIELDS), int(lc_cap))), numpy.empty(n_c, dtype=numpy.int64))
@@ -426,37 +431,9 @@ class Context(object):
         SDE_raw, chi2_min, period, T0, depth, the argmin/argmax indices, the template row -- from search,
         spectra and final T0 fit on the device (tls_power_batch); optionally the per-period arrays.
         with_spectra: also SR and power_raw (returned as two more arrays behind `power`)."""
-        t, periods = _f8(t), _f8(periods)
-        y_batch = numpy.ascontiguousarray(y_batch, dtype=numpy.float64)
-        dy_batch = numpy.ascontiguousarray(dy_batch, dtype=numpy.float64)
-        if y_batch.ndim != 2 or y_batch.shape != dy_batch.shape or y_batch.shape[1] != len(t):
-            raise ValueError("y_batch and dy_batch must both have shape [n_curves, len(t)]")
-        arrays, tm, pr = self._pack(table, params)
-        n_c, n_p = y_batch.shape[0], len(periods)
-        summary = numpy.zeros(n_c, dtype=POWER_SUMMARY_DTYPE)
-        assert summary.dtype.itemsize == ctypes.sizeof(PowerSummary)
-        chi2 = row = depth = power = None
-        if with_arrays:
-            chi2 = numpy.empty((n_c, n_p), dtype=numpy.float64)
-            row = numpy.empty((n_c, n_p), dtype=numpy.int64)
-            depth = numpy.empty((n_c, n_p), dtype=numpy.float64)
-        SR = power_raw = None
-        if with_power:
-            power = numpy.empty((n_c, n_p), dtype=numpy.float64)
-        if with_spectra:
-            SR = numpy.empty((n_c, n_p), dtype=numpy.float64)
-            power_raw = numpy.empty((n_c, n_p), dtype=numpy.float64)
-        self._invalidate_results()
-        self._check(self._lib.tls_power_batch(
-            self._h, _dp(t), _dp(y_batch), _dp(dy_batch), len(t), n_c, _dp(periods), n_p, ctypes.byref(tm),
-            ctypes.byref(pr), int(median_kernel), summary.ctypes.data_as(ctypes.c_void_p),
-            None if chi2 is None else _dp(chi2), None if row is None else _ip(row),
-            None if depth is None else _dp(depth), None if power is None else _dp(power),
-            None if SR is None else _dp(SR), None if power_raw is None else _dp(power_raw)))
-        self._n_periods = n_p
-        if with_spectra:
-            return summary, chi2, row, depth, power, SR, power_raw
-        return summary, chi2, row, depth, power
+        r = self._power_batch(t, y_batch, dy_batch, periods, table, params, median_kernel, with_arrays=with_arrays,
+                              with_power=with_power, with_spectra=with_spectra)
+        return tuple(r[k] for k in ("summary",) + PER_PERIOD_OUTPUTS[:4 + 2 * bool(with_spectra)])
 
     def power_batch_stats(self, t, y_batch, dy_batch, periods, table, params, median_kernel, fill_factor, root, max_epochs,
                           per_transit=False, with_arrays=False, with_spectra=False, models=None, lc_cap=0):
@@ -465,73 +442,73 @@ class Context(object):
         table.duration is the fractional duration of every template row; root[k] = float(k) ** 0.5, k = 0 .. len(t).
         with_spectra: SR and power_raw [n_curves, n_periods] follow.  models (a ModelTemplate): tls_power_batch_models, and
         (folded [n_curves, 3, n], model_folded [n_curves, n], lightcurve [n_curves, 2, lc_cap], lc_len [n_curves]) follow."""
+        r = self._power_batch(t, y_batch, dy_batch, periods, table, params, median_kernel, with_arrays=with_arrays,
+                              with_power=with_arrays, with_spectra=with_spectra, statistics=(fill_factor, root, max_epochs),
+                              per_transit=per_transit, models=models, lc_cap=lc_cap)
+        names = ("summary", "stats", "per_transit", "n_epochs") + PER_PERIOD_OUTPUTS[:4 + 2 * bool(with_spectra)]
+        return tuple(r[k] for k in names + (MODEL_OUTPUTS if models is not None else ()))
+
+    def _power_batch(self, t, y_batch, dy_batch, periods, table, params, median_kernel, with_arrays=False, with_power=False,
+                     with_spectra=False, statistics=None, per_transit=False, models=None, lc_cap=0):
+        """The three power-batch entries: tls_power_batch; with statistics = (fill_factor, root, max_epochs)
+        tls_power_batch_stats; with models (a ModelTemplate) as well, tls_power_batch_models.  A dict of the outputs by name:
+        summary; chi2, row, depth (with_arrays), power (with_power), SR and power_raw (with_spectra), None where not asked
+        for; with statistics also stats, per_transit and n_epochs (None without per_transit); with models MODEL_OUTPUTS."""
         t, periods = _f8(t), _f8(periods)
         y_batch = numpy.ascontiguousarray(y_batch, dtype=numpy.float64)
         dy_batch = numpy.ascontiguousarray(dy_batch, dtype=numpy.float64)
         if y_batch.ndim != 2 or y_batch.shape != dy_batch.shape or y_batch.shape[1] != len(t):
             raise ValueError("y_batch and dy_batch must both have shape [n_curves, len(t)]")
         arrays, tm, pr = self._pack(table, params)
-        row_duration, root = _f8(table.duration), _f8(root)
-        n_c, n_p, max_epochs = y_batch.shape[0], len(periods), int(max_epochs)
-        summary = numpy.zeros(n_c, dtype=POWER_SUMMARY_DTYPE)
-        stats = numpy.zeros(n_c, dtype=TRANSIT_STATS_DTYPE)
-        assert stats.dtype.itemsize == ctypes.sizeof(TransitStats)
-        rows = numpy.empty((n_c, len(PER_TRANSIT_FIELDS), max_epochs)) if per_transit else None
-        n_epochs = numpy.empty(n_c, dtype=numpy.int64) if per_transit else None
-        chi2 = row = depth = power = SR = power_raw = None
-        if with_arrays:
-            chi2, depth, power = (numpy.empty((n_c, n_p)) for _ in range(3))
-            row = numpy.empty((n_c, n_p), dtype=numpy.int64)
-        if with_spectra:
-            SR, power_raw = numpy.empty((n_c, n_p)), numpy.empty((n_c, n_p))
+        n_c, n_p = y_batch.shape[0], len(periods)
+        out = {"summary": numpy.zeros(n_c, dtype=POWER_SUMMARY_DTYPE)}
+        assert out["summary"].dtype.itemsize == ctypes.sizeof(PowerSummary)
+        wanted = (with_arrays, with_arrays, with_arrays, with_power, with_spectra, with_spectra)
+        for k, want in zip(PER_PERIOD_OUTPUTS, wanted):
+            out[k] = numpy.empty((n_c, n_p), dtype=numpy.int64 if k == "row" else numpy.float64) if want else None
         args = [self._h, _dp(t), _dp(y_batch), _dp(dy_batch), len(t), n_c, _dp(periods), n_p, ctypes.byref(tm),
-                ctypes.byref(pr), int(median_kernel), summary.ctypes.data_as(ctypes.c_void_p),
-                None if chi2 is None else _dp(chi2), None if row is None else _ip(row),
-                None if depth is None else _dp(depth), None if power is None else _dp(power),
-                None if SR is None else _dp(SR), None if power_raw is None else _dp(power_raw),
-                _dp(row_duration), float(fill_factor), _dp(root), len(root), stats.ctypes.data_as(ctypes.c_void_p), max_epochs,
-                None if rows is None else _dp(rows), None if n_epochs is None else _ip(n_epochs)]
+                ctypes.byref(pr), int(median_kernel), out["summary"].ctypes.data_as(ctypes.c_void_p)]
+        args += [None if out[k] is None else _ip(out[k]) if k == "row" else _dp(out[k]) for k in PER_PERIOD_OUTPUTS]
+        entry = self._lib.tls_power_batch
+        if statistics is not None:
+            fill_factor, root, max_epochs = statistics
+            row_duration, root, max_epochs = _f8(table.duration), _f8(root), int(max_epochs)
+            out["stats"] = numpy.zeros(n_c, dtype=TRANSIT_STATS_DTYPE)
+            assert out["stats"].dtype.itemsize == ctypes.sizeof(TransitStats)
+            out["per_transit"] = numpy.empty((n_c, len(PER_TRANSIT_FIELDS), max_epochs)) if per_transit else None
+            out["n_epochs"] = numpy.empty(n_c, dtype=numpy.int64) if per_transit else None
+            args += [_dp(row_duration), float(fill_factor), _dp(root), len(root), out["stats"].ctypes.data_as(ctypes.c_void_p),
+                     max_epochs, None if out["per_transit"] is None else _dp(out["per_transit"]),
+                     None if out["n_epochs"] is None else _ip(out["n_epochs"])]
+            entry = self._lib.tls_power_batch_stats
+            if models is not None:
+                model_out = _model_outputs(n_c, len(t), lc_cap)
+                out.update(zip(MODEL_OUTPUTS, model_out))
+                args += models.args(lc_cap, model_out)
+                entry = self._lib.tls_power_batch_models
         self._invalidate_results()
-        if models is None:
-            self._check(self._lib.tls_power_batch_stats(*args))
-        else:
-            out = _model_outputs(n_c, len(t), lc_cap)
-            self._check(self._lib.tls_power_batch_models(*(args + models.args(lc_cap, out))))
+        self._check(entry(*args))
         self._n_periods = n_p
-        result = (summary, stats, rows, n_epochs, chi2, row, depth, power)
-        if with_spectra:
-            result += (SR, power_raw)
-        if models is not None:
-            result += out
-        return result
+        return out
 
     def debug_transit_stats(self, y_batch, period, T0, best_row, depth, no_fit, index_power, power, row_duration,
                             fill_factor, root, max_epochs):
         """Developer/test entry: the statistics kernel of power_batch_stats on the prepared plan (prepare()) with injected
         picks -- period, T0, best_row, depth, no_fit, index_power per curve, power [n_curves, n_periods] -- and flux
         y_batch [n_curves, n]; (stats, per_transit [n_curves, 6, max_epochs], n_epochs)."""
-        y_batch = numpy.ascontiguousarray(y_batch, dtype=numpy.float64)
-        power = numpy.ascontiguousarray(power, dtype=numpy.float64)
-        n_c = len(y_batch)
-        if y_batch.ndim != 2 or power.shape != (n_c, self._n_periods):
-            raise ValueError("power must have shape [n_curves, n_periods] of the prepared plan, y_batch [n_curves, n]")
-        period, T0, depth = (_f8(numpy.broadcast_to(v, (n_c,))) for v in (period, T0, depth))
-        best_row, no_fit, index_power = (_i8(numpy.broadcast_to(v, (n_c,))) for v in (best_row, no_fit, index_power))
-        row_duration, root, max_epochs = _f8(row_duration), _f8(root), int(max_epochs)
-        stats = numpy.zeros(n_c, dtype=TRANSIT_STATS_DTYPE)
-        rows = numpy.empty((n_c, len(PER_TRANSIT_FIELDS), max_epochs))
-        n_epochs = numpy.empty(n_c, dtype=numpy.int64)
-        self._invalidate_results()
-        self._check(self._lib.tls_debug_transit_stats(
-            self._h, _dp(y_batch), n_c, _dp(period), _dp(T0), _ip(best_row), _dp(depth), _ip(no_fit), _ip(index_power),
-            _dp(power), _dp(row_duration), len(row_duration), float(fill_factor), _dp(root), len(root), max_epochs,
-            stats.ctypes.data_as(ctypes.c_void_p), _dp(rows), _ip(n_epochs)))
-        return stats, rows, n_epochs
+        return self._debug_transit(y_batch, period, T0, best_row, depth, no_fit, index_power, power, row_duration,
+                                   fill_factor, root, max_epochs)
 
     def debug_transit_models(self, y_batch, period, T0, best_row, depth, no_fit, index_power, power, row_duration,
                              fill_factor, root, max_epochs, models, lc_cap):
         """Developer/test entry: the statistics and model stages of power_batch_stats(models=...) on injected picks, as
         debug_transit_stats; (stats, per_transit, n_epochs, folded, model_folded, lightcurve, lc_len)."""
+        return self._debug_transit(y_batch, period, T0, best_row, depth, no_fit, index_power, power, row_duration,
+                                   fill_factor, root, max_epochs, models, lc_cap)
+
+    def _debug_transit(self, y_batch, period, T0, best_row, depth, no_fit, index_power, power, row_duration, fill_factor,
+                       root, max_epochs, models=None, lc_cap=0):
+        """tls_debug_transit_stats, or with models tls_debug_transit_models."""
         y_batch = numpy.ascontiguousarray(y_batch, dtype=numpy.float64)
         power = numpy.ascontiguousarray(power, dtype=numpy.float64)
         n_c = len(y_batch)
@@ -543,12 +520,15 @@ class Context(object):
         stats = numpy.zeros(n_c, dtype=TRANSIT_STATS_DTYPE)
         rows = numpy.empty((n_c, len(PER_TRANSIT_FIELDS), max_epochs))
         n_epochs = numpy.empty(n_c, dtype=numpy.int64)
-        out = _model_outputs(n_c, y_batch.shape[1], lc_cap)
+        args = [self._h, _dp(y_batch), n_c, _dp(period), _dp(T0), _ip(best_row), _dp(depth), _ip(no_fit), _ip(index_power),
+                _dp(power), _dp(row_duration), len(row_duration), float(fill_factor), _dp(root), len(root), max_epochs,
+                stats.ctypes.data_as(ctypes.c_void_p), _dp(rows), _ip(n_epochs)]
+        out = () if models is None else _model_outputs(n_c, y_batch.shape[1], lc_cap)
         self._invalidate_results()
-        self._check(self._lib.tls_debug_transit_models(
-            self._h, _dp(y_batch), n_c, _dp(period), _dp(T0), _ip(best_row), _dp(depth), _ip(no_fit), _ip(index_power),
-            _dp(power), _dp(row_duration), len(row_duration), float(fill_factor), _dp(root), len(root), max_epochs,
-            stats.ctypes.data_as(ctypes.c_void_p), _dp(rows), _ip(n_epochs), *models.args(lc_cap, out)))
+        if models is None:
+            self._check(self._lib.tls_debug_transit_stats(*args))
+        else:
+            self._check(self._lib.tls_debug_transit_models(*(args + models.args(lc_cap, out))))
         return (stats, rows, n_epochs) + out
 
     def _invalidate_results(self):

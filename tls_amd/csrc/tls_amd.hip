@@ -604,6 +604,14 @@ double flux_scatter(const double* y, int64_t n) {
     return (double)std::sqrt((double)(v / (long double)n));
 }
 
+// the search kernel variant of the next launch, from the scatter of its flux (a batch: the mean over the curves of its group)
+void choose_flux_kernels(tls_ctx* ctx, bool uniform, double sigma) {
+    ctx->flux_sigma = sigma;
+    const bool scr_ok = screen_admissible(ctx->resident, uniform, ctx->e_abs_max);
+    ctx->prune_kernel = uniform && pruning_pays(ctx->opt, ctx->host_widths, sigma, ctx->depth_min, ctx->resident, scr_ok);
+    ctx->screen_kernel = screen_pays(ctx->opt, ctx->host_widths, sigma, ctx->depth_min, scr_ok);
+}
+
 // Fast prefix-sum mode: half-width of the band around transit_depth_min inside which the plain scan
 // cannot decide a window -- 1.25 x the bound 2^-53 c_max on |dX/d - mean_reference| (c_max = (n + W) max|flux| bounds the
 // reference's running sum), plus 1e-14 for what the bound leaves out (the plain scan's own rounding, <= ~20 * 2^-53 *
@@ -1219,6 +1227,16 @@ struct ModelsRequest {
     double* out_folded = nullptr; double* out_model_folded = nullptr; double* out_lc = nullptr; int64_t* out_lc_len = nullptr;
     size_t stride(int64_t n) const { return (size_t)tlsdev::kModelsHeader + 4 * (size_t)n + 2 * (size_t)lc_cap; }
 };
+// the two requests from the flat arguments of the C entry points
+StatsRequest stats_request(const double* row_duration, int64_t n_rows, double fill_factor, const double* root, int64_t n_root,
+                           int64_t max_epochs, tls_transit_stats* out, double* out_per_transit, int64_t* out_n_epochs) {
+    return StatsRequest{row_duration, n_rows, fill_factor, root, n_root, max_epochs, out, out_per_transit, out_n_epochs};
+}
+ModelsRequest models_request(const double* curve_t, const double* curve_f, int64_t curve_n, double curve_lo, double curve_hi,
+                             double maxw, int64_t lc_cap, double* out_folded, double* out_model_folded, double* out_lc,
+                             int64_t* out_lc_len) {
+    return ModelsRequest{curve_t, curve_f, curve_n, curve_lo, curve_hi, maxw, lc_cap, out_folded, out_model_folded, out_lc, out_lc_len};
+}
 
 struct ModelsBufs { double *curve = nullptr, *scratch = nullptr, *out = nullptr; size_t scratch_stride = 0, out_stride = 0; bool resident = false; int nb = 0; size_t lds = 0; };
 
@@ -1327,6 +1345,113 @@ int read_summary(tls_ctx* ctx, const double* h_sde, int64_t group, int64_t c, in
         os.SDE_raw = h_sde[2 * c]; os.SDE = h_sde[2 * c + 1]; os.period = pk[3]; os.depth = pk[4]; os.T0 = T0;
     }
     return TLS_OK;
+}
+
+// ---- survey batches (tls_search_batch, tls_power_batch*): groups of up to `group` light curves, ONE search launch each
+using BatchSlot = tls_ctx::BatchSlot;
+
+// the events and the pinned staging of both slots: a group's flux in (stage_group's layout), `out_doubles` of results out
+int reserve_batch_staging(tls_ctx* ctx, int64_t group, size_t nn, size_t out_doubles) {
+    const size_t in_doubles = (size_t)group * nn * (ctx->uniform_w ? 1 : 2) + 2 * (size_t)group;
+    auto grow = [ctx](double*& buf, size_t& cap, size_t doubles) -> int {
+        if (cap >= doubles) return TLS_OK;
+        if (buf) TLS_HIP(ctx, hipHostFree(buf));
+        buf = nullptr; cap = 0;
+        TLS_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&buf), doubles * 8, hipHostMallocDefault));
+        cap = doubles;
+        return TLS_OK;
+    };
+    for (auto& sl : ctx->slot) {
+        for (hipEvent_t* ev : {&sl.ev_in, &sl.ev_kernel, &sl.ev_out})
+            if (!*ev) TLS_HIP(ctx, hipEventCreateWithFlags(ev, hipEventDisableTiming));
+        int rc = grow(sl.h_in, sl.h_in_cap, in_doubles);
+        if (rc || (rc = grow(sl.h_out, sl.h_out_cap, out_doubles))) return rc;
+    }
+    return TLS_OK;
+}
+
+// a slot's device buffers for one group: flux (weights), per-curve constants, search results
+int reserve_batch_slot(tls_ctx* ctx, BatchSlot& sl, int64_t group, size_t nn, size_t np) {
+    const size_t g = (size_t)group;
+    TLS_HIP(ctx, sl.d_y.reserve(g * nn));
+    if (!ctx->uniform_w) TLS_HIP(ctx, sl.d_w.reserve(g * nn));
+    TLS_HIP(ctx, sl.d_S0.reserve(g));
+    TLS_HIP(ctx, sl.d_w0.reserve(g));
+    TLS_HIP(ctx, sl.d_chi2.reserve(g * np));
+    TLS_HIP(ctx, sl.d_row.reserve(g * np));
+    TLS_HIP(ctx, sl.d_depth.reserve(g * np));
+    return TLS_OK;
+}
+
+// a group formed in a slot's pinned h_in (y | w, per-point dy only | S0 | w0; `group` curves each) and what its launch needs
+struct GroupState {
+    int64_t gc = 0;
+    double *y = nullptr, *w = nullptr, *S0 = nullptr, *w0 = nullptr;
+    double sigma_sum = 0, y_max = 0, e_max = 0;   // flux_scatter summed over the curves; largest |y| and |1 - y| (weights_from)
+};
+
+// host side of the group of curves c0 .. c0 + gc: flux, weights, S0 (core.py:127)
+int stage_group(tls_ctx* ctx, BatchSlot& sl, const double* y, const double* dy, int64_t n, int64_t c0, int64_t gc, int64_t group,
+                GroupState& st) {
+    const size_t nn = (size_t)n;
+    const bool uni = ctx->uniform_w;
+    st = GroupState{};
+    st.gc = gc;
+    st.y = sl.h_in; st.w = sl.h_in + (size_t)group * nn;
+    st.S0 = sl.h_in + (size_t)group * nn * (uni ? 1 : 2); st.w0 = st.S0 + group;
+    std::vector<double> w;
+    for (int64_t c = 0; c < gc; ++c) {
+        const double* yc = y + (c0 + c) * n;
+        bool uniform; double w0, S0;
+        weights_from(yc, dy + (c0 + c) * n, n, uniform, w0, w, S0, &st.y_max, &st.e_max);
+        if (uniform != uni) return fail(ctx, TLS_E_ARG, "light curves of a batch must all have uniform or all have per-point dy");
+        st.S0[c] = S0; st.w0[c] = w0;
+        std::memcpy(st.y + (size_t)c * nn, yc, nn * 8);
+        if (!uniform) std::memcpy(st.w + (size_t)c * nn, w.data(), nn * 8);
+        st.sigma_sum += flux_scatter(yc, n);
+    }
+    return TLS_OK;
+}
+
+// the staged group up to a slot's device buffers, on `stream`
+int upload_group(tls_ctx* ctx, BatchSlot& sl, const GroupState& st, size_t nn, hipStream_t stream) {
+    const size_t gc = (size_t)st.gc;
+    TLS_HIP(ctx, hipMemcpyAsync(sl.d_y.ptr, st.y, gc * nn * 8, hipMemcpyHostToDevice, stream));
+    if (!ctx->uniform_w) TLS_HIP(ctx, hipMemcpyAsync(sl.d_w.ptr, st.w, gc * nn * 8, hipMemcpyHostToDevice, stream));
+    TLS_HIP(ctx, hipMemcpyAsync(sl.d_S0.ptr, st.S0, gc * 8, hipMemcpyHostToDevice, stream));
+    TLS_HIP(ctx, hipMemcpyAsync(sl.d_w0.ptr, st.w0, gc * 8, hipMemcpyHostToDevice, stream));
+    return TLS_OK;
+}
+
+// enqueue() back on the context's own buffers
+void unbind_batch_slot(tls_ctx* ctx) {
+    ctx->batch_curves = 1;
+    ctx->over_y = ctx->over_w = ctx->over_S0 = ctx->over_w0 = nullptr;
+    ctx->over_chi2 = nullptr; ctx->over_row = nullptr; ctx->over_depth = nullptr;
+}
+
+// ONE search launch over a staged group whose flux is on slot sl (the fold + sort of a period is shared by the group's curves);
+// the context points at the slot for this call only, whichever way it returns
+int search_group(tls_ctx* ctx, BatchSlot& sl, const GroupState& st) {
+    ctx->S0 = st.S0[0]; ctx->w0 = st.w0[0]; ctx->y_abs_max = st.y_max; ctx->e_abs_max = st.e_max;
+    choose_flux_kernels(ctx, ctx->uniform_w, st.sigma_sum / (double)st.gc);
+    struct Unbind { tls_ctx* ctx; ~Unbind() { unbind_batch_slot(ctx); } } unbind{ctx};
+    ctx->batch_curves = (int)st.gc;
+    ctx->over_y = sl.d_y.ptr; ctx->over_w = ctx->uniform_w ? nullptr : sl.d_w.ptr; ctx->over_S0 = sl.d_S0.ptr; ctx->over_w0 = sl.d_w0.ptr;
+    ctx->over_chi2 = sl.d_chi2.ptr; ctx->over_row = sl.d_row.ptr; ctx->over_depth = sl.d_depth.ptr;
+    return enqueue(ctx, false);
+}
+
+// the one failure exit of both batch entries: nothing still copies into or out of the pinned slots or the caller's arrays
+// (asynchronous copies may be in flight on either stream), no launch override survives, and the context holds no results
+int end_batch(tls_ctx* ctx, int rc) {
+    if (ctx && rc != TLS_OK) {
+        (void)hipStreamSynchronize(ctx->stream);
+        if (ctx->copy_stream) (void)hipStreamSynchronize(ctx->copy_stream);
+        unbind_batch_slot(ctx);
+        ctx->executed = false;
+    }
+    return rc;
 }
 
 // compute units of the first visible device; 256 (MI355X) where no device can be asked (host-only planning)
@@ -1795,13 +1920,7 @@ int tls_prepare(tls_ctx* ctx, const double* t, const double* y, const double* dy
     ctx->uniform_w = uniform; ctx->w0 = w0; ctx->S0 = S0; ctx->depth_min = params->transit_depth_min;
     ctx->host_widths = widths;
     ctx->band_sigma = -1.0; ctx->d_band_now = nullptr;   // (d_band belongs to the previous width table)
-    {
-        const double sigma = flux_sigma;
-        ctx->flux_sigma = sigma;
-        const bool scr_ok = screen_admissible(ctx->resident, uniform, ctx->e_abs_max);
-        ctx->prune_kernel = uniform && pruning_pays(ctx->opt, widths, sigma, params->transit_depth_min, ctx->resident, scr_ok);
-        ctx->screen_kernel = screen_pays(ctx->opt, widths, sigma, params->transit_depth_min, scr_ok);
-    }
+    choose_flux_kernels(ctx, uniform, flux_sigma);
     ctx->plan_counters = pc;
 
     // ONE pinned staging buffer, ONE device allocation, ONE asynchronous copy; nothing is waited for here (the
@@ -1900,13 +2019,7 @@ int update_flux_impl(tls_ctx* ctx, const double* y, const double* dy) {
     weights_from(y, dy, ctx->n, uniform, w0, w, S0, &y_abs_max, &e_abs_max);
     if (uniform != ctx->uniform_w) return kWeightsDiffer;
     ctx->w0 = w0; ctx->S0 = S0; ctx->y_abs_max = y_abs_max; ctx->e_abs_max = e_abs_max;
-    {
-        const double sigma = flux_scatter(y, ctx->n);
-        ctx->flux_sigma = sigma;
-        const bool scr_ok = screen_admissible(ctx->resident, uniform, ctx->e_abs_max);
-        ctx->prune_kernel = uniform && pruning_pays(ctx->opt, ctx->host_widths, sigma, ctx->depth_min, ctx->resident, scr_ok);
-        ctx->screen_kernel = screen_pays(ctx->opt, ctx->host_widths, sigma, ctx->depth_min, scr_ok);
-    }
+    choose_flux_kernels(ctx, uniform, flux_scatter(y, ctx->n));
     const PlanLayout& L = ctx->layout;
     const size_t nn = (size_t)ctx->n;
     int rcs = stage_reserve(ctx, L.total);   // (waits for the previous upload out of the staging buffer)
@@ -2418,9 +2531,8 @@ static int debug_transit_impl(tls_ctx* ctx, const double* y, int64_t n_curves, c
     const PlanKey& k = ctx->key;
     const int64_t n = k.n, n_periods = k.n_periods;
     if (n_periods < 1) return fail(ctx, TLS_E_ARG, "tls_debug_transit_stats needs at least one period");
-    StatsRequest sr;
-    sr.row_duration = row_duration; sr.n_rows = n_rows; sr.fill_factor = fill_factor; sr.root = root; sr.n_root = n_root;
-    sr.max_epochs = max_epochs; sr.out = out_stats; sr.out_per_transit = out_per_transit; sr.out_n_epochs = out_n_epochs;
+    const StatsRequest sr = stats_request(row_duration, n_rows, fill_factor, root, n_root, max_epochs, out_stats, out_per_transit,
+                                          out_n_epochs);
     int rc = check_stats_request(ctx, sr, k.t.data(), n, k.n_rows);
     if (rc || (mr && (rc = check_models_request(ctx, *mr, n)))) return rc;
     const size_t np = (size_t)n_periods, nn = (size_t)n, gc = (size_t)n_curves;
@@ -2485,10 +2597,8 @@ int tls_debug_transit_models(tls_ctx* ctx, const double* y, int64_t n_curves, co
                              double* out_per_transit, int64_t* out_n_epochs, const double* curve_t, const double* curve_f,
                              int64_t curve_n, double curve_lo, double curve_hi, double maxw, int64_t lc_cap,
                              double* out_folded, double* out_model_folded, double* out_lc, int64_t* out_lc_len) {
-    ModelsRequest mr;
-    mr.curve_t = curve_t; mr.curve_f = curve_f; mr.curve_n = curve_n; mr.curve_lo = curve_lo; mr.curve_hi = curve_hi;
-    mr.maxw = maxw; mr.lc_cap = lc_cap;
-    mr.out_folded = out_folded; mr.out_model_folded = out_model_folded; mr.out_lc = out_lc; mr.out_lc_len = out_lc_len;
+    const ModelsRequest mr = models_request(curve_t, curve_f, curve_n, curve_lo, curve_hi, maxw, lc_cap, out_folded,
+                                            out_model_folded, out_lc, out_lc_len);
     return debug_transit_impl(ctx, y, n_curves, period, T0, best_row, depth, no_fit, index_power, power, row_duration, n_rows,
                               fill_factor, root, n_root, max_epochs, out_stats, out_per_transit, out_n_epochs, &mr);
 }
@@ -2633,53 +2743,17 @@ int tls_search(tls_ctx* ctx, const double* t, const double* y, const double* dy,
     return tls_fetch(ctx, out_chi2, out_row, out_depth, counters);
 }
 
-int tls_search_batch(tls_ctx* ctx, const double* t, const double* y, const double* dy, int64_t n, int64_t n_curves,
-                     const double* periods, int64_t n_periods, const tls_template* tmpl, const tls_params* params,
-                     double* out_chi2, int64_t* out_row, double* out_depth) {
-    if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
-    if (n_curves < 0) return fail(ctx, TLS_E_ARG, "negative number of light curves");
-    if (n_curves == 0) return TLS_OK;
-    if (!y || !dy || !out_chi2 || !out_row || !out_depth) return fail(ctx, TLS_E_ARG, "null argument");
-    int rc = tls_prepare(ctx, t, y, dy, n, periods, n_periods, tmpl, params);   // the plan, from the first curve
-    if (rc) return rc;
-    if (n_periods == 0) return TLS_OK;
-    // Curves go to the device in groups: ONE launch searches a whole group, and inside the kernel
-    // the fold + sort of a period is done once for all curves of the group (it depends on t only).
-    // The groups are pipelined over two slots of device and pinned host buffers: while group g is
-    // searched, group g+1 is prepared on the host (weights, S0) and uploaded on a second stream, and the
-    // results of group g-1 travel back and are copied into the caller's arrays.
+// the groups of tls_search_batch, pipelined over two slots of device and pinned host buffers: while group g is searched,
+// group g+1 is formed on the host (weights, S0) and uploaded on a second stream, and the results of group g-1 travel back
+// and are copied into the caller's arrays
+static int search_batch_impl(tls_ctx* ctx, const double* y, const double* dy, int64_t n, int64_t n_curves, int64_t n_periods,
+                             double* out_chi2, int64_t* out_row, double* out_depth) {
     const int64_t group = 32;
     const size_t np = (size_t)n_periods, nn = (size_t)n;
-    const bool uni = ctx->uniform_w;
     if (!ctx->copy_stream) TLS_HIP(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
-    const size_t in_doubles = (size_t)group * nn * (uni ? 1 : 2) + 2 * (size_t)group;
-    const size_t out_doubles = 3 * (size_t)group * np;
-    for (auto& sl : ctx->slot) {
-        if (!sl.ev_in) {
-            TLS_HIP(ctx, hipEventCreateWithFlags(&sl.ev_in, hipEventDisableTiming));
-            TLS_HIP(ctx, hipEventCreateWithFlags(&sl.ev_kernel, hipEventDisableTiming));
-            TLS_HIP(ctx, hipEventCreateWithFlags(&sl.ev_out, hipEventDisableTiming));
-        }
-        if (sl.h_in_cap < in_doubles) {
-            if (sl.h_in) TLS_HIP(ctx, hipHostFree(sl.h_in));
-            sl.h_in = nullptr; sl.h_in_cap = 0;
-            TLS_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&sl.h_in), in_doubles * 8, hipHostMallocDefault));
-            sl.h_in_cap = in_doubles;
-        }
-        if (sl.h_out_cap < out_doubles) {
-            if (sl.h_out) TLS_HIP(ctx, hipHostFree(sl.h_out));
-            sl.h_out = nullptr; sl.h_out_cap = 0;
-            TLS_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&sl.h_out), out_doubles * 8, hipHostMallocDefault));
-            sl.h_out_cap = out_doubles;
-        }
-        TLS_HIP(ctx, sl.d_y.reserve((size_t)group * nn));
-        if (!uni) TLS_HIP(ctx, sl.d_w.reserve((size_t)group * nn));
-        TLS_HIP(ctx, sl.d_S0.reserve((size_t)group));
-        TLS_HIP(ctx, sl.d_w0.reserve((size_t)group));
-        TLS_HIP(ctx, sl.d_chi2.reserve((size_t)group * np));
-        TLS_HIP(ctx, sl.d_row.reserve((size_t)group * np));
-        TLS_HIP(ctx, sl.d_depth.reserve((size_t)group * np));
-    }
+    int rc = reserve_batch_staging(ctx, group, nn, 3 * (size_t)group * np);
+    for (auto& sl : ctx->slot)
+        if (rc || (rc = reserve_batch_slot(ctx, sl, group, nn, np))) return rc;
     TLS_HIP(ctx, ctx->d_perm.reserve((size_t)std::max(ctx->blocks, ctx->slim_blocks) * nn));
     const int64_t n_groups = (n_curves + group - 1) / group;
     auto drain = [&](int64_t g) -> int {   // results of group g: wait for its download, copy to the caller's arrays
@@ -2692,57 +2766,18 @@ int tls_search_batch(tls_ctx* ctx, const double* t, const double* y, const doubl
         std::memcpy(out_depth + c0 * n_periods, sl.h_out + 2 * (size_t)group * np, cnt * 8);
         return TLS_OK;
     };
-    std::vector<double> w;
-    // (every HIP failure inside the pipeline leaves through `run`'s return value: the cleanup below then waits for
-    // both streams -- asynchronous copies may still target the pinned slots and the caller's arrays -- and clears
-    // the launch overrides)
     ctx->batch_group_ms.assign((size_t)n_groups, 0.0);
     ctx->batch_group_wait_ms.clear();
-    auto run = [&]() -> int {
-    int rc = TLS_OK;
-    for (int64_t g = 0; g < n_groups && rc == TLS_OK; ++g) {
+    GroupState st;
+    for (int64_t g = 0; g < n_groups; ++g) {
         auto& sl = ctx->slot[g & 1];
         const int64_t c0 = g * group, gc = std::min(group, n_curves - c0);
         const auto group_t0 = std::chrono::steady_clock::now();   // (pipelined: a group's time is its host loop pass, waits for older groups included)
-        if (g >= 2 && (rc = drain(g - 2))) break;           // the slot's buffers are free again
-        // host side of the group: flux into the pinned staging area, weights, S0 (core.py:127)
-        double* h_y = sl.h_in;
-        double* h_w = sl.h_in + (size_t)group * nn;
-        double* h_S0 = sl.h_in + (size_t)group * nn * (uni ? 1 : 2);
-        double* h_w0 = h_S0 + group;
-        double sigma_sum = 0.0;
-        double group_y_max = 0.0, group_e_max = 0.0;
-        for (int64_t c = 0; c < gc; ++c) {
-            bool uniform; double w0, S0;
-            weights_from(y + (c0 + c) * n, dy + (c0 + c) * n, n, uniform, w0, w, S0, &group_y_max, &group_e_max);
-            if (uniform != uni) { rc = fail(ctx, TLS_E_ARG, "light curves of a batch must all have uniform or all have per-point dy"); break; }
-            h_S0[c] = S0; h_w0[c] = w0;
-            std::memcpy(h_y + (size_t)c * nn, y + (c0 + c) * n, nn * 8);
-            if (!uniform) std::memcpy(h_w + (size_t)c * nn, w.data(), nn * 8);
-            sigma_sum += flux_scatter(y + (c0 + c) * n, n);
-        }
-        if (rc) break;
-        TLS_HIP(ctx, hipMemcpyAsync(sl.d_y.ptr, h_y, (size_t)gc * nn * 8, hipMemcpyHostToDevice, ctx->copy_stream));
-        if (!uni) TLS_HIP(ctx, hipMemcpyAsync(sl.d_w.ptr, h_w, (size_t)gc * nn * 8, hipMemcpyHostToDevice, ctx->copy_stream));
-        TLS_HIP(ctx, hipMemcpyAsync(sl.d_S0.ptr, h_S0, (size_t)gc * 8, hipMemcpyHostToDevice, ctx->copy_stream));
-        TLS_HIP(ctx, hipMemcpyAsync(sl.d_w0.ptr, h_w0, (size_t)gc * 8, hipMemcpyHostToDevice, ctx->copy_stream));
+        if (g >= 2 && (rc = drain(g - 2))) return rc;           // the slot's buffers are free again
+        if ((rc = stage_group(ctx, sl, y, dy, n, c0, gc, group, st)) || (rc = upload_group(ctx, sl, st, nn, ctx->copy_stream))) return rc;
         TLS_HIP(ctx, hipEventRecord(sl.ev_in, ctx->copy_stream));
         TLS_HIP(ctx, hipStreamWaitEvent(ctx->stream, sl.ev_in, 0));
-        ctx->S0 = h_S0[0]; ctx->w0 = h_w0[0]; ctx->y_abs_max = group_y_max; ctx->e_abs_max = group_e_max;
-        {
-            ctx->flux_sigma = sigma_sum / (double)gc;
-            const bool scr_ok = screen_admissible(ctx->resident, uni, ctx->e_abs_max);
-            ctx->prune_kernel = uni && pruning_pays(ctx->opt, ctx->host_widths, sigma_sum / (double)gc, ctx->depth_min, ctx->resident, scr_ok);
-            ctx->screen_kernel = screen_pays(ctx->opt, ctx->host_widths, sigma_sum / (double)gc, ctx->depth_min, scr_ok);
-        }
-        ctx->batch_curves = (int)gc;
-        ctx->over_y = sl.d_y.ptr; ctx->over_w = uni ? nullptr : sl.d_w.ptr; ctx->over_S0 = sl.d_S0.ptr; ctx->over_w0 = sl.d_w0.ptr;
-        ctx->over_chi2 = sl.d_chi2.ptr; ctx->over_row = sl.d_row.ptr; ctx->over_depth = sl.d_depth.ptr;
-        rc = enqueue(ctx, false);
-        ctx->batch_curves = 1;
-        ctx->over_y = ctx->over_w = ctx->over_S0 = ctx->over_w0 = nullptr;
-        ctx->over_chi2 = nullptr; ctx->over_row = nullptr; ctx->over_depth = nullptr;
-        if (rc) break;
+        if ((rc = search_group(ctx, sl, st))) return rc;
         TLS_HIP(ctx, hipEventRecord(sl.ev_kernel, ctx->stream));
         TLS_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, sl.ev_kernel, 0));
         TLS_HIP(ctx, hipMemcpyAsync(sl.h_out, sl.d_chi2.ptr, (size_t)gc * np * 8, hipMemcpyDeviceToHost, ctx->copy_stream));
@@ -2751,21 +2786,25 @@ int tls_search_batch(tls_ctx* ctx, const double* t, const double* y, const doubl
         TLS_HIP(ctx, hipEventRecord(sl.ev_out, ctx->copy_stream));
         ctx->batch_group_ms[(size_t)g] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - group_t0).count();
     }
-    if (rc == TLS_OK)
-        for (int64_t g = std::max<int64_t>(0, n_groups - 2); g < n_groups && rc == TLS_OK; ++g) rc = drain(g);
-    return rc;
-    };
-    rc = run();
-    if (rc != TLS_OK) {
-        (void)hipStreamSynchronize(ctx->stream); (void)hipStreamSynchronize(ctx->copy_stream);
-        ctx->batch_curves = 1;
-        ctx->over_y = ctx->over_w = ctx->over_S0 = ctx->over_w0 = nullptr;
-        ctx->over_chi2 = nullptr; ctx->over_row = nullptr; ctx->over_depth = nullptr;
-    }
+    for (int64_t g = std::max<int64_t>(0, n_groups - 2); g < n_groups; ++g)
+        if ((rc = drain(g))) return rc;
     // the context keeps the plan, but the search ran on the batch slots: a staged execute
     // must be preceded by tls_update_flux or a new tls_prepare
     ctx->executed = false;
-    return rc;
+    return TLS_OK;
+}
+
+int tls_search_batch(tls_ctx* ctx, const double* t, const double* y, const double* dy, int64_t n, int64_t n_curves,
+                     const double* periods, int64_t n_periods, const tls_template* tmpl, const tls_params* params,
+                     double* out_chi2, int64_t* out_row, double* out_depth) {
+    if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
+    if (n_curves < 0) return fail(ctx, TLS_E_ARG, "negative number of light curves");
+    if (n_curves == 0) return TLS_OK;
+    if (!y || !dy || !out_chi2 || !out_row || !out_depth) return fail(ctx, TLS_E_ARG, "null argument");
+    int rc = tls_prepare(ctx, t, y, dy, n, periods, n_periods, tmpl, params);   // the plan, from the first curve
+    if (rc) return rc;
+    if (n_periods == 0) return TLS_OK;
+    return end_batch(ctx, search_batch_impl(ctx, y, dy, n, n_curves, n_periods, out_chi2, out_row, out_depth));
 }
 
 static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, const double* dy, int64_t n, int64_t n_curves,
@@ -2774,14 +2813,12 @@ static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, cons
                             double* out_depth, double* out_power, double* out_SR, double* out_power_raw,
                             const StatsRequest* sr, const ModelsRequest* mr = nullptr);
 
-static int power_batch_finish(tls_ctx* ctx, int rc);
-
 int tls_power_batch(tls_ctx* ctx, const double* t, const double* y, const double* dy, int64_t n, int64_t n_curves,
                     const double* periods, int64_t n_periods, const tls_template* tmpl, const tls_params* params,
                     int64_t median_kernel, tls_power_summary* out_summary, double* out_chi2, int64_t* out_row,
                     double* out_depth, double* out_power, double* out_SR, double* out_power_raw) {
-    return power_batch_finish(ctx, power_batch_impl(ctx, t, y, dy, n, n_curves, periods, n_periods, tmpl, params, median_kernel,
-                                                    out_summary, out_chi2, out_row, out_depth, out_power, out_SR, out_power_raw, nullptr));
+    return end_batch(ctx, power_batch_impl(ctx, t, y, dy, n, n_curves, periods, n_periods, tmpl, params, median_kernel,
+                                           out_summary, out_chi2, out_row, out_depth, out_power, out_SR, out_power_raw, nullptr));
 }
 
 int tls_power_batch_stats(tls_ctx* ctx, const double* t, const double* y, const double* dy, int64_t n, int64_t n_curves,
@@ -2792,13 +2829,12 @@ int tls_power_batch_stats(tls_ctx* ctx, const double* t, const double* y, const 
                           tls_transit_stats* out_stats, int64_t max_epochs, double* out_per_transit, int64_t* out_n_epochs) {
     if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
     if (!t || !tmpl) return fail(ctx, TLS_E_ARG, "null argument");
-    StatsRequest sr;
-    sr.row_duration = row_duration; sr.n_rows = tmpl->n_rows; sr.fill_factor = fill_factor; sr.root = root; sr.n_root = n_root;
-    sr.max_epochs = max_epochs; sr.out = out_stats; sr.out_per_transit = out_per_transit; sr.out_n_epochs = out_n_epochs;
+    const StatsRequest sr = stats_request(row_duration, tmpl->n_rows, fill_factor, root, n_root, max_epochs, out_stats,
+                                          out_per_transit, out_n_epochs);
     const int rc = check_stats_request(ctx, sr, t, n, tmpl->n_rows);
     if (rc) return rc;
-    return power_batch_finish(ctx, power_batch_impl(ctx, t, y, dy, n, n_curves, periods, n_periods, tmpl, params, median_kernel,
-                                                    out_summary, out_chi2, out_row, out_depth, out_power, out_SR, out_power_raw, &sr));
+    return end_batch(ctx, power_batch_impl(ctx, t, y, dy, n, n_curves, periods, n_periods, tmpl, params, median_kernel,
+                                           out_summary, out_chi2, out_row, out_depth, out_power, out_SR, out_power_raw, &sr));
 }
 
 int tls_power_batch_models(tls_ctx* ctx, const double* t, const double* y, const double* dy, int64_t n, int64_t n_curves,
@@ -2812,32 +2848,15 @@ int tls_power_batch_models(tls_ctx* ctx, const double* t, const double* y, const
                            int64_t* out_lc_len) {
     if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
     if (!t || !tmpl) return fail(ctx, TLS_E_ARG, "null argument");
-    StatsRequest sr;
-    sr.row_duration = row_duration; sr.n_rows = tmpl->n_rows; sr.fill_factor = fill_factor; sr.root = root; sr.n_root = n_root;
-    sr.max_epochs = max_epochs; sr.out = out_stats; sr.out_per_transit = out_per_transit; sr.out_n_epochs = out_n_epochs;
-    ModelsRequest mr;
-    mr.curve_t = curve_t; mr.curve_f = curve_f; mr.curve_n = curve_n; mr.curve_lo = curve_lo; mr.curve_hi = curve_hi;
-    mr.maxw = maxw; mr.lc_cap = lc_cap;
-    mr.out_folded = out_folded; mr.out_model_folded = out_model_folded; mr.out_lc = out_lc; mr.out_lc_len = out_lc_len;
+    const StatsRequest sr = stats_request(row_duration, tmpl->n_rows, fill_factor, root, n_root, max_epochs, out_stats,
+                                          out_per_transit, out_n_epochs);
+    const ModelsRequest mr = models_request(curve_t, curve_f, curve_n, curve_lo, curve_hi, maxw, lc_cap, out_folded,
+                                            out_model_folded, out_lc, out_lc_len);
     int rc = check_stats_request(ctx, sr, t, n, tmpl->n_rows);
     if (rc || (rc = check_models_request(ctx, mr, n))) return rc;
-    return power_batch_finish(ctx, power_batch_impl(ctx, t, y, dy, n, n_curves, periods, n_periods, tmpl, params, median_kernel,
-                                                    out_summary, out_chi2, out_row, out_depth, out_power, out_SR, out_power_raw,
-                                                    &sr, &mr));
-}
-
-static int power_batch_finish(tls_ctx* ctx, int rc) {
-    if (ctx && rc != TLS_OK) {
-        // EVERY failure leaves through here: nothing is still copying into or out of the pinned staging buffers or the
-        // caller's arrays, and the context does not keep pointing at a batch slot
-        (void)hipStreamSynchronize(ctx->stream);
-        if (ctx->copy_stream) (void)hipStreamSynchronize(ctx->copy_stream);
-        ctx->batch_curves = 1;
-        ctx->over_y = ctx->over_w = ctx->over_S0 = ctx->over_w0 = nullptr;
-        ctx->over_chi2 = nullptr; ctx->over_row = nullptr; ctx->over_depth = nullptr;
-        ctx->executed = false;
-    }
-    return rc;
+    return end_batch(ctx, power_batch_impl(ctx, t, y, dy, n, n_curves, periods, n_periods, tmpl, params, median_kernel,
+                                           out_summary, out_chi2, out_row, out_depth, out_power, out_SR, out_power_raw,
+                                           &sr, &mr));
 }
 
 static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, const double* dy, int64_t n, int64_t n_curves,
@@ -2857,18 +2876,11 @@ static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, cons
     if (rc) return rc;
     const int64_t group = std::min<int64_t>(32, n_curves);              // (one light curve: the drop-in power() call)
     const size_t np = (size_t)n_periods, nn = (size_t)n;
-    const bool uni = ctx->uniform_w;
     double t_min = t[0], t_max = t[0];
     for (int64_t i = 1; i < n; ++i) { t_min = std::min(t_min, t[i]); t_max = std::max(t_max, t[i]); }
     // device buffers of one group: flux (weights), per-curve constants, search results, spectra, summaries, T0-fit inputs
     auto& sl = ctx->slot[0];
-    TLS_HIP(ctx, sl.d_y.reserve((size_t)group * nn));
-    if (!uni) TLS_HIP(ctx, sl.d_w.reserve((size_t)group * nn));
-    TLS_HIP(ctx, sl.d_S0.reserve((size_t)group));
-    TLS_HIP(ctx, sl.d_w0.reserve((size_t)group));
-    TLS_HIP(ctx, sl.d_chi2.reserve((size_t)group * np));
-    TLS_HIP(ctx, sl.d_row.reserve((size_t)group * np));
-    TLS_HIP(ctx, sl.d_depth.reserve((size_t)group * np));
+    if ((rc = reserve_batch_slot(ctx, sl, group, nn, np))) return rc;
     TLS_HIP(ctx, ctx->d_perm.reserve((size_t)std::max(ctx->blocks, ctx->slim_blocks) * nn));
     int64_t max_len = 1;
     for (int64_t r = 0; r < tmpl->n_rows; ++r) max_len = std::max(max_len, tmpl->length[r]);
@@ -2886,61 +2898,12 @@ static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, cons
     // pinned staging: flux in; summaries, T0 and (on request) the per-period arrays out.  TWO sets (the device buffers are
     // one: the stream runs the groups in order): while the device works on group g the host forms group g + 1 in the other
     // set and enqueues it, THEN waits for g -- the device never waits for the host between two groups (round 6)
-    const size_t in_doubles = (size_t)group * nn * (uni ? 1 : 2) + 2 * (size_t)group;
     const size_t arrays = (out_chi2 ? 3 : 0) + (out_power ? 1 : 0) + (out_SR ? 1 : 0) + (out_power_raw ? 1 : 0);
     const size_t out_doubles = (11 + stats_out + models_out) * (size_t)group + arrays * (size_t)group * np;
-    for (auto& hs : ctx->slot) {
-        if (!hs.ev_out) {
-            TLS_HIP(ctx, hipEventCreateWithFlags(&hs.ev_in, hipEventDisableTiming));
-            TLS_HIP(ctx, hipEventCreateWithFlags(&hs.ev_kernel, hipEventDisableTiming));
-            TLS_HIP(ctx, hipEventCreateWithFlags(&hs.ev_out, hipEventDisableTiming));
-        }
-        if (hs.h_in_cap < in_doubles) {
-            if (hs.h_in) TLS_HIP(ctx, hipHostFree(hs.h_in));
-            hs.h_in = nullptr; hs.h_in_cap = 0;
-            TLS_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&hs.h_in), in_doubles * 8, hipHostMallocDefault));
-            hs.h_in_cap = in_doubles;
-        }
-        if (hs.h_out_cap < out_doubles) {
-            if (hs.h_out) TLS_HIP(ctx, hipHostFree(hs.h_out));
-            hs.h_out = nullptr; hs.h_out_cap = 0;
-            TLS_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&hs.h_out), out_doubles * 8, hipHostMallocDefault));
-            hs.h_out_cap = out_doubles;
-        }
-    }
-    std::vector<double> w;
-    rc = TLS_OK;
+    if ((rc = reserve_batch_staging(ctx, group, nn, out_doubles))) return rc;
     const int64_t n_groups = (n_curves + group - 1) / group;
     ctx->batch_group_ms.assign((size_t)n_groups, 0.0);
     ctx->batch_group_wait_ms.assign((size_t)n_groups, 0.0);
-    // developer aid (TLS_AMD_STALL_DIAG set): per-period shader cycles of every group's search launch; a group whose wait
-    // exceeds a second prints where the cycles went (tools/gpu_stall_probe2.py).  (Not pipelined: a group is waited for at once.)
-    const bool diag = std::getenv("TLS_AMD_STALL_DIAG") != nullptr;
-    DevBuf<unsigned long long> d_diag;
-    if (diag) TLS_HIP(ctx, d_diag.reserve(np));
-    struct GroupState { double sigma_sum, y_max, e_max; };
-    GroupState gs[2];
-    // ---- host side of group g: flux into the pinned staging area, weights, S0 (core.py:127)
-    auto prepare_group = [&](int64_t g) -> int {
-        auto& hs = ctx->slot[g & 1];
-        const int64_t c0 = g * group, gc = std::min(group, n_curves - c0);
-        double* h_y = hs.h_in;
-        double* h_w = hs.h_in + (size_t)group * nn;
-        double* h_S0 = hs.h_in + (size_t)group * nn * (uni ? 1 : 2);
-        double* h_w0 = h_S0 + group;
-        GroupState& st = gs[g & 1];
-        st.sigma_sum = 0.0; st.y_max = 0.0; st.e_max = 0.0;
-        for (int64_t c = 0; c < gc; ++c) {
-            bool uniform; double w0, S0;
-            weights_from(y + (c0 + c) * n, dy + (c0 + c) * n, n, uniform, w0, w, S0, &st.y_max, &st.e_max);
-            if (uniform != uni) return fail(ctx, TLS_E_ARG, "light curves of a batch must all have uniform or all have per-point dy");
-            h_S0[c] = S0; h_w0[c] = w0;
-            std::memcpy(h_y + (size_t)c * nn, y + (c0 + c) * n, nn * 8);
-            if (!uniform) std::memcpy(h_w + (size_t)c * nn, w.data(), nn * 8);
-            st.sigma_sum += flux_scatter(y + (c0 + c) * n, n);
-        }
-        return TLS_OK;
-    };
     // host layout of a group's results (the same in both sets)
     struct OutLayout { double *sde, *pick, *T0, *stats, *chi2, *power, *SR, *praw, *spec3, *models; };
     auto out_layout = [&](int64_t g) -> OutLayout {
@@ -2959,37 +2922,14 @@ static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, cons
         if (mr) o.models = h_next;                       // the models' rows, on request
         return o;
     };
-    // ---- device side of group g, nothing waited for: flux up, search (tls_search_batch's launch: fold + sort shared by the
-    // group), spectra, pick, final T0 fit, results down, an event behind them
+    // ---- group g formed in pinned set g & 1, then its device side, nothing waited for: flux up, search, spectra, pick,
+    // final T0 fit, results down, an event behind them
+    GroupState st;
     auto enqueue_group = [&](int64_t g) -> int {
         auto& hs = ctx->slot[g & 1];
         const int64_t c0 = g * group, gc = std::min(group, n_curves - c0);
-        (void)c0;
-        const GroupState& st = gs[g & 1];
-        double* h_y = hs.h_in;
-        double* h_w = hs.h_in + (size_t)group * nn;
-        double* h_S0 = hs.h_in + (size_t)group * nn * (uni ? 1 : 2);
-        double* h_w0 = h_S0 + group;
-        if (diag) TLS_HIP(ctx, hipMemsetAsync(d_diag.ptr, 0, np * 8, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(sl.d_y.ptr, h_y, (size_t)gc * nn * 8, hipMemcpyHostToDevice, ctx->stream));
-        if (!uni) TLS_HIP(ctx, hipMemcpyAsync(sl.d_w.ptr, h_w, (size_t)gc * nn * 8, hipMemcpyHostToDevice, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(sl.d_S0.ptr, h_S0, (size_t)gc * 8, hipMemcpyHostToDevice, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(sl.d_w0.ptr, h_w0, (size_t)gc * 8, hipMemcpyHostToDevice, ctx->stream));
-        ctx->S0 = h_S0[0]; ctx->w0 = h_w0[0]; ctx->y_abs_max = st.y_max; ctx->e_abs_max = st.e_max;
-        {
-            ctx->flux_sigma = st.sigma_sum / (double)gc;
-            const bool scr_ok = screen_admissible(ctx->resident, uni, ctx->e_abs_max);
-            ctx->prune_kernel = uni && pruning_pays(ctx->opt, ctx->host_widths, st.sigma_sum / (double)gc, ctx->depth_min, ctx->resident, scr_ok);
-            ctx->screen_kernel = screen_pays(ctx->opt, ctx->host_widths, st.sigma_sum / (double)gc, ctx->depth_min, scr_ok);
-        }
-        ctx->batch_curves = (int)gc;
-        ctx->over_y = sl.d_y.ptr; ctx->over_w = uni ? nullptr : sl.d_w.ptr; ctx->over_S0 = sl.d_S0.ptr; ctx->over_w0 = sl.d_w0.ptr;
-        ctx->over_chi2 = sl.d_chi2.ptr; ctx->over_row = sl.d_row.ptr; ctx->over_depth = sl.d_depth.ptr;
-        int rc2 = enqueue(ctx, false, diag, nullptr, nullptr, diag ? d_diag.ptr : nullptr);
-        ctx->batch_curves = 1;
-        ctx->over_y = ctx->over_w = ctx->over_S0 = ctx->over_w0 = nullptr;
-        ctx->over_chi2 = nullptr; ctx->over_row = nullptr; ctx->over_depth = nullptr;
-        if (rc2) return rc2;
+        int rc2 = stage_group(ctx, hs, y, dy, n, c0, gc, group, st);
+        if (rc2 || (rc2 = upload_group(ctx, sl, st, nn, ctx->stream)) || (rc2 = search_group(ctx, sl, st))) return rc2;
         // ---- spectra, pick and final T0 fit of every curve of the group
         rc2 = enqueue_post_search(ctx, pb, gc, sl.d_chi2.ptr, sl.d_row.ptr, sl.d_depth.ptr, sl.d_y.ptr, n, n_periods, median_kernel,
                                   t_min, t_max, params->T0_fit_margin);
@@ -3024,22 +2964,6 @@ static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, cons
         const auto wait_t0 = std::chrono::steady_clock::now();
         TLS_HIP(ctx, hipEventSynchronize(hs.ev_out));
         ctx->batch_group_wait_ms[(size_t)g] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wait_t0).count();
-        if (diag && ctx->batch_group_wait_ms[(size_t)g] > 1000.0) {
-            std::vector<unsigned long long> cyc(np), ph(tlsdev::kPhases);
-            TLS_HIP(ctx, hipMemcpy(cyc.data(), d_diag.ptr, np * 8, hipMemcpyDeviceToHost));
-            TLS_HIP(ctx, hipMemcpy(ph.data(), ctx->d_phase.ptr, ph.size() * 8, hipMemcpyDeviceToHost));
-            std::vector<size_t> idx(np);
-            for (size_t i = 0; i < np; ++i) idx[i] = i;
-            std::sort(idx.begin(), idx.end(), [&](size_t a_, size_t b_) { return cyc[a_] > cyc[b_]; });
-            unsigned long long total = 0;
-            for (auto c : cyc) total += c;
-            std::fprintf(stderr, "[stall diag] group %lld wait %.1f ms: period cycles total %.4g, median %llu; top:", (long long)g,
-                         ctx->batch_group_wait_ms[(size_t)g], (double)total, cyc[idx[np / 2]]);
-            for (size_t k = 0; k < std::min<size_t>(8, np); ++k) std::fprintf(stderr, " p%zu(%.6g d)=%.4g", idx[k], periods[idx[k]], (double)cyc[idx[k]]);
-            std::fprintf(stderr, "\n[stall diag] phases:");
-            for (size_t k = 0; k < ph.size(); ++k) if (ph[k]) std::fprintf(stderr, " %zu:%.4g", k, (double)ph[k]);
-            std::fprintf(stderr, "\n");
-        }
         const OutLayout o = out_layout(g);
         for (int64_t c = 0; c < gc; ++c) {
             const int rc2 = read_summary(ctx, o.sde, group, c, c0 + c, out_summary[c0 + c]);
@@ -3077,21 +3001,12 @@ static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, cons
         last_done = now;
         return TLS_OK;
     };
-    rc = prepare_group(0);
-    if (rc == TLS_OK) rc = enqueue_group(0);
+    rc = enqueue_group(0);
     for (int64_t g = 0; g < n_groups && rc == TLS_OK; ++g) {
-        if (g + 1 < n_groups && !diag) {
-            rc = prepare_group(g + 1);
-            if (rc == TLS_OK) rc = enqueue_group(g + 1);
-            if (rc) break;
-        }
+        if (g + 1 < n_groups && (rc = enqueue_group(g + 1))) break;
         rc = consume_group(g);
-        if (rc == TLS_OK && g + 1 < n_groups && diag) {
-            rc = prepare_group(g + 1);
-            if (rc == TLS_OK) rc = enqueue_group(g + 1);
-        }
     }
-    ctx->executed = false;   // the search ran on the batch slot, see tls_search_batch
+    ctx->executed = false;   // the search ran on the batch slot, see search_batch_impl
     return rc;
 }
 

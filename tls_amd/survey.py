@@ -7,6 +7,7 @@ Across GPUs the light curves are simply dealt out: one process per GPU (bench.py
 (every visible GPU) on the calls below -- contiguous slices of the batch to the contexts of a `tls_amd.search.DeviceGroup`, one host thread each, no
 collective (every light curve's results come back over its own GPU's copy engine).
 """
+import contextlib
 import operator
 
 import numpy
@@ -79,6 +80,20 @@ def _on_devices(group, call, n_curves):
     return [p for p in parts if p is not None]
 
 
+def _run_batch(devices, device, context, n_curves, call):
+    """call(context, lo, hi) -> dict of arrays on the resolved context (the given one, or the device's default context) or on
+    every device's slice of the batch, the slices joined key by key (None stays None).  One part is returned as it is: the
+    padded model rows of a large batch run to hundreds of MB."""
+    kind, what = _resolve(devices, device, context, n_curves)
+    if kind == "group":
+        parts = _on_devices(what, call, n_curves)
+    else:
+        parts = [call(context if context is not None else _search.default_context(what), 0, n_curves)]
+    if len(parts) == 1:
+        return parts[0]
+    return {k: None if v is None else numpy.concatenate([p[k] for p in parts]) for k, v in parts[0].items()}
+
+
 def _max_epochs(t, periods):
     """Most transit epochs any pick on this grid can have (all_transit_times from a T0 in [min t, min t + period])."""
     return int(numpy.ceil((numpy.max(t) - numpy.min(t)) / numpy.min(periods))) + 2
@@ -144,12 +159,12 @@ def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_ar
 
     Returns (summary, periods[, chi2, row, depth, power][, per_transit][, models]): summary is a numpy structured array with
     the fields of tls_power_summary plus "duration" (and the statistics on request)."""
-    return _power_batch(t, flux_batch, dy_batch, context, device, with_arrays, devices, statistics, per_transit, models,
-                        False, power_kwargs)
+    return _power_batch(t, flux_batch, dy_batch, power_kwargs, context=context, device=device, devices=devices,
+                        with_arrays=with_arrays, statistics=statistics, per_transit=per_transit, models=models)
 
 
-def _power_batch(t, flux_batch, dy_batch, context, device, with_arrays, devices, statistics, per_transit, models, spectra,
-                 power_kwargs):
+def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=None, devices=None, with_arrays=False,
+                 statistics=False, per_transit=False, models=False, spectra=False):
     """power_batch; spectra=True (power_results) also returns SR and power_raw [n_curves, n_periods] behind the arrays."""
     models = bool(models)
     per_transit = bool(per_transit or models)
@@ -164,45 +179,25 @@ def _power_batch(t, flux_batch, dy_batch, context, device, with_arrays, devices,
     kernel = osf * C.SDE_MEDIAN_KERNEL_SIZE
     if kernel != int(kernel):
         raise ValueError("oversampling_factor * %d must be an integer" % C.SDE_MEDIAN_KERNEL_SIZE)
-
+    kw = dict(with_arrays=with_arrays, with_power=with_arrays, with_spectra=spectra)
     if statistics:
         from .stats import calculate_fill_factor
         fill_factor = calculate_fill_factor(inp["t"])
         root = numpy.array([float(k) ** 0.5 for k in range(len(inp["t"]) + 1)])   # (Python's pow, as power() forms k ** 0.5)
         max_epochs = _max_epochs(inp["t"], inp["periods"])
-        template = _model_template(inp) if models else None
-        lc_cap = _lc_cap(len(inp["t"]), max_epochs) if models else 0
+        kw.update(statistics=(fill_factor, root, max_epochs), per_transit=per_transit,
+                  models=_model_template(inp) if models else None, lc_cap=_lc_cap(len(inp["t"]), max_epochs) if models else 0)
 
-        def call(ctx, lo, hi):
-            return ctx.power_batch_stats(inp["t"], y_rows[lo:hi], dy_rows[lo:hi], inp["periods"], inp["table"], inp["params"],
-                                         int(kernel), fill_factor, root, max_epochs, per_transit=per_transit,
-                                         with_arrays=with_arrays, with_spectra=spectra, models=template, lc_cap=lc_cap)
-    else:
-        def call(ctx, lo, hi):
-            return ctx.power_batch(inp["t"], y_rows[lo:hi], dy_rows[lo:hi], inp["periods"], inp["table"], inp["params"],
-                                   int(kernel), with_arrays=with_arrays, with_power=with_arrays)
+    def call(ctx, lo, hi):
+        return ctx._power_batch(inp["t"], y_rows[lo:hi], dy_rows[lo:hi], inp["periods"], inp["table"], inp["params"],
+                                int(kernel), **kw)
 
-    kind, what = _resolve(devices, device, context, len(y_rows))
-    if kind == "group":
-        parts = _on_devices(what, call, len(y_rows))
-    else:
-        ctx = context if context is not None else _search.default_context(what)
-        parts = [call(ctx, 0, len(y_rows))]
-    # (one part: its arrays as they are -- the padded model rows of a large batch run to hundreds of MB)
-    out = [None if parts[0][k] is None else parts[0][k] if len(parts) == 1 else numpy.concatenate([p[k] for p in parts])
-           for k in range(len(parts[0]))]
-    if statistics:
-        raw, tstats, rows, n_epochs, chi2, row, depth, power = out[:8]
-        extra = out[8:]
-        if spectra:
-            SR, power_raw = extra[:2]
-            extra = extra[2:]
-    else:
-        raw, chi2, row, depth, power = out
+    out = _run_batch(devices, device, context, len(y_rows), call)
+    raw = out["summary"]
     names = list(raw.dtype.names) + ["duration"]
     fields = [(k, raw.dtype[k]) for k in raw.dtype.names] + [("duration", "f8")]
     if statistics:
-        fields += [(k, "f8") for k in tstats.dtype.names] + [("rp_rs", "f8"), ("FAP", "f8"), ("chi2red_min", "f8")]
+        fields += [(k, "f8") for k in out["stats"].dtype.names] + [("rp_rs", "f8"), ("FAP", "f8"), ("chi2red_min", "f8")]
     summary = numpy.zeros(len(raw), dtype=fields)
     for k in raw.dtype.names:
         summary[k] = raw[k]
@@ -210,8 +205,8 @@ def _power_batch(t, flux_batch, dy_batch, context, device, with_arrays, devices,
     assert names == list(summary.dtype.names)[:len(names)]
     if statistics:
         from .stats import limb_darkening_factor
-        for k in tstats.dtype.names:
-            summary[k] = tstats[k]
+        for k in out["stats"].dtype.names:
+            summary[k] = out["stats"][k]
         # rp_rs_from_depth(1 - depth) curve by curve (numpy's scalar ** 0.5, as power() takes it); NaN without a fit
         factor = limb_darkening_factor(inp["limb_dark"], inp["u"])
         fit = raw["no_fit"] == 0
@@ -221,14 +216,14 @@ def _power_batch(t, flux_batch, dy_batch, context, device, with_arrays, devices,
         summary["chi2red_min"] = raw["chi2_min"] / (len(inp["t"]) - 4)
     result = (summary, inp["periods"])
     if with_arrays:
-        result += (chi2, row, depth, power)
+        result += (out["chi2"], out["row"], out["depth"], out["power"])
     if per_transit:
         from ._lib import PER_TRANSIT_FIELDS
-        pt = {k: rows[:, i, :] for i, k in enumerate(PER_TRANSIT_FIELDS)}
-        pt["n_epochs"] = n_epochs
+        pt = {k: out["per_transit"][:, i, :] for i, k in enumerate(PER_TRANSIT_FIELDS)}
+        pt["n_epochs"] = out["n_epochs"]
         result += (pt,)
     if models:
-        folded, model_folded, lightcurve, lc_len = extra
+        folded, model_folded, lightcurve, lc_len = (out[k] for k in ("folded", "model_folded", "lightcurve", "lc_len"))
         n = len(inp["t"])
         m = dict(folded_phase=folded[:, 0], folded_y=folded[:, 1], model_folded_model=model_folded,
                  model_lightcurve_time=lightcurve[:, 0], model_lightcurve_model=lightcurve[:, 1], lc_len=lc_len,
@@ -240,7 +235,7 @@ def _power_batch(t, flux_batch, dy_batch, context, device, with_arrays, devices,
         m["folded_dy"][no_fit] = numpy.nan
         result += (m,)
     if spectra:
-        result += (SR, power_raw)
+        result += (out["SR"], out["power_raw"])
     return result
 
 
@@ -265,7 +260,8 @@ def power_results(t, flux_batch, dy_batch=None, context=None, device=None, devic
     if dy_batch is not None and numpy.shape(dy_batch) != numpy.shape(flux_batch):
         raise ValueError("dy_batch must have the shape of flux_batch")
     summary, periods, chi2, row, depth, power, pt, m, SR, power_raw = _power_batch(
-        t, flux_batch, dy_batch, context, device, True, devices, True, True, True, True, power_kwargs)
+        t, flux_batch, dy_batch, power_kwargs, context=context, device=device, devices=devices, with_arrays=True,
+        statistics=True, per_transit=True, models=True, spectra=True)
     n = len(m["model_folded_phase"])
     chi2red = chi2 / (n - 4)   # (main.py:210-212)
     out = []
@@ -305,16 +301,11 @@ def search_batch(t, flux_batch, dy_batch=None, context=None, device=None, device
     inp, y_rows, dy_rows = _batch_inputs(t, flux_batch, dy_batch, power_kwargs)
 
     def call(ctx, lo, hi):
-        return ctx.search_batch(inp["t"], y_rows[lo:hi], dy_rows[lo:hi], inp["periods"], inp["table"], inp["params"])
+        return dict(zip(("chi2", "row", "depth"), ctx.search_batch(inp["t"], y_rows[lo:hi], dy_rows[lo:hi], inp["periods"],
+                                                                   inp["table"], inp["params"])))
 
-    kind, what = _resolve(devices, device, context, len(y_rows))
-    if kind == "group":
-        parts = _on_devices(what, call, len(y_rows))
-        chi2, row, depth = (numpy.concatenate([p[k] for p in parts]) for k in range(3))
-    else:
-        ctx = context if context is not None else _search.default_context(what)
-        chi2, row, depth = call(ctx, 0, len(y_rows))
-    return inp["periods"], chi2, row, depth
+    out = _run_batch(devices, device, context, len(y_rows), call)
+    return inp["periods"], out["chi2"], out["row"], out["depth"]
 
 
 # ---- injection-recovery ---------------------------------------------------------------------------------------------------
@@ -441,6 +432,29 @@ def classify_recovery(injections, summary, n_in_transit=None, sde_threshold=7.0,
     return rec
 
 
+def _search_chunks(t, n_rows, chunk, form, dy, return_rows, statistics, context, device, devices, power_kwargs):
+    """power_batch on rows formed on the device chunk by chunk: form(ctx, lo, hi) -> (rows lo .. hi, extra) on the call's
+    device (the given context or device, or the group's first one, under the group's lock), then _power_batch on those rows
+    with dy (None, [n] or [n_rows, n]).  The lists (summaries, extras, rows -- empty without return_rows), one entry a chunk."""
+    kind, what = _resolve(devices, device, context, n_rows)
+    if kind == "group":
+        form_ctx, lock = what.contexts[0], what._lock
+    else:
+        form_ctx, lock = (context if context is not None else _search.default_context(what)), contextlib.nullcontext()
+    summaries, extras, all_rows = [], [], []
+    for lo in range(0, n_rows, chunk):
+        hi = min(n_rows, lo + chunk)
+        with lock:
+            rows, extra = form(form_ctx, lo, hi)
+        dy_rows = None if dy is None else (numpy.broadcast_to(dy, rows.shape) if dy.ndim == 1 else dy[lo:hi])
+        summaries.append(_power_batch(t, rows, dy_rows, power_kwargs, context=context, device=device, devices=devices,
+                                      statistics=statistics)[0])
+        extras.append(extra)
+        if return_rows:
+            all_rows.append(rows)
+    return summaries, extras, all_rows
+
+
 def _default_chunk(n):
     """Injections per chunk: the chunk's rows stay at or below about 256 MB, whole launch groups of 32 where that allows."""
     rows = max(1, (256 << 20) // (8 * max(int(n), 1)))
@@ -490,32 +504,14 @@ def injection_recovery(t, flux, injections, dy=None, inject_u=None, inject_limb_
                       None, sde_threshold, period_tolerance, aliases, epoch_tolerance)
     consts = injection_constants(table)
 
-    kind, what = _resolve(devices, device, context, n_inj)
-    if kind == "group":
-        inject_ctx, lock = what.contexts[0], what._lock
-    else:
-        inject_ctx, lock = (context if context is not None else _search.default_context(what)), None
+    def form(ctx, lo, hi):
+        return ctx.inject_transits(t, flux if flux.ndim == 1 else flux[lo:hi], consts[lo:hi], u1, u2)
 
-    summaries, counts, all_rows = [], [], []
-    for lo in range(0, n_inj, chunk):
-        hi = min(n_inj, lo + chunk)
-        base = flux if flux.ndim == 1 else flux[lo:hi]
-        if lock is not None:
-            with lock:
-                rows, count = inject_ctx.inject_transits(t, base, consts[lo:hi], u1, u2)
-        else:
-            rows, count = inject_ctx.inject_transits(t, base, consts[lo:hi], u1, u2)
-        dy_rows = None if dy is None else (numpy.broadcast_to(dy, rows.shape) if dy.ndim == 1 else dy[lo:hi])
-        summaries.append(_power_batch(t, rows, dy_rows, context, device, False, devices, statistics, False, False, False,
-                                      power_kwargs)[0])
-        counts.append(count)
-        if return_rows:
-            all_rows.append(rows)
-    if summaries:
-        summary = numpy.concatenate(summaries)
-        count = numpy.concatenate(counts)
-    else:
+    summaries, counts, all_rows = _search_chunks(t, n_inj, chunk, form, dy, return_rows, statistics, context, device, devices,
+                                                 power_kwargs)
+    if not summaries:
         raise ValueError("no injections")
+    summary, count = numpy.concatenate(summaries), numpy.concatenate(counts)
     recovery = classify_recovery(table, summary, count, sde_threshold, period_tolerance, aliases, epoch_tolerance)
     if return_rows:
         return recovery, summary, numpy.concatenate(all_rows)
@@ -652,29 +648,12 @@ def null_sde(t, n_trials, sigma=None, source=None, block=None, seed=0, first_tri
     if statistics and not numpy.all(t[1:] >= t[:-1]):
         raise ValueError("statistics=True needs ascending time stamps t")
 
-    kind, what = _resolve(devices, device, context, n_trials)
-    if kind == "group":
-        null_ctx, lock = what.contexts[0], what._lock
-    else:
-        null_ctx, lock = (context if context is not None else _search.default_context(what)), None
-
-    def rows_of(lo, hi):
+    def form(ctx, lo, hi):
         sig = None if mode == 1 else sigma if len(sigma) == 1 else sigma[lo:hi]
-        return null_ctx.null_rows(n, hi - lo, seed, first_trial + lo, sigma=sig, source=source, block=block)
+        return ctx.null_rows(n, hi - lo, seed, first_trial + lo, sigma=sig, source=source, block=block), None
 
-    summaries, all_rows = [], []
-    for lo in range(0, n_trials, chunk):
-        hi = min(n_trials, lo + chunk)
-        if lock is not None:
-            with lock:
-                rows = rows_of(lo, hi)
-        else:
-            rows = rows_of(lo, hi)
-        dy_rows = None if dy is None else (numpy.broadcast_to(dy, rows.shape) if dy.ndim == 1 else dy[lo:hi])
-        summaries.append(_power_batch(t, rows, dy_rows, context, device, False, devices, statistics, False, False, False,
-                                      power_kwargs)[0])
-        if return_rows:
-            all_rows.append(rows)
+    summaries, _, all_rows = _search_chunks(t, n_trials, chunk, form, dy, return_rows, statistics, context, device, devices,
+                                            power_kwargs)
     summary = numpy.concatenate(summaries)
     if return_rows:
         return summary, numpy.concatenate(all_rows)
