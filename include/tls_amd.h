@@ -35,7 +35,8 @@ extern "C" {
  * keeps the two caller-facing switches, the developer switches moved behind tls_debug_set_switch, tls_period_costs takes
  * them as text; 6: tls_transit_stats, tls_power_batch_stats, tls_debug_transit_stats; 7: tls_power_batch_models,
  * tls_debug_transit_models).  A binding compares it with tls_abi_version().  Entries added without changing a layout or
- * signature keep the version (7: tls_inject_transits, tls_null_rows, tls_debug_null_words). */
+ * signature keep the version (7: tls_inject_transits, tls_null_rows, tls_debug_null_words,
+ * tls_medfilt_detrend). */
 #define TLS_AMD_ABI_VERSION 7
 
 #define TLS_OK 0
@@ -372,6 +373,19 @@ int tls_null_rows(tls_ctx *ctx, int64_t n, int64_t n_rows, uint64_t seed, int64_
                   const double *sigma, int64_t n_sigma,
                   const double *src, int64_t n_src, int64_t block,
                   double *out);
+
+/* ---- survey-mode detrending: a median filter on the device ------------------------------------------------------- */
+/* The largest kernel size tls_medfilt_detrend takes (tls_amd._lib.MEDFILT_MAX_KERNEL mirrors it). */
+#define TLS_MEDFILT_MAX_KERNEL 4095
+/* For every row r < n_rows of y [n_rows][n]: out_trend[r] = scipy.signal.medfilt(y[r], kernel) -- the median of the `kernel`
+ * SAMPLES centred on each point, the row padded with zeros at both ends (ndimage.rank_filter(y, kernel // 2, size=kernel,
+ * mode="constant")) -- and out_flat[r] = y[r] / out_trend[r], one IEEE division per point.  The median is a selection, so
+ * both are bit-equal to scipy's.  out_trend may be NULL (not returned).  kernel odd, 1 <= kernel <= n and kernel <=
+ * TLS_MEDFILT_MAX_KERNEL: the padding then never reaches the median, so every trend value is > 0.  TLS_E_ARG for n outside
+ * [1, 1e8], n_rows < 0, an even kernel, one < 1, > n or > TLS_MEDFILT_MAX_KERNEL, and a NaN, infinite or non-positive y;
+ * n_rows == 0 is a no-op. */
+int tls_medfilt_detrend(tls_ctx *ctx, const double *y, int64_t n, int64_t n_rows, int64_t kernel,
+                        double *out_flat, double *out_trend);
 
 /* ---- host-only planning (no GPU needed) ------------------------------------------ */
 /* Trial cells (duration x T0 positions) each period will enumerate: the data-independent

@@ -5,6 +5,7 @@ raised as RuntimeError with the library's message.  No torch, no fallback: if th
 shared library is missing, or no GPU is usable, the error surfaces here.
 """
 import ctypes
+import operator
 import os
 import weakref
 
@@ -18,6 +19,7 @@ LIB_PATH = os.path.join(_HERE, "libtls_amd.so")
 if os.environ.get("TLS_AMD_DEBUG") == "1" and os.environ.get("TLS_AMD_LIB"):
     LIB_PATH = os.environ["TLS_AMD_LIB"]
 ABI_VERSION = 7   # include/tls_amd.h TLS_AMD_ABI_VERSION: checked against the library at load time
+MEDFILT_MAX_KERNEL = 4095   # include/tls_amd.h TLS_MEDFILT_MAX_KERNEL: the largest kernel size tls_medfilt_detrend takes
 
 # every symbol include/tls_amd.h declares (tests check the export list against the header)
 SYMBOLS = (
@@ -26,7 +28,7 @@ SYMBOLS = (
     "tls_synchronize", "tls_fetch", "tls_execute_timed", "tls_plan_info", "tls_last_kernel", "tls_grid_cells", "tls_period_costs", "tls_t0_fit", "tls_pink_noise", "tls_spectra", "tls_kernel_timing", "tls_debug_phase_cycles", "tls_debug_cumsum", "tls_debug_folded", "tls_debug_prefix", "tls_debug_check_counts", "tls_debug_poison_lds", "tls_debug_period_cycles", "tls_debug_batch_group_ms",
     "tls_debug_post_search", "tls_debug_device_bytes", "tls_power_batch_stats", "tls_debug_transit_stats",
     "tls_power_batch_models", "tls_debug_transit_models",
-    "tls_inject_transits", "tls_null_rows", "tls_debug_null_words",
+    "tls_inject_transits", "tls_null_rows", "tls_debug_null_words", "tls_medfilt_detrend",
     "tls_comm_unique_id", "tls_comm_init", "tls_comm_destroy", "tls_comm_info", "tls_comm_allgather_results", "tls_comm_allgather_device", "tls_comm_fetch_gathered",
     "tls_comm_stage_results", "tls_comm_allgather_staged", "tls_comm_fetch_staged",
     "tls_comm_barrier", "tls_comm_max",
@@ -257,6 +259,8 @@ def load():
     lib.tls_null_rows.argtypes = [vp, i64, i64, u64, i64, ci, _c_double_p, i64, _c_double_p, i64, i64, _c_double_p]
     lib.tls_debug_null_words.restype = ci
     lib.tls_debug_null_words.argtypes = [vp, i64, i64, u64, i64, ci, i64, ctypes.POINTER(u64)]
+    lib.tls_medfilt_detrend.restype = ci
+    lib.tls_medfilt_detrend.argtypes = [vp, _c_double_p, i64, i64, i64, _c_double_p, _c_double_p]
     lib.tls_debug_device_bytes.restype = ci
     lib.tls_debug_device_bytes.argtypes = [vp, _c_int64_p, _c_int64_p]
     lib.tls_debug_cumsum.restype = ci
@@ -292,6 +296,40 @@ def load():
     lib.tls_comm_max.argtypes = [vp, _c_double_p]
     _lib = lib
     return lib
+
+
+def medfilt_kernel(kernel, n):
+    """The kernel size as an int, checked as tls_medfilt_detrend checks it for rows of n points; ValueError for an even
+    size, one < 1, > n or > MEDFILT_MAX_KERNEL, and a non-integer or bool (scipy.signal.medfilt only warns for a kernel
+    larger than the row, and returns zeros in the trend there)."""
+    if isinstance(kernel, (bool, numpy.bool_)):
+        raise ValueError("the kernel size must be an odd integer, got %r" % (kernel,))
+    try:
+        k = operator.index(kernel)
+    except TypeError:
+        raise ValueError("the kernel size must be an odd integer, got %r" % (kernel,))
+    if k < 1 or k % 2 == 0:
+        raise ValueError("the kernel size must be odd and >= 1, got %d" % k)
+    if k > n:
+        raise ValueError("the kernel size %d exceeds the %d points of a row" % (k, n))
+    if k > MEDFILT_MAX_KERNEL:
+        raise ValueError("the kernel size %d exceeds MEDFILT_MAX_KERNEL = %d" % (k, MEDFILT_MAX_KERNEL))
+    return k
+
+
+def medfilt_arguments(y, kernel):
+    """(rows [n_rows, n] float64, kernel) from y [n] or [n_rows, n], checked as tls_medfilt_detrend checks them
+    (medfilt_kernel; every value finite and > 0); ValueError otherwise."""
+    rows = numpy.asarray(y, dtype=numpy.float64)
+    if rows.ndim == 1:
+        rows = rows[None, :]
+    if rows.ndim != 2 or not 1 <= rows.shape[1] <= 100000000:
+        raise ValueError("flux must have shape [n] or [n_rows, n] with n in [1, 1e8], got %s" % (numpy.shape(y),))
+    k = medfilt_kernel(kernel, rows.shape[1])
+    # (min and max propagate a NaN, which then fails both comparisons)
+    if rows.size and not (rows.min() > 0.0 and rows.max() < numpy.inf):
+        raise ValueError("flux has a NaN, infinite or non-positive value: the median filter needs flux > 0")
+    return numpy.ascontiguousarray(rows), k
 
 
 def _f8(a):
@@ -642,6 +680,19 @@ class Context(object):
                                                 src.shape[0], int(block), _dp(out)))
         return out
 
+    def medfilt_detrend(self, y, kernel, return_trend=False):
+        """flat = y / trend with trend = scipy.signal.medfilt(y, kernel) (tls_medfilt_detrend: a window of `kernel` samples,
+        zero padding at both ends, bit-equal to scipy) for y [n] or [n_rows, n]; (flat, trend) with return_trend=True.
+        ValueError for the arguments medfilt_arguments refuses."""
+        rows, k = medfilt_arguments(y, kernel)
+        flat = numpy.empty_like(rows)
+        trend = numpy.empty_like(rows) if return_trend else None
+        self._check(self._lib.tls_medfilt_detrend(self._h, _dp(rows), rows.shape[1], rows.shape[0], k, _dp(flat),
+                                                  None if trend is None else _dp(trend)))
+        if numpy.ndim(y) == 1:
+            flat, trend = flat[0], None if trend is None else trend[0]
+        return (flat, trend) if return_trend else flat
+
     def debug_null_words(self, n, n_rows, seed, first_trial=0, block=None):
         """The raw Philox words [n_rows, W] tls_null_rows draws for these trials (tls_debug_null_words): white-noise
         layout when `block` is None, the bootstrap's otherwise."""
@@ -745,7 +796,7 @@ class Context(object):
         if rc < 0:
             self._check(rc)
         names = ("lds_carve", "list_capacity", "dot_window", "predicate_read", "sort_window", "work_item",
-                 "singles_capacity", "tile_stage", "screen_split")
+                 "singles_capacity", "tile_stage", "screen_split", "detrend_slot")
         return bool(rc), dict(zip(names, [int(v) for v in arr]))
 
     def poison_lds(self, word=0x7ff80000):

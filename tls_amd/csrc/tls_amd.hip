@@ -236,6 +236,7 @@ struct tls_ctx {
     DevBuf<unsigned long long> d_inject_count;   // ... and its points in contact per injection
     DevBuf<double> d_null;          // tls_null_rows: source rows | sigma | rows of one slab
     DevBuf<unsigned long long> d_null_words;     // tls_debug_null_words: the words of one slab
+    DevBuf<double> d_detrend;       // tls_medfilt_detrend: rows | flat rows | trend rows of one slab
     size_t list_stride = 0;
     // two-kernel slab path (series in HBM, one light curve): fold kernel + search kernel per batch of periods
     bool split = false;                      // the plan supports it (enqueue uses it for single-curve launches)
@@ -1578,7 +1579,7 @@ void tls_ctx_destroy(tls_ctx* ctx) {
     ctx->d_partials.release(); ctx->d_tiles_done.release(); ctx->d_check.release(); ctx->d_spec.release(); ctx->d_queue.release(); ctx->d_squeue.release(); ctx->d_pqueues.release(); ctx->d_phase.release(); ctx->d_lists.release(); ctx->d_perm.release(); ctx->d_curve_S0.release(); ctx->d_curve_w0.release();
     ctx->d_ft.release(); ctx->d_fy.release(); ctx->d_fsig.release(); ctx->d_fep.release(); ctx->d_fres.release(); ctx->d_fscratch.release(); ctx->d_frot.release(); ctx->d_frperm.release(); ctx->d_pink.release();
     ctx->d_tstats.release(); ctx->d_tranges.release(); ctx->d_models.release(); ctx->d_inject.release(); ctx->d_inject_count.release();
-    ctx->d_null.release(); ctx->d_null_words.release();
+    ctx->d_null.release(); ctx->d_null_words.release(); ctx->d_detrend.release();
     ctx->d_split.release(); ctx->d_park.release(); ctx->d_band.release();
     if (ctx->h_band) (void)hipHostFree(ctx->h_band);
     for (auto& ev : ctx->ev_band) if (ev) (void)hipEventDestroy(ev);
@@ -2271,6 +2272,72 @@ int tls_debug_null_words(tls_ctx* ctx, int64_t n, int64_t n_rows, uint64_t seed,
         ctx->last_kernel = "tls_null_words";
         TLS_HIP(ctx, hipMemcpyAsync(out + (size_t)k0 * W, ctx->d_null_words.ptr, (size_t)rows * W * 8, hipMemcpyDeviceToHost,
                                     ctx->stream));
+        TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return TLS_OK;
+}
+
+static_assert(TLS_MEDFILT_MAX_KERNEL - 1 <= tlsdev::kDetrendMaxSpan / 2, "the largest kernel's span fits kDetrendMaxSpan");
+
+// P (sorted slots, a power of two) of a tile of tls_medfilt_detrend: about 2 (k - 1), so that a tile has as many outputs
+// as halo slots, at least 256 (no fewer than 128 outputs a tile), and no more than the whole row's span needs (small n).
+static int detrend_span(int64_t n, int64_t k) {
+    auto pow2 = [](int64_t v) { int64_t p = 64; while (p < v) p <<= 1; return (int)p; };
+    return std::min(pow2(std::max<int64_t>(2 * (k - 1), 256)), pow2(n + k - 1));
+}
+
+int tls_medfilt_detrend(tls_ctx* ctx, const double* y, int64_t n, int64_t n_rows, int64_t kernel, double* out_flat,
+                        double* out_trend) {
+    if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
+    if (n < 1 || n > 100000000) return fail(ctx, TLS_E_ARG, "medfilt: n out of range [1, 1e8]");
+    if (n_rows < 0) return fail(ctx, TLS_E_ARG, "medfilt: n_rows < 0");
+    if (kernel < 1 || kernel % 2 == 0) return fail(ctx, TLS_E_ARG, "medfilt: the kernel size must be odd and >= 1");
+    if (kernel > n) return fail(ctx, TLS_E_ARG, "medfilt: the kernel size exceeds the row length n");
+    if (kernel > TLS_MEDFILT_MAX_KERNEL)
+        return fail(ctx, TLS_E_ARG, "medfilt: the kernel size exceeds " + std::to_string(TLS_MEDFILT_MAX_KERNEL));
+    if (n_rows == 0) return TLS_OK;
+    if (!y || !out_flat) return fail(ctx, TLS_E_ARG, "null argument");
+    if ((uint64_t)n_rows > (uint64_t)(SIZE_MAX / 8) / (uint64_t)n) return fail(ctx, TLS_E_ARG, "medfilt: rows too large");
+    const size_t nn = (size_t)n;
+    for (size_t q = 0; q < (size_t)n_rows * nn; ++q)
+        if (!(std::isfinite(y[q]) && y[q] > 0.0))
+            return fail(ctx, TLS_E_ARG, "medfilt: row " + std::to_string(q / nn) + " has a non-finite or non-positive value");
+    TLS_HIP(ctx, hipSetDevice(ctx->device));
+    // rows per launch: at most 256 MB of rows (as the injection and null slabs), and gridDim.y within its limit
+    const int64_t slab = std::max<int64_t>(1, std::min<int64_t>({n_rows, (int64_t)65535, (int64_t)((256u << 20) / (8 * nn))}));
+    const int parts = out_trend ? 3 : 2;
+    // rows | flat rows [| trend rows]
+    TLS_HIP(ctx, ctx->d_detrend.reserve((size_t)parts * (size_t)slab * nn));
+    double* d_y = ctx->d_detrend.ptr;
+    double* d_flat = d_y + (size_t)slab * nn;
+    double* d_trend = out_trend ? d_flat + (size_t)slab * nn : nullptr;
+    const int P = detrend_span(n, kernel);
+    const int T = P - (int)(kernel - 1);
+    const size_t lds = (size_t)P * (sizeof(unsigned long long) + sizeof(unsigned int));
+    auto fn = tlsdev::tls_medfilt_detrend;
+    TLS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    tlsdev::DetrendArgs a;
+    a.y = d_y; a.flat = d_flat; a.trend = d_trend; a.check = nullptr;
+    a.n = (long long)n; a.k = (int)kernel; a.span = P; a.tile = T;
+#ifdef TLS_DEBUG_CHECKS
+    if (!ctx->d_check.ptr) {
+        TLS_HIP(ctx, ctx->d_check.reserve(tlsdev::kChecks));
+        TLS_HIP(ctx, hipMemsetAsync(ctx->d_check.ptr, 0, tlsdev::kChecks * sizeof(unsigned long long), ctx->stream));
+    }
+    a.check = ctx->d_check.ptr;
+#endif
+    const unsigned tiles = (unsigned)((n + T - 1) / T);
+    for (int64_t k0 = 0; k0 < n_rows; k0 += slab) {
+        const int64_t rows = std::min<int64_t>(slab, n_rows - k0);
+        const size_t bytes = (size_t)rows * nn * 8;
+        TLS_HIP(ctx, hipMemcpyAsync(d_y, y + (size_t)k0 * nn, bytes, hipMemcpyHostToDevice, ctx->stream));
+        hipLaunchKernelGGL(fn, dim3(tiles, (unsigned)rows), dim3(tlsdev::kDetrendThreads), lds, ctx->stream, a);
+        TLS_HIP(ctx, hipGetLastError());
+        ctx->last_kernel = "tls_medfilt_detrend";
+        TLS_HIP(ctx, hipMemcpyAsync(out_flat + (size_t)k0 * nn, d_flat, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        if (out_trend)
+            TLS_HIP(ctx, hipMemcpyAsync(out_trend + (size_t)k0 * nn, d_trend, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        // (the next slab overwrites the device rows: the copies above have to be done first)
         TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     return TLS_OK;

@@ -86,6 +86,7 @@ enum CheckCode {
     kChkSinglesCap = 6,    // re-listed positions outgrew the row's slots
     kChkTileStage = 7,     // a tile was staged beyond the LDS buffer
     kChkSplit = 8,         // fp32 screen: a sample is not the exact sum of its two fp32 halves
+    kChkDetrend = 9,       // tls_medfilt_detrend: an LDS index outside the staged slots, or a median outside the span
 };
 
 constexpr int kWave = 64;
@@ -4255,5 +4256,8 @@ __global__ void __launch_bounds__(512) tls_transit_models(const ModelsArgs a) {
 
 // survey-mode null light curves (tls_null_rows)
 #include "tls_null.hip.h"
+
+// survey-mode median-filter detrending (tls_medfilt_detrend)
+#include "tls_detrend.hip.h"
 
 }  // namespace tlsdev

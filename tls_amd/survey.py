@@ -134,8 +134,46 @@ def _model_template(inp):
     return ModelTemplate(t_s[first: -first + 1], f_s[first: -first + 1], t_s[first], t_s[-first - 1], maxw)
 
 
+# ---- detrending: a median filter on the device ----------------------------------------------------------------------------
+def detrend_batch(flux_batch, kernel_size=25, return_trend=False, context=None, device=None, devices=None):
+    """flat = flux / scipy.signal.medfilt(flux, kernel_size) for every row of flux_batch ([n] or [n_curves, n]), on the device
+    (tls_medfilt_detrend): the step in front of TLS in the reference's own workflow (its tutorials' y / medfilt(y, 25)).
+
+    The trend is the median of the kernel_size SAMPLES centred on each point -- a window in samples, not in time, blind to
+    gaps -- with the row padded by zeros at both ends, as scipy pads it (ndimage.rank_filter(y, k // 2, size=k,
+    mode="constant")); flat is one IEEE division per point.  Both are bit-equal to scipy's.  kernel_size must be an odd integer
+    in [1, min(n, MEDFILT_MAX_KERNEL)] and every flux value finite and > 0: a kernel longer than the row is an error here
+    (scipy only warns and returns zeros in the trend).  The arguments are checked before any device work.  A median filter of
+    k samples absorbs the middle of any transit longer than about k / 2 samples: keep kernel_size well above the longest
+    duration searched for.
+
+    devices=[...] deals the rows out over several GPUs, as the other survey calls.  Returns flat, or (flat, trend), in the
+    shape of flux_batch."""
+    from ._lib import medfilt_arguments
+    rows, k = medfilt_arguments(flux_batch, kernel_size)
+
+    def call(ctx, lo, hi):
+        out = ctx.medfilt_detrend(rows[lo:hi], k, return_trend=return_trend)
+        return dict(flat=out[0], trend=out[1]) if return_trend else dict(flat=out, trend=None)
+
+    out = _run_batch(devices, device, context, len(rows), call)
+    flat, trend = out["flat"], out["trend"]
+    if numpy.ndim(flux_batch) == 1:
+        flat, trend = flat[0], None if trend is None else trend[0]
+    return (flat, trend) if return_trend else flat
+
+
+def _detrended(t, flux_batch, detrend, context, device, devices):
+    """flux_batch as it is (detrend None), or detrend_batch(flux_batch, detrend) on the call's devices for [n_curves, len(t)]."""
+    if detrend is None:
+        return flux_batch
+    if numpy.ndim(flux_batch) != 2 or numpy.shape(flux_batch)[1] != len(t):
+        raise ValueError("flux_batch must have shape [n_curves, len(t)]")
+    return detrend_batch(flux_batch, detrend, context=context, device=device, devices=devices)
+
+
 def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_arrays=False, devices=None, statistics=False,
-                per_transit=False, models=False, **power_kwargs):
+                per_transit=False, models=False, detrend=None, **power_kwargs):
     """Survey-mode power(): for every light curve of `flux_batch` what `transitleastsquares(t, flux).power(**kwargs)`
     reports as SDE, SDE_raw, chi2_min, period, T0, depth and duration (fractional, lc_cache_overview["duration"] of
     the template row at the chi^2 minimum, main.py:199-200) -- search, SDE spectra and final T0 fit all on the
@@ -157,14 +195,19 @@ def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_ar
     power()'s numpy.argsort leaves the order of equal phases open, for distinct phases the two are the same.  A curve without
     a fit has NaN rows and lc_len 0.
 
+    detrend=k (an odd kernel size) searches flux_batch / medfilt(flux_batch, k) instead (detrend_batch, on the device; the
+    rows come back to the host and go through the search unchanged), so the result equals power_batch on the rows detrended
+    beforehand; dy_batch is passed through as it is.  detrend=None searches flux_batch as given.
+
     Returns (summary, periods[, chi2, row, depth, power][, per_transit][, models]): summary is a numpy structured array with
     the fields of tls_power_summary plus "duration" (and the statistics on request)."""
     return _power_batch(t, flux_batch, dy_batch, power_kwargs, context=context, device=device, devices=devices,
-                        with_arrays=with_arrays, statistics=statistics, per_transit=per_transit, models=models)
+                        with_arrays=with_arrays, statistics=statistics, per_transit=per_transit, models=models,
+                        detrend=detrend)
 
 
 def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=None, devices=None, with_arrays=False,
-                 statistics=False, per_transit=False, models=False, spectra=False):
+                 statistics=False, per_transit=False, models=False, spectra=False, detrend=None):
     """power_batch; spectra=True (power_results) also returns SR and power_raw [n_curves, n_periods] behind the arrays."""
     models = bool(models)
     per_transit = bool(per_transit or models)
@@ -173,6 +216,7 @@ def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=Non
         t_check = numpy.asarray(t, dtype=numpy.float64)
         if t_check.ndim != 1 or not numpy.all(t_check[1:] >= t_check[:-1]):
             raise ValueError("statistics=True needs ascending time stamps t")
+    flux_batch = _detrended(t, flux_batch, detrend, context, device, devices)
     inp, y_rows, dy_rows = _batch_inputs(t, flux_batch, dy_batch, power_kwargs)
     from . import constants as C
     osf = power_kwargs.get("oversampling_factor", C.OVERSAMPLING_FACTOR)
@@ -239,7 +283,7 @@ def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=Non
     return result
 
 
-def power_results(t, flux_batch, dy_batch=None, context=None, device=None, devices=None, **power_kwargs):
+def power_results(t, flux_batch, dy_batch=None, context=None, device=None, devices=None, detrend=None, **power_kwargs):
     """power()'s results object for every light curve of `flux_batch` (shape [n_curves, len(t)], shared ascending time
     stamps): a list of transitleastsquaresresults, element k equal to
     transitleastsquares(t, flux_batch[k], dy_batch[k]).power(**power_kwargs) key for key and in key order (41 keys).  Search,
@@ -252,7 +296,8 @@ def power_results(t, flux_batch, dy_batch=None, context=None, device=None, devic
     Memory: every object holds O(n_periods + n) doubles -- power, power_raw, SR, chi2, chi2red and the folded and model
     arrays, about 0.7 MB for the k2_90d configuration (90 days at 48 cadences a day), so 1024 curves take about 0.7 GB, and
     the call's own staging as much again while it runs.  Callers with large batches pass them in chunks.
-    devices=[...] deals the batch out over several GPUs, as the other survey calls."""
+    devices=[...] deals the batch out over several GPUs, as the other survey calls.  detrend=k searches
+    flux_batch / medfilt(flux_batch, k) (detrend_batch), as power_batch does; the objects then describe the detrended rows."""
     from .api import transitleastsquares
     from .results import transitleastsquaresresults
     if len(numpy.shape(flux_batch)) != 2 or numpy.shape(flux_batch)[1] != len(t):
@@ -261,7 +306,7 @@ def power_results(t, flux_batch, dy_batch=None, context=None, device=None, devic
         raise ValueError("dy_batch must have the shape of flux_batch")
     summary, periods, chi2, row, depth, power, pt, m, SR, power_raw = _power_batch(
         t, flux_batch, dy_batch, power_kwargs, context=context, device=device, devices=devices, with_arrays=True,
-        statistics=True, per_transit=True, models=True, spectra=True)
+        statistics=True, per_transit=True, models=True, spectra=True, detrend=detrend)
     n = len(m["model_folded_phase"])
     chi2red = chi2 / (n - 4)   # (main.py:210-212)
     out = []
@@ -290,14 +335,16 @@ def power_results(t, flux_batch, dy_batch=None, context=None, device=None, devic
     return out
 
 
-def search_batch(t, flux_batch, dy_batch=None, context=None, device=None, devices=None, **power_kwargs):
+def search_batch(t, flux_batch, dy_batch=None, context=None, device=None, devices=None, detrend=None, **power_kwargs):
     """Search every light curve of `flux_batch` (shape [n_curves, n_points]) on the grids that
     `transitleastsquares(t, flux).power(**power_kwargs)` would use.
 
     Returns (periods, chi2[n_curves, n_periods], row[...], depth[...]).  All light curves must
     share `t` and be free of invalid points (clean them first); a `dy_batch` must have the same
-    weight structure for every curve (all uniform or all per-point).
+    weight structure for every curve (all uniform or all per-point).  detrend=k searches flux_batch / medfilt(flux_batch, k)
+    (detrend_batch), as power_batch does.
     """
+    flux_batch = _detrended(t, flux_batch, detrend, context, device, devices)
     inp, y_rows, dy_rows = _batch_inputs(t, flux_batch, dy_batch, power_kwargs)
 
     def call(ctx, lo, hi):
@@ -463,7 +510,7 @@ def _default_chunk(n):
 
 def injection_recovery(t, flux, injections, dy=None, inject_u=None, inject_limb_dark=None, sde_threshold=7.0,
                        period_tolerance=0.01, aliases=(1.0,), epoch_tolerance=None, chunk=None, return_rows=False,
-                       statistics=False, context=None, device=None, devices=None, **power_kwargs):
+                       statistics=False, context=None, device=None, devices=None, detrend=None, **power_kwargs):
     """Injection-recovery in survey mode: inject every planet of `injections` into `flux` on the device
     (tls_inject_transits: flux * transit_model.light_curve(t, T0, period, rp_rs, a, inc, 0, 90, u, law)), search every
     injected light curve with power_batch, and classify each injection (classify_recovery).
@@ -478,6 +525,11 @@ def injection_recovery(t, flux, injections, dy=None, inject_u=None, inject_limb_
     device (the given context or device, or the group's first one), copied to the host, searched by power_batch (with
     `statistics` and `devices` passed through) and classified.  The round trip makes the search's inputs exactly
     power_batch's, so `summary` equals power_batch(t, rows, dy) on the same rows.
+
+    detrend=k (an odd kernel size): `flux` is the RAW light curve, and every injected row is detrended on the same device
+    right after the injection (row / medfilt(row, k), tls_medfilt_detrend) before it is searched, so the transits pass through
+    the filter the data pass through, and completeness counts what the filter absorbs.  rows are then the detrended rows;
+    n_in_transit and the classification are unchanged, and dy is passed through as it is.
 
     Returns (recovery, summary[, rows]): recovery a structured array -- the injected fields, T14, n_in_transit (points
     with z < 1 + rp_rs: 0 where every transit falls into a gap), period_match, epoch_offset, recovered -- and summary
@@ -502,10 +554,14 @@ def injection_recovery(t, flux, injections, dy=None, inject_u=None, inject_limb_
     # (checked before any device work)
     classify_recovery(table[:0], numpy.zeros(0, dtype=[("period", "f8"), ("T0", "f8"), ("SDE", "f8"), ("no_fit", "i8")]),
                       None, sde_threshold, period_tolerance, aliases, epoch_tolerance)
+    if detrend is not None:
+        from ._lib import medfilt_arguments
+        medfilt_arguments(flux, detrend)
     consts = injection_constants(table)
 
     def form(ctx, lo, hi):
-        return ctx.inject_transits(t, flux if flux.ndim == 1 else flux[lo:hi], consts[lo:hi], u1, u2)
+        rows, count = ctx.inject_transits(t, flux if flux.ndim == 1 else flux[lo:hi], consts[lo:hi], u1, u2)
+        return (rows if detrend is None else ctx.medfilt_detrend(rows, detrend)), count
 
     summaries, counts, all_rows = _search_chunks(t, n_inj, chunk, form, dy, return_rows, statistics, context, device, devices,
                                                  power_kwargs)
@@ -619,7 +675,7 @@ def _null_arguments(t, n_trials, sigma, source, block, seed, first_trial):
 
 
 def null_sde(t, n_trials, sigma=None, source=None, block=None, seed=0, first_trial=0, dy=None, chunk=None, return_rows=False,
-             statistics=False, context=None, device=None, devices=None, **power_kwargs):
+             statistics=False, context=None, device=None, devices=None, detrend=None, **power_kwargs):
     """Search `n_trials` null (noise-only) light curves formed on the device and return their power_batch summary: the
     SDE of every search of noise alone, the input of fap_table.
 
@@ -635,6 +691,11 @@ def null_sde(t, n_trials, sigma=None, source=None, block=None, seed=0, first_tri
     `statistics`, `devices` and power_kwargs passed through), so `summary` equals power_batch(t, rows, dy) on the same
     rows.  dy: None (std of each row, as power() takes it), [n] or [n_trials, n].
 
+    detrend=k (an odd kernel size) detrends every null row on the same device right after it is formed (row / medfilt(row, k),
+    tls_medfilt_detrend) and searches the detrended rows: the null of a pipeline that detrends.  A bootstrap then takes RAW
+    source rows, filtered after resampling as the data are.  A row still depends on (seed, R) alone; rows are then the
+    detrended rows, and dy is passed through as it is.
+
     Returns summary, or (summary, rows [n_trials, n]) with return_rows=True."""
     t, mode, sigma, source, block, seed, first_trial = _null_arguments(t, n_trials, sigma, source, block, seed, first_trial)
     n_trials, n = int(n_trials), len(t)
@@ -647,10 +708,14 @@ def null_sde(t, n_trials, sigma=None, source=None, block=None, seed=0, first_tri
     chunk = _default_chunk(n) if chunk is None else _integer("chunk", chunk, 1)
     if statistics and not numpy.all(t[1:] >= t[:-1]):
         raise ValueError("statistics=True needs ascending time stamps t")
+    if detrend is not None:
+        from ._lib import medfilt_kernel
+        medfilt_kernel(detrend, n)
 
     def form(ctx, lo, hi):
         sig = None if mode == 1 else sigma if len(sigma) == 1 else sigma[lo:hi]
-        return ctx.null_rows(n, hi - lo, seed, first_trial + lo, sigma=sig, source=source, block=block), None
+        rows = ctx.null_rows(n, hi - lo, seed, first_trial + lo, sigma=sig, source=source, block=block)
+        return (rows if detrend is None else ctx.medfilt_detrend(rows, detrend)), None
 
     summaries, _, all_rows = _search_chunks(t, n_trials, chunk, form, dy, return_rows, statistics, context, device, devices,
                                             power_kwargs)
