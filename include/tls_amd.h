@@ -36,7 +36,7 @@ extern "C" {
  * them as text; 6: tls_transit_stats, tls_power_batch_stats, tls_debug_transit_stats; 7: tls_power_batch_models,
  * tls_debug_transit_models).  A binding compares it with tls_abi_version().  Entries added without changing a layout or
  * signature keep the version (7: tls_inject_transits, tls_null_rows, tls_debug_null_words,
- * tls_medfilt_detrend). */
+ * tls_medfilt_detrend, tls_biweight_detrend). */
 #define TLS_AMD_ABI_VERSION 7
 
 #define TLS_OK 0
@@ -386,6 +386,29 @@ int tls_null_rows(tls_ctx *ctx, int64_t n, int64_t n_rows, uint64_t seed, int64_
  * n_rows == 0 is a no-op. */
 int tls_medfilt_detrend(tls_ctx *ctx, const double *y, int64_t n, int64_t n_rows, int64_t kernel,
                         double *out_flat, double *out_trend);
+
+/* ---- survey-mode detrending: a time-windowed biweight on the device ---------------------------------------------- */
+/* The most points one window of tls_biweight_detrend may hold (tls_amd._lib.BIWEIGHT_MAX_WINDOW mirrors it), and the
+ * estimator's fixed constants: the tuning constant C, the relative tolerance FTOL and the iteration cap (mirrored as
+ * BIWEIGHT_C, BIWEIGHT_FTOL, BIWEIGHT_MAX_ITER). */
+#define TLS_BIWEIGHT_MAX_WINDOW 4095
+#define TLS_BIWEIGHT_C 5.0
+#define TLS_BIWEIGHT_FTOL 1e-6
+#define TLS_BIWEIGHT_MAX_ITER 50
+/* For every row r < n_rows of y [n_rows][n] at the time stamps t [n] (shared by all rows, non-decreasing):
+ * out_trend[r][i] = Tukey's biweight location of the window of point i and out_flat[r][i] = y[r][i] / out_trend[r][i],
+ * one IEEE division per point.  A new segment starts at every j with t[j] - t[j-1] > break_tolerance (days; INFINITY: never);
+ * the window of i is every j of i's segment with fabs(t[j] - t[i]) <= 0.5 * window_length (days), a contiguous range that
+ * holds i.  In the window's values v: loc = median(v) (the mean (a + b) / 2 of the two middle values for an even count), then
+ * up to TLS_BIWEIGHT_MAX_ITER times: mad = median(|v - loc|), stop if mad == 0; u = (v - loc) / (TLS_BIWEIGHT_C * mad),
+ * w = (1 - u * u)^2 where |u| < 1, else 0; new = sum(w * v) / sum(w), both sums sequential in ascending index; stop after
+ * loc = new if |new - loc| <= TLS_BIWEIGHT_FTOL * |new|.  Every step is one IEEE double operation without contraction, so
+ * the result is bit-equal to a restatement of these lines in numpy; every trend value is > 0 and finite.  out_trend may be
+ * NULL (not returned).  TLS_E_ARG for n outside [1, 1e8], n_rows < 0, a non-finite or decreasing t, a window_length that is
+ * not finite and > 0, a break_tolerance that is not > 0, a window of more than TLS_BIWEIGHT_MAX_WINDOW points, and a NaN,
+ * infinite or non-positive y; n_rows == 0 is a no-op. */
+int tls_biweight_detrend(tls_ctx *ctx, const double *t, const double *y, int64_t n, int64_t n_rows,
+                         double window_length, double break_tolerance, double *out_flat, double *out_trend);
 
 /* ---- host-only planning (no GPU needed) ------------------------------------------ */
 /* Trial cells (duration x T0 positions) each period will enumerate: the data-independent

@@ -5,6 +5,7 @@ raised as RuntimeError with the library's message.  No torch, no fallback: if th
 shared library is missing, or no GPU is usable, the error surfaces here.
 """
 import ctypes
+import numbers
 import operator
 import os
 import weakref
@@ -20,6 +21,11 @@ if os.environ.get("TLS_AMD_DEBUG") == "1" and os.environ.get("TLS_AMD_LIB"):
     LIB_PATH = os.environ["TLS_AMD_LIB"]
 ABI_VERSION = 7   # include/tls_amd.h TLS_AMD_ABI_VERSION: checked against the library at load time
 MEDFILT_MAX_KERNEL = 4095   # include/tls_amd.h TLS_MEDFILT_MAX_KERNEL: the largest kernel size tls_medfilt_detrend takes
+# include/tls_amd.h TLS_BIWEIGHT_*: the most points of one window of tls_biweight_detrend, and the estimator's fixed constants
+BIWEIGHT_MAX_WINDOW = 4095
+BIWEIGHT_C = 5.0
+BIWEIGHT_FTOL = 1e-6
+BIWEIGHT_MAX_ITER = 50
 
 # every symbol include/tls_amd.h declares (tests check the export list against the header)
 SYMBOLS = (
@@ -29,6 +35,7 @@ SYMBOLS = (
     "tls_debug_post_search", "tls_debug_device_bytes", "tls_power_batch_stats", "tls_debug_transit_stats",
     "tls_power_batch_models", "tls_debug_transit_models",
     "tls_inject_transits", "tls_null_rows", "tls_debug_null_words", "tls_medfilt_detrend",
+    "tls_biweight_detrend",
     "tls_comm_unique_id", "tls_comm_init", "tls_comm_destroy", "tls_comm_info", "tls_comm_allgather_results", "tls_comm_allgather_device", "tls_comm_fetch_gathered",
     "tls_comm_stage_results", "tls_comm_allgather_staged", "tls_comm_fetch_staged",
     "tls_comm_barrier", "tls_comm_max",
@@ -261,6 +268,9 @@ def load():
     lib.tls_debug_null_words.argtypes = [vp, i64, i64, u64, i64, ci, i64, ctypes.POINTER(u64)]
     lib.tls_medfilt_detrend.restype = ci
     lib.tls_medfilt_detrend.argtypes = [vp, _c_double_p, i64, i64, i64, _c_double_p, _c_double_p]
+    lib.tls_biweight_detrend.restype = ci
+    lib.tls_biweight_detrend.argtypes = [vp, _c_double_p, _c_double_p, i64, i64, ctypes.c_double, ctypes.c_double,
+                                         _c_double_p, _c_double_p]
     lib.tls_debug_device_bytes.restype = ci
     lib.tls_debug_device_bytes.argtypes = [vp, _c_int64_p, _c_int64_p]
     lib.tls_debug_cumsum.restype = ci
@@ -330,6 +340,74 @@ def medfilt_arguments(y, kernel):
     if rows.size and not (rows.min() > 0.0 and rows.max() < numpy.inf):
         raise ValueError("flux has a NaN, infinite or non-positive value: the median filter needs flux > 0")
     return numpy.ascontiguousarray(rows), k
+
+
+def _days(name, value, allow_inf):
+    """value as a float, > 0 and finite (or +inf where allow_inf); ValueError otherwise (a bool or a non-number included)."""
+    if isinstance(value, (bool, numpy.bool_)) or not isinstance(value, numbers.Real):
+        raise ValueError("%s must be a number of days, got %r" % (name, value))
+    v = float(value)
+    if not (v > 0.0 and (v < numpy.inf or allow_inf)):
+        raise ValueError("%s must be %s, got %r" % (name, "> 0" if allow_inf else "finite and > 0", value))
+    return v
+
+
+def biweight_windows(t, window_length, break_tolerance):
+    """(t, window_length, break_tolerance, lo, hi), checked as tls_biweight_detrend checks them: t 1-D with n in [1, 1e8]
+    points, finite and non-decreasing; window_length finite and > 0; break_tolerance > 0 (inf: never split).  [lo[i], hi[i])
+    is the window of point i: every j of i's segment (a new one starts at every t[j] - t[j-1] > break_tolerance) with
+    abs(t[j] - t[i]) <= 0.5 * window_length, found by bisection with that exact test.  ValueError for a bad argument and for
+    a window of more than BIWEIGHT_MAX_WINDOW points."""
+    wl = _days("window_length", window_length, False)
+    bt = _days("break_tolerance", break_tolerance, True)
+    t = numpy.asarray(t, dtype=numpy.float64)
+    if t.ndim != 1 or not 1 <= len(t) <= 100000000:
+        raise ValueError("t must have shape [n] with n in [1, 1e8], got %s" % (t.shape,))
+    if not numpy.all(numpy.isfinite(t)) or not numpy.all(t[1:] >= t[:-1]):
+        raise ValueError("t must be finite and non-decreasing")
+    t = numpy.ascontiguousarray(t)
+    n = len(t)
+    idx = numpy.arange(n)
+    brk = numpy.ones(n, dtype=bool)
+    brk[1:] = (t[1:] - t[:-1]) > bt
+    starts = numpy.flatnonzero(brk)
+    seg = numpy.cumsum(brk) - 1
+    seg_lo, seg_hi = starts[seg], numpy.append(starts[1:], n)[seg]
+    half = 0.5 * wl
+
+    def bisect(a, b, first_false):
+        # the first j in [a, b) where the test fails (first_false), or the first where it holds; b where there is none
+        while True:
+            act = a < b
+            if not act.any():
+                return a
+            mid = (a + b) // 2
+            ok = numpy.abs(t[numpy.minimum(mid, n - 1)] - t) <= half
+            go_right = ok if first_false else ~ok
+            a = numpy.where(act & go_right, mid + 1, a)
+            b = numpy.where(act & ~go_right, mid, b)
+
+    lo = bisect(seg_lo, idx, False)
+    hi = bisect(idx + 1, seg_hi, True)
+    widest = int((hi - lo).max())
+    if widest > BIWEIGHT_MAX_WINDOW:
+        raise ValueError("a window holds %d points, more than BIWEIGHT_MAX_WINDOW = %d" % (widest, BIWEIGHT_MAX_WINDOW))
+    return t, wl, bt, lo, hi
+
+
+def biweight_arguments(t, y, window_length, break_tolerance):
+    """(t, rows [n_rows, n] float64, window_length, break_tolerance) from y [n] or [n_rows, n] at the time stamps t [n],
+    checked as tls_biweight_detrend checks them (biweight_windows; every flux value finite and > 0); ValueError otherwise."""
+    t, wl, bt, _, _ = biweight_windows(t, window_length, break_tolerance)
+    rows = numpy.asarray(y, dtype=numpy.float64)
+    if rows.ndim == 1:
+        rows = rows[None, :]
+    if rows.ndim != 2 or rows.shape[1] != len(t):
+        raise ValueError("flux must have shape [n] or [n_rows, n] with n = len(t) = %d, got %s" % (len(t), numpy.shape(y)))
+    # (min and max propagate a NaN, which then fails both comparisons)
+    if rows.size and not (rows.min() > 0.0 and rows.max() < numpy.inf):
+        raise ValueError("flux has a NaN, infinite or non-positive value: the biweight filter needs flux > 0")
+    return t, numpy.ascontiguousarray(rows), wl, bt
 
 
 def _f8(a):
@@ -693,6 +771,19 @@ class Context(object):
             flat, trend = flat[0], None if trend is None else trend[0]
         return (flat, trend) if return_trend else flat
 
+    def biweight_detrend(self, t, y, window_length, break_tolerance, return_trend=False):
+        """flat = y / trend with trend the time-windowed biweight location of every point (tls_biweight_detrend: windows of
+        window_length days split at gaps > break_tolerance) for y [n] or [n_rows, n] at the time stamps t [n]; (flat, trend)
+        with return_trend=True.  ValueError for the arguments biweight_arguments refuses."""
+        t, rows, wl, bt = biweight_arguments(t, y, window_length, break_tolerance)
+        flat = numpy.empty_like(rows)
+        trend = numpy.empty_like(rows) if return_trend else None
+        self._check(self._lib.tls_biweight_detrend(self._h, _dp(t), _dp(rows), rows.shape[1], rows.shape[0], wl, bt,
+                                                   _dp(flat), None if trend is None else _dp(trend)))
+        if numpy.ndim(y) == 1:
+            flat, trend = flat[0], None if trend is None else trend[0]
+        return (flat, trend) if return_trend else flat
+
     def debug_null_words(self, n, n_rows, seed, first_trial=0, block=None):
         """The raw Philox words [n_rows, W] tls_null_rows draws for these trials (tls_debug_null_words): white-noise
         layout when `block` is None, the bootstrap's otherwise."""
@@ -796,7 +887,8 @@ class Context(object):
         if rc < 0:
             self._check(rc)
         names = ("lds_carve", "list_capacity", "dot_window", "predicate_read", "sort_window", "work_item",
-                 "singles_capacity", "tile_stage", "screen_split", "detrend_slot")
+                 "singles_capacity", "tile_stage", "screen_split", "detrend_slot",
+                 "biweight_slot")
         return bool(rc), dict(zip(names, [int(v) for v in arr]))
 
     def poison_lds(self, word=0x7ff80000):

@@ -236,7 +236,8 @@ struct tls_ctx {
     DevBuf<unsigned long long> d_inject_count;   // ... and its points in contact per injection
     DevBuf<double> d_null;          // tls_null_rows: source rows | sigma | rows of one slab
     DevBuf<unsigned long long> d_null_words;     // tls_debug_null_words: the words of one slab
-    DevBuf<double> d_detrend;       // tls_medfilt_detrend: rows | flat rows | trend rows of one slab
+    DevBuf<double> d_detrend;       // tls_medfilt_detrend, tls_biweight_detrend: rows | flat rows | trend rows of one slab
+    DevBuf<int> d_windows;          // tls_biweight_detrend: lo [n] | hi [n], the window of every point
     size_t list_stride = 0;
     // two-kernel slab path (series in HBM, one light curve): fold kernel + search kernel per batch of periods
     bool split = false;                      // the plan supports it (enqueue uses it for single-curve launches)
@@ -1579,7 +1580,7 @@ void tls_ctx_destroy(tls_ctx* ctx) {
     ctx->d_partials.release(); ctx->d_tiles_done.release(); ctx->d_check.release(); ctx->d_spec.release(); ctx->d_queue.release(); ctx->d_squeue.release(); ctx->d_pqueues.release(); ctx->d_phase.release(); ctx->d_lists.release(); ctx->d_perm.release(); ctx->d_curve_S0.release(); ctx->d_curve_w0.release();
     ctx->d_ft.release(); ctx->d_fy.release(); ctx->d_fsig.release(); ctx->d_fep.release(); ctx->d_fres.release(); ctx->d_fscratch.release(); ctx->d_frot.release(); ctx->d_frperm.release(); ctx->d_pink.release();
     ctx->d_tstats.release(); ctx->d_tranges.release(); ctx->d_models.release(); ctx->d_inject.release(); ctx->d_inject_count.release();
-    ctx->d_null.release(); ctx->d_null_words.release(); ctx->d_detrend.release();
+    ctx->d_null.release(); ctx->d_null_words.release(); ctx->d_detrend.release(); ctx->d_windows.release();
     ctx->d_split.release(); ctx->d_park.release(); ctx->d_band.release();
     if (ctx->h_band) (void)hipHostFree(ctx->h_band);
     for (auto& ev : ctx->ev_band) if (ev) (void)hipEventDestroy(ev);
@@ -2338,6 +2339,105 @@ int tls_medfilt_detrend(tls_ctx* ctx, const double* y, int64_t n, int64_t n_rows
         if (out_trend)
             TLS_HIP(ctx, hipMemcpyAsync(out_trend + (size_t)k0 * nn, d_trend, bytes, hipMemcpyDeviceToHost, ctx->stream));
         // (the next slab overwrites the device rows: the copies above have to be done first)
+        TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return TLS_OK;
+}
+
+static_assert(2 * (TLS_BIWEIGHT_MAX_WINDOW - 1) + 4 <= tlsdev::kDetrendMaxSpan, "a tile at the largest window holds 4 outputs");
+static_assert(12 * tlsdev::kDetrendMaxSpan + 8 * tlsdev::kDetrendMaxSpan <= 160 * 1024, "the largest span fits the LDS");
+
+// The tiles of tls_biweight_detrend, from the windows [lo_i, hi_i) of the call (at most wmax points each).  P0 = about
+// 4 (wmax - 1), at least 256 and at most kDetrendMaxSpan; a row of n <= P0 points is one tile, otherwise a tile has
+// T = P0 - 2 (wmax - 1) outputs, so that its span [lo_first, hi_last) holds at most T + 2 (wmax - 1) = P0 slots (lo_i >=
+// i - (wmax - 1), hi_i <= i + wmax).  smax is the largest span of the call's tiles and P the power of two (>= 64) that sorts it.
+static void biweight_plan(const std::vector<int>& lo, const std::vector<int>& hi, int64_t wmax, int* T, int* P, int* smax) {
+    auto pow2 = [](int64_t v) { int64_t p = 64; while (p < v) p <<= 1; return (int)p; };
+    const int64_t n = (int64_t)lo.size();
+    const int64_t P0 = std::min<int64_t>(pow2(std::max<int64_t>(4 * (wmax - 1), 256)), tlsdev::kDetrendMaxSpan);
+    const int64_t tile = n <= P0 ? n : P0 - 2 * (wmax - 1);
+    int64_t s = 1;
+    for (int64_t f = 0; f < n; f += tile) s = std::max<int64_t>(s, hi[std::min(f + tile, n) - 1] - lo[f]);
+    *T = (int)tile;
+    *smax = (int)s;
+    *P = pow2(s);
+}
+
+int tls_biweight_detrend(tls_ctx* ctx, const double* t, const double* y, int64_t n, int64_t n_rows, double window_length,
+                         double break_tolerance, double* out_flat, double* out_trend) {
+    if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
+    if (n < 1 || n > 100000000) return fail(ctx, TLS_E_ARG, "biweight: n out of range [1, 1e8]");
+    if (n_rows < 0) return fail(ctx, TLS_E_ARG, "biweight: n_rows < 0");
+    if (!(std::isfinite(window_length) && window_length > 0.0))
+        return fail(ctx, TLS_E_ARG, "biweight: window_length must be finite and > 0");
+    if (!(break_tolerance > 0.0)) return fail(ctx, TLS_E_ARG, "biweight: break_tolerance must be > 0");
+    if (!t) return fail(ctx, TLS_E_ARG, "null argument");
+    for (int64_t i = 0; i < n; ++i)
+        if (!std::isfinite(t[i]) || (i > 0 && !(t[i] >= t[i - 1])))
+            return fail(ctx, TLS_E_ARG, "biweight: t must be finite and non-decreasing (index " + std::to_string(i) + ")");
+    // the windows: [lo_i, hi_i) inside i's segment, |t[j] - t[i]| <= window_length / 2 (both ends only move forward)
+    std::vector<int> lo((size_t)n), hi((size_t)n);
+    const double half = 0.5 * window_length;
+    int64_t seg = 0, wlo = 0, whi = 0, wmax = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        if (i > 0 && t[i] - t[i - 1] > break_tolerance) seg = i;
+        wlo = std::max(wlo, seg);
+        while (std::fabs(t[wlo] - t[i]) > half) ++wlo;
+        whi = std::max(whi, i + 1);
+        while (whi < n && !(t[whi] - t[whi - 1] > break_tolerance) && std::fabs(t[whi] - t[i]) <= half) ++whi;
+        lo[(size_t)i] = (int)wlo;
+        hi[(size_t)i] = (int)whi;
+        wmax = std::max(wmax, whi - wlo);
+    }
+    if (wmax > TLS_BIWEIGHT_MAX_WINDOW)
+        return fail(ctx, TLS_E_ARG, "biweight: a window holds " + std::to_string(wmax) + " points, more than " +
+                                        std::to_string(TLS_BIWEIGHT_MAX_WINDOW));
+    if (n_rows == 0) return TLS_OK;
+    if (!y || !out_flat) return fail(ctx, TLS_E_ARG, "null argument");
+    if ((uint64_t)n_rows > (uint64_t)(SIZE_MAX / 8) / (uint64_t)n) return fail(ctx, TLS_E_ARG, "biweight: rows too large");
+    const size_t nn = (size_t)n;
+    for (size_t q = 0; q < (size_t)n_rows * nn; ++q)
+        if (!(std::isfinite(y[q]) && y[q] > 0.0))
+            return fail(ctx, TLS_E_ARG, "biweight: row " + std::to_string(q / nn) + " has a non-finite or non-positive value");
+    TLS_HIP(ctx, hipSetDevice(ctx->device));
+    // rows per launch: at most 256 MB of rows (as the median filter's slabs), and gridDim.y within its limit
+    const int64_t slab = std::max<int64_t>(1, std::min<int64_t>({n_rows, (int64_t)65535, (int64_t)((256u << 20) / (8 * nn))}));
+    const int parts = out_trend ? 3 : 2;
+    TLS_HIP(ctx, ctx->d_detrend.reserve((size_t)parts * (size_t)slab * nn));
+    TLS_HIP(ctx, ctx->d_windows.reserve(2 * nn));
+    double* d_y = ctx->d_detrend.ptr;
+    double* d_flat = d_y + (size_t)slab * nn;
+    double* d_trend = out_trend ? d_flat + (size_t)slab * nn : nullptr;
+    TLS_HIP(ctx, hipMemcpyAsync(ctx->d_windows.ptr, lo.data(), nn * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(ctx->d_windows.ptr + nn, hi.data(), nn * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    int T = 0, P = 0, smax = 0;
+    biweight_plan(lo, hi, wmax, &T, &P, &smax);
+    const size_t lds = (size_t)P * (sizeof(unsigned long long) + sizeof(unsigned int)) + (size_t)smax * sizeof(double);
+    auto fn = tlsdev::tls_biweight_detrend;
+    TLS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    tlsdev::BiweightArgs a;
+    a.y = d_y; a.flat = d_flat; a.trend = d_trend; a.check = nullptr;
+    a.lo = ctx->d_windows.ptr; a.hi = ctx->d_windows.ptr + nn;
+    a.n = (long long)n; a.tile = T; a.span = P; a.smax = smax;
+#ifdef TLS_DEBUG_CHECKS
+    if (!ctx->d_check.ptr) {
+        TLS_HIP(ctx, ctx->d_check.reserve(tlsdev::kChecks));
+        TLS_HIP(ctx, hipMemsetAsync(ctx->d_check.ptr, 0, tlsdev::kChecks * sizeof(unsigned long long), ctx->stream));
+    }
+    a.check = ctx->d_check.ptr;
+#endif
+    const unsigned tiles = (unsigned)((n + T - 1) / T);
+    for (int64_t k0 = 0; k0 < n_rows; k0 += slab) {
+        const int64_t rows = std::min<int64_t>(slab, n_rows - k0);
+        const size_t bytes = (size_t)rows * nn * 8;
+        TLS_HIP(ctx, hipMemcpyAsync(d_y, y + (size_t)k0 * nn, bytes, hipMemcpyHostToDevice, ctx->stream));
+        hipLaunchKernelGGL(fn, dim3(tiles, (unsigned)rows), dim3(tlsdev::kDetrendThreads), lds, ctx->stream, a);
+        TLS_HIP(ctx, hipGetLastError());
+        ctx->last_kernel = "tls_biweight_detrend";
+        TLS_HIP(ctx, hipMemcpyAsync(out_flat + (size_t)k0 * nn, d_flat, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        if (out_trend)
+            TLS_HIP(ctx, hipMemcpyAsync(out_trend + (size_t)k0 * nn, d_trend, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        // (the next slab overwrites the device rows, and lo / hi live on this stack: the copies have to be done first)
         TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     return TLS_OK;

@@ -25,24 +25,22 @@ struct DetrendArgs {
     int tile;                     // T = P - (k - 1) outputs per workgroup
 };
 
-// LDS: keys [P] (uint64: the bit patterns) | slot numbers [P] (uint32), 12 P bytes.  Grid (ceil(n / T), rows).
-__global__ void __launch_bounds__(kDetrendThreads) tls_medfilt_detrend(const DetrendArgs a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned long long detrend_lds[];
-    const int P = a.span, T = a.tile, k = a.k, h = k >> 1;
-    const int S = T + k - 1;
-    unsigned long long* keys = detrend_lds;
-    unsigned int* slot = reinterpret_cast<unsigned int*>(keys + P);
-    const long long row = blockIdx.y;
-    const long long lo = (long long)blockIdx.x * T;
-    const double* y = a.y + row * a.n;
-
+// Stages the S values y[base + s], s < S (0.0 where base + s lies outside [0, n): the median filter's zero padding), as
+// (bit-pattern key, slot s) pairs into keys/slot [P], the slots S .. P - 1 with a key above every double and slot ~0u (in no
+// window), copies the values in index order into vals [S] unless vals is nullptr, and sorts the P pairs ascending by key
+// (bitonic, in LDS).  Every thread of the workgroup calls it; it ends with a barrier.  Shared by tls_medfilt_detrend and
+// tls_biweight_detrend (tls_biweight.hip.h); `chk` is the caller's check code.
+template <class A>
+__device__ __forceinline__ void detrend_stage_sort(const A& a, const double* y, long long base, long long n, int S, int P,
+                                                   unsigned long long* keys, unsigned int* slot, double* vals, int chk) {
     for (int s = threadIdx.x; s < P; s += kDetrendThreads) {
         unsigned long long key = ~0ull;   // (above every double: the padding slots sort last)
         unsigned int p = ~0u;             // (in no window)
         if (s < S) {
-            const long long g = lo - h + s;
-            key = (g >= 0 && g < a.n) ? (unsigned long long)__double_as_longlong(y[g]) : 0ull;   // (0ull: +0.0)
+            const long long g = base + s;
+            key = (g >= 0 && g < n) ? (unsigned long long)__double_as_longlong(y[g]) : 0ull;   // (0ull: +0.0)
             p = (unsigned int)s;
+            if (vals) vals[s] = __longlong_as_double((long long)key);
         }
         keys[s] = key;
         slot[s] = p;
@@ -55,7 +53,7 @@ __global__ void __launch_bounds__(kDetrendThreads) tls_medfilt_detrend(const Det
             for (int t = threadIdx.x; t < (P >> 1); t += kDetrendThreads) {
                 const int i = 2 * t - (t & (stride - 1));
                 const int j = i + stride;
-                TLS_CHECK(a, j < P, kChkDetrend);
+                TLS_CHECK(a, j < P, chk);
                 const unsigned long long ki = keys[i], kj = keys[j];
                 const bool up = (i & size) == 0;
                 if (up ? ki > kj : ki < kj) {
@@ -67,6 +65,20 @@ __global__ void __launch_bounds__(kDetrendThreads) tls_medfilt_detrend(const Det
             wg_sync();
         }
     }
+}
+
+// LDS: keys [P] (uint64: the bit patterns) | slot numbers [P] (uint32), 12 P bytes.  Grid (ceil(n / T), rows).
+__global__ void __launch_bounds__(kDetrendThreads) tls_medfilt_detrend(const DetrendArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long detrend_lds[];
+    const int P = a.span, T = a.tile, k = a.k, h = k >> 1;
+    const int S = T + k - 1;
+    unsigned long long* keys = detrend_lds;
+    unsigned int* slot = reinterpret_cast<unsigned int*>(keys + P);
+    const long long row = blockIdx.y;
+    const long long lo = (long long)blockIdx.x * T;
+    const double* y = a.y + row * a.n;
+
+    detrend_stage_sort(a, y, lo - h, a.n, S, P, keys, slot, nullptr, kChkDetrend);
 
     // selection: lane of output lo + i counts the sorted slots that fall into [i, i + k), four at a time, up to the (h+1)-th
     const uint4* slot4 = reinterpret_cast<const uint4*>(slot);

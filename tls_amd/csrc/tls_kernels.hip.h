@@ -87,6 +87,7 @@ enum CheckCode {
     kChkTileStage = 7,     // a tile was staged beyond the LDS buffer
     kChkSplit = 8,         // fp32 screen: a sample is not the exact sum of its two fp32 halves
     kChkDetrend = 9,       // tls_medfilt_detrend: an LDS index outside the staged slots, or a median outside the span
+    kChkBiweight = 10,     // tls_biweight_detrend: a span over its LDS, or an LDS index outside the staged slots
 };
 
 constexpr int kWave = 64;
@@ -4259,5 +4260,8 @@ __global__ void __launch_bounds__(512) tls_transit_models(const ModelsArgs a) {
 
 // survey-mode median-filter detrending (tls_medfilt_detrend)
 #include "tls_detrend.hip.h"
+
+// survey-mode biweight detrending (tls_biweight_detrend), on tls_detrend.hip.h's staging and sort
+#include "tls_biweight.hip.h"
 
 }  // namespace tlsdev

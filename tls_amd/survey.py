@@ -7,6 +7,7 @@ Across GPUs the light curves are simply dealt out: one process per GPU (bench.py
 (every visible GPU) on the calls below -- contiguous slices of the batch to the contexts of a `tls_amd.search.DeviceGroup`, one host thread each, no
 collective (every light curve's results come back over its own GPU's copy engine).
 """
+import collections
 import contextlib
 import operator
 
@@ -163,13 +164,71 @@ def detrend_batch(flux_batch, kernel_size=25, return_trend=False, context=None, 
     return (flat, trend) if return_trend else flat
 
 
+# ---- detrending: a time-windowed biweight on the device ------------------------------------------------------------------
+class Biweight(collections.namedtuple("Biweight", ("window_length", "break_tolerance"))):
+    """detrend=Biweight(window_length, break_tolerance=0.5) on the survey calls: Tukey's biweight over windows of
+    window_length days, split at gaps > break_tolerance days (biweight_batch).  An immutable value; its fields are checked
+    where it is used."""
+    __slots__ = ()
+
+    def __new__(cls, window_length, break_tolerance=0.5):
+        return super(Biweight, cls).__new__(cls, window_length, break_tolerance)
+
+
+def biweight_batch(t, flux_batch, window_length=0.5, break_tolerance=0.5, return_trend=False, context=None, device=None,
+                   devices=None):
+    """flat = flux / trend for every row of flux_batch ([n] or [n_curves, n], at the shared time stamps t), with trend Tukey's
+    biweight location over a window in TIME, on the device (tls_biweight_detrend): the robust filter the detrending comparison
+    of Hippke et al. 2019 (AJ 158, 143) recommends in front of a transit search, with window_length about three times the
+    longest transit duration searched for.
+
+    A new segment starts behind every gap t[j] - t[j-1] > break_tolerance (days; inf: never), and the window of point i is
+    every point of i's segment with |t[j] - t[i]| <= window_length / 2 (days), so no window reaches across a gap and the ends
+    of a row carry no padding.  Inside the window the location starts at the median and is reweighted up to
+    BIWEIGHT_MAX_ITER = 50 times with the biweight of tuning constant C = 5 around the MAD, until it moves by at most
+    FTOL = 1e-6 of itself (a relative tolerance: rows near 1e-300 and 1e300 behave like rows near 1) or the MAD is 0.  The
+    exact steps are in include/tls_amd.h; each is one IEEE double operation, so the result is bit-equal to a numpy
+    restatement of them.  t must be finite and non-decreasing, window_length finite and > 0, break_tolerance > 0, no window
+    may hold more than BIWEIGHT_MAX_WINDOW = 4095 points, and every flux value must be finite and > 0.  The arguments are
+    checked before any device work.
+
+    devices=[...] deals the rows out over several GPUs, as the other survey calls.  Returns flat, or (flat, trend), in the
+    shape of flux_batch."""
+    from ._lib import biweight_arguments
+    t, rows, wl, bt = biweight_arguments(t, flux_batch, window_length, break_tolerance)
+
+    def call(ctx, lo, hi):
+        out = ctx.biweight_detrend(t, rows[lo:hi], wl, bt, return_trend=return_trend)
+        return dict(flat=out[0], trend=out[1]) if return_trend else dict(flat=out, trend=None)
+
+    out = _run_batch(devices, device, context, len(rows), call)
+    flat, trend = out["flat"], out["trend"]
+    if numpy.ndim(flux_batch) == 1:
+        flat, trend = flat[0], None if trend is None else trend[0]
+    return (flat, trend) if return_trend else flat
+
+
 def _detrended(t, flux_batch, detrend, context, device, devices):
-    """flux_batch as it is (detrend None), or detrend_batch(flux_batch, detrend) on the call's devices for [n_curves, len(t)]."""
+    """flux_batch as it is (detrend None), biweight_batch (detrend a Biweight) or detrend_batch(flux_batch, detrend) on the
+    call's devices for [n_curves, len(t)]."""
     if detrend is None:
         return flux_batch
     if numpy.ndim(flux_batch) != 2 or numpy.shape(flux_batch)[1] != len(t):
         raise ValueError("flux_batch must have shape [n_curves, len(t)]")
+    if isinstance(detrend, Biweight):
+        return biweight_batch(t, flux_batch, detrend.window_length, detrend.break_tolerance, context=context, device=device,
+                              devices=devices)
     return detrend_batch(flux_batch, detrend, context=context, device=device, devices=devices)
+
+
+def _detrend_rows(ctx, t, rows, detrend):
+    """rows as they are (detrend None), or detrended on ctx: the biweight for a Biweight, the median filter of kernel size
+    detrend otherwise (the rows formed on the device by injection_recovery and null_sde, chunk by chunk)."""
+    if detrend is None:
+        return rows
+    if isinstance(detrend, Biweight):
+        return ctx.biweight_detrend(t, rows, detrend.window_length, detrend.break_tolerance)
+    return ctx.medfilt_detrend(rows, detrend)
 
 
 def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_arrays=False, devices=None, statistics=False,
@@ -197,7 +256,8 @@ def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_ar
 
     detrend=k (an odd kernel size) searches flux_batch / medfilt(flux_batch, k) instead (detrend_batch, on the device; the
     rows come back to the host and go through the search unchanged), so the result equals power_batch on the rows detrended
-    beforehand; dy_batch is passed through as it is.  detrend=None searches flux_batch as given.
+    beforehand; dy_batch is passed through as it is.  detrend=Biweight(window_length, break_tolerance) searches
+    biweight_batch(t, flux_batch, window_length, break_tolerance) the same way.  detrend=None searches flux_batch as given.
 
     Returns (summary, periods[, chi2, row, depth, power][, per_transit][, models]): summary is a numpy structured array with
     the fields of tls_power_summary plus "duration" (and the statistics on request)."""
@@ -297,7 +357,8 @@ def power_results(t, flux_batch, dy_batch=None, context=None, device=None, devic
     arrays, about 0.7 MB for the k2_90d configuration (90 days at 48 cadences a day), so 1024 curves take about 0.7 GB, and
     the call's own staging as much again while it runs.  Callers with large batches pass them in chunks.
     devices=[...] deals the batch out over several GPUs, as the other survey calls.  detrend=k searches
-    flux_batch / medfilt(flux_batch, k) (detrend_batch), as power_batch does; the objects then describe the detrended rows."""
+    flux_batch / medfilt(flux_batch, k) (detrend_batch), and detrend=Biweight(...) the rows biweight_batch forms, as
+    power_batch does; the objects then describe the detrended rows."""
     from .api import transitleastsquares
     from .results import transitleastsquaresresults
     if len(numpy.shape(flux_batch)) != 2 or numpy.shape(flux_batch)[1] != len(t):
@@ -342,7 +403,7 @@ def search_batch(t, flux_batch, dy_batch=None, context=None, device=None, device
     Returns (periods, chi2[n_curves, n_periods], row[...], depth[...]).  All light curves must
     share `t` and be free of invalid points (clean them first); a `dy_batch` must have the same
     weight structure for every curve (all uniform or all per-point).  detrend=k searches flux_batch / medfilt(flux_batch, k)
-    (detrend_batch), as power_batch does.
+    (detrend_batch), and detrend=Biweight(...) the rows biweight_batch forms, as power_batch does.
     """
     flux_batch = _detrended(t, flux_batch, detrend, context, device, devices)
     inp, y_rows, dy_rows = _batch_inputs(t, flux_batch, dy_batch, power_kwargs)
@@ -529,7 +590,8 @@ def injection_recovery(t, flux, injections, dy=None, inject_u=None, inject_limb_
     detrend=k (an odd kernel size): `flux` is the RAW light curve, and every injected row is detrended on the same device
     right after the injection (row / medfilt(row, k), tls_medfilt_detrend) before it is searched, so the transits pass through
     the filter the data pass through, and completeness counts what the filter absorbs.  rows are then the detrended rows;
-    n_in_transit and the classification are unchanged, and dy is passed through as it is.
+    n_in_transit and the classification are unchanged, and dy is passed through as it is.  detrend=Biweight(window_length,
+    break_tolerance) does the same with the time-windowed biweight (tls_biweight_detrend, biweight_batch).
 
     Returns (recovery, summary[, rows]): recovery a structured array -- the injected fields, T14, n_in_transit (points
     with z < 1 + rp_rs: 0 where every transit falls into a gap), period_match, epoch_offset, recovered -- and summary
@@ -554,14 +616,17 @@ def injection_recovery(t, flux, injections, dy=None, inject_u=None, inject_limb_
     # (checked before any device work)
     classify_recovery(table[:0], numpy.zeros(0, dtype=[("period", "f8"), ("T0", "f8"), ("SDE", "f8"), ("no_fit", "i8")]),
                       None, sde_threshold, period_tolerance, aliases, epoch_tolerance)
-    if detrend is not None:
+    if isinstance(detrend, Biweight):
+        from ._lib import biweight_arguments
+        biweight_arguments(t, flux, detrend.window_length, detrend.break_tolerance)
+    elif detrend is not None:
         from ._lib import medfilt_arguments
         medfilt_arguments(flux, detrend)
     consts = injection_constants(table)
 
     def form(ctx, lo, hi):
         rows, count = ctx.inject_transits(t, flux if flux.ndim == 1 else flux[lo:hi], consts[lo:hi], u1, u2)
-        return (rows if detrend is None else ctx.medfilt_detrend(rows, detrend)), count
+        return _detrend_rows(ctx, t, rows, detrend), count
 
     summaries, counts, all_rows = _search_chunks(t, n_inj, chunk, form, dy, return_rows, statistics, context, device, devices,
                                                  power_kwargs)
@@ -694,7 +759,8 @@ def null_sde(t, n_trials, sigma=None, source=None, block=None, seed=0, first_tri
     detrend=k (an odd kernel size) detrends every null row on the same device right after it is formed (row / medfilt(row, k),
     tls_medfilt_detrend) and searches the detrended rows: the null of a pipeline that detrends.  A bootstrap then takes RAW
     source rows, filtered after resampling as the data are.  A row still depends on (seed, R) alone; rows are then the
-    detrended rows, and dy is passed through as it is.
+    detrended rows, and dy is passed through as it is.  detrend=Biweight(window_length, break_tolerance) does the same with
+    the time-windowed biweight (tls_biweight_detrend, biweight_batch).
 
     Returns summary, or (summary, rows [n_trials, n]) with return_rows=True."""
     t, mode, sigma, source, block, seed, first_trial = _null_arguments(t, n_trials, sigma, source, block, seed, first_trial)
@@ -708,14 +774,17 @@ def null_sde(t, n_trials, sigma=None, source=None, block=None, seed=0, first_tri
     chunk = _default_chunk(n) if chunk is None else _integer("chunk", chunk, 1)
     if statistics and not numpy.all(t[1:] >= t[:-1]):
         raise ValueError("statistics=True needs ascending time stamps t")
-    if detrend is not None:
+    if isinstance(detrend, Biweight):
+        from ._lib import biweight_windows
+        biweight_windows(t, detrend.window_length, detrend.break_tolerance)
+    elif detrend is not None:
         from ._lib import medfilt_kernel
         medfilt_kernel(detrend, n)
 
     def form(ctx, lo, hi):
         sig = None if mode == 1 else sigma if len(sigma) == 1 else sigma[lo:hi]
         rows = ctx.null_rows(n, hi - lo, seed, first_trial + lo, sigma=sig, source=source, block=block)
-        return (rows if detrend is None else ctx.medfilt_detrend(rows, detrend)), None
+        return _detrend_rows(ctx, t, rows, detrend), None
 
     summaries, _, all_rows = _search_chunks(t, n_trials, chunk, form, dy, return_rows, statistics, context, device, devices,
                                             power_kwargs)
