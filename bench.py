@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the TLS grid-search hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config k2_90d] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config k2_90d] [--dump-outputs DIR] [--full]
 
 N > 1 runs one process per GPU: either under `python -m torch.distributed.run --nproc-per-node N
 ... bench.py --gpus N` (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment) or started
@@ -16,15 +16,21 @@ resident in HBM: the full period x duration x T0 grid search of BASELINE.json's 
     own seed); the per-period (chi2, row, depth) triples of all K steps are exchanged with ONE
     RCCL all-gather at the end of the timed region, so that every rank holds the whole batch ->
     per-GPU work is fixed, "scaling": "weak".
-  * N > 1 additionally times the PERIOD-SHARD layout north_star describes (BASELINE config 4): ONE
-    light curve per step, its period grid dealt out over the GPUs (cyclic shares: rank r searches
-    periods[r::N], tls_amd/shard.py), one RCCL all-gather per light curve -> strong scaling; reported
-    under "shard" for config 2 and for the TESS 2-min configuration, with every rank's kernel time.
+  * With --full, N > 1 additionally times the PERIOD-SHARD layout north_star describes (BASELINE
+    config 4): ONE light curve per step, its period grid dealt out over the GPUs (cyclic shares: rank r
+    searches periods[r::N], tls_amd/shard.py), one RCCL all-gather per light curve -> strong scaling;
+    reported under "shard" for config 2 and for the TESS 2-min configuration, with every rank's kernel
+    time.  --mode shard times that layout alone, as the headline (the other configurations with --full).
 value = trial cells of the whole job / wall time of the K timed steps (barrier + device sync on
 both sides, max over ranks), inputs resident in HBM when the timed region starts -- the bench contract
 of this build ("if the boundary hands over host buffers, note the PCIe-inclusive rate ... it is never
-`value`").  The search call FROM HOST BUFFERS (H2D + kernel + D2H through tls_search,
-plan reused / planned from scratch) is printed beside it as `value_one_shot` / `value_one_shot_cold`.
+`value`").
+
+A plain run does only what `value` needs: it sets up, warms up, times the K steps, writes --dump-outputs
+and prints the line (the headline and the configuration of the timed workload).  Everything below is
+measured after the timed steps, and only with --full.  The search call FROM HOST BUFFERS (SURVEY
+8(d)(i): H2D + kernel + D2H through tls_search, plan reused / planned from scratch) is printed beside
+`value` as `value_one_shot` / `value_one_shot_cold`.
 `roofline` prices the dominant kernel of the headline configuration against the ceiling that binds it:
 the LDS-resident kernel against the fp64 VECTOR rate (`bound: "fp64"`: one FMA per template tap of an
 evaluated cell over its HIP-event duration; 78.6 TF peak) -- its light curve is L2-resident and the
@@ -590,6 +596,165 @@ def survey_1024(ctx, n_curves):
             "recovered_10_123d": int(numpy.sum(numpy.abs(summary["period"] - 10.123) < 0.05))}
 
 
+def full_measurements(h, args, t, flux, kw, inp, info, kernel_ms, out):
+    """--full, rank 0, after the timed steps: everything the line carries beside the headline, added to `out` -- one counted
+    pass for the work statistics and the roofline of the timed kernel, the CPU baseline and, at N = 1, the untimed extras
+    (the search call from host buffers, the noisier variants, the power() wall clock, the other configurations, the survey
+    throughput, the one-GPU projection of the shard layout)."""
+    ctx, world = h.ctx, h.world
+    periods = inp["periods"]
+    extras = world == 1 and not args.no_extras
+    # one counted pass (outside the timed region) for the work statistics
+    ctx.prepare(inp["t"], inp["y"], inp["dy"], periods, inp["table"], inp["params"])
+    ctx.execute(count_work=True)
+    chi2, row, depth, counters = ctx.fetch(with_counters=True)
+
+    # SURVEY.md 8(d)(i): the one-shot call a user of the C ABI sees -- host buffers in, host
+    # buffers out: planning + H2D + kernel + D2H (tls_search), best of 5
+    one_shot = None
+    if extras:
+        # cold: the context holds the plan of ANOTHER period grid, so tls_prepare plans from scratch (duration
+        # windows, work order, template rows, one pinned upload).  warm: the same time stamps / grid / template
+        # as the call before (a survey, repeated power() calls): the library recognises the plan and only the
+        # flux travels.  Both: host buffers in, host buffers out.
+        def one_call(per):
+            t1 = time.perf_counter()
+            ctx.prepare(inp["t"], inp["y"], inp["dy"], per, inp["table"], inp["params"])
+            ctx.execute()
+            ctx.fetch()
+            return time.perf_counter() - t1
+        cold = warm = float("inf")
+        for _ in range(5):
+            one_call(periods[:-1])          # evicts the plan
+            cold = min(cold, one_call(periods))
+            warm = min(warm, one_call(periods))
+        one_shot = {"ms": 1e3 * warm, "trial_cells_per_s": info["grid_cells"] / warm,
+                    "cold_ms": 1e3 * cold, "cold_trial_cells_per_s": info["grid_cells"] / cold,
+                    "what": "tls_prepare + tls_execute + tls_fetch from host buffers (= tls_search): H2D, kernel, "
+                            "D2H; `ms` with the plan of the previous call reused inside the library (same t, "
+                            "periods, template: a survey), `cold_ms` with host planning from scratch"}
+
+    # the same grid at 500 ppm noise, where 55 % of the cells pass the depth predicate instead of 11 %
+    noisy = None
+    if extras and args.sigma is None and args.config == "k2_90d":
+        t5, f5, kw5 = synthetic.config(args.config, seed=0, sigma=500e-6)
+        i5 = synthetic.search_inputs(t5, f5, **kw5)
+        ctx.prepare(i5["t"], i5["y"], i5["dy"], i5["periods"], i5["table"], i5["params"])
+        ctx.execute(count_work=True)
+        c5 = ctx.fetch(with_counters=True)[3]
+        ms5 = ctx.execute_timed(5)
+        noisy = {"sigma_ppm": 500.0, "kernel_ms": ms5, "trial_cells_per_s": c5["grid_cells"] / (ms5 * 1e-3),
+                 "evaluated_fraction": c5["evaluated_cells"] / c5["grid_cells"],
+                 "inner_steps": c5["inner_steps"]}
+        # ... and at 100 ppm, where the host takes the fp32-screen variant of the kernel (tls_amd.hip, screen_pays):
+        # the three variants side by side (the context's switches, tls_options: prune / screen32)
+        t1_, f1_, kw1_ = synthetic.config(args.config, seed=0, sigma=100e-6)
+        i1_ = synthetic.search_inputs(t1_, f1_, **kw1_)
+        variants = {}
+        for label, sw in (("chosen_by_host", {"prune": None, "screen32": None}), ("plain", {"prune": 0, "screen32": 0}),
+                          ("fp32_screen", {"prune": 0, "screen32": 1}), ("pruning", {"prune": 1, "screen32": 0})):
+            ctx.set_options(**sw)
+            ctx.prepare(i1_["t"], i1_["y"], i1_["dy"], i1_["periods"], i1_["table"], i1_["params"])
+            ctx.execute(); ctx.synchronize()
+            variants[label] = ctx.execute_timed(10)
+        ctx.set_options(prune=None, screen32=None)
+        noisy["at_100_ppm_kernel_ms"] = variants
+
+    # wall clock of the whole drop-in call for one light curve (host buffers in, results object
+    # out: grids, template table, H2D, search, D2H, SDE spectra, device T0 fit, statistics)
+    power_wall_ms = None
+    if extras:
+        import tls_amd
+        model = tls_amd.transitleastsquares(t, flux, verbose=False)
+        best = float("inf")
+        for _ in range(4):
+            t1 = time.perf_counter()
+            model.power(verbose=False, show_progress_bar=False, context=ctx, **kw)
+            best = min(best, time.perf_counter() - t1)
+        power_wall_ms = 1e3 * best
+
+    # roofline.traffic measured in THIS run (N = 1): two rocprofv3 --pmc passes per configuration in a child process, while
+    # this process idles (its context stays alive: the counters are per process)
+    if extras and not args.no_live_traffic and args.sigma is None:
+        for name, stride in ((args.config, 1),) + ((("tess_27d", 1), ("kepler_4yr", 64)) if args.config == "k2_90d" else ()):
+            try:
+                live = measure_traffic_live(name, stride)
+                if live is not None:
+                    t_l, f_l, kw_l = synthetic.config(name, seed=0)
+                    n_per_l = len(inp["periods"]) if name == args.config else len(synthetic.search_inputs(t_l, f_l, **kw_l)["periods"])
+                    _LIVE_TRAFFIC[name] = (live[0], live[1], len(range(0, n_per_l, stride)))
+            except Exception:
+                pass
+
+    other = {}
+    if extras and args.config == "k2_90d":
+        for name, reps, noisy_sigma in (("tess_27d", 30, 1000e-6), ("kepler_4yr", 2, 500e-6)):
+            try:
+                other[name] = large_config(ctx, name, reps, warm=10 if name == "tess_27d" else 0)
+                other[name]["noisy_variant"] = noisy_variant(ctx, name, noisy_sigma, 1 if name == "kepler_4yr" else 3)
+            except Exception as exc:
+                other.setdefault(name, {})["error"] = str(exc)[:300]
+        try:
+            other["survey_1024"] = survey_1024(ctx, args.survey_curves)
+        except Exception as exc:
+            other["survey_1024"] = {"error": str(exc)[:300]}
+        other["shard_balance"] = []
+        for name in ("k2_90d", "tess_27d", "kepler_4yr"):
+            try:
+                other["shard_balance"].append(shard_balance(ctx, name, 8, 2 if name == "kepler_4yr" else 5))
+            except Exception as exc:
+                other["shard_balance"].append({"config": name, "error": str(exc)[:300]})
+
+    n = len(inp["t"])
+    kernel_s = 1e-3 * kernel_ms
+    algo_bytes = len(periods) * (24 * n + 24)          # SURVEY.md 8(d): B_period per period
+    achieved = algo_bytes / kernel_s / 1e9
+    ref_flops = 6.0 * counters["inner_steps"]           # reference flop count, core.py:68-69
+    useful_flops = 2.0 * counters["inner_steps"]        # what the reformulated kernel needs: one FMA per tap
+    issued_flops = 2.0 * counters["issued_fma"]         # what it issues (chunk padding, idle lanes, unroll slack)
+    traffic, traffic_source = recorded_traffic(args.config, len(periods))
+    # SURVEY 8(d)(i): the search call from host buffers (H2D + kernel + D2H); `_cold` with the host planning of a
+    # first call, the other with the plan of the previous call reused inside the library (a survey)
+    out["value_one_shot"] = (one_shot or {}).get("trial_cells_per_s")
+    out["value_one_shot_cold"] = (one_shot or {}).get("cold_trial_cells_per_s")
+    out["config"].update({"one_shot": one_shot, "power_call_wall_ms_per_light_curve": power_wall_ms,
+                          "evaluated_cells": counters["evaluated_cells"],
+                          "inner_steps": counters["inner_steps"], "issued_fma": counters["issued_fma"],
+                          "noisy_variant": noisy})
+    # What binds: the LDS-resident kernel (the light curve is 100 KB and L2-resident: measured HBM traffic is a
+    # fraction of the algorithmic bytes) is priced against the fp64 VECTOR rate -- frac = useful FMAs (one per
+    # template tap of an evaluated cell) over 78.6 TFLOP/s, half the guide's 157.3 TFLOP/s fp32 vector peak (fp64
+    # issues at half rate: 4 cycles per wave64 instruction; no fp64 MFMA advantage on gfx950 and no GEMM here) --
+    # with the HBM figure the contract asks for beside it.  The HBM-slab configurations are priced against HBM.
+    out["roofline"] = ({"bound": "fp64", "achieved": useful_flops / kernel_s / 1e12, "peak": FP64_VECTOR_PEAK_TF, "unit": "TFLOP/s",
+                       "frac": useful_flops / kernel_s / 1e12 / FP64_VECTOR_PEAK_TF} if info["resident"] else
+                      {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS})
+    out["roofline"].update({
+        "traffic": traffic, "traffic_source": traffic_source,
+        "kernel": "tls_slim_kernel" if getattr(h, "timed_kernel", "") == "slim" else "tls_search_kernel", "kernel_variant": getattr(h, "timed_kernel", ""),
+        "kernel_ms": 1e3 * kernel_s,
+        "algorithmic_bytes_per_launch": algo_bytes,
+        "hbm": {"achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                "note": "algorithmic bytes (24*N+24 B per period, SURVEY 8d) over the kernel time; nominal for the "
+                        "LDS-resident kernel, whose measured HBM traffic (`traffic`) is a fraction of them"},
+        "fp64": {"peak": FP64_VECTOR_PEAK_TF, "unit": "TFLOP/s",
+                 "peak_source": "half of MI355X_MICROARCH.md's 157.3 TFLOP/s fp32 vector peak (256 CUs x 4 SIMD-32 x 2.4 GHz)",
+                 "useful": useful_flops / kernel_s / 1e12,
+                 "useful_frac": useful_flops / kernel_s / 1e12 / FP64_VECTOR_PEAK_TF,
+                 "issued": issued_flops / kernel_s / 1e12,
+                 "issued_frac": issued_flops / kernel_s / 1e12 / FP64_VECTOR_PEAK_TF,
+                 "reference": ref_flops / kernel_s / 1e12,
+                 "reference_frac": ref_flops / kernel_s / 1e12 / FP64_VECTOR_PEAK_TF,
+                 "lane_efficiency": counters["inner_steps"] / max(counters["issued_fma"], 1),
+                 "note": "useful: one FMA per template tap; issued: FMAs actually issued (chunk padding, idle lanes, "
+                         "unroll slack); reference: the 6 flops per tap core.py:68-69 spends"}})
+    out["argmin_period_index"] = int(numpy.argmin(chi2))
+    out["chi2_min"] = float(numpy.min(chi2))
+    out.update(other)
+    if not args.no_cpu_baseline and world == 1:
+        out["cpu_baseline"] = cpu_baseline(inp, info["grid_cells"])
+
+
 def git_head():
     try:
         return subprocess.check_output(["git", "-C", ROOT, "rev-parse", "--short=12", "HEAD"],
@@ -608,15 +773,20 @@ def main():
     ap.add_argument("--config", default="k2_90d", choices=sorted(synthetic.CONFIGS))
     ap.add_argument("--sigma", type=float, default=None, help="noise override (e.g. 500e-6)")
     ap.add_argument("--mode", default="both", choices=["both", "survey", "shard"],
-                    help="N > 1: which layouts to time (value is always the survey layout when it runs)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="N > 1: which layouts to time (value is always the survey layout when it runs; "
+                         "`both` adds the shard layout only with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything beside the headline: counted pass and roofline, "
+                         "CPU baseline, other configurations and variants, power() wall clock, survey throughput, shard "
+                         "layout (N > 1) and its one-GPU projection (N = 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the untimed extras (other configurations, 500 ppm variant, power() wall clock, "
-                         "counted pass) so that a profiler sees only the timed workload's launches")
-    ap.add_argument("--survey-curves", type=int, default=1024)
+                    help="with --full: skip the untimed extras (other configurations, 500 ppm variant, power() wall clock); "
+                         "the counted pass, the roofline and the CPU baseline stay")
+    ap.add_argument("--survey-curves", type=int, default=1024, help="with --full: light curves of the survey throughput")
     ap.add_argument("--no-live-traffic", action="store_true",
-                    help="do not run the rocprofv3 --pmc passes that measure roofline.traffic in this run (~10 s per configuration); "
-                         "the committed record of profiles/hbm_traffic.json is reported instead")
+                    help="with --full: do not run the rocprofv3 --pmc passes that measure roofline.traffic in this run (~10 s "
+                         "per configuration); the committed record of profiles/hbm_traffic.json is reported instead")
     ap.add_argument("--allow-host-fallback", action="store_true",
                     help="N > 1 with one device per rank: time over the host channel when RCCL does not come up "
                          "(default: fail with a non-zero status)")
@@ -649,10 +819,10 @@ def main():
         elapsed, kernel_ms = run_survey(h, args, inp)
     info = ctx.plan_info()
     shard_out = None
-    if world > 1 and args.mode in ("both", "shard"):
+    if world > 1 and (args.mode == "shard" or args.mode == "both" and args.full):
         shard_out = [run_shard(h, args, args.config)]
         for other_cfg in ("tess_27d", "kepler_4yr"):   # BASELINE config 4, and config 3: the one grid with room to scale
-            if args.config != other_cfg:
+            if args.full and args.config != other_cfg:
                 shard_out.append(run_shard(h, args, other_cfg, steps=max(1, min(args.steps, 3)) if other_cfg == "kepler_4yr" else None))
         if elapsed is None:   # --mode shard: the first shard run is the headline
             elapsed = shard_out[0]["ms_per_step"] * 1e-3 * args.steps
@@ -663,130 +833,17 @@ def main():
         dumped = dump_outputs(args.dump_outputs, h.outputs)
         sys.stderr.write("bench: wrote %s to %s\n" % (", ".join(k + ".npy" for k in dumped), args.dump_outputs))
     if rank == 0:
-        extras = world == 1 and not args.no_extras
-        # one counted pass (outside the timed region) for the work statistics
-        ctx.prepare(inp["t"], inp["y"], inp["dy"], periods, inp["table"], inp["params"])
-        ctx.execute(count_work=True)
-        chi2, row, depth, counters = ctx.fetch(with_counters=True)
-
-        # the one-shot call a user of the C ABI sees -- host buffers in, host
-        # buffers out: planning + H2D + kernel + D2H (tls_search), best of 5
-        one_shot = None
-        if extras:
-            # cold: the context holds the plan of ANOTHER period grid, so tls_prepare plans from scratch (duration
-            # windows, work order, template rows, one pinned upload).  warm: the same time stamps / grid / template
-            # as the call before (a survey, repeated power() calls): the library recognises the plan and only the
-            # flux travels.  Both: host buffers in, host buffers out.
-            def one_call(per):
-                t1 = time.perf_counter()
-                ctx.prepare(inp["t"], inp["y"], inp["dy"], per, inp["table"], inp["params"])
-                ctx.execute()
-                ctx.fetch()
-                return time.perf_counter() - t1
-            cold = warm = float("inf")
-            for _ in range(5):
-                one_call(periods[:-1])          # evicts the plan
-                cold = min(cold, one_call(periods))
-                warm = min(warm, one_call(periods))
-            one_shot = {"ms": 1e3 * warm, "trial_cells_per_s": info["grid_cells"] / warm,
-                        "cold_ms": 1e3 * cold, "cold_trial_cells_per_s": info["grid_cells"] / cold,
-                        "what": "tls_prepare + tls_execute + tls_fetch from host buffers (= tls_search): H2D, kernel, "
-                                "D2H; `ms` with the plan of the previous call reused inside the library (same t, "
-                                "periods, template: a survey), `cold_ms` with host planning from scratch"}
-
-        # the same grid at 500 ppm noise, where 55 % of the cells pass the depth predicate instead of 11 %
-        noisy = None
-        if extras and args.sigma is None and args.config == "k2_90d":
-            t5, f5, kw5 = synthetic.config(args.config, seed=0, sigma=500e-6)
-            i5 = synthetic.search_inputs(t5, f5, **kw5)
-            ctx.prepare(i5["t"], i5["y"], i5["dy"], i5["periods"], i5["table"], i5["params"])
-            ctx.execute(count_work=True)
-            c5 = ctx.fetch(with_counters=True)[3]
-            ms5 = ctx.execute_timed(5)
-            noisy = {"sigma_ppm": 500.0, "kernel_ms": ms5, "trial_cells_per_s": c5["grid_cells"] / (ms5 * 1e-3),
-                     "evaluated_fraction": c5["evaluated_cells"] / c5["grid_cells"],
-                     "inner_steps": c5["inner_steps"]}
-            # ... and at 100 ppm, where the host takes the fp32-screen variant of the kernel (tls_amd.hip, screen_pays):
-            # the three variants side by side (the context's switches, tls_options: prune / screen32)
-            t1_, f1_, kw1_ = synthetic.config(args.config, seed=0, sigma=100e-6)
-            i1_ = synthetic.search_inputs(t1_, f1_, **kw1_)
-            variants = {}
-            for label, sw in (("chosen_by_host", {"prune": None, "screen32": None}), ("plain", {"prune": 0, "screen32": 0}),
-                              ("fp32_screen", {"prune": 0, "screen32": 1}), ("pruning", {"prune": 1, "screen32": 0})):
-                ctx.set_options(**sw)
-                ctx.prepare(i1_["t"], i1_["y"], i1_["dy"], i1_["periods"], i1_["table"], i1_["params"])
-                ctx.execute(); ctx.synchronize()
-                variants[label] = ctx.execute_timed(10)
-            ctx.set_options(prune=None, screen32=None)
-            noisy["at_100_ppm_kernel_ms"] = variants
-
-        # wall clock of the whole drop-in call for one light curve (host buffers in, results object
-        # out: grids, template table, H2D, search, D2H, SDE spectra, device T0 fit, statistics)
-        power_wall_ms = None
-        if extras:
-            import tls_amd
-            model = tls_amd.transitleastsquares(t, flux, verbose=False)
-            best = float("inf")
-            for _ in range(4):
-                t1 = time.perf_counter()
-                model.power(verbose=False, show_progress_bar=False, context=ctx, **kw)
-                best = min(best, time.perf_counter() - t1)
-            power_wall_ms = 1e3 * best
-
-        # roofline.traffic measured in THIS run (N = 1): two rocprofv3 --pmc passes per configuration in a child process, while
-        # this process idles (its context stays alive: the counters are per process)
-        if extras and not args.no_live_traffic and args.sigma is None:
-            for name, stride in ((args.config, 1),) + ((("tess_27d", 1), ("kepler_4yr", 64)) if args.config == "k2_90d" else ()):
-                try:
-                    live = measure_traffic_live(name, stride)
-                    if live is not None:
-                        t_l, f_l, kw_l = synthetic.config(name, seed=0)
-                        n_per_l = len(inp["periods"]) if name == args.config else len(synthetic.search_inputs(t_l, f_l, **kw_l)["periods"])
-                        _LIVE_TRAFFIC[name] = (live[0], live[1], len(range(0, n_per_l, stride)))
-                except Exception:
-                    pass
-
-        other = {}
-        if extras and args.config == "k2_90d":
-            for name, reps, noisy_sigma in (("tess_27d", 30, 1000e-6), ("kepler_4yr", 2, 500e-6)):
-                try:
-                    other[name] = large_config(ctx, name, reps, warm=10 if name == "tess_27d" else 0)
-                    other[name]["noisy_variant"] = noisy_variant(ctx, name, noisy_sigma, 1 if name == "kepler_4yr" else 3)
-                except Exception as exc:
-                    other.setdefault(name, {})["error"] = str(exc)[:300]
-            try:
-                other["survey_1024"] = survey_1024(ctx, args.survey_curves)
-            except Exception as exc:
-                other["survey_1024"] = {"error": str(exc)[:300]}
-            other["shard_balance"] = []
-            for name in ("k2_90d", "tess_27d", "kepler_4yr"):
-                try:
-                    other["shard_balance"].append(shard_balance(ctx, name, 8, 2 if name == "kepler_4yr" else 5))
-                except Exception as exc:
-                    other["shard_balance"].append({"config": name, "error": str(exc)[:300]})
-
         n = len(inp["t"])
         ms_per_step = 1e3 * elapsed / args.steps
         survey_ran = args.mode in ("both", "survey") or world == 1
         job_cells = info["grid_cells"] * world if survey_ran else shard_out[0]["trial_cells"]
         value = job_cells * args.steps / elapsed
-        kernel_s = 1e-3 * kernel_ms
-        algo_bytes = len(periods) * (24 * n + 24)          # B_period per period
-        achieved = algo_bytes / kernel_s / 1e9
-        ref_flops = 6.0 * counters["inner_steps"]           # reference flop count, core.py:68-69
-        useful_flops = 2.0 * counters["inner_steps"]        # what the reformulated kernel needs: one FMA per tap
-        issued_flops = 2.0 * counters["issued_fma"]         # what it issues (chunk padding, idle lanes, unroll slack)
-        traffic, traffic_source = recorded_traffic(args.config, len(periods))
         out = {
             "metric": "trial cells/sec (period x duration x T0)",
             "value": value, "unit": "trial cells/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
             "scaling": "weak" if survey_ran else "strong",
             "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            # the search call from host buffers (H2D + kernel + D2H); `_cold` with the host planning of a
-            # first call, the other with the plan of the previous call reused inside the library (a survey)
-            "value_one_shot": (one_shot or {}).get("trial_cells_per_s"),
-            "value_one_shot_cold": (one_shot or {}).get("cold_trial_cells_per_s"),
             "config": {"workload": "%s: %d points, %d periods x %d durations, %.3e trial cells per "
                                    "light curve; %s" % (
                                        args.config, n, len(periods), inp["table"].n_rows, info["grid_cells"],
@@ -803,47 +860,14 @@ def main():
                        "sigma_ppm": 1e6 * (args.sigma or synthetic.CONFIGS[args.config][2]),
                        "light_curves_per_step": world if survey_ran else 1,
                        "search_ms_per_light_curve": ms_per_step / (world if survey_ran else 1),
-                       "one_shot": one_shot,
-                       "power_call_wall_ms_per_light_curve": power_wall_ms,
-                       "evaluated_cells": counters["evaluated_cells"],
-                       "inner_steps": counters["inner_steps"], "issued_fma": counters["issued_fma"],
                        "device": ctx.name, "commit": git_head(),
                        "lds_bytes_per_workgroup": info["lds_bytes"], "workgroups": info["n_blocks"],
-                       "lds_resident": info["resident"], "noisy_variant": noisy},
-            # What binds: the LDS-resident kernel (the light curve is 100 KB and L2-resident: measured HBM traffic is a
-            # fraction of the algorithmic bytes) is priced against the fp64 VECTOR rate -- frac = useful FMAs (one per
-            # template tap of an evaluated cell) over 78.6 TFLOP/s, half the guide's 157.3 TFLOP/s fp32 vector peak (fp64
-            # issues at half rate: 4 cycles per wave64 instruction; no fp64 MFMA advantage on gfx950 and no GEMM here) --
-            # with the HBM figure the contract asks for beside it.  The HBM-slab configurations below are priced against HBM.
-            "roofline": ({"bound": "fp64", "achieved": useful_flops / kernel_s / 1e12, "peak": FP64_VECTOR_PEAK_TF, "unit": "TFLOP/s",
-                          "frac": useful_flops / kernel_s / 1e12 / FP64_VECTOR_PEAK_TF} if info["resident"] else
-                         {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS}),
-            "argmin_period_index": int(numpy.argmin(chi2)), "chi2_min": float(numpy.min(chi2)),
+                       "lds_resident": info["resident"]},
         }
-        out["roofline"].update({
-            "traffic": traffic, "traffic_source": traffic_source,
-            "kernel": "tls_slim_kernel" if getattr(h, "timed_kernel", "") == "slim" else "tls_search_kernel", "kernel_variant": getattr(h, "timed_kernel", ""),
-            "kernel_ms": 1e3 * kernel_s,
-            "algorithmic_bytes_per_launch": algo_bytes,
-            "hbm": {"achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                    "note": "algorithmic bytes (24*N+24 B per period, SURVEY 8d) over the kernel time; nominal for the "
-                            "LDS-resident kernel, whose measured HBM traffic (`traffic`) is a fraction of them"},
-            "fp64": {"peak": FP64_VECTOR_PEAK_TF, "unit": "TFLOP/s",
-                     "peak_source": "half of MI355X_MICROARCH.md's 157.3 TFLOP/s fp32 vector peak (256 CUs x 4 SIMD-32 x 2.4 GHz)",
-                     "useful": useful_flops / kernel_s / 1e12,
-                     "useful_frac": useful_flops / kernel_s / 1e12 / FP64_VECTOR_PEAK_TF,
-                     "issued": issued_flops / kernel_s / 1e12,
-                     "issued_frac": issued_flops / kernel_s / 1e12 / FP64_VECTOR_PEAK_TF,
-                     "reference": ref_flops / kernel_s / 1e12,
-                     "reference_frac": ref_flops / kernel_s / 1e12 / FP64_VECTOR_PEAK_TF,
-                     "lane_efficiency": counters["inner_steps"] / max(counters["issued_fma"], 1),
-                     "note": "useful: one FMA per template tap; issued: FMAs actually issued (chunk padding, idle lanes, "
-                             "unroll slack); reference: the 6 flops per tap core.py:68-69 spends"}})
-        out.update(other)
+        if args.full:
+            full_measurements(h, args, t, flux, kw, inp, info, kernel_ms, out)
         if shard_out is not None:
             out["shard"] = shard_out
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = cpu_baseline(inp, info["grid_cells"])
     h.barrier()
     if h.collective == "rccl":
         ctx.comm_destroy()
