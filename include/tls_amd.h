@@ -207,8 +207,9 @@ int tls_plan_info(const tls_ctx *ctx, tls_counters *counters, int64_t *lds_bytes
                   int64_t *n_blocks, int64_t *resident /* 1: folded series kept in LDS */);
 /* Which search kernel the context's last tls_execute launched: "resident" (LDS-resident series, two or one workgroups
  * per CU), "resident+prune", "resident+screen32", "slim" (LDS-resident, four 256-thread workgroups per CU), "slim512"
- * (the same kernel as two 512-thread workgroups per CU: series of 5280-8640 points), "slab", "slab+split"; "" before the
- * first launch.  The string is static. */
+ * (the same kernel as two 512-thread workgroups per CU: series of 5121-8889 points with the default duration grid at
+ * 30-minute cadence -- beyond the 5120 points of the 256-thread shape, while one region fits half the LDS; the edges move with
+ * the duration grid), "slab", "slab+split"; "" before the first launch.  The string is static. */
 const char *tls_last_kernel(const tls_ctx *ctx);
 
 /* ---- final T0 fit: the batched counterpart of stats.py:135-204 ------------------------ */
@@ -422,7 +423,9 @@ int tls_grid_cells(const double *t, int64_t n, const double *periods, int64_t n_
  * cells the sliding chi^2 of core.py:59-74 is evaluated for (sigma <= 0: all of them) -- and (time_per_period, may be
  * NULL) the modelled search time of the period in shader cycles of the kernel variant tls_prepare would choose:
  * a fixed part per period (fold, sort, prefix sum: O(n) whatever the duration window) + a part per trial cell
- * (depth predicate) + a part per expected tap, coefficients measured on an MI355X. */
+ * (depth predicate) + a part per expected tap, coefficients measured on an MI355X.
+ * The call has no dy: it plans for UNIFORM weights.  A search with per-point weights runs the classic kernel with three
+ * regions (never the four-slot kernel) and leaves the LDS earlier than the kernel priced here (PERF_LOG.md, open items). */
 int tls_period_costs(const double *t, int64_t n, const double *periods, int64_t n_periods,
                      const tls_template *tmpl, const tls_params *params, double sigma,
                      int64_t *cells_per_period, double *taps_per_period, double *time_per_period,

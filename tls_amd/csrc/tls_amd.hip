@@ -3237,7 +3237,8 @@ int tls_period_costs(const double* t, int64_t n, const double* periods, int64_t 
     for (int64_t p = 0; p < n_periods; ++p)
         taps_per_period[p] = prefix[(size_t)prow[(size_t)p].k_hi] - prefix[(size_t)prow[(size_t)p].k_lo];
     if (time_per_period) {
-        // Which kernel variant a search of this light curve runs (as tls_prepare decides it, uniform weights assumed),
+        // Which kernel variant a search of this light curve runs (as tls_prepare decides it, UNIFORM weights assumed: the call
+        // has no dy, and between the uniform and the per-point edges of the plan it prices a kernel a weighted search does not run),
         // and that variant's measured cost per period in shader cycles: a0 + aN * n + b * cells + c * taps, fitted to
         // tls_debug_period_cycles on an MI355X (tools/gpu_cost_model.py, profiles/r03_cost_model_fit.json).  Only the
         // ratios matter to the callers (tls_amd/shard.py places block boundaries by the cumulative sum).
