@@ -102,7 +102,8 @@ int tls_set_options(tls_ctx *ctx, const tls_options *opt);
 /* Developer / test switches, by name (not part of the stable ABI; negative value = the library decides): exact_prefix, slim
  * (the two of tls_options), prune, screen32, no_screen (kernel variant of an LDS-resident series), fast_slab, x_staged,
  * sort2, split, split_batch (series in the HBM slab: prefix-sum mode, sort, two-role kernel), threads, blocks, plan_threads
- * (launch shape, host planning), t0_rot (0: the final T0 fit checks every pair of every epoch), prune_min_live, band_max.  A context starts with the values
+ * (launch shape, host planning), t0_rot (0: the final T0 fit checks every pair of every epoch), prune_min_live, band_max,
+ * perm_table (the four-slot kernel's per-plan table of folded orders: 0 none, k > 0 at most k MiB).  A context starts with the values
  * of the TLS_<NAME> environment variables, read once per process; no call reads the environment after that.
  * tls_debug_get_switches writes all of them as "name=value,name=value" (ctx NULL: the process's) -- the text
  * tls_period_costs takes, so that the planning call prices the kernel the searching context will run. */
@@ -184,6 +185,10 @@ int tls_debug_poison_lds(tls_ctx *ctx, uint32_t word);
 int tls_debug_batch_group_ms(const tls_ctx *ctx, double *out, int64_t capacity);
 /* developer instrumentation: bytes of device memory the context holds, in all and in the final T0 fit's HBM scratch */
 int tls_debug_device_bytes(const tls_ctx *ctx, int64_t *total, int64_t *t0_fit_scratch);
+/* developer instrumentation: the table of folded orders of the held plan (four-slot kernel; switch perm_table) -- its size
+ * in bytes as the held plan uses it (0: the plan has none; the buffer behind it only grows and is counted by tls_debug_device_bytes) and whether a launch has filled it (1) or the next four-slot launch will (0); plan_reuses
+ * (may be NULL): the tls_prepare calls the context has answered from a held plan, which keep the table */
+int tls_debug_perm_table(const tls_ctx *ctx, int64_t *bytes, int64_t *filled, int64_t *plan_reuses);
 /* Test entry: the raw Philox words tls_null_rows draws for trials first_trial .. first_trial + n_rows - 1 with the same
  * (n, seed, mode, block): out [n_rows][W], W = the mode's words per trial rounded up to a multiple of 4 (the last W - words
  * of a row are drawn but not used).  The arguments are checked as tls_null_rows checks them. */

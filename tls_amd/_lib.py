@@ -32,7 +32,7 @@ SYMBOLS = (
     "tls_device_count", "tls_ctx_create", "tls_ctx_destroy", "tls_last_error", "tls_version", "tls_abi_version",
     "tls_device_name", "tls_get_options", "tls_set_options", "tls_debug_set_switch", "tls_debug_get_switches", "tls_search", "tls_search_batch", "tls_power_batch", "tls_prepare", "tls_update_flux", "tls_execute",
     "tls_synchronize", "tls_fetch", "tls_execute_timed", "tls_plan_info", "tls_last_kernel", "tls_grid_cells", "tls_period_costs", "tls_t0_fit", "tls_pink_noise", "tls_spectra", "tls_kernel_timing", "tls_debug_phase_cycles", "tls_debug_cumsum", "tls_debug_folded", "tls_debug_prefix", "tls_debug_check_counts", "tls_debug_poison_lds", "tls_debug_period_cycles", "tls_debug_batch_group_ms",
-    "tls_debug_post_search", "tls_debug_device_bytes", "tls_power_batch_stats", "tls_debug_transit_stats",
+    "tls_debug_post_search", "tls_debug_device_bytes", "tls_debug_perm_table", "tls_power_batch_stats", "tls_debug_transit_stats",
     "tls_power_batch_models", "tls_debug_transit_models",
     "tls_inject_transits", "tls_null_rows", "tls_debug_null_words", "tls_medfilt_detrend",
     "tls_biweight_detrend",
@@ -65,7 +65,7 @@ class Options(ctypes.Structure):
 
 # every switch tls_debug_set_switch knows (the two public ones included): Context.set_options(**switches) takes them all
 SWITCH_NAMES = ("exact_prefix", "slim", "prune", "screen32", "no_screen", "fast_slab", "x_staged", "split", "split_batch", "sort2",
-                "threads", "blocks", "plan_threads", "t0_rot", "prune_min_live", "band_max")
+                "threads", "blocks", "plan_threads", "t0_rot", "prune_min_live", "perm_table", "band_max")
 
 
 def switches_text(switches):
@@ -273,6 +273,8 @@ def load():
                                          _c_double_p, _c_double_p]
     lib.tls_debug_device_bytes.restype = ci
     lib.tls_debug_device_bytes.argtypes = [vp, _c_int64_p, _c_int64_p]
+    lib.tls_debug_perm_table.restype = ci
+    lib.tls_debug_perm_table.argtypes = [vp, _c_int64_p, _c_int64_p, _c_int64_p]
     lib.tls_debug_cumsum.restype = ci
     lib.tls_debug_cumsum.argtypes = [vp, _c_double_p, i64, _c_double_p, ci]
     lib.tls_grid_cells.restype = ci
@@ -831,6 +833,14 @@ class Context(object):
         total, scratch = ctypes.c_int64(0), ctypes.c_int64(0)
         self._check(self._lib.tls_debug_device_bytes(self._h, ctypes.byref(total), ctypes.byref(scratch)))
         return int(total.value), int(scratch.value)
+
+    def perm_table(self):
+        """The held plan's table of folded orders (four-slot kernel): `bytes` (0 when the plan has none), `filled` once a
+        launch of the plan has stored it (later launches read it and sort nothing), and `plan_reuses`, the prepare() calls the
+        context has answered from a held plan (they keep the table)."""
+        size, filled, reuses = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        self._check(self._lib.tls_debug_perm_table(self._h, ctypes.byref(size), ctypes.byref(filled), ctypes.byref(reuses)))
+        return {"bytes": int(size.value), "filled": bool(filled.value), "plan_reuses": int(reuses.value)}
 
     def folded(self, n_periods, n):
         """Developer/test entry: the folded flux of every period of the prepared plan, (n_periods, n), as the

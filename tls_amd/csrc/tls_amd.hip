@@ -88,6 +88,7 @@ struct Switches {
     int32_t exact_prefix, slim;
     int32_t prune, screen32, no_screen, fast_slab, x_staged, split, split_batch, sort2, threads, blocks, plan_threads, t0_rot;
     int64_t prune_min_live;
+    int64_t perm_table;   // the four-slot kernel's table of folded orders: -1 the library decides, 0 none, k > 0 at most k MiB
     double band_max;
 };
 struct SwitchName { const char* name; const char* env; size_t offset; int kind; };   // kind 0: int32, 1: int64, 2: double
@@ -98,6 +99,7 @@ const SwitchName kSwitchNames[] = {
     TLS_SW(x_staged, "TLS_X_STAGED", 0), TLS_SW(split, "TLS_SPLIT", 0), TLS_SW(split_batch, "TLS_SPLIT_BATCH", 0),
     TLS_SW(sort2, "TLS_SORT2", 0), TLS_SW(threads, "TLS_THREADS", 0), TLS_SW(blocks, "TLS_BLOCKS", 0),
     TLS_SW(plan_threads, "TLS_PLAN_THREADS", 0), TLS_SW(t0_rot, "TLS_T0_ROT", 0), TLS_SW(prune_min_live, "TLS_PRUNE_MIN_LIVE", 1),
+    TLS_SW(perm_table, "TLS_PERM_TABLE", 1),
     TLS_SW(band_max, "TLS_BAND_MAX", 2),
 };
 #undef TLS_SW
@@ -209,6 +211,12 @@ struct tls_ctx {
     DevBuf<unsigned long long> d_phase, d_check;
     DevBuf<unsigned int> d_queue, d_squeue, d_lists, d_perm, d_pqueues;   // d_pqueues: tls_power_batch's T0-fit queues   // d_squeue: the search kernel's self-rewinding queue
     DevBuf<double> d_curve_S0, d_curve_w0;   // survey batches
+    // The four-slot kernel's table of folded orders: one row per period of the plan (tlsdev::slim_perm_row entries).  The
+    // order is numpy's stable argsort of fold_phase(t, period) -- the flux, the weights and the noise do not enter it --, so
+    // it lives as long as the plan key: the plan's first four-slot launch stores it, every later one reads it.
+    DevBuf<unsigned short> d_perm_table;     // (grows like every DevBuf and is kept: plans of different period counts alternate on a context)
+    size_t perm_table_entries = 0;           // entries of it the held plan uses; 0: the plan has no table
+    bool perm_filled = false;                // a launch that stored every row has been enqueued (stream order does the rest)
     // survey batches: two slots of device + pinned host buffers, a second stream for the transfers
     struct BatchSlot {
         DevBuf<double> d_y, d_w, d_S0, d_w0, d_chi2, d_depth;
@@ -729,6 +737,17 @@ int64_t ctx_nb_for(int64_t n, size_t n_widths) {
     return std::min<int64_t>(n, (int64_t)((kLdsPerCU - hdr) / 4));
 }
 
+// words of d_perm: a stashed order per workgroup in flight (n entries of the classic family's index type; a row of the
+// four-slot kernel's thread-major layout, tlsdev::slim_perm_row 16-bit entries)
+size_t perm_scratch_words(const tls_ctx* ctx, size_t n) {
+    size_t per_block = n;
+    if (ctx->slim_blocks > 0) per_block = std::max(per_block, (size_t)tlsdev::slim_perm_row(ctx->slim_threads) / 2);
+    return (size_t)std::max(ctx->blocks, ctx->slim_blocks) * per_block;
+}
+
+// the table of folded orders of a four-slot plan is held up to this size (switch perm_table: another cap, or none)
+constexpr size_t kPermTableMaxBytes = (size_t)1 << 30;
+
 // work order of the period queue: most expensive first (longest-processing-time first), ties in grid order --
 // a stable LSD radix sort of the 32-bit key (max cost - cost), three passes of 11 bits
 void order_by_cost(const std::vector<int64_t>& cost, std::vector<int>& order) {
@@ -895,6 +914,7 @@ int enqueue(tls_ctx* ctx, bool count_work, bool phase_clock = false, double* deb
     a.curve_S0 = ctx->over_S0 ? ctx->over_S0 : ctx->d_curve_S0.ptr;
     a.curve_w0 = ctx->over_w0 ? ctx->over_w0 : ctx->d_curve_w0.ptr;
     a.perm_scratch = ctx->d_perm.ptr;
+    a.perm_table = nullptr; a.perm_filled = 0;
     a.n = ctx->n; a.W = ctx->W; a.M = ctx->M;
     a.n_periods = ctx->n_periods; a.n_widths = ctx->n_widths; a.nb = ctx->nb;
     a.batch_lo = 0; a.batch_n = 0; a.tile_prefix = ctx->d_tile_prefix.ptr;
@@ -950,6 +970,7 @@ int enqueue(tls_ctx* ctx, bool count_work, bool phase_clock = false, double* deb
         // four period slots per CU (tls_slim_kernel.hip.h): plain variant, uniform weights, 256-thread workgroups
         kernel_name = "slim";
         a.lds_bytes = (long long)ctx->slim_lds;
+        a.perm_table = ctx->perm_table_entries ? ctx->d_perm_table.ptr : nullptr; a.perm_filled = ctx->perm_filled ? 1 : 0;
         const bool wide = ctx->slim_threads == tlsdev::kSlimThreadsWide;
         auto kernel = wide ? (count_work ? tlsdev::tls_slim_kernel<true, tlsdev::kSlimThreadsWide> : tlsdev::tls_slim_kernel<false, tlsdev::kSlimThreadsWide>)
                            : (count_work ? tlsdev::tls_slim_kernel<true, tlsdev::kSlimThreads> : tlsdev::tls_slim_kernel<false, tlsdev::kSlimThreads>);
@@ -959,6 +980,7 @@ int enqueue(tls_ctx* ctx, bool count_work, bool phase_clock = false, double* deb
             hipLaunchKernelGGL(kernel, dim3((unsigned)ctx->slim_blocks), dim3((unsigned)ctx->slim_threads), ctx->slim_lds, ctx->stream, a);
             e = hipGetLastError();
         }
+        if (e == hipSuccess && a.perm_table) ctx->perm_filled = true;   // (every period of the plan passes through a launch)
     } else if (ctx->resident) e = TLS_LAUNCH_RESIDENT(ctx->blocks);
     else if (!split) e = TLS_LAUNCH_SLAB(ctx->blocks);
     else {
@@ -1577,7 +1599,7 @@ void tls_ctx_destroy(tls_ctx* ctx) {
     if (ctx->ev_stage) (void)hipEventDestroy(ctx->ev_stage);
     ctx->d_scratch.release(); ctx->d_pack.release();
     ctx->d_gather.release(); ctx->d_scalar.release(); ctx->d_stage.release();
-    ctx->d_partials.release(); ctx->d_tiles_done.release(); ctx->d_check.release(); ctx->d_spec.release(); ctx->d_queue.release(); ctx->d_squeue.release(); ctx->d_pqueues.release(); ctx->d_phase.release(); ctx->d_lists.release(); ctx->d_perm.release(); ctx->d_curve_S0.release(); ctx->d_curve_w0.release();
+    ctx->d_partials.release(); ctx->d_tiles_done.release(); ctx->d_check.release(); ctx->d_spec.release(); ctx->d_queue.release(); ctx->d_squeue.release(); ctx->d_pqueues.release(); ctx->d_phase.release(); ctx->d_lists.release(); ctx->d_perm.release(); ctx->d_perm_table.release(); ctx->d_curve_S0.release(); ctx->d_curve_w0.release();
     ctx->d_ft.release(); ctx->d_fy.release(); ctx->d_fsig.release(); ctx->d_fep.release(); ctx->d_fres.release(); ctx->d_fscratch.release(); ctx->d_frot.release(); ctx->d_frperm.release(); ctx->d_pink.release();
     ctx->d_tstats.release(); ctx->d_tranges.release(); ctx->d_models.release(); ctx->d_inject.release(); ctx->d_inject_count.release();
     ctx->d_null.release(); ctx->d_null_words.release(); ctx->d_detrend.release(); ctx->d_windows.release();
@@ -1620,6 +1642,7 @@ int tls_prepare(tls_ctx* ctx, const double* t, const double* y, const double* dy
         // uniform dy after per-point dy (or the reverse): a different kernel variant and layout -- plan again
     }
     ctx->key.valid = false;
+    ctx->perm_filled = false; ctx->perm_table_entries = 0;   // (the table of folded orders belongs to the key)
 
     std::vector<tlsdev::WidthEntry> widths;
     std::vector<double> q;
@@ -1912,7 +1935,22 @@ int tls_prepare(tls_ctx* ctx, const double* t, const double* y, const double* dy
     ctx->list_stride = (list_cap + 63) / 64 * 64;
     // three arrays per workgroup: the live units, (pruning) the bound of each, and the units the bound keeps
     TLS_HIP(ctx, ctx->d_lists.reserve((size_t)std::max(std::max(ctx->blocks, ctx->slim_blocks), (!ctx->resident && ctx->split) ? ctx->split_blocks : 0) * 3 * ctx->list_stride));
-    if (ctx->slim_blocks > 0) TLS_HIP(ctx, ctx->d_perm.reserve((size_t)std::max(ctx->blocks, ctx->slim_blocks) * (size_t)n));   // (band resolution stashes the order of a period)
+    if (ctx->slim_blocks > 0) TLS_HIP(ctx, ctx->d_perm.reserve(perm_scratch_words(ctx, (size_t)n)));   // (band resolution stashes the order of a period)
+    {
+        // the table of folded orders of a four-slot plan, within its budget; a plan without one sorts in every launch
+        size_t want = 0;
+        if (ctx->slim_blocks > 0 && ctx->opt.perm_table != 0) {
+            const size_t entries = (size_t)n_periods * (size_t)tlsdev::slim_perm_row(ctx->slim_threads);
+            const size_t cap = ctx->opt.perm_table > 0 ? (size_t)ctx->opt.perm_table << 20 : kPermTableMaxBytes;
+            if (entries * sizeof(unsigned short) <= cap) want = entries;
+        }
+        if (want > ctx->d_perm_table.cap && ctx->d_perm_table.reserve(want) != hipSuccess) {
+            (void)hipGetLastError();   // (no room on the device: not an error)
+            ctx->d_perm_table.release();
+            want = 0;
+        }
+        ctx->perm_table_entries = want;
+    }
     ctx->prune_min_live = ctx->opt.prune_min_live >= 0 ? (long long)ctx->opt.prune_min_live : 256;
     ctx->p2_shift = 4;  // block length of the coarse prefix sum of e^2: at most kP2MaxBlocks blocks
     while ((((size_t)M + ((size_t)1 << ctx->p2_shift) - 1) >> ctx->p2_shift) > (size_t)tlsdev::kP2MaxBlocks) ++ctx->p2_shift;
@@ -2604,7 +2642,7 @@ int tls_debug_poison_lds(tls_ctx* ctx, uint32_t word) {
     TLS_HIP(ctx, hipGetLastError());
     // ... and the per-workgroup scratch in HBM (slabs, live-unit lists, stashed orders, the screen's and the sorts' scratch, the
     // T0 fit's slabs): all ones -- NaNs as doubles -- as fresh device memory may be.  (Not the queues and counters, whose zero
-    // state between launches is the kernels' own invariant, nor the plan and the results.)
+    // state between launches is the kernels' own invariant, nor the plan, its table of folded orders and the results.)
     auto smear = [&](void* ptr, size_t bytes) -> hipError_t { return ptr && bytes ? hipMemsetAsync(ptr, 0xFF, bytes, ctx->stream) : hipSuccess; };
     TLS_HIP(ctx, smear(ctx->d_scratch.ptr, ctx->d_scratch.cap * sizeof(double)));
     TLS_HIP(ctx, smear(ctx->d_lists.ptr, ctx->d_lists.cap * sizeof(unsigned int)));
@@ -2777,7 +2815,7 @@ int tls_debug_device_bytes(const tls_ctx* ctx, int64_t* total, int64_t* t0_fit_s
     add(ctx->d_plan); add(ctx->d_out);
     add(ctx->d_scratch); add(ctx->d_pack); add(ctx->d_gather); add(ctx->d_scalar); add(ctx->d_stage);
     add(ctx->d_phase); add(ctx->d_check);
-    add(ctx->d_queue); add(ctx->d_squeue); add(ctx->d_lists); add(ctx->d_perm); add(ctx->d_pqueues);
+    add(ctx->d_queue); add(ctx->d_squeue); add(ctx->d_lists); add(ctx->d_perm); add(ctx->d_perm_table); add(ctx->d_pqueues);
     add(ctx->d_curve_S0); add(ctx->d_curve_w0);
     for (const auto& sl : ctx->slot) {
         add(sl.d_y); add(sl.d_w); add(sl.d_S0); add(sl.d_w0); add(sl.d_chi2); add(sl.d_depth); add(sl.d_row);
@@ -2788,6 +2826,14 @@ int tls_debug_device_bytes(const tls_ctx* ctx, int64_t* total, int64_t* t0_fit_s
     add(ctx->d_split); add(ctx->d_park); add(ctx->d_band);
     *total = (int64_t)sum;
     *t0_fit_scratch = (int64_t)(ctx->d_fscratch.cap * sizeof(double));
+    return TLS_OK;
+}
+
+int tls_debug_perm_table(const tls_ctx* ctx, int64_t* bytes, int64_t* filled, int64_t* plan_reuses) {
+    if (!ctx || !bytes || !filled) return TLS_E_ARG;
+    if (plan_reuses) *plan_reuses = ctx->plan_reuses;
+    *bytes = (int64_t)(ctx->perm_table_entries * sizeof(unsigned short));
+    *filled = ctx->perm_table_entries && ctx->perm_filled ? 1 : 0;
     return TLS_OK;
 }
 
@@ -2921,7 +2967,7 @@ static int search_batch_impl(tls_ctx* ctx, const double* y, const double* dy, in
     int rc = reserve_batch_staging(ctx, group, nn, 3 * (size_t)group * np);
     for (auto& sl : ctx->slot)
         if (rc || (rc = reserve_batch_slot(ctx, sl, group, nn, np))) return rc;
-    TLS_HIP(ctx, ctx->d_perm.reserve((size_t)std::max(ctx->blocks, ctx->slim_blocks) * nn));
+    TLS_HIP(ctx, ctx->d_perm.reserve(perm_scratch_words(ctx, nn)));
     const int64_t n_groups = (n_curves + group - 1) / group;
     auto drain = [&](int64_t g) -> int {   // results of group g: wait for its download, copy to the caller's arrays
         auto& sl = ctx->slot[g & 1];
@@ -3048,7 +3094,7 @@ static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, cons
     // device buffers of one group: flux (weights), per-curve constants, search results, spectra, summaries, T0-fit inputs
     auto& sl = ctx->slot[0];
     if ((rc = reserve_batch_slot(ctx, sl, group, nn, np))) return rc;
-    TLS_HIP(ctx, ctx->d_perm.reserve((size_t)std::max(ctx->blocks, ctx->slim_blocks) * nn));
+    TLS_HIP(ctx, ctx->d_perm.reserve(perm_scratch_words(ctx, nn)));
     int64_t max_len = 1;
     for (int64_t r = 0; r < tmpl->n_rows; ++r) max_len = std::max(max_len, tmpl->length[r]);
     PostSearchBufs pb;

@@ -525,7 +525,12 @@ struct SearchArgs {
     const double* curve_S0;     // [n_curves] S0 per curve (n_curves > 1; else S0 / w0 below)
     const double* curve_w0;     // [n_curves]
     unsigned int* perm_scratch; // [blocks][n] the sort permutation of the period in flight (n_curves > 1)
-    long long list_cap;         // entries of one array: live units | their bounds (float)
+    // four-slot kernel: the plan's table of folded orders, one row of slim_perm_row(THREADS) entries per period of the plan
+    // (tls_slim_kernel.hip.h, slim_perm_slot), or nullptr; perm_filled != 0: every row holds its period's order -- the launch
+    // reads it and sorts nothing; 0: the launch sorts and stores every row it passes
+    unsigned short* perm_table;
+    int perm_filled;
+    long long list_cap;        // entries of one array: live units | their bounds (float)
     long long prune_min_live;   // prune a period (tile) only when at least this many units are live
     int p2_shift;               // log2 of the block length of the coarse prefix sum of e^2 (pruning bound)
     double depth_min;

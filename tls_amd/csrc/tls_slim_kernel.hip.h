@@ -13,7 +13,8 @@
 //     the flux is gathered over its LDS home;
 //   * the prefix sum runs in place (fast mode: a plain scan; exact mode: exact_cumsum's aliased form, f shifted by one).
 // Uniform weights, no pruning, no fp32 screen (the host takes the other kernel for those); survey batches share the sort of a
-// period as there.  Cells, predicate, tie rule and reductions are the other kernel's code (consider_cells, settle_best, ...);
+// period as there, and the launches of a plan share it through the plan's table of folded orders (slim_perm_slot below: the
+// first launch stores every period's order, the later ones sort nothing).  Cells, predicate, tie rule and reductions are the other kernel's code (consider_cells, settle_best, ...);
 // values differ from it by the rounding of the difference taps (chi^2 to ~1e-13).
 //
 // Reference mapping as tls_search_body.inc.h: core.py:15-18,113-188, helpers.py:70-73.
@@ -349,6 +350,39 @@ __device__ __forceinline__ void slim_fold_and_sort(const double* t, int n, doubl
     }
 }
 
+// The folded order of a period in global memory: the stash of a survey group and of the band resolution (perm_scratch), and a
+// row of the plan's table (SearchArgs::perm_table) -- the order is a function of the time stamps and the period alone, so the
+// first launch of a plan stores every row and the later ones sort nothing.  THREAD-MAJOR: the gather's thread `tid` keeps the
+// entries k = tid + j * THREADS, j < kSlimPer, and finds them side by side (40 bytes: a few wide loads instead of twenty
+// 2-byte ones); a row has THREADS * kSlimPer entries whatever n is, entries of k >= n are zero.
+__host__ __device__ constexpr int slim_perm_row(int threads) { return threads * kSlimPer; }
+__host__ __device__ constexpr int slim_perm_slot(int threads, int k) {   // where the k-th folded point's index is kept in a row
+    return (int)(((unsigned int)k % (unsigned int)threads) * (unsigned int)kSlimPer + (unsigned int)k / (unsigned int)threads);
+}
+struct alignas(8) SlimOrderWords { unsigned int w[kSlimPer / 2]; };   // a thread's part of a row
+static_assert(kSlimPer % 2 == 0 && sizeof(SlimOrderWords) == 2 * kSlimPer, "a thread's entries are packed in pairs");
+template <int THREADS>
+__device__ __forceinline__ void slim_store_order(unsigned short* row, const unsigned short* perm, int n) {
+    const int tid = slim_fresh(threadIdx.x);
+    SlimOrderWords mine;
+#pragma unroll
+    for (int j = 0; j < kSlimPer; j += 2) {
+        const int k0 = tid + j * THREADS, k1 = k0 + THREADS;
+        const unsigned int lo = k0 < n ? (unsigned int)perm[k0] : 0u, hi = k1 < n ? (unsigned int)perm[k1] : 0u;
+        mine.w[j / 2] = lo | (hi << 16);
+    }
+    reinterpret_cast<SlimOrderWords*>(row)[tid] = mine;
+}
+template <int THREADS>
+__device__ __forceinline__ void slim_load_order(const unsigned short* row, int (&idx)[kSlimPer]) {
+    const SlimOrderWords mine = reinterpret_cast<const SlimOrderWords*>(row)[slim_fresh(threadIdx.x)];
+#pragma unroll
+    for (int j = 0; j < kSlimPer; j += 2) {
+        idx[j] = (int)(mine.w[j / 2] & 0xffffu);
+        idx[j + 1] = (int)(mine.w[j / 2] >> 16);
+    }
+}
+
 template <bool COUNTING, int THREADS = kSlimThreads>
 __global__ void __launch_bounds__(THREADS, 4)
 tls_slim_kernel(const SearchArgs) {
@@ -435,15 +469,22 @@ tls_slim_kernel(const SearchArgs) {
         pc.start(ap->phase_cycles);
 
         // ---- phase 1: fold + stable sort by phase (core.py:119-120), on 32-bit keys (slim_fold_and_sort) -------------------
-        slim_fold_and_sort<THREADS>(ap->t, n, period, RS, X, wsum, s_work, scratch, pc);
-        pc.mark(3);
-        // survey mode: the permutation outlives the light curves of the batch in global memory
+        // A plan whose table of orders is filled has nothing to sort: the period's row is the order (phase clocks 0-3 and 8
+        // stay zero).  Otherwise the period is sorted, and its row, where the plan has a table, stored for the launches to come.
+        unsigned short* const row_g = ap->perm_table ? ap->perm_table + (long long)p * slim_perm_row(THREADS) : nullptr;
         const unsigned short* perm_g = nullptr;
-        if (ap->n_curves > 1 || resolve_band) {   // (resolution evaluates the few windows that pass from the flux in global memory)
-            unsigned short* pg = reinterpret_cast<unsigned short*>(ap->perm_scratch + (long long)blockIdx.x * n);
-            for (int k = tid; k < n; k += nt) pg[k] = perm[k];
-            perm_g = pg;
-            wg_sync();
+        if (row_g != nullptr && ap->perm_filled != 0) {
+            perm_g = row_g;
+        } else {
+            slim_fold_and_sort<THREADS>(ap->t, n, period, RS, X, wsum, s_work, scratch, pc);
+            pc.mark(3);
+            // survey mode: the permutation outlives the light curves of the batch in global memory
+            const bool stash = ap->n_curves > 1 || resolve_band;   // (resolution evaluates the few windows that pass from the flux in global memory)
+            if (row_g != nullptr || stash) {
+                unsigned short* pg = row_g ? row_g : reinterpret_cast<unsigned short*>(ap->perm_scratch) + (long long)blockIdx.x * slim_perm_row(THREADS);
+                slim_store_order<THREADS>(pg, perm, n);
+                if (stash) { perm_g = pg; wg_sync(); }
+            }
         }
         for (int curve = 0; curve < ap->n_curves; ++curve) {
         const bool exact_mode = period_exact || curve_exact;
@@ -464,10 +505,14 @@ tls_slim_kernel(const SearchArgs) {
             // the folded order into registers first: the flux lands on the order's own LDS home
             int idx[kSlimPer];
             const int tid_g = slim_fresh(tid);
+            if (perm_g != nullptr) {
+                slim_load_order<THREADS>(perm_g, idx);
+            } else {
 #pragma unroll
-            for (int j = 0; j < kSlimPer; ++j) {
-                const int k = tid_g + j * nt;
-                idx[j] = k < n ? (perm_g ? (int)perm_g[k] : (int)perm[k]) : 0;
+                for (int j = 0; j < kSlimPer; ++j) {
+                    const int k = tid_g + j * nt;
+                    idx[j] = k < n ? (int)perm[k] : 0;
+                }
             }
             wg_sync();   // (every thread has its part of the order; global reads of perm_g included)
             double* fdst = exact_mode ? X + 1 : X;   // exact mode: C[k+1] goes over f[k] (exact_cumsum's aliased form)
@@ -840,7 +885,7 @@ tls_slim_kernel(const SearchArgs) {
                 double Bs = 0.0;
                 for (int tt = lane; tt < L; tt += kWave) {
                     const int pp = i + tt, src = pp < n ? pp : pp - n;
-                    Bs = fma(qg[tt], 1.0 - y_c[perm_g[src]], Bs);
+                    Bs = fma(qg[tt], 1.0 - y_c[perm_g[slim_perm_slot(THREADS, src)]], Bs);
                 }
 #pragma unroll
                 for (int delta = kWave / 2; delta > 0; delta >>= 1) Bs += __shfl_down(Bs, delta, kWave);
