@@ -87,6 +87,7 @@ struct View {
 struct Switches {
     int32_t exact_prefix, slim;
     int32_t prune, screen32, no_screen, fast_slab, x_staged, split, split_batch, sort2, threads, blocks, plan_threads, t0_rot;
+    int32_t reg_scan;     // four-slot kernel: stored orders stretch-major, phase 2 of a reading launch in registers (0: thread-major rows)
     int64_t prune_min_live;
     int64_t perm_table;   // the four-slot kernel's table of folded orders: -1 the library decides, 0 none, k > 0 at most k MiB
     double band_max;
@@ -99,7 +100,7 @@ const SwitchName kSwitchNames[] = {
     TLS_SW(x_staged, "TLS_X_STAGED", 0), TLS_SW(split, "TLS_SPLIT", 0), TLS_SW(split_batch, "TLS_SPLIT_BATCH", 0),
     TLS_SW(sort2, "TLS_SORT2", 0), TLS_SW(threads, "TLS_THREADS", 0), TLS_SW(blocks, "TLS_BLOCKS", 0),
     TLS_SW(plan_threads, "TLS_PLAN_THREADS", 0), TLS_SW(t0_rot, "TLS_T0_ROT", 0), TLS_SW(prune_min_live, "TLS_PRUNE_MIN_LIVE", 1),
-    TLS_SW(perm_table, "TLS_PERM_TABLE", 1),
+    TLS_SW(perm_table, "TLS_PERM_TABLE", 1), TLS_SW(reg_scan, "TLS_REG_SCAN", 0),
     TLS_SW(band_max, "TLS_BAND_MAX", 2),
 };
 #undef TLS_SW
@@ -217,6 +218,7 @@ struct tls_ctx {
     DevBuf<unsigned short> d_perm_table;     // (grows like every DevBuf and is kept: plans of different period counts alternate on a context)
     size_t perm_table_entries = 0;           // entries of it the held plan uses; 0: the plan has no table
     bool perm_filled = false;                // a launch that stored every row has been enqueued (stream order does the rest)
+    int slim_perm_per = 0;                   // the layout of the plan's stored orders (SearchArgs::perm_per): > 0 stretch-major
     // survey batches: two slots of device + pinned host buffers, a second stream for the transfers
     struct BatchSlot {
         DevBuf<double> d_y, d_w, d_S0, d_w0, d_chi2, d_depth;
@@ -738,7 +740,7 @@ int64_t ctx_nb_for(int64_t n, size_t n_widths) {
 }
 
 // words of d_perm: a stashed order per workgroup in flight (n entries of the classic family's index type; a row of the
-// four-slot kernel's thread-major layout, tlsdev::slim_perm_row 16-bit entries)
+// four-slot kernel in the plan's layout, tlsdev::slim_perm_row 16-bit entries)
 size_t perm_scratch_words(const tls_ctx* ctx, size_t n) {
     size_t per_block = n;
     if (ctx->slim_blocks > 0) per_block = std::max(per_block, (size_t)tlsdev::slim_perm_row(ctx->slim_threads) / 2);
@@ -914,7 +916,7 @@ int enqueue(tls_ctx* ctx, bool count_work, bool phase_clock = false, double* deb
     a.curve_S0 = ctx->over_S0 ? ctx->over_S0 : ctx->d_curve_S0.ptr;
     a.curve_w0 = ctx->over_w0 ? ctx->over_w0 : ctx->d_curve_w0.ptr;
     a.perm_scratch = ctx->d_perm.ptr;
-    a.perm_table = nullptr; a.perm_filled = 0;
+    a.perm_table = nullptr; a.perm_filled = 0; a.perm_per = 0;
     a.n = ctx->n; a.W = ctx->W; a.M = ctx->M;
     a.n_periods = ctx->n_periods; a.n_widths = ctx->n_widths; a.nb = ctx->nb;
     a.batch_lo = 0; a.batch_n = 0; a.tile_prefix = ctx->d_tile_prefix.ptr;
@@ -971,6 +973,7 @@ int enqueue(tls_ctx* ctx, bool count_work, bool phase_clock = false, double* deb
         kernel_name = "slim";
         a.lds_bytes = (long long)ctx->slim_lds;
         a.perm_table = ctx->perm_table_entries ? ctx->d_perm_table.ptr : nullptr; a.perm_filled = ctx->perm_filled ? 1 : 0;
+        a.perm_per = ctx->slim_perm_per;
         const bool wide = ctx->slim_threads == tlsdev::kSlimThreadsWide;
         auto kernel = wide ? (count_work ? tlsdev::tls_slim_kernel<true, tlsdev::kSlimThreadsWide> : tlsdev::tls_slim_kernel<false, tlsdev::kSlimThreadsWide>)
                            : (count_work ? tlsdev::tls_slim_kernel<true, tlsdev::kSlimThreads> : tlsdev::tls_slim_kernel<false, tlsdev::kSlimThreads>);
@@ -1950,6 +1953,10 @@ int tls_prepare(tls_ctx* ctx, const double* t, const double* y, const double* dy
             want = 0;
         }
         ctx->perm_table_entries = want;
+        // the layout of the plan's stored orders (table rows, a survey group's stash): stretch-major where the fast-mode
+        // scan's stretch fits a thread's entries (tls_slim_kernel.hip.h), thread-major otherwise (and by switch reg_scan = 0)
+        const int per = ctx->slim_blocks > 0 ? tlsdev::slim_scan_per(ctx->slim_threads, (int)M) : 0;
+        ctx->slim_perm_per = (ctx->opt.reg_scan != 0 && per <= tlsdev::kSlimPer && W <= n) ? per : 0;
     }
     ctx->prune_min_live = ctx->opt.prune_min_live >= 0 ? (long long)ctx->opt.prune_min_live : 256;
     ctx->p2_shift = 4;  // block length of the coarse prefix sum of e^2: at most kP2MaxBlocks blocks

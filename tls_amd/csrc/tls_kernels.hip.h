@@ -92,7 +92,8 @@ enum CheckCode {
 
 constexpr int kWave = 64;
 constexpr int kMaxWaves = 16;  // up to 1024 threads per workgroup
-constexpr int kPhases = 40;    // phase-clock slots 0..31 and work statistics 32..39 (tls_amd/_lib.py names them)
+constexpr int kPhases = 41;    // phase-clock slots 0..31 and work statistics 32..40 (tls_amd/_lib.py names them)
+constexpr int kStatRegisterScans = 40;   // four-slot kernel: prefix sums formed in registers from a stretch-major order (phase 2)
 #ifndef TLS_KR
 #define TLS_KR 5
 #endif
@@ -530,6 +531,9 @@ struct SearchArgs {
     // reads it and sorts nothing; 0: the launch sorts and stores every row it passes
     unsigned short* perm_table;
     int perm_filled;
+    // the layout of a row (and of a survey group's stash): > 0 stretch-major, thread `tid` keeps the patched positions
+    // [tid * perm_per, tid * perm_per + perm_per) -- the fast-mode scan's own stretches, perm_per <= kSlimPer --; 0 thread-major
+    int perm_per;
     long long list_cap;        // entries of one array: live units | their bounds (float)
     long long prune_min_live;   // prune a period (tile) only when at least this many units are live
     int p2_shift;               // log2 of the block length of the coarse prefix sum of e^2 (pruning bound)

@@ -11,7 +11,10 @@
 //   * the sort orders 32-bit phase keys held in registers (ties: the exact phases, then the index -- numpy's stable order),
 //     two points to a bucket, its records inside the region X takes afterwards; the permutation waits in registers while
 //     the flux is gathered over its LDS home;
-//   * the prefix sum runs in place (fast mode: a plain scan; exact mode: exact_cumsum's aliased form, f shifted by one).
+//   * the prefix sum runs in place (fast mode: a plain scan; exact mode: exact_cumsum's aliased form, f shifted by one);
+//   * a launch that READS a stored order in stretch-major layout (slim_perm_slot below: a thread's entries are the patched
+//     samples of its scan stretch) forms the fast-mode prefix sum in registers instead -- gather, patch and scan without the
+//     flux ever being in LDS, the in-place scan's operations in their order, X the same bits (phase 2 of the kernel).
 // Uniform weights, no pruning, no fp32 screen (the host takes the other kernel for those); survey batches share the sort of a
 // period as there, and the launches of a plan share it through the plan's table of folded orders (slim_perm_slot below: the
 // first launch stores every period's order, the later ones sort nothing).  Cells, predicate, tie rule and reductions are the other kernel's code (consider_cells, settle_best, ...);
@@ -352,27 +355,47 @@ __device__ __forceinline__ void slim_fold_and_sort(const double* t, int n, doubl
 
 // The folded order of a period in global memory: the stash of a survey group and of the band resolution (perm_scratch), and a
 // row of the plan's table (SearchArgs::perm_table) -- the order is a function of the time stamps and the period alone, so the
-// first launch of a plan stores every row and the later ones sort nothing.  THREAD-MAJOR: the gather's thread `tid` keeps the
-// entries k = tid + j * THREADS, j < kSlimPer, and finds them side by side (40 bytes: a few wide loads instead of twenty
-// 2-byte ones); a row has THREADS * kSlimPer entries whatever n is, entries of k >= n are zero.
+// first launch of a plan stores every row and the later ones sort nothing.  A row has THREADS * kSlimPer entries whatever n
+// is, a thread's kSlimPer entries side by side (40 bytes: a few wide loads instead of twenty 2-byte ones), in one of two
+// layouts, the plan's choice (SearchArgs::perm_per, slim_scan_per):
+//   * STRETCH-MAJOR (per > 0): thread `tid` keeps the PATCHED positions k = tid * per + j, j < per -- the stretch the
+//     fast-mode scan gives it -- as original indices, the patch (core.py:126) already applied: position k >= n holds the
+//     index of position k - n.  A reading launch in fast mode gathers, patches and scans in registers (phase 2 below).
+//     Plans whose stretch fits a thread's entries: per = ceil(M / THREADS) made odd <= kSlimPer;
+//   * THREAD-MAJOR (per == 0): thread `tid` keeps the folded positions k = tid + j * THREADS, the gather's own stride.
+// Unused entries are zero.
 __host__ __device__ constexpr int slim_perm_row(int threads) { return threads * kSlimPer; }
-__host__ __device__ constexpr int slim_perm_slot(int threads, int k) {   // where the k-th folded point's index is kept in a row
-    return (int)(((unsigned int)k % (unsigned int)threads) * (unsigned int)kSlimPer + (unsigned int)k / (unsigned int)threads);
+__host__ __device__ constexpr int slim_scan_per(int threads, int M) {   // the fast-mode scan's stretch: odd (LDS banks)
+    return ((M + threads - 1) / threads) | 1;
+}
+__host__ __device__ __forceinline__ constexpr int slim_perm_slot(int threads, int per, int k) {   // where the k-th folded point's index is kept in a row (k < n)
+    return per > 0 ? (int)((unsigned int)k / (unsigned int)per * (unsigned int)kSlimPer + (unsigned int)k % (unsigned int)per)
+                   : (int)(((unsigned int)k % (unsigned int)threads) * (unsigned int)kSlimPer + (unsigned int)k / (unsigned int)threads);
 }
 struct alignas(8) SlimOrderWords { unsigned int w[kSlimPer / 2]; };   // a thread's part of a row
 static_assert(kSlimPer % 2 == 0 && sizeof(SlimOrderWords) == 2 * kSlimPer, "a thread's entries are packed in pairs");
 template <int THREADS>
-__device__ __forceinline__ void slim_store_order(unsigned short* row, const unsigned short* perm, int n) {
+__device__ __forceinline__ void slim_store_order(unsigned short* row, const unsigned short* perm, int n, int M, int per) {
     const int tid = slim_fresh(threadIdx.x);
     SlimOrderWords mine;
+    if (per > 0) {
+        auto entry = [&](int j) -> unsigned int {
+            const int k = tid * per + j;
+            return (j < per && k < M) ? (unsigned int)perm[k < n ? k : k - n] : 0u;
+        };
 #pragma unroll
-    for (int j = 0; j < kSlimPer; j += 2) {
-        const int k0 = tid + j * THREADS, k1 = k0 + THREADS;
-        const unsigned int lo = k0 < n ? (unsigned int)perm[k0] : 0u, hi = k1 < n ? (unsigned int)perm[k1] : 0u;
-        mine.w[j / 2] = lo | (hi << 16);
+        for (int j = 0; j < kSlimPer; j += 2) mine.w[j / 2] = entry(j) | (entry(j + 1) << 16);
+    } else {
+#pragma unroll
+        for (int j = 0; j < kSlimPer; j += 2) {
+            const int k0 = tid + j * THREADS, k1 = k0 + THREADS;
+            const unsigned int lo = k0 < n ? (unsigned int)perm[k0] : 0u, hi = k1 < n ? (unsigned int)perm[k1] : 0u;
+            mine.w[j / 2] = lo | (hi << 16);
+        }
     }
     reinterpret_cast<SlimOrderWords*>(row)[tid] = mine;
 }
+// a thread's entries of a row, as the row's layout has them
 template <int THREADS>
 __device__ __forceinline__ void slim_load_order(const unsigned short* row, int (&idx)[kSlimPer]) {
     const SlimOrderWords mine = reinterpret_cast<const SlimOrderWords*>(row)[slim_fresh(threadIdx.x)];
@@ -482,7 +505,7 @@ tls_slim_kernel(const SearchArgs) {
             const bool stash = ap->n_curves > 1 || resolve_band;   // (resolution evaluates the few windows that pass from the flux in global memory)
             if (row_g != nullptr || stash) {
                 unsigned short* pg = row_g ? row_g : reinterpret_cast<unsigned short*>(ap->perm_scratch) + (long long)blockIdx.x * slim_perm_row(THREADS);
-                slim_store_order<THREADS>(pg, perm, n);
+                slim_store_order<THREADS>(pg, perm, n, M, ap->perm_per);
                 if (stash) { perm_g = pg; wg_sync(); }
             }
         }
@@ -501,26 +524,63 @@ tls_slim_kernel(const SearchArgs) {
         bool undecided = false;
         const double* y_c = ap->y + (long long)curve * n;
         // ---- phase 2: gather (core.py:121-123), patch (core.py:126), prefix sum (helpers.py:72) -- all in the one region ----
-        {
-            // the folded order into registers first: the flux lands on the order's own LDS home
+        // Fast mode on a stored order in stretch-major layout (a reading launch; a survey group's stash): the thread's entries
+        // ARE the samples of its scan stretch, patch included -- gathered into registers, summed from the left, scanned over
+        // the waves and written as X; no flux in LDS, no patch copy, no read-back.  The operations and their order are the
+        // in-place scan's below: X has the same bits.  (No barrier in front: the previous readers of X and of the scratch are
+        // behind the period's last barrier, the stash's store behind its own.)
+        if (perm_g != nullptr && ap->perm_per > 0 && !exact_mode) {
+            const int perm_per = ap->perm_per;
             int idx[kSlimPer];
-            const int tid_g = slim_fresh(tid);
-            if (perm_g != nullptr) {
-                slim_load_order<THREADS>(perm_g, idx);
-            } else {
-#pragma unroll
-                for (int j = 0; j < kSlimPer; ++j) {
-                    const int k = tid_g + j * nt;
-                    idx[j] = k < n ? (int)perm[k] : 0;
-                }
-            }
-            wg_sync();   // (every thread has its part of the order; global reads of perm_g included)
-            double* fdst = exact_mode ? X + 1 : X;   // exact mode: C[k+1] goes over f[k] (exact_cumsum's aliased form)
+            slim_load_order<THREADS>(perm_g, idx);
             double v[kSlimPer];
 #pragma unroll
-            for (int j = 0; j < kSlimPer; ++j) v[j] = y_c[idx[j]];
+            for (int j = 0; j < kSlimPer; ++j) v[j] = y_c[idx[j]];   // (unused entries are zero: a valid index)
+            double* wtot = reinterpret_cast<double*>(scratch);
+            const int lo = tid * perm_per < M ? tid * perm_per : M;
+            const int len = (lo + perm_per < M ? lo + perm_per : M) - lo;
+            double local = 0.0;
 #pragma unroll
-            for (int j = 0; j < kSlimPer; ++j) { const int k = tid_g + j * nt; if (k < n) fdst[k] = v[j]; }
+            for (int j = 0; j < kSlimPer; ++j) if (j < len) local += 1.0 - v[j];
+            pc.mark(4);   // (gather_patch: the row and the flux have arrived; the scan below is cumsum's)
+            const double incl = wave_inclusive_sum(local);
+            if (lane == kWave - 1) wtot[wave] = incl;
+            lds_barrier();
+            double run = 0.0, total = 0.0;
+            for (int u = 0; u < nw; ++u) { const double wv = wtot[u]; if (u < wave) run += wv; total += wv; }
+            run += incl - local;
+#pragma unroll
+            for (int j = 0; j < kSlimPer; ++j) if (j < len) { const double e1 = 1.0 - v[j]; X[lo + j] = run; run += e1; }
+            if (tid == nt - 1) X[M] = total;
+            if (ap->phase_cycles && tid == 0) atomicAdd(&ap->phase_cycles[kStatRegisterScans], 1ull);
+        } else {
+            double* fdst = exact_mode ? X + 1 : X;   // exact mode: C[k+1] goes over f[k] (exact_cumsum's aliased form)
+            if (perm_g != nullptr && ap->perm_per > 0) {
+                const int perm_per = ap->perm_per;
+                // (exact mode on a stretch-major order: rare, entry by entry through the accessor)
+                wg_sync();   // (the previous pass's last reads of X)
+#pragma unroll 1
+                for (int k = tid; k < n; k += nt) fdst[k] = y_c[perm_g[slim_perm_slot(THREADS, perm_per, k)]];
+            } else {
+                // the folded order into registers first: the flux lands on the order's own LDS home
+                int idx[kSlimPer];
+                const int tid_g = slim_fresh(tid);
+                if (perm_g != nullptr) {
+                    slim_load_order<THREADS>(perm_g, idx);
+                } else {
+#pragma unroll
+                    for (int j = 0; j < kSlimPer; ++j) {
+                        const int k = tid_g + j * nt;
+                        idx[j] = k < n ? (int)perm[k] : 0;
+                    }
+                }
+                wg_sync();   // (every thread has its part of the order; global reads of perm_g included)
+                double v[kSlimPer];
+#pragma unroll
+                for (int j = 0; j < kSlimPer; ++j) v[j] = y_c[idx[j]];
+#pragma unroll
+                for (int j = 0; j < kSlimPer; ++j) { const int k = tid_g + j * nt; if (k < n) fdst[k] = v[j]; }
+            }
             wg_sync();
             for (int k = tid; k < W; k += nt) fdst[n + k] = fdst[k];   // core.py:126
             wg_sync();
@@ -528,8 +588,7 @@ tls_slim_kernel(const SearchArgs) {
             if (!exact_mode) {
                 // X[k] = sum of e over [0, k), e = 1 - f: a plain scan in place (every thread its own stretch)
                 double* wtot = reinterpret_cast<double*>(scratch);
-                int per = (M + nt - 1) / nt;
-                if ((per & 1) == 0) per += 1;
+                const int per = slim_scan_per(nt, M);
                 const int lo = tid * per < M ? tid * per : M;
                 const int hi = lo + per < M ? lo + per : M;
                 double local = 0.0;
@@ -549,6 +608,8 @@ tls_slim_kernel(const SearchArgs) {
                 wg_sync();
                 for (int k = tid; k <= M; k += nt) X[k] = (double)k - X[k];   // X = k - numpy.cumsum: an exact subtraction
             }
+        }
+        {
             for (int k = tid; k < region_pad; k += nt) X[M + 1 + k] = -(double)(k + 1) * 1.0e300;   // sentinels (see the other kernel)
             wg_sync();
             pc.mark(5);
@@ -885,7 +946,7 @@ tls_slim_kernel(const SearchArgs) {
                 double Bs = 0.0;
                 for (int tt = lane; tt < L; tt += kWave) {
                     const int pp = i + tt, src = pp < n ? pp : pp - n;
-                    Bs = fma(qg[tt], 1.0 - y_c[perm_g[slim_perm_slot(THREADS, src)]], Bs);
+                    Bs = fma(qg[tt], 1.0 - y_c[perm_g[slim_perm_slot(THREADS, ap->perm_per, src)]], Bs);
                 }
 #pragma unroll
                 for (int delta = kWave / 2; delta > 0; delta >>= 1) Bs += __shfl_down(Bs, delta, kWave);
