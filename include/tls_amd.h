@@ -36,7 +36,7 @@ extern "C" {
  * them as text; 6: tls_transit_stats, tls_power_batch_stats, tls_debug_transit_stats; 7: tls_power_batch_models,
  * tls_debug_transit_models).  A binding compares it with tls_abi_version().  Entries added without changing a layout or
  * signature keep the version (7: tls_inject_transits, tls_null_rows, tls_debug_null_words,
- * tls_medfilt_detrend, tls_biweight_detrend). */
+ * tls_medfilt_detrend, tls_biweight_detrend), (7: tls_power_batch_peaks, tls_find_peaks). */
 #define TLS_AMD_ABI_VERSION 7
 
 #define TLS_OK 0
@@ -415,6 +415,49 @@ int tls_medfilt_detrend(tls_ctx *ctx, const double *y, int64_t n, int64_t n_rows
  * infinite or non-positive y; n_rows == 0 is a no-op. */
 int tls_biweight_detrend(tls_ctx *ctx, const double *t, const double *y, int64_t n, int64_t n_rows,
                          double window_length, double break_tolerance, double *out_flat, double *out_trend);
+
+/* ---- survey mode: the K harmonic-aware peaks of a periodogram, found on the device -------------------------------- */
+/* One peak.  chi2, depth and row are the search's values at the peak's index (NaN / -1 where the call has no source for
+ * them); entries past a row's n_peaks hold NaN in the doubles and -1 in the integers. */
+typedef struct tls_peak {
+    double period, power, chi2, depth;
+    int64_t index, row;
+} tls_peak;
+#define TLS_PEAKS_MAX_K 32
+#define TLS_PEAKS_MAX_RATIOS 16
+/* The selection on one row power[n] over periods[n] (greedy non-maximum suppression with harmonic ratios; the numpy
+ * restatement is tests/peaks_spec.py):
+ *   cand[j] = (j == 0 or power[j] > power[j-1]) and (j == n-1 or power[j] >= power[j+1]) and power[j] >= min_power
+ *   alive = cand; at most k times, while an index is alive:
+ *       j = the lowest index of the largest power among the alive ones (numpy.argmax); take j; P = periods[j]
+ *       for r in (1.0,) + ratios:  c = r * P;  w = min_separation * c;
+ *           alive[i] = false for every i with fabs(periods[i] - c) <= w
+ * A NaN fails every comparison (an index holding one, or next to one, is no candidate); c, w and periods[i] - c are one
+ * IEEE double operation each, without contraction; `periods` need not be sorted.  The result is a selection: bit-equal to
+ * the restatement.  The alive set is a bit mask in the workgroup's LDS up to 2^20 periods and in device memory beyond.
+ * Limits (TLS_E_ARG otherwise): 1 <= k <= TLS_PEAKS_MAX_K; min_separation finite and in [0, 1); 0 <= n_ratios <=
+ * TLS_PEAKS_MAX_RATIOS, every ratio finite and > 0; min_power not NaN (-INFINITY: none); 1 <= n_periods <= 2^30.
+ *
+ * tls_find_peaks: rows the caller holds, power [n_rows][n_periods]; chi2, row and depth each NULL or [n_rows][n_periods];
+ * out_peaks [n_rows][k], out_n_peaks [n_rows].  n_rows == 0 is a no-op. */
+int tls_find_peaks(tls_ctx *ctx, const double *power, const double *chi2, const int64_t *row, const double *depth,
+                   int64_t n_rows, int64_t n_periods, const double *periods, int64_t k, double min_separation,
+                   const double *ratios, int64_t n_ratios, double min_power, tls_peak *out_peaks, int64_t *out_n_peaks);
+/* tls_power_batch_stats plus the peaks of every light curve's detrended power (the row tls_power_batch picks index_power
+ * from), selected on the device behind the pick of each group and copied back with the group's summaries (still one wait
+ * per group).  The first peak of a curve with a fit is its summary's index_power; a curve without a fit has no peaks.
+ * out_stats == NULL: no statistics are computed and row_duration .. out_n_epochs are not read.  out_peaks [n_curves][k],
+ * out_n_peaks [n_curves]. */
+int tls_power_batch_peaks(tls_ctx *ctx, const double *t, const double *y, const double *dy, int64_t n,
+                          int64_t n_curves, const double *periods, int64_t n_periods,
+                          const tls_template *tmpl, const tls_params *params, int64_t median_kernel,
+                          tls_power_summary *out_summary, double *out_chi2, int64_t *out_row, double *out_depth,
+                          double *out_power, double *out_SR, double *out_power_raw,
+                          const double *row_duration, double fill_factor, const double *root, int64_t n_root,
+                          tls_transit_stats *out_stats, int64_t max_epochs, double *out_per_transit,
+                          int64_t *out_n_epochs,
+                          int64_t k, double min_separation, const double *ratios, int64_t n_ratios, double min_power,
+                          tls_peak *out_peaks /* [n_curves][k] */, int64_t *out_n_peaks /* [n_curves] */);
 
 /* ---- host-only planning (no GPU needed) ------------------------------------------ */
 /* Trial cells (duration x T0 positions) each period will enumerate: the data-independent

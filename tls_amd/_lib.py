@@ -26,6 +26,10 @@ BIWEIGHT_MAX_WINDOW = 4095
 BIWEIGHT_C = 5.0
 BIWEIGHT_FTOL = 1e-6
 BIWEIGHT_MAX_ITER = 50
+# include/tls_amd.h TLS_PEAKS_*: the most peaks per row and the most harmonic ratios tls_find_peaks takes
+PEAKS_MAX_K = 32
+PEAKS_MAX_RATIOS = 16
+PEAKS_LDS_PERIODS = 1 << 20   # tls_peaks.hip.h kPeaksLdsPeriods: a longer grid keeps its alive mask in device memory, not in LDS
 
 # every symbol include/tls_amd.h declares (tests check the export list against the header)
 SYMBOLS = (
@@ -35,7 +39,7 @@ SYMBOLS = (
     "tls_debug_post_search", "tls_debug_device_bytes", "tls_debug_perm_table", "tls_power_batch_stats", "tls_debug_transit_stats",
     "tls_power_batch_models", "tls_debug_transit_models",
     "tls_inject_transits", "tls_null_rows", "tls_debug_null_words", "tls_medfilt_detrend",
-    "tls_biweight_detrend",
+    "tls_biweight_detrend", "tls_find_peaks", "tls_power_batch_peaks",
     "tls_comm_unique_id", "tls_comm_init", "tls_comm_destroy", "tls_comm_info", "tls_comm_allgather_results", "tls_comm_allgather_device", "tls_comm_fetch_gathered",
     "tls_comm_stage_results", "tls_comm_allgather_staged", "tls_comm_fetch_staged",
     "tls_comm_barrier", "tls_comm_max",
@@ -131,6 +135,38 @@ MODEL_OUTPUTS = ("folded", "model_folded", "lightcurve", "lc_len")
 def _model_outputs(n_c, n, lc_cap):
     return (numpy.empty((n_c, len(FOLDED_FIELDS), n)), numpy.empty((n_c, n)),
             numpy.empty((n_c, len(LIGHTCURVE_FIELDS), int(lc_cap))), numpy.empty(n_c, dtype=numpy.int64))
+
+
+class Peak(ctypes.Structure):
+    """tls_peak: one peak of a periodogram (include/tls_amd.h), 48 bytes."""
+    _fields_ = [("period", ctypes.c_double), ("power", ctypes.c_double), ("chi2", ctypes.c_double),
+                ("depth", ctypes.c_double), ("index", ctypes.c_int64), ("row", ctypes.c_int64)]
+
+
+PEAK_DTYPE = numpy.dtype([("period", "f8"), ("power", "f8"), ("chi2", "f8"), ("depth", "f8"), ("index", "i8"), ("row", "i8")])
+
+
+def peaks_arguments(k, separation, ratios, min_power):
+    """(k, separation, ratios, min_power) as the peak selection takes them, checked as tls_find_peaks checks them: k an
+    integer in [1, PEAKS_MAX_K]; separation finite and in [0, 1); at most PEAKS_MAX_RATIOS ratios, each finite and > 0;
+    min_power not NaN (None: -inf, no threshold).  ValueError otherwise."""
+    if isinstance(k, bool) or not isinstance(k, numbers.Integral) or not 1 <= int(k) <= PEAKS_MAX_K:
+        raise ValueError("peaks: k must be an integer in [1, %d], got %r" % (PEAKS_MAX_K, k))
+    try:
+        sep = float(separation)
+        rat = numpy.array([] if ratios is None else ratios, dtype=numpy.float64).reshape(-1)
+        low = -numpy.inf if min_power is None else float(min_power)
+    except (TypeError, ValueError):
+        raise ValueError("peaks: separation, ratios and min_power must be numbers")
+    if not (numpy.isfinite(sep) and 0.0 <= sep < 1.0):
+        raise ValueError("peaks: the separation must be finite and in [0, 1), got %r" % (separation,))
+    if len(rat) > PEAKS_MAX_RATIOS:
+        raise ValueError("peaks: at most %d ratios, got %d" % (PEAKS_MAX_RATIOS, len(rat)))
+    if not numpy.all(numpy.isfinite(rat) & (rat > 0.0)):
+        raise ValueError("peaks: every ratio must be finite and > 0")
+    if numpy.isnan(low):
+        raise ValueError("peaks: min_power is NaN")
+    return int(k), sep, numpy.ascontiguousarray(rat), low
 
 
 INJECTION_FIELDS = ("tp", "period", "rp", "a", "sin_inc", "omega")
@@ -271,6 +307,11 @@ def load():
     lib.tls_biweight_detrend.restype = ci
     lib.tls_biweight_detrend.argtypes = [vp, _c_double_p, _c_double_p, i64, i64, ctypes.c_double, ctypes.c_double,
                                          _c_double_p, _c_double_p]
+    peaks = [i64, dbl, _c_double_p, i64, dbl, ctypes.c_void_p, _c_int64_p]
+    lib.tls_find_peaks.restype = ci
+    lib.tls_find_peaks.argtypes = [vp, _c_double_p, _c_double_p, _c_int64_p, _c_double_p, i64, i64, _c_double_p] + peaks
+    lib.tls_power_batch_peaks.restype = ci
+    lib.tls_power_batch_peaks.argtypes = lib.tls_power_batch_stats.argtypes + peaks
     lib.tls_debug_device_bytes.restype = ci
     lib.tls_debug_device_bytes.argtypes = [vp, _c_int64_p, _c_int64_p]
     lib.tls_debug_perm_table.restype = ci
@@ -567,11 +608,17 @@ class Context(object):
         return tuple(r[k] for k in names + (MODEL_OUTPUTS if models is not None else ()))
 
     def _power_batch(self, t, y_batch, dy_batch, periods, table, params, median_kernel, with_arrays=False, with_power=False,
-                     with_spectra=False, statistics=None, per_transit=False, models=None, lc_cap=0):
-        """The three power-batch entries: tls_power_batch; with statistics = (fill_factor, root, max_epochs)
+                     with_spectra=False, statistics=None, per_transit=False, models=None, lc_cap=0, peaks=None):
+        """The power-batch entries: tls_power_batch; with statistics = (fill_factor, root, max_epochs)
         tls_power_batch_stats; with models (a ModelTemplate) as well, tls_power_batch_models.  A dict of the outputs by name:
         summary; chi2, row, depth (with_arrays), power (with_power), SR and power_raw (with_spectra), None where not asked
-        for; with statistics also stats, per_transit and n_epochs (None without per_transit); with models MODEL_OUTPUTS."""
+        for; with statistics also stats, per_transit and n_epochs (None without per_transit); with models MODEL_OUTPUTS.
+        peaks = (k, separation, ratios, min_power) (peaks_arguments): tls_power_batch_peaks, with or without statistics, and
+        peaks (PEAK_DTYPE [n_curves, k]) and n_peaks [n_curves] as well; no entry carries peaks and models (ValueError)."""
+        if peaks is not None and models is not None:
+            raise ValueError("peaks and models cannot be combined: no entry point carries both")
+        if peaks is not None:
+            peaks = peaks_arguments(*peaks)
         t, periods = _f8(t), _f8(periods)
         y_batch = numpy.ascontiguousarray(y_batch, dtype=numpy.float64)
         dy_batch = numpy.ascontiguousarray(dy_batch, dtype=numpy.float64)
@@ -604,6 +651,15 @@ class Context(object):
                 out.update(zip(MODEL_OUTPUTS, model_out))
                 args += models.args(lc_cap, model_out)
                 entry = self._lib.tls_power_batch_models
+        if peaks is not None:
+            if statistics is None:   # (out_stats NULL: no statistics, their inputs are not read)
+                args += [None, 0.0, None, 0, None, 1, None, None]
+            k, sep, ratios, low = peaks
+            out["peaks"] = numpy.zeros((n_c, k), dtype=PEAK_DTYPE)
+            assert PEAK_DTYPE.itemsize == ctypes.sizeof(Peak)
+            out["n_peaks"] = numpy.zeros(n_c, dtype=numpy.int64)
+            args += [k, sep, _dp(ratios), len(ratios), low, out["peaks"].ctypes.data_as(ctypes.c_void_p), _ip(out["n_peaks"])]
+            entry = self._lib.tls_power_batch_peaks
         self._invalidate_results()
         self._check(entry(*args))
         self._n_periods = n_p
@@ -785,6 +841,33 @@ class Context(object):
         if numpy.ndim(y) == 1:
             flat, trend = flat[0], None if trend is None else trend[0]
         return (flat, trend) if return_trend else flat
+
+    def find_peaks(self, power, periods, k, separation=0.02, ratios=(), min_power=None, chi2=None, row=None, depth=None):
+        """The k harmonic-aware peaks of every row of power [n_rows, n_periods] (or one row) over `periods`, selected on the
+        device (tls_find_peaks; the selection: include/tls_amd.h, tests/peaks_spec.py): (peaks (PEAK_DTYPE [n_rows, k]),
+        n_peaks [n_rows]).  chi2, row and depth (each None or shaped like power) fill the fields of their names; a field
+        without a source, and every entry past a row's n_peaks, is NaN or -1."""
+        k, sep, ratios, low = peaks_arguments(k, separation, ratios, min_power)
+        periods = _f8(periods)
+        rows = numpy.ascontiguousarray(numpy.atleast_2d(numpy.asarray(power, dtype=numpy.float64)))
+        if rows.ndim != 2 or periods.ndim != 1 or rows.shape[1] != len(periods) or len(periods) < 1:
+            raise ValueError("power must be [n_periods] or [n_rows, n_periods] over at least one period")
+
+        def like(a, dtype):
+            if a is None:
+                return None
+            a = numpy.ascontiguousarray(numpy.atleast_2d(numpy.asarray(a, dtype=dtype)))
+            if a.shape != rows.shape:
+                raise ValueError("chi2, row and depth must have the shape of power")
+            return a
+        chi2, row, depth = like(chi2, numpy.float64), like(row, numpy.int64), like(depth, numpy.float64)
+        peaks = numpy.zeros((rows.shape[0], k), dtype=PEAK_DTYPE)
+        n_peaks = numpy.zeros(rows.shape[0], dtype=numpy.int64)
+        self._check(self._lib.tls_find_peaks(
+            self._h, _dp(rows), None if chi2 is None else _dp(chi2), None if row is None else _ip(row),
+            None if depth is None else _dp(depth), rows.shape[0], rows.shape[1], _dp(periods), k, sep, _dp(ratios),
+            len(ratios), low, peaks.ctypes.data_as(ctypes.c_void_p), _ip(n_peaks)))
+        return peaks, n_peaks
 
     def debug_null_words(self, n, n_rows, seed, first_trial=0, block=None):
         """The raw Philox words [n_rows, W] tls_null_rows draws for these trials (tls_debug_null_words): white-noise

@@ -248,6 +248,8 @@ struct tls_ctx {
     DevBuf<unsigned long long> d_null_words;     // tls_debug_null_words: the words of one slab
     DevBuf<double> d_detrend;       // tls_medfilt_detrend, tls_biweight_detrend: rows | flat rows | trend rows of one slab
     DevBuf<int> d_windows;          // tls_biweight_detrend: lo [n] | hi [n], the window of every point
+    DevBuf<double> d_peaks;         // tls_find_peaks: periods | records of one slab | power [| chi2 | depth | row] rows of one slab
+    DevBuf<unsigned long long> d_peak_mask;      // ... and tls_power_batch_peaks: a row's alive mask where the LDS does not hold it
     size_t list_stride = 0;
     // two-kernel slab path (series in HBM, one light curve): fold kernel + search kernel per batch of periods
     bool split = false;                      // the plan supports it (enqueue uses it for single-curve launches)
@@ -1103,23 +1105,33 @@ struct PostSearchBufs {
     int64_t max_len = 1;                       // longest template row: the stride of the scaled signals
     double *sde = nullptr, *pick = nullptr, *T0 = nullptr;   // [group][2] | [group][8] | [group], side by side (ONE copy out)
     double* stats = nullptr;                   // tls_power_batch_stats: [group][16] | per-transit [group][6][max_epochs], behind T0
+    double* per_transit = nullptr;             // ... the per-transit rows: behind the records, or behind the peaks where they are not copied out
+    double* peaks = nullptr;                   // tls_power_batch_peaks: [group][1 + 6 k], behind what of the statistics is copied out
     int64_t group = 0;
     int* n_epochs = nullptr;
     tlsdev::T0FitParams* fit = nullptr;
 };
 
-// stats_words: doubles of the statistics stage per curve behind T0 (0: no statistics requested)
+// stats_words: doubles of the statistics stage per curve behind T0 (0: no statistics requested); peaks_words: of the peaks
+// behind the first stats_copied (<= stats_words: the records alone, or the per-transit rows too) of those -- sde | pick | T0 |
+// statistics copied out | peaks are ONE contiguous copy, per-transit rows nobody asked for stay behind it
 int reserve_post_search(tls_ctx* ctx, int64_t group, int64_t n_periods, int64_t n, int64_t max_len, PostSearchBufs& b,
-                        size_t stats_words = 0) {
+                        size_t stats_words = 0, size_t peaks_words = 0, size_t stats_copied = 0) {
     const size_t np = (size_t)n_periods, g = (size_t)group;
     b.max_len = std::max<int64_t>(max_len, 1);
     b.spec_stride = 3 * np;
     b.group = group;
-    TLS_HIP(ctx, ctx->d_spec.reserve(g * b.spec_stride + 2 * g + 8 * g + g + stats_words * g));
+    TLS_HIP(ctx, ctx->d_spec.reserve(g * b.spec_stride + 2 * g + 8 * g + g + stats_words * g + peaks_words * g));
     b.sde = ctx->d_spec.ptr + g * b.spec_stride;
     b.pick = b.sde + 2 * g;
     b.T0 = b.pick + 8 * g;
     b.stats = stats_words ? b.T0 + g : nullptr;
+    b.per_transit = stats_words ? b.stats + (size_t)tlsdev::kTransitStats * g : nullptr;
+    if (peaks_words) {
+        const bool rows_copied = stats_copied == stats_words;
+        b.peaks = b.T0 + g + (rows_copied ? stats_words : (size_t)tlsdev::kTransitStats) * g;
+        if (stats_words && !rows_copied) b.per_transit = b.peaks + peaks_words * g;
+    }
     b.fit_stride = (size_t)n;
     TLS_HIP(ctx, ctx->d_fep.reserve(g * b.fit_stride));
     TLS_HIP(ctx, ctx->d_fres.reserve(g * b.fit_stride));
@@ -1208,7 +1220,7 @@ int enqueue_transit_stats(tls_ctx* ctx, const PostSearchBufs& b, const StatsBufs
     a.periods = ctx->d_periods.ptr; a.n_periods = (int)n_periods;
     a.row_duration = sb.row_duration; a.root = sb.root; a.n_root = (int)sr.n_root;
     a.fill_factor = sr.fill_factor; a.t_min = t_min; a.t_max = t_max;
-    a.stats = b.stats; a.per_transit = b.stats + (size_t)tlsdev::kTransitStats * (size_t)b.group;
+    a.stats = b.stats; a.per_transit = b.per_transit;
     a.ranges = sb.ranges; a.scratch = sb.scratch; a.scratch_stride = (long long)sb.scratch_stride;
     a.n = (int)n; a.max_epochs = (int)sr.max_epochs;
     hipLaunchKernelGGL(tlsdev::tls_transit_stats, dim3((unsigned)gc), dim3(256), 0, ctx->stream, a);
@@ -1300,7 +1312,7 @@ int enqueue_transit_models(tls_ctx* ctx, const PostSearchBufs& b, const StatsBuf
                            double t_min, double t_max) {
     tlsdev::ModelsArgs a;
     a.t = ctx->d_t.ptr; a.y = d_y; a.pick = b.pick; a.T0 = b.T0;
-    a.stats = b.stats; a.per_transit = b.stats + (size_t)tlsdev::kTransitStats * (size_t)b.group; a.max_epochs = (int)sr.max_epochs;
+    a.stats = b.stats; a.per_transit = b.per_transit; a.max_epochs = (int)sr.max_epochs;
     a.row_duration = sb.row_duration;
     a.curve_t = mb.curve; a.curve_f = mb.curve + mr.curve_n; a.curve_n = (int)mr.curve_n;
     a.curve_lo = mr.curve_lo; a.curve_hi = mr.curve_hi;
@@ -1353,6 +1365,70 @@ int read_transit_models(tls_ctx* ctx, const ModelsRequest& mr, const double* h, 
     }
     mr.out_lc_len[curve] = (int64_t)len;
     return TLS_OK;
+}
+
+// ---- the peaks of the detrended power (tls_power_batch_peaks; tls_find_peaks runs the same kernel on the caller's rows)
+struct PeaksRequest {
+    int64_t k = 0; double sep = 0; const double* ratios = nullptr; int64_t n_ratios = 0; double min_power = 0;
+    tls_peak* out = nullptr; int64_t* out_n = nullptr;
+    size_t words() const { return 1 + (size_t)tlsdev::kPeakWords * (size_t)k; }   // n_peaks | k records
+};
+static_assert(sizeof(tls_peak) == tlsdev::kPeakWords * 8, "tls_peak is the kernel's record");
+static_assert(TLS_PEAKS_MAX_K == tlsdev::kPeaksMaxK && TLS_PEAKS_MAX_RATIOS == tlsdev::kPeaksMaxRatios, "the header's limits");
+
+int check_peaks_request(tls_ctx* ctx, const PeaksRequest& pr, int64_t n_periods) {
+    if (pr.k < 1 || pr.k > TLS_PEAKS_MAX_K) return fail(ctx, TLS_E_ARG, "peaks: k out of range [1, 32]");
+    if (!(std::isfinite(pr.sep) && pr.sep >= 0.0 && pr.sep < 1.0)) return fail(ctx, TLS_E_ARG, "peaks: min_separation must be finite and in [0, 1)");
+    if (pr.n_ratios < 0 || pr.n_ratios > TLS_PEAKS_MAX_RATIOS) return fail(ctx, TLS_E_ARG, "peaks: at most 16 ratios");
+    if (pr.n_ratios > 0 && !pr.ratios) return fail(ctx, TLS_E_ARG, "peaks: null ratios");
+    for (int64_t r = 0; r < pr.n_ratios; ++r)
+        if (!(std::isfinite(pr.ratios[r]) && pr.ratios[r] > 0.0)) return fail(ctx, TLS_E_ARG, "peaks: every ratio must be finite and > 0");
+    if (std::isnan(pr.min_power)) return fail(ctx, TLS_E_ARG, "peaks: min_power is NaN");
+    if (n_periods < 1 || n_periods > tlsdev::kPeaksMaxPeriods) return fail(ctx, TLS_E_ARG, "peaks: n_periods out of range [1, 2^30]");
+    return TLS_OK;
+}
+
+// the alive masks of `rows` rows in HBM, where a row's mask does not fit the LDS (tls_peaks.hip.h)
+int reserve_peak_mask(tls_ctx* ctx, int64_t rows, int64_t n_periods) {
+    if (n_periods <= tlsdev::kPeaksLdsPeriods) return TLS_OK;
+    TLS_HIP(ctx, ctx->d_peak_mask.reserve((size_t)rows * (size_t)((n_periods + 63) / 64)));
+    return TLS_OK;
+}
+
+// the peaks of `rows` rows (power at stride power_stride; chi2 / row / depth nullptr or [rows][n_periods]; pick nullptr or the
+// records of tls_power_pick) into d_out [rows][words()], nothing waited for
+int enqueue_find_peaks(tls_ctx* ctx, const PeaksRequest& pr, int64_t rows, int64_t n_periods, const double* d_power,
+                       size_t power_stride, const double* d_periods, const double* d_chi2, const long long* d_row,
+                       const double* d_depth, const double* d_pick, double* d_out) {
+    tlsdev::PeaksArgs a;
+    a.power = d_power; a.power_stride = (long long)power_stride; a.periods = d_periods;
+    a.chi2 = d_chi2; a.row = d_row; a.depth = d_depth; a.pick = d_pick;
+    a.hbm_mask = ctx->d_peak_mask.ptr; a.out = reinterpret_cast<unsigned long long*>(d_out);
+    a.ratios[0] = 1.0;
+    for (int64_t r = 0; r < tlsdev::kPeaksMaxRatios; ++r) a.ratios[r + 1] = r < pr.n_ratios ? pr.ratios[r] : 0.0;
+    a.sep = pr.sep; a.min_power = pr.min_power; a.n_ratios = (int)pr.n_ratios + 1;
+    a.n = (int)n_periods; a.k = (int)pr.k;
+    hipError_t e;
+    if (n_periods <= tlsdev::kPeaksLdsPeriods) {
+        auto kernel = tlsdev::tls_find_peaks<true>;
+        const size_t lds = (size_t)((n_periods + 63) / 64) * 8;
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e == hipSuccess) { hipLaunchKernelGGL(kernel, dim3((unsigned)rows), dim3(1024), lds, ctx->stream, a); e = hipGetLastError(); }
+    } else {
+        hipLaunchKernelGGL(tlsdev::tls_find_peaks<false>, dim3((unsigned)rows), dim3(1024), 0, ctx->stream, a);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) return fail(ctx, TLS_E_HIP, std::string("peaks launch: ") + hipGetErrorString(e));
+    return TLS_OK;
+}
+
+// row c's peaks from a host copy of the kernel's records (`words()` doubles a row) into the caller's arrays
+void read_peaks(const PeaksRequest& pr, const double* h, int64_t c, int64_t curve) {
+    const double* rec = h + pr.words() * (size_t)c;
+    int64_t n_peaks;
+    std::memcpy(&n_peaks, rec, 8);
+    pr.out_n[curve] = n_peaks;
+    std::memcpy(pr.out + (size_t)curve * (size_t)pr.k, rec + 1, (size_t)pr.k * sizeof(tls_peak));
 }
 
 // the summary of curve c from the chain's results on the host (sde | pick | T0 of `group` curves, as reserve_post_search
@@ -1605,7 +1681,7 @@ void tls_ctx_destroy(tls_ctx* ctx) {
     ctx->d_partials.release(); ctx->d_tiles_done.release(); ctx->d_check.release(); ctx->d_spec.release(); ctx->d_queue.release(); ctx->d_squeue.release(); ctx->d_pqueues.release(); ctx->d_phase.release(); ctx->d_lists.release(); ctx->d_perm.release(); ctx->d_perm_table.release(); ctx->d_curve_S0.release(); ctx->d_curve_w0.release();
     ctx->d_ft.release(); ctx->d_fy.release(); ctx->d_fsig.release(); ctx->d_fep.release(); ctx->d_fres.release(); ctx->d_fscratch.release(); ctx->d_frot.release(); ctx->d_frperm.release(); ctx->d_pink.release();
     ctx->d_tstats.release(); ctx->d_tranges.release(); ctx->d_models.release(); ctx->d_inject.release(); ctx->d_inject_count.release();
-    ctx->d_null.release(); ctx->d_null_words.release(); ctx->d_detrend.release(); ctx->d_windows.release();
+    ctx->d_null.release(); ctx->d_null_words.release(); ctx->d_detrend.release(); ctx->d_windows.release(); ctx->d_peaks.release(); ctx->d_peak_mask.release();
     ctx->d_split.release(); ctx->d_park.release(); ctx->d_band.release();
     if (ctx->h_band) (void)hipHostFree(ctx->h_band);
     for (auto& ev : ctx->ev_band) if (ev) (void)hipEventDestroy(ev);
@@ -2829,6 +2905,7 @@ int tls_debug_device_bytes(const tls_ctx* ctx, int64_t* total, int64_t* t0_fit_s
     }
     add(ctx->d_ft); add(ctx->d_fy); add(ctx->d_fsig); add(ctx->d_fep); add(ctx->d_fres); add(ctx->d_fscratch);
     add(ctx->d_pink); add(ctx->d_frot); add(ctx->d_frperm); add(ctx->d_spec); add(ctx->d_tstats); add(ctx->d_tranges); add(ctx->d_models);
+    add(ctx->d_peaks); add(ctx->d_peak_mask);
     add(ctx->d_partials); add(ctx->d_tiles_done);
     add(ctx->d_split); add(ctx->d_park); add(ctx->d_band);
     *total = (int64_t)sum;
@@ -3031,7 +3108,7 @@ static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, cons
                             const double* periods, int64_t n_periods, const tls_template* tmpl, const tls_params* params,
                             int64_t median_kernel, tls_power_summary* out_summary, double* out_chi2, int64_t* out_row,
                             double* out_depth, double* out_power, double* out_SR, double* out_power_raw,
-                            const StatsRequest* sr, const ModelsRequest* mr = nullptr);
+                            const StatsRequest* sr, const ModelsRequest* mr = nullptr, const PeaksRequest* pk = nullptr);
 
 int tls_power_batch(tls_ctx* ctx, const double* t, const double* y, const double* dy, int64_t n, int64_t n_curves,
                     const double* periods, int64_t n_periods, const tls_template* tmpl, const tls_params* params,
@@ -3079,11 +3156,87 @@ int tls_power_batch_models(tls_ctx* ctx, const double* t, const double* y, const
                                            &sr, &mr));
 }
 
+int tls_power_batch_peaks(tls_ctx* ctx, const double* t, const double* y, const double* dy, int64_t n, int64_t n_curves,
+                          const double* periods, int64_t n_periods, const tls_template* tmpl, const tls_params* params,
+                          int64_t median_kernel, tls_power_summary* out_summary, double* out_chi2, int64_t* out_row,
+                          double* out_depth, double* out_power, double* out_SR, double* out_power_raw,
+                          const double* row_duration, double fill_factor, const double* root, int64_t n_root,
+                          tls_transit_stats* out_stats, int64_t max_epochs, double* out_per_transit, int64_t* out_n_epochs,
+                          int64_t k, double min_separation, const double* ratios, int64_t n_ratios, double min_power,
+                          tls_peak* out_peaks, int64_t* out_n_peaks) {
+    if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
+    if (!t || !tmpl) return fail(ctx, TLS_E_ARG, "null argument");
+    PeaksRequest pk;
+    pk.k = k; pk.sep = min_separation; pk.ratios = ratios; pk.n_ratios = n_ratios; pk.min_power = min_power;
+    pk.out = out_peaks; pk.out_n = out_n_peaks;
+    int rc = check_peaks_request(ctx, pk, n_periods);
+    if (rc) return rc;
+    if (n_curves > 0 && (!out_peaks || !out_n_peaks)) return fail(ctx, TLS_E_ARG, "null peaks argument");
+    StatsRequest sr;
+    if (out_stats) {   // (no statistics wanted: their inputs are not read)
+        sr = stats_request(row_duration, tmpl->n_rows, fill_factor, root, n_root, max_epochs, out_stats, out_per_transit, out_n_epochs);
+        if ((rc = check_stats_request(ctx, sr, t, n, tmpl->n_rows))) return rc;
+    }
+    return end_batch(ctx, power_batch_impl(ctx, t, y, dy, n, n_curves, periods, n_periods, tmpl, params, median_kernel,
+                                           out_summary, out_chi2, out_row, out_depth, out_power, out_SR, out_power_raw,
+                                           out_stats ? &sr : nullptr, nullptr, &pk));
+}
+
+int tls_find_peaks(tls_ctx* ctx, const double* power, const double* chi2, const int64_t* row, const double* depth,
+                   int64_t n_rows, int64_t n_periods, const double* periods, int64_t k, double min_separation,
+                   const double* ratios, int64_t n_ratios, double min_power, tls_peak* out_peaks, int64_t* out_n_peaks) {
+    if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
+    if (n_rows < 0) return fail(ctx, TLS_E_ARG, "peaks: n_rows < 0");
+    PeaksRequest pk;
+    pk.k = k; pk.sep = min_separation; pk.ratios = ratios; pk.n_ratios = n_ratios; pk.min_power = min_power;
+    pk.out = out_peaks; pk.out_n = out_n_peaks;
+    int rc = check_peaks_request(ctx, pk, n_periods);
+    if (rc || n_rows == 0) return rc;
+    if (!power || !periods || !out_peaks || !out_n_peaks) return fail(ctx, TLS_E_ARG, "null argument");
+    if ((uint64_t)n_rows > (uint64_t)(SIZE_MAX / 64) / (uint64_t)n_periods) return fail(ctx, TLS_E_ARG, "peaks: rows too large");
+    TLS_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t np = (size_t)n_periods, words = pk.words();
+    const size_t parts = 1 + (chi2 ? 1 : 0) + (row ? 1 : 0) + (depth ? 1 : 0);
+    // rows per launch: at most 256 MB of rows (as the detrending slabs)
+    const int64_t slab = std::max<int64_t>(1, std::min<int64_t>({n_rows, (int64_t)65535, (int64_t)((256u << 20) / (8 * np * parts))}));
+    // periods | records of one slab | power [| chi2 | depth | row] rows of one slab
+    TLS_HIP(ctx, ctx->d_peaks.reserve(np + (size_t)slab * words + parts * (size_t)slab * np));
+    if ((rc = reserve_peak_mask(ctx, slab, n_periods))) return rc;
+    double* d_periods = ctx->d_peaks.ptr;
+    double* d_out = d_periods + np;
+    double* d_power = d_out + (size_t)slab * words;
+    double* d_next = d_power + (size_t)slab * np;
+    double* d_chi2 = nullptr; double* d_depth = nullptr; long long* d_row = nullptr;
+    if (chi2) { d_chi2 = d_next; d_next += (size_t)slab * np; }
+    if (depth) { d_depth = d_next; d_next += (size_t)slab * np; }
+    if (row) d_row = reinterpret_cast<long long*>(d_next);
+    std::vector<double> h((size_t)slab * words);
+    TLS_HIP(ctx, hipMemcpyAsync(d_periods, periods, np * 8, hipMemcpyHostToDevice, ctx->stream));
+    for (int64_t k0 = 0; k0 < n_rows; k0 += slab) {
+        const int64_t rows = std::min<int64_t>(slab, n_rows - k0);
+        const size_t bytes = (size_t)rows * np * 8, at = (size_t)k0 * np;
+        TLS_HIP(ctx, hipMemcpyAsync(d_power, power + at, bytes, hipMemcpyHostToDevice, ctx->stream));
+        if (chi2) TLS_HIP(ctx, hipMemcpyAsync(d_chi2, chi2 + at, bytes, hipMemcpyHostToDevice, ctx->stream));
+        if (depth) TLS_HIP(ctx, hipMemcpyAsync(d_depth, depth + at, bytes, hipMemcpyHostToDevice, ctx->stream));
+        if (row) TLS_HIP(ctx, hipMemcpyAsync(d_row, row + at, bytes, hipMemcpyHostToDevice, ctx->stream));
+        if ((rc = enqueue_find_peaks(ctx, pk, rows, n_periods, d_power, np, d_periods, d_chi2, d_row, d_depth, nullptr, d_out))) {
+            (void)hipStreamSynchronize(ctx->stream);
+            return rc;
+        }
+        ctx->last_kernel = "tls_find_peaks";
+        TLS_HIP(ctx, hipMemcpyAsync(h.data(), d_out, (size_t)rows * words * 8, hipMemcpyDeviceToHost, ctx->stream));
+        // (the next slab overwrites the device rows: the copies above have to be done first)
+        TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        for (int64_t c = 0; c < rows; ++c) read_peaks(pk, h.data(), c, k0 + c);
+    }
+    return TLS_OK;
+}
+
 static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, const double* dy, int64_t n, int64_t n_curves,
                             const double* periods, int64_t n_periods, const tls_template* tmpl, const tls_params* params,
                             int64_t median_kernel, tls_power_summary* out_summary, double* out_chi2, int64_t* out_row,
                             double* out_depth, double* out_power, double* out_SR, double* out_power_raw,
-                            const StatsRequest* sr, const ModelsRequest* mr) {
+                            const StatsRequest* sr, const ModelsRequest* mr, const PeaksRequest* pk) {
     if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
     if (n_curves < 0) return fail(ctx, TLS_E_ARG, "negative number of light curves");
     if (n_curves == 0) return TLS_OK;
@@ -3104,13 +3257,16 @@ static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, cons
     TLS_HIP(ctx, ctx->d_perm.reserve(perm_scratch_words(ctx, nn)));
     int64_t max_len = 1;
     for (int64_t r = 0; r < tmpl->n_rows; ++r) max_len = std::max(max_len, tmpl->length[r]);
+    // (statistics requested: their records -- and the per-transit rows when asked for -- ride in the group's one copy out;
+    // peaks requested: their records lie behind those and ride in it too)
+    const size_t stats_out = !sr ? 0 : sr->out_per_transit ? sr->words() : (size_t)tlsdev::kTransitStats;
+    const size_t peaks_out = pk ? pk->words() : 0;
     PostSearchBufs pb;
-    if ((rc = reserve_post_search(ctx, group, n_periods, n, max_len, pb, sr ? sr->words() : 0))) return rc;
+    if ((rc = reserve_post_search(ctx, group, n_periods, n, max_len, pb, sr ? sr->words() : 0, peaks_out, stats_out))) return rc;
     const size_t spec_stride = pb.spec_stride;
-    // (statistics requested: their records -- and the per-transit rows when asked for -- ride in the group's one copy out)
     StatsBufs sb;
     if (sr && (rc = reserve_transit_stats(ctx, *sr, group, n, sb))) return rc;
-    const size_t stats_out = !sr ? 0 : sr->out_per_transit ? sr->words() : (size_t)tlsdev::kTransitStats;
+    if (pk && (rc = reserve_peak_mask(ctx, group, n_periods))) return rc;
     // (models requested: the folded light curve, the folded model and the padded model light curve of every curve, behind them)
     ModelsBufs mb;
     if (mr && (rc = reserve_transit_models(ctx, *mr, group, n, mb))) return rc;
@@ -3119,19 +3275,20 @@ static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, cons
     // one: the stream runs the groups in order): while the device works on group g the host forms group g + 1 in the other
     // set and enqueues it, THEN waits for g -- the device never waits for the host between two groups (round 6)
     const size_t arrays = (out_chi2 ? 3 : 0) + (out_power ? 1 : 0) + (out_SR ? 1 : 0) + (out_power_raw ? 1 : 0);
-    const size_t out_doubles = (11 + stats_out + models_out) * (size_t)group + arrays * (size_t)group * np;
+    const size_t out_doubles = (11 + stats_out + peaks_out + models_out) * (size_t)group + arrays * (size_t)group * np;
     if ((rc = reserve_batch_staging(ctx, group, nn, out_doubles))) return rc;
     const int64_t n_groups = (n_curves + group - 1) / group;
     ctx->batch_group_ms.assign((size_t)n_groups, 0.0);
     ctx->batch_group_wait_ms.assign((size_t)n_groups, 0.0);
     // host layout of a group's results (the same in both sets)
-    struct OutLayout { double *sde, *pick, *T0, *stats, *chi2, *power, *SR, *praw, *spec3, *models; };
+    struct OutLayout { double *sde, *pick, *T0, *stats, *peaks, *chi2, *power, *SR, *praw, *spec3, *models; };
     auto out_layout = [&](int64_t g) -> OutLayout {
         OutLayout o{};
         double* base = ctx->slot[g & 1].h_out;
         o.sde = base; o.pick = o.sde + 2 * (size_t)group; o.T0 = o.pick + 8 * (size_t)group;
         o.stats = o.T0 + group;                          // statistics records (and rows), on request
-        double* h_next = o.stats + stats_out * (size_t)group;   // chi2 | row | depth | power | SR | power_raw, on request
+        o.peaks = o.stats + stats_out * (size_t)group;   // peak records, on request
+        double* h_next = o.peaks + peaks_out * (size_t)group;   // chi2 | row | depth | power | SR | power_raw, on request
         if (out_chi2) { o.chi2 = h_next; h_next += 3 * (size_t)group * np; }
         if (out_power && out_SR && out_power_raw) { o.spec3 = h_next; h_next += 3 * (size_t)group * np; }
         else {
@@ -3154,11 +3311,14 @@ static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, cons
         rc2 = enqueue_post_search(ctx, pb, gc, sl.d_chi2.ptr, sl.d_row.ptr, sl.d_depth.ptr, sl.d_y.ptr, n, n_periods, median_kernel,
                                   t_min, t_max, params->T0_fit_margin);
         if (rc2) return rc2;
+        // (the peaks read the detrended power and the pick's no-fit flag: nothing of the T0 fit)
+        if (pk && (rc2 = enqueue_find_peaks(ctx, *pk, gc, n_periods, ctx->d_spec.ptr + 2 * np, spec_stride, ctx->d_periods.ptr,
+                                            sl.d_chi2.ptr, sl.d_row.ptr, sl.d_depth.ptr, pb.pick, pb.peaks))) return rc2;
         if (sr && (rc2 = enqueue_transit_stats(ctx, pb, sb, *sr, gc, sl.d_y.ptr, n, n_periods, t_min, t_max))) return rc2;
         if (mr && (rc2 = enqueue_transit_models(ctx, pb, sb, *sr, *mr, mb, gc, sl.d_y.ptr, n, t_min, t_max))) return rc2;
-        // (sde | pick | T0 [| statistics] lie side by side behind the spectra on the device: ONE copy, the host keeps the layout)
+        // (sde | pick | T0 [| statistics] [| peaks] lie side by side behind the spectra on the device: ONE copy, the host keeps the layout)
         const OutLayout o = out_layout(g);
-        TLS_HIP(ctx, hipMemcpyAsync(o.sde, pb.sde, (11 + stats_out) * (size_t)group * 8, hipMemcpyDeviceToHost, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(o.sde, pb.sde, (11 + stats_out + peaks_out) * (size_t)group * 8, hipMemcpyDeviceToHost, ctx->stream));
         if (out_chi2) {
             TLS_HIP(ctx, hipMemcpyAsync(o.chi2, sl.d_chi2.ptr, (size_t)gc * np * 8, hipMemcpyDeviceToHost, ctx->stream));
             TLS_HIP(ctx, hipMemcpyAsync(o.chi2 + (size_t)group * np, sl.d_row.ptr, (size_t)gc * np * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -3199,6 +3359,8 @@ static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, cons
                 const int rc2 = read_transit_models(ctx, *mr, o.models, mb.out_stride, c, c0 + c, n);
                 if (rc2) return rc2;
             }
+        if (pk)
+            for (int64_t c = 0; c < gc; ++c) read_peaks(*pk, o.peaks, c, c0 + c);
         if (out_chi2) {
             std::memcpy(out_chi2 + c0 * n_periods, o.chi2, (size_t)gc * np * 8);
             std::memcpy(out_row + c0 * n_periods, o.chi2 + (size_t)group * np, (size_t)gc * np * 8);

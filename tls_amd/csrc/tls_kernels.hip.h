@@ -4273,4 +4273,7 @@ __global__ void __launch_bounds__(512) tls_transit_models(const ModelsArgs a) {
 // survey-mode biweight detrending (tls_biweight_detrend), on tls_detrend.hip.h's staging and sort
 #include "tls_biweight.hip.h"
 
+// survey-mode periodogram peaks (tls_find_peaks, tls_power_batch_peaks)
+#include "tls_peaks.hip.h"
+
 }  // namespace tlsdev

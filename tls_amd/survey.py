@@ -231,8 +231,13 @@ def _detrend_rows(ctx, t, rows, detrend):
     return ctx.medfilt_detrend(rows, detrend)
 
 
+# the period ratios whose neighbourhoods a taken peak suppresses by default: its first harmonics and sub-harmonics
+HARMONICS = (0.5, 2.0, 1 / 3, 3.0, 2 / 3, 1.5)
+
+
 def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_arrays=False, devices=None, statistics=False,
-                per_transit=False, models=False, detrend=None, **power_kwargs):
+                per_transit=False, models=False, detrend=None, peaks=None, peak_separation=0.02, peak_ratios=HARMONICS,
+                peak_min_power=None, **power_kwargs):
     """Survey-mode power(): for every light curve of `flux_batch` what `transitleastsquares(t, flux).power(**kwargs)`
     reports as SDE, SDE_raw, chi2_min, period, T0, depth and duration (fractional, lc_cache_overview["duration"] of
     the template row at the chi^2 minimum, main.py:199-200) -- search, SDE spectra and final T0 fit all on the
@@ -259,16 +264,88 @@ def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_ar
     beforehand; dy_batch is passed through as it is.  detrend=Biweight(window_length, break_tolerance) searches
     biweight_batch(t, flux_batch, window_length, break_tolerance) the same way.  detrend=None searches flux_batch as given.
 
-    Returns (summary, periods[, chi2, row, depth, power][, per_transit][, models]): summary is a numpy structured array with
-    the fields of tls_power_summary plus "duration" (and the statistics on request)."""
+    peaks=K (1 to 32) also returns the K highest harmonic-aware peaks of every curve's detrended power -- the runners-up of the
+    one pick: a second planet, a binary under its alias -- selected on the device from the spectrum it already holds
+    (tls_power_batch_peaks; 48 K + 8 bytes more per curve, no per-period array comes back), as a dict: `peaks`, a structured
+    array [n_curves, K] with period, power, chi2, depth, index, row (the search's values at the peak's index) and duration
+    (table.duration[row]); `n_peaks` [n_curves].  Entries past a curve's n_peaks are NaN / -1; a curve without a fit has
+    none.  The selection is greedy non-maximum suppression (find_peaks below states it exactly; tests/peaks_spec.py is its
+    numpy restatement): candidates are the local maxima of the power at or above peak_min_power (None: all); the highest
+    one alive is taken (the lowest index among equals, so the first peak is index_power) and every candidate within
+    peak_separation * r * P of r * P leaves, for the taken period P, r = 1 and every r of peak_ratios -- by default
+    HARMONICS, without which ranks 2 to 4 of a strong planet are its own harmonics.  The final T0 fit stays the best
+    pick's: search a narrow period window around a peak for its epoch.  peaks combines with with_arrays, statistics,
+    per_transit, detrend and devices; peaks with models=True raises ValueError (no entry point carries both).  Bad peak
+    arguments raise ValueError before any device work.
+
+    Returns (summary, periods[, chi2, row, depth, power][, per_transit][, models][, peaks]): summary is a numpy structured
+    array with the fields of tls_power_summary plus "duration" (and the statistics on request)."""
     return _power_batch(t, flux_batch, dy_batch, power_kwargs, context=context, device=device, devices=devices,
                         with_arrays=with_arrays, statistics=statistics, per_transit=per_transit, models=models,
-                        detrend=detrend)
+                        detrend=detrend, peaks=_peaks_request(peaks, peak_separation, peak_ratios, peak_min_power, models))
+
+
+def _peaks_request(peaks, separation, ratios, min_power, models=False):
+    """None, or the checked (k, separation, ratios, min_power) of a peaks=K request (ValueError for a bad one)."""
+    if peaks is None:
+        return None
+    from ._lib import peaks_arguments
+    request = peaks_arguments(peaks, separation, ratios, min_power)
+    if models:
+        raise ValueError("peaks cannot be combined with models=True: no entry point carries both")
+    return request
+
+
+def _with_duration(peaks, duration):
+    """The device's peak records plus `duration`: table.duration[row], NaN where the row is -1."""
+    out = numpy.zeros(peaks.shape, dtype=peaks.dtype.descr + [("duration", "f8")])
+    for k in peaks.dtype.names:
+        out[k] = peaks[k]
+    known = peaks["row"] >= 0
+    out["duration"] = numpy.nan
+    if duration is not None:
+        out["duration"][known] = numpy.asarray(duration, dtype=numpy.float64)[peaks["row"][known]]
+    return out
+
+
+def find_peaks(power, periods, k, separation=0.02, ratios=HARMONICS, min_power=None, chi2=None, row=None, depth=None,
+               context=None, device=None):
+    """The k harmonic-aware peaks of a periodogram the caller holds -- power [n_periods] or [n_rows, n_periods] over `periods`
+    (any order) -- selected on the device (tls_find_peaks), the selection power_batch(peaks=k) applies to its own spectra:
+
+        cand[j] = (j == 0 or power[j] > power[j-1]) and (j == n-1 or power[j] >= power[j+1]) and power[j] >= min_power
+        alive = cand; at most k times, while an index is alive:
+            j = lowest index of the largest power among the alive ones (numpy.argmax); take j; P = periods[j]
+            for r in (1.0,) + ratios:  c = r * P;  w = separation * c;  alive[i] = False where fabs(periods[i] - c) <= w
+
+    A NaN fails every comparison: an index holding one, or next to one, is no candidate.  Each of c, w and periods[i] - c is
+    one IEEE double operation, and no arithmetic reaches the output, so the result is bit-equal to the numpy restatement in
+    tests/peaks_spec.py.  k in [1, 32]; separation finite and in [0, 1); at most 16 ratios, each finite and > 0; min_power
+    not NaN (None: no threshold); ValueError otherwise, before any device work.
+
+    Returns (peaks, n_peaks): a structured array with period, power, chi2, depth, index, row ([k] for one row, else
+    [n_rows, k]) and the number of peaks found per row.  chi2, row and depth (each None or shaped like power) fill the
+    fields of their names; a field without a source, and every entry past n_peaks, is NaN or -1."""
+    from ._lib import peaks_arguments
+    k, separation, ratios, min_power = peaks_arguments(k, separation, ratios, min_power)
+    if numpy.ndim(power) not in (1, 2) or numpy.shape(power)[-1] != numpy.size(periods) or numpy.ndim(periods) != 1:
+        raise ValueError("power must be [n_periods] or [n_rows, n_periods], periods [n_periods]")
+    if numpy.size(periods) < 1:
+        raise ValueError("find_peaks needs at least one period")
+    for other in (chi2, row, depth):
+        if other is not None and numpy.shape(other) != numpy.shape(power):
+            raise ValueError("chi2, row and depth must have the shape of power")
+    ctx = context if context is not None else _search.default_context(device)
+    peaks, n_peaks = ctx.find_peaks(power, periods, k, separation, ratios, min_power, chi2=chi2, row=row, depth=depth)
+    if numpy.ndim(power) == 1:
+        return peaks[0], n_peaks[0]
+    return peaks, n_peaks
 
 
 def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=None, devices=None, with_arrays=False,
-                 statistics=False, per_transit=False, models=False, spectra=False, detrend=None):
-    """power_batch; spectra=True (power_results) also returns SR and power_raw [n_curves, n_periods] behind the arrays."""
+                 statistics=False, per_transit=False, models=False, spectra=False, detrend=None, peaks=None):
+    """power_batch; spectra=True (power_results) also returns SR and power_raw [n_curves, n_periods] behind the arrays;
+    peaks: None or a checked request (_peaks_request)."""
     models = bool(models)
     per_transit = bool(per_transit or models)
     statistics = bool(statistics or per_transit)
@@ -283,7 +360,7 @@ def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=Non
     kernel = osf * C.SDE_MEDIAN_KERNEL_SIZE
     if kernel != int(kernel):
         raise ValueError("oversampling_factor * %d must be an integer" % C.SDE_MEDIAN_KERNEL_SIZE)
-    kw = dict(with_arrays=with_arrays, with_power=with_arrays, with_spectra=spectra)
+    kw = dict(with_arrays=with_arrays, with_power=with_arrays, with_spectra=spectra, peaks=peaks)
     if statistics:
         from .stats import calculate_fill_factor
         fill_factor = calculate_fill_factor(inp["t"])
@@ -338,6 +415,8 @@ def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=Non
         m["folded_dy"] = numpy.take_along_axis(dy_rows, numpy.where(no_fit[:, None], 0, order).astype(numpy.int64), axis=1)
         m["folded_dy"][no_fit] = numpy.nan
         result += (m,)
+    if peaks is not None:
+        result += (dict(peaks=_with_duration(out["peaks"], inp["table"].duration), n_peaks=out["n_peaks"]),)
     if spectra:
         result += (out["SR"], out["power_raw"])
     return result
