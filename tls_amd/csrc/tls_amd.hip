@@ -24,42 +24,15 @@
 
 #include "../../include/tls_amd.h"
 #include "tls_kernels.hip.h"
+#include "tls_plan.hip.h"
+
+using namespace tlsplan;
 
 namespace {
 
-// physical constants of the duration window (reference tls_constants.py:20-25,78)
-constexpr double kG = 6.673e-11;
-constexpr double kRsun = 695508000.0;
-constexpr double kRjup = 69911000.0;
-constexpr double kMsun = 1.989 * 1e30;
-constexpr double kSecondsPerDay = 86400.0;
-constexpr double kFracDurationMax = 0.12;
-constexpr double kPi = 3.141592653589793;
-
-constexpr size_t kLdsPerCU = 160 * 1024;
-// The four-slot kernel is taken when at least this many periods fit a CU's LDS.  Three (Tutorial 01: 100 d, 43.8 KB a period)
-// already beat the classic kernel's ONE 1024-thread workgroup per CU by 18 % (1.47 against 1.79 ms, same box); in the narrow
-// band where the classic kernel still fits two workgroups and this one only three, the classic one is 4 % faster (a 42-day
-// probe: 0.371 against 0.386 ms) -- a series length of one day in a hundred, not special-cased.
-#ifndef TLS_SLIM_MIN_SLOTS
-#define TLS_SLIM_MIN_SLOTS 3
-#endif
-constexpr size_t kSlimMinSlots = TLS_SLIM_MIN_SLOTS;
 constexpr size_t kEventRing = 64;   // launch-timing event pairs kept per context
 
 std::string g_create_error;  // tls_last_error(NULL)
-
-// grid.py:9-32 with the reference's operation order (libm pow, as CPython does)
-double t14(double R_s, double M_s, double P, bool small) {
-    P = P * kSecondsPerDay;
-    R_s = kRsun * R_s;
-    M_s = kMsun * M_s;
-    const double chord = std::pow((4 * P) / (kPi * kG * M_s), 1.0 / 3);
-    const double T14max = small ? R_s * chord : (R_s + 2 * kRjup) * chord;
-    double result = T14max / P;
-    if (result > kFracDurationMax) result = kFracDurationMax;
-    return result;
-}
 
 template <typename T>
 struct DevBuf {
@@ -81,17 +54,6 @@ struct View {
     T* ptr = nullptr;
 };
 
-// The switches of a context.  Two are public (tls_options: exact_prefix, slim); the others are developer / test switches
-// that select kernel variants and launch shapes for A/B runs, reached by name through tls_debug_set_switch (never part
-// of the stable ABI).  -1 (band_max, prune_min_live: negative) = the library decides.
-struct Switches {
-    int32_t exact_prefix, slim;
-    int32_t prune, screen32, no_screen, fast_slab, x_staged, split, split_batch, sort2, threads, blocks, plan_threads, t0_rot;
-    int32_t reg_scan;     // four-slot kernel: stored orders stretch-major, phase 2 of a reading launch in registers (0: thread-major rows)
-    int64_t prune_min_live;
-    int64_t perm_table;   // the four-slot kernel's table of folded orders: -1 the library decides, 0 none, k > 0 at most k MiB
-    double band_max;
-};
 struct SwitchName { const char* name; const char* env; size_t offset; int kind; };   // kind 0: int32, 1: int64, 2: double
 #define TLS_SW(field, env, kind) { #field, env, offsetof(Switches, field), kind }
 const SwitchName kSwitchNames[] = {
@@ -218,7 +180,6 @@ struct tls_ctx {
     DevBuf<unsigned short> d_perm_table;     // (grows like every DevBuf and is kept: plans of different period counts alternate on a context)
     size_t perm_table_entries = 0;           // entries of it the held plan uses; 0: the plan has no table
     bool perm_filled = false;                // a launch that stored every row has been enqueued (stream order does the rest)
-    int slim_perm_per = 0;                   // the layout of the plan's stored orders (SearchArgs::perm_per): > 0 stretch-major
     // survey batches: two slots of device + pinned host buffers, a second stream for the transfers
     struct BatchSlot {
         DevBuf<double> d_y, d_w, d_S0, d_w0, d_chi2, d_depth;
@@ -232,7 +193,6 @@ struct tls_ctx {
     const double* over_y = nullptr; const double* over_w = nullptr;
     const double* over_S0 = nullptr; const double* over_w0 = nullptr;
     double* over_chi2 = nullptr; long long* over_row = nullptr; double* over_depth = nullptr;
-    bool sort2 = false;                      // tiled variant: two-level sort
     int batch_curves = 1;                    // light curves the next launch searches (tls_search_batch)
     DevBuf<double> d_ft, d_fy, d_fsig, d_fep, d_fres, d_fscratch;  // final T0 fit
     DevBuf<double> d_pink;          // tls_pink_noise: data | terms | running sums
@@ -250,37 +210,20 @@ struct tls_ctx {
     DevBuf<int> d_windows;          // tls_biweight_detrend: lo [n] | hi [n], the window of every point
     DevBuf<double> d_peaks;         // tls_find_peaks: periods | records of one slab | power [| chi2 | depth | row] rows of one slab
     DevBuf<unsigned long long> d_peak_mask;      // ... and tls_power_batch_peaks: a row's alive mask where the LDS does not hold it
-    size_t list_stride = 0;
-    // two-kernel slab path (series in HBM, one light curve): fold kernel + search kernel per batch of periods
-    bool split = false;                      // the plan supports it (enqueue uses it for single-curve launches)
-    int split_blocks = 0;                    // workgroups of its launches (not capped by the number of periods: tiles are items too)
-    int split_batch = 0;                     // periods per batch: as many slabs are held in HBM
-    int64_t split_max_items = 0;             // most (period, tile, row part) items of any batch
-    bool split_fast = false;                 // the two roles may run fast prefix-sum mode (uniform weights, X at staging, dot products on X)
+    // two-role slab path (series in HBM, one light curve; SearchPlan::split)
     View<unsigned int> d_tile_prefix;        // [n_periods + 1] tiles in front of work item w (queue order)
-    std::vector<unsigned int> host_tile_prefix;
     DevBuf<double> d_partials;               // [split_max_items][3] a tile's winner
     DevBuf<unsigned int> d_tiles_done;       // [split_batch] tiles of the period that are done (zero between launches)
-    int hdr_bytes = 0, tile_len = 0, tile_halo = 0, region_pad = 0, p2_shift = 4;
-    bool prune_kernel = false;        // launch the pruning variant (pruning_pays)
     std::vector<tlsdev::WidthEntry> host_widths;  // kept for tls_update_flux's pruning decision
-    long long prune_min_live = 256;   // live units per period (tile) from which pruning pays; switch prune_min_live overrides
     Switches opt;                     // the context's switches (tls_set_options / tls_debug_set_switch; initially the process's TLS_* environment)
 
     // host-side plan
     bool prepared = false, executed = false;
-    bool uniform_w = true, resident = true;
-    int n = 0, W = 0, M = 0, n_periods = 0, n_widths = 0, nb = 0;
-    int threads = 512, blocks = 0;
+    SearchPlan plan;                 // what tls_prepare decided (plan_search): sizes, launch shapes, the slab's tiles
+    FluxChoice flux;                 // ... and what the flux of the next launch adds (choose_flux_kernels)
     const char* last_kernel = "";    // tls_last_kernel
-    int slim_blocks = 0;              // > 0: the plan fits the four-slots-per-CU kernel (tls_slim_kernel): its workgroups in flight
-    size_t slim_lds = 0;              // ... and its dynamic LDS
-    int slim_threads = 256;           // ... and its workgroup size: 256 (four or three to a CU) or 512 (two to a CU: series of 5-10 k points)
-    int cumsum_round = 2 * tlsdev::kCumsumChunk;
-    size_t lds_bytes = 0;
     double S0 = 0, w0 = 1, depth_min = 0;
     double y_abs_max = 1.0;   // largest |flux| of the light curve(s) of the next launch: bounds the prefix sum (fast mode's eps)
-    bool screen_kernel = false;   // the next launch takes the fp32-screen variant (screen_pays)
     double e_abs_max = INFINITY;   // largest |1 - flux| of the same (inf: a sample outside [0.5, 2]): admits the fp32 screen
     DevBuf<float> d_split;    // fp32 screen: low halves of the folded samples, one region per workgroup
     DevBuf<double> d_park;    // fp32 screen: parked cells, kParkCap per workgroup
@@ -288,7 +231,6 @@ struct tls_ctx {
     double* d_band_now = nullptr;   // the slot the next launch reads
     double* h_band = nullptr; size_t h_band_cap = 0;   // pinned: two slots of (n_widths + 1) doubles
     hipEvent_t ev_band[2] = {nullptr, nullptr}; bool band_used[2] = {false, false}; int band_slot = 0;
-    double flux_sigma = 0.0;  // scatter of the flux of the next launch (mean over the curves of a batch)
     double band_sigma = -1.0, band_eps = -1.0;   // what d_band was computed for
     long long q_count = 0;    // elements of the padded template rows (the fp32 screen's second copy starts there)
     tls_counters plan_counters = {0, 0, 0, 0, 0};
@@ -571,42 +513,6 @@ void build_screens(const std::vector<tlsdev::WidthEntry>& widths, const std::vec
     }
 }
 
-// Expected fraction of trial cells that pass the depth predicate (core.py:58) on a flat, white light curve, averaged
-// over the trial widths: large when the noise of a window mean, sigma/sqrt(d), is large against transit_depth_min.  It
-// says how much of a period is dot products -- what the pruning variant and the fp32 screen save (pick below).
-double passing_fraction(const std::vector<tlsdev::WidthEntry>& widths, double sigma, double depth_min) {
-    if (!(sigma > 0) || widths.empty()) return 0.0;
-    double acc = 0.0;
-    for (const auto& we : widths) acc += 0.5 * std::erfc(depth_min * std::sqrt((double)we.width) / sigma / std::sqrt(2.0));
-    return acc / (double)widths.size();
-}
-// fp32 screen of the dot products (tlsdev::screen_cells) admissible: LDS-resident series, uniform weights, every sample
-// e = 1 - flux the exact sum of two fp32 halves (flux in [0.5, 2] and |e| < 2^-5)
-bool screen_admissible(bool resident, bool uniform, double e_abs_max) {
-    return resident && uniform && e_abs_max < 0.03125;
-}
-// Which variant of the LDS-resident search kernel a launch takes, from the expected passing fraction f of the depth
-// predicate.  Round 4, 90-day configuration, same box, ms (plain / fp32 screen / pruning): 50 ppm (f = 0.09) 1.19 / 1.23 /
-// 1.61; 75 ppm (0.16) 1.67 / 1.62 / 1.87; 100 ppm (0.20) 2.10 / 1.94 / 2.14; 150 ppm (0.28) 2.62 / 2.34 / 2.37; 200 ppm
-// (0.32) 2.94 / 2.54 / 2.47; 300 ppm (0.38) 3.22 / 2.76 / 2.58; 500 ppm (0.42) 3.61 / 2.93 / 2.75.  The
-// screen halves the FMA instructions of the dot products but adds a split pass and a valuation pass per period (DESIGN
-// section 4): it pays where the dot products dominate and the pruning passes do not pay yet.
-// switch prune = 0/1 and ::screen32 = 0/1 force either choice (tests run all three variants).
-constexpr double kScreenFromFraction = 0.13, kPruneFromFraction = 0.24, kPruneFromFractionBesideScreen = 0.30;
-bool pruning_pays(const Switches& opt, const std::vector<tlsdev::WidthEntry>& widths, double sigma, double depth_min, bool resident,
-                  bool screen_ok = false) {
-    if (!resident) return false;   // (the bound's look-ups in X want the series in LDS: no slab instantiation)
-    if (opt.prune >= 0) return opt.prune != 0;
-    if (!(sigma > 0) || widths.empty()) return false;
-    for (const auto& we : widths) if (!we.prunable) return false;
-    if (opt.screen32 >= 0) screen_ok = screen_ok && opt.screen32 != 0;
-    return passing_fraction(widths, sigma, depth_min) >= (screen_ok ? kPruneFromFractionBesideScreen : kPruneFromFraction);
-}
-bool screen_pays(const Switches& opt, const std::vector<tlsdev::WidthEntry>& widths, double sigma, double depth_min, bool admissible) {
-    if (!admissible) return false;
-    if (opt.screen32 >= 0) return opt.screen32 != 0;
-    return passing_fraction(widths, sigma, depth_min) >= kScreenFromFraction;
-}
 
 // scatter of the flux itself: the noise estimate behind pruning_pays (a caller's dy may be in
 // arbitrary units -- validate.py:18 normalises it by its mean -- so it says nothing about the noise)
@@ -619,173 +525,31 @@ double flux_scatter(const double* y, int64_t n) {
 }
 
 // the search kernel variant of the next launch, from the scatter of its flux (a batch: the mean over the curves of its group)
-void choose_flux_kernels(tls_ctx* ctx, bool uniform, double sigma) {
-    ctx->flux_sigma = sigma;
-    const bool scr_ok = screen_admissible(ctx->resident, uniform, ctx->e_abs_max);
-    ctx->prune_kernel = uniform && pruning_pays(ctx->opt, ctx->host_widths, sigma, ctx->depth_min, ctx->resident, scr_ok);
-    ctx->screen_kernel = screen_pays(ctx->opt, ctx->host_widths, sigma, ctx->depth_min, scr_ok);
+void choose_flux_kernels(tls_ctx* ctx, double sigma) {
+    ctx->flux = choose_flux_kernels(ctx->plan, ctx->opt, ctx->host_widths, sigma, ctx->depth_min,
+                                    screen_admissible(ctx->plan.resident, ctx->plan.uniform, ctx->e_abs_max));
 }
 
-// Fast prefix-sum mode: half-width of the band around transit_depth_min inside which the plain scan
-// cannot decide a window -- 1.25 x the bound 2^-53 c_max on |dX/d - mean_reference| (c_max = (n + W) max|flux| bounds the
-// reference's running sum), plus 1e-14 for what the bound leaves out (the plain scan's own rounding, <= ~20 * 2^-53 *
-// max|X| / d, and the reference's division; rounds 3 and early 4 shipped 2 x: twice the second attempts for no safety).
-// (round 4, when a band hit cost a second search of the period -- Kepler full grid, same box: 0.35 -> 244 ms, 0.1 -> 241,
-// 0.01 -> 240, never -> 249.  Round 5: a hit costs one exact prefix pass (band_window in tls_kernels.hip.h) -- every 16th
-// Kepler period: 0 (all exact) 16.97 ms, 0.1 14.22, 1 14.02, 10 14.04, never 14.02; TESS 3.01 / 2.72 / 2.72 / 2.72 / 2.73.)
-constexpr double kBandMax = 1.0;
-constexpr double kBandHitCost = 0.15;   // of a period: the exact prefix pass and the few windows it decides
-double fast_mode_eps(int64_t M, double y_abs_max) {
-    return 1.25 * (1.1102230246251565e-16 * ((double)M * y_abs_max)) + 1e-14;
-}
-// Expected number of windows of width row k inside that band, as a prefix over the width table: n_pos * 2 eps * density of
-// the window mean at depth_min (a flat, white light curve: mean of 1 - flux ~ N(0, sigma^2 / d)).  A period's expectation
-// is pre[k_hi] - pre[k_lo]; above band_max the period starts in exact mode (kernel), and it weighs on the queue order (host).
-// n_pos of a row is (M - width) / xth + 1, the same for every period of the plan.
-void band_prefix_for(const std::vector<tlsdev::WidthEntry>& widths, double sigma, double depth_min, double eps,
-                     std::vector<double>& pre, int64_t M = -1) {
-    pre.assign(widths.size() + 1, 0.0);
-    for (size_t k = 0; k < widths.size(); ++k) {
-        const auto& we = widths[k];
-        const double n_pos = M >= 0 ? (double)((M - we.width) / we.xth + 1) : (double)we.n_pos;
-        const double sd = sigma / std::sqrt((double)we.width), z = depth_min / sd;
-        pre[k + 1] = pre[k] + n_pos * 2.0 * eps * std::exp(-0.5 * z * z) / (sd * 2.5066282746310002);
-    }
-}
 
-// In-range width window of every period (core.py:143-156) and its trial-cell count.
-// The same for every period of a grid (what tls_prepare and tls_grid_cells need): the in-range rows [k_lo, k_hi)
-// of the ascending width table by binary search, the dense rows [k_lo, k_x), and the trial-cell count from a
-// prefix sum over the table -- per period two pow() calls (t14, kept in the reference's operation order) and a few
-// dozen instructions instead of a walk over all widths.  Long grids are cut into slices for a few host threads
-// (a Kepler-size grid of 182 388 periods: 21 ms on one core).  Returns false on a non-positive or non-finite period.
-struct GridPlan {
-    int64_t cells = 0, pairs = 0;
-};
-bool plan_periods(const std::vector<tlsdev::WidthEntry>& widths, const tls_params* params, const double* periods,
-                  int64_t n_periods, double length, int64_t n, int64_t M, tlsdev::PeriodRows* prow, int64_t* cost,
-                  GridPlan* total, int plan_threads = -1) {
-    const int nw = (int)widths.size();
-    std::vector<int> wd((size_t)nw);
-    std::vector<int64_t> prefix((size_t)nw + 1, 0);
-    int first_strided = nw;   // xth = int(width * margin) never decreases with the width (core.py:50-55)
-    for (int k = 0; k < nw; ++k) {
-        wd[(size_t)k] = widths[(size_t)k].width;
-        prefix[(size_t)k + 1] = prefix[(size_t)k] + ((M - widths[(size_t)k].width) / widths[(size_t)k].xth + 1);
-        if (widths[(size_t)k].xth != 1 && first_strided == nw) first_strided = k;
-    }
-    for (int k = first_strided; k < nw; ++k)
-        if (widths[(size_t)k].xth == 1) first_strided = -1;   // not monotone (cannot happen): per-row walk below
-    auto slice = [&](int64_t p0, int64_t p1, GridPlan* out, bool* ok) {
-        GridPlan g;
-        for (int64_t p = p0; p < p1; ++p) {
-            const double P = periods[p];
-            if (!(P > 0) || !std::isfinite(P)) { *ok = false; return; }
-            const double duration_max = t14(params->R_star_max, params->M_star_max, P, false);
-            const double duration_min = t14(params->R_star_min, params->M_star_min, P, true);
-            const double naive = length / P;
-            const double correction = (naive + 1) / naive;
-            const double lo = std::floor(duration_min * (double)n);
-            const double hi = std::ceil(duration_max * (double)n * correction);
-            const int dlo = (int)std::max(-2.0e9, std::min(2.0e9, lo));
-            const int dhi = (int)std::max(-2.0e9, std::min(2.0e9, hi));
-            const int k_lo = (int)(std::lower_bound(wd.begin(), wd.end(), dlo) - wd.begin());
-            const int k_hi = std::max(k_lo, (int)(std::upper_bound(wd.begin(), wd.end(), dhi) - wd.begin()));
-            int k_x = std::min(k_hi, std::max(k_lo, first_strided));
-            if (first_strided < 0) {
-                k_x = k_lo;
-                for (int k = k_lo; k < k_hi; ++k) if (widths[(size_t)k].xth == 1) k_x = k + 1;
-            }
-            const int64_t c = prefix[(size_t)k_hi] - prefix[(size_t)k_lo];
-            if (prow) { prow[p].k_lo = k_lo; prow[p].k_hi = k_hi; prow[p].k_x = k_x; prow[p].pad = 0; }
-            if (cost) cost[p] = c;
-            g.cells += c; g.pairs += k_hi - k_lo;
-        }
-        *out = g;
-    };
-    unsigned n_threads = 1;
-    if (n_periods >= 4096) {
-        n_threads = std::min<unsigned>(std::max(1u, std::thread::hardware_concurrency()), 8u);
-        n_threads = (unsigned)std::min<int64_t>(n_threads, n_periods / 2048);
-        if (plan_threads > 0) n_threads = (unsigned)std::max(1, std::min(64, plan_threads));
-    }
-    std::vector<GridPlan> part(n_threads);
-    std::vector<char> ok(n_threads, 1);
-    if (n_threads <= 1) {
-        bool good = true;
-        slice(0, n_periods, &part[0], &good);
-        ok[0] = good;
-    } else {
-        std::vector<std::thread> pool;
-        std::vector<bool*> flags;
-        std::unique_ptr<bool[]> good(new bool[n_threads]);
-        for (unsigned i = 0; i < n_threads; ++i) {
-            good[i] = true;
-            const int64_t p0 = n_periods * i / n_threads, p1 = n_periods * (i + 1) / n_threads;
-            pool.emplace_back(slice, p0, p1, &part[i], &good[i]);
-        }
-        for (auto& th : pool) th.join();
-        for (unsigned i = 0; i < n_threads; ++i) ok[i] = good[i];
-    }
-    for (unsigned i = 0; i < n_threads; ++i) {
-        if (!ok[i]) return false;
-        total->cells += part[i].cells; total->pairs += part[i].pairs;
-    }
-    return true;
-}
 
-// sort buckets of the general fold_and_sort for a series of n points (the resident kernel uses n; the slab variant
-// what its LDS holds): only the order of magnitude matters to the caller
-int64_t ctx_nb_for(int64_t n, size_t n_widths) {
-    const size_t hdr = ((size_t)tlsdev::kFixedHeader + 4 * (3 * n_widths + 2) + 15) / 16 * 16;
-    return std::min<int64_t>(n, (int64_t)((kLdsPerCU - hdr) / 4));
-}
 
 // words of d_perm: a stashed order per workgroup in flight (n entries of the classic family's index type; a row of the
 // four-slot kernel in the plan's layout, tlsdev::slim_perm_row 16-bit entries)
 size_t perm_scratch_words(const tls_ctx* ctx, size_t n) {
     size_t per_block = n;
-    if (ctx->slim_blocks > 0) per_block = std::max(per_block, (size_t)tlsdev::slim_perm_row(ctx->slim_threads) / 2);
-    return (size_t)std::max(ctx->blocks, ctx->slim_blocks) * per_block;
+    if (ctx->plan.slim_blocks > 0) per_block = std::max(per_block, (size_t)tlsdev::slim_perm_row(ctx->plan.slim_threads) / 2);
+    return (size_t)std::max(ctx->plan.blocks, ctx->plan.slim_blocks) * per_block;
 }
 
-// the table of folded orders of a four-slot plan is held up to this size (switch perm_table: another cap, or none)
-constexpr size_t kPermTableMaxBytes = (size_t)1 << 30;
-
-// work order of the period queue: most expensive first (longest-processing-time first), ties in grid order --
-// a stable LSD radix sort of the 32-bit key (max cost - cost), three passes of 11 bits
-void order_by_cost(const std::vector<int64_t>& cost, std::vector<int>& order) {
-    const size_t np = cost.size();
-    order.resize(np);
-    int64_t cmax = 0;
-    for (size_t p = 0; p < np; ++p) cmax = std::max(cmax, cost[p]);
-    if (cmax >= (1LL << 33)) {   // (absurdly long series: comparison sort)
-        std::iota(order.begin(), order.end(), 0);
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return cost[(size_t)a] > cost[(size_t)b]; });
-        return;
-    }
-    std::vector<unsigned long long> key(np), tmp(np);
-    for (size_t p = 0; p < np; ++p) key[p] = ((unsigned long long)(cmax - cost[p]) << 31) | (unsigned long long)p;   // p < 2^31
-    for (int pass = 0; pass < 3; ++pass) {
-        const int shift = 31 + 11 * pass;
-        if (pass > 0 && (cmax >> (11 * pass)) == 0) break;
-        size_t hist[2049] = {0};
-        for (size_t p = 0; p < np; ++p) ++hist[((key[p] >> shift) & 2047u) + 1];
-        for (int b = 0; b < 2048; ++b) hist[b + 1] += hist[b];
-        for (size_t p = 0; p < np; ++p) tmp[hist[(key[p] >> shift) & 2047u]++] = key[p];
-        key.swap(tmp);
-    }
-    for (size_t p = 0; p < np; ++p) order[p] = (int)(key[p] & 0x7fffffffull);
-}
 
 // the two-role kernel of the slab path (fold role, then search role over (period, tile) items)
 template <bool UNI, bool COUNTING = false>
 hipError_t launch_split(tls_ctx* ctx, const tlsdev::SearchArgs& args, int blocks) {
     auto kernel = tlsdev::tls_fold_search_kernel<UNI, COUNTING>;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->lds_bytes);
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->plan.lds_bytes);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3((unsigned)ctx->threads), ctx->lds_bytes,
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3((unsigned)ctx->plan.threads), ctx->plan.lds_bytes,
                        ctx->stream, args);
     return hipGetLastError();
 }
@@ -794,9 +558,9 @@ template <bool RES, bool UNI, typename IdxT, bool PRUNING = false, bool COUNTING
 hipError_t launch_variant(tls_ctx* ctx, const tlsdev::SearchArgs& args, int blocks) {
     auto kernel = tlsdev::tls_search_kernel<RES, UNI, IdxT, PRUNING, COUNTING, SCREEN>;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->lds_bytes);
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->plan.lds_bytes);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3((unsigned)ctx->threads), ctx->lds_bytes,
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3((unsigned)ctx->plan.threads), ctx->plan.lds_bytes,
                        ctx->stream, args);
     return hipGetLastError();
 }
@@ -820,11 +584,11 @@ int enqueue(tls_ctx* ctx, bool count_work, bool phase_clock = false, double* deb
         TLS_HIP(ctx, hipMemsetAsync(ctx->d_counters.ptr, 0, 3 * sizeof(unsigned long long), ctx->stream));
     tlsdev::SearchArgs a;
     a.t = ctx->d_t.ptr; a.y = ctx->over_y ? ctx->over_y : ctx->d_y.ptr;
-    a.w = ctx->uniform_w ? nullptr : (ctx->over_w ? ctx->over_w : ctx->d_w.ptr);
+    a.w = ctx->plan.uniform ? nullptr : (ctx->over_w ? ctx->over_w : ctx->d_w.ptr);
     a.periods = ctx->d_periods.ptr; a.order = ctx->d_order.ptr; a.rows = ctx->d_rows.ptr;
-    a.widths = ctx->d_widths.ptr; a.q = ctx->d_q.ptr; a.q2 = ctx->uniform_w ? nullptr : ctx->d_q2.ptr;
-    a.q32 = ctx->uniform_w ? reinterpret_cast<const float*>(ctx->d_q2.ptr) : nullptr;
-    a.g = ((ctx->resident && ctx->slim_blocks == 0) || (!ctx->resident && ctx->opt.x_staged == 2)) ? nullptr : ctx->d_g.ptr;   // (x_staged = 2: A/B switch, X at staging time but the dot products on the re-staged samples)
+    a.widths = ctx->d_widths.ptr; a.q = ctx->d_q.ptr; a.q2 = ctx->plan.uniform ? nullptr : ctx->d_q2.ptr;
+    a.q32 = ctx->plan.uniform ? reinterpret_cast<const float*>(ctx->d_q2.ptr) : nullptr;
+    a.g = ((ctx->plan.resident && ctx->plan.slim_blocks == 0) || (!ctx->plan.resident && ctx->opt.x_staged == 2)) ? nullptr : ctx->d_g.ptr;   // (x_staged = 2: A/B switch, X at staging time but the dot products on the re-staged samples)
     a.split_lo = nullptr; a.park_cells = nullptr; a.e_abs_max = ctx->e_abs_max; a.q32_shifted = ctx->q_count;
     a.screens = ctx->d_screens.ptr;
     a.out_chi2 = ctx->over_chi2 ? ctx->over_chi2 : ctx->d_chi2.ptr;
@@ -838,7 +602,7 @@ int enqueue(tls_ctx* ctx, bool count_work, bool phase_clock = false, double* deb
         a.phase_cycles = ctx->d_phase.ptr;
     }
     a.debug_folded = debug_folded; a.debug_prefix = debug_prefix; a.period_cycles = period_cycles;
-    a.check = nullptr; a.lds_bytes = (long long)ctx->lds_bytes;
+    a.check = nullptr; a.lds_bytes = (long long)ctx->plan.lds_bytes;
 #ifdef TLS_DEBUG_CHECKS
     if (!ctx->d_check.ptr) {
         TLS_HIP(ctx, ctx->d_check.reserve(tlsdev::kChecks));
@@ -848,21 +612,21 @@ int enqueue(tls_ctx* ctx, bool count_work, bool phase_clock = false, double* deb
 #endif
     a.queue = ctx->d_squeue.ptr;
     a.scratch = ctx->d_scratch.ptr;
-    a.scratch_stride = (long long)(ctx->uniform_w ? 2 : 3) * ((ctx->M + 1 + ctx->region_pad + 1) & ~1);   // even regions (kernel: RS)
-    a.region_pad = ctx->region_pad;
-    a.chunk_lists = ctx->d_lists.ptr; a.list_stride = 3 * (long long)ctx->list_stride; a.list_cap = (long long)ctx->list_stride;
-    a.prune_min_live = ctx->prune_min_live; a.p2_shift = ctx->p2_shift; a.hdr_bytes = ctx->hdr_bytes; a.tile_len = ctx->tile_len; a.tile_halo = ctx->tile_halo;
+    a.scratch_stride = (long long)(ctx->plan.uniform ? 2 : 3) * ((ctx->plan.M + 1 + ctx->plan.region_pad + 1) & ~1);   // even regions (kernel: RS)
+    a.region_pad = ctx->plan.region_pad;
+    a.chunk_lists = ctx->d_lists.ptr; a.list_stride = 3 * (long long)ctx->plan.list_stride; a.list_cap = (long long)ctx->plan.list_stride;
+    a.prune_min_live = ctx->plan.prune_min_live; a.p2_shift = ctx->plan.p2_shift; a.hdr_bytes = ctx->plan.hdr_bytes; a.tile_len = ctx->plan.tile_len; a.tile_halo = ctx->plan.tile_halo;
     a.depth_min = ctx->depth_min; a.S0 = ctx->S0; a.w0 = ctx->w0;
-    a.cumsum_round = ctx->cumsum_round;
+    a.cumsum_round = ctx->plan.cumsum_round;
     {
         // the sequential cumsum C of the reference (helpers.py:72) rounds by at most half an ulp of its running value
         // per step, and C <= (n + W) * max|flux|: the two constants below follow from that (tls_kernels.hip.h,
         // depth_pass and window_bound)
-        const double c_max = (double)ctx->M * ctx->y_abs_max;
+        const double c_max = (double)ctx->plan.M * ctx->y_abs_max;
         // (band half-width: 1.25 x the bound 2^-53 c_max on |dX/d - mean_reference|, plus 1e-14 for what the bound leaves out --
         // the plain scan's own rounding, <= ~20 * 2^-53 * max|X| / d, and the reference's division; rounds 3 and early 4
         // shipped 2 x: twice the second attempts for no additional safety)
-        a.eps_fast = fast_mode_eps(ctx->M, ctx->y_abs_max);
+        a.eps_fast = fast_mode_eps(ctx->plan.M, ctx->y_abs_max);
         a.slack_unit = 2.5e-16 * c_max;
         a.exact_prefix = ctx->opt.exact_prefix == 1 ? 1 : 0;
         // Series in the HBM slab, one-workgroup-per-period kernel: fast mode too (switch fast_slab = 0: exact mode).
@@ -876,16 +640,14 @@ int enqueue(tls_ctx* ctx, bool count_work, bool phase_clock = false, double* deb
         a.fast_slab = ctx->opt.fast_slab == 0 ? 0 : 1;
     }
     a.x_at_staging = 0;
-    if (!ctx->resident && a.fast_slab) {
-        bool any_oversize = false;   // (rows evaluated straight from the slab list their cells with the first tile: they need all of X)
-        for (const auto& we : ctx->host_widths) any_oversize = any_oversize || we.oversize != 0;
-        a.x_at_staging = any_oversize ? 0 : 1;
+    if (!ctx->plan.resident && a.fast_slab) {
+        a.x_at_staging = ctx->plan.any_oversize ? 0 : 1;   // (rows evaluated straight from the slab list their cells with the first tile: they need all of X)
         if (ctx->opt.x_staged == 0) a.x_at_staging = 0;
     }
     a.band_prefix = nullptr;
     a.band_max = ctx->opt.band_max >= 0 ? ctx->opt.band_max : kBandMax;
-    if (!ctx->resident && a.fast_slab && ctx->flux_sigma > 0 &&
-        !(ctx->band_sigma == ctx->flux_sigma && ctx->band_eps == a.eps_fast && ctx->d_band_now)) {
+    if (!ctx->plan.resident && a.fast_slab && ctx->flux.sigma > 0 &&
+        !(ctx->band_sigma == ctx->flux.sigma && ctx->band_eps == a.eps_fast && ctx->d_band_now)) {
         // the band expectation of every width row (band_prefix_for), as a prefix over the width table: the kernel forms a
         // period's expectation from its duration window [k_lo, k_hi).  Uploaded from one of two pinned slots, nothing is
         // waited for (a survey changes sigma with every group of light curves: the launch in flight keeps reading its own slot).
@@ -904,27 +666,27 @@ int enqueue(tls_ctx* ctx, bool count_work, bool phase_clock = false, double* deb
         if (ctx->band_used[slot]) TLS_HIP(ctx, hipEventSynchronize(ctx->ev_band[slot]));   // (two uploads ago: long done)
         double* h = ctx->h_band + (size_t)slot * cnt;
         std::vector<double> pre;
-        band_prefix_for(ctx->host_widths, ctx->flux_sigma, ctx->depth_min, a.eps_fast, pre);
+        band_prefix_for(ctx->host_widths, ctx->flux.sigma, ctx->depth_min, a.eps_fast, pre);
         std::memcpy(h, pre.data(), cnt * sizeof(double));
         ctx->d_band_now = ctx->d_band.ptr + (size_t)slot * cnt;
         TLS_HIP(ctx, hipMemcpyAsync(ctx->d_band_now, h, cnt * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
         TLS_HIP(ctx, hipEventRecord(ctx->ev_band[slot], ctx->stream));
         ctx->band_used[slot] = true;
-        ctx->band_sigma = ctx->flux_sigma; ctx->band_eps = a.eps_fast;
+        ctx->band_sigma = ctx->flux.sigma; ctx->band_eps = a.eps_fast;
     }
-    if (!ctx->resident && a.fast_slab && ctx->flux_sigma > 0) a.band_prefix = ctx->d_band_now;
-    a.sort2 = ctx->sort2 ? 1 : 0;
+    if (!ctx->plan.resident && a.fast_slab && ctx->flux.sigma > 0) a.band_prefix = ctx->d_band_now;
+    a.sort2 = ctx->plan.sort2 ? 1 : 0;
     a.n_curves = ctx->batch_curves;
     a.curve_S0 = ctx->over_S0 ? ctx->over_S0 : ctx->d_curve_S0.ptr;
     a.curve_w0 = ctx->over_w0 ? ctx->over_w0 : ctx->d_curve_w0.ptr;
     a.perm_scratch = ctx->d_perm.ptr;
     a.perm_table = nullptr; a.perm_filled = 0; a.perm_per = 0;
-    a.n = ctx->n; a.W = ctx->W; a.M = ctx->M;
-    a.n_periods = ctx->n_periods; a.n_widths = ctx->n_widths; a.nb = ctx->nb;
+    a.n = ctx->plan.n; a.W = ctx->plan.W; a.M = ctx->plan.M;
+    a.n_periods = ctx->plan.n_periods; a.n_widths = ctx->plan.n_widths; a.nb = ctx->plan.nb;
     a.batch_lo = 0; a.batch_n = 0; a.tile_prefix = ctx->d_tile_prefix.ptr;
     a.partials = ctx->d_partials.ptr; a.tiles_done = ctx->d_tiles_done.ptr;
-    a.fold_ready = ctx->d_tiles_done.ptr ? ctx->d_tiles_done.ptr + ctx->split_batch : nullptr;   // (only the two-role plan has them)
-    a.split_fast = ctx->split_fast && a.x_at_staging && a.g != nullptr ? 1 : 0;
+    a.fold_ready = ctx->d_tiles_done.ptr ? ctx->d_tiles_done.ptr + ctx->plan.split_batch : nullptr;   // (only the two-role plan has them)
+    a.split_fast = ctx->plan.split_fast && a.x_at_staging && a.g != nullptr ? 1 : 0;
     hipError_t e;
     std::pair<hipEvent_t, hipEvent_t>* evp = nullptr;
     if ((e = timing_pair(ctx, &evp)) != hipSuccess) return fail(ctx, TLS_E_HIP, std::string("timing events: ") + hipGetErrorString(e));
@@ -932,77 +694,66 @@ int enqueue(tls_ctx* ctx, bool count_work, bool phase_clock = false, double* deb
         --ctx->ev_used;
         return fail(ctx, TLS_E_HIP, std::string("timing events: ") + hipGetErrorString(e));
     }
-    // pruning variant: LDS-resident series, uniform weights, noisy enough that most trial cells pass the depth predicate,
-    // and not while the evaluated cells are being counted (counting means evaluating all of them)
-    const bool prune = ctx->resident && ctx->uniform_w && ctx->prune_kernel && !count_work;
+    const SearchPlan& plan = ctx->plan;
+    const Kernel kernel_pick = pick_kernel(plan, ctx->flux, LaunchFlags{count_work, debug_folded || debug_prefix, ctx->batch_curves});
     // (counting has an instantiation of its own: the plain kernels do not keep the counters)
-#define TLS_LAUNCH_RESIDENT(BLOCKS)                                                                                          \
-    (!ctx->uniform_w ? (count_work ? launch_variant<true, false, unsigned short, false, true>(ctx, a, BLOCKS)                   \
-                                   : launch_variant<true, false, unsigned short, false, false>(ctx, a, BLOCKS))                  \
-     : prune         ? launch_variant<true, true, unsigned short, true, false>(ctx, a, BLOCKS)                                   \
-     : count_work    ? launch_variant<true, true, unsigned short, false, true>(ctx, a, BLOCKS)                                   \
-                     : launch_variant<true, true, unsigned short, false, false>(ctx, a, BLOCKS))
-#define TLS_LAUNCH_SLAB(BLOCKS)                                                                                              \
-    (!ctx->uniform_w ? (count_work ? launch_variant<false, false, unsigned int, false, true>(ctx, a, BLOCKS)                    \
-                                   : launch_variant<false, false, unsigned int, false, false>(ctx, a, BLOCKS))                   \
-     : count_work    ? launch_variant<false, true, unsigned int, false, true>(ctx, a, BLOCKS)                                    \
-                     : launch_variant<false, true, unsigned int, false, false>(ctx, a, BLOCKS))
-#define TLS_LAUNCH_SPLIT(BLOCKS)                                                                                             \
-    (!ctx->uniform_w ? (count_work ? launch_split<false, true>(ctx, a, BLOCKS) : launch_split<false, false>(ctx, a, BLOCKS))    \
-     : count_work    ? launch_split<true, true>(ctx, a, BLOCKS)                                                              \
-                     : launch_split<true, false>(ctx, a, BLOCKS))
-    const bool split = !ctx->resident && ctx->split && ctx->batch_curves == 1;
-    // fp32 screen of the dot products (tlsdev::screen_cells): where the host expects it to pay (screen_pays); counting the
-    // work and the debug entries run the plain variant, whose bits it returns anyway
-    const bool screen = ctx->screen_kernel && screen_admissible(ctx->resident, ctx->uniform_w, ctx->e_abs_max) && !prune &&
-                        !count_work && !debug_folded && !debug_prefix;
-    const char* kernel_name = ctx->resident ? (prune ? "resident+prune" : "resident") : split ? "slab+split" : "slab";
-    if (screen) {
-        kernel_name = "resident+screen32";
-        const size_t region = (size_t)ctx->M + 1 + (size_t)ctx->region_pad;
-        hipError_t er = ctx->d_split.reserve((size_t)ctx->blocks * region);
+    switch (kernel_pick) {
+    case Kernel::ResidentScreen: {
+        const size_t region = (size_t)plan.M + 1 + (size_t)plan.region_pad;
+        hipError_t er = ctx->d_split.reserve((size_t)plan.blocks * region);
         if (er != hipSuccess) { --ctx->ev_used; return fail(ctx, TLS_E_HIP, std::string("fp32 screen scratch: ") + hipGetErrorString(er)); }
         a.split_lo = ctx->d_split.ptr;
-        er = ctx->d_park.reserve((size_t)ctx->blocks * tlsdev::kParkCap * 2);   // (a ParkedCell is two doubles wide)
+        er = ctx->d_park.reserve((size_t)plan.blocks * tlsdev::kParkCap * 2);   // (a ParkedCell is two doubles wide)
         if (er != hipSuccess) { --ctx->ev_used; return fail(ctx, TLS_E_HIP, std::string("fp32 screen scratch: ") + hipGetErrorString(er)); }
         a.park_cells = ctx->d_park.ptr;
-        e = launch_variant<true, true, unsigned short, false, false, true>(ctx, a, ctx->blocks);
-    } else if (ctx->slim_blocks > 0 && ctx->uniform_w && !ctx->prune_kernel &&
-               !(ctx->screen_kernel && screen_admissible(ctx->resident, ctx->uniform_w, ctx->e_abs_max)) && !debug_folded && !debug_prefix) {
-        // (by the plan's choice, not this launch's: a search that counts its work runs the counting instantiation of the kernel
-        // the plain search takes -- the classic family where pruning or the screen is the host's choice -- and returns its bits)
-        // four period slots per CU (tls_slim_kernel.hip.h): plain variant, uniform weights, 256-thread workgroups
-        kernel_name = "slim";
-        a.lds_bytes = (long long)ctx->slim_lds;
+        e = launch_variant<true, true, unsigned short, false, false, true>(ctx, a, plan.blocks);
+        break;
+    }
+    case Kernel::Slim:
+    case Kernel::Slim512: {
+        a.lds_bytes = (long long)plan.slim_lds;
         a.perm_table = ctx->perm_table_entries ? ctx->d_perm_table.ptr : nullptr; a.perm_filled = ctx->perm_filled ? 1 : 0;
-        a.perm_per = ctx->slim_perm_per;
-        const bool wide = ctx->slim_threads == tlsdev::kSlimThreadsWide;
-        auto kernel = wide ? (count_work ? tlsdev::tls_slim_kernel<true, tlsdev::kSlimThreadsWide> : tlsdev::tls_slim_kernel<false, tlsdev::kSlimThreadsWide>)
-                           : (count_work ? tlsdev::tls_slim_kernel<true, tlsdev::kSlimThreads> : tlsdev::tls_slim_kernel<false, tlsdev::kSlimThreads>);
-        if (wide) kernel_name = "slim512";
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->slim_lds);
+        a.perm_per = plan.slim_perm_per;
+        auto kernel = kernel_pick == Kernel::Slim512
+                          ? (count_work ? tlsdev::tls_slim_kernel<true, tlsdev::kSlimThreadsWide> : tlsdev::tls_slim_kernel<false, tlsdev::kSlimThreadsWide>)
+                          : (count_work ? tlsdev::tls_slim_kernel<true, tlsdev::kSlimThreads> : tlsdev::tls_slim_kernel<false, tlsdev::kSlimThreads>);
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.slim_lds);
         if (e == hipSuccess) {
-            hipLaunchKernelGGL(kernel, dim3((unsigned)ctx->slim_blocks), dim3((unsigned)ctx->slim_threads), ctx->slim_lds, ctx->stream, a);
+            hipLaunchKernelGGL(kernel, dim3((unsigned)plan.slim_blocks), dim3((unsigned)plan.slim_threads), plan.slim_lds, ctx->stream, a);
             e = hipGetLastError();
         }
         if (e == hipSuccess && a.perm_table) ctx->perm_filled = true;   // (every period of the plan passes through a launch)
-    } else if (ctx->resident) e = TLS_LAUNCH_RESIDENT(ctx->blocks);
-    else if (!split) e = TLS_LAUNCH_SLAB(ctx->blocks);
-    else {
+        break;
+    }
+    case Kernel::Resident:
+    case Kernel::ResidentPrune:
+        e = !plan.uniform ? (count_work ? launch_variant<true, false, unsigned short, false, true>(ctx, a, plan.blocks)
+                                        : launch_variant<true, false, unsigned short, false, false>(ctx, a, plan.blocks))
+            : kernel_pick == Kernel::ResidentPrune ? launch_variant<true, true, unsigned short, true, false>(ctx, a, plan.blocks)
+            : count_work  ? launch_variant<true, true, unsigned short, false, true>(ctx, a, plan.blocks)
+                          : launch_variant<true, true, unsigned short, false, false>(ctx, a, plan.blocks);
+        break;
+    case Kernel::Slab:
+        e = !plan.uniform ? (count_work ? launch_variant<false, false, unsigned int, false, true>(ctx, a, plan.blocks)
+                                        : launch_variant<false, false, unsigned int, false, false>(ctx, a, plan.blocks))
+            : count_work  ? launch_variant<false, true, unsigned int, false, true>(ctx, a, plan.blocks)
+                          : launch_variant<false, true, unsigned int, false, false>(ctx, a, plan.blocks);
+        break;
+    case Kernel::SlabSplit:
         // series in the HBM slab, one light curve: per batch of periods ONE launch of the two-role kernel -- every
         // workgroup folds periods of the batch until none is left (one slab per period), then searches (period, tile) items
         e = hipSuccess;
-        for (int lo = 0; lo < ctx->n_periods && e == hipSuccess; lo += ctx->split_batch) {
-            a.batch_lo = lo; a.batch_n = std::min(ctx->split_batch, ctx->n_periods - lo);
+        for (int lo = 0; lo < plan.n_periods && e == hipSuccess; lo += plan.split_batch) {
+            a.batch_lo = lo; a.batch_n = std::min(plan.split_batch, plan.n_periods - lo);
             a.queue = ctx->d_squeue.ptr;   // [0..1] the fold role's queue, [2..3] the search role's
-            const int64_t items = (int64_t)ctx->host_tile_prefix[(size_t)(lo + a.batch_n)] - (int64_t)ctx->host_tile_prefix[(size_t)lo];
-            const int blocks = (int)std::min<int64_t>(ctx->split_blocks, std::max<int64_t>(items, 1));
-            e = TLS_LAUNCH_SPLIT(blocks);
+            const int64_t items = (int64_t)plan.tile_prefix[(size_t)(lo + a.batch_n)] - (int64_t)plan.tile_prefix[(size_t)lo];
+            const int blocks = (int)std::min<int64_t>(plan.split_blocks, std::max<int64_t>(items, 1));
+            e = !plan.uniform ? (count_work ? launch_split<false, true>(ctx, a, blocks) : launch_split<false, false>(ctx, a, blocks))
+                : count_work  ? launch_split<true, true>(ctx, a, blocks)
+                              : launch_split<true, false>(ctx, a, blocks);
         }
+        break;
     }
-#undef TLS_LAUNCH_SPLIT
-#undef TLS_LAUNCH_SLAB
-#undef TLS_LAUNCH_RESIDENT
     // (a failure from here on gives the event pair back: tls_kernel_timing must not meet a pair whose second event was
     // never recorded)
     if (e != hipSuccess) { --ctx->ev_used; return fail(ctx, TLS_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e)); }
@@ -1012,8 +763,20 @@ int enqueue(tls_ctx* ctx, bool count_work, bool phase_clock = false, double* deb
     }
     ctx->executed = true;
     ctx->counted = count_work;
-    ctx->last_kernel = kernel_name;
+    ctx->last_kernel = kernel_name(kernel_pick);
     return TLS_OK;
+}
+
+// tls_t0fit_kernel's layout (tls_transit_models shares it): a 272-byte header, then 16 bytes a point where the series fits
+// the LDS and its order 16 bits; else up to 16384 sort buckets, the series in HBM scratch
+struct T0FitShape { bool resident; int nb; size_t lds; };
+T0FitShape t0fit_shape(int64_t n) {
+    const size_t hdr = 272, resident_bytes = hdr + 16 * (size_t)n;
+    T0FitShape s;
+    s.resident = resident_bytes <= kLdsPerCU && n <= 65535;
+    s.nb = s.resident ? (int)n : (int)std::min<int64_t>(n, 16384);
+    s.lds = s.resident ? resident_bytes : hdr + 4 * (size_t)s.nb;
+    return s;
 }
 
 // T0-fit launch shared by tls_t0_fit and tls_power_batch: every pointer on the device, nothing waited for.
@@ -1035,21 +798,20 @@ int launch_t0_fit(tls_ctx* ctx, const double* d_t, const double* d_y, const doub
     a.params = d_params; a.y_stride = y_stride; a.signal_stride = signal_stride; a.epoch_stride = epoch_stride;
     a.n_fits = d_params ? (int)n_fits : 1;
     a.mode = 0; a.rot = nullptr; a.rot_perm = nullptr; a.rot_stride = 0; a.t_lo = t_lo; a.t_hi = t_hi;
-    const size_t hdr = 272;
-    const size_t resident_bytes = hdr + 16 * (size_t)n;
-    const bool resident = resident_bytes <= kLdsPerCU && n <= 65535;
-    size_t lds; int threads, blocks;
+    const T0FitShape shape = t0fit_shape(n);
+    const bool resident = shape.resident;
+    const size_t lds = shape.lds;
+    a.nb = shape.nb;
+    int threads, blocks;
     // (a batched launch does not know its fits' epoch counts on the host: every fit gets the full set of workgroups, those
     // beyond its epochs pass it over)
     const int64_t epochs_cap = d_params ? n : n_epochs;
     if (resident) {
-        a.nb = (int)n; lds = resident_bytes;
-        const size_t per_cu = kLdsPerCU / resident_bytes;
+        const size_t per_cu = kLdsPerCU / lds;
         threads = per_cu >= 2 ? 512 : 1024;
         const size_t wg_per_cu = std::min<size_t>(per_cu, 2048 / (size_t)threads);
         blocks = (int)std::min<int64_t>(epochs_cap, (int64_t)wg_per_cu * ctx->n_cu);
     } else {
-        a.nb = (int)std::min<int64_t>(n, 16384); lds = hdr + 4 * (size_t)a.nb;
         threads = 512; blocks = (int)std::min<int64_t>(epochs_cap, (int64_t)2 * ctx->n_cu);
         a.scratch_stride = 3 * n;
         TLS_HIP(ctx, ctx->d_fscratch.reserve((size_t)std::max<int64_t>(blocks, n_fits) * (size_t)a.scratch_stride));
@@ -1169,7 +931,7 @@ int enqueue_post_search(tls_ctx* ctx, const PostSearchBufs& b, int64_t gc, const
     // (WITHOUT a host round trip, round 6: trial epochs, the depth-scaled template and the fit's parameters are formed on the
     // device from the pick, all fits run in ONE set of launches, the first minimum is taken on the device)
     tlsdev::PrepArgs pr;
-    pr.pick = b.pick; pr.widths = ctx->d_widths.ptr; pr.n_widths = ctx->n_widths; pr.q = ctx->d_q.ptr;
+    pr.pick = b.pick; pr.widths = ctx->d_widths.ptr; pr.n_widths = ctx->plan.n_widths; pr.q = ctx->d_q.ptr;
     pr.signal = ctx->d_fsig.ptr; pr.signal_stride = (long long)b.max_len; pr.epochs = ctx->d_fep.ptr; pr.epoch_stride = (long long)b.fit_stride;
     pr.params = b.fit; pr.n_epochs = b.n_epochs; pr.t_min = t_min; pr.margin = margin; pr.n = (int)n;
     hipLaunchKernelGGL(tlsdev::tls_power_prep, dim3((unsigned)gc), dim3(256), 0, ctx->stream, pr);
@@ -1292,10 +1054,8 @@ int check_models_request(tls_ctx* ctx, const ModelsRequest& mr, int64_t n) {
 
 // the template curve (uploaded once per call), the O(group x n) scratch and results of one group, and the launch shape
 int reserve_transit_models(tls_ctx* ctx, const ModelsRequest& mr, int64_t group, int64_t n, ModelsBufs& mb) {
-    const size_t hdr = 272, resident_bytes = hdr + 16 * (size_t)n;   // (tls_t0fit_kernel's layout)
-    mb.resident = resident_bytes <= kLdsPerCU && n <= 65535;
-    mb.nb = mb.resident ? (int)n : (int)std::min<int64_t>(n, 16384);
-    mb.lds = mb.resident ? resident_bytes : hdr + 4 * (size_t)mb.nb;
+    const T0FitShape shape = t0fit_shape(n);
+    mb.resident = shape.resident; mb.nb = shape.nb; mb.lds = shape.lds;
     mb.scratch_stride = (mb.resident ? 0 : 3 * (size_t)n) + 2 * (size_t)tlsdev::kModelsOversample * (size_t)n;
     mb.out_stride = mr.stride(n);
     const size_t g = (size_t)group, curve = 2 * (size_t)mr.curve_n;
@@ -1455,7 +1215,7 @@ using BatchSlot = tls_ctx::BatchSlot;
 
 // the events and the pinned staging of both slots: a group's flux in (stage_group's layout), `out_doubles` of results out
 int reserve_batch_staging(tls_ctx* ctx, int64_t group, size_t nn, size_t out_doubles) {
-    const size_t in_doubles = (size_t)group * nn * (ctx->uniform_w ? 1 : 2) + 2 * (size_t)group;
+    const size_t in_doubles = (size_t)group * nn * (ctx->plan.uniform ? 1 : 2) + 2 * (size_t)group;
     auto grow = [ctx](double*& buf, size_t& cap, size_t doubles) -> int {
         if (cap >= doubles) return TLS_OK;
         if (buf) TLS_HIP(ctx, hipHostFree(buf));
@@ -1477,7 +1237,7 @@ int reserve_batch_staging(tls_ctx* ctx, int64_t group, size_t nn, size_t out_dou
 int reserve_batch_slot(tls_ctx* ctx, BatchSlot& sl, int64_t group, size_t nn, size_t np) {
     const size_t g = (size_t)group;
     TLS_HIP(ctx, sl.d_y.reserve(g * nn));
-    if (!ctx->uniform_w) TLS_HIP(ctx, sl.d_w.reserve(g * nn));
+    if (!ctx->plan.uniform) TLS_HIP(ctx, sl.d_w.reserve(g * nn));
     TLS_HIP(ctx, sl.d_S0.reserve(g));
     TLS_HIP(ctx, sl.d_w0.reserve(g));
     TLS_HIP(ctx, sl.d_chi2.reserve(g * np));
@@ -1497,7 +1257,7 @@ struct GroupState {
 int stage_group(tls_ctx* ctx, BatchSlot& sl, const double* y, const double* dy, int64_t n, int64_t c0, int64_t gc, int64_t group,
                 GroupState& st) {
     const size_t nn = (size_t)n;
-    const bool uni = ctx->uniform_w;
+    const bool uni = ctx->plan.uniform;
     st = GroupState{};
     st.gc = gc;
     st.y = sl.h_in; st.w = sl.h_in + (size_t)group * nn;
@@ -1520,7 +1280,7 @@ int stage_group(tls_ctx* ctx, BatchSlot& sl, const double* y, const double* dy, 
 int upload_group(tls_ctx* ctx, BatchSlot& sl, const GroupState& st, size_t nn, hipStream_t stream) {
     const size_t gc = (size_t)st.gc;
     TLS_HIP(ctx, hipMemcpyAsync(sl.d_y.ptr, st.y, gc * nn * 8, hipMemcpyHostToDevice, stream));
-    if (!ctx->uniform_w) TLS_HIP(ctx, hipMemcpyAsync(sl.d_w.ptr, st.w, gc * nn * 8, hipMemcpyHostToDevice, stream));
+    if (!ctx->plan.uniform) TLS_HIP(ctx, hipMemcpyAsync(sl.d_w.ptr, st.w, gc * nn * 8, hipMemcpyHostToDevice, stream));
     TLS_HIP(ctx, hipMemcpyAsync(sl.d_S0.ptr, st.S0, gc * 8, hipMemcpyHostToDevice, stream));
     TLS_HIP(ctx, hipMemcpyAsync(sl.d_w0.ptr, st.w0, gc * 8, hipMemcpyHostToDevice, stream));
     return TLS_OK;
@@ -1537,10 +1297,10 @@ void unbind_batch_slot(tls_ctx* ctx) {
 // the context points at the slot for this call only, whichever way it returns
 int search_group(tls_ctx* ctx, BatchSlot& sl, const GroupState& st) {
     ctx->S0 = st.S0[0]; ctx->w0 = st.w0[0]; ctx->y_abs_max = st.y_max; ctx->e_abs_max = st.e_max;
-    choose_flux_kernels(ctx, ctx->uniform_w, st.sigma_sum / (double)st.gc);
+    choose_flux_kernels(ctx, st.sigma_sum / (double)st.gc);
     struct Unbind { tls_ctx* ctx; ~Unbind() { unbind_batch_slot(ctx); } } unbind{ctx};
     ctx->batch_curves = (int)st.gc;
-    ctx->over_y = sl.d_y.ptr; ctx->over_w = ctx->uniform_w ? nullptr : sl.d_w.ptr; ctx->over_S0 = sl.d_S0.ptr; ctx->over_w0 = sl.d_w0.ptr;
+    ctx->over_y = sl.d_y.ptr; ctx->over_w = ctx->plan.uniform ? nullptr : sl.d_w.ptr; ctx->over_S0 = sl.d_S0.ptr; ctx->over_w0 = sl.d_w0.ptr;
     ctx->over_chi2 = sl.d_chi2.ptr; ctx->over_row = sl.d_row.ptr; ctx->over_depth = sl.d_depth.ptr;
     return enqueue(ctx, false);
 }
@@ -1701,6 +1461,123 @@ void tls_ctx_destroy(tls_ctx* ctx) {
     delete ctx;
 }
 
+namespace {
+// the device buffers the launches of ctx->plan need beside the plan arrays, and the results
+int reserve_plan_buffers(tls_ctx* ctx) {
+    const SearchPlan& plan = ctx->plan;
+    if (plan.split) {
+        TLS_HIP(ctx, ctx->d_partials.reserve(3 * (size_t)plan.split_max_items + 3));
+        // [split_batch] tiles done | [split_batch] fold ready: all zero between launches (the kernel resets them)
+        if (ctx->d_tiles_done.cap < 2 * (size_t)plan.split_batch) {
+            TLS_HIP(ctx, ctx->d_tiles_done.reserve(2 * (size_t)plan.split_batch));
+            TLS_HIP(ctx, hipMemsetAsync(ctx->d_tiles_done.ptr, 0, ctx->d_tiles_done.cap * sizeof(unsigned int), ctx->stream));
+        }
+    }
+    if (!plan.resident) TLS_HIP(ctx, ctx->d_scratch.reserve(plan.scratch_doubles));
+    // three arrays per workgroup: the live units, (pruning) the bound of each, and the units the bound keeps
+    TLS_HIP(ctx, ctx->d_lists.reserve((size_t)std::max(std::max(plan.blocks, plan.slim_blocks), plan.split ? plan.split_blocks : 0) * 3 * plan.list_stride));
+    if (plan.slim_blocks > 0) TLS_HIP(ctx, ctx->d_perm.reserve(perm_scratch_words(ctx, (size_t)plan.n)));   // (band resolution stashes the order of a period)
+    // the table of folded orders of a four-slot plan, within its budget; a plan without one sorts in every launch
+    size_t want = plan.perm_table_want;
+    if (want > ctx->d_perm_table.cap && ctx->d_perm_table.reserve(want) != hipSuccess) {
+        (void)hipGetLastError();   // (no room on the device: not an error)
+        ctx->d_perm_table.release();
+        want = 0;
+    }
+    ctx->perm_table_entries = want;
+    // results [chi2 | row | depth | counters[4]]
+    const size_t np = (size_t)plan.n_periods;
+    TLS_HIP(ctx, ctx->d_out.reserve(3 * np + 4));
+    ctx->d_chi2.ptr = ctx->d_out.ptr; ctx->d_row.ptr = reinterpret_cast<long long*>(ctx->d_out.ptr + np);
+    ctx->d_depth.ptr = ctx->d_out.ptr + 2 * np;
+    ctx->d_counters.ptr = reinterpret_cast<unsigned long long*>(ctx->d_out.ptr + 3 * np);
+    TLS_HIP(ctx, ctx->d_queue.reserve(1));
+    if (!ctx->d_squeue.ptr) {   // zero once per context: the kernel rewinds its queue itself
+        TLS_HIP(ctx, ctx->d_squeue.reserve(4));   // [0..1] the search (or fold) kernel's queue, [2..3] the split path's search kernel
+        TLS_HIP(ctx, hipMemsetAsync(ctx->d_squeue.ptr, 0, 4 * sizeof(unsigned int), ctx->stream));
+    }
+    return TLS_OK;
+}
+
+// the plan arrays of ctx->plan on the device
+int stage_plan(tls_ctx* ctx, const double* t, const double* y, const std::vector<double>& w, const double* periods,
+               const std::vector<int>& order, const std::vector<tlsdev::PeriodRows>& prow,
+               const std::vector<tlsdev::WidthEntry>& widths, const std::vector<double>& q) {
+    // ONE pinned staging buffer, ONE device allocation, ONE asynchronous copy; nothing is waited for here (the
+    // staging buffer is reused only after its event)
+    std::vector<tlsdev::RowScreen> screens;
+    build_screens(widths, q, screens, ctx->opt.no_screen == 1);
+    const bool uniform = ctx->plan.uniform;
+    PlanLayout& L = ctx->layout;
+    size_t off = 0;
+    auto place = [&](size_t bytes) { const size_t at = off; off = (off + bytes + 255) / 256 * 256; return at; };
+    const size_t nn = (size_t)ctx->plan.n, np = (size_t)ctx->plan.n_periods, nw = widths.size(), nq = q.size();
+    L.t = place(nn * 8); L.y = place(nn * 8); L.w = place(uniform ? 0 : nn * 8);
+    L.periods = place(np * 8); L.order = place(np * sizeof(int)); L.rows = place(np * sizeof(tlsdev::PeriodRows));
+    L.widths = place(nw * sizeof(tlsdev::WidthEntry)); L.screens = place(nw * sizeof(tlsdev::RowScreen));
+    L.q = place(nq * 8); L.q2 = place(nq * 8);   // (uniform weights: the fp32 rows of the screen instead of q^2)
+    const bool with_g = !ctx->plan.resident || ctx->plan.slim_blocks > 0;   // the difference taps: dot products on X (HBM slab; four-slot kernel)
+    L.g = place(with_g ? nq * 8 : 0);
+    const bool with_tiles = !ctx->plan.resident && ctx->plan.split;
+    L.tile_prefix = place(with_tiles ? (np + 1) * sizeof(unsigned int) : 0);
+    L.total = off;
+    int rcs = stage_reserve(ctx, L.total);
+    if (rcs) return rcs;
+    TLS_HIP(ctx, ctx->d_plan.reserve(L.total));
+    unsigned char* h = ctx->h_stage;
+    std::memcpy(h + L.t, t, nn * 8);
+    std::memcpy(h + L.y, y, nn * 8);
+    if (!uniform) std::memcpy(h + L.w, w.data(), nn * 8);
+    if (np) {
+        std::memcpy(h + L.periods, periods, np * 8);
+        std::memcpy(h + L.order, order.data(), np * sizeof(int));
+        std::memcpy(h + L.rows, prow.data(), np * sizeof(tlsdev::PeriodRows));
+    }
+    std::memcpy(h + L.widths, widths.data(), nw * sizeof(tlsdev::WidthEntry));
+    std::memcpy(h + L.screens, screens.data(), nw * sizeof(tlsdev::RowScreen));
+    std::memcpy(h + L.q, q.data(), nq * 8);
+    ctx->q_count = (long long)nq;
+    if (!uniform) {
+        double* q2 = reinterpret_cast<double*>(h + L.q2);
+        for (size_t j = 0; j < nq; ++j) q2[j] = q[j] * q[j];
+    } else {
+        float* q32 = reinterpret_cast<float*>(h + L.q2);   // [nq] the rows | [nq] the rows one element later
+        for (size_t j = 0; j < nq; ++j) { q32[j] = (float)q[j]; q32[nq + j] = j ? (float)q[j - 1] : 0.0f; }
+    }
+    if (with_g) {
+        // Difference taps of every row, same offsets: g_0 = -q_0, g_j = q_{j-1} - q_j, g_L = q_{L-1}.  With e_k =
+        // X_{k+1} - X_k (X the running sum of e) a window's dot product is  sum_j q_j e_{i+j} = sum_{j<=L} g_j X_{i+j}
+        // (summation by parts): the slab variant's fast mode evaluates it on the X a tile already holds in LDS for
+        // the depth predicate, instead of staging the tile's samples a second time (tls_search_body.inc.h, x_dot).
+        double* gt = reinterpret_cast<double*>(h + L.g);
+        std::memset(gt, 0, nq * 8);
+        for (const auto& we : widths) {
+            const double* qr = q.data() + we.q_offset;
+            double* gr = gt + we.q_offset;
+            gr[0] = -qr[0];
+            for (int j = 1; j < we.q_len; ++j) gr[j] = qr[j - 1] - qr[j];
+            gr[we.q_len] = qr[we.q_len - 1];
+        }
+    }
+    if (with_tiles) {
+        std::memcpy(h + L.tile_prefix, ctx->plan.tile_prefix.data(), (np + 1) * sizeof(unsigned int));
+    }
+    unsigned char* d = ctx->d_plan.ptr;
+    ctx->d_tile_prefix.ptr = reinterpret_cast<unsigned int*>(d + L.tile_prefix);
+    ctx->d_t.ptr = reinterpret_cast<double*>(d + L.t); ctx->d_y.ptr = reinterpret_cast<double*>(d + L.y);
+    ctx->d_w.ptr = reinterpret_cast<double*>(d + L.w); ctx->d_periods.ptr = reinterpret_cast<double*>(d + L.periods);
+    ctx->d_order.ptr = reinterpret_cast<int*>(d + L.order); ctx->d_rows.ptr = reinterpret_cast<tlsdev::PeriodRows*>(d + L.rows);
+    ctx->d_widths.ptr = reinterpret_cast<tlsdev::WidthEntry*>(d + L.widths);
+    ctx->d_screens.ptr = reinterpret_cast<tlsdev::RowScreen*>(d + L.screens);
+    ctx->d_q.ptr = reinterpret_cast<double*>(d + L.q); ctx->d_q2.ptr = reinterpret_cast<double*>(d + L.q2);
+    ctx->d_g.ptr = reinterpret_cast<double*>(d + L.g);
+    TLS_HIP(ctx, hipMemcpyAsync(d, h, L.total, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipEventRecord(ctx->ev_stage, ctx->stream));
+    ctx->stage_pending = true;
+    return TLS_OK;
+}
+}  // namespace
+
 int tls_prepare(tls_ctx* ctx, const double* t, const double* y, const double* dy, int64_t n,
                 const double* periods, int64_t n_periods, const tls_template* tmpl, const tls_params* params) {
     if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
@@ -1726,25 +1603,18 @@ int tls_prepare(tls_ctx* ctx, const double* t, const double* y, const double* dy
     std::vector<tlsdev::WidthEntry> widths;
     std::vector<double> q;
     { int rcw = build_widths(ctx, tmpl, params, n, widths, &q); if (rcw) return rcw; }
-    int64_t W = widths.back().width;  // core.py:114-116
-    if (W % 2 != 0) W += 1;
-    const int64_t M = n + W;
+    const int64_t M = n + padded_width(widths);
     if (M + 1 > 0x7fffffff / 4) return fail(ctx, TLS_E_ARG, "series too long");
     if (M < 4 * tlsdev::kR) return fail(ctx, TLS_E_ARG, "series too short (need n + widest width >= 20 samples)");
 
     // per-period duration window (core.py:143-156) and cost
-    double t_min = t[0], t_max = t[0];
-    for (int64_t i = 1; i < n; ++i) { t_min = std::min(t_min, t[i]); t_max = std::max(t_max, t[i]); }
-    std::vector<int> order;
+    double t_min, t_max;
+    time_range(t, n, t_min, t_max);
     std::vector<tlsdev::PeriodRows> prow((size_t)n_periods);
     std::vector<int64_t> cost((size_t)n_periods);
-    tls_counters pc = {0, 0, 0, 0, 0};
-    {
-        GridPlan gp;
-        if (!plan_periods(widths, params, periods, n_periods, t_max - t_min, n, M, prow.data(), cost.data(), &gp, ctx->opt.plan_threads))
-            return fail(ctx, TLS_E_ARG, "periods must be positive and finite");
-        pc.grid_cells = gp.cells; pc.pd_pairs = gp.pairs;
-    }
+    GridPlan gp;
+    if (!plan_periods(widths, params, periods, n_periods, t_max - t_min, n, M, prow.data(), cost.data(), &gp, ctx->opt.plan_threads))
+        return fail(ctx, TLS_E_ARG, "periods must be positive and finite");
     // weights
     std::vector<double> w;
     bool uniform; double w0, S0;
@@ -1753,381 +1623,21 @@ int tls_prepare(tls_ctx* ctx, const double* t, const double* y, const double* dy
     ctx->y_abs_max = y_abs_max; ctx->e_abs_max = e_abs_max;
     const double flux_sigma = flux_scatter(y, n);
 
-    // Work order: most expensive first.  A period commensurate with the cadence of a regularly sampled series piles
-    // the phases onto a few values and its sort costs several ordinary periods: such a period
-    // goes to the head of the queue, where its long run overlaps everything else instead of ending the launch.
-    {
-        std::vector<int64_t> queue_cost(cost);
-        bool regular = n >= 64;
-        double dt = 0.0;
-        if (regular) {
-            dt = (t[n - 1] - t[0]) / (double)(n - 1);
-            regular = dt > 0;
-            for (int64_t i = 1; i < n && regular; ++i) regular = std::fabs((t[i] - t[i - 1]) - dt) <= 1e-3 * dt;
-        }
-        if (regular) {
-            // (the four-slot kernel ranks piles from 9 points on by themselves, 2-3 x an ordinary period: a short series
-            // looks for smaller piles and higher resonances -- flagging too many only reorders the queue)
-            const bool fine_piles = uniform && n <= (int64_t)tlsdev::kSlimThreadsWide * tlsdev::kSlimPer;
-            const int k_max = fine_piles ? 8 : 4;
-            const double a_max = (double)n / (fine_piles ? 9.0 : 48.0);       // `a` distinct phase values: piles of n / a points
-            const double n_buckets = fine_piles ? 0.5 * (double)n : (double)ctx_nb_for(n, widths.size());
-            const double drift = (fine_piles ? 8.0 : 4.0) / ((double)n * n_buckets);   // a pile's phase range, in buckets, over the series
-            const double inv_dt = 1.0 / dt;
-            for (int64_t p = 0; p < n_periods; ++p) {
-                const double r = periods[p] * inv_dt;             // samples per period
-                for (int k = 1; k <= k_max; ++k) {
-                    const double rk = r * k, a = std::floor(rk + 0.5);   // r ~ a / k
-                    if (a > a_max) break;
-                    if (a < 1) continue;
-                    // n |k/a - 1/r| n_buckets < limit  <=>  |r k - a| < limit a r / (n n_buckets)
-                    if (std::fabs(rk - a) < drift * a * r) { queue_cost[(size_t)p] += 50 * cost[(size_t)p]; break; }
-                }
-            }
-        }
-        // Fast prefix-sum mode: a period whose windows are likely to meet the undecided band pays a second attempt
-        // pass (kBandHitCost of itself); among periods of similar cost the likelier ones start first, so that the extra
-        // passes fall into the body of the launch and not into its last round.  (Only the order: which mode a period takes
-        // never depends on it.)  The expectation is band_prefix_for's, as in enqueue; the LDS-resident kernel has no
-        // per-period expectation (every period starts in fast mode): the same weight orders its queue.
-        if (flux_sigma > 0 && ctx->opt.exact_prefix != 1) {
-            std::vector<double> pre;
-            band_prefix_for(widths, flux_sigma, params->transit_depth_min, fast_mode_eps(M, y_abs_max), pre, M);
-            const double band_max = ctx->opt.band_max >= 0 ? ctx->opt.band_max : kBandMax;
-            for (int64_t p = 0; p < n_periods; ++p) {
-                const double lambda = pre[(size_t)prow[(size_t)p].k_hi] - pre[(size_t)prow[(size_t)p].k_lo];
-                if (lambda > band_max) continue;                                   // (starts in exact mode: no second attempt)
-                queue_cost[(size_t)p] += (int64_t)(kBandHitCost * std::min(1.0, lambda) * (double)cost[(size_t)p]);
-            }
-        }
-        order_by_cost(queue_cost, order);
-    }
+    std::vector<int> order;
+    order_queue(t, n, periods, n_periods, widths, prow.data(), cost, uniform, M, flux_sigma, y_abs_max, params->transit_depth_min, ctx->opt, order);
 
-    // launch geometry
-    const size_t regions = uniform ? 2 : 3;
-    int widest_stride = 1;  // of the tiled rows: sizes the pads behind the folded series and the tile halo
-    for (const auto& we : widths) if (we.tiled) widest_stride = std::max(widest_stride, we.xth);
-    ctx->region_pad = tlsdev::region_pad_for(widest_stride);
-    const size_t region_doubles = (size_t)(M + 1 + ctx->region_pad);
-    // LDS header: fixed part + per-row live counters and batch prefix (+ the batch counter)
-    const size_t hdr = ((size_t)tlsdev::kFixedHeader + 4 * (3 * widths.size() + 2) + 15) / 16 * 16;
-    const size_t resident_bytes = hdr + regions * 8 * region_doubles;
-    ctx->hdr_bytes = (int)hdr;
-    ctx->resident = resident_bytes <= kLdsPerCU && n <= 65535;
-    ctx->slim_blocks = 0; ctx->slim_lds = 0;
-    if (ctx->resident) {
-        ctx->nb = (int)n;
-        ctx->tile_len = 0; ctx->tile_halo = 0; ctx->sort2 = false;
-        ctx->lds_bytes = resident_bytes;
-        const size_t per_cu = kLdsPerCU / resident_bytes;
-        ctx->threads = per_cu >= 2 ? 512 : 1024;
-        if (ctx->opt.threads > 0) ctx->threads = std::max(64, std::min(1024, ctx->opt.threads / 64 * 64));   // developer switch
-        const size_t wg_per_cu = std::min<size_t>(per_cu, 2048 / (size_t)ctx->threads);
-        ctx->blocks = (int)std::min<int64_t>(std::max<int64_t>(n_periods, 1), (int64_t)wg_per_cu * ctx->n_cu);
-        if (ctx->opt.blocks > 0) ctx->blocks = std::max(1, std::min(ctx->blocks, ctx->opt.blocks));   // developer switch
-        // Four (at least three) 256-thread workgroups per CU, phase 3 on X alone (tls_slim_kernel.hip.h): uniform weights, and
-        // the period's one region + header within a quarter (a third) of the LDS.  (switch slim = 0: never.)
-        // (auto: only while the library also decides between the classic kernel's variants -- an explicit switch prune
-        // or ::screen32 selects among THOSE; slim = 1 forces this kernel wherever neither pruning nor the screen is taken)
-        // (exact prefix-sum mode throughout is the classic kernel's: this one values its cells on the plain scan, and keeps
-        // the exact prefix sum for the windows the plain scan cannot decide)
-        const bool slim_wanted = ctx->opt.exact_prefix != 1 && (ctx->opt.slim == 1 || (ctx->opt.slim < 0 && ctx->opt.prune < 0 && ctx->opt.screen32 < 0));
-        if (uniform && slim_wanted && ctx->opt.threads <= 0) {
-            const long long need = tlsdev::slim_lds_bytes((int)n, (int)M, ctx->region_pad, (int)widths.size());
-            // (a series beyond 5120 points -- 107-200 d at 30 min, two TESS sectors at 10 min --: the same kernel with 512-thread
-            // workgroups, two to a CU, where the classic kernel runs ONE 1024-thread workgroup per CU; round 6)
-            const long long need_wide = tlsdev::slim_lds_bytes((int)n, (int)M, ctx->region_pad, (int)widths.size(), tlsdev::kSlimThreadsWide);
-            if (need > 0 && kSlimMinSlots * (size_t)need <= kLdsPerCU) {
-                ctx->slim_lds = (size_t)need; ctx->slim_threads = tlsdev::kSlimThreads;
-                ctx->slim_blocks = (int)std::min<int64_t>(std::max<int64_t>(n_periods, 1), (int64_t)std::min<size_t>(4, kLdsPerCU / (size_t)need) * ctx->n_cu);
-                if (ctx->opt.blocks > 0) ctx->slim_blocks = std::max(1, std::min(ctx->slim_blocks, ctx->opt.blocks));
-            } else if (need == 0 && need_wide > 0 && 2 * (size_t)need_wide <= kLdsPerCU) {
-                ctx->slim_lds = (size_t)need_wide; ctx->slim_threads = tlsdev::kSlimThreadsWide;
-                ctx->slim_blocks = (int)std::min<int64_t>(std::max<int64_t>(n_periods, 1), (int64_t)2 * ctx->n_cu);
-                if (ctx->opt.blocks > 0) ctx->slim_blocks = std::max(1, std::min(ctx->slim_blocks, ctx->opt.blocks));
-            }
-        }
-    } else {
-        // the folded series lives in a per-workgroup HBM slab; phase 3 stages it through LDS in
-        // tiles of `tile_len` window-start positions plus a halo of the widest window
-        // sort histogram: one bucket per point while the counters fit the LDS (fewer points per
-        // bucket = fewer comparisons in the in-bucket ranking)
-        // (as fine as the LDS allows: a NEARLY commensurate period spreads its piles over neighbouring buckets, and fine
-        // buckets keep them below the size from which the counting rank is left; what LDS remains behind the counters
-        // stages piled-up buckets for the workgroup sort, fold_and_sort)
-        // One 1024-thread workgroup per CU with all of its LDS (two 512-thread ones with half each were measured in rounds 3
-        // and 4 and lost: more tiles, more halo staged; the switch is gone).
-        const size_t lds_budget = kLdsPerCU;
-        ctx->nb = (int)std::min<int64_t>(n, (int64_t)((lds_budget - hdr) / 4));
-        size_t halo = (size_t)W + (size_t)(tlsdev::kR - 1) * (size_t)std::max(widest_stride, tlsdev::kMaxTiledStride) + 2 * tlsdev::kU + 4;
-        const size_t unit = (size_t)tlsdev::kR * tlsdev::kWave;  // tile bounds: multiples of 320
-        {
-            // Very long series (N beyond ~150 k with the default duration grid): the widest windows are longer
-            // than an LDS tile.  Rows wider than half the tile capacity are marked `oversize`: their (few,
-            // widely strided) trial positions are listed and evaluated straight from the slab, one window per
-            // wavefront, and the tile halo only has to cover the other rows.  The reference has no size
-            // limit (core.py:96-188).
-            const size_t cap1 = (lds_budget - hdr) / 8 / ((uniform ? 1 : 2));
-            if (cap1 < halo + 4 * unit) {
-                const size_t halo_cap = cap1 / 2;
-                size_t widest_fit = 1;
-                int stride_fit = 1;
-                for (auto& we : widths) {
-                    const size_t need = (size_t)we.width + (size_t)(tlsdev::kR - 1) * (size_t)std::max(we.tiled ? we.xth : 1, tlsdev::kMaxTiledStride) + 2 * tlsdev::kU + 4;
-                    if (need > halo_cap) { we.oversize = 1; we.tiled = 0; we.prunable = 0; }
-                    else { widest_fit = std::max(widest_fit, (size_t)we.width); if (we.tiled) stride_fit = std::max(stride_fit, we.xth); }
-                }
-                widest_stride = stride_fit;
-                ctx->region_pad = tlsdev::region_pad_for(widest_stride);
-                halo = widest_fit + (widest_fit & 1) + (size_t)(tlsdev::kR - 1) * (size_t)std::max(widest_stride, tlsdev::kMaxTiledStride) + 2 * tlsdev::kU + 4;
-            }
-        }
-        // staged per tile: e (or e*w), and w for per-point weights.  The prefix sum takes the samples' place for the
-        // predicate pass (or is formed in place from the staged flux: fast mode), the samples follow for the dot products --
-        // two stagings per tile, but fewer and larger tiles than with X staged beside the samples (TESS: 2 instead of 3,
-        // -8 %; Kepler-size: 7 instead of 82, most of a tile is halo; that variant was dropped in round 6).
-        const size_t buffers = uniform ? 1 : 2;
-        if ((lds_budget - hdr) / 8 / buffers < halo + unit) return fail(ctx, TLS_E_ARG, "widest transit window does not fit the LDS tile");
-        const size_t cap_doubles = (lds_budget - hdr) / 8 / buffers;
-        const size_t cap_tile = (cap_doubles - halo) / unit * unit;
-        const size_t n_tiles = ((size_t)M + cap_tile - 1) / cap_tile;
-        size_t tile = (((size_t)M + n_tiles - 1) / n_tiles + unit - 1) / unit * unit;
-        if (tile > cap_tile) tile = cap_tile;
-        ctx->tile_len = (int)tile; ctx->tile_halo = (int)halo;
-        // Per period the halo only has to cover the widest IN-RANGE window (core.py:148-156): long periods try
-        // narrow windows only, so their tiles can be longer (fewer tiles, less of the slab staged twice).  The
-        // LDS tile stays `tile + halo` doubles; PeriodRows::pad carries the period's own tile length.
-        {
-            const size_t staged = tile + halo;
-            // (widths ascend and strides never decrease with them: the widest in-range window and the largest stride
-            // of a period are those of its last in-range row that is not oversize -- one table over k_hi, one look-up
-            // per period instead of a walk over its rows)
-            const size_t nw = widths.size();
-            std::vector<int> tile_for_khi(nw + 1, 0);
-            {
-                size_t wmax = 1; int stride_p = 1;
-                for (size_t k = 0; k < nw; ++k) {
-                    const auto& we = widths[k];
-                    if (!we.oversize) {
-                        wmax = std::max(wmax, (size_t)we.width);
-                        if (we.tiled) stride_p = std::max(stride_p, we.xth);
-                    }
-                    const size_t halo_p = wmax + (wmax & 1) + (size_t)(tlsdev::kR - 1) * (size_t)std::max(stride_p, tlsdev::kMaxTiledStride) + 2 * tlsdev::kU + 4;
-                    if (halo_p >= halo) continue;   // (0: the plan's tile length)
-                    const size_t cap_p = (staged - halo_p) / unit * unit;
-                    const size_t tiles_p = ((size_t)M + cap_p - 1) / cap_p;
-                    size_t tile_p = (((size_t)M + tiles_p - 1) / tiles_p + unit - 1) / unit * unit;
-                    if (tile_p > cap_p) tile_p = cap_p;
-                    if (tile_p > tile) tile_for_khi[k + 1] = (int)tile_p;
-                }
-            }
-            for (int64_t p = 0; p < n_periods; ++p) {
-                tlsdev::PeriodRows& pr = prow[(size_t)p];
-                // (the running maxima above start at row 0, the period's at k_lo: the same whenever the period has a row)
-                pr.pad = pr.k_hi > pr.k_lo ? tile_for_khi[(size_t)pr.k_hi] : 0;
-            }
-        }
-        ctx->cumsum_round = 2 * tlsdev::kCumsumChunk;
-        const size_t cumsum_bytes = 8 * ((size_t)ctx->cumsum_round + 4);
-        ctx->lds_bytes = hdr + std::max<size_t>(std::max<size_t>(4 * (size_t)ctx->nb, cumsum_bytes),
-                                                buffers * 8 * (tile + halo));
-        ctx->threads = 1024;
-        if (ctx->opt.threads > 0) ctx->threads = std::max(64, std::min(1024, ctx->opt.threads / 64 * 64));   // developer switch
-        ctx->blocks = (int)std::min<int64_t>(std::max<int64_t>(n_periods, 1), (int64_t)ctx->n_cu);
-        if (ctx->opt.blocks > 0)   // developer switch: workgroups in flight (memory-system experiments)
-            ctx->blocks = std::max(1, std::min(ctx->blocks, ctx->opt.blocks));
-        // two-level sort with sequential HBM accesses (fold_and_sort_tiled) when its LDS windows fit
-        const size_t sort2_bytes = hdr + (size_t)tlsdev::sort2_lds_bytes((int)n, ctx->threads);
-        ctx->sort2 = sort2_bytes <= lds_budget && ctx->opt.sort2 != 0;
-        if (ctx->sort2) ctx->lds_bytes = std::max(ctx->lds_bytes, sort2_bytes);
-        // Two-role slab kernel: every workgroup folds periods into per-period slabs, then searches
-        // (period, tile) items; the periods go through it in batches that hold one slab per period in HBM (as many periods as
-        // fit `kSplitSlabBytes`, at least four rounds of workgroups; all of them when the grid is small).
-        // WHEN it is used (measured on one MI355X, same box, against the one-workgroup-per-period kernel): it wins where a
-        // GPU holds few periods of a long series -- the shard of a multi-GPU job -- because a period is then searched by
-        // several workgroups (260 periods of N = 70 128: 0.61 vs 0.79 ms); on a full grid the one-kernel path keeps every
-        // CU in a different phase and needs no hand-off (TESS 2.99 vs 3.50 ms, Kepler sample 5.37 vs 5.43 ms; 713 periods of
-        // N = 70 128, 2.8 rounds: 1.37 vs 1.63 ms; 308 periods of the TESS-size series: 0.53 ms both ways).  Hence: up to one
-        // and a half rounds of periods -> two-role kernel.  TLS_SPLIT=0/1 forces the choice (A/B, tests).
-        ctx->split_blocks = ctx->n_cu;
-        if (ctx->opt.blocks > 0) ctx->split_blocks = std::max(1, std::min(ctx->split_blocks, ctx->opt.blocks));
-        {
-            // WHICH launches take it.  The mode of a period never depends on the launch shape (enqueue), so the two roles must
-            // be able to run a period in the mode the one-workgroup kernel gives it: fast mode with X formed at tile-staging
-            // time and the dot products on X (`split_fast`: uniform weights, no row wider than an LDS tile, an even number of
-            // points), or a plan that is exact throughout.  Where that holds, a SHORT launch whose last round of periods would
-            // be partly filled -- the share of a rank of a multi-GPU search, a few hundred periods of a long series -- goes
-            // through the two roles: 3.6 items per workgroup instead of 1.2 periods, and the launch ends within a tile's work
-            // instead of a whole period's.  Measured (round 6, TESS-size series, same box, one-workgroup kernel / two roles):
-            // 307 periods 0.583 / 0.479 ms, 411 periods 0.522 / 0.489; but 256 periods (one full round) 0.567 / 0.623 and 512
-            // 0.484 / 0.509 -- a launch of whole rounds has no partly filled round to repair and pays the hand-off (slabs read
-            // across XCDs, the ready flags) for nothing; a full grid stays with the one-workgroup kernel (every CU in a
-            // different phase).  Hence: up to four rounds, and the last one filled to between 1 and 70 %.
-            // switch split = 0 / 1 forces the choice (A/B, tests).
-            bool any_oversize = false;
-            for (const auto& we : widths) any_oversize = any_oversize || we.oversize != 0;
-            const bool all_exact = ctx->opt.exact_prefix == 1 || ctx->opt.fast_slab == 0;
-            ctx->split_fast = uniform && !any_oversize && (n & 1) == 0 && !all_exact && ctx->opt.x_staged != 0;
-            const int64_t last_round = n_periods % (int64_t)ctx->split_blocks;
-            const bool short_launch = n_periods <= 4 * (int64_t)ctx->split_blocks && last_round > 0 && 10 * last_round <= 7 * (int64_t)ctx->split_blocks;
-            ctx->split = n_periods > 0 && (ctx->opt.split >= 0 ? ctx->opt.split != 0 : (all_exact || ctx->split_fast) && short_launch);
-            const size_t slab_bytes = regions * ((region_doubles + 1) & ~(size_t)1) * 8;
-            constexpr size_t kSplitSlabBytes = (size_t)12 << 30;
-            int64_t batch = std::max<int64_t>((int64_t)(kSplitSlabBytes / slab_bytes), (int64_t)4 * ctx->split_blocks);
-            if (ctx->opt.split_batch > 0) batch = ctx->opt.split_batch;
-            ctx->split_batch = (int)std::min<int64_t>(std::max<int64_t>(n_periods, 1), batch);
-            ctx->host_tile_prefix.assign((size_t)n_periods + 1, 0u);
-            ctx->split_max_items = 0;
-            if (ctx->split) {
-                for (int64_t wk = 0; wk < n_periods; ++wk) {
-                    const tlsdev::PeriodRows& pr = prow[(size_t)order[(size_t)wk]];
-                    const size_t tl = pr.pad > 0 ? (size_t)pr.pad : tile;      // the kernel's tile length of this period
-                    ctx->host_tile_prefix[(size_t)wk + 1] = ctx->host_tile_prefix[(size_t)wk] + (unsigned int)(((size_t)M + tl - 1) / tl);
-                }
-                for (int64_t lo = 0; lo < n_periods; lo += ctx->split_batch) {
-                    const int64_t hi = std::min<int64_t>(n_periods, lo + ctx->split_batch);
-                    ctx->split_max_items = std::max<int64_t>(ctx->split_max_items, (int64_t)ctx->host_tile_prefix[(size_t)hi] - (int64_t)ctx->host_tile_prefix[(size_t)lo]);
-                }
-                TLS_HIP(ctx, ctx->d_partials.reserve(3 * (size_t)ctx->split_max_items + 3));
-                // [split_batch] tiles done | [split_batch] fold ready: all zero between launches (the kernel resets them)
-                if (ctx->d_tiles_done.cap < 2 * (size_t)ctx->split_batch) {
-                    TLS_HIP(ctx, ctx->d_tiles_done.reserve(2 * (size_t)ctx->split_batch));
-                    TLS_HIP(ctx, hipMemsetAsync(ctx->d_tiles_done.ptr, 0, ctx->d_tiles_done.cap * sizeof(unsigned int), ctx->stream));
-                }
-            }
-        }
-        const size_t scratch_blocks = std::max<size_t>((size_t)ctx->blocks, ctx->split ? (size_t)ctx->split_batch : 0);
-        TLS_HIP(ctx, ctx->d_scratch.reserve(scratch_blocks * regions * (region_doubles + 1) + 16));
-    }
-    // per-width work units of phase 3 (M is fixed for the plan, so these are period independent)
-    // and the layout of one workgroup's live-unit lists: every unit of every width has a slot
-    size_t list_cap = 0;
-    for (auto& we : widths) {
-        const int64_t n_pos = (M - we.width) / we.xth + 1;
-        const int64_t r = we.tiled ? tlsdev::kR : 1;
-        we.n_pos = (int)n_pos;
-        we.n_chunks = (int)((n_pos + r - 1) / r);
-        we.list_base = (int)list_cap;
-        we.inv_d = 1.0 / (double)we.width;
-        list_cap += (size_t)we.n_chunks;
-    }
-    ctx->list_stride = (list_cap + 63) / 64 * 64;
-    // three arrays per workgroup: the live units, (pruning) the bound of each, and the units the bound keeps
-    TLS_HIP(ctx, ctx->d_lists.reserve((size_t)std::max(std::max(ctx->blocks, ctx->slim_blocks), (!ctx->resident && ctx->split) ? ctx->split_blocks : 0) * 3 * ctx->list_stride));
-    if (ctx->slim_blocks > 0) TLS_HIP(ctx, ctx->d_perm.reserve(perm_scratch_words(ctx, (size_t)n)));   // (band resolution stashes the order of a period)
-    {
-        // the table of folded orders of a four-slot plan, within its budget; a plan without one sorts in every launch
-        size_t want = 0;
-        if (ctx->slim_blocks > 0 && ctx->opt.perm_table != 0) {
-            const size_t entries = (size_t)n_periods * (size_t)tlsdev::slim_perm_row(ctx->slim_threads);
-            const size_t cap = ctx->opt.perm_table > 0 ? (size_t)ctx->opt.perm_table << 20 : kPermTableMaxBytes;
-            if (entries * sizeof(unsigned short) <= cap) want = entries;
-        }
-        if (want > ctx->d_perm_table.cap && ctx->d_perm_table.reserve(want) != hipSuccess) {
-            (void)hipGetLastError();   // (no room on the device: not an error)
-            ctx->d_perm_table.release();
-            want = 0;
-        }
-        ctx->perm_table_entries = want;
-        // the layout of the plan's stored orders (table rows, a survey group's stash): stretch-major where the fast-mode
-        // scan's stretch fits a thread's entries (tls_slim_kernel.hip.h), thread-major otherwise (and by switch reg_scan = 0)
-        const int per = ctx->slim_blocks > 0 ? tlsdev::slim_scan_per(ctx->slim_threads, (int)M) : 0;
-        ctx->slim_perm_per = (ctx->opt.reg_scan != 0 && per <= tlsdev::kSlimPer && W <= n) ? per : 0;
-    }
-    ctx->prune_min_live = ctx->opt.prune_min_live >= 0 ? (long long)ctx->opt.prune_min_live : 256;
-    ctx->p2_shift = 4;  // block length of the coarse prefix sum of e^2: at most kP2MaxBlocks blocks
-    while ((((size_t)M + ((size_t)1 << ctx->p2_shift) - 1) >> ctx->p2_shift) > (size_t)tlsdev::kP2MaxBlocks) ++ctx->p2_shift;
+    // launch geometry, and the device buffers it asks for
+    if (const char* why = plan_search(ctx->plan, n, widths, uniform, n_periods, ctx->n_cu, ctx->opt, prow.data(), order.data()))
+        return fail(ctx, TLS_E_ARG, why);
+    { int rcb = reserve_plan_buffers(ctx); if (rcb) return rcb; }
 
-    ctx->n = (int)n; ctx->W = (int)W; ctx->M = (int)M; ctx->n_periods = (int)n_periods;
-    ctx->n_widths = (int)widths.size();
-    ctx->uniform_w = uniform; ctx->w0 = w0; ctx->S0 = S0; ctx->depth_min = params->transit_depth_min;
+    ctx->w0 = w0; ctx->S0 = S0; ctx->depth_min = params->transit_depth_min;
     ctx->host_widths = widths;
     ctx->band_sigma = -1.0; ctx->d_band_now = nullptr;   // (d_band belongs to the previous width table)
-    choose_flux_kernels(ctx, uniform, flux_sigma);
-    ctx->plan_counters = pc;
+    choose_flux_kernels(ctx, flux_sigma);
+    ctx->plan_counters = tls_counters{gp.cells, 0, 0, gp.pairs, 0};
 
-    // ONE pinned staging buffer, ONE device allocation, ONE asynchronous copy; nothing is waited for here (the
-    // staging buffer is reused only after its event)
-    std::vector<tlsdev::RowScreen> screens;
-    build_screens(widths, q, screens, ctx->opt.no_screen == 1);
-    {
-        PlanLayout& L = ctx->layout;
-        size_t off = 0;
-        auto place = [&](size_t bytes) { const size_t at = off; off = (off + bytes + 255) / 256 * 256; return at; };
-        const size_t nn = (size_t)n, np = (size_t)n_periods, nw = widths.size(), nq = q.size();
-        L.t = place(nn * 8); L.y = place(nn * 8); L.w = place(uniform ? 0 : nn * 8);
-        L.periods = place(np * 8); L.order = place(np * sizeof(int)); L.rows = place(np * sizeof(tlsdev::PeriodRows));
-        L.widths = place(nw * sizeof(tlsdev::WidthEntry)); L.screens = place(nw * sizeof(tlsdev::RowScreen));
-        L.q = place(nq * 8); L.q2 = place(nq * 8);   // (uniform weights: the fp32 rows of the screen instead of q^2)
-        const bool with_g = !ctx->resident || ctx->slim_blocks > 0;   // the difference taps: dot products on X (HBM slab; four-slot kernel)
-        L.g = place(with_g ? nq * 8 : 0);
-        const bool with_tiles = !ctx->resident && ctx->split;
-        L.tile_prefix = place(with_tiles ? (np + 1) * sizeof(unsigned int) : 0);
-        L.total = off;
-        int rcs = stage_reserve(ctx, L.total);
-        if (rcs) return rcs;
-        TLS_HIP(ctx, ctx->d_plan.reserve(L.total));
-        unsigned char* h = ctx->h_stage;
-        std::memcpy(h + L.t, t, nn * 8);
-        std::memcpy(h + L.y, y, nn * 8);
-        if (!uniform) std::memcpy(h + L.w, w.data(), nn * 8);
-        if (np) {
-            std::memcpy(h + L.periods, periods, np * 8);
-            std::memcpy(h + L.order, order.data(), np * sizeof(int));
-            std::memcpy(h + L.rows, prow.data(), np * sizeof(tlsdev::PeriodRows));
-        }
-        std::memcpy(h + L.widths, widths.data(), nw * sizeof(tlsdev::WidthEntry));
-        std::memcpy(h + L.screens, screens.data(), nw * sizeof(tlsdev::RowScreen));
-        std::memcpy(h + L.q, q.data(), nq * 8);
-        ctx->q_count = (long long)nq;
-        if (!uniform) {
-            double* q2 = reinterpret_cast<double*>(h + L.q2);
-            for (size_t j = 0; j < nq; ++j) q2[j] = q[j] * q[j];
-        } else {
-            float* q32 = reinterpret_cast<float*>(h + L.q2);   // [nq] the rows | [nq] the rows one element later
-            for (size_t j = 0; j < nq; ++j) { q32[j] = (float)q[j]; q32[nq + j] = j ? (float)q[j - 1] : 0.0f; }
-        }
-        if (with_g) {
-            // Difference taps of every row, same offsets: g_0 = -q_0, g_j = q_{j-1} - q_j, g_L = q_{L-1}.  With e_k =
-            // X_{k+1} - X_k (X the running sum of e) a window's dot product is  sum_j q_j e_{i+j} = sum_{j<=L} g_j X_{i+j}
-            // (summation by parts): the slab variant's fast mode evaluates it on the X a tile already holds in LDS for
-            // the depth predicate, instead of staging the tile's samples a second time (tls_search_body.inc.h, x_dot).
-            double* gt = reinterpret_cast<double*>(h + L.g);
-            std::memset(gt, 0, nq * 8);
-            for (const auto& we : widths) {
-                const double* qr = q.data() + we.q_offset;
-                double* gr = gt + we.q_offset;
-                gr[0] = -qr[0];
-                for (int j = 1; j < we.q_len; ++j) gr[j] = qr[j - 1] - qr[j];
-                gr[we.q_len] = qr[we.q_len - 1];
-            }
-        }
-        if (with_tiles) {
-            std::memcpy(h + L.tile_prefix, ctx->host_tile_prefix.data(), (np + 1) * sizeof(unsigned int));
-        }
-        unsigned char* d = ctx->d_plan.ptr;
-        ctx->d_tile_prefix.ptr = reinterpret_cast<unsigned int*>(d + L.tile_prefix);
-        ctx->d_t.ptr = reinterpret_cast<double*>(d + L.t); ctx->d_y.ptr = reinterpret_cast<double*>(d + L.y);
-        ctx->d_w.ptr = reinterpret_cast<double*>(d + L.w); ctx->d_periods.ptr = reinterpret_cast<double*>(d + L.periods);
-        ctx->d_order.ptr = reinterpret_cast<int*>(d + L.order); ctx->d_rows.ptr = reinterpret_cast<tlsdev::PeriodRows*>(d + L.rows);
-        ctx->d_widths.ptr = reinterpret_cast<tlsdev::WidthEntry*>(d + L.widths);
-        ctx->d_screens.ptr = reinterpret_cast<tlsdev::RowScreen*>(d + L.screens);
-        ctx->d_q.ptr = reinterpret_cast<double*>(d + L.q); ctx->d_q2.ptr = reinterpret_cast<double*>(d + L.q2);
-        ctx->d_g.ptr = reinterpret_cast<double*>(d + L.g);
-        TLS_HIP(ctx, hipMemcpyAsync(d, h, L.total, hipMemcpyHostToDevice, ctx->stream));
-        TLS_HIP(ctx, hipEventRecord(ctx->ev_stage, ctx->stream));
-        ctx->stage_pending = true;
-        // results [chi2 | row | depth | counters[4]]
-        TLS_HIP(ctx, ctx->d_out.reserve(3 * np + 4));
-        ctx->d_chi2.ptr = ctx->d_out.ptr; ctx->d_row.ptr = reinterpret_cast<long long*>(ctx->d_out.ptr + np);
-        ctx->d_depth.ptr = ctx->d_out.ptr + 2 * np;
-        ctx->d_counters.ptr = reinterpret_cast<unsigned long long*>(ctx->d_out.ptr + 3 * np);
-    }
-    TLS_HIP(ctx, ctx->d_queue.reserve(1));
-    if (!ctx->d_squeue.ptr) {   // zero once per context: the kernel rewinds its queue itself
-        TLS_HIP(ctx, ctx->d_squeue.reserve(4));   // [0..1] the search (or fold) kernel's queue, [2..3] the split path's search kernel
-        TLS_HIP(ctx, hipMemsetAsync(ctx->d_squeue.ptr, 0, 4 * sizeof(unsigned int), ctx->stream));
-    }
+    { int rcs = stage_plan(ctx, t, y, w, periods, order, prow, widths, q); if (rcs) return rcs; }
     key_store(ctx->key, ctx->opt, t, n, periods, n_periods, tmpl, params);
     ctx->prepared = true;
     return TLS_OK;
@@ -2139,12 +1649,12 @@ int update_flux_impl(tls_ctx* ctx, const double* y, const double* dy) {
     std::vector<double> w;
     bool uniform; double w0, S0;
     double y_abs_max = 0.0, e_abs_max = 0.0;
-    weights_from(y, dy, ctx->n, uniform, w0, w, S0, &y_abs_max, &e_abs_max);
-    if (uniform != ctx->uniform_w) return kWeightsDiffer;
+    weights_from(y, dy, ctx->plan.n, uniform, w0, w, S0, &y_abs_max, &e_abs_max);
+    if (uniform != ctx->plan.uniform) return kWeightsDiffer;
     ctx->w0 = w0; ctx->S0 = S0; ctx->y_abs_max = y_abs_max; ctx->e_abs_max = e_abs_max;
-    choose_flux_kernels(ctx, uniform, flux_scatter(y, ctx->n));
+    choose_flux_kernels(ctx, flux_scatter(y, ctx->plan.n));
     const PlanLayout& L = ctx->layout;
-    const size_t nn = (size_t)ctx->n;
+    const size_t nn = (size_t)ctx->plan.n;
     int rcs = stage_reserve(ctx, L.total);   // (waits for the previous upload out of the staging buffer)
     if (rcs) return rcs;
     std::memcpy(ctx->h_stage + L.y, y, nn * 8);
@@ -2175,7 +1685,7 @@ int tls_execute(tls_ctx* ctx, int count_work) {
     if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
     if (!ctx->prepared) return fail(ctx, TLS_E_STATE, "tls_execute before tls_prepare");
     TLS_HIP(ctx, hipSetDevice(ctx->device));
-    if (ctx->n_periods == 0) { ctx->executed = true; return TLS_OK; }
+    if (ctx->plan.n_periods == 0) { ctx->executed = true; return TLS_OK; }
     return enqueue(ctx, (count_work & 1) != 0, (count_work & 2) != 0);
 }
 
@@ -2195,8 +1705,8 @@ int tls_t0_fit(tls_ctx* ctx, const double* t, const double* y, int64_t n, double
     if ((rc = upload(ctx, ctx->d_fep, epochs, (size_t)n_epochs))) return rc;
     TLS_HIP(ctx, ctx->d_fres.reserve((size_t)n_epochs));
     TLS_HIP(ctx, hipMemsetAsync(ctx->d_queue.ptr, 0, sizeof(unsigned int), ctx->stream));
-    double t_lo = t[0], t_hi = t[0];
-    for (int64_t i = 1; i < n; ++i) { t_lo = std::min(t_lo, t[i]); t_hi = std::max(t_hi, t[i]); }
+    double t_lo, t_hi;
+    time_range(t, n, t_lo, t_hi);
     if ((rc = launch_t0_fit(ctx, ctx->d_ft.ptr, ctx->d_fy.ptr, ctx->d_fsig.ptr, ctx->d_fep.ptr, ctx->d_fres.ptr, ctx->d_queue.ptr,
                             n, period, dur, n_epochs, roll, t_lo, t_hi))) return rc;
     TLS_HIP(ctx, hipMemcpyAsync(out_residuals, ctx->d_fres.ptr, (size_t)n_epochs * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -2570,10 +2080,10 @@ int tls_spectra(tls_ctx* ctx, const double* chi2, int64_t n, int64_t kernel, dou
     if (!out_SR || !out_power_raw || !out_power || !out_sde) return fail(ctx, TLS_E_ARG, "null output");
     // ((32 + kernel) doubles of dynamic LDS per median workgroup must stay within the 64 KB a launch gets without asking)
     if (kernel < 1 || kernel > 8000) return fail(ctx, TLS_E_ARG, "median kernel out of range [1, 8000]");
-    if (!chi2 && !(ctx->executed && ctx->n_periods > 0)) return fail(ctx, TLS_E_STATE, "tls_spectra without chi2 needs a finished search");
+    if (!chi2 && !(ctx->executed && ctx->plan.n_periods > 0)) return fail(ctx, TLS_E_STATE, "tls_spectra without chi2 needs a finished search");
     if (chi2 && (n < 1 || n > 100000000)) return fail(ctx, TLS_E_ARG, "n out of range");
     TLS_HIP(ctx, hipSetDevice(ctx->device));
-    if (!chi2) n = ctx->n_periods;
+    if (!chi2) n = ctx->plan.n_periods;
     if (kernel % 2 == 0) kernel += 1;                                   // stats.py:115-117
     const size_t nn = (size_t)n;
     TLS_HIP(ctx, ctx->d_spec.reserve(4 * nn + 2));
@@ -2611,7 +2121,7 @@ int tls_spectra(tls_ctx* ctx, const double* chi2, int64_t n, int64_t kernel, dou
 int tls_debug_folded(tls_ctx* ctx, double* out, int64_t capacity) {
     if (!ctx || !out) return fail(ctx, TLS_E_ARG, "bad argument");
     if (!ctx->prepared) return fail(ctx, TLS_E_STATE, "tls_debug_folded before tls_prepare");
-    const int64_t need = ctx->n_periods * ctx->n;
+    const int64_t need = ctx->plan.n_periods * ctx->plan.n;
     if (capacity < need) return fail(ctx, TLS_E_ARG, "tls_debug_folded: out holds fewer than n_periods * n doubles");
     if (need == 0) return TLS_OK;
     TLS_HIP(ctx, hipSetDevice(ctx->device));
@@ -2632,9 +2142,9 @@ int tls_debug_folded(tls_ctx* ctx, double* out, int64_t capacity) {
 int tls_debug_prefix(tls_ctx* ctx, double* out, int64_t capacity, int64_t* row_length) {
     if (!ctx || !row_length) return fail(ctx, TLS_E_ARG, "bad argument");
     if (!ctx->prepared) return fail(ctx, TLS_E_STATE, "tls_debug_prefix before tls_prepare");
-    *row_length = ctx->M + 1;
+    *row_length = ctx->plan.M + 1;
     if (!out) return TLS_OK;   // size query
-    const int64_t need = ctx->n_periods * (ctx->M + 1);
+    const int64_t need = ctx->plan.n_periods * (ctx->plan.M + 1);
     if (capacity < need) return fail(ctx, TLS_E_ARG, "tls_debug_prefix: out holds fewer than n_periods * row_length doubles");
     if (need == 0) return TLS_OK;
     TLS_HIP(ctx, hipSetDevice(ctx->device));
@@ -2655,15 +2165,15 @@ int tls_debug_prefix(tls_ctx* ctx, double* out, int64_t capacity, int64_t* row_l
 int tls_debug_period_cycles(tls_ctx* ctx, uint64_t* cycles, int64_t capacity) {
     if (!ctx || !cycles) return fail(ctx, TLS_E_ARG, "bad argument");
     if (!ctx->prepared) return fail(ctx, TLS_E_STATE, "tls_debug_period_cycles before tls_prepare");
-    if (capacity < ctx->n_periods) return fail(ctx, TLS_E_ARG, "tls_debug_period_cycles: out holds fewer than n_periods entries");
-    if (ctx->n_periods == 0) return TLS_OK;
+    if (capacity < ctx->plan.n_periods) return fail(ctx, TLS_E_ARG, "tls_debug_period_cycles: out holds fewer than n_periods entries");
+    if (ctx->plan.n_periods == 0) return TLS_OK;
     TLS_HIP(ctx, hipSetDevice(ctx->device));
     DevBuf<unsigned long long> d_out;
-    TLS_HIP(ctx, d_out.reserve((size_t)ctx->n_periods));
-    hipError_t e = hipMemsetAsync(d_out.ptr, 0, (size_t)ctx->n_periods * 8, ctx->stream);
+    TLS_HIP(ctx, d_out.reserve((size_t)ctx->plan.n_periods));
+    hipError_t e = hipMemsetAsync(d_out.ptr, 0, (size_t)ctx->plan.n_periods * 8, ctx->stream);
     int rc = e == hipSuccess ? enqueue(ctx, false, false, nullptr, nullptr, d_out.ptr) : fail(ctx, TLS_E_HIP, hipGetErrorString(e));
     if (rc == TLS_OK) {
-        e = hipMemcpyAsync(cycles, d_out.ptr, (size_t)ctx->n_periods * 8, hipMemcpyDeviceToHost, ctx->stream);
+        e = hipMemcpyAsync(cycles, d_out.ptr, (size_t)ctx->plan.n_periods * 8, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         if (e != hipSuccess) rc = fail(ctx, TLS_E_HIP, hipGetErrorString(e));
     } else {
@@ -2950,7 +2460,7 @@ int tls_execute_timed(tls_ctx* ctx, int reps, double* ms_per_execute) {
     if (!ctx->prepared) return fail(ctx, TLS_E_STATE, "tls_execute_timed before tls_prepare");
     if (reps < 1 || !ms_per_execute) return fail(ctx, TLS_E_ARG, "reps must be >= 1");
     TLS_HIP(ctx, hipSetDevice(ctx->device));
-    if (ctx->n_periods == 0) { *ms_per_execute = 0; return TLS_OK; }
+    if (ctx->plan.n_periods == 0) { *ms_per_execute = 0; return TLS_OK; }
     TLS_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
     for (int r = 0; r < reps; ++r) {
         int rc = enqueue(ctx, false);
@@ -2969,7 +2479,7 @@ int tls_fetch(tls_ctx* ctx, double* out_chi2, int64_t* out_row, double* out_dept
     if (!ctx->executed) return fail(ctx, TLS_E_STATE, "tls_fetch before tls_execute");
     if (!out_chi2 || !out_row || !out_depth) return fail(ctx, TLS_E_ARG, "null output");
     TLS_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t np = (size_t)ctx->n_periods;
+    const size_t np = (size_t)ctx->plan.n_periods;
     static_assert(sizeof(long long) == sizeof(int64_t), "int64 layout");
     unsigned long long dev_counts[3] = {0, 0, 0};
     if (np) {
@@ -3021,13 +2531,11 @@ const char* tls_last_kernel(const tls_ctx* ctx) { return ctx ? ctx->last_kernel 
 int tls_plan_info(const tls_ctx* ctx, tls_counters* counters, int64_t* lds_bytes, int64_t* n_blocks, int64_t* resident) {
     if (!ctx || !ctx->prepared) return TLS_E_STATE;
     if (counters) { *counters = ctx->plan_counters; counters->evaluated_cells = -1; counters->inner_steps = -1; counters->issued_fma = -1; }
-    // (the launch shape of the kernel a plain search of this plan takes: the four-slot kernel where the plan fits it and
-    // neither pruning nor the fp32 screen is the host's choice)
-    const bool slim = ctx->slim_blocks > 0 && ctx->uniform_w && !ctx->prune_kernel &&
-                      !(ctx->screen_kernel && screen_admissible(ctx->resident, ctx->uniform_w, ctx->e_abs_max));
-    if (lds_bytes) *lds_bytes = (int64_t)(slim ? ctx->slim_lds : ctx->lds_bytes);
-    if (n_blocks) *n_blocks = slim ? ctx->slim_blocks : ctx->blocks;
-    if (resident) *resident = ctx->resident ? 1 : 0;
+    // (the launch shape of the kernel a plain search of this plan takes)
+    const bool slim = is_slim(pick_kernel(ctx->plan, ctx->flux));
+    if (lds_bytes) *lds_bytes = (int64_t)(slim ? ctx->plan.slim_lds : ctx->plan.lds_bytes);
+    if (n_blocks) *n_blocks = slim ? ctx->plan.slim_blocks : ctx->plan.blocks;
+    if (resident) *resident = ctx->plan.resident ? 1 : 0;
     return TLS_OK;
 }
 
@@ -3249,8 +2757,8 @@ static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, cons
     if (rc) return rc;
     const int64_t group = std::min<int64_t>(32, n_curves);              // (one light curve: the drop-in power() call)
     const size_t np = (size_t)n_periods, nn = (size_t)n;
-    double t_min = t[0], t_max = t[0];
-    for (int64_t i = 1; i < n; ++i) { t_min = std::min(t_min, t[i]); t_max = std::max(t_max, t[i]); }
+    double t_min, t_max;
+    time_range(t, n, t_min, t_max);
     // device buffers of one group: flux (weights), per-curve constants, search results, spectra, summaries, T0-fit inputs
     auto& sl = ctx->slot[0];
     if ((rc = reserve_batch_slot(ctx, sl, group, nn, np))) return rc;
@@ -3401,12 +2909,10 @@ int tls_grid_cells(const double* t, int64_t n, const double* periods, int64_t n_
     std::vector<tlsdev::WidthEntry> widths;
     int rc = build_widths(nullptr, tmpl, params, n, widths, nullptr);
     if (rc) return rc;
-    int64_t W = widths.back().width;
-    if (W % 2 != 0) W += 1;
-    double t_min = t[0], t_max = t[0];
-    for (int64_t i = 1; i < n; ++i) { t_min = std::min(t_min, t[i]); t_max = std::max(t_max, t[i]); }
+    double t_min, t_max;
+    time_range(t, n, t_min, t_max);
     GridPlan gp;
-    if (!plan_periods(widths, params, periods, n_periods, t_max - t_min, n, n + W, nullptr, cells_per_period, &gp)) {
+    if (!plan_periods(widths, params, periods, n_periods, t_max - t_min, n, n + padded_width(widths), nullptr, cells_per_period, &gp)) {
         g_create_error = "tls_grid_cells: periods must be positive and finite";
         return TLS_E_ARG;
     }
@@ -3428,11 +2934,9 @@ int tls_period_costs(const double* t, int64_t n, const double* periods, int64_t 
     std::vector<tlsdev::WidthEntry> widths;
     int rc = build_widths(nullptr, tmpl, params, n, widths, nullptr);
     if (rc) return rc;
-    int64_t W = widths.back().width;
-    if (W % 2 != 0) W += 1;
-    const int64_t M = n + W;
-    double t_min = t[0], t_max = t[0];
-    for (int64_t i = 1; i < n; ++i) { t_min = std::min(t_min, t[i]); t_max = std::max(t_max, t[i]); }
+    const int64_t M = n + padded_width(widths);
+    double t_min, t_max;
+    time_range(t, n, t_min, t_max);
     std::vector<tlsdev::PeriodRows> prow((size_t)n_periods);
     GridPlan gp;
     if (!plan_periods(widths, params, periods, n_periods, t_max - t_min, n, M, prow.data(), cells_per_period, &gp)) {
@@ -3452,32 +2956,26 @@ int tls_period_costs(const double* t, int64_t n, const double* periods, int64_t 
     for (int64_t p = 0; p < n_periods; ++p)
         taps_per_period[p] = prefix[(size_t)prow[(size_t)p].k_hi] - prefix[(size_t)prow[(size_t)p].k_lo];
     if (time_per_period) {
-        // Which kernel variant a search of this light curve runs (as tls_prepare decides it, UNIFORM weights assumed: the call
-        // has no dy, and between the uniform and the per-point edges of the plan it prices a kernel a weighted search does not run),
-        // and that variant's measured cost per period in shader cycles: a0 + aN * n + b * cells + c * taps, fitted to
-        // tls_debug_period_cycles on an MI355X (tools/gpu_cost_model.py, profiles/r03_cost_model_fit.json).  Only the
+        // Which kernel a search of this light curve runs: the plan and the pick tls_prepare and enqueue make, UNIFORM weights
+        // assumed (the call has no dy: between the uniform and the per-point edges of the plan it prices a kernel a weighted
+        // search does not run) and a normalised flux (it admits the fp32 screen: the choice between plain and screen is the
+        // noise level's).  That kernel's measured cost per period in shader cycles: a0 + aN * n + b * cells + c * taps, fitted
+        // to tls_debug_period_cycles on an MI355X (tools/gpu_cost_model.py, profiles/r03_cost_model_fit.json).  Only the
         // ratios matter to the callers (tls_amd/shard.py places block boundaries by the cumulative sum).
-        int widest_stride = 1;
-        for (const auto& we : widths) if (we.tiled) widest_stride = std::max(widest_stride, we.xth);
-        const size_t region_doubles = (size_t)(M + 1 + tlsdev::region_pad_for(widest_stride));
-        const size_t hdr = ((size_t)tlsdev::kFixedHeader + 4 * (3 * widths.size() + 2) + 15) / 16 * 16;
-        const size_t resident_bytes = hdr + 2 * 8 * region_doubles;
-        const bool resident = resident_bytes <= kLdsPerCU && n <= 65535;
-        const bool two_per_cu = resident && kLdsPerCU / resident_bytes >= 2;
-        const bool prune = pruning_pays(po, widths, sigma, params->transit_depth_min, resident);
-        // the four-slot kernel where tls_prepare takes it (a normalised flux admits the fp32 screen: the host's choice between
-        // plain and screen is the noise level's)
-        const long long slim_need = tlsdev::slim_lds_bytes((int)n, (int)M, tlsdev::region_pad_for(widest_stride), (int)widths.size());
-        const bool slim_wanted = po.exact_prefix != 1 && (po.slim == 1 || (po.slim < 0 && po.prune < 0 && po.screen32 < 0));
-        const bool slim_base = resident && slim_wanted && po.threads <= 0 && !prune && !screen_pays(po, widths, sigma, params->transit_depth_min, true);
-        const long long slim_need_wide = tlsdev::slim_lds_bytes((int)n, (int)M, tlsdev::region_pad_for(widest_stride), (int)widths.size(), tlsdev::kSlimThreadsWide);
-        const bool slim_narrow = slim_base && slim_need > 0 && kSlimMinSlots * (size_t)slim_need <= kLdsPerCU;
-        const bool slim_wide = slim_base && !slim_narrow && slim_need == 0 && slim_need_wide > 0 && 2 * (size_t)slim_need_wide <= kLdsPerCU;   // (512-thread shape, two to a CU)
-        const bool slim = slim_narrow || slim_wide;
+        SearchPlan plan;
+        // (a series tls_prepare refuses is priced as the slab kernel it does not fit: the plan says `resident` either way)
+        (void)plan_search(plan, n, widths, /*uniform=*/true, n_periods, visible_compute_units(), po);
+        // kept from before the plan was shared: pruning is priced against the plain kernel's threshold
+        // although the screen is assumed admissible, where a search takes the threshold beside the screen
+        const bool prune_beside_screen = false;
+        const FluxChoice flux = choose_flux_kernels(plan, po, widths, sigma, params->transit_depth_min,
+                                                    screen_admissible(plan.resident, true, 0.0), prune_beside_screen);
+        const Kernel kernel = pick_kernel(plan, flux);
+        const bool resident = plan.resident, two_per_cu = plan.per_cu >= 2;
         double a0, aN, b, c;
         if (!resident) { a0 = 458384.0; aN = 4.5716; b = 0.4604; c = 0.03275; }        // HBM slab variant (TESS 27 d + Kepler 4 yr)
-        else if (slim) { a0 = 59538.0; aN = 0.0; b = 1.553; c = 0.2125; }               // LDS-resident, four 256-thread workgroups per CU (90 d at 50 ppm, round 5)
-        else if (prune) { a0 = 116100.0; aN = 0.0; b = 1.906; c = 0.0125; }             // LDS-resident, pruning kernel (90 d at 500 ppm)
+        else if (is_slim(kernel)) { a0 = 59538.0; aN = 0.0; b = 1.553; c = 0.2125; }    // LDS-resident, four 256-thread workgroups per CU (90 d at 50 ppm, round 5)
+        else if (kernel == Kernel::ResidentPrune) { a0 = 116100.0; aN = 0.0; b = 1.906; c = 0.0125; }   // LDS-resident, pruning kernel (90 d at 500 ppm)
         else if (two_per_cu) { a0 = 54603.0; aN = 0.0; b = 0.7823; c = 0.1888; }        // LDS-resident, two 512-thread workgroups per CU (90 d)
         else { a0 = 56564.0; aN = 0.0; b = 0.3189; c = 0.1267; }                        // LDS-resident, one 1024-thread workgroup per CU (100 d)
         for (int64_t p = 0; p < n_periods; ++p)
@@ -3502,7 +3000,8 @@ int tls_period_costs(const double* t, int64_t n, const double* periods, int64_t 
         // device is asked, a process without one plans for an MI355X), two workgroups per CU when two folded series fit
         // its LDS.  A block of n periods takes ceil(n / this) rounds, not n / this.  (The cycle coefficients above are
         // MI355X measurements; only their ratios matter.)
-        if (workgroups_in_flight) *workgroups_in_flight = (slim_narrow ? (int)std::min<size_t>(4, kLdsPerCU / (size_t)slim_need) : slim_wide ? 2 : two_per_cu ? 2 : 1) * visible_compute_units();
+        // (the classic kernel's registers let two of its workgroups be resident, however many its LDS share would admit)
+        if (workgroups_in_flight) *workgroups_in_flight = (is_slim(kernel) ? plan.slim_slots : two_per_cu ? 2 : 1) * visible_compute_units();
     } else if (workgroups_in_flight) {
         *workgroups_in_flight = visible_compute_units();
     }
@@ -3557,9 +3056,9 @@ int tls_comm_allgather_device(tls_ctx* ctx, int64_t count_per_rank) {
     if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
     if (!ctx->comm) return fail(ctx, TLS_E_STATE, "tls_comm_init first");
     if (!ctx->executed) return fail(ctx, TLS_E_STATE, "all-gather before tls_execute");
-    if (count_per_rank < ctx->n_periods || count_per_rank < 1) return fail(ctx, TLS_E_ARG, "count_per_rank smaller than this rank's shard");
+    if (count_per_rank < ctx->plan.n_periods || count_per_rank < 1) return fail(ctx, TLS_E_ARG, "count_per_rank smaller than this rank's shard");
     TLS_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t c = (size_t)count_per_rank, np = (size_t)ctx->n_periods, R = (size_t)ctx->n_ranks;
+    const size_t c = (size_t)count_per_rank, np = (size_t)ctx->plan.n_periods, R = (size_t)ctx->n_ranks;
     // pack [chi2 | row | depth] of this shard, zero padded: 24 B per period
     TLS_HIP(ctx, ctx->d_pack.reserve(3 * c));
     TLS_HIP(ctx, ctx->d_gather.reserve(3 * c * R));
@@ -3597,10 +3096,10 @@ int tls_comm_fetch_gathered(tls_ctx* ctx, int64_t count_per_rank, double* all_ch
 int tls_comm_stage_results(tls_ctx* ctx, int64_t count_per_rank, int64_t slot, int64_t n_slots) {
     if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
     if (!ctx->executed) return fail(ctx, TLS_E_STATE, "staging before tls_execute");
-    if (count_per_rank < ctx->n_periods || count_per_rank < 1 || n_slots < 1 || slot < 0 || slot >= n_slots)
+    if (count_per_rank < ctx->plan.n_periods || count_per_rank < 1 || n_slots < 1 || slot < 0 || slot >= n_slots)
         return fail(ctx, TLS_E_ARG, "bad slot layout");
     TLS_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t c = (size_t)count_per_rank, np = (size_t)ctx->n_periods;
+    const size_t c = (size_t)count_per_rank, np = (size_t)ctx->plan.n_periods;
     TLS_HIP(ctx, ctx->d_stage.reserve(3 * c * (size_t)n_slots));
     double* dst = ctx->d_stage.ptr + 3 * c * (size_t)slot;   // [chi2 | row | depth] of this slot, 24 B per period
     if (np < c) TLS_HIP(ctx, hipMemsetAsync(dst, 0, 3 * c * 8, ctx->stream));
