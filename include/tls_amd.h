@@ -36,7 +36,8 @@ extern "C" {
  * them as text; 6: tls_transit_stats, tls_power_batch_stats, tls_debug_transit_stats; 7: tls_power_batch_models,
  * tls_debug_transit_models).  A binding compares it with tls_abi_version().  Entries added without changing a layout or
  * signature keep the version (7: tls_inject_transits, tls_null_rows, tls_debug_null_words,
- * tls_medfilt_detrend, tls_biweight_detrend), (7: tls_power_batch_peaks, tls_find_peaks). */
+ * tls_medfilt_detrend, tls_biweight_detrend), (7: tls_power_batch_peaks, tls_find_peaks),
+ * (7: tls_power_batch_peak_fits, tls_debug_peak_fits). */
 #define TLS_AMD_ABI_VERSION 7
 
 #define TLS_OK 0
@@ -458,6 +459,44 @@ int tls_power_batch_peaks(tls_ctx *ctx, const double *t, const double *y, const 
                           int64_t *out_n_epochs,
                           int64_t k, double min_separation, const double *ratios, int64_t n_ratios, double min_power,
                           tls_peak *out_peaks /* [n_curves][k] */, int64_t *out_n_peaks /* [n_curves] */);
+
+/* ---- survey mode: the final T0 fit and the vetting statistics of every peak ------------------------------------------ */
+/* What the chain behind the search gives the one pick of a light curve, for one of its peaks: 18 doubles. */
+typedef struct tls_peak_fit {
+    double T0;       /* tls_first_min over the candidate's trial epochs; NaN when status != 0 */
+    double status;   /* 0 fitted; 1 no such peak (rank >= n_peaks); 2 the search fitted nothing at this index (row < 0) */
+    tls_transit_stats stats;   /* as the best pick's, from (period, depth, row, index) of the peak; NaN when status != 0 */
+} tls_peak_fit;
+/* tls_power_batch_peaks plus, for every peak of every light curve, the final T0 fit and the statistics record, computed on
+ * the device behind each group's peaks and copied back with them (still one wait per group).  A candidate takes period,
+ * depth AND template row from its own index (tls_peak.row); the best pick takes its row from argmin(chi2) and period and
+ * depth from argmax(power), so the first peak's fit equals the summary's T0 and out_stats exactly where index_best ==
+ * index_power.  The period-uncertainty walk starts at the peak's index.  Summary, statistics and peaks are those of
+ * tls_power_batch_peaks, bit for bit.  row_duration, fill_factor, root, n_root and max_epochs are read even when out_stats
+ * is NULL (then out_per_transit and out_n_epochs are not written); the time stamps must ascend; a candidate with more
+ * than max_epochs transit epochs, or whose row is not the first row of a template duration, is TLS_E_ARG.  The fits run
+ * in slabs of at most 128 (device memory: DESIGN.md "Peak fits").  out_fits [n_curves][k]. */
+int tls_power_batch_peak_fits(tls_ctx *ctx, const double *t, const double *y, const double *dy, int64_t n,
+                              int64_t n_curves, const double *periods, int64_t n_periods,
+                              const tls_template *tmpl, const tls_params *params, int64_t median_kernel,
+                              tls_power_summary *out_summary, double *out_chi2, int64_t *out_row, double *out_depth,
+                              double *out_power, double *out_SR, double *out_power_raw,
+                              const double *row_duration, double fill_factor, const double *root, int64_t n_root,
+                              tls_transit_stats *out_stats, int64_t max_epochs, double *out_per_transit,
+                              int64_t *out_n_epochs,
+                              int64_t k, double min_separation, const double *ratios, int64_t n_ratios, double min_power,
+                              tls_peak *out_peaks /* [n_curves][k] */, int64_t *out_n_peaks /* [n_curves] */,
+                              tls_peak_fit *out_fits /* [n_curves][k] */);
+/* Developer/test entry: the same stage on the prepared plan (tls_prepare) with injected peak records -- light curves
+ * y [n_curves][n], peaks [n_curves][k] of which the first n_peaks[c] count (index in [0, n_periods), row in [-1, n_rows);
+ * power is not read from the records), the detrended power [n_curves][n_periods] the period-uncertainty walk reads, and
+ * the statistics inputs.  out_fits [n_curves][k]; out_epochs and out_residuals (each NULL or [n_curves][k][n]) and
+ * out_n_epochs (NULL or [n_curves][k]) return every fit's trial epochs, as tls_debug_post_search does.  n_curves in
+ * [1, 1024]. */
+int tls_debug_peak_fits(tls_ctx *ctx, const double *y, int64_t n_curves, const tls_peak *peaks, const int64_t *n_peaks,
+                        int64_t k, const double *power, const double *row_duration, int64_t n_rows, double fill_factor,
+                        const double *root, int64_t n_root, int64_t max_epochs, tls_peak_fit *out_fits,
+                        double *out_epochs, double *out_residuals, int64_t *out_n_epochs);
 
 /* ---- host-only planning (no GPU needed) ------------------------------------------ */
 /* Trial cells (duration x T0 positions) each period will enumerate: the data-independent

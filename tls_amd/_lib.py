@@ -39,7 +39,7 @@ SYMBOLS = (
     "tls_debug_post_search", "tls_debug_device_bytes", "tls_debug_perm_table", "tls_power_batch_stats", "tls_debug_transit_stats",
     "tls_power_batch_models", "tls_debug_transit_models",
     "tls_inject_transits", "tls_null_rows", "tls_debug_null_words", "tls_medfilt_detrend",
-    "tls_biweight_detrend", "tls_find_peaks", "tls_power_batch_peaks",
+    "tls_biweight_detrend", "tls_find_peaks", "tls_power_batch_peaks", "tls_power_batch_peak_fits", "tls_debug_peak_fits",
     "tls_comm_unique_id", "tls_comm_init", "tls_comm_destroy", "tls_comm_info", "tls_comm_allgather_results", "tls_comm_allgather_device", "tls_comm_fetch_gathered",
     "tls_comm_stage_results", "tls_comm_allgather_staged", "tls_comm_fetch_staged",
     "tls_comm_barrier", "tls_comm_max",
@@ -144,6 +144,16 @@ class Peak(ctypes.Structure):
 
 
 PEAK_DTYPE = numpy.dtype([("period", "f8"), ("power", "f8"), ("chi2", "f8"), ("depth", "f8"), ("index", "i8"), ("row", "i8")])
+
+
+class PeakFit(ctypes.Structure):
+    """tls_peak_fit: the final T0 fit and the statistics record of one peak (include/tls_amd.h), 18 doubles."""
+    _fields_ = [("T0", ctypes.c_double), ("status", ctypes.c_double), ("stats", TransitStats)]
+
+
+PEAK_FIT_DTYPE = numpy.dtype([("T0", "f8"), ("status", "f8")] + [(k, "f8") for k in TRANSIT_STATS_FIELDS])
+# tls_peak_fit.status
+PEAK_FITTED, PEAK_NONE, PEAK_UNFITTED = 0, 1, 2
 
 
 def peaks_arguments(k, separation, ratios, min_power):
@@ -312,6 +322,11 @@ def load():
     lib.tls_find_peaks.argtypes = [vp, _c_double_p, _c_double_p, _c_int64_p, _c_double_p, i64, i64, _c_double_p] + peaks
     lib.tls_power_batch_peaks.restype = ci
     lib.tls_power_batch_peaks.argtypes = lib.tls_power_batch_stats.argtypes + peaks
+    lib.tls_power_batch_peak_fits.restype = ci
+    lib.tls_power_batch_peak_fits.argtypes = lib.tls_power_batch_peaks.argtypes + [ctypes.c_void_p]
+    lib.tls_debug_peak_fits.restype = ci
+    lib.tls_debug_peak_fits.argtypes = [vp, _c_double_p, i64, ctypes.c_void_p, _c_int64_p, i64, _c_double_p, _c_double_p, i64,
+                                        dbl, _c_double_p, i64, i64, ctypes.c_void_p, _c_double_p, _c_double_p, _c_int64_p]
     lib.tls_debug_device_bytes.restype = ci
     lib.tls_debug_device_bytes.argtypes = [vp, _c_int64_p, _c_int64_p]
     lib.tls_debug_perm_table.restype = ci
@@ -608,15 +623,20 @@ class Context(object):
         return tuple(r[k] for k in names + (MODEL_OUTPUTS if models is not None else ()))
 
     def _power_batch(self, t, y_batch, dy_batch, periods, table, params, median_kernel, with_arrays=False, with_power=False,
-                     with_spectra=False, statistics=None, per_transit=False, models=None, lc_cap=0, peaks=None):
+                     with_spectra=False, statistics=None, per_transit=False, models=None, lc_cap=0, peaks=None,
+                     peak_fits=None):
         """The power-batch entries: tls_power_batch; with statistics = (fill_factor, root, max_epochs)
         tls_power_batch_stats; with models (a ModelTemplate) as well, tls_power_batch_models.  A dict of the outputs by name:
         summary; chi2, row, depth (with_arrays), power (with_power), SR and power_raw (with_spectra), None where not asked
         for; with statistics also stats, per_transit and n_epochs (None without per_transit); with models MODEL_OUTPUTS.
         peaks = (k, separation, ratios, min_power) (peaks_arguments): tls_power_batch_peaks, with or without statistics, and
-        peaks (PEAK_DTYPE [n_curves, k]) and n_peaks [n_curves] as well; no entry carries peaks and models (ValueError)."""
+        peaks (PEAK_DTYPE [n_curves, k]) and n_peaks [n_curves] as well; no entry carries peaks and models (ValueError).
+        peak_fits = (fill_factor, root, max_epochs), with peaks only: tls_power_batch_peak_fits, and peak_fits (PEAK_FIT_DTYPE
+        [n_curves, k]: T0, status and the statistics record of every peak) as well, with or without statistics."""
         if peaks is not None and models is not None:
             raise ValueError("peaks and models cannot be combined: no entry point carries both")
+        if peak_fits is not None and peaks is None:
+            raise ValueError("peak_fits needs peaks: the fits are those of the peaks")
         if peaks is not None:
             peaks = peaks_arguments(*peaks)
         t, periods = _f8(t), _f8(periods)
@@ -652,7 +672,11 @@ class Context(object):
                 args += models.args(lc_cap, model_out)
                 entry = self._lib.tls_power_batch_models
         if peaks is not None:
-            if statistics is None:   # (out_stats NULL: no statistics, their inputs are not read)
+            if statistics is None and peak_fits is not None:   # (out_stats NULL: the fits read the inputs all the same)
+                fill_factor, root, max_epochs = peak_fits
+                row_duration, root = _f8(table.duration), _f8(root)
+                args += [_dp(row_duration), float(fill_factor), _dp(root), len(root), None, int(max_epochs), None, None]
+            elif statistics is None:   # (out_stats NULL: no statistics, their inputs are not read)
                 args += [None, 0.0, None, 0, None, 1, None, None]
             k, sep, ratios, low = peaks
             out["peaks"] = numpy.zeros((n_c, k), dtype=PEAK_DTYPE)
@@ -660,6 +684,11 @@ class Context(object):
             out["n_peaks"] = numpy.zeros(n_c, dtype=numpy.int64)
             args += [k, sep, _dp(ratios), len(ratios), low, out["peaks"].ctypes.data_as(ctypes.c_void_p), _ip(out["n_peaks"])]
             entry = self._lib.tls_power_batch_peaks
+            if peak_fits is not None:
+                out["peak_fits"] = numpy.zeros((n_c, k), dtype=PEAK_FIT_DTYPE)
+                assert PEAK_FIT_DTYPE.itemsize == ctypes.sizeof(PeakFit)
+                args += [out["peak_fits"].ctypes.data_as(ctypes.c_void_p)]
+                entry = self._lib.tls_power_batch_peak_fits
         self._invalidate_results()
         self._check(entry(*args))
         self._n_periods = n_p
@@ -704,6 +733,40 @@ class Context(object):
         else:
             self._check(self._lib.tls_debug_transit_models(*(args + models.args(lc_cap, out))))
         return (stats, rows, n_epochs) + out
+
+    def debug_peak_fits(self, y_batch, peaks, n_peaks, power, row_duration, fill_factor, root, max_epochs, with_fits=False):
+        """Developer/test entry: the peak-fit stage of power_batch(peaks=K, peak_fits=True) on the prepared plan (prepare())
+        with injected peak records (tls_debug_peak_fits) -- flux y_batch [n_curves, n], peaks [n_curves, k] with the fields
+        of PEAK_DTYPE (more are ignored), n_peaks [n_curves], the detrended power [n_curves, n_periods]: the fits
+        (PEAK_FIT_DTYPE [n_curves, k]); with_fits: also every fit's trial epochs and residuals [n_curves, k, n] and n_epochs
+        [n_curves, k]."""
+        y_batch = numpy.ascontiguousarray(y_batch, dtype=numpy.float64)
+        power = numpy.ascontiguousarray(power, dtype=numpy.float64)
+        n_c = len(y_batch)
+        if y_batch.ndim != 2 or power.shape != (n_c, self._n_periods):
+            raise ValueError("power must have shape [n_curves, n_periods] of the prepared plan, y_batch [n_curves, n]")
+        peaks = numpy.asarray(peaks)
+        if peaks.ndim != 2 or len(peaks) != n_c:
+            raise ValueError("peaks must have shape [n_curves, k]")
+        k = peaks.shape[1]
+        rec = numpy.zeros((n_c, k), dtype=PEAK_DTYPE)
+        for name in PEAK_DTYPE.names:
+            rec[name] = peaks[name]
+        n_peaks = _i8(numpy.broadcast_to(n_peaks, (n_c,)))
+        row_duration, root = _f8(row_duration), _f8(root)
+        fits = numpy.zeros((n_c, k), dtype=PEAK_FIT_DTYPE)
+        assert PEAK_FIT_DTYPE.itemsize == ctypes.sizeof(PeakFit)
+        n = y_batch.shape[1]
+        epochs = numpy.full((n_c, k, n), numpy.nan) if with_fits else None
+        residuals = numpy.full((n_c, k, n), numpy.nan) if with_fits else None
+        n_epochs = numpy.zeros((n_c, k), dtype=numpy.int64) if with_fits else None
+        self._invalidate_results()
+        self._check(self._lib.tls_debug_peak_fits(
+            self._h, _dp(y_batch), n_c, rec.ctypes.data_as(ctypes.c_void_p), _ip(n_peaks), k, _dp(power), _dp(row_duration),
+            len(row_duration), float(fill_factor), _dp(root), len(root), int(max_epochs), fits.ctypes.data_as(ctypes.c_void_p),
+            None if epochs is None else _dp(epochs), None if residuals is None else _dp(residuals),
+            None if n_epochs is None else _ip(n_epochs)))
+        return (fits, epochs, residuals, n_epochs) if with_fits else fits
 
     def _invalidate_results(self):
         """Every call that launches a search, replaces its inputs or reuses the result buffers: the chi2 array an

@@ -210,6 +210,10 @@ struct tls_ctx {
     DevBuf<int> d_windows;          // tls_biweight_detrend: lo [n] | hi [n], the window of every point
     DevBuf<double> d_peaks;         // tls_find_peaks: periods | records of one slab | power [| chi2 | depth | row] rows of one slab
     DevBuf<unsigned long long> d_peak_mask;      // ... and tls_power_batch_peaks: a row's alive mask where the LDS does not hold it
+    // the peak-fit stage (tls_power_batch_peak_fits), one slab of fits: picks | per-transit rows | signals | fit parameters |
+    // n_epochs | curve of fit; trial epochs; residuals; the statistics kernel's scratch and its chunk ranges
+    DevBuf<double> d_pfit, d_pfep, d_pfres, d_pfstats;
+    DevBuf<int> d_pfranges;
     // two-role slab path (series in HBM, one light curve; SearchPlan::split)
     View<unsigned int> d_tile_prefix;        // [n_periods + 1] tiles in front of work item w (queue order)
     DevBuf<double> d_partials;               // [split_max_items][3] a tile's winner
@@ -787,15 +791,17 @@ T0FitShape t0fit_shape(int64_t n) {
 // could close: its workgroups pass over the other fits).  Switch t0_rot = 0: the general kernel alone.  The general kernel's
 // `blocks` workgroups go through the fits one after the other: HBM scratch (series that do not fit the LDS) is one slab per
 // workgroup, max(blocks, n_fits) slabs in all (mode 1 has one workgroup per fit), whatever the number of fits.
+// d_curve: nullptr, or the curve of every fit (T0FitArgs::curve: several fits read one light curve's flux).
 int launch_t0_fit(tls_ctx* ctx, const double* d_t, const double* d_y, const double* d_signal, const double* d_epochs,
                   double* d_residuals, unsigned int* d_queue, int64_t n, double period, int64_t dur, int64_t n_epochs,
                   int64_t roll, double t_lo, double t_hi, const tlsdev::T0FitParams* d_params = nullptr, int64_t n_fits = 1,
-                  int64_t y_stride = 0, int64_t signal_stride = 0, int64_t epoch_stride = 0) {
+                  int64_t y_stride = 0, int64_t signal_stride = 0, int64_t epoch_stride = 0, const int* d_curve = nullptr) {
     tlsdev::T0FitArgs a;
     a.t = d_t; a.y = d_y; a.signal = d_signal; a.epochs = d_epochs;
     a.residuals = d_residuals; a.queue = d_queue; a.scratch = nullptr; a.scratch_stride = 0;
     a.period = period; a.n = (int)n; a.dur = (int)dur; a.roll = (int)(roll % n); a.n_epochs = (int)n_epochs;
     a.params = d_params; a.y_stride = y_stride; a.signal_stride = signal_stride; a.epoch_stride = epoch_stride;
+    a.curve = d_curve;
     a.n_fits = d_params ? (int)n_fits : 1;
     a.mode = 0; a.rot = nullptr; a.rot_perm = nullptr; a.rot_stride = 0; a.t_lo = t_lo; a.t_hi = t_hi;
     const T0FitShape shape = t0fit_shape(n);
@@ -869,6 +875,7 @@ struct PostSearchBufs {
     double* stats = nullptr;                   // tls_power_batch_stats: [group][16] | per-transit [group][6][max_epochs], behind T0
     double* per_transit = nullptr;             // ... the per-transit rows: behind the records, or behind the peaks where they are not copied out
     double* peaks = nullptr;                   // tls_power_batch_peaks: [group][1 + 6 k], behind what of the statistics is copied out
+    double* fits = nullptr;                    // tls_power_batch_peak_fits: T0 [group k] | status [group k] | records [group k][16], behind the peaks
     int64_t group = 0;
     int* n_epochs = nullptr;
     tlsdev::T0FitParams* fit = nullptr;
@@ -876,14 +883,15 @@ struct PostSearchBufs {
 
 // stats_words: doubles of the statistics stage per curve behind T0 (0: no statistics requested); peaks_words: of the peaks
 // behind the first stats_copied (<= stats_words: the records alone, or the per-transit rows too) of those -- sde | pick | T0 |
-// statistics copied out | peaks are ONE contiguous copy, per-transit rows nobody asked for stay behind it
+// statistics copied out | peaks | peak fits (fits_words doubles a curve, with peaks only) are ONE contiguous copy, per-transit
+// rows nobody asked for stay behind it
 int reserve_post_search(tls_ctx* ctx, int64_t group, int64_t n_periods, int64_t n, int64_t max_len, PostSearchBufs& b,
-                        size_t stats_words = 0, size_t peaks_words = 0, size_t stats_copied = 0) {
+                        size_t stats_words = 0, size_t peaks_words = 0, size_t stats_copied = 0, size_t fits_words = 0) {
     const size_t np = (size_t)n_periods, g = (size_t)group;
     b.max_len = std::max<int64_t>(max_len, 1);
     b.spec_stride = 3 * np;
     b.group = group;
-    TLS_HIP(ctx, ctx->d_spec.reserve(g * b.spec_stride + 2 * g + 8 * g + g + stats_words * g + peaks_words * g));
+    TLS_HIP(ctx, ctx->d_spec.reserve(g * b.spec_stride + 2 * g + 8 * g + g + stats_words * g + peaks_words * g + fits_words * g));
     b.sde = ctx->d_spec.ptr + g * b.spec_stride;
     b.pick = b.sde + 2 * g;
     b.T0 = b.pick + 8 * g;
@@ -892,7 +900,8 @@ int reserve_post_search(tls_ctx* ctx, int64_t group, int64_t n_periods, int64_t 
     if (peaks_words) {
         const bool rows_copied = stats_copied == stats_words;
         b.peaks = b.T0 + g + (rows_copied ? stats_words : (size_t)tlsdev::kTransitStats) * g;
-        if (stats_words && !rows_copied) b.per_transit = b.peaks + peaks_words * g;
+        if (fits_words) b.fits = b.peaks + peaks_words * g;
+        if (stats_words && !rows_copied) b.per_transit = b.peaks + (peaks_words + fits_words) * g;
     }
     b.fit_stride = (size_t)n;
     TLS_HIP(ctx, ctx->d_fep.reserve(g * b.fit_stride));
@@ -979,6 +988,7 @@ int enqueue_transit_stats(tls_ctx* ctx, const PostSearchBufs& b, const StatsBufs
     tlsdev::TransitStatsArgs a;
     a.t = ctx->d_t.ptr; a.y = d_y; a.pick = b.pick; a.T0 = b.T0;
     a.power = ctx->d_spec.ptr + 2 * (size_t)n_periods; a.power_stride = (long long)b.spec_stride;
+    a.curve = nullptr;
     a.periods = ctx->d_periods.ptr; a.n_periods = (int)n_periods;
     a.row_duration = sb.row_duration; a.root = sb.root; a.n_root = (int)sr.n_root;
     a.fill_factor = sr.fill_factor; a.t_min = t_min; a.t_max = t_max;
@@ -1008,8 +1018,9 @@ int read_transit_stats(tls_ctx* ctx, const StatsRequest& sr, const double* h_sta
 }
 
 // what the statistics stage requires beyond tls_power_batch's arguments
-int check_stats_request(tls_ctx* ctx, const StatsRequest& sr, const double* t, int64_t n, int64_t n_rows) {
-    if (!sr.row_duration || !sr.root || !sr.out) return fail(ctx, TLS_E_ARG, "null statistics argument");
+// (need_out false: the inputs alone, for the peak fits of a call that asks for no statistics of the best pick)
+int check_stats_request(tls_ctx* ctx, const StatsRequest& sr, const double* t, int64_t n, int64_t n_rows, bool need_out = true) {
+    if (!sr.row_duration || !sr.root || (need_out && !sr.out)) return fail(ctx, TLS_E_ARG, "null statistics argument");
     if (sr.n_rows != n_rows) return fail(ctx, TLS_E_ARG, "one fractional duration per template row wanted");
     if (sr.n_root < n + 1) return fail(ctx, TLS_E_ARG, "the k ** 0.5 table must cover k = 0 .. n");
     if (sr.max_epochs < 1 || sr.max_epochs > 100000000) return fail(ctx, TLS_E_ARG, "max_epochs out of range [1, 1e8]");
@@ -1189,6 +1200,133 @@ void read_peaks(const PeaksRequest& pr, const double* h, int64_t c, int64_t curv
     std::memcpy(&n_peaks, rec, 8);
     pr.out_n[curve] = n_peaks;
     std::memcpy(pr.out + (size_t)curve * (size_t)pr.k, rec + 1, (size_t)pr.k * sizeof(tls_peak));
+}
+
+// ---- the peak-fit stage (tls_power_batch_peak_fits; tls_debug_peak_fits feeds it injected peak records): the final T0 fit
+// and the statistics record of EVERY peak of a group, fits f = c k + r in slabs of kPeakFitSlab behind the group's peaks
+// kernel, on arrays of its own (tls_peak_fits.hip.h, DESIGN.md "Peak fits")
+struct PeakFitsRequest {
+    int64_t k = 0;
+    const StatsRequest* inputs = nullptr;      // row_duration, fill_factor, root, max_epochs (its outputs are not read)
+    tls_peak_fit* out = nullptr;               // [n_curves][k]
+    // tls_debug_peak_fits: every fit's trial epochs and residuals [n_curves][k][n], n_epochs [n_curves][k]
+    double* out_epochs = nullptr; double* out_residuals = nullptr; int64_t* out_n_epochs = nullptr;
+    size_t words() const { return (size_t)tlsdev::kPeakFitWords * (size_t)k; }
+};
+static_assert(sizeof(tls_peak_fit) == tlsdev::kPeakFitWords * 8, "tls_peak_fit is T0, status and the statistics record");
+
+struct PeakFitBufs {
+    double *pick = nullptr, *per_transit = nullptr, *signal = nullptr, *epochs = nullptr, *residuals = nullptr, *scratch = nullptr;
+    tlsdev::T0FitParams* fit = nullptr;
+    int *n_epochs = nullptr, *curve = nullptr, *ranges = nullptr;
+    size_t fit_stride = 0, scratch_stride = 0;
+    int64_t max_len = 1, slab = 1;
+};
+
+// the arrays of one slab of fits (device bytes: DESIGN.md "Peak fits" has the formula)
+int reserve_peak_fits(tls_ctx* ctx, int64_t fits_total, int64_t n, int64_t max_len, int64_t max_epochs, PeakFitBufs& fb) {
+    fb.slab = std::max<int64_t>(1, std::min<int64_t>(tlsdev::kPeakFitSlab, fits_total));
+    fb.max_len = std::max<int64_t>(max_len, 1);
+    fb.fit_stride = (size_t)n;
+    fb.scratch_stride = 4 * (size_t)n + 1;
+    const size_t s = (size_t)fb.slab, rows = (size_t)tlsdev::kPerTransitRows * (size_t)max_epochs;
+    TLS_HIP(ctx, ctx->d_pfit.reserve(8 * s + rows * s + (size_t)fb.max_len * s + 3 * s + s + s));
+    TLS_HIP(ctx, ctx->d_pfep.reserve(s * fb.fit_stride));
+    TLS_HIP(ctx, ctx->d_pfres.reserve(s * fb.fit_stride));
+    TLS_HIP(ctx, ctx->d_pfstats.reserve(s * fb.scratch_stride));
+    TLS_HIP(ctx, ctx->d_pfranges.reserve(s * 3 * (size_t)max_epochs));
+    fb.pick = ctx->d_pfit.ptr; fb.per_transit = fb.pick + 8 * s; fb.signal = fb.per_transit + rows * s;
+    fb.fit = reinterpret_cast<tlsdev::T0FitParams*>(fb.signal + (size_t)fb.max_len * s);
+    fb.n_epochs = reinterpret_cast<int*>(fb.signal + (size_t)fb.max_len * s + 3 * s);
+    fb.curve = reinterpret_cast<int*>(fb.signal + (size_t)fb.max_len * s + 4 * s);
+    fb.epochs = ctx->d_pfep.ptr; fb.residuals = ctx->d_pfres.ptr; fb.scratch = ctx->d_pfstats.ptr; fb.ranges = ctx->d_pfranges.ptr;
+    return TLS_OK;
+}
+
+// the fits of `gc` curves: d_peaks the group's peak records, d_y [gc][n] and d_power (stride power_stride) the curves' flux
+// and detrended power, sb the statistics inputs on the device; results into d_out = T0 [cap] | status [cap] | records
+// [cap][16], cap = group k.  Nothing waited for, unless the request wants the fits' epochs back (`first_curve`: the batch
+// index of the group's first curve in those arrays), which are copied slab by slab.
+int enqueue_peak_fits(tls_ctx* ctx, const PeakFitBufs& fb, const PeakFitsRequest& pf, const StatsBufs& sb, int64_t gc,
+                      int64_t group, const double* d_peaks, double* d_out, const double* d_y, const double* d_power,
+                      size_t power_stride, int64_t n, int64_t n_periods, double t_min, double t_max, double margin,
+                      int64_t first_curve = 0) {
+    const StatsRequest& in = *pf.inputs;
+    const int64_t total = gc * pf.k, cap = group * pf.k;
+    double* T0 = d_out; double* status = d_out + cap; double* stats = d_out + 2 * cap;
+    for (int64_t f0 = 0; f0 < total; f0 += fb.slab) {
+        const int64_t fits = std::min<int64_t>(fb.slab, total - f0);
+        tlsdev::PeakPicksArgs pa;
+        pa.peaks = reinterpret_cast<const unsigned long long*>(d_peaks);
+        pa.pick = fb.pick; pa.curve = fb.curve; pa.status = status + f0;
+        pa.k = (int)pf.k; pa.first = (int)f0; pa.fits = (int)fits;
+        hipLaunchKernelGGL(tlsdev::tls_peak_picks, dim3((unsigned)((fits + 255) / 256)), dim3(256), 0, ctx->stream, pa);
+        tlsdev::PrepArgs pr;
+        pr.pick = fb.pick; pr.widths = ctx->d_widths.ptr; pr.n_widths = ctx->plan.n_widths; pr.q = ctx->d_q.ptr;
+        pr.signal = fb.signal; pr.signal_stride = (long long)fb.max_len; pr.epochs = fb.epochs; pr.epoch_stride = (long long)fb.fit_stride;
+        pr.params = fb.fit; pr.n_epochs = fb.n_epochs; pr.t_min = t_min; pr.margin = margin; pr.n = (int)n;
+        hipLaunchKernelGGL(tlsdev::tls_power_prep, dim3((unsigned)fits), dim3(256), 0, ctx->stream, pr);
+        TLS_HIP(ctx, hipGetLastError());
+        int rc = launch_t0_fit(ctx, ctx->d_t.ptr, d_y, fb.signal, fb.epochs, fb.residuals, nullptr, n, 1.0, 0, 0, 0, t_min, t_max,
+                               fb.fit, fits, n, fb.max_len, (int64_t)fb.fit_stride, fb.curve);
+        if (rc) return rc;
+        tlsdev::FirstMinArgs fa;
+        fa.residuals = fb.residuals; fa.epochs = fb.epochs; fa.n_epochs = fb.n_epochs;
+        fa.T0 = T0 + f0; fa.stride = (long long)fb.fit_stride;
+        hipLaunchKernelGGL(tlsdev::tls_first_min, dim3((unsigned)fits), dim3(1024), 0, ctx->stream, fa);
+        tlsdev::TransitStatsArgs a;
+        a.t = ctx->d_t.ptr; a.y = d_y; a.pick = fb.pick; a.T0 = T0 + f0;
+        a.power = d_power; a.power_stride = (long long)power_stride; a.curve = fb.curve;
+        a.periods = ctx->d_periods.ptr; a.n_periods = (int)n_periods;
+        a.row_duration = sb.row_duration; a.root = sb.root; a.n_root = (int)in.n_root;
+        a.fill_factor = in.fill_factor; a.t_min = t_min; a.t_max = t_max;
+        a.stats = stats + (size_t)f0 * tlsdev::kTransitStats; a.per_transit = fb.per_transit;
+        a.ranges = fb.ranges; a.scratch = fb.scratch; a.scratch_stride = (long long)fb.scratch_stride;
+        a.n = (int)n; a.max_epochs = (int)in.max_epochs;
+        hipLaunchKernelGGL(tlsdev::tls_transit_stats, dim3((unsigned)fits), dim3(256), 0, ctx->stream, a);
+        TLS_HIP(ctx, hipGetLastError());
+        if (pf.out_epochs || pf.out_residuals || pf.out_n_epochs) {
+            // (the next slab overwrites these arrays: the copies are done before it is enqueued)
+            const size_t at = (size_t)(first_curve * pf.k + f0), bytes = (size_t)fits * fb.fit_stride * 8;
+            std::vector<int> nep((size_t)fits);
+            if (pf.out_epochs) TLS_HIP(ctx, hipMemcpyAsync(pf.out_epochs + at * fb.fit_stride, fb.epochs, bytes, hipMemcpyDeviceToHost, ctx->stream));
+            if (pf.out_residuals) TLS_HIP(ctx, hipMemcpyAsync(pf.out_residuals + at * fb.fit_stride, fb.residuals, bytes, hipMemcpyDeviceToHost, ctx->stream));
+            TLS_HIP(ctx, hipMemcpyAsync(nep.data(), fb.n_epochs, (size_t)fits * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+            TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            if (pf.out_n_epochs) for (int64_t l = 0; l < fits; ++l) pf.out_n_epochs[at + (size_t)l] = nep[(size_t)l];
+        }
+    }
+    return TLS_OK;
+}
+
+// the k fits of curve c from the group's host copy (enqueue_peak_fits' layout); TLS_E_ARG for a candidate whose row starts
+// no template duration (tls_power_prep's finding) or that has more than max_epochs epochs, as the main chain reports its pick
+int read_peak_fits(tls_ctx* ctx, const PeakFitsRequest& pf, const double* h, int64_t group, int64_t c, int64_t curve) {
+    const size_t cap = (size_t)group * (size_t)pf.k;
+    for (int64_t r = 0; r < pf.k; ++r) {
+        const size_t f = (size_t)(c * pf.k + r);
+        const double status = h[cap + f];
+        const double* rec = h + 2 * cap + f * (size_t)tlsdev::kTransitStats;
+        const std::string who = "peak " + std::to_string((long long)r) + " of light curve " + std::to_string((long long)curve);
+        // (tls_power_prep found no template width starting at the row and raised the pick's [7]: the statistics kernel left
+        // the record of a pick without fit)
+        if (status == tlsdev::kPeakFitted && std::isnan(rec[10]))
+            return fail(ctx, TLS_E_ARG, "the template row of " + who + " is not the first row of a duration");
+        tls_peak_fit& o = pf.out[(size_t)curve * (size_t)pf.k + (size_t)r];
+        o.status = status;
+        if (status != tlsdev::kPeakFitted) {
+            double* d = reinterpret_cast<double*>(&o.stats);
+            o.T0 = std::nan("");
+            std::fill(d, d + tlsdev::kTransitStats, std::nan(""));
+            continue;
+        }
+        if (rec[10] > (double)pf.inputs->max_epochs)
+            return fail(ctx, TLS_E_ARG, who + " has more than max_epochs = " + std::to_string((long long)pf.inputs->max_epochs) +
+                                        " transit epochs");
+        o.T0 = h[f];
+        std::memcpy(&o.stats, rec, sizeof(tls_transit_stats));
+    }
+    return TLS_OK;
 }
 
 // the summary of curve c from the chain's results on the host (sde | pick | T0 of `group` curves, as reserve_post_search
@@ -1442,6 +1580,7 @@ void tls_ctx_destroy(tls_ctx* ctx) {
     ctx->d_ft.release(); ctx->d_fy.release(); ctx->d_fsig.release(); ctx->d_fep.release(); ctx->d_fres.release(); ctx->d_fscratch.release(); ctx->d_frot.release(); ctx->d_frperm.release(); ctx->d_pink.release();
     ctx->d_tstats.release(); ctx->d_tranges.release(); ctx->d_models.release(); ctx->d_inject.release(); ctx->d_inject_count.release();
     ctx->d_null.release(); ctx->d_null_words.release(); ctx->d_detrend.release(); ctx->d_windows.release(); ctx->d_peaks.release(); ctx->d_peak_mask.release();
+    ctx->d_pfit.release(); ctx->d_pfep.release(); ctx->d_pfres.release(); ctx->d_pfstats.release(); ctx->d_pfranges.release();
     ctx->d_split.release(); ctx->d_park.release(); ctx->d_band.release();
     if (ctx->h_band) (void)hipHostFree(ctx->h_band);
     for (auto& ev : ctx->ev_band) if (ev) (void)hipEventDestroy(ev);
@@ -2401,6 +2540,67 @@ int tls_debug_transit_models(tls_ctx* ctx, const double* y, int64_t n_curves, co
                               fill_factor, root, n_root, max_epochs, out_stats, out_per_transit, out_n_epochs, &mr);
 }
 
+int tls_debug_peak_fits(tls_ctx* ctx, const double* y, int64_t n_curves, const tls_peak* peaks, const int64_t* n_peaks,
+                        int64_t k, const double* power, const double* row_duration, int64_t n_rows, double fill_factor,
+                        const double* root, int64_t n_root, int64_t max_epochs, tls_peak_fit* out_fits, double* out_epochs,
+                        double* out_residuals, int64_t* out_n_epochs) {
+    if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
+    if (!ctx->prepared || !ctx->key.valid) return fail(ctx, TLS_E_STATE, "tls_debug_peak_fits before tls_prepare");
+    if (!y || !peaks || !n_peaks || !power || !out_fits) return fail(ctx, TLS_E_ARG, "null argument");
+    if (n_curves < 1 || n_curves > 1024) return fail(ctx, TLS_E_ARG, "n_curves out of range [1, 1024]");
+    if (k < 1 || k > TLS_PEAKS_MAX_K) return fail(ctx, TLS_E_ARG, "peaks: k out of range [1, 32]");
+    TLS_HIP(ctx, hipSetDevice(ctx->device));
+    const PlanKey& key = ctx->key;
+    const int64_t n = key.n, n_periods = key.n_periods;
+    if (n_periods < 1) return fail(ctx, TLS_E_ARG, "tls_debug_peak_fits needs at least one period");
+    const StatsRequest sr = stats_request(row_duration, n_rows, fill_factor, root, n_root, max_epochs, nullptr, nullptr, nullptr);
+    int rc = check_stats_request(ctx, sr, key.t.data(), n, key.n_rows, false);
+    if (rc) return rc;
+    const size_t np = (size_t)n_periods, nn = (size_t)n, gc = (size_t)n_curves, kk = (size_t)k;
+    PeaksRequest pk;
+    pk.k = k;
+    // the records as tls_find_peaks leaves them: n_peaks | k records of six words
+    std::vector<unsigned long long> rec(gc * pk.words());
+    for (size_t c = 0; c < gc; ++c) {
+        if (n_peaks[c] < 0 || n_peaks[c] > k) return fail(ctx, TLS_E_ARG, "n_peaks out of range [0, k]");
+        for (int64_t r = 0; r < n_peaks[c]; ++r) {
+            const tls_peak& p = peaks[c * kk + (size_t)r];
+            if (p.index < 0 || p.index >= n_periods) return fail(ctx, TLS_E_ARG, "peak index out of range");
+            if (p.row < -1 || p.row >= n_rows) return fail(ctx, TLS_E_ARG, "peak row out of range");
+        }
+        rec[c * pk.words()] = (unsigned long long)n_peaks[c];
+        std::memcpy(&rec[c * pk.words() + 1], peaks + c * kk, kk * sizeof(tls_peak));
+    }
+    const double t_min = *std::min_element(key.t.begin(), key.t.end()), t_max = *std::max_element(key.t.begin(), key.t.end());
+    const int64_t max_len = *std::max_element(key.length.begin(), key.length.end());
+    PeakFitsRequest pf;
+    pf.k = k; pf.inputs = &sr; pf.out = out_fits;
+    pf.out_epochs = out_epochs; pf.out_residuals = out_residuals; pf.out_n_epochs = out_n_epochs;
+    auto& sl = ctx->slot[0];
+    TLS_HIP(ctx, sl.d_y.reserve(gc * nn));
+    PostSearchBufs pb;
+    if ((rc = reserve_post_search(ctx, n_curves, n_periods, n, max_len, pb, 0, pk.words(), 0, pf.words()))) return rc;
+    StatsBufs sb;
+    if ((rc = reserve_transit_stats(ctx, sr, 0, n, sb))) return rc;
+    PeakFitBufs fb;
+    if ((rc = reserve_peak_fits(ctx, n_curves * k, n, max_len, max_epochs, fb))) return rc;
+    TLS_HIP(ctx, hipMemcpyAsync(sl.d_y.ptr, y, gc * nn * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpy2DAsync(ctx->d_spec.ptr + 2 * np, pb.spec_stride * 8, power, np * 8, np * 8, gc, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(pb.peaks, rec.data(), rec.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = enqueue_peak_fits(ctx, fb, pf, sb, n_curves, n_curves, pb.peaks, pb.fits, sl.d_y.ptr, ctx->d_spec.ptr + 2 * np,
+                                pb.spec_stride, n, n_periods, t_min, t_max, key.params.T0_fit_margin))) {
+        (void)hipStreamSynchronize(ctx->stream);
+        return rc;
+    }
+    std::vector<double> h(gc * pf.words());
+    TLS_HIP(ctx, hipMemcpyAsync(h.data(), pb.fits, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->executed = false;   // (the batch slot's buffers were written: as after tls_power_batch)
+    for (int64_t c = 0; c < n_curves; ++c)
+        if ((rc = read_peak_fits(ctx, pf, h.data(), n_curves, c, c))) return rc;
+    return TLS_OK;
+}
+
 int tls_debug_device_bytes(const tls_ctx* ctx, int64_t* total, int64_t* t0_fit_scratch) {
     if (!ctx || !total || !t0_fit_scratch) return TLS_E_ARG;
     size_t sum = 0;
@@ -2416,6 +2616,7 @@ int tls_debug_device_bytes(const tls_ctx* ctx, int64_t* total, int64_t* t0_fit_s
     add(ctx->d_ft); add(ctx->d_fy); add(ctx->d_fsig); add(ctx->d_fep); add(ctx->d_fres); add(ctx->d_fscratch);
     add(ctx->d_pink); add(ctx->d_frot); add(ctx->d_frperm); add(ctx->d_spec); add(ctx->d_tstats); add(ctx->d_tranges); add(ctx->d_models);
     add(ctx->d_peaks); add(ctx->d_peak_mask);
+    add(ctx->d_pfit); add(ctx->d_pfep); add(ctx->d_pfres); add(ctx->d_pfstats); add(ctx->d_pfranges);
     add(ctx->d_partials); add(ctx->d_tiles_done);
     add(ctx->d_split); add(ctx->d_park); add(ctx->d_band);
     *total = (int64_t)sum;
@@ -2616,7 +2817,8 @@ static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, cons
                             const double* periods, int64_t n_periods, const tls_template* tmpl, const tls_params* params,
                             int64_t median_kernel, tls_power_summary* out_summary, double* out_chi2, int64_t* out_row,
                             double* out_depth, double* out_power, double* out_SR, double* out_power_raw,
-                            const StatsRequest* sr, const ModelsRequest* mr = nullptr, const PeaksRequest* pk = nullptr);
+                            const StatsRequest* sr, const ModelsRequest* mr = nullptr, const PeaksRequest* pk = nullptr,
+                            const PeakFitsRequest* pf = nullptr);
 
 int tls_power_batch(tls_ctx* ctx, const double* t, const double* y, const double* dy, int64_t n, int64_t n_curves,
                     const double* periods, int64_t n_periods, const tls_template* tmpl, const tls_params* params,
@@ -2690,6 +2892,33 @@ int tls_power_batch_peaks(tls_ctx* ctx, const double* t, const double* y, const 
                                            out_stats ? &sr : nullptr, nullptr, &pk));
 }
 
+int tls_power_batch_peak_fits(tls_ctx* ctx, const double* t, const double* y, const double* dy, int64_t n, int64_t n_curves,
+                              const double* periods, int64_t n_periods, const tls_template* tmpl, const tls_params* params,
+                              int64_t median_kernel, tls_power_summary* out_summary, double* out_chi2, int64_t* out_row,
+                              double* out_depth, double* out_power, double* out_SR, double* out_power_raw,
+                              const double* row_duration, double fill_factor, const double* root, int64_t n_root,
+                              tls_transit_stats* out_stats, int64_t max_epochs, double* out_per_transit, int64_t* out_n_epochs,
+                              int64_t k, double min_separation, const double* ratios, int64_t n_ratios, double min_power,
+                              tls_peak* out_peaks, int64_t* out_n_peaks, tls_peak_fit* out_fits) {
+    if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
+    if (!t || !tmpl) return fail(ctx, TLS_E_ARG, "null argument");
+    PeaksRequest pk;
+    pk.k = k; pk.sep = min_separation; pk.ratios = ratios; pk.n_ratios = n_ratios; pk.min_power = min_power;
+    pk.out = out_peaks; pk.out_n = out_n_peaks;
+    int rc = check_peaks_request(ctx, pk, n_periods);
+    if (rc) return rc;
+    if (n_curves > 0 && (!out_peaks || !out_n_peaks || !out_fits)) return fail(ctx, TLS_E_ARG, "null peaks argument");
+    // (the fits read the statistics inputs whether or not the best pick's statistics are wanted)
+    const StatsRequest sr = stats_request(row_duration, tmpl->n_rows, fill_factor, root, n_root, max_epochs, out_stats,
+                                          out_stats ? out_per_transit : nullptr, out_stats ? out_n_epochs : nullptr);
+    if ((rc = check_stats_request(ctx, sr, t, n, tmpl->n_rows, false))) return rc;
+    PeakFitsRequest pf;
+    pf.k = k; pf.inputs = &sr; pf.out = out_fits;
+    return end_batch(ctx, power_batch_impl(ctx, t, y, dy, n, n_curves, periods, n_periods, tmpl, params, median_kernel,
+                                           out_summary, out_chi2, out_row, out_depth, out_power, out_SR, out_power_raw,
+                                           out_stats ? &sr : nullptr, nullptr, &pk, &pf));
+}
+
 int tls_find_peaks(tls_ctx* ctx, const double* power, const double* chi2, const int64_t* row, const double* depth,
                    int64_t n_rows, int64_t n_periods, const double* periods, int64_t k, double min_separation,
                    const double* ratios, int64_t n_ratios, double min_power, tls_peak* out_peaks, int64_t* out_n_peaks) {
@@ -2744,7 +2973,7 @@ static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, cons
                             const double* periods, int64_t n_periods, const tls_template* tmpl, const tls_params* params,
                             int64_t median_kernel, tls_power_summary* out_summary, double* out_chi2, int64_t* out_row,
                             double* out_depth, double* out_power, double* out_SR, double* out_power_raw,
-                            const StatsRequest* sr, const ModelsRequest* mr, const PeaksRequest* pk) {
+                            const StatsRequest* sr, const ModelsRequest* mr, const PeaksRequest* pk, const PeakFitsRequest* pf) {
     if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
     if (n_curves < 0) return fail(ctx, TLS_E_ARG, "negative number of light curves");
     if (n_curves == 0) return TLS_OK;
@@ -2769,11 +2998,17 @@ static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, cons
     // peaks requested: their records lie behind those and ride in it too)
     const size_t stats_out = !sr ? 0 : sr->out_per_transit ? sr->words() : (size_t)tlsdev::kTransitStats;
     const size_t peaks_out = pk ? pk->words() : 0;
+    // (peak fits requested, with peaks only: T0, status and record of every peak, behind the peaks, in the same copy)
+    const size_t fits_out = pf ? pf->words() : 0;
     PostSearchBufs pb;
-    if ((rc = reserve_post_search(ctx, group, n_periods, n, max_len, pb, sr ? sr->words() : 0, peaks_out, stats_out))) return rc;
+    if ((rc = reserve_post_search(ctx, group, n_periods, n, max_len, pb, sr ? sr->words() : 0, peaks_out, stats_out, fits_out))) return rc;
     const size_t spec_stride = pb.spec_stride;
     StatsBufs sb;
     if (sr && (rc = reserve_transit_stats(ctx, *sr, group, n, sb))) return rc;
+    // (no statistics of the best pick: the peak fits still read the row durations and the root table on the device)
+    if (pf && !sr && (rc = reserve_transit_stats(ctx, *pf->inputs, 0, n, sb))) return rc;
+    PeakFitBufs fb;
+    if (pf && (rc = reserve_peak_fits(ctx, group * pf->k, n, max_len, pf->inputs->max_epochs, fb))) return rc;
     if (pk && (rc = reserve_peak_mask(ctx, group, n_periods))) return rc;
     // (models requested: the folded light curve, the folded model and the padded model light curve of every curve, behind them)
     ModelsBufs mb;
@@ -2783,20 +3018,21 @@ static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, cons
     // one: the stream runs the groups in order): while the device works on group g the host forms group g + 1 in the other
     // set and enqueues it, THEN waits for g -- the device never waits for the host between two groups (round 6)
     const size_t arrays = (out_chi2 ? 3 : 0) + (out_power ? 1 : 0) + (out_SR ? 1 : 0) + (out_power_raw ? 1 : 0);
-    const size_t out_doubles = (11 + stats_out + peaks_out + models_out) * (size_t)group + arrays * (size_t)group * np;
+    const size_t out_doubles = (11 + stats_out + peaks_out + fits_out + models_out) * (size_t)group + arrays * (size_t)group * np;
     if ((rc = reserve_batch_staging(ctx, group, nn, out_doubles))) return rc;
     const int64_t n_groups = (n_curves + group - 1) / group;
     ctx->batch_group_ms.assign((size_t)n_groups, 0.0);
     ctx->batch_group_wait_ms.assign((size_t)n_groups, 0.0);
     // host layout of a group's results (the same in both sets)
-    struct OutLayout { double *sde, *pick, *T0, *stats, *peaks, *chi2, *power, *SR, *praw, *spec3, *models; };
+    struct OutLayout { double *sde, *pick, *T0, *stats, *peaks, *fits, *chi2, *power, *SR, *praw, *spec3, *models; };
     auto out_layout = [&](int64_t g) -> OutLayout {
         OutLayout o{};
         double* base = ctx->slot[g & 1].h_out;
         o.sde = base; o.pick = o.sde + 2 * (size_t)group; o.T0 = o.pick + 8 * (size_t)group;
         o.stats = o.T0 + group;                          // statistics records (and rows), on request
         o.peaks = o.stats + stats_out * (size_t)group;   // peak records, on request
-        double* h_next = o.peaks + peaks_out * (size_t)group;   // chi2 | row | depth | power | SR | power_raw, on request
+        o.fits = o.peaks + peaks_out * (size_t)group;    // peak fits, on request
+        double* h_next = o.fits + fits_out * (size_t)group;     // chi2 | row | depth | power | SR | power_raw, on request
         if (out_chi2) { o.chi2 = h_next; h_next += 3 * (size_t)group * np; }
         if (out_power && out_SR && out_power_raw) { o.spec3 = h_next; h_next += 3 * (size_t)group * np; }
         else {
@@ -2823,10 +3059,13 @@ static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, cons
         if (pk && (rc2 = enqueue_find_peaks(ctx, *pk, gc, n_periods, ctx->d_spec.ptr + 2 * np, spec_stride, ctx->d_periods.ptr,
                                             sl.d_chi2.ptr, sl.d_row.ptr, sl.d_depth.ptr, pb.pick, pb.peaks))) return rc2;
         if (sr && (rc2 = enqueue_transit_stats(ctx, pb, sb, *sr, gc, sl.d_y.ptr, n, n_periods, t_min, t_max))) return rc2;
+        // (every peak's T0 fit and record, on the stage's own arrays: pick, T0 and statistics of the best pick stay as they are)
+        if (pf && (rc2 = enqueue_peak_fits(ctx, fb, *pf, sb, gc, group, pb.peaks, pb.fits, sl.d_y.ptr, ctx->d_spec.ptr + 2 * np,
+                                           spec_stride, n, n_periods, t_min, t_max, params->T0_fit_margin))) return rc2;
         if (mr && (rc2 = enqueue_transit_models(ctx, pb, sb, *sr, *mr, mb, gc, sl.d_y.ptr, n, t_min, t_max))) return rc2;
-        // (sde | pick | T0 [| statistics] [| peaks] lie side by side behind the spectra on the device: ONE copy, the host keeps the layout)
+        // (sde | pick | T0 [| statistics] [| peaks [| peak fits]] lie side by side behind the spectra on the device: ONE copy, the host keeps the layout)
         const OutLayout o = out_layout(g);
-        TLS_HIP(ctx, hipMemcpyAsync(o.sde, pb.sde, (11 + stats_out + peaks_out) * (size_t)group * 8, hipMemcpyDeviceToHost, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(o.sde, pb.sde, (11 + stats_out + peaks_out + fits_out) * (size_t)group * 8, hipMemcpyDeviceToHost, ctx->stream));
         if (out_chi2) {
             TLS_HIP(ctx, hipMemcpyAsync(o.chi2, sl.d_chi2.ptr, (size_t)gc * np * 8, hipMemcpyDeviceToHost, ctx->stream));
             TLS_HIP(ctx, hipMemcpyAsync(o.chi2 + (size_t)group * np, sl.d_row.ptr, (size_t)gc * np * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -2869,6 +3108,11 @@ static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, cons
             }
         if (pk)
             for (int64_t c = 0; c < gc; ++c) read_peaks(*pk, o.peaks, c, c0 + c);
+        if (pf)
+            for (int64_t c = 0; c < gc; ++c) {
+                const int rc2 = read_peak_fits(ctx, *pf, o.fits, group, c, c0 + c);
+                if (rc2) return rc2;
+            }
         if (out_chi2) {
             std::memcpy(out_chi2 + c0 * n_periods, o.chi2, (size_t)gc * np * 8);
             std::memcpy(out_row + c0 * n_periods, o.chi2 + (size_t)group * np, (size_t)gc * np * 8);

@@ -3124,6 +3124,9 @@ struct T0FitArgs {
     // signal + c * signal_stride, epochs / residuals + c * epoch_stride.  nullptr: one fit, the scalars above.
     const struct T0FitParams* params;
     long long y_stride, signal_stride, epoch_stride;
+    // curve of fit: nullptr, or fit c reads the flux of curve curve[c] (y + curve[c] * y_stride) -- several fits of one light
+    // curve (the peak-fit stage, tls_peak_fits.hip.h); signals, epochs and residuals stay per fit.  nullptr: curve c, as ever.
+    const int* curve;
     // Rotation path (round 6; tls_t0fit_rot below).  mode 0: every epoch of every fit in this kernel (the original form).
     // mode 1 ("base"): one workgroup per fit sorts the fit's FIRST epoch and leaves, per fit, in `rot` (rot_stride doubles a
     // fit): the flux in that order Fb[n] | the phases phb[n] | the out-of-transit quotients c[n] | state[4] = (sum of c,
@@ -3146,7 +3149,7 @@ __device__ __forceinline__ void t0fit_one(const T0FitArgs& a0, long long c) {
     if (a0.params != nullptr) {
         const T0FitParams fp = a0.params[c];
         a.period = fp.period; a.dur = fp.dur; a.roll = fp.roll; a.n_epochs = fp.n_epochs;
-        a.y = a0.y + c * a0.y_stride; a.signal = a0.signal + c * a0.signal_stride;
+        a.y = a0.y + (a0.curve ? (long long)a0.curve[c] : c) * a0.y_stride; a.signal = a0.signal + c * a0.signal_stride;
         a.epochs = a0.epochs + c * a0.epoch_stride; a.residuals = a0.residuals + c * a0.epoch_stride;
         if ((int)blockIdx.x >= a.n_epochs) return;
     }
@@ -3744,7 +3747,7 @@ __device__ __forceinline__ double numpy_pairwise_leaf(const At& at, int lo, int 
 // (numpy recurses; here the frames sit in a fixed array -- a run is at least halved per level, 28 levels cover 2^31 elements --
 // so the kernel needs no dynamic stack)
 template <typename At>
-__device__ double numpy_pairwise_sum(const At& at, int lo0, int n0) {
+__device__ double numpy_pairwise_block(const At& at, int lo0, int n0) {
     constexpr int kDepth = 28;
     int f_lo[kDepth], f_n[kDepth], f_stage[kDepth];
     double f_left[kDepth];
@@ -3768,6 +3771,22 @@ __device__ double numpy_pairwise_sum(const At& at, int lo0, int n0) {
         }
     }
     return ret;
+}
+// numpy.add.reduce of a contiguous array: the reduction's buffer holds 8192 elements, so pairwise_sum gets the array 8192
+// elements a call and the calls' sums are added from the left -- one pairwise sum up to 8192 elements, not beyond (the flux
+// out of transit of a series longer than that, whose std the SNR divides by)
+constexpr int kNumpyBufferSize = 8192;
+template <typename At>
+__device__ double numpy_pairwise_sum(const At& at, int lo0, int n0) {
+    double acc = 0.0;
+    int done = 0;
+    do {
+        const int m = n0 - done < kNumpyBufferSize ? n0 - done : kNumpyBufferSize;
+        const double block = numpy_pairwise_block(at, lo0 + done, m);
+        acc = done == 0 ? block : acc + block;
+        done += m;
+    } while (done < n0);
+    return acc;
 }
 __global__ void __launch_bounds__(256) tls_pink_terms(const double* data, int n_windows, int width, double root_width, double* terms) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -3802,6 +3821,7 @@ struct TransitStatsArgs {
     const double* t; const double* y;              // [n] ascending, [n_curves][n]
     const double* pick; const double* T0;          // [n_curves][8] (tls_power_pick), [n_curves] (tls_first_min)
     const double* power; long long power_stride;   // detrended power of curve c at power + c * power_stride
+    const int* curve;                              // nullptr, or record c reads flux and power of curve curve[c] (the peak-fit stage)
     const double* periods; int n_periods;
     const double* row_duration;                    // lc_cache_overview["duration"] of every template row
     const double* root; int n_root;                // root[k] = float(k) ** 0.5
@@ -3851,8 +3871,9 @@ __global__ void __launch_bounds__(256) tls_transit_stats(const TransitStatsArgs 
     const int tid = threadIdx.x, nt = blockDim.x, n = a.n, maxE = a.max_epochs;
     const int lane = tid & (kWave - 1), wave = tid / kWave, nw = nt / kWave;
     const long long c = blockIdx.x;
+    const long long cc = a.curve ? (long long)a.curve[c] : c;   // (the curve whose flux and power record c reads)
     const double* t = a.t;
-    const double* y = a.y + c * n;
+    const double* y = a.y + cc * n;
     const double* pk = a.pick + 8 * c;
     double* st = a.stats + c * kTransitStats;
     double* times = a.per_transit + c * (long long)kPerTransitRows * maxE;
@@ -3863,7 +3884,7 @@ __global__ void __launch_bounds__(256) tls_transit_stats(const TransitStatsArgs 
     if (tid == 0) {
         const bool flat = pk[6] != 0.0 || pk[7] != 0.0;
         const double period = pk[3], T0 = a.T0[c];
-        st[0] = period_uncertainty_walk(a.power + c * a.power_stride, a.periods, a.n_periods, flat ? 0 : (int)pk[2], flat);
+        st[0] = period_uncertainty_walk(a.power + cc * a.power_stride, a.periods, a.n_periods, flat ? 0 : (int)pk[2], flat);
         int mode = flat ? 1 : 0, E = 0;
         double d = NAN, dur = NAN;
         if (!flat) {
@@ -4275,5 +4296,6 @@ __global__ void __launch_bounds__(512) tls_transit_models(const ModelsArgs a) {
 
 // survey-mode periodogram peaks (tls_find_peaks, tls_power_batch_peaks)
 #include "tls_peaks.hip.h"
+#include "tls_peak_fits.hip.h"
 
 }  // namespace tlsdev

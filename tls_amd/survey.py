@@ -237,7 +237,7 @@ HARMONICS = (0.5, 2.0, 1 / 3, 3.0, 2 / 3, 1.5)
 
 def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_arrays=False, devices=None, statistics=False,
                 per_transit=False, models=False, detrend=None, peaks=None, peak_separation=0.02, peak_ratios=HARMONICS,
-                peak_min_power=None, **power_kwargs):
+                peak_min_power=None, peak_fits=False, **power_kwargs):
     """Survey-mode power(): for every light curve of `flux_batch` what `transitleastsquares(t, flux).power(**kwargs)`
     reports as SDE, SDE_raw, chi2_min, period, T0, depth and duration (fractional, lc_cache_overview["duration"] of
     the template row at the chi^2 minimum, main.py:199-200) -- search, SDE spectra and final T0 fit all on the
@@ -273,20 +273,35 @@ def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_ar
     numpy restatement): candidates are the local maxima of the power at or above peak_min_power (None: all); the highest
     one alive is taken (the lowest index among equals, so the first peak is index_power) and every candidate within
     peak_separation * r * P of r * P leaves, for the taken period P, r = 1 and every r of peak_ratios -- by default
-    HARMONICS, without which ranks 2 to 4 of a strong planet are its own harmonics.  The final T0 fit stays the best
-    pick's: search a narrow period window around a peak for its epoch.  peaks combines with with_arrays, statistics,
-    per_transit, detrend and devices; peaks with models=True raises ValueError (no entry point carries both).  Bad peak
-    arguments raise ValueError before any device work.
+    HARMONICS, without which ranks 2 to 4 of a strong planet are its own harmonics.  peaks combines with with_arrays,
+    statistics, per_transit, detrend and devices; peaks with models=True raises ValueError (no entry point carries both).
+    Bad peak arguments raise ValueError before any device work.
+
+    peak_fits=True (with peaks=K; needs ascending t) gives every peak what the one pick has: the final T0 fit and the
+    vetting statistics, on the device behind the group's peaks (tls_power_batch_peak_fits), 144 bytes more per peak in the
+    same copy.  The `peaks` array gains T0, status (0 fitted; 1 no such peak; 2 the search fitted nothing at the index), every
+    field of tls_transit_stats (duration_days, snr, odd_even_mismatch, depth_mean_odd / _even, the counts, ...) and rp_rs;
+    all NaN where status != 0.  A candidate takes period, depth AND template row from its own index (the pick takes its row
+    from argmin(chi2)), and its period uncertainty is walked from its own index: rank 0 equals the summary's T0 and statistics
+    wherever index_best == index_power.  Summary, statistics and the other peak fields do not change.  peak_fits without
+    peaks, or with models=True, raises ValueError before any device work.
 
     Returns (summary, periods[, chi2, row, depth, power][, per_transit][, models][, peaks]): summary is a numpy structured
     array with the fields of tls_power_summary plus "duration" (and the statistics on request)."""
     return _power_batch(t, flux_batch, dy_batch, power_kwargs, context=context, device=device, devices=devices,
                         with_arrays=with_arrays, statistics=statistics, per_transit=per_transit, models=models,
-                        detrend=detrend, peaks=_peaks_request(peaks, peak_separation, peak_ratios, peak_min_power, models))
+                        detrend=detrend, peaks=_peaks_request(peaks, peak_separation, peak_ratios, peak_min_power, models,
+                                                              peak_fits),
+                        peak_fits=bool(peak_fits))
 
 
-def _peaks_request(peaks, separation, ratios, min_power, models=False):
-    """None, or the checked (k, separation, ratios, min_power) of a peaks=K request (ValueError for a bad one)."""
+def _peaks_request(peaks, separation, ratios, min_power, models=False, peak_fits=False):
+    """None, or the checked (k, separation, ratios, min_power) of a peaks=K request (ValueError for a bad one, and for
+    peak_fits without peaks or with models)."""
+    if peak_fits and peaks is None:
+        raise ValueError("peak_fits=True needs peaks=K: the fits are those of the peaks")
+    if peak_fits and models:
+        raise ValueError("peak_fits cannot be combined with models=True: no entry point carries both")
     if peaks is None:
         return None
     from ._lib import peaks_arguments
@@ -305,6 +320,27 @@ def _with_duration(peaks, duration):
     out["duration"] = numpy.nan
     if duration is not None:
         out["duration"][known] = numpy.asarray(duration, dtype=numpy.float64)[peaks["row"][known]]
+    return out
+
+
+def peak_fit_fields():
+    """The fields power_batch(peaks=K, peak_fits=True) adds to the `peaks` array, in order: T0, status, the fields of
+    tls_transit_stats, rp_rs."""
+    from ._lib import TRANSIT_STATS_FIELDS
+    return ("T0", "status") + tuple(TRANSIT_STATS_FIELDS) + ("rp_rs",)
+
+
+def _with_fits(peaks, fits, factor):
+    """The peaks (with duration) plus the device's fit records and rp_rs: rp_rs_from_depth(1 - depth) of the candidate's
+    depth, formed as the summary's (numpy's scalar ** 0.5), NaN where nothing was fitted."""
+    out = numpy.zeros(peaks.shape, dtype=peaks.dtype.descr + [(k, "f8") for k in peak_fit_fields()])
+    for k in peaks.dtype.names:
+        out[k] = peaks[k]
+    for k in fits.dtype.names:
+        out[k] = fits[k]
+    fit = fits["status"] == 0
+    out["rp_rs"] = numpy.nan
+    out["rp_rs"][fit] = [x ** (1 / 2) for x in (1 - peaks["depth"][fit]) * factor]
     return out
 
 
@@ -343,16 +379,17 @@ def find_peaks(power, periods, k, separation=0.02, ratios=HARMONICS, min_power=N
 
 
 def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=None, devices=None, with_arrays=False,
-                 statistics=False, per_transit=False, models=False, spectra=False, detrend=None, peaks=None):
+                 statistics=False, per_transit=False, models=False, spectra=False, detrend=None, peaks=None,
+                 peak_fits=False):
     """power_batch; spectra=True (power_results) also returns SR and power_raw [n_curves, n_periods] behind the arrays;
-    peaks: None or a checked request (_peaks_request)."""
+    peaks: None or a checked request (_peaks_request); peak_fits: with peaks, their T0 fits and statistics."""
     models = bool(models)
     per_transit = bool(per_transit or models)
     statistics = bool(statistics or per_transit)
-    if statistics:
+    if statistics or peak_fits:
         t_check = numpy.asarray(t, dtype=numpy.float64)
         if t_check.ndim != 1 or not numpy.all(t_check[1:] >= t_check[:-1]):
-            raise ValueError("statistics=True needs ascending time stamps t")
+            raise ValueError("%s=True needs ascending time stamps t" % ("statistics" if statistics else "peak_fits"))
     flux_batch = _detrended(t, flux_batch, detrend, context, device, devices)
     inp, y_rows, dy_rows = _batch_inputs(t, flux_batch, dy_batch, power_kwargs)
     from . import constants as C
@@ -361,13 +398,16 @@ def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=Non
     if kernel != int(kernel):
         raise ValueError("oversampling_factor * %d must be an integer" % C.SDE_MEDIAN_KERNEL_SIZE)
     kw = dict(with_arrays=with_arrays, with_power=with_arrays, with_spectra=spectra, peaks=peaks)
-    if statistics:
+    if statistics or peak_fits:
         from .stats import calculate_fill_factor
         fill_factor = calculate_fill_factor(inp["t"])
         root = numpy.array([float(k) ** 0.5 for k in range(len(inp["t"]) + 1)])   # (Python's pow, as power() forms k ** 0.5)
         max_epochs = _max_epochs(inp["t"], inp["periods"])
+    if statistics:
         kw.update(statistics=(fill_factor, root, max_epochs), per_transit=per_transit,
                   models=_model_template(inp) if models else None, lc_cap=_lc_cap(len(inp["t"]), max_epochs) if models else 0)
+    if peak_fits:
+        kw.update(peak_fits=(fill_factor, root, max_epochs))
 
     def call(ctx, lo, hi):
         return ctx._power_batch(inp["t"], y_rows[lo:hi], dy_rows[lo:hi], inp["periods"], inp["table"], inp["params"],
@@ -416,7 +456,11 @@ def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=Non
         m["folded_dy"][no_fit] = numpy.nan
         result += (m,)
     if peaks is not None:
-        result += (dict(peaks=_with_duration(out["peaks"], inp["table"].duration), n_peaks=out["n_peaks"]),)
+        records = _with_duration(out["peaks"], inp["table"].duration)
+        if peak_fits:
+            from .stats import limb_darkening_factor
+            records = _with_fits(records, out["peak_fits"], limb_darkening_factor(inp["limb_dark"], inp["u"]))
+        result += (dict(peaks=records, n_peaks=out["n_peaks"]),)
     if spectra:
         result += (out["SR"], out["power_raw"])
     return result
