@@ -37,7 +37,8 @@ extern "C" {
  * tls_debug_transit_models).  A binding compares it with tls_abi_version().  Entries added without changing a layout or
  * signature keep the version (7: tls_inject_transits, tls_null_rows, tls_debug_null_words,
  * tls_medfilt_detrend, tls_biweight_detrend), (7: tls_power_batch_peaks, tls_find_peaks),
- * (7: tls_power_batch_peak_fits, tls_debug_peak_fits). */
+ * (7: tls_power_batch_peak_fits, tls_debug_peak_fits), (7: tls_phase_scan, tls_power_batch_phase_scan,
+ * tls_debug_peak_phase_scans). */
 #define TLS_AMD_ABI_VERSION 7
 
 #define TLS_OK 0
@@ -497,6 +498,63 @@ int tls_debug_peak_fits(tls_ctx *ctx, const double *y, int64_t n_curves, const t
                         int64_t k, const double *power, const double *row_duration, int64_t n_rows, double fill_factor,
                         const double *root, int64_t n_root, int64_t max_epochs, tls_peak_fit *out_fits,
                         double *out_epochs, double *out_residuals, int64_t *out_n_epochs);
+
+/* ---- survey mode: the secondary-eclipse phase scan of a candidate --------------------------------------------------- */
+/* The test against an eclipsing binary found at its true period: fold the light curve at (period, T0), measure the depth of
+ * a box of about one transit duration at every phase, and report the primary box, the deepest box away from it (the
+ * secondary candidate), the most negative one (a brightening) and the scatter of the box depths -- the empirical noise of
+ * such a box, red noise included.  Unweighted.  For a candidate (y [n] over t [n], P, T0, d = duration in days):
+ *   status 1 and NaN in every other field unless P, T0, d are finite, P > 0, d > 0 and q = 2.0 * P / d >= 16
+ *   B = int(min(floor(q), max_bins))                        bins of width 1/B >= d/(2P)
+ *   for i ascending:  x = (t[i] - T0) / P;  phi = x - floor(x);  b = min(int(phi * B), B - 1);  S[b] += y[i];  N[b] += 1
+ *   window j = bins j and (j+1) % B:  W[j] = S[j] + S[(j+1)%B],  M[j] = N[j] + N[(j+1)%B];  primary window p = B-1
+ *   baseline Sb, Nb: bins 2 .. B-3 summed ascending;  inside windows: 2 <= j <= B-4
+ *   delta[j] = (Sb - W[j]) / (Nb - M[j]) - W[j] / M[j]      inside j with M[j] >= min_count and Nb - M[j] >= 1
+ *   delta[p] = Sb / Nb - W[p] / M[p]                        if M[p] >= min_count and Nb >= 1;  every other delta NaN
+ *   js / jb = the first inside j of the largest / smallest delta that is no NaN (none: n_windows = 0, the rest NaN)
+ *   rest = those j with |j - js| > 2;  n_windows = len(rest);  where n_windows >= 8:
+ *   scan_mean = mu = sum(delta over rest, ascending) / n_windows;  scan_std = sqrt(sum((delta - mu)^2, ascending) / n_windows)
+ * Every step is one IEEE double operation and every sum runs in the stated order: the record equals the Python statement
+ * in tests/phase_scan_spec.py bit for bit.  The time stamps must be finite.  Counts are doubles.  12 doubles. */
+#define TLS_PHASE_SCAN_MIN_BINS 16
+#define TLS_PHASE_SCAN_MAX_BINS 4096
+typedef struct tls_phase_record {
+    double status;                 /* 0 scanned; 1 nothing to scan (no such fit, a bad candidate, or fewer than 16 bins) */
+    double n_bins, n_windows;      /* B; windows the scatter was taken over */
+    double primary_depth, primary_count;                        /* delta[p], M[p] */
+    double secondary_depth, secondary_phase, secondary_count;   /* delta[js], (js + 1) / B, M[js] */
+    double bump_depth, bump_phase;                              /* delta[jb], (jb + 1) / B */
+    double scan_mean, scan_std;
+} tls_phase_record;
+/* The scans of n_fits candidates the caller holds: fit f is light curve curve[f] of y [n_curves][n] over t [n] at
+ * (period[f], T0[f], duration[f] in days); out [n_fits].  Needs no plan and no search, and leaves a prepared plan as it is.
+ * n_fits == 0 is a no-op.  TLS_E_ARG when a curve[f] is outside [0, n_curves), max_bins outside [16, 4096], min_count < 1
+ * or a time stamp is not finite.  The device holds the whole batch during the call. */
+int tls_phase_scan(tls_ctx *ctx, const double *t, const double *y, int64_t n, int64_t n_curves, const int64_t *curve,
+                   const double *period, const double *T0, const double *duration, int64_t n_fits, int64_t max_bins,
+                   int64_t min_count, tls_phase_record *out);
+/* tls_power_batch_peak_fits plus the phase scan of every peak, on the device behind each slab's fits, from the period, T0
+ * and duration_days of the fit records there; the records ride in the group's one copy, 96 bytes a peak.  A fit of
+ * status != 0 gives a scan of status 1.  Summary, statistics, peaks and fits are those of tls_power_batch_peak_fits, bit
+ * for bit.  out_scans [n_curves][k]. */
+int tls_power_batch_phase_scan(tls_ctx *ctx, const double *t, const double *y, const double *dy, int64_t n,
+                               int64_t n_curves, const double *periods, int64_t n_periods,
+                               const tls_template *tmpl, const tls_params *params, int64_t median_kernel,
+                               tls_power_summary *out_summary, double *out_chi2, int64_t *out_row, double *out_depth,
+                               double *out_power, double *out_SR, double *out_power_raw,
+                               const double *row_duration, double fill_factor, const double *root, int64_t n_root,
+                               tls_transit_stats *out_stats, int64_t max_epochs, double *out_per_transit,
+                               int64_t *out_n_epochs,
+                               int64_t k, double min_separation, const double *ratios, int64_t n_ratios, double min_power,
+                               tls_peak *out_peaks /* [n_curves][k] */, int64_t *out_n_peaks /* [n_curves] */,
+                               tls_peak_fit *out_fits /* [n_curves][k] */, int64_t max_bins, int64_t min_count,
+                               tls_phase_record *out_scans /* [n_curves][k] */);
+/* Developer/test entry: tls_debug_peak_fits (without the fits' epochs) plus the phase scan of every injected peak record,
+ * as tls_power_batch_phase_scan runs it behind the fits.  out_scans [n_curves][k]. */
+int tls_debug_peak_phase_scans(tls_ctx *ctx, const double *y, int64_t n_curves, const tls_peak *peaks, const int64_t *n_peaks,
+                               int64_t k, const double *power, const double *row_duration, int64_t n_rows,
+                               double fill_factor, const double *root, int64_t n_root, int64_t max_epochs,
+                               tls_peak_fit *out_fits, int64_t max_bins, int64_t min_count, tls_phase_record *out_scans);
 
 /* ---- host-only planning (no GPU needed) ------------------------------------------ */
 /* Trial cells (duration x T0 positions) each period will enumerate: the data-independent

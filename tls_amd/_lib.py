@@ -29,6 +29,10 @@ BIWEIGHT_MAX_ITER = 50
 # include/tls_amd.h TLS_PEAKS_*: the most peaks per row and the most harmonic ratios tls_find_peaks takes
 PEAKS_MAX_K = 32
 PEAKS_MAX_RATIOS = 16
+# include/tls_amd.h TLS_PHASE_SCAN_*: the range of max_bins of the phase scan
+PHASE_SCAN_MIN_BINS = 16
+PHASE_SCAN_MAX_BINS = 4096
+PHASE_SCAN_CHUNK = 2048   # tls_phase_scan.hip.h kPhaseChunk: the points of a light curve the scan stages in LDS at a time
 PEAKS_LDS_PERIODS = 1 << 20   # tls_peaks.hip.h kPeaksLdsPeriods: a longer grid keeps its alive mask in device memory, not in LDS
 
 # every symbol include/tls_amd.h declares (tests check the export list against the header)
@@ -40,6 +44,7 @@ SYMBOLS = (
     "tls_power_batch_models", "tls_debug_transit_models",
     "tls_inject_transits", "tls_null_rows", "tls_debug_null_words", "tls_medfilt_detrend",
     "tls_biweight_detrend", "tls_find_peaks", "tls_power_batch_peaks", "tls_power_batch_peak_fits", "tls_debug_peak_fits",
+    "tls_phase_scan", "tls_power_batch_phase_scan", "tls_debug_peak_phase_scans",
     "tls_comm_unique_id", "tls_comm_init", "tls_comm_destroy", "tls_comm_info", "tls_comm_allgather_results", "tls_comm_allgather_device", "tls_comm_fetch_gathered",
     "tls_comm_stage_results", "tls_comm_allgather_staged", "tls_comm_fetch_staged",
     "tls_comm_barrier", "tls_comm_max",
@@ -154,6 +159,33 @@ class PeakFit(ctypes.Structure):
 PEAK_FIT_DTYPE = numpy.dtype([("T0", "f8"), ("status", "f8")] + [(k, "f8") for k in TRANSIT_STATS_FIELDS])
 # tls_peak_fit.status
 PEAK_FITTED, PEAK_NONE, PEAK_UNFITTED = 0, 1, 2
+
+
+# tls_phase_record (include/tls_amd.h): the phase scan of one candidate, 12 doubles
+PHASE_SCAN_FIELDS = ("status", "n_bins", "n_windows", "primary_depth", "primary_count", "secondary_depth", "secondary_phase",
+                     "secondary_count", "bump_depth", "bump_phase", "scan_mean", "scan_std")
+
+
+class PhaseRecord(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_double) for k in PHASE_SCAN_FIELDS]
+
+
+PHASE_SCAN_DTYPE = numpy.dtype([(k, "f8") for k in PHASE_SCAN_FIELDS])
+# tls_phase_record.status
+PHASE_SCANNED, PHASE_NOTHING = 0, 1
+
+
+def phase_scan_arguments(max_bins, min_count):
+    """(max_bins, min_count) as the phase scan takes them, checked as tls_phase_scan checks them: max_bins an integer in
+    [PHASE_SCAN_MIN_BINS, PHASE_SCAN_MAX_BINS], min_count an integer >= 1; ValueError otherwise."""
+    for name, v in (("max_bins", max_bins), ("min_count", min_count)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+            raise ValueError("phase scan: %s must be an integer, got %r" % (name, v))
+    if not PHASE_SCAN_MIN_BINS <= int(max_bins) <= PHASE_SCAN_MAX_BINS:
+        raise ValueError("phase scan: max_bins must be in [%d, %d], got %r" % (PHASE_SCAN_MIN_BINS, PHASE_SCAN_MAX_BINS, max_bins))
+    if not 1 <= int(min_count) < 2 ** 31:
+        raise ValueError("phase scan: min_count must be at least 1, got %r" % (min_count,))
+    return int(max_bins), int(min_count)
 
 
 def peaks_arguments(k, separation, ratios, min_power):
@@ -324,6 +356,14 @@ def load():
     lib.tls_power_batch_peaks.argtypes = lib.tls_power_batch_stats.argtypes + peaks
     lib.tls_power_batch_peak_fits.restype = ci
     lib.tls_power_batch_peak_fits.argtypes = lib.tls_power_batch_peaks.argtypes + [ctypes.c_void_p]
+    lib.tls_power_batch_phase_scan.restype = ci
+    lib.tls_power_batch_phase_scan.argtypes = lib.tls_power_batch_peak_fits.argtypes + [i64, i64, ctypes.c_void_p]
+    lib.tls_phase_scan.restype = ci
+    lib.tls_phase_scan.argtypes = [vp, _c_double_p, _c_double_p, i64, i64, _c_int64_p, _c_double_p, _c_double_p, _c_double_p,
+                                   i64, i64, i64, ctypes.c_void_p]
+    lib.tls_debug_peak_phase_scans.restype = ci
+    lib.tls_debug_peak_phase_scans.argtypes = [vp, _c_double_p, i64, ctypes.c_void_p, _c_int64_p, i64, _c_double_p, _c_double_p,
+                                               i64, dbl, _c_double_p, i64, i64, ctypes.c_void_p, i64, i64, ctypes.c_void_p]
     lib.tls_debug_peak_fits.restype = ci
     lib.tls_debug_peak_fits.argtypes = [vp, _c_double_p, i64, ctypes.c_void_p, _c_int64_p, i64, _c_double_p, _c_double_p, i64,
                                         dbl, _c_double_p, i64, i64, ctypes.c_void_p, _c_double_p, _c_double_p, _c_int64_p]
@@ -624,7 +664,7 @@ class Context(object):
 
     def _power_batch(self, t, y_batch, dy_batch, periods, table, params, median_kernel, with_arrays=False, with_power=False,
                      with_spectra=False, statistics=None, per_transit=False, models=None, lc_cap=0, peaks=None,
-                     peak_fits=None):
+                     peak_fits=None, phase_scan=None):
         """The power-batch entries: tls_power_batch; with statistics = (fill_factor, root, max_epochs)
         tls_power_batch_stats; with models (a ModelTemplate) as well, tls_power_batch_models.  A dict of the outputs by name:
         summary; chi2, row, depth (with_arrays), power (with_power), SR and power_raw (with_spectra), None where not asked
@@ -632,11 +672,17 @@ class Context(object):
         peaks = (k, separation, ratios, min_power) (peaks_arguments): tls_power_batch_peaks, with or without statistics, and
         peaks (PEAK_DTYPE [n_curves, k]) and n_peaks [n_curves] as well; no entry carries peaks and models (ValueError).
         peak_fits = (fill_factor, root, max_epochs), with peaks only: tls_power_batch_peak_fits, and peak_fits (PEAK_FIT_DTYPE
-        [n_curves, k]: T0, status and the statistics record of every peak) as well, with or without statistics."""
+        [n_curves, k]: T0, status and the statistics record of every peak) as well, with or without statistics.
+        phase_scan = (max_bins, min_count), with peak_fits only: tls_power_batch_phase_scan, and phase_scans (PHASE_SCAN_DTYPE
+        [n_curves, k]) as well."""
         if peaks is not None and models is not None:
             raise ValueError("peaks and models cannot be combined: no entry point carries both")
         if peak_fits is not None and peaks is None:
             raise ValueError("peak_fits needs peaks: the fits are those of the peaks")
+        if phase_scan is not None and peak_fits is None:
+            raise ValueError("phase_scan needs peak_fits: the scans read T0 and duration of the fits")
+        if phase_scan is not None:
+            phase_scan = phase_scan_arguments(*phase_scan)
         if peaks is not None:
             peaks = peaks_arguments(*peaks)
         t, periods = _f8(t), _f8(periods)
@@ -689,6 +735,11 @@ class Context(object):
                 assert PEAK_FIT_DTYPE.itemsize == ctypes.sizeof(PeakFit)
                 args += [out["peak_fits"].ctypes.data_as(ctypes.c_void_p)]
                 entry = self._lib.tls_power_batch_peak_fits
+            if phase_scan is not None:
+                out["phase_scans"] = numpy.zeros((n_c, k), dtype=PHASE_SCAN_DTYPE)
+                assert PHASE_SCAN_DTYPE.itemsize == ctypes.sizeof(PhaseRecord)
+                args += [phase_scan[0], phase_scan[1], out["phase_scans"].ctypes.data_as(ctypes.c_void_p)]
+                entry = self._lib.tls_power_batch_phase_scan
         self._invalidate_results()
         self._check(entry(*args))
         self._n_periods = n_p
@@ -734,12 +785,14 @@ class Context(object):
             self._check(self._lib.tls_debug_transit_models(*(args + models.args(lc_cap, out))))
         return (stats, rows, n_epochs) + out
 
-    def debug_peak_fits(self, y_batch, peaks, n_peaks, power, row_duration, fill_factor, root, max_epochs, with_fits=False):
+    def debug_peak_fits(self, y_batch, peaks, n_peaks, power, row_duration, fill_factor, root, max_epochs, with_fits=False,
+                        phase_scan=None):
         """Developer/test entry: the peak-fit stage of power_batch(peaks=K, peak_fits=True) on the prepared plan (prepare())
         with injected peak records (tls_debug_peak_fits) -- flux y_batch [n_curves, n], peaks [n_curves, k] with the fields
         of PEAK_DTYPE (more are ignored), n_peaks [n_curves], the detrended power [n_curves, n_periods]: the fits
         (PEAK_FIT_DTYPE [n_curves, k]); with_fits: also every fit's trial epochs and residuals [n_curves, k, n] and n_epochs
-        [n_curves, k]."""
+        [n_curves, k].  phase_scan = (max_bins, min_count), without with_fits: (fits, scans) with the fits' phase scans
+        (PHASE_SCAN_DTYPE [n_curves, k]) as power_batch(phase_scan=True) runs them (tls_debug_peak_phase_scans)."""
         y_batch = numpy.ascontiguousarray(y_batch, dtype=numpy.float64)
         power = numpy.ascontiguousarray(power, dtype=numpy.float64)
         n_c = len(y_batch)
@@ -761,6 +814,16 @@ class Context(object):
         residuals = numpy.full((n_c, k, n), numpy.nan) if with_fits else None
         n_epochs = numpy.zeros((n_c, k), dtype=numpy.int64) if with_fits else None
         self._invalidate_results()
+        if phase_scan is not None:
+            if with_fits:
+                raise ValueError("phase_scan and with_fits cannot be combined")
+            max_bins, min_count = phase_scan_arguments(*phase_scan)
+            scans = numpy.zeros((n_c, k), dtype=PHASE_SCAN_DTYPE)
+            self._check(self._lib.tls_debug_peak_phase_scans(
+                self._h, _dp(y_batch), n_c, rec.ctypes.data_as(ctypes.c_void_p), _ip(n_peaks), k, _dp(power), _dp(row_duration),
+                len(row_duration), float(fill_factor), _dp(root), len(root), int(max_epochs),
+                fits.ctypes.data_as(ctypes.c_void_p), max_bins, min_count, scans.ctypes.data_as(ctypes.c_void_p)))
+            return fits, scans
         self._check(self._lib.tls_debug_peak_fits(
             self._h, _dp(y_batch), n_c, rec.ctypes.data_as(ctypes.c_void_p), _ip(n_peaks), k, _dp(power), _dp(row_duration),
             len(row_duration), float(fill_factor), _dp(root), len(root), int(max_epochs), fits.ctypes.data_as(ctypes.c_void_p),
@@ -931,6 +994,37 @@ class Context(object):
             None if depth is None else _dp(depth), rows.shape[0], rows.shape[1], _dp(periods), k, sep, _dp(ratios),
             len(ratios), low, peaks.ctypes.data_as(ctypes.c_void_p), _ip(n_peaks)))
         return peaks, n_peaks
+
+    def phase_scan(self, t, y, period, T0, duration, curve=None, max_bins=PHASE_SCAN_MAX_BINS, min_count=3):
+        """The phase scans (tls_phase_scan; the scan: include/tls_amd.h, tests/phase_scan_spec.py) of the candidates
+        (period[f], T0[f], duration[f] in days) on light curve curve[f] (None: one fit a curve, in order) of y [n_curves, n]
+        (or one row) over the finite time stamps t [n]: PHASE_SCAN_DTYPE [n_fits].  ValueError for the arguments
+        phase_scan_arguments refuses, for shapes that do not agree and for a curve out of range."""
+        max_bins, min_count = phase_scan_arguments(max_bins, min_count)
+        t = _f8(t)
+        rows = numpy.ascontiguousarray(numpy.atleast_2d(numpy.asarray(y, dtype=numpy.float64)))
+        if t.ndim != 1 or rows.ndim != 2 or rows.shape[1] != len(t) or len(t) < 1:
+            raise ValueError("y must be [n] or [n_curves, n] over the time stamps t [n]")
+        if not numpy.all(numpy.isfinite(t)):
+            raise ValueError("phase scan: the time stamps must be finite")
+        period, T0, duration = (_f8(numpy.atleast_1d(numpy.asarray(a, dtype=numpy.float64))) for a in (period, T0, duration))
+        if period.ndim != 1 or not period.shape == T0.shape == duration.shape:
+            raise ValueError("period, T0 and duration must be [n_fits]")
+        if curve is None:
+            if len(period) != len(rows):
+                raise ValueError("curve=None takes one fit a light curve: %d fits, %d curves" % (len(period), len(rows)))
+            curve = numpy.arange(len(rows))
+        curve = _i8(numpy.atleast_1d(numpy.asarray(curve)))
+        if curve.shape != period.shape:
+            raise ValueError("curve must be [n_fits]")
+        if len(curve) and (curve.min() < 0 or curve.max() >= len(rows)):
+            raise ValueError("phase scan: curve out of range [0, %d)" % len(rows))
+        out = numpy.zeros(len(period), dtype=PHASE_SCAN_DTYPE)
+        assert PHASE_SCAN_DTYPE.itemsize == ctypes.sizeof(PhaseRecord)
+        self._check(self._lib.tls_phase_scan(self._h, _dp(t), _dp(rows), rows.shape[1], rows.shape[0], _ip(curve), _dp(period),
+                                             _dp(T0), _dp(duration), len(period), max_bins, min_count,
+                                             out.ctypes.data_as(ctypes.c_void_p)))
+        return out
 
     def debug_null_words(self, n, n_rows, seed, first_trial=0, block=None):
         """The raw Philox words [n_rows, W] tls_null_rows draws for these trials (tls_debug_null_words): white-noise

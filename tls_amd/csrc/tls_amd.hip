@@ -214,6 +214,7 @@ struct tls_ctx {
     // n_epochs | curve of fit; trial epochs; residuals; the statistics kernel's scratch and its chunk ranges
     DevBuf<double> d_pfit, d_pfep, d_pfres, d_pfstats;
     DevBuf<int> d_pfranges;
+    DevBuf<double> d_scan;          // tls_phase_scan: t | y rows | period | T0 | duration | records | curve of fit
     // two-role slab path (series in HBM, one light curve; SearchPlan::split)
     View<unsigned int> d_tile_prefix;        // [n_periods + 1] tiles in front of work item w (queue order)
     DevBuf<double> d_partials;               // [split_max_items][3] a tile's winner
@@ -876,6 +877,7 @@ struct PostSearchBufs {
     double* per_transit = nullptr;             // ... the per-transit rows: behind the records, or behind the peaks where they are not copied out
     double* peaks = nullptr;                   // tls_power_batch_peaks: [group][1 + 6 k], behind what of the statistics is copied out
     double* fits = nullptr;                    // tls_power_batch_peak_fits: T0 [group k] | status [group k] | records [group k][16], behind the peaks
+    double* scans = nullptr;                   // tls_power_batch_phase_scan: records [group k][12], behind the peak fits
     int64_t group = 0;
     int* n_epochs = nullptr;
     tlsdev::T0FitParams* fit = nullptr;
@@ -883,15 +885,16 @@ struct PostSearchBufs {
 
 // stats_words: doubles of the statistics stage per curve behind T0 (0: no statistics requested); peaks_words: of the peaks
 // behind the first stats_copied (<= stats_words: the records alone, or the per-transit rows too) of those -- sde | pick | T0 |
-// statistics copied out | peaks | peak fits (fits_words doubles a curve, with peaks only) are ONE contiguous copy, per-transit
-// rows nobody asked for stay behind it
+// statistics copied out | peaks | peak fits (fits_words doubles a curve, with peaks only) | phase scans (scans_words, with
+// peak fits only) are ONE contiguous copy, per-transit rows nobody asked for stay behind it
 int reserve_post_search(tls_ctx* ctx, int64_t group, int64_t n_periods, int64_t n, int64_t max_len, PostSearchBufs& b,
-                        size_t stats_words = 0, size_t peaks_words = 0, size_t stats_copied = 0, size_t fits_words = 0) {
+                        size_t stats_words = 0, size_t peaks_words = 0, size_t stats_copied = 0, size_t fits_words = 0,
+                        size_t scans_words = 0) {
     const size_t np = (size_t)n_periods, g = (size_t)group;
     b.max_len = std::max<int64_t>(max_len, 1);
     b.spec_stride = 3 * np;
     b.group = group;
-    TLS_HIP(ctx, ctx->d_spec.reserve(g * b.spec_stride + 2 * g + 8 * g + g + stats_words * g + peaks_words * g + fits_words * g));
+    TLS_HIP(ctx, ctx->d_spec.reserve(g * b.spec_stride + 2 * g + 8 * g + g + stats_words * g + peaks_words * g + fits_words * g + scans_words * g));
     b.sde = ctx->d_spec.ptr + g * b.spec_stride;
     b.pick = b.sde + 2 * g;
     b.T0 = b.pick + 8 * g;
@@ -901,7 +904,8 @@ int reserve_post_search(tls_ctx* ctx, int64_t group, int64_t n_periods, int64_t 
         const bool rows_copied = stats_copied == stats_words;
         b.peaks = b.T0 + g + (rows_copied ? stats_words : (size_t)tlsdev::kTransitStats) * g;
         if (fits_words) b.fits = b.peaks + peaks_words * g;
-        if (stats_words && !rows_copied) b.per_transit = b.peaks + (peaks_words + fits_words) * g;
+        if (scans_words) b.scans = b.fits + fits_words * g;
+        if (stats_words && !rows_copied) b.per_transit = b.peaks + (peaks_words + fits_words + scans_words) * g;
     }
     b.fit_stride = (size_t)n;
     TLS_HIP(ctx, ctx->d_fep.reserve(g * b.fit_stride));
@@ -1202,6 +1206,44 @@ void read_peaks(const PeaksRequest& pr, const double* h, int64_t c, int64_t curv
     std::memcpy(pr.out + (size_t)curve * (size_t)pr.k, rec + 1, (size_t)pr.k * sizeof(tls_peak));
 }
 
+// ---- the phase scan (tls_phase_scan on the caller's candidates; tls_power_batch_phase_scan behind every slab of peak fits):
+// one workgroup a fit (tls_phase_scan.hip.h, DESIGN.md "Phase scan")
+struct PhaseScanRequest {
+    int64_t max_bins = 0, min_count = 0;
+    tls_phase_record* out = nullptr;           // [n_fits], or [n_curves][k]
+};
+static_assert(sizeof(tls_phase_record) == tlsdev::kPhaseWords * 8, "tls_phase_record is the kernel's record");
+static_assert(TLS_PHASE_SCAN_MIN_BINS == tlsdev::kPhaseMinBins && TLS_PHASE_SCAN_MAX_BINS == tlsdev::kPhaseMaxBins, "the header's limits");
+
+int check_phase_scan_request(tls_ctx* ctx, const PhaseScanRequest& ps) {
+    if (ps.max_bins < TLS_PHASE_SCAN_MIN_BINS || ps.max_bins > TLS_PHASE_SCAN_MAX_BINS)
+        return fail(ctx, TLS_E_ARG, "phase scan: max_bins out of range [16, 4096]");
+    if (ps.min_count < 1 || ps.min_count > INT32_MAX) return fail(ctx, TLS_E_ARG, "phase scan: min_count < 1");
+    return TLS_OK;
+}
+
+// the scans of `fits` fits into d_out [fits][12], nothing waited for; fit f reads the flux row d_curve[f] of d_y [..][n],
+// d_period[f * period_stride], d_T0[f] and d_duration[f * duration_stride], and is not scanned where d_status[f] != 0
+int enqueue_phase_scan(tls_ctx* ctx, const PhaseScanRequest& ps, int64_t fits, const double* d_t, const double* d_y, int64_t n,
+                       const int* d_curve, const double* d_period, int period_stride, const double* d_T0,
+                       const double* d_duration, int duration_stride, const double* d_status, double* d_out) {
+    tlsdev::PhaseScanArgs a;
+    a.t = d_t; a.y = d_y; a.curve = d_curve;
+    a.period = d_period; a.T0 = d_T0; a.duration = d_duration;
+    a.period_stride = period_stride; a.duration_stride = duration_stride;
+    a.status = d_status; a.out = d_out;
+    a.n = (int)n; a.max_bins = (int)ps.max_bins; a.min_count = (int)ps.min_count;
+    auto kernel = tlsdev::tls_phase_scan_kernel;
+    const size_t lds = tlsdev::phase_scan_lds_bytes(a.max_bins);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)fits), dim3(tlsdev::kPhaseThreads), lds, ctx->stream, a);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) return fail(ctx, TLS_E_HIP, std::string("phase scan launch: ") + hipGetErrorString(e));
+    return TLS_OK;
+}
+
 // ---- the peak-fit stage (tls_power_batch_peak_fits; tls_debug_peak_fits feeds it injected peak records): the final T0 fit
 // and the statistics record of EVERY peak of a group, fits f = c k + r in slabs of kPeakFitSlab behind the group's peaks
 // kernel, on arrays of its own (tls_peak_fits.hip.h, DESIGN.md "Peak fits")
@@ -1246,11 +1288,12 @@ int reserve_peak_fits(tls_ctx* ctx, int64_t fits_total, int64_t n, int64_t max_l
 // the fits of `gc` curves: d_peaks the group's peak records, d_y [gc][n] and d_power (stride power_stride) the curves' flux
 // and detrended power, sb the statistics inputs on the device; results into d_out = T0 [cap] | status [cap] | records
 // [cap][16], cap = group k.  Nothing waited for, unless the request wants the fits' epochs back (`first_curve`: the batch
-// index of the group's first curve in those arrays), which are copied slab by slab.
+// index of the group's first curve in those arrays), which are copied slab by slab.  ps: every fit's phase scan behind its
+// slab, from the period of the slab's pick, T0 and duration_days of its record, into d_scans [cap][12].
 int enqueue_peak_fits(tls_ctx* ctx, const PeakFitBufs& fb, const PeakFitsRequest& pf, const StatsBufs& sb, int64_t gc,
                       int64_t group, const double* d_peaks, double* d_out, const double* d_y, const double* d_power,
                       size_t power_stride, int64_t n, int64_t n_periods, double t_min, double t_max, double margin,
-                      int64_t first_curve = 0) {
+                      int64_t first_curve = 0, const PhaseScanRequest* ps = nullptr, double* d_scans = nullptr) {
     const StatsRequest& in = *pf.inputs;
     const int64_t total = gc * pf.k, cap = group * pf.k;
     double* T0 = d_out; double* status = d_out + cap; double* stats = d_out + 2 * cap;
@@ -1285,6 +1328,9 @@ int enqueue_peak_fits(tls_ctx* ctx, const PeakFitBufs& fb, const PeakFitsRequest
         a.n = (int)n; a.max_epochs = (int)in.max_epochs;
         hipLaunchKernelGGL(tlsdev::tls_transit_stats, dim3((unsigned)fits), dim3(256), 0, ctx->stream, a);
         TLS_HIP(ctx, hipGetLastError());
+        if (ps && (rc = enqueue_phase_scan(ctx, *ps, fits, ctx->d_t.ptr, d_y, n, fb.curve, fb.pick + 3, 8, T0 + f0,
+                                           a.stats + 1, tlsdev::kTransitStats, status + f0,
+                                           d_scans + (size_t)f0 * tlsdev::kPhaseWords))) return rc;
         if (pf.out_epochs || pf.out_residuals || pf.out_n_epochs) {
             // (the next slab overwrites these arrays: the copies are done before it is enqueued)
             const size_t at = (size_t)(first_curve * pf.k + f0), bytes = (size_t)fits * fb.fit_stride * 8;
@@ -1581,6 +1627,7 @@ void tls_ctx_destroy(tls_ctx* ctx) {
     ctx->d_tstats.release(); ctx->d_tranges.release(); ctx->d_models.release(); ctx->d_inject.release(); ctx->d_inject_count.release();
     ctx->d_null.release(); ctx->d_null_words.release(); ctx->d_detrend.release(); ctx->d_windows.release(); ctx->d_peaks.release(); ctx->d_peak_mask.release();
     ctx->d_pfit.release(); ctx->d_pfep.release(); ctx->d_pfres.release(); ctx->d_pfstats.release(); ctx->d_pfranges.release();
+    ctx->d_scan.release();
     ctx->d_split.release(); ctx->d_park.release(); ctx->d_band.release();
     if (ctx->h_band) (void)hipHostFree(ctx->h_band);
     for (auto& ev : ctx->ev_band) if (ev) (void)hipEventDestroy(ev);
@@ -2540,10 +2587,11 @@ int tls_debug_transit_models(tls_ctx* ctx, const double* y, int64_t n_curves, co
                               fill_factor, root, n_root, max_epochs, out_stats, out_per_transit, out_n_epochs, &mr);
 }
 
-int tls_debug_peak_fits(tls_ctx* ctx, const double* y, int64_t n_curves, const tls_peak* peaks, const int64_t* n_peaks,
-                        int64_t k, const double* power, const double* row_duration, int64_t n_rows, double fill_factor,
-                        const double* root, int64_t n_root, int64_t max_epochs, tls_peak_fit* out_fits, double* out_epochs,
-                        double* out_residuals, int64_t* out_n_epochs) {
+// tls_debug_peak_fits; ps: tls_debug_peak_phase_scans, the fits' phase scans as well
+static int debug_peak_fits_impl(tls_ctx* ctx, const double* y, int64_t n_curves, const tls_peak* peaks, const int64_t* n_peaks,
+                                int64_t k, const double* power, const double* row_duration, int64_t n_rows, double fill_factor,
+                                const double* root, int64_t n_root, int64_t max_epochs, tls_peak_fit* out_fits, double* out_epochs,
+                                double* out_residuals, int64_t* out_n_epochs, const PhaseScanRequest* ps) {
     if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
     if (!ctx->prepared || !ctx->key.valid) return fail(ctx, TLS_E_STATE, "tls_debug_peak_fits before tls_prepare");
     if (!y || !peaks || !n_peaks || !power || !out_fits) return fail(ctx, TLS_E_ARG, "null argument");
@@ -2579,7 +2627,8 @@ int tls_debug_peak_fits(tls_ctx* ctx, const double* y, int64_t n_curves, const t
     auto& sl = ctx->slot[0];
     TLS_HIP(ctx, sl.d_y.reserve(gc * nn));
     PostSearchBufs pb;
-    if ((rc = reserve_post_search(ctx, n_curves, n_periods, n, max_len, pb, 0, pk.words(), 0, pf.words()))) return rc;
+    const size_t scans_out = ps ? (size_t)tlsdev::kPhaseWords * kk : 0;
+    if ((rc = reserve_post_search(ctx, n_curves, n_periods, n, max_len, pb, 0, pk.words(), 0, pf.words(), scans_out))) return rc;
     StatsBufs sb;
     if ((rc = reserve_transit_stats(ctx, sr, 0, n, sb))) return rc;
     PeakFitBufs fb;
@@ -2588,17 +2637,41 @@ int tls_debug_peak_fits(tls_ctx* ctx, const double* y, int64_t n_curves, const t
     TLS_HIP(ctx, hipMemcpy2DAsync(ctx->d_spec.ptr + 2 * np, pb.spec_stride * 8, power, np * 8, np * 8, gc, hipMemcpyHostToDevice, ctx->stream));
     TLS_HIP(ctx, hipMemcpyAsync(pb.peaks, rec.data(), rec.size() * 8, hipMemcpyHostToDevice, ctx->stream));
     if ((rc = enqueue_peak_fits(ctx, fb, pf, sb, n_curves, n_curves, pb.peaks, pb.fits, sl.d_y.ptr, ctx->d_spec.ptr + 2 * np,
-                                pb.spec_stride, n, n_periods, t_min, t_max, key.params.T0_fit_margin))) {
+                                pb.spec_stride, n, n_periods, t_min, t_max, key.params.T0_fit_margin, 0, ps, pb.scans))) {
         (void)hipStreamSynchronize(ctx->stream);
         return rc;
     }
-    std::vector<double> h(gc * pf.words());
+    // (fits and scans lie side by side; fit f = c k + r: the scans are already in the caller's order)
+    std::vector<double> h(gc * (pf.words() + scans_out));
     TLS_HIP(ctx, hipMemcpyAsync(h.data(), pb.fits, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
     TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->executed = false;   // (the batch slot's buffers were written: as after tls_power_batch)
     for (int64_t c = 0; c < n_curves; ++c)
         if ((rc = read_peak_fits(ctx, pf, h.data(), n_curves, c, c))) return rc;
+    if (ps) std::memcpy(ps->out, h.data() + gc * pf.words(), gc * scans_out * 8);
     return TLS_OK;
+}
+
+int tls_debug_peak_fits(tls_ctx* ctx, const double* y, int64_t n_curves, const tls_peak* peaks, const int64_t* n_peaks,
+                        int64_t k, const double* power, const double* row_duration, int64_t n_rows, double fill_factor,
+                        const double* root, int64_t n_root, int64_t max_epochs, tls_peak_fit* out_fits, double* out_epochs,
+                        double* out_residuals, int64_t* out_n_epochs) {
+    return debug_peak_fits_impl(ctx, y, n_curves, peaks, n_peaks, k, power, row_duration, n_rows, fill_factor, root, n_root,
+                                max_epochs, out_fits, out_epochs, out_residuals, out_n_epochs, nullptr);
+}
+
+int tls_debug_peak_phase_scans(tls_ctx* ctx, const double* y, int64_t n_curves, const tls_peak* peaks, const int64_t* n_peaks,
+                               int64_t k, const double* power, const double* row_duration, int64_t n_rows, double fill_factor,
+                               const double* root, int64_t n_root, int64_t max_epochs, tls_peak_fit* out_fits,
+                               int64_t max_bins, int64_t min_count, tls_phase_record* out_scans) {
+    if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
+    if (!out_scans) return fail(ctx, TLS_E_ARG, "null argument");
+    PhaseScanRequest ps;
+    ps.max_bins = max_bins; ps.min_count = min_count; ps.out = out_scans;
+    const int rc = check_phase_scan_request(ctx, ps);
+    if (rc) return rc;
+    return debug_peak_fits_impl(ctx, y, n_curves, peaks, n_peaks, k, power, row_duration, n_rows, fill_factor, root, n_root,
+                                max_epochs, out_fits, nullptr, nullptr, nullptr, &ps);
 }
 
 int tls_debug_device_bytes(const tls_ctx* ctx, int64_t* total, int64_t* t0_fit_scratch) {
@@ -2617,6 +2690,7 @@ int tls_debug_device_bytes(const tls_ctx* ctx, int64_t* total, int64_t* t0_fit_s
     add(ctx->d_pink); add(ctx->d_frot); add(ctx->d_frperm); add(ctx->d_spec); add(ctx->d_tstats); add(ctx->d_tranges); add(ctx->d_models);
     add(ctx->d_peaks); add(ctx->d_peak_mask);
     add(ctx->d_pfit); add(ctx->d_pfep); add(ctx->d_pfres); add(ctx->d_pfstats); add(ctx->d_pfranges);
+    add(ctx->d_scan);
     add(ctx->d_partials); add(ctx->d_tiles_done);
     add(ctx->d_split); add(ctx->d_park); add(ctx->d_band);
     *total = (int64_t)sum;
@@ -2818,7 +2892,7 @@ static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, cons
                             int64_t median_kernel, tls_power_summary* out_summary, double* out_chi2, int64_t* out_row,
                             double* out_depth, double* out_power, double* out_SR, double* out_power_raw,
                             const StatsRequest* sr, const ModelsRequest* mr = nullptr, const PeaksRequest* pk = nullptr,
-                            const PeakFitsRequest* pf = nullptr);
+                            const PeakFitsRequest* pf = nullptr, const PhaseScanRequest* ps = nullptr);
 
 int tls_power_batch(tls_ctx* ctx, const double* t, const double* y, const double* dy, int64_t n, int64_t n_curves,
                     const double* periods, int64_t n_periods, const tls_template* tmpl, const tls_params* params,
@@ -2919,6 +2993,85 @@ int tls_power_batch_peak_fits(tls_ctx* ctx, const double* t, const double* y, co
                                            out_stats ? &sr : nullptr, nullptr, &pk, &pf));
 }
 
+int tls_power_batch_phase_scan(tls_ctx* ctx, const double* t, const double* y, const double* dy, int64_t n, int64_t n_curves,
+                               const double* periods, int64_t n_periods, const tls_template* tmpl, const tls_params* params,
+                               int64_t median_kernel, tls_power_summary* out_summary, double* out_chi2, int64_t* out_row,
+                               double* out_depth, double* out_power, double* out_SR, double* out_power_raw,
+                               const double* row_duration, double fill_factor, const double* root, int64_t n_root,
+                               tls_transit_stats* out_stats, int64_t max_epochs, double* out_per_transit, int64_t* out_n_epochs,
+                               int64_t k, double min_separation, const double* ratios, int64_t n_ratios, double min_power,
+                               tls_peak* out_peaks, int64_t* out_n_peaks, tls_peak_fit* out_fits, int64_t max_bins,
+                               int64_t min_count, tls_phase_record* out_scans) {
+    if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
+    if (!t || !tmpl) return fail(ctx, TLS_E_ARG, "null argument");
+    PeaksRequest pk;
+    pk.k = k; pk.sep = min_separation; pk.ratios = ratios; pk.n_ratios = n_ratios; pk.min_power = min_power;
+    pk.out = out_peaks; pk.out_n = out_n_peaks;
+    int rc = check_peaks_request(ctx, pk, n_periods);
+    if (rc) return rc;
+    PhaseScanRequest ps;
+    ps.max_bins = max_bins; ps.min_count = min_count; ps.out = out_scans;
+    if ((rc = check_phase_scan_request(ctx, ps))) return rc;
+    if (n_curves > 0 && (!out_peaks || !out_n_peaks || !out_fits || !out_scans)) return fail(ctx, TLS_E_ARG, "null peaks argument");
+    const StatsRequest sr = stats_request(row_duration, tmpl->n_rows, fill_factor, root, n_root, max_epochs, out_stats,
+                                          out_stats ? out_per_transit : nullptr, out_stats ? out_n_epochs : nullptr);
+    if ((rc = check_stats_request(ctx, sr, t, n, tmpl->n_rows, false))) return rc;
+    PeakFitsRequest pf;
+    pf.k = k; pf.inputs = &sr; pf.out = out_fits;
+    return end_batch(ctx, power_batch_impl(ctx, t, y, dy, n, n_curves, periods, n_periods, tmpl, params, median_kernel,
+                                           out_summary, out_chi2, out_row, out_depth, out_power, out_SR, out_power_raw,
+                                           out_stats ? &sr : nullptr, nullptr, &pk, &pf, &ps));
+}
+
+int tls_phase_scan(tls_ctx* ctx, const double* t, const double* y, int64_t n, int64_t n_curves, const int64_t* curve,
+                   const double* period, const double* T0, const double* duration, int64_t n_fits, int64_t max_bins,
+                   int64_t min_count, tls_phase_record* out) {
+    if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
+    PhaseScanRequest ps;
+    ps.max_bins = max_bins; ps.min_count = min_count; ps.out = out;
+    int rc = check_phase_scan_request(ctx, ps);
+    if (rc) return rc;
+    if (n_fits < 0 || n_curves < 0) return fail(ctx, TLS_E_ARG, "phase scan: negative count");
+    if (n_fits == 0) return TLS_OK;
+    if (!t || !y || !curve || !period || !T0 || !duration || !out) return fail(ctx, TLS_E_ARG, "null argument");
+    if (n < 1 || n > INT32_MAX) return fail(ctx, TLS_E_ARG, "phase scan: n out of range [1, 2^31)");
+    if (n_fits > INT32_MAX || (uint64_t)n_curves > (uint64_t)(INT64_MAX / 16) / (uint64_t)n)
+        return fail(ctx, TLS_E_ARG, "phase scan: batch too large");
+    for (int64_t i = 0; i < n; ++i)
+        if (!std::isfinite(t[i])) return fail(ctx, TLS_E_ARG, "phase scan: the time stamps must be finite");
+    std::vector<int> h_curve((size_t)n_fits);
+    for (int64_t f = 0; f < n_fits; ++f) {
+        if (curve[f] < 0 || curve[f] >= n_curves) return fail(ctx, TLS_E_ARG, "phase scan: curve out of range [0, n_curves)");
+        h_curve[(size_t)f] = (int)curve[f];
+    }
+    TLS_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t nn = (size_t)n, rows = (size_t)n_curves, fits = (size_t)n_fits, words = (size_t)tlsdev::kPhaseWords;
+    // t | y rows | period | T0 | duration | records | curve of fit (the whole batch at once: DESIGN.md "Phase scan")
+    TLS_HIP(ctx, ctx->d_scan.reserve(nn + rows * nn + 3 * fits + words * fits + (fits + 1) / 2));
+    double* d_t = ctx->d_scan.ptr;
+    double* d_y = d_t + nn;
+    double* d_period = d_y + rows * nn;
+    double* d_T0 = d_period + fits;
+    double* d_duration = d_T0 + fits;
+    double* d_out = d_duration + fits;
+    int* d_curve = reinterpret_cast<int*>(d_out + words * fits);
+    TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_y, y, rows * nn * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_period, period, fits * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_T0, T0, fits * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_duration, duration, fits * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_curve, h_curve.data(), fits * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = enqueue_phase_scan(ctx, ps, n_fits, d_t, d_y, n, d_curve, d_period, 1, d_T0, d_duration, 1, nullptr, d_out))) {
+        (void)hipStreamSynchronize(ctx->stream);
+        return rc;
+    }
+    ctx->last_kernel = "tls_phase_scan";
+    TLS_HIP(ctx, hipMemcpyAsync(out, d_out, words * fits * 8, hipMemcpyDeviceToHost, ctx->stream));
+    // (h_curve is read by the copy above until the stream is done)
+    TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return TLS_OK;
+}
+
 int tls_find_peaks(tls_ctx* ctx, const double* power, const double* chi2, const int64_t* row, const double* depth,
                    int64_t n_rows, int64_t n_periods, const double* periods, int64_t k, double min_separation,
                    const double* ratios, int64_t n_ratios, double min_power, tls_peak* out_peaks, int64_t* out_n_peaks) {
@@ -2973,7 +3126,8 @@ static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, cons
                             const double* periods, int64_t n_periods, const tls_template* tmpl, const tls_params* params,
                             int64_t median_kernel, tls_power_summary* out_summary, double* out_chi2, int64_t* out_row,
                             double* out_depth, double* out_power, double* out_SR, double* out_power_raw,
-                            const StatsRequest* sr, const ModelsRequest* mr, const PeaksRequest* pk, const PeakFitsRequest* pf) {
+                            const StatsRequest* sr, const ModelsRequest* mr, const PeaksRequest* pk, const PeakFitsRequest* pf,
+                            const PhaseScanRequest* ps) {
     if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
     if (n_curves < 0) return fail(ctx, TLS_E_ARG, "negative number of light curves");
     if (n_curves == 0) return TLS_OK;
@@ -3000,8 +3154,10 @@ static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, cons
     const size_t peaks_out = pk ? pk->words() : 0;
     // (peak fits requested, with peaks only: T0, status and record of every peak, behind the peaks, in the same copy)
     const size_t fits_out = pf ? pf->words() : 0;
+    // (phase scans requested, with peak fits only: one record a peak, behind the fits, in the same copy)
+    const size_t scans_out = pf && ps ? (size_t)tlsdev::kPhaseWords * (size_t)pf->k : 0;
     PostSearchBufs pb;
-    if ((rc = reserve_post_search(ctx, group, n_periods, n, max_len, pb, sr ? sr->words() : 0, peaks_out, stats_out, fits_out))) return rc;
+    if ((rc = reserve_post_search(ctx, group, n_periods, n, max_len, pb, sr ? sr->words() : 0, peaks_out, stats_out, fits_out, scans_out))) return rc;
     const size_t spec_stride = pb.spec_stride;
     StatsBufs sb;
     if (sr && (rc = reserve_transit_stats(ctx, *sr, group, n, sb))) return rc;
@@ -3018,13 +3174,13 @@ static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, cons
     // one: the stream runs the groups in order): while the device works on group g the host forms group g + 1 in the other
     // set and enqueues it, THEN waits for g -- the device never waits for the host between two groups (round 6)
     const size_t arrays = (out_chi2 ? 3 : 0) + (out_power ? 1 : 0) + (out_SR ? 1 : 0) + (out_power_raw ? 1 : 0);
-    const size_t out_doubles = (11 + stats_out + peaks_out + fits_out + models_out) * (size_t)group + arrays * (size_t)group * np;
+    const size_t out_doubles = (11 + stats_out + peaks_out + fits_out + scans_out + models_out) * (size_t)group + arrays * (size_t)group * np;
     if ((rc = reserve_batch_staging(ctx, group, nn, out_doubles))) return rc;
     const int64_t n_groups = (n_curves + group - 1) / group;
     ctx->batch_group_ms.assign((size_t)n_groups, 0.0);
     ctx->batch_group_wait_ms.assign((size_t)n_groups, 0.0);
     // host layout of a group's results (the same in both sets)
-    struct OutLayout { double *sde, *pick, *T0, *stats, *peaks, *fits, *chi2, *power, *SR, *praw, *spec3, *models; };
+    struct OutLayout { double *sde, *pick, *T0, *stats, *peaks, *fits, *scans, *chi2, *power, *SR, *praw, *spec3, *models; };
     auto out_layout = [&](int64_t g) -> OutLayout {
         OutLayout o{};
         double* base = ctx->slot[g & 1].h_out;
@@ -3032,7 +3188,8 @@ static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, cons
         o.stats = o.T0 + group;                          // statistics records (and rows), on request
         o.peaks = o.stats + stats_out * (size_t)group;   // peak records, on request
         o.fits = o.peaks + peaks_out * (size_t)group;    // peak fits, on request
-        double* h_next = o.fits + fits_out * (size_t)group;     // chi2 | row | depth | power | SR | power_raw, on request
+        o.scans = o.fits + fits_out * (size_t)group;     // phase scans, on request
+        double* h_next = o.scans + scans_out * (size_t)group;   // chi2 | row | depth | power | SR | power_raw, on request
         if (out_chi2) { o.chi2 = h_next; h_next += 3 * (size_t)group * np; }
         if (out_power && out_SR && out_power_raw) { o.spec3 = h_next; h_next += 3 * (size_t)group * np; }
         else {
@@ -3061,11 +3218,12 @@ static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, cons
         if (sr && (rc2 = enqueue_transit_stats(ctx, pb, sb, *sr, gc, sl.d_y.ptr, n, n_periods, t_min, t_max))) return rc2;
         // (every peak's T0 fit and record, on the stage's own arrays: pick, T0 and statistics of the best pick stay as they are)
         if (pf && (rc2 = enqueue_peak_fits(ctx, fb, *pf, sb, gc, group, pb.peaks, pb.fits, sl.d_y.ptr, ctx->d_spec.ptr + 2 * np,
-                                           spec_stride, n, n_periods, t_min, t_max, params->T0_fit_margin))) return rc2;
+                                           spec_stride, n, n_periods, t_min, t_max, params->T0_fit_margin, 0,
+                                           scans_out ? ps : nullptr, pb.scans))) return rc2;
         if (mr && (rc2 = enqueue_transit_models(ctx, pb, sb, *sr, *mr, mb, gc, sl.d_y.ptr, n, t_min, t_max))) return rc2;
-        // (sde | pick | T0 [| statistics] [| peaks [| peak fits]] lie side by side behind the spectra on the device: ONE copy, the host keeps the layout)
+        // (sde | pick | T0 [| statistics] [| peaks [| peak fits [| phase scans]]] lie side by side behind the spectra on the device: ONE copy, the host keeps the layout)
         const OutLayout o = out_layout(g);
-        TLS_HIP(ctx, hipMemcpyAsync(o.sde, pb.sde, (11 + stats_out + peaks_out + fits_out) * (size_t)group * 8, hipMemcpyDeviceToHost, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(o.sde, pb.sde, (11 + stats_out + peaks_out + fits_out + scans_out) * (size_t)group * 8, hipMemcpyDeviceToHost, ctx->stream));
         if (out_chi2) {
             TLS_HIP(ctx, hipMemcpyAsync(o.chi2, sl.d_chi2.ptr, (size_t)gc * np * 8, hipMemcpyDeviceToHost, ctx->stream));
             TLS_HIP(ctx, hipMemcpyAsync(o.chi2 + (size_t)group * np, sl.d_row.ptr, (size_t)gc * np * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -3113,6 +3271,9 @@ static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, cons
                 const int rc2 = read_peak_fits(ctx, *pf, o.fits, group, c, c0 + c);
                 if (rc2) return rc2;
             }
+        if (scans_out)   // (fit f = c k + r of the group: curve c's k records lie side by side)
+            for (int64_t c = 0; c < gc; ++c)
+                std::memcpy(ps->out + (size_t)(c0 + c) * (size_t)pf->k, o.scans + (size_t)c * scans_out, scans_out * 8);
         if (out_chi2) {
             std::memcpy(out_chi2 + c0 * n_periods, o.chi2, (size_t)gc * np * 8);
             std::memcpy(out_row + c0 * n_periods, o.chi2 + (size_t)group * np, (size_t)gc * np * 8);

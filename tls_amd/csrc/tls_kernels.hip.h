@@ -4297,5 +4297,6 @@ __global__ void __launch_bounds__(512) tls_transit_models(const ModelsArgs a) {
 // survey-mode periodogram peaks (tls_find_peaks, tls_power_batch_peaks)
 #include "tls_peaks.hip.h"
 #include "tls_peak_fits.hip.h"
+#include "tls_phase_scan.hip.h"
 
 }  // namespace tlsdev

@@ -237,7 +237,8 @@ HARMONICS = (0.5, 2.0, 1 / 3, 3.0, 2 / 3, 1.5)
 
 def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_arrays=False, devices=None, statistics=False,
                 per_transit=False, models=False, detrend=None, peaks=None, peak_separation=0.02, peak_ratios=HARMONICS,
-                peak_min_power=None, peak_fits=False, **power_kwargs):
+                peak_min_power=None, peak_fits=False, phase_scan=False, phase_scan_max_bins=4096, phase_scan_min_count=3,
+                **power_kwargs):
     """Survey-mode power(): for every light curve of `flux_batch` what `transitleastsquares(t, flux).power(**kwargs)`
     reports as SDE, SDE_raw, chi2_min, period, T0, depth and duration (fractional, lc_cache_overview["duration"] of
     the template row at the chi^2 minimum, main.py:199-200) -- search, SDE spectra and final T0 fit all on the
@@ -286,13 +287,22 @@ def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_ar
     wherever index_best == index_power.  Summary, statistics and the other peak fields do not change.  peak_fits without
     peaks, or with models=True, raises ValueError before any device work.
 
+    phase_scan=True (with peak_fits=True) adds the secondary-eclipse phase scan of every peak -- the test against an
+    eclipsing binary found at its true period, as odd_even_mismatch is the test against one found at half of it -- on the
+    device behind each slab's fits (tls_power_batch_phase_scan), from the period, T0 and duration_days of the fit records
+    there, 96 bytes more per peak in the same copy.  The `peaks` array gains the fields phase_scan_fields() (phase_scan below
+    states the scan): scan_status is 1 and the others NaN where status != 0.  phase_scan_max_bins and phase_scan_min_count are
+    phase_scan's max_bins and min_count.  Everything else of the result stays as it is, bit for bit.  phase_scan without
+    peak_fits, or with a bad max_bins or min_count, raises ValueError before any device work.
+
     Returns (summary, periods[, chi2, row, depth, power][, per_transit][, models][, peaks]): summary is a numpy structured
     array with the fields of tls_power_summary plus "duration" (and the statistics on request)."""
     return _power_batch(t, flux_batch, dy_batch, power_kwargs, context=context, device=device, devices=devices,
                         with_arrays=with_arrays, statistics=statistics, per_transit=per_transit, models=models,
                         detrend=detrend, peaks=_peaks_request(peaks, peak_separation, peak_ratios, peak_min_power, models,
                                                               peak_fits),
-                        peak_fits=bool(peak_fits))
+                        peak_fits=bool(peak_fits),
+                        phase_scan=_phase_scan_request(phase_scan, peak_fits, phase_scan_max_bins, phase_scan_min_count))
 
 
 def _peaks_request(peaks, separation, ratios, min_power, models=False, peak_fits=False):
@@ -344,6 +354,78 @@ def _with_fits(peaks, fits, factor):
     return out
 
 
+def _phase_scan_request(phase_scan, peak_fits, max_bins, min_count):
+    """None, or the checked (max_bins, min_count) of a phase_scan=True request (ValueError for a bad one, and for phase_scan
+    without peak_fits)."""
+    if not phase_scan:
+        return None
+    if not peak_fits:
+        raise ValueError("phase_scan=True needs peak_fits=True: the scans read T0 and duration of the fits")
+    from ._lib import phase_scan_arguments
+    return phase_scan_arguments(max_bins, min_count)
+
+
+def phase_scan_fields():
+    """The fields of a phase scan, in order -- what phase_scan returns and power_batch(..., phase_scan=True) adds to the
+    `peaks` array: scan_status (tls_phase_record.status; the peaks array has the fit's `status` already), the other fields of
+    tls_phase_record, secondary_significance, primary_significance."""
+    from ._lib import PHASE_SCAN_FIELDS
+    return ("scan_status",) + tuple(PHASE_SCAN_FIELDS[1:]) + ("secondary_significance", "primary_significance")
+
+
+def _with_scans(records, scans):
+    """`records` (None, or the peaks with their fits) plus the device's scan records and the two significances,
+    (depth - scan_mean) / scan_std: NaN without a scatter, +-inf or NaN where the scatter is zero."""
+    names = phase_scan_fields()
+    base = [] if records is None else records.dtype.descr
+    out = numpy.zeros(scans.shape, dtype=base + [(k, "f8") for k in names])
+    if records is not None:
+        for k in records.dtype.names:
+            out[k] = records[k]
+    for k, source in zip(names, scans.dtype.names):
+        out[k] = scans[source]
+    with numpy.errstate(all="ignore"):
+        out["secondary_significance"] = (scans["secondary_depth"] - scans["scan_mean"]) / scans["scan_std"]
+        out["primary_significance"] = (scans["primary_depth"] - scans["scan_mean"]) / scans["scan_std"]
+    return out
+
+
+def phase_scan(t, flux_batch, period, T0, duration, curve=None, max_bins=4096, min_count=3, context=None, device=None):
+    """The secondary-eclipse phase scan of candidates the caller holds, on the device (tls_phase_scan): candidate f is
+    (period[f], T0[f], duration[f] in days) on light curve curve[f] of flux_batch [n_curves, n] (or one row [n]) over the
+    finite time stamps t; curve=None takes one candidate a curve, in order.  It needs no search.  The curve is folded into B
+    bins no narrower than half a duration, a window is two neighbouring bins -- a box of about one duration -- and every
+    window's depth is measured against the rest of the baseline (unweighted, as the reference's statistics are):
+
+        status 1 and NaN everywhere else unless P, T0, d are finite, P > 0, d > 0 and q = 2.0 * P / d >= 16
+        B = int(min(floor(q), max_bins))
+        for i ascending:  x = (t[i] - T0) / P;  phi = x - floor(x);  b = min(int(phi * B), B - 1);  S[b] += y[i];  N[b] += 1
+        W[j] = S[j] + S[(j+1)%B],  M[j] = N[j] + N[(j+1)%B];  primary window p = B-1 (phase [-1/B, 1/B))
+        baseline Sb, Nb: bins 2 .. B-3;  inside windows: 2 <= j <= B-4
+        delta[j] = (Sb - W[j]) / (Nb - M[j]) - W[j] / M[j]   inside j with M[j] >= min_count and Nb - M[j] >= 1
+        delta[p] = Sb / Nb - W[p] / M[p]                     if M[p] >= min_count and Nb >= 1
+        js, jb = the first inside j of the largest and of the smallest delta; rest = the valid inside j with |j - js| > 2
+        scan_mean, scan_std = mean and root mean square deviation of delta over rest, where it has 8 windows or more
+
+    Every step is one IEEE double operation and every sum runs in index order, so the result is bit-equal to the Python
+    statement in tests/phase_scan_spec.py.  max_bins in [16, 4096], min_count >= 1; ValueError otherwise, before any device
+    work.
+
+    Returns a structured array [n_fits] with the fields phase_scan_fields(): scan_status (0 scanned, 1 nothing to scan),
+    n_bins, n_windows, primary_depth and primary_count, secondary_depth, secondary_phase and secondary_count (the deepest
+    window away from the primary: the secondary-eclipse candidate, at phase (js + 1) / B), bump_depth and bump_phase (the
+    most negative window: a brightening), scan_mean and scan_std (the empirical scatter of such a box, red noise included),
+    and secondary_significance and primary_significance, (depth - scan_mean) / scan_std.  Of a planet the secondary
+    significance is that of the largest of B noise windows, 2 to 4; of an eclipsing binary it is many times that."""
+    from ._lib import phase_scan_arguments
+    max_bins, min_count = phase_scan_arguments(max_bins, min_count)
+    if numpy.ndim(flux_batch) not in (1, 2) or numpy.ndim(t) != 1 or numpy.shape(flux_batch)[-1] != numpy.size(t):
+        raise ValueError("flux_batch must be [n] or [n_curves, n] over the time stamps t [n]")
+    ctx = context if context is not None else _search.default_context(device)
+    return _with_scans(None, ctx.phase_scan(t, flux_batch, period, T0, duration, curve=curve, max_bins=max_bins,
+                                            min_count=min_count))
+
+
 def find_peaks(power, periods, k, separation=0.02, ratios=HARMONICS, min_power=None, chi2=None, row=None, depth=None,
                context=None, device=None):
     """The k harmonic-aware peaks of a periodogram the caller holds -- power [n_periods] or [n_rows, n_periods] over `periods`
@@ -380,9 +462,10 @@ def find_peaks(power, periods, k, separation=0.02, ratios=HARMONICS, min_power=N
 
 def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=None, devices=None, with_arrays=False,
                  statistics=False, per_transit=False, models=False, spectra=False, detrend=None, peaks=None,
-                 peak_fits=False):
+                 peak_fits=False, phase_scan=None):
     """power_batch; spectra=True (power_results) also returns SR and power_raw [n_curves, n_periods] behind the arrays;
-    peaks: None or a checked request (_peaks_request); peak_fits: with peaks, their T0 fits and statistics."""
+    peaks: None or a checked request (_peaks_request); peak_fits: with peaks, their T0 fits and statistics; phase_scan: None or a checked
+    request (_phase_scan_request), with peak_fits, the fits' phase scans."""
     models = bool(models)
     per_transit = bool(per_transit or models)
     statistics = bool(statistics or per_transit)
@@ -407,7 +490,7 @@ def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=Non
         kw.update(statistics=(fill_factor, root, max_epochs), per_transit=per_transit,
                   models=_model_template(inp) if models else None, lc_cap=_lc_cap(len(inp["t"]), max_epochs) if models else 0)
     if peak_fits:
-        kw.update(peak_fits=(fill_factor, root, max_epochs))
+        kw.update(peak_fits=(fill_factor, root, max_epochs), phase_scan=phase_scan)
 
     def call(ctx, lo, hi):
         return ctx._power_batch(inp["t"], y_rows[lo:hi], dy_rows[lo:hi], inp["periods"], inp["table"], inp["params"],
@@ -460,6 +543,8 @@ def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=Non
         if peak_fits:
             from .stats import limb_darkening_factor
             records = _with_fits(records, out["peak_fits"], limb_darkening_factor(inp["limb_dark"], inp["u"]))
+            if phase_scan is not None:
+                records = _with_scans(records, out["phase_scans"])
         result += (dict(peaks=records, n_peaks=out["n_peaks"]),)
     if spectra:
         result += (out["SR"], out["power_raw"])
