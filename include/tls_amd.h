@@ -38,7 +38,7 @@ extern "C" {
  * signature keep the version (7: tls_inject_transits, tls_null_rows, tls_debug_null_words,
  * tls_medfilt_detrend, tls_biweight_detrend), (7: tls_power_batch_peaks, tls_find_peaks),
  * (7: tls_power_batch_peak_fits, tls_debug_peak_fits), (7: tls_phase_scan, tls_power_batch_phase_scan,
- * tls_debug_peak_phase_scans). */
+ * tls_debug_peak_phase_scans), (7: tls_sysrem). */
 #define TLS_AMD_ABI_VERSION 7
 
 #define TLS_OK 0
@@ -417,6 +417,47 @@ int tls_medfilt_detrend(tls_ctx *ctx, const double *y, int64_t n, int64_t n_rows
  * infinite or non-positive y; n_rows == 0 is a no-op. */
 int tls_biweight_detrend(tls_ctx *ctx, const double *t, const double *y, int64_t n, int64_t n_rows,
                          double window_length, double break_tolerance, double *out_flat, double *out_trend);
+
+/* ---- survey-mode detrending: SysRem, the systematics the rows share, fitted across them on the device ------------- */
+/* The lanes of a row sum and the rows of a column sum's chunk (both part of the definition below), the most components and
+ * the most iterations per component (tls_amd._lib.SYSREM_* mirror them). */
+#define TLS_SYSREM_LANES 256
+#define TLS_SYSREM_ROW_CHUNK 32
+#define TLS_SYSREM_MAX_COMPONENTS 8
+#define TLS_SYSREM_MAX_ITER 1000
+/* SysRem (Tamuz, Mazeh & Zucker 2005) over the rows of y [n_rows][n] on shared epochs: K = n_components rank-1 terms
+ * c_i * a_j (star coefficient times epoch profile) are fitted to the residual matrix by alternating weighted least squares and
+ * divided out.  Every step is one IEEE double operation without contraction, and two reduction orders are part of the
+ * definition:
+ *   rowsum(v[0..n)): lane l of TLS_SYSREM_LANES adds v[l], v[l+256], ... in ascending order, starting from 0.0; the 256
+ *     partials are folded by the fixed tree: for s = 128, 64, ..., 1: p[l] = p[l] + p[l+s] for l < s; the result is p[0].
+ *   colsum(v[0..n_rows)): chunks of TLS_SYSREM_ROW_CHUNK consecutive rows, each summed in ascending row order from 0.0; the
+ *     chunk sums added in ascending chunk order from 0.0.
+ * The fit (all y finite and > 0; dy, when given, [n_rows][n] finite and > 0):
+ *   m_i = rowsum(y_i) / n;  x_ij = y_ij / m_i - 1.0
+ *   with dy: r = dy_ij / m_i; w_ij = 1.0 / (r * r)
+ *   without: v_i = rowsum(x_i * x_i) / n; w_ij = v_i > 0 ? 1.0 / v_i : 0.0 (a constant row carries no weight and comes out
+ *     as y / m)
+ *   for k = 0 .. K-1, from c_i = 1.0 and a_prev_j = 0.0, iterations 1 .. max_iter:
+ *     a_j = colsum_i((x_ij * c_i) * w_ij) / colsum_i((c_i * c_i) * w_ij), or 0.0 where the denominator is not > 0
+ *     c_i = rowsum_j((x_ij * a_j) * w_ij) / rowsum_j((a_j * a_j) * w_ij), or 0.0 likewise
+ *     the component is finished after the iteration in which max_j |a_j - a_prev_j| <= tol * max_j |a_j|; otherwise
+ *     a_prev = a and the next iteration runs
+ *     after the last iteration: x_ij = x_ij - c_i * a_j, C[i][k] = c_i, A[k][j] = a_j, iters[k] = iterations run
+ *   s_ij = 0.0; for k ascending: s_ij = s_ij + C[i][k] * A[k][j]
+ *   trend_ij = m_i * (1.0 + s_ij);  flat_ij = y_ij / trend_ij
+ * The maxima are exact in any order and everything else has its order fixed, so the result -- out_iters and the stop
+ * decision included -- is bit-equal to a restatement of these lines in numpy (tests/sysrem_spec.py).  dy, out_trend, out_c
+ * [n_rows][K], out_a [K][n] and out_iters [K] may be NULL.  The whole call is one stream submission: max_iter iterations per
+ * component are enqueued, and the launches behind a component's convergence return at once on a device-side flag.
+ * TLS_E_ARG, before any device work, for n outside [1, 1e8], n_rows < 2, n_components outside [1, min(
+ * TLS_SYSREM_MAX_COMPONENTS, n_rows - 1)], max_iter outside [1, TLS_SYSREM_MAX_ITER], a tol that is negative or not finite
+ * (0 is allowed: a component then stops only when a repeats itself exactly), and a NaN, infinite or non-positive y or dy.
+ * TLS_E_ARG after the device work where a trend value is not finite and > 0 (the fit can overshoot with wildly unequal dy): the
+ * message names the first such (row, point), the outputs are unspecified and the context stays usable. */
+int tls_sysrem(tls_ctx *ctx, const double *y, const double *dy, int64_t n, int64_t n_rows,
+               int64_t n_components, int64_t max_iter, double tol,
+               double *out_flat, double *out_trend, double *out_c, double *out_a, int64_t *out_iters);
 
 /* ---- survey mode: the K harmonic-aware peaks of a periodogram, found on the device -------------------------------- */
 /* One peak.  chi2, depth and row are the search's values at the peak's index (NaN / -1 where the call has no source for

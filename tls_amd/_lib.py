@@ -26,6 +26,12 @@ BIWEIGHT_MAX_WINDOW = 4095
 BIWEIGHT_C = 5.0
 BIWEIGHT_FTOL = 1e-6
 BIWEIGHT_MAX_ITER = 50
+# include/tls_amd.h TLS_SYSREM_*: the lanes of a row sum and the rows of a column sum's chunk (both part of tls_sysrem's
+# definition), the most components and the most iterations per component
+SYSREM_LANES = 256
+SYSREM_ROW_CHUNK = 32
+SYSREM_MAX_COMPONENTS = 8
+SYSREM_MAX_ITER = 1000
 # include/tls_amd.h TLS_PEAKS_*: the most peaks per row and the most harmonic ratios tls_find_peaks takes
 PEAKS_MAX_K = 32
 PEAKS_MAX_RATIOS = 16
@@ -43,7 +49,7 @@ SYMBOLS = (
     "tls_debug_post_search", "tls_debug_device_bytes", "tls_debug_perm_table", "tls_power_batch_stats", "tls_debug_transit_stats",
     "tls_power_batch_models", "tls_debug_transit_models",
     "tls_inject_transits", "tls_null_rows", "tls_debug_null_words", "tls_medfilt_detrend",
-    "tls_biweight_detrend", "tls_find_peaks", "tls_power_batch_peaks", "tls_power_batch_peak_fits", "tls_debug_peak_fits",
+    "tls_biweight_detrend", "tls_sysrem", "tls_find_peaks", "tls_power_batch_peaks", "tls_power_batch_peak_fits", "tls_debug_peak_fits",
     "tls_phase_scan", "tls_power_batch_phase_scan", "tls_debug_peak_phase_scans",
     "tls_comm_unique_id", "tls_comm_init", "tls_comm_destroy", "tls_comm_info", "tls_comm_allgather_results", "tls_comm_allgather_device", "tls_comm_fetch_gathered",
     "tls_comm_stage_results", "tls_comm_allgather_staged", "tls_comm_fetch_staged",
@@ -349,6 +355,9 @@ def load():
     lib.tls_biweight_detrend.restype = ci
     lib.tls_biweight_detrend.argtypes = [vp, _c_double_p, _c_double_p, i64, i64, ctypes.c_double, ctypes.c_double,
                                          _c_double_p, _c_double_p]
+    lib.tls_sysrem.restype = ci
+    lib.tls_sysrem.argtypes = [vp, _c_double_p, _c_double_p, i64, i64, i64, i64, ctypes.c_double, _c_double_p, _c_double_p,
+                               _c_double_p, _c_double_p, _c_int64_p]
     peaks = [i64, dbl, _c_double_p, i64, dbl, ctypes.c_void_p, _c_int64_p]
     lib.tls_find_peaks.restype = ci
     lib.tls_find_peaks.argtypes = [vp, _c_double_p, _c_double_p, _c_int64_p, _c_double_p, i64, i64, _c_double_p] + peaks
@@ -506,6 +515,49 @@ def biweight_arguments(t, y, window_length, break_tolerance):
     if rows.size and not (rows.min() > 0.0 and rows.max() < numpy.inf):
         raise ValueError("flux has a NaN, infinite or non-positive value: the biweight filter needs flux > 0")
     return t, numpy.ascontiguousarray(rows), wl, bt
+
+
+def _sysrem_integer(name, value, low, high, what):
+    """value as an int in [low, high]; ValueError otherwise (a bool or a non-integer included)."""
+    if isinstance(value, (bool, numpy.bool_)):
+        raise ValueError("%s must be an integer, got %r" % (name, value))
+    try:
+        v = operator.index(value)
+    except TypeError:
+        raise ValueError("%s must be an integer, got %r" % (name, value))
+    if not low <= v <= high:
+        raise ValueError("%s must be in [%d, %s], got %d" % (name, low, what, v))
+    return v
+
+
+def sysrem_arguments(y, n_components=1, dy=None, max_iter=50, tol=1e-6):
+    """(rows [n_rows, n] float64, dy rows or None, n_components, max_iter, tol), checked as tls_sysrem checks them: y
+    [n_rows, n] with n_rows >= 2 and n in [1, 1e8]; n_components an integer in [1, min(SYSREM_MAX_COMPONENTS, n_rows - 1)];
+    max_iter an integer in [1, SYSREM_MAX_ITER]; tol finite and >= 0; every y value, and every dy value of a dy (None, or
+    the shape of y), finite and > 0.  ValueError otherwise."""
+    rows = numpy.asarray(y, dtype=numpy.float64)
+    if rows.ndim != 2 or rows.shape[0] < 2 or not 1 <= rows.shape[1] <= 100000000:
+        raise ValueError("flux must have shape [n_rows, n] with n_rows >= 2 (SysRem fits across the rows) and n in [1, 1e8], "
+                         "got %s" % (numpy.shape(y),))
+    k = _sysrem_integer("n_components", n_components, 1, min(SYSREM_MAX_COMPONENTS, rows.shape[0] - 1),
+                        "min(SYSREM_MAX_COMPONENTS = %d, n_rows - 1 = %d)" % (SYSREM_MAX_COMPONENTS, rows.shape[0] - 1))
+    iters = _sysrem_integer("max_iter", max_iter, 1, SYSREM_MAX_ITER, "SYSREM_MAX_ITER = %d" % SYSREM_MAX_ITER)
+    if isinstance(tol, (bool, numpy.bool_)) or not isinstance(tol, numbers.Real):
+        raise ValueError("tol must be a number, got %r" % (tol,))
+    tol = float(tol)
+    if not 0.0 <= tol < numpy.inf:
+        raise ValueError("tol must be finite and >= 0, got %r" % (tol,))
+    # (min and max propagate a NaN, which then fails both comparisons)
+    if not (rows.min() > 0.0 and rows.max() < numpy.inf):
+        raise ValueError("flux has a NaN, infinite or non-positive value: SysRem needs flux > 0")
+    if dy is not None:
+        dy = numpy.asarray(dy, dtype=numpy.float64)
+        if dy.shape != rows.shape:
+            raise ValueError("dy must be None or have the shape of flux %s, got %s" % (rows.shape, dy.shape))
+        if not (dy.min() > 0.0 and dy.max() < numpy.inf):
+            raise ValueError("dy has a NaN, infinite or non-positive value: SysRem needs dy > 0")
+        dy = numpy.ascontiguousarray(dy)
+    return numpy.ascontiguousarray(rows), dy, k, iters, tol
 
 
 def _f8(a):
@@ -968,6 +1020,26 @@ class Context(object):
             flat, trend = flat[0], None if trend is None else trend[0]
         return (flat, trend) if return_trend else flat
 
+    def sysrem(self, y, n_components=1, dy=None, max_iter=50, tol=1e-6, return_trend=False, return_components=False):
+        """SysRem over the rows of y [n_rows, n] (tls_sysrem: n_components rank-1 terms c_i a_j of the residual matrix
+        y_ij / mean_i - 1, fitted across the rows by alternating least squares weighted with dy [n_rows, n], or with each
+        row's variance where dy is None, up to max_iter iterations a component until a moves by at most tol of its largest
+        value): flat = y / trend; then trend with return_trend=True; then (c [n_rows, K], a [K, n], iters [K]) with
+        return_components=True.  ValueError for the arguments sysrem_arguments refuses; RuntimeError where the fit drives a
+        trend value to 0 or below (wildly unequal dy)."""
+        rows, dy, k, iters, tol = sysrem_arguments(y, n_components, dy, max_iter, tol)
+        n_rows, n = rows.shape
+        flat = numpy.empty_like(rows)
+        trend = numpy.empty_like(rows) if return_trend else None
+        c = numpy.empty((n_rows, k)) if return_components else None
+        a = numpy.empty((k, n)) if return_components else None
+        ran = numpy.zeros(k, dtype=numpy.int64) if return_components else None
+        self._check(self._lib.tls_sysrem(self._h, _dp(rows), None if dy is None else _dp(dy), n, n_rows, k, iters, tol,
+                                         _dp(flat), None if trend is None else _dp(trend), None if c is None else _dp(c),
+                                         None if a is None else _dp(a), None if ran is None else _ip(ran)))
+        out = (flat,) + ((trend,) if return_trend else ()) + (((c, a, ran),) if return_components else ())
+        return out[0] if len(out) == 1 else out
+
     def find_peaks(self, power, periods, k, separation=0.02, ratios=(), min_power=None, chi2=None, row=None, depth=None):
         """The k harmonic-aware peaks of every row of power [n_rows, n_periods] (or one row) over `periods`, selected on the
         device (tls_find_peaks; the selection: include/tls_amd.h, tests/peaks_spec.py): (peaks (PEAK_DTYPE [n_rows, k]),
@@ -1138,7 +1210,7 @@ class Context(object):
             self._check(rc)
         names = ("lds_carve", "list_capacity", "dot_window", "predicate_read", "sort_window", "work_item",
                  "singles_capacity", "tile_stage", "screen_split", "detrend_slot",
-                 "biweight_slot")
+                 "biweight_slot", "sysrem_index")
         return bool(rc), dict(zip(names, [int(v) for v in arr]))
 
     def poison_lds(self, word=0x7ff80000):

@@ -208,6 +208,9 @@ struct tls_ctx {
     DevBuf<unsigned long long> d_null_words;     // tls_debug_null_words: the words of one slab
     DevBuf<double> d_detrend;       // tls_medfilt_detrend, tls_biweight_detrend: rows | flat rows | trend rows of one slab
     DevBuf<int> d_windows;          // tls_biweight_detrend: lo [n] | hi [n], the window of every point
+    // tls_sysrem: y | x | flat | dy | w (without dy: one weight a row) [| trend] | m | c [K] rows | a [K] | chunk partials
+    DevBuf<double> d_sysrem;
+    DevBuf<unsigned long long> d_sysrem_state;   // ... and its state words (tlsdev::kSysremState)
     DevBuf<double> d_peaks;         // tls_find_peaks: periods | records of one slab | power [| chi2 | depth | row] rows of one slab
     DevBuf<unsigned long long> d_peak_mask;      // ... and tls_power_batch_peaks: a row's alive mask where the LDS does not hold it
     // the peak-fit stage (tls_power_batch_peak_fits), one slab of fits: picks | per-transit rows | signals | fit parameters |
@@ -1625,7 +1628,7 @@ void tls_ctx_destroy(tls_ctx* ctx) {
     ctx->d_partials.release(); ctx->d_tiles_done.release(); ctx->d_check.release(); ctx->d_spec.release(); ctx->d_queue.release(); ctx->d_squeue.release(); ctx->d_pqueues.release(); ctx->d_phase.release(); ctx->d_lists.release(); ctx->d_perm.release(); ctx->d_perm_table.release(); ctx->d_curve_S0.release(); ctx->d_curve_w0.release();
     ctx->d_ft.release(); ctx->d_fy.release(); ctx->d_fsig.release(); ctx->d_fep.release(); ctx->d_fres.release(); ctx->d_fscratch.release(); ctx->d_frot.release(); ctx->d_frperm.release(); ctx->d_pink.release();
     ctx->d_tstats.release(); ctx->d_tranges.release(); ctx->d_models.release(); ctx->d_inject.release(); ctx->d_inject_count.release();
-    ctx->d_null.release(); ctx->d_null_words.release(); ctx->d_detrend.release(); ctx->d_windows.release(); ctx->d_peaks.release(); ctx->d_peak_mask.release();
+    ctx->d_null.release(); ctx->d_null_words.release(); ctx->d_detrend.release(); ctx->d_windows.release(); ctx->d_sysrem.release(); ctx->d_sysrem_state.release(); ctx->d_peaks.release(); ctx->d_peak_mask.release();
     ctx->d_pfit.release(); ctx->d_pfep.release(); ctx->d_pfres.release(); ctx->d_pfstats.release(); ctx->d_pfranges.release();
     ctx->d_scan.release();
     ctx->d_split.release(); ctx->d_park.release(); ctx->d_band.release();
@@ -2257,6 +2260,97 @@ int tls_biweight_detrend(tls_ctx* ctx, const double* t, const double* y, int64_t
         // (the next slab overwrites the device rows, and lo / hi live on this stack: the copies have to be done first)
         TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
+    return TLS_OK;
+}
+
+int tls_sysrem(tls_ctx* ctx, const double* y, const double* dy, int64_t n, int64_t n_rows, int64_t n_components,
+               int64_t max_iter, double tol, double* out_flat, double* out_trend, double* out_c, double* out_a,
+               int64_t* out_iters) {
+    if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
+    if (n < 1 || n > 100000000) return fail(ctx, TLS_E_ARG, "sysrem: n out of range [1, 1e8]");
+    if (n_rows < 2) return fail(ctx, TLS_E_ARG, "sysrem: n_rows < 2 (the fit runs across the rows)");
+    if (n_components < 1 || n_components > std::min<int64_t>(TLS_SYSREM_MAX_COMPONENTS, n_rows - 1))
+        return fail(ctx, TLS_E_ARG, "sysrem: n_components out of range [1, min(" + std::to_string(TLS_SYSREM_MAX_COMPONENTS) +
+                                        ", n_rows - 1)]");
+    if (max_iter < 1 || max_iter > TLS_SYSREM_MAX_ITER)
+        return fail(ctx, TLS_E_ARG, "sysrem: max_iter out of range [1, " + std::to_string(TLS_SYSREM_MAX_ITER) + "]");
+    if (!(std::isfinite(tol) && tol >= 0.0)) return fail(ctx, TLS_E_ARG, "sysrem: tol must be finite and >= 0");
+    if (!y || !out_flat) return fail(ctx, TLS_E_ARG, "null argument");
+    if ((uint64_t)n_rows > (uint64_t)(SIZE_MAX / 64) / (uint64_t)n) return fail(ctx, TLS_E_ARG, "sysrem: rows too large");
+    const size_t nn = (size_t)n, R = (size_t)n_rows, K = (size_t)n_components, cells = R * nn;
+    for (size_t q = 0; q < cells; ++q)
+        if (!(std::isfinite(y[q]) && y[q] > 0.0))
+            return fail(ctx, TLS_E_ARG, "sysrem: row " + std::to_string(q / nn) + " has a non-finite or non-positive value");
+    if (dy)
+        for (size_t q = 0; q < cells; ++q)
+            if (!(std::isfinite(dy[q]) && dy[q] > 0.0))
+                return fail(ctx, TLS_E_ARG, "sysrem: dy of row " + std::to_string(q / nn) + " has a non-finite or non-positive value");
+    TLS_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t chunks = (R + TLS_SYSREM_ROW_CHUNK - 1) / TLS_SYSREM_ROW_CHUNK;
+    const size_t matrices = 3 + (dy ? 2 : 0) + (out_trend ? 1 : 0);
+    TLS_HIP(ctx, ctx->d_sysrem.reserve(matrices * cells + (dy ? 1 : 2) * R + K * R + K * nn + 2 * chunks * nn));
+    TLS_HIP(ctx, ctx->d_sysrem_state.reserve(tlsdev::kSysremState));
+    double* at = ctx->d_sysrem.ptr;
+    auto take = [&](size_t count) { double* p = at; at += count; return p; };
+    double* d_y = take(cells);
+    tlsdev::SysremArgs a;
+    a.y = d_y; a.x = take(cells); a.flat = take(cells);
+    double* d_dy = dy ? take(cells) : nullptr;
+    a.dy = d_dy; a.w = dy ? take(cells) : take(R);   // (without dy: one weight a row)
+    a.trend = out_trend ? take(cells) : nullptr;
+    a.m = take(R);
+    a.c = take(K * R); a.a = take(K * nn); a.pnum = take(chunks * nn); a.pden = take(chunks * nn);
+    a.state = ctx->d_sysrem_state.ptr; a.check = nullptr;
+    a.n = (long long)n; a.rows = (long long)n_rows; a.chunks = (long long)chunks;
+    a.tol = tol; a.n_components = (int)n_components; a.k = 0; a.iter = 0;
+#ifdef TLS_DEBUG_CHECKS
+    if (!ctx->d_check.ptr) {
+        TLS_HIP(ctx, ctx->d_check.reserve(tlsdev::kChecks));
+        TLS_HIP(ctx, hipMemsetAsync(ctx->d_check.ptr, 0, tlsdev::kChecks * sizeof(unsigned long long), ctx->stream));
+    }
+    a.check = ctx->d_check.ptr;
+#endif
+    // one submission: the uploads, every launch of every component and the downloads, then one wait
+    TLS_HIP(ctx, hipMemsetAsync(a.state, 0, tlsdev::kSysremState * sizeof(unsigned long long), ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_y, y, cells * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (dy) TLS_HIP(ctx, hipMemcpyAsync(d_dy, dy, cells * 8, hipMemcpyHostToDevice, ctx->stream));
+    const dim3 block(tlsdev::kSysremLanes);
+    const unsigned tiles = (unsigned)((nn + tlsdev::kSysremLanes - 1) / tlsdev::kSysremLanes);
+    const dim3 by_row((unsigned)R), by_column(tiles);
+    const dim3 by_chunk(tiles, (unsigned)std::min<size_t>(chunks, 65535)), by_cell(tiles, (unsigned)std::min<size_t>(R, 65535));
+    hipLaunchKernelGGL(tlsdev::tls_sysrem_prepare, by_row, block, 0, ctx->stream, a);
+    for (int k = 0; k < (int)n_components; ++k) {
+        a.k = k;
+        for (int it = 1; it <= (int)max_iter; ++it) {
+            a.iter = it;
+            hipLaunchKernelGGL(tlsdev::tls_sysrem_columns, by_chunk, block, 0, ctx->stream, a);
+            hipLaunchKernelGGL(tlsdev::tls_sysrem_epochs, by_column, block, 0, ctx->stream, a);
+            hipLaunchKernelGGL(tlsdev::tls_sysrem_rows, by_row, block, 0, ctx->stream, a);
+        }
+        TLS_HIP(ctx, hipGetLastError());
+        if (k + 1 < (int)n_components) hipLaunchKernelGGL(tlsdev::tls_sysrem_subtract, by_cell, block, 0, ctx->stream, a);
+    }
+    hipLaunchKernelGGL(tlsdev::tls_sysrem_apply, by_cell, block, 0, ctx->stream, a);
+    TLS_HIP(ctx, hipGetLastError());
+    ctx->last_kernel = "tls_sysrem_apply";
+    unsigned long long state[tlsdev::kSysremState];
+    std::vector<double> c_rows(out_c ? K * R : 0);
+    TLS_HIP(ctx, hipMemcpyAsync(out_flat, a.flat, cells * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (out_trend) TLS_HIP(ctx, hipMemcpyAsync(out_trend, a.trend, cells * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (out_c) TLS_HIP(ctx, hipMemcpyAsync(c_rows.data(), a.c, K * R * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (out_a) TLS_HIP(ctx, hipMemcpyAsync(out_a, a.a, K * nn * 8, hipMemcpyDeviceToHost, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(state, a.state, sizeof state, hipMemcpyDeviceToHost, ctx->stream));
+    TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (state[tlsdev::kSysremBad]) {
+        const unsigned long long first = ~state[tlsdev::kSysremBad];
+        return fail(ctx, TLS_E_ARG, "sysrem: the trend of row " + std::to_string(first / nn) + ", point " +
+                                        std::to_string(first % nn) + " is not finite and > 0 (the fit overshoots: check dy)");
+    }
+    if (out_c)   // (the device keeps one row per component)
+        for (size_t i = 0; i < R; ++i)
+            for (size_t k = 0; k < K; ++k) out_c[i * K + k] = c_rows[k * R + i];
+    if (out_iters)
+        for (size_t k = 0; k < K; ++k) out_iters[k] = (int64_t)state[tlsdev::kSysremIters + k];
     return TLS_OK;
 }
 

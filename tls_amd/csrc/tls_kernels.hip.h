@@ -88,6 +88,7 @@ enum CheckCode {
     kChkSplit = 8,         // fp32 screen: a sample is not the exact sum of its two fp32 halves
     kChkDetrend = 9,       // tls_medfilt_detrend: an LDS index outside the staged slots, or a median outside the span
     kChkBiweight = 10,     // tls_biweight_detrend: a span over its LDS, or an LDS index outside the staged slots
+    kChkSysrem = 11,       // tls_sysrem: a row, a chunk or a component count outside the call's
 };
 
 constexpr int kWave = 64;
@@ -4293,6 +4294,9 @@ __global__ void __launch_bounds__(512) tls_transit_models(const ModelsArgs a) {
 
 // survey-mode biweight detrending (tls_biweight_detrend), on tls_detrend.hip.h's staging and sort
 #include "tls_biweight.hip.h"
+
+// survey-mode removal of shared systematics across the rows (tls_sysrem)
+#include "tls_sysrem.hip.h"
 
 // survey-mode periodogram peaks (tls_find_peaks, tls_power_batch_peaks)
 #include "tls_peaks.hip.h"

@@ -208,27 +208,107 @@ def biweight_batch(t, flux_batch, window_length=0.5, break_tolerance=0.5, return
     return (flat, trend) if return_trend else flat
 
 
-def _detrended(t, flux_batch, detrend, context, device, devices):
-    """flux_batch as it is (detrend None), biweight_batch (detrend a Biweight) or detrend_batch(flux_batch, detrend) on the
-    call's devices for [n_curves, len(t)]."""
+# ---- detrending: SysRem, the systematics the batch shares, fitted across its rows on the device ---------------------------
+class SysRem(collections.namedtuple("SysRem", ("n_components", "max_iter", "tol"))):
+    """detrend=SysRem(n_components=1, max_iter=50, tol=1e-6) on search_batch, power_batch and power_results: the shared
+    systematics of the WHOLE batch fitted across its rows and divided out (sysrem_batch).  An immutable value; its fields
+    are checked where it is used."""
+    __slots__ = ()
+
+    def __new__(cls, n_components=1, max_iter=50, tol=1e-6):
+        return super(SysRem, cls).__new__(cls, n_components, max_iter, tol)
+
+
+def sysrem_batch(flux_batch, n_components=1, dy_batch=None, max_iter=50, tol=1e-6, return_trend=False,
+                 return_components=False, context=None, device=None):
+    """flat = flux / trend for the rows of flux_batch [n_curves, n] on shared epochs, with trend the systematics the rows
+    SHARE, fitted across them on the device (tls_sysrem): SysRem (Tamuz, Mazeh & Zucker 2005), the ensemble step of WASP, HAT,
+    NGTS and the Kepler / TESS cotrending.  Pointing jitter, momentum dumps, thermal ramps and airmass reach every star at the
+    same epochs, each with its own strength; a per-row filter (detrend_batch, biweight_batch) cannot tell such an event from
+    a transit of the same length, a fit across the rows can.
+
+    With x_ij = flux_ij / mean_i - 1, every component is a rank-1 term c_i a_j (star coefficient times epoch profile) fitted
+    by alternating weighted least squares from c = 1 -- a_j = sum_i x c w / sum_i c c w, then c_i = sum_j x a w / sum_j a a w
+    -- until a moves by at most tol of its largest value, or max_iter iterations; it is subtracted from x before the next
+    one.  The weights are 1 / (dy / mean)^2 with a dy_batch, otherwise one weight a row, 1 / mean(x_i^2) (a constant row
+    carries none and comes out as flux / mean).  trend_ij = mean_i (1 + sum_k c_ik a_kj).  The exact steps and both summation
+    orders are in include/tls_amd.h; each step is one IEEE double operation, so the result is bit-equal to a numpy restatement
+    of them, the iteration counts included.  n_components is in [1, min(SYSREM_MAX_COMPONENTS = 8, n_curves - 1)], max_iter
+    in [1, SYSREM_MAX_ITER = 1000], tol finite and >= 0, and every flux and dy value finite and > 0; the arguments are checked
+    before any device work.  A star's own variability is not modelled: a strongly variable star pulls a component towards
+    itself.
+
+    The fit spans the batch, so it runs on ONE device (context, or device's default context) and takes no devices=.  Returns
+    flat[, trend][, (c [n_curves, K], a [K, n], iters [K])]."""
+    from ._lib import sysrem_arguments
+    rows, dy, k, iters, tol = sysrem_arguments(flux_batch, n_components, dy_batch, max_iter, tol)
+    ctx = context if context is not None else _search.default_context(device)
+    return ctx.sysrem(rows, k, dy=dy, max_iter=iters, tol=tol, return_trend=return_trend, return_components=return_components)
+
+
+def _detrend_steps(detrend):
+    """The steps of a detrend= argument, left to right: () for None, the one step of an int, a Biweight or a SysRem, and
+    the elements of a tuple or list of those."""
     if detrend is None:
+        return ()
+    if isinstance(detrend, (Biweight, SysRem)) or not isinstance(detrend, (tuple, list)):
+        return (detrend,)
+    for step in detrend:
+        if step is None or (isinstance(step, (tuple, list)) and not isinstance(step, (Biweight, SysRem))):
+            raise ValueError("a step of detrend must be a kernel size, a Biweight or a SysRem, got %r" % (step,))
+    return tuple(detrend)
+
+
+def _no_ensemble_step(detrend, caller):
+    """ValueError for a SysRem among the steps of detrend, in the calls whose rows all come from ONE star."""
+    if any(isinstance(step, SysRem) for step in _detrend_steps(detrend)):
+        raise ValueError("%s forms its rows from ONE star, so a fit across the rows is meaningless there: detrend=SysRem "
+                         "belongs on search_batch, power_batch and power_results" % caller)
+
+
+def _first_context(context, device, devices, n_curves):
+    """(context, lock) of the one device an ensemble step runs on: the given context, the first device of `devices` (with
+    its group's lock), or device's default context."""
+    kind, what = _resolve(devices, device, context, n_curves)
+    if kind == "group":
+        return what.contexts[0], what._lock
+    return (context if context is not None else _search.default_context(what)), contextlib.nullcontext()
+
+
+def _detrended(t, flux_batch, detrend, context, device, devices, dy_batch=None):
+    """flux_batch as it is (detrend None), or taken through the steps of detrend left to right on the call's devices for
+    [n_curves, len(t)]: biweight_batch for a Biweight, the whole batch through SysRem on the first device (weighted with
+    dy_batch where one is given) for a SysRem, detrend_batch(flux_batch, step) otherwise."""
+    steps = _detrend_steps(detrend)
+    if not steps:
         return flux_batch
     if numpy.ndim(flux_batch) != 2 or numpy.shape(flux_batch)[1] != len(t):
         raise ValueError("flux_batch must have shape [n_curves, len(t)]")
-    if isinstance(detrend, Biweight):
-        return biweight_batch(t, flux_batch, detrend.window_length, detrend.break_tolerance, context=context, device=device,
-                              devices=devices)
-    return detrend_batch(flux_batch, detrend, context=context, device=device, devices=devices)
+    for step in steps:
+        if isinstance(step, SysRem):
+            from ._lib import sysrem_arguments
+            rows, dy, k, iters, tol = sysrem_arguments(flux_batch, step.n_components, dy_batch, step.max_iter, step.tol)
+            ctx, lock = _first_context(context, device, devices, len(rows))
+            with lock:
+                flux_batch = ctx.sysrem(rows, k, dy=dy, max_iter=iters, tol=tol)
+        elif isinstance(step, Biweight):
+            flux_batch = biweight_batch(t, flux_batch, step.window_length, step.break_tolerance, context=context,
+                                        device=device, devices=devices)
+        else:
+            flux_batch = detrend_batch(flux_batch, step, context=context, device=device, devices=devices)
+    return flux_batch
 
 
 def _detrend_rows(ctx, t, rows, detrend):
-    """rows as they are (detrend None), or detrended on ctx: the biweight for a Biweight, the median filter of kernel size
-    detrend otherwise (the rows formed on the device by injection_recovery and null_sde, chunk by chunk)."""
-    if detrend is None:
-        return rows
-    if isinstance(detrend, Biweight):
-        return ctx.biweight_detrend(t, rows, detrend.window_length, detrend.break_tolerance)
-    return ctx.medfilt_detrend(rows, detrend)
+    """rows as they are (detrend None), or taken through the per-row steps of detrend on ctx: the biweight for a Biweight, the
+    median filter of kernel size step otherwise (the rows formed on the device by injection_recovery and null_sde, chunk by
+    chunk)."""
+    for step in _detrend_steps(detrend):
+        if isinstance(step, Biweight):
+            rows = ctx.biweight_detrend(t, rows, step.window_length, step.break_tolerance)
+        else:
+            rows = ctx.medfilt_detrend(rows, step)
+    return rows
 
 
 # the period ratios whose neighbourhoods a taken peak suppresses by default: its first harmonics and sub-harmonics
@@ -263,7 +343,10 @@ def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_ar
     detrend=k (an odd kernel size) searches flux_batch / medfilt(flux_batch, k) instead (detrend_batch, on the device; the
     rows come back to the host and go through the search unchanged), so the result equals power_batch on the rows detrended
     beforehand; dy_batch is passed through as it is.  detrend=Biweight(window_length, break_tolerance) searches
-    biweight_batch(t, flux_batch, window_length, break_tolerance) the same way.  detrend=None searches flux_batch as given.
+    biweight_batch(t, flux_batch, window_length, break_tolerance) the same way.  detrend=SysRem(n_components) first removes
+    the systematics the rows SHARE (sysrem_batch: fitted over the WHOLE batch on one device -- the given context, or the
+    first of `devices` -- and weighted with dy_batch where one is given; the rows are then dealt out as before), and a tuple
+    or list applies its steps left to right, e.g. (SysRem(2), Biweight(0.5)).  detrend=None searches flux_batch as given.
 
     peaks=K (1 to 32) also returns the K highest harmonic-aware peaks of every curve's detrended power -- the runners-up of the
     one pick: a second planet, a binary under its alias -- selected on the device from the spectrum it already holds
@@ -473,7 +556,7 @@ def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=Non
         t_check = numpy.asarray(t, dtype=numpy.float64)
         if t_check.ndim != 1 or not numpy.all(t_check[1:] >= t_check[:-1]):
             raise ValueError("%s=True needs ascending time stamps t" % ("statistics" if statistics else "peak_fits"))
-    flux_batch = _detrended(t, flux_batch, detrend, context, device, devices)
+    flux_batch = _detrended(t, flux_batch, detrend, context, device, devices, dy_batch)
     inp, y_rows, dy_rows = _batch_inputs(t, flux_batch, dy_batch, power_kwargs)
     from . import constants as C
     osf = power_kwargs.get("oversampling_factor", C.OVERSAMPLING_FACTOR)
@@ -565,8 +648,9 @@ def power_results(t, flux_batch, dy_batch=None, context=None, device=None, devic
     arrays, about 0.7 MB for the k2_90d configuration (90 days at 48 cadences a day), so 1024 curves take about 0.7 GB, and
     the call's own staging as much again while it runs.  Callers with large batches pass them in chunks.
     devices=[...] deals the batch out over several GPUs, as the other survey calls.  detrend=k searches
-    flux_batch / medfilt(flux_batch, k) (detrend_batch), and detrend=Biweight(...) the rows biweight_batch forms, as
-    power_batch does; the objects then describe the detrended rows."""
+    flux_batch / medfilt(flux_batch, k) (detrend_batch), detrend=Biweight(...) the rows biweight_batch forms,
+    detrend=SysRem(...) the rows sysrem_batch forms and a tuple its steps left to right, as power_batch does; the objects
+    then describe the detrended rows."""
     from .api import transitleastsquares
     from .results import transitleastsquaresresults
     if len(numpy.shape(flux_batch)) != 2 or numpy.shape(flux_batch)[1] != len(t):
@@ -611,9 +695,10 @@ def search_batch(t, flux_batch, dy_batch=None, context=None, device=None, device
     Returns (periods, chi2[n_curves, n_periods], row[...], depth[...]).  All light curves must
     share `t` and be free of invalid points (clean them first); a `dy_batch` must have the same
     weight structure for every curve (all uniform or all per-point).  detrend=k searches flux_batch / medfilt(flux_batch, k)
-    (detrend_batch), and detrend=Biweight(...) the rows biweight_batch forms, as power_batch does.
+    (detrend_batch), detrend=Biweight(...) the rows biweight_batch forms, detrend=SysRem(...) the rows sysrem_batch forms
+    (one fit over the whole batch) and a tuple its steps left to right, as power_batch does.
     """
-    flux_batch = _detrended(t, flux_batch, detrend, context, device, devices)
+    flux_batch = _detrended(t, flux_batch, detrend, context, device, devices, dy_batch)
     inp, y_rows, dy_rows = _batch_inputs(t, flux_batch, dy_batch, power_kwargs)
 
     def call(ctx, lo, hi):
@@ -799,7 +884,8 @@ def injection_recovery(t, flux, injections, dy=None, inject_u=None, inject_limb_
     right after the injection (row / medfilt(row, k), tls_medfilt_detrend) before it is searched, so the transits pass through
     the filter the data pass through, and completeness counts what the filter absorbs.  rows are then the detrended rows;
     n_in_transit and the classification are unchanged, and dy is passed through as it is.  detrend=Biweight(window_length,
-    break_tolerance) does the same with the time-windowed biweight (tls_biweight_detrend, biweight_batch).
+    break_tolerance) does the same with the time-windowed biweight (tls_biweight_detrend, biweight_batch), and a tuple of
+    such steps applies them left to right.  A SysRem raises ValueError: the rows all come from ONE star.
 
     Returns (recovery, summary[, rows]): recovery a structured array -- the injected fields, T14, n_in_transit (points
     with z < 1 + rp_rs: 0 where every transit falls into a gap), period_match, epoch_offset, recovered -- and summary
@@ -824,12 +910,14 @@ def injection_recovery(t, flux, injections, dy=None, inject_u=None, inject_limb_
     # (checked before any device work)
     classify_recovery(table[:0], numpy.zeros(0, dtype=[("period", "f8"), ("T0", "f8"), ("SDE", "f8"), ("no_fit", "i8")]),
                       None, sde_threshold, period_tolerance, aliases, epoch_tolerance)
-    if isinstance(detrend, Biweight):
-        from ._lib import biweight_arguments
-        biweight_arguments(t, flux, detrend.window_length, detrend.break_tolerance)
-    elif detrend is not None:
-        from ._lib import medfilt_arguments
-        medfilt_arguments(flux, detrend)
+    _no_ensemble_step(detrend, "injection_recovery")
+    for step in _detrend_steps(detrend):
+        if isinstance(step, Biweight):
+            from ._lib import biweight_arguments
+            biweight_arguments(t, flux, step.window_length, step.break_tolerance)
+        else:
+            from ._lib import medfilt_arguments
+            medfilt_arguments(flux, step)
     consts = injection_constants(table)
 
     def form(ctx, lo, hi):
@@ -968,7 +1056,8 @@ def null_sde(t, n_trials, sigma=None, source=None, block=None, seed=0, first_tri
     tls_medfilt_detrend) and searches the detrended rows: the null of a pipeline that detrends.  A bootstrap then takes RAW
     source rows, filtered after resampling as the data are.  A row still depends on (seed, R) alone; rows are then the
     detrended rows, and dy is passed through as it is.  detrend=Biweight(window_length, break_tolerance) does the same with
-    the time-windowed biweight (tls_biweight_detrend, biweight_batch).
+    the time-windowed biweight (tls_biweight_detrend, biweight_batch), and a tuple of such steps applies them left to
+    right.  A SysRem raises ValueError: the rows all come from ONE star.
 
     Returns summary, or (summary, rows [n_trials, n]) with return_rows=True."""
     t, mode, sigma, source, block, seed, first_trial = _null_arguments(t, n_trials, sigma, source, block, seed, first_trial)
@@ -982,12 +1071,14 @@ def null_sde(t, n_trials, sigma=None, source=None, block=None, seed=0, first_tri
     chunk = _default_chunk(n) if chunk is None else _integer("chunk", chunk, 1)
     if statistics and not numpy.all(t[1:] >= t[:-1]):
         raise ValueError("statistics=True needs ascending time stamps t")
-    if isinstance(detrend, Biweight):
-        from ._lib import biweight_windows
-        biweight_windows(t, detrend.window_length, detrend.break_tolerance)
-    elif detrend is not None:
-        from ._lib import medfilt_kernel
-        medfilt_kernel(detrend, n)
+    _no_ensemble_step(detrend, "null_sde")
+    for step in _detrend_steps(detrend):
+        if isinstance(step, Biweight):
+            from ._lib import biweight_windows
+            biweight_windows(t, step.window_length, step.break_tolerance)
+        else:
+            from ._lib import medfilt_kernel
+            medfilt_kernel(step, n)
 
     def form(ctx, lo, hi):
         sig = None if mode == 1 else sigma if len(sigma) == 1 else sigma[lo:hi]
