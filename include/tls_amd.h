@@ -38,7 +38,7 @@ extern "C" {
  * signature keep the version (7: tls_inject_transits, tls_null_rows, tls_debug_null_words,
  * tls_medfilt_detrend, tls_biweight_detrend), (7: tls_power_batch_peaks, tls_find_peaks),
  * (7: tls_power_batch_peak_fits, tls_debug_peak_fits), (7: tls_phase_scan, tls_power_batch_phase_scan,
- * tls_debug_peak_phase_scans), (7: tls_sysrem). */
+ * tls_debug_peak_phase_scans), (7: tls_sysrem), (7: tls_single_transits). */
 #define TLS_AMD_ABI_VERSION 7
 
 #define TLS_OK 0
@@ -596,6 +596,45 @@ int tls_debug_peak_phase_scans(tls_ctx *ctx, const double *y, int64_t n_curves, 
                                int64_t k, const double *power, const double *row_duration, int64_t n_rows,
                                double fill_factor, const double *root, int64_t n_root, int64_t max_epochs,
                                tls_peak_fit *out_fits, int64_t max_bins, int64_t min_count, tls_phase_record *out_scans);
+
+/* ---- survey mode: single-transit events ------------------------------------------------------------------------------ */
+/* The unfolded search: a planet that transits once in the window has no periodogram peak.  A template of every trial width
+ * slides along the time series itself.  For a curve (y [n], dy [n] over the ascending, finite t [n]), n_rows rows of strictly
+ * ascending widths L_r in [3, TLS_SINGLE_MAX_WIDTH] samples with shapes b_r[j] (0 out of transit, 1 at the bottom; row r is
+ * shape_values[shape_offset[r] .. + L_r)), span_max[r] in days and depth_min >= 0:
+ *   w = 1.0 / (dy * dy);  xw = (1.0 - y) * w;  bb_r[j] = b_r[j] * b_r[j]
+ *   for every centre c in 0..n-1, rows r ascending (nothing held at first):
+ *       h = (L_r - 1) / 2;  lo = c - h;  hi = lo + L_r - 1
+ *       skip if lo < 0 or hi > n - 1 or not (t[hi] - t[lo] <= span_max[r])           the window runs over a gap
+ *       N = 0; D = 0; for j = 0..L_r-1 ascending: N = N + xw[lo+j] * b_r[j];  D = D + w[lo+j] * bb_r[j]
+ *       d = N / D;  skip if not (d > depth_min)                                      least-squares depth; dips only
+ *       s = N / sqrt(D);  take (s, r, d) if nothing is held or s > held s            the first row wins ties
+ *   ses[c], row[c], depth[c] = held, or NaN, -1, NaN
+ * Events, at most k: a centre is alive where ses[c] is no NaN and ses[c] >= min_ses; its window is [lo, hi] of its own best
+ * row.  Repeat: the alive centre of the largest ses (the lowest index on ties) is taken; with g = int(separation * L) of its
+ * row, every alive centre whose window meets [lo - g, hi + g] leaves (integers only).  Stop at k events or when nothing is
+ * alive.  Every step is one IEEE double operation and every sum runs in the stated order: planes and records equal the Python
+ * statement in tests/single_transit_spec.py bit for bit.  8 doubles; ranks past a curve's n_events hold index -1 and NaN. */
+#define TLS_SINGLE_MAX_WIDTH 4096
+#define TLS_SINGLE_MAX_K 32
+typedef struct tls_single_event {
+    double index, time;            /* c, t[c] */
+    double ses, depth;             /* s and d of the centre's best row */
+    double row, width;             /* r, L_r */
+    double t_first, t_last;        /* t[lo], t[hi] */
+} tls_single_event;
+/* The events of n_curves curves y, dy [n_curves][n] on the shared time stamps t [n]: out_events [n_curves][k], out_n_events
+ * [n_curves]; out_ses, out_depth (double) and out_row (int64) [n_curves][n] are the planes, each NULL (not returned: they stay
+ * in the context's device scratch) or given.  Needs no plan and no search, and leaves a prepared plan as it is.  n_curves == 0
+ * is a no-op.  TLS_E_ARG, before any device work and with the outputs untouched, for n outside [1, 2^20], negative counts,
+ * n_rows < 1, widths not strictly ascending or outside [3, TLS_SINGLE_MAX_WIDTH], a negative shape_offset, k outside
+ * [1, TLS_SINGLE_MAX_K], a non-finite or negative depth_min, separation or span_max, a NaN min_ses, and a t that is not
+ * finite and non-decreasing.  y and dy are taken as they are (dy > 0). */
+int tls_single_transits(tls_ctx *ctx, const double *t, const double *y, const double *dy, int64_t n, int64_t n_curves,
+                        const double *shape_values, const int64_t *shape_offset, const int64_t *width, const double *span_max,
+                        int64_t n_rows, double depth_min, int64_t k, double min_ses, double separation,
+                        tls_single_event *out_events, int64_t *out_n_events, double *out_ses, int64_t *out_row,
+                        double *out_depth);
 
 /* ---- host-only planning (no GPU needed) ------------------------------------------ */
 /* Trial cells (duration x T0 positions) each period will enumerate: the data-independent

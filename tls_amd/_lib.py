@@ -39,6 +39,13 @@ PEAKS_MAX_RATIOS = 16
 PHASE_SCAN_MIN_BINS = 16
 PHASE_SCAN_MAX_BINS = 4096
 PHASE_SCAN_CHUNK = 2048   # tls_phase_scan.hip.h kPhaseChunk: the points of a light curve the scan stages in LDS at a time
+# include/tls_amd.h TLS_SINGLE_*: the widest row and the most events a curve of tls_single_transits; tls_single.hip.h
+# kSingleMinWidth, kSingleTile (the centres of a workgroup of the statistic kernel) and kSingleMaxPoints
+SINGLE_MAX_WIDTH = 4096
+SINGLE_MAX_K = 32
+SINGLE_MIN_WIDTH = 3
+SINGLE_TILE = 256
+SINGLE_MAX_POINTS = 1 << 20
 PEAKS_LDS_PERIODS = 1 << 20   # tls_peaks.hip.h kPeaksLdsPeriods: a longer grid keeps its alive mask in device memory, not in LDS
 
 # every symbol include/tls_amd.h declares (tests check the export list against the header)
@@ -50,7 +57,7 @@ SYMBOLS = (
     "tls_power_batch_models", "tls_debug_transit_models",
     "tls_inject_transits", "tls_null_rows", "tls_debug_null_words", "tls_medfilt_detrend",
     "tls_biweight_detrend", "tls_sysrem", "tls_find_peaks", "tls_power_batch_peaks", "tls_power_batch_peak_fits", "tls_debug_peak_fits",
-    "tls_phase_scan", "tls_power_batch_phase_scan", "tls_debug_peak_phase_scans",
+    "tls_phase_scan", "tls_power_batch_phase_scan", "tls_debug_peak_phase_scans", "tls_single_transits",
     "tls_comm_unique_id", "tls_comm_init", "tls_comm_destroy", "tls_comm_info", "tls_comm_allgather_results", "tls_comm_allgather_device", "tls_comm_fetch_gathered",
     "tls_comm_stage_results", "tls_comm_allgather_staged", "tls_comm_fetch_staged",
     "tls_comm_barrier", "tls_comm_max",
@@ -192,6 +199,104 @@ def phase_scan_arguments(max_bins, min_count):
     if not 1 <= int(min_count) < 2 ** 31:
         raise ValueError("phase scan: min_count must be at least 1, got %r" % (min_count,))
     return int(max_bins), int(min_count)
+
+
+# tls_single_event (include/tls_amd.h): one single-transit event, 8 doubles
+SINGLE_EVENT_FIELDS = ("index", "time", "ses", "depth", "row", "width", "t_first", "t_last")
+
+
+class SingleEvent(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_double) for k in SINGLE_EVENT_FIELDS]
+
+
+SINGLE_EVENT_DTYPE = numpy.dtype([(k, "f8") for k in SINGLE_EVENT_FIELDS])
+
+
+def _single_number(name, value, low=0.0):
+    """value as a float, finite and >= low; ValueError otherwise (a bool or a non-number included)."""
+    if isinstance(value, (bool, numpy.bool_)) or not isinstance(value, numbers.Real):
+        raise ValueError("single transits: %s must be a number, got %r" % (name, value))
+    v = float(value)
+    if not (low <= v < numpy.inf):
+        raise ValueError("single transits: %s must be finite and >= %g, got %r" % (name, low, value))
+    return v
+
+
+def single_widths(widths):
+    """The widths as an int64 array, checked as tls_single_transits checks them: integers, at least one, strictly ascending,
+    in [SINGLE_MIN_WIDTH, SINGLE_MAX_WIDTH]; ValueError otherwise."""
+    try:
+        if any(isinstance(v, (bool, numpy.bool_)) for v in widths):
+            raise TypeError
+        width = numpy.array([operator.index(v) for v in widths], dtype=numpy.int64)
+    except TypeError:
+        raise ValueError("single transits: the widths must be integers, got %r" % (widths,))
+    if len(width) < 1:
+        raise ValueError("single transits: at least one width is needed")
+    if width.min() < SINGLE_MIN_WIDTH or width.max() > SINGLE_MAX_WIDTH:
+        raise ValueError("single transits: every width must be in [%d, %d], got %d to %d"
+                         % (SINGLE_MIN_WIDTH, SINGLE_MAX_WIDTH, width.min(), width.max()))
+    if not numpy.all(width[1:] > width[:-1]):
+        raise ValueError("single transits: the widths must be strictly ascending")
+    return width
+
+
+def single_options(depth_min=0.0, k=8, min_ses=0.0, separation=0.5):
+    """(depth_min, k, min_ses, separation) as tls_single_transits takes them, checked as it checks them: depth_min and
+    separation finite and >= 0, k an integer in [1, SINGLE_MAX_K], min_ses no NaN (None: -inf, no threshold); ValueError
+    otherwise."""
+    if isinstance(k, (bool, numpy.bool_)) or not isinstance(k, numbers.Integral) or not 1 <= int(k) <= SINGLE_MAX_K:
+        raise ValueError("single transits: k must be an integer in [1, %d], got %r" % (SINGLE_MAX_K, k))
+    depth_min = _single_number("depth_min", depth_min)
+    separation = _single_number("separation", separation)
+    if min_ses is None:
+        min_ses = -numpy.inf
+    if isinstance(min_ses, (bool, numpy.bool_)) or not isinstance(min_ses, numbers.Real) or numpy.isnan(min_ses):
+        raise ValueError("single transits: min_ses must be a number and no NaN, got %r" % (min_ses,))
+    return depth_min, int(k), float(min_ses), separation
+
+
+def single_arguments(t, y, dy, widths, shapes, span_max, depth_min=0.0, k=8, min_ses=0.0, separation=0.5):
+    """What tls_single_transits takes, checked as it checks them and packed for it -- a dict with t [n], y and dy
+    [n_curves, n], width [n_rows] (int64), shape_values (the rows of `shapes` back to back), shape_offset [n_rows] (int64),
+    span_max [n_rows], depth_min, k, min_ses, separation.  t is 1-D with n in [1, SINGLE_MAX_POINTS], finite and
+    non-decreasing; y and dy are [n] or [n_curves, n], dy finite and > 0, y finite; widths are integers, strictly ascending,
+    in [SINGLE_MIN_WIDTH, SINGLE_MAX_WIDTH], at least one; shapes[r] holds widths[r] finite values; span_max[r], depth_min
+    and separation are finite and >= 0; k is an integer in [1, SINGLE_MAX_K]; min_ses is no NaN (None: -inf, no threshold).
+    ValueError otherwise.  GPU-free."""
+    t = numpy.asarray(t, dtype=numpy.float64)
+    if t.ndim != 1 or not 1 <= len(t) <= SINGLE_MAX_POINTS:
+        raise ValueError("single transits: t must have shape [n] with n in [1, %d], got %s" % (SINGLE_MAX_POINTS, t.shape))
+    if not numpy.all(numpy.isfinite(t)) or not numpy.all(t[1:] >= t[:-1]):
+        raise ValueError("single transits: t must be finite and non-decreasing")
+    y, dy = numpy.asarray(y, dtype=numpy.float64), numpy.asarray(dy, dtype=numpy.float64)
+    if y.ndim == 1:
+        y = y[None, :]
+    if dy.ndim == 1:
+        dy = dy[None, :]
+    if y.ndim != 2 or y.shape[1] != len(t) or dy.shape != y.shape:
+        raise ValueError("single transits: y and dy must be [n] or [n_curves, n] over the time stamps t [n]")
+    if y.size and not numpy.all(numpy.isfinite(y)):
+        raise ValueError("single transits: y has a NaN or an infinite value")
+    if dy.size and not (dy.min() > 0.0 and dy.max() < numpy.inf):
+        raise ValueError("single transits: dy has a NaN, infinite or non-positive value")
+    width = single_widths(widths)
+    if len(shapes) != len(width):
+        raise ValueError("single transits: %d shapes for %d widths" % (len(shapes), len(width)))
+    rows = [numpy.asarray(b, dtype=numpy.float64) for b in shapes]
+    for r, b in enumerate(rows):
+        if b.shape != (width[r],) or not numpy.all(numpy.isfinite(b)):
+            raise ValueError("single transits: shape %d must hold %d finite values" % (r, width[r]))
+    span = numpy.asarray(span_max, dtype=numpy.float64)
+    if span.shape != width.shape or not numpy.all(numpy.isfinite(span) & (span >= 0.0)):
+        raise ValueError("single transits: span_max must hold one finite value >= 0 a width")
+    depth_min, k, min_ses, separation = single_options(depth_min, k, min_ses, separation)
+    offset = numpy.zeros(len(width), dtype=numpy.int64)
+    offset[1:] = numpy.cumsum(width)[:-1]
+    return dict(t=numpy.ascontiguousarray(t), y=numpy.ascontiguousarray(y), dy=numpy.ascontiguousarray(dy), width=width,
+                shape_values=numpy.ascontiguousarray(numpy.concatenate(rows)), shape_offset=offset,
+                span_max=numpy.ascontiguousarray(span), depth_min=depth_min, k=k, min_ses=min_ses,
+                separation=separation)
 
 
 def peaks_arguments(k, separation, ratios, min_power):
@@ -370,6 +475,10 @@ def load():
     lib.tls_phase_scan.restype = ci
     lib.tls_phase_scan.argtypes = [vp, _c_double_p, _c_double_p, i64, i64, _c_int64_p, _c_double_p, _c_double_p, _c_double_p,
                                    i64, i64, i64, ctypes.c_void_p]
+    lib.tls_single_transits.restype = ci
+    lib.tls_single_transits.argtypes = [vp, _c_double_p, _c_double_p, _c_double_p, i64, i64, _c_double_p, _c_int64_p, _c_int64_p,
+                                        _c_double_p, i64, dbl, i64, dbl, dbl, ctypes.c_void_p, _c_int64_p, _c_double_p,
+                                        _c_int64_p, _c_double_p]
     lib.tls_debug_peak_phase_scans.restype = ci
     lib.tls_debug_peak_phase_scans.argtypes = [vp, _c_double_p, i64, ctypes.c_void_p, _c_int64_p, i64, _c_double_p, _c_double_p,
                                                i64, dbl, _c_double_p, i64, i64, ctypes.c_void_p, i64, i64, ctypes.c_void_p]
@@ -1098,6 +1207,27 @@ class Context(object):
                                              out.ctypes.data_as(ctypes.c_void_p)))
         return out
 
+    def single_transits(self, t, y, dy, widths, shapes, span_max, depth_min=0.0, k=8, min_ses=0.0, separation=0.5,
+                        with_arrays=False):
+        """The single-transit events (tls_single_transits; the search: include/tls_amd.h, tests/single_transit_spec.py) of
+        the curves y, dy [n_curves, n] (or one row) over t [n], for the rows (widths[r], shapes[r], span_max[r]):
+        (events SINGLE_EVENT_DTYPE [n_curves, k], n_events [n_curves]), with_arrays: and the planes ses, row, depth
+        [n_curves, n].  ValueError for what single_arguments refuses."""
+        a = single_arguments(t, y, dy, widths, shapes, span_max, depth_min, k, min_ses, separation)
+        n_c, n = a["y"].shape
+        events = numpy.zeros((n_c, a["k"]), dtype=SINGLE_EVENT_DTYPE)
+        n_events = numpy.zeros(n_c, dtype=numpy.int64)
+        assert SINGLE_EVENT_DTYPE.itemsize == ctypes.sizeof(SingleEvent)
+        ses = depth = row = None
+        if with_arrays:
+            ses, depth, row = numpy.empty((n_c, n)), numpy.empty((n_c, n)), numpy.empty((n_c, n), dtype=numpy.int64)
+        self._check(self._lib.tls_single_transits(
+            self._h, _dp(a["t"]), _dp(a["y"]), _dp(a["dy"]), n, n_c, _dp(a["shape_values"]), _ip(a["shape_offset"]),
+            _ip(a["width"]), _dp(a["span_max"]), len(a["width"]), a["depth_min"], a["k"], a["min_ses"], a["separation"],
+            events.ctypes.data_as(ctypes.c_void_p), _ip(n_events), None if ses is None else _dp(ses),
+            None if row is None else _ip(row), None if depth is None else _dp(depth)))
+        return (events, n_events, ses, row, depth) if with_arrays else (events, n_events)
+
     def debug_null_words(self, n, n_rows, seed, first_trial=0, block=None):
         """The raw Philox words [n_rows, W] tls_null_rows draws for these trials (tls_debug_null_words): white-noise
         layout when `block` is None, the bootstrap's otherwise."""
@@ -1210,7 +1340,7 @@ class Context(object):
             self._check(rc)
         names = ("lds_carve", "list_capacity", "dot_window", "predicate_read", "sort_window", "work_item",
                  "singles_capacity", "tile_stage", "screen_split", "detrend_slot",
-                 "biweight_slot", "sysrem_index")
+                 "biweight_slot", "sysrem_index", "single_window")
         return bool(rc), dict(zip(names, [int(v) for v in arr]))
 
     def poison_lds(self, word=0x7ff80000):

@@ -218,6 +218,8 @@ struct tls_ctx {
     DevBuf<double> d_pfit, d_pfep, d_pfres, d_pfstats;
     DevBuf<int> d_pfranges;
     DevBuf<double> d_scan;          // tls_phase_scan: t | y rows | period | T0 | duration | records | curve of fit
+    // tls_single_transits: t | rows | taps | of one slab: y | dy | ses | depth | events | n_events | row
+    DevBuf<double> d_single;
     // two-role slab path (series in HBM, one light curve; SearchPlan::split)
     View<unsigned int> d_tile_prefix;        // [n_periods + 1] tiles in front of work item w (queue order)
     DevBuf<double> d_partials;               // [split_max_items][3] a tile's winner
@@ -1631,6 +1633,7 @@ void tls_ctx_destroy(tls_ctx* ctx) {
     ctx->d_null.release(); ctx->d_null_words.release(); ctx->d_detrend.release(); ctx->d_windows.release(); ctx->d_sysrem.release(); ctx->d_sysrem_state.release(); ctx->d_peaks.release(); ctx->d_peak_mask.release();
     ctx->d_pfit.release(); ctx->d_pfep.release(); ctx->d_pfres.release(); ctx->d_pfstats.release(); ctx->d_pfranges.release();
     ctx->d_scan.release();
+    ctx->d_single.release();
     ctx->d_split.release(); ctx->d_park.release(); ctx->d_band.release();
     if (ctx->h_band) (void)hipHostFree(ctx->h_band);
     for (auto& ev : ctx->ev_band) if (ev) (void)hipEventDestroy(ev);
@@ -2785,6 +2788,7 @@ int tls_debug_device_bytes(const tls_ctx* ctx, int64_t* total, int64_t* t0_fit_s
     add(ctx->d_peaks); add(ctx->d_peak_mask);
     add(ctx->d_pfit); add(ctx->d_pfep); add(ctx->d_pfres); add(ctx->d_pfstats); add(ctx->d_pfranges);
     add(ctx->d_scan);
+    add(ctx->d_single);
     add(ctx->d_partials); add(ctx->d_tiles_done);
     add(ctx->d_split); add(ctx->d_park); add(ctx->d_band);
     *total = (int64_t)sum;
@@ -3163,6 +3167,125 @@ int tls_phase_scan(tls_ctx* ctx, const double* t, const double* y, int64_t n, in
     TLS_HIP(ctx, hipMemcpyAsync(out, d_out, words * fits * 8, hipMemcpyDeviceToHost, ctx->stream));
     // (h_curve is read by the copy above until the stream is done)
     TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return TLS_OK;
+}
+
+// ---- single-transit events (tls_single.hip.h, DESIGN.md "Single-transit events"): the statistic kernel over (tile, curve)
+// and the selection kernel, one workgroup a curve, slab by slab; the planes stay in the context's scratch unless asked for
+static_assert(sizeof(tls_single_event) == tlsdev::kSingleEventWords * 8, "tls_single_event is the kernel's record");
+static_assert(TLS_SINGLE_MAX_WIDTH == tlsdev::kSingleMaxWidth && TLS_SINGLE_MAX_K == tlsdev::kSingleMaxK, "the header's limits");
+static_assert(sizeof(tlsdev::SingleRow) == 16, "two doubles a row");
+
+int tls_single_transits(tls_ctx* ctx, const double* t, const double* y, const double* dy, int64_t n, int64_t n_curves,
+                        const double* shape_values, const int64_t* shape_offset, const int64_t* width, const double* span_max,
+                        int64_t n_rows, double depth_min, int64_t k, double min_ses, double separation,
+                        tls_single_event* out_events, int64_t* out_n_events, double* out_ses, int64_t* out_row,
+                        double* out_depth) {
+    if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
+    if (n_curves < 0 || n_rows < 0 || n < 0) return fail(ctx, TLS_E_ARG, "single transits: negative count");
+    if (k < 1 || k > TLS_SINGLE_MAX_K) return fail(ctx, TLS_E_ARG, "single transits: k out of range [1, 32]");
+    if (!(std::isfinite(depth_min) && depth_min >= 0.0)) return fail(ctx, TLS_E_ARG, "single transits: depth_min must be finite and >= 0");
+    if (!(std::isfinite(separation) && separation >= 0.0)) return fail(ctx, TLS_E_ARG, "single transits: separation must be finite and >= 0");
+    if (std::isnan(min_ses)) return fail(ctx, TLS_E_ARG, "single transits: min_ses is NaN");
+    if (n_rows < 1) return fail(ctx, TLS_E_ARG, "single transits: at least one row is needed");
+    if (!shape_values || !shape_offset || !width || !span_max) return fail(ctx, TLS_E_ARG, "null argument");
+    if (n_rows > TLS_SINGLE_MAX_WIDTH) return fail(ctx, TLS_E_ARG, "single transits: more rows than widths there are");
+    size_t n_taps = 0;
+    for (int64_t r = 0; r < n_rows; ++r) {
+        if (width[r] < tlsdev::kSingleMinWidth || width[r] > TLS_SINGLE_MAX_WIDTH)
+            return fail(ctx, TLS_E_ARG, "single transits: width out of range [3, 4096]");
+        if (r > 0 && width[r] <= width[r - 1]) return fail(ctx, TLS_E_ARG, "single transits: the widths must be strictly ascending");
+        if (shape_offset[r] < 0) return fail(ctx, TLS_E_ARG, "single transits: negative shape offset");
+        if (!(std::isfinite(span_max[r]) && span_max[r] >= 0.0)) return fail(ctx, TLS_E_ARG, "single transits: span_max must be finite and >= 0");
+        n_taps += (size_t)width[r];
+    }
+    if (n_curves == 0) return TLS_OK;
+    if (!t || !y || !dy || !out_events || !out_n_events) return fail(ctx, TLS_E_ARG, "null argument");
+    if (n < 1 || n > tlsdev::kSingleMaxPoints) return fail(ctx, TLS_E_ARG, "single transits: n out of range [1, 2^20]");
+    for (int64_t i = 0; i < n; ++i)
+        if (!std::isfinite(t[i]) || (i > 0 && t[i] < t[i - 1]))
+            return fail(ctx, TLS_E_ARG, "single transits: the time stamps must be finite and non-decreasing");
+    // the rows and their taps, pairs (b, b * b)
+    std::vector<tlsdev::SingleRow> h_rows((size_t)n_rows);
+    std::vector<double> h_taps(2 * n_taps);
+    size_t at = 0;
+    for (int64_t r = 0; r < n_rows; ++r) {
+        h_rows[(size_t)r].width = (int)width[r];
+        h_rows[(size_t)r].offset = (int)at;
+        h_rows[(size_t)r].span_max = span_max[r];
+        const double* b = shape_values + shape_offset[r];
+        for (int64_t j = 0; j < width[r]; ++j, ++at) {
+            const double v = b[j];
+            h_taps[2 * at] = v;
+            h_taps[2 * at + 1] = v * v;
+        }
+    }
+    const int max_width = (int)width[n_rows - 1];
+    TLS_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t nn = (size_t)n, words = (size_t)k * tlsdev::kSingleEventWords;
+    // curves per launch: at most 256 MB of rows and planes (as the detrending slabs), 36 bytes a point
+    const int64_t slab = std::max<int64_t>(1, std::min<int64_t>({n_curves, (int64_t)65535, (int64_t)((256u << 20) / (36 * nn))}));
+    const size_t sl = (size_t)slab;
+    // t | rows | taps | of one slab: y | dy | ses | depth | events | n_events | row
+    TLS_HIP(ctx, ctx->d_single.reserve(nn + 2 * (size_t)n_rows + 2 * n_taps + 4 * sl * nn + sl * words + sl + (sl * nn + 1) / 2));
+    double* d_t = ctx->d_single.ptr;
+    tlsdev::SingleRow* d_rows = reinterpret_cast<tlsdev::SingleRow*>(d_t + nn);
+    double* d_taps = d_t + nn + 2 * (size_t)n_rows;
+    double* d_y = d_taps + 2 * n_taps;
+    double* d_dy = d_y + sl * nn;
+    double* d_ses = d_dy + sl * nn;
+    double* d_depth = d_ses + sl * nn;
+    double* d_events = d_depth + sl * nn;
+    long long* d_n_events = reinterpret_cast<long long*>(d_events + sl * words);
+    int* d_row = reinterpret_cast<int*>(d_events + sl * words + sl);
+    if (!ctx->d_check.ptr) {
+        TLS_HIP(ctx, ctx->d_check.reserve(tlsdev::kChecks));
+        TLS_HIP(ctx, hipMemsetAsync(ctx->d_check.ptr, 0, tlsdev::kChecks * sizeof(unsigned long long), ctx->stream));
+    }
+    tlsdev::SingleArgs a;
+    a.t = d_t; a.y = d_y; a.dy = d_dy; a.rows = d_rows; a.taps = d_taps;
+    a.ses = d_ses; a.row = d_row; a.depth = d_depth; a.check = ctx->d_check.ptr;
+    a.depth_min = depth_min; a.n = (int)n; a.n_rows = (int)n_rows;
+    a.halo_lo = (max_width - 1) / 2; a.halo_hi = max_width / 2;
+    tlsdev::SingleSelectArgs s;
+    s.t = d_t; s.ses = d_ses; s.row = d_row; s.depth = d_depth; s.rows = d_rows;
+    s.events = d_events; s.n_events = d_n_events; s.check = ctx->d_check.ptr;
+    s.min_ses = min_ses; s.separation = separation; s.n = (int)n; s.n_rows = (int)n_rows; s.k = (int)k;
+    const size_t lds = tlsdev::single_lds_bytes(max_width), select_lds = tlsdev::single_select_lds_bytes((int)n);
+    auto statistic = tlsdev::tls_single_statistic_kernel;
+    auto select = tlsdev::tls_single_select_kernel;
+    TLS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(statistic), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    TLS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(select), hipFuncAttributeMaxDynamicSharedMemorySize, (int)select_lds));
+    TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_rows, h_rows.data(), (size_t)n_rows * sizeof(tlsdev::SingleRow), hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_taps, h_taps.data(), 2 * n_taps * 8, hipMemcpyHostToDevice, ctx->stream));
+    const unsigned tiles = (unsigned)((n + tlsdev::kSingleTile - 1) / tlsdev::kSingleTile);
+    std::vector<int> h_row(out_row ? sl * nn : 0);
+    for (int64_t k0 = 0; k0 < n_curves; k0 += slab) {
+        const int64_t curves = std::min<int64_t>(slab, n_curves - k0);
+        const size_t bytes = (size_t)curves * nn * 8, first = (size_t)k0 * nn;
+        TLS_HIP(ctx, hipMemcpyAsync(d_y, y + first, bytes, hipMemcpyHostToDevice, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(d_dy, dy + first, bytes, hipMemcpyHostToDevice, ctx->stream));
+        hipLaunchKernelGGL(statistic, dim3(tiles, (unsigned)curves), dim3(tlsdev::kSingleThreads), lds, ctx->stream, a);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(select, dim3((unsigned)curves), dim3(tlsdev::kSingleSelectThreads), select_lds, ctx->stream, s);
+            e = hipGetLastError();
+        }
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(ctx->stream);
+            return fail(ctx, TLS_E_HIP, std::string("single transits launch: ") + hipGetErrorString(e));
+        }
+        ctx->last_kernel = "tls_single_transits";
+        TLS_HIP(ctx, hipMemcpyAsync(out_events + (size_t)k0 * (size_t)k, d_events, (size_t)curves * words * 8, hipMemcpyDeviceToHost, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(out_n_events + k0, d_n_events, (size_t)curves * 8, hipMemcpyDeviceToHost, ctx->stream));
+        if (out_ses) TLS_HIP(ctx, hipMemcpyAsync(out_ses + first, d_ses, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        if (out_depth) TLS_HIP(ctx, hipMemcpyAsync(out_depth + first, d_depth, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        if (out_row) TLS_HIP(ctx, hipMemcpyAsync(h_row.data(), d_row, (size_t)curves * nn * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        // (the next slab overwrites the device rows, and h_rows / h_taps are read by the copies above until the stream is done)
+        TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (out_row) for (size_t i = 0; i < (size_t)curves * nn; ++i) out_row[first + i] = h_row[i];
+    }
     return TLS_OK;
 }
 

@@ -89,6 +89,7 @@ enum CheckCode {
     kChkDetrend = 9,       // tls_medfilt_detrend: an LDS index outside the staged slots, or a median outside the span
     kChkBiweight = 10,     // tls_biweight_detrend: a span over its LDS, or an LDS index outside the staged slots
     kChkSysrem = 11,       // tls_sysrem: a row, a chunk or a component count outside the call's
+    kChkSingle = 12,       // tls_single_transits: a window outside the staged slots, or a taken centre, row or window outside the series
 };
 
 constexpr int kWave = 64;
@@ -4300,6 +4301,8 @@ __global__ void __launch_bounds__(512) tls_transit_models(const ModelsArgs a) {
 
 // survey-mode periodogram peaks (tls_find_peaks, tls_power_batch_peaks)
 #include "tls_peaks.hip.h"
+// survey-mode single-transit events (tls_single_transits)
+#include "tls_single.hip.h"
 #include "tls_peak_fits.hip.h"
 #include "tls_phase_scan.hip.h"
 

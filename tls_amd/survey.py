@@ -709,6 +709,108 @@ def search_batch(t, flux_batch, dy_batch=None, context=None, device=None, device
     return inp["periods"], out["chi2"], out["row"], out["depth"]
 
 
+# ---- single-transit events: the template slid along the time series itself ------------------------------------------------
+def single_transit_widths(t, duration_min=None, duration_max=1.0, log_step=1.1):
+    """The default trial widths of single_transits, in samples: with dt = median(diff(t)), the sorted set of int(round(x))
+    over the geometric series x = lo, lo * log_step, lo * log_step^2, ... <= hi from lo = max(3, duration_min / dt)
+    (duration_min None: 3) to hi = min(duration_max / dt, 4096, n).  Durations are in days, log_step > 1.  At 30 min cadence
+    the defaults give 24 widths from 3 to 48 samples.  ValueError for an empty grid (hi < lo) and a bad argument."""
+    from ._lib import SINGLE_MAX_WIDTH, SINGLE_MIN_WIDTH
+    t = numpy.asarray(t, dtype=numpy.float64)
+    if t.ndim != 1 or len(t) < 2:
+        raise ValueError("single transits: t must hold at least two time stamps")
+    dt = float(numpy.median(numpy.diff(t)))
+    if not (dt > 0.0 and dt < numpy.inf):
+        raise ValueError("single transits: the median cadence of t must be finite and > 0, got %r" % dt)
+    if not (float(log_step) > 1.0 and float(log_step) < numpy.inf):
+        raise ValueError("single transits: log_step must be > 1, got %r" % (log_step,))
+    if not (float(duration_max) > 0.0) or (duration_min is not None and not (float(duration_min) > 0.0)):
+        raise ValueError("single transits: durations must be > 0 days")
+    lo = float(SINGLE_MIN_WIDTH) if duration_min is None else max(float(SINGLE_MIN_WIDTH), float(duration_min) / dt)
+    hi = min(float(duration_max) / dt, float(SINGLE_MAX_WIDTH), float(len(t)))
+    widths, i = set(), 0
+    while lo * float(log_step) ** i <= hi:
+        widths.add(int(round(lo * float(log_step) ** i)))
+        i += 1
+    if not widths:
+        raise ValueError("single transits: no trial width between %g and %g samples (durations %r to %r days at a cadence of "
+                         "%g days, %d points)" % (lo, hi, duration_min, duration_max, dt, len(t)))
+    return numpy.array(sorted(widths), dtype=numpy.int64)
+
+
+def single_event_fields():
+    """The fields of a single-transit event, in order: those of tls_single_event -- index, time = t[index], ses, depth, row,
+    width (samples), t_first and t_last (the window's first and last time stamp) -- and duration_days = width * dt, formed
+    on the host."""
+    from ._lib import SINGLE_EVENT_FIELDS
+    return tuple(SINGLE_EVENT_FIELDS) + ("duration_days",)
+
+
+def single_transits(t, flux_batch, dy_batch=None, widths=None, k=8, min_ses=0.0, separation=0.5, gap_tolerance=0.5,
+                    transit_depth_min=0.0, with_arrays=False, detrend=None, context=None, device=None, devices=None,
+                    **template_kwargs):
+    """The single-transit ("mono-transit") search of every light curve of flux_batch [n_curves, n] on the shared ascending
+    time stamps t, on the device (tls_single_transits): a planet that transits once in the window has no periodogram peak,
+    so the limb-darkened template of every trial width slides along the time series itself instead of along a fold.
+
+    With dt = median(diff(t)), row r is (L_r = widths[r] samples, b_r = 1 - template.reference_transit(L_r, **shape),
+    span_max[r] = (L_r - 1) * dt * (1 + gap_tolerance) days); widths=None takes single_transit_widths(t).  The shape comes
+    from the keywords and presets of power() -- transit_template, u, limb_dark, per, rp, a, ... -- in template_kwargs, and
+    y, dy are what a search of the same rows gets (dy_batch None: the row's standard deviation).
+
+        w = 1 / dy^2;  xw = (1 - y) w
+        for every centre c, rows ascending:  h = (L - 1) // 2;  lo = c - h;  hi = lo + L - 1
+            skip if the window leaves the series or t[hi] - t[lo] > span_max[r]      (it runs over a gap)
+            N = sum_j xw[lo+j] b[j];  D = sum_j w[lo+j] b[j]^2;  d = N / D           (the least-squares depth)
+            skip unless d > transit_depth_min;  s = N / sqrt(D)                      (sqrt of the chi^2 the template removes)
+            keep the row of the largest s (the first on ties):  ses[c], row[c], depth[c];  NaN, -1, NaN without one
+        events: alive = ses >= min_ses (None: every centre with a row); at most k times the alive centre of the largest ses
+        (the lowest index on ties) is taken, and with g = int(separation * L) every alive centre whose own window meets
+        [lo - g, hi + g] leaves -- a transit longer than the longest row would otherwise return as wing events.
+
+    Each step is one IEEE double operation and every sum runs in index order, so the result is bit-equal to the Python
+    statement in tests/single_transit_spec.py.  Widths are strictly ascending integers in [3, 4096], k is in [1, 32],
+    separation, gap_tolerance and transit_depth_min are finite and >= 0: ValueError otherwise, before any device work (the
+    detrending included).  The rows -- t finite and non-decreasing with n <= 2^20, flux and dy as a search takes them -- are
+    checked behind the detrending steps, before the search's own device work.  detrend= takes the steps and tuples of search_batch, devices=[...] deals the curves out over several GPUs.
+
+    Returns (events, n_events): a structured array [n_curves, k] with the fields single_event_fields() -- index, time, ses,
+    depth, row, width, t_first, t_last, duration_days; index -1 and NaN past a curve's n_events [n_curves] -- and, with
+    with_arrays=True, the planes ses, row and depth [n_curves, n] behind them."""
+    from ._lib import single_options, single_widths
+    from .template import reference_transit
+    depth_min, k, min_ses, separation = single_options(transit_depth_min, k, min_ses, separation)
+    if isinstance(gap_tolerance, bool) or not (0.0 <= float(gap_tolerance) < numpy.inf):
+        raise ValueError("single transits: gap_tolerance must be finite and >= 0, got %r" % (gap_tolerance,))
+    if widths is not None:
+        widths = single_widths(widths)
+    flux_batch = _detrended(t, flux_batch, detrend, context, device, devices, dy_batch)
+    kwargs = dict(template_kwargs)
+    kwargs.setdefault("oversampling_factor", 1)      # (the period grid of the plan inputs is not used: the coarsest will do)
+    inp, y_rows, dy_rows = _batch_inputs(t, flux_batch, dy_batch, kwargs)
+    if widths is None:
+        widths = single_transit_widths(inp["t"])
+    dt = float(numpy.median(numpy.diff(inp["t"]))) if len(inp["t"]) > 1 else 0.0
+    shapes = [1.0 - numpy.asarray(reference_transit(int(L), **inp["shape"])) for L in widths]
+    span_max = [(int(L) - 1) * dt * (1 + float(gap_tolerance)) for L in widths]
+
+    def call(ctx, lo, hi):
+        # (Context.single_transits checks the rows, single_arguments, before its device work)
+        out = ctx.single_transits(inp["t"], y_rows[lo:hi], dy_rows[lo:hi], widths, shapes, span_max, depth_min, k, min_ses,
+                                  separation, with_arrays=with_arrays)
+        return dict(zip(("events", "n_events", "ses", "row", "depth"), tuple(out) + (None,) * (5 - len(out))))
+
+    out = _run_batch(devices, device, context, len(y_rows), call)
+    raw = out["events"]
+    events = numpy.zeros(raw.shape, dtype=[(f, "f8") for f in single_event_fields()])
+    for f in raw.dtype.names:
+        events[f] = raw[f]
+    events["duration_days"] = raw["width"] * dt
+    if with_arrays:
+        return events, out["n_events"], out["ses"], out["row"], out["depth"]
+    return events, out["n_events"]
+
+
 # ---- injection-recovery ---------------------------------------------------------------------------------------------------
 INJECTION_FIELDS = ("T0", "period", "rp_rs", "a", "inc")
 INJECTION_LAWS = ("quadratic", "linear", "uniform")
