@@ -38,7 +38,7 @@ extern "C" {
  * signature keep the version (7: tls_inject_transits, tls_null_rows, tls_debug_null_words,
  * tls_medfilt_detrend, tls_biweight_detrend), (7: tls_power_batch_peaks, tls_find_peaks),
  * (7: tls_power_batch_peak_fits, tls_debug_peak_fits), (7: tls_phase_scan, tls_power_batch_phase_scan,
- * tls_debug_peak_phase_scans), (7: tls_sysrem), (7: tls_single_transits). */
+ * tls_debug_peak_phase_scans), (7: tls_sysrem), (7: tls_single_transits), (7: tls_transit_times). */
 #define TLS_AMD_ABI_VERSION 7
 
 #define TLS_OK 0
@@ -635,6 +635,76 @@ int tls_single_transits(tls_ctx *ctx, const double *t, const double *y, const do
                         int64_t n_rows, double depth_min, int64_t k, double min_ses, double separation,
                         tls_single_event *out_events, int64_t *out_n_events, double *out_ses, int64_t *out_row,
                         double *out_depth);
+
+/* ---- survey mode: individual transit times and a refitted ephemeris ---------------------------------------------------- */
+/* The transit-by-transit view of a candidate: every transit of a linear ephemeris (P, T0) is timed on its own with the
+ * template of the candidate's duration, and the straight line through the times gives a refined (period, T0) with errors that
+ * come from the transits themselves, the observed-minus-computed times and their chi^2.  For a curve (y [n], dy [n] over the
+ * ascending, finite t [n]), a candidate (P, T0, row r, reach S >= 1), row r of L in [3, TLS_SINGLE_MAX_WIDTH] samples with the
+ * shape b[j] (0 out of transit, 1 at the bottom; shape_values[shape_offset[r] .. + L)) and span_max in days, depth_min >= 0:
+ *   w = 1.0 / (dy * dy);  xw = (1.0 - y) * w
+ *   bb[j] = b[j]*b[j];  g[j] = 0.5 * (b[j+1] - b[j-1]) with b[-1] = b[L] = 0.0;  gg[j] = g[j]*g[j];  bg[j] = b[j]*g[j];  h = (L-1)/2
+ *   status 1 and NaN in every other field unless P and T0 are finite and P > 0
+ *   e_first = ceil((t[0] - T0) / P);  e_last = floor((t[n-1] - T0) / P);  n_epochs = (e_last - e_first) + 1.0       (doubles)
+ *   status 2 unless 1 <= n_epochs <= max_epochs: n_epochs is reported, the rest is NaN
+ *   every epoch e = e_first + i, i = 0 .. n_epochs-1:
+ *       tc = T0 + e * P;  j = first index with t[j] >= tc (n-1 if there is none)
+ *       if j > 0 and tc - t[j-1] <= t[j] - tc:  j = j - 1                             the nearer sample; the lower one on a tie
+ *       for s = -S .. S ascending:  c = j + s;  lo = c - h;  hi = lo + L - 1
+ *           skip if lo < 0 or hi > n-1 or not (t[hi] - t[lo] <= span_max)              the window runs over a gap
+ *           N = 0; D = 0; for k ascending:  N = N + xw[lo+k]*b[k];  D = D + w[lo+k]*bb[k]
+ *           d = N / D;  skip if not (d > depth_min);  q = N / sqrt(D)
+ *           hold (q, d, c, lo) if nothing is held or q > held q                        the first shift wins ties
+ *       nothing held: epoch status 1, time_linear = tc, the rest NaN
+ *       ses = q, depth = d, index = c;  tm = 0.5 * (t[lo+h] + t[lo+L-1-h])             the window's centre; t[c] for odd L
+ *       epoch status 3 if not (q >= min_ses)                                           too weak to time
+ *       epoch status 2 if c-1 < 0 or c+1 > n-1
+ *       H = 0; Bg = 0; G = 0; for k ascending:  H = H + xw[lo+k]*g[k];  Bg = Bg + w[lo+k]*bg[k];  G = G + w[lo+k]*gg[k]
+ *       delta = (d*Bg - H) / (d*G);  step = 0.5 * (t[c+1] - t[c-1])                    one Gauss-Newton step of the shift
+ *       epoch status 2 if not (fabs(delta) <= 1.0)                                     the step leaves the sample (NaN, G == 0)
+ *       epoch status 0:  time = tm + delta*step;  time_err = step / (d * sqrt(G))
+ *   over the epochs of status 0, ascending:  wgt = 1.0/(time_err*time_err);  x = e;  tau = time - T0
+ *       Sw += wgt;  Se += wgt*x;  See += (wgt*x)*x;  St += wgt*tau;  Set += (wgt*x)*tau;  Dl = Sw*See - Se*Se
+ *   where n_timed >= 2 and Dl > 0:  slope = (Sw*Set - Se*St)/Dl;  icpt = (See*St - Se*Set)/Dl
+ *       period = slope;  T0 = T0 + icpt;  period_err = sqrt(Sw/Dl);  T0_err = sqrt(See/Dl)
+ *   where also n_timed >= 3:  oc = tau - (icpt + slope*x);  rr = oc/time_err;  chi2 += rr*rr;  ss += oc*oc
+ *       ttv_chi2 = chi2;  ttv_rms = sqrt(ss / n_timed);  ttv_max_sigma, ttv_max_epoch = the largest fabs(rr), its epoch (the first)
+ * Everything that cannot be formed is NaN.  time_err is the Fisher bound of the shape at the fitted depth on white noise of
+ * the given dy: red noise and a wrong shape make the true scatter larger, which ttv_chi2 of a quiet star shows.  Every step is
+ * one IEEE double operation and every sum runs in the stated order: both records equal the Python statement in
+ * tests/transit_times_spec.py bit for bit.  All fields are doubles. */
+#define TLS_TIMES_MAX_REACH 4096
+#define TLS_TIMES_MAX_EPOCHS 65536
+typedef struct tls_ephemeris {
+    double status;                 /* 0 epochs were looked at; 1 no such ephemeris (P, T0); 2 n_epochs outside [1, max_epochs] */
+    double n_epochs, n_timed;      /* epochs inside the series; those of epoch status 0 */
+    double epoch_first;            /* e_first */
+    double period, period_err;     /* slope and its error (n_timed >= 2) */
+    double T0, T0_err;             /* T0 + intercept and its error */
+    double ttv_chi2, ttv_rms;      /* chi^2 and root mean square of the observed-minus-computed times (n_timed >= 3) */
+    double ttv_max_sigma, ttv_max_epoch;   /* the largest |o - c| / time_err and its epoch */
+} tls_ephemeris;
+typedef struct tls_transit_time {
+    double epoch;                  /* e; NaN at ranks past n_epochs */
+    double status;                 /* 0 timed; 1 no window with a dip (a gap, an end of the series); 2 found but not timed: the
+                                      step leaves the sample or the series; 3 found but weaker than min_ses */
+    double time_linear;            /* tc */
+    double time, time_err;         /* status 0 */
+    double ses, depth, index;      /* q, d, c of the held window (status 0, 2, 3) */
+} tls_transit_time;
+/* n_fits candidates (period[f], T0[f], row[f], reach[f]) on the curves curve[f] of y, dy [n_curves][n] over the shared time
+ * stamps t [n]; the rows as tls_single_transits takes them.  out [n_fits], out_times [n_fits][max_epochs].  Needs no plan and no
+ * search, and leaves a prepared plan as it is.  n_fits == 0 is a no-op.  Candidates are processed in slabs, so device memory
+ * stays bounded for any n_fits.  TLS_E_ARG, before any device work and with the outputs untouched, for a curve[f] outside
+ * [0, n_curves), a row[f] outside [0, n_rows), a reach[f] outside [1, TLS_TIMES_MAX_REACH], max_epochs outside
+ * [1, TLS_TIMES_MAX_EPOCHS], n outside [1, 2^30], negative counts, n_rows < 1, widths not strictly ascending or outside
+ * [3, TLS_SINGLE_MAX_WIDTH], a negative shape_offset, a non-finite or negative span_max or depth_min, a NaN min_ses, and a t
+ * that is not finite and non-decreasing.  y and dy are taken as they are (dy > 0). */
+int tls_transit_times(tls_ctx *ctx, const double *t, const double *y, const double *dy, int64_t n, int64_t n_curves,
+                      const int64_t *curve, const double *period, const double *T0, const int64_t *row, const int64_t *reach,
+                      int64_t n_fits, const double *shape_values, const int64_t *shape_offset, const int64_t *width,
+                      const double *span_max, int64_t n_rows, double depth_min, double min_ses, int64_t max_epochs,
+                      tls_ephemeris *out /* [n_fits] */, tls_transit_time *out_times /* [n_fits][max_epochs] */);
 
 /* ---- host-only planning (no GPU needed) ------------------------------------------ */
 /* Trial cells (duration x T0 positions) each period will enumerate: the data-independent

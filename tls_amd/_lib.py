@@ -46,6 +46,10 @@ SINGLE_MAX_K = 32
 SINGLE_MIN_WIDTH = 3
 SINGLE_TILE = 256
 SINGLE_MAX_POINTS = 1 << 20
+# include/tls_amd.h TLS_TIMES_*: the widest reach and the most epochs a candidate of tls_transit_times
+TIMES_MAX_REACH = 4096
+TIMES_MAX_EPOCHS = 65536
+TIMES_MAX_POINTS = 1 << 30   # tls_times.hip.h kTimesMaxPoints
 PEAKS_LDS_PERIODS = 1 << 20   # tls_peaks.hip.h kPeaksLdsPeriods: a longer grid keeps its alive mask in device memory, not in LDS
 
 # every symbol include/tls_amd.h declares (tests check the export list against the header)
@@ -58,6 +62,7 @@ SYMBOLS = (
     "tls_inject_transits", "tls_null_rows", "tls_debug_null_words", "tls_medfilt_detrend",
     "tls_biweight_detrend", "tls_sysrem", "tls_find_peaks", "tls_power_batch_peaks", "tls_power_batch_peak_fits", "tls_debug_peak_fits",
     "tls_phase_scan", "tls_power_batch_phase_scan", "tls_debug_peak_phase_scans", "tls_single_transits",
+    "tls_transit_times",
     "tls_comm_unique_id", "tls_comm_init", "tls_comm_destroy", "tls_comm_info", "tls_comm_allgather_results", "tls_comm_allgather_device", "tls_comm_fetch_gathered",
     "tls_comm_stage_results", "tls_comm_allgather_staged", "tls_comm_fetch_staged",
     "tls_comm_barrier", "tls_comm_max",
@@ -212,32 +217,32 @@ class SingleEvent(ctypes.Structure):
 SINGLE_EVENT_DTYPE = numpy.dtype([(k, "f8") for k in SINGLE_EVENT_FIELDS])
 
 
-def _single_number(name, value, low=0.0):
+def _single_number(name, value, low=0.0, what="single transits"):
     """value as a float, finite and >= low; ValueError otherwise (a bool or a non-number included)."""
     if isinstance(value, (bool, numpy.bool_)) or not isinstance(value, numbers.Real):
-        raise ValueError("single transits: %s must be a number, got %r" % (name, value))
+        raise ValueError("%s: %s must be a number, got %r" % (what, name, value))
     v = float(value)
     if not (low <= v < numpy.inf):
-        raise ValueError("single transits: %s must be finite and >= %g, got %r" % (name, low, value))
+        raise ValueError("%s: %s must be finite and >= %g, got %r" % (what, name, low, value))
     return v
 
 
-def single_widths(widths):
+def single_widths(widths, what="single transits"):
     """The widths as an int64 array, checked as tls_single_transits checks them: integers, at least one, strictly ascending,
-    in [SINGLE_MIN_WIDTH, SINGLE_MAX_WIDTH]; ValueError otherwise."""
+    in [SINGLE_MIN_WIDTH, SINGLE_MAX_WIDTH]; ValueError otherwise, its message headed by `what`."""
     try:
         if any(isinstance(v, (bool, numpy.bool_)) for v in widths):
             raise TypeError
         width = numpy.array([operator.index(v) for v in widths], dtype=numpy.int64)
     except TypeError:
-        raise ValueError("single transits: the widths must be integers, got %r" % (widths,))
+        raise ValueError("%s: the widths must be integers, got %r" % (what, widths,))
     if len(width) < 1:
-        raise ValueError("single transits: at least one width is needed")
+        raise ValueError("%s: at least one width is needed" % what)
     if width.min() < SINGLE_MIN_WIDTH or width.max() > SINGLE_MAX_WIDTH:
-        raise ValueError("single transits: every width must be in [%d, %d], got %d to %d"
-                         % (SINGLE_MIN_WIDTH, SINGLE_MAX_WIDTH, width.min(), width.max()))
+        raise ValueError("%s: every width must be in [%d, %d], got %d to %d"
+                         % (what, SINGLE_MIN_WIDTH, SINGLE_MAX_WIDTH, width.min(), width.max()))
     if not numpy.all(width[1:] > width[:-1]):
-        raise ValueError("single transits: the widths must be strictly ascending")
+        raise ValueError("%s: the widths must be strictly ascending" % what)
     return width
 
 
@@ -256,40 +261,42 @@ def single_options(depth_min=0.0, k=8, min_ses=0.0, separation=0.5):
     return depth_min, int(k), float(min_ses), separation
 
 
-def single_arguments(t, y, dy, widths, shapes, span_max, depth_min=0.0, k=8, min_ses=0.0, separation=0.5):
+def single_arguments(t, y, dy, widths, shapes, span_max, depth_min=0.0, k=8, min_ses=0.0, separation=0.5,
+                     what="single transits", max_points=SINGLE_MAX_POINTS):
     """What tls_single_transits takes, checked as it checks them and packed for it -- a dict with t [n], y and dy
     [n_curves, n], width [n_rows] (int64), shape_values (the rows of `shapes` back to back), shape_offset [n_rows] (int64),
     span_max [n_rows], depth_min, k, min_ses, separation.  t is 1-D with n in [1, SINGLE_MAX_POINTS], finite and
     non-decreasing; y and dy are [n] or [n_curves, n], dy finite and > 0, y finite; widths are integers, strictly ascending,
     in [SINGLE_MIN_WIDTH, SINGLE_MAX_WIDTH], at least one; shapes[r] holds widths[r] finite values; span_max[r], depth_min
     and separation are finite and >= 0; k is an integer in [1, SINGLE_MAX_K]; min_ses is no NaN (None: -inf, no threshold).
-    ValueError otherwise.  GPU-free."""
+    ValueError otherwise.  GPU-free.  tls_transit_times takes the same t, y, dy and rows: `what` heads the messages and
+    max_points is the entry's limit of n."""
     t = numpy.asarray(t, dtype=numpy.float64)
-    if t.ndim != 1 or not 1 <= len(t) <= SINGLE_MAX_POINTS:
-        raise ValueError("single transits: t must have shape [n] with n in [1, %d], got %s" % (SINGLE_MAX_POINTS, t.shape))
+    if t.ndim != 1 or not 1 <= len(t) <= max_points:
+        raise ValueError("%s: t must have shape [n] with n in [1, %d], got %s" % (what, max_points, t.shape))
     if not numpy.all(numpy.isfinite(t)) or not numpy.all(t[1:] >= t[:-1]):
-        raise ValueError("single transits: t must be finite and non-decreasing")
+        raise ValueError("%s: t must be finite and non-decreasing" % what)
     y, dy = numpy.asarray(y, dtype=numpy.float64), numpy.asarray(dy, dtype=numpy.float64)
     if y.ndim == 1:
         y = y[None, :]
     if dy.ndim == 1:
         dy = dy[None, :]
     if y.ndim != 2 or y.shape[1] != len(t) or dy.shape != y.shape:
-        raise ValueError("single transits: y and dy must be [n] or [n_curves, n] over the time stamps t [n]")
+        raise ValueError("%s: y and dy must be [n] or [n_curves, n] over the time stamps t [n]" % what)
     if y.size and not numpy.all(numpy.isfinite(y)):
-        raise ValueError("single transits: y has a NaN or an infinite value")
+        raise ValueError("%s: y has a NaN or an infinite value" % what)
     if dy.size and not (dy.min() > 0.0 and dy.max() < numpy.inf):
-        raise ValueError("single transits: dy has a NaN, infinite or non-positive value")
-    width = single_widths(widths)
+        raise ValueError("%s: dy has a NaN, infinite or non-positive value" % what)
+    width = single_widths(widths, what)
     if len(shapes) != len(width):
-        raise ValueError("single transits: %d shapes for %d widths" % (len(shapes), len(width)))
+        raise ValueError("%s: %d shapes for %d widths" % (what, len(shapes), len(width)))
     rows = [numpy.asarray(b, dtype=numpy.float64) for b in shapes]
     for r, b in enumerate(rows):
         if b.shape != (width[r],) or not numpy.all(numpy.isfinite(b)):
-            raise ValueError("single transits: shape %d must hold %d finite values" % (r, width[r]))
+            raise ValueError("%s: shape %d must hold %d finite values" % (what, r, width[r]))
     span = numpy.asarray(span_max, dtype=numpy.float64)
     if span.shape != width.shape or not numpy.all(numpy.isfinite(span) & (span >= 0.0)):
-        raise ValueError("single transits: span_max must hold one finite value >= 0 a width")
+        raise ValueError("%s: span_max must hold one finite value >= 0 a width" % what)
     depth_min, k, min_ses, separation = single_options(depth_min, k, min_ses, separation)
     offset = numpy.zeros(len(width), dtype=numpy.int64)
     offset[1:] = numpy.cumsum(width)[:-1]
@@ -297,6 +304,76 @@ def single_arguments(t, y, dy, widths, shapes, span_max, depth_min=0.0, k=8, min
                 shape_values=numpy.ascontiguousarray(numpy.concatenate(rows)), shape_offset=offset,
                 span_max=numpy.ascontiguousarray(span), depth_min=depth_min, k=k, min_ses=min_ses,
                 separation=separation)
+
+
+# tls_ephemeris and tls_transit_time (include/tls_amd.h): a candidate's refitted ephemeris, 12 doubles, and one of its
+# transits, 8 doubles
+EPHEMERIS_FIELDS = ("status", "n_epochs", "n_timed", "epoch_first", "period", "period_err", "T0", "T0_err", "ttv_chi2",
+                    "ttv_rms", "ttv_max_sigma", "ttv_max_epoch")
+TRANSIT_TIME_FIELDS = ("epoch", "status", "time_linear", "time", "time_err", "ses", "depth", "index")
+
+
+class Ephemeris(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_double) for k in EPHEMERIS_FIELDS]
+
+
+class TransitTime(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_double) for k in TRANSIT_TIME_FIELDS]
+
+
+EPHEMERIS_DTYPE = numpy.dtype([(k, "f8") for k in EPHEMERIS_FIELDS])
+TRANSIT_TIME_DTYPE = numpy.dtype([(k, "f8") for k in TRANSIT_TIME_FIELDS])
+
+
+def transit_times_options(depth_min=0.0, min_ses=3.0, max_epochs=1):
+    """(depth_min, min_ses, max_epochs) as tls_transit_times takes them, checked as it checks them: depth_min finite and
+    >= 0, min_ses a number and no NaN, max_epochs an integer in [1, TIMES_MAX_EPOCHS]; ValueError otherwise."""
+    if isinstance(depth_min, (bool, numpy.bool_)) or not isinstance(depth_min, numbers.Real) \
+            or not (0.0 <= float(depth_min) < numpy.inf):
+        raise ValueError("transit times: depth_min must be finite and >= 0, got %r" % (depth_min,))
+    if isinstance(min_ses, (bool, numpy.bool_)) or not isinstance(min_ses, numbers.Real) or numpy.isnan(min_ses):
+        raise ValueError("transit times: min_ses must be a number and no NaN, got %r" % (min_ses,))
+    if isinstance(max_epochs, (bool, numpy.bool_)) or not isinstance(max_epochs, numbers.Integral) \
+            or not 1 <= int(max_epochs) <= TIMES_MAX_EPOCHS:
+        raise ValueError("transit times: max_epochs must be an integer in [1, %d], got %r" % (TIMES_MAX_EPOCHS, max_epochs))
+    return float(depth_min), float(min_ses), int(max_epochs)
+
+
+def transit_times_arguments(t, y, dy, period, T0, row, reach, widths, shapes, span_max, curve=None, depth_min=0.0,
+                            min_ses=3.0, max_epochs=1):
+    """What tls_transit_times takes, checked as it checks them and packed for it -- the dict of single_arguments for t, y,
+    dy and the rows (width, shape_values, shape_offset, span_max: checked as single_arguments checks them, n up to
+    TIMES_MAX_POINTS), plus period, T0
+    [n_fits] (float64, any value: the device gives a candidate without an ephemeris status 1), curve (None: one candidate a
+    curve, in order), row and reach [n_fits] (int64; curve in [0, n_curves), row in [0, n_rows), reach in
+    [1, TIMES_MAX_REACH]), depth_min, min_ses, max_epochs (transit_times_options).  ValueError otherwise.  GPU-free."""
+    depth_min, min_ses, max_epochs = transit_times_options(depth_min, min_ses, max_epochs)
+    a = single_arguments(t, y, dy, widths, shapes, span_max, depth_min, what="transit times", max_points=TIMES_MAX_POINTS)
+    try:
+        period, T0 = (numpy.ascontiguousarray(numpy.atleast_1d(numpy.asarray(v, dtype=numpy.float64))) for v in (period, T0))
+    except (TypeError, ValueError):
+        raise ValueError("transit times: period and T0 must be numbers")
+    if period.ndim != 1 or period.shape != T0.shape:
+        raise ValueError("transit times: period and T0 must be [n_fits]")
+    n_fits, n_curves = len(period), len(a["y"])
+    if curve is None:
+        if n_fits != n_curves:
+            raise ValueError("transit times: curve=None takes one candidate a light curve: %d candidates, %d curves"
+                             % (n_fits, n_curves))
+        curve = numpy.arange(n_curves)
+    ints = {}
+    for name, v, lo, hi in (("curve", curve, 0, n_curves - 1), ("row", row, 0, len(a["width"]) - 1),
+                            ("reach", reach, 1, TIMES_MAX_REACH)):
+        v = numpy.atleast_1d(numpy.asarray(v))
+        if v.shape != period.shape or (v.size and v.dtype.kind not in "iu"):
+            raise ValueError("transit times: %s must hold one integer a candidate" % name)
+        if v.size and (v.min() < lo or v.max() > hi):
+            raise ValueError("transit times: %s out of range [%d, %d]" % (name, lo, hi))
+        ints[name] = numpy.ascontiguousarray(v, dtype=numpy.int64)
+    for k in ("k", "separation"):
+        del a[k]
+    a.update(ints, period=period, T0=T0, depth_min=depth_min, min_ses=min_ses, max_epochs=max_epochs)
+    return a
 
 
 def peaks_arguments(k, separation, ratios, min_power):
@@ -479,6 +556,10 @@ def load():
     lib.tls_single_transits.argtypes = [vp, _c_double_p, _c_double_p, _c_double_p, i64, i64, _c_double_p, _c_int64_p, _c_int64_p,
                                         _c_double_p, i64, dbl, i64, dbl, dbl, ctypes.c_void_p, _c_int64_p, _c_double_p,
                                         _c_int64_p, _c_double_p]
+    lib.tls_transit_times.restype = ci
+    lib.tls_transit_times.argtypes = [vp, _c_double_p, _c_double_p, _c_double_p, i64, i64, _c_int64_p, _c_double_p, _c_double_p,
+                                      _c_int64_p, _c_int64_p, i64, _c_double_p, _c_int64_p, _c_int64_p, _c_double_p, i64, dbl,
+                                      dbl, i64, ctypes.c_void_p, ctypes.c_void_p]
     lib.tls_debug_peak_phase_scans.restype = ci
     lib.tls_debug_peak_phase_scans.argtypes = [vp, _c_double_p, i64, ctypes.c_void_p, _c_int64_p, i64, _c_double_p, _c_double_p,
                                                i64, dbl, _c_double_p, i64, i64, ctypes.c_void_p, i64, i64, ctypes.c_void_p]
@@ -1227,6 +1308,27 @@ class Context(object):
             events.ctypes.data_as(ctypes.c_void_p), _ip(n_events), None if ses is None else _dp(ses),
             None if row is None else _ip(row), None if depth is None else _dp(depth)))
         return (events, n_events, ses, row, depth) if with_arrays else (events, n_events)
+
+    def transit_times(self, t, y, dy, period, T0, row, reach, widths, shapes, span_max, curve=None, depth_min=0.0,
+                      min_ses=3.0, max_epochs=1):
+        """The transit times and refitted ephemerides (tls_transit_times; the statement: include/tls_amd.h,
+        tests/transit_times_spec.py) of the candidates (period[f], T0[f], row[f], reach[f]) on the curves curve[f] (None: one
+        candidate a curve, in order) of y, dy [n_curves, n] (or one row) over t [n], for the rows (widths[r], shapes[r],
+        span_max[r]): (EPHEMERIS_DTYPE [n_fits], TRANSIT_TIME_DTYPE [n_fits, max_epochs]).  ValueError for what
+        transit_times_arguments refuses."""
+        a = transit_times_arguments(t, y, dy, period, T0, row, reach, widths, shapes, span_max, curve, depth_min, min_ses,
+                                    max_epochs)
+        n_c, n = a["y"].shape
+        n_fits = len(a["period"])
+        eph = numpy.zeros(n_fits, dtype=EPHEMERIS_DTYPE)
+        times = numpy.zeros((n_fits, a["max_epochs"]), dtype=TRANSIT_TIME_DTYPE)
+        assert EPHEMERIS_DTYPE.itemsize == ctypes.sizeof(Ephemeris) and TRANSIT_TIME_DTYPE.itemsize == ctypes.sizeof(TransitTime)
+        self._check(self._lib.tls_transit_times(
+            self._h, _dp(a["t"]), _dp(a["y"]), _dp(a["dy"]), n, n_c, _ip(a["curve"]), _dp(a["period"]), _dp(a["T0"]),
+            _ip(a["row"]), _ip(a["reach"]), n_fits, _dp(a["shape_values"]), _ip(a["shape_offset"]), _ip(a["width"]),
+            _dp(a["span_max"]), len(a["width"]), a["depth_min"], a["min_ses"], a["max_epochs"],
+            eph.ctypes.data_as(ctypes.c_void_p), times.ctypes.data_as(ctypes.c_void_p)))
+        return eph, times
 
     def debug_null_words(self, n, n_rows, seed, first_trial=0, block=None):
         """The raw Philox words [n_rows, W] tls_null_rows draws for these trials (tls_debug_null_words): white-noise

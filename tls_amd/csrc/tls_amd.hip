@@ -20,6 +20,7 @@
 #include <numeric>
 #include <string>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 #include "../../include/tls_amd.h"
@@ -220,6 +221,8 @@ struct tls_ctx {
     DevBuf<double> d_scan;          // tls_phase_scan: t | y rows | period | T0 | duration | records | curve of fit
     // tls_single_transits: t | rows | taps | of one slab: y | dy | ses | depth | events | n_events | row
     DevBuf<double> d_single;
+    // tls_transit_times: of one slab: pairs | y | dy | records | times | period | T0 | slot, row, reach; t | rows | taps | slopes
+    DevBuf<double> d_times;
     // two-role slab path (series in HBM, one light curve; SearchPlan::split)
     View<unsigned int> d_tile_prefix;        // [n_periods + 1] tiles in front of work item w (queue order)
     DevBuf<double> d_partials;               // [split_max_items][3] a tile's winner
@@ -1634,6 +1637,7 @@ void tls_ctx_destroy(tls_ctx* ctx) {
     ctx->d_pfit.release(); ctx->d_pfep.release(); ctx->d_pfres.release(); ctx->d_pfstats.release(); ctx->d_pfranges.release();
     ctx->d_scan.release();
     ctx->d_single.release();
+    ctx->d_times.release();
     ctx->d_split.release(); ctx->d_park.release(); ctx->d_band.release();
     if (ctx->h_band) (void)hipHostFree(ctx->h_band);
     for (auto& ev : ctx->ev_band) if (ev) (void)hipEventDestroy(ev);
@@ -2789,6 +2793,7 @@ int tls_debug_device_bytes(const tls_ctx* ctx, int64_t* total, int64_t* t0_fit_s
     add(ctx->d_pfit); add(ctx->d_pfep); add(ctx->d_pfres); add(ctx->d_pfstats); add(ctx->d_pfranges);
     add(ctx->d_scan);
     add(ctx->d_single);
+    add(ctx->d_times);
     add(ctx->d_partials); add(ctx->d_tiles_done);
     add(ctx->d_split); add(ctx->d_park); add(ctx->d_band);
     *total = (int64_t)sum;
@@ -3285,6 +3290,163 @@ int tls_single_transits(tls_ctx* ctx, const double* t, const double* y, const do
         // (the next slab overwrites the device rows, and h_rows / h_taps are read by the copies above until the stream is done)
         TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
         if (out_row) for (size_t i = 0; i < (size_t)curves * nn; ++i) out_row[first + i] = h_row[i];
+    }
+    return TLS_OK;
+}
+
+// ---- transit times and the refitted ephemeris (tls_times.hip.h, DESIGN.md "Transit times"): the pairs kernel over the curves a
+// slab of candidates reads, then one workgroup a candidate, slab by slab
+static_assert(sizeof(tls_ephemeris) == tlsdev::kTimesEphemerisWords * 8, "tls_ephemeris is the kernel's record");
+static_assert(sizeof(tls_transit_time) == tlsdev::kTimesTimeWords * 8, "tls_transit_time is the kernel's record");
+static_assert(TLS_TIMES_MAX_REACH == tlsdev::kTimesMaxReach && TLS_TIMES_MAX_EPOCHS == tlsdev::kTimesMaxEpochs, "the header's limits");
+
+int tls_transit_times(tls_ctx* ctx, const double* t, const double* y, const double* dy, int64_t n, int64_t n_curves,
+                      const int64_t* curve, const double* period, const double* T0, const int64_t* row, const int64_t* reach,
+                      int64_t n_fits, const double* shape_values, const int64_t* shape_offset, const int64_t* width,
+                      const double* span_max, int64_t n_rows, double depth_min, double min_ses, int64_t max_epochs,
+                      tls_ephemeris* out, tls_transit_time* out_times) {
+    if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
+    if (n_fits < 0 || n_curves < 0 || n_rows < 0 || n < 0) return fail(ctx, TLS_E_ARG, "transit times: negative count");
+    if (max_epochs < 1 || max_epochs > TLS_TIMES_MAX_EPOCHS) return fail(ctx, TLS_E_ARG, "transit times: max_epochs out of range [1, 65536]");
+    if (!(std::isfinite(depth_min) && depth_min >= 0.0)) return fail(ctx, TLS_E_ARG, "transit times: depth_min must be finite and >= 0");
+    if (std::isnan(min_ses)) return fail(ctx, TLS_E_ARG, "transit times: min_ses is NaN");
+    if (n_fits == 0) return TLS_OK;
+    if (n_rows < 1) return fail(ctx, TLS_E_ARG, "transit times: at least one row is needed");
+    if (!shape_values || !shape_offset || !width || !span_max) return fail(ctx, TLS_E_ARG, "null argument");
+    if (n_rows > TLS_SINGLE_MAX_WIDTH) return fail(ctx, TLS_E_ARG, "transit times: more rows than widths there are");
+    size_t n_taps = 0;
+    for (int64_t r = 0; r < n_rows; ++r) {
+        if (width[r] < tlsdev::kSingleMinWidth || width[r] > TLS_SINGLE_MAX_WIDTH)
+            return fail(ctx, TLS_E_ARG, "transit times: width out of range [3, 4096]");
+        if (r > 0 && width[r] <= width[r - 1]) return fail(ctx, TLS_E_ARG, "transit times: the widths must be strictly ascending");
+        if (shape_offset[r] < 0) return fail(ctx, TLS_E_ARG, "transit times: negative shape offset");
+        if (!(std::isfinite(span_max[r]) && span_max[r] >= 0.0)) return fail(ctx, TLS_E_ARG, "transit times: span_max must be finite and >= 0");
+        n_taps += (size_t)width[r];
+    }
+    if (!t || !y || !dy || !curve || !period || !T0 || !row || !reach || !out || !out_times) return fail(ctx, TLS_E_ARG, "null argument");
+    if (n < 1 || n > tlsdev::kTimesMaxPoints) return fail(ctx, TLS_E_ARG, "transit times: n out of range [1, 2^30]");
+    if (n_fits > INT32_MAX || (uint64_t)n_curves > (uint64_t)(INT64_MAX / 16) / (uint64_t)n)
+        return fail(ctx, TLS_E_ARG, "transit times: batch too large");
+    for (int64_t i = 0; i < n; ++i)
+        if (!std::isfinite(t[i]) || (i > 0 && t[i] < t[i - 1]))
+            return fail(ctx, TLS_E_ARG, "transit times: the time stamps must be finite and non-decreasing");
+    for (int64_t f = 0; f < n_fits; ++f) {
+        if (curve[f] < 0 || curve[f] >= n_curves) return fail(ctx, TLS_E_ARG, "transit times: curve out of range [0, n_curves)");
+        if (row[f] < 0 || row[f] >= n_rows) return fail(ctx, TLS_E_ARG, "transit times: row out of range [0, n_rows)");
+        if (reach[f] < 1 || reach[f] > TLS_TIMES_MAX_REACH) return fail(ctx, TLS_E_ARG, "transit times: reach out of range [1, 4096]");
+    }
+    // the rows and their taps: pairs (b, b * b) and triples (g, b * g, g * g), g the shape's slope per sample
+    std::vector<tlsdev::SingleRow> h_rows((size_t)n_rows);
+    std::vector<double> h_taps(2 * n_taps), h_slopes(3 * n_taps);
+    size_t at = 0;
+    for (int64_t r = 0; r < n_rows; ++r) {
+        h_rows[(size_t)r].width = (int)width[r];
+        h_rows[(size_t)r].offset = (int)at;
+        h_rows[(size_t)r].span_max = span_max[r];
+        const double* b = shape_values + shape_offset[r];
+        for (int64_t j = 0; j < width[r]; ++j, ++at) {
+            const double v = b[j];
+            const double next = j + 1 < width[r] ? b[j + 1] : 0.0, prev = j > 0 ? b[j - 1] : 0.0;
+            const double rise = next - prev;
+            const double g = 0.5 * rise;
+            h_taps[2 * at] = v;
+            h_taps[2 * at + 1] = v * v;
+            h_slopes[3 * at] = g;
+            h_slopes[3 * at + 1] = v * g;
+            h_slopes[3 * at + 2] = g * g;
+        }
+    }
+    TLS_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t nn = (size_t)n, me = (size_t)max_epochs;
+    const size_t eph_words = tlsdev::kTimesEphemerisWords, time_words = (size_t)tlsdev::kTimesTimeWords * me;
+    // a slab: at most 1024 candidates on at most 1024 curves, 256 MB of curves (32 bytes a point) and 256 MB of epoch records
+    const size_t budget = 256u << 20;
+    const size_t cs = std::max<size_t>(1, std::min<size_t>({(size_t)n_curves, 1024, budget / (32 * nn)}));
+    const size_t sl = std::max<size_t>(1, std::min<size_t>({(size_t)n_fits, 1024, budget / (8 * time_words)}));
+    // of one slab: pairs | y | dy | records | times | period | T0 | slot, row, reach;  t | rows | taps | slopes
+    TLS_HIP(ctx, ctx->d_times.reserve(4 * cs * nn + sl * (eph_words + time_words + 2) + (3 * sl + 1) / 2
+                                      + nn + 2 * (size_t)n_rows + 5 * n_taps));
+    double2* d_pairs = reinterpret_cast<double2*>(ctx->d_times.ptr);           // (the allocation's start: 16-byte aligned)
+    double* d_y = ctx->d_times.ptr + 2 * cs * nn;
+    double* d_dy = d_y + cs * nn;
+    double* d_out = d_dy + cs * nn;
+    double* d_out_times = d_out + sl * eph_words;
+    double* d_period = d_out_times + sl * time_words;
+    double* d_T0 = d_period + sl;
+    int* d_ints = reinterpret_cast<int*>(d_T0 + sl);
+    double* d_t = d_T0 + sl + (3 * sl + 1) / 2;
+    tlsdev::SingleRow* d_rows = reinterpret_cast<tlsdev::SingleRow*>(d_t + nn);
+    double* d_taps = d_t + nn + 2 * (size_t)n_rows;
+    double* d_slopes = d_taps + 2 * n_taps;
+    if (!ctx->d_check.ptr) {
+        TLS_HIP(ctx, ctx->d_check.reserve(tlsdev::kChecks));
+        TLS_HIP(ctx, hipMemsetAsync(ctx->d_check.ptr, 0, tlsdev::kChecks * sizeof(unsigned long long), ctx->stream));
+    }
+    tlsdev::TimesPairsArgs p;
+    p.y = d_y; p.dy = d_dy; p.pairs = d_pairs;
+    tlsdev::TimesArgs a;
+    a.t = d_t; a.pairs = d_pairs; a.rows = d_rows; a.taps = d_taps; a.slopes = d_slopes;
+    a.slot = d_ints; a.row = d_ints + sl; a.reach = d_ints + 2 * sl;
+    a.period = d_period; a.T0 = d_T0; a.out = d_out; a.out_times = d_out_times; a.check = ctx->d_check.ptr;
+    a.depth_min = depth_min; a.min_ses = min_ses; a.n = (int)n; a.max_epochs = (int)max_epochs;
+    auto pairs_kernel = tlsdev::tls_times_pairs_kernel;
+    auto times_kernel = tlsdev::tls_transit_times_kernel;
+    TLS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(times_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     tlsdev::kTimesLdsUnits * 8));
+    TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_rows, h_rows.data(), (size_t)n_rows * sizeof(tlsdev::SingleRow), hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_taps, h_taps.data(), 2 * n_taps * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_slopes, h_slopes.data(), 3 * n_taps * 8, hipMemcpyHostToDevice, ctx->stream));
+    std::vector<int> h_ints(3 * sl);
+    std::unordered_map<int64_t, int> slot_of;
+    struct Run { int64_t curve; size_t slot, count; };      // consecutive curves in consecutive slots: one copy
+    std::vector<Run> runs;
+    for (int64_t f0 = 0; f0 < n_fits;) {
+        slot_of.clear();
+        runs.clear();
+        size_t fits = 0, lds = 0;
+        while (f0 + (int64_t)fits < n_fits && fits < sl) {
+            const int64_t f = f0 + (int64_t)fits;
+            auto it = slot_of.find(curve[f]);
+            if (it == slot_of.end()) {
+                if (slot_of.size() == cs) break;     // (the next slab takes it; a slab's first candidate always finds a slot)
+                const size_t slot = slot_of.size();
+                it = slot_of.emplace(curve[f], (int)slot).first;
+                if (!runs.empty() && runs.back().curve + (int64_t)runs.back().count == curve[f]) ++runs.back().count;
+                else runs.push_back(Run{curve[f], slot, 1});
+            }
+            h_ints[fits] = it->second;
+            h_ints[sl + fits] = (int)row[f];
+            h_ints[2 * sl + fits] = (int)reach[f];
+            lds = std::max(lds, tlsdev::times_lds_bytes((int)reach[f], (int)max_epochs));
+            ++fits;
+        }
+        for (const Run& run : runs) {
+            const size_t from = (size_t)run.curve * nn, to = run.slot * nn, bytes = run.count * nn * 8;
+            TLS_HIP(ctx, hipMemcpyAsync(d_y + to, y + from, bytes, hipMemcpyHostToDevice, ctx->stream));
+            TLS_HIP(ctx, hipMemcpyAsync(d_dy + to, dy + from, bytes, hipMemcpyHostToDevice, ctx->stream));
+        }
+        TLS_HIP(ctx, hipMemcpyAsync(d_ints, h_ints.data(), 3 * sl * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(d_period, period + f0, fits * 8, hipMemcpyHostToDevice, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(d_T0, T0 + f0, fits * 8, hipMemcpyHostToDevice, ctx->stream));
+        p.count = (long long)(slot_of.size() * nn);
+        const unsigned blocks = (unsigned)std::min<long long>((p.count + tlsdev::kTimesThreads - 1) / tlsdev::kTimesThreads, 8192);
+        hipLaunchKernelGGL(pairs_kernel, dim3(blocks), dim3(tlsdev::kTimesThreads), 0, ctx->stream, p);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(times_kernel, dim3((unsigned)fits), dim3(tlsdev::kTimesThreads), lds, ctx->stream, a);
+            e = hipGetLastError();
+        }
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(ctx->stream);
+            return fail(ctx, TLS_E_HIP, std::string("transit times launch: ") + hipGetErrorString(e));
+        }
+        ctx->last_kernel = "tls_transit_times";
+        TLS_HIP(ctx, hipMemcpyAsync(out + f0, d_out, fits * eph_words * 8, hipMemcpyDeviceToHost, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(out_times + (size_t)f0 * me, d_out_times, fits * time_words * 8, hipMemcpyDeviceToHost, ctx->stream));
+        // (the next slab overwrites the device buffers and h_ints; h_rows, h_taps and h_slopes are read until the stream is done)
+        TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        f0 += (int64_t)fits;
     }
     return TLS_OK;
 }

@@ -90,6 +90,7 @@ enum CheckCode {
     kChkBiweight = 10,     // tls_biweight_detrend: a span over its LDS, or an LDS index outside the staged slots
     kChkSysrem = 11,       // tls_sysrem: a row, a chunk or a component count outside the call's
     kChkSingle = 12,       // tls_single_transits: a window outside the staged slots, or a taken centre, row or window outside the series
+    kChkTimes = 13,        // tls_transit_times: a reach or a width outside the entry's limits, or a picked window outside the series
 };
 
 constexpr int kWave = 64;
@@ -4303,6 +4304,8 @@ __global__ void __launch_bounds__(512) tls_transit_models(const ModelsArgs a) {
 #include "tls_peaks.hip.h"
 // survey-mode single-transit events (tls_single_transits)
 #include "tls_single.hip.h"
+// survey-mode transit times and refitted ephemeris (tls_transit_times)
+#include "tls_times.hip.h"
 #include "tls_peak_fits.hip.h"
 #include "tls_phase_scan.hip.h"
 

@@ -318,7 +318,7 @@ HARMONICS = (0.5, 2.0, 1 / 3, 3.0, 2 / 3, 1.5)
 def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_arrays=False, devices=None, statistics=False,
                 per_transit=False, models=False, detrend=None, peaks=None, peak_separation=0.02, peak_ratios=HARMONICS,
                 peak_min_power=None, peak_fits=False, phase_scan=False, phase_scan_max_bins=4096, phase_scan_min_count=3,
-                **power_kwargs):
+                transit_times=False, transit_times_search=1.0, transit_times_min_ses=3.0, **power_kwargs):
     """Survey-mode power(): for every light curve of `flux_batch` what `transitleastsquares(t, flux).power(**kwargs)`
     reports as SDE, SDE_raw, chi2_min, period, T0, depth and duration (fractional, lc_cache_overview["duration"] of
     the template row at the chi^2 minimum, main.py:199-200) -- search, SDE spectra and final T0 fit all on the
@@ -378,6 +378,16 @@ def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_ar
     phase_scan's max_bins and min_count.  Everything else of the result stays as it is, bit for bit.  phase_scan without
     peak_fits, or with a bad max_bins or min_count, raises ValueError before any device work.
 
+    transit_times=True (with peak_fits=True) times every transit of every fitted peak on its own and refits the ephemeris
+    through the times (transit_times below states it), in one call of tls_transit_times behind the search, on the device
+    that searched the curve and on the rows it searched, from the period of the peak and T0 and duration_days of its fit
+    record, with transit_times' defaults for gap_tolerance and transit_depth_min; transit_times_search and
+    transit_times_min_ses are its search and min_ses.  The `peaks` array gains tt_status, tt_n_timed, tt_period,
+    tt_period_err, tt_T0, tt_T0_err, tt_chi2, tt_rms and tt_max_sigma (tt_status 1 and the others NaN where status != 0), and
+    the peaks dict `transit_times`, a structured array [n_curves, K, max_epochs] with the fields transit_time_fields()
+    (max_epochs: the most epochs a period of the grid can have).  Everything else of the result stays as it is, bit for
+    bit.  transit_times without peak_fits, or with a bad search or min_ses, raises ValueError before any device work.
+
     Returns (summary, periods[, chi2, row, depth, power][, per_transit][, models][, peaks]): summary is a numpy structured
     array with the fields of tls_power_summary plus "duration" (and the statistics on request)."""
     return _power_batch(t, flux_batch, dy_batch, power_kwargs, context=context, device=device, devices=devices,
@@ -385,7 +395,9 @@ def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_ar
                         detrend=detrend, peaks=_peaks_request(peaks, peak_separation, peak_ratios, peak_min_power, models,
                                                               peak_fits),
                         peak_fits=bool(peak_fits),
-                        phase_scan=_phase_scan_request(phase_scan, peak_fits, phase_scan_max_bins, phase_scan_min_count))
+                        phase_scan=_phase_scan_request(phase_scan, peak_fits, phase_scan_max_bins, phase_scan_min_count),
+                        transit_times=_transit_times_request(transit_times, peak_fits, transit_times_search,
+                                                             transit_times_min_ses))
 
 
 def _peaks_request(peaks, separation, ratios, min_power, models=False, peak_fits=False):
@@ -545,10 +557,11 @@ def find_peaks(power, periods, k, separation=0.02, ratios=HARMONICS, min_power=N
 
 def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=None, devices=None, with_arrays=False,
                  statistics=False, per_transit=False, models=False, spectra=False, detrend=None, peaks=None,
-                 peak_fits=False, phase_scan=None):
+                 peak_fits=False, phase_scan=None, transit_times=None):
     """power_batch; spectra=True (power_results) also returns SR and power_raw [n_curves, n_periods] behind the arrays;
     peaks: None or a checked request (_peaks_request); peak_fits: with peaks, their T0 fits and statistics; phase_scan: None or a checked
-    request (_phase_scan_request), with peak_fits, the fits' phase scans."""
+    request (_phase_scan_request), with peak_fits, the fits' phase scans; transit_times: None or a checked request
+    (_transit_times_request), with peak_fits, the fits' transit times."""
     models = bool(models)
     per_transit = bool(per_transit or models)
     statistics = bool(statistics or per_transit)
@@ -575,9 +588,18 @@ def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=Non
     if peak_fits:
         kw.update(peak_fits=(fill_factor, root, max_epochs), phase_scan=phase_scan)
 
+    if transit_times is not None:
+        from ._lib import TIMES_MAX_EPOCHS
+        tt_epochs = min(max_epochs, TIMES_MAX_EPOCHS)
+
     def call(ctx, lo, hi):
-        return ctx._power_batch(inp["t"], y_rows[lo:hi], dy_rows[lo:hi], inp["periods"], inp["table"], inp["params"],
+        part = ctx._power_batch(inp["t"], y_rows[lo:hi], dy_rows[lo:hi], inp["periods"], inp["table"], inp["params"],
                                 int(kernel), **kw)
+        if transit_times is not None:
+            # (the same context, the same rows: the candidates are the peaks the search fitted)
+            part["tt_ephemeris"], part["tt_times"] = _peak_transit_times(
+                ctx, inp, y_rows[lo:hi], dy_rows[lo:hi], part["peaks"], part["peak_fits"], transit_times, tt_epochs)
+        return part
 
     out = _run_batch(devices, device, context, len(y_rows), call)
     raw = out["summary"]
@@ -628,7 +650,11 @@ def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=Non
             records = _with_fits(records, out["peak_fits"], limb_darkening_factor(inp["limb_dark"], inp["u"]))
             if phase_scan is not None:
                 records = _with_scans(records, out["phase_scans"])
-        result += (dict(peaks=records, n_peaks=out["n_peaks"]),)
+        found = dict(peaks=records, n_peaks=out["n_peaks"])
+        if transit_times is not None:
+            found["peaks"] = _with_ephemeris(records, out["tt_ephemeris"])
+            found["transit_times"] = _with_oc(out["tt_ephemeris"], out["tt_times"])
+        result += (found,)
     if spectra:
         result += (out["SR"], out["power_raw"])
     return result
@@ -809,6 +835,227 @@ def single_transits(t, flux_batch, dy_batch=None, widths=None, k=8, min_ses=0.0,
     if with_arrays:
         return events, out["n_events"], out["ses"], out["row"], out["depth"]
     return events, out["n_events"]
+
+
+# ---- individual transit times and a refitted ephemeris ---------------------------------------------------------------------
+# what power_batch(..., transit_times=True) adds to the `peaks` array, and the ephemeris field each comes from
+TRANSIT_TIMES_PEAK_FIELDS = (("tt_status", "status"), ("tt_n_timed", "n_timed"), ("tt_period", "period"),
+                             ("tt_period_err", "period_err"), ("tt_T0", "T0"), ("tt_T0_err", "T0_err"),
+                             ("tt_chi2", "ttv_chi2"), ("tt_rms", "ttv_rms"), ("tt_max_sigma", "ttv_max_sigma"))
+TRANSIT_TIMES_GAP_TOLERANCE = 0.5
+
+
+def ephemeris_fields():
+    """The fields of a refitted ephemeris, in order: those of tls_ephemeris."""
+    from ._lib import EPHEMERIS_FIELDS
+    return tuple(EPHEMERIS_FIELDS)
+
+
+def transit_time_fields():
+    """The fields of one timed transit, in order: those of tls_transit_time -- epoch, status, time_linear, time, time_err,
+    ses, depth, index -- and oc = time - (T0_fit + epoch * period_fit), formed on the host."""
+    from ._lib import TRANSIT_TIME_FIELDS
+    return tuple(TRANSIT_TIME_FIELDS) + ("oc",)
+
+
+def _transit_times_options(search, min_ses, gap_tolerance=TRANSIT_TIMES_GAP_TOLERANCE, transit_depth_min=0.0,
+                           max_epochs=None):
+    """(search, min_ses, gap_tolerance, depth_min, max_epochs) of transit_times, checked: search and gap_tolerance numbers,
+    search finite and > 0, gap_tolerance finite and >= 0; the others as _lib.transit_times_options checks them (max_epochs
+    None stays None).  ValueError otherwise."""
+    import numbers
+    from ._lib import transit_times_options
+    for name, v, low in (("search", search, False), ("gap_tolerance", gap_tolerance, True)):
+        if isinstance(v, (bool, numpy.bool_)) or not isinstance(v, numbers.Real) \
+                or not ((0.0 <= float(v) if low else 0.0 < float(v)) and float(v) < numpy.inf):
+            raise ValueError("transit times: %s must be finite and %s 0, got %r" % (name, ">=" if low else ">", v))
+    depth_min, min_ses, epochs = transit_times_options(transit_depth_min, min_ses, 1 if max_epochs is None else max_epochs)
+    return float(search), min_ses, float(gap_tolerance), depth_min, None if max_epochs is None else epochs
+
+
+def _transit_times_request(transit_times, peak_fits, search, min_ses):
+    """None, or the checked (search, min_ses) of a transit_times=True request (ValueError for a bad one, and for
+    transit_times without peak_fits)."""
+    if not transit_times:
+        return None
+    if not peak_fits:
+        raise ValueError("transit_times=True needs peak_fits=True: the times start from T0 and duration of the fits")
+    return _transit_times_options(search, min_ses)[:2]
+
+
+def transit_time_rows(t, period, duration, search=1.0, gap_tolerance=TRANSIT_TIMES_GAP_TOLERANCE):
+    """(widths, span_max, row, reach) of transit_times for candidates of `period` and `duration` [n_fits] (days) on the
+    time stamps t: with dt = median(diff(t)), L_f = clip(int(round(duration_f / dt)), 3, min(4096, n)); widths are the sorted
+    distinct L_f, row[f] the index of L_f among them, span_max[r] = (L_r - 1) * dt * (1 + gap_tolerance), and
+    reach_f = max(1, min(int(search * L_f), (int(P_f / dt) - 1) // 2, 4096)) -- two epochs never share a centre (a period that
+    is not finite and > 0 gets reach 1: the device reports status 1).  ValueError for fewer than 3 time stamps, a cadence or
+    a duration that is not finite and > 0."""
+    from ._lib import SINGLE_MAX_WIDTH, SINGLE_MIN_WIDTH, TIMES_MAX_REACH
+    t = numpy.asarray(t, dtype=numpy.float64)
+    if t.ndim != 1 or len(t) < SINGLE_MIN_WIDTH:
+        raise ValueError("transit times: t must hold at least %d time stamps" % SINGLE_MIN_WIDTH)
+    dt = float(numpy.median(numpy.diff(t)))
+    if not (0.0 < dt < numpy.inf):
+        raise ValueError("transit times: the median cadence of t must be finite and > 0, got %r" % dt)
+    period = numpy.atleast_1d(numpy.asarray(period, dtype=numpy.float64))
+    duration = numpy.atleast_1d(numpy.asarray(duration, dtype=numpy.float64))
+    if duration.size and not numpy.all((duration > 0.0) & (duration < numpy.inf)):
+        raise ValueError("transit times: every duration must be finite and > 0 days")
+    top = min(SINGLE_MAX_WIDTH, len(t))
+    L = numpy.array([min(max(int(round(float(d) / dt)), SINGLE_MIN_WIDTH), top) for d in duration], dtype=numpy.int64)
+    widths = numpy.unique(L)
+    row = numpy.searchsorted(widths, L).astype(numpy.int64)
+    span_max = [(int(w) - 1) * dt * (1 + float(gap_tolerance)) for w in widths]
+    reach = numpy.ones(len(L), dtype=numpy.int64)
+    for f, P in enumerate(period):
+        if 0.0 < P < numpy.inf:
+            apart = (int(min(float(P) / dt, 4.0 * TIMES_MAX_REACH)) - 1) // 2
+            reach[f] = max(1, min(int(float(search) * int(L[f])), apart, TIMES_MAX_REACH))
+    return widths, span_max, row, reach
+
+
+def _epoch_counts(t, period, T0):
+    """n_epochs of every candidate as the statement forms it; NaN without an ephemeris."""
+    period, T0 = numpy.asarray(period, dtype=numpy.float64), numpy.asarray(T0, dtype=numpy.float64)
+    with numpy.errstate(all="ignore"):
+        count = (numpy.floor((t[-1] - T0) / period) - numpy.ceil((t[0] - T0) / period)) + 1.0
+    return numpy.where(numpy.isfinite(period) & numpy.isfinite(T0) & (period > 0.0), count, numpy.nan)
+
+
+def _with_oc(ephemeris, times):
+    """The device's epoch records plus oc = time - (T0_fit + epoch * period_fit), NaN where either is: the final table is
+    allocated once and filled through its float view, one pass for the records and one for oc."""
+    names = transit_time_fields()
+    times = numpy.ascontiguousarray(times)
+    out = numpy.empty(times.shape, dtype=[(k, "f8") for k in names])
+    raw = times.view(numpy.float64).reshape(times.shape + (len(names) - 1,))
+    flat = out.view(numpy.float64).reshape(times.shape + (len(names),))
+    flat[..., :-1] = raw
+    epoch, time = raw[..., names.index("epoch")], raw[..., names.index("time")]
+    flat[..., -1] = time - (ephemeris["T0"][..., None] + epoch * ephemeris["period"][..., None])
+    return out
+
+
+def _with_ephemeris(records, ephemeris):
+    """The peaks (with their fits) plus the tt_ fields of the device's ephemeris records."""
+    out = numpy.zeros(records.shape, dtype=records.dtype.descr + [(k, "f8") for k, _ in TRANSIT_TIMES_PEAK_FIELDS])
+    for k in records.dtype.names:
+        out[k] = records[k]
+    for k, source in TRANSIT_TIMES_PEAK_FIELDS:
+        out[k] = ephemeris[source]
+    return out
+
+
+def _peak_transit_times(ctx, inp, y_rows, dy_rows, peaks, fits, request, max_epochs):
+    """(ephemeris [n_curves, K], times [n_curves, K, max_epochs]) of the peaks of a slice of the batch, on ctx.  Every peak
+    is a candidate, so the device writes the whole table in place and nothing is filled or scattered on the host: a peak
+    whose fit status is not 0 goes in without an ephemeris (period and T0 NaN, the first row, reach 1) and comes back as
+    the statement has it, status 1 and NaN in every other field."""
+    from .template import reference_transit
+    search, min_ses = request
+    n_curves, k = fits.shape
+    fitted = (fits["status"] == 0).reshape(-1)
+    period = numpy.where(fitted, peaks["period"].reshape(-1), numpy.nan)
+    T0 = numpy.where(fitted, fits["T0"].reshape(-1), numpy.nan)
+    row, reach = numpy.zeros(n_curves * k, dtype=numpy.int64), numpy.ones(n_curves * k, dtype=numpy.int64)
+    widths, span_max = numpy.array([3], dtype=numpy.int64), [0.0]        # (no fitted peak: one row nobody reads)
+    if fitted.any():
+        widths, span_max, row[fitted], reach[fitted] = transit_time_rows(
+            inp["t"], period[fitted], fits["duration_days"].reshape(-1)[fitted], search)
+    shapes = [1.0 - numpy.asarray(reference_transit(int(L), **inp["shape"])) for L in widths]
+    eph, times = ctx.transit_times(inp["t"], y_rows, dy_rows, period, T0, row, reach, widths, shapes, span_max,
+                                   curve=numpy.repeat(numpy.arange(n_curves), k), min_ses=min_ses, max_epochs=int(max_epochs))
+    return eph.reshape(n_curves, k), times.reshape(n_curves, k, int(max_epochs))
+
+
+def transit_times(t, flux_batch, period, T0, duration, curve=None, dy_batch=None, search=1.0, min_ses=3.0,
+                  gap_tolerance=TRANSIT_TIMES_GAP_TOLERANCE, transit_depth_min=0.0, max_epochs=None, detrend=None,
+                  context=None, device=None, **template_kwargs):
+    """The individual transit times and the refitted ephemeris of candidates the caller holds, on the device
+    (tls_transit_times): candidate f is (period[f], T0[f], duration[f] in days) on light curve curve[f] of flux_batch
+    [n_curves, n] (or one row [n]) over the ascending time stamps t; curve=None takes one candidate a curve, in order.  It
+    needs no search.  TLS assumes a strictly linear ephemeris; planets near resonance transit hours early and late, and a
+    candidate that rests on one or two events looks the same in the summary as a clean planet.  The table of observed-minus-
+    computed times tells them apart, and the line through the times is the (period, T0) of every follow-up, with errors that
+    come from the transits themselves.
+
+    With dt = median(diff(t)), candidate f gets the template of L_f = clip(int(round(duration_f / dt)), 3, min(4096, n))
+    samples, b = 1 - template.reference_transit(L_f, **shape) -- the shape from the keywords and presets of power() in
+    template_kwargs --, span_max = (L_f - 1) * dt * (1 + gap_tolerance) and reach_f = max(1, min(int(search * L_f),
+    (int(P_f / dt) - 1) // 2, 4096)) (transit_time_rows); y and dy are what a search of the same rows gets.
+
+        w = 1 / dy^2;  xw = (1 - y) w;  g[j] = (b[j+1] - b[j-1]) / 2                     (the shape's slope per sample)
+        for every epoch e with t[0] <= tc = T0 + e P <= t[n-1]:  j = the sample nearest tc
+            for s = -reach .. reach:  the window of L samples centred on c = j + s, skipped where it leaves the series or runs
+                over a gap;  N = sum xw b;  D = sum w b^2;  d = N / D;  skipped unless d > transit_depth_min;  q = N / sqrt(D)
+            the shift of the largest q is held (the first on ties): ses = q, depth = d, index = c
+            one Gauss-Newton step of the shift over the whole window -- a matched filter, not a parabola through three noisy
+            values:  H = sum xw g;  Bg = sum w b g;  G = sum w g^2;  delta = (d Bg - H) / (d G) samples
+            time = (the window's centre) + delta * step;  time_err = step / (d sqrt(G)),  step = (t[c+1] - t[c-1]) / 2
+        the weighted straight line through (e, time) of the timed epochs: period, T0 and their errors from two or more, and
+        from three or more the chi^2 and the root mean square of the residuals, the largest |o - c| / time_err and its epoch
+
+    time_err is the Fisher bound of the shape at the fitted depth on white noise of the given dy: correlated noise and a
+    wrong shape make the true scatter larger, so ttv_chi2 of a quiet star is of the order of n_timed - 2 only where both
+    hold.  Epoch status: 0 timed; 1 no window with a dip (the epoch lies in a gap or at an end of the series); 2 a dip was
+    found but not timed -- the step leaves its sample (|delta| > 1: the reach's edge, a shape that does not fit) or the
+    series; 3 the dip is weaker than min_ses.  Candidate status: 0 its epochs were looked at; 1 no such ephemeris (period or
+    T0 not finite, period <= 0); 2 it has no epoch inside the series, or more than max_epochs (None: the largest count among
+    the candidates, at most 65536).
+
+    Each step is one IEEE double operation and every sum runs in index order, so the result is bit-equal to the Python
+    statement in tests/transit_times_spec.py.  search finite and > 0, gap_tolerance and transit_depth_min finite and >= 0,
+    min_ses no NaN, max_epochs in [1, 65536], durations finite and > 0, period, T0, duration and curve [n_fits] with curve in
+    [0, n_curves): ValueError otherwise, before any device work (the detrending included).  The rows -- flux and dy as a search
+    takes them -- and the template keywords are checked behind the detrending steps, before the call's own device work.
+    detrend= takes the steps and tuples of search_batch.
+
+    Returns (ephemeris, times): a structured array [n_fits] with the fields ephemeris_fields() -- status, n_epochs, n_timed,
+    epoch_first, period, period_err, T0, T0_err, ttv_chi2, ttv_rms, ttv_max_sigma, ttv_max_epoch -- and one [n_fits,
+    max_epochs] with the fields transit_time_fields() -- epoch, status, time_linear, time, time_err, ses, depth, index and
+    oc = time - (T0_fit + epoch * period_fit); NaN past a candidate's n_epochs."""
+    search, min_ses, gap_tolerance, depth_min, max_epochs = _transit_times_options(search, min_ses, gap_tolerance,
+                                                                                   transit_depth_min, max_epochs)
+    t = numpy.asarray(t, dtype=numpy.float64)
+    if numpy.ndim(flux_batch) == 1:
+        flux_batch = numpy.asarray(flux_batch)[None, :]
+        dy_batch = None if dy_batch is None else numpy.asarray(dy_batch)[None, :]
+    if numpy.ndim(flux_batch) != 2 or t.ndim != 1 or numpy.shape(flux_batch)[1] != len(t):
+        raise ValueError("flux_batch must be [n] or [n_curves, n] over the time stamps t [n]")
+    if not numpy.all(numpy.isfinite(t)) or not numpy.all(t[1:] >= t[:-1]):
+        raise ValueError("transit times: t must be finite and non-decreasing")
+    try:
+        period, T0, duration = (numpy.atleast_1d(numpy.asarray(v, dtype=numpy.float64)) for v in (period, T0, duration))
+    except (TypeError, ValueError):
+        raise ValueError("transit times: period, T0 and duration must be numbers")
+    if period.ndim != 1 or not period.shape == T0.shape == duration.shape:
+        raise ValueError("transit times: period, T0 and duration must be [n_fits]")
+    n_curves = numpy.shape(flux_batch)[0]
+    if curve is None:
+        if len(period) != n_curves:
+            raise ValueError("transit times: curve=None takes one candidate a light curve: %d candidates, %d curves"
+                             % (len(period), n_curves))
+        curve = numpy.arange(n_curves)
+    curve = numpy.atleast_1d(numpy.asarray(curve))
+    if curve.shape != period.shape or (curve.size and (curve.dtype.kind not in "iu" or curve.min() < 0
+                                                        or curve.max() >= n_curves)):
+        raise ValueError("transit times: curve must hold one index in [0, %d) a candidate" % n_curves)
+    widths, span_max, row, reach = transit_time_rows(t, period, duration, search, gap_tolerance)
+    if max_epochs is None:
+        from ._lib import TIMES_MAX_EPOCHS
+        counts = _epoch_counts(t, period, T0)
+        counts = counts[(counts >= 1.0) & (counts <= TIMES_MAX_EPOCHS)]
+        max_epochs = int(counts.max()) if len(counts) else 1
+    flux_batch = _detrended(t, flux_batch, detrend, context, device, None, dy_batch)
+    kwargs = dict(template_kwargs)
+    kwargs.setdefault("oversampling_factor", 1)      # (the period grid of the plan inputs is not used: the coarsest will do)
+    inp, y_rows, dy_rows = _batch_inputs(t, flux_batch, dy_batch, kwargs)
+    from .template import reference_transit
+    shapes = [1.0 - numpy.asarray(reference_transit(int(L), **inp["shape"])) for L in widths]
+    ctx = context if context is not None else _search.default_context(device)
+    eph, times = ctx.transit_times(inp["t"], y_rows, dy_rows, period, T0, row, reach, widths, shapes, span_max, curve=curve,
+                                   depth_min=depth_min, min_ses=min_ses, max_epochs=max_epochs)
+    return eph, _with_oc(eph, times)
 
 
 # ---- injection-recovery ---------------------------------------------------------------------------------------------------
