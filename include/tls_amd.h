@@ -38,7 +38,8 @@ extern "C" {
  * signature keep the version (7: tls_inject_transits, tls_null_rows, tls_debug_null_words,
  * tls_medfilt_detrend, tls_biweight_detrend), (7: tls_power_batch_peaks, tls_find_peaks),
  * (7: tls_power_batch_peak_fits, tls_debug_peak_fits), (7: tls_phase_scan, tls_power_batch_phase_scan,
- * tls_debug_peak_phase_scans), (7: tls_sysrem), (7: tls_single_transits), (7: tls_transit_times). */
+ * tls_debug_peak_phase_scans), (7: tls_sysrem), (7: tls_single_transits), (7: tls_transit_times),
+ * (7: tls_shape_fit). */
 #define TLS_AMD_ABI_VERSION 7
 
 #define TLS_OK 0
@@ -705,6 +706,50 @@ int tls_transit_times(tls_ctx *ctx, const double *t, const double *y, const doub
                       int64_t n_fits, const double *shape_values, const int64_t *shape_offset, const int64_t *width,
                       const double *span_max, int64_t n_rows, double depth_min, double min_ses, int64_t max_epochs,
                       tls_ephemeris *out /* [n_fits] */, tls_transit_time *out_times /* [n_fits][max_epochs] */);
+
+/* The shape of a candidate's dip: a trapezoid of unit depth -- total duration T (T14), flat bottom T (1 - 2 g), g = T12/T14,
+ * centre shifted by c0 -- is fitted to the points around every transit of a linear ephemeris, over a grid of durations,
+ * ingress fractions and shifts, with the baseline fixed at 1.  A box is g = 0, a V is g = 0.5.  For a curve (y [n], dy [n]
+ * over the ascending, finite t [n]), a candidate (P, T0, d in days) and the ascending tables ratio[nT] > 0, ingress[nQ] with
+ * ingress[0] == 0.0 and ingress[nQ-1] == 0.5, shift[nS]:
+ *   w = 1.0 / (dy * dy);  xw = (1.0 - y) * w
+ *   status 1 and NaN in every other field unless P, T0, d are finite, P > 0, d > 0 and wd = window * d < 0.5 * P
+ *   members, i ascending:  x = (t[i] - T0) / P;  k = floor(x + 0.5);  tau = (x - k) * P;  member iff fabs(tau) <= wd
+ *   unit (a, b, c), a outermost, c innermost (unit index (a * nQ + b) * nS + c):
+ *       T = d * ratio[a];  ho = 0.5 * T;  hb = ho * (1.0 - 2.0 * ingress[b]);  r = 1.0 / (ho - hb) where hb < ho;  c0 = d * shift[c]
+ *       cnt = 0; N = 0; D = 0; over the members in index order:  u = fabs(tau - c0)
+ *           s = 1.0 if u <= hb, else (ho - u) * r if u < ho, else the member does not count
+ *           cnt += 1;  N = N + xw * s;  s2 = s * s;  D = D + w * s2
+ *       valid iff cnt >= min_count and D > 0 and dep = N / D > depth_min;  q = N / sqrt(D)
+ *   best = the valid unit of the largest q, the first in unit order among equals; box and vee = the same pick among the units
+ *   with b == 0 and with b == nQ - 1;  status 2 (n_points reported, the rest NaN) if no unit is valid.
+ * ses^2 - ses_vee^2 is the chi^2 by which the best trapezoid beats the best V; ses_box^2 - ses_vee^2 has the sign of the shape.
+ * The trapezoid knows nothing of limb darkening or exposure time: `ingress` of a planet is larger than its geometric T12/T14.
+ * Every step is one IEEE double operation and every sum runs in index order: the record equals the Python statement in
+ * tests/shape_fit_spec.py bit for bit.  All fields are doubles. */
+#define TLS_SHAPE_MAX_UNITS 65536
+typedef struct tls_shape_record {
+    double status;                 /* 0 fitted; 1 no such candidate (P, T0, d, or a window of half a period or more); 2 no valid unit */
+    double n_points;               /* the members */
+    double n_in;                   /* cnt of the best unit */
+    double ses, depth, depth_err;  /* q, N / D and 1 / sqrt(D) of the best unit */
+    double duration, ingress, shift;           /* T (days), ingress[b] (T12/T14), c0 (days) of the best unit */
+    double i_duration, i_ingress, i_shift;     /* a, b, c */
+    double ses_box, duration_box;  /* q and T of the best unit with b == 0 */
+    double ses_vee, duration_vee;  /* q and T of the best unit with b == nQ - 1 */
+} tls_shape_record;
+/* n_fits candidates (period[f], T0[f], duration[f]) on the curves curve[f] of y, dy [n_curves][n] over the shared time stamps
+ * t [n].  out [n_fits].  Needs no plan and no search, and leaves a prepared plan as it is.  n_fits == 0 is a no-op.
+ * Candidates are processed in slabs, so device memory stays bounded for any n_fits.  TLS_E_ARG, before any device work and
+ * with the output untouched, for a curve[f] outside [0, n_curves), n outside [1, 2^22], negative counts, an empty table,
+ * nT * nQ * nS above TLS_SHAPE_MAX_UNITS, a table that is not finite and non-decreasing, a ratio <= 0, ingress[0] != 0.0 or
+ * ingress[nQ-1] != 0.5, a window that is not finite or below 0.5 * ratio[nT-1] + max(fabs(shift[0]), fabs(shift[nS-1])) (the
+ * model must lie inside the window), min_count < 1, a non-finite or negative depth_min, and a t that is not finite and
+ * non-decreasing.  y and dy are taken as they are (dy > 0); period, T0 and duration may hold any value (status 1). */
+int tls_shape_fit(tls_ctx *ctx, const double *t, const double *y, const double *dy, int64_t n, int64_t n_curves,
+                  const double *period, const double *T0, const double *duration, const int64_t *curve, int64_t n_fits,
+                  const double *ratio, int64_t nT, const double *ingress, int64_t nQ, const double *shift, int64_t nS,
+                  double window, int64_t min_count, double depth_min, tls_shape_record *out /* [n_fits] */);
 
 /* ---- host-only planning (no GPU needed) ------------------------------------------ */
 /* Trial cells (duration x T0 positions) each period will enumerate: the data-independent

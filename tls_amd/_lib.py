@@ -50,6 +50,11 @@ SINGLE_MAX_POINTS = 1 << 20
 TIMES_MAX_REACH = 4096
 TIMES_MAX_EPOCHS = 65536
 TIMES_MAX_POINTS = 1 << 30   # tls_times.hip.h kTimesMaxPoints
+# include/tls_amd.h TLS_SHAPE_MAX_UNITS: the most (duration, ingress, shift) units of tls_shape_fit; tls_shape.hip.h
+# kShapeMaxPoints and kShapeLdsMembers (the members of a candidate the LDS holds; more are staged through it in tiles)
+SHAPE_MAX_UNITS = 65536
+SHAPE_MAX_POINTS = 1 << 22
+SHAPE_LDS_MEMBERS = 2048
 PEAKS_LDS_PERIODS = 1 << 20   # tls_peaks.hip.h kPeaksLdsPeriods: a longer grid keeps its alive mask in device memory, not in LDS
 
 # every symbol include/tls_amd.h declares (tests check the export list against the header)
@@ -62,7 +67,7 @@ SYMBOLS = (
     "tls_inject_transits", "tls_null_rows", "tls_debug_null_words", "tls_medfilt_detrend",
     "tls_biweight_detrend", "tls_sysrem", "tls_find_peaks", "tls_power_batch_peaks", "tls_power_batch_peak_fits", "tls_debug_peak_fits",
     "tls_phase_scan", "tls_power_batch_phase_scan", "tls_debug_peak_phase_scans", "tls_single_transits",
-    "tls_transit_times",
+    "tls_transit_times", "tls_shape_fit",
     "tls_comm_unique_id", "tls_comm_init", "tls_comm_destroy", "tls_comm_info", "tls_comm_allgather_results", "tls_comm_allgather_device", "tls_comm_fetch_gathered",
     "tls_comm_stage_results", "tls_comm_allgather_staged", "tls_comm_fetch_staged",
     "tls_comm_barrier", "tls_comm_max",
@@ -376,6 +381,108 @@ def transit_times_arguments(t, y, dy, period, T0, row, reach, widths, shapes, sp
     return a
 
 
+# tls_shape_record (include/tls_amd.h): a candidate's trapezoid shape fit, 16 doubles
+SHAPE_FIELDS = ("status", "n_points", "n_in", "ses", "depth", "depth_err", "duration", "ingress", "shift", "i_duration",
+                "i_ingress", "i_shift", "ses_box", "duration_box", "ses_vee", "duration_vee")
+
+
+class ShapeRecord(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_double) for k in SHAPE_FIELDS]
+
+
+SHAPE_DTYPE = numpy.dtype([(k, "f8") for k in SHAPE_FIELDS])
+
+
+def shape_fit_tables(ratios, ingress, shifts, window=2.0, min_count=3, depth_min=0.0):
+    """(ratio, ingress, shift, window, min_count, depth_min) as tls_shape_fit takes them, checked as it checks them: every
+    table 1-D, not empty, finite and non-decreasing; every ratio > 0; ingress[0] == 0.0 and ingress[-1] == 0.5; between 1 and
+    SHAPE_MAX_UNITS units; window finite and at least 0.5 * max(ratio) + max|shift| (the model must lie inside the window);
+    min_count an integer >= 1; depth_min finite and >= 0.  ValueError otherwise."""
+    tables = []
+    for name, v in (("ratios", ratios), ("ingress", ingress), ("shifts", shifts)):
+        try:
+            v = numpy.ascontiguousarray(numpy.asarray(v, dtype=numpy.float64))
+        except (TypeError, ValueError):
+            raise ValueError("shape fit: %s must hold numbers" % name)
+        if v.ndim != 1 or len(v) < 1:
+            raise ValueError("shape fit: %s must be a table [k] with k >= 1, got shape %s" % (name, v.shape))
+        if not numpy.all(numpy.isfinite(v)) or not numpy.all(v[1:] >= v[:-1]):
+            raise ValueError("shape fit: %s must be finite and ascending" % name)
+        tables.append(v)
+    ratio, ingress, shift = tables
+    if not ratio[0] > 0.0:
+        raise ValueError("shape fit: every ratio must be > 0, got %r" % ratio[0])
+    if ingress[0] != 0.0 or ingress[-1] != 0.5:
+        raise ValueError("shape fit: ingress must run from 0.0 (a box) to 0.5 (a V), got %r to %r" % (ingress[0], ingress[-1]))
+    units = len(ratio) * len(ingress) * len(shift)
+    if not 1 <= units <= SHAPE_MAX_UNITS:
+        raise ValueError("shape fit: %d units, outside [1, %d]" % (units, SHAPE_MAX_UNITS))
+    if isinstance(window, (bool, numpy.bool_)) or not isinstance(window, numbers.Real) or not numpy.isfinite(window):
+        raise ValueError("shape fit: window must be finite, got %r" % (window,))
+    least = 0.5 * float(ratio[-1]) + max(abs(float(shift[0])), abs(float(shift[-1])))
+    if not float(window) >= least:
+        raise ValueError("shape fit: window %r is below 0.5 * max(ratio) + max|shift| = %r: the model must lie inside it"
+                         % (window, least))
+    if isinstance(min_count, (bool, numpy.bool_)) or not isinstance(min_count, numbers.Integral) or int(min_count) < 1:
+        raise ValueError("shape fit: min_count must be an integer >= 1, got %r" % (min_count,))
+    if isinstance(depth_min, (bool, numpy.bool_)) or not isinstance(depth_min, numbers.Real) \
+            or not (0.0 <= float(depth_min) < numpy.inf):
+        raise ValueError("shape fit: transit_depth_min must be finite and >= 0, got %r" % (depth_min,))
+    return ratio, ingress, shift, float(window), int(min_count), float(depth_min)
+
+
+def shape_fit_candidates(period, T0, duration, curve, n_curves):
+    """(period, T0, duration [n_fits] float64, curve [n_fits] int64) of tls_shape_fit, checked: numbers of one 1-D shape (any
+    value: the device gives a candidate without an ephemeris status 1), curve (None: one candidate a curve, in order) integers
+    in [0, n_curves).  ValueError otherwise."""
+    try:
+        period, T0, duration = (numpy.ascontiguousarray(numpy.atleast_1d(numpy.asarray(v, dtype=numpy.float64)))
+                                for v in (period, T0, duration))
+    except (TypeError, ValueError):
+        raise ValueError("shape fit: period, T0 and duration must be numbers")
+    if period.ndim != 1 or not period.shape == T0.shape == duration.shape:
+        raise ValueError("shape fit: period, T0 and duration must be [n_fits]")
+    if curve is None:
+        if len(period) != n_curves:
+            raise ValueError("shape fit: curve=None takes one candidate a light curve: %d candidates, %d curves"
+                             % (len(period), n_curves))
+        curve = numpy.arange(n_curves)
+    curve = numpy.atleast_1d(numpy.asarray(curve))
+    if curve.shape != period.shape or (curve.size and (curve.dtype.kind not in "iu" or curve.min() < 0
+                                                        or curve.max() >= n_curves)):
+        raise ValueError("shape fit: curve must hold one index in [0, %d) a candidate" % n_curves)
+    return period, T0, duration, numpy.ascontiguousarray(curve, dtype=numpy.int64)
+
+
+def shape_fit_arguments(t, y, dy, period, T0, duration, ratios, ingress, shifts, curve=None, window=2.0, min_count=3,
+                        depth_min=0.0):
+    """What tls_shape_fit takes, checked as it checks them and packed for it -- a dict with t [n] (1-D, n in
+    [1, SHAPE_MAX_POINTS], finite and non-decreasing), y and dy [n_curves, n] (y finite, dy finite and > 0), period, T0,
+    duration, curve [n_fits] (shape_fit_candidates), ratio, ingress, shift, window, min_count, depth_min
+    (shape_fit_tables).  ValueError otherwise.  GPU-free."""
+    ratio, ingress, shift, window, min_count, depth_min = shape_fit_tables(ratios, ingress, shifts, window, min_count, depth_min)
+    t = numpy.asarray(t, dtype=numpy.float64)
+    if t.ndim != 1 or not 1 <= len(t) <= SHAPE_MAX_POINTS:
+        raise ValueError("shape fit: t must have shape [n] with n in [1, %d], got %s" % (SHAPE_MAX_POINTS, t.shape))
+    if not numpy.all(numpy.isfinite(t)) or not numpy.all(t[1:] >= t[:-1]):
+        raise ValueError("shape fit: t must be finite and non-decreasing")
+    y, dy = numpy.asarray(y, dtype=numpy.float64), numpy.asarray(dy, dtype=numpy.float64)
+    if y.ndim == 1:
+        y = y[None, :]
+    if dy.ndim == 1:
+        dy = dy[None, :]
+    if y.ndim != 2 or y.shape[1] != len(t) or dy.shape != y.shape:
+        raise ValueError("shape fit: y and dy must be [n] or [n_curves, n] over the time stamps t [n]")
+    if y.size and not numpy.all(numpy.isfinite(y)):
+        raise ValueError("shape fit: y has a NaN or an infinite value")
+    if dy.size and not (dy.min() > 0.0 and dy.max() < numpy.inf):
+        raise ValueError("shape fit: dy has a NaN, infinite or non-positive value")
+    period, T0, duration, curve = shape_fit_candidates(period, T0, duration, curve, len(y))
+    return dict(t=numpy.ascontiguousarray(t), y=numpy.ascontiguousarray(y), dy=numpy.ascontiguousarray(dy), period=period,
+                T0=T0, duration=duration, curve=curve, ratio=ratio, ingress=ingress, shift=shift, window=window,
+                min_count=min_count, depth_min=depth_min)
+
+
 def peaks_arguments(k, separation, ratios, min_power):
     """(k, separation, ratios, min_power) as the peak selection takes them, checked as tls_find_peaks checks them: k an
     integer in [1, PEAKS_MAX_K]; separation finite and in [0, 1); at most PEAKS_MAX_RATIOS ratios, each finite and > 0;
@@ -560,6 +667,10 @@ def load():
     lib.tls_transit_times.argtypes = [vp, _c_double_p, _c_double_p, _c_double_p, i64, i64, _c_int64_p, _c_double_p, _c_double_p,
                                       _c_int64_p, _c_int64_p, i64, _c_double_p, _c_int64_p, _c_int64_p, _c_double_p, i64, dbl,
                                       dbl, i64, ctypes.c_void_p, ctypes.c_void_p]
+    lib.tls_shape_fit.restype = ci
+    lib.tls_shape_fit.argtypes = [vp, _c_double_p, _c_double_p, _c_double_p, i64, i64, _c_double_p, _c_double_p, _c_double_p,
+                                  _c_int64_p, i64, _c_double_p, i64, _c_double_p, i64, _c_double_p, i64, dbl, i64, dbl,
+                                  ctypes.c_void_p]
     lib.tls_debug_peak_phase_scans.restype = ci
     lib.tls_debug_peak_phase_scans.argtypes = [vp, _c_double_p, i64, ctypes.c_void_p, _c_int64_p, i64, _c_double_p, _c_double_p,
                                                i64, dbl, _c_double_p, i64, i64, ctypes.c_void_p, i64, i64, ctypes.c_void_p]
@@ -1330,6 +1441,23 @@ class Context(object):
             eph.ctypes.data_as(ctypes.c_void_p), times.ctypes.data_as(ctypes.c_void_p)))
         return eph, times
 
+    def shape_fit(self, t, y, dy, period, T0, duration, ratios, ingress, shifts, curve=None, window=2.0, min_count=3,
+                  depth_min=0.0):
+        """The trapezoid shape fits (tls_shape_fit; the statement: include/tls_amd.h, tests/shape_fit_spec.py) of the
+        candidates (period[f], T0[f], duration[f] in days) on the curves curve[f] (None: one candidate a curve, in order) of
+        y, dy [n_curves, n] (or one row) over t [n], over the units of the tables ratios, ingress, shifts: SHAPE_DTYPE
+        [n_fits].  ValueError for what shape_fit_arguments refuses."""
+        a = shape_fit_arguments(t, y, dy, period, T0, duration, ratios, ingress, shifts, curve, window, min_count, depth_min)
+        n_c, n = a["y"].shape
+        n_fits = len(a["period"])
+        out = numpy.zeros(n_fits, dtype=SHAPE_DTYPE)
+        assert SHAPE_DTYPE.itemsize == ctypes.sizeof(ShapeRecord)
+        self._check(self._lib.tls_shape_fit(
+            self._h, _dp(a["t"]), _dp(a["y"]), _dp(a["dy"]), n, n_c, _dp(a["period"]), _dp(a["T0"]), _dp(a["duration"]),
+            _ip(a["curve"]), n_fits, _dp(a["ratio"]), len(a["ratio"]), _dp(a["ingress"]), len(a["ingress"]), _dp(a["shift"]),
+            len(a["shift"]), a["window"], a["min_count"], a["depth_min"], out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
     def debug_null_words(self, n, n_rows, seed, first_trial=0, block=None):
         """The raw Philox words [n_rows, W] tls_null_rows draws for these trials (tls_debug_null_words): white-noise
         layout when `block` is None, the bootstrap's otherwise."""
@@ -1442,7 +1570,7 @@ class Context(object):
             self._check(rc)
         names = ("lds_carve", "list_capacity", "dot_window", "predicate_read", "sort_window", "work_item",
                  "singles_capacity", "tile_stage", "screen_split", "detrend_slot",
-                 "biweight_slot", "sysrem_index", "single_window")
+                 "biweight_slot", "sysrem_index", "single_window", "times_window", "shape_index")
         return bool(rc), dict(zip(names, [int(v) for v in arr]))
 
     def poison_lds(self, word=0x7ff80000):

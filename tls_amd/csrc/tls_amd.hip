@@ -223,6 +223,8 @@ struct tls_ctx {
     DevBuf<double> d_single;
     // tls_transit_times: of one slab: pairs | y | dy | records | times | period | T0 | slot, row, reach; t | rows | taps | slopes
     DevBuf<double> d_times;
+    // tls_shape_fit: of one slab: pairs | y | dy | records | period | T0 | duration | slot; t | ratio | ingress | shift | scratch
+    DevBuf<double> d_shape;
     // two-role slab path (series in HBM, one light curve; SearchPlan::split)
     View<unsigned int> d_tile_prefix;        // [n_periods + 1] tiles in front of work item w (queue order)
     DevBuf<double> d_partials;               // [split_max_items][3] a tile's winner
@@ -1638,6 +1640,7 @@ void tls_ctx_destroy(tls_ctx* ctx) {
     ctx->d_scan.release();
     ctx->d_single.release();
     ctx->d_times.release();
+    ctx->d_shape.release();
     ctx->d_split.release(); ctx->d_park.release(); ctx->d_band.release();
     if (ctx->h_band) (void)hipHostFree(ctx->h_band);
     for (auto& ev : ctx->ev_band) if (ev) (void)hipEventDestroy(ev);
@@ -2794,6 +2797,7 @@ int tls_debug_device_bytes(const tls_ctx* ctx, int64_t* total, int64_t* t0_fit_s
     add(ctx->d_scan);
     add(ctx->d_single);
     add(ctx->d_times);
+    add(ctx->d_shape);
     add(ctx->d_partials); add(ctx->d_tiles_done);
     add(ctx->d_split); add(ctx->d_park); add(ctx->d_band);
     *total = (int64_t)sum;
@@ -3445,6 +3449,134 @@ int tls_transit_times(tls_ctx* ctx, const double* t, const double* y, const doub
         TLS_HIP(ctx, hipMemcpyAsync(out + f0, d_out, fits * eph_words * 8, hipMemcpyDeviceToHost, ctx->stream));
         TLS_HIP(ctx, hipMemcpyAsync(out_times + (size_t)f0 * me, d_out_times, fits * time_words * 8, hipMemcpyDeviceToHost, ctx->stream));
         // (the next slab overwrites the device buffers and h_ints; h_rows, h_taps and h_slopes are read until the stream is done)
+        TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        f0 += (int64_t)fits;
+    }
+    return TLS_OK;
+}
+
+// ---- the trapezoid shape fit (tls_shape.hip.h, DESIGN.md "Shape fit"): the pairs kernel of the transit times over the curves
+// a slab of candidates reads, then one workgroup a candidate, slab by slab
+static_assert(sizeof(tls_shape_record) == tlsdev::kShapeWords * 8, "tls_shape_record is the kernel's record");
+static_assert(TLS_SHAPE_MAX_UNITS == tlsdev::kShapeMaxUnits, "the header's limit");
+
+int tls_shape_fit(tls_ctx* ctx, const double* t, const double* y, const double* dy, int64_t n, int64_t n_curves,
+                  const double* period, const double* T0, const double* duration, const int64_t* curve, int64_t n_fits,
+                  const double* ratio, int64_t nT, const double* ingress, int64_t nQ, const double* shift, int64_t nS,
+                  double window, int64_t min_count, double depth_min, tls_shape_record* out) {
+    if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
+    if (n_fits < 0 || n_curves < 0 || n < 0) return fail(ctx, TLS_E_ARG, "shape fit: negative count");
+    if (nT < 1 || nQ < 1 || nS < 1) return fail(ctx, TLS_E_ARG, "shape fit: every table needs an entry");
+    if (nT > TLS_SHAPE_MAX_UNITS || nQ > TLS_SHAPE_MAX_UNITS || nS > TLS_SHAPE_MAX_UNITS || nT * nQ * nS > TLS_SHAPE_MAX_UNITS)
+        return fail(ctx, TLS_E_ARG, "shape fit: more than 65536 units");
+    if (!ratio || !ingress || !shift) return fail(ctx, TLS_E_ARG, "null argument");
+    for (const auto& table : {std::make_pair(ratio, nT), std::make_pair(ingress, nQ), std::make_pair(shift, nS)})
+        for (int64_t i = 0; i < table.second; ++i)
+            if (!std::isfinite(table.first[i]) || (i > 0 && table.first[i] < table.first[i - 1]))
+                return fail(ctx, TLS_E_ARG, "shape fit: the tables must be finite and non-decreasing");
+    if (!(ratio[0] > 0.0)) return fail(ctx, TLS_E_ARG, "shape fit: every ratio must be > 0");
+    if (ingress[0] != 0.0 || ingress[nQ - 1] != 0.5) return fail(ctx, TLS_E_ARG, "shape fit: ingress must run from 0.0 to 0.5");
+    if (!(std::isfinite(window) && window >= 0.5 * ratio[nT - 1] + std::max(std::fabs(shift[0]), std::fabs(shift[nS - 1]))))
+        return fail(ctx, TLS_E_ARG, "shape fit: the window must be finite and hold the widest, farthest shifted model");
+    if (min_count < 1) return fail(ctx, TLS_E_ARG, "shape fit: min_count < 1");
+    if (!(std::isfinite(depth_min) && depth_min >= 0.0)) return fail(ctx, TLS_E_ARG, "shape fit: depth_min must be finite and >= 0");
+    if (n_fits == 0) return TLS_OK;
+    if (!t || !y || !dy || !curve || !period || !T0 || !duration || !out) return fail(ctx, TLS_E_ARG, "null argument");
+    if (n < 1 || n > tlsdev::kShapeMaxPoints) return fail(ctx, TLS_E_ARG, "shape fit: n out of range [1, 2^22]");
+    if (n_fits > INT32_MAX || (uint64_t)n_curves > (uint64_t)(INT64_MAX / 16) / (uint64_t)n)
+        return fail(ctx, TLS_E_ARG, "shape fit: batch too large");
+    for (int64_t i = 0; i < n; ++i)
+        if (!std::isfinite(t[i]) || (i > 0 && t[i] < t[i - 1]))
+            return fail(ctx, TLS_E_ARG, "shape fit: the time stamps must be finite and non-decreasing");
+    for (int64_t f = 0; f < n_fits; ++f)
+        if (curve[f] < 0 || curve[f] >= n_curves) return fail(ctx, TLS_E_ARG, "shape fit: curve out of range [0, n_curves)");
+    TLS_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t nn = (size_t)n, words = tlsdev::kShapeWords, tables = (size_t)(nT + nQ + nS);
+    // a slab: at most 1024 candidates on at most 1024 curves, 256 MB of curves (32 bytes a point); the workgroups of a launch:
+    // at most 1024, 256 MB of member scratch (24 bytes a point each)
+    const size_t budget = 256u << 20;
+    const size_t cs = std::max<size_t>(1, std::min<size_t>({(size_t)n_curves, 1024, budget / (32 * nn)}));
+    const size_t sl = std::min<size_t>((size_t)n_fits, 1024);
+    const size_t groups = std::max<size_t>(1, std::min<size_t>({sl, (size_t)tlsdev::kShapeMaxGroups, budget / (24 * nn)}));
+    // of one slab: pairs | y | dy | records | period | T0 | duration | slot;  t | ratio | ingress | shift | scratch
+    TLS_HIP(ctx, ctx->d_shape.reserve(4 * cs * nn + sl * (words + 3) + (sl + 1) / 2 + nn + tables + 3 * groups * nn));
+    double2* d_pairs = reinterpret_cast<double2*>(ctx->d_shape.ptr);           // (the allocation's start: 16-byte aligned)
+    double* d_y = ctx->d_shape.ptr + 2 * cs * nn;
+    double* d_dy = d_y + cs * nn;
+    double* d_out = d_dy + cs * nn;
+    double* d_period = d_out + sl * words;
+    double* d_T0 = d_period + sl;
+    double* d_duration = d_T0 + sl;
+    int* d_slot = reinterpret_cast<int*>(d_duration + sl);
+    double* d_t = d_duration + sl + (sl + 1) / 2;
+    double* d_ratio = d_t + nn;
+    double* d_ingress = d_ratio + nT;
+    double* d_shift = d_ingress + nQ;
+    double* d_scratch = d_shift + nS;
+    if (!ctx->d_check.ptr) {
+        TLS_HIP(ctx, ctx->d_check.reserve(tlsdev::kChecks));
+        TLS_HIP(ctx, hipMemsetAsync(ctx->d_check.ptr, 0, tlsdev::kChecks * sizeof(unsigned long long), ctx->stream));
+    }
+    tlsdev::TimesPairsArgs p;
+    p.y = d_y; p.dy = d_dy; p.pairs = d_pairs;
+    tlsdev::ShapeArgs a;
+    a.t = d_t; a.pairs = d_pairs; a.slot = d_slot; a.period = d_period; a.T0 = d_T0; a.duration = d_duration;
+    a.ratio = d_ratio; a.ingress = d_ingress; a.shift = d_shift; a.scratch = d_scratch; a.out = d_out;
+    a.check = ctx->d_check.ptr; a.window = window; a.depth_min = depth_min;
+    a.n = (int)n; a.nT = (int)nT; a.nQ = (int)nQ; a.nS = (int)nS;
+    a.min_count = (int)std::min<int64_t>(min_count, INT32_MAX);
+    auto pairs_kernel = tlsdev::tls_times_pairs_kernel;
+    auto shape_kernel = tlsdev::tls_shape_fit_kernel;
+    TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_ratio, ratio, (size_t)nT * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_ingress, ingress, (size_t)nQ * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_shift, shift, (size_t)nS * 8, hipMemcpyHostToDevice, ctx->stream));
+    std::vector<int> h_slot(sl);
+    std::unordered_map<int64_t, int> slot_of;
+    struct Run { int64_t curve; size_t slot, count; };      // consecutive curves in consecutive slots: one copy
+    std::vector<Run> runs;
+    for (int64_t f0 = 0; f0 < n_fits;) {
+        slot_of.clear();
+        runs.clear();
+        size_t fits = 0;
+        while (f0 + (int64_t)fits < n_fits && fits < sl) {
+            const int64_t f = f0 + (int64_t)fits;
+            auto it = slot_of.find(curve[f]);
+            if (it == slot_of.end()) {
+                if (slot_of.size() == cs) break;     // (the next slab takes it; a slab's first candidate always finds a slot)
+                const size_t slot = slot_of.size();
+                it = slot_of.emplace(curve[f], (int)slot).first;
+                if (!runs.empty() && runs.back().curve + (int64_t)runs.back().count == curve[f]) ++runs.back().count;
+                else runs.push_back(Run{curve[f], slot, 1});
+            }
+            h_slot[fits] = it->second;
+            ++fits;
+        }
+        for (const Run& run : runs) {
+            const size_t from = (size_t)run.curve * nn, to = run.slot * nn, bytes = run.count * nn * 8;
+            TLS_HIP(ctx, hipMemcpyAsync(d_y + to, y + from, bytes, hipMemcpyHostToDevice, ctx->stream));
+            TLS_HIP(ctx, hipMemcpyAsync(d_dy + to, dy + from, bytes, hipMemcpyHostToDevice, ctx->stream));
+        }
+        TLS_HIP(ctx, hipMemcpyAsync(d_slot, h_slot.data(), fits * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(d_period, period + f0, fits * 8, hipMemcpyHostToDevice, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(d_T0, T0 + f0, fits * 8, hipMemcpyHostToDevice, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(d_duration, duration + f0, fits * 8, hipMemcpyHostToDevice, ctx->stream));
+        p.count = (long long)(slot_of.size() * nn);
+        a.fits = (int)fits;
+        const unsigned blocks = (unsigned)std::min<long long>((p.count + tlsdev::kTimesThreads - 1) / tlsdev::kTimesThreads, 8192);
+        hipLaunchKernelGGL(pairs_kernel, dim3(blocks), dim3(tlsdev::kTimesThreads), 0, ctx->stream, p);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(shape_kernel, dim3((unsigned)std::min(fits, groups)), dim3(tlsdev::kShapeThreads), 0, ctx->stream, a);
+            e = hipGetLastError();
+        }
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(ctx->stream);
+            return fail(ctx, TLS_E_HIP, std::string("shape fit launch: ") + hipGetErrorString(e));
+        }
+        ctx->last_kernel = "tls_shape_fit";
+        TLS_HIP(ctx, hipMemcpyAsync(out + f0, d_out, fits * words * 8, hipMemcpyDeviceToHost, ctx->stream));
+        // (the next slab overwrites the device buffers and h_slot)
         TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
         f0 += (int64_t)fits;
     }

@@ -91,6 +91,7 @@ enum CheckCode {
     kChkSysrem = 11,       // tls_sysrem: a row, a chunk or a component count outside the call's
     kChkSingle = 12,       // tls_single_transits: a window outside the staged slots, or a taken centre, row or window outside the series
     kChkTimes = 13,        // tls_transit_times: a reach or a width outside the entry's limits, or a picked window outside the series
+    kChkShape = 14,        // tls_shape_fit: a member's rank or a unit's table index outside its limits
 };
 
 constexpr int kWave = 64;
@@ -4306,6 +4307,8 @@ __global__ void __launch_bounds__(512) tls_transit_models(const ModelsArgs a) {
 #include "tls_single.hip.h"
 // survey-mode transit times and refitted ephemeris (tls_transit_times)
 #include "tls_times.hip.h"
+// survey-mode trapezoid shape fit (tls_shape_fit)
+#include "tls_shape.hip.h"
 #include "tls_peak_fits.hip.h"
 #include "tls_phase_scan.hip.h"
 

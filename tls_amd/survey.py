@@ -318,7 +318,8 @@ HARMONICS = (0.5, 2.0, 1 / 3, 3.0, 2 / 3, 1.5)
 def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_arrays=False, devices=None, statistics=False,
                 per_transit=False, models=False, detrend=None, peaks=None, peak_separation=0.02, peak_ratios=HARMONICS,
                 peak_min_power=None, peak_fits=False, phase_scan=False, phase_scan_max_bins=4096, phase_scan_min_count=3,
-                transit_times=False, transit_times_search=1.0, transit_times_min_ses=3.0, **power_kwargs):
+                transit_times=False, transit_times_search=1.0, transit_times_min_ses=3.0, shape_fit=False,
+                shape_fit_window=2.0, shape_fit_min_count=3, **power_kwargs):
     """Survey-mode power(): for every light curve of `flux_batch` what `transitleastsquares(t, flux).power(**kwargs)`
     reports as SDE, SDE_raw, chi2_min, period, T0, depth and duration (fractional, lc_cache_overview["duration"] of
     the template row at the chi^2 minimum, main.py:199-200) -- search, SDE spectra and final T0 fit all on the
@@ -388,6 +389,14 @@ def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_ar
     (max_epochs: the most epochs a period of the grid can have).  Everything else of the result stays as it is, bit for
     bit.  transit_times without peak_fits, or with a bad search or min_ses, raises ValueError before any device work.
 
+    shape_fit=True (with peak_fits=True) fits a trapezoid to the dip of every fitted peak -- flat-bottomed like a planet or
+    V-shaped like a grazing binary (shape_fit below states it) -- in one call of tls_shape_fit behind the search, on the
+    device that searched the curve and on the rows it searched, from the period of the peak and T0 and duration_days of its
+    fit record, over shape_fit's default tables; shape_fit_window and shape_fit_min_count are its window and min_count.  The
+    `peaks` array gains the fields shape_fit_fields() (shape_status 1 and the others NaN where status != 0).  Everything else
+    of the result stays as it is, bit for bit.  shape_fit without peak_fits, or with a bad window or min_count, raises
+    ValueError before any device work.
+
     Returns (summary, periods[, chi2, row, depth, power][, per_transit][, models][, peaks]): summary is a numpy structured
     array with the fields of tls_power_summary plus "duration" (and the statistics on request)."""
     return _power_batch(t, flux_batch, dy_batch, power_kwargs, context=context, device=device, devices=devices,
@@ -397,7 +406,8 @@ def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_ar
                         peak_fits=bool(peak_fits),
                         phase_scan=_phase_scan_request(phase_scan, peak_fits, phase_scan_max_bins, phase_scan_min_count),
                         transit_times=_transit_times_request(transit_times, peak_fits, transit_times_search,
-                                                             transit_times_min_ses))
+                                                             transit_times_min_ses),
+                        shape_fit=_shape_fit_request(shape_fit, peak_fits, shape_fit_window, shape_fit_min_count))
 
 
 def _peaks_request(peaks, separation, ratios, min_power, models=False, peak_fits=False):
@@ -557,11 +567,12 @@ def find_peaks(power, periods, k, separation=0.02, ratios=HARMONICS, min_power=N
 
 def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=None, devices=None, with_arrays=False,
                  statistics=False, per_transit=False, models=False, spectra=False, detrend=None, peaks=None,
-                 peak_fits=False, phase_scan=None, transit_times=None):
+                 peak_fits=False, phase_scan=None, transit_times=None, shape_fit=None):
     """power_batch; spectra=True (power_results) also returns SR and power_raw [n_curves, n_periods] behind the arrays;
     peaks: None or a checked request (_peaks_request); peak_fits: with peaks, their T0 fits and statistics; phase_scan: None or a checked
     request (_phase_scan_request), with peak_fits, the fits' phase scans; transit_times: None or a checked request
-    (_transit_times_request), with peak_fits, the fits' transit times."""
+    (_transit_times_request), with peak_fits, the fits' transit times; shape_fit: None or a checked request
+    (_shape_fit_request), with peak_fits, the fits' shape fits."""
     models = bool(models)
     per_transit = bool(per_transit or models)
     statistics = bool(statistics or per_transit)
@@ -599,6 +610,9 @@ def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=Non
             # (the same context, the same rows: the candidates are the peaks the search fitted)
             part["tt_ephemeris"], part["tt_times"] = _peak_transit_times(
                 ctx, inp, y_rows[lo:hi], dy_rows[lo:hi], part["peaks"], part["peak_fits"], transit_times, tt_epochs)
+        if shape_fit is not None:
+            part["shape_fits"] = _peak_shape_fits(ctx, inp, y_rows[lo:hi], dy_rows[lo:hi], part["peaks"], part["peak_fits"],
+                                                  shape_fit)
         return part
 
     out = _run_batch(devices, device, context, len(y_rows), call)
@@ -654,6 +668,8 @@ def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=Non
         if transit_times is not None:
             found["peaks"] = _with_ephemeris(records, out["tt_ephemeris"])
             found["transit_times"] = _with_oc(out["tt_ephemeris"], out["tt_times"])
+        if shape_fit is not None:
+            found["peaks"] = _with_shapes(found["peaks"], out["shape_fits"], found["peaks"]["period"])
         result += (found,)
     if spectra:
         result += (out["SR"], out["power_raw"])
@@ -1056,6 +1072,159 @@ def transit_times(t, flux_batch, period, T0, duration, curve=None, dy_batch=None
     eph, times = ctx.transit_times(inp["t"], y_rows, dy_rows, period, T0, row, reach, widths, shapes, span_max, curve=curve,
                                    depth_min=depth_min, min_ses=min_ses, max_epochs=max_epochs)
     return eph, _with_oc(eph, times)
+
+
+# ---- trapezoid shape fit and transit geometry --------------------------------------------------------------------------------
+SHAPE_FIT_RATIOS = numpy.geomspace(0.5, 2.0, 17)
+SHAPE_FIT_INGRESS = numpy.linspace(0.0, 0.5, 16)
+SHAPE_FIT_SHIFTS = numpy.linspace(-0.25, 0.25, 9)
+
+
+def shape_fit_fields():
+    """The fields of a shape fit, in order -- what shape_fit returns and power_batch(..., shape_fit=True) adds to the `peaks`
+    array: the fields of tls_shape_record, each behind the prefix shape_ (shape_status first; the peaks array has depth,
+    duration and status of its own), then shape_delta_chi2 = ses^2 - ses_vee^2 and the geometry of the best trapezoid
+    (transit_geometry): shape_impact, shape_a_rs, shape_rho_star."""
+    from ._lib import SHAPE_FIELDS
+    return tuple("shape_" + k for k in SHAPE_FIELDS) + ("shape_delta_chi2", "shape_impact", "shape_a_rs", "shape_rho_star")
+
+
+def transit_geometry(period, depth, duration, ingress):
+    """(impact, a_rs, rho_star) of a trapezoid of `depth`, total duration `duration` = T14 (days) and ingress fraction
+    `ingress` = T12/T14 at `period` (days): the analytic solution of Seager & Mallen-Ornelas (2003, ApJ 585, 1038, their
+    equations 7, 8 and 9) for a circular orbit and a star without limb darkening.  Plain numpy on the host, broadcasting.
+
+        tT = duration;  tF = duration * (1 - 2 ingress);  k = sqrt(depth);  sT = sin^2(pi tT / P);  r = sin^2(pi tF / P) / sT
+        b^2 = ((1 - k)^2 - r (1 + k)^2) / (1 - r)
+        a_rs = sqrt(((1 + k)^2 - b^2 (1 - sT)) / sT)
+        rho_star = 3 pi a_rs^3 / (G P^2), in units of the solar mean density
+
+    impact is b, a_rs the semi-major axis in stellar radii and rho_star the stellar density the transit implies, to be compared
+    with the catalogue's: a transit on another, blended star gives a different one.  NaN where b^2 < 0 -- no such geometry:
+    the ingress is shorter than that of a central transit of this depth, sin(pi tF / P) / sin(pi tT / P) > (1 - k) / (1 + k),
+    as for a box; a V, tF = 0, is the grazing b = 1 - k -- and where an input is not finite."""
+    from . import constants as C
+    period, depth, duration, ingress = numpy.broadcast_arrays(*(numpy.asarray(v, dtype=numpy.float64)
+                                                                for v in (period, depth, duration, ingress)))
+    with numpy.errstate(all="ignore"):
+        k = numpy.sqrt(depth)
+        sT = numpy.sin(numpy.pi * duration / period) ** 2
+        sF = numpy.sin(numpy.pi * (duration * (1.0 - 2.0 * ingress)) / period) ** 2
+        r = sF / sT
+        b2 = ((1.0 - k) ** 2 - r * (1.0 + k) ** 2) / (1.0 - r)
+        a_rs = numpy.sqrt(((1.0 + k) ** 2 - b2 * (1.0 - sT)) / sT)
+        rho_sun = C.M_sun / (4.0 / 3.0 * numpy.pi * float(C.R_sun) ** 3)
+        rho = 3.0 * numpy.pi * a_rs ** 3 / (C.G * (period * C.SECONDS_PER_DAY) ** 2) / rho_sun
+        good = numpy.isfinite(period) & numpy.isfinite(depth) & numpy.isfinite(duration) & numpy.isfinite(ingress) \
+            & (b2 >= 0.0) & numpy.isfinite(a_rs)
+        impact = numpy.where(good, numpy.sqrt(numpy.where(good, b2, 0.0)), numpy.nan)
+    return impact, numpy.where(good, a_rs, numpy.nan), numpy.where(good, rho, numpy.nan)
+
+
+def _shape_fit_request(shape_fit, peak_fits, window, min_count):
+    """None, or the checked (window, min_count) of a shape_fit=True request over the default tables (ValueError for a bad
+    one, and for shape_fit without peak_fits)."""
+    if not shape_fit:
+        return None
+    if not peak_fits:
+        raise ValueError("shape_fit=True needs peak_fits=True: the fits start from T0 and duration of the fits")
+    from ._lib import shape_fit_tables
+    return shape_fit_tables(SHAPE_FIT_RATIOS, SHAPE_FIT_INGRESS, SHAPE_FIT_SHIFTS, window, min_count)[3:5]
+
+
+def _with_shapes(records, shapes, period):
+    """`records` (None, or the peaks with their fits) plus the device's shape records, shape_delta_chi2 and the geometry of
+    the best trapezoid at `period`."""
+    names = shape_fit_fields()
+    base = [] if records is None else records.dtype.descr
+    out = numpy.zeros(shapes.shape, dtype=base + [(k, "f8") for k in names])
+    if records is not None:
+        for k in records.dtype.names:
+            out[k] = records[k]
+    for k, source in zip(names, shapes.dtype.names):
+        out[k] = shapes[source]
+    out["shape_delta_chi2"] = shapes["ses"] * shapes["ses"] - shapes["ses_vee"] * shapes["ses_vee"]
+    out["shape_impact"], out["shape_a_rs"], out["shape_rho_star"] = transit_geometry(
+        period, shapes["depth"], shapes["duration"], shapes["ingress"])
+    return out
+
+
+def _peak_shape_fits(ctx, inp, y_rows, dy_rows, peaks, fits, request):
+    """The shape records [n_curves, K] of the peaks of a slice of the batch, on ctx.  Every peak is a candidate, so the device
+    writes the whole table in place: a peak whose fit status is not 0 goes in as (NaN, NaN, NaN) and comes back as the
+    statement has it, status 1 and NaN in every other field."""
+    window, min_count = request
+    n_curves, k = fits.shape
+    fitted = (fits["status"] == 0).reshape(-1)
+    period = numpy.where(fitted, peaks["period"].reshape(-1), numpy.nan)
+    T0 = numpy.where(fitted, fits["T0"].reshape(-1), numpy.nan)
+    duration = numpy.where(fitted, fits["duration_days"].reshape(-1), numpy.nan)
+    out = ctx.shape_fit(inp["t"], y_rows, dy_rows, period, T0, duration, SHAPE_FIT_RATIOS, SHAPE_FIT_INGRESS,
+                        SHAPE_FIT_SHIFTS, curve=numpy.repeat(numpy.arange(n_curves), k), window=window, min_count=min_count)
+    return out.reshape(n_curves, k)
+
+
+def shape_fit(t, flux_batch, period, T0, duration, curve=None, dy_batch=None, ratios=None, ingress=None, shifts=None,
+              window=2.0, min_count=3, transit_depth_min=0.0, detrend=None, context=None, device=None, **power_kwargs):
+    """The shape of the dip of candidates the caller holds, on the device (tls_shape_fit): candidate f is (period[f], T0[f],
+    duration[f] in days) on light curve curve[f] of flux_batch [n_curves, n] (or one row [n]) over the ascending time stamps
+    t; curve=None takes one candidate a curve, in order.  It needs no search.  A grazing eclipsing binary, or a blend of one,
+    is V-shaped; a planet has a flat bottom and a short ingress.  The search cannot tell: it matches one limb-darkened
+    template whose duration moves in steps of 10 %.  Here a trapezoid of unit depth -- total duration T = T14, ingress
+    fraction g = T12/T14, centre T0 + c0 -- is matched to the points within window * duration of every transit, with the
+    baseline fixed at 1 as everywhere in TLS, over the grid of T = duration * ratios, g = ingress and c0 = duration * shifts
+    (defaults: numpy.geomspace(0.5, 2.0, 17), numpy.linspace(0.0, 0.5, 16), numpy.linspace(-0.25, 0.25, 9): 2448 units);
+    y and dy are what a search of the same rows gets (power_kwargs: the keywords of power()).
+
+        w = 1 / dy^2;  xw = (1 - y) w
+        status 1 and NaN in every other field unless P, T0, d finite, P > 0, d > 0 and wd = window * d < 0.5 * P
+        members, i ascending:  x = (t[i] - T0) / P;  k = floor(x + 0.5);  tau = (x - k) * P;  member iff |tau| <= wd
+        unit (a, b, c), a outermost, c innermost:
+            T = d * ratios[a];  ho = 0.5 * T;  hb = ho * (1.0 - 2.0 * ingress[b]);  r = 1.0 / (ho - hb) where hb < ho
+            c0 = d * shifts[c];  over the members in index order:  u = |tau - c0|
+                s = 1.0 if u <= hb,  (ho - u) * r if u < ho,  else the member does not count
+                cnt += 1;  N += xw * s;  D += w * (s * s)
+            valid iff cnt >= min_count and D > 0 and depth = N / D > transit_depth_min;  ses = N / sqrt(D)
+        best = the valid unit of the largest ses, the first in unit order on ties; box and vee = the same pick among the units
+        of ingress[0] == 0.0 and of ingress[-1] == 0.5;  status 2 (n_points reported, the rest NaN) if no unit is valid
+
+    Each step is one IEEE double operation and every sum runs in index order, so the result is bit-equal to the Python
+    statement in tests/shape_fit_spec.py.  The trapezoid knows nothing of limb darkening or of the exposure time: both round
+    the contacts, so `shape_ingress` of a planet is LARGER than its geometric T12/T14, and the geometry below inherits that.
+    What separates the classes is the comparison: shape_ses_box^2 - shape_ses_vee^2 has the sign of the shape, and
+    shape_delta_chi2 = ses^2 - ses_vee^2 is the chi^2 by which the best trapezoid beats the best V.
+
+    The tables must be finite and ascending, ratios > 0, ingress from 0.0 to 0.5, at most 65536 units; window finite and at
+    least 0.5 * max(ratios) + max|shifts| (the model must lie inside the window); min_count >= 1; transit_depth_min finite
+    and >= 0; period, T0, duration and curve [n_fits] with curve in [0, n_curves): ValueError otherwise, before any device
+    work (the detrending included).  detrend= takes the steps and tuples of search_batch.
+
+    Returns a structured array [n_fits] with the fields shape_fit_fields(): shape_status (0 fitted; 1 no such candidate; 2 no
+    valid unit), shape_n_points, shape_n_in, shape_ses, shape_depth, shape_depth_err, shape_duration (T14, days),
+    shape_ingress (T12/T14), shape_shift (days), shape_i_duration, shape_i_ingress, shape_i_shift, shape_ses_box,
+    shape_duration_box, shape_ses_vee, shape_duration_vee, shape_delta_chi2, and shape_impact, shape_a_rs, shape_rho_star:
+    transit_geometry of the best trapezoid (NaN where it has none)."""
+    from ._lib import shape_fit_candidates, shape_fit_tables
+    ratio, ingress, shift, window, min_count, depth_min = shape_fit_tables(
+        SHAPE_FIT_RATIOS if ratios is None else ratios, SHAPE_FIT_INGRESS if ingress is None else ingress,
+        SHAPE_FIT_SHIFTS if shifts is None else shifts, window, min_count, transit_depth_min)
+    t = numpy.asarray(t, dtype=numpy.float64)
+    if numpy.ndim(flux_batch) == 1:
+        flux_batch = numpy.asarray(flux_batch)[None, :]
+        dy_batch = None if dy_batch is None else numpy.asarray(dy_batch)[None, :]
+    if numpy.ndim(flux_batch) != 2 or t.ndim != 1 or numpy.shape(flux_batch)[1] != len(t):
+        raise ValueError("flux_batch must be [n] or [n_curves, n] over the time stamps t [n]")
+    if not numpy.all(numpy.isfinite(t)) or not numpy.all(t[1:] >= t[:-1]):
+        raise ValueError("shape fit: t must be finite and non-decreasing")
+    period, T0, duration, curve = shape_fit_candidates(period, T0, duration, curve, numpy.shape(flux_batch)[0])
+    flux_batch = _detrended(t, flux_batch, detrend, context, device, None, dy_batch)
+    kwargs = dict(power_kwargs)
+    kwargs.setdefault("oversampling_factor", 1)      # (the period grid of the plan inputs is not used: the coarsest will do)
+    inp, y_rows, dy_rows = _batch_inputs(t, flux_batch, dy_batch, kwargs)
+    ctx = context if context is not None else _search.default_context(device)
+    out = ctx.shape_fit(inp["t"], y_rows, dy_rows, period, T0, duration, ratio, ingress, shift, curve=curve, window=window,
+                        min_count=min_count, depth_min=depth_min)
+    return _with_shapes(None, out, period)
 
 
 # ---- injection-recovery ---------------------------------------------------------------------------------------------------
