@@ -39,7 +39,7 @@ extern "C" {
  * tls_medfilt_detrend, tls_biweight_detrend), (7: tls_power_batch_peaks, tls_find_peaks),
  * (7: tls_power_batch_peak_fits, tls_debug_peak_fits), (7: tls_phase_scan, tls_power_batch_phase_scan,
  * tls_debug_peak_phase_scans), (7: tls_sysrem), (7: tls_single_transits), (7: tls_transit_times),
- * (7: tls_shape_fit). */
+ * (7: tls_shape_fit), (7: tls_nudft, tls_lomb_scargle, tls_sine_test). */
 #define TLS_AMD_ABI_VERSION 7
 
 #define TLS_OK 0
@@ -750,6 +750,82 @@ int tls_shape_fit(tls_ctx *ctx, const double *t, const double *y, const double *
                   const double *period, const double *T0, const double *duration, const int64_t *curve, int64_t n_fits,
                   const double *ratio, int64_t nT, const double *ingress, int64_t nQ, const double *shift, int64_t nS,
                   double window, int64_t min_count, double depth_min, tls_shape_record *out /* [n_fits] */);
+
+/* The variability periodogram: the generalised (floating-mean, weighted) Lomb-Scargle periodogram of Zechmeister & Kuerster
+ * (2009, A&A 496, 577) of every curve of a batch on shared time stamps, and the sine test of a candidate.  Is the STAR
+ * periodic, and is a candidate just that variability?  For a curve y [n] (weights from dy [n], or uniform) over the ascending
+ * t [n], with t_0 = t[0]:
+ *   prologue, every sum in index order:
+ *       v_i = 1.0 / (dy_i * dy_i);  W = sum v_i;  w_i = v_i / W                   (without dy: w_i = 1.0 / n)
+ *       ybar = sum (w_i * y_i);  d_i = y_i - ybar;  a_i = w_i * d_i;  YY = sum (a_i * d_i)
+ *   phase of (frequency f, point i):  e = t_i - t_0;  x = f * e;  r = x - floor(x);  phi = 6.283185307179586 * r
+ *   six sums:  YC, YS = sum a_i cos phi, sum a_i sin phi;  C, S = sum w_i cos phi, sum w_i sin phi;  C2, S2 = the same two
+ *   of w at the frequency 2.0 * f.  They are a dense product -- the rows times one [n x 2 F] matrix that is generated on
+ *   the fly -- in fp64 FMAs, i ascending: equal to the exact sums within
+ *       (n + 2 pi max|f (t - t_0)| + 8) * 2^-52 * sum_i |A[r][i]|                 (A = a or w)
+ *   epilogue, one IEEE double operation a step:
+ *       CC = 0.5 * (1.0 + C2) - C * C;  SS = 0.5 * (1.0 - C2) - S * S;  CS = 0.5 * S2 - C * S;  D = CC * SS - CS * CS
+ *       power = (SS * YC * YC + CC * YS * YS - 2.0 * CS * YC * YS) / (YY * D)
+ *       ca = (YC * SS - YS * CS) / D;  sa = (YS * CC - YC * CS) / D
+ *       amplitude = sqrt(ca * ca + sa * sa);  phase = atan2(sa, ca) / 6.283185307179586       (cycles, at t_0)
+ *       NaN in all three where D <= 0 or YY <= 0.
+ * The prologue equals tests/gls_spec.py bit for bit, and power and amplitude equal its epilogue of the device's own sums bit
+ * for bit; phase comes from the device's atan2, which agrees with the host's within a few ulp, not bit for bit. */
+#define TLS_GLS_MAX_POINTS (1 << 22)
+#define TLS_GLS_MAX_FREQUENCIES (1 << 24)
+#define TLS_SINE_MAX_HARMONICS 8
+
+/* The non-uniform DFT of a row matrix: out[r][k] = (sum_i rows[r][i] cos phi_ki, sum_i rows[r][i] sin phi_ki) with phi as
+ * above, rows [n_rows][n], any frequencies [n_freq] (not assumed uniform), out [n_rows][n_freq][2].  Needs no plan.
+ * n_rows == 0 is a no-op.  TLS_E_ARG, before any device work, for n outside [1, 2^22], n_freq outside [1, 2^24], a t that
+ * is not finite and non-decreasing and a frequency that is not finite and > 0. */
+int tls_nudft(tls_ctx *ctx, const double *rows, int64_t n_rows, int64_t n, const double *t, const double *frequencies,
+              int64_t n_freq, double *out);
+
+/* The periodogram of y [n_curves][n] (dy [n_curves][n], or NULL: uniform weights) at frequencies [n_freq]: out_mean (ybar)
+ * and out_variance (YY) [n_curves]; out_power, out_amplitude, out_phase [n_curves][n_freq], each may be NULL.  k > 0 selects
+ * the k highest peaks of every curve's power on the device, where it lies, by the selection of tls_find_peaks with
+ * periods = 1.0 / frequencies, min_separation and the ratios (0.5, 2.0): out_peaks [n_curves][k], out_n_peaks [n_curves]
+ * (chi2, depth NaN and row -1: they have no source); k == 0 selects none.  For tests and tools: out_rows [n_curves][n] (a),
+ * out_weights ([n_curves][n] with dy, [n] without) and out_sums [n_curves][n_freq][6] (YC, YS, C, S, C2, S2), each may be
+ * NULL.  Curves are processed in slabs, so device memory stays bounded.  TLS_E_ARG as tls_nudft, for n < 3, and for a peaks
+ * request tls_find_peaks refuses.  y and dy are taken as they are (finite, dy > 0). */
+int tls_lomb_scargle(tls_ctx *ctx, const double *t, const double *y, const double *dy, int64_t n, int64_t n_curves,
+                     const double *frequencies, int64_t n_freq, double *out_mean, double *out_variance, double *out_power,
+                     double *out_amplitude, double *out_phase, int64_t k, double min_separation, tls_peak *out_peaks,
+                     int64_t *out_n_peaks, double *out_rows, double *out_weights, double *out_sums);
+
+/* The sine test of a candidate, after the SWEET test of the Kepler Robovetter: the periodogram's statistic of ONE curve at the
+ * periods h * P of a few harmonics h, on the out-of-transit baseline.  Candidate f is (period[f], T0[f], duration[f] in days)
+ * on curve curve[f]; T0 and duration may both be NULL (no mask).
+ *   status 1 (NaN elsewhere) unless P is finite and > 0 and, with a mask, T0 is finite and d is finite and > 0
+ *   with a mask, hw = 0.5 * mask * d:  x = (t_i - T0) / P;  k = floor(x + 0.5);  tau = (x - k) * P;  out iff fabs(tau) <= hw
+ *   n_used = the points left;  status 2 (n_used reported, NaN elsewhere) if n_used < 4
+ *   an ordered sum of terms q_i: lane j = i mod 256 adds q_i (0.0 for a point that is out) over its i ascending, starting from
+ *   0.0; the sum is lane 0's plus lane 1's ... plus lane 255's, in that order
+ *   the prologue over the points left with ordered sums (without dy: w_i = 1.0 / n_used); for every harmonic Ph = h * P,
+ *   f = 1.0 / Ph, f2 = 2.0 * f, the six sums as ordered sums of the rounded products a_i cos phi, ..., and the epilogue
+ *   amplitude_err = sqrt(2.0 * YY * (1.0 - power) / (n_used - 3.0));  significance = amplitude / amplitude_err
+ * n_used, mean and variance equal tests/gls_spec.py bit for bit, the sums lie within the bound above, and the harmonic
+ * records equal the statement's epilogue of the device's own sums.  All fields are doubles. */
+typedef struct tls_sine_record {
+    double status;                 /* 0 done; 1 no such candidate / non-finite inputs; 2 fewer than 4 points left */
+    double n_used;
+    double mean, variance;         /* ybar and YY of the points left */
+} tls_sine_record;
+typedef struct tls_sine_harmonic {
+    double power, amplitude, phase;
+    double amplitude_err, significance;
+} tls_sine_harmonic;
+/* n_fits candidates on the curves of y (dy, or NULL) [n_curves][n] over t [n]; harmonics [n_harmonics] finite and > 0, at
+ * most TLS_SINE_MAX_HARMONICS; mask finite and >= 0.  out [n_fits], out_harmonics [n_fits][n_harmonics], out_sums
+ * [n_fits][n_harmonics][6] or NULL.  Needs no plan; n_fits == 0 is a no-op; candidates are processed in slabs.  TLS_E_ARG,
+ * before any device work, for a curve[f] outside [0, n_curves), n outside [1, 2^22], negative counts, a bad harmonic or
+ * mask, one of T0 and duration without the other, and a t that is not finite and non-decreasing. */
+int tls_sine_test(tls_ctx *ctx, const double *t, const double *y, const double *dy, int64_t n, int64_t n_curves,
+                  const double *period, const double *T0, const double *duration, const int64_t *curve, int64_t n_fits,
+                  const double *harmonics, int64_t n_harmonics, double mask, tls_sine_record *out,
+                  tls_sine_harmonic *out_harmonics, double *out_sums);
 
 /* ---- host-only planning (no GPU needed) ------------------------------------------ */
 /* Trial cells (duration x T0 positions) each period will enumerate: the data-independent

@@ -55,6 +55,16 @@ TIMES_MAX_POINTS = 1 << 30   # tls_times.hip.h kTimesMaxPoints
 SHAPE_MAX_UNITS = 65536
 SHAPE_MAX_POINTS = 1 << 22
 SHAPE_LDS_MEMBERS = 2048
+# include/tls_amd.h TLS_GLS_MAX_POINTS, TLS_GLS_MAX_FREQUENCIES, TLS_SINE_MAX_HARMONICS; tls_gls.hip.h kGlsRowTile,
+# kGlsSmallRows (batches of at most this many rows take the 32-row kernel), kGlsFreqTile, kGlsChunk, kSineThreads
+GLS_MAX_POINTS = 1 << 22
+GLS_MAX_FREQUENCIES = 1 << 24
+GLS_ROW_TILE = 128
+GLS_SMALL_ROWS = 32
+GLS_FREQ_TILE = 64
+GLS_CHUNK = 32
+SINE_MAX_HARMONICS = 8
+SINE_LANES = 256
 PEAKS_LDS_PERIODS = 1 << 20   # tls_peaks.hip.h kPeaksLdsPeriods: a longer grid keeps its alive mask in device memory, not in LDS
 
 # every symbol include/tls_amd.h declares (tests check the export list against the header)
@@ -67,7 +77,7 @@ SYMBOLS = (
     "tls_inject_transits", "tls_null_rows", "tls_debug_null_words", "tls_medfilt_detrend",
     "tls_biweight_detrend", "tls_sysrem", "tls_find_peaks", "tls_power_batch_peaks", "tls_power_batch_peak_fits", "tls_debug_peak_fits",
     "tls_phase_scan", "tls_power_batch_phase_scan", "tls_debug_peak_phase_scans", "tls_single_transits",
-    "tls_transit_times", "tls_shape_fit",
+    "tls_transit_times", "tls_shape_fit", "tls_nudft", "tls_lomb_scargle", "tls_sine_test",
     "tls_comm_unique_id", "tls_comm_init", "tls_comm_destroy", "tls_comm_info", "tls_comm_allgather_results", "tls_comm_allgather_device", "tls_comm_fetch_gathered",
     "tls_comm_stage_results", "tls_comm_allgather_staged", "tls_comm_fetch_staged",
     "tls_comm_barrier", "tls_comm_max",
@@ -483,6 +493,118 @@ def shape_fit_arguments(t, y, dy, period, T0, duration, ratios, ingress, shifts,
                 min_count=min_count, depth_min=depth_min)
 
 
+# tls_sine_record and tls_sine_harmonic (include/tls_amd.h): the sine test of a candidate, 4 doubles and 5 a harmonic
+SINE_FIELDS = ("status", "n_used", "mean", "variance")
+SINE_HARMONIC_FIELDS = ("power", "amplitude", "phase", "amplitude_err", "significance")
+GLS_SUMS = ("YC", "YS", "C", "S", "C2", "S2")
+
+
+class SineRecord(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_double) for k in SINE_FIELDS]
+
+
+class SineHarmonic(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_double) for k in SINE_HARMONIC_FIELDS]
+
+
+SINE_DTYPE = numpy.dtype([(k, "f8") for k in SINE_FIELDS])
+SINE_HARMONIC_DTYPE = numpy.dtype([(k, "f8") for k in SINE_HARMONIC_FIELDS])
+
+
+def gls_axes(t, frequencies, n_min=3):
+    """(t [n], frequencies [F]) float64 and contiguous as the periodogram takes them: t 1-D, n in [n_min, GLS_MAX_POINTS],
+    finite and non-decreasing; frequencies 1-D, F in [1, GLS_MAX_FREQUENCIES], finite and > 0.  ValueError otherwise."""
+    try:
+        t = numpy.ascontiguousarray(numpy.asarray(t, dtype=numpy.float64))
+        f = numpy.ascontiguousarray(numpy.atleast_1d(numpy.asarray(frequencies, dtype=numpy.float64)))
+    except (TypeError, ValueError):
+        raise ValueError("periodogram: t and frequencies must hold numbers")
+    if t.ndim != 1 or not n_min <= len(t) <= GLS_MAX_POINTS:
+        raise ValueError("periodogram: t must have shape [n] with n in [%d, %d], got %s" % (n_min, GLS_MAX_POINTS, t.shape))
+    if not numpy.all(numpy.isfinite(t)) or not numpy.all(t[1:] >= t[:-1]):
+        raise ValueError("periodogram: t must be finite and ascending")
+    if f.ndim != 1 or not 1 <= len(f) <= GLS_MAX_FREQUENCIES:
+        raise ValueError("periodogram: frequencies must have shape [F] with F in [1, %d], got %s" % (GLS_MAX_FREQUENCIES, f.shape))
+    if not numpy.all(numpy.isfinite(f) & (f > 0.0)):
+        raise ValueError("periodogram: every frequency must be finite and > 0")
+    return t, f
+
+
+def gls_rows(t, y, dy, what="periodogram"):
+    """(y, dy) [n_curves, n] float64 and contiguous over the time stamps t [n] (one row becomes [1, n]; dy None stays None):
+    y finite, dy finite and > 0 and shaped like y.  ValueError otherwise."""
+    try:
+        y = numpy.asarray(y, dtype=numpy.float64)
+        dy = None if dy is None else numpy.asarray(dy, dtype=numpy.float64)
+    except (TypeError, ValueError):
+        raise ValueError("%s: the light curves must hold numbers" % what)
+    if y.ndim == 1:
+        y = y[None, :]
+        if dy is not None and dy.ndim == 1:
+            dy = dy[None, :]
+    if y.ndim != 2 or y.shape[1] != len(t) or (dy is not None and dy.shape != y.shape):
+        raise ValueError("%s: flux and dy must be [n] or [n_curves, n] over the time stamps t [n]" % what)
+    if y.size and not numpy.all(numpy.isfinite(y)):
+        raise ValueError("%s: the flux has a NaN or an infinite value" % what)
+    if dy is not None and dy.size and not (dy.min() > 0.0 and dy.max() < numpy.inf):
+        raise ValueError("%s: dy has a NaN, infinite or non-positive value" % what)
+    return numpy.ascontiguousarray(y), None if dy is None else numpy.ascontiguousarray(dy)
+
+
+def lomb_scargle_arguments(t, y, dy, frequencies, peaks=None, separation=0.02):
+    """What tls_lomb_scargle takes, checked as it checks them: a dict with t, frequencies (gls_axes, n >= 3), y, dy
+    (gls_rows), k (0: no peaks; else an integer in [1, PEAKS_MAX_K]) and separation (finite, in [0, 1)).  ValueError
+    otherwise.  GPU-free."""
+    t, f = gls_axes(t, frequencies, 3)
+    y, dy = gls_rows(t, y, dy)
+    k = 0
+    if peaks is not None:
+        k, separation = peaks_arguments(peaks, separation, (0.5, 2.0), None)[:2]
+    return dict(t=t, frequencies=f, y=y, dy=dy, k=k, separation=float(separation))
+
+
+def sine_test_arguments(t, y, dy, period, T0, duration, curve, mask, harmonics):
+    """What tls_sine_test takes, checked as it checks them: a dict with t [n] (n in [1, GLS_MAX_POINTS], finite and
+    ascending), y, dy (gls_rows), period [n_fits] (any value: status 1), T0 and duration (both None, or [n_fits]), curve
+    (None: one candidate a curve, in order; integers in [0, n_curves)), mask (finite, >= 0) and harmonics (1 to
+    SINE_MAX_HARMONICS, finite and > 0).  ValueError otherwise.  GPU-free."""
+    try:
+        t = numpy.ascontiguousarray(numpy.asarray(t, dtype=numpy.float64))
+    except (TypeError, ValueError):
+        raise ValueError("sine test: t must hold numbers")
+    if t.ndim != 1 or not 1 <= len(t) <= GLS_MAX_POINTS:
+        raise ValueError("sine test: t must have shape [n] with n in [1, %d], got %s" % (GLS_MAX_POINTS, t.shape))
+    if not numpy.all(numpy.isfinite(t)) or not numpy.all(t[1:] >= t[:-1]):
+        raise ValueError("sine test: t must be finite and ascending")
+    y, dy = gls_rows(t, y, dy, "sine test")
+    if (T0 is None) != (duration is None):
+        raise ValueError("sine test: T0 and duration come together")
+    try:
+        period = numpy.ascontiguousarray(numpy.atleast_1d(numpy.asarray(period, dtype=numpy.float64)))
+        if T0 is not None:
+            T0, duration = (numpy.ascontiguousarray(numpy.atleast_1d(numpy.asarray(v, dtype=numpy.float64))) for v in (T0, duration))
+        harmonics = numpy.ascontiguousarray(numpy.atleast_1d(numpy.asarray(harmonics, dtype=numpy.float64)))
+    except (TypeError, ValueError):
+        raise ValueError("sine test: period, T0, duration and harmonics must be numbers")
+    if period.ndim != 1 or (T0 is not None and not period.shape == T0.shape == duration.shape):
+        raise ValueError("sine test: period, T0 and duration must be [n_fits]")
+    if harmonics.ndim != 1 or not 1 <= len(harmonics) <= SINE_MAX_HARMONICS \
+            or not numpy.all(numpy.isfinite(harmonics) & (harmonics > 0.0)):
+        raise ValueError("sine test: harmonics must be 1 to %d finite values > 0" % SINE_MAX_HARMONICS)
+    if isinstance(mask, (bool, numpy.bool_)) or not isinstance(mask, numbers.Real) or not (0.0 <= float(mask) < numpy.inf):
+        raise ValueError("sine test: mask must be finite and >= 0, got %r" % (mask,))
+    if curve is None:
+        if len(period) != len(y):
+            raise ValueError("sine test: curve=None takes one candidate a light curve: %d candidates, %d curves"
+                             % (len(period), len(y)))
+        curve = numpy.arange(len(y))
+    curve = numpy.atleast_1d(numpy.asarray(curve))
+    if curve.shape != period.shape or (curve.size and (curve.dtype.kind not in "iu" or curve.min() < 0 or curve.max() >= len(y))):
+        raise ValueError("sine test: curve must hold one index in [0, %d) a candidate" % len(y))
+    return dict(t=t, y=y, dy=dy, period=period, T0=T0, duration=duration, curve=numpy.ascontiguousarray(curve, dtype=numpy.int64),
+                mask=float(mask), harmonics=harmonics)
+
+
 def peaks_arguments(k, separation, ratios, min_power):
     """(k, separation, ratios, min_power) as the peak selection takes them, checked as tls_find_peaks checks them: k an
     integer in [1, PEAKS_MAX_K]; separation finite and in [0, 1); at most PEAKS_MAX_RATIOS ratios, each finite and > 0;
@@ -671,6 +793,15 @@ def load():
     lib.tls_shape_fit.argtypes = [vp, _c_double_p, _c_double_p, _c_double_p, i64, i64, _c_double_p, _c_double_p, _c_double_p,
                                   _c_int64_p, i64, _c_double_p, i64, _c_double_p, i64, _c_double_p, i64, dbl, i64, dbl,
                                   ctypes.c_void_p]
+    lib.tls_nudft.restype = ci
+    lib.tls_nudft.argtypes = [vp, _c_double_p, i64, i64, _c_double_p, _c_double_p, i64, _c_double_p]
+    lib.tls_lomb_scargle.restype = ci
+    lib.tls_lomb_scargle.argtypes = [vp, _c_double_p, _c_double_p, _c_double_p, i64, i64, _c_double_p, i64, _c_double_p,
+                                     _c_double_p, _c_double_p, _c_double_p, _c_double_p, i64, dbl, ctypes.c_void_p, _c_int64_p,
+                                     _c_double_p, _c_double_p, _c_double_p]
+    lib.tls_sine_test.restype = ci
+    lib.tls_sine_test.argtypes = [vp, _c_double_p, _c_double_p, _c_double_p, i64, i64, _c_double_p, _c_double_p, _c_double_p,
+                                  _c_int64_p, i64, _c_double_p, i64, dbl, ctypes.c_void_p, ctypes.c_void_p, _c_double_p]
     lib.tls_debug_peak_phase_scans.restype = ci
     lib.tls_debug_peak_phase_scans.argtypes = [vp, _c_double_p, i64, ctypes.c_void_p, _c_int64_p, i64, _c_double_p, _c_double_p,
                                                i64, dbl, _c_double_p, i64, i64, ctypes.c_void_p, i64, i64, ctypes.c_void_p]
@@ -1457,6 +1588,66 @@ class Context(object):
             _ip(a["curve"]), n_fits, _dp(a["ratio"]), len(a["ratio"]), _dp(a["ingress"]), len(a["ingress"]), _dp(a["shift"]),
             len(a["shift"]), a["window"], a["min_count"], a["depth_min"], out.ctypes.data_as(ctypes.c_void_p)))
         return out
+
+    def nudft(self, rows, t, frequencies):
+        """The non-uniform DFT of the rows [n_rows, n] (or one row) over t [n] at `frequencies` [F] (tls_nudft; the statement:
+        include/tls_amd.h, tests/gls_spec.py): [n_rows, F, 2] with (sum_i rows[r, i] cos phi_ki, sum_i rows[r, i] sin phi_ki),
+        phi_ki = 2 pi frac(f_k (t_i - t_0)).  ValueError for what gls_axes refuses and for rows that are not finite."""
+        t, f = gls_axes(t, frequencies, 1)
+        rows = gls_rows(t, rows, None, "nudft")[0]
+        out = numpy.zeros((len(rows), len(f), 2))
+        self._check(self._lib.tls_nudft(self._h, _dp(rows), len(rows), len(t), _dp(t), _dp(f), len(f), _dp(out)))
+        return out
+
+    def lomb_scargle(self, t, y, frequencies, dy=None, peaks=None, separation=0.02, with_arrays=True, debug=False):
+        """The generalised Lomb-Scargle periodogram (tls_lomb_scargle; the statement: include/tls_amd.h, tests/gls_spec.py) of
+        y [n_curves, n] (or one row; dy: per-point errors, None: uniform weights) over t [n] at `frequencies` [F]: a dict with
+        mean, variance [n_curves]; with_arrays: power, amplitude, phase [n_curves, F]; peaks=K: peaks (PEAK_DTYPE
+        [n_curves, K], period = 1 / frequency) and n_peaks, selected on the device; debug: rows (a [n_curves, n]), weights
+        ([n_curves, n] with dy, [n] without) and sums [n_curves, F, 6] (GLS_SUMS).  ValueError for what
+        lomb_scargle_arguments refuses."""
+        a = lomb_scargle_arguments(t, y, dy, frequencies, peaks, separation)
+        n_c, n = a["y"].shape
+        F, k = len(a["frequencies"]), a["k"]
+        out = dict(mean=numpy.zeros(n_c), variance=numpy.zeros(n_c))
+        if with_arrays:
+            out.update(power=numpy.zeros((n_c, F)), amplitude=numpy.zeros((n_c, F)), phase=numpy.zeros((n_c, F)))
+        if k:
+            out.update(peaks=numpy.zeros((n_c, k), dtype=PEAK_DTYPE), n_peaks=numpy.zeros(n_c, dtype=numpy.int64))
+            assert PEAK_DTYPE.itemsize == ctypes.sizeof(Peak)
+        if debug:
+            out.update(rows=numpy.zeros((n_c, n)), weights=numpy.zeros(n if a["dy"] is None else (n_c, n)),
+                       sums=numpy.zeros((n_c, F, 6)))
+
+        def ptr(name):
+            return _dp(out[name]) if name in out else None
+        self._check(self._lib.tls_lomb_scargle(
+            self._h, _dp(a["t"]), _dp(a["y"]), None if a["dy"] is None else _dp(a["dy"]), n, n_c, _dp(a["frequencies"]), F,
+            _dp(out["mean"]), _dp(out["variance"]), ptr("power"), ptr("amplitude"), ptr("phase"), k, a["separation"],
+            out["peaks"].ctypes.data_as(ctypes.c_void_p) if k else None, _ip(out["n_peaks"]) if k else None,
+            ptr("rows"), ptr("weights"), ptr("sums")))
+        return out
+
+    def sine_test(self, t, y, period, curve=None, dy=None, T0=None, duration=None, mask=1.5, harmonics=(0.5, 1.0, 2.0),
+                  debug=False):
+        """The sine tests (tls_sine_test; the statement: include/tls_amd.h, tests/gls_spec.py) of the candidates (period[f],
+        and T0[f], duration[f] in days where the transits are to be masked) on the curves curve[f] (None: one candidate a
+        curve, in order) of y [n_curves, n] (or one row; dy: per-point errors) over t [n]: (records SINE_DTYPE [n_fits],
+        harmonic records SINE_HARMONIC_DTYPE [n_fits, n_harmonics]) and, with debug, the sums [n_fits, n_harmonics, 6]
+        (GLS_SUMS).  ValueError for what sine_test_arguments refuses."""
+        a = sine_test_arguments(t, y, dy, period, T0, duration, curve, mask, harmonics)
+        n_c, n = a["y"].shape
+        n_fits, nH = len(a["period"]), len(a["harmonics"])
+        out = numpy.zeros(n_fits, dtype=SINE_DTYPE)
+        out_h = numpy.zeros((n_fits, nH), dtype=SINE_HARMONIC_DTYPE)
+        sums = numpy.zeros((n_fits, nH, 6)) if debug else None
+        assert SINE_DTYPE.itemsize == ctypes.sizeof(SineRecord) and SINE_HARMONIC_DTYPE.itemsize == ctypes.sizeof(SineHarmonic)
+        self._check(self._lib.tls_sine_test(
+            self._h, _dp(a["t"]), _dp(a["y"]), None if a["dy"] is None else _dp(a["dy"]), n, n_c, _dp(a["period"]),
+            None if a["T0"] is None else _dp(a["T0"]), None if a["duration"] is None else _dp(a["duration"]), _ip(a["curve"]),
+            n_fits, _dp(a["harmonics"]), nH, a["mask"], out.ctypes.data_as(ctypes.c_void_p),
+            out_h.ctypes.data_as(ctypes.c_void_p), None if sums is None else _dp(sums)))
+        return (out, out_h, sums) if debug else (out, out_h)
 
     def debug_null_words(self, n, n_rows, seed, first_trial=0, block=None):
         """The raw Philox words [n_rows, W] tls_null_rows draws for these trials (tls_debug_null_words): white-noise

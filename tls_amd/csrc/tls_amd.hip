@@ -225,6 +225,8 @@ struct tls_ctx {
     DevBuf<double> d_times;
     // tls_shape_fit: of one slab: pairs | y | dy | records | period | T0 | duration | slot; t | ratio | ingress | shift | scratch
     DevBuf<double> d_shape;
+    // tls_nudft / tls_lomb_scargle / tls_sine_test: the sums of one slab first (16-byte aligned pairs), then its rows and tables
+    DevBuf<double> d_gls;
     // two-role slab path (series in HBM, one light curve; SearchPlan::split)
     View<unsigned int> d_tile_prefix;        // [n_periods + 1] tiles in front of work item w (queue order)
     DevBuf<double> d_partials;               // [split_max_items][3] a tile's winner
@@ -1641,6 +1643,7 @@ void tls_ctx_destroy(tls_ctx* ctx) {
     ctx->d_single.release();
     ctx->d_times.release();
     ctx->d_shape.release();
+    ctx->d_gls.release();
     ctx->d_split.release(); ctx->d_park.release(); ctx->d_band.release();
     if (ctx->h_band) (void)hipHostFree(ctx->h_band);
     for (auto& ev : ctx->ev_band) if (ev) (void)hipEventDestroy(ev);
@@ -2798,6 +2801,7 @@ int tls_debug_device_bytes(const tls_ctx* ctx, int64_t* total, int64_t* t0_fit_s
     add(ctx->d_single);
     add(ctx->d_times);
     add(ctx->d_shape);
+    add(ctx->d_gls);
     add(ctx->d_partials); add(ctx->d_tiles_done);
     add(ctx->d_split); add(ctx->d_park); add(ctx->d_band);
     *total = (int64_t)sum;
@@ -3576,6 +3580,286 @@ int tls_shape_fit(tls_ctx* ctx, const double* t, const double* y, const double* 
         }
         ctx->last_kernel = "tls_shape_fit";
         TLS_HIP(ctx, hipMemcpyAsync(out + f0, d_out, fits * words * 8, hipMemcpyDeviceToHost, ctx->stream));
+        // (the next slab overwrites the device buffers and h_slot)
+        TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        f0 += (int64_t)fits;
+    }
+    return TLS_OK;
+}
+
+// ---- the variability periodogram (tls_gls.hip.h, DESIGN.md "Variability periodogram"): the non-uniform DFT of a row matrix,
+// the generalised Lomb-Scargle periodogram built on it, and the sine test of a candidate
+static_assert(sizeof(tls_sine_record) == tlsdev::kSineWords * 8 && sizeof(tls_sine_harmonic) == tlsdev::kSineHarmonicWords * 8,
+              "the sine test's records are the kernel's");
+static_assert(TLS_SINE_MAX_HARMONICS == tlsdev::kSineMaxHarmonics && TLS_GLS_MAX_POINTS == tlsdev::kGlsMaxPoints, "the header's limits");
+
+namespace {
+
+int check_gls_axes(tls_ctx* ctx, const double* t, int64_t n, int64_t n_min, const double* f, int64_t F) {
+    if (n < n_min || n > TLS_GLS_MAX_POINTS) return fail(ctx, TLS_E_ARG, "periodogram: n out of range");
+    if (F < 1 || F > TLS_GLS_MAX_FREQUENCIES) return fail(ctx, TLS_E_ARG, "periodogram: n_freq out of range [1, 2^24]");
+    if (!t || !f) return fail(ctx, TLS_E_ARG, "null argument");
+    for (int64_t i = 0; i < n; ++i)
+        if (!std::isfinite(t[i]) || (i > 0 && t[i] < t[i - 1]))
+            return fail(ctx, TLS_E_ARG, "periodogram: the time stamps must be finite and non-decreasing");
+    for (int64_t k = 0; k < F; ++k)
+        if (!(std::isfinite(f[k]) && f[k] > 0.0)) return fail(ctx, TLS_E_ARG, "periodogram: every frequency must be finite and > 0");
+    return TLS_OK;
+}
+
+// out[r][k] = the (cos, sin) sums of the rows d_A [R][lda] at the frequencies d_f [F], nothing waited for
+int enqueue_nudft(tls_ctx* ctx, const double* d_A, int64_t R, int64_t lda, int64_t n, const double* d_t, const double* d_f,
+                  int64_t F, double2* d_out) {
+    tlsdev::NudftArgs a;
+    a.A = d_A; a.t = d_t; a.f = d_f; a.out = d_out; a.lda = (long long)lda; a.R = (int)R; a.n = (int)n; a.F = (int)F;
+    const unsigned gx = (unsigned)((F + tlsdev::kGlsFreqTile - 1) / tlsdev::kGlsFreqTile);
+    if (R <= tlsdev::kGlsSmallRows)
+        hipLaunchKernelGGL(tlsdev::tls_nudft_kernel<1>, dim3(gx, 1), dim3(tlsdev::kGlsThreads), 0, ctx->stream, a);
+    else
+        hipLaunchKernelGGL(tlsdev::tls_nudft_kernel<4>, dim3(gx, (unsigned)((R + tlsdev::kGlsRowTile - 1) / tlsdev::kGlsRowTile)),
+                           dim3(tlsdev::kGlsThreads), 0, ctx->stream, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(ctx, TLS_E_HIP, std::string("nudft launch: ") + hipGetErrorString(e));
+    ctx->last_kernel = "tls_nudft";
+    return TLS_OK;
+}
+
+// rows of a slab: the sums and spectra of a slab stay below 1 GB, a launch's grid.y below 2^16 tiles of 32 rows
+int64_t gls_slab(int64_t rows, int64_t n, int64_t F) {
+    const int64_t per_row = 8 * (3 * n + 9 * F) + 1;
+    return std::max<int64_t>(1, std::min<int64_t>({rows, (int64_t)32768, (int64_t)(1ll << 30) / per_row}));
+}
+
+}  // namespace
+
+int tls_nudft(tls_ctx* ctx, const double* rows, int64_t n_rows, int64_t n, const double* t, const double* frequencies,
+              int64_t n_freq, double* out) {
+    if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
+    if (n_rows < 0) return fail(ctx, TLS_E_ARG, "nudft: n_rows < 0");
+    int rc = check_gls_axes(ctx, t, n, 1, frequencies, n_freq);
+    if (rc || n_rows == 0) return rc;
+    if (!rows || !out) return fail(ctx, TLS_E_ARG, "null argument");
+    TLS_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t nn = (size_t)n, nf = (size_t)n_freq;
+    const int64_t slab = gls_slab(n_rows, n, n_freq);
+    // sums [slab][F] pairs | rows [slab][n] | t | f
+    TLS_HIP(ctx, ctx->d_gls.reserve(2 * (size_t)slab * nf + (size_t)slab * nn + nn + nf));
+    double2* d_out = reinterpret_cast<double2*>(ctx->d_gls.ptr);
+    double* d_rows = ctx->d_gls.ptr + 2 * (size_t)slab * nf;
+    double* d_t = d_rows + (size_t)slab * nn;
+    double* d_f = d_t + nn;
+    TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_f, frequencies, nf * 8, hipMemcpyHostToDevice, ctx->stream));
+    for (int64_t k0 = 0; k0 < n_rows; k0 += slab) {
+        const int64_t R = std::min<int64_t>(slab, n_rows - k0);
+        TLS_HIP(ctx, hipMemcpyAsync(d_rows, rows + (size_t)k0 * nn, (size_t)R * nn * 8, hipMemcpyHostToDevice, ctx->stream));
+        if ((rc = enqueue_nudft(ctx, d_rows, R, n, n, d_t, d_f, n_freq, d_out))) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+        TLS_HIP(ctx, hipMemcpyAsync(out + 2 * (size_t)k0 * nf, d_out, (size_t)R * nf * 16, hipMemcpyDeviceToHost, ctx->stream));
+        TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));       // (the next slab overwrites the device buffers)
+    }
+    return TLS_OK;
+}
+
+int tls_lomb_scargle(tls_ctx* ctx, const double* t, const double* y, const double* dy, int64_t n, int64_t n_curves,
+                     const double* frequencies, int64_t n_freq, double* out_mean, double* out_variance, double* out_power,
+                     double* out_amplitude, double* out_phase, int64_t k, double min_separation, tls_peak* out_peaks,
+                     int64_t* out_n_peaks, double* out_rows, double* out_weights, double* out_sums) {
+    if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
+    if (n_curves < 0) return fail(ctx, TLS_E_ARG, "periodogram: n_curves < 0");
+    int rc = check_gls_axes(ctx, t, n, 3, frequencies, n_freq);
+    if (rc) return rc;
+    const double ratios[2] = {0.5, 2.0};
+    PeaksRequest pk;
+    if (k != 0) {
+        pk.k = k; pk.sep = min_separation; pk.ratios = ratios; pk.n_ratios = 2; pk.min_power = -INFINITY;
+        pk.out = out_peaks; pk.out_n = out_n_peaks;
+        if ((rc = check_peaks_request(ctx, pk, n_freq))) return rc;
+        if (!out_peaks || !out_n_peaks) return fail(ctx, TLS_E_ARG, "null argument");
+    }
+    if (n_curves == 0) return TLS_OK;
+    if (!y || !out_mean || !out_variance) return fail(ctx, TLS_E_ARG, "null argument");
+    TLS_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t nn = (size_t)n, nf = (size_t)n_freq;
+    const int64_t slab = gls_slab(n_curves, n, n_freq);
+    const size_t sl = (size_t)slab, wl = dy ? sl : 1, words = k ? pk.words() : 0;
+    // (YC, YS) | (C, S) | (C2, S2) pairs; power | amplitude | phase; y | dy | a | w rows; mean | variance; t | f | 2 f | 1 / f; peaks
+    TLS_HIP(ctx, ctx->d_gls.reserve(2 * sl * nf + 4 * wl * nf + 3 * sl * nf + (dy ? 3 : 2) * sl * nn + wl * nn + 2 * sl + nn + 3 * nf
+                                    + sl * words));
+    if (k && (rc = reserve_peak_mask(ctx, slab, n_freq))) return rc;
+    double2* d_yc = reinterpret_cast<double2*>(ctx->d_gls.ptr);
+    double2* d_cs = d_yc + sl * nf;
+    double2* d_cs2 = d_cs + wl * nf;
+    double* d_power = reinterpret_cast<double*>(d_cs2 + wl * nf);
+    double* d_amplitude = d_power + sl * nf;
+    double* d_phase = d_amplitude + sl * nf;
+    double* d_y = d_phase + sl * nf;
+    double* d_dy = dy ? d_y + sl * nn : nullptr;
+    double* d_a = d_y + (dy ? 2 : 1) * sl * nn;
+    double* d_w = d_a + sl * nn;
+    double* d_mean = d_w + wl * nn;
+    double* d_var = d_mean + sl;
+    double* d_t = d_var + sl;
+    double* d_f = d_t + nn;
+    double* d_f2 = d_f + nf;
+    double* d_periods = d_f2 + nf;
+    double* d_peaks = d_periods + nf;
+    std::vector<double> twice(nf), periods(nf), h_peaks(sl * words);
+    for (size_t i = 0; i < nf; ++i) { twice[i] = 2.0 * frequencies[i]; periods[i] = 1.0 / frequencies[i]; }
+    TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_f, frequencies, nf * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_f2, twice.data(), nf * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_periods, periods.data(), nf * 8, hipMemcpyHostToDevice, ctx->stream));
+    std::vector<double> h_sums;
+    for (int64_t k0 = 0; k0 < n_curves; k0 += slab) {
+        const int64_t R = std::min<int64_t>(slab, n_curves - k0), Rw = dy ? R : 1;
+        const size_t at = (size_t)k0 * nn, bytes = (size_t)R * nn * 8, spec = (size_t)R * nf * 8;
+        TLS_HIP(ctx, hipMemcpyAsync(d_y, y + at, bytes, hipMemcpyHostToDevice, ctx->stream));
+        if (dy) TLS_HIP(ctx, hipMemcpyAsync(d_dy, dy + at, bytes, hipMemcpyHostToDevice, ctx->stream));
+        tlsdev::GlsPrologueArgs p;
+        p.y = d_y; p.dy = d_dy; p.rows = d_a; p.weights = d_w; p.mean = d_mean; p.variance = d_var; p.n = (int)n;
+        hipLaunchKernelGGL(tlsdev::tls_gls_prologue_kernel, dim3((unsigned)R), dim3(tlsdev::kGlsThreads), 0, ctx->stream, p);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); return fail(ctx, TLS_E_HIP, std::string("periodogram launch: ") + hipGetErrorString(e)); }
+        if ((rc = enqueue_nudft(ctx, d_a, R, n, n, d_t, d_f, n_freq, d_yc))) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+        if (dy || k0 == 0) {                         // (the one shared weight row: once)
+            if ((rc = enqueue_nudft(ctx, d_w, Rw, n, n, d_t, d_f, n_freq, d_cs))
+                || (rc = enqueue_nudft(ctx, d_w, Rw, n, n, d_t, d_f2, n_freq, d_cs2))) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+        }
+        tlsdev::GlsEpilogueArgs g;
+        g.yc = d_yc; g.cs = d_cs; g.cs2 = d_cs2; g.variance = d_var; g.power = d_power; g.amplitude = d_amplitude; g.phase = d_phase;
+        g.count = (long long)R * (long long)n_freq; g.F = (int)n_freq; g.shared_weights = dy ? 0 : 1;
+        const unsigned blocks = (unsigned)std::min<long long>((g.count + tlsdev::kGlsThreads - 1) / tlsdev::kGlsThreads, 16384);
+        hipLaunchKernelGGL(tlsdev::tls_gls_epilogue_kernel, dim3(blocks), dim3(tlsdev::kGlsThreads), 0, ctx->stream, g);
+        e = hipGetLastError();
+        if (e != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); return fail(ctx, TLS_E_HIP, std::string("periodogram launch: ") + hipGetErrorString(e)); }
+        if (k && (rc = enqueue_find_peaks(ctx, pk, R, n_freq, d_power, nf, d_periods, nullptr, nullptr, nullptr, nullptr, d_peaks))) {
+            (void)hipStreamSynchronize(ctx->stream);
+            return rc;
+        }
+        ctx->last_kernel = "tls_lomb_scargle";
+        TLS_HIP(ctx, hipMemcpyAsync(out_mean + k0, d_mean, (size_t)R * 8, hipMemcpyDeviceToHost, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(out_variance + k0, d_var, (size_t)R * 8, hipMemcpyDeviceToHost, ctx->stream));
+        if (out_power) TLS_HIP(ctx, hipMemcpyAsync(out_power + (size_t)k0 * nf, d_power, spec, hipMemcpyDeviceToHost, ctx->stream));
+        if (out_amplitude) TLS_HIP(ctx, hipMemcpyAsync(out_amplitude + (size_t)k0 * nf, d_amplitude, spec, hipMemcpyDeviceToHost, ctx->stream));
+        if (out_phase) TLS_HIP(ctx, hipMemcpyAsync(out_phase + (size_t)k0 * nf, d_phase, spec, hipMemcpyDeviceToHost, ctx->stream));
+        if (out_rows) TLS_HIP(ctx, hipMemcpyAsync(out_rows + at, d_a, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        if (out_weights && (dy || k0 == 0))
+            TLS_HIP(ctx, hipMemcpyAsync(out_weights + (dy ? at : 0), d_w, (size_t)Rw * nn * 8, hipMemcpyDeviceToHost, ctx->stream));
+        if (k) TLS_HIP(ctx, hipMemcpyAsync(h_peaks.data(), d_peaks, (size_t)R * words * 8, hipMemcpyDeviceToHost, ctx->stream));
+        if (out_sums) {
+            h_sums.resize(2 * ((size_t)R + 2 * (size_t)Rw) * nf);
+            TLS_HIP(ctx, hipMemcpyAsync(h_sums.data(), d_yc, (size_t)R * nf * 16, hipMemcpyDeviceToHost, ctx->stream));
+            TLS_HIP(ctx, hipMemcpyAsync(h_sums.data() + 2 * (size_t)R * nf, d_cs, (size_t)Rw * nf * 16, hipMemcpyDeviceToHost, ctx->stream));
+            TLS_HIP(ctx, hipMemcpyAsync(h_sums.data() + 2 * ((size_t)R + (size_t)Rw) * nf, d_cs2, (size_t)Rw * nf * 16, hipMemcpyDeviceToHost, ctx->stream));
+        }
+        TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));       // (the next slab overwrites the device buffers)
+        if (k) for (int64_t c = 0; c < R; ++c) read_peaks(pk, h_peaks.data(), c, k0 + c);
+        if (out_sums) {
+            const double* yc = h_sums.data();
+            const double* cs = yc + 2 * (size_t)R * nf;
+            const double* cs2 = cs + 2 * (size_t)Rw * nf;
+            for (size_t r = 0; r < (size_t)R; ++r)
+                for (size_t q = 0; q < nf; ++q) {
+                    double* o = out_sums + 6 * (((size_t)k0 + r) * nf + q);
+                    const size_t w = 2 * ((dy ? r : 0) * nf + q);
+                    o[0] = yc[2 * (r * nf + q)]; o[1] = yc[2 * (r * nf + q) + 1];
+                    o[2] = cs[w]; o[3] = cs[w + 1]; o[4] = cs2[w]; o[5] = cs2[w + 1];
+                }
+        }
+    }
+    return TLS_OK;
+}
+
+int tls_sine_test(tls_ctx* ctx, const double* t, const double* y, const double* dy, int64_t n, int64_t n_curves,
+                  const double* period, const double* T0, const double* duration, const int64_t* curve, int64_t n_fits,
+                  const double* harmonics, int64_t n_harmonics, double mask, tls_sine_record* out, tls_sine_harmonic* out_harmonics,
+                  double* out_sums) {
+    if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
+    if (n_fits < 0 || n_curves < 0 || n < 0) return fail(ctx, TLS_E_ARG, "sine test: negative count");
+    if (n_harmonics < 1 || n_harmonics > TLS_SINE_MAX_HARMONICS) return fail(ctx, TLS_E_ARG, "sine test: n_harmonics out of range [1, 8]");
+    if (!harmonics) return fail(ctx, TLS_E_ARG, "null argument");
+    for (int64_t h = 0; h < n_harmonics; ++h)
+        if (!(std::isfinite(harmonics[h]) && harmonics[h] > 0.0)) return fail(ctx, TLS_E_ARG, "sine test: every harmonic must be finite and > 0");
+    if (!(std::isfinite(mask) && mask >= 0.0)) return fail(ctx, TLS_E_ARG, "sine test: mask must be finite and >= 0");
+    if ((T0 == nullptr) != (duration == nullptr)) return fail(ctx, TLS_E_ARG, "sine test: T0 and duration come together");
+    if (n_fits == 0) return TLS_OK;
+    if (!t || !y || !curve || !period || !out || !out_harmonics) return fail(ctx, TLS_E_ARG, "null argument");
+    if (n < 1 || n > TLS_GLS_MAX_POINTS) return fail(ctx, TLS_E_ARG, "sine test: n out of range [1, 2^22]");
+    if (n_fits > INT32_MAX || (uint64_t)n_curves > (uint64_t)(INT64_MAX / 16) / (uint64_t)n)
+        return fail(ctx, TLS_E_ARG, "sine test: batch too large");
+    for (int64_t i = 0; i < n; ++i)
+        if (!std::isfinite(t[i]) || (i > 0 && t[i] < t[i - 1]))
+            return fail(ctx, TLS_E_ARG, "sine test: the time stamps must be finite and non-decreasing");
+    for (int64_t f = 0; f < n_fits; ++f)
+        if (curve[f] < 0 || curve[f] >= n_curves) return fail(ctx, TLS_E_ARG, "sine test: curve out of range [0, n_curves)");
+    TLS_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t nn = (size_t)n, nH = (size_t)n_harmonics;
+    // a slab: at most 1024 candidates on at most 1024 curves, 256 MB of curves
+    const size_t cs = std::max<size_t>(1, std::min<size_t>({(size_t)n_curves, 1024, (256u << 20) / (16 * nn)}));
+    const size_t sl = std::min<size_t>((size_t)n_fits, 1024);
+    const size_t per_fit = tlsdev::kSineWords + nH * (tlsdev::kSineHarmonicWords + 6);
+    // of one slab: y | dy | records | harmonic records | sums | period | T0 | duration | slot;  t | harmonics
+    TLS_HIP(ctx, ctx->d_gls.reserve(2 * cs * nn + sl * (per_fit + 3) + (sl + 1) / 2 + nn + nH));
+    double* d_y = ctx->d_gls.ptr;
+    double* d_dy = d_y + cs * nn;
+    double* d_out = d_dy + cs * nn;
+    double* d_out_h = d_out + sl * tlsdev::kSineWords;
+    double* d_sums = d_out_h + sl * nH * tlsdev::kSineHarmonicWords;
+    double* d_period = d_sums + sl * nH * 6;
+    double* d_T0 = d_period + sl;
+    double* d_duration = d_T0 + sl;
+    int* d_slot = reinterpret_cast<int*>(d_duration + sl);
+    double* d_t = d_duration + sl + (sl + 1) / 2;
+    double* d_harmonics = d_t + nn;
+    tlsdev::SineArgs a;
+    a.t = d_t; a.y = d_y; a.dy = dy ? d_dy : nullptr; a.slot = d_slot; a.period = d_period;
+    a.T0 = T0 ? d_T0 : nullptr; a.duration = T0 ? d_duration : nullptr; a.harmonics = d_harmonics;
+    a.out = d_out; a.out_h = d_out_h; a.out_sums = out_sums ? d_sums : nullptr; a.mask = mask; a.n = (int)n; a.nH = (int)n_harmonics;
+    TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_harmonics, harmonics, nH * 8, hipMemcpyHostToDevice, ctx->stream));
+    std::vector<int> h_slot(sl);
+    std::unordered_map<int64_t, int> slot_of;
+    struct Run { int64_t curve; size_t slot, count; };      // consecutive curves in consecutive slots: one copy
+    std::vector<Run> runs;
+    for (int64_t f0 = 0; f0 < n_fits;) {
+        slot_of.clear();
+        runs.clear();
+        size_t fits = 0;
+        while (f0 + (int64_t)fits < n_fits && fits < sl) {
+            const int64_t f = f0 + (int64_t)fits;
+            auto it = slot_of.find(curve[f]);
+            if (it == slot_of.end()) {
+                if (slot_of.size() == cs) break;     // (the next slab takes it; a slab's first candidate always finds a slot)
+                const size_t slot = slot_of.size();
+                it = slot_of.emplace(curve[f], (int)slot).first;
+                if (!runs.empty() && runs.back().curve + (int64_t)runs.back().count == curve[f]) ++runs.back().count;
+                else runs.push_back(Run{curve[f], slot, 1});
+            }
+            h_slot[fits] = it->second;
+            ++fits;
+        }
+        for (const Run& run : runs) {
+            const size_t from = (size_t)run.curve * nn, to = run.slot * nn, bytes = run.count * nn * 8;
+            TLS_HIP(ctx, hipMemcpyAsync(d_y + to, y + from, bytes, hipMemcpyHostToDevice, ctx->stream));
+            if (dy) TLS_HIP(ctx, hipMemcpyAsync(d_dy + to, dy + from, bytes, hipMemcpyHostToDevice, ctx->stream));
+        }
+        TLS_HIP(ctx, hipMemcpyAsync(d_slot, h_slot.data(), fits * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(d_period, period + f0, fits * 8, hipMemcpyHostToDevice, ctx->stream));
+        if (T0) {
+            TLS_HIP(ctx, hipMemcpyAsync(d_T0, T0 + f0, fits * 8, hipMemcpyHostToDevice, ctx->stream));
+            TLS_HIP(ctx, hipMemcpyAsync(d_duration, duration + f0, fits * 8, hipMemcpyHostToDevice, ctx->stream));
+        }
+        a.fits = (int)fits;
+        hipLaunchKernelGGL(tlsdev::tls_sine_test_kernel, dim3((unsigned)fits), dim3(tlsdev::kSineThreads), 0, ctx->stream, a);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(ctx->stream);
+            return fail(ctx, TLS_E_HIP, std::string("sine test launch: ") + hipGetErrorString(e));
+        }
+        ctx->last_kernel = "tls_sine_test";
+        TLS_HIP(ctx, hipMemcpyAsync(out + f0, d_out, fits * sizeof(tls_sine_record), hipMemcpyDeviceToHost, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(out_harmonics + (size_t)f0 * nH, d_out_h, fits * nH * sizeof(tls_sine_harmonic), hipMemcpyDeviceToHost, ctx->stream));
+        if (out_sums) TLS_HIP(ctx, hipMemcpyAsync(out_sums + (size_t)f0 * nH * 6, d_sums, fits * nH * 48, hipMemcpyDeviceToHost, ctx->stream));
         // (the next slab overwrites the device buffers and h_slot)
         TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
         f0 += (int64_t)fits;

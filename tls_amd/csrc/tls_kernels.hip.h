@@ -4309,6 +4309,8 @@ __global__ void __launch_bounds__(512) tls_transit_models(const ModelsArgs a) {
 #include "tls_times.hip.h"
 // survey-mode trapezoid shape fit (tls_shape_fit)
 #include "tls_shape.hip.h"
+// survey-mode variability periodogram and sine test (tls_nudft, tls_lomb_scargle, tls_sine_test)
+#include "tls_gls.hip.h"
 #include "tls_peak_fits.hip.h"
 #include "tls_phase_scan.hip.h"
 

@@ -9,6 +9,7 @@ collective (every light curve's results come back over its own GPU's copy engine
 """
 import collections
 import contextlib
+import numbers
 import operator
 
 import numpy
@@ -319,7 +320,8 @@ def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_ar
                 per_transit=False, models=False, detrend=None, peaks=None, peak_separation=0.02, peak_ratios=HARMONICS,
                 peak_min_power=None, peak_fits=False, phase_scan=False, phase_scan_max_bins=4096, phase_scan_min_count=3,
                 transit_times=False, transit_times_search=1.0, transit_times_min_ses=3.0, shape_fit=False,
-                shape_fit_window=2.0, shape_fit_min_count=3, **power_kwargs):
+                shape_fit_window=2.0, shape_fit_min_count=3, sine_test=False, sine_test_mask=1.5,
+                sine_test_harmonics=(0.5, 1.0, 2.0), **power_kwargs):
     """Survey-mode power(): for every light curve of `flux_batch` what `transitleastsquares(t, flux).power(**kwargs)`
     reports as SDE, SDE_raw, chi2_min, period, T0, depth and duration (fractional, lc_cache_overview["duration"] of
     the template row at the chi^2 minimum, main.py:199-200) -- search, SDE spectra and final T0 fit all on the
@@ -397,6 +399,15 @@ def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_ar
     of the result stays as it is, bit for bit.  shape_fit without peak_fits, or with a bad window or min_count, raises
     ValueError before any device work.
 
+    sine_test=True (with peak_fits=True) asks of every fitted peak whether it is the star's own variability -- a sinusoid at
+    the peak's period, half of it or twice it, as a contact binary, an ellipsoidal variable or a spotted star gives (sine_test
+    below states it) -- in one call of tls_sine_test behind the search, on the device that searched the curve and on the rows
+    it searched, from the period of the peak and T0 and duration_days of its fit record, whose transits are masked out
+    (sine_test_mask durations wide) before the sinusoid is measured; sine_test_harmonics are the period ratios.  The `peaks`
+    array gains the fields sine_test_fields() (sine_status 1 and the others NaN where status != 0).  Everything else of the
+    result stays as it is, bit for bit.  sine_test without peak_fits, or with a bad mask or harmonics, raises ValueError
+    before any device work.
+
     Returns (summary, periods[, chi2, row, depth, power][, per_transit][, models][, peaks]): summary is a numpy structured
     array with the fields of tls_power_summary plus "duration" (and the statistics on request)."""
     return _power_batch(t, flux_batch, dy_batch, power_kwargs, context=context, device=device, devices=devices,
@@ -407,7 +418,8 @@ def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_ar
                         phase_scan=_phase_scan_request(phase_scan, peak_fits, phase_scan_max_bins, phase_scan_min_count),
                         transit_times=_transit_times_request(transit_times, peak_fits, transit_times_search,
                                                              transit_times_min_ses),
-                        shape_fit=_shape_fit_request(shape_fit, peak_fits, shape_fit_window, shape_fit_min_count))
+                        shape_fit=_shape_fit_request(shape_fit, peak_fits, shape_fit_window, shape_fit_min_count),
+                        sine_test=_sine_test_request(sine_test, peak_fits, sine_test_mask, sine_test_harmonics))
 
 
 def _peaks_request(peaks, separation, ratios, min_power, models=False, peak_fits=False):
@@ -567,12 +579,13 @@ def find_peaks(power, periods, k, separation=0.02, ratios=HARMONICS, min_power=N
 
 def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=None, devices=None, with_arrays=False,
                  statistics=False, per_transit=False, models=False, spectra=False, detrend=None, peaks=None,
-                 peak_fits=False, phase_scan=None, transit_times=None, shape_fit=None):
+                 peak_fits=False, phase_scan=None, transit_times=None, shape_fit=None, sine_test=None):
     """power_batch; spectra=True (power_results) also returns SR and power_raw [n_curves, n_periods] behind the arrays;
     peaks: None or a checked request (_peaks_request); peak_fits: with peaks, their T0 fits and statistics; phase_scan: None or a checked
     request (_phase_scan_request), with peak_fits, the fits' phase scans; transit_times: None or a checked request
     (_transit_times_request), with peak_fits, the fits' transit times; shape_fit: None or a checked request
-    (_shape_fit_request), with peak_fits, the fits' shape fits."""
+    (_shape_fit_request), with peak_fits, the fits' shape fits; sine_test: None or a checked request (_sine_test_request),
+    with peak_fits, the fits' sine tests."""
     models = bool(models)
     per_transit = bool(per_transit or models)
     statistics = bool(statistics or per_transit)
@@ -613,6 +626,10 @@ def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=Non
         if shape_fit is not None:
             part["shape_fits"] = _peak_shape_fits(ctx, inp, y_rows[lo:hi], dy_rows[lo:hi], part["peaks"], part["peak_fits"],
                                                   shape_fit)
+        if sine_test is not None:
+            # (the weights are normalised, so the search's dy / mean(dy) serve; without dy_batch they are uniform)
+            part["sine_tests"], part["sine_harmonics"] = _peak_sine_tests(
+                ctx, inp, y_rows[lo:hi], None if dy_batch is None else dy_rows[lo:hi], part["peaks"], part["peak_fits"], sine_test)
         return part
 
     out = _run_batch(devices, device, context, len(y_rows), call)
@@ -670,6 +687,8 @@ def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=Non
             found["transit_times"] = _with_oc(out["tt_ephemeris"], out["tt_times"])
         if shape_fit is not None:
             found["peaks"] = _with_shapes(found["peaks"], out["shape_fits"], found["peaks"]["period"])
+        if sine_test is not None:
+            found["peaks"] = _with_sines(found["peaks"], out["sine_tests"], out["sine_harmonics"])
         result += (found,)
     if spectra:
         result += (out["SR"], out["power_raw"])
@@ -1225,6 +1244,166 @@ def shape_fit(t, flux_batch, period, T0, duration, curve=None, dy_batch=None, ra
     out = ctx.shape_fit(inp["t"], y_rows, dy_rows, period, T0, duration, ratio, ingress, shift, curve=curve, window=window,
                         min_count=min_count, depth_min=depth_min)
     return _with_shapes(None, out, period)
+
+
+# ---- variability periodogram and sine test -----------------------------------------------------------------------------------
+def variability_frequencies(t, oversampling=5, f_max=None):
+    """The default frequency grid of lomb_scargle: k / (oversampling * T) for k = 1, 2, ... up to f_max (cycles a day), with
+    T = t[-1] - t[0]; f_max None: 0.5 / median(diff(t)), the Nyquist frequency of the median cadence.  ValueError for a t
+    that is not 1-D, finite and ascending with T > 0, an oversampling that is not finite and > 0, and an f_max that is not
+    finite and at least 1 / (oversampling * T)."""
+    try:
+        t = numpy.asarray(t, dtype=numpy.float64)
+    except (TypeError, ValueError):
+        raise ValueError("periodogram: t must hold numbers")
+    if t.ndim != 1 or len(t) < 2 or not numpy.all(numpy.isfinite(t)) or not numpy.all(t[1:] >= t[:-1]) or not t[-1] > t[0]:
+        raise ValueError("periodogram: t must be [n], finite and ascending over a span > 0")
+    if isinstance(oversampling, bool) or not isinstance(oversampling, numbers.Real) or not (0.0 < float(oversampling) < numpy.inf):
+        raise ValueError("periodogram: oversampling must be finite and > 0, got %r" % (oversampling,))
+    step = 1.0 / (float(oversampling) * float(t[-1] - t[0]))
+    if f_max is None:
+        f_max = 0.5 / float(numpy.median(numpy.diff(t)))
+    if isinstance(f_max, bool) or not isinstance(f_max, numbers.Real) or not (step <= float(f_max) < numpy.inf):
+        raise ValueError("periodogram: f_max must be finite and at least 1 / (oversampling * T) = %r, got %r" % (step, f_max))
+    count = int(numpy.floor(float(f_max) / step))
+    return numpy.arange(1, count + 1) * step
+
+
+def lomb_scargle(t, flux_batch, frequencies=None, dy_batch=None, peaks=None, with_arrays=True, detrend=None, context=None,
+                 device=None, devices=None, peak_separation=0.02):
+    """The generalised (floating-mean, weighted) Lomb-Scargle periodogram of Zechmeister & Kuerster (2009) of every light
+    curve of flux_batch [n_curves, n] (or one row [n]) on the shared ascending time stamps t, on the device
+    (tls_lomb_scargle): is the STAR periodic -- spots, pulsations, a contact binary -- and at which period?  frequencies
+    (cycles a day, any order, None: variability_frequencies(t)); dy_batch: per-point errors (None: uniform weights).
+
+        prologue, every sum in index order:
+            w_i = 1 / dy_i^2, normalised to sum w = 1 (1 / n without dy_batch);  ybar = sum w_i y_i
+            a_i = w_i (y_i - ybar);  YY = sum a_i (y_i - ybar)
+        phi_ki = 2 pi frac(f_k (t_i - t_0)), the phase reduced in cycles before it is scaled
+        YC, YS = sum a_i cos phi, sum a_i sin phi;  C, S the same of w;  C2, S2 the same of w at 2 f
+        CC = 0.5 (1 + C2) - C C;  SS = 0.5 (1 - C2) - S S;  CS = 0.5 S2 - C S;  D = CC SS - CS CS
+        power = (SS YC YC + CC YS YS - 2 CS YC YS) / (YY D)         (the fraction of the variance a sinusoid removes)
+        ca = (YC SS - YS CS) / D;  sa = (YS CC - YC CS) / D;  amplitude = sqrt(ca^2 + sa^2);  phase = atan2(sa, ca) / (2 pi)
+        NaN where D <= 0 or YY <= 0 (a constant curve; a frequency at which every point has one phase)
+
+    The sums are one dense product -- the rows times a [n x 2 F] matrix of cos / sin that is generated on the fly and never
+    stored -- in fp64 FMAs; they lie within (n + 2 pi max|f (t - t_0)| + 8) 2^-52 sum|a| of the exact sums.  The prologue
+    equals the Python statement in tests/gls_spec.py bit for bit, and power and amplitude equal its epilogue applied to the
+    device's own sums bit for bit.  phase is the DEVICE's atan2: it agrees with numpy's within a few ulp, not bit for bit.
+
+    peaks=K also selects the K highest peaks of every curve on the device, from the power where it lies, by the selection of
+    find_peaks with periods = 1 / frequencies, separation peak_separation and the ratios (0.5, 2.0); with_arrays=False then
+    brings back the peaks alone.  detrend= takes the steps and tuples of search_batch, devices=[...] deals the curves out over
+    several GPUs.  ValueError, before any device work (the detrending included), for non-finite input, a t that is not
+    ascending, frequencies that are not finite and > 0, n < 3 and shapes that disagree.
+
+    Returns a dict: frequencies [F], mean (ybar) and variance (YY) [n_curves]; power, amplitude, phase [n_curves, F] with
+    with_arrays; peaks (period, power, index; [n_curves, K]) and n_peaks with peaks=K.  One row gives [F] and [K]."""
+    from ._lib import lomb_scargle_arguments
+    if frequencies is None:
+        frequencies = variability_frequencies(t)
+    one = numpy.ndim(flux_batch) == 1
+    a = lomb_scargle_arguments(t, flux_batch, dy_batch, frequencies, peaks, peak_separation)
+    rows = _detrended(a["t"], a["y"], detrend, context, device, devices, a["dy"])
+
+    def call(ctx, lo, hi):
+        return ctx.lomb_scargle(a["t"], rows[lo:hi], a["frequencies"], None if a["dy"] is None else a["dy"][lo:hi], peaks=peaks,
+                                separation=a["separation"], with_arrays=with_arrays)
+
+    out = dict(_run_batch(devices, device, context, len(a["y"]), call))
+    if one:
+        out = {k: v[0] for k, v in out.items()}
+    out["frequencies"] = a["frequencies"]
+    return out
+
+
+def sine_test_fields(harmonics=(0.5, 1.0, 2.0)):
+    """The fields of a sine test, in order -- what sine_test returns and power_batch(..., sine_test=True) adds to the `peaks`
+    array: sine_status (0 done; 1 no such candidate; 2 fewer than 4 points left), sine_n_used, sine_mean, sine_variance, then
+    sine_power, sine_amplitude, sine_phase, sine_amplitude_err and sine_significance, each [n_harmonics]."""
+    from ._lib import SINE_FIELDS, SINE_HARMONIC_FIELDS
+    return tuple("sine_" + k for k in SINE_FIELDS + SINE_HARMONIC_FIELDS)
+
+
+def _sine_test_request(sine_test, peak_fits, mask, harmonics):
+    """None, or the checked (mask, harmonics) of a sine_test=True request (ValueError for a bad one, and for sine_test
+    without peak_fits)."""
+    if not sine_test:
+        return None
+    if not peak_fits:
+        raise ValueError("sine_test=True needs peak_fits=True: the transits of the fits are masked out")
+    from ._lib import sine_test_arguments
+    a = sine_test_arguments([0.0], [1.0], None, [1.0], None, None, None, mask, harmonics)
+    return a["mask"], a["harmonics"]
+
+
+def _with_sines(records, sines, harmonics):
+    """`records` (None, or the peaks with their fits) plus the device's sine records and harmonic records."""
+    from ._lib import SINE_FIELDS, SINE_HARMONIC_FIELDS
+    nH = harmonics.shape[-1]
+    base = [] if records is None else records.dtype.descr
+    out = numpy.zeros(sines.shape, dtype=base + [("sine_" + k, "f8") for k in SINE_FIELDS]
+                      + [("sine_" + k, "f8", (nH,)) for k in SINE_HARMONIC_FIELDS])
+    if records is not None:
+        for k in records.dtype.names:
+            out[k] = records[k]
+    for k in SINE_FIELDS:
+        out["sine_" + k] = sines[k]
+    for k in SINE_HARMONIC_FIELDS:
+        out["sine_" + k] = harmonics[k]
+    return out
+
+
+def _peak_sine_tests(ctx, inp, y_rows, dy_rows, peaks, fits, request):
+    """The sine records [n_curves, K] and harmonic records [n_curves, K, n_harmonics] of the peaks of a slice of the batch,
+    on ctx.  Every peak is a candidate: a peak whose fit status is not 0 goes in as (NaN, NaN, NaN) and comes back as the
+    statement has it, status 1 and NaN in every other field."""
+    mask, harmonics = request
+    n_curves, k = fits.shape
+    fitted = (fits["status"] == 0).reshape(-1)
+    period = numpy.where(fitted, peaks["period"].reshape(-1), numpy.nan)
+    T0 = numpy.where(fitted, fits["T0"].reshape(-1), numpy.nan)
+    duration = numpy.where(fitted, fits["duration_days"].reshape(-1), numpy.nan)
+    out, out_h = ctx.sine_test(inp["t"], y_rows, period, curve=numpy.repeat(numpy.arange(n_curves), k), dy=dy_rows, T0=T0,
+                               duration=duration, mask=mask, harmonics=harmonics)
+    return out.reshape(n_curves, k), out_h.reshape(n_curves, k, len(harmonics))
+
+
+def sine_test(t, flux_batch, period, curve=None, dy_batch=None, T0=None, duration=None, mask=1.5, harmonics=(0.5, 1.0, 2.0),
+              detrend=None, context=None, device=None):
+    """Is a candidate the star's own variability?  The per-candidate counterpart of lomb_scargle, after the SWEET test of the
+    Kepler Robovetter, on the device (tls_sine_test): candidate f is period[f] (days) on light curve curve[f] of flux_batch
+    [n_curves, n] (or one row [n]) over the ascending time stamps t; curve=None takes one candidate a curve, in order.  A
+    contact binary or an ellipsoidal variable is a sinusoid at P or P / 2, a spotted star at P or 2 P; the odd-even test, the
+    phase scan and the shape fit all see such a curve as a wide, shallow dip.  With T0 and duration [n_fits] the points within
+    0.5 * mask * duration of a transit leave the fit (folded as shape_fit folds them), so the sinusoid is measured on the
+    out-of-transit baseline.
+
+        status 1 (NaN elsewhere) unless P finite and > 0 and, with T0 / duration, T0 finite and duration finite and > 0
+        x = (t_i - T0) / P;  k = floor(x + 0.5);  tau = (x - k) P;  point i is out iff |tau| <= 0.5 mask duration
+        n_used = the points left;  status 2 if n_used < 4
+        the prologue of lomb_scargle over the points left (1 / n_used without dy_batch), every sum an ordered sum: lane
+        j = i mod 256 adds its terms over i ascending (0.0 for a point that is out), the lanes are added in lane order
+        for every harmonic h: the six sums at f = 1 / (h P) and 2 f, ordered sums of rounded products, and the epilogue
+        amplitude_err = sqrt(2 YY (1 - power) / (n_used - 3));  significance = amplitude / amplitude_err
+
+    n_used, mean and variance equal the Python statement in tests/gls_spec.py bit for bit, the sums lie within the bound
+    lomb_scargle states, and the harmonic records equal the statement's epilogue applied to the device's own sums bit for
+    bit but for phase (the device's atan2).  There is no threshold here: on the statement's 1800-point curve (noise 3e-4,
+    seeds 0 to 4) a planet of rp 0.07 has a largest significance of 1.2 to 2.5, a contact-binary sinusoid of the same depth
+    233 to 246 (tests/test_gls_host.py reports both).  mask finite and >= 0; 1 to 8 harmonics, finite and > 0; T0 and duration come
+    together; curve in [0, n_curves): ValueError otherwise, before any device work (the detrending included).  detrend=
+    takes the steps and tuples of search_batch.
+
+    Returns a structured array [n_fits] with the fields sine_test_fields(): sine_status, sine_n_used, sine_mean,
+    sine_variance, and sine_power, sine_amplitude, sine_phase, sine_amplitude_err, sine_significance [n_harmonics]."""
+    from ._lib import sine_test_arguments
+    a = sine_test_arguments(t, flux_batch, dy_batch, period, T0, duration, curve, mask, harmonics)
+    rows = _detrended(a["t"], a["y"], detrend, context, device, None, a["dy"])
+    ctx = context if context is not None else _search.default_context(device)
+    out, out_h = ctx.sine_test(a["t"], rows, a["period"], curve=a["curve"], dy=a["dy"], T0=a["T0"], duration=a["duration"],
+                               mask=a["mask"], harmonics=a["harmonics"])
+    return _with_sines(None, out, out_h)
 
 
 # ---- injection-recovery ---------------------------------------------------------------------------------------------------
