@@ -39,8 +39,9 @@ extern "C" {
  * tls_medfilt_detrend, tls_biweight_detrend), (7: tls_power_batch_peaks, tls_find_peaks),
  * (7: tls_power_batch_peak_fits, tls_debug_peak_fits), (7: tls_phase_scan, tls_power_batch_phase_scan,
  * tls_debug_peak_phase_scans), (7: tls_sysrem), (7: tls_single_transits), (7: tls_transit_times),
- * (7: tls_shape_fit), (7: tls_nudft, tls_lomb_scargle, tls_sine_test). */
-#define TLS_AMD_ABI_VERSION 7
+ * (7: tls_shape_fit), (7: tls_nudft, tls_lomb_scargle, tls_sine_test); 8: every entry that takes `root, n_root` takes a
+ * second table, `root, root_count, n_root`). */
+#define TLS_AMD_ABI_VERSION 8
 
 #define TLS_OK 0
 #define TLS_E_ARG (-1)      /* invalid argument */
@@ -282,8 +283,12 @@ typedef struct tls_transit_stats {
 } tls_transit_stats;
 /* tls_power_batch plus the statistics of every light curve, computed on the device behind the final T0 fit of each group
  * and copied back with the group's summaries (still one wait per group).  row_duration: lc_cache_overview["duration"] of
- * every template row (tmpl->n_rows entries); fill_factor: calculate_fill_factor(t); root[k] = float(k) ** 0.5 as Python
- * forms it, k = 0 .. n_root - 1 with n_root > n.  out_per_transit (NULL: not returned): [n_curves][6][max_epochs] --
+ * every template row (tmpl->n_rows entries); fill_factor: calculate_fill_factor(t); root and root_count: the two forms of
+ * k ** 0.5 that power() takes of a count, k = 0 .. n_root - 1 with n_root > n, each formed by the caller's own Python and
+ * numpy -- root[k] = float(k) ** 0.5 (Python's pow: snr, the pink-noise width, depth_mean_std) and root_count[k] =
+ * numpy.sum(k) ** 0.5 (the power of a numpy integer scalar, which depth_mean_odd_std and depth_mean_even_std divide by and
+ * which is one ulp from the other at some k, a set that depends on the numpy build).  A NULL or too short table is
+ * TLS_E_ARG with the outputs untouched.  out_per_transit (NULL: not returned): [n_curves][6][max_epochs] --
  * transit_times, per_transit_count, transit_depths, transit_depths_uncertainties, snr_per_transit, snr_pink_per_transit --
  * NaN past a curve's epochs; out_n_epochs (NULL: not returned): epochs of every curve (0 without a fit).  TLS_E_ARG when t
  * is not non-decreasing, or when a curve has more than max_epochs transit epochs. */
@@ -292,7 +297,8 @@ int tls_power_batch_stats(tls_ctx *ctx, const double *t, const double *y, const 
                           const tls_template *tmpl, const tls_params *params, int64_t median_kernel,
                           tls_power_summary *out_summary, double *out_chi2, int64_t *out_row, double *out_depth,
                           double *out_power, double *out_SR, double *out_power_raw,
-                          const double *row_duration, double fill_factor, const double *root, int64_t n_root,
+                          const double *row_duration, double fill_factor, const double *root, const double *root_count,
+                          int64_t n_root,
                           tls_transit_stats *out_stats, int64_t max_epochs, double *out_per_transit,
                           int64_t *out_n_epochs);
 /* developer/test entry: the statistics stage of tls_power_batch_stats, the same kernel, on picks the caller supplies for
@@ -301,7 +307,8 @@ int tls_power_batch_stats(tls_ctx *ctx, const double *t, const double *y, const 
 int tls_debug_transit_stats(tls_ctx *ctx, const double *y, int64_t n_curves, const double *period, const double *T0,
                             const int64_t *best_row, const double *depth, const int64_t *no_fit, const int64_t *index_power,
                             const double *power, const double *row_duration, int64_t n_rows, double fill_factor,
-                            const double *root, int64_t n_root, int64_t max_epochs, tls_transit_stats *out_stats,
+                            const double *root, const double *root_count,
+                            int64_t n_root, int64_t max_epochs, tls_transit_stats *out_stats,
                             double *out_per_transit, int64_t *out_n_epochs);
 /* tls_power_batch_stats plus the arrays power() returns for plotting (api.py:175-203), computed on the device behind the
  * statistics of each group and copied back with them (still one wait per group):
@@ -320,7 +327,8 @@ int tls_power_batch_models(tls_ctx *ctx, const double *t, const double *y, const
                            const tls_template *tmpl, const tls_params *params, int64_t median_kernel,
                            tls_power_summary *out_summary, double *out_chi2, int64_t *out_row, double *out_depth,
                            double *out_power, double *out_SR, double *out_power_raw,
-                           const double *row_duration, double fill_factor, const double *root, int64_t n_root,
+                           const double *row_duration, double fill_factor, const double *root, const double *root_count,
+                           int64_t n_root,
                            tls_transit_stats *out_stats, int64_t max_epochs, double *out_per_transit,
                            int64_t *out_n_epochs, const double *curve_t, const double *curve_f, int64_t curve_n,
                            double curve_lo, double curve_hi, double maxw, int64_t lc_cap, double *out_folded,
@@ -330,7 +338,8 @@ int tls_power_batch_models(tls_ctx *ctx, const double *t, const double *y, const
 int tls_debug_transit_models(tls_ctx *ctx, const double *y, int64_t n_curves, const double *period, const double *T0,
                              const int64_t *best_row, const double *depth, const int64_t *no_fit, const int64_t *index_power,
                              const double *power, const double *row_duration, int64_t n_rows, double fill_factor,
-                             const double *root, int64_t n_root, int64_t max_epochs, tls_transit_stats *out_stats,
+                             const double *root, const double *root_count,
+                             int64_t n_root, int64_t max_epochs, tls_transit_stats *out_stats,
                              double *out_per_transit, int64_t *out_n_epochs, const double *curve_t, const double *curve_f,
                              int64_t curve_n, double curve_lo, double curve_hi, double maxw, int64_t lc_cap,
                              double *out_folded, double *out_model_folded, double *out_lc, int64_t *out_lc_len);
@@ -497,7 +506,8 @@ int tls_power_batch_peaks(tls_ctx *ctx, const double *t, const double *y, const 
                           const tls_template *tmpl, const tls_params *params, int64_t median_kernel,
                           tls_power_summary *out_summary, double *out_chi2, int64_t *out_row, double *out_depth,
                           double *out_power, double *out_SR, double *out_power_raw,
-                          const double *row_duration, double fill_factor, const double *root, int64_t n_root,
+                          const double *row_duration, double fill_factor, const double *root, const double *root_count,
+                          int64_t n_root,
                           tls_transit_stats *out_stats, int64_t max_epochs, double *out_per_transit,
                           int64_t *out_n_epochs,
                           int64_t k, double min_separation, const double *ratios, int64_t n_ratios, double min_power,
@@ -515,8 +525,8 @@ typedef struct tls_peak_fit {
  * depth AND template row from its own index (tls_peak.row); the best pick takes its row from argmin(chi2) and period and
  * depth from argmax(power), so the first peak's fit equals the summary's T0 and out_stats exactly where index_best ==
  * index_power.  The period-uncertainty walk starts at the peak's index.  Summary, statistics and peaks are those of
- * tls_power_batch_peaks, bit for bit.  row_duration, fill_factor, root, n_root and max_epochs are read even when out_stats
- * is NULL (then out_per_transit and out_n_epochs are not written); the time stamps must ascend; a candidate with more
+ * tls_power_batch_peaks, bit for bit.  row_duration, fill_factor, root, root_count, n_root and max_epochs are read even when
+ * out_stats is NULL (then out_per_transit and out_n_epochs are not written); the time stamps must ascend; a candidate with more
  * than max_epochs transit epochs, or whose row is not the first row of a template duration, is TLS_E_ARG.  The fits run
  * in slabs of at most 128 (device memory: DESIGN.md "Peak fits").  out_fits [n_curves][k]. */
 int tls_power_batch_peak_fits(tls_ctx *ctx, const double *t, const double *y, const double *dy, int64_t n,
@@ -524,7 +534,8 @@ int tls_power_batch_peak_fits(tls_ctx *ctx, const double *t, const double *y, co
                               const tls_template *tmpl, const tls_params *params, int64_t median_kernel,
                               tls_power_summary *out_summary, double *out_chi2, int64_t *out_row, double *out_depth,
                               double *out_power, double *out_SR, double *out_power_raw,
-                              const double *row_duration, double fill_factor, const double *root, int64_t n_root,
+                              const double *row_duration, double fill_factor, const double *root, const double *root_count,
+                              int64_t n_root,
                               tls_transit_stats *out_stats, int64_t max_epochs, double *out_per_transit,
                               int64_t *out_n_epochs,
                               int64_t k, double min_separation, const double *ratios, int64_t n_ratios, double min_power,
@@ -538,7 +549,8 @@ int tls_power_batch_peak_fits(tls_ctx *ctx, const double *t, const double *y, co
  * [1, 1024]. */
 int tls_debug_peak_fits(tls_ctx *ctx, const double *y, int64_t n_curves, const tls_peak *peaks, const int64_t *n_peaks,
                         int64_t k, const double *power, const double *row_duration, int64_t n_rows, double fill_factor,
-                        const double *root, int64_t n_root, int64_t max_epochs, tls_peak_fit *out_fits,
+                        const double *root, const double *root_count,
+                        int64_t n_root, int64_t max_epochs, tls_peak_fit *out_fits,
                         double *out_epochs, double *out_residuals, int64_t *out_n_epochs);
 
 /* ---- survey mode: the secondary-eclipse phase scan of a candidate --------------------------------------------------- */
@@ -584,7 +596,8 @@ int tls_power_batch_phase_scan(tls_ctx *ctx, const double *t, const double *y, c
                                const tls_template *tmpl, const tls_params *params, int64_t median_kernel,
                                tls_power_summary *out_summary, double *out_chi2, int64_t *out_row, double *out_depth,
                                double *out_power, double *out_SR, double *out_power_raw,
-                               const double *row_duration, double fill_factor, const double *root, int64_t n_root,
+                               const double *row_duration, double fill_factor, const double *root, const double *root_count,
+                               int64_t n_root,
                                tls_transit_stats *out_stats, int64_t max_epochs, double *out_per_transit,
                                int64_t *out_n_epochs,
                                int64_t k, double min_separation, const double *ratios, int64_t n_ratios, double min_power,
@@ -595,7 +608,8 @@ int tls_power_batch_phase_scan(tls_ctx *ctx, const double *t, const double *y, c
  * as tls_power_batch_phase_scan runs it behind the fits.  out_scans [n_curves][k]. */
 int tls_debug_peak_phase_scans(tls_ctx *ctx, const double *y, int64_t n_curves, const tls_peak *peaks, const int64_t *n_peaks,
                                int64_t k, const double *power, const double *row_duration, int64_t n_rows,
-                               double fill_factor, const double *root, int64_t n_root, int64_t max_epochs,
+                               double fill_factor, const double *root, const double *root_count,
+                               int64_t n_root, int64_t max_epochs,
                                tls_peak_fit *out_fits, int64_t max_bins, int64_t min_count, tls_phase_record *out_scans);
 
 /* ---- survey mode: single-transit events ------------------------------------------------------------------------------ */

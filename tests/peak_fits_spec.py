@@ -7,18 +7,9 @@ peak's own index:
     status  1 where rank >= n_peaks, 2 where row < 0, else 0; T0 and every statistics field NaN unless 0
     T0      stats.final_T0_fit of template row `row` scaled to `depth` (the residuals of the trial epochs from the device
             kernel of the single fit, search.t0_fit_residuals, on the same context: the product has no host evaluation)
-    stats   api.py:175-241 through stats.py, as tests/test_power_batch_statistics.py host_stats forms them, with the
-            period-uncertainty walk started at `index` instead of argmax(power)
-
-One place departs from host_stats, and it is stated here so that nobody takes it for agreement with the reference:
-depth_mean_odd_std and depth_mean_even_std (and odd_even_mismatch, their quotient) are formed as numpy.std(x) / float(len(x))
-** 0.5.  stats._mean_and_err, like the reference (stats.py:392-399), divides by numpy.sum(len(x)) ** 0.5, the power of a numpy
-INTEGER scalar, which under numpy 2 is one ulp away from float(k) ** 0.5 for about one count k in twenty (19, 51, 63, 75, 76,
-...).  tls_transit_stats reads every root from the table root[k] = float(k) ** 0.5, for the best pick as for a candidate, so
-for those counts the DEVICE is one ulp away from power() in these two fields -- in the main chain since it has statistics,
-where the existing tests' counts happen to miss such k.  A candidate must equal the main chain's record (rank 0 against the
-summary) and the main chain must not move in this change, so the spec compares the two fields with the root the device
-reads; the mismatch with the reference is open and is the main chain's to close (DESIGN.md "Peak fits").
+    stats   api.py:175-241 through stats.py, as tests/test_power_batch_statistics.py host_stats forms them (the odd and even
+            depth errors from stats.intransit_stats, like power()), with the period-uncertainty walk started at `index`
+            instead of argmax(power)
 """
 import warnings
 
@@ -71,9 +62,6 @@ def candidate_stats(t, y, period, T0, duration, periods, power, index):
         dms = numpy.std(all_flux) / numpy.sum(ptc) ** (0.5)
         snr = ((1 - dm) / std_ootr) * len(all_flux) ** (0.5)
         n_in, n_after, n_before = count_stats(t, y, transit_times, d)
-        # (the root of the count from the device's table, float(k) ** 0.5: see the module's docstring)
-        mos = numpy.std(fo) / float(len(fo)) ** 0.5 if len(fo) > 0 else numpy.nan
-        mes = numpy.std(fe) / float(len(fe)) ** 0.5 if len(fe) > 0 else numpy.nan
         mismatch = abs(mo - me) / (mos + mes)
         E = len(transit_times)
         empty = numpy.count_nonzero(ptc == 0)

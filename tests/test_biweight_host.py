@@ -44,16 +44,16 @@ def test_declaration_matches_argtypes():
     assert re.search(r"Entries added without changing a layout.*tls_biweight_detrend\)", _header(), flags=re.S)
 
 
-def test_constants_mirrored_and_abi_still_7():
+def test_constants_mirrored_and_abi_8():
     h = _header()
     m = re.search(r"#define TLS_BIWEIGHT_MAX_WINDOW (\d+)\b", h)
     assert m and int(m.group(1)) == _lib.BIWEIGHT_MAX_WINDOW == spec.MAX_WINDOW >= 4095
     assert float(re.search(r"#define TLS_BIWEIGHT_C (\S+)", h).group(1)) == _lib.BIWEIGHT_C == spec.C == 5.0
     assert float(re.search(r"#define TLS_BIWEIGHT_FTOL (\S+)", h).group(1)) == _lib.BIWEIGHT_FTOL == spec.FTOL == 1e-6
     assert int(re.search(r"#define TLS_BIWEIGHT_MAX_ITER (\d+)", h).group(1)) == _lib.BIWEIGHT_MAX_ITER == spec.MAX_ITER == 50
-    assert _lib.ABI_VERSION == 7
-    assert _lib.load().tls_abi_version() == 7
-    assert re.search(r"#define TLS_AMD_ABI_VERSION 7\b", h)
+    assert _lib.ABI_VERSION == 8
+    assert _lib.load().tls_abi_version() == 8
+    assert re.search(r"#define TLS_AMD_ABI_VERSION 8\b", h)
 
 
 # ---- hand-worked cases of the restatement

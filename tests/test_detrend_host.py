@@ -38,12 +38,12 @@ def test_declaration_matches_argtypes():
     assert "tls_medfilt_detrend" in _lib.SYMBOLS
 
 
-def test_max_kernel_mirrored_and_abi_still_7():
+def test_max_kernel_mirrored_and_abi_8():
     m = re.search(r"#define TLS_MEDFILT_MAX_KERNEL (\d+)\b", _header())
     assert m and int(m.group(1)) == _lib.MEDFILT_MAX_KERNEL >= 4095
-    assert _lib.ABI_VERSION == 7
-    assert _lib.load().tls_abi_version() == 7
-    assert re.search(r"#define TLS_AMD_ABI_VERSION 7\b", _header())
+    assert _lib.ABI_VERSION == 8
+    assert _lib.load().tls_abi_version() == 8
+    assert re.search(r"#define TLS_AMD_ABI_VERSION 8\b", _header())
 
 
 # ---- a numpy restatement of the kernel's selection (tls_detrend.hip.h, tls_medfilt_detrend's span choice)

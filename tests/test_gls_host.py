@@ -286,7 +286,7 @@ def test_header_binding_and_library_declare_the_entries():
         assert len(getattr(lib, name).argtypes) == declared.count(",") + 1 == count, name
     # (additive entries keep the version: the comment lists what it gained)
     assert "(7: tls_nudft, tls_lomb_scargle, tls_sine_test)" in text.split("#define TLS_AMD_ABI_VERSION")[0]
-    assert "#define TLS_AMD_ABI_VERSION 7" in text and _lib.ABI_VERSION == 7 == lib.tls_abi_version()
+    assert "#define TLS_AMD_ABI_VERSION 8" in text and _lib.ABI_VERSION == 8 == lib.tls_abi_version()
     makefile = open(os.path.join(REPO, "tls_amd", "csrc", "Makefile")).read()
     assert "tls_gls.hip.h" in re.search(r"^HDR = (.*)$", makefile, flags=re.M).group(1)
     for name in ("nudft", "lomb_scargle", "sine_test"):

@@ -50,10 +50,10 @@ def test_injection_struct_matches_header():
     assert ctypes.sizeof(_lib.Injection) == 48 == _lib.INJECTION_DTYPE.itemsize
 
 
-def test_abi_version_still_7():
-    assert _lib.ABI_VERSION == 7
-    assert _lib.load().tls_abi_version() == 7
-    assert re.search(r"#define TLS_AMD_ABI_VERSION 7\b", open(os.path.join(REPO, "include", "tls_amd.h")).read())
+def test_abi_version_is_8():
+    assert _lib.ABI_VERSION == 8
+    assert _lib.load().tls_abi_version() == 8
+    assert re.search(r"#define TLS_AMD_ABI_VERSION 8\b", open(os.path.join(REPO, "include", "tls_amd.h")).read())
 
 
 # ---- a numpy mirror of the device's per-point sequence (tls_inject.hip.h), fed the host-formed constants

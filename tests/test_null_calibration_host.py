@@ -94,8 +94,8 @@ def test_declaration_matches_argtypes(name):
     assert name in _lib.SYMBOLS
 
 
-def test_abi_version_still_7():
-    assert _lib.ABI_VERSION == 7 == _lib.load().tls_abi_version()
+def test_abi_version_is_8():
+    assert _lib.ABI_VERSION == 8 == _lib.load().tls_abi_version()
 
 
 # ---- the random stream

@@ -11,6 +11,7 @@ import warnings
 import numpy
 import pytest
 
+import count_lattice
 import peak_fits_spec as spec
 from tls_amd import _lib, survey, transit_model
 from tls_amd.planning import search_inputs
@@ -201,10 +202,13 @@ def records(inp, rng, n_curves, k, rows=None):
 
 def debug_fits(ctx, inp, y, rec, n_peaks, power, max_epochs=None, **kw):
     t = inp["t"]
+    # (the two tables from the scalar expressions of power() themselves, not from stats.count_roots)
     root = numpy.array([float(k) ** 0.5 for k in range(len(t) + 1)])
+    root_count = numpy.array([float(numpy.sum(k) ** 0.5) for k in range(len(t) + 1)])
     if max_epochs is None:
         max_epochs = survey._max_epochs(t, inp["periods"])
-    return ctx.debug_peak_fits(y, rec, n_peaks, power, inp["table"].duration, calculate_fill_factor(t), root, max_epochs, **kw)
+    return ctx.debug_peak_fits(y, rec, n_peaks, power, inp["table"].duration, calculate_fill_factor(t), root, max_epochs,
+                               root_count=root_count, **kw)
 
 
 def with_a_repeated_width(inp):
@@ -285,6 +289,30 @@ def test_injected_records(ctx, oracle_lib, shared):
     with pytest.raises(RuntimeError, match="row out of range"):
         debug_fits(ctx, inp, y, worse, n_peaks, power)
     debug_fits(ctx, inp, y, worse, numpy.array([0, 2, 4, 3]), power)        # (a record past n_peaks is never read)
+    # either k ** 0.5 table missing or short: an error
+    tables = (numpy.array([float(i) ** 0.5 for i in range(len(T) + 1)]),
+              numpy.array([float(numpy.sum(i) ** 0.5) for i in range(len(T) + 1)]))
+    common = (y, rec, n_peaks, power, inp["table"].duration, calculate_fill_factor(inp["t"]))
+    cap = survey._max_epochs(inp["t"], inp["periods"])
+    for a, b in ((tables[0], tables[1][:-1]), (tables[0][:-1], tables[1])):
+        with pytest.raises(RuntimeError, match="must cover"):
+            ctx.debug_peak_fits(*common, a, cap, root_count=b)
+    assert ctx.debug_peak_fits(*common, tables[0], cap, root_count=tables[1]).tobytes() == got.tobytes()
+    assert ctx.debug_peak_fits(*common, tables[0], cap).tobytes() == got.tobytes()     # (the binding's own second table)
+    # ... and NULL at the C entry: TLS_E_ARG, the fits untouched
+    import ctypes
+    raw_rec = numpy.zeros(rec.shape, dtype=_lib.PEAK_DTYPE)
+    for name in _lib.PEAK_DTYPE.names:
+        raw_rec[name] = rec[name]
+    dur, yy, pw = (numpy.ascontiguousarray(v, dtype=float) for v in (inp["table"].duration, y, power))
+    for root_p, count_p in ((_lib._dp(tables[0]), None), (None, _lib._dp(tables[1]))):
+        fits = numpy.zeros(rec.shape, dtype=_lib.PEAK_FIT_DTYPE)
+        fits.view(numpy.float64)[:] = -7.0
+        rc = ctx._lib.tls_debug_peak_fits(ctx._h, _lib._dp(yy), len(yy), raw_rec.ctypes.data_as(ctypes.c_void_p),
+                                          _lib._ip(numpy.ascontiguousarray(n_peaks, dtype=numpy.int64)), k, _lib._dp(pw),
+                                          _lib._dp(dur), len(dur), calculate_fill_factor(inp["t"]), root_p, count_p,
+                                          len(tables[0]), cap, fits.ctypes.data_as(ctypes.c_void_p), None, None, None)
+        assert rc == -1 and (fits.view(numpy.float64) == -7.0).all()
     # more epochs than max_epochs: an error, not a truncated record
     short = float(inp["periods"].min())
     assert 40.0 / short > 30
@@ -304,6 +332,84 @@ def test_injected_records(ctx, oracle_lib, shared):
     worse["row"][3, 3] = 1
     with pytest.raises(RuntimeError, match="not the first row"):
         debug_fits(ctx, again, y, worse, n_peaks, power)
+
+
+def lattice_candidates(inp, n_curves, k, seed):
+    """Peak records from tests/count_lattice.py: the lattice picks whose odd or even in-transit count, at the lattice's own
+    T0, is one where the two forms of k ** 0.5 differ (or one of the fixed list), thinned evenly to n_curves * k, as
+    candidates of period and duration -- the T0 is the fit's to find.  The plan has fewer rows than the lattice has
+    durations: duration j stands in the row_duration table at the j-th row that starts a template width, j < that many."""
+    t = inp["t"]
+    good = reported_rows(inp["table"])
+    targets = sorted(set(count_lattice.disagreeing_counts(len(t))) | set(count_lattice.FIXED))
+    table = count_lattice.lattice_counts(t)
+    lattice = count_lattice.lattice()
+    at = [i for i in numpy.flatnonzero(numpy.isin(table, targets).any(axis=1)) if lattice[i][2] < len(good)]
+    assert len(at) >= n_curves * k
+    at = [at[i] for i in numpy.linspace(0, len(at) - 1, n_curves * k).astype(int)]
+    row_duration = numpy.full(inp["table"].n_rows, count_lattice.DURATIONS[0])
+    row_duration[good] = count_lattice.DURATIONS[:len(good)]
+    rng = numpy.random.RandomState(seed)
+    rec, power = records(inp, rng, n_curves, k)
+    rec["period"] = numpy.array([lattice[i][0] for i in at]).reshape(n_curves, k)
+    rec["row"] = numpy.array([good[lattice[i][2]] for i in at]).reshape(n_curves, k)
+    return rec, power, row_duration, targets
+
+
+def test_candidates_at_counts_where_the_two_roots_differ(ctx):
+    """Candidates on four noisy curves of count_lattice.TIME, 32 ranks each, steered to the in-transit counts at which
+    numpy.sum(k) ** 0.5 (the odd and even depth errors) is not float(k) ** 0.5 (snr, pink noise): every fit equals the spec,
+    whose errors are stats.intransit_stats' own, and rank 0 of every curve -- and every fit that reached such a count --
+    equals the main chain's record for the same pick (tls_debug_transit_stats at the fitted T0).
+
+    A fit puts its T0 wherever the noise has its minimum, so a candidate's counts scatter around the lattice's; the test
+    asks that 3 distinct members of the targets are reached by the fits, as an odd or an even count.  (128 candidates with
+    two counts each between about 10 and 110, 7 targets or more among those values: a dozen hits are expected, and a test
+    that reached fewer than 3 would say little.)"""
+    n_curves, k = 4, 32
+    t = count_lattice.TIME
+    rng = numpy.random.RandomState(41)
+    y = 1 + rng.normal(0, 4e-4, (n_curves, len(t)))
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        inp = search_inputs(t, y[0], period_min=1.5, period_max=9.0, oversampling_factor=1)
+    y[0] = inp["y"]
+    ctx.prepare(inp["t"], y[0], numpy.full(len(t), numpy.std(y[0])), inp["periods"], inp["table"], inp["params"])
+    rec, power, row_duration, targets = lattice_candidates(inp, n_curves, k, 43)
+    n_peaks = numpy.full(n_curves, k)
+    root = numpy.array([float(i) ** 0.5 for i in range(len(t) + 1)])
+    root_count = numpy.array([float(numpy.sum(i) ** 0.5) for i in range(len(t) + 1)])
+    fill = calculate_fill_factor(t)
+    got = ctx.debug_peak_fits(y, rec, n_peaks, power, row_duration, fill, root, 32, root_count=root_count)
+    assert (got["status"] == 0).all()
+    reached, again, hits = set(), [], 0
+    for c in range(n_curves):
+        for r in range(k):
+            p = rec[c, r]
+            T0 = spec.candidate_T0(ctx, inp, y[c], float(p["period"]), float(p["depth"]), int(p["row"]))
+            duration = row_duration[int(p["row"])]
+            want = spec.candidate_stats(t, y[c], float(p["period"]), T0, duration, inp["periods"], power[c], int(p["index"]))
+            odd, even, _ = count_lattice.counts(t, float(p["period"]), T0, duration)
+            expect_equal(got["T0"][c, r], T0, (c, r, "T0"))
+            for name, v in want.items():
+                expect_equal(got[name][c, r], v, (c, r, name, "odd %d even %d" % (odd, even)))
+            hit = {odd, even} & set(targets)
+            reached |= hit
+            hits += bool(hit)
+            if hit or r == 0:
+                again.append((c, r))
+    print("\n%d of %d fits have an odd or even count among the targets; distinct members reached: %s"
+          % (hits, n_curves * k, sorted(reached)))
+    assert len(reached) >= 3
+    # the main chain on the same picks: one record, whichever stage formed it
+    for c in range(n_curves):
+        mine = [r for cc, r in again if cc == c]
+        stats, _, _ = ctx.debug_transit_stats(
+            numpy.repeat(y[c][None, :], len(mine), axis=0), rec["period"][c, mine], got["T0"][c, mine], rec["row"][c, mine],
+            rec["depth"][c, mine], 0, rec["index"][c, mine], numpy.repeat(power[c][None, :], len(mine), axis=0), row_duration,
+            fill, root, 32, root_count=root_count)
+        for name in _lib.TRANSIT_STATS_FIELDS:
+            expect_equal(stats[name], got[name][c, mine], (c, name, "main chain"))
 
 
 def test_two_contexts_equal_the_one_device_call():

@@ -94,7 +94,7 @@ def test_header_binding_and_library_declare_both_entries():
         assert name in _lib.SYMBOLS
         assert hasattr(lib, name)
         assert name in text.split("#define TLS_AMD_ABI_VERSION")[0]      # (the version comment lists the entries it gained)
-    assert "#define TLS_AMD_ABI_VERSION 7" in text and _lib.ABI_VERSION == 7 == lib.tls_abi_version()
+    assert "#define TLS_AMD_ABI_VERSION 8" in text and _lib.ABI_VERSION == 8 == lib.tls_abi_version()
     # the arguments of tls_power_batch_peaks, then the fits
     peaks, fits = (re.search(r"\bint\s+%s\s*\((.*?)\);" % n, code, flags=re.S).group(1)
                    for n in ("tls_power_batch_peaks", "tls_power_batch_peak_fits"))

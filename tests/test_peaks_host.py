@@ -149,7 +149,7 @@ def test_header_and_binding_declare_both_entries():
         assert name in _lib.SYMBOLS
         assert name in text.split("#define TLS_AMD_ABI_VERSION")[0]      # (the version comment lists the entries it gained)
     assert re.search(r"typedef struct tls_peak \{\s*double period, power, chi2, depth;\s*int64_t index, row;\s*\} tls_peak;", code)
-    assert "#define TLS_AMD_ABI_VERSION 7" in text
+    assert "#define TLS_AMD_ABI_VERSION 8" in text
     assert [n for n, _ in _lib.Peak._fields_] == list(_lib.PEAK_DTYPE.names) == ["period", "power", "chi2", "depth", "index", "row"]
     assert _lib.PEAK_DTYPE.itemsize == 48
     assert ("#define TLS_PEAKS_MAX_K %d" % _lib.PEAKS_MAX_K) in text and ("#define TLS_PEAKS_MAX_RATIOS %d" % _lib.PEAKS_MAX_RATIOS) in text

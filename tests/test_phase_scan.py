@@ -319,10 +319,11 @@ def test_injected_records_of_every_status(ctx, shared):
     n_peaks = numpy.array([0, 2, 4])
     ctx.prepare(inp["t"], y[0], numpy.full(len(T), numpy.std(y[0])), inp["periods"], inp["table"], inp["params"])
     root = numpy.array([float(i) ** 0.5 for i in range(len(T) + 1)])
+    root_count = numpy.array([float(numpy.sum(i) ** 0.5) for i in range(len(T) + 1)])
     args = (y, rec, n_peaks, power, inp["table"].duration, calculate_fill_factor(inp["t"]), root,
             survey._max_epochs(inp["t"], inp["periods"]))
-    fits, scans = ctx.debug_peak_fits(*args, phase_scan=(4096, 3))
-    assert fits.tobytes() == ctx.debug_peak_fits(*args).tobytes()
+    fits, scans = ctx.debug_peak_fits(*args, phase_scan=(4096, 3), root_count=root_count)
+    assert fits.tobytes() == ctx.debug_peak_fits(*args, root_count=root_count).tobytes()
     expect_equal(fits["status"], [[1, 1, 1, 1], [0, 0, 1, 1], [0, 2, 0, 0]], "fit status")
     expect_equal(scans["status"], [[1, 1, 1, 1], [0, 0, 1, 1], [0, 1, 0, 0]], "scan status")
     for c in range(3):

@@ -115,12 +115,14 @@ def run_injected(ctx, inp, y, period, T0, durations, depth, lc_cap=None):
     power = rng.uniform(0, 1, (n_c, len(inp["periods"])))
     max_epochs = 4 * n
     root = numpy.array([float(k) ** 0.5 for k in range(n + 1)])
+    root_count = numpy.array([float(numpy.sum(k) ** 0.5) for k in range(n + 1)])
     row_duration = inp["table"].duration.copy()   # (one per template row; curve c takes row c)
     assert len(row_duration) >= n_c
     row_duration[:n_c] = durations
     cap = lc_cap or 15 * n + 10
     return ctx.debug_transit_models(y, period, T0, numpy.arange(n_c), depth, 0, 0, power, row_duration,
-                                    calculate_fill_factor(inp["t"]), root, max_epochs, survey._model_template(inp), cap)
+                                    calculate_fill_factor(inp["t"]), root, max_epochs, survey._model_template(inp), cap,
+                                    root_count=root_count)
 
 
 def test_model_stage_edges_equal_the_host_sequence():

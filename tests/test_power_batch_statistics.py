@@ -1,12 +1,14 @@
 """Survey-mode power()'s per-transit vetting statistics on the device (tls_power_batch_stats, tls_debug_transit_stats): every
 field bit-equal to what power() reports for the same light curve, and to the host sequence of api.py:175-241 on injected
-picks that reach the edge branches."""
+picks that reach the edge branches -- among them the in-transit counts at which the two forms of k ** 0.5 that power()
+takes of a count differ (tests/count_lattice.py)."""
 import time
 import warnings
 
 import numpy
 import pytest
 
+import count_lattice
 import tls_amd
 from tls_amd import _lib, survey, synthetic, transit_model
 from tls_amd.helpers import transit_mask
@@ -118,7 +120,7 @@ def host_stats(t, y, period, T0, duration, periods, power):
                    in_transit_count=n_in, after_transit_count=n_after, before_transit_count=n_before)
         rows = (transit_times, ptc, td, tdu, spt, sppt)
         width = int(numpy.mean(ptc))
-    return rec, rows, dict(width=width, n_ootr=len(flux_ootr), filled=E - empty, odd=len(fo))
+    return rec, rows, dict(width=width, n_ootr=len(flux_ootr), filled=E - empty, odd=len(fo), even=len(fe))
 
 
 def prepared(ctx, t, flux, **kw):
@@ -131,20 +133,25 @@ def run_injected(ctx, inp, y, picks, row_duration, powers, max_epochs=4000):
     """picks: (period, T0, best_row) per curve; every curve's statistics from the device and from the host."""
     t = inp["t"]
     n_c = len(picks)
+    # (the two tables from the scalar expressions of power() themselves, not from stats.count_roots)
     root = numpy.array([float(k) ** 0.5 for k in range(len(t) + 1)])
+    root_count = numpy.array([float(numpy.sum(k) ** 0.5) for k in range(len(t) + 1)])
     index_power = [int(numpy.argmax(p)) for p in powers]
     stats, rows, n_ep = ctx.debug_transit_stats(
         numpy.repeat(y[None, :], n_c, axis=0), [p[0] for p in picks], [p[1] for p in picks], [p[2] for p in picks],
-        0.999, 0, index_power, numpy.array(powers), row_duration, calculate_fill_factor(t), root, max_epochs)
+        0.999, 0, index_power, numpy.array(powers), row_duration, calculate_fill_factor(t), root, max_epochs,
+        root_count=root_count)
     infos = []
     for c, (period, T0, best_row) in enumerate(picks):
         rec, want_rows, info = host_stats(t, y, period, T0, row_duration[best_row], inp["periods"], powers[c])
+        where = "pick %d (period %r, T0 %r, duration %r; %d odd and %d even points in transit)" % (
+            c, period, T0, float(row_duration[best_row]), info["odd"], info["even"])
         for k, v in rec.items():
-            expect_equal(stats[k][c], v, "pick %d: %s" % (c, k))
+            expect_equal(stats[k][c], v, "%s: %s" % (where, k))
         e = int(n_ep[c])
         assert e == rec["transit_count"]
         for i, v in enumerate(want_rows):
-            expect_equal(rows[c, i, :e], v, "pick %d: %s" % (c, PER_TRANSIT[i]))
+            expect_equal(rows[c, i, :e], v, "%s: %s" % (where, PER_TRANSIT[i]))
             assert numpy.all(numpy.isnan(rows[c, i, e:]))
         infos.append(info)
     return stats, infos
@@ -199,6 +206,212 @@ def test_more_than_512_filled_epochs_follow_the_segmented_form():
     wide = numpy.full(inp["table"].n_rows, 0.4)
     stats, infos = run_injected(ctx, inp, inp["y"], [(0.1, 3.05, 0), (0.23, 3.1, 0)], wide, [power, power])
     assert infos[0]["filled"] > 512 and infos[1]["filled"] <= 512
+    ctx.close()
+
+
+@pytest.fixture(scope="module")
+def lattice_table():
+    """Odd and even in-transit count of every pick of count_lattice.lattice(): host work alone."""
+    return count_lattice.lattice_counts()
+
+
+def run_lattice(ctx, inp, y, picks, power):
+    """run_injected on picks (period, T0, index into count_lattice.DURATIONS): the plan has fewer template rows than the
+    lattice has durations, so the picks go by the row_duration table that holds theirs, in slabs of 256; the info of every
+    pick, in the order of `picks`."""
+    tables, table_of, row_of = count_lattice.duration_tables(inp["table"].n_rows)
+    infos = [None] * len(picks)
+    for i, table in enumerate(tables):
+        mine = [c for c, p in enumerate(picks) if table_of[p[2]] == i]
+        for lo in range(0, len(mine), 256):
+            slab = mine[lo:lo + 256]
+            injected = [(picks[c][0], picks[c][1], int(row_of[picks[c][2]])) for c in slab]
+            _, got = run_injected(ctx, inp, y, injected, table, [power] * len(slab), max_epochs=32)
+            for c, info in zip(slab, got):
+                infos[c] = info
+    return infos
+
+
+def lattice_inputs(ctx):
+    t = count_lattice.TIME
+    rng = numpy.random.RandomState(19)
+    inp = prepared(ctx, t, 1 + rng.normal(0, 4e-4, len(t)), period_min=1.5, period_max=9.0, oversampling_factor=1)
+    n_p = len(inp["periods"])
+    power = numpy.exp(-0.5 * ((numpy.arange(n_p) - n_p / 3) / 30.0) ** 2) + rng.uniform(0, 0.05, n_p)
+    return inp, power
+
+
+def test_odd_and_even_counts_where_the_two_roots_differ(lattice_table):
+    """power() divides the odd and the even depth error by numpy.sum(len(x)) ** 0.5, the power of a numpy integer scalar, and
+    forms snr and the pink noise with float(k) ** 0.5; at the counts D the two differ by one ulp.  Picks chosen on the host,
+    before any device call, so that their odd or even count is a member of D (formed with the running numpy) or of the fixed
+    list 19, 51, 63, 75, 76, 78, 107: every field and every per-transit row equals the host's.  A kernel that read one table
+    for both fails here in depth_mean_odd_std or depth_mean_even_std wherever D is not empty; where it is empty the test
+    runs on the fixed list and cannot tell the two roots apart."""
+    t = count_lattice.TIME
+    lattice = count_lattice.lattice()
+    D = count_lattice.disagreeing_counts(len(t))
+    print("\nnumpy %s: numpy.sum(k) ** 0.5 != float(k) ** 0.5 at len(D) = %d counts k <= %d: %s ..."
+          % (numpy.__version__, len(D), len(t), D[:12]))
+    targets = sorted(set(D) | set(count_lattice.FIXED))
+    keep, odd_reached, even_reached = count_lattice.covering(targets, lattice_table)
+    print("distinct members reached: %d as odd counts %s, %d as even counts %s, by %d picks"
+          % (len(odd_reached), sorted(odd_reached), len(even_reached), sorted(even_reached), len(keep)))
+    assert len(odd_reached) >= 5 and len(even_reached) >= 5
+    assert len(keep) <= 64
+    picks = [lattice[i] for i in keep]
+    # ... a pick without an odd epoch, and one whose epochs hold 0, 1 and 2 points
+    single = (20.0, 19.5, 3)
+    assert count_lattice.counts(t, single[0], single[1], count_lattice.DURATIONS[3])[0] == 0
+    sparse = next(p for p in lattice if p[2] < 8 and
+                  set(count_lattice.counts(t, p[0], p[1], count_lattice.DURATIONS[p[2]])[2].tolist()) == {0, 1, 2})
+    picks += [single, sparse]
+    ctx = _lib.Context(0)
+    inp, power = lattice_inputs(ctx)
+    t0 = time.perf_counter()
+    infos = run_lattice(ctx, inp, inp["y"], picks, power)
+    print("%d picks compared in %.2f s" % (len(picks), time.perf_counter() - t0))
+    for i, info in zip(keep, infos):
+        assert (info["odd"], info["even"]) == tuple(lattice_table[i])     # (the counts the picks were chosen for)
+    assert {info["odd"] for info in infos} >= odd_reached and {info["even"] for info in infos} >= even_reached
+    assert infos[-2]["odd"] == 0 and infos[-2]["even"] > 0
+    ctx.close()
+
+
+def test_a_sweep_of_counts_up_to_146(lattice_table):
+    """Every 6th pick of the lattice (882 picks: 133 distinct odd and even counts from 0 to 146, empty epochs and the gap
+    included) through the same comparison, whatever their counts are: no choice of examples decides what is seen.  Stride 6:
+    the host side (host_stats of every pick) takes about 0.8 s, the whole test about 2 s."""
+    lattice = count_lattice.lattice()
+    chosen = list(range(0, len(lattice), 6))
+    assert len(chosen) == 882
+    seen = set(lattice_table[chosen].ravel().tolist())
+    assert min(seen) == 0 and max(seen) >= 140 and len(seen) >= 120
+    ctx = _lib.Context(0)
+    inp, power = lattice_inputs(ctx)
+    t0 = time.perf_counter()
+    infos = run_lattice(ctx, inp, inp["y"], [lattice[i] for i in chosen], power)
+    print("\n%d picks compared in %.2f s" % (len(chosen), time.perf_counter() - t0))
+    for i, info in zip(chosen, infos):
+        assert (info["odd"], info["even"]) == tuple(lattice_table[i])
+    empty = [0 in count_lattice.counts(count_lattice.TIME, p, T0, count_lattice.DURATIONS[j])[2]
+             for p, T0, j in (lattice[i] for i in chosen)]
+    assert 100 < sum(empty) < len(chosen)      # (epochs inside the gap, and picks without one)
+    ctx.close()
+
+
+PLANTED_SEED = 9      # (of seeds 0 to 29 one that puts 6 curves on a count of D under numpy 2.2.6; worked out on the host,
+                      # with the CPU oracle's search in power())
+PLANTED_KW = dict(period_min=3.0, period_max=6.0, oversampling_factor=1)
+
+
+def planted_batch(n_curves=24, seed=PLANTED_SEED):
+    """Light curves on count_lattice.TIME with one planet each: durations spread evenly from 0.1 d to 0.5 d (a / R_star from
+    the period), so that the odd and even in-transit counts of the picks spread from about 12 to 80."""
+    t = count_lattice.TIME
+    rng = numpy.random.RandomState(seed)
+    fluxes = []
+    for s in range(n_curves):
+        per = float(rng.uniform(3.3, 5.7))
+        days = 0.1 + 0.4 * s / (n_curves - 1)
+        f = transit_model.light_curve(t, 3.2 + float(rng.uniform(0, 1)) * per, per, float(rng.uniform(0.05, 0.08)),
+                                      per / (numpy.pi * days), 90.0, 0, 90, [0.4, 0.3], "quadratic")
+        fluxes.append(f + rng.normal(0, 4e-4, len(t)))
+    return numpy.array(fluxes)
+
+
+def test_end_to_end_at_counts_where_the_two_roots_differ():
+    """survey.power_batch(statistics=True, per_transit=True) and survey.power_results against transitleastsquares(t,
+    y_k).power() for 24 light curves whose planets' durations spread from 0.1 d to 0.5 d: every statistics field, every
+    per-transit array and every one of the 41 keys.  At least 3 curves have, in the pick the device made, an odd or an even
+    in-transit count in D (the counts at which numpy.sum(k) ** 0.5 is not float(k) ** 0.5 under the running numpy), read
+    from power()'s own per_transit_count -- unless D is empty, which is printed."""
+    from test_power_batch_results import assert_results_equal
+    t = count_lattice.TIME
+    fluxes = planted_batch()
+    D = set(count_lattice.disagreeing_counts(len(t)))
+    ctx = _lib.Context(0)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        t0 = time.perf_counter()
+        summary, periods, pt = survey.power_batch(t, fluxes, context=ctx, statistics=True, per_transit=True, **PLANTED_KW)
+        results = survey.power_results(t, fluxes, context=ctx, **PLANTED_KW)
+        device_s = time.perf_counter() - t0
+        at_D = []
+        for s in range(len(fluxes)):
+            one = tls_amd.transitleastsquares(t, fluxes[s], verbose=False).power(
+                context=ctx, verbose=False, show_progress_bar=False, **PLANTED_KW)
+            rec = summary[s]
+            assert not rec["no_fit"]
+            expect_equal([rec["T0"], rec["period"]], [one.T0, one.period], "curve %d: T0, period" % s)
+            count = numpy.asarray(one.per_transit_count)
+            odd, even = int(count[1::2].sum()), int(count[0::2].sum())
+            where = "curve %d (%d odd and %d even points in transit)" % (s, odd, even)
+            for field, (key, i) in RESULT_OF.items():
+                want = one[key] if i is None else one[key][i]
+                expect_equal(rec[field], want, "%s: %s" % (where, field))
+            e = int(pt["n_epochs"][s])
+            assert e == len(one.transit_times) == rec["transit_count"]
+            for key in PER_TRANSIT:
+                expect_equal(pt[key][s, :e], one[key], "%s: %s" % (where, key))
+                assert numpy.all(numpy.isnan(pt[key][s, e:])), (s, key)
+            assert_results_equal(results[s], one, where)
+            if odd in D or even in D:
+                at_D.append((s, odd, even))
+    print("\nnumpy %s, len(D) = %d; %d of %d curves have an odd or even count in D: %s; the two device calls took %.2f s"
+          % (numpy.__version__, len(D), len(at_D), len(fluxes), at_D, device_s))
+    if D:
+        assert len(at_D) >= 3
+    else:
+        print("D is empty on this machine: the condition on the counts is dropped")
+    ctx.close()
+
+
+def test_a_missing_or_short_root_table_is_an_argument_error():
+    """Either k ** 0.5 table NULL or shorter than n + 1 entries: TLS_E_ARG at the C entry with every output untouched, and a
+    RuntimeError through the binding for a short one, for the injected picks and for the whole chain."""
+    import ctypes
+    ctx = _lib.Context(0)
+    t = gapped_time()
+    n = len(t)
+    rng = numpy.random.RandomState(23)
+    inp = prepared(ctx, t, 1 + rng.normal(0, 4e-4, n), period_min=1.5, period_max=9.0, oversampling_factor=1)
+    n_p, dur = len(inp["periods"]), numpy.ascontiguousarray(inp["table"].duration)
+    root = numpy.array([float(k) ** 0.5 for k in range(n + 1)])
+    root_count = numpy.array([float(numpy.sum(k) ** 0.5) for k in range(n + 1)])
+    y, power = numpy.ascontiguousarray(inp["y"][None, :]), numpy.ones((1, n_p))
+    period, T0, depth = numpy.array([4.321]), numpy.array([4.1]), numpy.array([0.999])
+    row, no_fit, index = numpy.array([3]), numpy.array([0]), numpy.array([n_p // 2])
+    dp, ip = _lib._dp, _lib._ip
+
+    def call(root_p, count_p, n_root):
+        stats = numpy.zeros(1, dtype=_lib.TRANSIT_STATS_DTYPE)
+        stats.view(numpy.float64)[:] = -7.0
+        rows, n_ep = numpy.full((1, 6, 32), -7.0), numpy.full(1, -7, dtype=numpy.int64)
+        rc = ctx._lib.tls_debug_transit_stats(ctx._h, dp(y), 1, dp(period), dp(T0), ip(row), dp(depth), ip(no_fit), ip(index),
+                                              dp(power), dp(dur), len(dur), calculate_fill_factor(t), root_p, count_p, n_root,
+                                              32, stats.ctypes.data_as(ctypes.c_void_p), dp(rows), ip(n_ep))
+        untouched = bool((stats.view(numpy.float64) == -7.0).all() and (rows == -7.0).all() and (n_ep == -7).all())
+        return rc, untouched
+
+    assert call(dp(root), dp(root_count), n + 1) == (0, False)
+    for bad in ((None, dp(root_count), n + 1), (dp(root), None, n + 1), (None, None, n + 1), (dp(root), dp(root_count), n),
+                (dp(root), dp(root_count), 0)):
+        assert call(*bad) == (-1, True), bad                      # TLS_E_ARG
+    fill = calculate_fill_factor(t)
+    injected = (y, period, T0, row, depth, no_fit, index, power, dur, fill)
+    with pytest.raises(RuntimeError, match="must cover"):
+        ctx.debug_transit_stats(*injected, root, 32, root_count=root_count[:n])
+    with pytest.raises(RuntimeError, match="must cover"):
+        ctx.debug_transit_stats(*injected, root[:n], 32, root_count=root_count)
+    # (the binding forms the second table itself when it is not given: stats.count_roots)
+    given = ctx.debug_transit_stats(*injected, root, 32, root_count=root_count)
+    formed = ctx.debug_transit_stats(*injected, root, 32)
+    assert given[0].tobytes() == formed[0].tobytes()
+    chain = (inp["t"], y, inp["dy"][None, :], inp["periods"], inp["table"], inp["params"], 30, fill)
+    with pytest.raises(RuntimeError, match="must cover"):
+        ctx.power_batch_stats(*chain, root, 32, root_count=root_count[:n])
+    assert len(ctx.power_batch_stats(*chain, root, 32, root_count=root_count)[1]) == 1
     ctx.close()
 
 

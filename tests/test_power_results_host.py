@@ -21,7 +21,7 @@ def declaration(name):
 
 def test_binding_matches_the_header():
     text = open(os.path.join(REPO, "include", "tls_amd.h")).read()
-    assert int(re.search(r"#define TLS_AMD_ABI_VERSION (\d+)", text).group(1)) == _lib.ABI_VERSION == 7
+    assert int(re.search(r"#define TLS_AMD_ABI_VERSION (\d+)", text).group(1)) == _lib.ABI_VERSION == 8
     lib = _lib.load()
     for name in ("tls_power_batch_models", "tls_debug_transit_models"):
         assert name in _lib.SYMBOLS

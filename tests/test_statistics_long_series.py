@@ -8,9 +8,7 @@ statistics=True) runs, against host_stats of tests/test_power_batch_statistics.p
 
 The noise seeds: on 1, 11 and 12 a single pairwise pass over the 10 182 out-of-transit points rounds their std, and with it
 the snr, the other way than numpy's blocks do (worked out on the host, from numpy's pairwise_sum restated in Python, for
-seeds 1 to 12); on seed 2 both agree.  The pick's odd and even in-transit counts (39 and 40) are none of the counts k for
-which numpy 2 rounds numpy.sum(k) ** 0.5 unlike float(k) ** 0.5, the root the kernel reads: that mismatch of
-depth_mean_odd_std and depth_mean_even_std is another matter and is open (tests/peak_fits_spec.py states it)."""
+seeds 1 to 12); on seed 2 both agree."""
 import numpy
 import pytest
 

@@ -45,7 +45,7 @@ def test_declaration_matches_argtypes():
     assert re.search(r"Entries added without changing a layout.*tls_sysrem\)", _header(), flags=re.S)
 
 
-def test_constants_mirrored_and_abi_still_7():
+def test_constants_mirrored_and_abi_8():
     h = _header()
     for name, mine, its in (("LANES", _lib.SYSREM_LANES, spec.LANES), ("ROW_CHUNK", _lib.SYSREM_ROW_CHUNK, spec.ROW_CHUNK),
                             ("MAX_COMPONENTS", _lib.SYSREM_MAX_COMPONENTS, spec.MAX_COMPONENTS),
@@ -53,9 +53,9 @@ def test_constants_mirrored_and_abi_still_7():
         m = re.search(r"#define TLS_SYSREM_%s (\d+)\b" % name, h)
         assert m and int(m.group(1)) == mine == its, name
     assert (_lib.SYSREM_LANES, _lib.SYSREM_ROW_CHUNK, _lib.SYSREM_MAX_COMPONENTS, _lib.SYSREM_MAX_ITER) == (256, 32, 8, 1000)
-    assert _lib.ABI_VERSION == 7
-    assert _lib.load().tls_abi_version() == 7
-    assert re.search(r"#define TLS_AMD_ABI_VERSION 7\b", h)
+    assert _lib.ABI_VERSION == 8
+    assert _lib.load().tls_abi_version() == 8
+    assert re.search(r"#define TLS_AMD_ABI_VERSION 8\b", h)
 
 
 # ---- hand-worked cases of the restatement

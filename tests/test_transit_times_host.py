@@ -166,7 +166,7 @@ def test_header_binding_and_library_declare_the_entry():
     assert re.search(r"\bint\s+%s\s*\(" % name, code)
     assert name in _lib.SYMBOLS and hasattr(lib, name)
     assert name in text.split("#define TLS_AMD_ABI_VERSION")[0]      # (the version comment lists the entries it gained)
-    assert "#define TLS_AMD_ABI_VERSION 7" in text and _lib.ABI_VERSION == 7 == lib.tls_abi_version()
+    assert "#define TLS_AMD_ABI_VERSION 8" in text and _lib.ABI_VERSION == 8 == lib.tls_abi_version()
     squeeze = lambda s: re.sub(r"\s*,\s*", ", ", re.sub(r"\s+", " ", s)).strip()
     declared = squeeze(re.search(r"\bint\s+%s\s*\((.*?)\);" % name, code, flags=re.S).group(1))
     assert len(lib.tls_transit_times.argtypes) == declared.count(",") + 1 == 22

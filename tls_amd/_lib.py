@@ -19,7 +19,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtls_amd.so")
 if os.environ.get("TLS_AMD_DEBUG") == "1" and os.environ.get("TLS_AMD_LIB"):
     LIB_PATH = os.environ["TLS_AMD_LIB"]
-ABI_VERSION = 7   # include/tls_amd.h TLS_AMD_ABI_VERSION: checked against the library at load time
+ABI_VERSION = 8   # include/tls_amd.h TLS_AMD_ABI_VERSION: checked against the library at load time
 MEDFILT_MAX_KERNEL = 4095   # include/tls_amd.h TLS_MEDFILT_MAX_KERNEL: the largest kernel size tls_medfilt_detrend takes
 # include/tls_amd.h TLS_BIWEIGHT_*: the most points of one window of tls_biweight_detrend, and the estimator's fixed constants
 BIWEIGHT_MAX_WINDOW = 4095
@@ -742,11 +742,12 @@ def load():
     lib.tls_power_batch_stats.restype = ci
     lib.tls_power_batch_stats.argtypes = [vp, _c_double_p, _c_double_p, _c_double_p, i64, i64, _c_double_p, i64,
                                           tp, pp, i64, ctypes.c_void_p, _c_double_p, _c_int64_p, _c_double_p, _c_double_p,
-                                          _c_double_p, _c_double_p, _c_double_p, dbl, _c_double_p, i64, ctypes.c_void_p, i64,
-                                          _c_double_p, _c_int64_p]
+                                          _c_double_p, _c_double_p, _c_double_p, dbl, _c_double_p, _c_double_p, i64,
+                                          ctypes.c_void_p, i64, _c_double_p, _c_int64_p]
     lib.tls_debug_transit_stats.restype = ci
     lib.tls_debug_transit_stats.argtypes = [vp, _c_double_p, i64, _c_double_p, _c_double_p, _c_int64_p, _c_double_p, _c_int64_p,
-                                            _c_int64_p, _c_double_p, _c_double_p, i64, dbl, _c_double_p, i64, i64, ctypes.c_void_p,
+                                            _c_int64_p, _c_double_p, _c_double_p, i64, dbl, _c_double_p, _c_double_p, i64, i64,
+                                            ctypes.c_void_p,
                                             _c_double_p, _c_int64_p]
     models = [_c_double_p, _c_double_p, i64, dbl, dbl, dbl, i64, _c_double_p, _c_double_p, _c_double_p, _c_int64_p]
     lib.tls_power_batch_models.restype = ci
@@ -804,10 +805,12 @@ def load():
                                   _c_int64_p, i64, _c_double_p, i64, dbl, ctypes.c_void_p, ctypes.c_void_p, _c_double_p]
     lib.tls_debug_peak_phase_scans.restype = ci
     lib.tls_debug_peak_phase_scans.argtypes = [vp, _c_double_p, i64, ctypes.c_void_p, _c_int64_p, i64, _c_double_p, _c_double_p,
-                                               i64, dbl, _c_double_p, i64, i64, ctypes.c_void_p, i64, i64, ctypes.c_void_p]
+                                               i64, dbl, _c_double_p, _c_double_p, i64, i64, ctypes.c_void_p, i64, i64,
+                                               ctypes.c_void_p]
     lib.tls_debug_peak_fits.restype = ci
     lib.tls_debug_peak_fits.argtypes = [vp, _c_double_p, i64, ctypes.c_void_p, _c_int64_p, i64, _c_double_p, _c_double_p, i64,
-                                        dbl, _c_double_p, i64, i64, ctypes.c_void_p, _c_double_p, _c_double_p, _c_int64_p]
+                                        dbl, _c_double_p, _c_double_p, i64, i64, ctypes.c_void_p, _c_double_p, _c_double_p,
+                                        _c_int64_p]
     lib.tls_debug_device_bytes.restype = ci
     lib.tls_debug_device_bytes.argtypes = [vp, _c_int64_p, _c_int64_p]
     lib.tls_debug_perm_table.restype = ci
@@ -1000,6 +1003,15 @@ def _i8(a):
     return numpy.ascontiguousarray(a, dtype=numpy.int64)
 
 
+def _root_count(root, root_count):
+    """The second k ** 0.5 table of the statistics entries as float64: the caller's, or (None) stats.count_roots' own for as
+    many counts as `root` covers."""
+    if root_count is None:
+        from .stats import count_roots
+        return count_roots(len(root) - 1)[1]
+    return _f8(root_count)
+
+
 def _dp(a):
     return a.ctypes.data_as(_c_double_p)
 
@@ -1134,14 +1146,17 @@ class Context(object):
         return tuple(r[k] for k in ("summary",) + PER_PERIOD_OUTPUTS[:4 + 2 * bool(with_spectra)])
 
     def power_batch_stats(self, t, y_batch, dy_batch, periods, table, params, median_kernel, fill_factor, root, max_epochs,
-                          per_transit=False, with_arrays=False, with_spectra=False, models=None, lc_cap=0):
+                          per_transit=False, with_arrays=False, with_spectra=False, models=None, lc_cap=0, root_count=None):
         """power_batch plus the per-transit statistics of every light curve (tls_power_batch_stats): (summary, stats
         (TRANSIT_STATS_DTYPE), per_transit [n_curves, 6, max_epochs] or None, n_epochs or None, chi2, row, depth, power).
-        table.duration is the fractional duration of every template row; root[k] = float(k) ** 0.5, k = 0 .. len(t).
+        table.duration is the fractional duration of every template row; root and root_count are the two tables of
+        stats.count_roots(len(t)): root[k] = float(k) ** 0.5 and root_count[k] = numpy.sum(k) ** 0.5, k = 0 .. len(t)
+        (the entry reads as many entries as the shorter one has; root_count None: stats.count_roots' own, as long as root).
         with_spectra: SR and power_raw [n_curves, n_periods] follow.  models (a ModelTemplate): tls_power_batch_models, and
         (folded [n_curves, 3, n], model_folded [n_curves, n], lightcurve [n_curves, 2, lc_cap], lc_len [n_curves]) follow."""
         r = self._power_batch(t, y_batch, dy_batch, periods, table, params, median_kernel, with_arrays=with_arrays,
-                              with_power=with_arrays, with_spectra=with_spectra, statistics=(fill_factor, root, max_epochs),
+                              with_power=with_arrays, with_spectra=with_spectra,
+                              statistics=(fill_factor, root, _root_count(root, root_count), max_epochs),
                               per_transit=per_transit, models=models, lc_cap=lc_cap)
         names = ("summary", "stats", "per_transit", "n_epochs") + PER_PERIOD_OUTPUTS[:4 + 2 * bool(with_spectra)]
         return tuple(r[k] for k in names + (MODEL_OUTPUTS if models is not None else ()))
@@ -1149,14 +1164,14 @@ class Context(object):
     def _power_batch(self, t, y_batch, dy_batch, periods, table, params, median_kernel, with_arrays=False, with_power=False,
                      with_spectra=False, statistics=None, per_transit=False, models=None, lc_cap=0, peaks=None,
                      peak_fits=None, phase_scan=None):
-        """The power-batch entries: tls_power_batch; with statistics = (fill_factor, root, max_epochs)
+        """The power-batch entries: tls_power_batch; with statistics = (fill_factor, root, root_count, max_epochs)
         tls_power_batch_stats; with models (a ModelTemplate) as well, tls_power_batch_models.  A dict of the outputs by name:
         summary; chi2, row, depth (with_arrays), power (with_power), SR and power_raw (with_spectra), None where not asked
         for; with statistics also stats, per_transit and n_epochs (None without per_transit); with models MODEL_OUTPUTS.
         peaks = (k, separation, ratios, min_power) (peaks_arguments): tls_power_batch_peaks, with or without statistics, and
         peaks (PEAK_DTYPE [n_curves, k]) and n_peaks [n_curves] as well; no entry carries peaks and models (ValueError).
-        peak_fits = (fill_factor, root, max_epochs), with peaks only: tls_power_batch_peak_fits, and peak_fits (PEAK_FIT_DTYPE
-        [n_curves, k]: T0, status and the statistics record of every peak) as well, with or without statistics.
+        peak_fits = (fill_factor, root, root_count, max_epochs), with peaks only: tls_power_batch_peak_fits, and peak_fits
+        (PEAK_FIT_DTYPE [n_curves, k]: T0, status and the statistics record of every peak) as well, with or without statistics.
         phase_scan = (max_bins, min_count), with peak_fits only: tls_power_batch_phase_scan, and phase_scans (PHASE_SCAN_DTYPE
         [n_curves, k]) as well."""
         if peaks is not None and models is not None:
@@ -1186,14 +1201,15 @@ class Context(object):
         args += [None if out[k] is None else _ip(out[k]) if k == "row" else _dp(out[k]) for k in PER_PERIOD_OUTPUTS]
         entry = self._lib.tls_power_batch
         if statistics is not None:
-            fill_factor, root, max_epochs = statistics
-            row_duration, root, max_epochs = _f8(table.duration), _f8(root), int(max_epochs)
+            fill_factor, root, root_count, max_epochs = statistics
+            row_duration, root, root_count, max_epochs = _f8(table.duration), _f8(root), _f8(root_count), int(max_epochs)
             out["stats"] = numpy.zeros(n_c, dtype=TRANSIT_STATS_DTYPE)
             assert out["stats"].dtype.itemsize == ctypes.sizeof(TransitStats)
             out["per_transit"] = numpy.empty((n_c, len(PER_TRANSIT_FIELDS), max_epochs)) if per_transit else None
             out["n_epochs"] = numpy.empty(n_c, dtype=numpy.int64) if per_transit else None
-            args += [_dp(row_duration), float(fill_factor), _dp(root), len(root), out["stats"].ctypes.data_as(ctypes.c_void_p),
-                     max_epochs, None if out["per_transit"] is None else _dp(out["per_transit"]),
+            args += [_dp(row_duration), float(fill_factor), _dp(root), _dp(root_count), min(len(root), len(root_count)),
+                     out["stats"].ctypes.data_as(ctypes.c_void_p), max_epochs,
+                     None if out["per_transit"] is None else _dp(out["per_transit"]),
                      None if out["n_epochs"] is None else _ip(out["n_epochs"])]
             entry = self._lib.tls_power_batch_stats
             if models is not None:
@@ -1203,11 +1219,12 @@ class Context(object):
                 entry = self._lib.tls_power_batch_models
         if peaks is not None:
             if statistics is None and peak_fits is not None:   # (out_stats NULL: the fits read the inputs all the same)
-                fill_factor, root, max_epochs = peak_fits
-                row_duration, root = _f8(table.duration), _f8(root)
-                args += [_dp(row_duration), float(fill_factor), _dp(root), len(root), None, int(max_epochs), None, None]
+                fill_factor, root, root_count, max_epochs = peak_fits
+                row_duration, root, root_count = _f8(table.duration), _f8(root), _f8(root_count)
+                args += [_dp(row_duration), float(fill_factor), _dp(root), _dp(root_count),
+                         min(len(root), len(root_count)), None, int(max_epochs), None, None]
             elif statistics is None:   # (out_stats NULL: no statistics, their inputs are not read)
-                args += [None, 0.0, None, 0, None, 1, None, None]
+                args += [None, 0.0, None, None, 0, None, 1, None, None]
             k, sep, ratios, low = peaks
             out["peaks"] = numpy.zeros((n_c, k), dtype=PEAK_DTYPE)
             assert PEAK_DTYPE.itemsize == ctypes.sizeof(Peak)
@@ -1230,22 +1247,23 @@ class Context(object):
         return out
 
     def debug_transit_stats(self, y_batch, period, T0, best_row, depth, no_fit, index_power, power, row_duration,
-                            fill_factor, root, max_epochs):
+                            fill_factor, root, max_epochs, root_count=None):
         """Developer/test entry: the statistics kernel of power_batch_stats on the prepared plan (prepare()) with injected
         picks -- period, T0, best_row, depth, no_fit, index_power per curve, power [n_curves, n_periods] -- and flux
-        y_batch [n_curves, n]; (stats, per_transit [n_curves, 6, max_epochs], n_epochs)."""
+        y_batch [n_curves, n]; root and root_count as power_batch_stats takes them; (stats, per_transit [n_curves, 6,
+        max_epochs], n_epochs)."""
         return self._debug_transit(y_batch, period, T0, best_row, depth, no_fit, index_power, power, row_duration,
-                                   fill_factor, root, max_epochs)
+                                   fill_factor, root, max_epochs, root_count=root_count)
 
     def debug_transit_models(self, y_batch, period, T0, best_row, depth, no_fit, index_power, power, row_duration,
-                             fill_factor, root, max_epochs, models, lc_cap):
+                             fill_factor, root, max_epochs, models, lc_cap, root_count=None):
         """Developer/test entry: the statistics and model stages of power_batch_stats(models=...) on injected picks, as
         debug_transit_stats; (stats, per_transit, n_epochs, folded, model_folded, lightcurve, lc_len)."""
         return self._debug_transit(y_batch, period, T0, best_row, depth, no_fit, index_power, power, row_duration,
-                                   fill_factor, root, max_epochs, models, lc_cap)
+                                   fill_factor, root, max_epochs, models, lc_cap, root_count=root_count)
 
     def _debug_transit(self, y_batch, period, T0, best_row, depth, no_fit, index_power, power, row_duration, fill_factor,
-                       root, max_epochs, models=None, lc_cap=0):
+                       root, max_epochs, models=None, lc_cap=0, root_count=None):
         """tls_debug_transit_stats, or with models tls_debug_transit_models."""
         y_batch = numpy.ascontiguousarray(y_batch, dtype=numpy.float64)
         power = numpy.ascontiguousarray(power, dtype=numpy.float64)
@@ -1255,12 +1273,15 @@ class Context(object):
         period, T0, depth = (_f8(numpy.broadcast_to(v, (n_c,))) for v in (period, T0, depth))
         best_row, no_fit, index_power = (_i8(numpy.broadcast_to(v, (n_c,))) for v in (best_row, no_fit, index_power))
         row_duration, root, max_epochs = _f8(row_duration), _f8(root), int(max_epochs)
+        root_count = _root_count(root, root_count)
+        n_root = min(len(root), len(root_count))
         stats = numpy.zeros(n_c, dtype=TRANSIT_STATS_DTYPE)
         rows = numpy.empty((n_c, len(PER_TRANSIT_FIELDS), max_epochs))
         n_epochs = numpy.empty(n_c, dtype=numpy.int64)
         args = [self._h, _dp(y_batch), n_c, _dp(period), _dp(T0), _ip(best_row), _dp(depth), _ip(no_fit), _ip(index_power),
-                _dp(power), _dp(row_duration), len(row_duration), float(fill_factor), _dp(root), len(root), max_epochs,
-                stats.ctypes.data_as(ctypes.c_void_p), _dp(rows), _ip(n_epochs)]
+                _dp(power), _dp(row_duration), len(row_duration), float(fill_factor), _dp(root),
+                _dp(root_count), n_root, max_epochs, stats.ctypes.data_as(ctypes.c_void_p),
+                _dp(rows), _ip(n_epochs)]
         out = () if models is None else _model_outputs(n_c, y_batch.shape[1], lc_cap)
         self._invalidate_results()
         if models is None:
@@ -1270,10 +1291,11 @@ class Context(object):
         return (stats, rows, n_epochs) + out
 
     def debug_peak_fits(self, y_batch, peaks, n_peaks, power, row_duration, fill_factor, root, max_epochs, with_fits=False,
-                        phase_scan=None):
+                        phase_scan=None, root_count=None):
         """Developer/test entry: the peak-fit stage of power_batch(peaks=K, peak_fits=True) on the prepared plan (prepare())
         with injected peak records (tls_debug_peak_fits) -- flux y_batch [n_curves, n], peaks [n_curves, k] with the fields
-        of PEAK_DTYPE (more are ignored), n_peaks [n_curves], the detrended power [n_curves, n_periods]: the fits
+        of PEAK_DTYPE (more are ignored), n_peaks [n_curves], the detrended power [n_curves, n_periods], root and
+        root_count (a keyword) as power_batch_stats takes them: the fits
         (PEAK_FIT_DTYPE [n_curves, k]); with_fits: also every fit's trial epochs and residuals [n_curves, k, n] and n_epochs
         [n_curves, k].  phase_scan = (max_bins, min_count), without with_fits: (fits, scans) with the fits' phase scans
         (PHASE_SCAN_DTYPE [n_curves, k]) as power_batch(phase_scan=True) runs them (tls_debug_peak_phase_scans)."""
@@ -1291,6 +1313,9 @@ class Context(object):
             rec[name] = peaks[name]
         n_peaks = _i8(numpy.broadcast_to(n_peaks, (n_c,)))
         row_duration, root = _f8(row_duration), _f8(root)
+        root_count = _root_count(root, root_count)
+        n_root = min(len(root), len(root_count))
+        rc_p = _dp(root_count)
         fits = numpy.zeros((n_c, k), dtype=PEAK_FIT_DTYPE)
         assert PEAK_FIT_DTYPE.itemsize == ctypes.sizeof(PeakFit)
         n = y_batch.shape[1]
@@ -1305,12 +1330,13 @@ class Context(object):
             scans = numpy.zeros((n_c, k), dtype=PHASE_SCAN_DTYPE)
             self._check(self._lib.tls_debug_peak_phase_scans(
                 self._h, _dp(y_batch), n_c, rec.ctypes.data_as(ctypes.c_void_p), _ip(n_peaks), k, _dp(power), _dp(row_duration),
-                len(row_duration), float(fill_factor), _dp(root), len(root), int(max_epochs),
+                len(row_duration), float(fill_factor), _dp(root), rc_p, n_root, int(max_epochs),
                 fits.ctypes.data_as(ctypes.c_void_p), max_bins, min_count, scans.ctypes.data_as(ctypes.c_void_p)))
             return fits, scans
         self._check(self._lib.tls_debug_peak_fits(
             self._h, _dp(y_batch), n_c, rec.ctypes.data_as(ctypes.c_void_p), _ip(n_peaks), k, _dp(power), _dp(row_duration),
-            len(row_duration), float(fill_factor), _dp(root), len(root), int(max_epochs), fits.ctypes.data_as(ctypes.c_void_p),
+            len(row_duration), float(fill_factor), _dp(root), rc_p, n_root, int(max_epochs),
+            fits.ctypes.data_as(ctypes.c_void_p),
             None if epochs is None else _dp(epochs), None if residuals is None else _dp(residuals),
             None if n_epochs is None else _ip(n_epochs)))
         return (fits, epochs, residuals, n_epochs) if with_fits else fits

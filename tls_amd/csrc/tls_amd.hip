@@ -200,7 +200,7 @@ struct tls_ctx {
     DevBuf<double> d_frot;          // ... its rotation path: per fit flux | phases | quotients of the base order, state
     DevBuf<int> d_frperm;           // ... and the base order itself
     DevBuf<double> d_spec;                                         // SDE spectra: SR | power_raw | power | sde[2] | chi2 copy
-    DevBuf<double> d_tstats;        // tls_power_batch_stats: row durations | root table | per-curve scratch of one group
+    DevBuf<double> d_tstats;        // tls_power_batch_stats: row durations | the two root tables | per-curve scratch of one group
     DevBuf<int> d_tranges;          // ... and every epoch's chunk start | stop | offset
     DevBuf<double> d_models;        // tls_power_batch_models: template curve | per-curve scratch of one group | results of one group
     DevBuf<double> d_inject;        // tls_inject_transits: t | base rows | injected rows | constants of one slab
@@ -976,25 +976,29 @@ int enqueue_post_search(tls_ctx* ctx, const PostSearchBufs& b, int64_t gc, const
 struct StatsRequest {
     const double* row_duration = nullptr; int64_t n_rows = 0;   // lc_cache_overview["duration"] of every template row
     double fill_factor = 0;
-    const double* root = nullptr; int64_t n_root = 0;           // float(k) ** 0.5, k < n_root (n_root > n)
+    // float(k) ** 0.5 (snr, pink-noise width, depth_mean_std) and numpy.sum(k) ** 0.5 (the odd and even depth errors),
+    // k < n_root (n_root > n), each as the caller's Python and numpy form it
+    const double* root = nullptr; const double* root_count = nullptr; int64_t n_root = 0;
     int64_t max_epochs = 1;
     tls_transit_stats* out = nullptr; double* out_per_transit = nullptr; int64_t* out_n_epochs = nullptr;
     size_t words() const { return (size_t)tlsdev::kTransitStats + (size_t)tlsdev::kPerTransitRows * (size_t)max_epochs; }
 };
 static_assert(sizeof(tls_transit_stats) == tlsdev::kTransitStats * 8, "tls_transit_stats is the kernel's record");
 
-struct StatsBufs { double *row_duration = nullptr, *root = nullptr, *scratch = nullptr; int* ranges = nullptr; size_t scratch_stride = 0; };
+struct StatsBufs { double *row_duration = nullptr, *root = nullptr, *root_count = nullptr, *scratch = nullptr; int* ranges = nullptr; size_t scratch_stride = 0; };
 
 // device inputs of a request (uploaded once per call) and the O(group x n) scratch of one group
 int reserve_transit_stats(tls_ctx* ctx, const StatsRequest& sr, int64_t group, int64_t n, StatsBufs& sb) {
     sb.scratch_stride = 4 * (size_t)n + 1;   // flux_ootr | concat(odd, even) | pink terms | running sums
-    const size_t ins = (size_t)sr.n_rows + (size_t)sr.n_root;
+    const size_t ins = (size_t)sr.n_rows + 2 * (size_t)sr.n_root;
     TLS_HIP(ctx, ctx->d_tstats.reserve(ins + (size_t)group * sb.scratch_stride));
     TLS_HIP(ctx, ctx->d_tranges.reserve((size_t)group * 3 * (size_t)sr.max_epochs));
-    sb.row_duration = ctx->d_tstats.ptr; sb.root = sb.row_duration + sr.n_rows; sb.scratch = sb.root + sr.n_root;
+    sb.row_duration = ctx->d_tstats.ptr; sb.root = sb.row_duration + sr.n_rows; sb.root_count = sb.root + sr.n_root;
+    sb.scratch = sb.root_count + sr.n_root;
     sb.ranges = ctx->d_tranges.ptr;
     TLS_HIP(ctx, hipMemcpyAsync(sb.row_duration, sr.row_duration, (size_t)sr.n_rows * 8, hipMemcpyHostToDevice, ctx->stream));
     TLS_HIP(ctx, hipMemcpyAsync(sb.root, sr.root, (size_t)sr.n_root * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(sb.root_count, sr.root_count, (size_t)sr.n_root * 8, hipMemcpyHostToDevice, ctx->stream));
     return TLS_OK;
 }
 
@@ -1006,7 +1010,7 @@ int enqueue_transit_stats(tls_ctx* ctx, const PostSearchBufs& b, const StatsBufs
     a.power = ctx->d_spec.ptr + 2 * (size_t)n_periods; a.power_stride = (long long)b.spec_stride;
     a.curve = nullptr;
     a.periods = ctx->d_periods.ptr; a.n_periods = (int)n_periods;
-    a.row_duration = sb.row_duration; a.root = sb.root; a.n_root = (int)sr.n_root;
+    a.row_duration = sb.row_duration; a.root = sb.root; a.root_count = sb.root_count; a.n_root = (int)sr.n_root;
     a.fill_factor = sr.fill_factor; a.t_min = t_min; a.t_max = t_max;
     a.stats = b.stats; a.per_transit = b.per_transit;
     a.ranges = sb.ranges; a.scratch = sb.scratch; a.scratch_stride = (long long)sb.scratch_stride;
@@ -1036,9 +1040,9 @@ int read_transit_stats(tls_ctx* ctx, const StatsRequest& sr, const double* h_sta
 // what the statistics stage requires beyond tls_power_batch's arguments
 // (need_out false: the inputs alone, for the peak fits of a call that asks for no statistics of the best pick)
 int check_stats_request(tls_ctx* ctx, const StatsRequest& sr, const double* t, int64_t n, int64_t n_rows, bool need_out = true) {
-    if (!sr.row_duration || !sr.root || (need_out && !sr.out)) return fail(ctx, TLS_E_ARG, "null statistics argument");
+    if (!sr.row_duration || !sr.root || !sr.root_count || (need_out && !sr.out)) return fail(ctx, TLS_E_ARG, "null statistics argument");
     if (sr.n_rows != n_rows) return fail(ctx, TLS_E_ARG, "one fractional duration per template row wanted");
-    if (sr.n_root < n + 1) return fail(ctx, TLS_E_ARG, "the k ** 0.5 table must cover k = 0 .. n");
+    if (sr.n_root < n + 1) return fail(ctx, TLS_E_ARG, "the two k ** 0.5 tables must cover k = 0 .. n");
     if (sr.max_epochs < 1 || sr.max_epochs > 100000000) return fail(ctx, TLS_E_ARG, "max_epochs out of range [1, 1e8]");
     if (n > 0x3fffffff) return fail(ctx, TLS_E_ARG, "n too large for the statistics stage");
     for (int64_t i = 1; i < n; ++i)
@@ -1056,9 +1060,11 @@ struct ModelsRequest {
     size_t stride(int64_t n) const { return (size_t)tlsdev::kModelsHeader + 4 * (size_t)n + 2 * (size_t)lc_cap; }
 };
 // the two requests from the flat arguments of the C entry points
-StatsRequest stats_request(const double* row_duration, int64_t n_rows, double fill_factor, const double* root, int64_t n_root,
+StatsRequest stats_request(const double* row_duration, int64_t n_rows, double fill_factor, const double* root,
+                           const double* root_count, int64_t n_root,
                            int64_t max_epochs, tls_transit_stats* out, double* out_per_transit, int64_t* out_n_epochs) {
-    return StatsRequest{row_duration, n_rows, fill_factor, root, n_root, max_epochs, out, out_per_transit, out_n_epochs};
+    return StatsRequest{row_duration, n_rows, fill_factor, root, root_count, n_root, max_epochs, out, out_per_transit,
+                        out_n_epochs};
 }
 ModelsRequest models_request(const double* curve_t, const double* curve_f, int64_t curve_n, double curve_lo, double curve_hi,
                              double maxw, int64_t lc_cap, double* out_folded, double* out_model_folded, double* out_lc,
@@ -1261,7 +1267,7 @@ int enqueue_phase_scan(tls_ctx* ctx, const PhaseScanRequest& ps, int64_t fits, c
 // kernel, on arrays of its own (tls_peak_fits.hip.h, DESIGN.md "Peak fits")
 struct PeakFitsRequest {
     int64_t k = 0;
-    const StatsRequest* inputs = nullptr;      // row_duration, fill_factor, root, max_epochs (its outputs are not read)
+    const StatsRequest* inputs = nullptr;      // row_duration, fill_factor, root, root_count, max_epochs (its outputs are not read)
     tls_peak_fit* out = nullptr;               // [n_curves][k]
     // tls_debug_peak_fits: every fit's trial epochs and residuals [n_curves][k][n], n_epochs [n_curves][k]
     double* out_epochs = nullptr; double* out_residuals = nullptr; int64_t* out_n_epochs = nullptr;
@@ -1333,7 +1339,7 @@ int enqueue_peak_fits(tls_ctx* ctx, const PeakFitBufs& fb, const PeakFitsRequest
         a.t = ctx->d_t.ptr; a.y = d_y; a.pick = fb.pick; a.T0 = T0 + f0;
         a.power = d_power; a.power_stride = (long long)power_stride; a.curve = fb.curve;
         a.periods = ctx->d_periods.ptr; a.n_periods = (int)n_periods;
-        a.row_duration = sb.row_duration; a.root = sb.root; a.n_root = (int)in.n_root;
+        a.row_duration = sb.row_duration; a.root = sb.root; a.root_count = sb.root_count; a.n_root = (int)in.n_root;
         a.fill_factor = in.fill_factor; a.t_min = t_min; a.t_max = t_max;
         a.stats = stats + (size_t)f0 * tlsdev::kTransitStats; a.per_transit = fb.per_transit;
         a.ranges = fb.ranges; a.scratch = fb.scratch; a.scratch_stride = (long long)fb.scratch_stride;
@@ -2612,7 +2618,8 @@ int tls_debug_post_search(tls_ctx* ctx, const double* y, int64_t n_curves, const
 static int debug_transit_impl(tls_ctx* ctx, const double* y, int64_t n_curves, const double* period, const double* T0,
                               const int64_t* best_row, const double* depth, const int64_t* no_fit, const int64_t* index_power,
                               const double* power, const double* row_duration, int64_t n_rows, double fill_factor,
-                              const double* root, int64_t n_root, int64_t max_epochs, tls_transit_stats* out_stats,
+                              const double* root, const double* root_count, int64_t n_root, int64_t max_epochs,
+                              tls_transit_stats* out_stats,
                               double* out_per_transit, int64_t* out_n_epochs, const ModelsRequest* mr) {
     if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
     if (!ctx->prepared || !ctx->key.valid) return fail(ctx, TLS_E_STATE, "tls_debug_transit_stats before tls_prepare");
@@ -2622,7 +2629,8 @@ static int debug_transit_impl(tls_ctx* ctx, const double* y, int64_t n_curves, c
     const PlanKey& k = ctx->key;
     const int64_t n = k.n, n_periods = k.n_periods;
     if (n_periods < 1) return fail(ctx, TLS_E_ARG, "tls_debug_transit_stats needs at least one period");
-    const StatsRequest sr = stats_request(row_duration, n_rows, fill_factor, root, n_root, max_epochs, out_stats, out_per_transit,
+    const StatsRequest sr = stats_request(row_duration, n_rows, fill_factor, root, root_count, n_root, max_epochs, out_stats,
+                                          out_per_transit,
                                           out_n_epochs);
     int rc = check_stats_request(ctx, sr, k.t.data(), n, k.n_rows);
     if (rc || (mr && (rc = check_models_request(ctx, *mr, n)))) return rc;
@@ -2675,29 +2683,32 @@ static int debug_transit_impl(tls_ctx* ctx, const double* y, int64_t n_curves, c
 int tls_debug_transit_stats(tls_ctx* ctx, const double* y, int64_t n_curves, const double* period, const double* T0,
                             const int64_t* best_row, const double* depth, const int64_t* no_fit, const int64_t* index_power,
                             const double* power, const double* row_duration, int64_t n_rows, double fill_factor,
-                            const double* root, int64_t n_root, int64_t max_epochs, tls_transit_stats* out_stats,
+                            const double* root, const double* root_count, int64_t n_root, int64_t max_epochs,
+                            tls_transit_stats* out_stats,
                             double* out_per_transit, int64_t* out_n_epochs) {
     return debug_transit_impl(ctx, y, n_curves, period, T0, best_row, depth, no_fit, index_power, power, row_duration, n_rows,
-                              fill_factor, root, n_root, max_epochs, out_stats, out_per_transit, out_n_epochs, nullptr);
+                              fill_factor, root, root_count, n_root, max_epochs, out_stats, out_per_transit, out_n_epochs, nullptr);
 }
 
 int tls_debug_transit_models(tls_ctx* ctx, const double* y, int64_t n_curves, const double* period, const double* T0,
                              const int64_t* best_row, const double* depth, const int64_t* no_fit, const int64_t* index_power,
                              const double* power, const double* row_duration, int64_t n_rows, double fill_factor,
-                             const double* root, int64_t n_root, int64_t max_epochs, tls_transit_stats* out_stats,
+                             const double* root, const double* root_count, int64_t n_root, int64_t max_epochs,
+                             tls_transit_stats* out_stats,
                              double* out_per_transit, int64_t* out_n_epochs, const double* curve_t, const double* curve_f,
                              int64_t curve_n, double curve_lo, double curve_hi, double maxw, int64_t lc_cap,
                              double* out_folded, double* out_model_folded, double* out_lc, int64_t* out_lc_len) {
     const ModelsRequest mr = models_request(curve_t, curve_f, curve_n, curve_lo, curve_hi, maxw, lc_cap, out_folded,
                                             out_model_folded, out_lc, out_lc_len);
     return debug_transit_impl(ctx, y, n_curves, period, T0, best_row, depth, no_fit, index_power, power, row_duration, n_rows,
-                              fill_factor, root, n_root, max_epochs, out_stats, out_per_transit, out_n_epochs, &mr);
+                              fill_factor, root, root_count, n_root, max_epochs, out_stats, out_per_transit, out_n_epochs, &mr);
 }
 
 // tls_debug_peak_fits; ps: tls_debug_peak_phase_scans, the fits' phase scans as well
 static int debug_peak_fits_impl(tls_ctx* ctx, const double* y, int64_t n_curves, const tls_peak* peaks, const int64_t* n_peaks,
                                 int64_t k, const double* power, const double* row_duration, int64_t n_rows, double fill_factor,
-                                const double* root, int64_t n_root, int64_t max_epochs, tls_peak_fit* out_fits, double* out_epochs,
+                                const double* root, const double* root_count, int64_t n_root, int64_t max_epochs,
+                                tls_peak_fit* out_fits, double* out_epochs,
                                 double* out_residuals, int64_t* out_n_epochs, const PhaseScanRequest* ps) {
     if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
     if (!ctx->prepared || !ctx->key.valid) return fail(ctx, TLS_E_STATE, "tls_debug_peak_fits before tls_prepare");
@@ -2708,7 +2719,8 @@ static int debug_peak_fits_impl(tls_ctx* ctx, const double* y, int64_t n_curves,
     const PlanKey& key = ctx->key;
     const int64_t n = key.n, n_periods = key.n_periods;
     if (n_periods < 1) return fail(ctx, TLS_E_ARG, "tls_debug_peak_fits needs at least one period");
-    const StatsRequest sr = stats_request(row_duration, n_rows, fill_factor, root, n_root, max_epochs, nullptr, nullptr, nullptr);
+    const StatsRequest sr = stats_request(row_duration, n_rows, fill_factor, root, root_count, n_root, max_epochs, nullptr,
+                                          nullptr, nullptr);
     int rc = check_stats_request(ctx, sr, key.t.data(), n, key.n_rows, false);
     if (rc) return rc;
     const size_t np = (size_t)n_periods, nn = (size_t)n, gc = (size_t)n_curves, kk = (size_t)k;
@@ -2761,15 +2773,18 @@ static int debug_peak_fits_impl(tls_ctx* ctx, const double* y, int64_t n_curves,
 
 int tls_debug_peak_fits(tls_ctx* ctx, const double* y, int64_t n_curves, const tls_peak* peaks, const int64_t* n_peaks,
                         int64_t k, const double* power, const double* row_duration, int64_t n_rows, double fill_factor,
-                        const double* root, int64_t n_root, int64_t max_epochs, tls_peak_fit* out_fits, double* out_epochs,
+                        const double* root, const double* root_count, int64_t n_root, int64_t max_epochs, tls_peak_fit* out_fits,
+                        double* out_epochs,
                         double* out_residuals, int64_t* out_n_epochs) {
-    return debug_peak_fits_impl(ctx, y, n_curves, peaks, n_peaks, k, power, row_duration, n_rows, fill_factor, root, n_root,
+    return debug_peak_fits_impl(ctx, y, n_curves, peaks, n_peaks, k, power, row_duration, n_rows, fill_factor, root, root_count,
+                                n_root,
                                 max_epochs, out_fits, out_epochs, out_residuals, out_n_epochs, nullptr);
 }
 
 int tls_debug_peak_phase_scans(tls_ctx* ctx, const double* y, int64_t n_curves, const tls_peak* peaks, const int64_t* n_peaks,
                                int64_t k, const double* power, const double* row_duration, int64_t n_rows, double fill_factor,
-                               const double* root, int64_t n_root, int64_t max_epochs, tls_peak_fit* out_fits,
+                               const double* root, const double* root_count, int64_t n_root, int64_t max_epochs,
+                               tls_peak_fit* out_fits,
                                int64_t max_bins, int64_t min_count, tls_phase_record* out_scans) {
     if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
     if (!out_scans) return fail(ctx, TLS_E_ARG, "null argument");
@@ -2777,7 +2792,8 @@ int tls_debug_peak_phase_scans(tls_ctx* ctx, const double* y, int64_t n_curves, 
     ps.max_bins = max_bins; ps.min_count = min_count; ps.out = out_scans;
     const int rc = check_phase_scan_request(ctx, ps);
     if (rc) return rc;
-    return debug_peak_fits_impl(ctx, y, n_curves, peaks, n_peaks, k, power, row_duration, n_rows, fill_factor, root, n_root,
+    return debug_peak_fits_impl(ctx, y, n_curves, peaks, n_peaks, k, power, row_duration, n_rows, fill_factor, root, root_count,
+                                n_root,
                                 max_epochs, out_fits, nullptr, nullptr, nullptr, &ps);
 }
 
@@ -3017,11 +3033,12 @@ int tls_power_batch_stats(tls_ctx* ctx, const double* t, const double* y, const 
                           const double* periods, int64_t n_periods, const tls_template* tmpl, const tls_params* params,
                           int64_t median_kernel, tls_power_summary* out_summary, double* out_chi2, int64_t* out_row,
                           double* out_depth, double* out_power, double* out_SR, double* out_power_raw,
-                          const double* row_duration, double fill_factor, const double* root, int64_t n_root,
+                          const double* row_duration, double fill_factor, const double* root, const double* root_count,
+                          int64_t n_root,
                           tls_transit_stats* out_stats, int64_t max_epochs, double* out_per_transit, int64_t* out_n_epochs) {
     if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
     if (!t || !tmpl) return fail(ctx, TLS_E_ARG, "null argument");
-    const StatsRequest sr = stats_request(row_duration, tmpl->n_rows, fill_factor, root, n_root, max_epochs, out_stats,
+    const StatsRequest sr = stats_request(row_duration, tmpl->n_rows, fill_factor, root, root_count, n_root, max_epochs, out_stats,
                                           out_per_transit, out_n_epochs);
     const int rc = check_stats_request(ctx, sr, t, n, tmpl->n_rows);
     if (rc) return rc;
@@ -3033,14 +3050,15 @@ int tls_power_batch_models(tls_ctx* ctx, const double* t, const double* y, const
                            const double* periods, int64_t n_periods, const tls_template* tmpl, const tls_params* params,
                            int64_t median_kernel, tls_power_summary* out_summary, double* out_chi2, int64_t* out_row,
                            double* out_depth, double* out_power, double* out_SR, double* out_power_raw,
-                           const double* row_duration, double fill_factor, const double* root, int64_t n_root,
+                           const double* row_duration, double fill_factor, const double* root, const double* root_count,
+                           int64_t n_root,
                            tls_transit_stats* out_stats, int64_t max_epochs, double* out_per_transit, int64_t* out_n_epochs,
                            const double* curve_t, const double* curve_f, int64_t curve_n, double curve_lo, double curve_hi,
                            double maxw, int64_t lc_cap, double* out_folded, double* out_model_folded, double* out_lc,
                            int64_t* out_lc_len) {
     if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
     if (!t || !tmpl) return fail(ctx, TLS_E_ARG, "null argument");
-    const StatsRequest sr = stats_request(row_duration, tmpl->n_rows, fill_factor, root, n_root, max_epochs, out_stats,
+    const StatsRequest sr = stats_request(row_duration, tmpl->n_rows, fill_factor, root, root_count, n_root, max_epochs, out_stats,
                                           out_per_transit, out_n_epochs);
     const ModelsRequest mr = models_request(curve_t, curve_f, curve_n, curve_lo, curve_hi, maxw, lc_cap, out_folded,
                                             out_model_folded, out_lc, out_lc_len);
@@ -3055,7 +3073,8 @@ int tls_power_batch_peaks(tls_ctx* ctx, const double* t, const double* y, const 
                           const double* periods, int64_t n_periods, const tls_template* tmpl, const tls_params* params,
                           int64_t median_kernel, tls_power_summary* out_summary, double* out_chi2, int64_t* out_row,
                           double* out_depth, double* out_power, double* out_SR, double* out_power_raw,
-                          const double* row_duration, double fill_factor, const double* root, int64_t n_root,
+                          const double* row_duration, double fill_factor, const double* root, const double* root_count,
+                          int64_t n_root,
                           tls_transit_stats* out_stats, int64_t max_epochs, double* out_per_transit, int64_t* out_n_epochs,
                           int64_t k, double min_separation, const double* ratios, int64_t n_ratios, double min_power,
                           tls_peak* out_peaks, int64_t* out_n_peaks) {
@@ -3069,7 +3088,8 @@ int tls_power_batch_peaks(tls_ctx* ctx, const double* t, const double* y, const 
     if (n_curves > 0 && (!out_peaks || !out_n_peaks)) return fail(ctx, TLS_E_ARG, "null peaks argument");
     StatsRequest sr;
     if (out_stats) {   // (no statistics wanted: their inputs are not read)
-        sr = stats_request(row_duration, tmpl->n_rows, fill_factor, root, n_root, max_epochs, out_stats, out_per_transit, out_n_epochs);
+        sr = stats_request(row_duration, tmpl->n_rows, fill_factor, root, root_count, n_root, max_epochs, out_stats,
+                           out_per_transit, out_n_epochs);
         if ((rc = check_stats_request(ctx, sr, t, n, tmpl->n_rows))) return rc;
     }
     return end_batch(ctx, power_batch_impl(ctx, t, y, dy, n, n_curves, periods, n_periods, tmpl, params, median_kernel,
@@ -3081,7 +3101,8 @@ int tls_power_batch_peak_fits(tls_ctx* ctx, const double* t, const double* y, co
                               const double* periods, int64_t n_periods, const tls_template* tmpl, const tls_params* params,
                               int64_t median_kernel, tls_power_summary* out_summary, double* out_chi2, int64_t* out_row,
                               double* out_depth, double* out_power, double* out_SR, double* out_power_raw,
-                              const double* row_duration, double fill_factor, const double* root, int64_t n_root,
+                              const double* row_duration, double fill_factor, const double* root, const double* root_count,
+                              int64_t n_root,
                               tls_transit_stats* out_stats, int64_t max_epochs, double* out_per_transit, int64_t* out_n_epochs,
                               int64_t k, double min_separation, const double* ratios, int64_t n_ratios, double min_power,
                               tls_peak* out_peaks, int64_t* out_n_peaks, tls_peak_fit* out_fits) {
@@ -3094,7 +3115,7 @@ int tls_power_batch_peak_fits(tls_ctx* ctx, const double* t, const double* y, co
     if (rc) return rc;
     if (n_curves > 0 && (!out_peaks || !out_n_peaks || !out_fits)) return fail(ctx, TLS_E_ARG, "null peaks argument");
     // (the fits read the statistics inputs whether or not the best pick's statistics are wanted)
-    const StatsRequest sr = stats_request(row_duration, tmpl->n_rows, fill_factor, root, n_root, max_epochs, out_stats,
+    const StatsRequest sr = stats_request(row_duration, tmpl->n_rows, fill_factor, root, root_count, n_root, max_epochs, out_stats,
                                           out_stats ? out_per_transit : nullptr, out_stats ? out_n_epochs : nullptr);
     if ((rc = check_stats_request(ctx, sr, t, n, tmpl->n_rows, false))) return rc;
     PeakFitsRequest pf;
@@ -3108,7 +3129,8 @@ int tls_power_batch_phase_scan(tls_ctx* ctx, const double* t, const double* y, c
                                const double* periods, int64_t n_periods, const tls_template* tmpl, const tls_params* params,
                                int64_t median_kernel, tls_power_summary* out_summary, double* out_chi2, int64_t* out_row,
                                double* out_depth, double* out_power, double* out_SR, double* out_power_raw,
-                               const double* row_duration, double fill_factor, const double* root, int64_t n_root,
+                               const double* row_duration, double fill_factor, const double* root, const double* root_count,
+                               int64_t n_root,
                                tls_transit_stats* out_stats, int64_t max_epochs, double* out_per_transit, int64_t* out_n_epochs,
                                int64_t k, double min_separation, const double* ratios, int64_t n_ratios, double min_power,
                                tls_peak* out_peaks, int64_t* out_n_peaks, tls_peak_fit* out_fits, int64_t max_bins,
@@ -3124,7 +3146,7 @@ int tls_power_batch_phase_scan(tls_ctx* ctx, const double* t, const double* y, c
     ps.max_bins = max_bins; ps.min_count = min_count; ps.out = out_scans;
     if ((rc = check_phase_scan_request(ctx, ps))) return rc;
     if (n_curves > 0 && (!out_peaks || !out_n_peaks || !out_fits || !out_scans)) return fail(ctx, TLS_E_ARG, "null peaks argument");
-    const StatsRequest sr = stats_request(row_duration, tmpl->n_rows, fill_factor, root, n_root, max_epochs, out_stats,
+    const StatsRequest sr = stats_request(row_duration, tmpl->n_rows, fill_factor, root, root_count, n_root, max_epochs, out_stats,
                                           out_stats ? out_per_transit : nullptr, out_stats ? out_n_epochs : nullptr);
     if ((rc = check_stats_request(ctx, sr, t, n, tmpl->n_rows, false))) return rc;
     PeakFitsRequest pf;

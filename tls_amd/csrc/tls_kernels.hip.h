@@ -3817,7 +3817,11 @@ __global__ void __launch_bounds__(1024) tls_cumsum_kernel(const double* f, doubl
 // chunk of every epoch (two binary searches on ascending t), per-epoch count / mean / population std, the odd and even
 // concatenations, the out-of-transit flux (transit_mask's order kept by a ballot compaction), pink noise, SNR, counts and
 // the period uncertainty.  Every numpy.mean / numpy.std is numpy_pairwise_sum in numpy's association, squares rounded before
-// they are summed; every `k ** 0.5` Python forms from a count is root[k], a table the caller built with Python's pow.
+// they are summed; every `k ** 0.5` power() forms from a count is read from a table the caller built with the expression
+// power() uses: root[k] = float(k) ** 0.5 (Python's pow: `len(x) ** 0.5` of snr, `width ** 0.5` of the pink noise, and
+// numpy.sum(per_transit_count) ** 0.5 of depth_mean_std, a float64 power that equals it) and root_count[k] =
+// numpy.sum(k) ** 0.5 (the power of a numpy INTEGER scalar, which the odd and even depth errors divide by: one ulp from
+// root[k] at some counts, a set that belongs to the caller's numpy build).
 constexpr int kTransitStats = 16;      // doubles of one tls_transit_stats record
 constexpr int kPerTransitRows = 6;     // transit_times | per_transit_count | transit_depths | ..._uncertainties | snr | snr_pink
 constexpr int kExactSegments = 512;    // stats._EXACT_SEGMENTS: non-empty epochs up to which power() sums each chunk on its own
@@ -3828,7 +3832,8 @@ struct TransitStatsArgs {
     const int* curve;                              // nullptr, or record c reads flux and power of curve curve[c] (the peak-fit stage)
     const double* periods; int n_periods;
     const double* row_duration;                    // lc_cache_overview["duration"] of every template row
-    const double* root; int n_root;                // root[k] = float(k) ** 0.5
+    const double* root; const double* root_count;  // root[k] = float(k) ** 0.5, root_count[k] = numpy.sum(k) ** 0.5
+    int n_root;                                    // entries of each, > n
     double fill_factor, t_min, t_max;
     double* stats;                                 // [n_curves][kTransitStats]
     double* per_transit;                           // [n_curves][kPerTransitRows][max_epochs]
@@ -4062,7 +4067,10 @@ __global__ void __launch_bounds__(256) tls_transit_stats(const TransitStatsArgs 
         s_sum[2 * wave] = mean; s_sum[2 * wave + 1] = sd;
     }
     wg_sync();
+    // (every count is at most n, and every entry point refuses tables with n_root <= n -- check_stats_request, before
+    // anything is written -- so the bound below always holds; it stays so that a short table could not be read past)
     auto root = [&](long long k) { return k < a.n_root ? a.root[k] : sqrt((double)k); };
+    auto root_count = [&](long long k) { return k < a.n_root ? a.root_count[k] : sqrt((double)k); };
     const double std_ootr = s_sum[7], pink = s_pink;
     const double std_snr = L > 0 ? std_ootr : NAN;
     for (int k = tid; k < maxE; k += nt) {
@@ -4078,8 +4086,8 @@ __global__ void __launch_bounds__(256) tls_transit_stats(const TransitStatsArgs 
     if (tid == 0) {
         const long long M_even = M_all - M_odd;
         const double mean_odd = s_sum[0], mean_even = s_sum[2], depth_mean = s_sum[4];
-        const double err_odd = M_odd > 0 ? s_sum[1] / root(M_odd) : NAN;
-        const double err_even = M_even > 0 ? s_sum[3] / root(M_even) : NAN;
+        const double err_odd = M_odd > 0 ? s_sum[1] / root_count(M_odd) : NAN;
+        const double err_even = M_even > 0 ? s_sum[3] / root_count(M_even) : NAN;
         st[1] = d;
         st[2] = depth_mean; st[3] = s_sum[5] / root(M_all);
         st[4] = mean_even; st[5] = err_even; st[6] = mean_odd; st[7] = err_odd;

@@ -282,6 +282,22 @@ def _mean_and_err(values):
     return numpy.mean(values), numpy.std(values) / numpy.sum(len(values)) ** (0.5)
 
 
+def count_roots(n):
+    """The two forms of k ** 0.5 that power() takes of a count, as tables for k = 0 .. n (the statistics kernel reads them):
+
+        root[k]        float(k) ** 0.5, Python's pow: `len(all_flux) ** 0.5` of snr, `width ** 0.5` of pink_noise, and
+                       numpy.sum(per_transit_count) ** 0.5 of depth_mean_std (a float64 power, the same value)
+        root_count[k]  numpy.sum(k) ** 0.5, the power of a numpy INTEGER scalar, which _mean_and_err divides by
+
+    The two differ by one ulp at some k (about one in twenty under numpy 2 with AVX-512; which ones belongs to the numpy
+    build and the CPU it dispatches for), so both are formed here, by the running Python and numpy.  root_count is the
+    power of an integer ARRAY, which numpy evaluates like the integer scalar's (tests/test_transit_stats_host.py compares
+    the two element by element); of a float array it would be a square root, which is not the same."""
+    root = numpy.array([float(k) ** 0.5 for k in range(n + 1)])
+    root_count = numpy.arange(n + 1, dtype=numpy.int64) ** 0.5
+    return root, root_count
+
+
 def _intransit_fluxes(t, y, transit_times, transit_duration_in_days):
     """The in-transit flux of every epoch (mid - d/2 < t < mid + d/2), as a list of arrays."""
     mid = numpy.asarray(transit_times, dtype=float)

@@ -602,15 +602,15 @@ def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=Non
         raise ValueError("oversampling_factor * %d must be an integer" % C.SDE_MEDIAN_KERNEL_SIZE)
     kw = dict(with_arrays=with_arrays, with_power=with_arrays, with_spectra=spectra, peaks=peaks)
     if statistics or peak_fits:
-        from .stats import calculate_fill_factor
+        from .stats import calculate_fill_factor, count_roots
         fill_factor = calculate_fill_factor(inp["t"])
-        root = numpy.array([float(k) ** 0.5 for k in range(len(inp["t"]) + 1)])   # (Python's pow, as power() forms k ** 0.5)
+        root, root_count = count_roots(len(inp["t"]))   # (k ** 0.5 of a count, in the two forms power() takes it)
         max_epochs = _max_epochs(inp["t"], inp["periods"])
     if statistics:
-        kw.update(statistics=(fill_factor, root, max_epochs), per_transit=per_transit,
+        kw.update(statistics=(fill_factor, root, root_count, max_epochs), per_transit=per_transit,
                   models=_model_template(inp) if models else None, lc_cap=_lc_cap(len(inp["t"]), max_epochs) if models else 0)
     if peak_fits:
-        kw.update(peak_fits=(fill_factor, root, max_epochs), phase_scan=phase_scan)
+        kw.update(peak_fits=(fill_factor, root, root_count, max_epochs), phase_scan=phase_scan)
 
     if transit_times is not None:
         from ._lib import TIMES_MAX_EPOCHS
