@@ -40,7 +40,7 @@ extern "C" {
  * (7: tls_power_batch_peak_fits, tls_debug_peak_fits), (7: tls_phase_scan, tls_power_batch_phase_scan,
  * tls_debug_peak_phase_scans), (7: tls_sysrem), (7: tls_single_transits), (7: tls_transit_times),
  * (7: tls_shape_fit), (7: tls_nudft, tls_lomb_scargle, tls_sine_test); 8: every entry that takes `root, n_root` takes a
- * second table, `root, root_count, n_root`). */
+ * second table, `root, root_count, n_root`), (8: tls_ephemeris_match). */
 #define TLS_AMD_ABI_VERSION 8
 
 #define TLS_OK 0
@@ -840,6 +840,45 @@ int tls_sine_test(tls_ctx *ctx, const double *t, const double *y, const double *
                   const double *period, const double *T0, const double *duration, const int64_t *curve, int64_t n_fits,
                   const double *harmonics, int64_t n_harmonics, double mask, tls_sine_record *out,
                   tls_sine_harmonic *out_harmonics, double *out_sums);
+
+/* ---- survey mode: the ephemeris match across the candidates of a batch ----------------------------------------------- */
+/* The test that looks across the stars (Coughlin et al. 2014): the stars of one field, camera and sector contaminate one
+ * another and share instrumental periods.  A faint star next to an eclipsing binary shows the binary's period and epoch at a
+ * diluted depth and passes every single-curve test, because the signal in its light curve is real.  Candidates on different
+ * stars that share a period (or an integer multiple of it) and an epoch are flagged, the strongest is taken as the source,
+ * and a period that many stars show with no common epoch is a systematic: that count is reported too.
+ * Candidate f is (star[f], any int64; period[f], T0[f], duration[f] in days; strength[f], larger = more likely the source).
+ * It is GOOD when period, T0, duration and strength are finite, period > 0 and duration > 0.  A bad candidate gets status 1
+ * and NaN in every other field, and is invisible to every other candidate.  For a good f and every good g != f with
+ * star[g] != star[f], with (l, s) = the member of the longer / the shorter period (equal periods: either gives the same bits):
+ *   m = rint(P_l / P_s)  (half to even);  e = m * P_s;  dP = fabs(P_l - e);  c = span / P_l;  drift = dP * c
+ *   dmax = fmax(d_f, d_g);  plim = drift_tolerance * dmax;  elim = epoch_tolerance * dmax
+ *   period_match = (m <= max_ratio) and (drift <= plim)
+ *   x = (T0_l - T0_s) / P_s;  r = rint(x);  u = x - r;  dt = fabs(u) * P_s
+ *   match = period_match and (dt <= elim)
+ * Both relations are symmetric in (f, g) bit for bit.  drift is how far the two ephemerides slide apart over the span, dt
+ * the distance of the epochs modulo the shorter period.  The record of f:
+ *   n_same = the g with period_match and m == 1 (the pile-up count);  n_period = the g with period_match;  n_match = the g
+ *   with match;  best = the index g of the match of the largest strength, the lowest index among equals, -1 without one;
+ *   best_ratio = +m if P_best >= P_f, else -m;  best_dt, best_drift = that pair's dt and drift;  best_strength =
+ *   strength[best];  child = 1 if strength[best] > strength[f], else 0;  the last five NaN without a match.
+ * Every step is one IEEE double operation, counts and an argmax with the lowest index do not depend on the order of
+ * evaluation, and no sum of doubles occurs: the record equals the numpy statement in tests/ephemeris_match_spec.py bit for
+ * bit.  Counts and indices are doubles.  10 doubles. */
+#define TLS_MATCH_MAX_CANDIDATES 1048576
+#define TLS_MATCH_MAX_RATIO 64
+typedef struct tls_match_record {
+    double status;                 /* 0 matched against the others; 1 a bad candidate */
+    double n_same, n_period, n_match;
+    double best, best_ratio, best_dt, best_drift, best_strength;
+    double child;
+} tls_match_record;
+/* The records of n candidates; out [n].  Needs no plan and no search, and leaves a prepared plan as it is.  TLS_E_ARG, before
+ * any device work, unless span is finite and > 0, both tolerances are finite and >= 0, max_ratio is in [1, 64] and
+ * n is in [0, 2^20].  n == 0 is a no-op.  All pairs are tested: the work grows with n * n. */
+int tls_ephemeris_match(tls_ctx *ctx, const int64_t *star, const double *period, const double *T0, const double *duration,
+                        const double *strength, int64_t n, double span, double drift_tolerance, double epoch_tolerance,
+                        int64_t max_ratio, tls_match_record *out);
 
 /* ---- host-only planning (no GPU needed) ------------------------------------------ */
 /* Trial cells (duration x T0 positions) each period will enumerate: the data-independent

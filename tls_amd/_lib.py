@@ -65,6 +65,14 @@ GLS_FREQ_TILE = 64
 GLS_CHUNK = 32
 SINE_MAX_HARMONICS = 8
 SINE_LANES = 256
+# include/tls_amd.h TLS_MATCH_*: the most candidates and the largest max_ratio of tls_ephemeris_match; tls_match.hip.h
+# kMatchTile (the candidates of a workgroup, and of a staged tile of the other side), kMatchTargetGroups and kMatchMaxChunks
+# (match_chunks below)
+MATCH_MAX_CANDIDATES = 1 << 20
+MATCH_MAX_RATIO = 64
+MATCH_TILE = 256
+MATCH_TARGET_GROUPS = 1024
+MATCH_MAX_CHUNKS = 16
 PEAKS_LDS_PERIODS = 1 << 20   # tls_peaks.hip.h kPeaksLdsPeriods: a longer grid keeps its alive mask in device memory, not in LDS
 
 # every symbol include/tls_amd.h declares (tests check the export list against the header)
@@ -78,6 +86,7 @@ SYMBOLS = (
     "tls_biweight_detrend", "tls_sysrem", "tls_find_peaks", "tls_power_batch_peaks", "tls_power_batch_peak_fits", "tls_debug_peak_fits",
     "tls_phase_scan", "tls_power_batch_phase_scan", "tls_debug_peak_phase_scans", "tls_single_transits",
     "tls_transit_times", "tls_shape_fit", "tls_nudft", "tls_lomb_scargle", "tls_sine_test",
+    "tls_ephemeris_match",
     "tls_comm_unique_id", "tls_comm_init", "tls_comm_destroy", "tls_comm_info", "tls_comm_allgather_results", "tls_comm_allgather_device", "tls_comm_fetch_gathered",
     "tls_comm_stage_results", "tls_comm_allgather_staged", "tls_comm_fetch_staged",
     "tls_comm_barrier", "tls_comm_max",
@@ -219,6 +228,65 @@ def phase_scan_arguments(max_bins, min_count):
     if not 1 <= int(min_count) < 2 ** 31:
         raise ValueError("phase scan: min_count must be at least 1, got %r" % (min_count,))
     return int(max_bins), int(min_count)
+
+
+# tls_match_record (include/tls_amd.h): the ephemeris match of one candidate, 10 doubles
+MATCH_FIELDS = ("status", "n_same", "n_period", "n_match", "best", "best_ratio", "best_dt", "best_drift", "best_strength", "child")
+
+
+class MatchRecord(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_double) for k in MATCH_FIELDS]
+
+
+MATCH_DTYPE = numpy.dtype([(k, "f8") for k in MATCH_FIELDS])
+# tls_match_record.status
+MATCH_MATCHED, MATCH_BAD = 0, 1
+
+
+def match_chunks(n):
+    """The first candidate of every chunk of the g range tls_ephemeris_match cuts n candidates into, and n at the end
+    (tls_match.hip.h match_chunks): whole tiles of MATCH_TILE, enough chunks to reach MATCH_TARGET_GROUPS workgroups, at most
+    MATCH_MAX_CHUNKS and at most one a tile; chunk c holds the tiles [c * tiles // chunks, (c + 1) * tiles // chunks)."""
+    n = int(n)
+    tiles = -(-n // MATCH_TILE)
+    if tiles == 0:
+        return [0]
+    chunks = min(-(-MATCH_TARGET_GROUPS // tiles), tiles, MATCH_MAX_CHUNKS)
+    return [min(n, MATCH_TILE * (c * tiles // chunks)) for c in range(chunks)] + [n]
+
+
+def ephemeris_match_arguments(star, period, T0, duration, strength, span, drift_tolerance=0.5, epoch_tolerance=0.5, max_ratio=3):
+    """What tls_ephemeris_match takes, checked as it checks them: a dict with star (int64 [M], any values), period, T0,
+    duration and strength (float64 [M], any values: a bad candidate gets status 1), M <= MATCH_MAX_CANDIDATES, span finite
+    and > 0, drift_tolerance and epoch_tolerance finite and >= 0, max_ratio an integer in [1, MATCH_MAX_RATIO].  ValueError
+    otherwise.  GPU-free."""
+    what = "ephemeris match"
+    for name, v in (("span", span), ("drift_tolerance", drift_tolerance), ("epoch_tolerance", epoch_tolerance)):
+        if isinstance(v, (bool, numpy.bool_)) or not isinstance(v, numbers.Real):
+            raise ValueError("%s: %s must be a number, got %r" % (what, name, v))
+    if not 0.0 < float(span) < numpy.inf:
+        raise ValueError("%s: span must be finite and > 0, got %r" % (what, span))
+    for name, v in (("drift_tolerance", drift_tolerance), ("epoch_tolerance", epoch_tolerance)):
+        if not 0.0 <= float(v) < numpy.inf:
+            raise ValueError("%s: %s must be finite and >= 0, got %r" % (what, name, v))
+    if isinstance(max_ratio, (bool, numpy.bool_)) or not isinstance(max_ratio, numbers.Integral) \
+            or not 1 <= int(max_ratio) <= MATCH_MAX_RATIO:
+        raise ValueError("%s: max_ratio must be an integer in [1, %d], got %r" % (what, MATCH_MAX_RATIO, max_ratio))
+    star = numpy.atleast_1d(numpy.asarray(star))
+    if star.size and star.dtype.kind not in "iu":
+        raise ValueError("%s: star must hold integers" % what)
+    try:
+        star = numpy.ascontiguousarray(star, dtype=numpy.int64)
+        period, T0, duration, strength = (numpy.ascontiguousarray(numpy.atleast_1d(numpy.asarray(v, dtype=numpy.float64)))
+                                          for v in (period, T0, duration, strength))
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("%s: star must hold 64-bit integers, period, T0, duration and strength numbers" % what)
+    if star.ndim != 1 or not star.shape == period.shape == T0.shape == duration.shape == strength.shape:
+        raise ValueError("%s: star, period, T0, duration and strength must all be [M]" % what)
+    if len(star) > MATCH_MAX_CANDIDATES:
+        raise ValueError("%s: at most %d candidates, got %d" % (what, MATCH_MAX_CANDIDATES, len(star)))
+    return dict(star=star, period=period, T0=T0, duration=duration, strength=strength, span=float(span),
+                drift_tolerance=float(drift_tolerance), epoch_tolerance=float(epoch_tolerance), max_ratio=int(max_ratio))
 
 
 # tls_single_event (include/tls_amd.h): one single-transit event, 8 doubles
@@ -803,6 +871,9 @@ def load():
     lib.tls_sine_test.restype = ci
     lib.tls_sine_test.argtypes = [vp, _c_double_p, _c_double_p, _c_double_p, i64, i64, _c_double_p, _c_double_p, _c_double_p,
                                   _c_int64_p, i64, _c_double_p, i64, dbl, ctypes.c_void_p, ctypes.c_void_p, _c_double_p]
+    lib.tls_ephemeris_match.restype = ci
+    lib.tls_ephemeris_match.argtypes = [vp, _c_int64_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, i64, dbl, dbl, dbl,
+                                        i64, ctypes.c_void_p]
     lib.tls_debug_peak_phase_scans.restype = ci
     lib.tls_debug_peak_phase_scans.argtypes = [vp, _c_double_p, i64, ctypes.c_void_p, _c_int64_p, i64, _c_double_p, _c_double_p,
                                                i64, dbl, _c_double_p, _c_double_p, i64, i64, ctypes.c_void_p, i64, i64,
@@ -1674,6 +1745,19 @@ class Context(object):
             n_fits, _dp(a["harmonics"]), nH, a["mask"], out.ctypes.data_as(ctypes.c_void_p),
             out_h.ctypes.data_as(ctypes.c_void_p), None if sums is None else _dp(sums)))
         return (out, out_h, sums) if debug else (out, out_h)
+
+    def ephemeris_match(self, star, period, T0, duration, strength, span, drift_tolerance=0.5, epoch_tolerance=0.5,
+                        max_ratio=3):
+        """The ephemeris match (tls_ephemeris_match; the statement: include/tls_amd.h, tests/ephemeris_match_spec.py) of the
+        candidates (star[f], period[f], T0[f], duration[f] in days, strength[f]) against one another: MATCH_DTYPE [M].
+        ValueError for what ephemeris_match_arguments refuses."""
+        a = ephemeris_match_arguments(star, period, T0, duration, strength, span, drift_tolerance, epoch_tolerance, max_ratio)
+        out = numpy.zeros(len(a["star"]), dtype=MATCH_DTYPE)
+        assert MATCH_DTYPE.itemsize == ctypes.sizeof(MatchRecord)
+        self._check(self._lib.tls_ephemeris_match(
+            self._h, _ip(a["star"]), _dp(a["period"]), _dp(a["T0"]), _dp(a["duration"]), _dp(a["strength"]), len(a["star"]),
+            a["span"], a["drift_tolerance"], a["epoch_tolerance"], a["max_ratio"], out.ctypes.data_as(ctypes.c_void_p)))
+        return out
 
     def debug_null_words(self, n, n_rows, seed, first_trial=0, block=None):
         """The raw Philox words [n_rows, W] tls_null_rows draws for these trials (tls_debug_null_words): white-noise

@@ -227,6 +227,8 @@ struct tls_ctx {
     DevBuf<double> d_shape;
     // tls_nudft / tls_lomb_scargle / tls_sine_test: the sums of one slab first (16-byte aligned pairs), then its rows and tables
     DevBuf<double> d_gls;
+    // tls_ephemeris_match: star | period | T0 | duration | strength | records | partial records of every chunk
+    DevBuf<double> d_match;
     // two-role slab path (series in HBM, one light curve; SearchPlan::split)
     View<unsigned int> d_tile_prefix;        // [n_periods + 1] tiles in front of work item w (queue order)
     DevBuf<double> d_partials;               // [split_max_items][3] a tile's winner
@@ -1650,6 +1652,7 @@ void tls_ctx_destroy(tls_ctx* ctx) {
     ctx->d_times.release();
     ctx->d_shape.release();
     ctx->d_gls.release();
+    ctx->d_match.release();
     ctx->d_split.release(); ctx->d_park.release(); ctx->d_band.release();
     if (ctx->h_band) (void)hipHostFree(ctx->h_band);
     for (auto& ev : ctx->ev_band) if (ev) (void)hipEventDestroy(ev);
@@ -2818,6 +2821,7 @@ int tls_debug_device_bytes(const tls_ctx* ctx, int64_t* total, int64_t* t0_fit_s
     add(ctx->d_times);
     add(ctx->d_shape);
     add(ctx->d_gls);
+    add(ctx->d_match);
     add(ctx->d_partials); add(ctx->d_tiles_done);
     add(ctx->d_split); add(ctx->d_park); add(ctx->d_band);
     *total = (int64_t)sum;
@@ -3886,6 +3890,66 @@ int tls_sine_test(tls_ctx* ctx, const double* t, const double* y, const double* 
         TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
         f0 += (int64_t)fits;
     }
+    return TLS_OK;
+}
+
+// ---- the ephemeris match (tls_match.hip.h, DESIGN.md "Ephemeris match"): every candidate against every other, the g range in
+// chunks along gridDim.y, then the chunks' partial records combined
+static_assert(sizeof(tls_match_record) == tlsdev::kMatchWords * 8, "tls_match_record is the kernel's record");
+static_assert(TLS_MATCH_MAX_CANDIDATES == tlsdev::kMatchMaxCandidates && TLS_MATCH_MAX_RATIO == tlsdev::kMatchMaxRatio, "the header's limits");
+static_assert(sizeof(tlsdev::MatchPartial) % 8 == 0, "partial records lie in a buffer of doubles");
+
+int tls_ephemeris_match(tls_ctx* ctx, const int64_t* star, const double* period, const double* T0, const double* duration,
+                        const double* strength, int64_t n, double span, double drift_tolerance, double epoch_tolerance,
+                        int64_t max_ratio, tls_match_record* out) {
+    if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
+    if (!(std::isfinite(span) && span > 0.0)) return fail(ctx, TLS_E_ARG, "ephemeris match: span must be finite and > 0");
+    if (!(std::isfinite(drift_tolerance) && drift_tolerance >= 0.0))
+        return fail(ctx, TLS_E_ARG, "ephemeris match: drift_tolerance must be finite and >= 0");
+    if (!(std::isfinite(epoch_tolerance) && epoch_tolerance >= 0.0))
+        return fail(ctx, TLS_E_ARG, "ephemeris match: epoch_tolerance must be finite and >= 0");
+    if (max_ratio < 1 || max_ratio > TLS_MATCH_MAX_RATIO) return fail(ctx, TLS_E_ARG, "ephemeris match: max_ratio out of range [1, 64]");
+    if (n < 0 || n > TLS_MATCH_MAX_CANDIDATES) return fail(ctx, TLS_E_ARG, "ephemeris match: n out of range [0, 2^20]");
+    if (n == 0) return TLS_OK;
+    if (!star || !period || !T0 || !duration || !strength || !out) return fail(ctx, TLS_E_ARG, "null argument");
+    TLS_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t nn = (size_t)n, words = (size_t)tlsdev::kMatchWords;
+    const int tiles = (int)((n + tlsdev::kMatchTile - 1) / tlsdev::kMatchTile);
+    const int chunks = tlsdev::match_chunks(tiles);
+    const size_t partial_words = sizeof(tlsdev::MatchPartial) / 8;
+    TLS_HIP(ctx, ctx->d_match.reserve(5 * nn + words * nn + partial_words * (size_t)chunks * nn));
+    double* d_star = ctx->d_match.ptr;
+    double* d_period = d_star + nn;
+    double* d_T0 = d_period + nn;
+    double* d_duration = d_T0 + nn;
+    double* d_strength = d_duration + nn;
+    double* d_out = d_strength + nn;
+    double* d_partial = d_out + words * nn;
+    TLS_HIP(ctx, hipMemcpyAsync(d_star, star, nn * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_period, period, nn * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_T0, T0, nn * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_duration, duration, nn * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_strength, strength, nn * 8, hipMemcpyHostToDevice, ctx->stream));
+    tlsdev::MatchArgs a;
+    a.star = reinterpret_cast<const long long*>(d_star);
+    a.period = d_period; a.T0 = d_T0; a.duration = d_duration; a.strength = d_strength;
+    a.partial = reinterpret_cast<tlsdev::MatchPartial*>(d_partial); a.out = d_out;
+    a.span = span; a.drift_tolerance = drift_tolerance; a.epoch_tolerance = epoch_tolerance; a.max_ratio = (double)max_ratio;
+    a.n = (int)n; a.tiles = tiles; a.chunks = chunks;
+    hipLaunchKernelGGL(tlsdev::tls_match_pairs_kernel, dim3((unsigned)tiles, (unsigned)chunks), dim3(tlsdev::kMatchTile), 0,
+                       ctx->stream, a);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(tlsdev::tls_match_combine_kernel, dim3((unsigned)tiles), dim3(tlsdev::kMatchTile), 0, ctx->stream, a);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(ctx->stream);
+        return fail(ctx, TLS_E_HIP, std::string("ephemeris match launch: ") + hipGetErrorString(e));
+    }
+    ctx->last_kernel = "tls_ephemeris_match";
+    TLS_HIP(ctx, hipMemcpyAsync(out, d_out, words * nn * 8, hipMemcpyDeviceToHost, ctx->stream));
+    TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return TLS_OK;
 }
 

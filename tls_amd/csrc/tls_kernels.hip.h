@@ -4321,5 +4321,7 @@ __global__ void __launch_bounds__(512) tls_transit_models(const ModelsArgs a) {
 #include "tls_gls.hip.h"
 #include "tls_peak_fits.hip.h"
 #include "tls_phase_scan.hip.h"
+// survey-mode ephemeris match across the candidates of a batch (tls_ephemeris_match)
+#include "tls_match.hip.h"
 
 }  // namespace tlsdev

@@ -321,7 +321,8 @@ def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_ar
                 peak_min_power=None, peak_fits=False, phase_scan=False, phase_scan_max_bins=4096, phase_scan_min_count=3,
                 transit_times=False, transit_times_search=1.0, transit_times_min_ses=3.0, shape_fit=False,
                 shape_fit_window=2.0, shape_fit_min_count=3, sine_test=False, sine_test_mask=1.5,
-                sine_test_harmonics=(0.5, 1.0, 2.0), **power_kwargs):
+                sine_test_harmonics=(0.5, 1.0, 2.0), ephemeris_match=False, ephemeris_match_drift=0.5,
+                ephemeris_match_epoch=0.5, ephemeris_match_max_ratio=3, **power_kwargs):
     """Survey-mode power(): for every light curve of `flux_batch` what `transitleastsquares(t, flux).power(**kwargs)`
     reports as SDE, SDE_raw, chi2_min, period, T0, depth and duration (fractional, lc_cache_overview["duration"] of
     the template row at the chi^2 minimum, main.py:199-200) -- search, SDE spectra and final T0 fit all on the
@@ -408,6 +409,19 @@ def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_ar
     result stays as it is, bit for bit.  sine_test without peak_fits, or with a bad mask or harmonics, raises ValueError
     before any device work.
 
+    ephemeris_match=True (with peak_fits=True) is the one test that looks ACROSS the batch: the curves of a batch share their
+    time stamps -- one field, camera and sector -- and so contaminate one another and share instrumental periods.  Every
+    fitted peak of every curve is matched against the fitted peaks of every OTHER curve for a common period (or an integer
+    multiple up to ephemeris_match_max_ratio) and epoch (ephemeris_match below states it; ephemeris_match_drift and
+    ephemeris_match_epoch are its two tolerances), in one call of tls_ephemeris_match on one device -- the given context, or
+    the first of `devices` -- after the slices of all devices are joined.  The candidates are the peaks of status 0 with
+    star = the curve's index, the peak's period, T0 and duration_days of its fit record, strength = 1 - depth and
+    span = max t - min t.  The `peaks` array gains the fields ephemeris_match_peak_fields(): match_status (1, and the others
+    NaN or -1, where status != 0), match_n_same, match_n_period, match_n_match, match_curve and match_rank (the strongest match
+    as an index into `peaks`, -1 without one), match_ratio, match_dt, match_drift, match_strength and match_child (1: the
+    match is deeper, this peak is its diluted copy).  Everything else of the result stays as it is, bit for bit.
+    ephemeris_match without peak_fits, or with a bad tolerance or max_ratio, raises ValueError before any device work.
+
     Returns (summary, periods[, chi2, row, depth, power][, per_transit][, models][, peaks]): summary is a numpy structured
     array with the fields of tls_power_summary plus "duration" (and the statistics on request)."""
     return _power_batch(t, flux_batch, dy_batch, power_kwargs, context=context, device=device, devices=devices,
@@ -419,7 +433,9 @@ def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_ar
                         transit_times=_transit_times_request(transit_times, peak_fits, transit_times_search,
                                                              transit_times_min_ses),
                         shape_fit=_shape_fit_request(shape_fit, peak_fits, shape_fit_window, shape_fit_min_count),
-                        sine_test=_sine_test_request(sine_test, peak_fits, sine_test_mask, sine_test_harmonics))
+                        sine_test=_sine_test_request(sine_test, peak_fits, sine_test_mask, sine_test_harmonics),
+                        ephemeris_match=_ephemeris_match_request(ephemeris_match, peak_fits, ephemeris_match_drift,
+                                                                 ephemeris_match_epoch, ephemeris_match_max_ratio))
 
 
 def _peaks_request(peaks, separation, ratios, min_power, models=False, peak_fits=False):
@@ -579,13 +595,14 @@ def find_peaks(power, periods, k, separation=0.02, ratios=HARMONICS, min_power=N
 
 def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=None, devices=None, with_arrays=False,
                  statistics=False, per_transit=False, models=False, spectra=False, detrend=None, peaks=None,
-                 peak_fits=False, phase_scan=None, transit_times=None, shape_fit=None, sine_test=None):
+                 peak_fits=False, phase_scan=None, transit_times=None, shape_fit=None, sine_test=None, ephemeris_match=None):
     """power_batch; spectra=True (power_results) also returns SR and power_raw [n_curves, n_periods] behind the arrays;
     peaks: None or a checked request (_peaks_request); peak_fits: with peaks, their T0 fits and statistics; phase_scan: None or a checked
     request (_phase_scan_request), with peak_fits, the fits' phase scans; transit_times: None or a checked request
     (_transit_times_request), with peak_fits, the fits' transit times; shape_fit: None or a checked request
     (_shape_fit_request), with peak_fits, the fits' shape fits; sine_test: None or a checked request (_sine_test_request),
-    with peak_fits, the fits' sine tests."""
+    with peak_fits, the fits' sine tests; ephemeris_match: None or a checked request (_ephemeris_match_request), with
+    peak_fits, the match of the fitted peaks across the curves."""
     models = bool(models)
     per_transit = bool(per_transit or models)
     statistics = bool(statistics or per_transit)
@@ -633,6 +650,11 @@ def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=Non
         return part
 
     out = _run_batch(devices, device, context, len(y_rows), call)
+    if ephemeris_match is not None:
+        # (across the curves, so behind the join: one call on one device, as the SysRem step)
+        ctx, lock = _first_context(context, device, devices, len(y_rows))
+        with lock:
+            out["matches"] = _peak_matches(ctx, inp, out["peaks"], out["peak_fits"], ephemeris_match)
     raw = out["summary"]
     names = list(raw.dtype.names) + ["duration"]
     fields = [(k, raw.dtype[k]) for k in raw.dtype.names] + [("duration", "f8")]
@@ -689,6 +711,8 @@ def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=Non
             found["peaks"] = _with_shapes(found["peaks"], out["shape_fits"], found["peaks"]["period"])
         if sine_test is not None:
             found["peaks"] = _with_sines(found["peaks"], out["sine_tests"], out["sine_harmonics"])
+        if ephemeris_match is not None:
+            found["peaks"] = _with_matches(found["peaks"], out["matches"])
         result += (found,)
     if spectra:
         result += (out["SR"], out["power_raw"])
@@ -1404,6 +1428,123 @@ def sine_test(t, flux_batch, period, curve=None, dy_batch=None, T0=None, duratio
     out, out_h = ctx.sine_test(a["t"], rows, a["period"], curve=a["curve"], dy=a["dy"], T0=a["T0"], duration=a["duration"],
                                mask=a["mask"], harmonics=a["harmonics"])
     return _with_sines(None, out, out_h)
+
+
+# ---- the ephemeris match: the test across the stars of a batch -----------------------------------------------------------------
+def ephemeris_match_fields():
+    """The fields of an ephemeris match, in order -- what ephemeris_match returns (tls_match_record): status, n_same,
+    n_period, n_match, best, best_ratio, best_dt, best_drift, best_strength, child."""
+    from ._lib import MATCH_FIELDS
+    return tuple(MATCH_FIELDS)
+
+
+def ephemeris_match_peak_fields():
+    """The fields power_batch(..., ephemeris_match=True) adds to the `peaks` array, in order: those of
+    ephemeris_match_fields() under the prefix match_, with `best` as the pair (match_curve, match_rank), both int64."""
+    return ("match_status", "match_n_same", "match_n_period", "match_n_match", "match_curve", "match_rank", "match_ratio",
+            "match_dt", "match_drift", "match_strength", "match_child")
+
+
+def _ephemeris_match_request(ephemeris_match, peak_fits, drift, epoch, max_ratio):
+    """None, or the checked (drift_tolerance, epoch_tolerance, max_ratio) of an ephemeris_match=True request (ValueError for
+    a bad one, and for ephemeris_match without peak_fits)."""
+    if not ephemeris_match:
+        return None
+    if not peak_fits:
+        raise ValueError("ephemeris_match=True needs peak_fits=True: the match reads T0 and duration of the fits")
+    from ._lib import ephemeris_match_arguments
+    a = ephemeris_match_arguments([], [], [], [], [], 1.0, drift, epoch, max_ratio)
+    return a["drift_tolerance"], a["epoch_tolerance"], a["max_ratio"]
+
+
+def _peak_matches(ctx, inp, peaks, fits, request):
+    """The match records of the fitted peaks of the whole batch, on ctx: (records MATCH_DTYPE [M], the candidates' flat
+    indices c K + r into [n_curves, K], the shape).  A candidate is a peak of fit status 0: star = its curve, its period, T0
+    and duration_days of its fit, strength = 1 - depth; span = max t - min t."""
+    drift, epoch, max_ratio = request
+    n_curves, k = fits.shape
+    at = numpy.flatnonzero((fits["status"] == 0).reshape(-1))
+    t = inp["t"]
+    records = ctx.ephemeris_match(at // k, peaks["period"].reshape(-1)[at], fits["T0"].reshape(-1)[at],
+                                  fits["duration_days"].reshape(-1)[at], 1 - peaks["depth"].reshape(-1)[at],
+                                  numpy.max(t) - numpy.min(t), drift, epoch, max_ratio)
+    return records, at, (n_curves, k)
+
+
+def _with_matches(records, matches):
+    """`records` (the peaks with their fits) plus the match records of the fitted ones (_peak_matches): match_status 1, -1 in
+    match_curve and match_rank and NaN in the others where nothing was fitted."""
+    from ._lib import MATCH_FIELDS
+    found, at, shape = matches
+    k = shape[1]
+    names = ephemeris_match_peak_fields()
+    out = numpy.zeros(shape, dtype=records.dtype.descr + [(n, "i8" if n in ("match_curve", "match_rank") else "f8") for n in names])
+    for n in records.dtype.names:
+        out[n] = records[n]
+    flat = out.reshape(-1)
+    for n in names:
+        flat[n] = -1 if n in ("match_curve", "match_rank") else numpy.nan
+    flat["match_status"] = 1
+    for n, source in zip(names[:4] + names[6:], MATCH_FIELDS[:4] + MATCH_FIELDS[5:]):
+        flat[n][at] = found[source]
+    best = found["best"].astype(numpy.int64)
+    there = best >= 0
+    target = at[numpy.where(there, best, 0)]
+    flat["match_curve"][at] = numpy.where(there, target // k, -1)
+    flat["match_rank"][at] = numpy.where(there, target % k, -1)
+    return out
+
+
+def ephemeris_match(star, period, T0, duration, strength, span, drift_tolerance=0.5, epoch_tolerance=0.5, max_ratio=3,
+                    context=None, device=None):
+    """The ephemeris match of the Kepler and TESS false-positive catalogues (Coughlin et al. 2014), on the device
+    (tls_ephemeris_match): which candidates on DIFFERENT stars share a period (or an integer multiple of it) and an epoch?
+    The stars of one field contaminate one another: a faint star next to an eclipsing binary shows the binary's ephemeris at
+    a diluted depth and passes every single-curve test, because the signal in its light curve is real.  The strongest member
+    of such a group is taken as the source.  A period that many stars show with no common epoch is a systematic: n_same
+    counts it.  Candidate f is (star[f], any integer: candidates of one star are never matched, so `star` may name groups of
+    the caller's own; period[f], T0[f], duration[f] in days; strength[f], larger = more likely the source, e.g. the depth);
+    span is the length of the observations in days.  All pairs are tested, up to 2^20 candidates.
+
+        good[f] = period, T0, duration, strength finite, period > 0, duration > 0;  a bad f: status 1, NaN elsewhere, and
+        invisible to the others.  For a good f and every good g != f with star[g] != star[f], (l, s) = the member of the
+        longer / the shorter period:
+        m = rint(P_l / P_s);  e = m * P_s;  dP = fabs(P_l - e);  c = span / P_l;  drift = dP * c
+        dmax = fmax(d_f, d_g);  plim = drift_tolerance * dmax;  elim = epoch_tolerance * dmax
+        period_match = (m <= max_ratio) and (drift <= plim)
+        x = (T0_l - T0_s) / P_s;  r = rint(x);  u = x - r;  dt = fabs(u) * P_s;  match = period_match and (dt <= elim)
+
+    drift is how far the two ephemerides slide apart over the span, dt the distance of the epochs modulo the shorter period;
+    both are held against the longer of the two durations.  Every step is one IEEE double operation, the counts and the
+    argmax do not depend on the order of evaluation and no doubles are summed, so the result is bit-equal to the numpy
+    statement in tests/ephemeris_match_spec.py.  span finite and > 0, both tolerances finite and >= 0, max_ratio an integer in
+    [1, 64]; ValueError otherwise, before any device work.
+
+    Returns a structured array [M] with the fields ephemeris_match_fields(), all doubles: status (0; 1 a bad candidate),
+    n_same (the g with period_match and m == 1: the pile-up count), n_period (the g with period_match), n_match (the g with
+    match), best (the index of the match of the largest strength, the lowest index among equals; -1 without one), best_ratio
+    (+m if P_best >= P_f, else -m), best_dt, best_drift, best_strength, and child (1 if strength[best] > strength[f], else 0);
+    the last five NaN without a match.  ephemeris_groups names every candidate's source."""
+    from ._lib import ephemeris_match_arguments
+    a = ephemeris_match_arguments(star, period, T0, duration, strength, span, drift_tolerance, epoch_tolerance, max_ratio)
+    ctx = context if context is not None else _search.default_context(device)
+    return ctx.ephemeris_match(**a)
+
+
+def ephemeris_groups(records):
+    """The root of every candidate of ephemeris_match's records [M]: follow `best` while child == 1 -- strength rises
+    strictly along the chain, so it ends -- and report where it ends; a candidate without a stronger match is its own root.
+    int64 [M].  Host only."""
+    records = numpy.asarray(records)
+    best = records["best"]
+    child = records["child"] == 1
+    root = numpy.arange(len(records), dtype=numpy.int64)
+    for f in range(len(records)):
+        at = f
+        while child[at]:
+            at = int(best[at])
+        root[f] = at
+    return root
 
 
 # ---- injection-recovery ---------------------------------------------------------------------------------------------------
