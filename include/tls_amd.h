@@ -107,7 +107,8 @@ int tls_set_options(tls_ctx *ctx, const tls_options *opt);
  * (the two of tls_options), prune, screen32, no_screen (kernel variant of an LDS-resident series), fast_slab, x_staged,
  * sort2, split, split_batch (series in the HBM slab: prefix-sum mode, sort, two-role kernel), threads, blocks, plan_threads
  * (launch shape, host planning), t0_rot (0: the final T0 fit checks every pair of every epoch), prune_min_live, band_max,
- * perm_table (the four-slot kernel's per-plan table of folded orders: 0 none, k > 0 at most k MiB).  A context starts with the values
+ * perm_table (the four-slot kernel's per-plan table of folded orders: 0 none, k > 0 at most k MiB), reg_scan, dense_hoist (its row
+ * layout and its fast-mode dense predicate: 0 the former forms).  A context starts with the values
  * of the TLS_<NAME> environment variables, read once per process; no call reads the environment after that.
  * tls_debug_get_switches writes all of them as "name=value,name=value" (ctx NULL: the process's) -- the text
  * tls_period_costs takes, so that the planning call prices the kernel the searching context will run. */

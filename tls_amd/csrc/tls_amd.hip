@@ -64,6 +64,7 @@ const SwitchName kSwitchNames[] = {
     TLS_SW(sort2, "TLS_SORT2", 0), TLS_SW(threads, "TLS_THREADS", 0), TLS_SW(blocks, "TLS_BLOCKS", 0),
     TLS_SW(plan_threads, "TLS_PLAN_THREADS", 0), TLS_SW(t0_rot, "TLS_T0_ROT", 0), TLS_SW(prune_min_live, "TLS_PRUNE_MIN_LIVE", 1),
     TLS_SW(perm_table, "TLS_PERM_TABLE", 1), TLS_SW(reg_scan, "TLS_REG_SCAN", 0),
+    TLS_SW(dense_hoist, "TLS_DENSE_HOIST", 0),
     TLS_SW(band_max, "TLS_BAND_MAX", 2),
 };
 #undef TLS_SW
@@ -733,9 +734,14 @@ int enqueue(tls_ctx* ctx, bool count_work, bool phase_clock = false, double* deb
         a.lds_bytes = (long long)plan.slim_lds;
         a.perm_table = ctx->perm_table_entries ? ctx->d_perm_table.ptr : nullptr; a.perm_filled = ctx->perm_filled ? 1 : 0;
         a.perm_per = plan.slim_perm_per;
-        auto kernel = kernel_pick == Kernel::Slim512
-                          ? (count_work ? tlsdev::tls_slim_kernel<true, tlsdev::kSlimThreadsWide> : tlsdev::tls_slim_kernel<false, tlsdev::kSlimThreadsWide>)
-                          : (count_work ? tlsdev::tls_slim_kernel<true, tlsdev::kSlimThreads> : tlsdev::tls_slim_kernel<false, tlsdev::kSlimThreads>);
+        // (switch dense_hoist = 0: the instantiations whose fast-mode dense predicate is the loop exact mode keeps)
+        auto kernel = ctx->opt.dense_hoist != 0
+                          ? (kernel_pick == Kernel::Slim512
+                                 ? (count_work ? tlsdev::tls_slim_kernel<true, tlsdev::kSlimThreadsWide> : tlsdev::tls_slim_kernel<false, tlsdev::kSlimThreadsWide>)
+                                 : (count_work ? tlsdev::tls_slim_kernel<true, tlsdev::kSlimThreads> : tlsdev::tls_slim_kernel<false, tlsdev::kSlimThreads>))
+                          : (kernel_pick == Kernel::Slim512
+                                 ? (count_work ? tlsdev::tls_slim_kernel<true, tlsdev::kSlimThreadsWide, false> : tlsdev::tls_slim_kernel<false, tlsdev::kSlimThreadsWide, false>)
+                                 : (count_work ? tlsdev::tls_slim_kernel<true, tlsdev::kSlimThreads, false> : tlsdev::tls_slim_kernel<false, tlsdev::kSlimThreads, false>));
         e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.slim_lds);
         if (e == hipSuccess) {
             hipLaunchKernelGGL(kernel, dim3((unsigned)plan.slim_blocks), dim3((unsigned)plan.slim_threads), plan.slim_lds, ctx->stream, a);

@@ -59,8 +59,9 @@ struct Switches {
     int32_t exact_prefix, slim;
     int32_t prune, screen32, no_screen, fast_slab, x_staged, split, split_batch, sort2, threads, blocks, plan_threads, t0_rot;
     int32_t reg_scan;     // four-slot kernel: stored orders stretch-major, phase 2 of a reading launch in registers (0: thread-major rows)
+    int32_t dense_hoist;  // four-slot kernel, fast-mode dense depth predicate: one loop per case, band test per step, no mask for lanes without a unit (slim_dense_tile; 0: the kernel instantiations with the loop exact mode keeps)
     int64_t prune_min_live;
-    int64_t perm_table;   // the four-slot kernel's table of folded orders: -1 the library decides, 0 none, k > 0 at most k MiB
+    int64_t perm_table;  // the four-slot kernel's table of folded orders: -1 the library decides, 0 none, k > 0 at most k MiB
     double band_max;
 };
 

@@ -406,7 +406,85 @@ __device__ __forceinline__ void slim_load_order(const unsigned short* row, int (
     }
 }
 
-template <bool COUNTING, int THREADS = kSlimThreads>
+// ---- phase 3a, fast mode: the dense rows over one tile of 64 units (developer switch `dense_hoist`) ----
+// Every cell is decided by the operations of the kernel's own loop (exact mode, and the switch at 0) on its values:
+// dX_r = X[min(u0 + d, M + 1) + r] - X[u0c + r], the maximum over r = 0..4 in that order, times 1/d, against the two
+// thresholds.  What is rare is out of the rows' way: whether the rows go to the lanes of a mask pair or to push_live is the
+// caller's choice (MANY), not the row's; a lane without a unit holds +inf for X[u0c + r], fails both compares and needs no
+// mask; a step's band masks are tested together, and the block that notes the windows reads X again, so that nothing of the
+// step stays in registers for it.  (PERF_LOG.md, "dense depth predicate": the other half of the proposal -- row constants out
+// of lanes, four rows a step, single 64-bit reads -- was measured beside this one and dropped.)
+#ifndef TLS_SLIM_ROW_BATCH
+#define TLS_SLIM_ROW_BATCH 2
+#endif
+template <bool MANY>
+__device__ __forceinline__ void slim_dense_tile(const_width_ptr widths_c, const double* c_base, int M, int k_lo, int k_x, int unit, int lane,
+                                                const double (&c_lo)[kR], unsigned long long valid_mask, const DepthRule& rule,
+                                                double thr_hi, double thr_lo, int& row_lo, int& row_hi,
+                                                unsigned long long& band_mask, bool& undecided, unsigned int* live, unsigned int* chunk_list) {
+    constexpr int kB = TLS_SLIM_ROW_BATCH;
+    const int u0 = unit * kR;
+    double lo[kR];
+#pragma unroll
+    for (int r = 0; r < kR; ++r) lo[r] = ((valid_mask >> lane) & 1ull) ? c_lo[r] : INFINITY;
+    for (int k = k_lo; k < k_x; k += kB) {
+        int dv[kB];
+        double inv[kB], m_fast[kB];
+        double c_hi[kB][kR];
+#pragma unroll
+        for (int j = 0; j < kB; ++j) {
+            const int kk = k + j < k_x ? k + j : k_x - 1;
+            dv[j] = widths_c[kk].width;
+            inv[j] = widths_c[kk].inv_d;
+            const int hi0 = min(u0 + dv[j], M + 1);
+#pragma unroll
+            for (int r = 0; r < kR; ++r) c_hi[j][r] = c_base[hi0 + r];
+        }
+#pragma unroll
+        for (int j = 0; j < kB; ++j) {
+            double m = c_hi[j][0] - lo[0];
+#pragma unroll
+            for (int r = 1; r < kR; ++r) m = fmax(m, c_hi[j][r] - lo[r]);
+            m_fast[j] = m * inv[j];
+        }
+        // (a row behind the last one repeats it: the same masks into the same lane, nothing pushed or noted twice)
+        unsigned long long band[kB], band_any = 0ull;
+#pragma unroll
+        for (int j = 0; j < kB; ++j) {
+            const unsigned long long mask = ballot64(m_fast[j] > thr_hi);
+            band[j] = ballot64(m_fast[j] >= thr_lo) & ~mask;
+            band_any |= band[j];
+            const int kk = k + j < k_x ? k + j : k_x - 1;
+            if constexpr (MANY) {
+                push_live(k + j < k_x && ((mask >> lane) & 1ull) != 0ull, (unsigned int)unit, &live[kk - k_lo],
+                          chunk_list + widths_c[kk].list_base, lane);
+            } else {
+                set_lane(row_lo, (int)(unsigned int)mask, kk - k_lo);
+                set_lane(row_hi, (int)(unsigned int)(mask >> 32), kk - k_lo);
+            }
+        }
+        if (band_any != 0ull) {   // (a scalar branch, rarely taken)
+            if (rule.band_count != nullptr) {
+                asm volatile("" ::: "memory");   // (X is read again: the step's values end here)
+#pragma unroll
+                for (int j = 0; j < kB; ++j) {
+                    if (k + j < k_x && ((band[j] >> lane) & 1ull)) {
+                        const int hi0 = min(u0 + dv[j], M + 1);
+#pragma unroll
+                        for (int r = 0; r < kR; ++r) {
+                            const double dXr = c_base[hi0 + r] - lo[r];
+                            if (dXr * inv[j] >= thr_lo) band_window(rule, k + j, u0 + r, dXr, undecided);
+                        }
+                    }
+                }
+            } else {
+                band_mask |= band_any;
+            }
+        }
+    }
+}
+
+template <bool COUNTING, int THREADS = kSlimThreads, bool DENSE_HOIST = true>
 __global__ void __launch_bounds__(THREADS, 4)
 tls_slim_kernel(const SearchArgs) {
     constexpr bool UNIFORM_W = true;
@@ -633,6 +711,9 @@ tls_slim_kernel(const SearchArgs) {
         if (k_x > k_lo) {
             const int units0 = widths_c[k_lo].n_chunks;
             const int n_dense = k_x - k_lo;
+            // fast mode: the dense rows by slim_dense_tile (exact mode, and the instantiations of switch `dense_hoist` = 0, keep
+            // the loop below)
+            const bool dense_hoist = DENSE_HOIST && !exact_u;
             for (int tile = wave; tile * kWave < units0; tile += nw) {
                 const int unit = tile * kWave + lane;
                 const int u0 = unit * kR;
@@ -643,10 +724,15 @@ tls_slim_kernel(const SearchArgs) {
                 int row_lo = 0, row_hi = 0;
                 unsigned long long band_mask = 0ull;
                 const unsigned long long valid_mask = ballot64(unit < units0);
-#ifndef TLS_SLIM_ROW_BATCH
-#define TLS_SLIM_ROW_BATCH 2
-#endif
                 constexpr int kRowBatch = TLS_SLIM_ROW_BATCH;
+                if (dense_hoist) {
+                    if (n_dense <= kWave)
+                        slim_dense_tile<false>(widths_c, c_base, M, k_lo, k_x, unit, lane, c_lo, valid_mask, rule, thr_hi, thr_lo, row_lo, row_hi,
+                                               band_mask, undecided, rt.live, chunk_list);
+                    else
+                        slim_dense_tile<true>(widths_c, c_base, M, k_lo, k_x, unit, lane, c_lo, valid_mask, rule, thr_hi, thr_lo, row_lo, row_hi,
+                                              band_mask, undecided, rt.live, chunk_list);
+                } else
                 for (int k = k_lo; k < k_x; k += kRowBatch) {
                     int dv[kRowBatch];
                     double inv[kRowBatch], dC[kRowBatch];
