@@ -40,7 +40,7 @@ extern "C" {
  * (7: tls_power_batch_peak_fits, tls_debug_peak_fits), (7: tls_phase_scan, tls_power_batch_phase_scan,
  * tls_debug_peak_phase_scans), (7: tls_sysrem), (7: tls_single_transits), (7: tls_transit_times),
  * (7: tls_shape_fit), (7: tls_nudft, tls_lomb_scargle, tls_sine_test); 8: every entry that takes `root, n_root` takes a
- * second table, `root, root_count, n_root`), (8: tls_ephemeris_match). */
+ * second table, `root, root_count, n_root`), (8: tls_ephemeris_match), (8: tls_folded_views). */
 #define TLS_AMD_ABI_VERSION 8
 
 #define TLS_OK 0
@@ -765,6 +765,48 @@ int tls_shape_fit(tls_ctx *ctx, const double *t, const double *y, const double *
                   const double *period, const double *T0, const double *duration, const int64_t *curve, int64_t n_fits,
                   const double *ratio, int64_t nT, const double *ingress, int64_t nQ, const double *shift, int64_t nS,
                   double window, int64_t min_count, double depth_min, tls_shape_record *out /* [n_fits] */);
+
+/* The folded views of a candidate: its light curve folded at the ephemeris and binned by the MEDIAN on a fixed number of
+ * bins -- the "global view" and "local view" of Shallue & Vanderburg (2018, AJ 155, 94), and the even, odd and
+ * secondary-eclipse local views Valizadegan et al. (2022, ApJ 926, 120) add to them: what a data-validation report plots and
+ * a neural-net vetter reads.  For a row y [n] over the ascending, finite t [n], a candidate (P, T0, d in days, phi_s) and a
+ * view (phi_c, x_min, x_max, w, B, parity):
+ *   points, i ascending:  x = (t[i] - T0) / P;  u = x - phi_c;  e = floor(u + 0.5);  tau = (u - e) * P
+ *   bin b, 0 <= b < B:    s = ((x_max - x_min) - w) / (B - 1);  lo = b * s + x_min;  hi = lo + w
+ *                         member iff lo <= tau and tau < hi (and, with a parity, e - 2.0 * floor(e / 2.0) == parity)
+ *   count[b] = the members;  median[b] = the middle member by value (count odd), (a + b) / 2.0 of the two middle ones (even),
+ *   NaN (none);  n_members = the points that are a member of at least one bin
+ * Nothing but those two comparisons decides membership: with w > s a point is in several bins, with w < s maybe in none.
+ * The five views, with k = local_durations and width = local_width:
+ *   global      (0.0,   -0.5 * P, 0.5 * P, P / n_global, n_global, none)
+ *   local       (0.0,   -(k * d), k * d,   width * d,    n_local,  none)
+ *   local_even  the same with parity 0.0: the transits of even e -- T0 the fit's own: the first, third, ... transit of the
+ *               series, power()'s transit_depths[::2] and depth_mean_even;  local_odd with parity 1.0
+ *   secondary   the local view about phi_c = phi_s
+ * status 1 (every median NaN, every count 0, every n_* 0) unless P, T0, d are finite, P > 0 and d > 0; secondary_status 1 and
+ * the secondary view alone NaN / 0 where phi_s is not finite or secondary_phase is NULL.  Every step is one IEEE double
+ * operation and a median is a selection: records and arrays equal the Python statement in tests/folded_views_spec.py bit for
+ * bit.  All fields are doubles. */
+#define TLS_VIEWS_MAX_BINS 65536
+typedef struct tls_views_record {
+    double status;                 /* 0 binned; 1 no such candidate */
+    double secondary_status;       /* 0 binned; 1 no secondary view (no candidate, or no finite phi_s) */
+    double n_global, n_local, n_local_even, n_local_odd, n_secondary;   /* n_members of the five views */
+} tls_views_record;
+/* n_fits candidates (period[f], T0[f], duration[f], secondary_phase[f]; secondary_phase NULL: no secondary view) on the rows
+ * curve[f] (NULL: candidate f is curve f) of y [n_curves][n] over the shared time stamps t [n].  out [n_fits];
+ * global_median, global_count [n_fits][n_global]; local_median, local_count [n_fits][4][n_local] in the order local,
+ * local_even, local_odd, secondary.  The device writes every entry.  Needs no plan and no search, and leaves a prepared plan
+ * as it is.  n_fits == 0 is a no-op.  Candidates are processed in slabs, so device memory stays bounded for any n_fits.
+ * TLS_E_ARG, before any device work and with the outputs untouched, for n_global or n_local outside
+ * [2, TLS_VIEWS_MAX_BINS], a local_durations or local_width that is not finite and > 0, local_width > 2 * local_durations,
+ * a curve[f] outside [0, n_curves), n outside [1, 2^20], negative counts, and a t that is not finite and non-decreasing.
+ * y is taken as it is (finite); period, T0, duration and secondary_phase may hold any value. */
+int tls_folded_views(tls_ctx *ctx, const double *t, const double *y, int64_t n, int64_t n_curves, const double *period,
+                     const double *T0, const double *duration, const double *secondary_phase, const int64_t *curve,
+                     int64_t n_fits, int64_t n_global, int64_t n_local, double local_durations, double local_width,
+                     tls_views_record *out /* [n_fits] */, double *global_median, int32_t *global_count,
+                     double *local_median, int32_t *local_count);
 
 /* The variability periodogram: the generalised (floating-mean, weighted) Lomb-Scargle periodogram of Zechmeister & Kuerster
  * (2009, A&A 496, 577) of every curve of a batch on shared time stamps, and the sine test of a candidate.  Is the STAR

@@ -55,6 +55,14 @@ TIMES_MAX_POINTS = 1 << 30   # tls_times.hip.h kTimesMaxPoints
 SHAPE_MAX_UNITS = 65536
 SHAPE_MAX_POINTS = 1 << 22
 SHAPE_LDS_MEMBERS = 2048
+# include/tls_amd.h TLS_VIEWS_MAX_BINS: the most bins of a view of tls_folded_views; tls_views.hip.h kViewsMaxPoints,
+# kViewsLdsPoints (the points of a series the LDS holds; a longer one is ordered in device scratch), kViewsLaneMembers (a bin
+# of up to this many members is selected by one lane, a larger one by a wave) and kViewsSlab (the candidates of a launch)
+VIEWS_MAX_BINS = 65536
+VIEWS_MAX_POINTS = 1 << 20
+VIEWS_LDS_POINTS = 4608
+VIEWS_LANE_MEMBERS = 8
+VIEWS_SLAB = 1024
 # include/tls_amd.h TLS_GLS_MAX_POINTS, TLS_GLS_MAX_FREQUENCIES, TLS_SINE_MAX_HARMONICS; tls_gls.hip.h kGlsRowTile,
 # kGlsSmallRows (batches of at most this many rows take the 32-row kernel), kGlsFreqTile, kGlsChunk, kSineThreads
 GLS_MAX_POINTS = 1 << 22
@@ -86,7 +94,7 @@ SYMBOLS = (
     "tls_biweight_detrend", "tls_sysrem", "tls_find_peaks", "tls_power_batch_peaks", "tls_power_batch_peak_fits", "tls_debug_peak_fits",
     "tls_phase_scan", "tls_power_batch_phase_scan", "tls_debug_peak_phase_scans", "tls_single_transits",
     "tls_transit_times", "tls_shape_fit", "tls_nudft", "tls_lomb_scargle", "tls_sine_test",
-    "tls_ephemeris_match",
+    "tls_ephemeris_match", "tls_folded_views",
     "tls_comm_unique_id", "tls_comm_init", "tls_comm_destroy", "tls_comm_info", "tls_comm_allgather_results", "tls_comm_allgather_device", "tls_comm_fetch_gathered",
     "tls_comm_stage_results", "tls_comm_allgather_staged", "tls_comm_fetch_staged",
     "tls_comm_barrier", "tls_comm_max",
@@ -562,6 +570,69 @@ def shape_fit_arguments(t, y, dy, period, T0, duration, ratios, ingress, shifts,
                 min_count=min_count, depth_min=depth_min)
 
 
+# tls_views_record (include/tls_amd.h): a candidate's folded views, 7 doubles; the local views in the order of the arrays
+VIEWS_FIELDS = ("status", "secondary_status", "n_global", "n_local", "n_local_even", "n_local_odd", "n_secondary")
+VIEWS_LOCAL = ("local", "local_even", "local_odd", "secondary")
+
+
+class ViewsRecord(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_double) for k in VIEWS_FIELDS]
+
+
+VIEWS_DTYPE = numpy.dtype([(k, "f8") for k in VIEWS_FIELDS])
+
+
+def folded_views_tables(n_global=2001, n_local=201, local_durations=4.0, local_width=0.16):
+    """(n_global, n_local, local_durations, local_width) as tls_folded_views takes them, checked as it checks them: the bin
+    counts integers in [2, VIEWS_MAX_BINS]; local_durations finite and > 0; local_width finite, > 0 and at most
+    2 * local_durations (a bin no wider than the view).  ValueError otherwise."""
+    for name, v in (("n_global", n_global), ("n_local", n_local)):
+        if isinstance(v, (bool, numpy.bool_)) or not isinstance(v, numbers.Integral) or not 2 <= int(v) <= VIEWS_MAX_BINS:
+            raise ValueError("folded views: %s must be an integer in [2, %d], got %r" % (name, VIEWS_MAX_BINS, v))
+    for name, v in (("local_durations", local_durations), ("local_width", local_width)):
+        if isinstance(v, (bool, numpy.bool_)) or not isinstance(v, numbers.Real) or not (0.0 < float(v) < numpy.inf):
+            raise ValueError("folded views: %s must be finite and > 0, got %r" % (name, v))
+    if float(local_width) > 2.0 * float(local_durations):
+        raise ValueError("folded views: local_width %r is wider than the view, 2 * local_durations = %r"
+                         % (local_width, 2.0 * float(local_durations)))
+    return int(n_global), int(n_local), float(local_durations), float(local_width)
+
+
+def folded_views_arguments(t, y, period, T0, duration, curve=None, secondary_phase=None, n_global=2001, n_local=201,
+                           local_durations=4.0, local_width=0.16):
+    """What tls_folded_views takes, checked as it checks them and packed for it -- a dict with t [n] (1-D, n in
+    [1, VIEWS_MAX_POINTS], finite and non-decreasing), y [n_curves, n] (finite), period, T0, duration, curve [n_fits]
+    (shape_fit_candidates: any value, curve in [0, n_curves)), secondary_phase [n_fits] or None, and the four table
+    parameters (folded_views_tables).  ValueError otherwise.  GPU-free."""
+    n_global, n_local, k, width = folded_views_tables(n_global, n_local, local_durations, local_width)
+    t = numpy.asarray(t, dtype=numpy.float64)
+    if t.ndim != 1 or not 1 <= len(t) <= VIEWS_MAX_POINTS:
+        raise ValueError("folded views: t must have shape [n] with n in [1, %d], got %s" % (VIEWS_MAX_POINTS, t.shape))
+    if not numpy.all(numpy.isfinite(t)) or not numpy.all(t[1:] >= t[:-1]):
+        raise ValueError("folded views: t must be finite and non-decreasing")
+    y = numpy.asarray(y, dtype=numpy.float64)
+    if y.ndim == 1:
+        y = y[None, :]
+    if y.ndim != 2 or y.shape[1] != len(t):
+        raise ValueError("folded views: y must be [n] or [n_curves, n] over the time stamps t [n]")
+    if y.size and not numpy.all(numpy.isfinite(y)):
+        raise ValueError("folded views: y has a NaN or an infinite value")
+    try:
+        period, T0, duration, curve = shape_fit_candidates(period, T0, duration, curve, len(y))
+    except ValueError as e:
+        raise ValueError(str(e).replace("shape fit", "folded views"))
+    if secondary_phase is not None:
+        try:
+            secondary_phase = numpy.ascontiguousarray(numpy.atleast_1d(numpy.asarray(secondary_phase, dtype=numpy.float64)))
+        except (TypeError, ValueError):
+            raise ValueError("folded views: secondary_phase must hold numbers")
+        if secondary_phase.shape != period.shape:
+            raise ValueError("folded views: secondary_phase must be [n_fits], one phase a candidate")
+    return dict(t=numpy.ascontiguousarray(t), y=numpy.ascontiguousarray(y), period=period, T0=T0, duration=duration,
+                curve=curve, secondary_phase=secondary_phase, n_global=n_global, n_local=n_local, local_durations=k,
+                local_width=width)
+
+
 # tls_sine_record and tls_sine_harmonic (include/tls_amd.h): the sine test of a candidate, 4 doubles and 5 a harmonic
 SINE_FIELDS = ("status", "n_used", "mean", "variance")
 SINE_HARMONIC_FIELDS = ("power", "amplitude", "phase", "amplitude_err", "significance")
@@ -859,6 +930,10 @@ def load():
     lib.tls_transit_times.argtypes = [vp, _c_double_p, _c_double_p, _c_double_p, i64, i64, _c_int64_p, _c_double_p, _c_double_p,
                                       _c_int64_p, _c_int64_p, i64, _c_double_p, _c_int64_p, _c_int64_p, _c_double_p, i64, dbl,
                                       dbl, i64, ctypes.c_void_p, ctypes.c_void_p]
+    lib.tls_folded_views.restype = ci
+    lib.tls_folded_views.argtypes = [vp, _c_double_p, _c_double_p, i64, i64, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
+                                     _c_int64_p, i64, i64, i64, ctypes.c_double, ctypes.c_double, vp, _c_double_p, vp,
+                                     _c_double_p, vp]
     lib.tls_shape_fit.restype = ci
     lib.tls_shape_fit.argtypes = [vp, _c_double_p, _c_double_p, _c_double_p, i64, i64, _c_double_p, _c_double_p, _c_double_p,
                                   _c_int64_p, i64, _c_double_p, i64, _c_double_p, i64, _c_double_p, i64, dbl, i64, dbl,
@@ -1687,6 +1762,31 @@ class Context(object):
             len(a["shift"]), a["window"], a["min_count"], a["depth_min"], out.ctypes.data_as(ctypes.c_void_p)))
         return out
 
+    def folded_views(self, t, y, period, T0, duration, curve=None, secondary_phase=None, n_global=2001, n_local=201,
+                     local_durations=4.0, local_width=0.16):
+        """The folded, median-binned views (tls_folded_views; the statement: include/tls_amd.h, tests/folded_views_spec.py)
+        of the candidates (period[f], T0[f], duration[f] in days, secondary_phase[f]; None: no secondary view) on the rows
+        curve[f] (None: one candidate a curve, in order) of y [n_curves, n] (or one row) over t [n]: (records VIEWS_DTYPE
+        [n_fits], global_median [n_fits, n_global], global_count (int32), local_median [n_fits, 4, n_local] in the order
+        VIEWS_LOCAL, local_count).  ValueError for what folded_views_arguments refuses."""
+        a = folded_views_arguments(t, y, period, T0, duration, curve, secondary_phase, n_global, n_local, local_durations,
+                                   local_width)
+        n_c, n = a["y"].shape
+        n_fits = len(a["period"])
+        out = numpy.zeros(n_fits, dtype=VIEWS_DTYPE)
+        g_med = numpy.empty((n_fits, a["n_global"]))
+        g_cnt = numpy.empty((n_fits, a["n_global"]), dtype=numpy.int32)
+        l_med = numpy.empty((n_fits, len(VIEWS_LOCAL), a["n_local"]))
+        l_cnt = numpy.empty((n_fits, len(VIEWS_LOCAL), a["n_local"]), dtype=numpy.int32)
+        assert VIEWS_DTYPE.itemsize == ctypes.sizeof(ViewsRecord)
+        phi = a["secondary_phase"]
+        self._check(self._lib.tls_folded_views(
+            self._h, _dp(a["t"]), _dp(a["y"]), n, n_c, _dp(a["period"]), _dp(a["T0"]), _dp(a["duration"]),
+            None if phi is None else _dp(phi), _ip(a["curve"]), n_fits, a["n_global"], a["n_local"], a["local_durations"],
+            a["local_width"], out.ctypes.data_as(ctypes.c_void_p), _dp(g_med), g_cnt.ctypes.data_as(ctypes.c_void_p),
+            _dp(l_med), l_cnt.ctypes.data_as(ctypes.c_void_p)))
+        return out, g_med, g_cnt, l_med, l_cnt
+
     def nudft(self, rows, t, frequencies):
         """The non-uniform DFT of the rows [n_rows, n] (or one row) over t [n] at `frequencies` [F] (tls_nudft; the statement:
         include/tls_amd.h, tests/gls_spec.py): [n_rows, F, 2] with (sum_i rows[r, i] cos phi_ki, sum_i rows[r, i] sin phi_ki),
@@ -1872,7 +1972,7 @@ class Context(object):
             self._check(rc)
         names = ("lds_carve", "list_capacity", "dot_window", "predicate_read", "sort_window", "work_item",
                  "singles_capacity", "tile_stage", "screen_split", "detrend_slot",
-                 "biweight_slot", "sysrem_index", "single_window", "times_window", "shape_index")
+                 "biweight_slot", "sysrem_index", "single_window", "times_window", "shape_index", "views_range")
         return bool(rc), dict(zip(names, [int(v) for v in arr]))
 
     def poison_lds(self, word=0x7ff80000):

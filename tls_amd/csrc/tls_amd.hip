@@ -226,6 +226,9 @@ struct tls_ctx {
     DevBuf<double> d_times;
     // tls_shape_fit: of one slab: pairs | y | dy | records | period | T0 | duration | slot; t | ratio | ingress | shift | scratch
     DevBuf<double> d_shape;
+    // tls_folded_views: of one slab: y | records | period | T0 | duration | secondary | global and local medians | slot | global
+    // and local counts; t | scratch
+    DevBuf<double> d_views;
     // tls_nudft / tls_lomb_scargle / tls_sine_test: the sums of one slab first (16-byte aligned pairs), then its rows and tables
     DevBuf<double> d_gls;
     // tls_ephemeris_match: star | period | T0 | duration | strength | records | partial records of every chunk
@@ -1657,6 +1660,7 @@ void tls_ctx_destroy(tls_ctx* ctx) {
     ctx->d_single.release();
     ctx->d_times.release();
     ctx->d_shape.release();
+    ctx->d_views.release();
     ctx->d_gls.release();
     ctx->d_match.release();
     ctx->d_split.release(); ctx->d_park.release(); ctx->d_band.release();
@@ -2553,6 +2557,7 @@ int tls_debug_poison_lds(tls_ctx* ctx, uint32_t word) {
     TLS_HIP(ctx, smear(ctx->d_fscratch.ptr, ctx->d_fscratch.cap * sizeof(double)));
     TLS_HIP(ctx, smear(ctx->d_frot.ptr, ctx->d_frot.cap * sizeof(double)));
     TLS_HIP(ctx, smear(ctx->d_frperm.ptr, ctx->d_frperm.cap * sizeof(int)));
+    TLS_HIP(ctx, smear(ctx->d_views.ptr, ctx->d_views.cap * sizeof(double)));
     return TLS_OK;
 }
 
@@ -2826,6 +2831,7 @@ int tls_debug_device_bytes(const tls_ctx* ctx, int64_t* total, int64_t* t0_fit_s
     add(ctx->d_single);
     add(ctx->d_times);
     add(ctx->d_shape);
+    add(ctx->d_views);
     add(ctx->d_gls);
     add(ctx->d_match);
     add(ctx->d_partials); add(ctx->d_tiles_done);
@@ -3612,6 +3618,122 @@ int tls_shape_fit(tls_ctx* ctx, const double* t, const double* y, const double* 
         }
         ctx->last_kernel = "tls_shape_fit";
         TLS_HIP(ctx, hipMemcpyAsync(out + f0, d_out, fits * words * 8, hipMemcpyDeviceToHost, ctx->stream));
+        // (the next slab overwrites the device buffers and h_slot)
+        TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        f0 += (int64_t)fits;
+    }
+    return TLS_OK;
+}
+
+// ---- the folded views (tls_views.hip.h, DESIGN.md "Folded views"): one workgroup a candidate, slab by slab; the device writes
+// every entry of every output, so the host neither fills nor scatters
+static_assert(sizeof(tls_views_record) == tlsdev::kViewsWords * 8, "tls_views_record is the kernel's record");
+static_assert(TLS_VIEWS_MAX_BINS == tlsdev::kViewsMaxBins, "the header's limit");
+
+int tls_folded_views(tls_ctx* ctx, const double* t, const double* y, int64_t n, int64_t n_curves, const double* period,
+                     const double* T0, const double* duration, const double* secondary_phase, const int64_t* curve,
+                     int64_t n_fits, int64_t n_global, int64_t n_local, double local_durations, double local_width,
+                     tls_views_record* out, double* global_median, int32_t* global_count, double* local_median,
+                     int32_t* local_count) {
+    if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
+    if (n_fits < 0 || n_curves < 0 || n < 0) return fail(ctx, TLS_E_ARG, "folded views: negative count");
+    if (n_global < 2 || n_local < 2 || n_global > TLS_VIEWS_MAX_BINS || n_local > TLS_VIEWS_MAX_BINS)
+        return fail(ctx, TLS_E_ARG, "folded views: n_global and n_local must lie in [2, 65536]");
+    if (!(std::isfinite(local_durations) && local_durations > 0.0))
+        return fail(ctx, TLS_E_ARG, "folded views: local_durations must be finite and > 0");
+    if (!(std::isfinite(local_width) && local_width > 0.0 && local_width <= 2.0 * local_durations))
+        return fail(ctx, TLS_E_ARG, "folded views: local_width must be finite, > 0 and at most 2 * local_durations");
+    if (n_fits == 0) return TLS_OK;
+    if (!t || !y || !period || !T0 || !duration || !out || !global_median || !global_count || !local_median || !local_count)
+        return fail(ctx, TLS_E_ARG, "null argument");
+    if (n < 1 || n > tlsdev::kViewsMaxPoints) return fail(ctx, TLS_E_ARG, "folded views: n out of range [1, 2^20]");
+    if (n_fits > INT32_MAX || (uint64_t)n_curves > (uint64_t)(INT64_MAX / 16) / (uint64_t)n)
+        return fail(ctx, TLS_E_ARG, "folded views: batch too large");
+    for (int64_t i = 0; i < n; ++i)
+        if (!std::isfinite(t[i]) || (i > 0 && t[i] < t[i - 1]))
+            return fail(ctx, TLS_E_ARG, "folded views: the time stamps must be finite and non-decreasing");
+    for (int64_t f = 0; f < n_fits; ++f) {
+        const int64_t c = curve ? curve[f] : f;
+        if (c < 0 || c >= n_curves) return fail(ctx, TLS_E_ARG, "folded views: curve out of range [0, n_curves)");
+    }
+    TLS_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t nn = (size_t)n, words = tlsdev::kViewsWords, ng = (size_t)n_global, nl = (size_t)tlsdev::kViewsLocal * (size_t)n_local;
+    // a slab: at most 1024 candidates (256 MB of medians and counts, 12 bytes a bin) on at most 1024 curves, 256 MB of curves;
+    // the workgroups of a launch: at most 1024, and 256 MB of scratch where the series is longer than the LDS holds
+    const size_t budget = 256u << 20;
+    const size_t cs = std::max<size_t>(1, std::min<size_t>({(size_t)n_curves, 1024, budget / (8 * nn)}));
+    const size_t sl = std::min<size_t>({(size_t)n_fits, (size_t)tlsdev::kViewsSlab, std::max<size_t>(1, budget / (12 * (ng + nl)))});
+    const size_t stretch = n > tlsdev::kViewsLdsPoints ? tlsdev::views_scratch_words(nn) : 0;
+    const size_t groups = std::max<size_t>(1, std::min<size_t>({sl, (size_t)tlsdev::kViewsMaxGroups, stretch ? budget / (8 * stretch) : sl}));
+    const size_t ints = (sl * (1 + ng + nl) + 1) / 2;        // slot | global counts | local counts, in doubles
+    TLS_HIP(ctx, ctx->d_views.reserve(cs * nn + sl * (words + 4 + ng + nl) + ints + nn + groups * stretch));
+    double* d_y = ctx->d_views.ptr;
+    double* d_out = d_y + cs * nn;
+    double* d_period = d_out + sl * words;
+    double* d_T0 = d_period + sl;
+    double* d_duration = d_T0 + sl;
+    double* d_secondary = d_duration + sl;
+    double* d_gmed = d_secondary + sl;
+    double* d_lmed = d_gmed + sl * ng;
+    int* d_slot = reinterpret_cast<int*>(d_lmed + sl * nl);
+    int* d_gcnt = d_slot + sl;
+    int* d_lcnt = d_gcnt + sl * ng;
+    double* d_t = d_lmed + sl * nl + ints;
+    double* d_scratch = d_t + nn;
+    if (!ctx->d_check.ptr) {
+        TLS_HIP(ctx, ctx->d_check.reserve(tlsdev::kChecks));
+        TLS_HIP(ctx, hipMemsetAsync(ctx->d_check.ptr, 0, tlsdev::kChecks * sizeof(unsigned long long), ctx->stream));
+    }
+    tlsdev::ViewsArgs a;
+    a.t = d_t; a.y = d_y; a.slot = d_slot; a.period = d_period; a.T0 = d_T0; a.duration = d_duration;
+    a.secondary = secondary_phase ? d_secondary : nullptr;
+    a.scratch = d_scratch; a.out = d_out; a.global_median = d_gmed; a.global_count = d_gcnt; a.local_median = d_lmed;
+    a.local_count = d_lcnt; a.check = ctx->d_check.ptr; a.k = local_durations; a.width = local_width;
+    a.n = (int)n; a.n_global = (int)n_global; a.n_local = (int)n_local;
+    auto views_kernel = tlsdev::tls_folded_views_kernel;
+    TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, ctx->stream));
+    std::vector<int> h_slot(sl);
+    std::unordered_map<int64_t, int> slot_of;
+    struct Run { int64_t curve; size_t slot, count; };      // consecutive curves in consecutive slots: one copy
+    std::vector<Run> runs;
+    for (int64_t f0 = 0; f0 < n_fits;) {
+        slot_of.clear();
+        runs.clear();
+        size_t fits = 0;
+        while (f0 + (int64_t)fits < n_fits && fits < sl) {
+            const int64_t f = f0 + (int64_t)fits;
+            const int64_t c = curve ? curve[f] : f;
+            auto it = slot_of.find(c);
+            if (it == slot_of.end()) {
+                if (slot_of.size() == cs) break;     // (the next slab takes it; a slab's first candidate always finds a slot)
+                const size_t slot = slot_of.size();
+                it = slot_of.emplace(c, (int)slot).first;
+                if (!runs.empty() && runs.back().curve + (int64_t)runs.back().count == c) ++runs.back().count;
+                else runs.push_back(Run{c, slot, 1});
+            }
+            h_slot[fits] = it->second;
+            ++fits;
+        }
+        for (const Run& run : runs)
+            TLS_HIP(ctx, hipMemcpyAsync(d_y + run.slot * nn, y + (size_t)run.curve * nn, run.count * nn * 8, hipMemcpyHostToDevice, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(d_slot, h_slot.data(), fits * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(d_period, period + f0, fits * 8, hipMemcpyHostToDevice, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(d_T0, T0 + f0, fits * 8, hipMemcpyHostToDevice, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(d_duration, duration + f0, fits * 8, hipMemcpyHostToDevice, ctx->stream));
+        if (secondary_phase) TLS_HIP(ctx, hipMemcpyAsync(d_secondary, secondary_phase + f0, fits * 8, hipMemcpyHostToDevice, ctx->stream));
+        a.fits = (int)fits;
+        hipLaunchKernelGGL(views_kernel, dim3((unsigned)std::min(fits, groups)), dim3(tlsdev::kViewsThreads), 0, ctx->stream, a);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(ctx->stream);
+            return fail(ctx, TLS_E_HIP, std::string("folded views launch: ") + hipGetErrorString(e));
+        }
+        ctx->last_kernel = "tls_folded_views";
+        TLS_HIP(ctx, hipMemcpyAsync(out + f0, d_out, fits * words * 8, hipMemcpyDeviceToHost, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(global_median + (size_t)f0 * ng, d_gmed, fits * ng * 8, hipMemcpyDeviceToHost, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(global_count + (size_t)f0 * ng, d_gcnt, fits * ng * 4, hipMemcpyDeviceToHost, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(local_median + (size_t)f0 * nl, d_lmed, fits * nl * 8, hipMemcpyDeviceToHost, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(local_count + (size_t)f0 * nl, d_lcnt, fits * nl * 4, hipMemcpyDeviceToHost, ctx->stream));
         // (the next slab overwrites the device buffers and h_slot)
         TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
         f0 += (int64_t)fits;

@@ -322,7 +322,8 @@ def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_ar
                 transit_times=False, transit_times_search=1.0, transit_times_min_ses=3.0, shape_fit=False,
                 shape_fit_window=2.0, shape_fit_min_count=3, sine_test=False, sine_test_mask=1.5,
                 sine_test_harmonics=(0.5, 1.0, 2.0), ephemeris_match=False, ephemeris_match_drift=0.5,
-                ephemeris_match_epoch=0.5, ephemeris_match_max_ratio=3, **power_kwargs):
+                ephemeris_match_epoch=0.5, ephemeris_match_max_ratio=3, views=False, views_global_bins=2001,
+                views_local_bins=201, views_local_durations=4.0, views_local_width=0.16, **power_kwargs):
     """Survey-mode power(): for every light curve of `flux_batch` what `transitleastsquares(t, flux).power(**kwargs)`
     reports as SDE, SDE_raw, chi2_min, period, T0, depth and duration (fractional, lc_cache_overview["duration"] of
     the template row at the chi^2 minimum, main.py:199-200) -- search, SDE spectra and final T0 fit all on the
@@ -422,6 +423,17 @@ def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_ar
     match is deeper, this peak is its diluted copy).  Everything else of the result stays as it is, bit for bit.
     ephemeris_match without peak_fits, or with a bad tolerance or max_ratio, raises ValueError before any device work.
 
+    views=True (with peak_fits=True) folds and median-bins every fitted peak into the five views a vetter reads -- global,
+    local, local_even, local_odd and secondary (folded_views below states them) -- in one call of tls_folded_views behind the
+    search, on the device that searched the curve and on the rows it searched, from the period of the peak and T0 and
+    duration_days of its fit record; views_global_bins, views_local_bins, views_local_durations and views_local_width are
+    folded_views' n_global, n_local, local_durations and local_width.  With phase_scan=True the secondary view is centred on
+    the scan's secondary_phase; without it that view is NaN / 0.  The peaks dict gains `views`, the dict of arrays of
+    folded_views shaped [n_curves, K, bins], and the `peaks` array views_status (1, and NaN / 0 in the arrays, where
+    status != 0) and views_n_global, views_n_local, views_n_local_even, views_n_local_odd, views_n_secondary.  Everything else
+    of the result stays as it is, bit for bit.  views without peak_fits, or with a bad table, raises ValueError before any
+    device work.
+
     Returns (summary, periods[, chi2, row, depth, power][, per_transit][, models][, peaks]): summary is a numpy structured
     array with the fields of tls_power_summary plus "duration" (and the statistics on request)."""
     return _power_batch(t, flux_batch, dy_batch, power_kwargs, context=context, device=device, devices=devices,
@@ -435,7 +447,9 @@ def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_ar
                         shape_fit=_shape_fit_request(shape_fit, peak_fits, shape_fit_window, shape_fit_min_count),
                         sine_test=_sine_test_request(sine_test, peak_fits, sine_test_mask, sine_test_harmonics),
                         ephemeris_match=_ephemeris_match_request(ephemeris_match, peak_fits, ephemeris_match_drift,
-                                                                 ephemeris_match_epoch, ephemeris_match_max_ratio))
+                                                                 ephemeris_match_epoch, ephemeris_match_max_ratio),
+                        views=_views_request(views, peak_fits, views_global_bins, views_local_bins, views_local_durations,
+                                             views_local_width))
 
 
 def _peaks_request(peaks, separation, ratios, min_power, models=False, peak_fits=False):
@@ -595,14 +609,16 @@ def find_peaks(power, periods, k, separation=0.02, ratios=HARMONICS, min_power=N
 
 def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=None, devices=None, with_arrays=False,
                  statistics=False, per_transit=False, models=False, spectra=False, detrend=None, peaks=None,
-                 peak_fits=False, phase_scan=None, transit_times=None, shape_fit=None, sine_test=None, ephemeris_match=None):
+                 peak_fits=False, phase_scan=None, transit_times=None, shape_fit=None, sine_test=None, ephemeris_match=None,
+                 views=None):
     """power_batch; spectra=True (power_results) also returns SR and power_raw [n_curves, n_periods] behind the arrays;
     peaks: None or a checked request (_peaks_request); peak_fits: with peaks, their T0 fits and statistics; phase_scan: None or a checked
     request (_phase_scan_request), with peak_fits, the fits' phase scans; transit_times: None or a checked request
     (_transit_times_request), with peak_fits, the fits' transit times; shape_fit: None or a checked request
     (_shape_fit_request), with peak_fits, the fits' shape fits; sine_test: None or a checked request (_sine_test_request),
     with peak_fits, the fits' sine tests; ephemeris_match: None or a checked request (_ephemeris_match_request), with
-    peak_fits, the match of the fitted peaks across the curves."""
+    peak_fits, the match of the fitted peaks across the curves; views: None or a checked request (_views_request), with
+    peak_fits, the fits' folded views."""
     models = bool(models)
     per_transit = bool(per_transit or models)
     statistics = bool(statistics or per_transit)
@@ -647,6 +663,10 @@ def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=Non
             # (the weights are normalised, so the search's dy / mean(dy) serve; without dy_batch they are uniform)
             part["sine_tests"], part["sine_harmonics"] = _peak_sine_tests(
                 ctx, inp, y_rows[lo:hi], None if dy_batch is None else dy_rows[lo:hi], part["peaks"], part["peak_fits"], sine_test)
+        if views is not None:
+            (part["views_records"], part["views_global"], part["views_global_count"], part["views_local"],
+             part["views_local_count"]) = _peak_views(ctx, inp, y_rows[lo:hi], part["peaks"], part["peak_fits"],
+                                                      part["phase_scans"] if phase_scan is not None else None, views)
         return part
 
     out = _run_batch(devices, device, context, len(y_rows), call)
@@ -713,6 +733,13 @@ def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=Non
             found["peaks"] = _with_sines(found["peaks"], out["sine_tests"], out["sine_harmonics"])
         if ephemeris_match is not None:
             found["peaks"] = _with_matches(found["peaks"], out["matches"])
+        if views is not None:
+            found["peaks"] = _with_views(found["peaks"], out["views_records"])
+            found["views"] = _views_dict(out["views_global"].reshape((-1,) + out["views_global"].shape[2:]),
+                                         out["views_global_count"].reshape((-1,) + out["views_global_count"].shape[2:]),
+                                         out["views_local"].reshape((-1,) + out["views_local"].shape[2:]),
+                                         out["views_local_count"].reshape((-1,) + out["views_local_count"].shape[2:]),
+                                         lead=out["views_records"].shape)
         result += (found,)
     if spectra:
         result += (out["SR"], out["power_raw"])
@@ -1268,6 +1295,129 @@ def shape_fit(t, flux_batch, period, T0, duration, curve=None, dy_batch=None, ra
     out = ctx.shape_fit(inp["t"], y_rows, dy_rows, period, T0, duration, ratio, ingress, shift, curve=curve, window=window,
                         min_count=min_count, depth_min=depth_min)
     return _with_shapes(None, out, period)
+
+
+# ---- folded, median-binned views ------------------------------------------------------------------------------------------------
+def folded_view_fields():
+    """The fields of a folded-views record, in order (tls_views_record): status (0 binned; 1 no such candidate),
+    secondary_status (0 binned; 1 no secondary view), and n_global, n_local, n_local_even, n_local_odd, n_secondary -- the
+    points that are a member of at least one bin of the view.  power_batch(..., views=True) adds views_status and the five
+    counts as views_n_global ... views_n_secondary to the `peaks` array."""
+    from ._lib import VIEWS_FIELDS
+    return tuple(VIEWS_FIELDS)
+
+
+def _views_dict(g_med, g_cnt, l_med, l_cnt, lead):
+    """The dict of view arrays from the device's four arrays, their candidate axis reshaped to `lead`."""
+    from ._lib import VIEWS_LOCAL
+    views = {"global": g_med.reshape(lead + g_med.shape[1:]), "global_count": g_cnt.reshape(lead + g_cnt.shape[1:])}
+    for i, name in enumerate(VIEWS_LOCAL):
+        views[name] = l_med[:, i].reshape(lead + l_med.shape[2:])
+        views[name + "_count"] = l_cnt[:, i].reshape(lead + l_cnt.shape[2:])
+    return views
+
+
+def folded_views(t, flux_batch, period, T0, duration, curve=None, secondary_phase=None, n_global=2001, n_local=201,
+                 local_durations=4.0, local_width=0.16, context=None, device=None):
+    """The phase-folded, median-binned views of candidates the caller holds, on the device (tls_folded_views): candidate f
+    is (period[f], T0[f], duration[f] in days) on light curve curve[f] of flux_batch [n_curves, n] (or one row [n]) over the
+    ascending time stamps t; curve=None takes one candidate a curve, in order.  It needs no search.  These are the "global
+    view" and "local view" of Shallue & Vanderburg (2018) and the even, odd and secondary-eclipse local views of
+    Valizadegan et al. (2022) -- the panels of a data-validation report, the input of a neural-net vetter.  A view is
+    (phi_c, x_min, x_max, w, B, parity):
+
+        x = (t[i] - T0) / P;  u = x - phi_c;  e = floor(u + 0.5);  tau = (u - e) * P         (days from the view's centre)
+        bin b:  s = ((x_max - x_min) - w) / (B - 1);  lo = b * s + x_min;  member iff lo <= tau and tau < lo + w
+                (with a parity also e - 2 * floor(e / 2) == parity)
+        count[b] = the members;  median[b] = the middle member by value, (a + b) / 2 of the two middle ones, NaN of none
+
+        global      phi_c 0      -0.5 P .. 0.5 P                          w = P / n_global         n_global bins
+        local       phi_c 0      -local_durations d .. local_durations d  w = local_width d        n_local bins
+        local_even, local_odd    the local view of the epochs e of parity 0 and 1: with the fit's own T0 -- its first
+                                 transit -- even is the first, third, ... transit, power()'s transit_depths[::2]
+        secondary   the local view about phi_c = secondary_phase[f] (phase_scan's secondary_phase); NaN / 0 where that is
+                    not finite, and everywhere with secondary_phase=None
+
+    Each step is one IEEE double operation and a median is a selection, so records and arrays are bit-equal to the Python
+    statement in tests/folded_views_spec.py.  The medians are unweighted.  The defaults are Astronet's.  n_global and n_local
+    in [2, 65536], local_durations and local_width finite and > 0, local_width <= 2 * local_durations, curve in
+    [0, n_curves), t finite and ascending, flux finite: ValueError otherwise, before any device work.
+
+    Returns (records, views): a structured array [n_fits] with the fields folded_view_fields(), and a dict of arrays
+    [n_fits, bins]: global, local, local_even, local_odd, secondary (float64 medians) and the same names + "_count" (int32).
+    A candidate without an ephemeris (status 1) has NaN and 0 everywhere.  normalize_views scales them for a vetter."""
+    from ._lib import folded_views_arguments
+    a = folded_views_arguments(t, flux_batch, period, T0, duration, curve, secondary_phase, n_global, n_local,
+                               local_durations, local_width)
+    ctx = context if context is not None else _search.default_context(device)
+    out = ctx.folded_views(a["t"], a["y"], a["period"], a["T0"], a["duration"], curve=a["curve"],
+                           secondary_phase=a["secondary_phase"], n_global=a["n_global"], n_local=a["n_local"],
+                           local_durations=a["local_durations"], local_width=a["local_width"])
+    return out[0], _views_dict(*out[1:], lead=(len(out[0]),))
+
+
+def normalize_views(views):
+    """The views as a vetter takes them (host numpy; the Astronet convention, stated in tests/folded_views_spec.py): in every
+    row of every array of medians the empty bins (NaN) are filled by linear interpolation between the neighbouring non-empty
+    ones, the edges held; the row's median is subtracted; the row is divided by the absolute value of its minimum, so the
+    deepest bin is -1.  A row whose minimum is 0 is left undivided, a row without a non-empty bin stays NaN.  The "_count"
+    arrays are copied as they are.  Returns a new dict."""
+    out = {}
+    for name, v in views.items():
+        if name.endswith("_count"):
+            out[name] = numpy.array(v)
+            continue
+        v = numpy.array(v, dtype=numpy.float64)
+        rows = v.reshape(-1, v.shape[-1]) if v.ndim else v.reshape(1, 1)
+        where = numpy.arange(rows.shape[1], dtype=numpy.float64)
+        for row in rows:
+            full = ~numpy.isnan(row)
+            if not full.any():
+                continue
+            filled = numpy.interp(where, where[full], row[full])
+            filled = filled - numpy.median(filled)
+            low = filled.min()
+            row[:] = filled if low == 0.0 else filled / abs(low)
+        out[name] = v
+    return out
+
+
+def _views_request(views, peak_fits, n_global, n_local, local_durations, local_width):
+    """None, or the checked (n_global, n_local, local_durations, local_width) of a views=True request (ValueError for a bad
+    one, and for views without peak_fits)."""
+    if not views:
+        return None
+    if not peak_fits:
+        raise ValueError("views=True needs peak_fits=True: the views fold at T0 and bin by duration_days of the fits")
+    from ._lib import folded_views_tables
+    return folded_views_tables(n_global, n_local, local_durations, local_width)
+
+
+def _peak_views(ctx, inp, y_rows, peaks, fits, scans, request):
+    """The views of the peaks of a slice of the batch, on ctx: the records [n_curves, K] and the four arrays of the device,
+    [n_curves, K, ...].  Every peak is a candidate: one whose fit status is not 0 goes in as NaN and comes back with status 1,
+    NaN and 0.  scans (None: no secondary view) are the slice's phase-scan records."""
+    n_global, n_local, k, width = request
+    n_curves, K = fits.shape
+    fitted = (fits["status"] == 0).reshape(-1)
+    period = numpy.where(fitted, peaks["period"].reshape(-1), numpy.nan)
+    T0 = numpy.where(fitted, fits["T0"].reshape(-1), numpy.nan)
+    duration = numpy.where(fitted, fits["duration_days"].reshape(-1), numpy.nan)
+    phi = None if scans is None else numpy.where(fitted, scans["secondary_phase"].reshape(-1), numpy.nan)
+    out = ctx.folded_views(inp["t"], y_rows, period, T0, duration, curve=numpy.repeat(numpy.arange(n_curves), K),
+                           secondary_phase=phi, n_global=n_global, n_local=n_local, local_durations=k, local_width=width)
+    return tuple(v.reshape((n_curves, K) + v.shape[1:]) for v in out)
+
+
+def _with_views(records, views):
+    """The peaks plus views_status and the five views_n_* member counts of the device's view records."""
+    names = [("views_status", "status")] + [("views_" + k, k) for k in folded_view_fields()[2:]]
+    out = numpy.zeros(records.shape, dtype=records.dtype.descr + [(k, "f8") for k, _ in names])
+    for k in records.dtype.names:
+        out[k] = records[k]
+    for k, source in names:
+        out[k] = views[source]
+    return out
 
 
 # ---- variability periodogram and sine test -----------------------------------------------------------------------------------
