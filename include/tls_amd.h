@@ -40,7 +40,8 @@ extern "C" {
  * (7: tls_power_batch_peak_fits, tls_debug_peak_fits), (7: tls_phase_scan, tls_power_batch_phase_scan,
  * tls_debug_peak_phase_scans), (7: tls_sysrem), (7: tls_single_transits), (7: tls_transit_times),
  * (7: tls_shape_fit), (7: tls_nudft, tls_lomb_scargle, tls_sine_test); 8: every entry that takes `root, n_root` takes a
- * second table, `root, root_count, n_root`), (8: tls_ephemeris_match), (8: tls_folded_views). */
+ * second table, `root, root_count, n_root`), (8: tls_ephemeris_match), (8: tls_folded_views),
+ * (8: tls_event_vetting). */
 #define TLS_AMD_ABI_VERSION 8
 
 #define TLS_OK 0
@@ -721,6 +722,84 @@ int tls_transit_times(tls_ctx *ctx, const double *t, const double *y, const doub
                       int64_t n_fits, const double *shape_values, const int64_t *shape_offset, const int64_t *width,
                       const double *span_max, int64_t n_rows, double depth_min, double min_ses, int64_t max_epochs,
                       tls_ephemeris *out /* [n_fits] */, tls_transit_time *out_times /* [n_fits][max_epochs] */);
+
+/* Per-transit event vetting: the tests of a candidate's INDIVIDUAL events (after the Kepler Robovetter's individual transit
+ * metrics, Thompson et al. 2018, A.3.7) -- is an event unique in its neighbourhood, does it rest on one sample, does the flux
+ * come back to the baseline, does the candidate survive without its bad events or without its strongest one.  The inputs are
+ * those of tls_transit_times; a candidate also has a chase reach R >= 0 and a guard Gd >= 0 in samples and a chase_span > 0 in
+ * days, the call chase_fraction in (0, 1], chase_min in [0, 1], point_fraction > 0 and step_fraction > 0.
+ *   w = 1.0 / (dy * dy);  xw = (1.0 - y) * w;  bb[k] = b[k]*b[k];  h = (L - 1) / 2
+ *   candidate status 1 / 2 and n_epochs as tls_transit_times has them
+ *   every epoch e = e_first + i:
+ *       tc, the nearest sample j and the held window (q, d, c, lo) over the shifts -S .. S as tls_transit_times finds them (the
+ *       same skips, the same chains, the first shift wins ties); N, D of the held window are kept
+ *       nothing held: event status 1, epoch and time_linear = tc reported, every other field NaN
+ *       event status 0:  ses = q;  depth = d;  index = c;  depth_err = 1.0 / sqrt(D)
+ *       point:   pm = xw[lo]*b[0];  k = 1 .. L-1 ascending:  v = xw[lo+k]*b[k];  pm = v if v > pm
+ *                point_share = pm / N                                  the numerator's share resting on one sample
+ *       sides:   before over [lo-L, lo-1], after over [lo+L, lo+2L-1]; for a side [a, z]:
+ *                NaN if a < 0 or z > n-1 or not (t[z] - t[a] <= span_max)
+ *                Ns = 0; Ws = 0; k ascending:  Ns = Ns + xw[a+k];  Ws = Ws + w[a+k];   side = (Ns / Ws) / d
+ *       chase:   n_chased = 0;  found = false
+ *                for m = Gd+1 .. R, for c' in (c - m, c + m):  lo' = c' - h;  hi' = lo' + L - 1
+ *                    skip if lo' < 0 or hi' > n-1 or not (t[hi'] - t[lo'] <= span_max)
+ *                    n_chased += 1;  N', D' as N, D (k ascending);  q' = N' / sqrt(D')
+ *                    if fabs(q') >= chase_fraction * q:  dtc = fabs(t[c'] - t[c]);  chase_dt = dtc if not found or dtc < chase_dt
+ *                                                        found = true
+ *                chases = NaN if n_chased == 0;  1.0 if not found;  else x = chase_dt / chase_span, 1.0 if not (x < 1.0)
+ *                chase_dt is NaN unless found
+ *       flags = 1 * (not q >= min_ses) + 2 * (point_share > point_fraction)
+ *             + 4 * (before > step_fraction or after > step_fraction) + 8 * (chases < chase_min)      NaN compares false
+ *       good iff flags == 0
+ *   candidate, over the events of status 0 ascending (n_held of them):
+ *       SN = SN + N;  SD = SD + D;  mes = SN / sqrt(SD);  depth_mean = SN / SD
+ *       ses_max, ses_max_epoch: the largest q and its epoch, the first on ties;  dominance = ses_max / mes
+ *       n_good, mes_good: the same two sums over the good events only (NaN where n_good == 0)
+ *       mes_rest: the same over the held events except the ses_max epoch (NaN where n_held < 2)
+ *       depth_chi2:  r = d_e - depth_mean;  chi2 = chi2 + (r*r)*D_e
+ *       chases_min, chases_mean (sum / count, ascending) over the events whose chases is not NaN; NaN if none
+ *       n_held == 0: n_held = 0, n_good = 0, the rest NaN (status, n_epochs and epoch_first stay)
+ * chase_dt is a minimum of non-negative doubles and n_chased a count, so neither depends on the order the chase windows are
+ * visited in; every other sum runs in the stated order and every step is one IEEE double operation: both records equal the
+ * Python statement in tests/event_vetting_spec.py bit for bit.  mes is formed from each event's BEST shift, so it is biased
+ * upward against a strictly linear ephemeris: compare it with mes_good and mes_rest, not with the search's SNR.  All fields
+ * are doubles. */
+#define TLS_EVENTS_MAX_CHASE 8192
+typedef struct tls_event_summary {
+    double status;                 /* 0 epochs were looked at; 1 no such ephemeris (P, T0); 2 n_epochs outside [1, max_epochs] */
+    double n_epochs, epoch_first;  /* epochs inside the series; e_first */
+    double n_held, n_good;         /* events of status 0; those without a flag */
+    double mes, mes_good, mes_rest;    /* SN / sqrt(SD) over the held events, over the good ones, over all but the strongest */
+    double ses_max, ses_max_epoch, dominance;   /* the strongest event, its epoch, ses_max / mes */
+    double depth_mean, depth_chi2; /* SN / SD, and the chi^2 of the events' depths about it */
+    double chases_min, chases_mean;    /* over the events that had a chase window */
+} tls_event_summary;
+typedef struct tls_event_record {
+    double epoch;                  /* e; NaN at ranks past n_epochs */
+    double status;                 /* 0 an event is held; 1 no window with a dip (a gap, an end of the series) */
+    double time_linear;            /* tc */
+    double ses, depth, depth_err, index;   /* q, d, 1 / sqrt(D), c of the held window */
+    double point_share;            /* the largest term of N over N: > point_fraction, the event rests on one sample */
+    double before, after;          /* the mean dip of the L samples on either side over d: > step_fraction, the flux is not at
+                                      the baseline there (a step, a ramp); NaN where the side leaves the series or runs over a gap */
+    double chases;                 /* min(chase_dt / chase_span, 1): how far away the nearest comparable event is; 1 none */
+    double chase_dt, n_chased;     /* days to the nearest comparable window (NaN: none); windows looked at */
+    double flags;                  /* 1 weaker than min_ses | 2 point | 4 step | 8 chased */
+} tls_event_record;
+/* n_fits candidates (period[f], T0[f], row[f], reach[f], chase_reach[f], guard[f], chase_span[f]) on the curves curve[f]; the
+ * other arguments as tls_transit_times takes them.  out [n_fits], out_events [n_fits][max_epochs].  Needs no plan and no
+ * search, and leaves a prepared plan as it is.  n_fits == 0 is a no-op.  Candidates are processed in slabs, so device memory
+ * stays bounded for any n_fits.  TLS_E_ARG, before any device work and with the outputs untouched, for everything
+ * tls_transit_times rejects, and for a chase_reach[f] outside [0, TLS_EVENTS_MAX_CHASE], a negative guard[f], a chase_span[f]
+ * that is not finite and > 0, chase_fraction outside (0, 1], chase_min outside [0, 1], and a point_fraction or step_fraction
+ * that is not > 0 (NaN included). */
+int tls_event_vetting(tls_ctx *ctx, const double *t, const double *y, const double *dy, int64_t n, int64_t n_curves,
+                      const int64_t *curve, const double *period, const double *T0, const int64_t *row, const int64_t *reach,
+                      const int64_t *chase_reach, const int64_t *guard, const double *chase_span, int64_t n_fits,
+                      const double *shape_values, const int64_t *shape_offset, const int64_t *width, const double *span_max,
+                      int64_t n_rows, double depth_min, double min_ses, double chase_fraction, double chase_min,
+                      double point_fraction, double step_fraction, int64_t max_epochs,
+                      tls_event_summary *out /* [n_fits] */, tls_event_record *out_events /* [n_fits][max_epochs] */);
 
 /* The shape of a candidate's dip: a trapezoid of unit depth -- total duration T (T14), flat bottom T (1 - 2 g), g = T12/T14,
  * centre shifted by c0 -- is fitted to the points around every transit of a linear ephemeris, over a grid of durations,

@@ -50,6 +50,7 @@ SINGLE_MAX_POINTS = 1 << 20
 TIMES_MAX_REACH = 4096
 TIMES_MAX_EPOCHS = 65536
 TIMES_MAX_POINTS = 1 << 30   # tls_times.hip.h kTimesMaxPoints
+EVENTS_MAX_CHASE = 8192      # include/tls_amd.h TLS_EVENTS_MAX_CHASE: the widest chase reach of a candidate of tls_event_vetting
 # include/tls_amd.h TLS_SHAPE_MAX_UNITS: the most (duration, ingress, shift) units of tls_shape_fit; tls_shape.hip.h
 # kShapeMaxPoints and kShapeLdsMembers (the members of a candidate the LDS holds; more are staged through it in tiles)
 SHAPE_MAX_UNITS = 65536
@@ -94,7 +95,7 @@ SYMBOLS = (
     "tls_biweight_detrend", "tls_sysrem", "tls_find_peaks", "tls_power_batch_peaks", "tls_power_batch_peak_fits", "tls_debug_peak_fits",
     "tls_phase_scan", "tls_power_batch_phase_scan", "tls_debug_peak_phase_scans", "tls_single_transits",
     "tls_transit_times", "tls_shape_fit", "tls_nudft", "tls_lomb_scargle", "tls_sine_test",
-    "tls_ephemeris_match", "tls_folded_views",
+    "tls_ephemeris_match", "tls_folded_views", "tls_event_vetting",
     "tls_comm_unique_id", "tls_comm_init", "tls_comm_destroy", "tls_comm_info", "tls_comm_allgather_results", "tls_comm_allgather_device", "tls_comm_fetch_gathered",
     "tls_comm_stage_results", "tls_comm_allgather_staged", "tls_comm_fetch_staged",
     "tls_comm_barrier", "tls_comm_max",
@@ -465,6 +466,72 @@ def transit_times_arguments(t, y, dy, period, T0, row, reach, widths, shapes, sp
     for k in ("k", "separation"):
         del a[k]
     a.update(ints, period=period, T0=T0, depth_min=depth_min, min_ses=min_ses, max_epochs=max_epochs)
+    return a
+
+
+# tls_event_summary and tls_event_record (include/tls_amd.h): a candidate's event vetting, 15 doubles, and one of its events,
+# 14 doubles
+EVENT_SUMMARY_FIELDS = ("status", "n_epochs", "epoch_first", "n_held", "n_good", "mes", "mes_good", "mes_rest", "ses_max",
+                        "ses_max_epoch", "dominance", "depth_mean", "depth_chi2", "chases_min", "chases_mean")
+EVENT_RECORD_FIELDS = ("epoch", "status", "time_linear", "ses", "depth", "depth_err", "index", "point_share", "before", "after",
+                       "chases", "chase_dt", "n_chased", "flags")
+
+
+class EventSummary(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_double) for k in EVENT_SUMMARY_FIELDS]
+
+
+class EventRecord(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_double) for k in EVENT_RECORD_FIELDS]
+
+
+EVENT_SUMMARY_DTYPE = numpy.dtype([(k, "f8") for k in EVENT_SUMMARY_FIELDS])
+EVENT_RECORD_DTYPE = numpy.dtype([(k, "f8") for k in EVENT_RECORD_FIELDS])
+
+
+def event_vetting_options(chase_fraction=0.6, chase_min=0.5, point_fraction=0.5, step_fraction=0.5):
+    """(chase_fraction, chase_min, point_fraction, step_fraction) as tls_event_vetting takes them, checked as it checks them:
+    numbers, chase_fraction in (0, 1], chase_min in [0, 1], point_fraction and step_fraction > 0; ValueError otherwise."""
+    out = []
+    for name, v, ok, text in (("chase_fraction", chase_fraction, lambda x: 0.0 < x <= 1.0, "in (0, 1]"),
+                              ("chase_min", chase_min, lambda x: 0.0 <= x <= 1.0, "in [0, 1]"),
+                              ("point_fraction", point_fraction, lambda x: x > 0.0, "> 0"),
+                              ("step_fraction", step_fraction, lambda x: x > 0.0, "> 0")):
+        if isinstance(v, (bool, numpy.bool_)) or not isinstance(v, numbers.Real) or not ok(float(v)):
+            raise ValueError("event vetting: %s must be a number %s, got %r" % (name, text, v))
+        out.append(float(v))
+    return tuple(out)
+
+
+def event_vetting_arguments(t, y, dy, period, T0, row, reach, chase_reach, guard, chase_span, widths, shapes, span_max,
+                            curve=None, depth_min=0.0, min_ses=3.0, chase_fraction=0.6, chase_min=0.5, point_fraction=0.5,
+                            step_fraction=0.5, max_epochs=1):
+    """What tls_event_vetting takes, checked as it checks them and packed for it: the dict of transit_times_arguments (its
+    messages headed "event vetting"), plus chase_reach and guard [n_fits] (int64; chase_reach in [0, EVENTS_MAX_CHASE],
+    guard >= 0), chase_span [n_fits] (float64, finite and > 0) and the four parameters (event_vetting_options).  ValueError
+    otherwise.  GPU-free."""
+    options = event_vetting_options(chase_fraction, chase_min, point_fraction, step_fraction)
+    try:
+        a = transit_times_arguments(t, y, dy, period, T0, row, reach, widths, shapes, span_max, curve, depth_min, min_ses,
+                                    max_epochs)
+    except ValueError as e:
+        raise ValueError(str(e).replace("transit times", "event vetting"))
+    shape = a["period"].shape
+    for name, v, hi in (("chase_reach", chase_reach, EVENTS_MAX_CHASE), ("guard", guard, None)):
+        v = numpy.atleast_1d(numpy.asarray(v))
+        if v.shape != shape or (v.size and v.dtype.kind not in "iu"):
+            raise ValueError("event vetting: %s must hold one integer a candidate" % name)
+        if v.size and (v.min() < 0 or (hi is not None and v.max() > hi)):
+            raise ValueError("event vetting: %s out of range [0, %s]" % (name, "2^63)" if hi is None else "%d" % hi))
+        a[name] = numpy.ascontiguousarray(v, dtype=numpy.int64)
+    try:
+        span = numpy.ascontiguousarray(numpy.atleast_1d(numpy.asarray(chase_span, dtype=numpy.float64)))
+    except (TypeError, ValueError):
+        raise ValueError("event vetting: chase_span must hold numbers")
+    if span.shape != shape or not numpy.all(numpy.isfinite(span) & (span > 0.0)):
+        raise ValueError("event vetting: chase_span must hold one finite value > 0 a candidate")
+    a.update(chase_span=span, chase_fraction=options[0], chase_min=options[1], point_fraction=options[2],
+             step_fraction=options[3])
     return a
 
 
@@ -930,6 +997,11 @@ def load():
     lib.tls_transit_times.argtypes = [vp, _c_double_p, _c_double_p, _c_double_p, i64, i64, _c_int64_p, _c_double_p, _c_double_p,
                                       _c_int64_p, _c_int64_p, i64, _c_double_p, _c_int64_p, _c_int64_p, _c_double_p, i64, dbl,
                                       dbl, i64, ctypes.c_void_p, ctypes.c_void_p]
+    lib.tls_event_vetting.restype = ci
+    lib.tls_event_vetting.argtypes = [vp, _c_double_p, _c_double_p, _c_double_p, i64, i64, _c_int64_p, _c_double_p, _c_double_p,
+                                      _c_int64_p, _c_int64_p, _c_int64_p, _c_int64_p, _c_double_p, i64, _c_double_p, _c_int64_p,
+                                      _c_int64_p, _c_double_p, i64, dbl, dbl, dbl, dbl, dbl, dbl, i64, ctypes.c_void_p,
+                                      ctypes.c_void_p]
     lib.tls_folded_views.restype = ci
     lib.tls_folded_views.argtypes = [vp, _c_double_p, _c_double_p, i64, i64, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
                                      _c_int64_p, i64, i64, i64, ctypes.c_double, ctypes.c_double, vp, _c_double_p, vp,
@@ -1744,6 +1816,30 @@ class Context(object):
             _dp(a["span_max"]), len(a["width"]), a["depth_min"], a["min_ses"], a["max_epochs"],
             eph.ctypes.data_as(ctypes.c_void_p), times.ctypes.data_as(ctypes.c_void_p)))
         return eph, times
+
+    def event_vetting(self, t, y, dy, period, T0, row, reach, chase_reach, guard, chase_span, widths, shapes, span_max,
+                      curve=None, depth_min=0.0, min_ses=3.0, chase_fraction=0.6, chase_min=0.5, point_fraction=0.5,
+                      step_fraction=0.5, max_epochs=1):
+        """The per-transit event vetting (tls_event_vetting; the statement: include/tls_amd.h, tests/event_vetting_spec.py)
+        of the candidates (period[f], T0[f], row[f], reach[f], chase_reach[f], guard[f], chase_span[f]) on the curves curve[f]
+        (None: one candidate a curve, in order) of y, dy [n_curves, n] (or one row) over t [n], for the rows (widths[r],
+        shapes[r], span_max[r]): (EVENT_SUMMARY_DTYPE [n_fits], EVENT_RECORD_DTYPE [n_fits, max_epochs]).  ValueError for what
+        event_vetting_arguments refuses."""
+        a = event_vetting_arguments(t, y, dy, period, T0, row, reach, chase_reach, guard, chase_span, widths, shapes, span_max,
+                                    curve, depth_min, min_ses, chase_fraction, chase_min, point_fraction, step_fraction,
+                                    max_epochs)
+        n_c, n = a["y"].shape
+        n_fits = len(a["period"])
+        out = numpy.zeros(n_fits, dtype=EVENT_SUMMARY_DTYPE)
+        events = numpy.zeros((n_fits, a["max_epochs"]), dtype=EVENT_RECORD_DTYPE)
+        assert EVENT_SUMMARY_DTYPE.itemsize == ctypes.sizeof(EventSummary) and EVENT_RECORD_DTYPE.itemsize == ctypes.sizeof(EventRecord)
+        self._check(self._lib.tls_event_vetting(
+            self._h, _dp(a["t"]), _dp(a["y"]), _dp(a["dy"]), n, n_c, _ip(a["curve"]), _dp(a["period"]), _dp(a["T0"]),
+            _ip(a["row"]), _ip(a["reach"]), _ip(a["chase_reach"]), _ip(a["guard"]), _dp(a["chase_span"]), n_fits,
+            _dp(a["shape_values"]), _ip(a["shape_offset"]), _ip(a["width"]), _dp(a["span_max"]), len(a["width"]),
+            a["depth_min"], a["min_ses"], a["chase_fraction"], a["chase_min"], a["point_fraction"], a["step_fraction"],
+            a["max_epochs"], out.ctypes.data_as(ctypes.c_void_p), events.ctypes.data_as(ctypes.c_void_p)))
+        return out, events
 
     def shape_fit(self, t, y, dy, period, T0, duration, ratios, ingress, shifts, curve=None, window=2.0, min_count=3,
                   depth_min=0.0):

@@ -224,6 +224,9 @@ struct tls_ctx {
     DevBuf<double> d_single;
     // tls_transit_times: of one slab: pairs | y | dy | records | times | period | T0 | slot, row, reach; t | rows | taps | slopes
     DevBuf<double> d_times;
+    // tls_event_vetting: of one slab: pairs | held (N, D) | y | dy | summaries | events | period | T0 | chase_span | slot, row,
+    // reach, chase, guard; t | rows | taps
+    DevBuf<double> d_vetting;
     // tls_shape_fit: of one slab: pairs | y | dy | records | period | T0 | duration | slot; t | ratio | ingress | shift | scratch
     DevBuf<double> d_shape;
     // tls_folded_views: of one slab: y | records | period | T0 | duration | secondary | global and local medians | slot | global
@@ -1659,6 +1662,7 @@ void tls_ctx_destroy(tls_ctx* ctx) {
     ctx->d_scan.release();
     ctx->d_single.release();
     ctx->d_times.release();
+    ctx->d_vetting.release();
     ctx->d_shape.release();
     ctx->d_views.release();
     ctx->d_gls.release();
@@ -2830,6 +2834,7 @@ int tls_debug_device_bytes(const tls_ctx* ctx, int64_t* total, int64_t* t0_fit_s
     add(ctx->d_scan);
     add(ctx->d_single);
     add(ctx->d_times);
+    add(ctx->d_vetting);
     add(ctx->d_shape);
     add(ctx->d_views);
     add(ctx->d_gls);
@@ -3491,6 +3496,176 @@ int tls_transit_times(tls_ctx* ctx, const double* t, const double* y, const doub
         TLS_HIP(ctx, hipMemcpyAsync(out + f0, d_out, fits * eph_words * 8, hipMemcpyDeviceToHost, ctx->stream));
         TLS_HIP(ctx, hipMemcpyAsync(out_times + (size_t)f0 * me, d_out_times, fits * time_words * 8, hipMemcpyDeviceToHost, ctx->stream));
         // (the next slab overwrites the device buffers and h_ints; h_rows, h_taps and h_slopes are read until the stream is done)
+        TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        f0 += (int64_t)fits;
+    }
+    return TLS_OK;
+}
+
+// ---- per-transit event vetting (tls_events.hip.h, DESIGN.md "Event vetting"): the pairs kernel of the transit times over the
+// curves a slab of candidates reads, then one workgroup a candidate, slab by slab
+static_assert(sizeof(tls_event_summary) == tlsdev::kEventsSummaryWords * 8, "tls_event_summary is the kernel's record");
+static_assert(sizeof(tls_event_record) == tlsdev::kEventsRecordWords * 8, "tls_event_record is the kernel's record");
+static_assert(TLS_EVENTS_MAX_CHASE == tlsdev::kEventsMaxChase, "the header's limit");
+
+int tls_event_vetting(tls_ctx* ctx, const double* t, const double* y, const double* dy, int64_t n, int64_t n_curves,
+                      const int64_t* curve, const double* period, const double* T0, const int64_t* row, const int64_t* reach,
+                      const int64_t* chase_reach, const int64_t* guard, const double* chase_span, int64_t n_fits,
+                      const double* shape_values, const int64_t* shape_offset, const int64_t* width, const double* span_max,
+                      int64_t n_rows, double depth_min, double min_ses, double chase_fraction, double chase_min,
+                      double point_fraction, double step_fraction, int64_t max_epochs,
+                      tls_event_summary* out, tls_event_record* out_events) {
+    if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
+    if (n_fits < 0 || n_curves < 0 || n_rows < 0 || n < 0) return fail(ctx, TLS_E_ARG, "event vetting: negative count");
+    if (max_epochs < 1 || max_epochs > TLS_TIMES_MAX_EPOCHS) return fail(ctx, TLS_E_ARG, "event vetting: max_epochs out of range [1, 65536]");
+    if (!(std::isfinite(depth_min) && depth_min >= 0.0)) return fail(ctx, TLS_E_ARG, "event vetting: depth_min must be finite and >= 0");
+    if (std::isnan(min_ses)) return fail(ctx, TLS_E_ARG, "event vetting: min_ses is NaN");
+    if (!(chase_fraction > 0.0 && chase_fraction <= 1.0)) return fail(ctx, TLS_E_ARG, "event vetting: chase_fraction out of range (0, 1]");
+    if (!(chase_min >= 0.0 && chase_min <= 1.0)) return fail(ctx, TLS_E_ARG, "event vetting: chase_min out of range [0, 1]");
+    if (!(point_fraction > 0.0)) return fail(ctx, TLS_E_ARG, "event vetting: point_fraction must be > 0");
+    if (!(step_fraction > 0.0)) return fail(ctx, TLS_E_ARG, "event vetting: step_fraction must be > 0");
+    if (n_fits == 0) return TLS_OK;
+    if (n_rows < 1) return fail(ctx, TLS_E_ARG, "event vetting: at least one row is needed");
+    if (!shape_values || !shape_offset || !width || !span_max) return fail(ctx, TLS_E_ARG, "event vetting: null argument");
+    if (n_rows > TLS_SINGLE_MAX_WIDTH) return fail(ctx, TLS_E_ARG, "event vetting: more rows than widths there are");
+    size_t n_taps = 0;
+    for (int64_t r = 0; r < n_rows; ++r) {
+        if (width[r] < tlsdev::kSingleMinWidth || width[r] > TLS_SINGLE_MAX_WIDTH)
+            return fail(ctx, TLS_E_ARG, "event vetting: width out of range [3, 4096]");
+        if (r > 0 && width[r] <= width[r - 1]) return fail(ctx, TLS_E_ARG, "event vetting: the widths must be strictly ascending");
+        if (shape_offset[r] < 0) return fail(ctx, TLS_E_ARG, "event vetting: negative shape offset");
+        if (!(std::isfinite(span_max[r]) && span_max[r] >= 0.0)) return fail(ctx, TLS_E_ARG, "event vetting: span_max must be finite and >= 0");
+        n_taps += (size_t)width[r];
+    }
+    if (!t || !y || !dy || !curve || !period || !T0 || !row || !reach || !chase_reach || !guard || !chase_span || !out || !out_events)
+        return fail(ctx, TLS_E_ARG, "event vetting: null argument");
+    if (n < 1 || n > tlsdev::kTimesMaxPoints) return fail(ctx, TLS_E_ARG, "event vetting: n out of range [1, 2^30]");
+    if (n_fits > INT32_MAX || (uint64_t)n_curves > (uint64_t)(INT64_MAX / 16) / (uint64_t)n)
+        return fail(ctx, TLS_E_ARG, "event vetting: batch too large");
+    for (int64_t i = 0; i < n; ++i)
+        if (!std::isfinite(t[i]) || (i > 0 && t[i] < t[i - 1]))
+            return fail(ctx, TLS_E_ARG, "event vetting: the time stamps must be finite and non-decreasing");
+    for (int64_t f = 0; f < n_fits; ++f) {
+        if (curve[f] < 0 || curve[f] >= n_curves) return fail(ctx, TLS_E_ARG, "event vetting: curve out of range [0, n_curves)");
+        if (row[f] < 0 || row[f] >= n_rows) return fail(ctx, TLS_E_ARG, "event vetting: row out of range [0, n_rows)");
+        if (reach[f] < 1 || reach[f] > TLS_TIMES_MAX_REACH) return fail(ctx, TLS_E_ARG, "event vetting: reach out of range [1, 4096]");
+        if (chase_reach[f] < 0 || chase_reach[f] > TLS_EVENTS_MAX_CHASE)
+            return fail(ctx, TLS_E_ARG, "event vetting: chase_reach out of range [0, 8192]");
+        if (guard[f] < 0) return fail(ctx, TLS_E_ARG, "event vetting: negative guard");
+        if (!(std::isfinite(chase_span[f]) && chase_span[f] > 0.0))
+            return fail(ctx, TLS_E_ARG, "event vetting: chase_span must be finite and > 0");
+    }
+    // the rows and their taps: pairs (b, b * b)
+    std::vector<tlsdev::SingleRow> h_rows((size_t)n_rows);
+    std::vector<double> h_taps(2 * n_taps);
+    size_t at = 0;
+    for (int64_t r = 0; r < n_rows; ++r) {
+        h_rows[(size_t)r].width = (int)width[r];
+        h_rows[(size_t)r].offset = (int)at;
+        h_rows[(size_t)r].span_max = span_max[r];
+        const double* b = shape_values + shape_offset[r];
+        for (int64_t j = 0; j < width[r]; ++j, ++at) {
+            const double v = b[j];
+            h_taps[2 * at] = v;
+            h_taps[2 * at + 1] = v * v;
+        }
+    }
+    TLS_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t nn = (size_t)n, me = (size_t)max_epochs;
+    const size_t sum_words = tlsdev::kEventsSummaryWords, event_words = (size_t)tlsdev::kEventsRecordWords * me;
+    // a slab: at most 1024 candidates on at most 1024 curves, 256 MB of curves (32 bytes a point) and 256 MB of event records
+    // and held sums (16 doubles an epoch)
+    const size_t budget = 256u << 20;
+    const size_t cs = std::max<size_t>(1, std::min<size_t>({(size_t)n_curves, 1024, budget / (32 * nn)}));
+    const size_t sl = std::max<size_t>(1, std::min<size_t>({(size_t)n_fits, 1024, budget / (8 * (event_words + 2 * me))}));
+    // of one slab: pairs | held | y | dy | summaries | events | period | T0 | chase_span | slot, row, reach, chase, guard;
+    // t | rows | taps
+    TLS_HIP(ctx, ctx->d_vetting.reserve(4 * cs * nn + sl * (2 * me + sum_words + event_words + 3) + (5 * sl + 1) / 2
+                                        + nn + 2 * (size_t)n_rows + 2 * n_taps));
+    double2* d_pairs = reinterpret_cast<double2*>(ctx->d_vetting.ptr);         // (the allocation's start: 16-byte aligned)
+    double2* d_held = d_pairs + cs * nn;
+    double* d_y = ctx->d_vetting.ptr + 2 * cs * nn + 2 * sl * me;
+    double* d_dy = d_y + cs * nn;
+    double* d_out = d_dy + cs * nn;
+    double* d_out_events = d_out + sl * sum_words;
+    double* d_period = d_out_events + sl * event_words;
+    double* d_T0 = d_period + sl;
+    double* d_span = d_T0 + sl;
+    int* d_ints = reinterpret_cast<int*>(d_span + sl);
+    double* d_t = d_span + sl + (5 * sl + 1) / 2;
+    tlsdev::SingleRow* d_rows = reinterpret_cast<tlsdev::SingleRow*>(d_t + nn);
+    double* d_taps = d_t + nn + 2 * (size_t)n_rows;
+    if (!ctx->d_check.ptr) {
+        TLS_HIP(ctx, ctx->d_check.reserve(tlsdev::kChecks));
+        TLS_HIP(ctx, hipMemsetAsync(ctx->d_check.ptr, 0, tlsdev::kChecks * sizeof(unsigned long long), ctx->stream));
+    }
+    tlsdev::TimesPairsArgs p;
+    p.y = d_y; p.dy = d_dy; p.pairs = d_pairs;
+    tlsdev::EventsArgs a;
+    a.t = d_t; a.pairs = d_pairs; a.rows = d_rows; a.taps = d_taps;
+    a.slot = d_ints; a.row = d_ints + sl; a.reach = d_ints + 2 * sl; a.chase = d_ints + 3 * sl; a.guard = d_ints + 4 * sl;
+    a.period = d_period; a.T0 = d_T0; a.chase_span = d_span; a.out = d_out; a.out_events = d_out_events; a.held = d_held;
+    a.check = ctx->d_check.ptr;
+    a.depth_min = depth_min; a.min_ses = min_ses; a.chase_fraction = chase_fraction; a.chase_min = chase_min;
+    a.point_fraction = point_fraction; a.step_fraction = step_fraction; a.n = (int)n; a.max_epochs = (int)max_epochs;
+    auto pairs_kernel = tlsdev::tls_times_pairs_kernel;
+    auto events_kernel = tlsdev::tls_event_vetting_kernel;
+    TLS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(events_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     tlsdev::kTimesLdsUnits * 8));
+    TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_rows, h_rows.data(), (size_t)n_rows * sizeof(tlsdev::SingleRow), hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_taps, h_taps.data(), 2 * n_taps * 8, hipMemcpyHostToDevice, ctx->stream));
+    std::vector<int> h_ints(5 * sl);
+    std::unordered_map<int64_t, int> slot_of;
+    struct Run { int64_t curve; size_t slot, count; };      // consecutive curves in consecutive slots: one copy
+    std::vector<Run> runs;
+    for (int64_t f0 = 0; f0 < n_fits;) {
+        slot_of.clear();
+        runs.clear();
+        size_t fits = 0, lds = 0;
+        while (f0 + (int64_t)fits < n_fits && fits < sl) {
+            const int64_t f = f0 + (int64_t)fits;
+            auto it = slot_of.find(curve[f]);
+            if (it == slot_of.end()) {
+                if (slot_of.size() == cs) break;     // (the next slab takes it; a slab's first candidate always finds a slot)
+                const size_t slot = slot_of.size();
+                it = slot_of.emplace(curve[f], (int)slot).first;
+                if (!runs.empty() && runs.back().curve + (int64_t)runs.back().count == curve[f]) ++runs.back().count;
+                else runs.push_back(Run{curve[f], slot, 1});
+            }
+            h_ints[fits] = it->second;
+            h_ints[sl + fits] = (int)row[f];
+            h_ints[2 * sl + fits] = (int)reach[f];
+            h_ints[3 * sl + fits] = (int)chase_reach[f];
+            h_ints[4 * sl + fits] = (int)std::min(guard[f], chase_reach[f]);   // (a guard at or beyond the reach: no chase window)
+            lds = std::max(lds, tlsdev::times_lds_bytes((int)reach[f], (int)max_epochs));
+            ++fits;
+        }
+        for (const Run& run : runs) {
+            const size_t from = (size_t)run.curve * nn, to = run.slot * nn, bytes = run.count * nn * 8;
+            TLS_HIP(ctx, hipMemcpyAsync(d_y + to, y + from, bytes, hipMemcpyHostToDevice, ctx->stream));
+            TLS_HIP(ctx, hipMemcpyAsync(d_dy + to, dy + from, bytes, hipMemcpyHostToDevice, ctx->stream));
+        }
+        TLS_HIP(ctx, hipMemcpyAsync(d_ints, h_ints.data(), 5 * sl * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(d_period, period + f0, fits * 8, hipMemcpyHostToDevice, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(d_T0, T0 + f0, fits * 8, hipMemcpyHostToDevice, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(d_span, chase_span + f0, fits * 8, hipMemcpyHostToDevice, ctx->stream));
+        p.count = (long long)(slot_of.size() * nn);
+        const unsigned blocks = (unsigned)std::min<long long>((p.count + tlsdev::kTimesThreads - 1) / tlsdev::kTimesThreads, 8192);
+        hipLaunchKernelGGL(pairs_kernel, dim3(blocks), dim3(tlsdev::kTimesThreads), 0, ctx->stream, p);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(events_kernel, dim3((unsigned)fits), dim3(tlsdev::kEventsThreads), lds, ctx->stream, a);
+            e = hipGetLastError();
+        }
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(ctx->stream);
+            return fail(ctx, TLS_E_HIP, std::string("event vetting launch: ") + hipGetErrorString(e));
+        }
+        ctx->last_kernel = "tls_event_vetting";
+        TLS_HIP(ctx, hipMemcpyAsync(out + f0, d_out, fits * sum_words * 8, hipMemcpyDeviceToHost, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(out_events + (size_t)f0 * me, d_out_events, fits * event_words * 8, hipMemcpyDeviceToHost, ctx->stream));
+        // (the next slab overwrites the device buffers and h_ints; h_rows and h_taps are read until the stream is done)
         TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
         f0 += (int64_t)fits;
     }

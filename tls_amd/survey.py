@@ -323,7 +323,10 @@ def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_ar
                 shape_fit_window=2.0, shape_fit_min_count=3, sine_test=False, sine_test_mask=1.5,
                 sine_test_harmonics=(0.5, 1.0, 2.0), ephemeris_match=False, ephemeris_match_drift=0.5,
                 ephemeris_match_epoch=0.5, ephemeris_match_max_ratio=3, views=False, views_global_bins=2001,
-                views_local_bins=201, views_local_durations=4.0, views_local_width=0.16, **power_kwargs):
+                views_local_bins=201, views_local_durations=4.0, views_local_width=0.16, event_vetting=False,
+                event_vetting_search=1.0, event_vetting_chase_window=0.1, event_vetting_guard=1.5, event_vetting_min_ses=3.0,
+                event_vetting_chase_fraction=0.6, event_vetting_chase_min=0.5, event_vetting_point_fraction=0.5,
+                event_vetting_step_fraction=0.5, **power_kwargs):
     """Survey-mode power(): for every light curve of `flux_batch` what `transitleastsquares(t, flux).power(**kwargs)`
     reports as SDE, SDE_raw, chi2_min, period, T0, depth and duration (fractional, lc_cache_overview["duration"] of
     the template row at the chi^2 minimum, main.py:199-200) -- search, SDE spectra and final T0 fit all on the
@@ -434,6 +437,18 @@ def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_ar
     of the result stays as it is, bit for bit.  views without peak_fits, or with a bad table, raises ValueError before any
     device work.
 
+    event_vetting=True (with peak_fits=True) vets the INDIVIDUAL events of every fitted peak -- is each unique in its
+    neighbourhood, does it rest on one sample, does the flux come back to the baseline, does the candidate survive without
+    its bad events or its strongest one (event_vetting below states it) -- in one call of tls_event_vetting behind the
+    search, on the device that searched the curve and on the rows it searched, from the period of the peak and T0 and
+    duration_days of its fit record, with event_vetting's defaults for gap_tolerance and transit_depth_min;
+    event_vetting_search, _chase_window, _guard, _min_ses, _chase_fraction, _chase_min, _point_fraction and _step_fraction
+    are its parameters of those names.  The `peaks` array gains, behind every other group, the fields event_summary_fields()
+    with the prefix ev_ (ev_status 1 and the others NaN where status != 0), and the peaks dict `events`, a structured array
+    [n_curves, K, max_epochs] with the fields event_fields() (max_epochs: the most epochs a period of the grid can have).
+    Everything else of the result stays as it is, bit for bit.  event_vetting without peak_fits, or with a bad parameter,
+    raises ValueError before any device work.
+
     Returns (summary, periods[, chi2, row, depth, power][, per_transit][, models][, peaks]): summary is a numpy structured
     array with the fields of tls_power_summary plus "duration" (and the statistics on request)."""
     return _power_batch(t, flux_batch, dy_batch, power_kwargs, context=context, device=device, devices=devices,
@@ -449,7 +464,12 @@ def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_ar
                         ephemeris_match=_ephemeris_match_request(ephemeris_match, peak_fits, ephemeris_match_drift,
                                                                  ephemeris_match_epoch, ephemeris_match_max_ratio),
                         views=_views_request(views, peak_fits, views_global_bins, views_local_bins, views_local_durations,
-                                             views_local_width))
+                                             views_local_width),
+                        event_vetting=_event_vetting_request(event_vetting, peak_fits, event_vetting_search,
+                                                             event_vetting_chase_window, event_vetting_guard,
+                                                             event_vetting_min_ses, event_vetting_chase_fraction,
+                                                             event_vetting_chase_min, event_vetting_point_fraction,
+                                                             event_vetting_step_fraction))
 
 
 def _peaks_request(peaks, separation, ratios, min_power, models=False, peak_fits=False):
@@ -610,7 +630,7 @@ def find_peaks(power, periods, k, separation=0.02, ratios=HARMONICS, min_power=N
 def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=None, devices=None, with_arrays=False,
                  statistics=False, per_transit=False, models=False, spectra=False, detrend=None, peaks=None,
                  peak_fits=False, phase_scan=None, transit_times=None, shape_fit=None, sine_test=None, ephemeris_match=None,
-                 views=None):
+                 views=None, event_vetting=None):
     """power_batch; spectra=True (power_results) also returns SR and power_raw [n_curves, n_periods] behind the arrays;
     peaks: None or a checked request (_peaks_request); peak_fits: with peaks, their T0 fits and statistics; phase_scan: None or a checked
     request (_phase_scan_request), with peak_fits, the fits' phase scans; transit_times: None or a checked request
@@ -618,7 +638,8 @@ def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=Non
     (_shape_fit_request), with peak_fits, the fits' shape fits; sine_test: None or a checked request (_sine_test_request),
     with peak_fits, the fits' sine tests; ephemeris_match: None or a checked request (_ephemeris_match_request), with
     peak_fits, the match of the fitted peaks across the curves; views: None or a checked request (_views_request), with
-    peak_fits, the fits' folded views."""
+    peak_fits, the fits' folded views; event_vetting: None or a checked request (_event_vetting_request), with peak_fits, the
+    fits' event vetting."""
     models = bool(models)
     per_transit = bool(per_transit or models)
     statistics = bool(statistics or per_transit)
@@ -645,7 +666,7 @@ def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=Non
     if peak_fits:
         kw.update(peak_fits=(fill_factor, root, root_count, max_epochs), phase_scan=phase_scan)
 
-    if transit_times is not None:
+    if transit_times is not None or event_vetting is not None:
         from ._lib import TIMES_MAX_EPOCHS
         tt_epochs = min(max_epochs, TIMES_MAX_EPOCHS)
 
@@ -667,6 +688,9 @@ def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=Non
             (part["views_records"], part["views_global"], part["views_global_count"], part["views_local"],
              part["views_local_count"]) = _peak_views(ctx, inp, y_rows[lo:hi], part["peaks"], part["peak_fits"],
                                                       part["phase_scans"] if phase_scan is not None else None, views)
+        if event_vetting is not None:
+            part["ev_summaries"], part["ev_events"] = _peak_event_vetting(
+                ctx, inp, y_rows[lo:hi], dy_rows[lo:hi], part["peaks"], part["peak_fits"], event_vetting, tt_epochs)
         return part
 
     out = _run_batch(devices, device, context, len(y_rows), call)
@@ -740,6 +764,9 @@ def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=Non
                                          out["views_local"].reshape((-1,) + out["views_local"].shape[2:]),
                                          out["views_local_count"].reshape((-1,) + out["views_local_count"].shape[2:]),
                                          lead=out["views_records"].shape)
+        if event_vetting is not None:
+            found["peaks"] = _with_events(found["peaks"], out["ev_summaries"])
+            found["events"] = out["ev_events"]
         result += (found,)
     if spectra:
         result += (out["SR"], out["power_raw"])
@@ -1142,6 +1169,212 @@ def transit_times(t, flux_batch, period, T0, duration, curve=None, dy_batch=None
     eph, times = ctx.transit_times(inp["t"], y_rows, dy_rows, period, T0, row, reach, widths, shapes, span_max, curve=curve,
                                    depth_min=depth_min, min_ses=min_ses, max_epochs=max_epochs)
     return eph, _with_oc(eph, times)
+
+
+# ---- per-transit event vetting ---------------------------------------------------------------------------------------------
+EVENT_VETTING_CHASE_WINDOW = 0.1
+EVENT_VETTING_GUARD = 1.5
+
+
+def event_summary_fields():
+    """The fields of a candidate's event vetting, in order: those of tls_event_summary.  power_batch(...,
+    event_vetting=True) adds each to the `peaks` array behind the prefix ev_."""
+    from ._lib import EVENT_SUMMARY_FIELDS
+    return tuple(EVENT_SUMMARY_FIELDS)
+
+
+def event_fields():
+    """The fields of one vetted event, in order: those of tls_event_record -- epoch, status, time_linear, ses, depth,
+    depth_err, index, point_share, before, after, chases, chase_dt, n_chased, flags."""
+    from ._lib import EVENT_RECORD_FIELDS
+    return tuple(EVENT_RECORD_FIELDS)
+
+
+def _event_vetting_options(search, chase_window, guard, min_ses, chase_fraction, chase_min, point_fraction, step_fraction,
+                           gap_tolerance=TRANSIT_TIMES_GAP_TOLERANCE, transit_depth_min=0.0, max_epochs=None):
+    """The options of event_vetting, checked, as a dict: search, min_ses, gap_tolerance, depth_min and max_epochs as
+    _transit_times_options checks them (its messages headed "event vetting"); chase_window a number, finite and > 0; guard a
+    number, finite and >= 0; the four parameters as _lib.event_vetting_options checks them.  ValueError otherwise."""
+    import numbers
+    from ._lib import event_vetting_options
+    try:
+        search, min_ses, gap_tolerance, depth_min, max_epochs = _transit_times_options(search, min_ses, gap_tolerance,
+                                                                                       transit_depth_min, max_epochs)
+    except ValueError as e:
+        raise ValueError(str(e).replace("transit times", "event vetting"))
+    for name, v, low in (("chase_window", chase_window, False), ("guard", guard, True)):
+        if isinstance(v, (bool, numpy.bool_)) or not isinstance(v, numbers.Real) \
+                or not ((0.0 <= float(v) if low else 0.0 < float(v)) and float(v) < numpy.inf):
+            raise ValueError("event vetting: %s must be finite and %s 0, got %r" % (name, ">=" if low else ">", v))
+    chase_fraction, chase_min, point_fraction, step_fraction = event_vetting_options(chase_fraction, chase_min, point_fraction,
+                                                                                     step_fraction)
+    return dict(search=search, chase_window=float(chase_window), guard=float(guard), min_ses=min_ses,
+                chase_fraction=chase_fraction, chase_min=chase_min, point_fraction=point_fraction,
+                step_fraction=step_fraction, gap_tolerance=gap_tolerance, depth_min=depth_min, max_epochs=max_epochs)
+
+
+def _event_vetting_request(event_vetting, peak_fits, search, chase_window, guard, min_ses, chase_fraction, chase_min,
+                           point_fraction, step_fraction):
+    """None, or the checked options of an event_vetting=True request (ValueError for a bad one, and for event_vetting
+    without peak_fits)."""
+    if not event_vetting:
+        return None
+    if not peak_fits:
+        raise ValueError("event_vetting=True needs peak_fits=True: the events start from T0 and duration of the fits")
+    return _event_vetting_options(search, chase_window, guard, min_ses, chase_fraction, chase_min, point_fraction,
+                                  step_fraction)
+
+
+def event_vetting_rows(t, period, duration, search=1.0, chase_window=EVENT_VETTING_CHASE_WINDOW, guard=EVENT_VETTING_GUARD,
+                       gap_tolerance=TRANSIT_TIMES_GAP_TOLERANCE):
+    """(widths, span_max, row, reach, chase_reach, guard, chase_span) of event_vetting for candidates of `period` and
+    `duration` [n_fits] (days) on the time stamps t: the four arrays of transit_time_rows, and with dt = median(diff(t)) and
+    L_f the candidate's width, chase_reach_f = min(int(chase_window * P_f / dt), 8192) samples, guard_f = int(guard * L_f)
+    samples and chase_span_f = chase_window * P_f days.  Where the cap of 8192 samples bites, the span stays
+    chase_window * P: `chases` keeps its meaning as a fraction of the period, and the windows beyond the cap are not looked
+    at.  A period that is not finite and > 0 gets chase_reach 0 and chase_span 1 (the device reports status 1)."""
+    from ._lib import EVENTS_MAX_CHASE
+    widths, span_max, row, reach = transit_time_rows(t, period, duration, search, gap_tolerance)
+    dt = float(numpy.median(numpy.diff(numpy.asarray(t, dtype=numpy.float64))))
+    period = numpy.atleast_1d(numpy.asarray(period, dtype=numpy.float64))
+    chase_reach = numpy.zeros(len(period), dtype=numpy.int64)
+    guards = numpy.zeros(len(period), dtype=numpy.int64)
+    chase_span = numpy.ones(len(period), dtype=numpy.float64)
+    for f, P in enumerate(period):
+        guards[f] = int(float(guard) * int(widths[row[f]]))
+        if 0.0 < P < numpy.inf:
+            span = float(chase_window) * float(P)
+            if 0.0 < span < numpy.inf:
+                chase_reach[f] = int(min(span / dt, float(EVENTS_MAX_CHASE)))
+                chase_span[f] = span
+    return widths, span_max, row, reach, chase_reach, guards, chase_span
+
+
+def _with_events(records, summaries):
+    """The peaks (with whatever they carry) plus the ev_ fields of the device's event summaries."""
+    names = event_summary_fields()
+    out = numpy.zeros(records.shape, dtype=records.dtype.descr + [("ev_" + k, "f8") for k in names])
+    for k in records.dtype.names:
+        out[k] = records[k]
+    for k in names:
+        out["ev_" + k] = summaries[k]
+    return out
+
+
+def _peak_event_vetting(ctx, inp, y_rows, dy_rows, peaks, fits, request, max_epochs):
+    """(summaries [n_curves, K], events [n_curves, K, max_epochs]) of the peaks of a slice of the batch, on ctx.  Every peak
+    is a candidate, as in _peak_transit_times: a peak whose fit status is not 0 goes in without an ephemeris and comes back
+    as the statement has it, status 1 and NaN in every other field."""
+    from .template import reference_transit
+    n_curves, k = fits.shape
+    fitted = (fits["status"] == 0).reshape(-1)
+    period = numpy.where(fitted, peaks["period"].reshape(-1), numpy.nan)
+    T0 = numpy.where(fitted, fits["T0"].reshape(-1), numpy.nan)
+    row, reach = numpy.zeros(n_curves * k, dtype=numpy.int64), numpy.ones(n_curves * k, dtype=numpy.int64)
+    chase_reach, guard = numpy.zeros(n_curves * k, dtype=numpy.int64), numpy.zeros(n_curves * k, dtype=numpy.int64)
+    chase_span = numpy.ones(n_curves * k)
+    widths, span_max = numpy.array([3], dtype=numpy.int64), [0.0]        # (no fitted peak: one row nobody reads)
+    if fitted.any():
+        (widths, span_max, row[fitted], reach[fitted], chase_reach[fitted], guard[fitted],
+         chase_span[fitted]) = event_vetting_rows(inp["t"], period[fitted], fits["duration_days"].reshape(-1)[fitted],
+                                                  request["search"], request["chase_window"], request["guard"])
+    shapes = [1.0 - numpy.asarray(reference_transit(int(L), **inp["shape"])) for L in widths]
+    out, events = ctx.event_vetting(inp["t"], y_rows, dy_rows, period, T0, row, reach, chase_reach, guard, chase_span, widths,
+                                    shapes, span_max, curve=numpy.repeat(numpy.arange(n_curves), k),
+                                    min_ses=request["min_ses"], chase_fraction=request["chase_fraction"],
+                                    chase_min=request["chase_min"], point_fraction=request["point_fraction"],
+                                    step_fraction=request["step_fraction"], max_epochs=int(max_epochs))
+    return out.reshape(n_curves, k), events.reshape(n_curves, k, int(max_epochs))
+
+
+def event_vetting(t, flux_batch, period, T0, duration, curve=None, dy_batch=None, search=1.0,
+                  chase_window=EVENT_VETTING_CHASE_WINDOW, guard=EVENT_VETTING_GUARD, min_ses=3.0, chase_fraction=0.6,
+                  chase_min=0.5, point_fraction=0.5, step_fraction=0.5, gap_tolerance=TRANSIT_TIMES_GAP_TOLERANCE,
+                  transit_depth_min=0.0, max_epochs=None, detrend=None, context=None, device=None, **template_kwargs):
+    """The vetting of the INDIVIDUAL events of candidates the caller holds, on the device (tls_event_vetting): candidate f is
+    (period[f], T0[f], duration[f] in days) on light curve curve[f] of flux_batch [n_curves, n] (or one row [n]) over the
+    ascending time stamps t; curve=None takes one candidate a curve, in order.  It needs no search.  Every other vetting test
+    judges the stacked signal; a candidate of three to six transits can be three unrelated events -- an outlier, a sensitivity
+    step with its recovery, a detrending wiggle -- that line up on a linear ephemeris, and passes them all.  These tests are
+    the Kepler Robovetter's individual transit metrics (Thompson et al. 2018, A.3.7): Chases, Marshall / Zuma in the plain
+    form of a one-sample and a baseline test, and Rubble as the counts.
+
+    Rows, template, reach, y and dy are those of transit_times (transit_time_rows); with dt = median(diff(t)),
+    chase_reach_f = min(int(chase_window * P_f / dt), 8192), guard_f = int(guard * L_f), chase_span_f = chase_window * P_f
+    (event_vetting_rows).
+
+        every epoch: the held window as transit_times finds it (the largest q = N / sqrt(D) over the shifts): ses, depth, index
+            point_share = (the largest term of N) / N                        > point_fraction: the event rests on one sample
+            before, after = the mean dip of the L samples on either side of the window, over the depth
+                                                                             > step_fraction: the flux is not at the baseline
+            chase: every window centred guard_f + 1 .. chase_reach_f samples to either side of the event; one whose
+                |q'| >= chase_fraction * q is comparable (a bump counts as a dip does);  chase_dt = the distance in days to the
+                nearest comparable one;  chases = min(chase_dt / chase_span, 1), 1 without one  < chase_min: not unique
+            flags = 1 (ses < min_ses) | 2 (point) | 4 (step) | 8 (chased); an event without a flag is good
+        the candidate: n_held, n_good; mes = SN / sqrt(SD) over the held events, mes_good over the good ones, mes_rest over all
+            but the strongest; ses_max, its epoch and dominance = ses_max / mes; depth_mean and the chi^2 of the events' depths
+            about it; the least and the mean chases
+
+    mes is formed from every event's BEST shift, so it is biased upward against a strictly linear ephemeris: compare it with
+    mes_good and mes_rest, which are formed the same way, not with the search's SNR.  Event status: 0 an event is held; 1 no
+    window with a dip.  Candidate status as transit_times has it.
+
+    Each step is one IEEE double operation and every sum runs in index order (the chase's minimum and count do not depend on
+    an order), so the result is bit-equal to the Python statement in tests/event_vetting_spec.py.  The arguments are checked
+    as transit_times checks its own; chase_window finite and > 0, guard finite and >= 0, chase_fraction in (0, 1], chase_min
+    in [0, 1], point_fraction and step_fraction > 0: ValueError otherwise, before any device work.  detrend= takes the steps
+    and tuples of search_batch.
+
+    Returns (summary, events): a structured array [n_fits] with the fields event_summary_fields() and one [n_fits,
+    max_epochs] with the fields event_fields(); NaN past a candidate's n_epochs."""
+    o = _event_vetting_options(search, chase_window, guard, min_ses, chase_fraction, chase_min, point_fraction, step_fraction,
+                               gap_tolerance, transit_depth_min, max_epochs)
+    t = numpy.asarray(t, dtype=numpy.float64)
+    if numpy.ndim(flux_batch) == 1:
+        flux_batch = numpy.asarray(flux_batch)[None, :]
+        dy_batch = None if dy_batch is None else numpy.asarray(dy_batch)[None, :]
+    if numpy.ndim(flux_batch) != 2 or t.ndim != 1 or numpy.shape(flux_batch)[1] != len(t):
+        raise ValueError("flux_batch must be [n] or [n_curves, n] over the time stamps t [n]")
+    if not numpy.all(numpy.isfinite(t)) or not numpy.all(t[1:] >= t[:-1]):
+        raise ValueError("event vetting: t must be finite and non-decreasing")
+    try:
+        period, T0, duration = (numpy.atleast_1d(numpy.asarray(v, dtype=numpy.float64)) for v in (period, T0, duration))
+    except (TypeError, ValueError):
+        raise ValueError("event vetting: period, T0 and duration must be numbers")
+    if period.ndim != 1 or not period.shape == T0.shape == duration.shape:
+        raise ValueError("event vetting: period, T0 and duration must be [n_fits]")
+    n_curves = numpy.shape(flux_batch)[0]
+    if curve is None:
+        if len(period) != n_curves:
+            raise ValueError("event vetting: curve=None takes one candidate a light curve: %d candidates, %d curves"
+                             % (len(period), n_curves))
+        curve = numpy.arange(n_curves)
+    curve = numpy.atleast_1d(numpy.asarray(curve))
+    if curve.shape != period.shape or (curve.size and (curve.dtype.kind not in "iu" or curve.min() < 0
+                                                        or curve.max() >= n_curves)):
+        raise ValueError("event vetting: curve must hold one index in [0, %d) a candidate" % n_curves)
+    try:
+        widths, span_max, row, reach, chase_reach, guards, chase_span = event_vetting_rows(
+            t, period, duration, o["search"], o["chase_window"], o["guard"], o["gap_tolerance"])
+    except ValueError as e:
+        raise ValueError(str(e).replace("transit times", "event vetting"))
+    max_epochs = o["max_epochs"]
+    if max_epochs is None:
+        from ._lib import TIMES_MAX_EPOCHS
+        counts = _epoch_counts(t, period, T0)
+        counts = counts[(counts >= 1.0) & (counts <= TIMES_MAX_EPOCHS)]
+        max_epochs = int(counts.max()) if len(counts) else 1
+    flux_batch = _detrended(t, flux_batch, detrend, context, device, None, dy_batch)
+    kwargs = dict(template_kwargs)
+    kwargs.setdefault("oversampling_factor", 1)      # (the period grid of the plan inputs is not used: the coarsest will do)
+    inp, y_rows, dy_rows = _batch_inputs(t, flux_batch, dy_batch, kwargs)
+    from .template import reference_transit
+    shapes = [1.0 - numpy.asarray(reference_transit(int(L), **inp["shape"])) for L in widths]
+    ctx = context if context is not None else _search.default_context(device)
+    return ctx.event_vetting(inp["t"], y_rows, dy_rows, period, T0, row, reach, chase_reach, guards, chase_span, widths, shapes,
+                             span_max, curve=curve, depth_min=o["depth_min"], min_ses=o["min_ses"],
+                             chase_fraction=o["chase_fraction"], chase_min=o["chase_min"], point_fraction=o["point_fraction"],
+                             step_fraction=o["step_fraction"], max_epochs=max_epochs)
 
 
 # ---- trapezoid shape fit and transit geometry --------------------------------------------------------------------------------
