@@ -41,7 +41,7 @@ extern "C" {
  * tls_debug_peak_phase_scans), (7: tls_sysrem), (7: tls_single_transits), (7: tls_transit_times),
  * (7: tls_shape_fit), (7: tls_nudft, tls_lomb_scargle, tls_sine_test); 8: every entry that takes `root, n_root` takes a
  * second table, `root, root_count, n_root`), (8: tls_ephemeris_match), (8: tls_folded_views),
- * (8: tls_event_vetting). */
+ * (8: tls_event_vetting), (8: tls_centroid_test). */
 #define TLS_AMD_ABI_VERSION 8
 
 #define TLS_OK 0
@@ -844,6 +844,59 @@ int tls_shape_fit(tls_ctx *ctx, const double *t, const double *y, const double *
                   const double *period, const double *T0, const double *duration, const int64_t *curve, int64_t n_fits,
                   const double *ratio, int64_t nT, const double *ingress, int64_t nQ, const double *shift, int64_t nS,
                   double window, int64_t min_count, double depth_min, tls_shape_record *out /* [n_fits] */);
+
+/* The centroid-shift test: WHICH star dims.  A background eclipsing binary a few pixels from the target, diluted to a
+ * planet-like depth, passes every test of the flux alone; the flux-weighted photocentre of the aperture (MOM_CENTR1/2 of a
+ * Kepler, K2 or TESS light-curve file, on the flux's own time stamps) moves in transit when the dimming source is not at the
+ * photocentre (Bryson et al. 2013, PASP 125, 889; Twicken et al. 2018, PASP 130, 064502).  The transit template at the
+ * candidate's ephemeris is regressed on three series -- the flux deficit 1 - y, the column centroid cx and the row centroid
+ * cy -- over the points within `window` durations of every transit, with a free baseline in every epoch (centroids drift
+ * with the pointing).  For a curve (y, cx, cy [n]) over the ascending, finite t [n], a candidate (P, T0, d in days) and the
+ * shape b [L] (1 - the limb-darkened reference transit: 0 out of transit, 1 at the bottom):
+ *   status 1 and NaN in every other field unless P, T0, d finite, P > 0, d > 0 and wd = window * d < 0.5 * P
+ *   points, i ascending:  x = (t[i] - T0) / P;  k = floor(x + 0.5);  tau = (x - k) * P
+ *       member iff fabs(tau) <= wd and cx[i], cy[i] both finite;  its epoch is k
+ *       v = tau / d + 0.5;  inside iff 0 <= v <= 1
+ *       s = 0.0 if not inside, else  u = v * (L - 1);  j = min(floor(u), L - 2);  fr = u - j;  s = b[j] + (b[j+1] - b[j]) * fr
+ *   status 2 (n_points = the members, the rest NaN) if the epochs holding a member are more than max_epochs
+ *   epoch k, its members in index order:  m = count;  m_in = count(inside);  used iff m_in >= min_in and m - m_in >= min_out
+ *       Ss = Ss + s;  sbar = Ss / m;  for each channel c in (1 - y, cx, cy):  Sc = Sc + c;  cbar = Sc / m          (pass 1)
+ *       ds = s - sbar;  De = De + ds * ds;  dc = c - cbar;  Ne[c] = Ne[c] + ds * dc;  Qe[c] = Qe[c] + dc * dc      (pass 2)
+ *   used epochs ascending:  D = D + De;  N[c] = N[c] + Ne[c];  Q[c] = Q[c] + Qe[c];  n_points += m;  n_in += m_in
+ *   status 2 (n_epochs, n_skipped, n_points, n_in reported, the rest NaN) unless n_used >= 1 and D > 0
+ *   A[c] = N[c] / D;  dof = n_points - n_used - 1
+ *   var[c] = (Q[c] - A[c] * N[c]) / dof where dof >= 1 and that is > 0, else NaN
+ *   err[c] = sqrt(var[c] / D);  rms[c] = sqrt(var[c])
+ *   chi2[c] = sum over the used epochs with De > 0, ascending, of  r = Ne[c] / De - A[c];  (r * r) * De,  then / var[c]
+ * A linear drift across a window is orthogonal to the symmetric template, so the constant of an epoch is enough for a slow
+ * pointing drift, and what it leaves inflates rms, not the shift.  chi2 has n_epochs - 1 degrees of freedom: a shift that
+ * one event carries is a systematic, not a source.  Every step is one IEEE double operation in the stated order: the record
+ * equals the Python statement in tests/centroid_spec.py bit for bit.  All fields are doubles. */
+#define TLS_CENTROID_MAX_EPOCHS 65536
+#define TLS_CENTROID_MAX_SHAPE 1048576
+typedef struct tls_centroid_record {
+    double status;                 /* 0 measured; 1 no such candidate (P, T0, d, or a window of half a period or more); 2 too
+                                      many epochs, no usable epoch, or no point on the template's slope */
+    double n_epochs, n_skipped;    /* the used epochs; epochs with members that are not used */
+    double n_points, n_in;         /* members of the used epochs; those inside the transit */
+    double depth, depth_err;       /* A, err of 1 - y: the depth measured on the same points in the same way */
+    double shift_x, shift_x_err;   /* A, err of cx: the in-transit shift of the photocentre, in the unit of cx */
+    double shift_y, shift_y_err;   /* of cy */
+    double rms_x, rms_y;           /* the scatter of the centroid residuals */
+    double chi2_depth, chi2_x, chi2_y;     /* the epochs' own amplitudes about the common one */
+} tls_centroid_record;
+/* n_fits candidates (period[f], T0[f], duration[f]) on the curves curve[f] of y, cx, cy [n_curves][n] over the shared time
+ * stamps t [n]; shape [L].  out [n_fits].  Needs no plan and no search, and leaves a prepared plan as it is.  n_fits == 0 is
+ * a no-op.  Candidates are processed in slabs, so device memory stays bounded for any n_fits.  TLS_E_ARG, before any device
+ * work and with the output untouched, for a curve[f] outside [0, n_curves), n outside [1, 2^22], negative counts, L outside
+ * [2, TLS_CENTROID_MAX_SHAPE], a shape value that is not finite, a window that is not finite and >= 1, min_in < 1,
+ * min_out < 1, max_epochs outside [1, TLS_CENTROID_MAX_EPOCHS], and a t that is not finite and non-decreasing.  y is taken
+ * as it is (finite); cx and cy may hold NaN and infinities (the point is skipped); period, T0 and duration may hold any
+ * value (status 1). */
+int tls_centroid_test(tls_ctx *ctx, const double *t, const double *y, const double *cx, const double *cy, int64_t n,
+                      int64_t n_curves, const double *period, const double *T0, const double *duration, const int64_t *curve,
+                      int64_t n_fits, const double *shape, int64_t L, double window, int64_t min_in, int64_t min_out,
+                      int64_t max_epochs, tls_centroid_record *out /* [n_fits] */);
 
 /* The folded views of a candidate: its light curve folded at the ephemeris and binned by the MEDIAN on a fixed number of
  * bins -- the "global view" and "local view" of Shallue & Vanderburg (2018, AJ 155, 94), and the even, odd and

@@ -56,6 +56,16 @@ EVENTS_MAX_CHASE = 8192      # include/tls_amd.h TLS_EVENTS_MAX_CHASE: the wides
 SHAPE_MAX_UNITS = 65536
 SHAPE_MAX_POINTS = 1 << 22
 SHAPE_LDS_MEMBERS = 2048
+# include/tls_amd.h TLS_CENTROID_MAX_EPOCHS, TLS_CENTROID_MAX_SHAPE: the most epochs of a candidate of tls_centroid_test and
+# the most samples of its shape; tls_centroid.hip.h kCentroidMaxPoints, kCentroidThreads and kCentroidLdsEpochs (the epochs of
+# a candidate the LDS holds; later ones keep their sums in device scratch); CENTROID_SHAPE_SAMPLES: the samples
+# survey.centroid_test takes of the reference transit
+CENTROID_MAX_EPOCHS = 65536
+CENTROID_MAX_SHAPE = 1 << 20
+CENTROID_MAX_POINTS = 1 << 22
+CENTROID_THREADS = 256
+CENTROID_LDS_EPOCHS = 256
+CENTROID_SHAPE_SAMPLES = 1025
 # include/tls_amd.h TLS_VIEWS_MAX_BINS: the most bins of a view of tls_folded_views; tls_views.hip.h kViewsMaxPoints,
 # kViewsLdsPoints (the points of a series the LDS holds; a longer one is ordered in device scratch), kViewsLaneMembers (a bin
 # of up to this many members is selected by one lane, a larger one by a wave) and kViewsSlab (the candidates of a launch)
@@ -95,7 +105,7 @@ SYMBOLS = (
     "tls_biweight_detrend", "tls_sysrem", "tls_find_peaks", "tls_power_batch_peaks", "tls_power_batch_peak_fits", "tls_debug_peak_fits",
     "tls_phase_scan", "tls_power_batch_phase_scan", "tls_debug_peak_phase_scans", "tls_single_transits",
     "tls_transit_times", "tls_shape_fit", "tls_nudft", "tls_lomb_scargle", "tls_sine_test",
-    "tls_ephemeris_match", "tls_folded_views", "tls_event_vetting",
+    "tls_ephemeris_match", "tls_folded_views", "tls_event_vetting", "tls_centroid_test",
     "tls_comm_unique_id", "tls_comm_init", "tls_comm_destroy", "tls_comm_info", "tls_comm_allgather_results", "tls_comm_allgather_device", "tls_comm_fetch_gathered",
     "tls_comm_stage_results", "tls_comm_allgather_staged", "tls_comm_fetch_staged",
     "tls_comm_barrier", "tls_comm_max",
@@ -637,6 +647,86 @@ def shape_fit_arguments(t, y, dy, period, T0, duration, ratios, ingress, shifts,
                 min_count=min_count, depth_min=depth_min)
 
 
+# tls_centroid_record (include/tls_amd.h): a candidate's centroid-shift test, 16 doubles
+CENTROID_FIELDS = ("status", "n_epochs", "n_skipped", "n_points", "n_in", "depth", "depth_err", "shift_x", "shift_x_err",
+                   "shift_y", "shift_y_err", "rms_x", "rms_y", "chi2_depth", "chi2_x", "chi2_y")
+
+
+class CentroidRecord(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_double) for k in CENTROID_FIELDS]
+
+
+CENTROID_DTYPE = numpy.dtype([(k, "f8") for k in CENTROID_FIELDS])
+
+
+def centroid_options(window=3.0, min_in=1, min_out=3, max_epochs=CENTROID_MAX_EPOCHS):
+    """(window, min_in, min_out, max_epochs) as tls_centroid_test takes them, checked as it checks them: window a finite
+    number >= 1; min_in and min_out integers >= 1; max_epochs an integer in [1, CENTROID_MAX_EPOCHS].  ValueError otherwise."""
+    if isinstance(window, (bool, numpy.bool_)) or not isinstance(window, numbers.Real) or not (1.0 <= float(window) < numpy.inf):
+        raise ValueError("centroid test: window must be finite and >= 1, got %r" % (window,))
+    for name, v in (("min_in", min_in), ("min_out", min_out)):
+        if isinstance(v, (bool, numpy.bool_)) or not isinstance(v, numbers.Integral) or int(v) < 1:
+            raise ValueError("centroid test: %s must be an integer >= 1, got %r" % (name, v))
+    if isinstance(max_epochs, (bool, numpy.bool_)) or not isinstance(max_epochs, numbers.Integral) \
+            or not 1 <= int(max_epochs) <= CENTROID_MAX_EPOCHS:
+        raise ValueError("centroid test: max_epochs must be an integer in [1, %d], got %r" % (CENTROID_MAX_EPOCHS, max_epochs))
+    return float(window), int(min_in), int(min_out), int(max_epochs)
+
+
+def centroid_rows(cx, cy, shape):
+    """(cx, cy) as float64 arrays of `shape` = flux_batch's ([n_curves, n]; one row [n] is taken as [1, n]); any value, NaN
+    and infinities included (the device skips such a point).  ValueError for anything else."""
+    rows = []
+    for name, v in (("cx", cx), ("cy", cy)):
+        try:
+            v = numpy.asarray(v, dtype=numpy.float64)
+        except (TypeError, ValueError):
+            raise ValueError("centroid test: %s must hold numbers" % name)
+        if v.ndim == 1:
+            v = v[None, :]
+        if v.shape != tuple(shape):
+            raise ValueError("centroid test: %s must have the shape of the flux, %s, got %s" % (name, tuple(shape), v.shape))
+        rows.append(numpy.ascontiguousarray(v))
+    return rows[0], rows[1]
+
+
+def centroid_arguments(t, y, cx, cy, period, T0, duration, shape, curve=None, window=3.0, min_in=1, min_out=3,
+                       max_epochs=CENTROID_MAX_EPOCHS):
+    """What tls_centroid_test takes, checked as it checks them and packed for it -- a dict with t [n] (1-D, n in
+    [1, CENTROID_MAX_POINTS], finite and non-decreasing), y [n_curves, n] (finite), cx and cy of y's shape (centroid_rows),
+    period, T0, duration, curve [n_fits] (shape_fit_candidates), shape [L] (1-D, L in [2, CENTROID_MAX_SHAPE], finite) and
+    window, min_in, min_out, max_epochs (centroid_options).  ValueError otherwise.  GPU-free."""
+    window, min_in, min_out, max_epochs = centroid_options(window, min_in, min_out, max_epochs)
+    try:
+        shape = numpy.ascontiguousarray(numpy.asarray(shape, dtype=numpy.float64))
+    except (TypeError, ValueError):
+        raise ValueError("centroid test: the shape must hold numbers")
+    if shape.ndim != 1 or not 2 <= len(shape) <= CENTROID_MAX_SHAPE:
+        raise ValueError("centroid test: the shape must be [L] with L in [2, %d], got %s" % (CENTROID_MAX_SHAPE, shape.shape))
+    if not numpy.all(numpy.isfinite(shape)):
+        raise ValueError("centroid test: the shape must be finite")
+    t = numpy.asarray(t, dtype=numpy.float64)
+    if t.ndim != 1 or not 1 <= len(t) <= CENTROID_MAX_POINTS:
+        raise ValueError("centroid test: t must have shape [n] with n in [1, %d], got %s" % (CENTROID_MAX_POINTS, t.shape))
+    if not numpy.all(numpy.isfinite(t)) or not numpy.all(t[1:] >= t[:-1]):
+        raise ValueError("centroid test: t must be finite and non-decreasing")
+    y = numpy.asarray(y, dtype=numpy.float64)
+    if y.ndim == 1:
+        y = y[None, :]
+    if y.ndim != 2 or y.shape[1] != len(t):
+        raise ValueError("centroid test: y must be [n] or [n_curves, n] over the time stamps t [n]")
+    if y.size and not numpy.all(numpy.isfinite(y)):
+        raise ValueError("centroid test: y has a NaN or an infinite value")
+    cx, cy = centroid_rows(cx, cy, y.shape)
+    try:
+        period, T0, duration, curve = shape_fit_candidates(period, T0, duration, curve, len(y))
+    except ValueError as e:
+        raise ValueError(str(e).replace("shape fit", "centroid test"))
+    return dict(t=numpy.ascontiguousarray(t), y=numpy.ascontiguousarray(y), cx=cx, cy=cy, period=period, T0=T0,
+                duration=duration, curve=curve, shape=shape, window=window, min_in=min_in, min_out=min_out,
+                max_epochs=max_epochs)
+
+
 # tls_views_record (include/tls_amd.h): a candidate's folded views, 7 doubles; the local views in the order of the arrays
 VIEWS_FIELDS = ("status", "secondary_status", "n_global", "n_local", "n_local_even", "n_local_odd", "n_secondary")
 VIEWS_LOCAL = ("local", "local_even", "local_odd", "secondary")
@@ -1010,6 +1100,10 @@ def load():
     lib.tls_shape_fit.argtypes = [vp, _c_double_p, _c_double_p, _c_double_p, i64, i64, _c_double_p, _c_double_p, _c_double_p,
                                   _c_int64_p, i64, _c_double_p, i64, _c_double_p, i64, _c_double_p, i64, dbl, i64, dbl,
                                   ctypes.c_void_p]
+    lib.tls_centroid_test.restype = ci
+    lib.tls_centroid_test.argtypes = [vp, _c_double_p, _c_double_p, _c_double_p, _c_double_p, i64, i64, _c_double_p,
+                                      _c_double_p, _c_double_p, _c_int64_p, i64, _c_double_p, i64, dbl, i64, i64, i64,
+                                      ctypes.c_void_p]
     lib.tls_nudft.restype = ci
     lib.tls_nudft.argtypes = [vp, _c_double_p, i64, i64, _c_double_p, _c_double_p, i64, _c_double_p]
     lib.tls_lomb_scargle.restype = ci
@@ -1856,6 +1950,23 @@ class Context(object):
             self._h, _dp(a["t"]), _dp(a["y"]), _dp(a["dy"]), n, n_c, _dp(a["period"]), _dp(a["T0"]), _dp(a["duration"]),
             _ip(a["curve"]), n_fits, _dp(a["ratio"]), len(a["ratio"]), _dp(a["ingress"]), len(a["ingress"]), _dp(a["shift"]),
             len(a["shift"]), a["window"], a["min_count"], a["depth_min"], out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def centroid_test(self, t, y, cx, cy, period, T0, duration, shape, curve=None, window=3.0, min_in=1, min_out=3,
+                      max_epochs=CENTROID_MAX_EPOCHS):
+        """The centroid-shift tests (tls_centroid_test; the statement: include/tls_amd.h, tests/centroid_spec.py) of the
+        candidates (period[f], T0[f], duration[f] in days) on the curves curve[f] (None: one candidate a curve, in order) of
+        y, cx, cy [n_curves, n] (or one row) over t [n], with the shape [L] (0 out of transit, 1 at the bottom):
+        CENTROID_DTYPE [n_fits].  ValueError for what centroid_arguments refuses."""
+        a = centroid_arguments(t, y, cx, cy, period, T0, duration, shape, curve, window, min_in, min_out, max_epochs)
+        n_c, n = a["y"].shape
+        n_fits = len(a["period"])
+        out = numpy.zeros(n_fits, dtype=CENTROID_DTYPE)
+        assert CENTROID_DTYPE.itemsize == ctypes.sizeof(CentroidRecord)
+        self._check(self._lib.tls_centroid_test(
+            self._h, _dp(a["t"]), _dp(a["y"]), _dp(a["cx"]), _dp(a["cy"]), n, n_c, _dp(a["period"]), _dp(a["T0"]),
+            _dp(a["duration"]), _ip(a["curve"]), n_fits, _dp(a["shape"]), len(a["shape"]), a["window"], a["min_in"],
+            a["min_out"], a["max_epochs"], out.ctypes.data_as(ctypes.c_void_p)))
         return out
 
     def folded_views(self, t, y, period, T0, duration, curve=None, secondary_phase=None, n_global=2001, n_local=201,

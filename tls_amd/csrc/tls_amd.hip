@@ -229,6 +229,8 @@ struct tls_ctx {
     DevBuf<double> d_vetting;
     // tls_shape_fit: of one slab: pairs | y | dy | records | period | T0 | duration | slot; t | ratio | ingress | shift | scratch
     DevBuf<double> d_shape;
+    // tls_centroid_test: of one slab: y | cx | cy | records | period | T0 | duration | slot; t | shape | scratch
+    DevBuf<double> d_centroid;
     // tls_folded_views: of one slab: y | records | period | T0 | duration | secondary | global and local medians | slot | global
     // and local counts; t | scratch
     DevBuf<double> d_views;
@@ -1664,6 +1666,7 @@ void tls_ctx_destroy(tls_ctx* ctx) {
     ctx->d_times.release();
     ctx->d_vetting.release();
     ctx->d_shape.release();
+    ctx->d_centroid.release();
     ctx->d_views.release();
     ctx->d_gls.release();
     ctx->d_match.release();
@@ -2836,6 +2839,7 @@ int tls_debug_device_bytes(const tls_ctx* ctx, int64_t* total, int64_t* t0_fit_s
     add(ctx->d_times);
     add(ctx->d_vetting);
     add(ctx->d_shape);
+    add(ctx->d_centroid);
     add(ctx->d_views);
     add(ctx->d_gls);
     add(ctx->d_match);
@@ -3792,6 +3796,119 @@ int tls_shape_fit(tls_ctx* ctx, const double* t, const double* y, const double* 
             return fail(ctx, TLS_E_HIP, std::string("shape fit launch: ") + hipGetErrorString(e));
         }
         ctx->last_kernel = "tls_shape_fit";
+        TLS_HIP(ctx, hipMemcpyAsync(out + f0, d_out, fits * words * 8, hipMemcpyDeviceToHost, ctx->stream));
+        // (the next slab overwrites the device buffers and h_slot)
+        TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        f0 += (int64_t)fits;
+    }
+    return TLS_OK;
+}
+
+// ---- the centroid-shift test (tls_centroid.hip.h, DESIGN.md "Centroid test"): the flux and the two centroid rows of the
+// curves a slab of candidates reads, then one workgroup a candidate, slab by slab
+static_assert(sizeof(tls_centroid_record) == tlsdev::kCentroidWords * 8, "tls_centroid_record is the kernel's record");
+static_assert(TLS_CENTROID_MAX_EPOCHS == tlsdev::kCentroidMaxEpochs && TLS_CENTROID_MAX_SHAPE == tlsdev::kCentroidMaxShape,
+              "the header's limits");
+
+int tls_centroid_test(tls_ctx* ctx, const double* t, const double* y, const double* cx, const double* cy, int64_t n,
+                      int64_t n_curves, const double* period, const double* T0, const double* duration, const int64_t* curve,
+                      int64_t n_fits, const double* shape, int64_t L, double window, int64_t min_in, int64_t min_out,
+                      int64_t max_epochs, tls_centroid_record* out) {
+    if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
+    if (n_fits < 0 || n_curves < 0 || n < 0) return fail(ctx, TLS_E_ARG, "centroid test: negative count");
+    if (!(std::isfinite(window) && window >= 1.0)) return fail(ctx, TLS_E_ARG, "centroid test: the window must be finite and >= 1");
+    if (min_in < 1 || min_out < 1) return fail(ctx, TLS_E_ARG, "centroid test: min_in and min_out must be >= 1");
+    if (max_epochs < 1 || max_epochs > TLS_CENTROID_MAX_EPOCHS)
+        return fail(ctx, TLS_E_ARG, "centroid test: max_epochs out of range [1, 65536]");
+    if (L < 2 || L > TLS_CENTROID_MAX_SHAPE) return fail(ctx, TLS_E_ARG, "centroid test: L out of range [2, 2^20]");
+    if (!shape) return fail(ctx, TLS_E_ARG, "null argument");
+    for (int64_t j = 0; j < L; ++j)
+        if (!std::isfinite(shape[j])) return fail(ctx, TLS_E_ARG, "centroid test: the shape must be finite");
+    if (n_fits == 0) return TLS_OK;
+    if (!t || !y || !cx || !cy || !curve || !period || !T0 || !duration || !out) return fail(ctx, TLS_E_ARG, "null argument");
+    if (n < 1 || n > tlsdev::kCentroidMaxPoints) return fail(ctx, TLS_E_ARG, "centroid test: n out of range [1, 2^22]");
+    if (n_fits > INT32_MAX || (uint64_t)n_curves > (uint64_t)(INT64_MAX / 16) / (uint64_t)n)
+        return fail(ctx, TLS_E_ARG, "centroid test: batch too large");
+    for (int64_t i = 0; i < n; ++i)
+        if (!std::isfinite(t[i]) || (i > 0 && t[i] < t[i - 1]))
+            return fail(ctx, TLS_E_ARG, "centroid test: the time stamps must be finite and non-decreasing");
+    for (int64_t f = 0; f < n_fits; ++f)
+        if (curve[f] < 0 || curve[f] >= n_curves) return fail(ctx, TLS_E_ARG, "centroid test: curve out of range [0, n_curves)");
+    TLS_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t nn = (size_t)n, words = tlsdev::kCentroidWords, ll = (size_t)L;
+    // a slab: at most 1024 candidates on at most 1024 curves, 256 MB of curves (24 bytes a point); the workgroups of a launch:
+    // at most 1024, 256 MB of epoch scratch (72 bytes an epoch beyond those the LDS holds)
+    const size_t budget = 256u << 20;
+    const size_t cs = std::max<size_t>(1, std::min<size_t>({(size_t)n_curves, 1024, budget / (24 * nn)}));
+    const size_t sl = std::min<size_t>((size_t)n_fits, 1024);
+    const size_t stretch = max_epochs > tlsdev::kCentroidLdsEpochs
+        ? (size_t)(max_epochs - tlsdev::kCentroidLdsEpochs) * tlsdev::kCentroidEpochWords : 0;
+    const size_t groups = std::max<size_t>(1, std::min<size_t>({sl, (size_t)tlsdev::kCentroidMaxGroups, stretch ? budget / (8 * stretch) : sl}));
+    // of one slab: y | cx | cy | records | period | T0 | duration | slot;  t | shape | scratch
+    TLS_HIP(ctx, ctx->d_centroid.reserve(3 * cs * nn + sl * (words + 3) + (sl + 1) / 2 + nn + ll + groups * stretch));
+    double* d_y = ctx->d_centroid.ptr;
+    double* d_cx = d_y + cs * nn;
+    double* d_cy = d_cx + cs * nn;
+    double* d_out = d_cy + cs * nn;
+    double* d_period = d_out + sl * words;
+    double* d_T0 = d_period + sl;
+    double* d_duration = d_T0 + sl;
+    int* d_slot = reinterpret_cast<int*>(d_duration + sl);
+    double* d_t = d_duration + sl + (sl + 1) / 2;
+    double* d_b = d_t + nn;
+    double* d_scratch = d_b + ll;
+    if (!ctx->d_check.ptr) {
+        TLS_HIP(ctx, ctx->d_check.reserve(tlsdev::kChecks));
+        TLS_HIP(ctx, hipMemsetAsync(ctx->d_check.ptr, 0, tlsdev::kChecks * sizeof(unsigned long long), ctx->stream));
+    }
+    tlsdev::CentroidArgs a;
+    a.t = d_t; a.y = d_y; a.cx = d_cx; a.cy = d_cy; a.slot = d_slot; a.period = d_period; a.T0 = d_T0; a.duration = d_duration;
+    a.shape = d_b; a.scratch = d_scratch; a.out = d_out; a.check = ctx->d_check.ptr; a.window = window;
+    a.n = (int)n; a.L = (int)L; a.max_epochs = (int)max_epochs;
+    a.min_in = (int)std::min<int64_t>(min_in, INT32_MAX);
+    a.min_out = (int)std::min<int64_t>(min_out, INT32_MAX);
+    auto centroid_kernel = tlsdev::tls_centroid_kernel;
+    TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_b, shape, ll * 8, hipMemcpyHostToDevice, ctx->stream));
+    std::vector<int> h_slot(sl);
+    std::unordered_map<int64_t, int> slot_of;
+    struct Run { int64_t curve; size_t slot, count; };      // consecutive curves in consecutive slots: one copy
+    std::vector<Run> runs;
+    for (int64_t f0 = 0; f0 < n_fits;) {
+        slot_of.clear();
+        runs.clear();
+        size_t fits = 0;
+        while (f0 + (int64_t)fits < n_fits && fits < sl) {
+            const int64_t f = f0 + (int64_t)fits;
+            auto it = slot_of.find(curve[f]);
+            if (it == slot_of.end()) {
+                if (slot_of.size() == cs) break;     // (the next slab takes it; a slab's first candidate always finds a slot)
+                const size_t slot = slot_of.size();
+                it = slot_of.emplace(curve[f], (int)slot).first;
+                if (!runs.empty() && runs.back().curve + (int64_t)runs.back().count == curve[f]) ++runs.back().count;
+                else runs.push_back(Run{curve[f], slot, 1});
+            }
+            h_slot[fits] = it->second;
+            ++fits;
+        }
+        for (const Run& run : runs) {
+            const size_t from = (size_t)run.curve * nn, to = run.slot * nn, bytes = run.count * nn * 8;
+            TLS_HIP(ctx, hipMemcpyAsync(d_y + to, y + from, bytes, hipMemcpyHostToDevice, ctx->stream));
+            TLS_HIP(ctx, hipMemcpyAsync(d_cx + to, cx + from, bytes, hipMemcpyHostToDevice, ctx->stream));
+            TLS_HIP(ctx, hipMemcpyAsync(d_cy + to, cy + from, bytes, hipMemcpyHostToDevice, ctx->stream));
+        }
+        TLS_HIP(ctx, hipMemcpyAsync(d_slot, h_slot.data(), fits * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(d_period, period + f0, fits * 8, hipMemcpyHostToDevice, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(d_T0, T0 + f0, fits * 8, hipMemcpyHostToDevice, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(d_duration, duration + f0, fits * 8, hipMemcpyHostToDevice, ctx->stream));
+        a.fits = (int)fits;
+        hipLaunchKernelGGL(centroid_kernel, dim3((unsigned)std::min(fits, groups)), dim3(tlsdev::kCentroidThreads), 0, ctx->stream, a);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(ctx->stream);
+            return fail(ctx, TLS_E_HIP, std::string("centroid test launch: ") + hipGetErrorString(e));
+        }
+        ctx->last_kernel = "tls_centroid_test";
         TLS_HIP(ctx, hipMemcpyAsync(out + f0, d_out, fits * words * 8, hipMemcpyDeviceToHost, ctx->stream));
         // (the next slab overwrites the device buffers and h_slot)
         TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));

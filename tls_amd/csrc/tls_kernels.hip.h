@@ -91,7 +91,8 @@ enum CheckCode {
     kChkSysrem = 11,       // tls_sysrem: a row, a chunk or a component count outside the call's
     kChkSingle = 12,       // tls_single_transits: a window outside the staged slots, or a taken centre, row or window outside the series
     kChkTimes = 13,        // tls_transit_times, tls_event_vetting: a reach or a width outside the entry's limits, or a picked window outside the series
-    kChkShape = 14,        // tls_shape_fit: a member's rank or a unit's table index outside its limits
+    kChkShape = 14,        // tls_shape_fit: a member's rank or a unit's table index outside its limits; tls_centroid_test: a
+                           // shape or an epoch count outside the entry's limits, or an epoch's head outside the series
     kChkViews = 15,        // tls_folded_views: a bin's range outside its part, a member outside the series, or no single middle member
 };
 
@@ -4320,6 +4321,8 @@ __global__ void __launch_bounds__(512) tls_transit_models(const ModelsArgs a) {
 #include "tls_events.hip.h"
 // survey-mode trapezoid shape fit (tls_shape_fit)
 #include "tls_shape.hip.h"
+// survey-mode centroid-shift test of a candidate (tls_centroid_test)
+#include "tls_centroid.hip.h"
 // survey-mode folded, median-binned views of a candidate (tls_folded_views)
 #include "tls_views.hip.h"
 // survey-mode variability periodogram and sine test (tls_nudft, tls_lomb_scargle, tls_sine_test)

@@ -326,7 +326,8 @@ def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_ar
                 views_local_bins=201, views_local_durations=4.0, views_local_width=0.16, event_vetting=False,
                 event_vetting_search=1.0, event_vetting_chase_window=0.1, event_vetting_guard=1.5, event_vetting_min_ses=3.0,
                 event_vetting_chase_fraction=0.6, event_vetting_chase_min=0.5, event_vetting_point_fraction=0.5,
-                event_vetting_step_fraction=0.5, **power_kwargs):
+                event_vetting_step_fraction=0.5, centroids=None, centroid_window=3.0, centroid_min_in=1,
+                centroid_min_out=3, **power_kwargs):
     """Survey-mode power(): for every light curve of `flux_batch` what `transitleastsquares(t, flux).power(**kwargs)`
     reports as SDE, SDE_raw, chi2_min, period, T0, depth and duration (fractional, lc_cache_overview["duration"] of
     the template row at the chi^2 minimum, main.py:199-200) -- search, SDE spectra and final T0 fit all on the
@@ -449,6 +450,16 @@ def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_ar
     Everything else of the result stays as it is, bit for bit.  event_vetting without peak_fits, or with a bad parameter,
     raises ValueError before any device work.
 
+    centroids=(cx_batch, cy_batch) (with peak_fits=True) -- the flux-weighted centroids of the apertures, of flux_batch's
+    shape and on its time stamps, in any unit, NaN where a cadence has none -- measures the in-transit shift of the
+    photocentre of every fitted peak (centroid_test below states it): WHICH star dims.  One call of tls_centroid_test behind
+    the search, on the device that searched the curve, on the flux rows it searched and the centroid rows of the same curves
+    (they are never detrended), from the period of the peak and T0 and duration_days of its fit record, with the search's
+    template; centroid_window, centroid_min_in and centroid_min_out are centroid_test's window, min_in and min_out.  The
+    `peaks` array gains, behind every other group, the fields centroid_fields() (cen_status 1 and the others NaN where
+    status != 0).  Everything else of the result stays as it is, bit for bit.  centroids without peak_fits, of another shape
+    than flux_batch, or with a bad parameter, raises ValueError before any device work.
+
     Returns (summary, periods[, chi2, row, depth, power][, per_transit][, models][, peaks]): summary is a numpy structured
     array with the fields of tls_power_summary plus "duration" (and the statistics on request)."""
     return _power_batch(t, flux_batch, dy_batch, power_kwargs, context=context, device=device, devices=devices,
@@ -469,7 +480,9 @@ def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_ar
                                                              event_vetting_chase_window, event_vetting_guard,
                                                              event_vetting_min_ses, event_vetting_chase_fraction,
                                                              event_vetting_chase_min, event_vetting_point_fraction,
-                                                             event_vetting_step_fraction))
+                                                             event_vetting_step_fraction),
+                        centroids=_centroid_request(centroids, peak_fits, numpy.shape(flux_batch), centroid_window,
+                                                    centroid_min_in, centroid_min_out))
 
 
 def _peaks_request(peaks, separation, ratios, min_power, models=False, peak_fits=False):
@@ -630,7 +643,7 @@ def find_peaks(power, periods, k, separation=0.02, ratios=HARMONICS, min_power=N
 def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=None, devices=None, with_arrays=False,
                  statistics=False, per_transit=False, models=False, spectra=False, detrend=None, peaks=None,
                  peak_fits=False, phase_scan=None, transit_times=None, shape_fit=None, sine_test=None, ephemeris_match=None,
-                 views=None, event_vetting=None):
+                 views=None, event_vetting=None, centroids=None):
     """power_batch; spectra=True (power_results) also returns SR and power_raw [n_curves, n_periods] behind the arrays;
     peaks: None or a checked request (_peaks_request); peak_fits: with peaks, their T0 fits and statistics; phase_scan: None or a checked
     request (_phase_scan_request), with peak_fits, the fits' phase scans; transit_times: None or a checked request
@@ -639,7 +652,7 @@ def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=Non
     with peak_fits, the fits' sine tests; ephemeris_match: None or a checked request (_ephemeris_match_request), with
     peak_fits, the match of the fitted peaks across the curves; views: None or a checked request (_views_request), with
     peak_fits, the fits' folded views; event_vetting: None or a checked request (_event_vetting_request), with peak_fits, the
-    fits' event vetting."""
+    fits' event vetting; centroids: None or a checked request (_centroid_request), with peak_fits, the fits' centroid tests."""
     models = bool(models)
     per_transit = bool(per_transit or models)
     statistics = bool(statistics or per_transit)
@@ -669,6 +682,9 @@ def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=Non
     if transit_times is not None or event_vetting is not None:
         from ._lib import TIMES_MAX_EPOCHS
         tt_epochs = min(max_epochs, TIMES_MAX_EPOCHS)
+    if centroids is not None:
+        from ._lib import CENTROID_MAX_EPOCHS
+        cen_epochs = min(max_epochs, CENTROID_MAX_EPOCHS)
 
     def call(ctx, lo, hi):
         part = ctx._power_batch(inp["t"], y_rows[lo:hi], dy_rows[lo:hi], inp["periods"], inp["table"], inp["params"],
@@ -691,6 +707,10 @@ def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=Non
         if event_vetting is not None:
             part["ev_summaries"], part["ev_events"] = _peak_event_vetting(
                 ctx, inp, y_rows[lo:hi], dy_rows[lo:hi], part["peaks"], part["peak_fits"], event_vetting, tt_epochs)
+        if centroids is not None:
+            # (the centroid rows of the curves this device searched, beside their flux rows)
+            part["centroid_tests"] = _peak_centroid_tests(ctx, inp, y_rows[lo:hi], centroids["cx"][lo:hi], centroids["cy"][lo:hi],
+                                                          part["peaks"], part["peak_fits"], centroids, cen_epochs)
         return part
 
     out = _run_batch(devices, device, context, len(y_rows), call)
@@ -767,6 +787,8 @@ def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=Non
         if event_vetting is not None:
             found["peaks"] = _with_events(found["peaks"], out["ev_summaries"])
             found["events"] = out["ev_events"]
+        if centroids is not None:
+            found["peaks"] = _with_centroids(found["peaks"], out["centroid_tests"])
         result += (found,)
     if spectra:
         result += (out["SR"], out["power_raw"])
@@ -1528,6 +1550,185 @@ def shape_fit(t, flux_batch, period, T0, duration, curve=None, dy_batch=None, ra
     out = ctx.shape_fit(inp["t"], y_rows, dy_rows, period, T0, duration, ratio, ingress, shift, curve=curve, window=window,
                         min_count=min_count, depth_min=depth_min)
     return _with_shapes(None, out, period)
+
+
+# ---- centroid-shift test ------------------------------------------------------------------------------------------------------
+def centroid_fields():
+    """The fields of a centroid test, in order -- what centroid_test returns and power_batch(..., centroids=(cx, cy)) adds to
+    the `peaks` array: the fields of tls_centroid_record, each behind the prefix cen_ (cen_status first), then what
+    centroid_offsets forms of them on the host: cen_shift, cen_significance, cen_offset_x, cen_offset_y, cen_offset,
+    cen_offset_err."""
+    from ._lib import CENTROID_FIELDS
+    return tuple("cen_" + k for k in CENTROID_FIELDS) + ("cen_shift", "cen_significance", "cen_offset_x", "cen_offset_y",
+                                                         "cen_offset", "cen_offset_err")
+
+
+def centroid_offsets(depth, depth_err, shift_x, shift_x_err, shift_y, shift_y_err):
+    """(shift, significance, offset_x, offset_y, offset, offset_err) of a measured in-transit shift (sx +- ex, sy +- ey) of
+    the photocentre and the depth D +- eD measured on the same points.  Plain numpy on the host, broadcasting.
+
+        shift = sqrt(sx^2 + sy^2);  significance = sqrt((sx / ex)^2 + (sy / ey)^2)
+        offset_x = -sx (1 - D) / D;  offset_y = -sy (1 - D) / D;  offset = shift (1 - D) / D
+        offset_err^2 = ((1 - D) / D)^2 (sx^2 ex^2 + sy^2 ey^2) / shift^2 + (shift / D^2)^2 eD^2
+
+    The photocentre of an aperture is the flux-weighted mean of its stars.  When a star at position r (relative to the
+    out-of-transit photocentre) loses the share D of the aperture's flux, the photocentre moves by -r D / (1 - D): the offset
+    is r, the position of the DIMMING source, in the unit of the centroids (pixels), and offset_err its error to first order
+    in the errors of the shift and of the depth.  significance is, without a shift, a chi variable of 2 degrees of freedom:
+    5 is exceeded by chance 4e-6 of the time.  All six are NaN where depth <= 0 or an input is NaN; offset_err also where the
+    shift is exactly 0."""
+    D, eD, sx, ex, sy, ey = numpy.broadcast_arrays(*(numpy.asarray(v, dtype=numpy.float64)
+                                                     for v in (depth, depth_err, shift_x, shift_x_err, shift_y, shift_y_err)))
+    with numpy.errstate(all="ignore"):
+        good = D > 0.0
+        shift = numpy.sqrt(sx * sx + sy * sy)
+        significance = numpy.sqrt((sx / ex) ** 2 + (sy / ey) ** 2)
+        lever = (1.0 - D) / D
+        offset_x, offset_y, offset = -sx * lever, -sy * lever, shift * lever
+        var_shift = (sx * sx * ex * ex + sy * sy * ey * ey) / (shift * shift)
+        offset_err = numpy.sqrt(lever * lever * var_shift + (shift / (D * D)) ** 2 * eD * eD)
+    return tuple(numpy.where(good, v, numpy.nan) for v in (shift, significance, offset_x, offset_y, offset, offset_err))
+
+
+def _centroid_shape(inp):
+    """The shape tls_centroid_test takes: 1 - the search's reference transit on CENTROID_SHAPE_SAMPLES samples (0 out of
+    transit, 1 at the bottom)."""
+    from ._lib import CENTROID_SHAPE_SAMPLES
+    from .template import reference_transit
+    return 1.0 - reference_transit(CENTROID_SHAPE_SAMPLES, **inp["shape"])
+
+
+def _centroid_request(centroids, peak_fits, flux_shape, window, min_in, min_out):
+    """None, or the checked request of centroids=(cx_batch, cy_batch): a dict with cx, cy (float64, of the flux's shape),
+    window, min_in, min_out (ValueError for a bad one, and for centroids without peak_fits)."""
+    if centroids is None:
+        return None
+    if not peak_fits:
+        raise ValueError("centroids=(cx, cy) needs peak_fits=True: the test starts from T0 and duration of the fits")
+    from ._lib import centroid_options, centroid_rows
+    window, min_in, min_out, _ = centroid_options(window, min_in, min_out)
+    try:
+        cx, cy = centroids
+    except (TypeError, ValueError):
+        raise ValueError("centroids must be the pair (cx_batch, cy_batch)")
+    if len(flux_shape) != 2:
+        raise ValueError("flux_batch must have shape [n_curves, len(t)]")
+    cx, cy = centroid_rows(cx, cy, flux_shape)
+    return dict(cx=cx, cy=cy, window=window, min_in=min_in, min_out=min_out)
+
+
+def _with_centroids(records, tests):
+    """`records` (None, or the peaks with their fits) plus the device's centroid records and what centroid_offsets forms of
+    them."""
+    names = centroid_fields()
+    base = [] if records is None else records.dtype.descr
+    out = numpy.zeros(tests.shape, dtype=base + [(k, "f8") for k in names])
+    if records is not None:
+        for k in records.dtype.names:
+            out[k] = records[k]
+    for k, source in zip(names, tests.dtype.names):
+        out[k] = tests[source]
+    (out["cen_shift"], out["cen_significance"], out["cen_offset_x"], out["cen_offset_y"], out["cen_offset"],
+     out["cen_offset_err"]) = centroid_offsets(tests["depth"], tests["depth_err"], tests["shift_x"], tests["shift_x_err"],
+                                               tests["shift_y"], tests["shift_y_err"])
+    return out
+
+
+def _peak_centroid_tests(ctx, inp, y_rows, cx_rows, cy_rows, peaks, fits, request, max_epochs):
+    """The centroid records [n_curves, K] of the peaks of a slice of the batch, on ctx.  Every peak is a candidate, so the
+    device writes the whole table in place: a peak whose fit status is not 0 goes in as (NaN, NaN, NaN) and comes back as the
+    statement has it, status 1 and NaN in every other field."""
+    n_curves, k = fits.shape
+    fitted = (fits["status"] == 0).reshape(-1)
+    period = numpy.where(fitted, peaks["period"].reshape(-1), numpy.nan)
+    T0 = numpy.where(fitted, fits["T0"].reshape(-1), numpy.nan)
+    duration = numpy.where(fitted, fits["duration_days"].reshape(-1), numpy.nan)
+    out = ctx.centroid_test(inp["t"], y_rows, cx_rows, cy_rows, period, T0, duration, _centroid_shape(inp),
+                            curve=numpy.repeat(numpy.arange(n_curves), k), window=request["window"],
+                            min_in=request["min_in"], min_out=request["min_out"], max_epochs=max_epochs)
+    return out.reshape(n_curves, k)
+
+
+def centroid_epochs(t, period):
+    """The max_epochs centroid_test takes by default: the most epochs a candidate of these periods can have on t, at most
+    CENTROID_MAX_EPOCHS (periods that are not finite and > 0 have no epochs)."""
+    from ._lib import CENTROID_MAX_EPOCHS
+    t, period = numpy.asarray(t, dtype=numpy.float64), numpy.asarray(period, dtype=numpy.float64)
+    real = period[numpy.isfinite(period) & (period > 0.0)]
+    if len(t) == 0 or len(real) == 0:
+        return 1
+    with numpy.errstate(all="ignore"):
+        most = numpy.ceil((t[-1] - t[0]) / numpy.min(real)) + 2.0
+    return int(min(max(most, 1.0), CENTROID_MAX_EPOCHS))
+
+
+def centroid_test(t, flux_batch, cx_batch, cy_batch, period, T0, duration, curve=None, window=3.0, min_in=1, min_out=3,
+                  max_epochs=None, detrend=None, context=None, device=None, **power_kwargs):
+    """WHICH star dims: the in-transit shift of the flux-weighted photocentre of candidates the caller holds, on the device
+    (tls_centroid_test).  Candidate f is (period[f], T0[f], duration[f] in days) on light curve curve[f] of flux_batch
+    [n_curves, n] (or one row [n]) over the ascending time stamps t; curve=None takes one candidate a curve, in order.
+    cx_batch and cy_batch, of flux_batch's shape, are the column and row centroids of the aperture on the same cadences
+    (MOM_CENTR1, MOM_CENTR2 of a Kepler, K2 or TESS light-curve file), in any unit; a cadence whose centroid is NaN or
+    infinite is skipped.  It needs no search.  A background eclipsing binary a few pixels from the target, diluted to a
+    planet-like depth, passes every test of the flux alone; the photocentre gives it away.
+
+    The search's limb-darkened template (power_kwargs: the keywords of power()) at the candidate's ephemeris, s = 1 at the
+    bottom and 0 out of transit, is regressed on three series -- the flux deficit 1 - y, cx and cy -- over the points within
+    window * duration of every transit, with a free constant in every epoch, because centroids drift with the pointing:
+
+        status 1 and NaN in every other field unless P, T0, d finite, P > 0, d > 0 and wd = window * d < 0.5 * P
+        points, i ascending:  x = (t[i] - T0) / P;  k = floor(x + 0.5);  tau = (x - k) * P
+            member iff |tau| <= wd and cx[i], cy[i] both finite;  its epoch is k;  inside iff |tau| <= d / 2
+        an epoch is used iff it has min_in members inside and min_out outside;  status 2 without a used epoch, or with more
+            epochs than max_epochs (default: the most the shortest period can have on t, at most 65536)
+        in every used epoch the means of s and of the three series are taken off;  D = sum ds^2,  N = sum ds dc,  Q = sum dc^2
+        amplitude A = N / D;  var = (Q - A N) / (n_points - n_epochs - 1);  err = sqrt(var / D);  rms = sqrt(var)
+        chi2 = sum over the used epochs of (A_epoch - A)^2 D_epoch / var:  n_epochs - 1 degrees of freedom
+
+    tests/centroid_spec.py states every step, and the result is bit-equal to it.  A linear drift across a window is orthogonal
+    to the symmetric template, so the constant is enough for a slow pointing drift; what it leaves inflates rms, not the
+    shift.  The flux is detrended where detrend= asks for it (the steps and tuples of search_batch); the centroids never are.
+
+    How to read it.  cen_shift_x, cen_shift_y are the motion of the photocentre in transit and cen_significance its
+    distance from zero in sigmas.  An isolated target gives no shift and an offset of 0: the dimming star is at the
+    photocentre.  In a crowded aperture the photocentre is not on the target, so even a true planet gives a shift: what
+    counts is cen_offset_x, cen_offset_y -- the position of the dimming source relative to the out-of-transit photocentre
+    (centroid_offsets) -- held against the target's catalogue position relative to that photocentre, not the shift against
+    zero.  A cen_chi2_x or cen_chi2_y far above cen_n_epochs - 1 says single events carry the shift: a systematic, not a
+    source.  cen_depth is the depth measured in the same way on the same points.
+
+    window must be finite and >= 1, min_in and min_out integers >= 1, max_epochs in [1, 65536]; cx_batch and cy_batch of
+    flux_batch's shape; period, T0, duration and curve [n_fits] with curve in [0, n_curves): ValueError otherwise, before
+    any device work (the detrending included).
+
+    Returns a structured array [n_fits] with the fields centroid_fields(): cen_status (0 measured; 1 no such candidate; 2
+    no usable epoch, or too many), cen_n_epochs, cen_n_skipped, cen_n_points, cen_n_in, cen_depth, cen_depth_err,
+    cen_shift_x, cen_shift_x_err, cen_shift_y, cen_shift_y_err, cen_rms_x, cen_rms_y, cen_chi2_depth, cen_chi2_x,
+    cen_chi2_y, and cen_shift, cen_significance, cen_offset_x, cen_offset_y, cen_offset, cen_offset_err (NaN where
+    cen_depth is not > 0)."""
+    from ._lib import centroid_options, centroid_rows, shape_fit_candidates
+    t = numpy.asarray(t, dtype=numpy.float64)
+    if numpy.ndim(flux_batch) == 1:
+        flux_batch = numpy.asarray(flux_batch)[None, :]
+    if numpy.ndim(flux_batch) != 2 or t.ndim != 1 or numpy.shape(flux_batch)[1] != len(t):
+        raise ValueError("flux_batch must be [n] or [n_curves, n] over the time stamps t [n]")
+    if not numpy.all(numpy.isfinite(t)) or not numpy.all(t[1:] >= t[:-1]):
+        raise ValueError("centroid test: t must be finite and non-decreasing")
+    cx_rows, cy_rows = centroid_rows(cx_batch, cy_batch, numpy.shape(flux_batch))
+    try:
+        period, T0, duration, curve = shape_fit_candidates(period, T0, duration, curve, numpy.shape(flux_batch)[0])
+    except ValueError as e:
+        raise ValueError(str(e).replace("shape fit", "centroid test"))
+    window, min_in, min_out, max_epochs = centroid_options(window, min_in, min_out,
+                                                           centroid_epochs(t, period) if max_epochs is None else max_epochs)
+    flux_batch = _detrended(t, flux_batch, detrend, context, device, None, None)
+    kwargs = dict(power_kwargs)
+    kwargs.setdefault("oversampling_factor", 1)      # (the period grid of the plan inputs is not used: the coarsest will do)
+    inp, y_rows, _ = _batch_inputs(t, flux_batch, None, kwargs)
+    ctx = context if context is not None else _search.default_context(device)
+    out = ctx.centroid_test(inp["t"], y_rows, cx_rows, cy_rows, period, T0, duration, _centroid_shape(inp), curve=curve,
+                            window=window, min_in=min_in, min_out=min_out, max_epochs=max_epochs)
+    return _with_centroids(None, out)
 
 
 # ---- folded, median-binned views ------------------------------------------------------------------------------------------------
