@@ -109,7 +109,8 @@ int tls_set_options(tls_ctx *ctx, const tls_options *opt);
  * sort2, split, split_batch (series in the HBM slab: prefix-sum mode, sort, two-role kernel), threads, blocks, plan_threads
  * (launch shape, host planning), t0_rot (0: the final T0 fit checks every pair of every epoch), prune_min_live, band_max,
  * perm_table (the four-slot kernel's per-plan table of folded orders: 0 none, k > 0 at most k MiB), reg_scan, dense_hoist (its row
- * layout and its fast-mode dense predicate: 0 the former forms).  A context starts with the values
+ * layout and its fast-mode dense predicate: 0 the former forms), claim_ahead (the tickets of its period queue: bit 0 a
+ * workgroup's first ticket is its index; 0 every ticket is drawn from the queue word).  A context starts with the values
  * of the TLS_<NAME> environment variables, read once per process; no call reads the environment after that.
  * tls_debug_get_switches writes all of them as "name=value,name=value" (ctx NULL: the process's) -- the text
  * tls_period_costs takes, so that the planning call prices the kernel the searching context will run. */

@@ -136,7 +136,7 @@ class Options(ctypes.Structure):
 # every switch tls_debug_set_switch knows (the two public ones included): Context.set_options(**switches) takes them all
 SWITCH_NAMES = ("exact_prefix", "slim", "prune", "screen32", "no_screen", "fast_slab", "x_staged", "split", "split_batch", "sort2",
                 "threads", "blocks", "plan_threads", "t0_rot", "prune_min_live", "perm_table", "reg_scan", "dense_hoist",
-                "band_max")
+                "claim_ahead", "band_max")
 
 
 def switches_text(switches):
@@ -2143,15 +2143,16 @@ class Context(object):
     def phase_cycles(self):
         """Developer instrumentation: per-phase shader-cycle sums of the last
         execute(phase_clock=True)."""
-        arr = (ctypes.c_uint64 * 41)()
-        self._check(self._lib.tls_debug_phase_cycles(self._h, arr, 41))
+        arr = (ctypes.c_uint64 * 42)()
+        self._check(self._lib.tls_debug_phase_cycles(self._h, arr, 42))
         names = ("fold_count", "scan", "scatter", "rank", "gather_patch", "cumsum", "batch_prefix",
                  "chi2", "e_convert", "predicate_strided", "cumsum_blocks", "cumsum_fallbacks",
                  "tile_staging", "predicate_dense", "cs_A", "cs_B1", "cs_B2", "cs_scan", "screen_split", "screen_resolve",
                  "tile_wait", "chi2_wait", "prune_e2", "prune_bounds", "prune_incumbent", "select_relist",
                  "slab_copy_in", "slab_copy_out", "part_fold", "part_scan", "part_lds", "part_store",
                  "stat_live_units", "stat_kept_units", "stat_singles", "stat_batches", "stat_pruned_periods",
-                 "stat_exact_retries", "stat_screen_parked", "stat_screen_valued", "stat_register_scans")
+                 "stat_exact_retries", "stat_screen_parked", "stat_screen_valued", "stat_register_scans",
+                 "claim")   # (four-slot kernel: a period's last barrier to the next period's first phase)
         return dict(zip(names, [int(v) for v in arr]))
 
     def period_cycles(self):

@@ -64,7 +64,7 @@ const SwitchName kSwitchNames[] = {
     TLS_SW(sort2, "TLS_SORT2", 0), TLS_SW(threads, "TLS_THREADS", 0), TLS_SW(blocks, "TLS_BLOCKS", 0),
     TLS_SW(plan_threads, "TLS_PLAN_THREADS", 0), TLS_SW(t0_rot, "TLS_T0_ROT", 0), TLS_SW(prune_min_live, "TLS_PRUNE_MIN_LIVE", 1),
     TLS_SW(perm_table, "TLS_PERM_TABLE", 1), TLS_SW(reg_scan, "TLS_REG_SCAN", 0),
-    TLS_SW(dense_hoist, "TLS_DENSE_HOIST", 0),
+    TLS_SW(dense_hoist, "TLS_DENSE_HOIST", 0), TLS_SW(claim_ahead, "TLS_CLAIM_AHEAD", 0),
     TLS_SW(band_max, "TLS_BAND_MAX", 2),
 };
 #undef TLS_SW
@@ -639,6 +639,7 @@ int enqueue(tls_ctx* ctx, bool count_work, bool phase_clock = false, double* deb
     a.check = ctx->d_check.ptr;
 #endif
     a.queue = ctx->d_squeue.ptr;
+    a.claim_ahead = 0;
     a.scratch = ctx->d_scratch.ptr;
     a.scratch_stride = (long long)(ctx->plan.uniform ? 2 : 3) * ((ctx->plan.M + 1 + ctx->plan.region_pad + 1) & ~1);   // even regions (kernel: RS)
     a.region_pad = ctx->plan.region_pad;
@@ -742,6 +743,7 @@ int enqueue(tls_ctx* ctx, bool count_work, bool phase_clock = false, double* deb
         a.lds_bytes = (long long)plan.slim_lds;
         a.perm_table = ctx->perm_table_entries ? ctx->d_perm_table.ptr : nullptr; a.perm_filled = ctx->perm_filled ? 1 : 0;
         a.perm_per = plan.slim_perm_per;
+        a.claim_ahead = claim_ahead_bits(ctx->opt);
         // (switch dense_hoist = 0: the instantiations whose fast-mode dense predicate is the loop exact mode keeps)
         auto kernel = ctx->opt.dense_hoist != 0
                           ? (kernel_pick == Kernel::Slim512

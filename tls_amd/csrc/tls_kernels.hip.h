@@ -98,7 +98,8 @@ enum CheckCode {
 
 constexpr int kWave = 64;
 constexpr int kMaxWaves = 16;  // up to 1024 threads per workgroup
-constexpr int kPhases = 41;    // phase-clock slots 0..31 and work statistics 32..40 (tls_amd/_lib.py names them)
+constexpr int kPhases = 42;    // phase-clock slots 0..31 and 41, work statistics 32..40 (tls_amd/_lib.py names them)
+constexpr int kPhaseClaim = 41;          // four-slot kernel: from a period's last barrier to the next period's first phase (the queue claim and the period's set-up)
 constexpr int kStatRegisterScans = 40;   // four-slot kernel: prefix sums formed in registers from a stretch-major order (phase 2)
 #ifndef TLS_KR
 #define TLS_KR 5
@@ -576,6 +577,9 @@ struct SearchArgs {
     unsigned int* tiles_done;          // [periods of the largest batch], zero between launches
     unsigned int* fold_ready;          // [periods of the largest batch] 1: the slab is complete; zero between launches
     int split_fast;                    // two roles: != 0 the plan supports fast prefix-sum mode there (uniform weights, X at staging, taps g)
+    // four-slot kernel, the period queue's ticket protocol (tls_slim_kernel.hip.h, slim_ticket; developer switch
+    // claim_ahead): bit 0 a workgroup's first ticket is its own index; 0: every ticket is drawn from the queue word
+    int claim_ahead;
 };
 
 __device__ __forceinline__ double fold_phase(double t, double period, double epoch) {

@@ -60,6 +60,7 @@ struct Switches {
     int32_t prune, screen32, no_screen, fast_slab, x_staged, split, split_batch, sort2, threads, blocks, plan_threads, t0_rot;
     int32_t reg_scan;     // four-slot kernel: stored orders stretch-major, phase 2 of a reading launch in registers (0: thread-major rows)
     int32_t dense_hoist;  // four-slot kernel, fast-mode dense depth predicate: one loop per case, band test per step, no mask for lanes without a unit (slim_dense_tile; 0: the kernel instantiations with the loop exact mode keeps)
+    int32_t claim_ahead;  // four-slot kernel, the period queue's tickets (tls_slim_kernel.hip.h, slim_ticket): bit 0 a workgroup's first ticket is its index and the queue word hands out the later ones; 0: every ticket from the queue word; -1: kClaimAheadDefault
     int64_t prune_min_live;
     int64_t perm_table;  // the four-slot kernel's table of folded orders: -1 the library decides, 0 none, k > 0 at most k MiB
     double band_max;
@@ -229,6 +230,10 @@ inline void time_range(const double* t, int64_t n, double& t_min, double& t_max)
     t_min = t_max = t[0];
     for (int64_t i = 1; i < n; ++i) { t_min = std::min(t_min, t[i]); t_max = std::max(t_max, t[i]); }
 }
+
+// the four-slot kernel's ticket protocol where the switch claim_ahead leaves it to the library (PERF_LOG.md: the one part kept)
+constexpr int kClaimAheadDefault = 1;
+inline int claim_ahead_bits(const Switches& opt) { return opt.claim_ahead < 0 ? kClaimAheadDefault : (opt.claim_ahead & 1); }
 
 // the table of folded orders of a four-slot plan is held up to this size (switch perm_table: another cap, or none)
 constexpr size_t kPermTableMaxBytes = (size_t)1 << 30;

@@ -484,6 +484,19 @@ __device__ __forceinline__ void slim_dense_tile(const_width_ptr widths_c, const 
     }
 }
 
+// ---- the period queue's tickets (developer switch `claim_ahead`, SearchArgs::claim_ahead) ----
+// Ticket w is work item w of the plan's queue (SearchArgs::order); a workgroup searches the periods of its tickets until it
+// draws one at or above n_periods -- every workgroup draws exactly one such ticket and then leaves, and the last one to
+// leave rewinds both queue words for the next launch (the classic and the slab kernels share the words and keep their own
+// protocol).  Bit 0: a workgroup's first ticket is its own index and the queue word hands out gridDim.x, gridDim.x + 1, ...
+// -- a launch no longer begins with one atomic per workgroup on one address, and a workgroup whose index is no period
+// leaves without touching the word.  (Drawing the NEXT period's ticket during the dot products was measured and dropped:
+// a ticket held for two thirds of a period costs more at the end of the launch than the round trip it hides, PERF_LOG.md.)
+__device__ __forceinline__ int slim_ticket(args_ptr ap, bool first) {
+    if ((ap->claim_ahead & 1) == 0) return (int)atomicAdd(ap->queue, 1u);
+    return first ? (int)blockIdx.x : (int)(gridDim.x + atomicAdd(ap->queue, 1u));
+}
+
 template <bool COUNTING, int THREADS = kSlimThreads, bool DENSE_HOIST = true>
 __global__ void __launch_bounds__(THREADS, 4)
 tls_slim_kernel(const SearchArgs) {
@@ -530,10 +543,13 @@ tls_slim_kernel(const SearchArgs) {
     unsigned int kept_eval = 0;
     unsigned long long kept_steps = 0, kept_issued = 0;
     BandEntry* const band_list = reinterpret_cast<BandEntry*>(chunk_list + ap->list_cap);   // (the pruning variant's second list: idle here)
-    int work = 0;
+    int work = -1;   // (no ticket yet)
+#if TLS_PHASE_CLOCKS
+    long long c_period_end = 0;   // (phase clock 41, `claim`: from a period's last barrier to the next period's start)
+#endif
     for (;;) {
         if (!retry_exact) {
-            if (tid == 0) { s_work[0] = (int)atomicAdd(ap->queue, 1u); s_work[1] = 0; s_work[2] = 0; s_work[4] = 0; }
+            if (tid == 0) { s_work[0] = slim_ticket(ap, work < 0); s_work[1] = 0; s_work[2] = 0; s_work[4] = 0; }
             wg_sync();
             work = __builtin_amdgcn_readfirstlane(s_work[0]);
             wg_sync();
@@ -568,6 +584,9 @@ tls_slim_kernel(const SearchArgs) {
         if (ap->period_cycles && tid == 0) t_period = clock64();
         PhaseClock pc;
         pc.start(ap->phase_cycles);
+#if TLS_PHASE_CLOCKS
+        if (ap->phase_cycles && tid == 0 && c_period_end != 0) atomicAdd(&ap->phase_cycles[kPhaseClaim], (unsigned long long)(pc.last - c_period_end));
+#endif
 
         // ---- phase 1: fold + stable sort by phase (core.py:119-120), on 32-bit keys (slim_fold_and_sort) -------------------
         // A plan whose table of orders is filled has nothing to sort: the period's row is the order (phase clocks 0-3 and 8
@@ -1123,6 +1142,9 @@ tls_slim_kernel(const SearchArgs) {
         }
         wg_sync();
         }  // light curves of the batch
+#if TLS_PHASE_CLOCKS
+        if (ap->phase_cycles && tid == 0) c_period_end = clock64();
+#endif
         if (ap->period_cycles && tid == 0) atomicAdd(&ap->period_cycles[p], (unsigned long long)(clock64() - t_period));
     }
 }
