@@ -65,7 +65,13 @@ typedef struct tls_counters {
 
 /* Template table = the reference's (lc_cache_overview, lc_arr) of transit.py:98-160,
  * flattened: row r is values[offset[r] .. offset[r]+length[r]), trial width width[r]
- * samples, depth-normalisation factor overshoot[r]. */
+ * samples, depth-normalisation factor overshoot[r].
+ * 1 <= length[r] <= width[r].  A row SHORTER than its width (an eccentric orbit's table: transit.py:143-149 trims the slow
+ * side of the transit) is searched as the reference searches it (core.py:59-70): the window of width[r] samples leaves
+ * the out-of-transit sum, the model covers its first length[r] samples, the others count for nothing --
+ * chi2 = S0 + rs^2 A - 2 rs B - sum_{j >= length} e_j^2 w_j, with A, B and inner_steps over length[r] taps.  A table with
+ * such a row takes the plain classic kernel (LDS-resident series) or the slab kernels: never the four-slot kernel nor the
+ * classic kernel's fp32-screen and pruning variants, whatever the switches say (tls_last_kernel reports the choice). */
 typedef struct tls_template {
     const double *values;
     const int64_t *offset;

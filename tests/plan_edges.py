@@ -143,7 +143,13 @@ def slim_header(threads):
     return 128 + threads // 64 * 24 + 48 + 1328
 
 
-def expected_plan(n, M, n_widths, pad, uniform=True, exact_prefix=False, noise_variant=None):
+def short_rows(inp):
+    """A template row shorter than its width (an eccentric orbit's table): the plan keeps such a table out of the four-slot
+    kernel and out of the classic kernel's fp32-screen and pruning variants, forced or not (include/tls_amd.h)."""
+    return bool((numpy.asarray(inp["table"].length) < numpy.asarray(inp["table"].width)).any())
+
+
+def expected_plan(n, M, n_widths, pad, uniform=True, exact_prefix=False, noise_variant=None, short_rows=False):
     """(kernel, periods a CU holds side by side) of a search of at most ~60 periods, restated from the documents: README
     ("Kernel variants"), DESIGN.md section 4, the header comments of tls_slim_kernel.hip.h and include/tls_amd.h.
     noise_variant: "resident+screen32" / "resident+prune" where the host takes one of those by the noise level.
@@ -155,7 +161,7 @@ def expected_plan(n, M, n_widths, pad, uniform=True, exact_prefix=False, noise_v
     if classic > LDS or n > 65535:
         return ("slab+split" if uniform and n % 2 == 0 and not exact_prefix else "slab"), 1
     classic_slots = 2 if 2 * classic <= LDS else 1
-    if not uniform or exact_prefix:
+    if not uniform or exact_prefix or short_rows:           # (a short row: the plain classic kernel, whatever the noise level)
         return "resident", classic_slots
     if noise_variant:
         return noise_variant, classic_slots

@@ -1,5 +1,5 @@
 """The search of one trial period (the reference's search_period, core.py:96-188) stated as its DEFINITION in plain numpy,
-for test_search_spec_host.py and test_input_scales.py: the yardstick the CPU oracle and the kernels are both read against.
+for test_search_spec_host.py, test_input_scales.py and the template-shape modules (template_shapes.py): the yardstick the CPU oracle and the kernels are both read against.
 
 It is neither arithmetic.  The oracle restates the reference's (a running out-of-transit sum, core.py:79-93, plus
 `intransit + ootr[i] - edge`), the kernels compute S0 + rs^2 A - 2 rs B in double; this module values a cell as what both
@@ -20,6 +20,14 @@ approximate, with every sum in numpy.longdouble (64-bit significand, 2^-64 a ste
                 chi2(d, i) = sum over the n folded points of (f - model)^2 / s^2, model = 1 - q_j rs inside the window
                              (patched positions i .. i + d - 1: it wraps through the patch, so no edge correction) and 1 outside
                            = S0 + rs^2 A - 2 rs B,   S0 = sum_k e_k^2 w_k (k < n),  A = sum_j q_j^2 w_{i+j},  B = sum_j q_j (e w)_{i+j}
+      short row a row may be SHORTER than its width, L = len(signal) < d (an eccentric orbit's table: the stability cut-off trims
+                the slow side of the transit, transit.py:143-149).  The reference takes the whole window of d samples out of the
+                out-of-transit sum and puts back the residuals of the row's first L (core.py:59-70): the last d - L samples
+                of the window count for nothing, neither as data nor as model,
+                chi2(d, i) = S0 + rs^2 A - 2 rs B - sum_{j = L}^{d - 1} e_{i+j}^2 w_{i+j},   A and B over j < L;
+                the cell set, the depth scale (the mean over all d samples) and the stride stay those of the width d, and a
+                cell costs L template samples (`inner_steps`).  `pad_short_rows` values the row as if it were padded to d
+                with q = 0 (no tail term): what a kernel without the term computes -- for the tests that show the difference.
       select    as the reference: a duration starts from `datapoints` = n and takes the first cell (ascending i) with the
                 strictly smallest value below it (core.py:46,71); the period starts from infinity and takes, durations
                 ascending, each duration whose value is strictly smaller (core.py:183).  best_row is the row of the duration
@@ -31,7 +39,7 @@ win -- the winner's value against the smallest value any OTHER duration reports 
 a period where nothing was fitted, n against the smallest cell of any other duration.  Two arithmetics that agree to less
 than the gap must report the same row.  `period_gap` is the same between the smallest and the second smallest chi2 of a list.
 
-A template row is as long as its width (len(signal) == width for every table the host builds: SURVEY.md, a11); asserted."""
+`reverse_rows` reads every row backwards (q_j -> q_{L-1-j}): what a kernel that pairs tap j with sample d - 1 - j computes."""
 import math
 
 import numpy
@@ -92,7 +100,7 @@ def fold_order(t, period):
     return numpy.argsort(x - numpy.floor(x), kind="mergesort")
 
 
-def search_period(t, y, dy, period, table, params):
+def search_period(t, y, dy, period, table, params, reverse_rows=False, pad_short_rows=False):
     """dict(chi2 (long double), row, depth, row_gap, evaluated_cells, inner_steps) of one period."""
     t, y, dy = (numpy.asarray(a, dtype=numpy.float64) for a in (t, y, dy))
     period = float(period)
@@ -109,12 +117,16 @@ def search_period(t, y, dy, period, table, params):
     w = LD(1) / (ps.astype(LD) * ps.astype(LD))
     ew = e * w
     S0 = numpy.sum((e * e * w)[:n])
+    E2 = numpy.cumsum(numpy.insert(e * e * w, 0, LD(0)))        # (long double: a tail term is E2[i + d] - E2[i + L])
 
     reported, smallest_cell, rows, depths = [], [], [], []      # per in-range duration
     evaluated = steps = 0
     for d, row in durations_in_range(t, period, table, params):
         signal = numpy.asarray(table.values[table.offset[row]: table.offset[row] + table.length[row]], dtype=numpy.float64)
-        assert len(signal) == d, (row, len(signal), d)
+        L = len(signal)
+        assert 1 <= L <= d, (row, L, d)
+        if reverse_rows:
+            signal = signal[::-1]
         mean = 1 - (C[d:] - C[:-d]) / float(d)
         at = numpy.nonzero((mean > params["transit_depth_min"])
                            & (numpy.arange(len(mean)) % stride(d, params["T0_fit_margin"]) == 0))[0]
@@ -123,15 +135,17 @@ def search_period(t, y, dy, period, table, params):
             target = mean[at] * float(table.overshoot[row])
             rs = target.astype(LD) / LD(SIGNAL_DEPTH)
             q = LD(1) - signal.astype(LD)
-            A = sliding_window_view(w, d)[at] @ (q * q)
-            B = sliding_window_view(ew, d)[at] @ q
+            A = sliding_window_view(w, L)[at] @ (q * q)
+            B = sliding_window_view(ew, L)[at] @ q
             chi2 = S0 + rs * rs * A - LD(2) * rs * B
+            if L < d and not pad_short_rows:
+                chi2 = chi2 - (E2[at + d] - E2[at + L])
             k = int(numpy.argmin(chi2))                          # the first of the smallest: strict '<', ascending i
             cell = chi2[k]
             if cell < value:
                 value, depth = cell, float(1 - target[k])
             evaluated += len(at)
-            steps += len(at) * d
+            steps += len(at) * L
         reported.append(value)
         smallest_cell.append(cell)
         rows.append(row)
@@ -160,10 +174,10 @@ def period_gap(chi2):
     return float((v[1] - v[0]) / v[0]) if len(v) > 1 and numpy.isfinite(v[0]) else float("inf")
 
 
-def search(t, y, dy, periods, table, params):
+def search(t, y, dy, periods, table, params, **variant):
     """dict of arrays over the periods (chi2 long double, row, depth, row_gap, evaluated_cells, inner_steps), `period_gap`
     and `argmin`."""
-    per = [search_period(t, y, dy, P, table, params) for P in periods]
+    per = [search_period(t, y, dy, P, table, params, **variant) for P in periods]
     out = {key: numpy.array([p[key] for p in per], dtype=(LD if key == "chi2" else None)) for key in per[0]}
     out["period_gap"] = period_gap(out["chi2"])
     out["argmin"] = int(numpy.argmin(out["chi2"]))

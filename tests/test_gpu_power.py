@@ -18,7 +18,7 @@ def make_model(t, y, dy):
     return tls_amd.transitleastsquares(t, y, dy, verbose=False)
 
 
-@pytest.mark.parametrize("name", ["small", "weights", "nofit"])
+@pytest.mark.parametrize("name", ["small", "weights", "nofit", "grazing", "box", "ecc"])
 def test_power_matches_reference_golden(name):
     pins.check_power_golden(make_model, name)
 

@@ -30,7 +30,7 @@ def make_model(monkeypatch, oracle_lib):
     return lambda t, y, dy: tls_amd.transitleastsquares(t, y, dy, verbose=False)
 
 
-@pytest.mark.parametrize("name", ["small", "weights", "nofit"])
+@pytest.mark.parametrize("name", ["small", "weights", "nofit", "grazing", "box", "ecc"])
 def test_power_matches_reference_golden(make_model, name):
     pins.check_power_golden(make_model, name)
 

@@ -456,7 +456,7 @@ struct WidthEntry {
     int width;        // trial duration d in samples
     int row;          // template row reported for this width
     int q_offset;     // index of q_0 of this row in the padded q array
-    int q_len;        // len(signal) (== width in practice)
+    int q_len;        // len(signal) <= width (shorter: an eccentric orbit's table, short_row_tail)
     int xth;          // T0 stride (core.py:50-55)
     int n_pos;        // trial T0 positions u = 0..n_pos-1, window start i = u*xth <= M-d
     int n_chunks;     // phase-3 work units of this width: ceil(n_pos/kR) if tiled, else n_pos
@@ -1724,6 +1724,57 @@ __device__ __forceinline__ void exact_cell(double dX, double dd, double overshoo
     td = mean * overshoot;                        // core.py:61
     const double rs = 2.0 * td;                   // 1/(SIGNAL_DEPTH/td), core.py:62-63
     stat = rs * (rs * A - 2.0 * B);
+}
+
+// A template row SHORTER than its width (len(signal) = L < d: an eccentric orbit's table, whose slow side template.py
+// trims).  The reference takes the whole window of d samples out of the out-of-transit sum and puts back the row's L
+// (core.py:59-70), so a cell is worth
+//     rs^2 A - 2 rs B - tail,   tail = sum_{j = L}^{d - 1} e_{i+j}^2 w_{i+j}   (A and B over the L taps),
+// in the statistic's units (uniform weights: e^2 alone).  The plan sends a table with such a row to the plain classic or
+// slab kernel (tlsplan::SearchPlan::short_rows), whose dot-product phase forms the d - L terms (1 to 5 for power()'s
+// tables) from what it holds of the window; a full row never gets here (wave-uniform).
+// ... from the staged samples: e (uniform weights), or e w beside w
+template <bool UNIFORM_W>
+__device__ __forceinline__ double short_row_tail(const double* e, const double* w, int i, int L, int d) {
+    double tail = 0.0;
+    for (int j = i + L; j < i + d; ++j) {
+        const double ev = e[j];
+        if constexpr (UNIFORM_W) tail = fma(ev, ev, tail);
+        else { const double wv = w[j]; tail += wv > 0.0 ? ev * ev / wv : 0.0; }   // (behind the series: e w = w = 0)
+    }
+    return tail;
+}
+// ... from the tile's X where the dot products run on X (uniform weights, fast mode: X is exact there, so are its differences)
+__device__ __forceinline__ double short_row_tail_x(const double* x_tile, int i, int L, int d) {
+    double tail = 0.0;
+    double x0 = *((lds_f64_ptr)x_tile + (i + L));
+    for (int j = i + L; j < i + d; ++j) {
+        const double x1 = *((lds_f64_ptr)x_tile + (j + 1));
+        tail = fma(x1 - x0, x1 - x0, tail);
+        x0 = x1;
+    }
+    return tail;
+}
+// ... from the slab's flux and weights, the patch as an index mapping (a window evaluated straight from the slab)
+template <bool UNIFORM_W>
+__device__ __forceinline__ double short_row_tail_slab(const double* f, const double* w, int n, int i, int L, int d) {
+    double tail = 0.0;
+    for (int j = i + L; j < i + d; ++j) {
+        const int src = j < n ? j : j - n;
+        const double ev = 1.0 - f[src];
+        tail = fma(UNIFORM_W ? ev : ev * w[src], ev, tail);
+    }
+    return tail;
+}
+// The term enters a cell THROUGH ITS DOT PRODUCT: B + tail / (2 rs), with the rs of exact_cell (the reference's own
+// expression of the mean).  exact_cell's value -- what a period reports -- is then rs^2 A - 2 rs B - tail as it stands; the
+// ESTIMATE consider() orders the cells by carries tail * rs_f / rs, and the two depth scales differ by ~1e-16 absolute on the
+// mean: 1e-11 of the tail, inside the band (rule.reach, >= 1e-9 of the statistic) in which consider() lets the reference's
+// values decide.  Lead, Best and every comparison stay as they are.  (A window mean of exactly 0 has no rs: such a cell
+// is live only under a negative transit_depth_min and is then not valued -- NaN loses every comparison.)
+__device__ __forceinline__ double with_tail(double B, double tail, double dX, double dd, double overshoot) {
+    const double mean = 1.0 - (dd - dX) / dd;   // (exact_cell's)
+    return B + tail / (4.0 * (mean * overshoot));
 }
 
 // One trial cell against the lane's best (core.py:58-74).  Cells are ordered by an ESTIMATE of the statistic (the mean

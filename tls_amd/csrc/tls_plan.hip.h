@@ -322,6 +322,7 @@ struct SearchPlan {
     // sizes
     int n = 0, W = 0, M = 0, n_periods = 0, n_widths = 0;
     bool uniform = true;
+    bool short_rows = false;          // a template row shorter than its width (tlsdev::short_row_tail): the plain classic or slab kernel only
     // classic launch (LDS-resident or slab)
     int region_pad = 0, hdr_bytes = 0;
     bool resident = true;
@@ -365,6 +366,7 @@ inline const char* plan_search(SearchPlan& plan, int64_t n, std::vector<tlsdev::
     const int64_t W = padded_width(widths), M = n + W;
     plan.n = (int)n; plan.W = (int)W; plan.M = (int)M; plan.n_periods = (int)n_periods;
     plan.n_widths = (int)widths.size(); plan.uniform = uniform;
+    for (const auto& we : widths) plan.short_rows = plan.short_rows || we.q_len < we.width;
     const size_t regions = uniform ? 2 : 3;
     int widest_stride = 1;  // of the tiled rows: sizes the pads behind the folded series and the tile halo
     for (const auto& we : widths) if (we.tiled) widest_stride = std::max(widest_stride, we.xth);
@@ -391,7 +393,8 @@ inline const char* plan_search(SearchPlan& plan, int64_t n, std::vector<tlsdev::
         // (exact prefix-sum mode throughout is the classic kernel's: this one values its cells on the plain scan, and keeps
         // the exact prefix sum for the windows the plain scan cannot decide)
         const bool slim_wanted = opt.exact_prefix != 1 && (opt.slim == 1 || (opt.slim < 0 && opt.prune < 0 && opt.screen32 < 0));
-        if (uniform && slim_wanted && opt.threads <= 0) {
+        // (a table with a short row: the classic kernel, whose dot-product phase forms the row's tail term)
+        if (uniform && slim_wanted && opt.threads <= 0 && !plan.short_rows) {
             const long long need = tlsdev::slim_lds_bytes((int)n, (int)M, plan.region_pad, (int)widths.size());
             // (a series beyond 5120 points -- 107-200 d at 30 min, two TESS sectors at 10 min --: the same kernel with 512-thread
             // workgroups, two to a CU, where the classic kernel runs ONE 1024-thread workgroup per CU; round 6)
@@ -597,8 +600,8 @@ inline FluxChoice choose_flux_kernels(const SearchPlan& plan, const Switches& op
                                       double sigma, double depth_min, bool screen_admits, bool prune_beside_screen = true) {
     FluxChoice f;
     f.sigma = sigma;
-    f.admissible = screen_admits;
-    f.prune = plan.uniform && pruning_pays(opt, widths, sigma, depth_min, plan.resident, prune_beside_screen && f.admissible);
+    f.admissible = screen_admits && !plan.short_rows;   // (neither variant forms a short row's tail term: the plain kernel, switches or not)
+    f.prune = plan.uniform && !plan.short_rows && pruning_pays(opt, widths, sigma, depth_min, plan.resident, prune_beside_screen && f.admissible);
     f.screen = screen_pays(opt, widths, sigma, depth_min, f.admissible);
     return f;
 }

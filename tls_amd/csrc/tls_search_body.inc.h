@@ -1315,6 +1315,16 @@
                         for (int r = 0; r < kR; ++r) Av[r] = sum_q2;
                     }
                     if (have) {
+                        if (L < d) {   // a short row: every window's tail term, into its dot product (short_row_tail)
+#pragma unroll
+                            for (int r = 0; r < kR; ++r) {
+                                const int at = b + r * xth;
+                                if (x_dot) Bv[r] = with_tail(Bv[r], short_row_tail_x(x_tile, at, L, d),
+                                                             x_load<true>(x_tile, at + d) - x_load<true>(x_tile, at), dd, overshoot);
+                                else Bv[r] = with_tail(Bv[r], short_row_tail<UNIFORM_W>(e_base, w_base, at, L, d),
+                                                       c_base[at + d] - c_base[at], dd, overshoot);
+                            }
+                        }
                         if (x_dot) consider_cells<UNIFORM_W, !RESIDENT, kR, COUNTING, true>(lead, x_tile, b, xth, d, inv_d, dd, rule, overshoot, Av, Bv, k, n_eval, undecided, widths_c, regB);
                         else consider_cells<UNIFORM_W, !RESIDENT, kR, COUNTING>(lead, c_base, b, xth, d, inv_d, dd, rule, overshoot, Av, Bv, k, n_eval, undecided, widths_c, regB);
                     }
@@ -1348,6 +1358,7 @@
                         }
                         if (have) {
                             const int i = unit * xth;
+                            if (L < d) myB = with_tail(myB, short_row_tail_slab<UNIFORM_W>(regA, regW, n, i, L, d), regB[i + d] - regB[i], dd, overshoot);
                             consider<UNIFORM_W, !RESIDENT>(lead, regB[i], regB[i + d], i, inv_d, dd, rule, overshoot, myA, myB, k, n_eval, undecided, widths_c, regB);
                         }
                         n_steps += (unsigned long long)(n_eval - evals_before) * (unsigned long long)L;
@@ -1396,6 +1407,9 @@
                         double x0, x1;
                         if (x_dot) { x0 = x_load<true>(x_tile, i); x1 = x_load<true>(x_tile, i + d); }
                         else { x0 = c_base[i]; x1 = c_base[i + d]; }
+                        if (L < d)   // a short row: the window's tail term, into its dot product (short_row_tail)
+                            B0 = with_tail(B0, x_dot ? short_row_tail_x(x_tile, i, L, d)
+                                                     : short_row_tail<UNIFORM_W>(e_base, w_base, i, L, d), x1 - x0, dd, overshoot);
                         consider<UNIFORM_W, !RESIDENT>(lead, x0, x1, i, inv_d, dd, rule, overshoot, A0 + A1, B0 + B1, k, n_eval, undecided, widths_c, regB);
                     }
                 }
@@ -1439,6 +1453,7 @@
                     }
                     if (lane == 0) {
                         bool und_none = false;
+                        if (L < d) Bs = with_tail(Bs, short_row_tail_slab<UNIFORM_W>(regA, regW, n, i, L, d), dX_noted, dd, overshoot);
                         consider<UNIFORM_W, true, true>(lead, 0.0, dX_noted, i, inv_d, dd, rule, overshoot, UNIFORM_W ? sum_q2 : As, Bs, k, n_eval,
                                                         und_none, widths_c, regB);
                         if constexpr (COUNTING) n_steps += (unsigned long long)L;

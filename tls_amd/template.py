@@ -87,7 +87,8 @@ class TemplateTable(object):
 
     values    f8[sum(len(row))]  all rows back to back
     offset    i8[rows]           start of row r in `values`
-    length    i8[rows]           len(row r) (== width in practice, see a11 in SURVEY.md)
+    length    i8[rows]           len(row r) (== width for a circular orbit, a11 in SURVEY.md; an eccentric one's rows
+                                 are up to a few samples shorter: the cut-off below trims the slow side of the transit)
     width     i8[rows]           trial duration of row r in samples
     overshoot f8[rows]           1 / (2 - mean(row)/min(row))
     duration  f8[rows]           fractional duration of row r

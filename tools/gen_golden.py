@@ -19,6 +19,7 @@ the cases are small; full-size parity runs against the C oracle, which is itself
 pinned by these files (tests/test_oracle_golden.py).
 
 Usage: python tools/gen_golden.py            (takes a few minutes)
+       python tools/gen_golden.py shapes     (only the template-shape cases: search_/power_ grazing, box, ecc)
 """
 import json
 import os
@@ -145,7 +146,25 @@ def injected(n_days, per_day, sigma, seed, per, rp, a, t0_offset=1.0, start=3.14
     return t, sig + numpy.random.normal(0, sigma, n)
 
 
+# power() keywords of the template-shape cases (tests/template_shapes.py): the two presets, and an eccentric orbit whose
+# table rows are one sample shorter than their width (transit.py:143-149 trims the slow side of the transit)
+TEMPLATE_SHAPES = (("grazing", dict(transit_template="grazing")), ("box", dict(transit_template="box")),
+                   ("ecc", dict(ecc=0.6, w=20)))
+
+
+def template_shape_cases():
+    """The "small" case's series and arguments under each template shape."""
+    t, y = injected(30, 24, 2e-4, 0, 4.321, 0.05, 12)
+    for name, shape in TEMPLATE_SHAPES:
+        search_case(name, t, y, None, 3, period_min=3.5, period_max=5.5, oversampling_factor=2, **shape)
+    for name, shape in TEMPLATE_SHAPES:
+        power_case(name, t, y, None, period_min=3.5, period_max=5.5, oversampling_factor=2, **shape)
+
+
 def main():
+    if sys.argv[1:] == ["shapes"]:
+        template_shape_cases()
+        return
     # ---- grids and template tables
     grids = {}
     sets = [dict(R_star=1, M_star=1, time_span=0.1), dict(R_star=1, M_star=1, time_span=20),
@@ -205,6 +224,7 @@ def main():
     power_case("weights", t, y2, dy, period_min=3.5, period_max=5.5, oversampling_factor=2)
     power_case("nofit", t, y, None, period_min=3.5, period_max=5.5, oversampling_factor=2,
                transit_depth_min=0.05)
+    template_shape_cases()
 
     # ---- the reference's own data fixtures, as arrays
     for epic in ("EPIC201367065", "EPIC206154641"):
