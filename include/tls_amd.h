@@ -207,6 +207,13 @@ int tls_debug_perm_table(const tls_ctx *ctx, int64_t *bytes, int64_t *filled, in
  * of a row are drawn but not used).  The arguments are checked as tls_null_rows checks them. */
 int tls_debug_null_words(tls_ctx *ctx, int64_t n, int64_t n_rows, uint64_t seed, int64_t first_trial, int mode,
                          int64_t block, uint64_t *out);
+/* Test entry, host only (no context, no GPU): how the per-candidate stages (tls_transit_times, tls_event_vetting,
+ * tls_shape_fit, tls_centroid_test, tls_folded_views, tls_sine_test) cut n_fits candidates into slabs of at most max_fits
+ * candidates on at most max_curves distinct curves.  curve [n_fits] (NULL: candidate f reads curve f); out_slab, out_slot
+ * [n_fits]: every candidate's slab and the slot of its curve in it; out_runs [n_fits, *n_slabs used]: the row copies a
+ * slab takes, consecutive curves in consecutive slots being one; *n_slabs: the slabs there are. */
+int tls_debug_candidate_slabs(const int64_t *curve, int64_t n_fits, int64_t max_curves, int64_t max_fits, int64_t *out_slab,
+                              int64_t *out_slot, int64_t *out_runs, int64_t *n_slabs);
 /* block until the stream is idle */
 int tls_synchronize(tls_ctx *ctx);
 /* fetch: copy results (and counters, may be NULL) back; synchronises. */

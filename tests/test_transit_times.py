@@ -256,6 +256,45 @@ def test_candidates_curves_and_slabs(ctx):
     assert numpy.isnan(times["epoch"][:, 9:]).all()
 
 
+def test_a_slab_that_ends_on_its_curve_slots(ctx):
+    """n = 2^15 points: 256 MB of curves are 2^28 / (32 n) = 256 slots, and 300 candidates visit 257 curves, so the first slab
+    ends where the 257th curve appears, not at a candidate count.  The whole call equals, byte for byte, the two calls on the
+    candidates in front of that cut and behind it, and the statement next to the cut.  Every curve has a dip of its own depth
+    at its own place at four epochs (flat elsewhere, one vectorised expression), so a curve in a wrong slot shows; curves
+    100 .. 119 are first met in order, one copy of twenty rows."""
+    n, n_curves, n_fits, P = 1 << 15, 257, 300, 8192 * DT
+    t = series(n)
+    rng = numpy.random.RandomState(21)
+    move, depth = rng.randint(-40, 41, n_curves), 3e-3 + 1e-5 * numpy.arange(n_curves)
+    y = numpy.ones((n_curves, n))
+    y[numpy.arange(n_curves)[:, None, None],
+      (4096 + move)[:, None, None] + 8192 * numpy.arange(4)[None, :, None] + numpy.arange(-2, 3)[None, None, :]] -= depth[:, None, None]
+    dy = numpy.full((n_curves, n), 1e-3)
+    others = rng.permutation(numpy.r_[0:100, 120:n_curves])
+    curve = numpy.r_[others[:60], 100:120, others[60:]]
+    for at in numpy.sort(rng.randint(1, n_curves, 30))[::-1]:      # repeats: 30 on the way, each after its first visit, ...
+        curve = numpy.insert(curve, at, curve[rng.randint(0, at)])
+    curve = numpy.r_[curve, rng.randint(0, n_curves, n_fits - len(curve))]        # ... and 13 behind the last curve
+    assert len(curve) == n_fits and len(set(curve.tolist())) == n_curves
+    slab, slot, runs = _lib.candidate_slabs(curve, n_fits, 256, n_fits)
+    cut = int(numpy.flatnonzero(slab == 1)[0])
+    assert slab[-1] == 1 and cut < n_fits and len(set(curve[:cut].tolist())) == 256 and runs[0] <= 256 - 19
+    period, T0 = numpy.full(n_fits, P), t[4096 + move[curve]] + rng.randint(-2, 3, n_fits) * DT / 4
+    row, reach = rng.randint(0, 4, n_fits), rng.randint(1, 6, n_fits)
+    tables = (WIDTHS, shapes_of(WIDTHS), spans_of(WIDTHS))
+    eph, times = ctx.transit_times(t, y, dy, period, T0, row, reach, *tables, curve=curve, max_epochs=4)
+    assert (eph["n_epochs"] == 4).all() and (eph["n_timed"] >= 2).sum() > 250
+    for part in (slice(0, cut), slice(cut, n_fits)):
+        alone = ctx.transit_times(t, y, dy, period[part], T0[part], row[part], reach[part], *tables, curve=curve[part], max_epochs=4)
+        assert alone[0].tobytes() == eph[part].tobytes() and alone[1].tobytes() == times[part].tobytes(), part
+    near = slice(cut - 4, min(cut + 4, n_fits))
+    want = spec.expected(t, y, dy, curve[near], period[near], T0[near], row[near], reach[near], tables[1], tables[2], max_epochs=4)
+    for f in spec.EPHEMERIS_FIELDS:
+        expect_equal(eph[near][f], want[0][f], ("cut", f))
+    for f in spec.TIME_FIELDS:
+        expect_equal(times[near][f], want[1][f], ("cut", f))
+
+
 def test_two_contexts(ctx):
     n = 300
     t = series(n)

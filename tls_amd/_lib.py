@@ -98,7 +98,7 @@ PEAKS_LDS_PERIODS = 1 << 20   # tls_peaks.hip.h kPeaksLdsPeriods: a longer grid 
 SYMBOLS = (
     "tls_device_count", "tls_ctx_create", "tls_ctx_destroy", "tls_last_error", "tls_version", "tls_abi_version",
     "tls_device_name", "tls_get_options", "tls_set_options", "tls_debug_set_switch", "tls_debug_get_switches", "tls_search", "tls_search_batch", "tls_power_batch", "tls_prepare", "tls_update_flux", "tls_execute",
-    "tls_synchronize", "tls_fetch", "tls_execute_timed", "tls_plan_info", "tls_last_kernel", "tls_grid_cells", "tls_period_costs", "tls_t0_fit", "tls_pink_noise", "tls_spectra", "tls_kernel_timing", "tls_debug_phase_cycles", "tls_debug_cumsum", "tls_debug_folded", "tls_debug_prefix", "tls_debug_check_counts", "tls_debug_poison_lds", "tls_debug_period_cycles", "tls_debug_batch_group_ms",
+    "tls_synchronize", "tls_fetch", "tls_execute_timed", "tls_plan_info", "tls_last_kernel", "tls_grid_cells", "tls_period_costs", "tls_debug_candidate_slabs", "tls_t0_fit", "tls_pink_noise", "tls_spectra", "tls_kernel_timing", "tls_debug_phase_cycles", "tls_debug_cumsum", "tls_debug_folded", "tls_debug_prefix", "tls_debug_check_counts", "tls_debug_poison_lds", "tls_debug_period_cycles", "tls_debug_batch_group_ms",
     "tls_debug_post_search", "tls_debug_device_bytes", "tls_debug_perm_table", "tls_power_batch_stats", "tls_debug_transit_stats",
     "tls_power_batch_models", "tls_debug_transit_models",
     "tls_inject_transits", "tls_null_rows", "tls_debug_null_words", "tls_medfilt_detrend",
@@ -1132,6 +1132,8 @@ def load():
     lib.tls_debug_cumsum.argtypes = [vp, _c_double_p, i64, _c_double_p, ci]
     lib.tls_grid_cells.restype = ci
     lib.tls_grid_cells.argtypes = [_c_double_p, i64, _c_double_p, i64, tp, pp, _c_int64_p]
+    lib.tls_debug_candidate_slabs.restype = ci
+    lib.tls_debug_candidate_slabs.argtypes = [_c_int64_p, i64, i64, i64, _c_int64_p, _c_int64_p, _c_int64_p, _c_int64_p]
     lib.tls_period_costs.restype = ci
     lib.tls_period_costs.argtypes = [_c_double_p, i64, _c_double_p, i64, tp, pp, dbl, _c_int64_p, _c_double_p, _c_double_p,
                                      _c_int64_p, ctypes.c_char_p]
@@ -2313,6 +2315,20 @@ def grid_cells(t, periods, table, params):
     if rc != 0:
         raise RuntimeError("tls_amd error %d: %s" % (rc, lib.tls_last_error(None).decode()))
     return out
+
+
+def candidate_slabs(curve, n_fits, max_curves, max_fits):
+    """(slab of every candidate, slot of its curve in that slab, row copies of every slab): how the per-candidate
+    stages cut n_fits candidates into slabs (host-only, needs no GPU).  curve None: candidate f reads curve f."""
+    lib = load()
+    curve = None if curve is None else _i8(curve)
+    slab, slot, runs = (numpy.zeros(max(n_fits, 0), dtype=numpy.int64) for _ in range(3))
+    n_slabs = ctypes.c_int64(0)
+    rc = lib.tls_debug_candidate_slabs(None if curve is None else _ip(curve), n_fits, max_curves, max_fits, _ip(slab),
+                                       _ip(slot), _ip(runs), ctypes.byref(n_slabs))
+    if rc != 0:
+        raise RuntimeError("tls_amd error %d: %s" % (rc, lib.tls_last_error(None).decode()))
+    return slab, slot, runs[:n_slabs.value].copy()
 
 
 def period_costs(t, periods, table, params, sigma, with_slots=False, options=None):

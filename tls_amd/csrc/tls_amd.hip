@@ -20,12 +20,12 @@
 #include <numeric>
 #include <string>
 #include <thread>
-#include <unordered_map>
 #include <vector>
 
 #include "../../include/tls_amd.h"
 #include "tls_kernels.hip.h"
 #include "tls_plan.hip.h"
+#include "tls_candidate_slabs.h"
 
 using namespace tlsplan;
 
@@ -222,6 +222,9 @@ struct tls_ctx {
     DevBuf<double> d_scan;          // tls_phase_scan: t | y rows | period | T0 | duration | records | curve of fit
     // tls_single_transits: t | rows | taps | of one slab: y | dy | ses | depth | events | n_events | row
     DevBuf<double> d_single;
+    // The per-candidate stages (run_candidate_slabs): of one slab the curve rows [cs][n] -- in front of them the pairs
+    // [cs][n] where the pairs kernel runs, at the 16-byte aligned start --, then the per-candidate arrays [sl] with the packed
+    // int columns [sl] each last (padded to a whole double); behind the semicolon what every slab of the call shares.
     // tls_transit_times: of one slab: pairs | y | dy | records | times | period | T0 | slot, row, reach; t | rows | taps | slopes
     DevBuf<double> d_times;
     // tls_event_vetting: of one slab: pairs | held (N, D) | y | dy | summaries | events | period | T0 | chase_span | slot, row,
@@ -234,7 +237,8 @@ struct tls_ctx {
     // tls_folded_views: of one slab: y | records | period | T0 | duration | secondary | global and local medians | slot | global
     // and local counts; t | scratch
     DevBuf<double> d_views;
-    // tls_nudft / tls_lomb_scargle / tls_sine_test: the sums of one slab first (16-byte aligned pairs), then its rows and tables
+    // tls_nudft / tls_lomb_scargle: the sums of one slab first (16-byte aligned pairs), then its rows and tables
+    // tls_sine_test: of one slab: y | dy | records | harmonic records | sums | period | T0 | duration | slot; t | harmonics
     DevBuf<double> d_gls;
     // tls_ephemeris_match: star | period | T0 | duration | strength | records | partial records of every chunk
     DevBuf<double> d_match;
@@ -310,6 +314,44 @@ int stage_reserve(tls_ctx* ctx, size_t bytes) {
         ctx->h_stage_cap = cap;
     }
     return TLS_OK;
+}
+
+// the bound-check counters (tls_debug_check_counts): allocated and zeroed on first use
+int ensure_check_counters(tls_ctx* ctx) {
+    if (ctx->d_check.ptr) return TLS_OK;
+    TLS_HIP(ctx, ctx->d_check.reserve(tlsdev::kChecks));
+    TLS_HIP(ctx, hipMemsetAsync(ctx->d_check.ptr, 0, tlsdev::kChecks * sizeof(unsigned long long), ctx->stream));
+    return TLS_OK;
+}
+
+// ---- argument checks the survey stages share; `what` ("transit times") starts every message
+int check_batch(tls_ctx* ctx, const std::string& what, int64_t n, int64_t n_max, const char* range_text, int64_t n_fits,
+                int64_t n_curves) {
+    if (n < 1 || n > n_max) return fail(ctx, TLS_E_ARG, what + ": n out of range " + range_text);
+    if (n_fits > INT32_MAX || (uint64_t)n_curves > (uint64_t)(INT64_MAX / 16) / (uint64_t)n)
+        return fail(ctx, TLS_E_ARG, what + ": batch too large");
+    return TLS_OK;
+}
+
+int check_time_stamps(tls_ctx* ctx, const std::string& what, const double* t, int64_t n) {
+    for (int64_t i = 0; i < n; ++i)
+        if (!std::isfinite(t[i]) || (i > 0 && t[i] < t[i - 1]))
+            return fail(ctx, TLS_E_ARG, what + ": the time stamps must be finite and non-decreasing");
+    return TLS_OK;
+}
+
+// curve null: candidate f reads curve f; more(f): what else a stage asks of candidate f, checked behind its curve
+template <typename More>
+int check_curves(tls_ctx* ctx, const std::string& what, const int64_t* curve, int64_t n_fits, int64_t n_curves, More more) {
+    for (int64_t f = 0; f < n_fits; ++f) {
+        const int64_t c = curve ? curve[f] : f;
+        if (c < 0 || c >= n_curves) return fail(ctx, TLS_E_ARG, what + ": curve out of range [0, n_curves)");
+        if (int rc = more(f)) return rc;
+    }
+    return TLS_OK;
+}
+int check_curves(tls_ctx* ctx, const std::string& what, const int64_t* curve, int64_t n_fits, int64_t n_curves) {
+    return check_curves(ctx, what, curve, n_fits, n_curves, [](int64_t) { return TLS_OK; });
 }
 
 size_t template_values(const tls_template* tmpl) {
@@ -632,10 +674,7 @@ int enqueue(tls_ctx* ctx, bool count_work, bool phase_clock = false, double* deb
     a.debug_folded = debug_folded; a.debug_prefix = debug_prefix; a.period_cycles = period_cycles;
     a.check = nullptr; a.lds_bytes = (long long)ctx->plan.lds_bytes;
 #ifdef TLS_DEBUG_CHECKS
-    if (!ctx->d_check.ptr) {
-        TLS_HIP(ctx, ctx->d_check.reserve(tlsdev::kChecks));
-        TLS_HIP(ctx, hipMemsetAsync(ctx->d_check.ptr, 0, tlsdev::kChecks * sizeof(unsigned long long), ctx->stream));
-    }
+    if (int rc = ensure_check_counters(ctx)) return rc;
     a.check = ctx->d_check.ptr;
 #endif
     a.queue = ctx->d_squeue.ptr;
@@ -1548,6 +1587,115 @@ int visible_compute_units() {
     return cached;
 }
 
+// ---- the duration rows of tls_single.hip.h and their taps, as tls_single_transits, tls_transit_times and
+// tls_event_vetting read them
+struct RowTables {
+    std::vector<tlsdev::SingleRow> rows;
+    std::vector<double> taps;      // pairs (b, b * b)
+    std::vector<double> slopes;    // on request: triples (g, b * g, g * g), g the shape's slope per sample
+    size_t n_taps = 0;
+};
+
+int build_row_tables(tls_ctx* ctx, const std::string& what, const char* null_text, const double* shape_values,
+                     const int64_t* shape_offset, const int64_t* width, const double* span_max, int64_t n_rows, bool with_slopes,
+                     RowTables& tb) {
+    if (n_rows < 1) return fail(ctx, TLS_E_ARG, what + ": at least one row is needed");
+    if (!shape_values || !shape_offset || !width || !span_max) return fail(ctx, TLS_E_ARG, null_text);
+    if (n_rows > TLS_SINGLE_MAX_WIDTH) return fail(ctx, TLS_E_ARG, what + ": more rows than widths there are");
+    for (int64_t r = 0; r < n_rows; ++r) {
+        if (width[r] < tlsdev::kSingleMinWidth || width[r] > TLS_SINGLE_MAX_WIDTH)
+            return fail(ctx, TLS_E_ARG, what + ": width out of range [3, 4096]");
+        if (r > 0 && width[r] <= width[r - 1]) return fail(ctx, TLS_E_ARG, what + ": the widths must be strictly ascending");
+        if (shape_offset[r] < 0) return fail(ctx, TLS_E_ARG, what + ": negative shape offset");
+        if (!(std::isfinite(span_max[r]) && span_max[r] >= 0.0)) return fail(ctx, TLS_E_ARG, what + ": span_max must be finite and >= 0");
+        tb.n_taps += (size_t)width[r];
+    }
+    tb.rows.resize((size_t)n_rows);
+    tb.taps.resize(2 * tb.n_taps);
+    tb.slopes.resize(with_slopes ? 3 * tb.n_taps : 0);
+    size_t at = 0;
+    for (int64_t r = 0; r < n_rows; ++r) {
+        tb.rows[(size_t)r].width = (int)width[r];
+        tb.rows[(size_t)r].offset = (int)at;
+        tb.rows[(size_t)r].span_max = span_max[r];
+        const double* b = shape_values + shape_offset[r];
+        for (int64_t j = 0; j < width[r]; ++j, ++at) {
+            const double v = b[j];
+            tb.taps[2 * at] = v;
+            tb.taps[2 * at + 1] = v * v;
+            if (!with_slopes) continue;
+            const double next = j + 1 < width[r] ? b[j + 1] : 0.0, prev = j > 0 ? b[j - 1] : 0.0;
+            const double rise = next - prev;
+            const double g = 0.5 * rise;
+            tb.slopes[3 * at] = g;
+            tb.slopes[3 * at + 1] = v * g;
+            tb.slopes[3 * at + 2] = g * g;
+        }
+    }
+    return TLS_OK;
+}
+
+// ---- candidate slabs (tls_candidate_slabs.h, DESIGN.md "Candidate slabs"): the loop the per-candidate stages share
+struct SlabCopy { double* dev; const double* host; };          // an array of one slab and the caller's whole array (null: not given)
+struct SlabView { int64_t f0; size_t fits, curves, lds; };     // lds: the largest dynamic LDS size the pack hook asked for
+
+struct SlabStage {
+    const char* what;              // "transit times": starts the messages
+    const char* kernel;            // what tls_last_kernel reports
+    const int64_t* curve;
+    int64_t n_fits;
+    size_t n;
+    size_t cs, sl;                 // curves and candidates of one slab at most: the stage's memory statement
+    std::vector<SlabCopy> rows;    // curve rows, [cs][n] of [n_curves][n]: one copy per run
+    std::vector<SlabCopy> columns; // per-candidate values, [sl] of [n_fits]
+    int* d_ints;                   // slot | the pack hook's columns, each sl long
+    size_t int_columns;
+};
+
+// Walks the slabs of a stage.  pack(f, at) fills candidate f's further integer columns (at[sl], at[2 * sl], ...) and returns
+// the dynamic LDS its workgroup needs; launch(slab) enqueues the stage's kernels and checks nothing; fetch(slab) enqueues
+// the copies back.
+template <typename Pack, typename Launch, typename Fetch>
+int run_candidate_slabs(tls_ctx* ctx, const SlabStage& st, Pack pack, Launch launch, Fetch fetch) {
+    std::vector<int> h_ints(st.int_columns * st.sl);
+    tlsslab::Slab slab;
+    for (int64_t f0 = 0; f0 < st.n_fits; f0 += (int64_t)slab.fits) {
+        tlsslab::next_slab(st.curve, st.n_fits, f0, st.cs, st.sl, h_ints.data(), slab);
+        SlabView s{f0, slab.fits, slab.curves, 0};
+        for (size_t i = 0; i < s.fits; ++i) s.lds = std::max<size_t>(s.lds, pack(f0 + (int64_t)i, &h_ints[i]));
+        for (const tlsslab::Run& run : slab.runs)
+            for (const SlabCopy& r : st.rows)
+                if (r.host) TLS_HIP(ctx, hipMemcpyAsync(r.dev + run.slot * st.n, r.host + (size_t)run.curve * st.n, run.count * st.n * 8, hipMemcpyHostToDevice, ctx->stream));
+        const size_t ints = st.int_columns > 1 ? st.int_columns * st.sl : s.fits;
+        TLS_HIP(ctx, hipMemcpyAsync(st.d_ints, h_ints.data(), ints * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+        for (const SlabCopy& c : st.columns)
+            if (c.host) TLS_HIP(ctx, hipMemcpyAsync(c.dev, c.host + f0, s.fits * 8, hipMemcpyHostToDevice, ctx->stream));
+        launch(s);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(ctx->stream);
+            return fail(ctx, TLS_E_HIP, std::string(st.what) + " launch: " + hipGetErrorString(e));
+        }
+        ctx->last_kernel = st.kernel;
+        if (int rc = fetch(s)) return rc;
+        // (the next slab overwrites the device buffers and h_ints; what a stage uploaded before the loop is read until the
+        // stream is done)
+        TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return TLS_OK;
+}
+
+const auto no_int_columns = [](int64_t, int*) { return (size_t)0; };
+
+// the pairs kernel of tls_times.hip.h over the first `curves` slots of a slab; false: the launch failed (the error stays
+// for hipGetLastError) and the stage's own kernel is not to follow
+bool launch_times_pairs(tls_ctx* ctx, tlsdev::TimesPairsArgs p, size_t curves, size_t n) {
+    p.count = (long long)(curves * n);
+    const unsigned blocks = (unsigned)std::min<long long>((p.count + tlsdev::kTimesThreads - 1) / tlsdev::kTimesThreads, 8192);
+    hipLaunchKernelGGL(tlsdev::tls_times_pairs_kernel, dim3(blocks), dim3(tlsdev::kTimesThreads), 0, ctx->stream, p);
+    return hipPeekAtLastError() == hipSuccess;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2182,10 +2330,7 @@ int tls_medfilt_detrend(tls_ctx* ctx, const double* y, int64_t n, int64_t n_rows
     a.y = d_y; a.flat = d_flat; a.trend = d_trend; a.check = nullptr;
     a.n = (long long)n; a.k = (int)kernel; a.span = P; a.tile = T;
 #ifdef TLS_DEBUG_CHECKS
-    if (!ctx->d_check.ptr) {
-        TLS_HIP(ctx, ctx->d_check.reserve(tlsdev::kChecks));
-        TLS_HIP(ctx, hipMemsetAsync(ctx->d_check.ptr, 0, tlsdev::kChecks * sizeof(unsigned long long), ctx->stream));
-    }
+    if (int rc = ensure_check_counters(ctx)) return rc;
     a.check = ctx->d_check.ptr;
 #endif
     const unsigned tiles = (unsigned)((n + T - 1) / T);
@@ -2281,10 +2426,7 @@ int tls_biweight_detrend(tls_ctx* ctx, const double* t, const double* y, int64_t
     a.lo = ctx->d_windows.ptr; a.hi = ctx->d_windows.ptr + nn;
     a.n = (long long)n; a.tile = T; a.span = P; a.smax = smax;
 #ifdef TLS_DEBUG_CHECKS
-    if (!ctx->d_check.ptr) {
-        TLS_HIP(ctx, ctx->d_check.reserve(tlsdev::kChecks));
-        TLS_HIP(ctx, hipMemsetAsync(ctx->d_check.ptr, 0, tlsdev::kChecks * sizeof(unsigned long long), ctx->stream));
-    }
+    if (int rc = ensure_check_counters(ctx)) return rc;
     a.check = ctx->d_check.ptr;
 #endif
     const unsigned tiles = (unsigned)((n + T - 1) / T);
@@ -2345,10 +2487,7 @@ int tls_sysrem(tls_ctx* ctx, const double* y, const double* dy, int64_t n, int64
     a.n = (long long)n; a.rows = (long long)n_rows; a.chunks = (long long)chunks;
     a.tol = tol; a.n_components = (int)n_components; a.k = 0; a.iter = 0;
 #ifdef TLS_DEBUG_CHECKS
-    if (!ctx->d_check.ptr) {
-        TLS_HIP(ctx, ctx->d_check.reserve(tlsdev::kChecks));
-        TLS_HIP(ctx, hipMemsetAsync(ctx->d_check.ptr, 0, tlsdev::kChecks * sizeof(unsigned long long), ctx->stream));
-    }
+    if (int rc = ensure_check_counters(ctx)) return rc;
     a.check = ctx->d_check.ptr;
 #endif
     // one submission: the uploads, every launch of every component and the downloads, then one wait
@@ -3194,10 +3333,8 @@ int tls_phase_scan(tls_ctx* ctx, const double* t, const double* y, int64_t n, in
     if (n_fits < 0 || n_curves < 0) return fail(ctx, TLS_E_ARG, "phase scan: negative count");
     if (n_fits == 0) return TLS_OK;
     if (!t || !y || !curve || !period || !T0 || !duration || !out) return fail(ctx, TLS_E_ARG, "null argument");
-    if (n < 1 || n > INT32_MAX) return fail(ctx, TLS_E_ARG, "phase scan: n out of range [1, 2^31)");
-    if (n_fits > INT32_MAX || (uint64_t)n_curves > (uint64_t)(INT64_MAX / 16) / (uint64_t)n)
-        return fail(ctx, TLS_E_ARG, "phase scan: batch too large");
-    for (int64_t i = 0; i < n; ++i)
+    if ((rc = check_batch(ctx, "phase scan", n, INT32_MAX, "[1, 2^31)", n_fits, n_curves))) return rc;
+    for (int64_t i = 0; i < n; ++i)       // (finite is all this entry asks of them: not check_time_stamps)
         if (!std::isfinite(t[i])) return fail(ctx, TLS_E_ARG, "phase scan: the time stamps must be finite");
     std::vector<int> h_curve((size_t)n_fits);
     for (int64_t f = 0; f < n_fits; ++f) {
@@ -3249,39 +3386,13 @@ int tls_single_transits(tls_ctx* ctx, const double* t, const double* y, const do
     if (!(std::isfinite(depth_min) && depth_min >= 0.0)) return fail(ctx, TLS_E_ARG, "single transits: depth_min must be finite and >= 0");
     if (!(std::isfinite(separation) && separation >= 0.0)) return fail(ctx, TLS_E_ARG, "single transits: separation must be finite and >= 0");
     if (std::isnan(min_ses)) return fail(ctx, TLS_E_ARG, "single transits: min_ses is NaN");
-    if (n_rows < 1) return fail(ctx, TLS_E_ARG, "single transits: at least one row is needed");
-    if (!shape_values || !shape_offset || !width || !span_max) return fail(ctx, TLS_E_ARG, "null argument");
-    if (n_rows > TLS_SINGLE_MAX_WIDTH) return fail(ctx, TLS_E_ARG, "single transits: more rows than widths there are");
-    size_t n_taps = 0;
-    for (int64_t r = 0; r < n_rows; ++r) {
-        if (width[r] < tlsdev::kSingleMinWidth || width[r] > TLS_SINGLE_MAX_WIDTH)
-            return fail(ctx, TLS_E_ARG, "single transits: width out of range [3, 4096]");
-        if (r > 0 && width[r] <= width[r - 1]) return fail(ctx, TLS_E_ARG, "single transits: the widths must be strictly ascending");
-        if (shape_offset[r] < 0) return fail(ctx, TLS_E_ARG, "single transits: negative shape offset");
-        if (!(std::isfinite(span_max[r]) && span_max[r] >= 0.0)) return fail(ctx, TLS_E_ARG, "single transits: span_max must be finite and >= 0");
-        n_taps += (size_t)width[r];
-    }
-    if (n_curves == 0) return TLS_OK;
+    RowTables tb;
+    int rc = build_row_tables(ctx, "single transits", "null argument", shape_values, shape_offset, width, span_max, n_rows, false, tb);
+    if (rc || n_curves == 0) return rc;
     if (!t || !y || !dy || !out_events || !out_n_events) return fail(ctx, TLS_E_ARG, "null argument");
     if (n < 1 || n > tlsdev::kSingleMaxPoints) return fail(ctx, TLS_E_ARG, "single transits: n out of range [1, 2^20]");
-    for (int64_t i = 0; i < n; ++i)
-        if (!std::isfinite(t[i]) || (i > 0 && t[i] < t[i - 1]))
-            return fail(ctx, TLS_E_ARG, "single transits: the time stamps must be finite and non-decreasing");
-    // the rows and their taps, pairs (b, b * b)
-    std::vector<tlsdev::SingleRow> h_rows((size_t)n_rows);
-    std::vector<double> h_taps(2 * n_taps);
-    size_t at = 0;
-    for (int64_t r = 0; r < n_rows; ++r) {
-        h_rows[(size_t)r].width = (int)width[r];
-        h_rows[(size_t)r].offset = (int)at;
-        h_rows[(size_t)r].span_max = span_max[r];
-        const double* b = shape_values + shape_offset[r];
-        for (int64_t j = 0; j < width[r]; ++j, ++at) {
-            const double v = b[j];
-            h_taps[2 * at] = v;
-            h_taps[2 * at + 1] = v * v;
-        }
-    }
+    if ((rc = check_time_stamps(ctx, "single transits", t, n))) return rc;
+    const size_t n_taps = tb.n_taps;
     const int max_width = (int)width[n_rows - 1];
     TLS_HIP(ctx, hipSetDevice(ctx->device));
     const size_t nn = (size_t)n, words = (size_t)k * tlsdev::kSingleEventWords;
@@ -3300,10 +3411,7 @@ int tls_single_transits(tls_ctx* ctx, const double* t, const double* y, const do
     double* d_events = d_depth + sl * nn;
     long long* d_n_events = reinterpret_cast<long long*>(d_events + sl * words);
     int* d_row = reinterpret_cast<int*>(d_events + sl * words + sl);
-    if (!ctx->d_check.ptr) {
-        TLS_HIP(ctx, ctx->d_check.reserve(tlsdev::kChecks));
-        TLS_HIP(ctx, hipMemsetAsync(ctx->d_check.ptr, 0, tlsdev::kChecks * sizeof(unsigned long long), ctx->stream));
-    }
+    if ((rc = ensure_check_counters(ctx))) return rc;
     tlsdev::SingleArgs a;
     a.t = d_t; a.y = d_y; a.dy = d_dy; a.rows = d_rows; a.taps = d_taps;
     a.ses = d_ses; a.row = d_row; a.depth = d_depth; a.check = ctx->d_check.ptr;
@@ -3319,8 +3427,8 @@ int tls_single_transits(tls_ctx* ctx, const double* t, const double* y, const do
     TLS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(statistic), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     TLS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(select), hipFuncAttributeMaxDynamicSharedMemorySize, (int)select_lds));
     TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(d_rows, h_rows.data(), (size_t)n_rows * sizeof(tlsdev::SingleRow), hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(d_taps, h_taps.data(), 2 * n_taps * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_rows, tb.rows.data(), (size_t)n_rows * sizeof(tlsdev::SingleRow), hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_taps, tb.taps.data(), 2 * n_taps * 8, hipMemcpyHostToDevice, ctx->stream));
     const unsigned tiles = (unsigned)((n + tlsdev::kSingleTile - 1) / tlsdev::kSingleTile);
     std::vector<int> h_row(out_row ? sl * nn : 0);
     for (int64_t k0 = 0; k0 < n_curves; k0 += slab) {
@@ -3344,7 +3452,7 @@ int tls_single_transits(tls_ctx* ctx, const double* t, const double* y, const do
         if (out_ses) TLS_HIP(ctx, hipMemcpyAsync(out_ses + first, d_ses, bytes, hipMemcpyDeviceToHost, ctx->stream));
         if (out_depth) TLS_HIP(ctx, hipMemcpyAsync(out_depth + first, d_depth, bytes, hipMemcpyDeviceToHost, ctx->stream));
         if (out_row) TLS_HIP(ctx, hipMemcpyAsync(h_row.data(), d_row, (size_t)curves * nn * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        // (the next slab overwrites the device rows, and h_rows / h_taps are read by the copies above until the stream is done)
+        // (the next slab overwrites the device rows, and tb is read by the copies above until the stream is done)
         TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
         if (out_row) for (size_t i = 0; i < (size_t)curves * nn; ++i) out_row[first + i] = h_row[i];
     }
@@ -3368,53 +3476,21 @@ int tls_transit_times(tls_ctx* ctx, const double* t, const double* y, const doub
     if (!(std::isfinite(depth_min) && depth_min >= 0.0)) return fail(ctx, TLS_E_ARG, "transit times: depth_min must be finite and >= 0");
     if (std::isnan(min_ses)) return fail(ctx, TLS_E_ARG, "transit times: min_ses is NaN");
     if (n_fits == 0) return TLS_OK;
-    if (n_rows < 1) return fail(ctx, TLS_E_ARG, "transit times: at least one row is needed");
-    if (!shape_values || !shape_offset || !width || !span_max) return fail(ctx, TLS_E_ARG, "null argument");
-    if (n_rows > TLS_SINGLE_MAX_WIDTH) return fail(ctx, TLS_E_ARG, "transit times: more rows than widths there are");
-    size_t n_taps = 0;
-    for (int64_t r = 0; r < n_rows; ++r) {
-        if (width[r] < tlsdev::kSingleMinWidth || width[r] > TLS_SINGLE_MAX_WIDTH)
-            return fail(ctx, TLS_E_ARG, "transit times: width out of range [3, 4096]");
-        if (r > 0 && width[r] <= width[r - 1]) return fail(ctx, TLS_E_ARG, "transit times: the widths must be strictly ascending");
-        if (shape_offset[r] < 0) return fail(ctx, TLS_E_ARG, "transit times: negative shape offset");
-        if (!(std::isfinite(span_max[r]) && span_max[r] >= 0.0)) return fail(ctx, TLS_E_ARG, "transit times: span_max must be finite and >= 0");
-        n_taps += (size_t)width[r];
-    }
+    RowTables tb;
+    int rc = build_row_tables(ctx, "transit times", "null argument", shape_values, shape_offset, width, span_max, n_rows, true, tb);
+    if (rc) return rc;
     if (!t || !y || !dy || !curve || !period || !T0 || !row || !reach || !out || !out_times) return fail(ctx, TLS_E_ARG, "null argument");
-    if (n < 1 || n > tlsdev::kTimesMaxPoints) return fail(ctx, TLS_E_ARG, "transit times: n out of range [1, 2^30]");
-    if (n_fits > INT32_MAX || (uint64_t)n_curves > (uint64_t)(INT64_MAX / 16) / (uint64_t)n)
-        return fail(ctx, TLS_E_ARG, "transit times: batch too large");
-    for (int64_t i = 0; i < n; ++i)
-        if (!std::isfinite(t[i]) || (i > 0 && t[i] < t[i - 1]))
-            return fail(ctx, TLS_E_ARG, "transit times: the time stamps must be finite and non-decreasing");
-    for (int64_t f = 0; f < n_fits; ++f) {
-        if (curve[f] < 0 || curve[f] >= n_curves) return fail(ctx, TLS_E_ARG, "transit times: curve out of range [0, n_curves)");
-        if (row[f] < 0 || row[f] >= n_rows) return fail(ctx, TLS_E_ARG, "transit times: row out of range [0, n_rows)");
-        if (reach[f] < 1 || reach[f] > TLS_TIMES_MAX_REACH) return fail(ctx, TLS_E_ARG, "transit times: reach out of range [1, 4096]");
-    }
-    // the rows and their taps: pairs (b, b * b) and triples (g, b * g, g * g), g the shape's slope per sample
-    std::vector<tlsdev::SingleRow> h_rows((size_t)n_rows);
-    std::vector<double> h_taps(2 * n_taps), h_slopes(3 * n_taps);
-    size_t at = 0;
-    for (int64_t r = 0; r < n_rows; ++r) {
-        h_rows[(size_t)r].width = (int)width[r];
-        h_rows[(size_t)r].offset = (int)at;
-        h_rows[(size_t)r].span_max = span_max[r];
-        const double* b = shape_values + shape_offset[r];
-        for (int64_t j = 0; j < width[r]; ++j, ++at) {
-            const double v = b[j];
-            const double next = j + 1 < width[r] ? b[j + 1] : 0.0, prev = j > 0 ? b[j - 1] : 0.0;
-            const double rise = next - prev;
-            const double g = 0.5 * rise;
-            h_taps[2 * at] = v;
-            h_taps[2 * at + 1] = v * v;
-            h_slopes[3 * at] = g;
-            h_slopes[3 * at + 1] = v * g;
-            h_slopes[3 * at + 2] = g * g;
-        }
-    }
+    if ((rc = check_batch(ctx, "transit times", n, tlsdev::kTimesMaxPoints, "[1, 2^30]", n_fits, n_curves))
+        || (rc = check_time_stamps(ctx, "transit times", t, n)))
+        return rc;
+    if ((rc = check_curves(ctx, "transit times", curve, n_fits, n_curves, [&](int64_t f) {
+            if (row[f] < 0 || row[f] >= n_rows) return fail(ctx, TLS_E_ARG, "transit times: row out of range [0, n_rows)");
+            if (reach[f] < 1 || reach[f] > TLS_TIMES_MAX_REACH) return fail(ctx, TLS_E_ARG, "transit times: reach out of range [1, 4096]");
+            return TLS_OK;
+        })))
+        return rc;
     TLS_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t nn = (size_t)n, me = (size_t)max_epochs;
+    const size_t nn = (size_t)n, me = (size_t)max_epochs, n_taps = tb.n_taps;
     const size_t eph_words = tlsdev::kTimesEphemerisWords, time_words = (size_t)tlsdev::kTimesTimeWords * me;
     // a slab: at most 1024 candidates on at most 1024 curves, 256 MB of curves (32 bytes a point) and 256 MB of epoch records
     const size_t budget = 256u << 20;
@@ -3435,10 +3511,7 @@ int tls_transit_times(tls_ctx* ctx, const double* t, const double* y, const doub
     tlsdev::SingleRow* d_rows = reinterpret_cast<tlsdev::SingleRow*>(d_t + nn);
     double* d_taps = d_t + nn + 2 * (size_t)n_rows;
     double* d_slopes = d_taps + 2 * n_taps;
-    if (!ctx->d_check.ptr) {
-        TLS_HIP(ctx, ctx->d_check.reserve(tlsdev::kChecks));
-        TLS_HIP(ctx, hipMemsetAsync(ctx->d_check.ptr, 0, tlsdev::kChecks * sizeof(unsigned long long), ctx->stream));
-    }
+    if ((rc = ensure_check_counters(ctx))) return rc;
     tlsdev::TimesPairsArgs p;
     p.y = d_y; p.dy = d_dy; p.pairs = d_pairs;
     tlsdev::TimesArgs a;
@@ -3446,66 +3519,30 @@ int tls_transit_times(tls_ctx* ctx, const double* t, const double* y, const doub
     a.slot = d_ints; a.row = d_ints + sl; a.reach = d_ints + 2 * sl;
     a.period = d_period; a.T0 = d_T0; a.out = d_out; a.out_times = d_out_times; a.check = ctx->d_check.ptr;
     a.depth_min = depth_min; a.min_ses = min_ses; a.n = (int)n; a.max_epochs = (int)max_epochs;
-    auto pairs_kernel = tlsdev::tls_times_pairs_kernel;
     auto times_kernel = tlsdev::tls_transit_times_kernel;
     TLS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(times_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                      tlsdev::kTimesLdsUnits * 8));
     TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(d_rows, h_rows.data(), (size_t)n_rows * sizeof(tlsdev::SingleRow), hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(d_taps, h_taps.data(), 2 * n_taps * 8, hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(d_slopes, h_slopes.data(), 3 * n_taps * 8, hipMemcpyHostToDevice, ctx->stream));
-    std::vector<int> h_ints(3 * sl);
-    std::unordered_map<int64_t, int> slot_of;
-    struct Run { int64_t curve; size_t slot, count; };      // consecutive curves in consecutive slots: one copy
-    std::vector<Run> runs;
-    for (int64_t f0 = 0; f0 < n_fits;) {
-        slot_of.clear();
-        runs.clear();
-        size_t fits = 0, lds = 0;
-        while (f0 + (int64_t)fits < n_fits && fits < sl) {
-            const int64_t f = f0 + (int64_t)fits;
-            auto it = slot_of.find(curve[f]);
-            if (it == slot_of.end()) {
-                if (slot_of.size() == cs) break;     // (the next slab takes it; a slab's first candidate always finds a slot)
-                const size_t slot = slot_of.size();
-                it = slot_of.emplace(curve[f], (int)slot).first;
-                if (!runs.empty() && runs.back().curve + (int64_t)runs.back().count == curve[f]) ++runs.back().count;
-                else runs.push_back(Run{curve[f], slot, 1});
-            }
-            h_ints[fits] = it->second;
-            h_ints[sl + fits] = (int)row[f];
-            h_ints[2 * sl + fits] = (int)reach[f];
-            lds = std::max(lds, tlsdev::times_lds_bytes((int)reach[f], (int)max_epochs));
-            ++fits;
-        }
-        for (const Run& run : runs) {
-            const size_t from = (size_t)run.curve * nn, to = run.slot * nn, bytes = run.count * nn * 8;
-            TLS_HIP(ctx, hipMemcpyAsync(d_y + to, y + from, bytes, hipMemcpyHostToDevice, ctx->stream));
-            TLS_HIP(ctx, hipMemcpyAsync(d_dy + to, dy + from, bytes, hipMemcpyHostToDevice, ctx->stream));
-        }
-        TLS_HIP(ctx, hipMemcpyAsync(d_ints, h_ints.data(), 3 * sl * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(d_period, period + f0, fits * 8, hipMemcpyHostToDevice, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(d_T0, T0 + f0, fits * 8, hipMemcpyHostToDevice, ctx->stream));
-        p.count = (long long)(slot_of.size() * nn);
-        const unsigned blocks = (unsigned)std::min<long long>((p.count + tlsdev::kTimesThreads - 1) / tlsdev::kTimesThreads, 8192);
-        hipLaunchKernelGGL(pairs_kernel, dim3(blocks), dim3(tlsdev::kTimesThreads), 0, ctx->stream, p);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(times_kernel, dim3((unsigned)fits), dim3(tlsdev::kTimesThreads), lds, ctx->stream, a);
-            e = hipGetLastError();
-        }
-        if (e != hipSuccess) {
-            (void)hipStreamSynchronize(ctx->stream);
-            return fail(ctx, TLS_E_HIP, std::string("transit times launch: ") + hipGetErrorString(e));
-        }
-        ctx->last_kernel = "tls_transit_times";
-        TLS_HIP(ctx, hipMemcpyAsync(out + f0, d_out, fits * eph_words * 8, hipMemcpyDeviceToHost, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(out_times + (size_t)f0 * me, d_out_times, fits * time_words * 8, hipMemcpyDeviceToHost, ctx->stream));
-        // (the next slab overwrites the device buffers and h_ints; h_rows, h_taps and h_slopes are read until the stream is done)
-        TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        f0 += (int64_t)fits;
-    }
-    return TLS_OK;
+    TLS_HIP(ctx, hipMemcpyAsync(d_rows, tb.rows.data(), (size_t)n_rows * sizeof(tlsdev::SingleRow), hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_taps, tb.taps.data(), 2 * n_taps * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_slopes, tb.slopes.data(), 3 * n_taps * 8, hipMemcpyHostToDevice, ctx->stream));
+    const SlabStage stage{"transit times", "tls_transit_times", curve, n_fits, nn, cs, sl,
+                          {{d_y, y}, {d_dy, dy}}, {{d_period, period}, {d_T0, T0}}, d_ints, 3};
+    return run_candidate_slabs(ctx, stage,
+        [&](int64_t f, int* at) {
+            at[sl] = (int)row[f];
+            at[2 * sl] = (int)reach[f];
+            return tlsdev::times_lds_bytes((int)reach[f], (int)max_epochs);
+        },
+        [&](const SlabView& s) {
+            if (launch_times_pairs(ctx, p, s.curves, nn))
+                hipLaunchKernelGGL(times_kernel, dim3((unsigned)s.fits), dim3(tlsdev::kTimesThreads), s.lds, ctx->stream, a);
+        },
+        [&](const SlabView& s) {
+            TLS_HIP(ctx, hipMemcpyAsync(out + s.f0, d_out, s.fits * eph_words * 8, hipMemcpyDeviceToHost, ctx->stream));
+            TLS_HIP(ctx, hipMemcpyAsync(out_times + (size_t)s.f0 * me, d_out_times, s.fits * time_words * 8, hipMemcpyDeviceToHost, ctx->stream));
+            return TLS_OK;
+        });
 }
 
 // ---- per-transit event vetting (tls_events.hip.h, DESIGN.md "Event vetting"): the pairs kernel of the transit times over the
@@ -3531,53 +3568,28 @@ int tls_event_vetting(tls_ctx* ctx, const double* t, const double* y, const doub
     if (!(point_fraction > 0.0)) return fail(ctx, TLS_E_ARG, "event vetting: point_fraction must be > 0");
     if (!(step_fraction > 0.0)) return fail(ctx, TLS_E_ARG, "event vetting: step_fraction must be > 0");
     if (n_fits == 0) return TLS_OK;
-    if (n_rows < 1) return fail(ctx, TLS_E_ARG, "event vetting: at least one row is needed");
-    if (!shape_values || !shape_offset || !width || !span_max) return fail(ctx, TLS_E_ARG, "event vetting: null argument");
-    if (n_rows > TLS_SINGLE_MAX_WIDTH) return fail(ctx, TLS_E_ARG, "event vetting: more rows than widths there are");
-    size_t n_taps = 0;
-    for (int64_t r = 0; r < n_rows; ++r) {
-        if (width[r] < tlsdev::kSingleMinWidth || width[r] > TLS_SINGLE_MAX_WIDTH)
-            return fail(ctx, TLS_E_ARG, "event vetting: width out of range [3, 4096]");
-        if (r > 0 && width[r] <= width[r - 1]) return fail(ctx, TLS_E_ARG, "event vetting: the widths must be strictly ascending");
-        if (shape_offset[r] < 0) return fail(ctx, TLS_E_ARG, "event vetting: negative shape offset");
-        if (!(std::isfinite(span_max[r]) && span_max[r] >= 0.0)) return fail(ctx, TLS_E_ARG, "event vetting: span_max must be finite and >= 0");
-        n_taps += (size_t)width[r];
-    }
+    RowTables tb;
+    int rc = build_row_tables(ctx, "event vetting", "event vetting: null argument", shape_values, shape_offset, width, span_max,
+                              n_rows, false, tb);
+    if (rc) return rc;
     if (!t || !y || !dy || !curve || !period || !T0 || !row || !reach || !chase_reach || !guard || !chase_span || !out || !out_events)
         return fail(ctx, TLS_E_ARG, "event vetting: null argument");
-    if (n < 1 || n > tlsdev::kTimesMaxPoints) return fail(ctx, TLS_E_ARG, "event vetting: n out of range [1, 2^30]");
-    if (n_fits > INT32_MAX || (uint64_t)n_curves > (uint64_t)(INT64_MAX / 16) / (uint64_t)n)
-        return fail(ctx, TLS_E_ARG, "event vetting: batch too large");
-    for (int64_t i = 0; i < n; ++i)
-        if (!std::isfinite(t[i]) || (i > 0 && t[i] < t[i - 1]))
-            return fail(ctx, TLS_E_ARG, "event vetting: the time stamps must be finite and non-decreasing");
-    for (int64_t f = 0; f < n_fits; ++f) {
-        if (curve[f] < 0 || curve[f] >= n_curves) return fail(ctx, TLS_E_ARG, "event vetting: curve out of range [0, n_curves)");
-        if (row[f] < 0 || row[f] >= n_rows) return fail(ctx, TLS_E_ARG, "event vetting: row out of range [0, n_rows)");
-        if (reach[f] < 1 || reach[f] > TLS_TIMES_MAX_REACH) return fail(ctx, TLS_E_ARG, "event vetting: reach out of range [1, 4096]");
-        if (chase_reach[f] < 0 || chase_reach[f] > TLS_EVENTS_MAX_CHASE)
-            return fail(ctx, TLS_E_ARG, "event vetting: chase_reach out of range [0, 8192]");
-        if (guard[f] < 0) return fail(ctx, TLS_E_ARG, "event vetting: negative guard");
-        if (!(std::isfinite(chase_span[f]) && chase_span[f] > 0.0))
-            return fail(ctx, TLS_E_ARG, "event vetting: chase_span must be finite and > 0");
-    }
-    // the rows and their taps: pairs (b, b * b)
-    std::vector<tlsdev::SingleRow> h_rows((size_t)n_rows);
-    std::vector<double> h_taps(2 * n_taps);
-    size_t at = 0;
-    for (int64_t r = 0; r < n_rows; ++r) {
-        h_rows[(size_t)r].width = (int)width[r];
-        h_rows[(size_t)r].offset = (int)at;
-        h_rows[(size_t)r].span_max = span_max[r];
-        const double* b = shape_values + shape_offset[r];
-        for (int64_t j = 0; j < width[r]; ++j, ++at) {
-            const double v = b[j];
-            h_taps[2 * at] = v;
-            h_taps[2 * at + 1] = v * v;
-        }
-    }
+    if ((rc = check_batch(ctx, "event vetting", n, tlsdev::kTimesMaxPoints, "[1, 2^30]", n_fits, n_curves))
+        || (rc = check_time_stamps(ctx, "event vetting", t, n)))
+        return rc;
+    if ((rc = check_curves(ctx, "event vetting", curve, n_fits, n_curves, [&](int64_t f) {
+            if (row[f] < 0 || row[f] >= n_rows) return fail(ctx, TLS_E_ARG, "event vetting: row out of range [0, n_rows)");
+            if (reach[f] < 1 || reach[f] > TLS_TIMES_MAX_REACH) return fail(ctx, TLS_E_ARG, "event vetting: reach out of range [1, 4096]");
+            if (chase_reach[f] < 0 || chase_reach[f] > TLS_EVENTS_MAX_CHASE)
+                return fail(ctx, TLS_E_ARG, "event vetting: chase_reach out of range [0, 8192]");
+            if (guard[f] < 0) return fail(ctx, TLS_E_ARG, "event vetting: negative guard");
+            if (!(std::isfinite(chase_span[f]) && chase_span[f] > 0.0))
+                return fail(ctx, TLS_E_ARG, "event vetting: chase_span must be finite and > 0");
+            return TLS_OK;
+        })))
+        return rc;
     TLS_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t nn = (size_t)n, me = (size_t)max_epochs;
+    const size_t nn = (size_t)n, me = (size_t)max_epochs, n_taps = tb.n_taps;
     const size_t sum_words = tlsdev::kEventsSummaryWords, event_words = (size_t)tlsdev::kEventsRecordWords * me;
     // a slab: at most 1024 candidates on at most 1024 curves, 256 MB of curves (32 bytes a point) and 256 MB of event records
     // and held sums (16 doubles an epoch)
@@ -3601,10 +3613,7 @@ int tls_event_vetting(tls_ctx* ctx, const double* t, const double* y, const doub
     double* d_t = d_span + sl + (5 * sl + 1) / 2;
     tlsdev::SingleRow* d_rows = reinterpret_cast<tlsdev::SingleRow*>(d_t + nn);
     double* d_taps = d_t + nn + 2 * (size_t)n_rows;
-    if (!ctx->d_check.ptr) {
-        TLS_HIP(ctx, ctx->d_check.reserve(tlsdev::kChecks));
-        TLS_HIP(ctx, hipMemsetAsync(ctx->d_check.ptr, 0, tlsdev::kChecks * sizeof(unsigned long long), ctx->stream));
-    }
+    if ((rc = ensure_check_counters(ctx))) return rc;
     tlsdev::TimesPairsArgs p;
     p.y = d_y; p.dy = d_dy; p.pairs = d_pairs;
     tlsdev::EventsArgs a;
@@ -3614,68 +3623,31 @@ int tls_event_vetting(tls_ctx* ctx, const double* t, const double* y, const doub
     a.check = ctx->d_check.ptr;
     a.depth_min = depth_min; a.min_ses = min_ses; a.chase_fraction = chase_fraction; a.chase_min = chase_min;
     a.point_fraction = point_fraction; a.step_fraction = step_fraction; a.n = (int)n; a.max_epochs = (int)max_epochs;
-    auto pairs_kernel = tlsdev::tls_times_pairs_kernel;
     auto events_kernel = tlsdev::tls_event_vetting_kernel;
     TLS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(events_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                      tlsdev::kTimesLdsUnits * 8));
     TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(d_rows, h_rows.data(), (size_t)n_rows * sizeof(tlsdev::SingleRow), hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(d_taps, h_taps.data(), 2 * n_taps * 8, hipMemcpyHostToDevice, ctx->stream));
-    std::vector<int> h_ints(5 * sl);
-    std::unordered_map<int64_t, int> slot_of;
-    struct Run { int64_t curve; size_t slot, count; };      // consecutive curves in consecutive slots: one copy
-    std::vector<Run> runs;
-    for (int64_t f0 = 0; f0 < n_fits;) {
-        slot_of.clear();
-        runs.clear();
-        size_t fits = 0, lds = 0;
-        while (f0 + (int64_t)fits < n_fits && fits < sl) {
-            const int64_t f = f0 + (int64_t)fits;
-            auto it = slot_of.find(curve[f]);
-            if (it == slot_of.end()) {
-                if (slot_of.size() == cs) break;     // (the next slab takes it; a slab's first candidate always finds a slot)
-                const size_t slot = slot_of.size();
-                it = slot_of.emplace(curve[f], (int)slot).first;
-                if (!runs.empty() && runs.back().curve + (int64_t)runs.back().count == curve[f]) ++runs.back().count;
-                else runs.push_back(Run{curve[f], slot, 1});
-            }
-            h_ints[fits] = it->second;
-            h_ints[sl + fits] = (int)row[f];
-            h_ints[2 * sl + fits] = (int)reach[f];
-            h_ints[3 * sl + fits] = (int)chase_reach[f];
-            h_ints[4 * sl + fits] = (int)std::min(guard[f], chase_reach[f]);   // (a guard at or beyond the reach: no chase window)
-            lds = std::max(lds, tlsdev::times_lds_bytes((int)reach[f], (int)max_epochs));
-            ++fits;
-        }
-        for (const Run& run : runs) {
-            const size_t from = (size_t)run.curve * nn, to = run.slot * nn, bytes = run.count * nn * 8;
-            TLS_HIP(ctx, hipMemcpyAsync(d_y + to, y + from, bytes, hipMemcpyHostToDevice, ctx->stream));
-            TLS_HIP(ctx, hipMemcpyAsync(d_dy + to, dy + from, bytes, hipMemcpyHostToDevice, ctx->stream));
-        }
-        TLS_HIP(ctx, hipMemcpyAsync(d_ints, h_ints.data(), 5 * sl * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(d_period, period + f0, fits * 8, hipMemcpyHostToDevice, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(d_T0, T0 + f0, fits * 8, hipMemcpyHostToDevice, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(d_span, chase_span + f0, fits * 8, hipMemcpyHostToDevice, ctx->stream));
-        p.count = (long long)(slot_of.size() * nn);
-        const unsigned blocks = (unsigned)std::min<long long>((p.count + tlsdev::kTimesThreads - 1) / tlsdev::kTimesThreads, 8192);
-        hipLaunchKernelGGL(pairs_kernel, dim3(blocks), dim3(tlsdev::kTimesThreads), 0, ctx->stream, p);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(events_kernel, dim3((unsigned)fits), dim3(tlsdev::kEventsThreads), lds, ctx->stream, a);
-            e = hipGetLastError();
-        }
-        if (e != hipSuccess) {
-            (void)hipStreamSynchronize(ctx->stream);
-            return fail(ctx, TLS_E_HIP, std::string("event vetting launch: ") + hipGetErrorString(e));
-        }
-        ctx->last_kernel = "tls_event_vetting";
-        TLS_HIP(ctx, hipMemcpyAsync(out + f0, d_out, fits * sum_words * 8, hipMemcpyDeviceToHost, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(out_events + (size_t)f0 * me, d_out_events, fits * event_words * 8, hipMemcpyDeviceToHost, ctx->stream));
-        // (the next slab overwrites the device buffers and h_ints; h_rows and h_taps are read until the stream is done)
-        TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        f0 += (int64_t)fits;
-    }
-    return TLS_OK;
+    TLS_HIP(ctx, hipMemcpyAsync(d_rows, tb.rows.data(), (size_t)n_rows * sizeof(tlsdev::SingleRow), hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_taps, tb.taps.data(), 2 * n_taps * 8, hipMemcpyHostToDevice, ctx->stream));
+    const SlabStage stage{"event vetting", "tls_event_vetting", curve, n_fits, nn, cs, sl,
+                          {{d_y, y}, {d_dy, dy}}, {{d_period, period}, {d_T0, T0}, {d_span, chase_span}}, d_ints, 5};
+    return run_candidate_slabs(ctx, stage,
+        [&](int64_t f, int* at) {
+            at[sl] = (int)row[f];
+            at[2 * sl] = (int)reach[f];
+            at[3 * sl] = (int)chase_reach[f];
+            at[4 * sl] = (int)std::min(guard[f], chase_reach[f]);   // (a guard at or beyond the reach: no chase window)
+            return tlsdev::times_lds_bytes((int)reach[f], (int)max_epochs);
+        },
+        [&](const SlabView& s) {
+            if (launch_times_pairs(ctx, p, s.curves, nn))
+                hipLaunchKernelGGL(events_kernel, dim3((unsigned)s.fits), dim3(tlsdev::kEventsThreads), s.lds, ctx->stream, a);
+        },
+        [&](const SlabView& s) {
+            TLS_HIP(ctx, hipMemcpyAsync(out + s.f0, d_out, s.fits * sum_words * 8, hipMemcpyDeviceToHost, ctx->stream));
+            TLS_HIP(ctx, hipMemcpyAsync(out_events + (size_t)s.f0 * me, d_out_events, s.fits * event_words * 8, hipMemcpyDeviceToHost, ctx->stream));
+            return TLS_OK;
+        });
 }
 
 // ---- the trapezoid shape fit (tls_shape.hip.h, DESIGN.md "Shape fit"): the pairs kernel of the transit times over the curves
@@ -3705,14 +3677,10 @@ int tls_shape_fit(tls_ctx* ctx, const double* t, const double* y, const double* 
     if (!(std::isfinite(depth_min) && depth_min >= 0.0)) return fail(ctx, TLS_E_ARG, "shape fit: depth_min must be finite and >= 0");
     if (n_fits == 0) return TLS_OK;
     if (!t || !y || !dy || !curve || !period || !T0 || !duration || !out) return fail(ctx, TLS_E_ARG, "null argument");
-    if (n < 1 || n > tlsdev::kShapeMaxPoints) return fail(ctx, TLS_E_ARG, "shape fit: n out of range [1, 2^22]");
-    if (n_fits > INT32_MAX || (uint64_t)n_curves > (uint64_t)(INT64_MAX / 16) / (uint64_t)n)
-        return fail(ctx, TLS_E_ARG, "shape fit: batch too large");
-    for (int64_t i = 0; i < n; ++i)
-        if (!std::isfinite(t[i]) || (i > 0 && t[i] < t[i - 1]))
-            return fail(ctx, TLS_E_ARG, "shape fit: the time stamps must be finite and non-decreasing");
-    for (int64_t f = 0; f < n_fits; ++f)
-        if (curve[f] < 0 || curve[f] >= n_curves) return fail(ctx, TLS_E_ARG, "shape fit: curve out of range [0, n_curves)");
+    int rc;
+    if ((rc = check_batch(ctx, "shape fit", n, tlsdev::kShapeMaxPoints, "[1, 2^22]", n_fits, n_curves))
+        || (rc = check_time_stamps(ctx, "shape fit", t, n)) || (rc = check_curves(ctx, "shape fit", curve, n_fits, n_curves)))
+        return rc;
     TLS_HIP(ctx, hipSetDevice(ctx->device));
     const size_t nn = (size_t)n, words = tlsdev::kShapeWords, tables = (size_t)(nT + nQ + nS);
     // a slab: at most 1024 candidates on at most 1024 curves, 256 MB of curves (32 bytes a point); the workgroups of a launch:
@@ -3736,10 +3704,7 @@ int tls_shape_fit(tls_ctx* ctx, const double* t, const double* y, const double* 
     double* d_ingress = d_ratio + nT;
     double* d_shift = d_ingress + nQ;
     double* d_scratch = d_shift + nS;
-    if (!ctx->d_check.ptr) {
-        TLS_HIP(ctx, ctx->d_check.reserve(tlsdev::kChecks));
-        TLS_HIP(ctx, hipMemsetAsync(ctx->d_check.ptr, 0, tlsdev::kChecks * sizeof(unsigned long long), ctx->stream));
-    }
+    if ((rc = ensure_check_counters(ctx))) return rc;
     tlsdev::TimesPairsArgs p;
     p.y = d_y; p.dy = d_dy; p.pairs = d_pairs;
     tlsdev::ShapeArgs a;
@@ -3748,62 +3713,22 @@ int tls_shape_fit(tls_ctx* ctx, const double* t, const double* y, const double* 
     a.check = ctx->d_check.ptr; a.window = window; a.depth_min = depth_min;
     a.n = (int)n; a.nT = (int)nT; a.nQ = (int)nQ; a.nS = (int)nS;
     a.min_count = (int)std::min<int64_t>(min_count, INT32_MAX);
-    auto pairs_kernel = tlsdev::tls_times_pairs_kernel;
-    auto shape_kernel = tlsdev::tls_shape_fit_kernel;
     TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, ctx->stream));
     TLS_HIP(ctx, hipMemcpyAsync(d_ratio, ratio, (size_t)nT * 8, hipMemcpyHostToDevice, ctx->stream));
     TLS_HIP(ctx, hipMemcpyAsync(d_ingress, ingress, (size_t)nQ * 8, hipMemcpyHostToDevice, ctx->stream));
     TLS_HIP(ctx, hipMemcpyAsync(d_shift, shift, (size_t)nS * 8, hipMemcpyHostToDevice, ctx->stream));
-    std::vector<int> h_slot(sl);
-    std::unordered_map<int64_t, int> slot_of;
-    struct Run { int64_t curve; size_t slot, count; };      // consecutive curves in consecutive slots: one copy
-    std::vector<Run> runs;
-    for (int64_t f0 = 0; f0 < n_fits;) {
-        slot_of.clear();
-        runs.clear();
-        size_t fits = 0;
-        while (f0 + (int64_t)fits < n_fits && fits < sl) {
-            const int64_t f = f0 + (int64_t)fits;
-            auto it = slot_of.find(curve[f]);
-            if (it == slot_of.end()) {
-                if (slot_of.size() == cs) break;     // (the next slab takes it; a slab's first candidate always finds a slot)
-                const size_t slot = slot_of.size();
-                it = slot_of.emplace(curve[f], (int)slot).first;
-                if (!runs.empty() && runs.back().curve + (int64_t)runs.back().count == curve[f]) ++runs.back().count;
-                else runs.push_back(Run{curve[f], slot, 1});
-            }
-            h_slot[fits] = it->second;
-            ++fits;
-        }
-        for (const Run& run : runs) {
-            const size_t from = (size_t)run.curve * nn, to = run.slot * nn, bytes = run.count * nn * 8;
-            TLS_HIP(ctx, hipMemcpyAsync(d_y + to, y + from, bytes, hipMemcpyHostToDevice, ctx->stream));
-            TLS_HIP(ctx, hipMemcpyAsync(d_dy + to, dy + from, bytes, hipMemcpyHostToDevice, ctx->stream));
-        }
-        TLS_HIP(ctx, hipMemcpyAsync(d_slot, h_slot.data(), fits * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(d_period, period + f0, fits * 8, hipMemcpyHostToDevice, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(d_T0, T0 + f0, fits * 8, hipMemcpyHostToDevice, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(d_duration, duration + f0, fits * 8, hipMemcpyHostToDevice, ctx->stream));
-        p.count = (long long)(slot_of.size() * nn);
-        a.fits = (int)fits;
-        const unsigned blocks = (unsigned)std::min<long long>((p.count + tlsdev::kTimesThreads - 1) / tlsdev::kTimesThreads, 8192);
-        hipLaunchKernelGGL(pairs_kernel, dim3(blocks), dim3(tlsdev::kTimesThreads), 0, ctx->stream, p);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(shape_kernel, dim3((unsigned)std::min(fits, groups)), dim3(tlsdev::kShapeThreads), 0, ctx->stream, a);
-            e = hipGetLastError();
-        }
-        if (e != hipSuccess) {
-            (void)hipStreamSynchronize(ctx->stream);
-            return fail(ctx, TLS_E_HIP, std::string("shape fit launch: ") + hipGetErrorString(e));
-        }
-        ctx->last_kernel = "tls_shape_fit";
-        TLS_HIP(ctx, hipMemcpyAsync(out + f0, d_out, fits * words * 8, hipMemcpyDeviceToHost, ctx->stream));
-        // (the next slab overwrites the device buffers and h_slot)
-        TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        f0 += (int64_t)fits;
-    }
-    return TLS_OK;
+    const SlabStage stage{"shape fit", "tls_shape_fit", curve, n_fits, nn, cs, sl,
+                          {{d_y, y}, {d_dy, dy}}, {{d_period, period}, {d_T0, T0}, {d_duration, duration}}, d_slot, 1};
+    return run_candidate_slabs(ctx, stage, no_int_columns,
+        [&](const SlabView& s) {
+            a.fits = (int)s.fits;
+            if (launch_times_pairs(ctx, p, s.curves, nn))
+                hipLaunchKernelGGL(tlsdev::tls_shape_fit_kernel, dim3((unsigned)std::min(s.fits, groups)), dim3(tlsdev::kShapeThreads), 0, ctx->stream, a);
+        },
+        [&](const SlabView& s) {
+            TLS_HIP(ctx, hipMemcpyAsync(out + s.f0, d_out, s.fits * words * 8, hipMemcpyDeviceToHost, ctx->stream));
+            return TLS_OK;
+        });
 }
 
 // ---- the centroid-shift test (tls_centroid.hip.h, DESIGN.md "Centroid test"): the flux and the two centroid rows of the
@@ -3828,14 +3753,10 @@ int tls_centroid_test(tls_ctx* ctx, const double* t, const double* y, const doub
         if (!std::isfinite(shape[j])) return fail(ctx, TLS_E_ARG, "centroid test: the shape must be finite");
     if (n_fits == 0) return TLS_OK;
     if (!t || !y || !cx || !cy || !curve || !period || !T0 || !duration || !out) return fail(ctx, TLS_E_ARG, "null argument");
-    if (n < 1 || n > tlsdev::kCentroidMaxPoints) return fail(ctx, TLS_E_ARG, "centroid test: n out of range [1, 2^22]");
-    if (n_fits > INT32_MAX || (uint64_t)n_curves > (uint64_t)(INT64_MAX / 16) / (uint64_t)n)
-        return fail(ctx, TLS_E_ARG, "centroid test: batch too large");
-    for (int64_t i = 0; i < n; ++i)
-        if (!std::isfinite(t[i]) || (i > 0 && t[i] < t[i - 1]))
-            return fail(ctx, TLS_E_ARG, "centroid test: the time stamps must be finite and non-decreasing");
-    for (int64_t f = 0; f < n_fits; ++f)
-        if (curve[f] < 0 || curve[f] >= n_curves) return fail(ctx, TLS_E_ARG, "centroid test: curve out of range [0, n_curves)");
+    int rc;
+    if ((rc = check_batch(ctx, "centroid test", n, tlsdev::kCentroidMaxPoints, "[1, 2^22]", n_fits, n_curves))
+        || (rc = check_time_stamps(ctx, "centroid test", t, n)) || (rc = check_curves(ctx, "centroid test", curve, n_fits, n_curves)))
+        return rc;
     TLS_HIP(ctx, hipSetDevice(ctx->device));
     const size_t nn = (size_t)n, words = tlsdev::kCentroidWords, ll = (size_t)L;
     // a slab: at most 1024 candidates on at most 1024 curves, 256 MB of curves (24 bytes a point); the workgroups of a launch:
@@ -3859,64 +3780,26 @@ int tls_centroid_test(tls_ctx* ctx, const double* t, const double* y, const doub
     double* d_t = d_duration + sl + (sl + 1) / 2;
     double* d_b = d_t + nn;
     double* d_scratch = d_b + ll;
-    if (!ctx->d_check.ptr) {
-        TLS_HIP(ctx, ctx->d_check.reserve(tlsdev::kChecks));
-        TLS_HIP(ctx, hipMemsetAsync(ctx->d_check.ptr, 0, tlsdev::kChecks * sizeof(unsigned long long), ctx->stream));
-    }
+    if ((rc = ensure_check_counters(ctx))) return rc;
     tlsdev::CentroidArgs a;
     a.t = d_t; a.y = d_y; a.cx = d_cx; a.cy = d_cy; a.slot = d_slot; a.period = d_period; a.T0 = d_T0; a.duration = d_duration;
     a.shape = d_b; a.scratch = d_scratch; a.out = d_out; a.check = ctx->d_check.ptr; a.window = window;
     a.n = (int)n; a.L = (int)L; a.max_epochs = (int)max_epochs;
     a.min_in = (int)std::min<int64_t>(min_in, INT32_MAX);
     a.min_out = (int)std::min<int64_t>(min_out, INT32_MAX);
-    auto centroid_kernel = tlsdev::tls_centroid_kernel;
     TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, ctx->stream));
     TLS_HIP(ctx, hipMemcpyAsync(d_b, shape, ll * 8, hipMemcpyHostToDevice, ctx->stream));
-    std::vector<int> h_slot(sl);
-    std::unordered_map<int64_t, int> slot_of;
-    struct Run { int64_t curve; size_t slot, count; };      // consecutive curves in consecutive slots: one copy
-    std::vector<Run> runs;
-    for (int64_t f0 = 0; f0 < n_fits;) {
-        slot_of.clear();
-        runs.clear();
-        size_t fits = 0;
-        while (f0 + (int64_t)fits < n_fits && fits < sl) {
-            const int64_t f = f0 + (int64_t)fits;
-            auto it = slot_of.find(curve[f]);
-            if (it == slot_of.end()) {
-                if (slot_of.size() == cs) break;     // (the next slab takes it; a slab's first candidate always finds a slot)
-                const size_t slot = slot_of.size();
-                it = slot_of.emplace(curve[f], (int)slot).first;
-                if (!runs.empty() && runs.back().curve + (int64_t)runs.back().count == curve[f]) ++runs.back().count;
-                else runs.push_back(Run{curve[f], slot, 1});
-            }
-            h_slot[fits] = it->second;
-            ++fits;
-        }
-        for (const Run& run : runs) {
-            const size_t from = (size_t)run.curve * nn, to = run.slot * nn, bytes = run.count * nn * 8;
-            TLS_HIP(ctx, hipMemcpyAsync(d_y + to, y + from, bytes, hipMemcpyHostToDevice, ctx->stream));
-            TLS_HIP(ctx, hipMemcpyAsync(d_cx + to, cx + from, bytes, hipMemcpyHostToDevice, ctx->stream));
-            TLS_HIP(ctx, hipMemcpyAsync(d_cy + to, cy + from, bytes, hipMemcpyHostToDevice, ctx->stream));
-        }
-        TLS_HIP(ctx, hipMemcpyAsync(d_slot, h_slot.data(), fits * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(d_period, period + f0, fits * 8, hipMemcpyHostToDevice, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(d_T0, T0 + f0, fits * 8, hipMemcpyHostToDevice, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(d_duration, duration + f0, fits * 8, hipMemcpyHostToDevice, ctx->stream));
-        a.fits = (int)fits;
-        hipLaunchKernelGGL(centroid_kernel, dim3((unsigned)std::min(fits, groups)), dim3(tlsdev::kCentroidThreads), 0, ctx->stream, a);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) {
-            (void)hipStreamSynchronize(ctx->stream);
-            return fail(ctx, TLS_E_HIP, std::string("centroid test launch: ") + hipGetErrorString(e));
-        }
-        ctx->last_kernel = "tls_centroid_test";
-        TLS_HIP(ctx, hipMemcpyAsync(out + f0, d_out, fits * words * 8, hipMemcpyDeviceToHost, ctx->stream));
-        // (the next slab overwrites the device buffers and h_slot)
-        TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        f0 += (int64_t)fits;
-    }
-    return TLS_OK;
+    const SlabStage stage{"centroid test", "tls_centroid_test", curve, n_fits, nn, cs, sl,
+                          {{d_y, y}, {d_cx, cx}, {d_cy, cy}}, {{d_period, period}, {d_T0, T0}, {d_duration, duration}}, d_slot, 1};
+    return run_candidate_slabs(ctx, stage, no_int_columns,
+        [&](const SlabView& s) {
+            a.fits = (int)s.fits;
+            hipLaunchKernelGGL(tlsdev::tls_centroid_kernel, dim3((unsigned)std::min(s.fits, groups)), dim3(tlsdev::kCentroidThreads), 0, ctx->stream, a);
+        },
+        [&](const SlabView& s) {
+            TLS_HIP(ctx, hipMemcpyAsync(out + s.f0, d_out, s.fits * words * 8, hipMemcpyDeviceToHost, ctx->stream));
+            return TLS_OK;
+        });
 }
 
 // ---- the folded views (tls_views.hip.h, DESIGN.md "Folded views"): one workgroup a candidate, slab by slab; the device writes
@@ -3940,16 +3823,10 @@ int tls_folded_views(tls_ctx* ctx, const double* t, const double* y, int64_t n, 
     if (n_fits == 0) return TLS_OK;
     if (!t || !y || !period || !T0 || !duration || !out || !global_median || !global_count || !local_median || !local_count)
         return fail(ctx, TLS_E_ARG, "null argument");
-    if (n < 1 || n > tlsdev::kViewsMaxPoints) return fail(ctx, TLS_E_ARG, "folded views: n out of range [1, 2^20]");
-    if (n_fits > INT32_MAX || (uint64_t)n_curves > (uint64_t)(INT64_MAX / 16) / (uint64_t)n)
-        return fail(ctx, TLS_E_ARG, "folded views: batch too large");
-    for (int64_t i = 0; i < n; ++i)
-        if (!std::isfinite(t[i]) || (i > 0 && t[i] < t[i - 1]))
-            return fail(ctx, TLS_E_ARG, "folded views: the time stamps must be finite and non-decreasing");
-    for (int64_t f = 0; f < n_fits; ++f) {
-        const int64_t c = curve ? curve[f] : f;
-        if (c < 0 || c >= n_curves) return fail(ctx, TLS_E_ARG, "folded views: curve out of range [0, n_curves)");
-    }
+    int rc;
+    if ((rc = check_batch(ctx, "folded views", n, tlsdev::kViewsMaxPoints, "[1, 2^20]", n_fits, n_curves))
+        || (rc = check_time_stamps(ctx, "folded views", t, n)) || (rc = check_curves(ctx, "folded views", curve, n_fits, n_curves)))
+        return rc;
     TLS_HIP(ctx, hipSetDevice(ctx->device));
     const size_t nn = (size_t)n, words = tlsdev::kViewsWords, ng = (size_t)n_global, nl = (size_t)tlsdev::kViewsLocal * (size_t)n_local;
     // a slab: at most 1024 candidates (256 MB of medians and counts, 12 bytes a bin) on at most 1024 curves, 256 MB of curves;
@@ -3960,6 +3837,8 @@ int tls_folded_views(tls_ctx* ctx, const double* t, const double* y, int64_t n, 
     const size_t stretch = n > tlsdev::kViewsLdsPoints ? tlsdev::views_scratch_words(nn) : 0;
     const size_t groups = std::max<size_t>(1, std::min<size_t>({sl, (size_t)tlsdev::kViewsMaxGroups, stretch ? budget / (8 * stretch) : sl}));
     const size_t ints = (sl * (1 + ng + nl) + 1) / 2;        // slot | global counts | local counts, in doubles
+    // of one slab: y | records | period | T0 | duration | secondary | global and local medians | slot | global and local
+    // counts;  t | scratch
     TLS_HIP(ctx, ctx->d_views.reserve(cs * nn + sl * (words + 4 + ng + nl) + ints + nn + groups * stretch));
     double* d_y = ctx->d_views.ptr;
     double* d_out = d_y + cs * nn;
@@ -3974,65 +3853,30 @@ int tls_folded_views(tls_ctx* ctx, const double* t, const double* y, int64_t n, 
     int* d_lcnt = d_gcnt + sl * ng;
     double* d_t = d_lmed + sl * nl + ints;
     double* d_scratch = d_t + nn;
-    if (!ctx->d_check.ptr) {
-        TLS_HIP(ctx, ctx->d_check.reserve(tlsdev::kChecks));
-        TLS_HIP(ctx, hipMemsetAsync(ctx->d_check.ptr, 0, tlsdev::kChecks * sizeof(unsigned long long), ctx->stream));
-    }
+    if ((rc = ensure_check_counters(ctx))) return rc;
     tlsdev::ViewsArgs a;
     a.t = d_t; a.y = d_y; a.slot = d_slot; a.period = d_period; a.T0 = d_T0; a.duration = d_duration;
     a.secondary = secondary_phase ? d_secondary : nullptr;
     a.scratch = d_scratch; a.out = d_out; a.global_median = d_gmed; a.global_count = d_gcnt; a.local_median = d_lmed;
     a.local_count = d_lcnt; a.check = ctx->d_check.ptr; a.k = local_durations; a.width = local_width;
     a.n = (int)n; a.n_global = (int)n_global; a.n_local = (int)n_local;
-    auto views_kernel = tlsdev::tls_folded_views_kernel;
     TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, ctx->stream));
-    std::vector<int> h_slot(sl);
-    std::unordered_map<int64_t, int> slot_of;
-    struct Run { int64_t curve; size_t slot, count; };      // consecutive curves in consecutive slots: one copy
-    std::vector<Run> runs;
-    for (int64_t f0 = 0; f0 < n_fits;) {
-        slot_of.clear();
-        runs.clear();
-        size_t fits = 0;
-        while (f0 + (int64_t)fits < n_fits && fits < sl) {
-            const int64_t f = f0 + (int64_t)fits;
-            const int64_t c = curve ? curve[f] : f;
-            auto it = slot_of.find(c);
-            if (it == slot_of.end()) {
-                if (slot_of.size() == cs) break;     // (the next slab takes it; a slab's first candidate always finds a slot)
-                const size_t slot = slot_of.size();
-                it = slot_of.emplace(c, (int)slot).first;
-                if (!runs.empty() && runs.back().curve + (int64_t)runs.back().count == c) ++runs.back().count;
-                else runs.push_back(Run{c, slot, 1});
-            }
-            h_slot[fits] = it->second;
-            ++fits;
-        }
-        for (const Run& run : runs)
-            TLS_HIP(ctx, hipMemcpyAsync(d_y + run.slot * nn, y + (size_t)run.curve * nn, run.count * nn * 8, hipMemcpyHostToDevice, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(d_slot, h_slot.data(), fits * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(d_period, period + f0, fits * 8, hipMemcpyHostToDevice, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(d_T0, T0 + f0, fits * 8, hipMemcpyHostToDevice, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(d_duration, duration + f0, fits * 8, hipMemcpyHostToDevice, ctx->stream));
-        if (secondary_phase) TLS_HIP(ctx, hipMemcpyAsync(d_secondary, secondary_phase + f0, fits * 8, hipMemcpyHostToDevice, ctx->stream));
-        a.fits = (int)fits;
-        hipLaunchKernelGGL(views_kernel, dim3((unsigned)std::min(fits, groups)), dim3(tlsdev::kViewsThreads), 0, ctx->stream, a);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) {
-            (void)hipStreamSynchronize(ctx->stream);
-            return fail(ctx, TLS_E_HIP, std::string("folded views launch: ") + hipGetErrorString(e));
-        }
-        ctx->last_kernel = "tls_folded_views";
-        TLS_HIP(ctx, hipMemcpyAsync(out + f0, d_out, fits * words * 8, hipMemcpyDeviceToHost, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(global_median + (size_t)f0 * ng, d_gmed, fits * ng * 8, hipMemcpyDeviceToHost, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(global_count + (size_t)f0 * ng, d_gcnt, fits * ng * 4, hipMemcpyDeviceToHost, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(local_median + (size_t)f0 * nl, d_lmed, fits * nl * 8, hipMemcpyDeviceToHost, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(local_count + (size_t)f0 * nl, d_lcnt, fits * nl * 4, hipMemcpyDeviceToHost, ctx->stream));
-        // (the next slab overwrites the device buffers and h_slot)
-        TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        f0 += (int64_t)fits;
-    }
-    return TLS_OK;
+    const SlabStage stage{"folded views", "tls_folded_views", curve, n_fits, nn, cs, sl, {{d_y, y}},
+                          {{d_period, period}, {d_T0, T0}, {d_duration, duration}, {d_secondary, secondary_phase}}, d_slot, 1};
+    return run_candidate_slabs(ctx, stage, no_int_columns,
+        [&](const SlabView& s) {
+            a.fits = (int)s.fits;
+            hipLaunchKernelGGL(tlsdev::tls_folded_views_kernel, dim3((unsigned)std::min(s.fits, groups)), dim3(tlsdev::kViewsThreads), 0, ctx->stream, a);
+        },
+        [&](const SlabView& s) {
+            const size_t f0 = (size_t)s.f0;
+            TLS_HIP(ctx, hipMemcpyAsync(out + f0, d_out, s.fits * words * 8, hipMemcpyDeviceToHost, ctx->stream));
+            TLS_HIP(ctx, hipMemcpyAsync(global_median + f0 * ng, d_gmed, s.fits * ng * 8, hipMemcpyDeviceToHost, ctx->stream));
+            TLS_HIP(ctx, hipMemcpyAsync(global_count + f0 * ng, d_gcnt, s.fits * ng * 4, hipMemcpyDeviceToHost, ctx->stream));
+            TLS_HIP(ctx, hipMemcpyAsync(local_median + f0 * nl, d_lmed, s.fits * nl * 8, hipMemcpyDeviceToHost, ctx->stream));
+            TLS_HIP(ctx, hipMemcpyAsync(local_count + f0 * nl, d_lcnt, s.fits * nl * 4, hipMemcpyDeviceToHost, ctx->stream));
+            return TLS_OK;
+        });
 }
 
 // ---- the variability periodogram (tls_gls.hip.h, DESIGN.md "Variability periodogram"): the non-uniform DFT of a row matrix,
@@ -4047,9 +3891,7 @@ int check_gls_axes(tls_ctx* ctx, const double* t, int64_t n, int64_t n_min, cons
     if (n < n_min || n > TLS_GLS_MAX_POINTS) return fail(ctx, TLS_E_ARG, "periodogram: n out of range");
     if (F < 1 || F > TLS_GLS_MAX_FREQUENCIES) return fail(ctx, TLS_E_ARG, "periodogram: n_freq out of range [1, 2^24]");
     if (!t || !f) return fail(ctx, TLS_E_ARG, "null argument");
-    for (int64_t i = 0; i < n; ++i)
-        if (!std::isfinite(t[i]) || (i > 0 && t[i] < t[i - 1]))
-            return fail(ctx, TLS_E_ARG, "periodogram: the time stamps must be finite and non-decreasing");
+    if (int rc = check_time_stamps(ctx, "periodogram", t, n)) return rc;
     for (int64_t k = 0; k < F; ++k)
         if (!(std::isfinite(f[k]) && f[k] > 0.0)) return fail(ctx, TLS_E_ARG, "periodogram: every frequency must be finite and > 0");
     return TLS_OK;
@@ -4232,14 +4074,10 @@ int tls_sine_test(tls_ctx* ctx, const double* t, const double* y, const double* 
     if ((T0 == nullptr) != (duration == nullptr)) return fail(ctx, TLS_E_ARG, "sine test: T0 and duration come together");
     if (n_fits == 0) return TLS_OK;
     if (!t || !y || !curve || !period || !out || !out_harmonics) return fail(ctx, TLS_E_ARG, "null argument");
-    if (n < 1 || n > TLS_GLS_MAX_POINTS) return fail(ctx, TLS_E_ARG, "sine test: n out of range [1, 2^22]");
-    if (n_fits > INT32_MAX || (uint64_t)n_curves > (uint64_t)(INT64_MAX / 16) / (uint64_t)n)
-        return fail(ctx, TLS_E_ARG, "sine test: batch too large");
-    for (int64_t i = 0; i < n; ++i)
-        if (!std::isfinite(t[i]) || (i > 0 && t[i] < t[i - 1]))
-            return fail(ctx, TLS_E_ARG, "sine test: the time stamps must be finite and non-decreasing");
-    for (int64_t f = 0; f < n_fits; ++f)
-        if (curve[f] < 0 || curve[f] >= n_curves) return fail(ctx, TLS_E_ARG, "sine test: curve out of range [0, n_curves)");
+    int rc;
+    if ((rc = check_batch(ctx, "sine test", n, TLS_GLS_MAX_POINTS, "[1, 2^22]", n_fits, n_curves))
+        || (rc = check_time_stamps(ctx, "sine test", t, n)) || (rc = check_curves(ctx, "sine test", curve, n_fits, n_curves)))
+        return rc;
     TLS_HIP(ctx, hipSetDevice(ctx->device));
     const size_t nn = (size_t)n, nH = (size_t)n_harmonics;
     // a slab: at most 1024 candidates on at most 1024 curves, 256 MB of curves
@@ -4265,54 +4103,20 @@ int tls_sine_test(tls_ctx* ctx, const double* t, const double* y, const double* 
     a.out = d_out; a.out_h = d_out_h; a.out_sums = out_sums ? d_sums : nullptr; a.mask = mask; a.n = (int)n; a.nH = (int)n_harmonics;
     TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, ctx->stream));
     TLS_HIP(ctx, hipMemcpyAsync(d_harmonics, harmonics, nH * 8, hipMemcpyHostToDevice, ctx->stream));
-    std::vector<int> h_slot(sl);
-    std::unordered_map<int64_t, int> slot_of;
-    struct Run { int64_t curve; size_t slot, count; };      // consecutive curves in consecutive slots: one copy
-    std::vector<Run> runs;
-    for (int64_t f0 = 0; f0 < n_fits;) {
-        slot_of.clear();
-        runs.clear();
-        size_t fits = 0;
-        while (f0 + (int64_t)fits < n_fits && fits < sl) {
-            const int64_t f = f0 + (int64_t)fits;
-            auto it = slot_of.find(curve[f]);
-            if (it == slot_of.end()) {
-                if (slot_of.size() == cs) break;     // (the next slab takes it; a slab's first candidate always finds a slot)
-                const size_t slot = slot_of.size();
-                it = slot_of.emplace(curve[f], (int)slot).first;
-                if (!runs.empty() && runs.back().curve + (int64_t)runs.back().count == curve[f]) ++runs.back().count;
-                else runs.push_back(Run{curve[f], slot, 1});
-            }
-            h_slot[fits] = it->second;
-            ++fits;
-        }
-        for (const Run& run : runs) {
-            const size_t from = (size_t)run.curve * nn, to = run.slot * nn, bytes = run.count * nn * 8;
-            TLS_HIP(ctx, hipMemcpyAsync(d_y + to, y + from, bytes, hipMemcpyHostToDevice, ctx->stream));
-            if (dy) TLS_HIP(ctx, hipMemcpyAsync(d_dy + to, dy + from, bytes, hipMemcpyHostToDevice, ctx->stream));
-        }
-        TLS_HIP(ctx, hipMemcpyAsync(d_slot, h_slot.data(), fits * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(d_period, period + f0, fits * 8, hipMemcpyHostToDevice, ctx->stream));
-        if (T0) {
-            TLS_HIP(ctx, hipMemcpyAsync(d_T0, T0 + f0, fits * 8, hipMemcpyHostToDevice, ctx->stream));
-            TLS_HIP(ctx, hipMemcpyAsync(d_duration, duration + f0, fits * 8, hipMemcpyHostToDevice, ctx->stream));
-        }
-        a.fits = (int)fits;
-        hipLaunchKernelGGL(tlsdev::tls_sine_test_kernel, dim3((unsigned)fits), dim3(tlsdev::kSineThreads), 0, ctx->stream, a);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) {
-            (void)hipStreamSynchronize(ctx->stream);
-            return fail(ctx, TLS_E_HIP, std::string("sine test launch: ") + hipGetErrorString(e));
-        }
-        ctx->last_kernel = "tls_sine_test";
-        TLS_HIP(ctx, hipMemcpyAsync(out + f0, d_out, fits * sizeof(tls_sine_record), hipMemcpyDeviceToHost, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(out_harmonics + (size_t)f0 * nH, d_out_h, fits * nH * sizeof(tls_sine_harmonic), hipMemcpyDeviceToHost, ctx->stream));
-        if (out_sums) TLS_HIP(ctx, hipMemcpyAsync(out_sums + (size_t)f0 * nH * 6, d_sums, fits * nH * 48, hipMemcpyDeviceToHost, ctx->stream));
-        // (the next slab overwrites the device buffers and h_slot)
-        TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        f0 += (int64_t)fits;
-    }
-    return TLS_OK;
+    const SlabStage stage{"sine test", "tls_sine_test", curve, n_fits, nn, cs, sl,
+                          {{d_y, y}, {d_dy, dy}}, {{d_period, period}, {d_T0, T0}, {d_duration, duration}}, d_slot, 1};
+    return run_candidate_slabs(ctx, stage, no_int_columns,
+        [&](const SlabView& s) {
+            a.fits = (int)s.fits;
+            hipLaunchKernelGGL(tlsdev::tls_sine_test_kernel, dim3((unsigned)s.fits), dim3(tlsdev::kSineThreads), 0, ctx->stream, a);
+        },
+        [&](const SlabView& s) {
+            const size_t f0 = (size_t)s.f0;
+            TLS_HIP(ctx, hipMemcpyAsync(out + f0, d_out, s.fits * sizeof(tls_sine_record), hipMemcpyDeviceToHost, ctx->stream));
+            TLS_HIP(ctx, hipMemcpyAsync(out_harmonics + f0 * nH, d_out_h, s.fits * nH * sizeof(tls_sine_harmonic), hipMemcpyDeviceToHost, ctx->stream));
+            if (out_sums) TLS_HIP(ctx, hipMemcpyAsync(out_sums + f0 * nH * 6, d_sums, s.fits * nH * 48, hipMemcpyDeviceToHost, ctx->stream));
+            return TLS_OK;
+        });
 }
 
 // ---- the ephemeris match (tls_match.hip.h, DESIGN.md "Ephemeris match"): every candidate against every other, the g range in
@@ -4623,6 +4427,23 @@ int tls_grid_cells(const double* t, int64_t n, const double* periods, int64_t n_
     if (!plan_periods(widths, params, periods, n_periods, t_max - t_min, n, n + padded_width(widths), nullptr, cells_per_period, &gp)) {
         g_create_error = "tls_grid_cells: periods must be positive and finite";
         return TLS_E_ARG;
+    }
+    return TLS_OK;
+}
+
+int tls_debug_candidate_slabs(const int64_t* curve, int64_t n_fits, int64_t max_curves, int64_t max_fits, int64_t* out_slab,
+                              int64_t* out_slot, int64_t* out_runs, int64_t* n_slabs) {
+    if (n_fits < 0 || max_curves < 1 || max_fits < 1 || !n_slabs || (n_fits > 0 && (!out_slab || !out_slot || !out_runs))) {
+        g_create_error = "tls_debug_candidate_slabs: invalid argument";
+        return TLS_E_ARG;
+    }
+    std::vector<int> slot((size_t)std::min(max_fits, n_fits));
+    tlsslab::Slab slab;
+    *n_slabs = 0;
+    for (int64_t f0 = 0; f0 < n_fits; f0 += (int64_t)slab.fits, ++*n_slabs) {
+        tlsslab::next_slab(curve, n_fits, f0, (size_t)max_curves, (size_t)max_fits, slot.data(), slab);
+        for (size_t i = 0; i < slab.fits; ++i) { out_slab[f0 + (int64_t)i] = *n_slabs; out_slot[f0 + (int64_t)i] = slot[i]; }
+        out_runs[*n_slabs] = (int64_t)slab.runs.size();
     }
     return TLS_OK;
 }
