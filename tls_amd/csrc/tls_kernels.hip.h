@@ -2285,6 +2285,67 @@ __device__ __forceinline__ void dot_windows_weighted_rt(const double* ew, const 
     }
 }
 
+// dot_windows<true, XTH> of the four-slot kernel with the taps BROADCAST FROM LANES instead of held in SGPRs: lane l of a
+// VGPR pair holds tap base + (l & 15), loaded by one global_load_dwordx2 of the wave, and each FMA names its tap by the
+// row_newbcast index of v_fmac_f64_dpp (the tap is its first source).  A vector load is counted by vmcnt and returns in
+// order, so the pair(s) of step t + 1 are requested before the reads of step t, and lgkmcnt counts the eight ds_read_b64
+// alone: sample u is multiplied behind lgkmcnt(7 - u), when IT has landed.  The same FMAs on the same operands in the same
+// order per accumulator as dot_windows: the same bits.  No scalar register in the loop.
+//   e_addr: the LDS byte address of the lane's first sample; tap_off: the byte offset in `q` of the lane's tap of step 0,
+//   8 * (q_offset - S + (lane & 15)); n_steps >= 1 steps of kU samples; ta0: the lane's tap of step 0, which the caller
+//   loads beside the batch's unit so that the two round trips overlap (the second pair of XTH >= 3 is requested here).  The 16-wide pairs and the request past the last
+//   step stay inside the row's zero pads (pad_front / pad_back: at most 38 entries behind the row's L + 1 taps are read).
+// EXEC MUST BE ALL ONES: a DPP read of a disabled source lane drops the write.  The callers run these loops on every lane
+// (a lane without a unit works on unit 0) from wave-uniform branches only.  The whole loop is ONE asm block: the compiler
+// sees no register with a load in flight.  The text comes from tools/gen_slim_dot_asm.py.
+#include "tls_slim_dot_asm.inc.h"
+template <int XTH>
+__device__ __forceinline__ void slim_dot_windows(unsigned e_addr, const double* q, unsigned tap_off, int n_steps, double ta0, double (&B)[kR]) {
+    static_assert(kR == 5 && kU == 8 && XTH >= 1 && XTH <= kMaxTiledStride, "the asm text is written for these");
+    double x0, x1, x2, x3, x4, x5, x6, x7, tb0;
+    if constexpr (kU + (kR - 1) * XTH <= 16) {   // the kU + S taps of a step fit one pair
+#define SLIM_DOT_OPERANDS \
+        : [b0] "+v"(B[0]), [b1] "+v"(B[1]), [b2] "+v"(B[2]), [b3] "+v"(B[3]), [b4] "+v"(B[4]), \
+          [x0] "=&v"(x0), [x1] "=&v"(x1), [x2] "=&v"(x2), [x3] "=&v"(x3), [x4] "=&v"(x4), [x5] "=&v"(x5), [x6] "=&v"(x6), [x7] "=&v"(x7), \
+          [ta0] "+v"(ta0), [tb0] "=&v"(tb0), [ea] "+v"(e_addr), [toff] "+v"(tap_off), [n] "+s"(n_steps) \
+        : [q] "s"(q) : "memory", "scc"
+        if constexpr (XTH == 1) asm volatile(SLIM_DOT_ASM_TILED_1 SLIM_DOT_OPERANDS);
+        else asm volatile(SLIM_DOT_ASM_TILED_2 SLIM_DOT_OPERANDS);
+#undef SLIM_DOT_OPERANDS
+    } else {
+        double ta1, tb1;
+#define SLIM_DOT_OPERANDS \
+        : [b0] "+v"(B[0]), [b1] "+v"(B[1]), [b2] "+v"(B[2]), [b3] "+v"(B[3]), [b4] "+v"(B[4]), \
+          [x0] "=&v"(x0), [x1] "=&v"(x1), [x2] "=&v"(x2), [x3] "=&v"(x3), [x4] "=&v"(x4), [x5] "=&v"(x5), [x6] "=&v"(x6), [x7] "=&v"(x7), \
+          [ta0] "+v"(ta0), [ta1] "=&v"(ta1), [tb0] "=&v"(tb0), [tb1] "=&v"(tb1), [ea] "+v"(e_addr), [toff] "+v"(tap_off), [n] "+s"(n_steps) \
+        : [q] "s"(q) : "memory", "scc"
+        if constexpr (XTH == 3) asm volatile(SLIM_DOT_ASM_TILED_3 SLIM_DOT_OPERANDS);
+        else if constexpr (XTH == 4) asm volatile(SLIM_DOT_ASM_TILED_4 SLIM_DOT_OPERANDS);
+        else asm volatile(SLIM_DOT_ASM_TILED_5 SLIM_DOT_OPERANDS);
+#undef SLIM_DOT_OPERANDS
+    }
+}
+// dot_windows_rt<true>: window r reads its taps t0 - r * xth + u (lanes 0..7 of a pair) through a base pointer of its own;
+// two pairs take turns.  tap_off is the lane's offset for window 0.
+__device__ __forceinline__ void slim_dot_windows_rt(unsigned e_addr, const double* q, unsigned tap_off, int xth, int n_steps, double (&B)[kR]) {
+    static_assert(kR == 5 && kU == 8, "the asm text is written for these");
+    double x0, x1, x2, x3, x4, x5, x6, x7, ta0, tb0;
+    asm volatile(SLIM_DOT_ASM_RT
+                 : [b0] "+v"(B[0]), [b1] "+v"(B[1]), [b2] "+v"(B[2]), [b3] "+v"(B[3]), [b4] "+v"(B[4]),
+                   [x0] "=&v"(x0), [x1] "=&v"(x1), [x2] "=&v"(x2), [x3] "=&v"(x3), [x4] "=&v"(x4), [x5] "=&v"(x5), [x6] "=&v"(x6), [x7] "=&v"(x7),
+                   [ta0] "=&v"(ta0), [tb0] "=&v"(tb0), [ea] "+v"(e_addr), [toff] "+v"(tap_off), [n] "+s"(n_steps)
+                 : [q0] "s"(q), [q1] "s"(q - xth), [q2] "s"(q - 2 * xth), [q3] "s"(q - 3 * xth), [q4] "s"(q - 4 * xth) : "memory", "scc");
+}
+// One window per lane (re-listed and untiled rows): one accumulator, the taps in order.
+__device__ __forceinline__ void slim_dot_one(unsigned e_addr, const double* q, unsigned tap_off, int n_steps, double ta0, double& B0) {
+    static_assert(kU == 8, "the asm text is written for this");
+    double x0, x1, x2, x3, x4, x5, x6, x7, tb0;
+    asm volatile(SLIM_DOT_ASM_ONE
+                 : [b0] "+v"(B0), [x0] "=&v"(x0), [x1] "=&v"(x1), [x2] "=&v"(x2), [x3] "=&v"(x3), [x4] "=&v"(x4), [x5] "=&v"(x5), [x6] "=&v"(x6), [x7] "=&v"(x7),
+                   [ta0] "+v"(ta0), [tb0] "=&v"(tb0), [ea] "+v"(e_addr), [toff] "+v"(tap_off), [n] "+s"(n_steps)
+                 : [q] "s"(q) : "memory", "scc");
+}
+
 // Fold `t` at (period, epoch) and produce the STABLE ascending order of the phases
 // (numpy.argsort(kind="mergesort"), core.py:119-120 / stats.py:178-179): perm[k] = original index
 // of the k-th smallest phase.  Bucket sort: histogram of floor(phase*nb) with LDS atomics, scan,

@@ -530,7 +530,8 @@ tls_slim_kernel(const SearchArgs) {
     }
     const const_width_ptr widths_c = (const_width_ptr)ap->widths;
     const const_rows_ptr rows_c = (const_rows_ptr)ap->rows;
-    const const_f64_ptr g_all = (const_f64_ptr)ap->g;
+    const double* const g_all = ap->g;   // (the taps are read by vector loads: slim_dot_windows)
+    const unsigned X_addr = (unsigned)(uintptr_t)(lds_f64_ptr)X;
     const double dmin = ap->depth_min;
 
     bool retry_exact = false;
@@ -985,45 +986,46 @@ tls_slim_kernel(const SearchArgs) {
                 const bool relisted = in_row >= chunk_batches;
                 const unsigned int slot = (relisted ? in_row - chunk_batches : in_row) * kWave + lane;
                 const bool have = slot < (unsigned int)(relisted ? n_singles : n_live);
+                // The lane's template tap of step 0 (slim_dot_windows: lane l of a pair holds tap base + (l & 15)), requested HERE,
+                // beside the batch's unit: the two round trips overlap.
+                const int reach = (tiled && !relisted) ? (kR - 1) * xth : 0;
+                int lane16 = lane;
+                asm volatile("" : "+v"(lane16));   // (formed per batch: hoisted, lane & 15 holds a register through the whole period)
+                const int tap = q_offset - (xth <= kMaxTiledStride ? reach : 0) + (lane16 & 15);
+                const double ta0 = g_all[tap];
                 const int unit = have ? (int)chunk_list[list_base + (relisted ? n_live : 0) + slot] : 0;
-                const const_f64_ptr g = g_all + q_offset;
                 const int Lx = L + 1;   // difference taps: one more than the row
                 const unsigned int evals_before = n_eval;
-                if (COUNTING && ap->counters) {
-                    const int reach = (tiled && !relisted) ? (kR - 1) * xth : 0;
-                    n_issued += (unsigned long long)((Lx + reach + kU - 1) / kU * kU) * (reach ? kR : 1);
-                }
-                if (tiled && !relisted) {
+                if (COUNTING && ap->counters) n_issued += (unsigned long long)((Lx + reach + kU - 1) / kU * kU) * (reach ? kR : 1);
+                const int steps = (Lx + reach + kU - 1) / kU;
+                const unsigned tap_off = 8u * (unsigned)tap;
+                // The FMAs read their taps through DPP row broadcasts, and a DPP read of a disabled lane drops the write: EXEC
+                // is all ones here -- every lane of the wave runs the loops, a lane without a unit on unit 0, and every branch
+                // down to them is wave-uniform.
+                TLS_CHECK(*ap, __builtin_amdgcn_read_exec() == ~0ull, kChkDotWindow);
+                if (reach) {
                     const int b = unit * kR * xth;
                     TLS_CHECK(*ap, !have || (b >= 0 && b + (Lx + (kR - 1) * xth + kU - 1) / kU * kU <= M + 1 + region_pad), kChkDotWindow);
-                    const double* e = X + b;
+                    const unsigned e_addr = X_addr + 8u * (unsigned)b;
                     double Bv[kR], Av[kR];
 #pragma unroll
                     for (int r = 0; r < kR; ++r) { Bv[r] = 0.0; Av[r] = sum_q2; }
                     switch (xth) {
-                        case 1: dot_windows<true, 1>(e, g, Lx, Bv); break;
-                        case 2: dot_windows<true, 2>(e, g, Lx, Bv); break;
-                        case 3: dot_windows<true, 3>(e, g, Lx, Bv); break;
-                        case 4: dot_windows<true, 4>(e, g, Lx, Bv); break;
-                        case 5: dot_windows<true, 5>(e, g, Lx, Bv); break;
-                        default: dot_windows_rt<true>(e, g, Lx, xth, Bv); break;
+                        case 1: slim_dot_windows<1>(e_addr, g_all, tap_off, steps, ta0, Bv); break;
+                        case 2: slim_dot_windows<2>(e_addr, g_all, tap_off, steps, ta0, Bv); break;
+                        case 3: slim_dot_windows<3>(e_addr, g_all, tap_off, steps, ta0, Bv); break;
+                        case 4: slim_dot_windows<4>(e_addr, g_all, tap_off, steps, ta0, Bv); break;
+                        case 5: slim_dot_windows<5>(e_addr, g_all, tap_off, steps, ta0, Bv); break;
+                        default: slim_dot_windows_rt(e_addr, g_all, tap_off, xth, steps, Bv); break;
                     }
                     if (have)
                         consider_cells<UNIFORM_W, false, kR, COUNTING>(lead, c_base, b, xth, d, inv_d, dd, rule, overshoot, Av, Bv, k, n_eval, undecided, widths_c, X);
                 } else {
                     const int i = unit * xth;
                     TLS_CHECK(*ap, !have || (i >= 0 && i + (Lx + kU - 1) / kU * kU <= M + 1 + region_pad), kChkDotWindow);
-                    const double* e = X + i;
                     double B0 = 0.0;
-                    for (int t0 = 0; t0 < Lx; t0 += kU) {
-                        const const_f64_ptr gs = g + t0;
-                        double taps[kU], x[kU];
-#pragma unroll
-                        for (int u = 0; u < kU; ++u) taps[u] = gs[u];
-                        load_taps<true>(e + t0, x);
-#pragma unroll
-                        for (int u = 0; u < kU; ++u) B0 = fma(taps[u], x[u], B0);   // one accumulator, taps in order: the tiled form's rounding
-                    }
+                    // one accumulator, taps in order: the tiled form's rounding
+                    slim_dot_one(X_addr + 8u * (unsigned)i, g_all, tap_off, steps, ta0, B0);
                     if (have) consider<UNIFORM_W, false>(lead, c_base[i], c_base[i + d], i, inv_d, dd, rule, overshoot, sum_q2, B0, k, n_eval, undecided, widths_c, X);
                 }
                 if constexpr (COUNTING) n_steps += (unsigned long long)(n_eval - evals_before) * (unsigned long long)L;
