@@ -1030,6 +1030,56 @@ int tls_sine_test(tls_ctx *ctx, const double *t, const double *y, const double *
                   const double *harmonics, int64_t n_harmonics, double mask, tls_sine_record *out,
                   tls_sine_harmonic *out_harmonics, double *out_sums);
 
+/* Iterative sinusoid pre-whitening: the variability of a star that is FASTER than a transit -- pulsations, a contact binary next
+ * door, rapid rotation -- measured by the periodogram above and removed term by term, where no median or biweight window can
+ * follow it without flattening the transit too (the harmonic remover of the Kepler TPS, Period04).  For a curve y [n] (weights
+ * from dy [n], or uniform) over t [n] and the grid frequencies [n_freq]; r starts as y and trend as 0.0.  Iteration
+ * j = 0 .. n_terms - 1, while the curve runs:
+ *   spectrum: the periodogram of r on the grid as tls_lomb_scargle forms it (the prologue in index order, the dense product,
+ *       the epilogue).  C, S, C2, S2 depend on the weights alone and are formed once a call.  ybar_0 = the mean of the first
+ *       prologue.
+ *   pick: k = the first index of the largest finite power.  None (a constant row): status 2, the curve stops.
+ *       power[k] < min_power: status 1, the curve stops.  The row of a curve that stopped is final.
+ *   refine: if 0 < k < n_freq - 1, both neighbours are finite and den = p[k-1] - 2.0 * p[k] + p[k+1] < 0:
+ *       half = 0.5 * (f[k+1] - f[k-1]);  f* = f[k] + 0.5 * half * (p[k-1] - p[k+1]) / den;      otherwise f* = f[k]
+ *   fit and subtract, for h = 1 .. n_harmonics in turn, each on the row the harmonic before left:  fh = h * f*; the statement
+ *       of tls_sine_test without a mask at the frequencies fh and 2.0 * fh (ordered 256-lane sums: W, ybar, YY, then the six
+ *       sums of the rounded products, then the epilogue with ca and sa).  A NaN epilogue: the harmonic is skipped, term status
+ *       1.  Otherwise, for every i:  u = cos phi_i - C;  v = sin phi_i - S;  q = ca * u + sa * v;  r_i = r_i - q;
+ *       trend_i = trend_i + q
+ * At the end trend_i = ybar_0 + trend_i and flat_i = y_i / trend_i: the variability multiplies the transit, and the other
+ * detrenders return flat = y / trend too.  Every step is one IEEE double operation, contraction off.  The means and variances
+ * equal tests/prewhiten_spec.py bit for bit, the six sums lie within the periodogram's bound, the pick equals the statement's
+ * wherever its highest power stands clear of the others, f*, ca, sa, power and amplitude equal the statement's steps on the
+ * device's own powers and sums bit for bit, and a subtraction differs from the statement's by the few ulp of the device's
+ * cos and sin.  A term fitted near a transit's period or one of its harmonics removes part of the transit: min_power and the
+ * frequency grid are the caller's protection (DESIGN.md "Pre-whitening").  All fields are doubles.  16 doubles. */
+#define TLS_PREWHITEN_MAX_TERMS 32
+#define TLS_PREWHITEN_LDS_POINTS 6144   /* rows of at most this many points are fitted in the LDS, longer ones in device memory */
+typedef struct tls_prewhiten_term {
+    double status;                 /* 0 fitted and subtracted; 1 the epilogue was NaN, nothing subtracted; 2 not reached */
+    double index, frequency_grid;  /* k and f[k] of the pick */
+    double power_left, power_peak, power_right;   /* p[k-1], p[k], p[k+1]; NaN where the grid ends */
+    double frequency;              /* h * f* */
+    double mean, variance;         /* ybar and YY of the row fitted (ordered 256-lane sums) */
+    double ca, sa, C, S;
+    double power, amplitude, phase;   /* at `frequency`, of the row fitted */
+} tls_prewhiten_term;
+/* y (dy, or NULL: uniform weights) [n_curves][n] over t [n]; n_terms in [1, TLS_PREWHITEN_MAX_TERMS], n_harmonics in
+ * [1, TLS_SINE_MAX_HARMONICS], min_power in [0, 1].  out_flat [n_curves][n]; out_trend the same or NULL; out_terms
+ * [n_curves][n_terms][n_harmonics]; out_n_iterations [n_curves]: the iterations that fitted; out_status [n_curves]: 0 every
+ * iteration ran, 1 stopped below min_power, 2 stopped without a finite power.  For tests: out_steps
+ * [n_terms * n_harmonics + 1][n_curves][n], the row entering every (iteration, harmonic) and, last, the final row (a step
+ * that was not reached holds the final row), or NULL; out_sums [n_curves][n_terms][n_harmonics][6] (YC, YS, C, S, C2, S2) or
+ * NULL.  The rows stay on the device for the whole call; the host reads one count an iteration and stops when no curve
+ * runs.  Curves are processed in slabs, so device memory stays bounded.  Needs no plan.  n_curves == 0 is a no-op.
+ * TLS_E_ARG, before any device work, as tls_lomb_scargle, and for n_terms, n_harmonics or min_power out of range.  y and dy
+ * are taken as they are (finite, dy > 0). */
+int tls_prewhiten(tls_ctx *ctx, const double *t, const double *y, const double *dy, int64_t n, int64_t n_curves,
+                  const double *frequencies, int64_t n_freq, int64_t n_terms, int64_t n_harmonics, double min_power,
+                  double *out_flat, double *out_trend, tls_prewhiten_term *out_terms, int64_t *out_n_iterations,
+                  double *out_status, double *out_steps, double *out_sums);
+
 /* ---- survey mode: the ephemeris match across the candidates of a batch ----------------------------------------------- */
 /* The test that looks across the stars (Coughlin et al. 2014): the stars of one field, camera and sector contaminate one
  * another and share instrumental periods.  A faint star next to an eclipsing binary shows the binary's period and epoch at a

@@ -84,6 +84,9 @@ GLS_FREQ_TILE = 64
 GLS_CHUNK = 32
 SINE_MAX_HARMONICS = 8
 SINE_LANES = 256
+# include/tls_amd.h TLS_PREWHITEN_MAX_TERMS, TLS_PREWHITEN_LDS_POINTS (a row of at most this many points is fitted in the LDS)
+PREWHITEN_MAX_TERMS = 32
+PREWHITEN_LDS_POINTS = 6144
 # include/tls_amd.h TLS_MATCH_*: the most candidates and the largest max_ratio of tls_ephemeris_match; tls_match.hip.h
 # kMatchTile (the candidates of a workgroup, and of a staged tile of the other side), kMatchTargetGroups and kMatchMaxChunks
 # (match_chunks below)
@@ -104,7 +107,7 @@ SYMBOLS = (
     "tls_inject_transits", "tls_null_rows", "tls_debug_null_words", "tls_medfilt_detrend",
     "tls_biweight_detrend", "tls_sysrem", "tls_find_peaks", "tls_power_batch_peaks", "tls_power_batch_peak_fits", "tls_debug_peak_fits",
     "tls_phase_scan", "tls_power_batch_phase_scan", "tls_debug_peak_phase_scans", "tls_single_transits",
-    "tls_transit_times", "tls_shape_fit", "tls_nudft", "tls_lomb_scargle", "tls_sine_test",
+    "tls_transit_times", "tls_shape_fit", "tls_nudft", "tls_lomb_scargle", "tls_sine_test", "tls_prewhiten",
     "tls_ephemeris_match", "tls_folded_views", "tls_event_vetting", "tls_centroid_test",
     "tls_comm_unique_id", "tls_comm_init", "tls_comm_destroy", "tls_comm_info", "tls_comm_allgather_results", "tls_comm_allgather_device", "tls_comm_fetch_gathered",
     "tls_comm_stage_results", "tls_comm_allgather_staged", "tls_comm_fetch_staged",
@@ -860,6 +863,37 @@ def lomb_scargle_arguments(t, y, dy, frequencies, peaks=None, separation=0.02):
     return dict(t=t, frequencies=f, y=y, dy=dy, k=k, separation=float(separation))
 
 
+# tls_prewhiten_term of include/tls_amd.h, in order: all doubles
+PREWHITEN_FIELDS = ("status", "index", "frequency_grid", "power_left", "power_peak", "power_right", "frequency", "mean",
+                    "variance", "ca", "sa", "C", "S", "power", "amplitude", "phase")
+
+
+class PrewhitenTerm(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_double) for k in PREWHITEN_FIELDS]
+
+
+PREWHITEN_DTYPE = numpy.dtype([(k, "f8") for k in PREWHITEN_FIELDS])
+
+
+def prewhiten_arguments(t, y, dy, frequencies, n_terms=3, harmonics=1, min_power=0.0):
+    """What tls_prewhiten takes, checked as it checks them: a dict with t, frequencies (gls_axes, n >= 3), y, dy (gls_rows),
+    n_terms (an integer in [1, PREWHITEN_MAX_TERMS]), harmonics (an integer in [1, SINE_MAX_HARMONICS]) and min_power (in
+    [0, 1]).  ValueError otherwise.  GPU-free."""
+    t, f = gls_axes(t, frequencies, 3)
+    y, dy = gls_rows(t, y, dy, "prewhiten")
+
+    def integer(name, value, high):
+        if isinstance(value, (bool, numpy.bool_)) or not isinstance(value, numbers.Integral) or not 1 <= int(value) <= high:
+            raise ValueError("prewhiten: %s must be an integer in [1, %d], got %r" % (name, high, value))
+        return int(value)
+
+    k = integer("n_terms", n_terms, PREWHITEN_MAX_TERMS)
+    h = integer("harmonics", harmonics, SINE_MAX_HARMONICS)
+    if isinstance(min_power, (bool, numpy.bool_)) or not isinstance(min_power, numbers.Real) or not (0.0 <= float(min_power) <= 1.0):
+        raise ValueError("prewhiten: min_power must lie in [0, 1], got %r" % (min_power,))
+    return dict(t=t, frequencies=f, y=y, dy=dy, n_terms=k, harmonics=h, min_power=float(min_power))
+
+
 def sine_test_arguments(t, y, dy, period, T0, duration, curve, mask, harmonics):
     """What tls_sine_test takes, checked as it checks them: a dict with t [n] (n in [1, GLS_MAX_POINTS], finite and
     ascending), y, dy (gls_rows), period [n_fits] (any value: status 1), T0 and duration (both None, or [n_fits]), curve
@@ -1113,6 +1147,9 @@ def load():
     lib.tls_sine_test.restype = ci
     lib.tls_sine_test.argtypes = [vp, _c_double_p, _c_double_p, _c_double_p, i64, i64, _c_double_p, _c_double_p, _c_double_p,
                                   _c_int64_p, i64, _c_double_p, i64, dbl, ctypes.c_void_p, ctypes.c_void_p, _c_double_p]
+    lib.tls_prewhiten.restype = ci
+    lib.tls_prewhiten.argtypes = [vp, _c_double_p, _c_double_p, _c_double_p, i64, i64, _c_double_p, i64, i64, i64, dbl,
+                                  _c_double_p, _c_double_p, ctypes.c_void_p, _c_int64_p, _c_double_p, _c_double_p, _c_double_p]
     lib.tls_ephemeris_match.restype = ci
     lib.tls_ephemeris_match.argtypes = [vp, _c_int64_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, i64, dbl, dbl, dbl,
                                         i64, ctypes.c_void_p]
@@ -2055,6 +2092,34 @@ class Context(object):
             n_fits, _dp(a["harmonics"]), nH, a["mask"], out.ctypes.data_as(ctypes.c_void_p),
             out_h.ctypes.data_as(ctypes.c_void_p), None if sums is None else _dp(sums)))
         return (out, out_h, sums) if debug else (out, out_h)
+
+    def prewhiten(self, t, y, frequencies, n_terms=3, harmonics=1, min_power=0.0, dy=None, return_trend=False,
+                  return_terms=False, debug=False):
+        """Iterative sinusoid pre-whitening (tls_prewhiten; the statement: include/tls_amd.h, tests/prewhiten_spec.py) of
+        y [n_curves, n] (or one row; dy: per-point errors, None: uniform weights) over t [n] on the grid `frequencies` [F]:
+        flat [n_curves, n] (one row: [n]); then trend with return_trend=True; then a dict with terms (PREWHITEN_DTYPE
+        [n_curves, n_terms, harmonics]), n_iterations and status [n_curves] with return_terms=True; with debug the dict also
+        holds steps [n_terms * harmonics + 1, n_curves, n] (the row entering every (iteration, harmonic), then the final
+        row) and sums [n_curves, n_terms, harmonics, 6] (GLS_SUMS).  ValueError for what prewhiten_arguments refuses."""
+        a = prewhiten_arguments(t, y, dy, frequencies, n_terms, harmonics, min_power)
+        n_c, n = a["y"].shape
+        K, H = a["n_terms"], a["harmonics"]
+        flat = numpy.empty_like(a["y"])
+        trend = numpy.empty_like(a["y"]) if return_trend else None
+        terms = numpy.zeros((n_c, K, H), dtype=PREWHITEN_DTYPE)
+        info = dict(terms=terms, n_iterations=numpy.zeros(n_c, dtype=numpy.int64), status=numpy.zeros(n_c))
+        if debug:
+            info.update(steps=numpy.zeros((K * H + 1, n_c, n)), sums=numpy.zeros((n_c, K, H, 6)))
+        assert PREWHITEN_DTYPE.itemsize == ctypes.sizeof(PrewhitenTerm)
+        self._check(self._lib.tls_prewhiten(
+            self._h, _dp(a["t"]), _dp(a["y"]), None if a["dy"] is None else _dp(a["dy"]), n, n_c, _dp(a["frequencies"]),
+            len(a["frequencies"]), K, H, a["min_power"], _dp(flat), None if trend is None else _dp(trend),
+            terms.ctypes.data_as(ctypes.c_void_p), _ip(info["n_iterations"]), _dp(info["status"]),
+            _dp(info["steps"]) if debug else None, _dp(info["sums"]) if debug else None))
+        if numpy.ndim(y) == 1:   # (one row comes back as [n]; the records keep their leading axis)
+            flat, trend = flat[0], None if trend is None else trend[0]
+        out = (flat,) + ((trend,) if return_trend else ()) + ((info,) if return_terms or debug else ())
+        return out[0] if len(out) == 1 else out
 
     def ephemeris_match(self, star, period, T0, duration, strength, span, drift_tolerance=0.5, epoch_tolerance=0.5,
                         max_ratio=3):

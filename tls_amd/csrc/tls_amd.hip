@@ -4119,6 +4119,149 @@ int tls_sine_test(tls_ctx* ctx, const double* t, const double* y, const double* 
         });
 }
 
+// ---- pre-whitening (tls_prewhiten.hip.h, DESIGN.md "Pre-whitening"): the periodogram's kernels and the step kernel, iteration
+// by iteration on rows that stay on the device; the host reads one count an iteration
+static_assert(sizeof(tls_prewhiten_term) == tlsdev::kPrewhitenWords * 8, "tls_prewhiten_term is the kernel's record");
+static_assert(TLS_PREWHITEN_MAX_TERMS == tlsdev::kPrewhitenMaxTerms && TLS_PREWHITEN_LDS_POINTS == tlsdev::kPrewhitenLdsPoints,
+              "the header's limits");
+
+int tls_prewhiten(tls_ctx* ctx, const double* t, const double* y, const double* dy, int64_t n, int64_t n_curves,
+                  const double* frequencies, int64_t n_freq, int64_t n_terms, int64_t n_harmonics, double min_power,
+                  double* out_flat, double* out_trend, tls_prewhiten_term* out_terms, int64_t* out_n_iterations,
+                  double* out_status, double* out_steps, double* out_sums) {
+    if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
+    if (n_curves < 0) return fail(ctx, TLS_E_ARG, "prewhiten: n_curves < 0");
+    int rc = check_gls_axes(ctx, t, n, 3, frequencies, n_freq);
+    if (rc) return rc;
+    if (n_terms < 1 || n_terms > TLS_PREWHITEN_MAX_TERMS) return fail(ctx, TLS_E_ARG, "prewhiten: n_terms out of range [1, 32]");
+    if (n_harmonics < 1 || n_harmonics > TLS_SINE_MAX_HARMONICS) return fail(ctx, TLS_E_ARG, "prewhiten: n_harmonics out of range [1, 8]");
+    if (!(min_power >= 0.0 && min_power <= 1.0)) return fail(ctx, TLS_E_ARG, "prewhiten: min_power must lie in [0, 1]");
+    if (n_curves == 0) return TLS_OK;
+    if (!y || !out_flat || !out_terms || !out_n_iterations || !out_status) return fail(ctx, TLS_E_ARG, "null argument");
+    TLS_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t nn = (size_t)n, nf = (size_t)n_freq, K = (size_t)n_terms, KH = K * (size_t)n_harmonics;
+    const size_t words = tlsdev::kPrewhitenWords;
+    // rows of a slab: the rows, sums and spectra of a slab stay below 1 GB, and at most 4096 curves
+    const size_t per_row = 8 * ((out_steps ? 7 + KH : 6) * nn + 9 * nf + KH * (words + 6) + 8);
+    const size_t sl = std::max<size_t>(1, std::min<size_t>({(size_t)n_curves, 4096, ((size_t)1 << 30) / per_row}));
+    const size_t wl = dy ? sl : 1;
+    // (YC, YS) | (C, S) | (C2, S2) pairs; power | amplitude | phase; y | r | dy | a (flat at the end) | w | trend; mean_0 | mean |
+    // variance | status; terms | sums; t | f | 2 f; n_iterations | counts | active; steps
+    const size_t ints = (sl + 1) / 2;
+    TLS_HIP(ctx, ctx->d_gls.reserve(2 * sl * nf + 4 * wl * nf + 3 * sl * nf + (dy ? 5 : 4) * sl * nn + wl * nn + 4 * sl
+                                    + sl * KH * (words + 6) + nn + 2 * nf + sl + K + ints + (out_steps ? (KH + 1) * sl * nn : 0)));
+    double2* d_yc = reinterpret_cast<double2*>(ctx->d_gls.ptr);
+    double2* d_cs = d_yc + sl * nf;
+    double2* d_cs2 = d_cs + wl * nf;
+    double* d_power = reinterpret_cast<double*>(d_cs2 + wl * nf);
+    double* d_amplitude = d_power + sl * nf;
+    double* d_phase = d_amplitude + sl * nf;
+    double* d_y = d_phase + sl * nf;
+    double* d_r = d_y + sl * nn;
+    double* d_dy = dy ? d_r + sl * nn : nullptr;
+    double* d_a = d_r + (dy ? 2 : 1) * sl * nn;
+    double* d_w = d_a + sl * nn;
+    double* d_trend = d_w + wl * nn;
+    double* d_mean0 = d_trend + sl * nn;
+    double* d_mean = d_mean0 + sl;
+    double* d_var = d_mean + sl;
+    double* d_status = d_var + sl;
+    double* d_terms = d_status + sl;
+    double* d_sums = d_terms + sl * KH * words;
+    double* d_t = d_sums + sl * KH * 6;
+    double* d_f = d_t + nn;
+    double* d_f2 = d_f + nf;
+    long long* d_iterations = reinterpret_cast<long long*>(d_f2 + nf);
+    unsigned long long* d_counts = reinterpret_cast<unsigned long long*>(d_iterations + sl);
+    int* d_active = reinterpret_cast<int*>(d_counts + K);
+    double* d_steps = out_steps ? reinterpret_cast<double*>(d_counts + K) + ints : nullptr;
+    const bool lds = n <= tlsdev::kPrewhitenLdsPoints;
+    const size_t lds_bytes = tlsdev::prewhiten_lds_bytes((int)n, lds);
+    auto step_kernel = lds ? tlsdev::tls_prewhiten_step_kernel<true> : tlsdev::tls_prewhiten_step_kernel<false>;
+    TLS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(step_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+    std::vector<double> twice(nf);
+    for (size_t i = 0; i < nf; ++i) twice[i] = 2.0 * frequencies[i];
+    // a term that was not reached: status 2, NaN elsewhere
+    std::vector<double> blank(sl * KH * (words + 6), (double)NAN);
+    for (size_t q = 0; q < sl * KH; ++q) blank[q * words] = 2.0;
+    std::vector<int> ones(sl, 1);
+    TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_f, frequencies, nf * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_f2, twice.data(), nf * 8, hipMemcpyHostToDevice, ctx->stream));
+    auto launched = [&](const char* what) -> int {
+        const hipError_t e = hipGetLastError();
+        if (e == hipSuccess) return TLS_OK;
+        (void)hipStreamSynchronize(ctx->stream);
+        return fail(ctx, TLS_E_HIP, std::string("prewhiten ") + what + " launch: " + hipGetErrorString(e));
+    };
+    for (int64_t k0 = 0; k0 < n_curves; k0 += (int64_t)sl) {
+        const int64_t R = std::min<int64_t>((int64_t)sl, n_curves - k0), Rw = dy ? R : 1;
+        const size_t at = (size_t)k0 * nn, rows = (size_t)R, bytes = rows * nn * 8;
+        TLS_HIP(ctx, hipMemcpyAsync(d_y, y + at, bytes, hipMemcpyHostToDevice, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(d_r, d_y, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+        if (dy) TLS_HIP(ctx, hipMemcpyAsync(d_dy, dy + at, bytes, hipMemcpyHostToDevice, ctx->stream));
+        TLS_HIP(ctx, hipMemsetAsync(d_trend, 0, bytes, ctx->stream));
+        TLS_HIP(ctx, hipMemsetAsync(d_status, 0, rows * 8, ctx->stream));
+        TLS_HIP(ctx, hipMemsetAsync(d_iterations, 0, (sl + K) * 8, ctx->stream));            // (and the counts behind them)
+        TLS_HIP(ctx, hipMemcpyAsync(d_active, ones.data(), rows * 4, hipMemcpyHostToDevice, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(d_terms, blank.data(), rows * KH * words * 8, hipMemcpyHostToDevice, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(d_sums, blank.data() + sl * KH * words, rows * KH * 48, hipMemcpyHostToDevice, ctx->stream));
+        int64_t ran = 0;
+        for (int64_t j = 0; j < n_terms; ++j) {
+            tlsdev::GlsPrologueArgs p;
+            p.y = d_r; p.dy = d_dy; p.rows = d_a; p.weights = d_w; p.mean = j == 0 ? d_mean0 : d_mean; p.variance = d_var; p.n = (int)n;
+            hipLaunchKernelGGL(tlsdev::tls_gls_prologue_kernel, dim3((unsigned)R), dim3(tlsdev::kGlsThreads), 0, ctx->stream, p);
+            if ((rc = launched("prologue"))) return rc;
+            if ((rc = enqueue_nudft(ctx, d_a, R, n, n, d_t, d_f, n_freq, d_yc))) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+            if (j == 0 && (dy || k0 == 0)) {         // (the sums of the weights: once a call, or once a slab with dy)
+                if ((rc = enqueue_nudft(ctx, d_w, Rw, n, n, d_t, d_f, n_freq, d_cs))
+                    || (rc = enqueue_nudft(ctx, d_w, Rw, n, n, d_t, d_f2, n_freq, d_cs2))) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+            }
+            tlsdev::GlsEpilogueArgs g;
+            g.yc = d_yc; g.cs = d_cs; g.cs2 = d_cs2; g.variance = d_var; g.power = d_power; g.amplitude = d_amplitude; g.phase = d_phase;
+            g.count = (long long)R * (long long)n_freq; g.F = (int)n_freq; g.shared_weights = dy ? 0 : 1;
+            const unsigned blocks = (unsigned)std::min<long long>((g.count + tlsdev::kGlsThreads - 1) / tlsdev::kGlsThreads, 16384);
+            hipLaunchKernelGGL(tlsdev::tls_gls_epilogue_kernel, dim3(blocks), dim3(tlsdev::kGlsThreads), 0, ctx->stream, g);
+            if ((rc = launched("epilogue"))) return rc;
+            tlsdev::PrewhitenArgs a;
+            a.t = d_t; a.f = d_f; a.dy = d_dy; a.power = d_power; a.r = d_r; a.trend = d_trend; a.terms = d_terms; a.sums = d_sums;
+            a.steps = d_steps; a.active = d_active; a.n_iterations = d_iterations; a.status = d_status; a.counts = d_counts;
+            a.min_power = min_power; a.n = (int)n; a.F = (int)n_freq; a.R = (int)R; a.K = (int)n_terms; a.H = (int)n_harmonics; a.j = (int)j;
+            hipLaunchKernelGGL(step_kernel, dim3((unsigned)R), dim3(tlsdev::kPrewhitenThreads), lds_bytes, ctx->stream, a);
+            if ((rc = launched("step"))) return rc;
+            ctx->last_kernel = "tls_prewhiten";
+            ran = j + 1;
+            if (j + 1 < n_terms) {
+                unsigned long long going = 0;
+                TLS_HIP(ctx, hipMemcpyAsync(&going, d_counts + j, 8, hipMemcpyDeviceToHost, ctx->stream));
+                TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+                if (going == 0) break;
+            }
+        }
+        // (the steps no iteration reached, and the one behind the last, hold the final rows)
+        if (d_steps)
+            for (size_t s = (size_t)ran * (size_t)n_harmonics; s <= KH; ++s)
+                TLS_HIP(ctx, hipMemcpyAsync(d_steps + s * rows * nn, d_r, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+        tlsdev::PrewhitenFinishArgs fin;
+        fin.y = d_y; fin.mean0 = d_mean0; fin.trend = d_trend; fin.flat = d_a; fin.count = (long long)R * (long long)n; fin.n = (int)n;
+        const unsigned fblocks = (unsigned)std::min<long long>((fin.count + tlsdev::kPrewhitenThreads - 1) / tlsdev::kPrewhitenThreads, 16384);
+        hipLaunchKernelGGL(tlsdev::tls_prewhiten_finish_kernel, dim3(fblocks), dim3(tlsdev::kPrewhitenThreads), 0, ctx->stream, fin);
+        if ((rc = launched("finish"))) return rc;
+        TLS_HIP(ctx, hipMemcpyAsync(out_flat + at, d_a, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        if (out_trend) TLS_HIP(ctx, hipMemcpyAsync(out_trend + at, d_trend, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(out_terms + (size_t)k0 * KH, d_terms, rows * KH * words * 8, hipMemcpyDeviceToHost, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(out_n_iterations + k0, d_iterations, rows * 8, hipMemcpyDeviceToHost, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(out_status + k0, d_status, rows * 8, hipMemcpyDeviceToHost, ctx->stream));
+        if (out_sums) TLS_HIP(ctx, hipMemcpyAsync(out_sums + (size_t)k0 * KH * 6, d_sums, rows * KH * 48, hipMemcpyDeviceToHost, ctx->stream));
+        if (out_steps)
+            for (size_t s = 0; s <= KH; ++s)
+                TLS_HIP(ctx, hipMemcpyAsync(out_steps + s * (size_t)n_curves * nn + at, d_steps + s * rows * nn, bytes,
+                                            hipMemcpyDeviceToHost, ctx->stream));
+        TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));       // (the next slab overwrites the device buffers)
+    }
+    return TLS_OK;
+}
+
 // ---- the ephemeris match (tls_match.hip.h, DESIGN.md "Ephemeris match"): every candidate against every other, the g range in
 // chunks along gridDim.y, then the chunks' partial records combined
 static_assert(sizeof(tls_match_record) == tlsdev::kMatchWords * 8, "tls_match_record is the kernel's record");

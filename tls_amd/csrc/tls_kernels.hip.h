@@ -4443,6 +4443,8 @@ __global__ void __launch_bounds__(512) tls_transit_models(const ModelsArgs a) {
 #include "tls_views.hip.h"
 // survey-mode variability periodogram and sine test (tls_nudft, tls_lomb_scargle, tls_sine_test)
 #include "tls_gls.hip.h"
+// survey-mode iterative sinusoid pre-whitening (tls_prewhiten), on tls_gls.hip.h's periodogram
+#include "tls_prewhiten.hip.h"
 #include "tls_peak_fits.hip.h"
 #include "tls_phase_scan.hip.h"
 // survey-mode ephemeris match across the candidates of a batch (tls_ephemeris_match)

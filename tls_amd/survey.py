@@ -247,15 +247,139 @@ def sysrem_batch(flux_batch, n_components=1, dy_batch=None, max_iter=50, tol=1e-
     return ctx.sysrem(rows, k, dy=dy, max_iter=iters, tol=tol, return_trend=return_trend, return_components=return_components)
 
 
+# ---- detrending: iterative sinusoid pre-whitening on the device -------------------------------------------------------------
+class Prewhiten(collections.namedtuple("Prewhiten", ("n_terms", "harmonics", "min_power", "f_min", "f_max"))):
+    """detrend=Prewhiten(n_terms=3, harmonics=1, min_power=None, f_min=None, f_max=None) on the survey calls: the n_terms
+    strongest sinusoids of every row (each with `harmonics` harmonics) fitted and divided out (prewhiten_batch) on the part
+    [f_min, f_max] (cycles a day; None: no cut) of variability_frequencies(t).  An immutable value; its fields are checked
+    where it is used."""
+    __slots__ = ()
+
+    def __new__(cls, n_terms=3, harmonics=1, min_power=None, f_min=None, f_max=None):
+        return super(Prewhiten, cls).__new__(cls, n_terms, harmonics, min_power, f_min, f_max)
+
+
+def gls_power_threshold(n, n_freq, fap, oversampling=5):
+    """The periodogram power that white noise exceeds somewhere on the grid with probability fap (Zechmeister & Kuerster 2009,
+    eqs. 24-25, in the approximation fap = M Prob(p > P) for small values): 1 - (fap / M)^(2 / (n - 3)) with
+    M = n_freq / oversampling independent frequencies among the n_freq of a grid oversampled `oversampling` times.  Host
+    only; a min_power for prewhiten_batch.  ValueError unless n > 3 is an integer, n_freq >= 1, oversampling is finite and > 0
+    and 0 < fap <= M."""
+    if isinstance(n, bool) or not isinstance(n, numbers.Integral) or n <= 3:
+        raise ValueError("gls_power_threshold: n must be an integer > 3, got %r" % (n,))
+    if isinstance(n_freq, bool) or not isinstance(n_freq, numbers.Integral) or n_freq < 1:
+        raise ValueError("gls_power_threshold: n_freq must be an integer >= 1, got %r" % (n_freq,))
+    if isinstance(oversampling, bool) or not isinstance(oversampling, numbers.Real) or not (0.0 < float(oversampling) < numpy.inf):
+        raise ValueError("gls_power_threshold: oversampling must be finite and > 0, got %r" % (oversampling,))
+    m = float(n_freq) / float(oversampling)
+    if isinstance(fap, bool) or not isinstance(fap, numbers.Real) or not (0.0 < float(fap) <= m):
+        raise ValueError("gls_power_threshold: fap must lie in (0, n_freq / oversampling], got %r" % (fap,))
+    return 1.0 - (float(fap) / m) ** (2.0 / (int(n) - 3.0))
+
+
+PREWHITEN_FAP = 1e-3   # the false-alarm probability behind prewhiten_batch's default min_power
+
+
+def prewhiten_term_fields():
+    """The fields of a pre-whitening term, in order (tls_prewhiten_term of include/tls_amd.h): what
+    prewhiten_batch(..., return_terms=True) returns for every (curve, iteration, harmonic)."""
+    from ._lib import PREWHITEN_FIELDS
+    return PREWHITEN_FIELDS
+
+
+def _prewhiten_grid(t, f_min=None, f_max=None):
+    """variability_frequencies(t) cut to [f_min, f_max] (None: no cut).  ValueError for a bound that is not a finite number
+    > 0, and for a cut that leaves no frequency."""
+    grid = variability_frequencies(t)
+    for name, bound in (("f_min", f_min), ("f_max", f_max)):
+        if bound is not None and (isinstance(bound, bool) or not isinstance(bound, numbers.Real) or not (0.0 < float(bound) < numpy.inf)):
+            raise ValueError("prewhiten: %s must be None or finite and > 0, got %r" % (name, bound))
+    if f_min is not None:
+        grid = grid[grid >= float(f_min)]
+    if f_max is not None:
+        grid = grid[grid <= float(f_max)]
+    if not len(grid):
+        raise ValueError("prewhiten: no frequency of variability_frequencies(t) lies in [f_min, f_max] = [%r, %r]" % (f_min, f_max))
+    return grid
+
+
+def _prewhiten_step(t, step, n):
+    """(frequencies, n_terms, harmonics, min_power) of a Prewhiten step on rows of n points over t: the grid cut, and the
+    default min_power (gls_power_threshold at PREWHITEN_FAP) where the step names none."""
+    grid = _prewhiten_grid(t, step.f_min, step.f_max)
+    low = step.min_power
+    if low is None:
+        low = gls_power_threshold(n, len(grid), PREWHITEN_FAP) if n > 3 else 1.0
+    return grid, step.n_terms, step.harmonics, low
+
+
+def prewhiten_batch(t, flux_batch, n_terms=3, harmonics=1, min_power=None, frequencies=None, dy_batch=None, return_trend=False,
+                    return_terms=False, context=None, device=None, devices=None):
+    """flat = flux / trend for every row of flux_batch ([n] or [n_curves, n], at the shared ascending time stamps t), with
+    trend the row's mean plus its n_terms strongest sinusoids, found and fitted one after the other on the device
+    (tls_prewhiten): iterative pre-whitening, the harmonic remover of the Kepler TPS and of Period04.  It is the detrender
+    for variability FASTER than a transit -- delta Scuti and gamma Dor pulsations, a contact binary next door, rapid
+    rotation -- which no median or biweight window can follow without flattening the transit too.
+
+        r = flux; iteration j = 0 .. n_terms - 1, while the row runs:
+            the periodogram of lomb_scargle of r on `frequencies` (None: variability_frequencies(t))
+            k = the first index of the highest finite power; none (a constant row): status 2, stop;
+            power[k] < min_power: status 1, stop
+            f* = the vertex of the parabola through the powers at k - 1, k, k + 1 (f[k] itself at the ends of the grid, next
+            to a NaN, and where the three do not curve downwards)
+            for h = 1 .. harmonics: the weighted least-squares sinusoid with a floating mean at h f* (the sine test's sums
+            over 256 lanes) is fitted to r and subtracted from it:  r_i -= ca (cos phi_i - C) + sa (sin phi_i - S)
+        trend = ybar_0 + everything subtracted;  flat = flux / trend
+
+    The exact steps are in include/tls_amd.h and tests/prewhiten_spec.py; each is one IEEE double operation.  The rows stay on
+    the device for the whole call: an iteration is one dense product of the rows, the periodogram's epilogue and one step
+    kernel, and the host reads a single count per iteration to stop when no row runs any more.
+
+    min_power None: gls_power_threshold(n, F, fap=PREWHITEN_FAP = 1e-3), the power white noise reaches on the grid once in a
+    thousand curves, so that noise alone has nothing removed.  THE TRANSIT IS NOT PROTECTED: a box transit is itself periodic
+    (a 0.5 % transit of 3.3 d in 30 d of 3e-4 noise has periodogram power 0.07, well above that default), and once the
+    stellar terms are gone the next term lands on the transit's period or a harmonic of it and removes part of the depth.
+    Keep n_terms at the number of stellar signals, or keep the grid away from planetary periods with `frequencies` (or
+    Prewhiten's f_min); DESIGN.md "Pre-whitening" has the measured depth kept in each case.  dy_batch: per-point errors (None:
+    uniform weights).
+
+    ValueError, before any device work, for non-finite input, a t that is not ascending, frequencies that are not finite and
+    > 0, n < 3, n_terms outside [1, 32], harmonics outside [1, 8], min_power outside [0, 1] and shapes that disagree.
+    devices=[...] deals the rows out over several GPUs, as the other survey calls.  Returns flat[, trend][, info] in the shape
+    of flux_batch; info (return_terms=True) is a dict: terms (a record array [n_curves, n_terms, harmonics] with the fields of
+    prewhiten_term_fields(); status 0 fitted, 1 skipped, 2 not reached), n_iterations and status [n_curves]."""
+    from ._lib import prewhiten_arguments
+    if frequencies is None:
+        frequencies = variability_frequencies(t)
+    n = numpy.shape(flux_batch)[-1] if numpy.ndim(flux_batch) else 0
+    if min_power is None:
+        min_power = gls_power_threshold(int(n), len(frequencies), PREWHITEN_FAP) if n > 3 else 1.0
+    a = prewhiten_arguments(t, flux_batch, dy_batch, frequencies, n_terms, harmonics, min_power)
+
+    def call(ctx, lo, hi):
+        out = ctx.prewhiten(a["t"], a["y"][lo:hi], a["frequencies"], a["n_terms"], a["harmonics"], a["min_power"],
+                            dy=None if a["dy"] is None else a["dy"][lo:hi], return_trend=True, return_terms=True)
+        return dict(flat=out[0], trend=out[1], **out[2])
+
+    out = _run_batch(devices, device, context, len(a["y"]), call)
+    flat, trend = out["flat"], out["trend"]
+    info = dict(terms=out["terms"], n_iterations=out["n_iterations"], status=out["status"])
+    if numpy.ndim(flux_batch) == 1:
+        flat, trend = flat[0], trend[0]
+        info = {k: v[0] for k, v in info.items()}
+    res = (flat,) + ((trend,) if return_trend else ()) + ((info,) if return_terms else ())
+    return res[0] if len(res) == 1 else res
+
+
 def _detrend_steps(detrend):
-    """The steps of a detrend= argument, left to right: () for None, the one step of an int, a Biweight or a SysRem, and
-    the elements of a tuple or list of those."""
+    """The steps of a detrend= argument, left to right: () for None, the one step of an int, a Biweight, a SysRem or a
+    Prewhiten, and the elements of a tuple or list of those."""
     if detrend is None:
         return ()
-    if isinstance(detrend, (Biweight, SysRem)) or not isinstance(detrend, (tuple, list)):
+    if isinstance(detrend, (Biweight, SysRem, Prewhiten)) or not isinstance(detrend, (tuple, list)):
         return (detrend,)
     for step in detrend:
-        if step is None or (isinstance(step, (tuple, list)) and not isinstance(step, (Biweight, SysRem))):
+        if step is None or (isinstance(step, (tuple, list)) and not isinstance(step, (Biweight, SysRem, Prewhiten))):
             raise ValueError("a step of detrend must be a kernel size, a Biweight or a SysRem, got %r" % (step,))
     return tuple(detrend)
 
@@ -279,7 +403,8 @@ def _first_context(context, device, devices, n_curves):
 def _detrended(t, flux_batch, detrend, context, device, devices, dy_batch=None):
     """flux_batch as it is (detrend None), or taken through the steps of detrend left to right on the call's devices for
     [n_curves, len(t)]: biweight_batch for a Biweight, the whole batch through SysRem on the first device (weighted with
-    dy_batch where one is given) for a SysRem, detrend_batch(flux_batch, step) otherwise."""
+    dy_batch where one is given) for a SysRem, prewhiten_batch (on variability_frequencies(t) cut to the step's range, weighted
+    with dy_batch where one is given) for a Prewhiten, detrend_batch(flux_batch, step) otherwise."""
     steps = _detrend_steps(detrend)
     if not steps:
         return flux_batch
@@ -295,18 +420,26 @@ def _detrended(t, flux_batch, detrend, context, device, devices, dy_batch=None):
         elif isinstance(step, Biweight):
             flux_batch = biweight_batch(t, flux_batch, step.window_length, step.break_tolerance, context=context,
                                         device=device, devices=devices)
+        elif isinstance(step, Prewhiten):
+            grid, k, h, low = _prewhiten_step(t, step, len(t))
+            flux_batch = prewhiten_batch(t, flux_batch, k, h, low, frequencies=grid, dy_batch=dy_batch, context=context,
+                                         device=device, devices=devices)
         else:
             flux_batch = detrend_batch(flux_batch, step, context=context, device=device, devices=devices)
     return flux_batch
 
 
 def _detrend_rows(ctx, t, rows, detrend):
-    """rows as they are (detrend None), or taken through the per-row steps of detrend on ctx: the biweight for a Biweight, the
+    """rows as they are (detrend None), or taken through the per-row steps of detrend on ctx: the biweight for a Biweight,
+    pre-whitening with uniform weights for a Prewhiten, the
     median filter of kernel size step otherwise (the rows formed on the device by injection_recovery and null_sde, chunk by
     chunk)."""
     for step in _detrend_steps(detrend):
         if isinstance(step, Biweight):
             rows = ctx.biweight_detrend(t, rows, step.window_length, step.break_tolerance)
+        elif isinstance(step, Prewhiten):
+            grid, k, h, low = _prewhiten_step(t, step, len(t))
+            rows = ctx.prewhiten(t, rows, grid, k, h, low)
         else:
             rows = ctx.medfilt_detrend(rows, step)
     return rows
@@ -2337,6 +2470,10 @@ def injection_recovery(t, flux, injections, dy=None, inject_u=None, inject_limb_
         if isinstance(step, Biweight):
             from ._lib import biweight_arguments
             biweight_arguments(t, flux, step.window_length, step.break_tolerance)
+        elif isinstance(step, Prewhiten):
+            from ._lib import prewhiten_arguments
+            grid, k, h, low = _prewhiten_step(t, step, n)
+            prewhiten_arguments(t, flux, None, grid, k, h, low)
         else:
             from ._lib import medfilt_arguments
             medfilt_arguments(flux, step)
@@ -2498,6 +2635,10 @@ def null_sde(t, n_trials, sigma=None, source=None, block=None, seed=0, first_tri
         if isinstance(step, Biweight):
             from ._lib import biweight_windows
             biweight_windows(t, step.window_length, step.break_tolerance)
+        elif isinstance(step, Prewhiten):
+            from ._lib import prewhiten_arguments
+            grid, k, h, low = _prewhiten_step(t, step, n)
+            prewhiten_arguments(t, numpy.ones(n), None, grid, k, h, low)
         else:
             from ._lib import medfilt_kernel
             medfilt_kernel(step, n)
