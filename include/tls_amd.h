@@ -187,10 +187,12 @@ int tls_debug_period_cycles(tls_ctx *ctx, uint64_t *cycles, int64_t capacity);
  * bound of the search kernel on the device and counts violations per check (names in
  * tls_amd/_lib.py::check_counts); returns 1 from a checked build, 0 (all counts zero) otherwise. */
 int tls_debug_check_counts(tls_ctx *ctx, uint64_t *counts, int n);
-/* Test entry: fills the LDS of every CU with `word` (0x7ff80000 pairs read as fp64 NaNs) and the context's per-workgroup
- * scratch in HBM (slabs, lists, stashed orders) with all-ones bytes, on the context's stream -- what a previous tenant of
- * the GPU may have left there.  A search after it must return the bits of a search before it
- * (tests/test_gpu_parity.py: no kernel reads memory it has not written). */
+/* Test entry: fills the LDS of every CU with `word` (0x7ff80000 pairs read as fp64 NaNs) and, with all-ones bytes, every
+ * device buffer of the context that a call fills for itself before it reads it -- the search's per-workgroup scratch (slabs,
+ * lists, stashed orders), the post-search chain's arrays, every survey stage's buffer; not the plan, the results, the queues
+ * and counters, the batch slots -- on the context's stream: what a previous tenant of the GPU may have left there.  A call
+ * after it must return the bits of a call before it (tests/test_gpu_parity.py, tests/test_stage_memory.py: no kernel reads
+ * memory it has not written). */
 int tls_debug_poison_lds(tls_ctx *ctx, uint32_t word);
 /* developer instrumentation: host wall time (ms) of every group of 32 light curves of the context's last tls_power_batch /
  * tls_search_batch call (a stall in one group -- a transfer, a wait, a T0-fit launch -- shows here; bench.py prints the

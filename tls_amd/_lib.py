@@ -2251,7 +2251,8 @@ class Context(object):
         return bool(rc), dict(zip(names, [int(v) for v in arr]))
 
     def poison_lds(self, word=0x7ff80000):
-        """Test entry: every CU's LDS filled with `word` (default: fp64 NaNs) on the context's stream."""
+        """Test entry: every CU's LDS filled with `word` (default: fp64 NaNs) and every device buffer a call fills for itself
+        smeared with 0xFF bytes (DESIGN.md section 7 lists them), on the context's stream."""
         self._check(self._lib.tls_debug_poison_lds(self._h, int(word)))
 
     def synchronize(self):

@@ -2694,18 +2694,65 @@ int tls_debug_poison_lds(tls_ctx* ctx, uint32_t word) {
                        static_cast<unsigned int*>(nullptr));
     TLS_HIP(ctx, hipGetLastError());
     // ... and the per-workgroup scratch in HBM (slabs, live-unit lists, stashed orders, the screen's and the sorts' scratch, the
-    // T0 fit's slabs): all ones -- NaNs as doubles -- as fresh device memory may be.  (Not the queues and counters, whose zero
-    // state between launches is the kernels' own invariant, nor the plan, its table of folded orders and the results.)
-    auto smear = [&](void* ptr, size_t bytes) -> hipError_t { return ptr && bytes ? hipMemsetAsync(ptr, 0xFF, bytes, ctx->stream) : hipSuccess; };
-    TLS_HIP(ctx, smear(ctx->d_scratch.ptr, ctx->d_scratch.cap * sizeof(double)));
-    TLS_HIP(ctx, smear(ctx->d_lists.ptr, ctx->d_lists.cap * sizeof(unsigned int)));
-    TLS_HIP(ctx, smear(ctx->d_perm.ptr, ctx->d_perm.cap * sizeof(unsigned int)));
-    TLS_HIP(ctx, smear(ctx->d_split.ptr, ctx->d_split.cap * sizeof(float)));
-    TLS_HIP(ctx, smear(ctx->d_park.ptr, ctx->d_park.cap * sizeof(double)));
-    TLS_HIP(ctx, smear(ctx->d_fscratch.ptr, ctx->d_fscratch.cap * sizeof(double)));
-    TLS_HIP(ctx, smear(ctx->d_frot.ptr, ctx->d_frot.cap * sizeof(double)));
-    TLS_HIP(ctx, smear(ctx->d_frperm.ptr, ctx->d_frperm.cap * sizeof(int)));
-    TLS_HIP(ctx, smear(ctx->d_views.ptr, ctx->d_views.cap * sizeof(double)));
+    // T0 fit's slabs), the post-search chain's arrays and every survey stage's buffer: all ones -- NaNs as doubles -- as fresh
+    // device memory may be.  Every buffer below is one whose next call uploads or writes all that it reads from it.
+    // Not smeared, because what they hold between calls is state by design:
+    //   d_plan, d_perm_table, d_band      the plan, its table of folded orders, and the band prefix the host caches by sigma
+    //   d_out, d_stage, d_gather          the results a later call may trust (tls_spectra without chi2, the staged / gathered
+    //                                     results of the comm calls)
+    //   d_queue, d_squeue, d_pqueues, d_tiles_done, d_check, d_phase, d_sysrem_state
+    //                                     queues and counters whose zero state between launches is the kernels' own invariant
+    //   d_curve_S0, d_curve_w0 and the batch slots (slot[].d_*)
+    //                                     the inputs and results of the survey batches
+    auto smear = [&](auto& buf) -> hipError_t {
+        return buf.ptr && buf.cap ? hipMemsetAsync(buf.ptr, 0xFF, buf.cap * sizeof(*buf.ptr), ctx->stream) : hipSuccess;
+    };
+    TLS_HIP(ctx, smear(ctx->d_scratch));
+    TLS_HIP(ctx, smear(ctx->d_lists));
+    TLS_HIP(ctx, smear(ctx->d_perm));
+    TLS_HIP(ctx, smear(ctx->d_split));
+    TLS_HIP(ctx, smear(ctx->d_park));
+    TLS_HIP(ctx, smear(ctx->d_partials));
+    TLS_HIP(ctx, smear(ctx->d_pack));
+    TLS_HIP(ctx, smear(ctx->d_scalar));
+    // the final T0 fit and the post-search chain
+    TLS_HIP(ctx, smear(ctx->d_ft));
+    TLS_HIP(ctx, smear(ctx->d_fy));
+    TLS_HIP(ctx, smear(ctx->d_fsig));
+    TLS_HIP(ctx, smear(ctx->d_fep));
+    TLS_HIP(ctx, smear(ctx->d_fres));
+    TLS_HIP(ctx, smear(ctx->d_fscratch));
+    TLS_HIP(ctx, smear(ctx->d_frot));
+    TLS_HIP(ctx, smear(ctx->d_frperm));
+    TLS_HIP(ctx, smear(ctx->d_pink));
+    TLS_HIP(ctx, smear(ctx->d_spec));
+    TLS_HIP(ctx, smear(ctx->d_tstats));
+    TLS_HIP(ctx, smear(ctx->d_tranges));
+    TLS_HIP(ctx, smear(ctx->d_models));
+    TLS_HIP(ctx, smear(ctx->d_peaks));
+    TLS_HIP(ctx, smear(ctx->d_peak_mask));
+    TLS_HIP(ctx, smear(ctx->d_pfit));
+    TLS_HIP(ctx, smear(ctx->d_pfep));
+    TLS_HIP(ctx, smear(ctx->d_pfres));
+    TLS_HIP(ctx, smear(ctx->d_pfstats));
+    TLS_HIP(ctx, smear(ctx->d_pfranges));
+    // the survey stages
+    TLS_HIP(ctx, smear(ctx->d_inject));
+    TLS_HIP(ctx, smear(ctx->d_inject_count));
+    TLS_HIP(ctx, smear(ctx->d_null));
+    TLS_HIP(ctx, smear(ctx->d_null_words));
+    TLS_HIP(ctx, smear(ctx->d_detrend));
+    TLS_HIP(ctx, smear(ctx->d_windows));
+    TLS_HIP(ctx, smear(ctx->d_sysrem));
+    TLS_HIP(ctx, smear(ctx->d_scan));
+    TLS_HIP(ctx, smear(ctx->d_single));
+    TLS_HIP(ctx, smear(ctx->d_times));
+    TLS_HIP(ctx, smear(ctx->d_vetting));
+    TLS_HIP(ctx, smear(ctx->d_shape));
+    TLS_HIP(ctx, smear(ctx->d_centroid));
+    TLS_HIP(ctx, smear(ctx->d_views));
+    TLS_HIP(ctx, smear(ctx->d_gls));
+    TLS_HIP(ctx, smear(ctx->d_match));
     return TLS_OK;
 }
 
