@@ -41,7 +41,7 @@ extern "C" {
  * tls_debug_peak_phase_scans), (7: tls_sysrem), (7: tls_single_transits), (7: tls_transit_times),
  * (7: tls_shape_fit), (7: tls_nudft, tls_lomb_scargle, tls_sine_test); 8: every entry that takes `root, n_root` takes a
  * second table, `root, root_count, n_root`), (8: tls_ephemeris_match), (8: tls_folded_views),
- * (8: tls_event_vetting), (8: tls_centroid_test). */
+ * (8: tls_event_vetting), (8: tls_centroid_test), (8: tls_noise_profile). */
 #define TLS_AMD_ABI_VERSION 8
 
 #define TLS_OK 0
@@ -1120,6 +1120,45 @@ typedef struct tls_match_record {
 int tls_ephemeris_match(tls_ctx *ctx, const int64_t *star, const double *period, const double *T0, const double *duration,
                         const double *strength, int64_t n, double span, double drift_tolerance, double epoch_tolerance,
                         int64_t max_ratio, tls_match_record *out);
+
+/* ---- survey mode: the per-star noise profile (a robust CDPP by window width) ------------------------------------------- */
+/* How noisy is each star on the time scale of a transit?  For every curve y [n] (a -0.0 is taken as +0.0) over the shared time
+ * stamps t [n] (or NULL: no gaps), with K = 1.4826022185056018 and median(v [m]) = the value of rank m / 2 of the sorted
+ * values for odd m, 0.5 * (s[m/2 - 1] + s[m/2]) for even m:
+ *   m = median(y);  d_j = y_j - m;  sigma = K * median(|d_j|)
+ *   sigma == 0: status 1, n_clipped 0, n_pairs 0, sigma_p2p NaN, every per-width value NaN, every count 0
+ *   keep_j = (d_j <= clip_upper * sigma) and (d_j >= -(clip_lower * sigma));  n_clipped = the others.  One pass, internal to
+ *   the measurement; an infinite clip switches its side off
+ *   pairs = the j with keep_j, keep_{j+1} and t_{j+1} - t_j <= pair_span;  n_pairs their number
+ *   sigma_p2p = (K * median(|y_{j+1} - y_j| over the pairs)) / 1.4142135623730951, NaN without a pair
+ * and for every width w = widths[k] (samples), window i = the samples [i, i + w), i = 0 .. n - w:
+ *   valid_i = every sample kept and t[i + w - 1] - t[i] <= span_max[k]
+ *   v_i = (((0.0 + d_i) + d_{i+1}) + ... + d_{i+w-1}) / w          (the direct sum, left to right: no prefix sums)
+ *   count = the valid windows;  count < min_count: robust and rms NaN
+ *   mu = median(valid v);  robust = K * median(|v_i - mu| over the valid)
+ *   mean = lanes(v) / count;  rms = sqrt(lanes((v_i - mean) * (v_i - mean)) / count)
+ * lanes() is the sine test's ordered sum over 256 lanes (window i on lane i mod 256).  Every step is one IEEE double
+ * operation and every median a selection, so the results equal the numpy statement in tests/noise_profile_spec.py bit for
+ * bit.  The caller forms span_max[k] = (w - 1 + gap_tolerance) * cadence and pair_span = (1 + gap_tolerance) * cadence.
+ * Counts in the record are doubles.  6 doubles. */
+#define TLS_NOISE_MAX_WIDTH 4096
+#define TLS_NOISE_MAX_WIDTHS 64
+#define TLS_NOISE_MAX_POINTS 4194304
+#define TLS_NOISE_LDS_POINTS 8192   /* rows of at most this many points are measured in the LDS, longer ones in device memory */
+typedef struct tls_noise_curve {
+    double status;                 /* 0 measured; 1 sigma == 0 (a constant row, or more than half of it on one value) */
+    double n_clipped, n_pairs;
+    double median, sigma, sigma_p2p;
+} tls_noise_curve;
+/* The profiles of n_curves rows; out_curves [n_curves], out_count, out_robust, out_rms [n_curves][n_widths].  Needs no plan
+ * and no search, and leaves a prepared plan as it is.  Curves are processed in slabs, so device memory stays bounded.
+ * n_curves == 0 is a no-op.  TLS_E_ARG, before any device work, unless n is in [3, TLS_NOISE_MAX_POINTS], n_widths in
+ * [1, TLS_NOISE_MAX_WIDTHS], the widths strictly ascending in [1, min(n, TLS_NOISE_MAX_WIDTH)], every span_max and
+ * pair_span >= 0 (inf allowed), both clips >= 0 (inf allowed), min_count >= 1, y finite and t (where given) finite and
+ * ascending. */
+int tls_noise_profile(tls_ctx *ctx, const double *t, const double *y, int64_t n, int64_t n_curves, const int64_t *widths,
+                      const double *span_max, int64_t n_widths, double pair_span, double clip_upper, double clip_lower,
+                      int64_t min_count, tls_noise_curve *out_curves, int64_t *out_count, double *out_robust, double *out_rms);
 
 /* ---- host-only planning (no GPU needed) ------------------------------------------ */
 /* Trial cells (duration x T0 positions) each period will enumerate: the data-independent

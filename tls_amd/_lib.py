@@ -95,6 +95,13 @@ MATCH_MAX_RATIO = 64
 MATCH_TILE = 256
 MATCH_TARGET_GROUPS = 1024
 MATCH_MAX_CHUNKS = 16
+# include/tls_amd.h TLS_NOISE_*: the widest window, the most widths and the longest row of tls_noise_profile, and the points
+# of a row the LDS holds (a longer one is measured in device scratch); tls_noise.hip.h kNoiseThreads
+NOISE_MAX_WIDTH = 4096
+NOISE_MAX_WIDTHS = 64
+NOISE_MAX_POINTS = 1 << 22
+NOISE_LDS_POINTS = 8192
+NOISE_THREADS = 256
 PEAKS_LDS_PERIODS = 1 << 20   # tls_peaks.hip.h kPeaksLdsPeriods: a longer grid keeps its alive mask in device memory, not in LDS
 
 # every symbol include/tls_amd.h declares (tests check the export list against the header)
@@ -108,7 +115,7 @@ SYMBOLS = (
     "tls_biweight_detrend", "tls_sysrem", "tls_find_peaks", "tls_power_batch_peaks", "tls_power_batch_peak_fits", "tls_debug_peak_fits",
     "tls_phase_scan", "tls_power_batch_phase_scan", "tls_debug_peak_phase_scans", "tls_single_transits",
     "tls_transit_times", "tls_shape_fit", "tls_nudft", "tls_lomb_scargle", "tls_sine_test", "tls_prewhiten",
-    "tls_ephemeris_match", "tls_folded_views", "tls_event_vetting", "tls_centroid_test",
+    "tls_ephemeris_match", "tls_folded_views", "tls_event_vetting", "tls_centroid_test", "tls_noise_profile",
     "tls_comm_unique_id", "tls_comm_init", "tls_comm_destroy", "tls_comm_info", "tls_comm_allgather_results", "tls_comm_allgather_device", "tls_comm_fetch_gathered",
     "tls_comm_stage_results", "tls_comm_allgather_staged", "tls_comm_fetch_staged",
     "tls_comm_barrier", "tls_comm_max",
@@ -312,8 +319,70 @@ def ephemeris_match_arguments(star, period, T0, duration, strength, span, drift_
                 drift_tolerance=float(drift_tolerance), epoch_tolerance=float(epoch_tolerance), max_ratio=int(max_ratio))
 
 
+# tls_noise_curve (include/tls_amd.h): the per-curve part of a noise profile, 6 doubles
+NOISE_CURVE_FIELDS = ("status", "n_clipped", "n_pairs", "median", "sigma", "sigma_p2p")
+
+
+class NoiseCurve(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_double) for k in NOISE_CURVE_FIELDS]
+
+
+NOISE_CURVE_DTYPE = numpy.dtype([(k, "f8") for k in NOISE_CURVE_FIELDS])
+# tls_noise_curve.status
+NOISE_MEASURED, NOISE_NO_SIGMA = 0, 1
+
+
+def noise_arguments(t, y, widths, span_max, pair_span, clip_upper=5.0, clip_lower=5.0, min_count=3):
+    """What tls_noise_profile takes, checked as it checks them: a dict with t (float64 [n], finite and ascending, or None), y
+    (float64 [n_curves, n], finite; one row becomes [1, n]), n in [3, NOISE_MAX_POINTS], widths (int64 [W], W in
+    [1, NOISE_MAX_WIDTHS], integers, strictly ascending in [1, min(n, NOISE_MAX_WIDTH)]), span_max (float64 [W], >= 0, inf
+    allowed), pair_span (>= 0, inf allowed), clip_upper and clip_lower (>= 0, inf allowed) and min_count (an integer >= 1).
+    ValueError otherwise.  GPU-free."""
+    what = "noise profile"
+    try:
+        y = numpy.asarray(y, dtype=numpy.float64)
+        t = None if t is None else numpy.ascontiguousarray(numpy.asarray(t, dtype=numpy.float64))
+    except (TypeError, ValueError):
+        raise ValueError("%s: the light curves and t must hold numbers" % what)
+    if y.ndim == 1:
+        y = y[None, :]
+    if y.ndim != 2 or (t is not None and (t.ndim != 1 or y.shape[1] != len(t))):
+        raise ValueError("%s: flux must be [n] or [n_curves, n] over the time stamps t [n]" % what)
+    n = y.shape[1]
+    if not 3 <= n <= NOISE_MAX_POINTS:
+        raise ValueError("%s: n must lie in [3, %d], got %d" % (what, NOISE_MAX_POINTS, n))
+    if t is not None and (not numpy.all(numpy.isfinite(t)) or not numpy.all(t[1:] >= t[:-1])):
+        raise ValueError("%s: t must be finite and ascending" % what)
+    if y.size and not numpy.all(numpy.isfinite(y)):
+        raise ValueError("%s: the flux has a NaN or an infinite value" % what)
+    raw = numpy.atleast_1d(numpy.asarray(widths))
+    if raw.ndim != 1 or not 1 <= len(raw) <= NOISE_MAX_WIDTHS:
+        raise ValueError("%s: widths must be [W] with W in [1, %d]" % (what, NOISE_MAX_WIDTHS))
+    if raw.dtype.kind == "f" and numpy.all(numpy.isfinite(raw)) and numpy.all(raw == numpy.floor(raw)):
+        raw = raw.astype(numpy.int64)
+    if raw.dtype.kind not in "iu":
+        raise ValueError("%s: the widths must be integers, got %r" % (what, widths))
+    w = numpy.ascontiguousarray(raw, dtype=numpy.int64)
+    if w.min() < 1 or w.max() > min(n, NOISE_MAX_WIDTH) or not numpy.all(w[1:] > w[:-1]):
+        raise ValueError("%s: the widths must ascend strictly within [1, min(n, %d)] = [1, %d], got %r"
+                         % (what, NOISE_MAX_WIDTH, min(n, NOISE_MAX_WIDTH), w.tolist()))
+    try:
+        span = numpy.ascontiguousarray(numpy.atleast_1d(numpy.asarray(span_max, dtype=numpy.float64)))
+    except (TypeError, ValueError):
+        raise ValueError("%s: span_max must hold numbers" % what)
+    if span.shape != w.shape or not numpy.all(span >= 0.0):
+        raise ValueError("%s: span_max must hold one value >= 0 a width" % what)
+    for name, v in (("pair_span", pair_span), ("clip_upper", clip_upper), ("clip_lower", clip_lower)):
+        if isinstance(v, (bool, numpy.bool_)) or not isinstance(v, numbers.Real) or not float(v) >= 0.0:
+            raise ValueError("%s: %s must be a number >= 0, got %r" % (what, name, v))
+    if isinstance(min_count, (bool, numpy.bool_)) or not isinstance(min_count, numbers.Integral) or not 1 <= int(min_count) < 2 ** 31:
+        raise ValueError("%s: min_count must be an integer >= 1, got %r" % (what, min_count))
+    return dict(t=t, y=numpy.ascontiguousarray(y), widths=w, span_max=span, pair_span=float(pair_span),
+                clip_upper=float(clip_upper), clip_lower=float(clip_lower), min_count=int(min_count))
+
+
 # tls_single_event (include/tls_amd.h): one single-transit event, 8 doubles
-SINGLE_EVENT_FIELDS = ("index", "time", "ses", "depth", "row", "width", "t_first", "t_last")
+SINGLE_EVENT_FIELDS =("index", "time", "ses", "depth", "row", "width", "t_first", "t_last")
 
 
 class SingleEvent(ctypes.Structure):
@@ -1153,6 +1222,9 @@ def load():
     lib.tls_ephemeris_match.restype = ci
     lib.tls_ephemeris_match.argtypes = [vp, _c_int64_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, i64, dbl, dbl, dbl,
                                         i64, ctypes.c_void_p]
+    lib.tls_noise_profile.restype = ci
+    lib.tls_noise_profile.argtypes = [vp, _c_double_p, _c_double_p, i64, i64, _c_int64_p, _c_double_p, i64, dbl, dbl, dbl, i64,
+                                      ctypes.c_void_p, _c_int64_p, _c_double_p, _c_double_p]
     lib.tls_debug_peak_phase_scans.restype = ci
     lib.tls_debug_peak_phase_scans.argtypes = [vp, _c_double_p, i64, ctypes.c_void_p, _c_int64_p, i64, _c_double_p, _c_double_p,
                                                i64, dbl, _c_double_p, _c_double_p, i64, i64, ctypes.c_void_p, i64, i64,
@@ -2134,6 +2206,24 @@ class Context(object):
             a["span"], a["drift_tolerance"], a["epoch_tolerance"], a["max_ratio"], out.ctypes.data_as(ctypes.c_void_p)))
         return out
 
+    def noise_profile(self, t, y, widths, span_max, pair_span, clip_upper=5.0, clip_lower=5.0, min_count=3):
+        """The noise profiles (tls_noise_profile; the statement: include/tls_amd.h, tests/noise_profile_spec.py) of the curves
+        y [n_curves, n] (or one row) over t [n] (None: no gaps) at the window widths `widths` [W] (samples) with the span
+        limits span_max [W] and pair_span: (records NOISE_CURVE_DTYPE [n_curves], count int64 [n_curves, W], robust and rms
+        [n_curves, W]).  ValueError for what noise_arguments refuses."""
+        a = noise_arguments(t, y, widths, span_max, pair_span, clip_upper, clip_lower, min_count)
+        n_c, n = a["y"].shape
+        W = len(a["widths"])
+        records = numpy.zeros(n_c, dtype=NOISE_CURVE_DTYPE)
+        count = numpy.zeros((n_c, W), dtype=numpy.int64)
+        robust, rms = numpy.zeros((n_c, W)), numpy.zeros((n_c, W))
+        assert NOISE_CURVE_DTYPE.itemsize == ctypes.sizeof(NoiseCurve)
+        self._check(self._lib.tls_noise_profile(
+            self._h, None if a["t"] is None else _dp(a["t"]), _dp(a["y"]), n, n_c, _ip(a["widths"]), _dp(a["span_max"]), W,
+            a["pair_span"], a["clip_upper"], a["clip_lower"], a["min_count"], records.ctypes.data_as(ctypes.c_void_p),
+            _ip(count), _dp(robust), _dp(rms)))
+        return records, count, robust, rms
+
     def debug_null_words(self, n, n_rows, seed, first_trial=0, block=None):
         """The raw Philox words [n_rows, W] tls_null_rows draws for these trials (tls_debug_null_words): white-noise
         layout when `block` is None, the bootstrap's otherwise."""
@@ -2241,13 +2331,14 @@ class Context(object):
 
     def check_counts(self):
         """(checked_build, {check name: violations}) -- device-side bound checks of the debug build."""
-        arr = (ctypes.c_uint64 * 16)()
-        rc = self._lib.tls_debug_check_counts(self._h, arr, 16)
+        arr = (ctypes.c_uint64 * 17)()
+        rc = self._lib.tls_debug_check_counts(self._h, arr, 17)
         if rc < 0:
             self._check(rc)
         names = ("lds_carve", "list_capacity", "dot_window", "predicate_read", "sort_window", "work_item",
                  "singles_capacity", "tile_stage", "screen_split", "detrend_slot",
-                 "biweight_slot", "sysrem_index", "single_window", "times_window", "shape_index", "views_range")
+                 "biweight_slot", "sysrem_index", "single_window", "times_window", "shape_index", "views_range",
+                 "noise_window")
         return bool(rc), dict(zip(names, [int(v) for v in arr]))
 
     def poison_lds(self, word=0x7ff80000):

@@ -242,6 +242,9 @@ struct tls_ctx {
     DevBuf<double> d_gls;
     // tls_ephemeris_match: star | period | T0 | duration | strength | records | partial records of every chunk
     DevBuf<double> d_match;
+    // tls_noise_profile: t | span_max | widths; of one slab: rows | d | records | count | robust | rms | clip counts | and for
+    // rows that do not fit the LDS the window means and validity words of every (curve, width)
+    DevBuf<double> d_noise;
     // two-role slab path (series in HBM, one light curve; SearchPlan::split)
     View<unsigned int> d_tile_prefix;        // [n_periods + 1] tiles in front of work item w (queue order)
     DevBuf<double> d_partials;               // [split_max_items][3] a tile's winner
@@ -1820,6 +1823,7 @@ void tls_ctx_destroy(tls_ctx* ctx) {
     ctx->d_views.release();
     ctx->d_gls.release();
     ctx->d_match.release();
+    ctx->d_noise.release();
     ctx->d_split.release(); ctx->d_park.release(); ctx->d_band.release();
     if (ctx->h_band) (void)hipHostFree(ctx->h_band);
     for (auto& ev : ctx->ev_band) if (ev) (void)hipEventDestroy(ev);
@@ -2753,6 +2757,7 @@ int tls_debug_poison_lds(tls_ctx* ctx, uint32_t word) {
     TLS_HIP(ctx, smear(ctx->d_views));
     TLS_HIP(ctx, smear(ctx->d_gls));
     TLS_HIP(ctx, smear(ctx->d_match));
+    TLS_HIP(ctx, smear(ctx->d_noise));
     return TLS_OK;
 }
 
@@ -3031,6 +3036,7 @@ int tls_debug_device_bytes(const tls_ctx* ctx, int64_t* total, int64_t* t0_fit_s
     add(ctx->d_views);
     add(ctx->d_gls);
     add(ctx->d_match);
+    add(ctx->d_noise);
     add(ctx->d_partials); add(ctx->d_tiles_done);
     add(ctx->d_split); add(ctx->d_park); add(ctx->d_band);
     *total = (int64_t)sum;
@@ -4366,6 +4372,107 @@ int tls_ephemeris_match(tls_ctx* ctx, const int64_t* star, const double* period,
     ctx->last_kernel = "tls_ephemeris_match";
     TLS_HIP(ctx, hipMemcpyAsync(out, d_out, words * nn * 8, hipMemcpyDeviceToHost, ctx->stream));
     TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return TLS_OK;
+}
+
+// ---- the noise profile (tls_noise.hip.h, DESIGN.md "Noise profile"): a curve kernel (median, sigma, the clipped points, the
+// point-to-point sigma), then one workgroup a (width, curve)
+static_assert(sizeof(tls_noise_curve) == tlsdev::kNoiseWords * 8, "tls_noise_curve is the kernel's record");
+static_assert(TLS_NOISE_MAX_WIDTH == tlsdev::kNoiseMaxWidth && TLS_NOISE_MAX_WIDTHS == tlsdev::kNoiseMaxWidths &&
+              TLS_NOISE_LDS_POINTS == tlsdev::kNoiseLdsPoints, "the header's limits");
+static_assert(tlsdev::noise_width_lds_bytes(tlsdev::kNoiseLdsPoints, true) <= 160 * 1024, "the longest resident row fits the LDS");
+
+int tls_noise_profile(tls_ctx* ctx, const double* t, const double* y, int64_t n, int64_t n_curves, const int64_t* widths,
+                      const double* span_max, int64_t n_widths, double pair_span, double clip_upper, double clip_lower,
+                      int64_t min_count, tls_noise_curve* out_curves, int64_t* out_count, double* out_robust, double* out_rms) {
+    if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
+    if (n < 3 || n > TLS_NOISE_MAX_POINTS) return fail(ctx, TLS_E_ARG, "noise profile: n out of range [3, 2^22]");
+    if (n_curves < 0) return fail(ctx, TLS_E_ARG, "noise profile: n_curves < 0");
+    if (n_widths < 1 || n_widths > TLS_NOISE_MAX_WIDTHS) return fail(ctx, TLS_E_ARG, "noise profile: n_widths out of range [1, 64]");
+    if (!widths || !span_max) return fail(ctx, TLS_E_ARG, "null argument");
+    for (int64_t k = 0; k < n_widths; ++k) {
+        if (widths[k] < 1 || widths[k] > n || widths[k] > TLS_NOISE_MAX_WIDTH || (k > 0 && widths[k] <= widths[k - 1]))
+            return fail(ctx, TLS_E_ARG, "noise profile: the widths must ascend strictly within [1, min(n, " + std::to_string(TLS_NOISE_MAX_WIDTH) + ")]");
+        if (!(span_max[k] >= 0.0)) return fail(ctx, TLS_E_ARG, "noise profile: every span_max must be >= 0");
+    }
+    if (!(pair_span >= 0.0)) return fail(ctx, TLS_E_ARG, "noise profile: pair_span must be >= 0");
+    if (!(clip_upper >= 0.0) || !(clip_lower >= 0.0)) return fail(ctx, TLS_E_ARG, "noise profile: the clips must be >= 0");
+    if (min_count < 1) return fail(ctx, TLS_E_ARG, "noise profile: min_count < 1");
+    if (n_curves == 0) return TLS_OK;
+    if (!y || !out_curves || !out_count || !out_robust || !out_rms) return fail(ctx, TLS_E_ARG, "null argument");
+    const size_t nn = (size_t)n, W = (size_t)n_widths;
+    if ((uint64_t)n_curves > (uint64_t)(SIZE_MAX / 8) / (uint64_t)n) return fail(ctx, TLS_E_ARG, "noise profile: rows too large");
+    if (t)
+        for (size_t i = 0; i < nn; ++i)
+            if (!std::isfinite(t[i]) || (i > 0 && t[i] < t[i - 1])) return fail(ctx, TLS_E_ARG, "noise profile: t must be finite and ascending");
+    for (size_t q = 0; q < (size_t)n_curves * nn; ++q)
+        if (!std::isfinite(y[q])) return fail(ctx, TLS_E_ARG, "noise profile: row " + std::to_string(q / nn) + " has a non-finite value");
+    TLS_HIP(ctx, hipSetDevice(ctx->device));
+    const bool lds = n <= tlsdev::kNoiseLdsPoints;
+    const size_t mask_words = tlsdev::noise_mask_words((int)n);
+    // curves per launch: at most 256 MB of rows, at most 256 MB of window means where they lie in device memory, and
+    // gridDim.y within its limit
+    int64_t slab = std::min<int64_t>({n_curves, (int64_t)65535, (int64_t)((256u << 20) / (8 * nn))});
+    if (!lds) slab = std::min<int64_t>(slab, (int64_t)((256u << 20) / (8 * nn * W)));
+    slab = std::max<int64_t>(1, slab);
+    const size_t S = (size_t)slab;
+    const size_t width_words = (W + 1) / 2;                        // int32 widths in doubles
+    const size_t bad_words = (S * (nn + 1) + 1) / 2;               // uint32 counts in doubles
+    const size_t scratch_words = lds ? 0 : S * W * (nn + mask_words);
+    TLS_HIP(ctx, ctx->d_noise.reserve(nn + W + width_words + 2 * S * nn + S * tlsdev::kNoiseWords + 3 * S * W + bad_words + scratch_words));
+    double* d_t = ctx->d_noise.ptr;
+    double* d_span = d_t + nn;
+    double* d_widths = d_span + W;
+    double* d_y = d_widths + width_words;
+    double* d_d = d_y + S * nn;
+    double* d_records = d_d + S * nn;
+    double* d_count = d_records + S * tlsdev::kNoiseWords;
+    double* d_robust = d_count + S * W;
+    double* d_rms = d_robust + S * W;
+    double* d_bad = d_rms + S * W;
+    double* d_v = d_bad + bad_words;
+    double* d_mask = d_v + S * W * nn;
+    std::vector<int> w32((size_t)n_widths);
+    for (size_t k = 0; k < W; ++k) w32[k] = (int)widths[k];
+    if (t) TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_span, span_max, W * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_widths, w32.data(), W * 4, hipMemcpyHostToDevice, ctx->stream));
+    const size_t curve_lds = tlsdev::noise_curve_lds_bytes((int)n, lds), width_lds = tlsdev::noise_width_lds_bytes((int)n, lds);
+    auto curve_kernel = lds ? tlsdev::tls_noise_curve_kernel<true> : tlsdev::tls_noise_curve_kernel<false>;
+    auto width_kernel = lds ? tlsdev::tls_noise_width_kernel<true> : tlsdev::tls_noise_width_kernel<false>;
+    TLS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(curve_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)curve_lds));
+    TLS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(width_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)width_lds));
+    tlsdev::NoiseArgs a;
+    a.t = t ? d_t : nullptr; a.y = d_y; a.d = d_d; a.bad = reinterpret_cast<unsigned int*>(d_bad); a.records = d_records;
+    a.widths = reinterpret_cast<const int*>(d_widths); a.span_max = d_span;
+    a.v = lds ? nullptr : d_v; a.mask = lds ? nullptr : reinterpret_cast<unsigned long long*>(d_mask);
+    a.count = reinterpret_cast<long long*>(d_count); a.robust = d_robust; a.rms = d_rms; a.check = nullptr;
+    a.pair_span = pair_span; a.clip_upper = clip_upper; a.clip_lower = clip_lower;
+    a.n = (int)n; a.W = (int)n_widths; a.min_count = (int)std::min<int64_t>(min_count, (int64_t)INT32_MAX);
+#ifdef TLS_DEBUG_CHECKS
+    if (int rc = ensure_check_counters(ctx)) return rc;
+    a.check = ctx->d_check.ptr;
+#endif
+    for (int64_t k0 = 0; k0 < n_curves; k0 += slab) {
+        const size_t rows = (size_t)std::min<int64_t>(slab, n_curves - k0);
+        TLS_HIP(ctx, hipMemcpyAsync(d_y, y + (size_t)k0 * nn, rows * nn * 8, hipMemcpyHostToDevice, ctx->stream));
+        hipLaunchKernelGGL(curve_kernel, dim3((unsigned)rows), dim3(tlsdev::kNoiseThreads), curve_lds, ctx->stream, a);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(width_kernel, dim3((unsigned)W, (unsigned)rows), dim3(tlsdev::kNoiseThreads), width_lds, ctx->stream, a);
+            e = hipGetLastError();
+        }
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(ctx->stream);
+            return fail(ctx, TLS_E_HIP, std::string("noise profile launch: ") + hipGetErrorString(e));
+        }
+        ctx->last_kernel = "tls_noise_profile";
+        TLS_HIP(ctx, hipMemcpyAsync(out_curves + k0, d_records, rows * tlsdev::kNoiseWords * 8, hipMemcpyDeviceToHost, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(out_count + (size_t)k0 * W, d_count, rows * W * 8, hipMemcpyDeviceToHost, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(out_robust + (size_t)k0 * W, d_robust, rows * W * 8, hipMemcpyDeviceToHost, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(out_rms + (size_t)k0 * W, d_rms, rows * W * 8, hipMemcpyDeviceToHost, ctx->stream));
+        TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));       // (the next slab overwrites the device buffers; w32 lives until here)
+    }
     return TLS_OK;
 }
 

@@ -75,7 +75,7 @@
 
 namespace tlsdev {
 
-constexpr int kChecks = 16;   // slots of SearchArgs::check
+constexpr int kChecks = 17;   // slots of SearchArgs::check
 enum CheckCode {
     kChkLdsCarve = 0,      // header + regions exceed the dynamic LDS of the launch
     kChkListCap = 1,       // a live-unit list outgrew its row's slots
@@ -94,6 +94,7 @@ enum CheckCode {
     kChkShape = 14,        // tls_shape_fit: a member's rank or a unit's table index outside its limits; tls_centroid_test: a
                            // shape or an epoch count outside the entry's limits, or an epoch's head outside the series
     kChkViews = 15,        // tls_folded_views: a bin's range outside its part, a member outside the series, or no single middle member
+    kChkNoise = 16,        // tls_noise_profile: a width or a window outside the row, a rank outside its bins, or a count above its windows
 };
 
 constexpr int kWave = 64;
@@ -4449,5 +4450,7 @@ __global__ void __launch_bounds__(512) tls_transit_models(const ModelsArgs a) {
 #include "tls_phase_scan.hip.h"
 // survey-mode ephemeris match across the candidates of a batch (tls_ephemeris_match)
 #include "tls_match.hip.h"
+// survey-mode per-star noise profile (tls_noise_profile)
+#include "tls_noise.hip.h"
 
 }  // namespace tlsdev

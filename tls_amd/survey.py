@@ -460,7 +460,7 @@ def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_ar
                 event_vetting_search=1.0, event_vetting_chase_window=0.1, event_vetting_guard=1.5, event_vetting_min_ses=3.0,
                 event_vetting_chase_fraction=0.6, event_vetting_chase_min=0.5, event_vetting_point_fraction=0.5,
                 event_vetting_step_fraction=0.5, centroids=None, centroid_window=3.0, centroid_min_in=1,
-                centroid_min_out=3, **power_kwargs):
+                centroid_min_out=3, noise=None, **power_kwargs):
     """Survey-mode power(): for every light curve of `flux_batch` what `transitleastsquares(t, flux).power(**kwargs)`
     reports as SDE, SDE_raw, chi2_min, period, T0, depth and duration (fractional, lc_cache_overview["duration"] of
     the template row at the chi^2 minimum, main.py:199-200) -- search, SDE spectra and final T0 fit all on the
@@ -593,6 +593,15 @@ def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_ar
     status != 0).  Everything else of the result stays as it is, bit for bit.  centroids without peak_fits, of another shape
     than flux_batch, or with a bad parameter, raises ValueError before any device work.
 
+    noise=True (with peak_fits=True), or noise=widths (samples), measures the noise profile of every curve -- a robust CDPP at
+    the Kepler pulse durations (noise_widths(t)) or at the given widths (noise_profile below states it, with its defaults for
+    the clips, gap_tolerance and min_count) -- in one call of tls_noise_profile behind the search, on the device that searched
+    the curve and on the rows it searched.  The peaks dict gains `noise`, the dict noise_profile returns, and the `peaks`
+    array, behind every other group, noise_width (the profile width nearest duration_days / cadence, the smaller one on a
+    tie), noise_sigma (robust at that width) and noise_mes = depth_mean * sqrt(transit_count) / noise_sigma, formed on the
+    host; NaN, and noise_width -1, where status != 0 or noise_sigma is NaN.  Everything else of the result stays as it is,
+    bit for bit.  noise without peak_fits, or with bad widths, raises ValueError before any device work.
+
     Returns (summary, periods[, chi2, row, depth, power][, per_transit][, models][, peaks]): summary is a numpy structured
     array with the fields of tls_power_summary plus "duration" (and the statistics on request)."""
     return _power_batch(t, flux_batch, dy_batch, power_kwargs, context=context, device=device, devices=devices,
@@ -615,7 +624,8 @@ def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_ar
                                                              event_vetting_chase_min, event_vetting_point_fraction,
                                                              event_vetting_step_fraction),
                         centroids=_centroid_request(centroids, peak_fits, numpy.shape(flux_batch), centroid_window,
-                                                    centroid_min_in, centroid_min_out))
+                                                    centroid_min_in, centroid_min_out),
+                        noise=_noise_request(noise, peak_fits, t))
 
 
 def _peaks_request(peaks, separation, ratios, min_power, models=False, peak_fits=False):
@@ -776,7 +786,7 @@ def find_peaks(power, periods, k, separation=0.02, ratios=HARMONICS, min_power=N
 def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=None, devices=None, with_arrays=False,
                  statistics=False, per_transit=False, models=False, spectra=False, detrend=None, peaks=None,
                  peak_fits=False, phase_scan=None, transit_times=None, shape_fit=None, sine_test=None, ephemeris_match=None,
-                 views=None, event_vetting=None, centroids=None):
+                 views=None, event_vetting=None, centroids=None, noise=None):
     """power_batch; spectra=True (power_results) also returns SR and power_raw [n_curves, n_periods] behind the arrays;
     peaks: None or a checked request (_peaks_request); peak_fits: with peaks, their T0 fits and statistics; phase_scan: None or a checked
     request (_phase_scan_request), with peak_fits, the fits' phase scans; transit_times: None or a checked request
@@ -785,7 +795,8 @@ def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=Non
     with peak_fits, the fits' sine tests; ephemeris_match: None or a checked request (_ephemeris_match_request), with
     peak_fits, the match of the fitted peaks across the curves; views: None or a checked request (_views_request), with
     peak_fits, the fits' folded views; event_vetting: None or a checked request (_event_vetting_request), with peak_fits, the
-    fits' event vetting; centroids: None or a checked request (_centroid_request), with peak_fits, the fits' centroid tests."""
+    fits' event vetting; centroids: None or a checked request (_centroid_request), with peak_fits, the fits' centroid tests;
+    noise: None or a checked request (_noise_request), with peak_fits, the curves' noise profiles."""
     models = bool(models)
     per_transit = bool(per_transit or models)
     statistics = bool(statistics or per_transit)
@@ -844,6 +855,11 @@ def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=Non
             # (the centroid rows of the curves this device searched, beside their flux rows)
             part["centroid_tests"] = _peak_centroid_tests(ctx, inp, y_rows[lo:hi], centroids["cx"][lo:hi], centroids["cy"][lo:hi],
                                                           part["peaks"], part["peak_fits"], centroids, cen_epochs)
+        if noise is not None:
+            # (the same context, the same rows: the profile of what was searched)
+            part["noise_curves"], part["noise_count"], part["noise_robust"], part["noise_rms"] = ctx.noise_profile(
+                inp["t"], y_rows[lo:hi], noise["widths"], noise["span_max"], noise["pair_span"], NOISE_CLIP, NOISE_CLIP,
+                NOISE_MIN_COUNT)
         return part
 
     out = _run_batch(devices, device, context, len(y_rows), call)
@@ -922,6 +938,11 @@ def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=Non
             found["events"] = out["ev_events"]
         if centroids is not None:
             found["peaks"] = _with_centroids(found["peaks"], out["centroid_tests"])
+        if noise is not None:
+            found["noise"] = dict(widths=noise["widths"], curves=out["noise_curves"], count=out["noise_count"],
+                                  robust=out["noise_robust"], rms=out["noise_rms"],
+                                  beta=_noise_beta(out["noise_robust"], noise["widths"], out["noise_curves"]["sigma"]))
+            found["peaks"] = _with_noise(found["peaks"], found["noise"], noise["cadence"])
         result += (found,)
     if spectra:
         result += (out["SR"], out["power_raw"])
@@ -2265,6 +2286,173 @@ def ephemeris_groups(records):
 
 
 # ---- injection-recovery ---------------------------------------------------------------------------------------------------
+# ---- the per-star noise profile ------------------------------------------------------------------------------------------------
+# the 14 pulse durations (hours) of Kepler's rms CDPP table
+KEPLER_PULSE_HOURS = (1.5, 2.0, 2.5, 3.0, 3.5, 4.5, 5.0, 6.0, 7.5, 9.0, 10.5, 12.0, 12.5, 15.0)
+NOISE_CLIP = 5.0
+NOISE_GAP_TOLERANCE = 0.5
+NOISE_MIN_COUNT = 3
+
+
+def noise_curve_fields():
+    """The fields of the per-curve record of a noise profile, in order: status (0 measured; 1 sigma == 0: a constant row, or
+    more than half of it on one value), n_clipped, n_pairs, median, sigma (1.4826 * MAD) and sigma_p2p (the point-to-point
+    sigma of the kept neighbours)."""
+    from ._lib import NOISE_CURVE_FIELDS
+    return NOISE_CURVE_FIELDS
+
+
+def _noise_cadence(t, what="noise profile"):
+    """(t as float64, numpy.median(numpy.diff(t))): ValueError unless t is [n >= 3], finite and ascending with a cadence > 0."""
+    try:
+        t = numpy.asarray(t, dtype=numpy.float64)
+    except (TypeError, ValueError):
+        raise ValueError("%s: t must hold numbers" % what)
+    if t.ndim != 1 or len(t) < 3 or not numpy.all(numpy.isfinite(t)) or not numpy.all(t[1:] >= t[:-1]):
+        raise ValueError("%s: t must be [n] with n >= 3, finite and ascending" % what)
+    cadence = numpy.median(numpy.diff(t))
+    if not 0.0 < cadence < numpy.inf:
+        raise ValueError("%s: the median cadence of t must be finite and > 0, got %r" % (what, cadence))
+    return t, cadence
+
+
+def noise_widths(t, hours=KEPLER_PULSE_HOURS):
+    """The default window widths (samples) of noise_profile on the time stamps t: max(1, round(h / 24 / cadence)) for every h
+    of `hours` (by default the 14 Kepler pulse durations) and 1, unique and ascending, cut at min(n, NOISE_MAX_WIDTH);
+    cadence = numpy.median(numpy.diff(t)).  At 30 min that is 1, 3, 4, 5, 6, 7, 9, 10, 12, 15, 18, 21, 24, 25, 30.  ValueError
+    for a t that is not [n >= 3], finite and ascending with a cadence > 0, and for hours that are not finite and > 0."""
+    from ._lib import NOISE_MAX_WIDTH
+    t, cadence = _noise_cadence(t)
+    try:
+        hours = numpy.atleast_1d(numpy.asarray(hours, dtype=numpy.float64))
+    except (TypeError, ValueError):
+        raise ValueError("noise profile: hours must hold numbers")
+    if hours.ndim != 1 or not numpy.all(numpy.isfinite(hours) & (hours > 0.0)):
+        raise ValueError("noise profile: every pulse duration must be finite and > 0 hours")
+    widths = {1} | {max(1, int(round(float(h) / 24.0 / float(cadence)))) for h in hours}
+    top = min(len(t), NOISE_MAX_WIDTH)
+    return numpy.array(sorted(w for w in widths if w <= top), dtype=numpy.int64)
+
+
+def _noise_spans(t, widths, gap_tolerance):
+    """(span_max [W], pair_span) of noise_profile: (w - 1 + gap_tolerance) * cadence for every width and
+    (1 + gap_tolerance) * cadence, the adjacency limit of the point-to-point sigma; all inf without t."""
+    if isinstance(gap_tolerance, (bool, numpy.bool_)) or not isinstance(gap_tolerance, numbers.Real) or not 0.0 <= float(gap_tolerance) < numpy.inf:
+        raise ValueError("noise profile: gap_tolerance must be finite and >= 0, got %r" % (gap_tolerance,))
+    try:
+        count = len(numpy.atleast_1d(numpy.asarray(widths)))
+        steps = [numpy.float64(int(w) - 1) for w in numpy.atleast_1d(numpy.asarray(widths))]
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("noise profile: the widths must be integers, got %r" % (widths,))
+    if t is None:
+        return numpy.full(count, numpy.inf), numpy.inf
+    t, cadence = _noise_cadence(t)
+    g = numpy.float64(gap_tolerance)
+    return numpy.array([(s + g) * cadence for s in steps], dtype=numpy.float64).reshape(count), float((numpy.float64(1.0) + g) * cadence)
+
+
+def _noise_beta(robust, widths, sigma):
+    """robust * sqrt(w) / sigma: 1 for white noise, larger with red noise."""
+    with numpy.errstate(all="ignore"):
+        return robust * numpy.sqrt(numpy.asarray(widths, dtype=numpy.float64)) / numpy.asarray(sigma)[..., None]
+
+
+def noise_profile(flux_batch, t=None, widths=None, clip_upper=NOISE_CLIP, clip_lower=NOISE_CLIP, gap_tolerance=NOISE_GAP_TOLERANCE,
+                  min_count=NOISE_MIN_COUNT, detrend=None, context=None, device=None, devices=None):
+    """How noisy is every star on the time scale of a transit: a robust CDPP at the window widths `widths` (samples; None:
+    noise_widths(t), the Kepler pulse durations), of every light curve of flux_batch [n_curves, n] (or one row [n]) on the
+    shared ascending time stamps t (None: no gaps), on the device (tls_noise_profile).  K = 1.4826022185056018:
+
+        m = median(y);  d = y - m;  sigma = K median(|d|);  sigma == 0: status 1, everything else NaN / 0
+        keep = (d <= clip_upper sigma) and (d >= -clip_lower sigma): ONE pass, internal to the measurement (a deep eclipse
+            does not inflate the profile; no row that is searched changes); inf switches a side off
+        sigma_p2p = K median(|y_{j+1} - y_j|) / sqrt(2) over the kept neighbours at most (1 + gap_tolerance) cadences apart
+        width w: v_i = the mean of d over the samples [i, i + w), valid when all are kept and t[i + w - 1] - t[i] <=
+            (w - 1 + gap_tolerance) cadence;  count = the valid windows;  count < min_count: NaN
+            robust = K median(|v - median(v)|);  rms = the standard deviation of v;  beta = robust sqrt(w) / sigma
+
+    robust is the noise a transit of w samples competes with (depth sqrt(n_transits) / robust is its expected detection
+    statistic), rms the same without the robustness (a transit inflates it), beta 1 for white noise and larger with red
+    noise.  cadence = numpy.median(numpy.diff(t)).  The device equals the numpy statement in tests/noise_profile_spec.py bit
+    for bit.  detrend= takes the steps and tuples of search_batch (a Biweight or a Prewhiten needs t), devices=[...] deals the
+    curves out over several GPUs.  ValueError, before any device work (the detrending included), for non-finite input, a t
+    that is not ascending, n < 3, widths that are not integers, not strictly ascending, below 1, above n or above
+    NOISE_MAX_WIDTH, a negative or NaN clip, min_count < 1, widths=None without t and shapes that disagree.
+
+    Returns a dict: widths [W]; curves, a structured array [n_curves] with noise_curve_fields(); count (int64), robust, rms
+    and beta [n_curves, W].  One row gives one record and [W]."""
+    from ._lib import noise_arguments
+    if widths is None:
+        if t is None:
+            raise ValueError("noise profile: widths=None takes the Kepler pulse durations at the cadence of t, so it needs t")
+        widths = noise_widths(t)
+    one = numpy.ndim(flux_batch) == 1
+    span_max, pair_span = _noise_spans(t, widths, gap_tolerance)
+    a = noise_arguments(t, flux_batch, widths, span_max, pair_span, clip_upper, clip_lower, min_count)
+    rows = a["y"]
+    if _detrend_steps(detrend):
+        if a["t"] is None and any(isinstance(step, (Biweight, Prewhiten)) for step in _detrend_steps(detrend)):
+            raise ValueError("noise profile: a Biweight or a Prewhiten step of detrend needs t")
+        axis = a["t"] if a["t"] is not None else numpy.arange(rows.shape[1], dtype=numpy.float64)
+        rows = _detrended(axis, rows, detrend, context, device, devices)
+
+    def call(ctx, lo, hi):
+        curves, count, robust, rms = ctx.noise_profile(a["t"], rows[lo:hi], a["widths"], a["span_max"], a["pair_span"],
+                                                       a["clip_upper"], a["clip_lower"], a["min_count"])
+        return dict(curves=curves, count=count, robust=robust, rms=rms)
+
+    out = dict(_run_batch(devices, device, context, len(rows), call))
+    out["beta"] = _noise_beta(out["robust"], a["widths"], out["curves"]["sigma"])
+    if one:
+        out = {k: v[0] for k, v in out.items()}
+    out["widths"] = a["widths"]
+    return out
+
+
+def _noise_request(noise, peak_fits, t):
+    """None, or the checked request of noise=True (noise_widths(t)) or noise=widths of power_batch: a dict with widths,
+    span_max, pair_span and cadence (ValueError for a bad one, and for noise without peak_fits)."""
+    if noise is None or noise is False:
+        return None
+    if not peak_fits:
+        raise ValueError("noise needs peak_fits=True: noise_mes is formed from depth_mean and transit_count of the fits")
+    from ._lib import noise_arguments
+    t, cadence = _noise_cadence(t)
+    widths = noise_widths(t) if noise is True else noise
+    span_max, pair_span = _noise_spans(t, widths, NOISE_GAP_TOLERANCE)
+    a = noise_arguments(t, numpy.ones((1, len(t))), widths, span_max, pair_span, NOISE_CLIP, NOISE_CLIP, NOISE_MIN_COUNT)
+    return dict(widths=a["widths"], span_max=a["span_max"], pair_span=a["pair_span"], cadence=float(cadence))
+
+
+def noise_width_index(duration_days, cadence, widths):
+    """The index of the profile width nearest duration_days / cadence, the smaller one on a tie; -1 where the duration is not
+    finite."""
+    x = numpy.asarray(duration_days, dtype=numpy.float64) / numpy.float64(cadence)
+    w = numpy.asarray(widths, dtype=numpy.float64)
+    with numpy.errstate(invalid="ignore"):
+        index = numpy.argmin(numpy.fabs(w - x[..., None]), axis=-1)   # (the first of equals: the smaller width)
+    return numpy.where(numpy.isfinite(x), index, -1)
+
+
+def _with_noise(records, profile, cadence):
+    """The peaks plus noise_width (the profile width nearest duration_days / cadence, the smaller one on a tie), noise_sigma
+    (robust at that width) and noise_mes = depth_mean * sqrt(transit_count) / noise_sigma; NaN, and noise_width -1, where
+    status != 0 or noise_sigma is NaN."""
+    out = numpy.zeros(records.shape, dtype=records.dtype.descr + [("noise_width", "f8"), ("noise_sigma", "f8"), ("noise_mes", "f8")])
+    for k in records.dtype.names:
+        out[k] = records[k]
+    index = noise_width_index(records["duration_days"], cadence, profile["widths"])
+    curve = numpy.arange(records.shape[0])[:, None]
+    sigma = numpy.where(index >= 0, profile["robust"][curve, numpy.maximum(index, 0)], numpy.nan)
+    good = (records["status"] == 0) & (index >= 0) & ~numpy.isnan(sigma)
+    with numpy.errstate(all="ignore"):
+        mes = records["depth_mean"] * numpy.sqrt(records["transit_count"]) / sigma
+    out["noise_width"] = numpy.where(good, profile["widths"][numpy.maximum(index, 0)], -1)
+    out["noise_sigma"] = numpy.where(good, sigma, numpy.nan)
+    out["noise_mes"] = numpy.where(good, mes, numpy.nan)
+    return out
+
+
 INJECTION_FIELDS = ("T0", "period", "rp_rs", "a", "inc")
 INJECTION_LAWS = ("quadratic", "linear", "uniform")
 
