@@ -118,6 +118,10 @@ int tls_set_options(tls_ctx *ctx, const tls_options *opt);
  * layout and its fast-mode dense predicate: 0 the former forms), claim_ahead (the tickets of its period queue: bit 0 a
  * workgroup's first ticket is its index; 0 every ticket is drawn from the queue word).  A context starts with the values
  * of the TLS_<NAME> environment variables, read once per process; no call reads the environment after that.
+ * One more name, `lanes`, is no planning switch (no part of a plan's key, of tls_debug_get_switches' text or of the
+ * environment): 0 sends every search launch to lane A, one after the other on one stream; default on -- back-to-back
+ * tls_execute calls of a filled four-slot plan alternate between two launch lanes.  It changes where
+ * a launch runs, never a result.
  * tls_debug_get_switches writes all of them as "name=value,name=value" (ctx NULL: the process's) -- the text
  * tls_period_costs takes, so that the planning call prices the kernel the searching context will run. */
 int tls_debug_set_switch(tls_ctx *ctx, const char *name, double value);
@@ -204,6 +208,13 @@ int tls_debug_device_bytes(const tls_ctx *ctx, int64_t *total, int64_t *t0_fit_s
  * in bytes as the held plan uses it (0: the plan has none; the buffer behind it only grows and is counted by tls_debug_device_bytes) and whether a launch has filled it (1) or the next four-slot launch will (0); plan_reuses
  * (may be NULL): the tls_prepare calls the context has answered from a held plan, which keep the table */
 int tls_debug_perm_table(const tls_ctx *ctx, int64_t *bytes, int64_t *filled, int64_t *plan_reuses);
+/* developer instrumentation: search launches the context has sent to launch lane A and to launch lane B so far (host-side
+ * counters), and whether the lanes are on (switch `lanes`; on may be NULL) */
+int tls_debug_lanes(const tls_ctx *ctx, int64_t *lane_a, int64_t *lane_b, int64_t *on);
+/* developer instrumentation: what tls_kernel_timing charges each launch it holds (ms, oldest slot of its ring of 64 first):
+ * a launch's own event pair, or for an overlapped launch the shorter of that and the time from the end of the launch before
+ * it to its own end.  Waits for both lanes.  Returns the number of launches (negative: an error); out may be NULL. */
+int tls_debug_launch_ms(tls_ctx *ctx, double *out, int64_t capacity);
 /* Test entry: the raw Philox words tls_null_rows draws for trials first_trial .. first_trial + n_rows - 1 with the same
  * (n, seed, mode, block): out [n_rows][W], W = the mode's words per trial rounded up to a multiple of 4 (the last W - words
  * of a row are drawn but not used).  The arguments are checked as tls_null_rows checks them. */

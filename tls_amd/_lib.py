@@ -109,7 +109,7 @@ SYMBOLS = (
     "tls_device_count", "tls_ctx_create", "tls_ctx_destroy", "tls_last_error", "tls_version", "tls_abi_version",
     "tls_device_name", "tls_get_options", "tls_set_options", "tls_debug_set_switch", "tls_debug_get_switches", "tls_search", "tls_search_batch", "tls_power_batch", "tls_prepare", "tls_update_flux", "tls_execute",
     "tls_synchronize", "tls_fetch", "tls_execute_timed", "tls_plan_info", "tls_last_kernel", "tls_grid_cells", "tls_period_costs", "tls_debug_candidate_slabs", "tls_t0_fit", "tls_pink_noise", "tls_spectra", "tls_kernel_timing", "tls_debug_phase_cycles", "tls_debug_cumsum", "tls_debug_folded", "tls_debug_prefix", "tls_debug_check_counts", "tls_debug_poison_lds", "tls_debug_period_cycles", "tls_debug_batch_group_ms",
-    "tls_debug_post_search", "tls_debug_device_bytes", "tls_debug_perm_table", "tls_power_batch_stats", "tls_debug_transit_stats",
+    "tls_debug_post_search", "tls_debug_device_bytes", "tls_debug_perm_table", "tls_debug_lanes", "tls_debug_launch_ms", "tls_power_batch_stats", "tls_debug_transit_stats",
     "tls_power_batch_models", "tls_debug_transit_models",
     "tls_inject_transits", "tls_null_rows", "tls_debug_null_words", "tls_medfilt_detrend",
     "tls_biweight_detrend", "tls_sysrem", "tls_find_peaks", "tls_power_batch_peaks", "tls_power_batch_peak_fits", "tls_debug_peak_fits",
@@ -146,7 +146,7 @@ class Options(ctypes.Structure):
 # every switch tls_debug_set_switch knows (the two public ones included): Context.set_options(**switches) takes them all
 SWITCH_NAMES = ("exact_prefix", "slim", "prune", "screen32", "no_screen", "fast_slab", "x_staged", "split", "split_batch", "sort2",
                 "threads", "blocks", "plan_threads", "t0_rot", "prune_min_live", "perm_table", "reg_scan", "dense_hoist",
-                "claim_ahead", "band_max")
+                "claim_ahead", "band_max", "lanes")
 
 
 def switches_text(switches):
@@ -1237,6 +1237,11 @@ def load():
     lib.tls_debug_device_bytes.argtypes = [vp, _c_int64_p, _c_int64_p]
     lib.tls_debug_perm_table.restype = ci
     lib.tls_debug_perm_table.argtypes = [vp, _c_int64_p, _c_int64_p, _c_int64_p]
+    if hasattr(lib, "tls_debug_lanes"):   # (an A/B run against a library built from older sources has none)
+        lib.tls_debug_lanes.restype = ci
+        lib.tls_debug_lanes.argtypes = [vp, _c_int64_p, _c_int64_p, _c_int64_p]
+        lib.tls_debug_launch_ms.restype = ci
+        lib.tls_debug_launch_ms.argtypes = [vp, _c_double_p, i64]
     lib.tls_debug_cumsum.restype = ci
     lib.tls_debug_cumsum.argtypes = [vp, _c_double_p, i64, _c_double_p, ci]
     lib.tls_grid_cells.restype = ci
@@ -2279,6 +2284,25 @@ class Context(object):
         size, filled, reuses = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
         self._check(self._lib.tls_debug_perm_table(self._h, ctypes.byref(size), ctypes.byref(filled), ctypes.byref(reuses)))
         return {"bytes": int(size.value), "filled": bool(filled.value), "plan_reuses": int(reuses.value)}
+
+    def lanes(self):
+        """Search launches the context has sent to launch lane A (`a`) and lane B (`b`) so far, and whether the lanes are
+        `on` (switch `lanes`): back-to-back execute() calls of a filled four-slot plan alternate between the two."""
+        a, b, on = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        self._check(self._lib.tls_debug_lanes(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(on)))
+        return {"a": int(a.value), "b": int(b.value), "on": bool(on.value)}
+
+    def launch_ms(self):
+        """What kernel_timing charges each launch it holds, in ms: an overlapped launch is charged the shorter of its own
+        event pair and the time from the end of the launch before it to its own end."""
+        n = self._lib.tls_debug_launch_ms(self._h, None, 0)
+        if n < 0:
+            self._check(n)
+        out = numpy.zeros(max(n, 1), dtype=numpy.float64)
+        n = self._lib.tls_debug_launch_ms(self._h, _dp(out), len(out))
+        if n < 0:
+            self._check(n)
+        return out[:n]
 
     def folded(self, n_periods, n):
         """Developer/test entry: the folded flux of every period of the prepared plan, (n_periods, n), as the

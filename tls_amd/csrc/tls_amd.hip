@@ -32,6 +32,11 @@ using namespace tlsplan;
 namespace {
 
 constexpr size_t kEventRing = 64;   // launch-timing event pairs kept per context
+// what a new context's switch `lanes` starts as (A/B builds: make variant NAME=nolanes DEFS=-DTLS_LANES_DEFAULT=0 runs an
+// unchanged bench.py with every launch on lane A)
+#ifndef TLS_LANES_DEFAULT
+#define TLS_LANES_DEFAULT -1
+#endif
 
 std::string g_create_error;  // tls_last_error(NULL)
 
@@ -140,12 +145,45 @@ struct PlanKey {
     Switches opt;
 };
 
+// Lane B of a context (tls_ctx::lane_b; DESIGN.md section 4, "Launch lanes"): a second stream and a second set of exactly
+// what an overlappable four-slot launch writes, and of the flux.  Allocated at lane B's first use.
+struct LaneB {
+    hipStream_t stream = nullptr;
+    DevBuf<unsigned int> d_squeue, d_lists, d_perm;
+    DevBuf<double> d_out, d_y;            // [chi2 | row | depth | counters[4]]; the flux
+    unsigned char* h_stage = nullptr; size_t h_stage_cap = 0;   // pinned: the flux on its way to d_y
+    hipEvent_t ev_stage = nullptr; bool stage_pending = false;   // ... and its last upload
+    hipEvent_t ev_done = nullptr;         // behind the last command on `stream` (launch or upload)
+    bool outstanding = false;             // ev_done is recorded and lane A has not waited for it
+    bool saw_state = false;               // `stream` has waited for the latest record of ev_state
+};
+
 }  // namespace
 
 struct tls_ctx {
     int device = 0;
-    hipStream_t stream = nullptr;
+    // Lane A's stream: the context's one stream for everything but a lane-B launch and its flux.  Every use outside the
+    // lane path goes through main_stream(ctx), which first orders the stream behind lane B (join) -- hence the name no
+    // other code spells.
+    hipStream_t lane_a_stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    // Launch lanes: back-to-back plain four-slot searches of a plan whose table of folded orders is
+    // filled alternate between lane A (the buffers below, as ever) and lane B -- a second stream and a second set of
+    // exactly what such a launch writes (queue words, live-unit lists with the band list, stashed orders, results) and of
+    // the flux --, so that search i+1 starts on the compute units search i has already left.  Lane B's buffers are
+    // allocated at its first use (a context that never overlaps holds none of them).
+    LaneB lane_b;
+    hipEvent_t ev_state = nullptr;            // lane A's state a lane-B command must see: uploads, the filling launch, consumers
+    bool state_dirty = true;                  // lane A's stream got a command other than an overlapped launch since ev_state's record
+    int lanes = TLS_LANES_DEFAULT;            // developer switch `lanes` (0: every launch on lane A); not part of the plan key
+    int run_lane = -1;                        // lane of the previous launch if it was an overlappable one and nothing but tls_update_flux came since; else -1
+    int result_lane = 0;                      // lane whose results d_latest / d_chi2 / d_row / d_depth / d_counters denote: the LATEST launch's
+    int flux_lane = 0;                        // lane whose flux buffer d_y denotes: the flux of the NEXT launch
+    bool flux_b_unseen = false;               // lane B's flux was uploaded and lane A's stream has not waited for that
+    bool a_reads_flux_b = false, b_reads_flux_a = false;   // a launch read the OTHER lane's flux, and that lane's stream is not yet ordered behind it
+    bool perm_filled_before_prev = false;     // perm_filled as the previous launch found it
+    int64_t lane_launches[2] = {0, 0};        // launches sent to each lane (tls_debug_lanes)
+    View<double> d_y_a;                       // lane A's flux (inside d_plan)
     std::string err;
     std::string name;
     int n_cu = 0;
@@ -161,8 +199,10 @@ struct tls_ctx {
     View<tlsdev::RowScreen> d_screens;
     unsigned char* h_stage = nullptr; size_t h_stage_cap = 0;   // pinned: the plan (tls_prepare) / the flux (tls_update_flux)
     hipEvent_t ev_stage = nullptr; bool stage_pending = false;  // its last upload
-    // results: [chi2 | row | depth | counters[4]] in one allocation, fetched by one copy into pinned memory
+    // results: [chi2 | row | depth | counters[4]] in one allocation, fetched by one copy into pinned memory.  d_out is
+    // lane A's allocation; the views denote the results of the LATEST launch, whichever lane it took (point_results)
     DevBuf<double> d_out;
+    View<double> d_latest;
     View<double> d_chi2, d_depth;
     View<long long> d_row;
     View<unsigned long long> d_counters;
@@ -271,8 +311,9 @@ struct tls_ctx {
     tls_counters plan_counters = {0, 0, 0, 0, 0};
     bool counted = false;
 
-    // per-launch kernel timing (HIP events on the context's stream)
+    // per-launch kernel timing (HIP events on the launch's stream)
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
+    std::vector<char> ev_overlapped;   // [ring slot] the launch may have begun before the one in the slot before it ended
     size_t ev_used = 0;
 
     // RCCL
@@ -305,6 +346,42 @@ int fail(tls_ctx* ctx, int code, const std::string& msg) {
             return fail(ctx, TLS_E_RCCL, std::string(#call) + ": " + ncclGetErrorString(r_)); \
     } while (0)
 
+// ---- launch lanes: ordering -------------------------------------------------------------------------------------------
+// Every wait names an event recorded EARLIER in host order, so the dependencies form a DAG: nothing can wait on itself.
+
+// lane A's stream ordered behind everything lane B has been given; costs nothing when lane B has nothing outstanding
+void lanes_join(tls_ctx* ctx) {
+    auto& lb = ctx->lane_b;
+    if (lb.outstanding) {
+        if (hipStreamWaitEvent(ctx->lane_a_stream, lb.ev_done, 0) != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipStreamSynchronize(lb.stream);   // (the host waits instead: always right)
+        }
+        lb.outstanding = false;
+    }
+    ctx->flux_b_unseen = false; ctx->b_reads_flux_a = false;
+}
+
+// The context's stream for every command outside the lane path: joined, and the command that follows ends the run of
+// overlappable launches (the next search takes lane A) and is something lane B's next command has to see.
+hipStream_t main_stream(tls_ctx* ctx) {
+    lanes_join(ctx);
+    ctx->run_lane = -1;
+    ctx->state_dirty = true;
+    return ctx->lane_a_stream;
+}
+
+// the results the views denote: those of `lane`
+void point_results(tls_ctx* ctx, int lane) {
+    double* base = lane ? ctx->lane_b.d_out.ptr : ctx->d_out.ptr;
+    const size_t np = (size_t)ctx->plan.n_periods;
+    ctx->d_latest.ptr = base;
+    ctx->d_chi2.ptr = base; ctx->d_row.ptr = reinterpret_cast<long long*>(base + np);
+    ctx->d_depth.ptr = base + 2 * np;
+    ctx->d_counters.ptr = reinterpret_cast<unsigned long long*>(base + 3 * np);
+    ctx->result_lane = lane;
+}
+
 // the pinned staging buffer, at least `bytes` long and no longer read by an upload in flight
 int stage_reserve(tls_ctx* ctx, size_t bytes) {
     if (!ctx->ev_stage) TLS_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_stage, hipEventDisableTiming));
@@ -323,7 +400,7 @@ int stage_reserve(tls_ctx* ctx, size_t bytes) {
 int ensure_check_counters(tls_ctx* ctx) {
     if (ctx->d_check.ptr) return TLS_OK;
     TLS_HIP(ctx, ctx->d_check.reserve(tlsdev::kChecks));
-    TLS_HIP(ctx, hipMemsetAsync(ctx->d_check.ptr, 0, tlsdev::kChecks * sizeof(unsigned long long), ctx->stream));
+    TLS_HIP(ctx, hipMemsetAsync(ctx->d_check.ptr, 0, tlsdev::kChecks * sizeof(unsigned long long), main_stream(ctx)));
     return TLS_OK;
 }
 
@@ -392,7 +469,7 @@ template <typename T>
 int upload(tls_ctx* ctx, DevBuf<T>& buf, const T* host, size_t count) {
     TLS_HIP(ctx, buf.reserve(count));
     if (count)
-        TLS_HIP(ctx, hipMemcpyAsync(buf.ptr, host, count * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(buf.ptr, host, count * sizeof(T), hipMemcpyHostToDevice, main_stream(ctx)));
     return TLS_OK;
 }
 
@@ -623,7 +700,7 @@ hipError_t launch_split(tls_ctx* ctx, const tlsdev::SearchArgs& args, int blocks
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->plan.lds_bytes);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3((unsigned)ctx->plan.threads), ctx->plan.lds_bytes,
-                       ctx->stream, args);
+                       main_stream(ctx), args);
     return hipGetLastError();
 }
 
@@ -634,7 +711,7 @@ hipError_t launch_variant(tls_ctx* ctx, const tlsdev::SearchArgs& args, int bloc
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->plan.lds_bytes);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3((unsigned)ctx->plan.threads), ctx->plan.lds_bytes,
-                       ctx->stream, args);
+                       main_stream(ctx), args);
     return hipGetLastError();
 }
 
@@ -647,14 +724,69 @@ hipError_t timing_pair(tls_ctx* ctx, std::pair<hipEvent_t, hipEvent_t>** out) {
         if ((e = hipEventCreate(&a)) != hipSuccess || (e = hipEventCreate(&b)) != hipSuccess) return e;
         ctx->ev_pool.emplace_back(a, b);
     }
+    ctx->ev_overlapped.resize(kEventRing, 0);
+    ctx->ev_overlapped[ctx->ev_used % kEventRing] = 0;
     *out = &ctx->ev_pool[ctx->ev_used++ % kEventRing];
     return hipSuccess;
 }
 
+// lane B's stream, events and buffers, sized for the plan the context holds (first use, or a larger plan since)
+int ensure_lane_b(tls_ctx* ctx) {
+    auto& lb = ctx->lane_b;
+    if (!lb.stream) TLS_HIP(ctx, hipStreamCreateWithFlags(&lb.stream, hipStreamNonBlocking));
+    if (!lb.ev_done) TLS_HIP(ctx, hipEventCreateWithFlags(&lb.ev_done, hipEventDisableTiming));
+    if (!lb.ev_stage) TLS_HIP(ctx, hipEventCreateWithFlags(&lb.ev_stage, hipEventDisableTiming));
+    if (!lb.d_squeue.ptr) {   // zero once: the kernel rewinds its queue itself
+        TLS_HIP(ctx, lb.d_squeue.reserve(4));
+        TLS_HIP(ctx, hipMemsetAsync(lb.d_squeue.ptr, 0, 4 * sizeof(unsigned int), lb.stream));
+    }
+    TLS_HIP(ctx, lb.d_lists.reserve(ctx->d_lists.cap));
+    TLS_HIP(ctx, lb.d_perm.reserve(ctx->d_perm.cap));
+    TLS_HIP(ctx, lb.d_out.reserve(3 * (size_t)ctx->plan.n_periods + 4));
+    TLS_HIP(ctx, lb.d_y.reserve((size_t)ctx->plan.n));
+    return TLS_OK;
+}
+
+// lane B's next command sees lane A's state as of the latest record of ev_state
+int lane_b_see_state(tls_ctx* ctx) {
+    auto& lb = ctx->lane_b;
+    if (!lb.saw_state) {
+        TLS_HIP(ctx, hipStreamWaitEvent(lb.stream, ctx->ev_state, 0));
+        lb.saw_state = true;
+    }
+    return TLS_OK;
+}
+
+// lane: -1 a launch outside the lane path (lane A's buffers, behind everything: joined); 0 / 1 an overlappable launch on
+// lane A / lane B (tls_execute decides)
 int enqueue(tls_ctx* ctx, bool count_work, bool phase_clock = false, double* debug_folded = nullptr, double* debug_prefix = nullptr,
-            unsigned long long* period_cycles = nullptr) {
+            unsigned long long* period_cycles = nullptr, int lane = -1) {
+    auto& lb = ctx->lane_b;
+    hipStream_t stream = nullptr;
+    const bool filled_before = ctx->perm_filled;
+    const bool overlapped = lane >= 0 && ctx->run_lane >= 0;   // (the launch before it may still run when this one begins)
+    if (lane < 0) {
+        stream = main_stream(ctx);
+    } else if (lane == 0) {
+        stream = ctx->lane_a_stream;
+        if (ctx->state_dirty) {   // (covers the plan's uploads, the filling launch and every consumer so far; not this launch)
+            TLS_HIP(ctx, hipEventRecord(ctx->ev_state, stream));
+            ctx->state_dirty = false; lb.saw_state = false; ctx->a_reads_flux_b = false;
+        }
+        if (ctx->flux_lane == 1 && ctx->flux_b_unseen) {
+            TLS_HIP(ctx, hipStreamWaitEvent(stream, lb.ev_stage, 0));
+            ctx->flux_b_unseen = false;
+        }
+    } else {
+        if (int rc = ensure_lane_b(ctx)) return rc;
+        if (int rc = lane_b_see_state(ctx)) return rc;
+        stream = lb.stream;
+    }
+    if (ctx->flux_lane == 1 && lane != 1) ctx->a_reads_flux_b = true;
+    if (ctx->flux_lane == 0 && lane == 1) ctx->b_reads_flux_a = true;
+    point_results(ctx, lane == 1 ? 1 : 0);
     if (count_work)
-        TLS_HIP(ctx, hipMemsetAsync(ctx->d_counters.ptr, 0, 3 * sizeof(unsigned long long), ctx->stream));
+        TLS_HIP(ctx, hipMemsetAsync(ctx->d_counters.ptr, 0, 3 * sizeof(unsigned long long), stream));
     tlsdev::SearchArgs a;
     a.t = ctx->d_t.ptr; a.y = ctx->over_y ? ctx->over_y : ctx->d_y.ptr;
     a.w = ctx->plan.uniform ? nullptr : (ctx->over_w ? ctx->over_w : ctx->d_w.ptr);
@@ -671,7 +803,7 @@ int enqueue(tls_ctx* ctx, bool count_work, bool phase_clock = false, double* deb
     a.phase_cycles = nullptr;
     if (phase_clock) {
         TLS_HIP(ctx, ctx->d_phase.reserve(tlsdev::kPhases));
-        TLS_HIP(ctx, hipMemsetAsync(ctx->d_phase.ptr, 0, tlsdev::kPhases * sizeof(unsigned long long), ctx->stream));
+        TLS_HIP(ctx, hipMemsetAsync(ctx->d_phase.ptr, 0, tlsdev::kPhases * sizeof(unsigned long long), stream));
         a.phase_cycles = ctx->d_phase.ptr;
     }
     a.debug_folded = debug_folded; a.debug_prefix = debug_prefix; a.period_cycles = period_cycles;
@@ -680,12 +812,12 @@ int enqueue(tls_ctx* ctx, bool count_work, bool phase_clock = false, double* deb
     if (int rc = ensure_check_counters(ctx)) return rc;
     a.check = ctx->d_check.ptr;
 #endif
-    a.queue = ctx->d_squeue.ptr;
+    a.queue = lane == 1 ? lb.d_squeue.ptr : ctx->d_squeue.ptr;
     a.claim_ahead = 0;
     a.scratch = ctx->d_scratch.ptr;
     a.scratch_stride = (long long)(ctx->plan.uniform ? 2 : 3) * ((ctx->plan.M + 1 + ctx->plan.region_pad + 1) & ~1);   // even regions (kernel: RS)
     a.region_pad = ctx->plan.region_pad;
-    a.chunk_lists = ctx->d_lists.ptr; a.list_stride = 3 * (long long)ctx->plan.list_stride; a.list_cap = (long long)ctx->plan.list_stride;
+    a.chunk_lists = lane == 1 ? lb.d_lists.ptr : ctx->d_lists.ptr; a.list_stride = 3 * (long long)ctx->plan.list_stride; a.list_cap = (long long)ctx->plan.list_stride;
     a.prune_min_live = ctx->plan.prune_min_live; a.p2_shift = ctx->plan.p2_shift; a.hdr_bytes = ctx->plan.hdr_bytes; a.tile_len = ctx->plan.tile_len; a.tile_halo = ctx->plan.tile_halo;
     a.depth_min = ctx->depth_min; a.S0 = ctx->S0; a.w0 = ctx->w0;
     a.cumsum_round = ctx->plan.cumsum_round;
@@ -724,7 +856,7 @@ int enqueue(tls_ctx* ctx, bool count_work, bool phase_clock = false, double* deb
         // waited for (a survey changes sigma with every group of light curves: the launch in flight keeps reading its own slot).
         const size_t cnt = ctx->host_widths.size() + 1;
         if (ctx->h_band_cap < 2 * cnt) {
-            TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            TLS_HIP(ctx, hipStreamSynchronize(stream));
             if (ctx->h_band) TLS_HIP(ctx, hipHostFree(ctx->h_band));
             ctx->h_band = nullptr; ctx->h_band_cap = 0;
             TLS_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->h_band), 2 * cnt * sizeof(double), hipHostMallocDefault));
@@ -740,8 +872,8 @@ int enqueue(tls_ctx* ctx, bool count_work, bool phase_clock = false, double* deb
         band_prefix_for(ctx->host_widths, ctx->flux.sigma, ctx->depth_min, a.eps_fast, pre);
         std::memcpy(h, pre.data(), cnt * sizeof(double));
         ctx->d_band_now = ctx->d_band.ptr + (size_t)slot * cnt;
-        TLS_HIP(ctx, hipMemcpyAsync(ctx->d_band_now, h, cnt * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        TLS_HIP(ctx, hipEventRecord(ctx->ev_band[slot], ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(ctx->d_band_now, h, cnt * sizeof(double), hipMemcpyHostToDevice, stream));
+        TLS_HIP(ctx, hipEventRecord(ctx->ev_band[slot], stream));
         ctx->band_used[slot] = true;
         ctx->band_sigma = ctx->flux.sigma; ctx->band_eps = a.eps_fast;
     }
@@ -750,7 +882,7 @@ int enqueue(tls_ctx* ctx, bool count_work, bool phase_clock = false, double* deb
     a.n_curves = ctx->batch_curves;
     a.curve_S0 = ctx->over_S0 ? ctx->over_S0 : ctx->d_curve_S0.ptr;
     a.curve_w0 = ctx->over_w0 ? ctx->over_w0 : ctx->d_curve_w0.ptr;
-    a.perm_scratch = ctx->d_perm.ptr;
+    a.perm_scratch = lane == 1 ? lb.d_perm.ptr : ctx->d_perm.ptr;
     a.perm_table = nullptr; a.perm_filled = 0; a.perm_per = 0;
     a.n = ctx->plan.n; a.W = ctx->plan.W; a.M = ctx->plan.M;
     a.n_periods = ctx->plan.n_periods; a.n_widths = ctx->plan.n_widths; a.nb = ctx->plan.nb;
@@ -761,12 +893,13 @@ int enqueue(tls_ctx* ctx, bool count_work, bool phase_clock = false, double* deb
     hipError_t e;
     std::pair<hipEvent_t, hipEvent_t>* evp = nullptr;
     if ((e = timing_pair(ctx, &evp)) != hipSuccess) return fail(ctx, TLS_E_HIP, std::string("timing events: ") + hipGetErrorString(e));
-    if ((e = hipEventRecord(evp->first, ctx->stream)) != hipSuccess) {
+    if ((e = hipEventRecord(evp->first, stream)) != hipSuccess) {
         --ctx->ev_used;
         return fail(ctx, TLS_E_HIP, std::string("timing events: ") + hipGetErrorString(e));
     }
     const SearchPlan& plan = ctx->plan;
     const Kernel kernel_pick = pick_kernel(plan, ctx->flux, LaunchFlags{count_work, debug_folded || debug_prefix, ctx->batch_curves});
+    if (lane >= 0 && !is_slim(kernel_pick)) { --ctx->ev_used; return fail(ctx, TLS_E_STATE, "launch lanes: not a four-slot launch"); }
     // (counting has an instantiation of its own: the plain kernels do not keep the counters)
     switch (kernel_pick) {
     case Kernel::ResidentScreen: {
@@ -796,7 +929,7 @@ int enqueue(tls_ctx* ctx, bool count_work, bool phase_clock = false, double* deb
                                  : (count_work ? tlsdev::tls_slim_kernel<true, tlsdev::kSlimThreads, false> : tlsdev::tls_slim_kernel<false, tlsdev::kSlimThreads, false>));
         e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.slim_lds);
         if (e == hipSuccess) {
-            hipLaunchKernelGGL(kernel, dim3((unsigned)plan.slim_blocks), dim3((unsigned)plan.slim_threads), plan.slim_lds, ctx->stream, a);
+            hipLaunchKernelGGL(kernel, dim3((unsigned)plan.slim_blocks), dim3((unsigned)plan.slim_threads), plan.slim_lds, stream, a);
             e = hipGetLastError();
         }
         if (e == hipSuccess && a.perm_table) ctx->perm_filled = true;   // (every period of the plan passes through a launch)
@@ -834,10 +967,18 @@ int enqueue(tls_ctx* ctx, bool count_work, bool phase_clock = false, double* deb
     // (a failure from here on gives the event pair back: tls_kernel_timing must not meet a pair whose second event was
     // never recorded)
     if (e != hipSuccess) { --ctx->ev_used; return fail(ctx, TLS_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e)); }
-    if ((e = hipEventRecord(evp->second, ctx->stream)) != hipSuccess) {
+    if ((e = hipEventRecord(evp->second, stream)) != hipSuccess) {
         --ctx->ev_used;
         return fail(ctx, TLS_E_HIP, std::string("timing events: ") + hipGetErrorString(e));
     }
+    ctx->ev_overlapped[(ctx->ev_used - 1) % kEventRing] = overlapped ? 1 : 0;
+    if (lane == 1) {
+        TLS_HIP(ctx, hipEventRecord(lb.ev_done, stream));
+        lb.outstanding = true;
+    }
+    ctx->perm_filled_before_prev = filled_before;
+    ctx->run_lane = lane;   // (-1: the launch ends a run of overlappable ones)
+    ++ctx->lane_launches[lane == 1 ? 1 : 0];
     ctx->executed = true;
     ctx->counted = count_work;
     ctx->last_kernel = kernel_name(kernel_pick);
@@ -913,11 +1054,11 @@ int launch_t0_fit(tls_ctx* ctx, const double* d_t, const double* d_y, const doub
         if (resident) {
             auto kernel = tlsdev::tls_t0fit_kernel<true, unsigned short>;
             e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e == hipSuccess) { hipLaunchKernelGGL(kernel, grid, dim3((unsigned)threads), lds, ctx->stream, b); e = hipGetLastError(); }
+            if (e == hipSuccess) { hipLaunchKernelGGL(kernel, grid, dim3((unsigned)threads), lds, main_stream(ctx), b); e = hipGetLastError(); }
         } else {
             auto kernel = tlsdev::tls_t0fit_kernel<false, unsigned int>;
             e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e == hipSuccess) { hipLaunchKernelGGL(kernel, grid, dim3((unsigned)threads), lds, ctx->stream, b); e = hipGetLastError(); }
+            if (e == hipSuccess) { hipLaunchKernelGGL(kernel, grid, dim3((unsigned)threads), lds, main_stream(ctx), b); e = hipGetLastError(); }
         }
         return e;
     };
@@ -927,7 +1068,7 @@ int launch_t0_fit(tls_ctx* ctx, const double* d_t, const double* d_y, const doub
         if (e == hipSuccess) {
             const unsigned waves_per_wg = 4;
             const dim3 grid((unsigned)((epochs_cap + waves_per_wg - 1) / waves_per_wg), fits);
-            hipLaunchKernelGGL(tlsdev::tls_t0fit_rot, grid, dim3(waves_per_wg * 64), 0, ctx->stream, a);
+            hipLaunchKernelGGL(tlsdev::tls_t0fit_rot, grid, dim3(waves_per_wg * 64), 0, main_stream(ctx), a);
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = launch(2, (unsigned)blocks);
@@ -1001,25 +1142,25 @@ int enqueue_post_search(tls_ctx* ctx, const PostSearchBufs& b, int64_t gc, const
     sa.chi2 = d_chi2; sa.SR = ctx->d_spec.ptr; sa.power_raw = ctx->d_spec.ptr + np; sa.power = ctx->d_spec.ptr + 2 * np;
     sa.sde = b.sde; sa.n = (int)n_periods; sa.kernel = (int)kernel; sa.detrend = n_periods > 2 * kernel ? 1 : 0;   // stats.py:118
     sa.chi2_stride = (long long)np; sa.out_stride = (long long)b.spec_stride; sa.sde_stride = 2;
-    hipLaunchKernelGGL(tlsdev::tls_spectra_head, dim3(1, (unsigned)gc), dim3(1024), 0, ctx->stream, sa);
+    hipLaunchKernelGGL(tlsdev::tls_spectra_head, dim3(1, (unsigned)gc), dim3(1024), 0, main_stream(ctx), sa);
     if (sa.detrend) {
         const int n_med = (int)(n_periods - kernel + 1), per = tlsdev::kMedianWindows;
         const size_t lds = (size_t)(2 * per + kernel) * 8;
         hipLaunchKernelGGL(tlsdev::tls_spectra_median, dim3((unsigned)((n_med + per - 1) / per), (unsigned)gc), dim3(256), lds,
-                           ctx->stream, sa);
-        hipLaunchKernelGGL(tlsdev::tls_spectra_tail, dim3(1, (unsigned)gc), dim3(1024), 0, ctx->stream, sa);
+                           main_stream(ctx), sa);
+        hipLaunchKernelGGL(tlsdev::tls_spectra_tail, dim3(1, (unsigned)gc), dim3(1024), 0, main_stream(ctx), sa);
     }
     tlsdev::PickArgs pa;
     pa.chi2 = d_chi2; pa.row = d_row; pa.depth = d_depth; pa.power = ctx->d_spec.ptr + 2 * np;
     pa.periods = ctx->d_periods.ptr; pa.out = b.pick; pa.power_stride = (long long)b.spec_stride; pa.n = (int)n_periods;
-    hipLaunchKernelGGL(tlsdev::tls_power_pick, dim3((unsigned)gc), dim3(1024), 0, ctx->stream, pa);
+    hipLaunchKernelGGL(tlsdev::tls_power_pick, dim3((unsigned)gc), dim3(1024), 0, main_stream(ctx), pa);
     // (WITHOUT a host round trip, round 6: trial epochs, the depth-scaled template and the fit's parameters are formed on the
     // device from the pick, all fits run in ONE set of launches, the first minimum is taken on the device)
     tlsdev::PrepArgs pr;
     pr.pick = b.pick; pr.widths = ctx->d_widths.ptr; pr.n_widths = ctx->plan.n_widths; pr.q = ctx->d_q.ptr;
     pr.signal = ctx->d_fsig.ptr; pr.signal_stride = (long long)b.max_len; pr.epochs = ctx->d_fep.ptr; pr.epoch_stride = (long long)b.fit_stride;
     pr.params = b.fit; pr.n_epochs = b.n_epochs; pr.t_min = t_min; pr.margin = margin; pr.n = (int)n;
-    hipLaunchKernelGGL(tlsdev::tls_power_prep, dim3((unsigned)gc), dim3(256), 0, ctx->stream, pr);
+    hipLaunchKernelGGL(tlsdev::tls_power_prep, dim3((unsigned)gc), dim3(256), 0, main_stream(ctx), pr);
     TLS_HIP(ctx, hipGetLastError());
     int rc = launch_t0_fit(ctx, ctx->d_t.ptr, d_y, ctx->d_fsig.ptr, ctx->d_fep.ptr, ctx->d_fres.ptr, nullptr, n, 1.0, 0, 0, 0,
                            t_min, t_max, b.fit, gc, n, b.max_len, (int64_t)b.fit_stride);
@@ -1027,7 +1168,7 @@ int enqueue_post_search(tls_ctx* ctx, const PostSearchBufs& b, int64_t gc, const
     tlsdev::FirstMinArgs fa;
     fa.residuals = ctx->d_fres.ptr; fa.epochs = ctx->d_fep.ptr; fa.n_epochs = b.n_epochs;
     fa.T0 = b.T0; fa.stride = (long long)b.fit_stride;
-    hipLaunchKernelGGL(tlsdev::tls_first_min, dim3((unsigned)gc), dim3(1024), 0, ctx->stream, fa);
+    hipLaunchKernelGGL(tlsdev::tls_first_min, dim3((unsigned)gc), dim3(1024), 0, main_stream(ctx), fa);
     TLS_HIP(ctx, hipGetLastError());
     return TLS_OK;
 }
@@ -1056,9 +1197,9 @@ int reserve_transit_stats(tls_ctx* ctx, const StatsRequest& sr, int64_t group, i
     sb.row_duration = ctx->d_tstats.ptr; sb.root = sb.row_duration + sr.n_rows; sb.root_count = sb.root + sr.n_root;
     sb.scratch = sb.root_count + sr.n_root;
     sb.ranges = ctx->d_tranges.ptr;
-    TLS_HIP(ctx, hipMemcpyAsync(sb.row_duration, sr.row_duration, (size_t)sr.n_rows * 8, hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(sb.root, sr.root, (size_t)sr.n_root * 8, hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(sb.root_count, sr.root_count, (size_t)sr.n_root * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(sb.row_duration, sr.row_duration, (size_t)sr.n_rows * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(sb.root, sr.root, (size_t)sr.n_root * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(sb.root_count, sr.root_count, (size_t)sr.n_root * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     return TLS_OK;
 }
 
@@ -1075,7 +1216,7 @@ int enqueue_transit_stats(tls_ctx* ctx, const PostSearchBufs& b, const StatsBufs
     a.stats = b.stats; a.per_transit = b.per_transit;
     a.ranges = sb.ranges; a.scratch = sb.scratch; a.scratch_stride = (long long)sb.scratch_stride;
     a.n = (int)n; a.max_epochs = (int)sr.max_epochs;
-    hipLaunchKernelGGL(tlsdev::tls_transit_stats, dim3((unsigned)gc), dim3(256), 0, ctx->stream, a);
+    hipLaunchKernelGGL(tlsdev::tls_transit_stats, dim3((unsigned)gc), dim3(256), 0, main_stream(ctx), a);
     TLS_HIP(ctx, hipGetLastError());
     return TLS_OK;
 }
@@ -1154,8 +1295,8 @@ int reserve_transit_models(tls_ctx* ctx, const ModelsRequest& mr, int64_t group,
     const size_t g = (size_t)group, curve = 2 * (size_t)mr.curve_n;
     TLS_HIP(ctx, ctx->d_models.reserve(curve + g * mb.scratch_stride + g * mb.out_stride));
     mb.curve = ctx->d_models.ptr; mb.scratch = mb.curve + curve; mb.out = mb.scratch + g * mb.scratch_stride;
-    TLS_HIP(ctx, hipMemcpyAsync(mb.curve, mr.curve_t, (size_t)mr.curve_n * 8, hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(mb.curve + mr.curve_n, mr.curve_f, (size_t)mr.curve_n * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(mb.curve, mr.curve_t, (size_t)mr.curve_n * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(mb.curve + mr.curve_n, mr.curve_f, (size_t)mr.curve_n * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     return TLS_OK;
 }
 
@@ -1177,11 +1318,11 @@ int enqueue_transit_models(tls_ctx* ctx, const PostSearchBufs& b, const StatsBuf
     if (mb.resident) {
         auto kernel = tlsdev::tls_transit_models<true, unsigned short>;
         e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mb.lds);
-        if (e == hipSuccess) { hipLaunchKernelGGL(kernel, dim3((unsigned)gc), dim3(512), mb.lds, ctx->stream, a); e = hipGetLastError(); }
+        if (e == hipSuccess) { hipLaunchKernelGGL(kernel, dim3((unsigned)gc), dim3(512), mb.lds, main_stream(ctx), a); e = hipGetLastError(); }
     } else {
         auto kernel = tlsdev::tls_transit_models<false, unsigned int>;
         e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mb.lds);
-        if (e == hipSuccess) { hipLaunchKernelGGL(kernel, dim3((unsigned)gc), dim3(512), mb.lds, ctx->stream, a); e = hipGetLastError(); }
+        if (e == hipSuccess) { hipLaunchKernelGGL(kernel, dim3((unsigned)gc), dim3(512), mb.lds, main_stream(ctx), a); e = hipGetLastError(); }
     }
     if (e != hipSuccess) return fail(ctx, TLS_E_HIP, std::string("model launch: ") + hipGetErrorString(e));
     return TLS_OK;
@@ -1266,9 +1407,9 @@ int enqueue_find_peaks(tls_ctx* ctx, const PeaksRequest& pr, int64_t rows, int64
         auto kernel = tlsdev::tls_find_peaks<true>;
         const size_t lds = (size_t)((n_periods + 63) / 64) * 8;
         e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e == hipSuccess) { hipLaunchKernelGGL(kernel, dim3((unsigned)rows), dim3(1024), lds, ctx->stream, a); e = hipGetLastError(); }
+        if (e == hipSuccess) { hipLaunchKernelGGL(kernel, dim3((unsigned)rows), dim3(1024), lds, main_stream(ctx), a); e = hipGetLastError(); }
     } else {
-        hipLaunchKernelGGL(tlsdev::tls_find_peaks<false>, dim3((unsigned)rows), dim3(1024), 0, ctx->stream, a);
+        hipLaunchKernelGGL(tlsdev::tls_find_peaks<false>, dim3((unsigned)rows), dim3(1024), 0, main_stream(ctx), a);
         e = hipGetLastError();
     }
     if (e != hipSuccess) return fail(ctx, TLS_E_HIP, std::string("peaks launch: ") + hipGetErrorString(e));
@@ -1315,7 +1456,7 @@ int enqueue_phase_scan(tls_ctx* ctx, const PhaseScanRequest& ps, int64_t fits, c
     const size_t lds = tlsdev::phase_scan_lds_bytes(a.max_bins);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(kernel, dim3((unsigned)fits), dim3(tlsdev::kPhaseThreads), lds, ctx->stream, a);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)fits), dim3(tlsdev::kPhaseThreads), lds, main_stream(ctx), a);
         e = hipGetLastError();
     }
     if (e != hipSuccess) return fail(ctx, TLS_E_HIP, std::string("phase scan launch: ") + hipGetErrorString(e));
@@ -1381,12 +1522,12 @@ int enqueue_peak_fits(tls_ctx* ctx, const PeakFitBufs& fb, const PeakFitsRequest
         pa.peaks = reinterpret_cast<const unsigned long long*>(d_peaks);
         pa.pick = fb.pick; pa.curve = fb.curve; pa.status = status + f0;
         pa.k = (int)pf.k; pa.first = (int)f0; pa.fits = (int)fits;
-        hipLaunchKernelGGL(tlsdev::tls_peak_picks, dim3((unsigned)((fits + 255) / 256)), dim3(256), 0, ctx->stream, pa);
+        hipLaunchKernelGGL(tlsdev::tls_peak_picks, dim3((unsigned)((fits + 255) / 256)), dim3(256), 0, main_stream(ctx), pa);
         tlsdev::PrepArgs pr;
         pr.pick = fb.pick; pr.widths = ctx->d_widths.ptr; pr.n_widths = ctx->plan.n_widths; pr.q = ctx->d_q.ptr;
         pr.signal = fb.signal; pr.signal_stride = (long long)fb.max_len; pr.epochs = fb.epochs; pr.epoch_stride = (long long)fb.fit_stride;
         pr.params = fb.fit; pr.n_epochs = fb.n_epochs; pr.t_min = t_min; pr.margin = margin; pr.n = (int)n;
-        hipLaunchKernelGGL(tlsdev::tls_power_prep, dim3((unsigned)fits), dim3(256), 0, ctx->stream, pr);
+        hipLaunchKernelGGL(tlsdev::tls_power_prep, dim3((unsigned)fits), dim3(256), 0, main_stream(ctx), pr);
         TLS_HIP(ctx, hipGetLastError());
         int rc = launch_t0_fit(ctx, ctx->d_t.ptr, d_y, fb.signal, fb.epochs, fb.residuals, nullptr, n, 1.0, 0, 0, 0, t_min, t_max,
                                fb.fit, fits, n, fb.max_len, (int64_t)fb.fit_stride, fb.curve);
@@ -1394,7 +1535,7 @@ int enqueue_peak_fits(tls_ctx* ctx, const PeakFitBufs& fb, const PeakFitsRequest
         tlsdev::FirstMinArgs fa;
         fa.residuals = fb.residuals; fa.epochs = fb.epochs; fa.n_epochs = fb.n_epochs;
         fa.T0 = T0 + f0; fa.stride = (long long)fb.fit_stride;
-        hipLaunchKernelGGL(tlsdev::tls_first_min, dim3((unsigned)fits), dim3(1024), 0, ctx->stream, fa);
+        hipLaunchKernelGGL(tlsdev::tls_first_min, dim3((unsigned)fits), dim3(1024), 0, main_stream(ctx), fa);
         tlsdev::TransitStatsArgs a;
         a.t = ctx->d_t.ptr; a.y = d_y; a.pick = fb.pick; a.T0 = T0 + f0;
         a.power = d_power; a.power_stride = (long long)power_stride; a.curve = fb.curve;
@@ -1404,7 +1545,7 @@ int enqueue_peak_fits(tls_ctx* ctx, const PeakFitBufs& fb, const PeakFitsRequest
         a.stats = stats + (size_t)f0 * tlsdev::kTransitStats; a.per_transit = fb.per_transit;
         a.ranges = fb.ranges; a.scratch = fb.scratch; a.scratch_stride = (long long)fb.scratch_stride;
         a.n = (int)n; a.max_epochs = (int)in.max_epochs;
-        hipLaunchKernelGGL(tlsdev::tls_transit_stats, dim3((unsigned)fits), dim3(256), 0, ctx->stream, a);
+        hipLaunchKernelGGL(tlsdev::tls_transit_stats, dim3((unsigned)fits), dim3(256), 0, main_stream(ctx), a);
         TLS_HIP(ctx, hipGetLastError());
         if (ps && (rc = enqueue_phase_scan(ctx, *ps, fits, ctx->d_t.ptr, d_y, n, fb.curve, fb.pick + 3, 8, T0 + f0,
                                            a.stats + 1, tlsdev::kTransitStats, status + f0,
@@ -1413,10 +1554,10 @@ int enqueue_peak_fits(tls_ctx* ctx, const PeakFitBufs& fb, const PeakFitsRequest
             // (the next slab overwrites these arrays: the copies are done before it is enqueued)
             const size_t at = (size_t)(first_curve * pf.k + f0), bytes = (size_t)fits * fb.fit_stride * 8;
             std::vector<int> nep((size_t)fits);
-            if (pf.out_epochs) TLS_HIP(ctx, hipMemcpyAsync(pf.out_epochs + at * fb.fit_stride, fb.epochs, bytes, hipMemcpyDeviceToHost, ctx->stream));
-            if (pf.out_residuals) TLS_HIP(ctx, hipMemcpyAsync(pf.out_residuals + at * fb.fit_stride, fb.residuals, bytes, hipMemcpyDeviceToHost, ctx->stream));
-            TLS_HIP(ctx, hipMemcpyAsync(nep.data(), fb.n_epochs, (size_t)fits * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-            TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            if (pf.out_epochs) TLS_HIP(ctx, hipMemcpyAsync(pf.out_epochs + at * fb.fit_stride, fb.epochs, bytes, hipMemcpyDeviceToHost, main_stream(ctx)));
+            if (pf.out_residuals) TLS_HIP(ctx, hipMemcpyAsync(pf.out_residuals + at * fb.fit_stride, fb.residuals, bytes, hipMemcpyDeviceToHost, main_stream(ctx)));
+            TLS_HIP(ctx, hipMemcpyAsync(nep.data(), fb.n_epochs, (size_t)fits * sizeof(int), hipMemcpyDeviceToHost, main_stream(ctx)));
+            TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));
             if (pf.out_n_epochs) for (int64_t l = 0; l < fits; ++l) pf.out_n_epochs[at + (size_t)l] = nep[(size_t)l];
         }
     }
@@ -1571,7 +1712,7 @@ int search_group(tls_ctx* ctx, BatchSlot& sl, const GroupState& st) {
 // (asynchronous copies may be in flight on either stream), no launch override survives, and the context holds no results
 int end_batch(tls_ctx* ctx, int rc) {
     if (ctx && rc != TLS_OK) {
-        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipStreamSynchronize(main_stream(ctx));
         if (ctx->copy_stream) (void)hipStreamSynchronize(ctx->copy_stream);
         unbind_batch_slot(ctx);
         ctx->executed = false;
@@ -1668,22 +1809,22 @@ int run_candidate_slabs(tls_ctx* ctx, const SlabStage& st, Pack pack, Launch lau
         for (size_t i = 0; i < s.fits; ++i) s.lds = std::max<size_t>(s.lds, pack(f0 + (int64_t)i, &h_ints[i]));
         for (const tlsslab::Run& run : slab.runs)
             for (const SlabCopy& r : st.rows)
-                if (r.host) TLS_HIP(ctx, hipMemcpyAsync(r.dev + run.slot * st.n, r.host + (size_t)run.curve * st.n, run.count * st.n * 8, hipMemcpyHostToDevice, ctx->stream));
+                if (r.host) TLS_HIP(ctx, hipMemcpyAsync(r.dev + run.slot * st.n, r.host + (size_t)run.curve * st.n, run.count * st.n * 8, hipMemcpyHostToDevice, main_stream(ctx)));
         const size_t ints = st.int_columns > 1 ? st.int_columns * st.sl : s.fits;
-        TLS_HIP(ctx, hipMemcpyAsync(st.d_ints, h_ints.data(), ints * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(st.d_ints, h_ints.data(), ints * sizeof(int), hipMemcpyHostToDevice, main_stream(ctx)));
         for (const SlabCopy& c : st.columns)
-            if (c.host) TLS_HIP(ctx, hipMemcpyAsync(c.dev, c.host + f0, s.fits * 8, hipMemcpyHostToDevice, ctx->stream));
+            if (c.host) TLS_HIP(ctx, hipMemcpyAsync(c.dev, c.host + f0, s.fits * 8, hipMemcpyHostToDevice, main_stream(ctx)));
         launch(s);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) {
-            (void)hipStreamSynchronize(ctx->stream);
+            (void)hipStreamSynchronize(main_stream(ctx));
             return fail(ctx, TLS_E_HIP, std::string(st.what) + " launch: " + hipGetErrorString(e));
         }
         ctx->last_kernel = st.kernel;
         if (int rc = fetch(s)) return rc;
         // (the next slab overwrites the device buffers and h_ints; what a stage uploaded before the loop is read until the
         // stream is done)
-        TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));
     }
     return TLS_OK;
 }
@@ -1695,7 +1836,7 @@ const auto no_int_columns = [](int64_t, int*) { return (size_t)0; };
 bool launch_times_pairs(tls_ctx* ctx, tlsdev::TimesPairsArgs p, size_t curves, size_t n) {
     p.count = (long long)(curves * n);
     const unsigned blocks = (unsigned)std::min<long long>((p.count + tlsdev::kTimesThreads - 1) / tlsdev::kTimesThreads, 8192);
-    hipLaunchKernelGGL(tlsdev::tls_times_pairs_kernel, dim3(blocks), dim3(tlsdev::kTimesThreads), 0, ctx->stream, p);
+    hipLaunchKernelGGL(tlsdev::tls_times_pairs_kernel, dim3(blocks), dim3(tlsdev::kTimesThreads), 0, main_stream(ctx), p);
     return hipPeekAtLastError() == hipSuccess;
 }
 
@@ -1736,8 +1877,9 @@ tls_ctx* tls_ctx_create(int device_id) {
     ctx->opt = process_options();
     hipDeviceProp_t prop;
     if ((e = hipSetDevice(device_id)) != hipSuccess || (e = hipGetDeviceProperties(&prop, device_id)) != hipSuccess ||
-        (e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking)) != hipSuccess ||
-        (e = hipEventCreate(&ctx->ev0)) != hipSuccess || (e = hipEventCreate(&ctx->ev1)) != hipSuccess) {
+        (e = hipStreamCreateWithFlags(&ctx->lane_a_stream, hipStreamNonBlocking)) != hipSuccess ||
+        (e = hipEventCreate(&ctx->ev0)) != hipSuccess || (e = hipEventCreate(&ctx->ev1)) != hipSuccess ||
+        (e = hipEventCreateWithFlags(&ctx->ev_state, hipEventDisableTiming)) != hipSuccess) {
         g_create_error = std::string("context setup: ") + hipGetErrorString(e);
         delete ctx;
         return nullptr;
@@ -1777,6 +1919,13 @@ int tls_set_options(tls_ctx* ctx, const tls_options* opt) {
 
 int tls_debug_set_switch(tls_ctx* ctx, const char* name, double value) {
     if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
+    if (name && std::strcmp(name, "lanes") == 0) {
+        // launch lanes on (default) or off: where a launch runs, never what it computes -- not a planning switch, so it is
+        // no part of the plan key, of tls_debug_get_switches' text or of the environment; changing it joins the lanes
+        const int v = value < 0 ? -1 : (int)value;
+        if (v != ctx->lanes) { (void)main_stream(ctx); ctx->lanes = v; }
+        return TLS_OK;
+    }
     const SwitchName* sw = find_switch(name);
     if (!sw) return fail(ctx, TLS_E_ARG, std::string("unknown switch: ") + (name ? name : "(null)"));
     Switches o = ctx->opt;
@@ -1802,7 +1951,17 @@ void tls_ctx_destroy(tls_ctx* ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     if (ctx->comm) (void)ncclCommDestroy(ctx->comm);
-    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+    if (ctx->lane_b.stream) (void)hipStreamSynchronize(ctx->lane_b.stream);
+    if (ctx->lane_a_stream) (void)hipStreamSynchronize(ctx->lane_a_stream);
+    {
+        auto& lb = ctx->lane_b;
+        lb.d_squeue.release(); lb.d_lists.release(); lb.d_perm.release(); lb.d_out.release(); lb.d_y.release();
+        if (lb.h_stage) (void)hipHostFree(lb.h_stage);
+        if (lb.ev_stage) (void)hipEventDestroy(lb.ev_stage);
+        if (lb.ev_done) (void)hipEventDestroy(lb.ev_done);
+        if (lb.stream) (void)hipStreamDestroy(lb.stream);
+    }
+    if (ctx->ev_state) (void)hipEventDestroy(ctx->ev_state);
     ctx->d_plan.release(); ctx->d_out.release();
     if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
     if (ctx->h_out) (void)hipHostFree(ctx->h_out);
@@ -1839,7 +1998,7 @@ void tls_ctx_destroy(tls_ctx* ctx) {
     for (auto& evp : ctx->ev_pool) { (void)hipEventDestroy(evp.first); (void)hipEventDestroy(evp.second); }
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
-    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
+    if (ctx->lane_a_stream) (void)hipStreamDestroy(ctx->lane_a_stream);
     delete ctx;
 }
 
@@ -1852,7 +2011,7 @@ int reserve_plan_buffers(tls_ctx* ctx) {
         // [split_batch] tiles done | [split_batch] fold ready: all zero between launches (the kernel resets them)
         if (ctx->d_tiles_done.cap < 2 * (size_t)plan.split_batch) {
             TLS_HIP(ctx, ctx->d_tiles_done.reserve(2 * (size_t)plan.split_batch));
-            TLS_HIP(ctx, hipMemsetAsync(ctx->d_tiles_done.ptr, 0, ctx->d_tiles_done.cap * sizeof(unsigned int), ctx->stream));
+            TLS_HIP(ctx, hipMemsetAsync(ctx->d_tiles_done.ptr, 0, ctx->d_tiles_done.cap * sizeof(unsigned int), main_stream(ctx)));
         }
     }
     if (!plan.resident) TLS_HIP(ctx, ctx->d_scratch.reserve(plan.scratch_doubles));
@@ -1870,13 +2029,11 @@ int reserve_plan_buffers(tls_ctx* ctx) {
     // results [chi2 | row | depth | counters[4]]
     const size_t np = (size_t)plan.n_periods;
     TLS_HIP(ctx, ctx->d_out.reserve(3 * np + 4));
-    ctx->d_chi2.ptr = ctx->d_out.ptr; ctx->d_row.ptr = reinterpret_cast<long long*>(ctx->d_out.ptr + np);
-    ctx->d_depth.ptr = ctx->d_out.ptr + 2 * np;
-    ctx->d_counters.ptr = reinterpret_cast<unsigned long long*>(ctx->d_out.ptr + 3 * np);
+    point_results(ctx, 0);
     TLS_HIP(ctx, ctx->d_queue.reserve(1));
     if (!ctx->d_squeue.ptr) {   // zero once per context: the kernel rewinds its queue itself
         TLS_HIP(ctx, ctx->d_squeue.reserve(4));   // [0..1] the search (or fold) kernel's queue, [2..3] the split path's search kernel
-        TLS_HIP(ctx, hipMemsetAsync(ctx->d_squeue.ptr, 0, 4 * sizeof(unsigned int), ctx->stream));
+        TLS_HIP(ctx, hipMemsetAsync(ctx->d_squeue.ptr, 0, 4 * sizeof(unsigned int), main_stream(ctx)));
     }
     return TLS_OK;
 }
@@ -1946,15 +2103,16 @@ int stage_plan(tls_ctx* ctx, const double* t, const double* y, const std::vector
     }
     unsigned char* d = ctx->d_plan.ptr;
     ctx->d_tile_prefix.ptr = reinterpret_cast<unsigned int*>(d + L.tile_prefix);
-    ctx->d_t.ptr = reinterpret_cast<double*>(d + L.t); ctx->d_y.ptr = reinterpret_cast<double*>(d + L.y);
+    ctx->d_t.ptr = reinterpret_cast<double*>(d + L.t); ctx->d_y_a.ptr = reinterpret_cast<double*>(d + L.y);
+    ctx->d_y.ptr = ctx->d_y_a.ptr; ctx->flux_lane = 0; ctx->a_reads_flux_b = false;   // (the plan's flux is lane A's)
     ctx->d_w.ptr = reinterpret_cast<double*>(d + L.w); ctx->d_periods.ptr = reinterpret_cast<double*>(d + L.periods);
     ctx->d_order.ptr = reinterpret_cast<int*>(d + L.order); ctx->d_rows.ptr = reinterpret_cast<tlsdev::PeriodRows*>(d + L.rows);
     ctx->d_widths.ptr = reinterpret_cast<tlsdev::WidthEntry*>(d + L.widths);
     ctx->d_screens.ptr = reinterpret_cast<tlsdev::RowScreen*>(d + L.screens);
     ctx->d_q.ptr = reinterpret_cast<double*>(d + L.q); ctx->d_q2.ptr = reinterpret_cast<double*>(d + L.q2);
     ctx->d_g.ptr = reinterpret_cast<double*>(d + L.g);
-    TLS_HIP(ctx, hipMemcpyAsync(d, h, L.total, hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipEventRecord(ctx->ev_stage, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d, h, L.total, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipEventRecord(ctx->ev_stage, main_stream(ctx)));
     ctx->stage_pending = true;
     return TLS_OK;
 }
@@ -1970,6 +2128,7 @@ int tls_prepare(tls_ctx* ctx, const double* t, const double* y, const double* dy
     if (tmpl->n_rows < 1 || !tmpl->values || !tmpl->offset || !tmpl->length || !tmpl->width || !tmpl->overshoot)
         return fail(ctx, TLS_E_ARG, "empty template table");
     TLS_HIP(ctx, hipSetDevice(ctx->device));
+    (void)main_stream(ctx);   // (tls_prepare always joins the lanes: the flux goes to lane A, the next search starts there)
 
     // The same time stamps, periods, template and parameters as the plan this context already holds (a survey, or
     // repeated power() calls): only the flux is new.  tls_prepare then costs two passes over y and one upload.
@@ -1980,7 +2139,7 @@ int tls_prepare(tls_ctx* ctx, const double* t, const double* y, const double* dy
         // uniform dy after per-point dy (or the reverse): a different kernel variant and layout -- plan again
     }
     ctx->key.valid = false;
-    ctx->perm_filled = false; ctx->perm_table_entries = 0;   // (the table of folded orders belongs to the key)
+    ctx->perm_filled = false; ctx->perm_filled_before_prev = false; ctx->perm_table_entries = 0;   // (the table of folded orders belongs to the key)
 
     std::vector<tlsdev::WidthEntry> widths;
     std::vector<double> q;
@@ -2026,6 +2185,53 @@ int tls_prepare(tls_ctx* ctx, const double* t, const double* y, const double* dy
 }
 
 namespace {
+// A plain search of the held plan and flux may overlap its neighbours: lanes on, the four-slot kernel, one light curve from
+// the context's own buffers, and a table of folded orders that is filled (such a launch writes nothing but its lane's state).
+bool launch_overlappable(const tls_ctx* ctx) {
+    return ctx->lanes != 0 && ctx->perm_table_entries > 0 && ctx->perm_filled && ctx->batch_curves == 1 && !ctx->over_y &&
+           !ctx->over_w && !ctx->over_S0 && !ctx->over_w0 && !ctx->over_chi2 && !ctx->over_row && !ctx->over_depth &&
+           is_slim(pick_kernel(ctx->plan, ctx->flux));
+}
+
+// the flux of the next search into lane B's buffer, on lane B's stream (behind lane B's earlier launch, and nothing newer)
+int update_flux_lane_b(tls_ctx* ctx, const double* y) {
+    auto& lb = ctx->lane_b;
+    const size_t bytes = (size_t)ctx->plan.n * 8;
+    if (int rc = ensure_lane_b(ctx)) return rc;
+    if (lb.stage_pending) { TLS_HIP(ctx, hipEventSynchronize(lb.ev_stage)); lb.stage_pending = false; }
+    if (lb.h_stage_cap < bytes) {
+        if (lb.h_stage) TLS_HIP(ctx, hipHostFree(lb.h_stage));
+        lb.h_stage = nullptr; lb.h_stage_cap = 0;
+        const size_t cap = std::max<size_t>(bytes + bytes / 4, 1 << 16);
+        TLS_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&lb.h_stage), cap, hipHostMallocDefault));
+        lb.h_stage_cap = cap;
+    }
+    std::memcpy(lb.h_stage, y, bytes);
+    if (int rc = lane_b_see_state(ctx)) return rc;
+    TLS_HIP(ctx, hipMemcpyAsync(lb.d_y.ptr, lb.h_stage, bytes, hipMemcpyHostToDevice, lb.stream));
+    TLS_HIP(ctx, hipEventRecord(lb.ev_stage, lb.stream));
+    lb.stage_pending = true;
+    TLS_HIP(ctx, hipEventRecord(lb.ev_done, lb.stream));
+    lb.outstanding = true;
+    ctx->flux_b_unseen = true;
+    ctx->d_y.ptr = lb.d_y.ptr; ctx->flux_lane = 1;
+    return TLS_OK;
+}
+
+// ... and into lane A's, on lane A's stream without a join (the launch in flight on lane B reads lane B's flux)
+int update_flux_lane_a(tls_ctx* ctx, const double* y) {
+    const PlanLayout& L = ctx->layout;
+    const size_t bytes = (size_t)ctx->plan.n * 8;
+    if (int rc = stage_reserve(ctx, L.total)) return rc;
+    std::memcpy(ctx->h_stage + L.y, y, bytes);
+    TLS_HIP(ctx, hipMemcpyAsync(ctx->d_y_a.ptr, ctx->h_stage + L.y, bytes, hipMemcpyHostToDevice, ctx->lane_a_stream));
+    TLS_HIP(ctx, hipEventRecord(ctx->ev_stage, ctx->lane_a_stream));
+    ctx->stage_pending = true;
+    ctx->state_dirty = true;   // (lane B's next command has to see this upload)
+    ctx->d_y.ptr = ctx->d_y_a.ptr; ctx->flux_lane = 0;
+    return TLS_OK;
+}
+
 // the flux (and weights) of a prepared plan replaced; kWeightsDiffer when the new dy changes the weight structure
 int update_flux_impl(tls_ctx* ctx, const double* y, const double* dy) {
     std::vector<double> w;
@@ -2037,15 +2243,26 @@ int update_flux_impl(tls_ctx* ctx, const double* y, const double* dy) {
     choose_flux_kernels(ctx, flux_scatter(y, ctx->plan.n));
     const PlanLayout& L = ctx->layout;
     const size_t nn = (size_t)ctx->plan.n;
+    // Inside a run of overlappable searches the flux goes to the lane the NEXT search takes, on that lane's stream: it waits
+    // for that lane's earlier launch through stream order and for nothing else -- the launch in flight on the other lane
+    // keeps reading its own flux.  (S0, w0, y_abs_max and the kernel choice are kernel arguments, taken at enqueue.)
+    if (ctx->run_lane >= 0 && launch_overlappable(ctx)) {
+        const int target = ctx->run_lane ^ 1;
+        if (target == 1 ? !ctx->a_reads_flux_b : !ctx->b_reads_flux_a) {
+            ctx->executed = false;
+            return target == 1 ? update_flux_lane_b(ctx, y) : update_flux_lane_a(ctx, y);
+        }
+    }
     int rcs = stage_reserve(ctx, L.total);   // (waits for the previous upload out of the staging buffer)
     if (rcs) return rcs;
     std::memcpy(ctx->h_stage + L.y, y, nn * 8);
-    TLS_HIP(ctx, hipMemcpyAsync(ctx->d_y.ptr, ctx->h_stage + L.y, nn * 8, hipMemcpyHostToDevice, ctx->stream));
+    ctx->d_y.ptr = ctx->d_y_a.ptr; ctx->flux_lane = 0;
+    TLS_HIP(ctx, hipMemcpyAsync(ctx->d_y.ptr, ctx->h_stage + L.y, nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     if (!uniform) {
         std::memcpy(ctx->h_stage + L.w, w.data(), nn * 8);
-        TLS_HIP(ctx, hipMemcpyAsync(ctx->d_w.ptr, ctx->h_stage + L.w, nn * 8, hipMemcpyHostToDevice, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(ctx->d_w.ptr, ctx->h_stage + L.w, nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     }
-    TLS_HIP(ctx, hipEventRecord(ctx->ev_stage, ctx->stream));
+    TLS_HIP(ctx, hipEventRecord(ctx->ev_stage, main_stream(ctx)));
     ctx->stage_pending = true;
     ctx->executed = false;
     return TLS_OK;
@@ -2068,7 +2285,13 @@ int tls_execute(tls_ctx* ctx, int count_work) {
     if (!ctx->prepared) return fail(ctx, TLS_E_STATE, "tls_execute before tls_prepare");
     TLS_HIP(ctx, hipSetDevice(ctx->device));
     if (ctx->plan.n_periods == 0) { ctx->executed = true; return TLS_OK; }
-    return enqueue(ctx, (count_work & 1) != 0, (count_work & 2) != 0);
+    // Launch lanes: a plain four-slot search whose table of folded orders was filled before the PREVIOUS launch was enqueued
+    // (so that lane A's recorded state covers the filling launch) may overlap its neighbours.  It takes lane B when the launch
+    // before it was such a one on lane A and nothing but tls_update_flux came between; otherwise lane A.  Every other launch
+    // joins the lanes and runs on lane A as ever.
+    int lane = -1;
+    if (count_work == 0 && ctx->perm_filled_before_prev && launch_overlappable(ctx)) lane = ctx->run_lane == 0 ? 1 : 0;
+    return enqueue(ctx, (count_work & 1) != 0, (count_work & 2) != 0, nullptr, nullptr, nullptr, lane);
 }
 
 int tls_t0_fit(tls_ctx* ctx, const double* t, const double* y, int64_t n, double period, const double* signal,
@@ -2086,13 +2309,13 @@ int tls_t0_fit(tls_ctx* ctx, const double* t, const double* y, int64_t n, double
     if ((rc = upload(ctx, ctx->d_fsig, signal, (size_t)dur))) return rc;
     if ((rc = upload(ctx, ctx->d_fep, epochs, (size_t)n_epochs))) return rc;
     TLS_HIP(ctx, ctx->d_fres.reserve((size_t)n_epochs));
-    TLS_HIP(ctx, hipMemsetAsync(ctx->d_queue.ptr, 0, sizeof(unsigned int), ctx->stream));
+    TLS_HIP(ctx, hipMemsetAsync(ctx->d_queue.ptr, 0, sizeof(unsigned int), main_stream(ctx)));
     double t_lo, t_hi;
     time_range(t, n, t_lo, t_hi);
     if ((rc = launch_t0_fit(ctx, ctx->d_ft.ptr, ctx->d_fy.ptr, ctx->d_fsig.ptr, ctx->d_fep.ptr, ctx->d_fres.ptr, ctx->d_queue.ptr,
                             n, period, dur, n_epochs, roll, t_lo, t_hi))) return rc;
-    TLS_HIP(ctx, hipMemcpyAsync(out_residuals, ctx->d_fres.ptr, (size_t)n_epochs * 8, hipMemcpyDeviceToHost, ctx->stream));
-    TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(out_residuals, ctx->d_fres.ptr, (size_t)n_epochs * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+    TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));
     return TLS_OK;
 }
 
@@ -2106,17 +2329,17 @@ int tls_pink_noise(tls_ctx* ctx, const double* data, int64_t n, int64_t width, d
     // data | terms | running sums (n_windows + 1)
     TLS_HIP(ctx, ctx->d_pink.reserve((size_t)n + 2 * (size_t)n_windows + 1));
     double* d_data = ctx->d_pink.ptr; double* d_terms = d_data + n; double* d_sums = d_terms + n_windows;
-    TLS_HIP(ctx, hipMemcpyAsync(d_data, data, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(tlsdev::tls_pink_terms, dim3((unsigned)((n_windows + 255) / 256)), dim3(256), 0, ctx->stream,
+    TLS_HIP(ctx, hipMemcpyAsync(d_data, data, (size_t)n * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    hipLaunchKernelGGL(tlsdev::tls_pink_terms, dim3((unsigned)((n_windows + 255) / 256)), dim3(256), 0, main_stream(ctx),
                        (const double*)d_data, (int)n_windows, (int)width, root_width, d_terms);
     TLS_HIP(ctx, hipGetLastError());
     // (the reference adds the terms one by one from the left: the exact sequential prefix sum of the search, terms >= 0)
-    hipLaunchKernelGGL(tlsdev::tls_cumsum_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const double*)d_terms, d_sums, (int)n_windows, 0,
+    hipLaunchKernelGGL(tlsdev::tls_cumsum_kernel, dim3(1), dim3(1024), 0, main_stream(ctx), (const double*)d_terms, d_sums, (int)n_windows, 0,
                        static_cast<unsigned long long*>(nullptr));
     TLS_HIP(ctx, hipGetLastError());
     double last = 0.0;
-    TLS_HIP(ctx, hipMemcpyAsync(&last, d_sums + n_windows, 8, hipMemcpyDeviceToHost, ctx->stream));
-    TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(&last, d_sums + n_windows, 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+    TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));
     *out = last / (double)n_windows;
     return TLS_OK;
 }
@@ -2153,29 +2376,29 @@ int tls_inject_transits(tls_ctx* ctx, const double* t, int64_t n, const double* 
     double* d_base = d_t + nn;
     double* d_out = d_base + base_len;
     double* d_consts = d_out + (size_t)slab * nn;
-    TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (flux_rows == 1) TLS_HIP(ctx, hipMemcpyAsync(d_base, flux, nn * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    if (flux_rows == 1) TLS_HIP(ctx, hipMemcpyAsync(d_base, flux, nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     for (int64_t k0 = 0; k0 < n_inj; k0 += slab) {
         const int64_t rows = std::min<int64_t>(slab, n_inj - k0);
         if (flux_rows != 1)
-            TLS_HIP(ctx, hipMemcpyAsync(d_base, flux + (size_t)k0 * nn, (size_t)rows * nn * 8, hipMemcpyHostToDevice, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(d_consts, inj + k0, (size_t)rows * sizeof(tls_injection), hipMemcpyHostToDevice, ctx->stream));
-        TLS_HIP(ctx, hipMemsetAsync(ctx->d_inject_count.ptr, 0, (size_t)rows * sizeof(unsigned long long), ctx->stream));
+            TLS_HIP(ctx, hipMemcpyAsync(d_base, flux + (size_t)k0 * nn, (size_t)rows * nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+        TLS_HIP(ctx, hipMemcpyAsync(d_consts, inj + k0, (size_t)rows * sizeof(tls_injection), hipMemcpyHostToDevice, main_stream(ctx)));
+        TLS_HIP(ctx, hipMemsetAsync(ctx->d_inject_count.ptr, 0, (size_t)rows * sizeof(unsigned long long), main_stream(ctx)));
         tlsdev::InjectArgs a;
         a.t = d_t; a.flux = d_base; a.consts = d_consts; a.u1 = u1; a.u2 = u2; a.out = d_out;
         a.count = ctx->d_inject_count.ptr; a.n = (long long)n; a.flux_stride = flux_rows == 1 ? 0 : (long long)n;
         hipLaunchKernelGGL(tlsdev::tls_inject_transits, dim3((unsigned)((n + 255) / 256), (unsigned)rows), dim3(256), 0,
-                           ctx->stream, a);
+                           main_stream(ctx), a);
         TLS_HIP(ctx, hipGetLastError());
         ctx->last_kernel = "tls_inject_transits";
-        TLS_HIP(ctx, hipMemcpyAsync(out_flux + (size_t)k0 * nn, d_out, (size_t)rows * nn * 8, hipMemcpyDeviceToHost, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(out_flux + (size_t)k0 * nn, d_out, (size_t)rows * nn * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
         if (out_in_transit) {
             static_assert(sizeof(unsigned long long) == sizeof(int64_t), "count width");
             TLS_HIP(ctx, hipMemcpyAsync(out_in_transit + k0, ctx->d_inject_count.ptr, (size_t)rows * 8, hipMemcpyDeviceToHost,
-                                        ctx->stream));
+                                        main_stream(ctx)));
         }
         // (the next slab overwrites the device rows: the copies above have to be done first)
-        TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));
     }
     return TLS_OK;
 }
@@ -2238,8 +2461,8 @@ int tls_null_rows(tls_ctx* ctx, int64_t n, int64_t n_rows, uint64_t seed, int64_
     double* d_src = ctx->d_null.ptr;
     double* d_sigma = d_src + src_len;
     double* d_out = d_sigma + sigma_len;
-    if (src_len) TLS_HIP(ctx, hipMemcpyAsync(d_src, src, src_len * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (sigma_len) TLS_HIP(ctx, hipMemcpyAsync(d_sigma, sigma, sigma_len * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (src_len) TLS_HIP(ctx, hipMemcpyAsync(d_src, src, src_len * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    if (sigma_len) TLS_HIP(ctx, hipMemcpyAsync(d_sigma, sigma, sigma_len * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     for (int64_t k0 = 0; k0 < n_rows; k0 += slab) {
         const int64_t rows = std::min<int64_t>(slab, n_rows - k0);
         tlsdev::NullArgs a;
@@ -2249,17 +2472,17 @@ int tls_null_rows(tls_ctx* ctx, int64_t n, int64_t n_rows, uint64_t seed, int64_
         a.sigma = mode == 0 ? d_sigma + (n_sigma == 1 ? 0 : k0) : nullptr;
         if (mode == 0) {
             hipLaunchKernelGGL(tlsdev::tls_null_white, dim3((unsigned)((blocks + 255) / 256), (unsigned)rows), dim3(256), 0,
-                               ctx->stream, a);
+                               main_stream(ctx), a);
             ctx->last_kernel = "tls_null_white";
         } else {
             hipLaunchKernelGGL(tlsdev::tls_null_bootstrap, dim3((unsigned)((n + 255) / 256), (unsigned)rows), dim3(256), 0,
-                               ctx->stream, a);
+                               main_stream(ctx), a);
             ctx->last_kernel = "tls_null_bootstrap";
         }
         TLS_HIP(ctx, hipGetLastError());
-        TLS_HIP(ctx, hipMemcpyAsync(out + (size_t)k0 * nn, d_out, (size_t)rows * nn * 8, hipMemcpyDeviceToHost, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(out + (size_t)k0 * nn, d_out, (size_t)rows * nn * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
         // (the next slab overwrites the device rows: the copy above has to be done first)
-        TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));
     }
     return TLS_OK;
 }
@@ -2281,12 +2504,12 @@ int tls_debug_null_words(tls_ctx* ctx, int64_t n, int64_t n_rows, uint64_t seed,
         tlsdev::NullArgs a{};
         a.seed = (unsigned long long)seed; a.first_trial = (long long)(first_trial + k0); a.blocks = (long long)blocks;
         hipLaunchKernelGGL(tlsdev::tls_null_words, dim3((unsigned)((blocks + 255) / 256), (unsigned)rows), dim3(256), 0,
-                           ctx->stream, a, ctx->d_null_words.ptr);
+                           main_stream(ctx), a, ctx->d_null_words.ptr);
         TLS_HIP(ctx, hipGetLastError());
         ctx->last_kernel = "tls_null_words";
         TLS_HIP(ctx, hipMemcpyAsync(out + (size_t)k0 * W, ctx->d_null_words.ptr, (size_t)rows * W * 8, hipMemcpyDeviceToHost,
-                                    ctx->stream));
-        TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+                                    main_stream(ctx)));
+        TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));
     }
     return TLS_OK;
 }
@@ -2341,15 +2564,15 @@ int tls_medfilt_detrend(tls_ctx* ctx, const double* y, int64_t n, int64_t n_rows
     for (int64_t k0 = 0; k0 < n_rows; k0 += slab) {
         const int64_t rows = std::min<int64_t>(slab, n_rows - k0);
         const size_t bytes = (size_t)rows * nn * 8;
-        TLS_HIP(ctx, hipMemcpyAsync(d_y, y + (size_t)k0 * nn, bytes, hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(fn, dim3(tiles, (unsigned)rows), dim3(tlsdev::kDetrendThreads), lds, ctx->stream, a);
+        TLS_HIP(ctx, hipMemcpyAsync(d_y, y + (size_t)k0 * nn, bytes, hipMemcpyHostToDevice, main_stream(ctx)));
+        hipLaunchKernelGGL(fn, dim3(tiles, (unsigned)rows), dim3(tlsdev::kDetrendThreads), lds, main_stream(ctx), a);
         TLS_HIP(ctx, hipGetLastError());
         ctx->last_kernel = "tls_medfilt_detrend";
-        TLS_HIP(ctx, hipMemcpyAsync(out_flat + (size_t)k0 * nn, d_flat, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(out_flat + (size_t)k0 * nn, d_flat, bytes, hipMemcpyDeviceToHost, main_stream(ctx)));
         if (out_trend)
-            TLS_HIP(ctx, hipMemcpyAsync(out_trend + (size_t)k0 * nn, d_trend, bytes, hipMemcpyDeviceToHost, ctx->stream));
+            TLS_HIP(ctx, hipMemcpyAsync(out_trend + (size_t)k0 * nn, d_trend, bytes, hipMemcpyDeviceToHost, main_stream(ctx)));
         // (the next slab overwrites the device rows: the copies above have to be done first)
-        TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));
     }
     return TLS_OK;
 }
@@ -2418,8 +2641,8 @@ int tls_biweight_detrend(tls_ctx* ctx, const double* t, const double* y, int64_t
     double* d_y = ctx->d_detrend.ptr;
     double* d_flat = d_y + (size_t)slab * nn;
     double* d_trend = out_trend ? d_flat + (size_t)slab * nn : nullptr;
-    TLS_HIP(ctx, hipMemcpyAsync(ctx->d_windows.ptr, lo.data(), nn * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(ctx->d_windows.ptr + nn, hi.data(), nn * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(ctx->d_windows.ptr, lo.data(), nn * sizeof(int), hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(ctx->d_windows.ptr + nn, hi.data(), nn * sizeof(int), hipMemcpyHostToDevice, main_stream(ctx)));
     int T = 0, P = 0, smax = 0;
     biweight_plan(lo, hi, wmax, &T, &P, &smax);
     const size_t lds = (size_t)P * (sizeof(unsigned long long) + sizeof(unsigned int)) + (size_t)smax * sizeof(double);
@@ -2437,15 +2660,15 @@ int tls_biweight_detrend(tls_ctx* ctx, const double* t, const double* y, int64_t
     for (int64_t k0 = 0; k0 < n_rows; k0 += slab) {
         const int64_t rows = std::min<int64_t>(slab, n_rows - k0);
         const size_t bytes = (size_t)rows * nn * 8;
-        TLS_HIP(ctx, hipMemcpyAsync(d_y, y + (size_t)k0 * nn, bytes, hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(fn, dim3(tiles, (unsigned)rows), dim3(tlsdev::kDetrendThreads), lds, ctx->stream, a);
+        TLS_HIP(ctx, hipMemcpyAsync(d_y, y + (size_t)k0 * nn, bytes, hipMemcpyHostToDevice, main_stream(ctx)));
+        hipLaunchKernelGGL(fn, dim3(tiles, (unsigned)rows), dim3(tlsdev::kDetrendThreads), lds, main_stream(ctx), a);
         TLS_HIP(ctx, hipGetLastError());
         ctx->last_kernel = "tls_biweight_detrend";
-        TLS_HIP(ctx, hipMemcpyAsync(out_flat + (size_t)k0 * nn, d_flat, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(out_flat + (size_t)k0 * nn, d_flat, bytes, hipMemcpyDeviceToHost, main_stream(ctx)));
         if (out_trend)
-            TLS_HIP(ctx, hipMemcpyAsync(out_trend + (size_t)k0 * nn, d_trend, bytes, hipMemcpyDeviceToHost, ctx->stream));
+            TLS_HIP(ctx, hipMemcpyAsync(out_trend + (size_t)k0 * nn, d_trend, bytes, hipMemcpyDeviceToHost, main_stream(ctx)));
         // (the next slab overwrites the device rows, and lo / hi live on this stack: the copies have to be done first)
-        TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));
     }
     return TLS_OK;
 }
@@ -2495,36 +2718,36 @@ int tls_sysrem(tls_ctx* ctx, const double* y, const double* dy, int64_t n, int64
     a.check = ctx->d_check.ptr;
 #endif
     // one submission: the uploads, every launch of every component and the downloads, then one wait
-    TLS_HIP(ctx, hipMemsetAsync(a.state, 0, tlsdev::kSysremState * sizeof(unsigned long long), ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(d_y, y, cells * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (dy) TLS_HIP(ctx, hipMemcpyAsync(d_dy, dy, cells * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemsetAsync(a.state, 0, tlsdev::kSysremState * sizeof(unsigned long long), main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_y, y, cells * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    if (dy) TLS_HIP(ctx, hipMemcpyAsync(d_dy, dy, cells * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     const dim3 block(tlsdev::kSysremLanes);
     const unsigned tiles = (unsigned)((nn + tlsdev::kSysremLanes - 1) / tlsdev::kSysremLanes);
     const dim3 by_row((unsigned)R), by_column(tiles);
     const dim3 by_chunk(tiles, (unsigned)std::min<size_t>(chunks, 65535)), by_cell(tiles, (unsigned)std::min<size_t>(R, 65535));
-    hipLaunchKernelGGL(tlsdev::tls_sysrem_prepare, by_row, block, 0, ctx->stream, a);
+    hipLaunchKernelGGL(tlsdev::tls_sysrem_prepare, by_row, block, 0, main_stream(ctx), a);
     for (int k = 0; k < (int)n_components; ++k) {
         a.k = k;
         for (int it = 1; it <= (int)max_iter; ++it) {
             a.iter = it;
-            hipLaunchKernelGGL(tlsdev::tls_sysrem_columns, by_chunk, block, 0, ctx->stream, a);
-            hipLaunchKernelGGL(tlsdev::tls_sysrem_epochs, by_column, block, 0, ctx->stream, a);
-            hipLaunchKernelGGL(tlsdev::tls_sysrem_rows, by_row, block, 0, ctx->stream, a);
+            hipLaunchKernelGGL(tlsdev::tls_sysrem_columns, by_chunk, block, 0, main_stream(ctx), a);
+            hipLaunchKernelGGL(tlsdev::tls_sysrem_epochs, by_column, block, 0, main_stream(ctx), a);
+            hipLaunchKernelGGL(tlsdev::tls_sysrem_rows, by_row, block, 0, main_stream(ctx), a);
         }
         TLS_HIP(ctx, hipGetLastError());
-        if (k + 1 < (int)n_components) hipLaunchKernelGGL(tlsdev::tls_sysrem_subtract, by_cell, block, 0, ctx->stream, a);
+        if (k + 1 < (int)n_components) hipLaunchKernelGGL(tlsdev::tls_sysrem_subtract, by_cell, block, 0, main_stream(ctx), a);
     }
-    hipLaunchKernelGGL(tlsdev::tls_sysrem_apply, by_cell, block, 0, ctx->stream, a);
+    hipLaunchKernelGGL(tlsdev::tls_sysrem_apply, by_cell, block, 0, main_stream(ctx), a);
     TLS_HIP(ctx, hipGetLastError());
     ctx->last_kernel = "tls_sysrem_apply";
     unsigned long long state[tlsdev::kSysremState];
     std::vector<double> c_rows(out_c ? K * R : 0);
-    TLS_HIP(ctx, hipMemcpyAsync(out_flat, a.flat, cells * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (out_trend) TLS_HIP(ctx, hipMemcpyAsync(out_trend, a.trend, cells * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (out_c) TLS_HIP(ctx, hipMemcpyAsync(c_rows.data(), a.c, K * R * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (out_a) TLS_HIP(ctx, hipMemcpyAsync(out_a, a.a, K * nn * 8, hipMemcpyDeviceToHost, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(state, a.state, sizeof state, hipMemcpyDeviceToHost, ctx->stream));
-    TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(out_flat, a.flat, cells * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+    if (out_trend) TLS_HIP(ctx, hipMemcpyAsync(out_trend, a.trend, cells * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+    if (out_c) TLS_HIP(ctx, hipMemcpyAsync(c_rows.data(), a.c, K * R * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+    if (out_a) TLS_HIP(ctx, hipMemcpyAsync(out_a, a.a, K * nn * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(state, a.state, sizeof state, hipMemcpyDeviceToHost, main_stream(ctx)));
+    TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));
     if (state[tlsdev::kSysremBad]) {
         const unsigned long long first = ~state[tlsdev::kSysremBad];
         return fail(ctx, TLS_E_ARG, "sysrem: the trend of row " + std::to_string(first / nn) + ", point " +
@@ -2554,31 +2777,31 @@ int tls_spectra(tls_ctx* ctx, const double* chi2, int64_t n, int64_t kernel, dou
     double* d_in = ctx->d_chi2.ptr;
     if (chi2) {
         d_in = ctx->d_spec.ptr + 3 * nn + 2;
-        TLS_HIP(ctx, hipMemcpyAsync(d_in, chi2, nn * 8, hipMemcpyHostToDevice, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(d_in, chi2, nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     }
     tlsdev::SpectraArgs a;
     a.chi2 = d_in; a.SR = ctx->d_spec.ptr; a.power_raw = ctx->d_spec.ptr + nn; a.power = ctx->d_spec.ptr + 2 * nn;
     a.sde = ctx->d_spec.ptr + 3 * nn; a.n = (int)n; a.kernel = (int)kernel; a.detrend = n > 2 * kernel ? 1 : 0;
     a.chi2_stride = 0; a.out_stride = 0; a.sde_stride = 0;
-    hipLaunchKernelGGL(tlsdev::tls_spectra_head, dim3(1), dim3(1024), 0, ctx->stream, a);
+    hipLaunchKernelGGL(tlsdev::tls_spectra_head, dim3(1), dim3(1024), 0, main_stream(ctx), a);
     if (a.detrend) {
         const int n_med = (int)(n - kernel + 1), threads = 256, per = tlsdev::kMedianWindows;
         const size_t lds = (size_t)(2 * per + kernel) * 8;
         hipLaunchKernelGGL(tlsdev::tls_spectra_median, dim3((unsigned)((n_med + per - 1) / per)), dim3(threads), lds,
-                           ctx->stream, a);
-        hipLaunchKernelGGL(tlsdev::tls_spectra_tail, dim3(1), dim3(1024), 0, ctx->stream, a);
+                           main_stream(ctx), a);
+        hipLaunchKernelGGL(tlsdev::tls_spectra_tail, dim3(1), dim3(1024), 0, main_stream(ctx), a);
     }
     TLS_HIP(ctx, hipGetLastError());
     if (out_power_raw == out_SR + nn && out_power == out_power_raw + nn && out_sde == out_power + nn) {
         // the caller's four outputs are one block, like the device's: one copy instead of four
-        TLS_HIP(ctx, hipMemcpyAsync(out_SR, a.SR, (3 * nn + 2) * 8, hipMemcpyDeviceToHost, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(out_SR, a.SR, (3 * nn + 2) * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
     } else {
-        TLS_HIP(ctx, hipMemcpyAsync(out_SR, a.SR, nn * 8, hipMemcpyDeviceToHost, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(out_power_raw, a.power_raw, nn * 8, hipMemcpyDeviceToHost, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(out_power, a.power, nn * 8, hipMemcpyDeviceToHost, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(out_sde, a.sde, 16, hipMemcpyDeviceToHost, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(out_SR, a.SR, nn * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+        TLS_HIP(ctx, hipMemcpyAsync(out_power_raw, a.power_raw, nn * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+        TLS_HIP(ctx, hipMemcpyAsync(out_power, a.power, nn * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+        TLS_HIP(ctx, hipMemcpyAsync(out_sde, a.sde, 16, hipMemcpyDeviceToHost, main_stream(ctx)));
     }
-    TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));
     return TLS_OK;
 }
 
@@ -2594,11 +2817,11 @@ int tls_debug_folded(tls_ctx* ctx, double* out, int64_t capacity) {
     int rc = enqueue(ctx, false, false, d_out.ptr);
     if (rc == TLS_OK) {
         ctx->executed = true;
-        hipError_t e = hipMemcpyAsync(out, d_out.ptr, (size_t)need * 8, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        hipError_t e = hipMemcpyAsync(out, d_out.ptr, (size_t)need * 8, hipMemcpyDeviceToHost, main_stream(ctx));
+        if (e == hipSuccess) e = hipStreamSynchronize(main_stream(ctx));
         if (e != hipSuccess) rc = fail(ctx, TLS_E_HIP, hipGetErrorString(e));
     }
-    if (rc != TLS_OK) (void)hipStreamSynchronize(ctx->stream);
+    if (rc != TLS_OK) (void)hipStreamSynchronize(main_stream(ctx));
     d_out.release();   // (on every path)
     return rc;
 }
@@ -2617,11 +2840,11 @@ int tls_debug_prefix(tls_ctx* ctx, double* out, int64_t capacity, int64_t* row_l
     int rc = enqueue(ctx, false, false, nullptr, d_out.ptr);
     if (rc == TLS_OK) {
         ctx->executed = true;
-        hipError_t e = hipMemcpyAsync(out, d_out.ptr, (size_t)need * 8, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        hipError_t e = hipMemcpyAsync(out, d_out.ptr, (size_t)need * 8, hipMemcpyDeviceToHost, main_stream(ctx));
+        if (e == hipSuccess) e = hipStreamSynchronize(main_stream(ctx));
         if (e != hipSuccess) rc = fail(ctx, TLS_E_HIP, hipGetErrorString(e));
     }
-    if (rc != TLS_OK) (void)hipStreamSynchronize(ctx->stream);
+    if (rc != TLS_OK) (void)hipStreamSynchronize(main_stream(ctx));
     d_out.release();   // (on every path)
     return rc;
 }
@@ -2634,14 +2857,14 @@ int tls_debug_period_cycles(tls_ctx* ctx, uint64_t* cycles, int64_t capacity) {
     TLS_HIP(ctx, hipSetDevice(ctx->device));
     DevBuf<unsigned long long> d_out;
     TLS_HIP(ctx, d_out.reserve((size_t)ctx->plan.n_periods));
-    hipError_t e = hipMemsetAsync(d_out.ptr, 0, (size_t)ctx->plan.n_periods * 8, ctx->stream);
+    hipError_t e = hipMemsetAsync(d_out.ptr, 0, (size_t)ctx->plan.n_periods * 8, main_stream(ctx));
     int rc = e == hipSuccess ? enqueue(ctx, false, false, nullptr, nullptr, d_out.ptr) : fail(ctx, TLS_E_HIP, hipGetErrorString(e));
     if (rc == TLS_OK) {
-        e = hipMemcpyAsync(cycles, d_out.ptr, (size_t)ctx->plan.n_periods * 8, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        e = hipMemcpyAsync(cycles, d_out.ptr, (size_t)ctx->plan.n_periods * 8, hipMemcpyDeviceToHost, main_stream(ctx));
+        if (e == hipSuccess) e = hipStreamSynchronize(main_stream(ctx));
         if (e != hipSuccess) rc = fail(ctx, TLS_E_HIP, hipGetErrorString(e));
     } else {
-        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipStreamSynchronize(main_stream(ctx));
     }
     d_out.release();
     return rc;
@@ -2654,16 +2877,16 @@ int tls_debug_cumsum(tls_ctx* ctx, const double* f, int64_t count, double* out, 
     DevBuf<double> d_f, d_out;
     TLS_HIP(ctx, d_f.reserve((size_t)count));
     TLS_HIP(ctx, d_out.reserve((size_t)count + 1));
-    if (count) TLS_HIP(ctx, hipMemcpyAsync(d_f.ptr, f, (size_t)count * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (count) TLS_HIP(ctx, hipMemcpyAsync(d_f.ptr, f, (size_t)count * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     const int variant = 0;   // (1: the first version of the routine, kept in the kernel for A/B builds)
     // block / fallback counts of this call land in the phase-clock buffer (tls_debug_phase_cycles slots 10, 11)
     TLS_HIP(ctx, ctx->d_phase.reserve(tlsdev::kPhases));
-    TLS_HIP(ctx, hipMemsetAsync(ctx->d_phase.ptr, 0, tlsdev::kPhases * sizeof(unsigned long long), ctx->stream));
-    { const unsigned long long big = ~0ull; TLS_HIP(ctx, hipMemcpyAsync(ctx->d_phase.ptr + 22, &big, 8, hipMemcpyHostToDevice, ctx->stream)); TLS_HIP(ctx, hipStreamSynchronize(ctx->stream)); }
-    hipLaunchKernelGGL(tlsdev::tls_cumsum_kernel, dim3(1), dim3((unsigned)threads), 0, ctx->stream, d_f.ptr, d_out.ptr, (int)count, variant, ctx->d_phase.ptr);
+    TLS_HIP(ctx, hipMemsetAsync(ctx->d_phase.ptr, 0, tlsdev::kPhases * sizeof(unsigned long long), main_stream(ctx)));
+    { const unsigned long long big = ~0ull; TLS_HIP(ctx, hipMemcpyAsync(ctx->d_phase.ptr + 22, &big, 8, hipMemcpyHostToDevice, main_stream(ctx))); TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx))); }
+    hipLaunchKernelGGL(tlsdev::tls_cumsum_kernel, dim3(1), dim3((unsigned)threads), 0, main_stream(ctx), d_f.ptr, d_out.ptr, (int)count, variant, ctx->d_phase.ptr);
     TLS_HIP(ctx, hipGetLastError());
-    TLS_HIP(ctx, hipMemcpyAsync(out, d_out.ptr, ((size_t)count + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-    TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(out, d_out.ptr, ((size_t)count + 1) * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+    TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));
     d_f.release(); d_out.release();
     return TLS_OK;
 }
@@ -2672,7 +2895,7 @@ int tls_debug_phase_cycles(tls_ctx* ctx, uint64_t* cycles, int n) {
     if (!ctx || !cycles || n < 1) return fail(ctx, TLS_E_ARG, "bad argument");
     if (!ctx->d_phase.ptr) return fail(ctx, TLS_E_STATE, "no execute with the phase clock (count_work & 2)");
     TLS_HIP(ctx, hipSetDevice(ctx->device));
-    TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));
     unsigned long long host[tlsdev::kPhases];
     TLS_HIP(ctx, hipMemcpy(host, ctx->d_phase.ptr, sizeof host, hipMemcpyDeviceToHost));
     for (int i = 0; i < n && i < tlsdev::kPhases; ++i) cycles[i] = host[i];
@@ -2694,7 +2917,7 @@ int tls_debug_poison_lds(tls_ctx* ctx, uint32_t word) {
     if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
     TLS_HIP(ctx, hipSetDevice(ctx->device));
     TLS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(tls_poison_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    hipLaunchKernelGGL(tls_poison_lds_kernel, dim3((unsigned)(4 * ctx->n_cu)), dim3(1024), 160 * 1024, ctx->stream, (unsigned int)word,
+    hipLaunchKernelGGL(tls_poison_lds_kernel, dim3((unsigned)(4 * ctx->n_cu)), dim3(1024), 160 * 1024, main_stream(ctx), (unsigned int)word,
                        static_cast<unsigned int*>(nullptr));
     TLS_HIP(ctx, hipGetLastError());
     // ... and the per-workgroup scratch in HBM (slabs, live-unit lists, stashed orders, the screen's and the sorts' scratch, the
@@ -2709,11 +2932,13 @@ int tls_debug_poison_lds(tls_ctx* ctx, uint32_t word) {
     //   d_curve_S0, d_curve_w0 and the batch slots (slot[].d_*)
     //                                     the inputs and results of the survey batches
     auto smear = [&](auto& buf) -> hipError_t {
-        return buf.ptr && buf.cap ? hipMemsetAsync(buf.ptr, 0xFF, buf.cap * sizeof(*buf.ptr), ctx->stream) : hipSuccess;
+        return buf.ptr && buf.cap ? hipMemsetAsync(buf.ptr, 0xFF, buf.cap * sizeof(*buf.ptr), main_stream(ctx)) : hipSuccess;
     };
     TLS_HIP(ctx, smear(ctx->d_scratch));
     TLS_HIP(ctx, smear(ctx->d_lists));
     TLS_HIP(ctx, smear(ctx->d_perm));
+    TLS_HIP(ctx, smear(ctx->lane_b.d_lists));   // (lane B's: on the joined stream, which its next command waits for)
+    TLS_HIP(ctx, smear(ctx->lane_b.d_perm));
     TLS_HIP(ctx, smear(ctx->d_split));
     TLS_HIP(ctx, smear(ctx->d_park));
     TLS_HIP(ctx, smear(ctx->d_partials));
@@ -2796,27 +3021,27 @@ int tls_debug_post_search(tls_ctx* ctx, const double* y, int64_t n_curves, const
     PostSearchBufs pb;
     int rc = reserve_post_search(ctx, n_curves, n_periods, n, max_len, pb);
     if (rc) return rc;
-    TLS_HIP(ctx, hipMemcpyAsync(sl.d_y.ptr, y, gc * nn * 8, hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(sl.d_chi2.ptr, chi2, gc * np * 8, hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(sl.d_row.ptr, row, gc * np * 8, hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(sl.d_depth.ptr, depth, gc * np * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(sl.d_y.ptr, y, gc * nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(sl.d_chi2.ptr, chi2, gc * np * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(sl.d_row.ptr, row, gc * np * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(sl.d_depth.ptr, depth, gc * np * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     if ((rc = enqueue_post_search(ctx, pb, n_curves, sl.d_chi2.ptr, sl.d_row.ptr, sl.d_depth.ptr, sl.d_y.ptr, n, n_periods,
                                   median_kernel, t_min, t_max, k.params.T0_fit_margin))) {
-        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipStreamSynchronize(main_stream(ctx));
         return rc;
     }
     std::vector<double> h(11 * gc);
-    TLS_HIP(ctx, hipMemcpyAsync(h.data(), pb.sde, 11 * gc * 8, hipMemcpyDeviceToHost, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(h.data(), pb.sde, 11 * gc * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
     std::vector<int> nep(gc);
-    TLS_HIP(ctx, hipMemcpyAsync(nep.data(), pb.n_epochs, gc * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    if (out_epochs) TLS_HIP(ctx, hipMemcpyAsync(out_epochs, ctx->d_fep.ptr, gc * nn * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (out_residuals) TLS_HIP(ctx, hipMemcpyAsync(out_residuals, ctx->d_fres.ptr, gc * nn * 8, hipMemcpyDeviceToHost, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(nep.data(), pb.n_epochs, gc * sizeof(int), hipMemcpyDeviceToHost, main_stream(ctx)));
+    if (out_epochs) TLS_HIP(ctx, hipMemcpyAsync(out_epochs, ctx->d_fep.ptr, gc * nn * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+    if (out_residuals) TLS_HIP(ctx, hipMemcpyAsync(out_residuals, ctx->d_fres.ptr, gc * nn * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
     // (the rotation path's flag of every fit: state[1] behind the base order's three arrays, launch_t0_fit's layout)
     const bool rotation = ctx->opt.t0_rot != 0 && n >= tlsdev::kT0RotMinPoints;
     std::vector<double> flag(gc, -1.0);
     if (out_handed_back && rotation)
-        TLS_HIP(ctx, hipMemcpy2DAsync(flag.data(), 8, ctx->d_frot.ptr + 3 * nn + 1, (3 * nn + 4) * 8, 8, gc, hipMemcpyDeviceToHost, ctx->stream));
-    TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        TLS_HIP(ctx, hipMemcpy2DAsync(flag.data(), 8, ctx->d_frot.ptr + 3 * nn + 1, (3 * nn + 4) * 8, 8, gc, hipMemcpyDeviceToHost, main_stream(ctx)));
+    TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));
     for (size_t c = 0; c < gc; ++c) {
         if (out_n_epochs) out_n_epochs[c] = nep[c];
         // (a fit with no trial epoch never ran: its slot of the rotation path holds nothing of it)
@@ -2870,21 +3095,21 @@ static int debug_transit_impl(tls_ctx* ctx, const double* y, int64_t n_curves, c
         pk[6] = no_fit[c] ? 1.0 : 0.0;
         pick[8 * gc + c] = T0[c];
     }
-    TLS_HIP(ctx, hipMemcpyAsync(sl.d_y.ptr, y, gc * nn * 8, hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpy2DAsync(ctx->d_spec.ptr + 2 * np, pb.spec_stride * 8, power, np * 8, np * 8, gc, hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(pb.pick, pick.data(), pick.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(sl.d_y.ptr, y, gc * nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpy2DAsync(ctx->d_spec.ptr + 2 * np, pb.spec_stride * 8, power, np * 8, np * 8, gc, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(pb.pick, pick.data(), pick.size() * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     if ((rc = enqueue_transit_stats(ctx, pb, sb, sr, n_curves, sl.d_y.ptr, n, n_periods, t_min, t_max))) {
-        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipStreamSynchronize(main_stream(ctx));
         return rc;
     }
     if (mr && (rc = enqueue_transit_models(ctx, pb, sb, sr, *mr, mb, n_curves, sl.d_y.ptr, n, t_min, t_max))) {
-        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipStreamSynchronize(main_stream(ctx));
         return rc;
     }
     std::vector<double> h(gc * sr.words()), hm(mr ? gc * mb.out_stride : 0);
-    TLS_HIP(ctx, hipMemcpyAsync(h.data(), pb.stats, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (mr) TLS_HIP(ctx, hipMemcpyAsync(hm.data(), mb.out, hm.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-    TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(h.data(), pb.stats, h.size() * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+    if (mr) TLS_HIP(ctx, hipMemcpyAsync(hm.data(), mb.out, hm.size() * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+    TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));
     ctx->executed = false;   // (the batch slot's buffers were written: as after tls_power_batch)
     for (int64_t c = 0; c < n_curves; ++c)
         if ((rc = read_transit_stats(ctx, sr, h.data(), n_curves, c, c, true))) return rc;
@@ -2966,18 +3191,18 @@ static int debug_peak_fits_impl(tls_ctx* ctx, const double* y, int64_t n_curves,
     if ((rc = reserve_transit_stats(ctx, sr, 0, n, sb))) return rc;
     PeakFitBufs fb;
     if ((rc = reserve_peak_fits(ctx, n_curves * k, n, max_len, max_epochs, fb))) return rc;
-    TLS_HIP(ctx, hipMemcpyAsync(sl.d_y.ptr, y, gc * nn * 8, hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpy2DAsync(ctx->d_spec.ptr + 2 * np, pb.spec_stride * 8, power, np * 8, np * 8, gc, hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(pb.peaks, rec.data(), rec.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(sl.d_y.ptr, y, gc * nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpy2DAsync(ctx->d_spec.ptr + 2 * np, pb.spec_stride * 8, power, np * 8, np * 8, gc, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(pb.peaks, rec.data(), rec.size() * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     if ((rc = enqueue_peak_fits(ctx, fb, pf, sb, n_curves, n_curves, pb.peaks, pb.fits, sl.d_y.ptr, ctx->d_spec.ptr + 2 * np,
                                 pb.spec_stride, n, n_periods, t_min, t_max, key.params.T0_fit_margin, 0, ps, pb.scans))) {
-        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipStreamSynchronize(main_stream(ctx));
         return rc;
     }
     // (fits and scans lie side by side; fit f = c k + r: the scans are already in the caller's order)
     std::vector<double> h(gc * (pf.words() + scans_out));
-    TLS_HIP(ctx, hipMemcpyAsync(h.data(), pb.fits, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-    TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(h.data(), pb.fits, h.size() * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+    TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));
     ctx->executed = false;   // (the batch slot's buffers were written: as after tls_power_batch)
     for (int64_t c = 0; c < n_curves; ++c)
         if ((rc = read_peak_fits(ctx, pf, h.data(), n_curves, c, c))) return rc;
@@ -3016,6 +3241,7 @@ int tls_debug_device_bytes(const tls_ctx* ctx, int64_t* total, int64_t* t0_fit_s
     size_t sum = 0;
     auto add = [&](const auto& b) { sum += b.cap * sizeof(*b.ptr); };
     add(ctx->d_plan); add(ctx->d_out);
+    add(ctx->lane_b.d_squeue); add(ctx->lane_b.d_lists); add(ctx->lane_b.d_perm); add(ctx->lane_b.d_out); add(ctx->lane_b.d_y);
     add(ctx->d_scratch); add(ctx->d_pack); add(ctx->d_gather); add(ctx->d_scalar); add(ctx->d_stage);
     add(ctx->d_phase); add(ctx->d_check);
     add(ctx->d_queue); add(ctx->d_squeue); add(ctx->d_lists); add(ctx->d_perm); add(ctx->d_perm_table); add(ctx->d_pqueues);
@@ -3044,6 +3270,13 @@ int tls_debug_device_bytes(const tls_ctx* ctx, int64_t* total, int64_t* t0_fit_s
     return TLS_OK;
 }
 
+int tls_debug_lanes(const tls_ctx* ctx, int64_t* lane_a, int64_t* lane_b, int64_t* on) {
+    if (!ctx || !lane_a || !lane_b) return TLS_E_ARG;
+    *lane_a = ctx->lane_launches[0]; *lane_b = ctx->lane_launches[1];
+    if (on) *on = ctx->lanes != 0 ? 1 : 0;
+    return TLS_OK;
+}
+
 int tls_debug_perm_table(const tls_ctx* ctx, int64_t* bytes, int64_t* filled, int64_t* plan_reuses) {
     if (!ctx || !bytes || !filled) return TLS_E_ARG;
     if (plan_reuses) *plan_reuses = ctx->plan_reuses;
@@ -3057,7 +3290,7 @@ int tls_debug_check_counts(tls_ctx* ctx, uint64_t* counts, int n) {
     for (int i = 0; i < n; ++i) counts[i] = 0;
 #ifdef TLS_DEBUG_CHECKS
     TLS_HIP(ctx, hipSetDevice(ctx->device));
-    TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));
     if (ctx->d_check.ptr) {
         unsigned long long host[tlsdev::kChecks];
         TLS_HIP(ctx, hipMemcpy(host, ctx->d_check.ptr, sizeof host, hipMemcpyDeviceToHost));
@@ -3072,7 +3305,8 @@ int tls_debug_check_counts(tls_ctx* ctx, uint64_t* counts, int n) {
 int tls_synchronize(tls_ctx* ctx) {
     if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
     TLS_HIP(ctx, hipSetDevice(ctx->device));
-    TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (ctx->lane_b.stream) TLS_HIP(ctx, hipStreamSynchronize(ctx->lane_b.stream));   // (both lanes)
+    TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));
     return TLS_OK;
 }
 
@@ -3082,12 +3316,12 @@ int tls_execute_timed(tls_ctx* ctx, int reps, double* ms_per_execute) {
     if (reps < 1 || !ms_per_execute) return fail(ctx, TLS_E_ARG, "reps must be >= 1");
     TLS_HIP(ctx, hipSetDevice(ctx->device));
     if (ctx->plan.n_periods == 0) { *ms_per_execute = 0; return TLS_OK; }
-    TLS_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    TLS_HIP(ctx, hipEventRecord(ctx->ev0, main_stream(ctx)));
     for (int r = 0; r < reps; ++r) {
         int rc = enqueue(ctx, false);
         if (rc) return rc;
     }
-    TLS_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+    TLS_HIP(ctx, hipEventRecord(ctx->ev1, main_stream(ctx)));
     TLS_HIP(ctx, hipEventSynchronize(ctx->ev1));
     float ms = 0;
     TLS_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
@@ -3112,14 +3346,14 @@ int tls_fetch(tls_ctx* ctx, double* out_chi2, int64_t* out_row, double* out_dept
             TLS_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->h_out), (words + words / 4) * 8, hipHostMallocDefault));
             ctx->h_out_cap = words + words / 4;
         }
-        TLS_HIP(ctx, hipMemcpyAsync(ctx->h_out, ctx->d_out.ptr, words * 8, hipMemcpyDeviceToHost, ctx->stream));
-        TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(ctx->h_out, ctx->d_latest.ptr, words * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+        TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));
         std::memcpy(out_chi2, ctx->h_out, np * 8);
         std::memcpy(out_row, ctx->h_out + np, np * 8);
         std::memcpy(out_depth, ctx->h_out + 2 * np, np * 8);
         std::memcpy(dev_counts, ctx->h_out + 3 * np, sizeof dev_counts);
     } else {
-        TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));
     }
     if (counters) {
         *counters = ctx->plan_counters;
@@ -3130,21 +3364,54 @@ int tls_fetch(tls_ctx* ctx, double* out_chi2, int64_t* out_row, double* out_dept
     return TLS_OK;
 }
 
-int tls_kernel_timing(tls_ctx* ctx, int reset, double* total_ms, int64_t* launches) {
-    if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
+namespace {
+// what every launch in the event ring is charged, in ring order (both lanes waited for)
+int launch_terms(tls_ctx* ctx, std::vector<double>& terms) {
     TLS_HIP(ctx, hipSetDevice(ctx->device));
-    TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    double sum = 0;
+    if (ctx->lane_b.stream) TLS_HIP(ctx, hipStreamSynchronize(ctx->lane_b.stream));   // (both lanes)
+    TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));
     const size_t n_timed = std::min(ctx->ev_used, ctx->ev_pool.size());
+    terms.assign(n_timed, 0.0);
+    // An overlapped launch's own pair starts when its marker runs -- up to a whole launch before its workgroups find room on
+    // the device.  It is charged the shorter of its own pair and (end of the launch before it -> its own end), so that the sum
+    // over a run of overlapped launches is the time the run took and the mean stays a per-search figure.
+    const size_t oldest = ctx->ev_used > kEventRing ? ctx->ev_used % kEventRing : 0;   // (its predecessor's slot holds a newer launch)
     for (size_t i = 0; i < n_timed; ++i) {
         float ms = 0;
         TLS_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev_pool[i].first, ctx->ev_pool[i].second));
-        sum += ms;
+        if (ctx->ev_overlapped[i] && i != oldest) {
+            float since_prev = 0;
+            // (a launch that ended before its predecessor did keeps its own pair)
+            if (hipEventElapsedTime(&since_prev, ctx->ev_pool[(i + kEventRing - 1) % kEventRing].second, ctx->ev_pool[i].second) != hipSuccess) {
+                (void)hipGetLastError();
+                since_prev = 0;
+            }
+            if (since_prev > 0 && since_prev < ms) ms = since_prev;
+        }
+        terms[i] = ms;
     }
+    return TLS_OK;
+}
+}  // namespace
+
+int tls_kernel_timing(tls_ctx* ctx, int reset, double* total_ms, int64_t* launches) {
+    if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
+    std::vector<double> terms;
+    if (int rc = launch_terms(ctx, terms)) return rc;
+    double sum = 0;
+    for (double ms : terms) sum += ms;
     if (total_ms) *total_ms = sum;
-    if (launches) *launches = (int64_t)n_timed;
+    if (launches) *launches = (int64_t)terms.size();
     if (reset) ctx->ev_used = 0;
     return TLS_OK;
+}
+
+int tls_debug_launch_ms(tls_ctx* ctx, double* out, int64_t capacity) {
+    if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
+    std::vector<double> terms;
+    if (int rc = launch_terms(ctx, terms)) return rc;
+    if (out) for (size_t i = 0; i < terms.size() && (int64_t)i < capacity; ++i) out[i] = terms[i];
+    return (int)terms.size();
 }
 
 const char* tls_last_kernel(const tls_ctx* ctx) { return ctx ? ctx->last_kernel : ""; }
@@ -3202,9 +3469,9 @@ static int search_batch_impl(tls_ctx* ctx, const double* y, const double* dy, in
         if (g >= 2 && (rc = drain(g - 2))) return rc;           // the slot's buffers are free again
         if ((rc = stage_group(ctx, sl, y, dy, n, c0, gc, group, st)) || (rc = upload_group(ctx, sl, st, nn, ctx->copy_stream))) return rc;
         TLS_HIP(ctx, hipEventRecord(sl.ev_in, ctx->copy_stream));
-        TLS_HIP(ctx, hipStreamWaitEvent(ctx->stream, sl.ev_in, 0));
+        TLS_HIP(ctx, hipStreamWaitEvent(main_stream(ctx), sl.ev_in, 0));
         if ((rc = search_group(ctx, sl, st))) return rc;
-        TLS_HIP(ctx, hipEventRecord(sl.ev_kernel, ctx->stream));
+        TLS_HIP(ctx, hipEventRecord(sl.ev_kernel, main_stream(ctx)));
         TLS_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, sl.ev_kernel, 0));
         TLS_HIP(ctx, hipMemcpyAsync(sl.h_out, sl.d_chi2.ptr, (size_t)gc * np * 8, hipMemcpyDeviceToHost, ctx->copy_stream));
         TLS_HIP(ctx, hipMemcpyAsync(sl.h_out + (size_t)group * np, sl.d_row.ptr, (size_t)gc * np * 8, hipMemcpyDeviceToHost, ctx->copy_stream));
@@ -3405,20 +3672,20 @@ int tls_phase_scan(tls_ctx* ctx, const double* t, const double* y, int64_t n, in
     double* d_duration = d_T0 + fits;
     double* d_out = d_duration + fits;
     int* d_curve = reinterpret_cast<int*>(d_out + words * fits);
-    TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(d_y, y, rows * nn * 8, hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(d_period, period, fits * 8, hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(d_T0, T0, fits * 8, hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(d_duration, duration, fits * 8, hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(d_curve, h_curve.data(), fits * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_y, y, rows * nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_period, period, fits * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_T0, T0, fits * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_duration, duration, fits * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_curve, h_curve.data(), fits * sizeof(int), hipMemcpyHostToDevice, main_stream(ctx)));
     if ((rc = enqueue_phase_scan(ctx, ps, n_fits, d_t, d_y, n, d_curve, d_period, 1, d_T0, d_duration, 1, nullptr, d_out))) {
-        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipStreamSynchronize(main_stream(ctx));
         return rc;
     }
     ctx->last_kernel = "tls_phase_scan";
-    TLS_HIP(ctx, hipMemcpyAsync(out, d_out, words * fits * 8, hipMemcpyDeviceToHost, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(out, d_out, words * fits * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
     // (h_curve is read by the copy above until the stream is done)
-    TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));
     return TLS_OK;
 }
 
@@ -3479,34 +3746,34 @@ int tls_single_transits(tls_ctx* ctx, const double* t, const double* y, const do
     auto select = tlsdev::tls_single_select_kernel;
     TLS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(statistic), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     TLS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(select), hipFuncAttributeMaxDynamicSharedMemorySize, (int)select_lds));
-    TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(d_rows, tb.rows.data(), (size_t)n_rows * sizeof(tlsdev::SingleRow), hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(d_taps, tb.taps.data(), 2 * n_taps * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_rows, tb.rows.data(), (size_t)n_rows * sizeof(tlsdev::SingleRow), hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_taps, tb.taps.data(), 2 * n_taps * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     const unsigned tiles = (unsigned)((n + tlsdev::kSingleTile - 1) / tlsdev::kSingleTile);
     std::vector<int> h_row(out_row ? sl * nn : 0);
     for (int64_t k0 = 0; k0 < n_curves; k0 += slab) {
         const int64_t curves = std::min<int64_t>(slab, n_curves - k0);
         const size_t bytes = (size_t)curves * nn * 8, first = (size_t)k0 * nn;
-        TLS_HIP(ctx, hipMemcpyAsync(d_y, y + first, bytes, hipMemcpyHostToDevice, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(d_dy, dy + first, bytes, hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(statistic, dim3(tiles, (unsigned)curves), dim3(tlsdev::kSingleThreads), lds, ctx->stream, a);
+        TLS_HIP(ctx, hipMemcpyAsync(d_y, y + first, bytes, hipMemcpyHostToDevice, main_stream(ctx)));
+        TLS_HIP(ctx, hipMemcpyAsync(d_dy, dy + first, bytes, hipMemcpyHostToDevice, main_stream(ctx)));
+        hipLaunchKernelGGL(statistic, dim3(tiles, (unsigned)curves), dim3(tlsdev::kSingleThreads), lds, main_stream(ctx), a);
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) {
-            hipLaunchKernelGGL(select, dim3((unsigned)curves), dim3(tlsdev::kSingleSelectThreads), select_lds, ctx->stream, s);
+            hipLaunchKernelGGL(select, dim3((unsigned)curves), dim3(tlsdev::kSingleSelectThreads), select_lds, main_stream(ctx), s);
             e = hipGetLastError();
         }
         if (e != hipSuccess) {
-            (void)hipStreamSynchronize(ctx->stream);
+            (void)hipStreamSynchronize(main_stream(ctx));
             return fail(ctx, TLS_E_HIP, std::string("single transits launch: ") + hipGetErrorString(e));
         }
         ctx->last_kernel = "tls_single_transits";
-        TLS_HIP(ctx, hipMemcpyAsync(out_events + (size_t)k0 * (size_t)k, d_events, (size_t)curves * words * 8, hipMemcpyDeviceToHost, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(out_n_events + k0, d_n_events, (size_t)curves * 8, hipMemcpyDeviceToHost, ctx->stream));
-        if (out_ses) TLS_HIP(ctx, hipMemcpyAsync(out_ses + first, d_ses, bytes, hipMemcpyDeviceToHost, ctx->stream));
-        if (out_depth) TLS_HIP(ctx, hipMemcpyAsync(out_depth + first, d_depth, bytes, hipMemcpyDeviceToHost, ctx->stream));
-        if (out_row) TLS_HIP(ctx, hipMemcpyAsync(h_row.data(), d_row, (size_t)curves * nn * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(out_events + (size_t)k0 * (size_t)k, d_events, (size_t)curves * words * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+        TLS_HIP(ctx, hipMemcpyAsync(out_n_events + k0, d_n_events, (size_t)curves * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+        if (out_ses) TLS_HIP(ctx, hipMemcpyAsync(out_ses + first, d_ses, bytes, hipMemcpyDeviceToHost, main_stream(ctx)));
+        if (out_depth) TLS_HIP(ctx, hipMemcpyAsync(out_depth + first, d_depth, bytes, hipMemcpyDeviceToHost, main_stream(ctx)));
+        if (out_row) TLS_HIP(ctx, hipMemcpyAsync(h_row.data(), d_row, (size_t)curves * nn * sizeof(int), hipMemcpyDeviceToHost, main_stream(ctx)));
         // (the next slab overwrites the device rows, and tb is read by the copies above until the stream is done)
-        TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));
         if (out_row) for (size_t i = 0; i < (size_t)curves * nn; ++i) out_row[first + i] = h_row[i];
     }
     return TLS_OK;
@@ -3575,10 +3842,10 @@ int tls_transit_times(tls_ctx* ctx, const double* t, const double* y, const doub
     auto times_kernel = tlsdev::tls_transit_times_kernel;
     TLS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(times_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                      tlsdev::kTimesLdsUnits * 8));
-    TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(d_rows, tb.rows.data(), (size_t)n_rows * sizeof(tlsdev::SingleRow), hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(d_taps, tb.taps.data(), 2 * n_taps * 8, hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(d_slopes, tb.slopes.data(), 3 * n_taps * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_rows, tb.rows.data(), (size_t)n_rows * sizeof(tlsdev::SingleRow), hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_taps, tb.taps.data(), 2 * n_taps * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_slopes, tb.slopes.data(), 3 * n_taps * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     const SlabStage stage{"transit times", "tls_transit_times", curve, n_fits, nn, cs, sl,
                           {{d_y, y}, {d_dy, dy}}, {{d_period, period}, {d_T0, T0}}, d_ints, 3};
     return run_candidate_slabs(ctx, stage,
@@ -3589,11 +3856,11 @@ int tls_transit_times(tls_ctx* ctx, const double* t, const double* y, const doub
         },
         [&](const SlabView& s) {
             if (launch_times_pairs(ctx, p, s.curves, nn))
-                hipLaunchKernelGGL(times_kernel, dim3((unsigned)s.fits), dim3(tlsdev::kTimesThreads), s.lds, ctx->stream, a);
+                hipLaunchKernelGGL(times_kernel, dim3((unsigned)s.fits), dim3(tlsdev::kTimesThreads), s.lds, main_stream(ctx), a);
         },
         [&](const SlabView& s) {
-            TLS_HIP(ctx, hipMemcpyAsync(out + s.f0, d_out, s.fits * eph_words * 8, hipMemcpyDeviceToHost, ctx->stream));
-            TLS_HIP(ctx, hipMemcpyAsync(out_times + (size_t)s.f0 * me, d_out_times, s.fits * time_words * 8, hipMemcpyDeviceToHost, ctx->stream));
+            TLS_HIP(ctx, hipMemcpyAsync(out + s.f0, d_out, s.fits * eph_words * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+            TLS_HIP(ctx, hipMemcpyAsync(out_times + (size_t)s.f0 * me, d_out_times, s.fits * time_words * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
             return TLS_OK;
         });
 }
@@ -3679,9 +3946,9 @@ int tls_event_vetting(tls_ctx* ctx, const double* t, const double* y, const doub
     auto events_kernel = tlsdev::tls_event_vetting_kernel;
     TLS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(events_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                      tlsdev::kTimesLdsUnits * 8));
-    TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(d_rows, tb.rows.data(), (size_t)n_rows * sizeof(tlsdev::SingleRow), hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(d_taps, tb.taps.data(), 2 * n_taps * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_rows, tb.rows.data(), (size_t)n_rows * sizeof(tlsdev::SingleRow), hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_taps, tb.taps.data(), 2 * n_taps * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     const SlabStage stage{"event vetting", "tls_event_vetting", curve, n_fits, nn, cs, sl,
                           {{d_y, y}, {d_dy, dy}}, {{d_period, period}, {d_T0, T0}, {d_span, chase_span}}, d_ints, 5};
     return run_candidate_slabs(ctx, stage,
@@ -3694,11 +3961,11 @@ int tls_event_vetting(tls_ctx* ctx, const double* t, const double* y, const doub
         },
         [&](const SlabView& s) {
             if (launch_times_pairs(ctx, p, s.curves, nn))
-                hipLaunchKernelGGL(events_kernel, dim3((unsigned)s.fits), dim3(tlsdev::kEventsThreads), s.lds, ctx->stream, a);
+                hipLaunchKernelGGL(events_kernel, dim3((unsigned)s.fits), dim3(tlsdev::kEventsThreads), s.lds, main_stream(ctx), a);
         },
         [&](const SlabView& s) {
-            TLS_HIP(ctx, hipMemcpyAsync(out + s.f0, d_out, s.fits * sum_words * 8, hipMemcpyDeviceToHost, ctx->stream));
-            TLS_HIP(ctx, hipMemcpyAsync(out_events + (size_t)s.f0 * me, d_out_events, s.fits * event_words * 8, hipMemcpyDeviceToHost, ctx->stream));
+            TLS_HIP(ctx, hipMemcpyAsync(out + s.f0, d_out, s.fits * sum_words * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+            TLS_HIP(ctx, hipMemcpyAsync(out_events + (size_t)s.f0 * me, d_out_events, s.fits * event_words * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
             return TLS_OK;
         });
 }
@@ -3766,20 +4033,20 @@ int tls_shape_fit(tls_ctx* ctx, const double* t, const double* y, const double* 
     a.check = ctx->d_check.ptr; a.window = window; a.depth_min = depth_min;
     a.n = (int)n; a.nT = (int)nT; a.nQ = (int)nQ; a.nS = (int)nS;
     a.min_count = (int)std::min<int64_t>(min_count, INT32_MAX);
-    TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(d_ratio, ratio, (size_t)nT * 8, hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(d_ingress, ingress, (size_t)nQ * 8, hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(d_shift, shift, (size_t)nS * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_ratio, ratio, (size_t)nT * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_ingress, ingress, (size_t)nQ * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_shift, shift, (size_t)nS * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     const SlabStage stage{"shape fit", "tls_shape_fit", curve, n_fits, nn, cs, sl,
                           {{d_y, y}, {d_dy, dy}}, {{d_period, period}, {d_T0, T0}, {d_duration, duration}}, d_slot, 1};
     return run_candidate_slabs(ctx, stage, no_int_columns,
         [&](const SlabView& s) {
             a.fits = (int)s.fits;
             if (launch_times_pairs(ctx, p, s.curves, nn))
-                hipLaunchKernelGGL(tlsdev::tls_shape_fit_kernel, dim3((unsigned)std::min(s.fits, groups)), dim3(tlsdev::kShapeThreads), 0, ctx->stream, a);
+                hipLaunchKernelGGL(tlsdev::tls_shape_fit_kernel, dim3((unsigned)std::min(s.fits, groups)), dim3(tlsdev::kShapeThreads), 0, main_stream(ctx), a);
         },
         [&](const SlabView& s) {
-            TLS_HIP(ctx, hipMemcpyAsync(out + s.f0, d_out, s.fits * words * 8, hipMemcpyDeviceToHost, ctx->stream));
+            TLS_HIP(ctx, hipMemcpyAsync(out + s.f0, d_out, s.fits * words * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
             return TLS_OK;
         });
 }
@@ -3840,17 +4107,17 @@ int tls_centroid_test(tls_ctx* ctx, const double* t, const double* y, const doub
     a.n = (int)n; a.L = (int)L; a.max_epochs = (int)max_epochs;
     a.min_in = (int)std::min<int64_t>(min_in, INT32_MAX);
     a.min_out = (int)std::min<int64_t>(min_out, INT32_MAX);
-    TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(d_b, shape, ll * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_b, shape, ll * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     const SlabStage stage{"centroid test", "tls_centroid_test", curve, n_fits, nn, cs, sl,
                           {{d_y, y}, {d_cx, cx}, {d_cy, cy}}, {{d_period, period}, {d_T0, T0}, {d_duration, duration}}, d_slot, 1};
     return run_candidate_slabs(ctx, stage, no_int_columns,
         [&](const SlabView& s) {
             a.fits = (int)s.fits;
-            hipLaunchKernelGGL(tlsdev::tls_centroid_kernel, dim3((unsigned)std::min(s.fits, groups)), dim3(tlsdev::kCentroidThreads), 0, ctx->stream, a);
+            hipLaunchKernelGGL(tlsdev::tls_centroid_kernel, dim3((unsigned)std::min(s.fits, groups)), dim3(tlsdev::kCentroidThreads), 0, main_stream(ctx), a);
         },
         [&](const SlabView& s) {
-            TLS_HIP(ctx, hipMemcpyAsync(out + s.f0, d_out, s.fits * words * 8, hipMemcpyDeviceToHost, ctx->stream));
+            TLS_HIP(ctx, hipMemcpyAsync(out + s.f0, d_out, s.fits * words * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
             return TLS_OK;
         });
 }
@@ -3913,21 +4180,21 @@ int tls_folded_views(tls_ctx* ctx, const double* t, const double* y, int64_t n, 
     a.scratch = d_scratch; a.out = d_out; a.global_median = d_gmed; a.global_count = d_gcnt; a.local_median = d_lmed;
     a.local_count = d_lcnt; a.check = ctx->d_check.ptr; a.k = local_durations; a.width = local_width;
     a.n = (int)n; a.n_global = (int)n_global; a.n_local = (int)n_local;
-    TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     const SlabStage stage{"folded views", "tls_folded_views", curve, n_fits, nn, cs, sl, {{d_y, y}},
                           {{d_period, period}, {d_T0, T0}, {d_duration, duration}, {d_secondary, secondary_phase}}, d_slot, 1};
     return run_candidate_slabs(ctx, stage, no_int_columns,
         [&](const SlabView& s) {
             a.fits = (int)s.fits;
-            hipLaunchKernelGGL(tlsdev::tls_folded_views_kernel, dim3((unsigned)std::min(s.fits, groups)), dim3(tlsdev::kViewsThreads), 0, ctx->stream, a);
+            hipLaunchKernelGGL(tlsdev::tls_folded_views_kernel, dim3((unsigned)std::min(s.fits, groups)), dim3(tlsdev::kViewsThreads), 0, main_stream(ctx), a);
         },
         [&](const SlabView& s) {
             const size_t f0 = (size_t)s.f0;
-            TLS_HIP(ctx, hipMemcpyAsync(out + f0, d_out, s.fits * words * 8, hipMemcpyDeviceToHost, ctx->stream));
-            TLS_HIP(ctx, hipMemcpyAsync(global_median + f0 * ng, d_gmed, s.fits * ng * 8, hipMemcpyDeviceToHost, ctx->stream));
-            TLS_HIP(ctx, hipMemcpyAsync(global_count + f0 * ng, d_gcnt, s.fits * ng * 4, hipMemcpyDeviceToHost, ctx->stream));
-            TLS_HIP(ctx, hipMemcpyAsync(local_median + f0 * nl, d_lmed, s.fits * nl * 8, hipMemcpyDeviceToHost, ctx->stream));
-            TLS_HIP(ctx, hipMemcpyAsync(local_count + f0 * nl, d_lcnt, s.fits * nl * 4, hipMemcpyDeviceToHost, ctx->stream));
+            TLS_HIP(ctx, hipMemcpyAsync(out + f0, d_out, s.fits * words * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+            TLS_HIP(ctx, hipMemcpyAsync(global_median + f0 * ng, d_gmed, s.fits * ng * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+            TLS_HIP(ctx, hipMemcpyAsync(global_count + f0 * ng, d_gcnt, s.fits * ng * 4, hipMemcpyDeviceToHost, main_stream(ctx)));
+            TLS_HIP(ctx, hipMemcpyAsync(local_median + f0 * nl, d_lmed, s.fits * nl * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+            TLS_HIP(ctx, hipMemcpyAsync(local_count + f0 * nl, d_lcnt, s.fits * nl * 4, hipMemcpyDeviceToHost, main_stream(ctx)));
             return TLS_OK;
         });
 }
@@ -3957,10 +4224,10 @@ int enqueue_nudft(tls_ctx* ctx, const double* d_A, int64_t R, int64_t lda, int64
     a.A = d_A; a.t = d_t; a.f = d_f; a.out = d_out; a.lda = (long long)lda; a.R = (int)R; a.n = (int)n; a.F = (int)F;
     const unsigned gx = (unsigned)((F + tlsdev::kGlsFreqTile - 1) / tlsdev::kGlsFreqTile);
     if (R <= tlsdev::kGlsSmallRows)
-        hipLaunchKernelGGL(tlsdev::tls_nudft_kernel<1>, dim3(gx, 1), dim3(tlsdev::kGlsThreads), 0, ctx->stream, a);
+        hipLaunchKernelGGL(tlsdev::tls_nudft_kernel<1>, dim3(gx, 1), dim3(tlsdev::kGlsThreads), 0, main_stream(ctx), a);
     else
         hipLaunchKernelGGL(tlsdev::tls_nudft_kernel<4>, dim3(gx, (unsigned)((R + tlsdev::kGlsRowTile - 1) / tlsdev::kGlsRowTile)),
-                           dim3(tlsdev::kGlsThreads), 0, ctx->stream, a);
+                           dim3(tlsdev::kGlsThreads), 0, main_stream(ctx), a);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(ctx, TLS_E_HIP, std::string("nudft launch: ") + hipGetErrorString(e));
     ctx->last_kernel = "tls_nudft";
@@ -3991,14 +4258,14 @@ int tls_nudft(tls_ctx* ctx, const double* rows, int64_t n_rows, int64_t n, const
     double* d_rows = ctx->d_gls.ptr + 2 * (size_t)slab * nf;
     double* d_t = d_rows + (size_t)slab * nn;
     double* d_f = d_t + nn;
-    TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(d_f, frequencies, nf * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_f, frequencies, nf * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     for (int64_t k0 = 0; k0 < n_rows; k0 += slab) {
         const int64_t R = std::min<int64_t>(slab, n_rows - k0);
-        TLS_HIP(ctx, hipMemcpyAsync(d_rows, rows + (size_t)k0 * nn, (size_t)R * nn * 8, hipMemcpyHostToDevice, ctx->stream));
-        if ((rc = enqueue_nudft(ctx, d_rows, R, n, n, d_t, d_f, n_freq, d_out))) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-        TLS_HIP(ctx, hipMemcpyAsync(out + 2 * (size_t)k0 * nf, d_out, (size_t)R * nf * 16, hipMemcpyDeviceToHost, ctx->stream));
-        TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));       // (the next slab overwrites the device buffers)
+        TLS_HIP(ctx, hipMemcpyAsync(d_rows, rows + (size_t)k0 * nn, (size_t)R * nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+        if ((rc = enqueue_nudft(ctx, d_rows, R, n, n, d_t, d_f, n_freq, d_out))) { (void)hipStreamSynchronize(main_stream(ctx)); return rc; }
+        TLS_HIP(ctx, hipMemcpyAsync(out + 2 * (size_t)k0 * nf, d_out, (size_t)R * nf * 16, hipMemcpyDeviceToHost, main_stream(ctx)));
+        TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));       // (the next slab overwrites the device buffers)
     }
     return TLS_OK;
 }
@@ -4048,54 +4315,54 @@ int tls_lomb_scargle(tls_ctx* ctx, const double* t, const double* y, const doubl
     double* d_peaks = d_periods + nf;
     std::vector<double> twice(nf), periods(nf), h_peaks(sl * words);
     for (size_t i = 0; i < nf; ++i) { twice[i] = 2.0 * frequencies[i]; periods[i] = 1.0 / frequencies[i]; }
-    TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(d_f, frequencies, nf * 8, hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(d_f2, twice.data(), nf * 8, hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(d_periods, periods.data(), nf * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_f, frequencies, nf * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_f2, twice.data(), nf * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_periods, periods.data(), nf * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     std::vector<double> h_sums;
     for (int64_t k0 = 0; k0 < n_curves; k0 += slab) {
         const int64_t R = std::min<int64_t>(slab, n_curves - k0), Rw = dy ? R : 1;
         const size_t at = (size_t)k0 * nn, bytes = (size_t)R * nn * 8, spec = (size_t)R * nf * 8;
-        TLS_HIP(ctx, hipMemcpyAsync(d_y, y + at, bytes, hipMemcpyHostToDevice, ctx->stream));
-        if (dy) TLS_HIP(ctx, hipMemcpyAsync(d_dy, dy + at, bytes, hipMemcpyHostToDevice, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(d_y, y + at, bytes, hipMemcpyHostToDevice, main_stream(ctx)));
+        if (dy) TLS_HIP(ctx, hipMemcpyAsync(d_dy, dy + at, bytes, hipMemcpyHostToDevice, main_stream(ctx)));
         tlsdev::GlsPrologueArgs p;
         p.y = d_y; p.dy = d_dy; p.rows = d_a; p.weights = d_w; p.mean = d_mean; p.variance = d_var; p.n = (int)n;
-        hipLaunchKernelGGL(tlsdev::tls_gls_prologue_kernel, dim3((unsigned)R), dim3(tlsdev::kGlsThreads), 0, ctx->stream, p);
+        hipLaunchKernelGGL(tlsdev::tls_gls_prologue_kernel, dim3((unsigned)R), dim3(tlsdev::kGlsThreads), 0, main_stream(ctx), p);
         hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); return fail(ctx, TLS_E_HIP, std::string("periodogram launch: ") + hipGetErrorString(e)); }
-        if ((rc = enqueue_nudft(ctx, d_a, R, n, n, d_t, d_f, n_freq, d_yc))) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+        if (e != hipSuccess) { (void)hipStreamSynchronize(main_stream(ctx)); return fail(ctx, TLS_E_HIP, std::string("periodogram launch: ") + hipGetErrorString(e)); }
+        if ((rc = enqueue_nudft(ctx, d_a, R, n, n, d_t, d_f, n_freq, d_yc))) { (void)hipStreamSynchronize(main_stream(ctx)); return rc; }
         if (dy || k0 == 0) {                         // (the one shared weight row: once)
             if ((rc = enqueue_nudft(ctx, d_w, Rw, n, n, d_t, d_f, n_freq, d_cs))
-                || (rc = enqueue_nudft(ctx, d_w, Rw, n, n, d_t, d_f2, n_freq, d_cs2))) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+                || (rc = enqueue_nudft(ctx, d_w, Rw, n, n, d_t, d_f2, n_freq, d_cs2))) { (void)hipStreamSynchronize(main_stream(ctx)); return rc; }
         }
         tlsdev::GlsEpilogueArgs g;
         g.yc = d_yc; g.cs = d_cs; g.cs2 = d_cs2; g.variance = d_var; g.power = d_power; g.amplitude = d_amplitude; g.phase = d_phase;
         g.count = (long long)R * (long long)n_freq; g.F = (int)n_freq; g.shared_weights = dy ? 0 : 1;
         const unsigned blocks = (unsigned)std::min<long long>((g.count + tlsdev::kGlsThreads - 1) / tlsdev::kGlsThreads, 16384);
-        hipLaunchKernelGGL(tlsdev::tls_gls_epilogue_kernel, dim3(blocks), dim3(tlsdev::kGlsThreads), 0, ctx->stream, g);
+        hipLaunchKernelGGL(tlsdev::tls_gls_epilogue_kernel, dim3(blocks), dim3(tlsdev::kGlsThreads), 0, main_stream(ctx), g);
         e = hipGetLastError();
-        if (e != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); return fail(ctx, TLS_E_HIP, std::string("periodogram launch: ") + hipGetErrorString(e)); }
+        if (e != hipSuccess) { (void)hipStreamSynchronize(main_stream(ctx)); return fail(ctx, TLS_E_HIP, std::string("periodogram launch: ") + hipGetErrorString(e)); }
         if (k && (rc = enqueue_find_peaks(ctx, pk, R, n_freq, d_power, nf, d_periods, nullptr, nullptr, nullptr, nullptr, d_peaks))) {
-            (void)hipStreamSynchronize(ctx->stream);
+            (void)hipStreamSynchronize(main_stream(ctx));
             return rc;
         }
         ctx->last_kernel = "tls_lomb_scargle";
-        TLS_HIP(ctx, hipMemcpyAsync(out_mean + k0, d_mean, (size_t)R * 8, hipMemcpyDeviceToHost, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(out_variance + k0, d_var, (size_t)R * 8, hipMemcpyDeviceToHost, ctx->stream));
-        if (out_power) TLS_HIP(ctx, hipMemcpyAsync(out_power + (size_t)k0 * nf, d_power, spec, hipMemcpyDeviceToHost, ctx->stream));
-        if (out_amplitude) TLS_HIP(ctx, hipMemcpyAsync(out_amplitude + (size_t)k0 * nf, d_amplitude, spec, hipMemcpyDeviceToHost, ctx->stream));
-        if (out_phase) TLS_HIP(ctx, hipMemcpyAsync(out_phase + (size_t)k0 * nf, d_phase, spec, hipMemcpyDeviceToHost, ctx->stream));
-        if (out_rows) TLS_HIP(ctx, hipMemcpyAsync(out_rows + at, d_a, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(out_mean + k0, d_mean, (size_t)R * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+        TLS_HIP(ctx, hipMemcpyAsync(out_variance + k0, d_var, (size_t)R * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+        if (out_power) TLS_HIP(ctx, hipMemcpyAsync(out_power + (size_t)k0 * nf, d_power, spec, hipMemcpyDeviceToHost, main_stream(ctx)));
+        if (out_amplitude) TLS_HIP(ctx, hipMemcpyAsync(out_amplitude + (size_t)k0 * nf, d_amplitude, spec, hipMemcpyDeviceToHost, main_stream(ctx)));
+        if (out_phase) TLS_HIP(ctx, hipMemcpyAsync(out_phase + (size_t)k0 * nf, d_phase, spec, hipMemcpyDeviceToHost, main_stream(ctx)));
+        if (out_rows) TLS_HIP(ctx, hipMemcpyAsync(out_rows + at, d_a, bytes, hipMemcpyDeviceToHost, main_stream(ctx)));
         if (out_weights && (dy || k0 == 0))
-            TLS_HIP(ctx, hipMemcpyAsync(out_weights + (dy ? at : 0), d_w, (size_t)Rw * nn * 8, hipMemcpyDeviceToHost, ctx->stream));
-        if (k) TLS_HIP(ctx, hipMemcpyAsync(h_peaks.data(), d_peaks, (size_t)R * words * 8, hipMemcpyDeviceToHost, ctx->stream));
+            TLS_HIP(ctx, hipMemcpyAsync(out_weights + (dy ? at : 0), d_w, (size_t)Rw * nn * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+        if (k) TLS_HIP(ctx, hipMemcpyAsync(h_peaks.data(), d_peaks, (size_t)R * words * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
         if (out_sums) {
             h_sums.resize(2 * ((size_t)R + 2 * (size_t)Rw) * nf);
-            TLS_HIP(ctx, hipMemcpyAsync(h_sums.data(), d_yc, (size_t)R * nf * 16, hipMemcpyDeviceToHost, ctx->stream));
-            TLS_HIP(ctx, hipMemcpyAsync(h_sums.data() + 2 * (size_t)R * nf, d_cs, (size_t)Rw * nf * 16, hipMemcpyDeviceToHost, ctx->stream));
-            TLS_HIP(ctx, hipMemcpyAsync(h_sums.data() + 2 * ((size_t)R + (size_t)Rw) * nf, d_cs2, (size_t)Rw * nf * 16, hipMemcpyDeviceToHost, ctx->stream));
+            TLS_HIP(ctx, hipMemcpyAsync(h_sums.data(), d_yc, (size_t)R * nf * 16, hipMemcpyDeviceToHost, main_stream(ctx)));
+            TLS_HIP(ctx, hipMemcpyAsync(h_sums.data() + 2 * (size_t)R * nf, d_cs, (size_t)Rw * nf * 16, hipMemcpyDeviceToHost, main_stream(ctx)));
+            TLS_HIP(ctx, hipMemcpyAsync(h_sums.data() + 2 * ((size_t)R + (size_t)Rw) * nf, d_cs2, (size_t)Rw * nf * 16, hipMemcpyDeviceToHost, main_stream(ctx)));
         }
-        TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));       // (the next slab overwrites the device buffers)
+        TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));       // (the next slab overwrites the device buffers)
         if (k) for (int64_t c = 0; c < R; ++c) read_peaks(pk, h_peaks.data(), c, k0 + c);
         if (out_sums) {
             const double* yc = h_sums.data();
@@ -4154,20 +4421,20 @@ int tls_sine_test(tls_ctx* ctx, const double* t, const double* y, const double* 
     a.t = d_t; a.y = d_y; a.dy = dy ? d_dy : nullptr; a.slot = d_slot; a.period = d_period;
     a.T0 = T0 ? d_T0 : nullptr; a.duration = T0 ? d_duration : nullptr; a.harmonics = d_harmonics;
     a.out = d_out; a.out_h = d_out_h; a.out_sums = out_sums ? d_sums : nullptr; a.mask = mask; a.n = (int)n; a.nH = (int)n_harmonics;
-    TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(d_harmonics, harmonics, nH * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_harmonics, harmonics, nH * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     const SlabStage stage{"sine test", "tls_sine_test", curve, n_fits, nn, cs, sl,
                           {{d_y, y}, {d_dy, dy}}, {{d_period, period}, {d_T0, T0}, {d_duration, duration}}, d_slot, 1};
     return run_candidate_slabs(ctx, stage, no_int_columns,
         [&](const SlabView& s) {
             a.fits = (int)s.fits;
-            hipLaunchKernelGGL(tlsdev::tls_sine_test_kernel, dim3((unsigned)s.fits), dim3(tlsdev::kSineThreads), 0, ctx->stream, a);
+            hipLaunchKernelGGL(tlsdev::tls_sine_test_kernel, dim3((unsigned)s.fits), dim3(tlsdev::kSineThreads), 0, main_stream(ctx), a);
         },
         [&](const SlabView& s) {
             const size_t f0 = (size_t)s.f0;
-            TLS_HIP(ctx, hipMemcpyAsync(out + f0, d_out, s.fits * sizeof(tls_sine_record), hipMemcpyDeviceToHost, ctx->stream));
-            TLS_HIP(ctx, hipMemcpyAsync(out_harmonics + f0 * nH, d_out_h, s.fits * nH * sizeof(tls_sine_harmonic), hipMemcpyDeviceToHost, ctx->stream));
-            if (out_sums) TLS_HIP(ctx, hipMemcpyAsync(out_sums + f0 * nH * 6, d_sums, s.fits * nH * 48, hipMemcpyDeviceToHost, ctx->stream));
+            TLS_HIP(ctx, hipMemcpyAsync(out + f0, d_out, s.fits * sizeof(tls_sine_record), hipMemcpyDeviceToHost, main_stream(ctx)));
+            TLS_HIP(ctx, hipMemcpyAsync(out_harmonics + f0 * nH, d_out_h, s.fits * nH * sizeof(tls_sine_harmonic), hipMemcpyDeviceToHost, main_stream(ctx)));
+            if (out_sums) TLS_HIP(ctx, hipMemcpyAsync(out_sums + f0 * nH * 6, d_sums, s.fits * nH * 48, hipMemcpyDeviceToHost, main_stream(ctx)));
             return TLS_OK;
         });
 }
@@ -4238,79 +4505,79 @@ int tls_prewhiten(tls_ctx* ctx, const double* t, const double* y, const double* 
     std::vector<double> blank(sl * KH * (words + 6), (double)NAN);
     for (size_t q = 0; q < sl * KH; ++q) blank[q * words] = 2.0;
     std::vector<int> ones(sl, 1);
-    TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(d_f, frequencies, nf * 8, hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(d_f2, twice.data(), nf * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_f, frequencies, nf * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_f2, twice.data(), nf * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     auto launched = [&](const char* what) -> int {
         const hipError_t e = hipGetLastError();
         if (e == hipSuccess) return TLS_OK;
-        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipStreamSynchronize(main_stream(ctx));
         return fail(ctx, TLS_E_HIP, std::string("prewhiten ") + what + " launch: " + hipGetErrorString(e));
     };
     for (int64_t k0 = 0; k0 < n_curves; k0 += (int64_t)sl) {
         const int64_t R = std::min<int64_t>((int64_t)sl, n_curves - k0), Rw = dy ? R : 1;
         const size_t at = (size_t)k0 * nn, rows = (size_t)R, bytes = rows * nn * 8;
-        TLS_HIP(ctx, hipMemcpyAsync(d_y, y + at, bytes, hipMemcpyHostToDevice, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(d_r, d_y, bytes, hipMemcpyDeviceToDevice, ctx->stream));
-        if (dy) TLS_HIP(ctx, hipMemcpyAsync(d_dy, dy + at, bytes, hipMemcpyHostToDevice, ctx->stream));
-        TLS_HIP(ctx, hipMemsetAsync(d_trend, 0, bytes, ctx->stream));
-        TLS_HIP(ctx, hipMemsetAsync(d_status, 0, rows * 8, ctx->stream));
-        TLS_HIP(ctx, hipMemsetAsync(d_iterations, 0, (sl + K) * 8, ctx->stream));            // (and the counts behind them)
-        TLS_HIP(ctx, hipMemcpyAsync(d_active, ones.data(), rows * 4, hipMemcpyHostToDevice, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(d_terms, blank.data(), rows * KH * words * 8, hipMemcpyHostToDevice, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(d_sums, blank.data() + sl * KH * words, rows * KH * 48, hipMemcpyHostToDevice, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(d_y, y + at, bytes, hipMemcpyHostToDevice, main_stream(ctx)));
+        TLS_HIP(ctx, hipMemcpyAsync(d_r, d_y, bytes, hipMemcpyDeviceToDevice, main_stream(ctx)));
+        if (dy) TLS_HIP(ctx, hipMemcpyAsync(d_dy, dy + at, bytes, hipMemcpyHostToDevice, main_stream(ctx)));
+        TLS_HIP(ctx, hipMemsetAsync(d_trend, 0, bytes, main_stream(ctx)));
+        TLS_HIP(ctx, hipMemsetAsync(d_status, 0, rows * 8, main_stream(ctx)));
+        TLS_HIP(ctx, hipMemsetAsync(d_iterations, 0, (sl + K) * 8, main_stream(ctx)));            // (and the counts behind them)
+        TLS_HIP(ctx, hipMemcpyAsync(d_active, ones.data(), rows * 4, hipMemcpyHostToDevice, main_stream(ctx)));
+        TLS_HIP(ctx, hipMemcpyAsync(d_terms, blank.data(), rows * KH * words * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+        TLS_HIP(ctx, hipMemcpyAsync(d_sums, blank.data() + sl * KH * words, rows * KH * 48, hipMemcpyHostToDevice, main_stream(ctx)));
         int64_t ran = 0;
         for (int64_t j = 0; j < n_terms; ++j) {
             tlsdev::GlsPrologueArgs p;
             p.y = d_r; p.dy = d_dy; p.rows = d_a; p.weights = d_w; p.mean = j == 0 ? d_mean0 : d_mean; p.variance = d_var; p.n = (int)n;
-            hipLaunchKernelGGL(tlsdev::tls_gls_prologue_kernel, dim3((unsigned)R), dim3(tlsdev::kGlsThreads), 0, ctx->stream, p);
+            hipLaunchKernelGGL(tlsdev::tls_gls_prologue_kernel, dim3((unsigned)R), dim3(tlsdev::kGlsThreads), 0, main_stream(ctx), p);
             if ((rc = launched("prologue"))) return rc;
-            if ((rc = enqueue_nudft(ctx, d_a, R, n, n, d_t, d_f, n_freq, d_yc))) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+            if ((rc = enqueue_nudft(ctx, d_a, R, n, n, d_t, d_f, n_freq, d_yc))) { (void)hipStreamSynchronize(main_stream(ctx)); return rc; }
             if (j == 0 && (dy || k0 == 0)) {         // (the sums of the weights: once a call, or once a slab with dy)
                 if ((rc = enqueue_nudft(ctx, d_w, Rw, n, n, d_t, d_f, n_freq, d_cs))
-                    || (rc = enqueue_nudft(ctx, d_w, Rw, n, n, d_t, d_f2, n_freq, d_cs2))) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+                    || (rc = enqueue_nudft(ctx, d_w, Rw, n, n, d_t, d_f2, n_freq, d_cs2))) { (void)hipStreamSynchronize(main_stream(ctx)); return rc; }
             }
             tlsdev::GlsEpilogueArgs g;
             g.yc = d_yc; g.cs = d_cs; g.cs2 = d_cs2; g.variance = d_var; g.power = d_power; g.amplitude = d_amplitude; g.phase = d_phase;
             g.count = (long long)R * (long long)n_freq; g.F = (int)n_freq; g.shared_weights = dy ? 0 : 1;
             const unsigned blocks = (unsigned)std::min<long long>((g.count + tlsdev::kGlsThreads - 1) / tlsdev::kGlsThreads, 16384);
-            hipLaunchKernelGGL(tlsdev::tls_gls_epilogue_kernel, dim3(blocks), dim3(tlsdev::kGlsThreads), 0, ctx->stream, g);
+            hipLaunchKernelGGL(tlsdev::tls_gls_epilogue_kernel, dim3(blocks), dim3(tlsdev::kGlsThreads), 0, main_stream(ctx), g);
             if ((rc = launched("epilogue"))) return rc;
             tlsdev::PrewhitenArgs a;
             a.t = d_t; a.f = d_f; a.dy = d_dy; a.power = d_power; a.r = d_r; a.trend = d_trend; a.terms = d_terms; a.sums = d_sums;
             a.steps = d_steps; a.active = d_active; a.n_iterations = d_iterations; a.status = d_status; a.counts = d_counts;
             a.min_power = min_power; a.n = (int)n; a.F = (int)n_freq; a.R = (int)R; a.K = (int)n_terms; a.H = (int)n_harmonics; a.j = (int)j;
-            hipLaunchKernelGGL(step_kernel, dim3((unsigned)R), dim3(tlsdev::kPrewhitenThreads), lds_bytes, ctx->stream, a);
+            hipLaunchKernelGGL(step_kernel, dim3((unsigned)R), dim3(tlsdev::kPrewhitenThreads), lds_bytes, main_stream(ctx), a);
             if ((rc = launched("step"))) return rc;
             ctx->last_kernel = "tls_prewhiten";
             ran = j + 1;
             if (j + 1 < n_terms) {
                 unsigned long long going = 0;
-                TLS_HIP(ctx, hipMemcpyAsync(&going, d_counts + j, 8, hipMemcpyDeviceToHost, ctx->stream));
-                TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+                TLS_HIP(ctx, hipMemcpyAsync(&going, d_counts + j, 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+                TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));
                 if (going == 0) break;
             }
         }
         // (the steps no iteration reached, and the one behind the last, hold the final rows)
         if (d_steps)
             for (size_t s = (size_t)ran * (size_t)n_harmonics; s <= KH; ++s)
-                TLS_HIP(ctx, hipMemcpyAsync(d_steps + s * rows * nn, d_r, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+                TLS_HIP(ctx, hipMemcpyAsync(d_steps + s * rows * nn, d_r, bytes, hipMemcpyDeviceToDevice, main_stream(ctx)));
         tlsdev::PrewhitenFinishArgs fin;
         fin.y = d_y; fin.mean0 = d_mean0; fin.trend = d_trend; fin.flat = d_a; fin.count = (long long)R * (long long)n; fin.n = (int)n;
         const unsigned fblocks = (unsigned)std::min<long long>((fin.count + tlsdev::kPrewhitenThreads - 1) / tlsdev::kPrewhitenThreads, 16384);
-        hipLaunchKernelGGL(tlsdev::tls_prewhiten_finish_kernel, dim3(fblocks), dim3(tlsdev::kPrewhitenThreads), 0, ctx->stream, fin);
+        hipLaunchKernelGGL(tlsdev::tls_prewhiten_finish_kernel, dim3(fblocks), dim3(tlsdev::kPrewhitenThreads), 0, main_stream(ctx), fin);
         if ((rc = launched("finish"))) return rc;
-        TLS_HIP(ctx, hipMemcpyAsync(out_flat + at, d_a, bytes, hipMemcpyDeviceToHost, ctx->stream));
-        if (out_trend) TLS_HIP(ctx, hipMemcpyAsync(out_trend + at, d_trend, bytes, hipMemcpyDeviceToHost, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(out_terms + (size_t)k0 * KH, d_terms, rows * KH * words * 8, hipMemcpyDeviceToHost, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(out_n_iterations + k0, d_iterations, rows * 8, hipMemcpyDeviceToHost, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(out_status + k0, d_status, rows * 8, hipMemcpyDeviceToHost, ctx->stream));
-        if (out_sums) TLS_HIP(ctx, hipMemcpyAsync(out_sums + (size_t)k0 * KH * 6, d_sums, rows * KH * 48, hipMemcpyDeviceToHost, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(out_flat + at, d_a, bytes, hipMemcpyDeviceToHost, main_stream(ctx)));
+        if (out_trend) TLS_HIP(ctx, hipMemcpyAsync(out_trend + at, d_trend, bytes, hipMemcpyDeviceToHost, main_stream(ctx)));
+        TLS_HIP(ctx, hipMemcpyAsync(out_terms + (size_t)k0 * KH, d_terms, rows * KH * words * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+        TLS_HIP(ctx, hipMemcpyAsync(out_n_iterations + k0, d_iterations, rows * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+        TLS_HIP(ctx, hipMemcpyAsync(out_status + k0, d_status, rows * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+        if (out_sums) TLS_HIP(ctx, hipMemcpyAsync(out_sums + (size_t)k0 * KH * 6, d_sums, rows * KH * 48, hipMemcpyDeviceToHost, main_stream(ctx)));
         if (out_steps)
             for (size_t s = 0; s <= KH; ++s)
                 TLS_HIP(ctx, hipMemcpyAsync(out_steps + s * (size_t)n_curves * nn + at, d_steps + s * rows * nn, bytes,
-                                            hipMemcpyDeviceToHost, ctx->stream));
-        TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));       // (the next slab overwrites the device buffers)
+                                            hipMemcpyDeviceToHost, main_stream(ctx)));
+        TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));       // (the next slab overwrites the device buffers)
     }
     return TLS_OK;
 }
@@ -4347,11 +4614,11 @@ int tls_ephemeris_match(tls_ctx* ctx, const int64_t* star, const double* period,
     double* d_strength = d_duration + nn;
     double* d_out = d_strength + nn;
     double* d_partial = d_out + words * nn;
-    TLS_HIP(ctx, hipMemcpyAsync(d_star, star, nn * 8, hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(d_period, period, nn * 8, hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(d_T0, T0, nn * 8, hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(d_duration, duration, nn * 8, hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(d_strength, strength, nn * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_star, star, nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_period, period, nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_T0, T0, nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_duration, duration, nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_strength, strength, nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     tlsdev::MatchArgs a;
     a.star = reinterpret_cast<const long long*>(d_star);
     a.period = d_period; a.T0 = d_T0; a.duration = d_duration; a.strength = d_strength;
@@ -4359,19 +4626,19 @@ int tls_ephemeris_match(tls_ctx* ctx, const int64_t* star, const double* period,
     a.span = span; a.drift_tolerance = drift_tolerance; a.epoch_tolerance = epoch_tolerance; a.max_ratio = (double)max_ratio;
     a.n = (int)n; a.tiles = tiles; a.chunks = chunks;
     hipLaunchKernelGGL(tlsdev::tls_match_pairs_kernel, dim3((unsigned)tiles, (unsigned)chunks), dim3(tlsdev::kMatchTile), 0,
-                       ctx->stream, a);
+                       main_stream(ctx), a);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(tlsdev::tls_match_combine_kernel, dim3((unsigned)tiles), dim3(tlsdev::kMatchTile), 0, ctx->stream, a);
+        hipLaunchKernelGGL(tlsdev::tls_match_combine_kernel, dim3((unsigned)tiles), dim3(tlsdev::kMatchTile), 0, main_stream(ctx), a);
         e = hipGetLastError();
     }
     if (e != hipSuccess) {
-        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipStreamSynchronize(main_stream(ctx));
         return fail(ctx, TLS_E_HIP, std::string("ephemeris match launch: ") + hipGetErrorString(e));
     }
     ctx->last_kernel = "tls_ephemeris_match";
-    TLS_HIP(ctx, hipMemcpyAsync(out, d_out, words * nn * 8, hipMemcpyDeviceToHost, ctx->stream));
-    TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(out, d_out, words * nn * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+    TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));
     return TLS_OK;
 }
 
@@ -4434,9 +4701,9 @@ int tls_noise_profile(tls_ctx* ctx, const double* t, const double* y, int64_t n,
     double* d_mask = d_v + S * W * nn;
     std::vector<int> w32((size_t)n_widths);
     for (size_t k = 0; k < W; ++k) w32[k] = (int)widths[k];
-    if (t) TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(d_span, span_max, W * 8, hipMemcpyHostToDevice, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(d_widths, w32.data(), W * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (t) TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_span, span_max, W * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_widths, w32.data(), W * 4, hipMemcpyHostToDevice, main_stream(ctx)));
     const size_t curve_lds = tlsdev::noise_curve_lds_bytes((int)n, lds), width_lds = tlsdev::noise_width_lds_bytes((int)n, lds);
     auto curve_kernel = lds ? tlsdev::tls_noise_curve_kernel<true> : tlsdev::tls_noise_curve_kernel<false>;
     auto width_kernel = lds ? tlsdev::tls_noise_width_kernel<true> : tlsdev::tls_noise_width_kernel<false>;
@@ -4455,23 +4722,23 @@ int tls_noise_profile(tls_ctx* ctx, const double* t, const double* y, int64_t n,
 #endif
     for (int64_t k0 = 0; k0 < n_curves; k0 += slab) {
         const size_t rows = (size_t)std::min<int64_t>(slab, n_curves - k0);
-        TLS_HIP(ctx, hipMemcpyAsync(d_y, y + (size_t)k0 * nn, rows * nn * 8, hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(curve_kernel, dim3((unsigned)rows), dim3(tlsdev::kNoiseThreads), curve_lds, ctx->stream, a);
+        TLS_HIP(ctx, hipMemcpyAsync(d_y, y + (size_t)k0 * nn, rows * nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+        hipLaunchKernelGGL(curve_kernel, dim3((unsigned)rows), dim3(tlsdev::kNoiseThreads), curve_lds, main_stream(ctx), a);
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) {
-            hipLaunchKernelGGL(width_kernel, dim3((unsigned)W, (unsigned)rows), dim3(tlsdev::kNoiseThreads), width_lds, ctx->stream, a);
+            hipLaunchKernelGGL(width_kernel, dim3((unsigned)W, (unsigned)rows), dim3(tlsdev::kNoiseThreads), width_lds, main_stream(ctx), a);
             e = hipGetLastError();
         }
         if (e != hipSuccess) {
-            (void)hipStreamSynchronize(ctx->stream);
+            (void)hipStreamSynchronize(main_stream(ctx));
             return fail(ctx, TLS_E_HIP, std::string("noise profile launch: ") + hipGetErrorString(e));
         }
         ctx->last_kernel = "tls_noise_profile";
-        TLS_HIP(ctx, hipMemcpyAsync(out_curves + k0, d_records, rows * tlsdev::kNoiseWords * 8, hipMemcpyDeviceToHost, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(out_count + (size_t)k0 * W, d_count, rows * W * 8, hipMemcpyDeviceToHost, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(out_robust + (size_t)k0 * W, d_robust, rows * W * 8, hipMemcpyDeviceToHost, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(out_rms + (size_t)k0 * W, d_rms, rows * W * 8, hipMemcpyDeviceToHost, ctx->stream));
-        TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));       // (the next slab overwrites the device buffers; w32 lives until here)
+        TLS_HIP(ctx, hipMemcpyAsync(out_curves + k0, d_records, rows * tlsdev::kNoiseWords * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+        TLS_HIP(ctx, hipMemcpyAsync(out_count + (size_t)k0 * W, d_count, rows * W * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+        TLS_HIP(ctx, hipMemcpyAsync(out_robust + (size_t)k0 * W, d_robust, rows * W * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+        TLS_HIP(ctx, hipMemcpyAsync(out_rms + (size_t)k0 * W, d_rms, rows * W * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+        TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));       // (the next slab overwrites the device buffers; w32 lives until here)
     }
     return TLS_OK;
 }
@@ -4505,22 +4772,22 @@ int tls_find_peaks(tls_ctx* ctx, const double* power, const double* chi2, const 
     if (depth) { d_depth = d_next; d_next += (size_t)slab * np; }
     if (row) d_row = reinterpret_cast<long long*>(d_next);
     std::vector<double> h((size_t)slab * words);
-    TLS_HIP(ctx, hipMemcpyAsync(d_periods, periods, np * 8, hipMemcpyHostToDevice, ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(d_periods, periods, np * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     for (int64_t k0 = 0; k0 < n_rows; k0 += slab) {
         const int64_t rows = std::min<int64_t>(slab, n_rows - k0);
         const size_t bytes = (size_t)rows * np * 8, at = (size_t)k0 * np;
-        TLS_HIP(ctx, hipMemcpyAsync(d_power, power + at, bytes, hipMemcpyHostToDevice, ctx->stream));
-        if (chi2) TLS_HIP(ctx, hipMemcpyAsync(d_chi2, chi2 + at, bytes, hipMemcpyHostToDevice, ctx->stream));
-        if (depth) TLS_HIP(ctx, hipMemcpyAsync(d_depth, depth + at, bytes, hipMemcpyHostToDevice, ctx->stream));
-        if (row) TLS_HIP(ctx, hipMemcpyAsync(d_row, row + at, bytes, hipMemcpyHostToDevice, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(d_power, power + at, bytes, hipMemcpyHostToDevice, main_stream(ctx)));
+        if (chi2) TLS_HIP(ctx, hipMemcpyAsync(d_chi2, chi2 + at, bytes, hipMemcpyHostToDevice, main_stream(ctx)));
+        if (depth) TLS_HIP(ctx, hipMemcpyAsync(d_depth, depth + at, bytes, hipMemcpyHostToDevice, main_stream(ctx)));
+        if (row) TLS_HIP(ctx, hipMemcpyAsync(d_row, row + at, bytes, hipMemcpyHostToDevice, main_stream(ctx)));
         if ((rc = enqueue_find_peaks(ctx, pk, rows, n_periods, d_power, np, d_periods, d_chi2, d_row, d_depth, nullptr, d_out))) {
-            (void)hipStreamSynchronize(ctx->stream);
+            (void)hipStreamSynchronize(main_stream(ctx));
             return rc;
         }
         ctx->last_kernel = "tls_find_peaks";
-        TLS_HIP(ctx, hipMemcpyAsync(h.data(), d_out, (size_t)rows * words * 8, hipMemcpyDeviceToHost, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(h.data(), d_out, (size_t)rows * words * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
         // (the next slab overwrites the device rows: the copies above have to be done first)
-        TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));
         for (int64_t c = 0; c < rows; ++c) read_peaks(pk, h.data(), c, k0 + c);
     }
     return TLS_OK;
@@ -4611,7 +4878,7 @@ static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, cons
         auto& hs = ctx->slot[g & 1];
         const int64_t c0 = g * group, gc = std::min(group, n_curves - c0);
         int rc2 = stage_group(ctx, hs, y, dy, n, c0, gc, group, st);
-        if (rc2 || (rc2 = upload_group(ctx, sl, st, nn, ctx->stream)) || (rc2 = search_group(ctx, sl, st))) return rc2;
+        if (rc2 || (rc2 = upload_group(ctx, sl, st, nn, main_stream(ctx))) || (rc2 = search_group(ctx, sl, st))) return rc2;
         // ---- spectra, pick and final T0 fit of every curve of the group
         rc2 = enqueue_post_search(ctx, pb, gc, sl.d_chi2.ptr, sl.d_row.ptr, sl.d_depth.ptr, sl.d_y.ptr, n, n_periods, median_kernel,
                                   t_min, t_max, params->T0_fit_margin);
@@ -4627,22 +4894,22 @@ static int power_batch_impl(tls_ctx* ctx, const double* t, const double* y, cons
         if (mr && (rc2 = enqueue_transit_models(ctx, pb, sb, *sr, *mr, mb, gc, sl.d_y.ptr, n, t_min, t_max))) return rc2;
         // (sde | pick | T0 [| statistics] [| peaks [| peak fits [| phase scans]]] lie side by side behind the spectra on the device: ONE copy, the host keeps the layout)
         const OutLayout o = out_layout(g);
-        TLS_HIP(ctx, hipMemcpyAsync(o.sde, pb.sde, (11 + stats_out + peaks_out + fits_out + scans_out) * (size_t)group * 8, hipMemcpyDeviceToHost, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(o.sde, pb.sde, (11 + stats_out + peaks_out + fits_out + scans_out) * (size_t)group * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
         if (out_chi2) {
-            TLS_HIP(ctx, hipMemcpyAsync(o.chi2, sl.d_chi2.ptr, (size_t)gc * np * 8, hipMemcpyDeviceToHost, ctx->stream));
-            TLS_HIP(ctx, hipMemcpyAsync(o.chi2 + (size_t)group * np, sl.d_row.ptr, (size_t)gc * np * 8, hipMemcpyDeviceToHost, ctx->stream));
-            TLS_HIP(ctx, hipMemcpyAsync(o.chi2 + 2 * (size_t)group * np, sl.d_depth.ptr, (size_t)gc * np * 8, hipMemcpyDeviceToHost, ctx->stream));
+            TLS_HIP(ctx, hipMemcpyAsync(o.chi2, sl.d_chi2.ptr, (size_t)gc * np * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+            TLS_HIP(ctx, hipMemcpyAsync(o.chi2 + (size_t)group * np, sl.d_row.ptr, (size_t)gc * np * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+            TLS_HIP(ctx, hipMemcpyAsync(o.chi2 + 2 * (size_t)group * np, sl.d_depth.ptr, (size_t)gc * np * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
         }
         // (SR | power_raw | power lie side by side per light curve: all three asked for = one contiguous copy, else one strided copy each)
         auto fetch_spec = [&](double* host, size_t which) -> hipError_t {
-            return hipMemcpy2DAsync(host, np * 8, ctx->d_spec.ptr + which * np, spec_stride * 8, np * 8, (size_t)gc, hipMemcpyDeviceToHost, ctx->stream);
+            return hipMemcpy2DAsync(host, np * 8, ctx->d_spec.ptr + which * np, spec_stride * 8, np * 8, (size_t)gc, hipMemcpyDeviceToHost, main_stream(ctx));
         };
-        if (o.spec3) TLS_HIP(ctx, hipMemcpyAsync(o.spec3, ctx->d_spec.ptr, (size_t)gc * spec_stride * 8, hipMemcpyDeviceToHost, ctx->stream));
+        if (o.spec3) TLS_HIP(ctx, hipMemcpyAsync(o.spec3, ctx->d_spec.ptr, (size_t)gc * spec_stride * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
         if (o.power) TLS_HIP(ctx, fetch_spec(o.power, 2));
         if (o.SR) TLS_HIP(ctx, fetch_spec(o.SR, 0));
         if (o.praw) TLS_HIP(ctx, fetch_spec(o.praw, 1));
-        if (o.models) TLS_HIP(ctx, hipMemcpyAsync(o.models, mb.out, (size_t)gc * mb.out_stride * 8, hipMemcpyDeviceToHost, ctx->stream));
-        TLS_HIP(ctx, hipEventRecord(hs.ev_out, ctx->stream));
+        if (o.models) TLS_HIP(ctx, hipMemcpyAsync(o.models, mb.out, (size_t)gc * mb.out_stride * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+        TLS_HIP(ctx, hipEventRecord(hs.ev_out, main_stream(ctx)));
         return TLS_OK;
     };
     // ---- results of group g: the ONE wait of the group, then the caller's arrays
@@ -4888,13 +5155,13 @@ int tls_comm_allgather_device(tls_ctx* ctx, int64_t count_per_rank) {
     // pack [chi2 | row | depth] of this shard, zero padded: 24 B per period
     TLS_HIP(ctx, ctx->d_pack.reserve(3 * c));
     TLS_HIP(ctx, ctx->d_gather.reserve(3 * c * R));
-    TLS_HIP(ctx, hipMemsetAsync(ctx->d_pack.ptr, 0, 3 * c * 8, ctx->stream));
+    TLS_HIP(ctx, hipMemsetAsync(ctx->d_pack.ptr, 0, 3 * c * 8, main_stream(ctx)));
     if (np) {
-        TLS_HIP(ctx, hipMemcpyAsync(ctx->d_pack.ptr, ctx->d_chi2.ptr, np * 8, hipMemcpyDeviceToDevice, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(ctx->d_pack.ptr + c, ctx->d_row.ptr, np * 8, hipMemcpyDeviceToDevice, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(ctx->d_pack.ptr + 2 * c, ctx->d_depth.ptr, np * 8, hipMemcpyDeviceToDevice, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(ctx->d_pack.ptr, ctx->d_chi2.ptr, np * 8, hipMemcpyDeviceToDevice, main_stream(ctx)));
+        TLS_HIP(ctx, hipMemcpyAsync(ctx->d_pack.ptr + c, ctx->d_row.ptr, np * 8, hipMemcpyDeviceToDevice, main_stream(ctx)));
+        TLS_HIP(ctx, hipMemcpyAsync(ctx->d_pack.ptr + 2 * c, ctx->d_depth.ptr, np * 8, hipMemcpyDeviceToDevice, main_stream(ctx)));
     }
-    TLS_NCCL(ctx, ncclAllGather(ctx->d_pack.ptr, ctx->d_gather.ptr, 3 * c, ncclDouble, ctx->comm, ctx->stream));
+    TLS_NCCL(ctx, ncclAllGather(ctx->d_pack.ptr, ctx->d_gather.ptr, 3 * c, ncclDouble, ctx->comm, main_stream(ctx)));
     ctx->gathered_count = (int64_t)c;
     return TLS_OK;
 }
@@ -4908,8 +5175,8 @@ int tls_comm_fetch_gathered(tls_ctx* ctx, int64_t count_per_rank, double* all_ch
     TLS_HIP(ctx, hipSetDevice(ctx->device));
     const size_t c = (size_t)count_per_rank, R = (size_t)ctx->n_ranks;
     std::vector<double> host(3 * c * R);
-    TLS_HIP(ctx, hipMemcpyAsync(host.data(), ctx->d_gather.ptr, host.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-    TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(host.data(), ctx->d_gather.ptr, host.size() * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+    TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));
     for (size_t r = 0; r < R; ++r) {
         const double* blk = host.data() + r * 3 * c;
         std::memcpy(all_chi2 + r * c, blk, c * 8);
@@ -4928,11 +5195,11 @@ int tls_comm_stage_results(tls_ctx* ctx, int64_t count_per_rank, int64_t slot, i
     const size_t c = (size_t)count_per_rank, np = (size_t)ctx->plan.n_periods;
     TLS_HIP(ctx, ctx->d_stage.reserve(3 * c * (size_t)n_slots));
     double* dst = ctx->d_stage.ptr + 3 * c * (size_t)slot;   // [chi2 | row | depth] of this slot, 24 B per period
-    if (np < c) TLS_HIP(ctx, hipMemsetAsync(dst, 0, 3 * c * 8, ctx->stream));
+    if (np < c) TLS_HIP(ctx, hipMemsetAsync(dst, 0, 3 * c * 8, main_stream(ctx)));
     if (np) {
-        TLS_HIP(ctx, hipMemcpyAsync(dst, ctx->d_chi2.ptr, np * 8, hipMemcpyDeviceToDevice, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(dst + c, ctx->d_row.ptr, np * 8, hipMemcpyDeviceToDevice, ctx->stream));
-        TLS_HIP(ctx, hipMemcpyAsync(dst + 2 * c, ctx->d_depth.ptr, np * 8, hipMemcpyDeviceToDevice, ctx->stream));
+        TLS_HIP(ctx, hipMemcpyAsync(dst, ctx->d_chi2.ptr, np * 8, hipMemcpyDeviceToDevice, main_stream(ctx)));
+        TLS_HIP(ctx, hipMemcpyAsync(dst + c, ctx->d_row.ptr, np * 8, hipMemcpyDeviceToDevice, main_stream(ctx)));
+        TLS_HIP(ctx, hipMemcpyAsync(dst + 2 * c, ctx->d_depth.ptr, np * 8, hipMemcpyDeviceToDevice, main_stream(ctx)));
     }
     return TLS_OK;
 }
@@ -4945,7 +5212,7 @@ int tls_comm_allgather_staged(tls_ctx* ctx, int64_t count_per_rank, int64_t n_sl
     if (ctx->d_stage.cap < per_rank) return fail(ctx, TLS_E_STATE, "nothing staged for that layout");
     TLS_HIP(ctx, hipSetDevice(ctx->device));
     TLS_HIP(ctx, ctx->d_gather.reserve(per_rank * (size_t)ctx->n_ranks));
-    TLS_NCCL(ctx, ncclAllGather(ctx->d_stage.ptr, ctx->d_gather.ptr, per_rank, ncclDouble, ctx->comm, ctx->stream));
+    TLS_NCCL(ctx, ncclAllGather(ctx->d_stage.ptr, ctx->d_gather.ptr, per_rank, ncclDouble, ctx->comm, main_stream(ctx)));
     ctx->gathered_count = -(int64_t)per_rank;   // marks a staged gather (tls_comm_fetch_gathered refuses it)
     return TLS_OK;
 }
@@ -4962,8 +5229,8 @@ int tls_comm_fetch_staged(tls_ctx* ctx, int64_t count_per_rank, int64_t n_slots,
     std::vector<double> host(3 * c);
     for (size_t r = 0; r < R; ++r) {
         TLS_HIP(ctx, hipMemcpyAsync(host.data(), ctx->d_gather.ptr + r * per_rank + 3 * c * (size_t)slot, 3 * c * 8,
-                                    hipMemcpyDeviceToHost, ctx->stream));
-        TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+                                    hipMemcpyDeviceToHost, main_stream(ctx)));
+        TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));
         std::memcpy(all_chi2 + r * c, host.data(), c * 8);
         std::memcpy(all_row + r * c, host.data() + c, c * 8);  // int64 bit patterns travel as 8-byte words
         std::memcpy(all_depth + r * c, host.data() + 2 * c, c * 8);
@@ -4981,10 +5248,10 @@ int tls_comm_max(tls_ctx* ctx, double* value_inout) {
     if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
     if (!ctx->comm) return fail(ctx, TLS_E_STATE, "tls_comm_init first");
     TLS_HIP(ctx, hipSetDevice(ctx->device));
-    TLS_HIP(ctx, hipMemcpyAsync(ctx->d_scalar.ptr, value_inout, 8, hipMemcpyHostToDevice, ctx->stream));
-    TLS_NCCL(ctx, ncclAllReduce(ctx->d_scalar.ptr, ctx->d_scalar.ptr + 1, 1, ncclDouble, ncclMax, ctx->comm, ctx->stream));
-    TLS_HIP(ctx, hipMemcpyAsync(value_inout, ctx->d_scalar.ptr + 1, 8, hipMemcpyDeviceToHost, ctx->stream));
-    TLS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    TLS_HIP(ctx, hipMemcpyAsync(ctx->d_scalar.ptr, value_inout, 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_NCCL(ctx, ncclAllReduce(ctx->d_scalar.ptr, ctx->d_scalar.ptr + 1, 1, ncclDouble, ncclMax, ctx->comm, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(value_inout, ctx->d_scalar.ptr + 1, 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+    TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));
     return TLS_OK;
 }
 
