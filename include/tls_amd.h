@@ -457,6 +457,36 @@ int tls_medfilt_detrend(tls_ctx *ctx, const double *y, int64_t n, int64_t n_rows
 int tls_biweight_detrend(tls_ctx *ctx, const double *t, const double *y, int64_t n, int64_t n_rows,
                          double window_length, double break_tolerance, double *out_flat, double *out_trend);
 
+/* ---- survey-mode detrending with the transits protected: the two-pass flow (search, mask, detrend again, search) -------- */
+/* The in-transit flags of a batch: out_mask [n_curves][n], 1 = protected, from n_candidates candidates (curve[k] in
+ * [0, n_curves), or curve NULL: candidate k belongs to curve k; period[k], T0[k], duration[k] in days).  Point i of curve c is
+ * protected if any candidate k of curve c has
+ *     d = t[i] - T0[k];  e = floor(d / period[k] + 0.5);  r = d - e * period[k];  fabs(r) <= 0.5 * (factor * duration[k]),
+ * one IEEE double operation a step in this order, no contraction.  A candidate takes part only if its period, T0 and duration
+ * are finite, its period > 0 and its duration > 0; any other is skipped silently.  The candidates of a curve may come in any
+ * order and number; the host groups them by curve (a stable sort), one thread owns one (curve, point).  t need not be sorted.
+ * Needs no plan and leaves a prepared one as it is.  n_curves == 0 is a no-op.  TLS_E_ARG, before any device work, for n
+ * outside [1, 1e8], a negative count, a factor that is not finite and > 0, a non-finite t and a curve outside [0, n_curves). */
+int tls_transit_mask(tls_ctx *ctx, const double *t, int64_t n, const int64_t *curve, const double *period, const double *T0,
+                     const double *duration, int64_t n_candidates, double factor, int64_t n_curves, uint8_t *out_mask);
+/* tls_biweight_detrend with the protected points (mask [n_rows][n], != 0) left out of every fit.  The windows [lo_i, hi_i) are
+ * exactly those of tls_biweight_detrend -- they depend on t alone, and a protected i keeps its window centred on t[i].  The
+ * members of window i are its unprotected j, m_i their number.
+ *   m_i >= min(min_points, hi_i - lo_i) (min_points >= 1; a window that holds fewer than min_points points altogether is
+ *     fitted when none of them is protected, as tls_biweight_detrend fits it): out_trend[i] = the biweight location of the
+ *     members by the loop above (median, MAD, reweighting, both sums in ascending index, over the members only); status 0.
+ *   otherwise i is open; a and b = the nearest points of status 0 to the left and right in i's segment:
+ *     both: trend = ta + (tb - ta) * ((t[i] - t[a]) / (t[b] - t[a])), operations in this order, ta where t[b] == t[a]; status 1
+ *     one: that point's trend; status 1
+ *     none (every point of the segment is open): the plain biweight of i's own window, the mask ignored; status 2.
+ * out_flat = y / trend.  The trend is always defined, so out_flat is finite and > 0 for every input tls_biweight_detrend
+ * accepts.  An all-zero mask gives tls_biweight_detrend's out_flat and out_trend bit for bit; an all-ones row the same values
+ * with status 2 everywhere.  out_trend and out_status ([n_rows][n]) may be NULL.  TLS_E_ARG as tls_biweight_detrend, and for
+ * min_points < 1. */
+int tls_biweight_detrend_masked(tls_ctx *ctx, const double *t, const double *y, const uint8_t *mask, int64_t n, int64_t n_rows,
+                                double window_length, double break_tolerance, int64_t min_points, double *out_flat,
+                                double *out_trend, uint8_t *out_status);
+
 /* ---- survey-mode detrending: SysRem, the systematics the rows share, fitted across them on the device ------------- */
 /* The lanes of a row sum and the rows of a column sum's chunk (both part of the definition below), the most components and
  * the most iterations per component (tls_amd._lib.SYSREM_* mirror them). */
@@ -1092,6 +1122,19 @@ int tls_prewhiten(tls_ctx *ctx, const double *t, const double *y, const double *
                   const double *frequencies, int64_t n_freq, int64_t n_terms, int64_t n_harmonics, double min_power,
                   double *out_flat, double *out_trend, tls_prewhiten_term *out_terms, int64_t *out_n_iterations,
                   double *out_status, double *out_steps, double *out_sums);
+/* Pre-whitening that cannot see the transit: tls_prewhiten with other weights and nothing else changed.  mask [n_curves][n],
+ * != 0: protected.  v_i = 0.0 at a protected point and 1.0 / (dy_i * dy_i) or, without dy, 1.0 elsewhere; W = the ordered sum of
+ * the v_i (in index order in the periodogram's prologue, over 256 lanes in the fit) and w_i = v_i / W.  Mean, variance,
+ * periodogram, pick, refinement and sinusoid fit use these weights (every curve has a weight row of its own, as with a dy);
+ * the subtraction and the trend cover EVERY point, the protected ones included.  A row with fewer than 3 unprotected points
+ * has nothing removed: status 2, n_iterations 0, trend = its mean with the mask ignored.  An all-zero mask has the weights of
+ * tls_prewhiten (without dy, W is the sum of n ones, so 1.0 / W is 1.0 / n); without dy the sums of the weights then come from
+ * one dense product a curve instead of one a call, which may move the last bits.  Everything else, the errors included, as
+ * tls_prewhiten. */
+int tls_prewhiten_masked(tls_ctx *ctx, const double *t, const double *y, const double *dy, const uint8_t *mask, int64_t n,
+                         int64_t n_curves, const double *frequencies, int64_t n_freq, int64_t n_terms, int64_t n_harmonics,
+                         double min_power, double *out_flat, double *out_trend, tls_prewhiten_term *out_terms,
+                         int64_t *out_n_iterations, double *out_status, double *out_steps, double *out_sums);
 
 /* ---- survey mode: the ephemeris match across the candidates of a batch ----------------------------------------------- */
 /* The test that looks across the stars (Coughlin et al. 2014): the stars of one field, camera and sector contaminate one

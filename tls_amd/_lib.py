@@ -116,6 +116,7 @@ SYMBOLS = (
     "tls_phase_scan", "tls_power_batch_phase_scan", "tls_debug_peak_phase_scans", "tls_single_transits",
     "tls_transit_times", "tls_shape_fit", "tls_nudft", "tls_lomb_scargle", "tls_sine_test", "tls_prewhiten",
     "tls_ephemeris_match", "tls_folded_views", "tls_event_vetting", "tls_centroid_test", "tls_noise_profile",
+    "tls_transit_mask", "tls_biweight_detrend_masked", "tls_prewhiten_masked",
     "tls_comm_unique_id", "tls_comm_init", "tls_comm_destroy", "tls_comm_info", "tls_comm_allgather_results", "tls_comm_allgather_device", "tls_comm_fetch_gathered",
     "tls_comm_stage_results", "tls_comm_allgather_staged", "tls_comm_fetch_staged",
     "tls_comm_barrier", "tls_comm_max",
@@ -1222,6 +1223,16 @@ def load():
     lib.tls_ephemeris_match.restype = ci
     lib.tls_ephemeris_match.argtypes = [vp, _c_int64_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, i64, dbl, dbl, dbl,
                                         i64, ctypes.c_void_p]
+    u8p = ctypes.POINTER(ctypes.c_uint8)
+    lib.tls_transit_mask.restype = ci
+    lib.tls_transit_mask.argtypes = [vp, _c_double_p, i64, _c_int64_p, _c_double_p, _c_double_p, _c_double_p, i64, dbl, i64, u8p]
+    lib.tls_biweight_detrend_masked.restype = ci
+    lib.tls_biweight_detrend_masked.argtypes = [vp, _c_double_p, _c_double_p, u8p, i64, i64, dbl, dbl, i64, _c_double_p,
+                                                _c_double_p, u8p]
+    lib.tls_prewhiten_masked.restype = ci
+    lib.tls_prewhiten_masked.argtypes = [vp, _c_double_p, _c_double_p, _c_double_p, u8p, i64, i64, _c_double_p, i64, i64, i64, dbl,
+                                         _c_double_p, _c_double_p, ctypes.c_void_p, _c_int64_p, _c_double_p, _c_double_p,
+                                         _c_double_p]
     lib.tls_noise_profile.restype = ci
     lib.tls_noise_profile.argtypes = [vp, _c_double_p, _c_double_p, i64, i64, _c_int64_p, _c_double_p, i64, dbl, dbl, dbl, i64,
                                       ctypes.c_void_p, _c_int64_p, _c_double_p, _c_double_p]
@@ -1379,6 +1390,69 @@ def biweight_arguments(t, y, window_length, break_tolerance):
     if rows.size and not (rows.min() > 0.0 and rows.max() < numpy.inf):
         raise ValueError("flux has a NaN, infinite or non-positive value: the biweight filter needs flux > 0")
     return t, numpy.ascontiguousarray(rows), wl, bt
+
+
+def detrend_mask_rows(mask, shape, what="mask"):
+    """mask as contiguous uint8 rows of `shape` ([n_rows, n]; a [n] mask serves one row): a uint8 or bool array, any byte
+    other than 0 protected.  ValueError for another dtype or shape.  GPU-free."""
+    rows = numpy.asarray(mask)
+    if rows.dtype != numpy.uint8 and rows.dtype != numpy.bool_:
+        raise ValueError("%s must be a uint8 or bool array, got dtype %s" % (what, rows.dtype))
+    if rows.ndim == 1 and shape[0] == 1:
+        rows = rows[None, :]
+    if rows.shape != tuple(shape):
+        raise ValueError("%s must have shape %s, got %s" % (what, tuple(shape), numpy.shape(mask)))
+    return numpy.ascontiguousarray(rows.view(numpy.uint8) if rows.dtype == numpy.bool_ else rows)
+
+
+def _min_points(min_points):
+    if isinstance(min_points, (bool, numpy.bool_)) or not isinstance(min_points, numbers.Integral) or not 1 <= int(min_points) < 2 ** 31:
+        raise ValueError("min_points must be an integer >= 1, got %r" % (min_points,))
+    return int(min_points)
+
+
+def biweight_masked_arguments(t, y, mask, window_length, break_tolerance, min_points=3):
+    """(t, rows, mask rows uint8, window_length, break_tolerance, min_points), checked as tls_biweight_detrend_masked checks
+    them: biweight_arguments, a mask of the rows' shape (detrend_mask_rows) and min_points an integer >= 1.  ValueError
+    otherwise.  GPU-free."""
+    t, rows, wl, bt = biweight_arguments(t, y, window_length, break_tolerance)
+    return t, rows, detrend_mask_rows(mask, rows.shape), wl, bt, _min_points(min_points)
+
+
+def transit_mask_arguments(t, period, T0, duration, curve=None, n_curves=None, factor=1.5):
+    """What tls_transit_mask takes, checked as it checks them: a dict with t [n] (n in [1, 1e8], finite), period, T0 and
+    duration [m] (any values: a candidate that is not finite and > 0 takes no part), curve (None: candidate k belongs to curve
+    k; integers in [0, n_curves)), n_curves (None: m without curve, max(curve) + 1 with) and factor (finite, > 0).  ValueError
+    otherwise.  GPU-free."""
+    try:
+        t = numpy.ascontiguousarray(numpy.asarray(t, dtype=numpy.float64))
+        period, T0, duration = (numpy.ascontiguousarray(numpy.atleast_1d(numpy.asarray(v, dtype=numpy.float64)))
+                                for v in (period, T0, duration))
+    except (TypeError, ValueError):
+        raise ValueError("transit mask: t, period, T0 and duration must hold numbers")
+    if t.ndim != 1 or not 1 <= len(t) <= 100000000:
+        raise ValueError("transit mask: t must have shape [n] with n in [1, 1e8], got %s" % (t.shape,))
+    if not numpy.all(numpy.isfinite(t)):
+        raise ValueError("transit mask: t must be finite")
+    if period.ndim != 1 or not period.shape == T0.shape == duration.shape:
+        raise ValueError("transit mask: period, T0 and duration must have one shape [m], got %s, %s, %s"
+                         % (period.shape, T0.shape, duration.shape))
+    m = len(period)
+    if curve is not None:
+        curve = numpy.asarray(curve)
+        if curve.shape != (m,) or (m and curve.dtype.kind not in "iu"):
+            raise ValueError("transit mask: curve must hold %d integers, got shape %s dtype %s" % (m, curve.shape, curve.dtype))
+        curve = numpy.ascontiguousarray(curve, dtype=numpy.int64)
+    if n_curves is None:
+        n_curves = m if curve is None else (int(curve.max()) + 1 if m else 0)
+    if isinstance(n_curves, (bool, numpy.bool_)) or not isinstance(n_curves, numbers.Integral) or n_curves < 0:
+        raise ValueError("transit mask: n_curves must be an integer >= 0, got %r" % (n_curves,))
+    n_curves = int(n_curves)
+    if (curve is None and m > n_curves) or (curve is not None and m and not (0 <= curve.min() and curve.max() < n_curves)):
+        raise ValueError("transit mask: curve out of range [0, n_curves = %d)" % n_curves)
+    if isinstance(factor, (bool, numpy.bool_)) or not isinstance(factor, numbers.Real) or not (0.0 < float(factor) < numpy.inf):
+        raise ValueError("transit mask: factor must be finite and > 0, got %r" % (factor,))
+    return dict(t=t, period=period, T0=T0, duration=duration, curve=curve, n_curves=n_curves, factor=float(factor))
 
 
 def _sysrem_integer(name, value, low, high, what):
@@ -2228,6 +2302,65 @@ class Context(object):
             a["pair_span"], a["clip_upper"], a["clip_lower"], a["min_count"], records.ctypes.data_as(ctypes.c_void_p),
             _ip(count), _dp(robust), _dp(rms)))
         return records, count, robust, rms
+
+    def transit_mask(self, t, period, T0, duration, curve=None, n_curves=None, factor=1.5):
+        """The in-transit flags uint8 [n_curves, n] (1 = protected) of the candidates (curve[k], period[k], T0[k], duration[k]
+        in days) at the time stamps t, `factor` durations wide (tls_transit_mask; the statement: include/tls_amd.h,
+        tests/transit_protect_spec.py).  ValueError for what transit_mask_arguments refuses."""
+        a = transit_mask_arguments(t, period, T0, duration, curve, n_curves, factor)
+        out = numpy.zeros((a["n_curves"], len(a["t"])), dtype=numpy.uint8)
+        u8 = ctypes.POINTER(ctypes.c_uint8)
+        self._check(self._lib.tls_transit_mask(
+            self._h, _dp(a["t"]), len(a["t"]), None if a["curve"] is None else _ip(a["curve"]), _dp(a["period"]), _dp(a["T0"]),
+            _dp(a["duration"]), len(a["period"]), a["factor"], a["n_curves"], out.ctypes.data_as(u8)))
+        return out
+
+    def biweight_detrend_masked(self, t, y, mask, window_length, break_tolerance, min_points=3, return_trend=False,
+                                return_status=False):
+        """biweight_detrend with the points of mask (uint8 or bool, y's shape, != 0: protected) left out of every fit
+        (tls_biweight_detrend_masked): a window with min_points unprotected points gets their biweight location (status 0), any
+        other point the trend interpolated between its nearest fitted neighbours (status 1), a segment without a fitted point
+        the plain biweight (status 2).  flat[, trend][, status uint8] in y's shape.  ValueError for what
+        biweight_masked_arguments refuses."""
+        t, rows, mk, wl, bt, low = biweight_masked_arguments(t, y, mask, window_length, break_tolerance, min_points)
+        flat = numpy.empty_like(rows)
+        trend = numpy.empty_like(rows) if return_trend else None
+        status = numpy.empty(rows.shape, dtype=numpy.uint8) if return_status else None
+        u8 = ctypes.POINTER(ctypes.c_uint8)
+        self._check(self._lib.tls_biweight_detrend_masked(
+            self._h, _dp(t), _dp(rows), mk.ctypes.data_as(u8), rows.shape[1], rows.shape[0], wl, bt, low, _dp(flat),
+            None if trend is None else _dp(trend), None if status is None else status.ctypes.data_as(u8)))
+        out = (flat,) + ((trend,) if return_trend else ()) + ((status,) if return_status else ())
+        if numpy.ndim(y) == 1:
+            out = tuple(v[0] for v in out)
+        return out[0] if len(out) == 1 else out
+
+    def prewhiten_masked(self, t, y, mask, frequencies, n_terms=3, harmonics=1, min_power=0.0, dy=None, return_trend=False,
+                         return_terms=False, debug=False):
+        """prewhiten with the points of mask (uint8 or bool, y's shape, != 0: protected) given weight 0.0 in the periodogram
+        and in the fit (tls_prewhiten_masked); the subtraction and the trend cover every point.  A row with fewer than 3
+        unprotected points has nothing removed (status 2).  Returns what prewhiten returns.  ValueError for what
+        prewhiten_arguments and detrend_mask_rows refuse."""
+        a = prewhiten_arguments(t, y, dy, frequencies, n_terms, harmonics, min_power)
+        mk = detrend_mask_rows(mask, a["y"].shape)
+        n_c, n = a["y"].shape
+        K, H = a["n_terms"], a["harmonics"]
+        flat = numpy.empty_like(a["y"])
+        trend = numpy.empty_like(a["y"]) if return_trend else None
+        terms = numpy.zeros((n_c, K, H), dtype=PREWHITEN_DTYPE)
+        info = dict(terms=terms, n_iterations=numpy.zeros(n_c, dtype=numpy.int64), status=numpy.zeros(n_c))
+        if debug:
+            info.update(steps=numpy.zeros((K * H + 1, n_c, n)), sums=numpy.zeros((n_c, K, H, 6)))
+        self._check(self._lib.tls_prewhiten_masked(
+            self._h, _dp(a["t"]), _dp(a["y"]), None if a["dy"] is None else _dp(a["dy"]),
+            mk.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), n, n_c, _dp(a["frequencies"]), len(a["frequencies"]), K, H,
+            a["min_power"], _dp(flat), None if trend is None else _dp(trend), terms.ctypes.data_as(ctypes.c_void_p),
+            _ip(info["n_iterations"]), _dp(info["status"]), _dp(info["steps"]) if debug else None,
+            _dp(info["sums"]) if debug else None))
+        if numpy.ndim(y) == 1:
+            flat, trend = flat[0], None if trend is None else trend[0]
+        out = (flat,) + ((trend,) if return_trend else ()) + ((info,) if return_terms or debug else ())
+        return out[0] if len(out) == 1 else out
 
     def debug_null_words(self, n, n_rows, seed, first_trial=0, block=None):
         """The raw Philox words [n_rows, W] tls_null_rows draws for these trials (tls_debug_null_words): white-noise

@@ -250,6 +250,12 @@ struct tls_ctx {
     DevBuf<unsigned long long> d_null_words;     // tls_debug_null_words: the words of one slab
     DevBuf<double> d_detrend;       // tls_medfilt_detrend, tls_biweight_detrend: rows | flat rows | trend rows of one slab
     DevBuf<int> d_windows;          // tls_biweight_detrend: lo [n] | hi [n], the window of every point
+    // tls_transit_mask: t | period | T0 | duration of the candidates grouped by curve | their offsets [n_curves + 1] (64-bit
+    // words); tls_biweight_detrend_masked: t
+    DevBuf<double> d_protect;
+    // tls_transit_mask: the mask rows of one slab; tls_biweight_detrend_masked: mask | open marks | status rows of one slab;
+    // tls_prewhiten_masked: the mask rows of one slab
+    DevBuf<unsigned char> d_protect_bytes;
     // tls_sysrem: y | x | flat | dy | w (without dy: one weight a row) [| trend] | m | c [K] rows | a [K] | chunk partials
     DevBuf<double> d_sysrem;
     DevBuf<unsigned long long> d_sysrem_state;   // ... and its state words (tlsdev::kSysremState)
@@ -2596,11 +2602,14 @@ static void biweight_plan(const std::vector<int>& lo, const std::vector<int>& hi
     *P = pow2(s);
 }
 
-int tls_biweight_detrend(tls_ctx* ctx, const double* t, const double* y, int64_t n, int64_t n_rows, double window_length,
-                         double break_tolerance, double* out_flat, double* out_trend) {
+// tls_biweight_detrend (masked false: mask, min_points and out_status are not looked at) and tls_biweight_detrend_masked
+static int biweight_detrend(tls_ctx* ctx, const double* t, const double* y, bool masked, const uint8_t* mask, int64_t n,
+                            int64_t n_rows, double window_length, double break_tolerance, int64_t min_points, double* out_flat,
+                            double* out_trend, uint8_t* out_status) {
     if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
     if (n < 1 || n > 100000000) return fail(ctx, TLS_E_ARG, "biweight: n out of range [1, 1e8]");
     if (n_rows < 0) return fail(ctx, TLS_E_ARG, "biweight: n_rows < 0");
+    if (masked && (min_points < 1 || min_points > INT32_MAX)) return fail(ctx, TLS_E_ARG, "biweight: min_points must be >= 1");
     if (!(std::isfinite(window_length) && window_length > 0.0))
         return fail(ctx, TLS_E_ARG, "biweight: window_length must be finite and > 0");
     if (!(break_tolerance > 0.0)) return fail(ctx, TLS_E_ARG, "biweight: break_tolerance must be > 0");
@@ -2626,7 +2635,7 @@ int tls_biweight_detrend(tls_ctx* ctx, const double* t, const double* y, int64_t
         return fail(ctx, TLS_E_ARG, "biweight: a window holds " + std::to_string(wmax) + " points, more than " +
                                         std::to_string(TLS_BIWEIGHT_MAX_WINDOW));
     if (n_rows == 0) return TLS_OK;
-    if (!y || !out_flat) return fail(ctx, TLS_E_ARG, "null argument");
+    if (!y || !out_flat || (masked && !mask)) return fail(ctx, TLS_E_ARG, "null argument");
     if ((uint64_t)n_rows > (uint64_t)(SIZE_MAX / 8) / (uint64_t)n) return fail(ctx, TLS_E_ARG, "biweight: rows too large");
     const size_t nn = (size_t)n;
     for (size_t q = 0; q < (size_t)n_rows * nn; ++q)
@@ -2635,20 +2644,36 @@ int tls_biweight_detrend(tls_ctx* ctx, const double* t, const double* y, int64_t
     TLS_HIP(ctx, hipSetDevice(ctx->device));
     // rows per launch: at most 256 MB of rows (as the median filter's slabs), and gridDim.y within its limit
     const int64_t slab = std::max<int64_t>(1, std::min<int64_t>({n_rows, (int64_t)65535, (int64_t)((256u << 20) / (8 * nn))}));
-    const int parts = out_trend ? 3 : 2;
+    const int parts = out_trend || masked ? 3 : 2;   // (the masked call interpolates between trend values: it always forms them)
     TLS_HIP(ctx, ctx->d_detrend.reserve((size_t)parts * (size_t)slab * nn));
     TLS_HIP(ctx, ctx->d_windows.reserve(2 * nn));
     double* d_y = ctx->d_detrend.ptr;
     double* d_flat = d_y + (size_t)slab * nn;
-    double* d_trend = out_trend ? d_flat + (size_t)slab * nn : nullptr;
+    double* d_trend = parts == 3 ? d_flat + (size_t)slab * nn : nullptr;
+    // the masked call: the time stamps; the mask rows, the masked pass's marks and the status rows of a slab
+    unsigned char *d_mask = nullptr, *d_open = nullptr, *d_status = nullptr;
+    if (masked) {
+        TLS_HIP(ctx, ctx->d_protect.reserve(nn));
+        TLS_HIP(ctx, ctx->d_protect_bytes.reserve(3 * (size_t)slab * nn));
+        d_mask = ctx->d_protect_bytes.ptr; d_open = d_mask + (size_t)slab * nn; d_status = d_open + (size_t)slab * nn;
+        TLS_HIP(ctx, hipMemcpyAsync(ctx->d_protect.ptr, t, nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    }
     TLS_HIP(ctx, hipMemcpyAsync(ctx->d_windows.ptr, lo.data(), nn * sizeof(int), hipMemcpyHostToDevice, main_stream(ctx)));
     TLS_HIP(ctx, hipMemcpyAsync(ctx->d_windows.ptr + nn, hi.data(), nn * sizeof(int), hipMemcpyHostToDevice, main_stream(ctx)));
     int T = 0, P = 0, smax = 0;
     biweight_plan(lo, hi, wmax, &T, &P, &smax);
     const size_t lds = (size_t)P * (sizeof(unsigned long long) + sizeof(unsigned int)) + (size_t)smax * sizeof(double);
     auto fn = tlsdev::tls_biweight_detrend;
-    TLS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    tlsdev::BiweightArgs a;
+    auto fn_masked = tlsdev::tls_biweight_detrend_masked;
+    auto fn_fallback = tlsdev::tls_biweight_detrend_fallback;
+    if (masked) {
+        TLS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(fn_masked), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        TLS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(fn_fallback), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    } else {
+        TLS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    }
+    tlsdev::BiweightMaskedArgs a;   // (the plain kernel takes its base, BiweightArgs)
+    a.mask = d_mask; a.status = d_open; a.min_points = (int)min_points;
     a.y = d_y; a.flat = d_flat; a.trend = d_trend; a.check = nullptr;
     a.lo = ctx->d_windows.ptr; a.hi = ctx->d_windows.ptr + nn;
     a.n = (long long)n; a.tile = T; a.span = P; a.smax = smax;
@@ -2661,13 +2686,109 @@ int tls_biweight_detrend(tls_ctx* ctx, const double* t, const double* y, int64_t
         const int64_t rows = std::min<int64_t>(slab, n_rows - k0);
         const size_t bytes = (size_t)rows * nn * 8;
         TLS_HIP(ctx, hipMemcpyAsync(d_y, y + (size_t)k0 * nn, bytes, hipMemcpyHostToDevice, main_stream(ctx)));
-        hipLaunchKernelGGL(fn, dim3(tiles, (unsigned)rows), dim3(tlsdev::kDetrendThreads), lds, main_stream(ctx), a);
-        TLS_HIP(ctx, hipGetLastError());
-        ctx->last_kernel = "tls_biweight_detrend";
+        if (!masked) {
+            hipLaunchKernelGGL(fn, dim3(tiles, (unsigned)rows), dim3(tlsdev::kDetrendThreads), lds, main_stream(ctx),
+                               static_cast<const tlsdev::BiweightArgs&>(a));
+            TLS_HIP(ctx, hipGetLastError());
+            ctx->last_kernel = "tls_biweight_detrend";
+        } else {
+            // the members' biweight where a window holds min_points of them; the open points from their neighbours; the plain
+            // biweight where a whole segment is open
+            TLS_HIP(ctx, hipMemcpyAsync(d_mask, mask + (size_t)k0 * nn, (size_t)rows * nn, hipMemcpyHostToDevice, main_stream(ctx)));
+            a.status = d_open;
+            hipLaunchKernelGGL(fn_masked, dim3(tiles, (unsigned)rows), dim3(tlsdev::kDetrendThreads), lds, main_stream(ctx), a);
+            TLS_HIP(ctx, hipGetLastError());
+            tlsdev::BiweightFillArgs f;
+            f.t = ctx->d_protect.ptr; f.y = d_y; f.flat = d_flat; f.trend = d_trend; f.open = d_open; f.status = d_status;
+            f.n = (long long)n; f.count = (long long)rows * (long long)n; f.break_tolerance = break_tolerance;
+            const unsigned blocks = (unsigned)std::min<long long>((f.count + tlsdev::kDetrendThreads - 1) / tlsdev::kDetrendThreads, 65536);
+            hipLaunchKernelGGL(tlsdev::tls_biweight_fill, dim3(blocks), dim3(tlsdev::kDetrendThreads), 0, main_stream(ctx), f);
+            TLS_HIP(ctx, hipGetLastError());
+            a.status = d_status;
+            hipLaunchKernelGGL(fn_fallback, dim3(tiles, (unsigned)rows), dim3(tlsdev::kDetrendThreads), lds, main_stream(ctx), a);
+            TLS_HIP(ctx, hipGetLastError());
+            ctx->last_kernel = "tls_biweight_detrend_masked";
+            if (out_status)
+                TLS_HIP(ctx, hipMemcpyAsync(out_status + (size_t)k0 * nn, d_status, (size_t)rows * nn, hipMemcpyDeviceToHost, main_stream(ctx)));
+        }
         TLS_HIP(ctx, hipMemcpyAsync(out_flat + (size_t)k0 * nn, d_flat, bytes, hipMemcpyDeviceToHost, main_stream(ctx)));
         if (out_trend)
             TLS_HIP(ctx, hipMemcpyAsync(out_trend + (size_t)k0 * nn, d_trend, bytes, hipMemcpyDeviceToHost, main_stream(ctx)));
         // (the next slab overwrites the device rows, and lo / hi live on this stack: the copies have to be done first)
+        TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));
+    }
+    return TLS_OK;
+}
+
+int tls_biweight_detrend(tls_ctx* ctx, const double* t, const double* y, int64_t n, int64_t n_rows, double window_length,
+                         double break_tolerance, double* out_flat, double* out_trend) {
+    return biweight_detrend(ctx, t, y, false, nullptr, n, n_rows, window_length, break_tolerance, 1, out_flat, out_trend, nullptr);
+}
+
+int tls_biweight_detrend_masked(tls_ctx* ctx, const double* t, const double* y, const uint8_t* mask, int64_t n, int64_t n_rows,
+                                double window_length, double break_tolerance, int64_t min_points, double* out_flat,
+                                double* out_trend, uint8_t* out_status) {
+    return biweight_detrend(ctx, t, y, true, mask, n, n_rows, window_length, break_tolerance, min_points, out_flat, out_trend,
+                            out_status);
+}
+
+// ---- the in-transit flags of a batch (tls_protect.hip.h)
+int tls_transit_mask(tls_ctx* ctx, const double* t, int64_t n, const int64_t* curve, const double* period, const double* T0,
+                     const double* duration, int64_t n_candidates, double factor, int64_t n_curves, uint8_t* out_mask) {
+    if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
+    if (n < 1 || n > 100000000) return fail(ctx, TLS_E_ARG, "transit mask: n out of range [1, 1e8]");
+    if (n_curves < 0 || n_candidates < 0) return fail(ctx, TLS_E_ARG, "transit mask: n_curves < 0 or n_candidates < 0");
+    if (!(std::isfinite(factor) && factor > 0.0)) return fail(ctx, TLS_E_ARG, "transit mask: factor must be finite and > 0");
+    if (!t || (n_candidates > 0 && (!period || !T0 || !duration))) return fail(ctx, TLS_E_ARG, "null argument");
+    if (!curve && n_candidates > n_curves) return fail(ctx, TLS_E_ARG, "transit mask: curve out of range [0, n_curves)");
+    for (int64_t i = 0; i < n; ++i)
+        if (!std::isfinite(t[i])) return fail(ctx, TLS_E_ARG, "transit mask: the time stamps must be finite");
+    if (int rc = check_curves(ctx, "transit mask", curve, n_candidates, n_curves)) return rc;
+    if (n_curves == 0) return TLS_OK;
+    if (!out_mask) return fail(ctx, TLS_E_ARG, "null argument");
+    if ((uint64_t)n_curves > (uint64_t)(INT64_MAX / 16) / (uint64_t)n) return fail(ctx, TLS_E_ARG, "transit mask: batch too large");
+    // the candidates that take part, grouped by curve in their order of appearance (a stable counting sort)
+    const size_t nc = (size_t)n_curves, nn = (size_t)n;
+    auto takes_part = [&](int64_t k) {
+        return std::isfinite(period[k]) && std::isfinite(T0[k]) && std::isfinite(duration[k]) && period[k] > 0.0 && duration[k] > 0.0;
+    };
+    std::vector<long long> offset(nc + 1, 0);
+    for (int64_t k = 0; k < n_candidates; ++k)
+        if (takes_part(k)) ++offset[(size_t)(curve ? curve[k] : k) + 1];
+    for (size_t c = 0; c < nc; ++c) offset[c + 1] += offset[c];
+    const size_t m = (size_t)offset[nc];
+    std::vector<double> sorted(3 * m);
+    {
+        std::vector<long long> at(offset.begin(), offset.end() - 1);
+        for (int64_t k = 0; k < n_candidates; ++k) {
+            if (!takes_part(k)) continue;
+            const size_t q = (size_t)at[(size_t)(curve ? curve[k] : k)]++;
+            sorted[q] = period[k]; sorted[m + q] = T0[k]; sorted[2 * m + q] = duration[k];
+        }
+    }
+    TLS_HIP(ctx, hipSetDevice(ctx->device));
+    static_assert(sizeof(long long) == sizeof(double), "the offsets lie in a buffer of doubles");
+    // curves per launch: at most 256 MB of flags
+    const size_t slab = std::max<size_t>(1, std::min<size_t>(nc, ((size_t)256 << 20) / nn));
+    TLS_HIP(ctx, ctx->d_protect.reserve(nn + 3 * m + nc + 1));
+    TLS_HIP(ctx, ctx->d_protect_bytes.reserve(slab * nn));
+    double* d_t = ctx->d_protect.ptr;
+    double* d_cand = d_t + nn;
+    long long* d_offset = reinterpret_cast<long long*>(d_cand + 3 * m);
+    TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    if (m) TLS_HIP(ctx, hipMemcpyAsync(d_cand, sorted.data(), 3 * m * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_offset, offset.data(), (nc + 1) * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    for (size_t c0 = 0; c0 < nc; c0 += slab) {
+        const size_t curves = std::min(slab, nc - c0);
+        tlsdev::TransitMaskArgs a;
+        a.t = d_t; a.period = d_cand; a.T0 = d_cand + m; a.duration = d_cand + 2 * m; a.offset = d_offset + c0;
+        a.mask = ctx->d_protect_bytes.ptr; a.n = (long long)n; a.count = (long long)curves * (long long)n; a.factor = factor;
+        const unsigned blocks = (unsigned)std::min<long long>((a.count + tlsdev::kProtectThreads - 1) / tlsdev::kProtectThreads, 65536);
+        hipLaunchKernelGGL(tlsdev::tls_transit_mask_kernel, dim3(blocks), dim3(tlsdev::kProtectThreads), 0, main_stream(ctx), a);
+        TLS_HIP(ctx, hipGetLastError());
+        ctx->last_kernel = "tls_transit_mask";
+        TLS_HIP(ctx, hipMemcpyAsync(out_mask + c0 * nn, ctx->d_protect_bytes.ptr, curves * nn, hipMemcpyDeviceToHost, main_stream(ctx)));
+        // (the next slab overwrites the device rows, and the sorted candidates live on this stack)
         TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));
     }
     return TLS_OK;
@@ -2972,6 +3093,8 @@ int tls_debug_poison_lds(tls_ctx* ctx, uint32_t word) {
     TLS_HIP(ctx, smear(ctx->d_null_words));
     TLS_HIP(ctx, smear(ctx->d_detrend));
     TLS_HIP(ctx, smear(ctx->d_windows));
+    TLS_HIP(ctx, smear(ctx->d_protect));
+    TLS_HIP(ctx, smear(ctx->d_protect_bytes));
     TLS_HIP(ctx, smear(ctx->d_sysrem));
     TLS_HIP(ctx, smear(ctx->d_scan));
     TLS_HIP(ctx, smear(ctx->d_single));
@@ -4445,10 +4568,11 @@ static_assert(sizeof(tls_prewhiten_term) == tlsdev::kPrewhitenWords * 8, "tls_pr
 static_assert(TLS_PREWHITEN_MAX_TERMS == tlsdev::kPrewhitenMaxTerms && TLS_PREWHITEN_LDS_POINTS == tlsdev::kPrewhitenLdsPoints,
               "the header's limits");
 
-int tls_prewhiten(tls_ctx* ctx, const double* t, const double* y, const double* dy, int64_t n, int64_t n_curves,
-                  const double* frequencies, int64_t n_freq, int64_t n_terms, int64_t n_harmonics, double min_power,
-                  double* out_flat, double* out_trend, tls_prewhiten_term* out_terms, int64_t* out_n_iterations,
-                  double* out_status, double* out_steps, double* out_sums) {
+// tls_prewhiten (masked false: mask is not looked at) and tls_prewhiten_masked, whose weights are the curve's own as with a dy
+static int prewhiten(tls_ctx* ctx, const double* t, const double* y, const double* dy, bool masked, const uint8_t* mask, int64_t n,
+                     int64_t n_curves, const double* frequencies, int64_t n_freq, int64_t n_terms, int64_t n_harmonics,
+                     double min_power, double* out_flat, double* out_trend, tls_prewhiten_term* out_terms,
+                     int64_t* out_n_iterations, double* out_status, double* out_steps, double* out_sums) {
     if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
     if (n_curves < 0) return fail(ctx, TLS_E_ARG, "prewhiten: n_curves < 0");
     int rc = check_gls_axes(ctx, t, n, 3, frequencies, n_freq);
@@ -4457,14 +4581,17 @@ int tls_prewhiten(tls_ctx* ctx, const double* t, const double* y, const double* 
     if (n_harmonics < 1 || n_harmonics > TLS_SINE_MAX_HARMONICS) return fail(ctx, TLS_E_ARG, "prewhiten: n_harmonics out of range [1, 8]");
     if (!(min_power >= 0.0 && min_power <= 1.0)) return fail(ctx, TLS_E_ARG, "prewhiten: min_power must lie in [0, 1]");
     if (n_curves == 0) return TLS_OK;
-    if (!y || !out_flat || !out_terms || !out_n_iterations || !out_status) return fail(ctx, TLS_E_ARG, "null argument");
+    if (!y || !out_flat || !out_terms || !out_n_iterations || !out_status || (masked && !mask)) return fail(ctx, TLS_E_ARG, "null argument");
     TLS_HIP(ctx, hipSetDevice(ctx->device));
+    const bool own = dy || masked;                   // every curve has a weight row of its own
     const size_t nn = (size_t)n, nf = (size_t)n_freq, K = (size_t)n_terms, KH = K * (size_t)n_harmonics;
     const size_t words = tlsdev::kPrewhitenWords;
     // rows of a slab: the rows, sums and spectra of a slab stay below 1 GB, and at most 4096 curves
     const size_t per_row = 8 * ((out_steps ? 7 + KH : 6) * nn + 9 * nf + KH * (words + 6) + 8);
     const size_t sl = std::max<size_t>(1, std::min<size_t>({(size_t)n_curves, 4096, ((size_t)1 << 30) / per_row}));
-    const size_t wl = dy ? sl : 1;
+    const size_t wl = own ? sl : 1;
+    if (masked) TLS_HIP(ctx, ctx->d_protect_bytes.reserve(sl * nn));
+    const unsigned char* d_mask = masked ? ctx->d_protect_bytes.ptr : nullptr;
     // (YC, YS) | (C, S) | (C2, S2) pairs; power | amplitude | phase; y | r | dy | a (flat at the end) | w | trend; mean_0 | mean |
     // variance | status; terms | sums; t | f | 2 f; n_iterations | counts | active; steps
     const size_t ints = (sl + 1) / 2;
@@ -4498,7 +4625,9 @@ int tls_prewhiten(tls_ctx* ctx, const double* t, const double* y, const double* 
     const bool lds = n <= tlsdev::kPrewhitenLdsPoints;
     const size_t lds_bytes = tlsdev::prewhiten_lds_bytes((int)n, lds);
     auto step_kernel = lds ? tlsdev::tls_prewhiten_step_kernel<true> : tlsdev::tls_prewhiten_step_kernel<false>;
-    TLS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(step_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+    auto step_masked_kernel = lds ? tlsdev::tls_prewhiten_step_masked_kernel<true> : tlsdev::tls_prewhiten_step_masked_kernel<false>;
+    TLS_HIP(ctx, hipFuncSetAttribute(masked ? reinterpret_cast<const void*>(step_masked_kernel) : reinterpret_cast<const void*>(step_kernel),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     std::vector<double> twice(nf);
     for (size_t i = 0; i < nf; ++i) twice[i] = 2.0 * frequencies[i];
     // a term that was not reached: status 2, NaN elsewhere
@@ -4515,11 +4644,12 @@ int tls_prewhiten(tls_ctx* ctx, const double* t, const double* y, const double* 
         return fail(ctx, TLS_E_HIP, std::string("prewhiten ") + what + " launch: " + hipGetErrorString(e));
     };
     for (int64_t k0 = 0; k0 < n_curves; k0 += (int64_t)sl) {
-        const int64_t R = std::min<int64_t>((int64_t)sl, n_curves - k0), Rw = dy ? R : 1;
+        const int64_t R = std::min<int64_t>((int64_t)sl, n_curves - k0), Rw = own ? R : 1;
         const size_t at = (size_t)k0 * nn, rows = (size_t)R, bytes = rows * nn * 8;
         TLS_HIP(ctx, hipMemcpyAsync(d_y, y + at, bytes, hipMemcpyHostToDevice, main_stream(ctx)));
         TLS_HIP(ctx, hipMemcpyAsync(d_r, d_y, bytes, hipMemcpyDeviceToDevice, main_stream(ctx)));
         if (dy) TLS_HIP(ctx, hipMemcpyAsync(d_dy, dy + at, bytes, hipMemcpyHostToDevice, main_stream(ctx)));
+        if (masked) TLS_HIP(ctx, hipMemcpyAsync(ctx->d_protect_bytes.ptr, mask + at, rows * nn, hipMemcpyHostToDevice, main_stream(ctx)));
         TLS_HIP(ctx, hipMemsetAsync(d_trend, 0, bytes, main_stream(ctx)));
         TLS_HIP(ctx, hipMemsetAsync(d_status, 0, rows * 8, main_stream(ctx)));
         TLS_HIP(ctx, hipMemsetAsync(d_iterations, 0, (sl + K) * 8, main_stream(ctx)));            // (and the counts behind them)
@@ -4530,16 +4660,17 @@ int tls_prewhiten(tls_ctx* ctx, const double* t, const double* y, const double* 
         for (int64_t j = 0; j < n_terms; ++j) {
             tlsdev::GlsPrologueArgs p;
             p.y = d_r; p.dy = d_dy; p.rows = d_a; p.weights = d_w; p.mean = j == 0 ? d_mean0 : d_mean; p.variance = d_var; p.n = (int)n;
-            hipLaunchKernelGGL(tlsdev::tls_gls_prologue_kernel, dim3((unsigned)R), dim3(tlsdev::kGlsThreads), 0, main_stream(ctx), p);
+            if (masked) hipLaunchKernelGGL(tlsdev::tls_gls_prologue_masked_kernel, dim3((unsigned)R), dim3(tlsdev::kGlsThreads), 0, main_stream(ctx), p, d_mask);
+            else hipLaunchKernelGGL(tlsdev::tls_gls_prologue_kernel, dim3((unsigned)R), dim3(tlsdev::kGlsThreads), 0, main_stream(ctx), p);
             if ((rc = launched("prologue"))) return rc;
             if ((rc = enqueue_nudft(ctx, d_a, R, n, n, d_t, d_f, n_freq, d_yc))) { (void)hipStreamSynchronize(main_stream(ctx)); return rc; }
-            if (j == 0 && (dy || k0 == 0)) {         // (the sums of the weights: once a call, or once a slab with dy)
+            if (j == 0 && (own || k0 == 0)) {         // (the sums of the weights: once a call, or once a slab with dy)
                 if ((rc = enqueue_nudft(ctx, d_w, Rw, n, n, d_t, d_f, n_freq, d_cs))
                     || (rc = enqueue_nudft(ctx, d_w, Rw, n, n, d_t, d_f2, n_freq, d_cs2))) { (void)hipStreamSynchronize(main_stream(ctx)); return rc; }
             }
             tlsdev::GlsEpilogueArgs g;
             g.yc = d_yc; g.cs = d_cs; g.cs2 = d_cs2; g.variance = d_var; g.power = d_power; g.amplitude = d_amplitude; g.phase = d_phase;
-            g.count = (long long)R * (long long)n_freq; g.F = (int)n_freq; g.shared_weights = dy ? 0 : 1;
+            g.count = (long long)R * (long long)n_freq; g.F = (int)n_freq; g.shared_weights = own ? 0 : 1;
             const unsigned blocks = (unsigned)std::min<long long>((g.count + tlsdev::kGlsThreads - 1) / tlsdev::kGlsThreads, 16384);
             hipLaunchKernelGGL(tlsdev::tls_gls_epilogue_kernel, dim3(blocks), dim3(tlsdev::kGlsThreads), 0, main_stream(ctx), g);
             if ((rc = launched("epilogue"))) return rc;
@@ -4547,9 +4678,10 @@ int tls_prewhiten(tls_ctx* ctx, const double* t, const double* y, const double* 
             a.t = d_t; a.f = d_f; a.dy = d_dy; a.power = d_power; a.r = d_r; a.trend = d_trend; a.terms = d_terms; a.sums = d_sums;
             a.steps = d_steps; a.active = d_active; a.n_iterations = d_iterations; a.status = d_status; a.counts = d_counts;
             a.min_power = min_power; a.n = (int)n; a.F = (int)n_freq; a.R = (int)R; a.K = (int)n_terms; a.H = (int)n_harmonics; a.j = (int)j;
-            hipLaunchKernelGGL(step_kernel, dim3((unsigned)R), dim3(tlsdev::kPrewhitenThreads), lds_bytes, main_stream(ctx), a);
+            if (masked) hipLaunchKernelGGL(step_masked_kernel, dim3((unsigned)R), dim3(tlsdev::kPrewhitenThreads), lds_bytes, main_stream(ctx), a, d_mask);
+            else hipLaunchKernelGGL(step_kernel, dim3((unsigned)R), dim3(tlsdev::kPrewhitenThreads), lds_bytes, main_stream(ctx), a);
             if ((rc = launched("step"))) return rc;
-            ctx->last_kernel = "tls_prewhiten";
+            ctx->last_kernel = masked ? "tls_prewhiten_masked" : "tls_prewhiten";
             ran = j + 1;
             if (j + 1 < n_terms) {
                 unsigned long long going = 0;
@@ -4580,6 +4712,22 @@ int tls_prewhiten(tls_ctx* ctx, const double* t, const double* y, const double* 
         TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));       // (the next slab overwrites the device buffers)
     }
     return TLS_OK;
+}
+
+int tls_prewhiten(tls_ctx* ctx, const double* t, const double* y, const double* dy, int64_t n, int64_t n_curves,
+                  const double* frequencies, int64_t n_freq, int64_t n_terms, int64_t n_harmonics, double min_power,
+                  double* out_flat, double* out_trend, tls_prewhiten_term* out_terms, int64_t* out_n_iterations,
+                  double* out_status, double* out_steps, double* out_sums) {
+    return prewhiten(ctx, t, y, dy, false, nullptr, n, n_curves, frequencies, n_freq, n_terms, n_harmonics, min_power, out_flat,
+                     out_trend, out_terms, out_n_iterations, out_status, out_steps, out_sums);
+}
+
+int tls_prewhiten_masked(tls_ctx* ctx, const double* t, const double* y, const double* dy, const uint8_t* mask, int64_t n,
+                         int64_t n_curves, const double* frequencies, int64_t n_freq, int64_t n_terms, int64_t n_harmonics,
+                         double min_power, double* out_flat, double* out_trend, tls_prewhiten_term* out_terms,
+                         int64_t* out_n_iterations, double* out_status, double* out_steps, double* out_sums) {
+    return prewhiten(ctx, t, y, dy, true, mask, n, n_curves, frequencies, n_freq, n_terms, n_harmonics, min_power, out_flat,
+                     out_trend, out_terms, out_n_iterations, out_status, out_steps, out_sums);
 }
 
 // ---- the ephemeris match (tls_match.hip.h, DESIGN.md "Ephemeris match"): every candidate against every other, the g range in

@@ -165,7 +165,12 @@ __device__ __forceinline__ double gls_add_tile(const double* term, int count, do
     return sum;
 }
 
-__global__ void __launch_bounds__(kGlsThreads) tls_gls_prologue_kernel(const GlsPrologueArgs a) {
+// MASKED (tls_prewhiten_masked): v_i = 0.0 where mask[i] != 0, elsewhere 1.0 / (dy_i * dy_i) or, without dy, 1.0; W = the sum
+// of the v_i in index order and w_i = v_i / W -- the per-curve weight rows of the dy case, with or without a dy.  A row with
+// fewer than 3 unprotected points is not fitted: its weights and mean ignore the mask and its variance is reported as 0.0, so
+// that every power of the row is NaN (gls_epilogue) as a constant row's is.
+template <bool MASKED>
+__device__ __forceinline__ void gls_prologue(const GlsPrologueArgs& a, const unsigned char* mask_rows) {
 #pragma clang fp contract(off)
     __shared__ double term[kGlsTile];
     __shared__ double total;
@@ -173,14 +178,39 @@ __global__ void __launch_bounds__(kGlsThreads) tls_gls_prologue_kernel(const Gls
     const long long at = (long long)blockIdx.x * n;
     const double* y = a.y + at;
     const double* dy = a.dy ? a.dy + at : nullptr;
-    double* w_out = a.dy ? a.weights + at : a.weights;
+    const bool own = MASKED || a.dy;                 // a weight row of the curve's own
+    double* w_out = own ? a.weights + at : a.weights;
     const double uniform = 1.0 / (double)n;
+    const unsigned char* mask = nullptr;
+    bool fitted = true;
+    if constexpr (MASKED) {
+        __shared__ int members[kGlsThreads];
+        int mine = 0;
+        for (int i = tid; i < n; i += kGlsThreads) mine += mask_rows[at + i] == 0;
+        members[tid] = mine;
+        wg_sync();
+        if (tid == 0) { int c = 0; for (int m = 0; m < kGlsThreads; ++m) c += members[m]; members[0] = c; }
+        wg_sync();
+        fitted = members[0] >= 3;
+        if (fitted) mask = mask_rows + at;
+        wg_sync();
+    }
+    [[maybe_unused]] auto inverse_variance = [&](int i) -> double {
+#pragma clang fp contract(off)
+        if (MASKED && mask && mask[i]) return 0.0;
+        if (!dy) return 1.0;
+        const double d = dy[i]; const double p = d * d;
+        return 1.0 / p;
+    };
     double W = 1.0;
-    if (dy) {
+    if (own) {
         double sum = 0.0;
         for (int base = 0; base < n; base += kGlsTile) {
             const int count = n - base < kGlsTile ? n - base : kGlsTile;
-            for (int m = tid; m < count; m += kGlsThreads) { const double d = dy[base + m]; const double p = d * d; term[m] = 1.0 / p; }
+            for (int m = tid; m < count; m += kGlsThreads) {
+                if constexpr (MASKED) term[m] = inverse_variance(base + m);
+                else { const double d = dy[base + m]; const double p = d * d; term[m] = 1.0 / p; }
+            }
             wg_sync();
             if (tid == 0) sum = gls_add_tile(term, count, sum);
             wg_sync();
@@ -195,7 +225,8 @@ __global__ void __launch_bounds__(kGlsThreads) tls_gls_prologue_kernel(const Gls
         const int count = n - base < kGlsTile ? n - base : kGlsTile;
         for (int m = tid; m < count; m += kGlsThreads) {
             double w = uniform;
-            if (dy) { const double d = dy[base + m]; const double p = d * d; const double v = 1.0 / p; w = v / W; }
+            if constexpr (MASKED) { const double v = inverse_variance(base + m); w = v / W; }
+            else if (dy) { const double d = dy[base + m]; const double p = d * d; const double v = 1.0 / p; w = v / W; }
             w_out[base + m] = w;
             term[m] = w * y[base + m];
         }
@@ -220,7 +251,16 @@ __global__ void __launch_bounds__(kGlsThreads) tls_gls_prologue_kernel(const Gls
         if (tid == 0) sum = gls_add_tile(term, count, sum);
         wg_sync();
     }
-    if (tid == 0) { a.mean[blockIdx.x] = ybar; a.variance[blockIdx.x] = sum; }
+    if (tid == 0) { a.mean[blockIdx.x] = ybar; a.variance[blockIdx.x] = fitted ? sum : 0.0; }
+}
+
+__global__ void __launch_bounds__(kGlsThreads) tls_gls_prologue_kernel(const GlsPrologueArgs a) {
+    gls_prologue<false>(a, nullptr);
+}
+
+// weights [R][n] always; mask [R][n]
+__global__ void __launch_bounds__(kGlsThreads) tls_gls_prologue_masked_kernel(const GlsPrologueArgs a, const unsigned char* mask) {
+    gls_prologue<true>(a, mask);
 }
 
 struct GlsEpilogueArgs {

@@ -4422,8 +4422,11 @@ __global__ void __launch_bounds__(512) tls_transit_models(const ModelsArgs a) {
 // survey-mode median-filter detrending (tls_medfilt_detrend)
 #include "tls_detrend.hip.h"
 
-// survey-mode biweight detrending (tls_biweight_detrend), on tls_detrend.hip.h's staging and sort
+// survey-mode biweight detrending (tls_biweight_detrend, tls_biweight_detrend_masked), on tls_detrend.hip.h's staging and sort
 #include "tls_biweight.hip.h"
+
+// survey-mode in-transit flags of a batch for the masked detrenders (tls_transit_mask)
+#include "tls_protect.hip.h"
 
 // survey-mode removal of shared systematics across the rows (tls_sysrem)
 #include "tls_sysrem.hip.h"

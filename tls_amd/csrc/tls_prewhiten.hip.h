@@ -81,8 +81,11 @@ struct PrewhitenArgs {
     int n, F, R, K, H, j;
 };
 
-template <bool LDS>
-__global__ void __launch_bounds__(kPrewhitenThreads) tls_prewhiten_step_kernel(const PrewhitenArgs a) {
+// MASKED (tls_prewhiten_masked; mask_rows [R][n], != 0: protected): the weights of the fit are v_i / W with v_i = 0.0 at a
+// protected point and 1.0 / (dy_i * dy_i) or, without dy, 1.0 elsewhere, W their ordered lane sum; the subtraction and the trend
+// cover every point.  (A row with fewer than 3 unprotected points never gets here: every power of it is NaN.)
+template <bool LDS, bool MASKED>
+__device__ __forceinline__ void prewhiten_step(const PrewhitenArgs& a, const unsigned char* mask_rows) {
 #pragma clang fp contract(off)
     extern __shared__ __attribute__((aligned(16))) double prewhiten_lds[];
     double (*part)[kPrewhitenThreads] = reinterpret_cast<double (*)[kPrewhitenThreads]>(prewhiten_lds);
@@ -165,6 +168,14 @@ __global__ void __launch_bounds__(kPrewhitenThreads) tls_prewhiten_step_kernel(c
         // (every thread reads back only what it wrote: no barrier)
     }
     const double* dy = a.dy ? a.dy + at : nullptr;
+    const unsigned char* mask = MASKED ? mask_rows + at : nullptr;
+    [[maybe_unused]] auto inverse_variance = [&](int i) -> double {   // (MASKED only)
+#pragma clang fp contract(off)
+        if (mask[i]) return 0.0;
+        if (!dy) return 1.0;
+        const double e = dy[i]; const double pp = e * e;
+        return 1.0 / pp;
+    };
     const double t0 = a.t[0];
     // the lanes of a sum are added by one thread in lane order
     auto lanes = [&](double mine) -> double {
@@ -178,7 +189,11 @@ __global__ void __launch_bounds__(kPrewhitenThreads) tls_prewhiten_step_kernel(c
         return s;
     };
     double W = 1.0;
-    if (dy) {
+    if constexpr (MASKED) {
+        double sv = 0.0;
+        for (int i = tid; i < n; i += kPrewhitenThreads) { const double v = inverse_variance(i); sv = sv + v; }
+        W = lanes(sv);
+    } else if (dy) {
         double sv = 0.0;
         for (int i = tid; i < n; i += kPrewhitenThreads) { const double e = dy[i]; const double pp = e * e; const double v = 1.0 / pp; sv = sv + v; }
         W = lanes(sv);
@@ -186,6 +201,7 @@ __global__ void __launch_bounds__(kPrewhitenThreads) tls_prewhiten_step_kernel(c
     const double uniform = 1.0 / (double)n;
     auto weight = [&](int i) -> double {
 #pragma clang fp contract(off)
+        if constexpr (MASKED) { const double v = inverse_variance(i); return v / W; }
         if (!dy) return uniform;
         const double e = dy[i]; const double pp = e * e; const double v = 1.0 / pp;
         return v / W;
@@ -261,6 +277,16 @@ __global__ void __launch_bounds__(kPrewhitenThreads) tls_prewhiten_step_kernel(c
         if (j + 1 < a.K) atomicAdd(&a.counts[j], 1ull);
         else a.active[c] = 0;
     }
+}
+
+template <bool LDS>
+__global__ void __launch_bounds__(kPrewhitenThreads) tls_prewhiten_step_kernel(const PrewhitenArgs a) {
+    prewhiten_step<LDS, false>(a, nullptr);
+}
+
+template <bool LDS>
+__global__ void __launch_bounds__(kPrewhitenThreads) tls_prewhiten_step_masked_kernel(const PrewhitenArgs a, const unsigned char* mask) {
+    prewhiten_step<LDS, true>(a, mask);
 }
 
 struct PrewhitenFinishArgs {

@@ -9,6 +9,7 @@ collective (every light curve's results come back over its own GPU's copy engine
 """
 import collections
 import contextlib
+import inspect
 import numbers
 import operator
 
@@ -177,7 +178,7 @@ class Biweight(collections.namedtuple("Biweight", ("window_length", "break_toler
 
 
 def biweight_batch(t, flux_batch, window_length=0.5, break_tolerance=0.5, return_trend=False, context=None, device=None,
-                   devices=None):
+                   devices=None, mask=None, min_points=3, return_status=False):
     """flat = flux / trend for every row of flux_batch ([n] or [n_curves, n], at the shared time stamps t), with trend Tukey's
     biweight location over a window in TIME, on the device (tls_biweight_detrend): the robust filter the detrending comparison
     of Hippke et al. 2019 (AJ 158, 143) recommends in front of a transit search, with window_length about three times the
@@ -193,20 +194,64 @@ def biweight_batch(t, flux_batch, window_length=0.5, break_tolerance=0.5, return
     may hold more than BIWEIGHT_MAX_WINDOW = 4095 points, and every flux value must be finite and > 0.  The arguments are
     checked before any device work.
 
-    devices=[...] deals the rows out over several GPUs, as the other survey calls.  Returns flat, or (flat, trend), in the
-    shape of flux_batch."""
-    from ._lib import biweight_arguments
-    t, rows, wl, bt = biweight_arguments(t, flux_batch, window_length, break_tolerance)
+    mask (uint8 or bool, flux_batch's shape, anything but 0: protected; None: today's call, untouched) leaves the protected
+    points -- the transits of a first search, transit_mask -- out of every fit (tls_biweight_detrend_masked).  The windows
+    stay those of t; the members of a window are its unprotected points.  A window with at least min_points (>= 1) members
+    -- or with all of its points, where it holds fewer than min_points -- gets their biweight location by the same loop
+    (status 0).  Any other point is open: its trend is interpolated linearly in
+    t between the nearest status-0 points to its left and right inside its segment, or taken from the one there is (status 1);
+    where the whole segment is open the point gets the plain biweight of its own window, the mask ignored (status 2), so the
+    trend is always defined.  flat = flux / trend at every point, the protected ones included.  An all-zero mask returns the
+    unmasked call's bits.  return_status=True (with a mask) appends the status rows (uint8).
+
+    devices=[...] deals the rows out over several GPUs, as the other survey calls (the mask rows with them).  Returns flat, or
+    (flat[, trend][, status]), in the shape of flux_batch."""
+    from ._lib import biweight_arguments, biweight_masked_arguments
+    if mask is None:
+        if return_status:
+            raise ValueError("return_status=True needs a mask")
+        t, rows, wl, bt = biweight_arguments(t, flux_batch, window_length, break_tolerance)
+
+        def call(ctx, lo, hi):
+            out = ctx.biweight_detrend(t, rows[lo:hi], wl, bt, return_trend=return_trend)
+            return dict(flat=out[0], trend=out[1]) if return_trend else dict(flat=out, trend=None)
+
+        out = _run_batch(devices, device, context, len(rows), call)
+        flat, trend = out["flat"], out["trend"]
+        if numpy.ndim(flux_batch) == 1:
+            flat, trend = flat[0], None if trend is None else trend[0]
+        return (flat, trend) if return_trend else flat
+    t, rows, mk, wl, bt, low = biweight_masked_arguments(t, flux_batch, mask, window_length, break_tolerance, min_points)
 
     def call(ctx, lo, hi):
-        out = ctx.biweight_detrend(t, rows[lo:hi], wl, bt, return_trend=return_trend)
-        return dict(flat=out[0], trend=out[1]) if return_trend else dict(flat=out, trend=None)
+        flat, trend, status = ctx.biweight_detrend_masked(t, rows[lo:hi], mk[lo:hi], wl, bt, low, return_trend=True,
+                                                          return_status=True)
+        return dict(flat=flat, trend=trend, status=status)
 
     out = _run_batch(devices, device, context, len(rows), call)
-    flat, trend = out["flat"], out["trend"]
+    res = (out["flat"],) + ((out["trend"],) if return_trend else ()) + ((out["status"],) if return_status else ())
     if numpy.ndim(flux_batch) == 1:
-        flat, trend = flat[0], None if trend is None else trend[0]
-    return (flat, trend) if return_trend else flat
+        res = tuple(v[0] for v in res)
+    return res[0] if len(res) == 1 else res
+
+
+# ---- detrending with the transits protected: the in-transit flags of a batch ----------------------------------------------
+def transit_mask(t, period, T0, duration, curve=None, n_curves=None, factor=1.5, context=None, device=None):
+    """The in-transit flags of a batch, uint8 [n_curves, len(t)] with 1 = protected, on the device (tls_transit_mask): what
+    biweight_batch(mask=), prewhiten_batch(mask=) and detrend_mask= of the survey calls take.  Candidate k -- period[k], T0[k],
+    duration[k] (days), of curve curve[k] (None: candidate k belongs to curve k) -- protects the points of its curve with
+
+        d = t[i] - T0;  e = floor(d / period + 0.5);  r = d - e * period;  abs(r) <= 0.5 * (factor * duration)
+
+    one IEEE double operation a step, so the flags equal tests/transit_protect_spec.py's bit for bit.  A curve may have any
+    number of candidates, in any order, or none; a candidate whose period, T0 or duration is not finite, or whose period or
+    duration is not > 0, is skipped silently (the NaN rows of a peaks array can be passed as they are).  n_curves None: the
+    number of candidates without curve, max(curve) + 1 with.  ValueError, before any device work, for shapes that disagree, a
+    non-finite t, a curve outside [0, n_curves) and a factor that is not finite and > 0."""
+    from ._lib import transit_mask_arguments
+    a = transit_mask_arguments(t, period, T0, duration, curve, n_curves, factor)
+    ctx = context if context is not None else _search.default_context(device)
+    return ctx.transit_mask(a["t"], a["period"], a["T0"], a["duration"], a["curve"], a["n_curves"], a["factor"])
 
 
 # ---- detrending: SysRem, the systematics the batch shares, fitted across its rows on the device ---------------------------
@@ -314,7 +359,7 @@ def _prewhiten_step(t, step, n):
 
 
 def prewhiten_batch(t, flux_batch, n_terms=3, harmonics=1, min_power=None, frequencies=None, dy_batch=None, return_trend=False,
-                    return_terms=False, context=None, device=None, devices=None):
+                    return_terms=False, context=None, device=None, devices=None, mask=None):
     """flat = flux / trend for every row of flux_batch ([n] or [n_curves, n], at the shared ascending time stamps t), with
     trend the row's mean plus its n_terms strongest sinusoids, found and fitted one after the other on the device
     (tls_prewhiten): iterative pre-whitening, the harmonic remover of the Kepler TPS and of Period04.  It is the detrender
@@ -336,12 +381,18 @@ def prewhiten_batch(t, flux_batch, n_terms=3, harmonics=1, min_power=None, frequ
     kernel, and the host reads a single count per iteration to stop when no row runs any more.
 
     min_power None: gls_power_threshold(n, F, fap=PREWHITEN_FAP = 1e-3), the power white noise reaches on the grid once in a
-    thousand curves, so that noise alone has nothing removed.  THE TRANSIT IS NOT PROTECTED: a box transit is itself periodic
+    thousand curves, so that noise alone has nothing removed.  WITHOUT A MASK THE TRANSIT IS NOT PROTECTED: a box transit is itself periodic
     (a 0.5 % transit of 3.3 d in 30 d of 3e-4 noise has periodogram power 0.07, well above that default), and once the
     stellar terms are gone the next term lands on the transit's period or a harmonic of it and removes part of the depth.
     Keep n_terms at the number of stellar signals, or keep the grid away from planetary periods with `frequencies` (or
     Prewhiten's f_min); DESIGN.md "Pre-whitening" has the measured depth kept in each case.  dy_batch: per-point errors (None:
     uniform weights).
+
+    mask (uint8 or bool, flux_batch's shape, anything but 0: protected; None: the call above, untouched) is the remedy where
+    the transits are known from a first search (transit_mask): a protected point has weight 0.0 in the mean, the variance, the
+    periodogram, the pick and the sinusoid fit (tls_prewhiten_masked; elsewhere 1 / dy^2, or 1.0, normalised to sum 1), so no
+    term can land on the transit; the subtraction and the trend still cover EVERY point.  A row with fewer than 3 unprotected
+    points has nothing removed (status 2).  The default min_power keeps using n = len(t).
 
     ValueError, before any device work, for non-finite input, a t that is not ascending, frequencies that are not finite and
     > 0, n < 3, n_terms outside [1, 32], harmonics outside [1, 8], min_power outside [0, 1] and shapes that disagree.
@@ -355,10 +406,18 @@ def prewhiten_batch(t, flux_batch, n_terms=3, harmonics=1, min_power=None, frequ
     if min_power is None:
         min_power = gls_power_threshold(int(n), len(frequencies), PREWHITEN_FAP) if n > 3 else 1.0
     a = prewhiten_arguments(t, flux_batch, dy_batch, frequencies, n_terms, harmonics, min_power)
+    if mask is not None:
+        from ._lib import detrend_mask_rows
+        mask = detrend_mask_rows(mask, a["y"].shape)
 
     def call(ctx, lo, hi):
-        out = ctx.prewhiten(a["t"], a["y"][lo:hi], a["frequencies"], a["n_terms"], a["harmonics"], a["min_power"],
-                            dy=None if a["dy"] is None else a["dy"][lo:hi], return_trend=True, return_terms=True)
+        dy = None if a["dy"] is None else a["dy"][lo:hi]
+        if mask is None:
+            out = ctx.prewhiten(a["t"], a["y"][lo:hi], a["frequencies"], a["n_terms"], a["harmonics"], a["min_power"], dy=dy,
+                                return_trend=True, return_terms=True)
+        else:
+            out = ctx.prewhiten_masked(a["t"], a["y"][lo:hi], mask[lo:hi], a["frequencies"], a["n_terms"], a["harmonics"],
+                                       a["min_power"], dy=dy, return_trend=True, return_terms=True)
         return dict(flat=out[0], trend=out[1], **out[2])
 
     out = _run_batch(devices, device, context, len(a["y"]), call)
@@ -400,12 +459,23 @@ def _first_context(context, device, devices, n_curves):
     return (context if context is not None else _search.default_context(what)), contextlib.nullcontext()
 
 
-def _detrended(t, flux_batch, detrend, context, device, devices, dy_batch=None):
+def _detrended(t, flux_batch, detrend, context, device, devices, dy_batch=None, detrend_mask=None):
     """flux_batch as it is (detrend None), or taken through the steps of detrend left to right on the call's devices for
     [n_curves, len(t)]: biweight_batch for a Biweight, the whole batch through SysRem on the first device (weighted with
     dy_batch where one is given) for a SysRem, prewhiten_batch (on variability_frequencies(t) cut to the step's range, weighted
-    with dy_batch where one is given) for a Prewhiten, detrend_batch(flux_batch, step) otherwise."""
+    with dy_batch where one is given) for a Prewhiten, detrend_batch(flux_batch, step) otherwise.  detrend_mask ([n_curves,
+    len(t)], uint8 or bool) goes to every Biweight and Prewhiten step as its mask; a SysRem step runs unmasked, a median-filter
+    step with a mask is a ValueError (before any step runs)."""
     steps = _detrend_steps(detrend)
+    if detrend_mask is not None:
+        from ._lib import detrend_mask_rows
+        if numpy.ndim(flux_batch) != 2:
+            raise ValueError("flux_batch must have shape [n_curves, len(t)]")
+        detrend_mask = detrend_mask_rows(detrend_mask, numpy.shape(flux_batch), "detrend_mask")
+        for step in steps:
+            if not isinstance(step, (Biweight, SysRem, Prewhiten)):
+                raise ValueError("detrend_mask: the median filter (detrend=%r) is defined by its sample count and zero padding "
+                                 "and has no masked form; use Biweight or Prewhiten steps with a mask" % (step,))
     if not steps:
         return flux_batch
     if numpy.ndim(flux_batch) != 2 or numpy.shape(flux_batch)[1] != len(t):
@@ -419,11 +489,11 @@ def _detrended(t, flux_batch, detrend, context, device, devices, dy_batch=None):
                 flux_batch = ctx.sysrem(rows, k, dy=dy, max_iter=iters, tol=tol)
         elif isinstance(step, Biweight):
             flux_batch = biweight_batch(t, flux_batch, step.window_length, step.break_tolerance, context=context,
-                                        device=device, devices=devices)
+                                        device=device, devices=devices, mask=detrend_mask)
         elif isinstance(step, Prewhiten):
             grid, k, h, low = _prewhiten_step(t, step, len(t))
             flux_batch = prewhiten_batch(t, flux_batch, k, h, low, frequencies=grid, dy_batch=dy_batch, context=context,
-                                         device=device, devices=devices)
+                                         device=device, devices=devices, mask=detrend_mask)
         else:
             flux_batch = detrend_batch(flux_batch, step, context=context, device=device, devices=devices)
     return flux_batch
@@ -460,7 +530,7 @@ def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_ar
                 event_vetting_search=1.0, event_vetting_chase_window=0.1, event_vetting_guard=1.5, event_vetting_min_ses=3.0,
                 event_vetting_chase_fraction=0.6, event_vetting_chase_min=0.5, event_vetting_point_fraction=0.5,
                 event_vetting_step_fraction=0.5, centroids=None, centroid_window=3.0, centroid_min_in=1,
-                centroid_min_out=3, noise=None, **power_kwargs):
+                centroid_min_out=3, noise=None, detrend_mask=None, **power_kwargs):
     """Survey-mode power(): for every light curve of `flux_batch` what `transitleastsquares(t, flux).power(**kwargs)`
     reports as SDE, SDE_raw, chi2_min, period, T0, depth and duration (fractional, lc_cache_overview["duration"] of
     the template row at the chi^2 minimum, main.py:199-200) -- search, SDE spectra and final T0 fit all on the
@@ -489,6 +559,11 @@ def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_ar
     the systematics the rows SHARE (sysrem_batch: fitted over the WHOLE batch on one device -- the given context, or the
     first of `devices` -- and weighted with dy_batch where one is given; the rows are then dealt out as before), and a tuple
     or list applies its steps left to right, e.g. (SysRem(2), Biweight(0.5)).  detrend=None searches flux_batch as given.
+    detrend_mask ([n_curves, n], uint8 or bool, anything but 0: protected -- transit_mask) is given to every Biweight and
+    Prewhiten step of detrend as its mask (biweight_batch, prewhiten_batch): the protected points are left out of the fits, the
+    rows that are searched keep every point.  A SysRem step runs UNMASKED (its fit spans the rows and has no masked form here);
+    a median-filter step together with a mask raises ValueError before any device work (that filter is defined by its sample
+    count and zero padding, equal to scipy, and gets no masked form).  power_batch_protected is the two-pass flow in one call.
 
     peaks=K (1 to 32) also returns the K highest harmonic-aware peaks of every curve's detrended power -- the runners-up of the
     one pick: a second planet, a binary under its alias -- selected on the device from the spectrum it already holds
@@ -606,8 +681,8 @@ def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_ar
     array with the fields of tls_power_summary plus "duration" (and the statistics on request)."""
     return _power_batch(t, flux_batch, dy_batch, power_kwargs, context=context, device=device, devices=devices,
                         with_arrays=with_arrays, statistics=statistics, per_transit=per_transit, models=models,
-                        detrend=detrend, peaks=_peaks_request(peaks, peak_separation, peak_ratios, peak_min_power, models,
-                                                              peak_fits),
+                        detrend=detrend, detrend_mask=detrend_mask,
+                        peaks=_peaks_request(peaks, peak_separation, peak_ratios, peak_min_power, models, peak_fits),
                         peak_fits=bool(peak_fits),
                         phase_scan=_phase_scan_request(phase_scan, peak_fits, phase_scan_max_bins, phase_scan_min_count),
                         transit_times=_transit_times_request(transit_times, peak_fits, transit_times_search,
@@ -786,7 +861,7 @@ def find_peaks(power, periods, k, separation=0.02, ratios=HARMONICS, min_power=N
 def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=None, devices=None, with_arrays=False,
                  statistics=False, per_transit=False, models=False, spectra=False, detrend=None, peaks=None,
                  peak_fits=False, phase_scan=None, transit_times=None, shape_fit=None, sine_test=None, ephemeris_match=None,
-                 views=None, event_vetting=None, centroids=None, noise=None):
+                 views=None, event_vetting=None, centroids=None, noise=None, detrend_mask=None):
     """power_batch; spectra=True (power_results) also returns SR and power_raw [n_curves, n_periods] behind the arrays;
     peaks: None or a checked request (_peaks_request); peak_fits: with peaks, their T0 fits and statistics; phase_scan: None or a checked
     request (_phase_scan_request), with peak_fits, the fits' phase scans; transit_times: None or a checked request
@@ -804,7 +879,7 @@ def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=Non
         t_check = numpy.asarray(t, dtype=numpy.float64)
         if t_check.ndim != 1 or not numpy.all(t_check[1:] >= t_check[:-1]):
             raise ValueError("%s=True needs ascending time stamps t" % ("statistics" if statistics else "peak_fits"))
-    flux_batch = _detrended(t, flux_batch, detrend, context, device, devices, dy_batch)
+    flux_batch = _detrended(t, flux_batch, detrend, context, device, devices, dy_batch, detrend_mask)
     inp, y_rows, dy_rows = _batch_inputs(t, flux_batch, dy_batch, power_kwargs)
     from . import constants as C
     osf = power_kwargs.get("oversampling_factor", C.OVERSAMPLING_FACTOR)
@@ -949,7 +1024,8 @@ def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=Non
     return result
 
 
-def power_results(t, flux_batch, dy_batch=None, context=None, device=None, devices=None, detrend=None, **power_kwargs):
+def power_results(t, flux_batch, dy_batch=None, context=None, device=None, devices=None, detrend=None, detrend_mask=None,
+                  **power_kwargs):
     """power()'s results object for every light curve of `flux_batch` (shape [n_curves, len(t)], shared ascending time
     stamps): a list of transitleastsquaresresults, element k equal to
     transitleastsquares(t, flux_batch[k], dy_batch[k]).power(**power_kwargs) key for key and in key order (41 keys).  Search,
@@ -965,7 +1041,8 @@ def power_results(t, flux_batch, dy_batch=None, context=None, device=None, devic
     devices=[...] deals the batch out over several GPUs, as the other survey calls.  detrend=k searches
     flux_batch / medfilt(flux_batch, k) (detrend_batch), detrend=Biweight(...) the rows biweight_batch forms,
     detrend=SysRem(...) the rows sysrem_batch forms and a tuple its steps left to right, as power_batch does; the objects
-    then describe the detrended rows."""
+    then describe the detrended rows.  detrend_mask: power_batch's (the mask of every Biweight and Prewhiten step; SysRem
+    runs unmasked; a median-filter step with a mask is a ValueError)."""
     from .api import transitleastsquares
     from .results import transitleastsquaresresults
     if len(numpy.shape(flux_batch)) != 2 or numpy.shape(flux_batch)[1] != len(t):
@@ -974,7 +1051,7 @@ def power_results(t, flux_batch, dy_batch=None, context=None, device=None, devic
         raise ValueError("dy_batch must have the shape of flux_batch")
     summary, periods, chi2, row, depth, power, pt, m, SR, power_raw = _power_batch(
         t, flux_batch, dy_batch, power_kwargs, context=context, device=device, devices=devices, with_arrays=True,
-        statistics=True, per_transit=True, models=True, spectra=True, detrend=detrend)
+        statistics=True, per_transit=True, models=True, spectra=True, detrend=detrend, detrend_mask=detrend_mask)
     n = len(m["model_folded_phase"])
     chi2red = chi2 / (n - 4)   # (main.py:210-212)
     out = []
@@ -1003,7 +1080,58 @@ def power_results(t, flux_batch, dy_batch=None, context=None, device=None, devic
     return out
 
 
-def search_batch(t, flux_batch, dy_batch=None, context=None, device=None, devices=None, detrend=None, **power_kwargs):
+def power_batch_protected(t, flux_batch, detrend, sde_min, factor=1.5, n_peaks=1, **power_batch_kwargs):
+    """The two-pass flow in one call: search, mask the candidates' transits, detrend the RAW rows again with those points left
+    out of the fits, search the result.
+
+        pass 1: power_batch(t, flux_batch, detrend=detrend, peaks=n_peaks, peak_fits=True, ...)
+        mask:   transit_mask of the fitted peaks (period, T0, duration_days; status 0) of the curves with SDE >= sde_min,
+                `factor` durations wide, built on the device
+        pass 2: power_batch(t, flux_batch, detrend=detrend, detrend_mask=mask, ...) with the caller's own options
+
+    sde_min has no default: sde_threshold (from null_sde's table) chooses it.  A curve below sde_min has an all-zero mask row
+    and comes out of pass 2 as from plain power_batch(detrend=...).  power_batch_kwargs are power_batch's (dy_batch, context,
+    device, devices, statistics, peaks, ..., and the search's own keywords); pass 1 takes of them only what the search itself
+    needs (dy_batch, the context or devices and the search's keywords) with peak_ratios, peak_separation and peak_min_power.
+    detrend must hold a Biweight or Prewhiten step for the mask to act; a median-filter step raises ValueError, a SysRem step
+    runs unmasked.  ValueError, before any device work, for a factor that is not finite and > 0, an sde_min that is not a
+    number (NaN included) and n_peaks outside [1, 32].
+
+    Returns (pass 2's result, info): info is a dict with `protected` [n_curves] bool (SDE of pass 1 >= sde_min), `mask`
+    (uint8 [n_curves, n]) and `summary` (pass 1's)."""
+    if isinstance(factor, (bool, numpy.bool_)) or not isinstance(factor, numbers.Real) or not (0.0 < float(factor) < numpy.inf):
+        raise ValueError("power_batch_protected: factor must be finite and > 0, got %r" % (factor,))
+    if isinstance(sde_min, (bool, numpy.bool_)) or not isinstance(sde_min, numbers.Real) or numpy.isnan(sde_min):
+        raise ValueError("power_batch_protected: sde_min must be a number, got %r" % (sde_min,))
+    if "detrend_mask" in power_batch_kwargs:
+        raise ValueError("power_batch_protected forms detrend_mask itself")
+    for step in _detrend_steps(detrend):
+        if not isinstance(step, (Biweight, SysRem, Prewhiten)):
+            raise ValueError("power_batch_protected: the median filter (detrend=%r) has no masked form; use Biweight or "
+                             "Prewhiten steps" % (step,))
+    _peaks_request(n_peaks, power_batch_kwargs.get("peak_separation", 0.02), power_batch_kwargs.get("peak_ratios", HARMONICS),
+                   power_batch_kwargs.get("peak_min_power"), False, True)
+    keep = {"dy_batch", "context", "device", "devices", "peak_separation", "peak_ratios", "peak_min_power"}
+    named = {k for k, p in inspect.signature(power_batch).parameters.items() if p.kind is p.POSITIONAL_OR_KEYWORD}
+    first = {k: v for k, v in power_batch_kwargs.items() if k in keep or k not in named}   # (not named: the search's keywords)
+    out = power_batch(t, flux_batch, detrend=detrend, peaks=n_peaks, peak_fits=True, **first)
+    summary, peaks = out[0], out[-1]["peaks"]
+    protected = summary["SDE"] >= sde_min
+    n_curves = len(summary)
+    use = protected[:, None] & (peaks["status"] == 0)
+    curve = numpy.broadcast_to(numpy.arange(n_curves)[:, None], use.shape)[use]
+    from ._lib import transit_mask_arguments
+    a = transit_mask_arguments(t, peaks["period"][use], peaks["T0"][use], peaks["duration_days"][use], curve, n_curves, factor)
+    ctx, lock = _first_context(power_batch_kwargs.get("context"), power_batch_kwargs.get("device"),
+                               power_batch_kwargs.get("devices"), n_curves)
+    with lock:
+        mask = ctx.transit_mask(a["t"], a["period"], a["T0"], a["duration"], a["curve"], a["n_curves"], a["factor"])
+    result = power_batch(t, flux_batch, detrend=detrend, detrend_mask=mask, **power_batch_kwargs)
+    return result, dict(protected=protected, mask=mask, summary=summary)
+
+
+def search_batch(t, flux_batch, dy_batch=None, context=None, device=None, devices=None, detrend=None, detrend_mask=None,
+                 **power_kwargs):
     """Search every light curve of `flux_batch` (shape [n_curves, n_points]) on the grids that
     `transitleastsquares(t, flux).power(**power_kwargs)` would use.
 
@@ -1011,9 +1139,10 @@ def search_batch(t, flux_batch, dy_batch=None, context=None, device=None, device
     share `t` and be free of invalid points (clean them first); a `dy_batch` must have the same
     weight structure for every curve (all uniform or all per-point).  detrend=k searches flux_batch / medfilt(flux_batch, k)
     (detrend_batch), detrend=Biweight(...) the rows biweight_batch forms, detrend=SysRem(...) the rows sysrem_batch forms
-    (one fit over the whole batch) and a tuple its steps left to right, as power_batch does.
+    (one fit over the whole batch) and a tuple its steps left to right, as power_batch does.  detrend_mask: power_batch's (the
+    mask of every Biweight and Prewhiten step; SysRem runs unmasked; a median-filter step with a mask is a ValueError).
     """
-    flux_batch = _detrended(t, flux_batch, detrend, context, device, devices, dy_batch)
+    flux_batch = _detrended(t, flux_batch, detrend, context, device, devices, dy_batch, detrend_mask)
     inp, y_rows, dy_rows = _batch_inputs(t, flux_batch, dy_batch, power_kwargs)
 
     def call(ctx, lo, hi):
@@ -2032,7 +2161,7 @@ def variability_frequencies(t, oversampling=5, f_max=None):
 
 
 def lomb_scargle(t, flux_batch, frequencies=None, dy_batch=None, peaks=None, with_arrays=True, detrend=None, context=None,
-                 device=None, devices=None, peak_separation=0.02):
+                 device=None, devices=None, peak_separation=0.02, detrend_mask=None):
     """The generalised (floating-mean, weighted) Lomb-Scargle periodogram of Zechmeister & Kuerster (2009) of every light
     curve of flux_batch [n_curves, n] (or one row [n]) on the shared ascending time stamps t, on the device
     (tls_lomb_scargle): is the STAR periodic -- spots, pulsations, a contact binary -- and at which period?  frequencies
@@ -2055,8 +2184,9 @@ def lomb_scargle(t, flux_batch, frequencies=None, dy_batch=None, peaks=None, wit
 
     peaks=K also selects the K highest peaks of every curve on the device, from the power where it lies, by the selection of
     find_peaks with periods = 1 / frequencies, separation peak_separation and the ratios (0.5, 2.0); with_arrays=False then
-    brings back the peaks alone.  detrend= takes the steps and tuples of search_batch, devices=[...] deals the curves out over
-    several GPUs.  ValueError, before any device work (the detrending included), for non-finite input, a t that is not
+    brings back the peaks alone.  detrend= takes the steps and tuples of search_batch and detrend_mask= its mask (for the
+    Biweight and Prewhiten steps; SysRem runs unmasked; a median-filter step with a mask is a ValueError; the periodogram
+    itself uses every point), devices=[...] deals the curves out over several GPUs.  ValueError, before any device work (the detrending included), for non-finite input, a t that is not
     ascending, frequencies that are not finite and > 0, n < 3 and shapes that disagree.
 
     Returns a dict: frequencies [F], mean (ybar) and variance (YY) [n_curves]; power, amplitude, phase [n_curves, F] with
@@ -2066,7 +2196,7 @@ def lomb_scargle(t, flux_batch, frequencies=None, dy_batch=None, peaks=None, wit
         frequencies = variability_frequencies(t)
     one = numpy.ndim(flux_batch) == 1
     a = lomb_scargle_arguments(t, flux_batch, dy_batch, frequencies, peaks, peak_separation)
-    rows = _detrended(a["t"], a["y"], detrend, context, device, devices, a["dy"])
+    rows = _detrended(a["t"], a["y"], detrend, context, device, devices, a["dy"], detrend_mask)
 
     def call(ctx, lo, hi):
         return ctx.lomb_scargle(a["t"], rows[lo:hi], a["frequencies"], None if a["dy"] is None else a["dy"][lo:hi], peaks=peaks,
