@@ -41,7 +41,7 @@ extern "C" {
  * tls_debug_peak_phase_scans), (7: tls_sysrem), (7: tls_single_transits), (7: tls_transit_times),
  * (7: tls_shape_fit), (7: tls_nudft, tls_lomb_scargle, tls_sine_test); 8: every entry that takes `root, n_root` takes a
  * second table, `root, root_count, n_root`), (8: tls_ephemeris_match), (8: tls_folded_views),
- * (8: tls_event_vetting), (8: tls_centroid_test), (8: tls_noise_profile). */
+ * (8: tls_event_vetting), (8: tls_centroid_test), (8: tls_noise_profile), (8: tls_transit_fit). */
 #define TLS_AMD_ABI_VERSION 8
 
 #define TLS_OK 0
@@ -1213,6 +1213,69 @@ typedef struct tls_noise_curve {
 int tls_noise_profile(tls_ctx *ctx, const double *t, const double *y, int64_t n, int64_t n_curves, const int64_t *widths,
                       const double *span_max, int64_t n_widths, double pair_span, double clip_upper, double clip_lower,
                       int64_t min_count, tls_noise_curve *out_curves, int64_t *out_count, double *out_robust, double *out_rms);
+
+/* The limb-darkened transit fit: the planet's size, impact parameter and T14 from the dip itself, with the exposure time in
+ * the model.  A straight chord at constant speed crosses a limb-darkened disc: the separation is z^2 = b^2 + ((1 + k)^2 - b^2)
+ * v^2, v = (time from mid-transit) / (T / 2), contacts at |v| == 1; the dip at z comes from a profile table the HOST forms
+ * (any limb-darkening law: the device needs no acos and no log), averaged over S sub-exposures; the depth amplitude A is free
+ * and the baseline fixed at 1.  For a curve (y [n], dy [n] over the ascending, finite t [n]), a candidate (P, T0, d in days,
+ * seed row j0), the table k_rows[nK] ascending and > 0 with profile[nK][M + 1], profile[j][m] = 1 - F((1 + k_rows[j]) m / M;
+ * k_rows[j]) and profile[j][M] = 0, the ascending tables impact[nB] in [0, 1) (b as a fraction of 1 + k), ratio[nT] > 0,
+ * shift[nS], and the sub-exposure offsets sub[S] in days (S == 1, sub[0] == 0: no smearing):
+ *   w = 1.0 / (dy * dy);  xw = (1.0 - y) * w
+ *   status 1 and NaN in every other field unless P, T0, d are finite, P > 0, d > 0 and wd = window * d < 0.5 * P
+ *   members, i ascending:  x = (t[i] - T0) / P;  k = floor(x + 0.5);  tau = (x - k) * P;  member iff fabs(tau) <= wd
+ *   x2 = x2 + (xw * xw) / w over the members in index order
+ *   one pass with row j, p = profile[j]:  e1 = 1.0 + k_rows[j];  e2 = e1 * e1;  sM = M / e1
+ *     unit (ib, a, c), ib outermost, c innermost (unit index (ib * nT + a) * nS + c):
+ *       b = impact[ib] * e1;  bb = b * b;  cc = e2 - bb;  T = d * ratio[a];  rh = 1.0 / (0.5 * T);  c0 = d * shift[c]
+ *       cnt = 0; N = 0; D = 0; over the members in index order:
+ *         acc = 0.0;  for s = 0 .. S - 1:  ts = tau + sub[s];  v = (ts - c0) * rh;  vv = v * v;  zz = bb + cc * vv
+ *           sample = 0.0 unless zz < e2, else  z = sqrt(zz);  q = z * sM;  m = min(floor(q), M - 1);  fr = q - m
+ *           sample = p[m] + (p[m + 1] - p[m]) * fr;  acc = acc + sample
+ *         mval = acc / S;  the member counts iff mval > 0:  cnt += 1;  N = N + xw * mval;  D = D + w * (mval * mval)
+ *       valid iff cnt >= min_count and D > 0 and A = N / D > 0;  q = N / sqrt(D)
+ *     the pick = the valid unit of the largest q, the first in unit order among equals
+ *   pass 1 uses row j0;  k1 = k_rows[j0] * sqrt(A of its pick);  j1 = the row of the least fabs(k_rows[j] - k1), the lowest j
+ *   among equals;  pass 2 uses row j1 (where j1 == j0 it is pass 1);  status 2 (n_points reported, the rest NaN) if a pass
+ *   has no valid unit.  The row only shapes ingress and egress; the size is carried by A:  k = k_rows[j1] * sqrt(A).
+ *   intervals: the least and the largest k_rows[j1] * sqrt(A_u), b_u, T_u, c0_u over the valid units of pass 2 with
+ *   q_u * q_u >= q * q - delta: a profile-likelihood range.
+ * Every step is one IEEE double operation and every sum runs in index order: the record equals the Python statement in
+ * tests/transit_fit_spec.py bit for bit.  All fields are doubles; `reserved` is 0 whatever the status. */
+#define TLS_TRANSIT_FIT_MAX_UNITS 65536
+#define TLS_TRANSIT_FIT_MAX_M 4096
+#define TLS_TRANSIT_FIT_MAX_SUB 16
+#define TLS_TRANSIT_FIT_MAX_ROWS 4096
+typedef struct tls_transit_fit_record {
+    double status;                 /* 0 fitted; 1 no such candidate (P, T0, d, or a window of half a period or more); 2 no valid unit */
+    double n_points;               /* the members */
+    double n_in;                   /* cnt of the pick */
+    double row_first, row;         /* j0, j1 */
+    double ses, amplitude;         /* q and A of the pick */
+    double k, b, duration, shift;  /* k_rows[j1] * sqrt(A), impact[ib] * (1 + k_rows[j1]), T (days), c0 (days) */
+    double i_impact, i_duration, i_shift;      /* ib, a, c */
+    double x2;                     /* sum of (1 - y)^2 / dy^2 over the members */
+    double k_lo, k_hi, b_lo, b_hi, duration_lo, duration_hi, shift_lo, shift_hi;
+    double reserved;
+} tls_transit_fit_record;
+/* n_fits candidates (period[f], T0[f], duration[f], row_first[f]) on the curves curve[f] of y, dy [n_curves][n] over the
+ * shared time stamps t [n].  out_records [n_fits].  Needs no plan and no search, and leaves a prepared plan as it is.
+ * n_fits == 0 is a no-op.  Candidates are processed in slabs, so device memory stays bounded for any n_fits.  TLS_E_ARG,
+ * before any device work and with the output untouched, for a curve[f] outside [0, n_curves), a row_first[f] outside
+ * [0, n_k), n outside [1, 2^22], negative counts, an empty table, n_b * n_t * n_s above TLS_TRANSIT_FIT_MAX_UNITS, M outside
+ * [1, TLS_TRANSIT_FIT_MAX_M], n_sub outside [1, TLS_TRANSIT_FIT_MAX_SUB], n_k above TLS_TRANSIT_FIT_MAX_ROWS, a table that is
+ * not finite and non-decreasing (sub and profile: finite), k_rows[0] <= 0, impact outside [0, 1), a ratio <= 0, a window
+ * that is not finite or, for a candidate with finite d > 0, has window * d below (0.5 * ratio[n_t-1] + max(fabs(shift[0]),
+ * fabs(shift[n_s-1]))) * d + max fabs(sub[s]) (the widest, farthest shifted model plus half an exposure must lie inside the
+ * window), min_count < 1, a non-finite or negative delta, and a t that is not finite and non-decreasing.  y and dy are taken
+ * as they are (dy > 0); period, T0 and duration may hold any value (status 1). */
+int tls_transit_fit(tls_ctx *ctx, const double *t, const double *y, const double *dy, int64_t n, int64_t n_curves,
+                    const int64_t *curve, const double *period, const double *T0, const double *duration,
+                    const int64_t *row_first, int64_t n_fits, const double *k_rows, const double *profile, int64_t n_k,
+                    int64_t M, const double *impact, int64_t n_b, const double *ratio, int64_t n_t, const double *shift,
+                    int64_t n_s, const double *sub, int64_t n_sub, double window, int64_t min_count, double delta,
+                    tls_transit_fit_record *out_records /* [n_fits] */);
 
 /* ---- host-only planning (no GPU needed) ------------------------------------------ */
 /* Trial cells (duration x T0 positions) each period will enumerate: the data-independent

@@ -116,6 +116,7 @@ SYMBOLS = (
     "tls_phase_scan", "tls_power_batch_phase_scan", "tls_debug_peak_phase_scans", "tls_single_transits",
     "tls_transit_times", "tls_shape_fit", "tls_nudft", "tls_lomb_scargle", "tls_sine_test", "tls_prewhiten",
     "tls_ephemeris_match", "tls_folded_views", "tls_event_vetting", "tls_centroid_test", "tls_noise_profile",
+    "tls_transit_fit",
     "tls_transit_mask", "tls_biweight_detrend_masked", "tls_prewhiten_masked",
     "tls_comm_unique_id", "tls_comm_init", "tls_comm_destroy", "tls_comm_info", "tls_comm_allgather_results", "tls_comm_allgather_device", "tls_comm_fetch_gathered",
     "tls_comm_stage_results", "tls_comm_allgather_staged", "tls_comm_fetch_staged",
@@ -720,6 +721,110 @@ def shape_fit_arguments(t, y, dy, period, T0, duration, ratios, ingress, shifts,
                 min_count=min_count, depth_min=depth_min)
 
 
+# tls_transit_fit_record (include/tls_amd.h): a candidate's limb-darkened transit fit, 24 doubles; the limits of
+# tls_transit_fit (TLS_TRANSIT_FIT_MAX_*; tls_transit_fit.hip.h kTransitMax*)
+TRANSIT_FIT_FIELDS = ("status", "n_points", "n_in", "row_first", "row", "ses", "amplitude", "k", "b", "duration", "shift",
+                      "i_impact", "i_duration", "i_shift", "x2", "k_lo", "k_hi", "b_lo", "b_hi", "duration_lo", "duration_hi",
+                      "shift_lo", "shift_hi", "reserved")
+TRANSIT_FIT_MAX_UNITS = 65536
+TRANSIT_FIT_MAX_M = 4096
+TRANSIT_FIT_MAX_SUB = 16
+TRANSIT_FIT_MAX_ROWS = 4096
+TRANSIT_FIT_SLAB = 512
+
+
+class TransitFitRecord(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_double) for k in TRANSIT_FIT_FIELDS]
+
+
+TRANSIT_FIT_DTYPE = numpy.dtype([(k, "f8") for k in TRANSIT_FIT_FIELDS])
+
+
+def transit_fit_tables(k_rows, profile, impacts, ratios, shifts, sub, window=1.0, min_count=3, delta=1.0):
+    """(k_rows, profile, impact, ratio, shift, sub, window, min_count, delta) as tls_transit_fit takes them, checked as it
+    checks them: k_rows [nK] finite, ascending and > 0, nK <= TRANSIT_FIT_MAX_ROWS; profile [nK, M + 1] finite with M in
+    [1, TRANSIT_FIT_MAX_M]; impacts, ratios, shifts 1-D, not empty, finite and ascending, impacts in [0, 1), ratios > 0, at
+    most TRANSIT_FIT_MAX_UNITS units; sub [S] finite, S in [1, TRANSIT_FIT_MAX_SUB]; window finite and at least
+    0.5 * max(ratio) + max|shift|; min_count an integer >= 1; delta finite and >= 0.  ValueError otherwise."""
+    tables = []
+    for name, v in (("k_rows", k_rows), ("impacts", impacts), ("ratios", ratios), ("shifts", shifts), ("sub", sub)):
+        try:
+            v = numpy.ascontiguousarray(numpy.asarray(v, dtype=numpy.float64))
+        except (TypeError, ValueError):
+            raise ValueError("transit fit: %s must hold numbers" % name)
+        if v.ndim != 1 or len(v) < 1:
+            raise ValueError("transit fit: %s must be a table [k] with k >= 1, got shape %s" % (name, v.shape))
+        if not numpy.all(numpy.isfinite(v)) or (name != "sub" and not numpy.all(v[1:] >= v[:-1])):
+            raise ValueError("transit fit: %s must be finite%s" % (name, "" if name == "sub" else " and ascending"))
+        tables.append(v)
+    k_rows, impact, ratio, shift, sub = tables
+    if not k_rows[0] > 0.0 or len(k_rows) > TRANSIT_FIT_MAX_ROWS:
+        raise ValueError("transit fit: k_rows must hold at most %d values > 0" % TRANSIT_FIT_MAX_ROWS)
+    try:
+        profile = numpy.ascontiguousarray(numpy.asarray(profile, dtype=numpy.float64))
+    except (TypeError, ValueError):
+        raise ValueError("transit fit: profile must hold numbers")
+    if profile.ndim != 2 or profile.shape[0] != len(k_rows) or not 1 <= profile.shape[1] - 1 <= TRANSIT_FIT_MAX_M:
+        raise ValueError("transit fit: profile must be [len(k_rows), M + 1] with M in [1, %d], got shape %s"
+                         % (TRANSIT_FIT_MAX_M, profile.shape))
+    if not numpy.all(numpy.isfinite(profile)):
+        raise ValueError("transit fit: profile must be finite")
+    if not (impact[0] >= 0.0 and impact[-1] < 1.0):
+        raise ValueError("transit fit: every impact must be in [0, 1)")
+    if not ratio[0] > 0.0:
+        raise ValueError("transit fit: every ratio must be > 0, got %r" % ratio[0])
+    if len(sub) > TRANSIT_FIT_MAX_SUB:
+        raise ValueError("transit fit: n_sub %d outside [1, %d]" % (len(sub), TRANSIT_FIT_MAX_SUB))
+    units = len(impact) * len(ratio) * len(shift)
+    if not 1 <= units <= TRANSIT_FIT_MAX_UNITS:
+        raise ValueError("transit fit: %d units, outside [1, %d]" % (units, TRANSIT_FIT_MAX_UNITS))
+    if isinstance(window, (bool, numpy.bool_)) or not isinstance(window, numbers.Real) or not numpy.isfinite(window):
+        raise ValueError("transit fit: window must be finite, got %r" % (window,))
+    least = 0.5 * float(ratio[-1]) + max(abs(float(shift[0])), abs(float(shift[-1])))
+    if not float(window) >= least:
+        raise ValueError("transit fit: window %r is below 0.5 * max(ratio) + max|shift| = %r: the model must lie inside it"
+                         % (window, least))
+    if isinstance(min_count, (bool, numpy.bool_)) or not isinstance(min_count, numbers.Integral) or int(min_count) < 1:
+        raise ValueError("transit fit: min_count must be an integer >= 1, got %r" % (min_count,))
+    if isinstance(delta, (bool, numpy.bool_)) or not isinstance(delta, numbers.Real) or not (0.0 <= float(delta) < numpy.inf):
+        raise ValueError("transit fit: delta must be finite and >= 0, got %r" % (delta,))
+    return k_rows, profile, impact, ratio, shift, sub, float(window), int(min_count), float(delta)
+
+
+def transit_fit_window_holds(duration, ratio, shift, sub, window):
+    """Whether the window of every candidate with a finite duration > 0 holds the widest, farthest shifted model plus half an
+    exposure, as tls_transit_fit checks it: window * d >= (0.5 * ratio[-1] + max|shift|) * d + max|sub|."""
+    d = numpy.asarray(duration, dtype=numpy.float64)
+    reach = 0.5 * float(ratio[-1]) + max(abs(float(shift[0])), abs(float(shift[-1])))
+    sub_reach = float(numpy.max(numpy.fabs(sub)))
+    with numpy.errstate(all="ignore"):
+        checked = numpy.isfinite(d) & (d > 0.0)
+        return bool(numpy.all(~checked | (float(window) * d >= reach * d + sub_reach)))
+
+
+def transit_fit_arguments(t, y, dy, period, T0, duration, row_first, k_rows, profile, impacts, ratios, shifts, sub, curve=None,
+                          window=1.0, min_count=3, delta=1.0):
+    """What tls_transit_fit takes, checked as it checks them and packed for it -- a dict with t [n], y and dy [n_curves, n],
+    period, T0, duration, curve [n_fits] (as shape_fit_arguments has them), row_first [n_fits] int64 in [0, nK), and k_rows,
+    profile, impact, ratio, shift, sub, window, min_count, delta (transit_fit_tables).  ValueError otherwise.  GPU-free."""
+    k_rows, profile, impact, ratio, shift, sub, window, min_count, delta = transit_fit_tables(
+        k_rows, profile, impacts, ratios, shifts, sub, window, min_count, delta)
+    try:
+        a = shape_fit_arguments(t, y, dy, period, T0, duration, [1.0], [0.0, 0.5], [0.0], curve)
+    except ValueError as e:
+        raise ValueError(str(e).replace("shape fit:", "transit fit:"))
+    rows = numpy.atleast_1d(numpy.asarray(row_first))
+    if rows.shape != a["period"].shape or (rows.size and (rows.dtype.kind not in "iu" or rows.min() < 0
+                                                            or rows.max() >= len(k_rows))):
+        raise ValueError("transit fit: row_first must hold one row in [0, %d) a candidate" % len(k_rows))
+    if not transit_fit_window_holds(a["duration"], ratio, shift, sub, window):
+        raise ValueError("transit fit: window %r does not hold the widest, farthest shifted model plus half an exposure for "
+                         "the shortest duration" % (window,))
+    return dict(t=a["t"], y=a["y"], dy=a["dy"], period=a["period"], T0=a["T0"], duration=a["duration"], curve=a["curve"],
+                row_first=numpy.ascontiguousarray(rows, dtype=numpy.int64), k_rows=k_rows, profile=profile, impact=impact,
+                ratio=ratio, shift=shift, sub=sub, window=window, min_count=min_count, delta=delta)
+
+
 # tls_centroid_record (include/tls_amd.h): a candidate's centroid-shift test, 16 doubles
 CENTROID_FIELDS = ("status", "n_epochs", "n_skipped", "n_points", "n_in", "depth", "depth_err", "shift_x", "shift_x_err",
                    "shift_y", "shift_y_err", "rms_x", "rms_y", "chi2_depth", "chi2_x", "chi2_y")
@@ -1204,6 +1309,10 @@ def load():
     lib.tls_shape_fit.argtypes = [vp, _c_double_p, _c_double_p, _c_double_p, i64, i64, _c_double_p, _c_double_p, _c_double_p,
                                   _c_int64_p, i64, _c_double_p, i64, _c_double_p, i64, _c_double_p, i64, dbl, i64, dbl,
                                   ctypes.c_void_p]
+    lib.tls_transit_fit.restype = ci
+    lib.tls_transit_fit.argtypes = [vp, _c_double_p, _c_double_p, _c_double_p, i64, i64, _c_int64_p, _c_double_p, _c_double_p,
+                                    _c_double_p, _c_int64_p, i64, _c_double_p, _c_double_p, i64, i64, _c_double_p, i64,
+                                    _c_double_p, i64, _c_double_p, i64, _c_double_p, i64, dbl, i64, dbl, ctypes.c_void_p]
     lib.tls_centroid_test.restype = ci
     lib.tls_centroid_test.argtypes = [vp, _c_double_p, _c_double_p, _c_double_p, _c_double_p, i64, i64, _c_double_p,
                                       _c_double_p, _c_double_p, _c_int64_p, i64, _c_double_p, i64, dbl, i64, i64, i64,
@@ -2302,6 +2411,27 @@ class Context(object):
             a["pair_span"], a["clip_upper"], a["clip_lower"], a["min_count"], records.ctypes.data_as(ctypes.c_void_p),
             _ip(count), _dp(robust), _dp(rms)))
         return records, count, robust, rms
+
+    def transit_fit(self, t, y, dy, period, T0, duration, row_first, k_rows, profile, impacts, ratios, shifts, sub, curve=None,
+                    window=1.0, min_count=3, delta=1.0):
+        """The limb-darkened transit fits (tls_transit_fit; the statement: include/tls_amd.h, tests/transit_fit_spec.py) of
+        the candidates (period[f], T0[f], duration[f] in days, seed row row_first[f]) on the curves curve[f] (None: one
+        candidate a curve, in order) of y, dy [n_curves, n] (or one row) over t [n], with the profile table (k_rows,
+        profile), over the units of the tables impacts, ratios, shifts and the sub-exposure offsets sub:
+        TRANSIT_FIT_DTYPE [n_fits].  ValueError for what transit_fit_arguments refuses."""
+        a = transit_fit_arguments(t, y, dy, period, T0, duration, row_first, k_rows, profile, impacts, ratios, shifts, sub,
+                                  curve, window, min_count, delta)
+        n_c, n = a["y"].shape
+        n_fits = len(a["period"])
+        out = numpy.zeros(n_fits, dtype=TRANSIT_FIT_DTYPE)
+        assert TRANSIT_FIT_DTYPE.itemsize == ctypes.sizeof(TransitFitRecord)
+        self._check(self._lib.tls_transit_fit(
+            self._h, _dp(a["t"]), _dp(a["y"]), _dp(a["dy"]), n, n_c, _ip(a["curve"]), _dp(a["period"]), _dp(a["T0"]),
+            _dp(a["duration"]), _ip(a["row_first"]), n_fits, _dp(a["k_rows"]), _dp(a["profile"]), len(a["k_rows"]),
+            a["profile"].shape[1] - 1, _dp(a["impact"]), len(a["impact"]), _dp(a["ratio"]), len(a["ratio"]), _dp(a["shift"]),
+            len(a["shift"]), _dp(a["sub"]), len(a["sub"]), a["window"], a["min_count"], a["delta"],
+            out.ctypes.data_as(ctypes.c_void_p)))
+        return out
 
     def transit_mask(self, t, period, T0, duration, curve=None, n_curves=None, factor=1.5):
         """The in-transit flags uint8 [n_curves, n] (1 = protected) of the candidates (curve[k], period[k], T0[k], duration[k]

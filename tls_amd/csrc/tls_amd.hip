@@ -278,6 +278,9 @@ struct tls_ctx {
     DevBuf<double> d_vetting;
     // tls_shape_fit: of one slab: pairs | y | dy | records | period | T0 | duration | slot; t | ratio | ingress | shift | scratch
     DevBuf<double> d_shape;
+    // tls_transit_fit: of one slab: pairs | y | dy | records | period | T0 | duration | slot | row_first; t | k_rows | profile |
+    // impact | ratio | shift | sub | scratch
+    DevBuf<double> d_transit;
     // tls_centroid_test: of one slab: y | cx | cy | records | period | T0 | duration | slot; t | shape | scratch
     DevBuf<double> d_centroid;
     // tls_folded_views: of one slab: y | records | period | T0 | duration | secondary | global and local medians | slot | global
@@ -1984,6 +1987,7 @@ void tls_ctx_destroy(tls_ctx* ctx) {
     ctx->d_times.release();
     ctx->d_vetting.release();
     ctx->d_shape.release();
+    ctx->d_transit.release();
     ctx->d_centroid.release();
     ctx->d_views.release();
     ctx->d_gls.release();
@@ -3101,6 +3105,7 @@ int tls_debug_poison_lds(tls_ctx* ctx, uint32_t word) {
     TLS_HIP(ctx, smear(ctx->d_times));
     TLS_HIP(ctx, smear(ctx->d_vetting));
     TLS_HIP(ctx, smear(ctx->d_shape));
+    TLS_HIP(ctx, smear(ctx->d_transit));
     TLS_HIP(ctx, smear(ctx->d_centroid));
     TLS_HIP(ctx, smear(ctx->d_views));
     TLS_HIP(ctx, smear(ctx->d_gls));
@@ -3381,6 +3386,7 @@ int tls_debug_device_bytes(const tls_ctx* ctx, int64_t* total, int64_t* t0_fit_s
     add(ctx->d_times);
     add(ctx->d_vetting);
     add(ctx->d_shape);
+    add(ctx->d_transit);
     add(ctx->d_centroid);
     add(ctx->d_views);
     add(ctx->d_gls);
@@ -4170,6 +4176,123 @@ int tls_shape_fit(tls_ctx* ctx, const double* t, const double* y, const double* 
         },
         [&](const SlabView& s) {
             TLS_HIP(ctx, hipMemcpyAsync(out + s.f0, d_out, s.fits * words * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+            return TLS_OK;
+        });
+}
+
+// ---- the limb-darkened transit fit (tls_transit_fit.hip.h, DESIGN.md "Transit fit"): the pairs kernel of the transit times
+// over the curves a slab of candidates reads, then one workgroup a candidate, slab by slab
+static_assert(sizeof(tls_transit_fit_record) == tlsdev::kTransitWords * 8, "tls_transit_fit_record is the kernel's record");
+static_assert(TLS_TRANSIT_FIT_MAX_UNITS == tlsdev::kTransitMaxUnits && TLS_TRANSIT_FIT_MAX_M == tlsdev::kTransitMaxM
+              && TLS_TRANSIT_FIT_MAX_SUB == tlsdev::kTransitMaxSub && TLS_TRANSIT_FIT_MAX_ROWS == tlsdev::kTransitMaxRows,
+              "the header's limits");
+
+int tls_transit_fit(tls_ctx* ctx, const double* t, const double* y, const double* dy, int64_t n, int64_t n_curves,
+                    const int64_t* curve, const double* period, const double* T0, const double* duration,
+                    const int64_t* row_first, int64_t n_fits, const double* k_rows, const double* profile, int64_t n_k,
+                    int64_t M, const double* impact, int64_t n_b, const double* ratio, int64_t n_t, const double* shift,
+                    int64_t n_s, const double* sub, int64_t n_sub, double window, int64_t min_count, double delta,
+                    tls_transit_fit_record* out_records) {
+    if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
+    const std::string what = "transit fit";
+    if (n_fits < 0 || n_curves < 0 || n < 0) return fail(ctx, TLS_E_ARG, what + ": negative count");
+    if (n_k < 1 || n_b < 1 || n_t < 1 || n_s < 1) return fail(ctx, TLS_E_ARG, what + ": every table needs an entry");
+    if (n_k > TLS_TRANSIT_FIT_MAX_ROWS) return fail(ctx, TLS_E_ARG, what + ": more than 4096 profile rows");
+    if (M < 1 || M > TLS_TRANSIT_FIT_MAX_M) return fail(ctx, TLS_E_ARG, what + ": M out of range [1, 4096]");
+    if (n_sub < 1 || n_sub > TLS_TRANSIT_FIT_MAX_SUB) return fail(ctx, TLS_E_ARG, what + ": n_sub out of range [1, 16]");
+    if (n_b > TLS_TRANSIT_FIT_MAX_UNITS || n_t > TLS_TRANSIT_FIT_MAX_UNITS || n_s > TLS_TRANSIT_FIT_MAX_UNITS
+        || n_b * n_t * n_s > TLS_TRANSIT_FIT_MAX_UNITS)
+        return fail(ctx, TLS_E_ARG, what + ": more than 65536 units");
+    if (!k_rows || !profile || !impact || !ratio || !shift || !sub) return fail(ctx, TLS_E_ARG, what + ": null argument");
+    for (const auto& table : {std::make_pair(k_rows, n_k), std::make_pair(impact, n_b), std::make_pair(ratio, n_t), std::make_pair(shift, n_s)})
+        for (int64_t i = 0; i < table.second; ++i)
+            if (!std::isfinite(table.first[i]) || (i > 0 && table.first[i] < table.first[i - 1]))
+                return fail(ctx, TLS_E_ARG, what + ": the tables must be finite and non-decreasing");
+    if (!(k_rows[0] > 0.0)) return fail(ctx, TLS_E_ARG, what + ": every k_rows must be > 0");
+    if (!(impact[0] >= 0.0 && impact[n_b - 1] < 1.0)) return fail(ctx, TLS_E_ARG, what + ": every impact must be in [0, 1)");
+    if (!(ratio[0] > 0.0)) return fail(ctx, TLS_E_ARG, what + ": every ratio must be > 0");
+    double sub_reach = 0.0;
+    for (int64_t s = 0; s < n_sub; ++s) {
+        if (!std::isfinite(sub[s])) return fail(ctx, TLS_E_ARG, what + ": sub must be finite");
+        sub_reach = std::max(sub_reach, std::fabs(sub[s]));
+    }
+    for (int64_t i = 0; i < n_k * (M + 1); ++i)
+        if (!std::isfinite(profile[i])) return fail(ctx, TLS_E_ARG, what + ": the profile must be finite");
+    const double reach = 0.5 * ratio[n_t - 1] + std::max(std::fabs(shift[0]), std::fabs(shift[n_s - 1]));
+    if (!(std::isfinite(window) && window >= reach))
+        return fail(ctx, TLS_E_ARG, what + ": the window must be finite and hold the widest, farthest shifted model");
+    if (min_count < 1) return fail(ctx, TLS_E_ARG, what + ": min_count < 1");
+    if (!(std::isfinite(delta) && delta >= 0.0)) return fail(ctx, TLS_E_ARG, what + ": delta must be finite and >= 0");
+    if (n_fits == 0) return TLS_OK;
+    if (!t || !y || !dy || !period || !T0 || !duration || !row_first || !out_records) return fail(ctx, TLS_E_ARG, what + ": null argument");
+    int rc;
+    if ((rc = check_batch(ctx, what, n, tlsdev::kShapeMaxPoints, "[1, 2^22]", n_fits, n_curves))
+        || (rc = check_time_stamps(ctx, what, t, n))
+        || (rc = check_curves(ctx, what, curve, n_fits, n_curves, [&](int64_t f) {
+               if (row_first[f] < 0 || row_first[f] >= n_k) return fail(ctx, TLS_E_ARG, what + ": row_first out of range [0, n_k)");
+               const double d = duration[f];
+               if (std::isfinite(d) && d > 0.0 && !(window * d >= reach * d + sub_reach))
+                   return fail(ctx, TLS_E_ARG, what + ": the window of candidate " + std::to_string(f)
+                                                   + " does not hold the widest, farthest shifted model plus half an exposure");
+               return (int)TLS_OK;
+           })))
+        return rc;
+    TLS_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t nn = (size_t)n, words = tlsdev::kTransitWords, units = (size_t)(n_b * n_t * n_s);
+    const size_t rows = (size_t)n_k, row_words = (size_t)M + 1, tables = rows + rows * row_words + (size_t)(n_b + n_t + n_s + n_sub);
+    // a slab: at most 512 candidates on at most 512 curves, 256 MB of curves (32 bytes a point); the workgroups of a launch:
+    // at most 512, 256 MB of scratch (24 bytes a point and 16 bytes a unit each)
+    const size_t budget = 256u << 20, stretch = 3 * nn + 2 * units;
+    const size_t cs = std::max<size_t>(1, std::min<size_t>({(size_t)n_curves, (size_t)tlsdev::kTransitSlab, budget / (32 * nn)}));
+    const size_t sl = std::min<size_t>((size_t)n_fits, (size_t)tlsdev::kTransitSlab);
+    const size_t groups = std::max<size_t>(1, std::min<size_t>(sl, budget / (8 * stretch)));
+    // of one slab: pairs | y | dy | records | period | T0 | duration | slot, row_first;  t | the tables | scratch
+    TLS_HIP(ctx, ctx->d_transit.reserve(4 * cs * nn + sl * (words + 3) + sl + nn + tables + groups * stretch));
+    double2* d_pairs = reinterpret_cast<double2*>(ctx->d_transit.ptr);         // (the allocation's start: 16-byte aligned)
+    double* d_y = ctx->d_transit.ptr + 2 * cs * nn;
+    double* d_dy = d_y + cs * nn;
+    double* d_out = d_dy + cs * nn;
+    double* d_period = d_out + sl * words;
+    double* d_T0 = d_period + sl;
+    double* d_duration = d_T0 + sl;
+    int* d_ints = reinterpret_cast<int*>(d_duration + sl);                     // slot [sl] | row_first [sl]
+    double* d_t = d_duration + sl + sl;
+    double* d_k = d_t + nn;
+    double* d_profile = d_k + rows;
+    double* d_impact = d_profile + rows * row_words;
+    double* d_ratio = d_impact + n_b;
+    double* d_shift = d_ratio + n_t;
+    double* d_sub = d_shift + n_s;
+    double* d_scratch = d_sub + n_sub;
+    if ((rc = ensure_check_counters(ctx))) return rc;
+    tlsdev::TimesPairsArgs p;
+    p.y = d_y; p.dy = d_dy; p.pairs = d_pairs;
+    tlsdev::TransitFitArgs a;
+    a.t = d_t; a.pairs = d_pairs; a.slot = d_ints; a.row_first = d_ints + sl; a.period = d_period; a.T0 = d_T0; a.duration = d_duration;
+    a.k_rows = d_k; a.profile = d_profile; a.impact = d_impact; a.ratio = d_ratio; a.shift = d_shift; a.sub = d_sub;
+    a.scratch = d_scratch; a.out = d_out; a.check = ctx->d_check.ptr; a.window = window; a.delta = delta;
+    a.n = (int)n; a.nK = (int)n_k; a.M = (int)M; a.nB = (int)n_b; a.nT = (int)n_t; a.nS = (int)n_s; a.S = (int)n_sub;
+    a.min_count = (int)std::min<int64_t>(min_count, INT32_MAX);
+    const size_t lds = row_words * 8;
+    TLS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(tlsdev::tls_transit_fit_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_k, k_rows, rows * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_profile, profile, rows * row_words * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_impact, impact, (size_t)n_b * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_ratio, ratio, (size_t)n_t * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_shift, shift, (size_t)n_s * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_sub, sub, (size_t)n_sub * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    const SlabStage stage{"transit fit", "tls_transit_fit", curve, n_fits, nn, cs, sl,
+                          {{d_y, y}, {d_dy, dy}}, {{d_period, period}, {d_T0, T0}, {d_duration, duration}}, d_ints, 2};
+    return run_candidate_slabs(ctx, stage,
+        [&](int64_t f, int* at) { at[sl] = (int)row_first[f]; return (size_t)0; },
+        [&](const SlabView& s) {
+            a.fits = (int)s.fits;
+            if (launch_times_pairs(ctx, p, s.curves, nn))
+                hipLaunchKernelGGL(tlsdev::tls_transit_fit_kernel, dim3((unsigned)std::min(s.fits, groups)), dim3(tlsdev::kShapeThreads), lds, main_stream(ctx), a);
+        },
+        [&](const SlabView& s) {
+            TLS_HIP(ctx, hipMemcpyAsync(out_records + s.f0, d_out, s.fits * words * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
             return TLS_OK;
         });
 }

@@ -530,7 +530,7 @@ def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_ar
                 event_vetting_search=1.0, event_vetting_chase_window=0.1, event_vetting_guard=1.5, event_vetting_min_ses=3.0,
                 event_vetting_chase_fraction=0.6, event_vetting_chase_min=0.5, event_vetting_point_fraction=0.5,
                 event_vetting_step_fraction=0.5, centroids=None, centroid_window=3.0, centroid_min_in=1,
-                centroid_min_out=3, noise=None, detrend_mask=None, **power_kwargs):
+                centroid_min_out=3, noise=None, detrend_mask=None, transit_fit=False, **power_kwargs):
     """Survey-mode power(): for every light curve of `flux_batch` what `transitleastsquares(t, flux).power(**kwargs)`
     reports as SDE, SDE_raw, chi2_min, period, T0, depth and duration (fractional, lc_cache_overview["duration"] of
     the template row at the chi^2 minimum, main.py:199-200) -- search, SDE spectra and final T0 fit all on the
@@ -677,6 +677,16 @@ def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_ar
     host; NaN, and noise_width -1, where status != 0 or noise_sigma is NaN.  Everything else of the result stays as it is,
     bit for bit.  noise without peak_fits, or with bad widths, raises ValueError before any device work.
 
+    transit_fit=True (with peak_fits=True), or transit_fit=dict(...) with keywords of transit_fit below (impacts, ratios,
+    shifts, exposure, n_sub, window, min_count, delta, profile), fits a limb-darkened, exposure-integrated transit to every
+    fitted peak -- planet size, impact parameter, T14 and their profile-likelihood ranges (transit_fit below states it) -- in
+    one call of tls_transit_fit behind the search, on the device that searched the curve and on the rows it searched, from
+    the period and depth of the peak and T0 and duration_days of its fit record, with the search's u / limb_dark.  The `peaks`
+    array gains, behind every other group, the fields transit_fit_fields() (fit_status 1 and the others NaN where
+    status != 0, and where the peak's duration is too short for the window to hold the widest, farthest shifted model plus
+    half an exposure: pass transit_fit=dict(window=1.5) for short peaks).  Everything else of the result stays as it is, bit
+    for bit.  transit_fit without peak_fits, or with a bad table or window, raises ValueError before any device work.
+
     Returns (summary, periods[, chi2, row, depth, power][, per_transit][, models][, peaks]): summary is a numpy structured
     array with the fields of tls_power_summary plus "duration" (and the statistics on request)."""
     return _power_batch(t, flux_batch, dy_batch, power_kwargs, context=context, device=device, devices=devices,
@@ -700,7 +710,8 @@ def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_ar
                                                              event_vetting_step_fraction),
                         centroids=_centroid_request(centroids, peak_fits, numpy.shape(flux_batch), centroid_window,
                                                     centroid_min_in, centroid_min_out),
-                        noise=_noise_request(noise, peak_fits, t))
+                        noise=_noise_request(noise, peak_fits, t),
+                        transit_fit=_transit_fit_request(transit_fit, peak_fits, t, power_kwargs))
 
 
 def _peaks_request(peaks, separation, ratios, min_power, models=False, peak_fits=False):
@@ -861,7 +872,7 @@ def find_peaks(power, periods, k, separation=0.02, ratios=HARMONICS, min_power=N
 def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=None, devices=None, with_arrays=False,
                  statistics=False, per_transit=False, models=False, spectra=False, detrend=None, peaks=None,
                  peak_fits=False, phase_scan=None, transit_times=None, shape_fit=None, sine_test=None, ephemeris_match=None,
-                 views=None, event_vetting=None, centroids=None, noise=None, detrend_mask=None):
+                 views=None, event_vetting=None, centroids=None, noise=None, detrend_mask=None, transit_fit=None):
     """power_batch; spectra=True (power_results) also returns SR and power_raw [n_curves, n_periods] behind the arrays;
     peaks: None or a checked request (_peaks_request); peak_fits: with peaks, their T0 fits and statistics; phase_scan: None or a checked
     request (_phase_scan_request), with peak_fits, the fits' phase scans; transit_times: None or a checked request
@@ -871,7 +882,8 @@ def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=Non
     peak_fits, the match of the fitted peaks across the curves; views: None or a checked request (_views_request), with
     peak_fits, the fits' folded views; event_vetting: None or a checked request (_event_vetting_request), with peak_fits, the
     fits' event vetting; centroids: None or a checked request (_centroid_request), with peak_fits, the fits' centroid tests;
-    noise: None or a checked request (_noise_request), with peak_fits, the curves' noise profiles."""
+    noise: None or a checked request (_noise_request), with peak_fits, the curves' noise profiles; transit_fit: None or a
+    checked request (_transit_fit_request), with peak_fits, the fits' limb-darkened transit fits."""
     models = bool(models)
     per_transit = bool(per_transit or models)
     statistics = bool(statistics or per_transit)
@@ -935,6 +947,9 @@ def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=Non
             part["noise_curves"], part["noise_count"], part["noise_robust"], part["noise_rms"] = ctx.noise_profile(
                 inp["t"], y_rows[lo:hi], noise["widths"], noise["span_max"], noise["pair_span"], NOISE_CLIP, NOISE_CLIP,
                 NOISE_MIN_COUNT)
+        if transit_fit is not None:
+            part["transit_fits"] = _peak_transit_fits(ctx, inp, y_rows[lo:hi], dy_rows[lo:hi], part["peaks"],
+                                                      part["peak_fits"], transit_fit)
         return part
 
     out = _run_batch(devices, device, context, len(y_rows), call)
@@ -1018,6 +1033,9 @@ def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=Non
                                   robust=out["noise_robust"], rms=out["noise_rms"],
                                   beta=_noise_beta(out["noise_robust"], noise["widths"], out["noise_curves"]["sigma"]))
             found["peaks"] = _with_noise(found["peaks"], found["noise"], noise["cadence"])
+        if transit_fit is not None:
+            found["peaks"] = _with_transit_fits(found["peaks"], out["transit_fits"], found["peaks"]["period"],
+                                                found["peaks"]["T0"])
         result += (found,)
     if spectra:
         result += (out["SR"], out["power_raw"])
@@ -1833,6 +1851,244 @@ def shape_fit(t, flux_batch, period, T0, duration, curve=None, dy_batch=None, ra
     out = ctx.shape_fit(inp["t"], y_rows, dy_rows, period, T0, duration, ratio, ingress, shift, curve=curve, window=window,
                         min_count=min_count, depth_min=depth_min)
     return _with_shapes(None, out, period)
+
+
+# ---- limb-darkened transit fit -------------------------------------------------------------------------------------------------
+TRANSIT_FIT_K_ROWS = numpy.geomspace(0.01, 0.5, 81)
+TRANSIT_FIT_IMPACTS = numpy.linspace(0.0, 0.96, 13)
+TRANSIT_FIT_RATIOS = numpy.geomspace(0.7, 1.4, 29)
+TRANSIT_FIT_SHIFTS = numpy.linspace(-0.1, 0.1, 9)
+
+
+def transit_profile(k_rows=None, M=1024, **template_kwargs):
+    """(k_rows, profile): the table tls_transit_fit reads its dips from.  Row j is the dip of a planet of k_rows[j] stellar
+    radii over a star of the template's limb darkening -- u and limb_dark as power() takes them (transit_template="box"
+    included), the other template keywords are not used -- at M + 1 separations from the centre to the contact:
+    profile[j][m] = 1 - F((1 + k_rows[j]) m / M; k_rows[j]) and profile[j][M] = 0, F being transit_model.quadratic_ld_flux for
+    the quadratic, linear and uniform laws and transit_model.numerical_ld_flux for the others.  Default rows:
+    numpy.geomspace(0.01, 0.5, 81).  Formed on the host, so the device stage is the same for every law."""
+    import warnings
+    from . import transit_model, validate
+    from ._lib import TRANSIT_FIT_MAX_M
+    k_rows = numpy.array(TRANSIT_FIT_K_ROWS if k_rows is None else k_rows, dtype=numpy.float64)
+    if k_rows.ndim != 1 or len(k_rows) < 1 or not numpy.all(numpy.isfinite(k_rows)) or not k_rows[0] > 0.0 \
+            or not numpy.all(k_rows[1:] >= k_rows[:-1]):
+        raise ValueError("transit fit: k_rows must be a finite, ascending table of values > 0")
+    if isinstance(M, (bool, numpy.bool_)) or not isinstance(M, numbers.Integral) or not 1 <= int(M) <= TRANSIT_FIT_MAX_M:
+        raise ValueError("transit fit: M must be an integer in [1, %d], got %r" % (TRANSIT_FIT_MAX_M, M))
+    M = int(M)
+
+    class _Template(object):
+        pass
+
+    chosen = _Template()
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        validate.validate_args(chosen, dict(template_kwargs, verbose=False))
+    law = chosen.limb_dark
+    u = [float(v) for v in numpy.atleast_1d(chosen.u)] if chosen.u is not None else []
+    profile = numpy.zeros((len(k_rows), M + 1))
+    grid = numpy.arange(M + 1) / float(M)
+    for j, k in enumerate(k_rows.tolist()):
+        z = (1.0 + k) * grid
+        if law == "quadratic":
+            flux = transit_model.quadratic_ld_flux(z, k, u[0], u[1])
+        elif law == "linear":
+            flux = transit_model.quadratic_ld_flux(z, k, u[0], 0.0)
+        elif law == "uniform":
+            flux = transit_model.quadratic_ld_flux(z, k, 0.0, 0.0)
+        else:
+            flux = transit_model.numerical_ld_flux(z, k, law, u)
+        profile[j] = 1.0 - flux
+        profile[j, M] = 0.0
+    if not numpy.all(numpy.isfinite(profile)):
+        raise ValueError("transit fit: the profile of %r with u = %r is not finite" % (law, u))
+    return k_rows, profile
+
+
+def transit_fit_fields():
+    """The fields of a transit fit, in order -- what transit_fit returns and power_batch(..., transit_fit=True) adds to the
+    `peaks` array: the fields of tls_transit_fit_record, each behind the prefix fit_ (fit_status first), then the host-formed
+    fit_T0 = T0 + fit_shift and the geometry of the fit (transit_fit_geometry): fit_a_rs, fit_inc, fit_rho_star."""
+    from ._lib import TRANSIT_FIT_FIELDS
+    return tuple("fit_" + k for k in TRANSIT_FIT_FIELDS) + ("fit_T0", "fit_a_rs", "fit_inc", "fit_rho_star")
+
+
+def transit_fit_geometry(period, k, b, T14):
+    """(a_rs, inc, rho_star) of a planet of k stellar radii crossing at impact parameter b in T14 days (first to last
+    contact) on a circular orbit of `period` days, by the exact contact formula sin(pi T14 / P) = sqrt((1 + k)^2 - b^2) /
+    (a_rs sin i) with b = a_rs cos i (Seager & Mallen-Ornelas 2003, equation 3):
+
+        sT = sin^2(pi T14 / P);  a_rs = sqrt(b^2 + ((1 + k)^2 - b^2) / sT);  inc = arccos(b / a_rs) in degrees
+        rho_star = 3 pi a_rs^3 / (G P^2), in units of the solar mean density
+
+    Plain numpy on the host, broadcasting.  NaN where an input is not finite, (1 + k)^2 <= b^2, or T14 is not in (0, P / 2]."""
+    from . import constants as C
+    period, k, b, T14 = numpy.broadcast_arrays(*(numpy.asarray(v, dtype=numpy.float64) for v in (period, k, b, T14)))
+    with numpy.errstate(all="ignore"):
+        sT = numpy.sin(numpy.pi * T14 / period) ** 2
+        chord2 = (1.0 + k) ** 2 - b * b
+        a_rs = numpy.sqrt(b * b + chord2 / sT)
+        inc = numpy.degrees(numpy.arccos(b / a_rs))
+        rho_sun = C.M_sun / (4.0 / 3.0 * numpy.pi * float(C.R_sun) ** 3)
+        rho = 3.0 * numpy.pi * a_rs ** 3 / (C.G * (period * C.SECONDS_PER_DAY) ** 2) / rho_sun
+        good = numpy.isfinite(period) & numpy.isfinite(k) & numpy.isfinite(b) & numpy.isfinite(T14) & (chord2 > 0.0) \
+            & (T14 > 0.0) & (T14 <= 0.5 * period) & (b >= 0.0) & numpy.isfinite(a_rs)
+    return numpy.where(good, a_rs, numpy.nan), numpy.where(good, inc, numpy.nan), numpy.where(good, rho, numpy.nan)
+
+
+def _transit_fit_setup(t, impacts, ratios, shifts, exposure, n_sub, window, min_count, delta, profile, template_kwargs):
+    """The checked tables of a transit fit: a dict with k_rows, profile, impact, ratio, shift, sub, window, min_count, delta.
+    exposure None: the median cadence of t; 0: no smearing."""
+    from ._lib import TRANSIT_FIT_MAX_SUB, transit_fit_tables
+    if isinstance(n_sub, (bool, numpy.bool_)) or not isinstance(n_sub, numbers.Integral) or not 1 <= int(n_sub) <= TRANSIT_FIT_MAX_SUB:
+        raise ValueError("transit fit: n_sub must be an integer in [1, %d], got %r" % (TRANSIT_FIT_MAX_SUB, n_sub))
+    if exposure is None:
+        t = numpy.asarray(t, dtype=numpy.float64)
+        exposure = float(numpy.median(numpy.diff(t))) if t.ndim == 1 and len(t) > 1 else 0.0
+    if isinstance(exposure, (bool, numpy.bool_)) or not isinstance(exposure, numbers.Real) or not (0.0 <= float(exposure) < numpy.inf):
+        raise ValueError("transit fit: exposure must be finite and >= 0 (days), got %r" % (exposure,))
+    S = int(n_sub) if float(exposure) > 0.0 else 1
+    sub = float(exposure) * ((2.0 * numpy.arange(S) + 1.0) / (2.0 * S) - 0.5) if S > 1 else numpy.zeros(1)
+    if profile is None:
+        profile = transit_profile(**template_kwargs)
+    try:
+        k_rows, table = profile
+    except (TypeError, ValueError):
+        raise ValueError("transit fit: profile must be the pair (k_rows, profile) of transit_profile")
+    names = ("k_rows", "profile", "impact", "ratio", "shift", "sub", "window", "min_count", "delta")
+    return dict(zip(names, transit_fit_tables(
+        k_rows, table, TRANSIT_FIT_IMPACTS if impacts is None else impacts, TRANSIT_FIT_RATIOS if ratios is None else ratios,
+        TRANSIT_FIT_SHIFTS if shifts is None else shifts, sub, window, min_count, delta)))
+
+
+def _seed_rows(k_rows, depth):
+    """The row of k_rows nearest sqrt(depth), the lowest on ties; row 0 where the depth is not a finite number >= 0."""
+    depth = numpy.asarray(depth, dtype=numpy.float64)
+    with numpy.errstate(all="ignore"):
+        k0 = numpy.sqrt(numpy.where(numpy.isfinite(depth) & (depth >= 0.0), depth, 0.0))
+    return numpy.argmin(numpy.fabs(k_rows[None, :] - k0.reshape(-1, 1)), axis=1).astype(numpy.int64).reshape(depth.shape)
+
+
+def _with_transit_fits(records, fits, period, T0):
+    """`records` (None, or the peaks with their fits) plus the device's transit-fit records, fit_T0 and the geometry."""
+    names = transit_fit_fields()
+    base = [] if records is None else records.dtype.descr
+    out = numpy.zeros(fits.shape, dtype=base + [(k, "f8") for k in names])
+    if records is not None:
+        for k in records.dtype.names:
+            out[k] = records[k]
+    for k, source in zip(names, fits.dtype.names):
+        out[k] = fits[source]
+    out["fit_T0"] = numpy.asarray(T0, dtype=numpy.float64) + fits["shift"]
+    out["fit_a_rs"], out["fit_inc"], out["fit_rho_star"] = transit_fit_geometry(period, fits["k"], fits["b"], fits["duration"])
+    return out
+
+
+def _transit_fit_request(transit_fit, peak_fits, t, power_kwargs):
+    """None, or the checked tables (_transit_fit_setup) of a transit_fit=True / transit_fit=dict request -- the dict holds
+    keywords of survey.transit_fit: impacts, ratios, shifts, exposure, n_sub, window, min_count, delta, profile (ValueError
+    for a bad one, for an unknown key, and for transit_fit without peak_fits)."""
+    if transit_fit is None or transit_fit is False:
+        return None
+    if not peak_fits:
+        raise ValueError("transit_fit needs peak_fits=True: the fits start from T0 and duration of the fits")
+    options = {} if transit_fit is True else transit_fit
+    known = ("impacts", "ratios", "shifts", "exposure", "n_sub", "window", "min_count", "delta", "profile")
+    if not isinstance(options, dict) or any(k not in known for k in options):
+        raise ValueError("transit_fit must be True or a dict with keys among %s" % (known,))
+    o = dict(dict(impacts=None, ratios=None, shifts=None, exposure=None, n_sub=5, window=1.0, min_count=3, delta=1.0,
+                  profile=None), **options)
+    template = {k: power_kwargs[k] for k in ("u", "limb_dark", "transit_template") if k in power_kwargs}
+    return _transit_fit_setup(t, o["impacts"], o["ratios"], o["shifts"], o["exposure"], o["n_sub"], o["window"],
+                              o["min_count"], o["delta"], o["profile"], template)
+
+
+def _peak_transit_fits(ctx, inp, y_rows, dy_rows, peaks, fits, request):
+    """The transit-fit records [n_curves, K] of the peaks of a slice of the batch, on ctx.  Every peak is a candidate: one
+    whose fit status is not 0 goes in as (NaN, NaN, NaN) and comes back as the statement has it, status 1 -- and so does a
+    peak whose duration is too short for the window to hold the widest, farthest shifted model plus half an exposure (the
+    entry refuses such a candidate, and the durations are known only behind the search)."""
+    n_curves, k = fits.shape
+    fitted = (fits["status"] == 0).reshape(-1)
+    reach = 0.5 * float(request["ratio"][-1]) + max(abs(float(request["shift"][0])), abs(float(request["shift"][-1])))
+    with numpy.errstate(all="ignore"):
+        d = fits["duration_days"].reshape(-1)
+        fitted = fitted & (request["window"] * d >= reach * d + float(numpy.max(numpy.fabs(request["sub"]))))
+    period = numpy.where(fitted, peaks["period"].reshape(-1), numpy.nan)
+    T0 = numpy.where(fitted, fits["T0"].reshape(-1), numpy.nan)
+    duration = numpy.where(fitted, fits["duration_days"].reshape(-1), numpy.nan)
+    rows = _seed_rows(request["k_rows"], numpy.where(fitted, 1.0 - peaks["depth"].reshape(-1), numpy.nan))
+    out = ctx.transit_fit(inp["t"], y_rows, dy_rows, period, T0, duration, rows, request["k_rows"], request["profile"],
+                          request["impact"], request["ratio"], request["shift"], request["sub"],
+                          curve=numpy.repeat(numpy.arange(n_curves), k), window=request["window"],
+                          min_count=request["min_count"], delta=request["delta"])
+    return out.reshape(n_curves, k)
+
+
+def transit_fit(t, flux_batch, period, T0, duration, depth, curve=None, dy_batch=None, impacts=None, ratios=None, shifts=None,
+                exposure=None, n_sub=5, window=1.0, min_count=3, delta=1.0, profile=None, detrend=None, context=None,
+                device=None, **template_kwargs):
+    """The limb-darkened transit fit of candidates the caller holds, on the device (tls_transit_fit): candidate f is
+    (period[f], T0[f], duration[f] in days, depth[f]) on light curve curve[f] of flux_batch [n_curves, n] (or one row [n])
+    over the ascending time stamps t; curve=None takes one candidate a curve, in order.  It needs no search.  The search gives
+    rp_rs from the depth alone, and the trapezoid of shape_fit knows nothing of limb darkening or of the exposure time.  Here
+    the model is a planet of radius k crossing a limb-darkened star on a straight chord at constant speed, the separation
+    z^2 = b^2 + ((1 + k)^2 - b^2) v^2 with v = (time from mid-transit) / (T14 / 2), averaged over n_sub sub-exposures of
+    `exposure` days (None: the median cadence of t; 0: no smearing).  Its dip comes from a table the host forms once
+    (transit_profile: any law power() takes, from u / limb_dark / transit_template in template_kwargs, or profile=(k_rows,
+    profile)); the depth amplitude A is free and the baseline fixed at 1, as everywhere in TLS.  The grid is b / (1 + k) =
+    impacts, T14 = duration * ratios and the centre T0 + duration * shifts (defaults: numpy.linspace(0, 0.96, 13),
+    numpy.geomspace(0.7, 1.4, 29), numpy.linspace(-0.1, 0.1, 9): 3393 units), searched twice: with the profile row nearest
+    sqrt(depth), then with the row nearest k of the first pass.  The row only shapes ingress and egress; the size is carried
+    by A: k = k_rows[row] * sqrt(A).  The statement is in tests/transit_fit_spec.py and include/tls_amd.h, and the device
+    equals it bit for bit.
+
+    fit_k_lo .. fit_shift_hi are the least and the largest value over the units whose chi^2 lies within `delta` of the best:
+    a profile-likelihood range, the honest answer where b, k and T14 are degenerate (at 30-minute cadence they are).  The
+    straight chord differs from the circular orbit by about (pi T14 / P)^2 / 6 of the duration.
+
+    The tables must be finite and ascending, impacts in [0, 1), ratios > 0, at most 65536 units; n_sub in [1, 16]; window
+    finite, at least 0.5 * max(ratios) + max|shifts|, and for every candidate with a duration wide enough to hold the widest,
+    farthest shifted model plus half an exposure; min_count >= 1; delta finite and >= 0; period, T0, duration, depth and
+    curve [n_fits] with curve in [0, n_curves): ValueError otherwise, before any device work (the detrending included).
+    detrend= takes the steps and tuples of search_batch.
+
+    Returns a structured array [n_fits] with the fields transit_fit_fields(): fit_status (0 fitted; 1 no such candidate; 2 no
+    valid unit), fit_n_points, fit_n_in, fit_row_first, fit_row, fit_ses, fit_amplitude, fit_k (rp / R*), fit_b,
+    fit_duration (T14, days), fit_shift (days), fit_i_impact, fit_i_duration, fit_i_shift, fit_x2, the eight interval ends,
+    fit_reserved, and fit_T0 = T0 + fit_shift, fit_a_rs, fit_inc (degrees), fit_rho_star (solar): transit_fit_geometry of the
+    fit (NaN where it has none)."""
+    from ._lib import shape_fit_candidates, transit_fit_window_holds
+    setup = _transit_fit_setup(t, impacts, ratios, shifts, exposure, n_sub, window, min_count, delta, profile, template_kwargs)
+    t = numpy.asarray(t, dtype=numpy.float64)
+    if numpy.ndim(flux_batch) == 1:
+        flux_batch = numpy.asarray(flux_batch)[None, :]
+        dy_batch = None if dy_batch is None else numpy.asarray(dy_batch)[None, :]
+    if numpy.ndim(flux_batch) != 2 or t.ndim != 1 or numpy.shape(flux_batch)[1] != len(t):
+        raise ValueError("flux_batch must be [n] or [n_curves, n] over the time stamps t [n]")
+    if not numpy.all(numpy.isfinite(t)) or not numpy.all(t[1:] >= t[:-1]):
+        raise ValueError("transit fit: t must be finite and non-decreasing")
+    try:
+        period, T0, duration, curve = shape_fit_candidates(period, T0, duration, curve, numpy.shape(flux_batch)[0])
+        depth = numpy.ascontiguousarray(numpy.atleast_1d(numpy.asarray(depth, dtype=numpy.float64)))
+    except (TypeError, ValueError) as e:
+        raise ValueError(str(e).replace("shape fit:", "transit fit:"))
+    if depth.shape != period.shape:
+        raise ValueError("transit fit: depth must hold one value a candidate")
+    if not transit_fit_window_holds(duration, setup["ratio"], setup["shift"], setup["sub"], setup["window"]):
+        raise ValueError("transit fit: window %r does not hold the widest, farthest shifted model plus half an exposure for "
+                         "the shortest duration" % (setup["window"],))
+    rows = _seed_rows(setup["k_rows"], depth)
+    flux_batch = _detrended(t, flux_batch, detrend, context, device, None, dy_batch)
+    kwargs = dict(template_kwargs)
+    kwargs.setdefault("oversampling_factor", 1)      # (the period grid of the plan inputs is not used: the coarsest will do)
+    inp, y_rows, dy_rows = _batch_inputs(t, flux_batch, dy_batch, kwargs)
+    ctx = context if context is not None else _search.default_context(device)
+    out = ctx.transit_fit(inp["t"], y_rows, dy_rows, period, T0, duration, rows, setup["k_rows"], setup["profile"],
+                          setup["impact"], setup["ratio"], setup["shift"], setup["sub"], curve=curve, window=setup["window"],
+                          min_count=setup["min_count"], delta=setup["delta"])
+    return _with_transit_fits(None, out, period, T0)
 
 
 # ---- centroid-shift test ------------------------------------------------------------------------------------------------------
