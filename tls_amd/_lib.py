@@ -669,26 +669,26 @@ def shape_fit_tables(ratios, ingress, shifts, window=2.0, min_count=3, depth_min
     return ratio, ingress, shift, float(window), int(min_count), float(depth_min)
 
 
-def shape_fit_candidates(period, T0, duration, curve, n_curves):
+def shape_fit_candidates(period, T0, duration, curve, n_curves, what="shape fit"):
     """(period, T0, duration [n_fits] float64, curve [n_fits] int64) of tls_shape_fit, checked: numbers of one 1-D shape (any
     value: the device gives a candidate without an ephemeris status 1), curve (None: one candidate a curve, in order) integers
-    in [0, n_curves).  ValueError otherwise."""
+    in [0, n_curves).  ValueError otherwise, headed `what`."""
     try:
         period, T0, duration = (numpy.ascontiguousarray(numpy.atleast_1d(numpy.asarray(v, dtype=numpy.float64)))
                                 for v in (period, T0, duration))
     except (TypeError, ValueError):
-        raise ValueError("shape fit: period, T0 and duration must be numbers")
+        raise ValueError("%s: period, T0 and duration must be numbers" % what)
     if period.ndim != 1 or not period.shape == T0.shape == duration.shape:
-        raise ValueError("shape fit: period, T0 and duration must be [n_fits]")
+        raise ValueError("%s: period, T0 and duration must be [n_fits]" % what)
     if curve is None:
         if len(period) != n_curves:
-            raise ValueError("shape fit: curve=None takes one candidate a light curve: %d candidates, %d curves"
-                             % (len(period), n_curves))
+            raise ValueError("%s: curve=None takes one candidate a light curve: %d candidates, %d curves"
+                             % (what, len(period), n_curves))
         curve = numpy.arange(n_curves)
     curve = numpy.atleast_1d(numpy.asarray(curve))
     if curve.shape != period.shape or (curve.size and (curve.dtype.kind not in "iu" or curve.min() < 0
                                                         or curve.max() >= n_curves)):
-        raise ValueError("shape fit: curve must hold one index in [0, %d) a candidate" % n_curves)
+        raise ValueError("%s: curve must hold one index in [0, %d) a candidate" % (what, n_curves))
     return period, T0, duration, numpy.ascontiguousarray(curve, dtype=numpy.int64)
 
 
@@ -896,10 +896,7 @@ def centroid_arguments(t, y, cx, cy, period, T0, duration, shape, curve=None, wi
     if y.size and not numpy.all(numpy.isfinite(y)):
         raise ValueError("centroid test: y has a NaN or an infinite value")
     cx, cy = centroid_rows(cx, cy, y.shape)
-    try:
-        period, T0, duration, curve = shape_fit_candidates(period, T0, duration, curve, len(y))
-    except ValueError as e:
-        raise ValueError(str(e).replace("shape fit", "centroid test"))
+    period, T0, duration, curve = shape_fit_candidates(period, T0, duration, curve, len(y), "centroid test")
     return dict(t=numpy.ascontiguousarray(t), y=numpy.ascontiguousarray(y), cx=cx, cy=cy, period=period, T0=T0,
                 duration=duration, curve=curve, shape=shape, window=window, min_in=min_in, min_out=min_out,
                 max_epochs=max_epochs)
@@ -952,10 +949,7 @@ def folded_views_arguments(t, y, period, T0, duration, curve=None, secondary_pha
         raise ValueError("folded views: y must be [n] or [n_curves, n] over the time stamps t [n]")
     if y.size and not numpy.all(numpy.isfinite(y)):
         raise ValueError("folded views: y has a NaN or an infinite value")
-    try:
-        period, T0, duration, curve = shape_fit_candidates(period, T0, duration, curve, len(y))
-    except ValueError as e:
-        raise ValueError(str(e).replace("shape fit", "folded views"))
+    period, T0, duration, curve = shape_fit_candidates(period, T0, duration, curve, len(y), "folded views")
     if secondary_phase is not None:
         try:
             secondary_phase = numpy.ascontiguousarray(numpy.atleast_1d(numpy.asarray(secondary_phase, dtype=numpy.float64)))

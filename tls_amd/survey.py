@@ -515,6 +515,30 @@ def _detrend_rows(ctx, t, rows, detrend):
     return rows
 
 
+def _candidate_rows(what, t, flux_batch, dy_batch=None):
+    """(t as float64, flux_batch, dy_batch) of a stand-alone candidate entry: one row [n] brought to [1, n]; ValueError
+    unless flux_batch is [n_curves, n] over t [n] and t is finite and non-decreasing (that message headed `what`)."""
+    t = numpy.asarray(t, dtype=numpy.float64)
+    if numpy.ndim(flux_batch) == 1:
+        flux_batch = numpy.asarray(flux_batch)[None, :]
+        dy_batch = None if dy_batch is None else numpy.asarray(dy_batch)[None, :]
+    if numpy.ndim(flux_batch) != 2 or t.ndim != 1 or numpy.shape(flux_batch)[1] != len(t):
+        raise ValueError("flux_batch must be [n] or [n_curves, n] over the time stamps t [n]")
+    if not numpy.all(numpy.isfinite(t)) or not numpy.all(t[1:] >= t[:-1]):
+        raise ValueError("%s: t must be finite and non-decreasing" % what)
+    return t, flux_batch, dy_batch
+
+
+def _candidate_inputs(t, flux_batch, dy_batch, detrend, context, device, template_kwargs):
+    """(inp, y_rows, dy_rows, ctx) of a stand-alone candidate entry, behind its argument checks: the rows detrended on the
+    call's device, the plan inputs a search of them gets (_batch_inputs) and the context."""
+    flux_batch = _detrended(t, flux_batch, detrend, context, device, None, dy_batch)
+    kwargs = dict(template_kwargs)
+    kwargs.setdefault("oversampling_factor", 1)      # (the period grid of the plan inputs is not used: the coarsest will do)
+    inp, y_rows, dy_rows = _batch_inputs(t, flux_batch, dy_batch, kwargs)
+    return inp, y_rows, dy_rows, context if context is not None else _search.default_context(device)
+
+
 # the period ratios whose neighbourhoods a taken peak suppresses by default: its first harmonics and sub-harmonics
 HARMONICS = (0.5, 2.0, 1 / 3, 3.0, 2 / 3, 1.5)
 
@@ -689,29 +713,14 @@ def power_batch(t, flux_batch, dy_batch=None, context=None, device=None, with_ar
 
     Returns (summary, periods[, chi2, row, depth, power][, per_transit][, models][, peaks]): summary is a numpy structured
     array with the fields of tls_power_summary plus "duration" (and the statistics on request)."""
+    given = dict(locals())     # (every argument by its name, for the stages' requests)
+    peaks = _peaks_request(peaks, peak_separation, peak_ratios, peak_min_power, models, peak_fits)
+    phase_scan = _phase_scan_request(phase_scan, peak_fits, phase_scan_max_bins, phase_scan_min_count)
+    stages = {stage.name: stage.request(*(given[k] for k in stage.keywords)) for stage in _PEAK_STAGES}
     return _power_batch(t, flux_batch, dy_batch, power_kwargs, context=context, device=device, devices=devices,
                         with_arrays=with_arrays, statistics=statistics, per_transit=per_transit, models=models,
-                        detrend=detrend, detrend_mask=detrend_mask,
-                        peaks=_peaks_request(peaks, peak_separation, peak_ratios, peak_min_power, models, peak_fits),
-                        peak_fits=bool(peak_fits),
-                        phase_scan=_phase_scan_request(phase_scan, peak_fits, phase_scan_max_bins, phase_scan_min_count),
-                        transit_times=_transit_times_request(transit_times, peak_fits, transit_times_search,
-                                                             transit_times_min_ses),
-                        shape_fit=_shape_fit_request(shape_fit, peak_fits, shape_fit_window, shape_fit_min_count),
-                        sine_test=_sine_test_request(sine_test, peak_fits, sine_test_mask, sine_test_harmonics),
-                        ephemeris_match=_ephemeris_match_request(ephemeris_match, peak_fits, ephemeris_match_drift,
-                                                                 ephemeris_match_epoch, ephemeris_match_max_ratio),
-                        views=_views_request(views, peak_fits, views_global_bins, views_local_bins, views_local_durations,
-                                             views_local_width),
-                        event_vetting=_event_vetting_request(event_vetting, peak_fits, event_vetting_search,
-                                                             event_vetting_chase_window, event_vetting_guard,
-                                                             event_vetting_min_ses, event_vetting_chase_fraction,
-                                                             event_vetting_chase_min, event_vetting_point_fraction,
-                                                             event_vetting_step_fraction),
-                        centroids=_centroid_request(centroids, peak_fits, numpy.shape(flux_batch), centroid_window,
-                                                    centroid_min_in, centroid_min_out),
-                        noise=_noise_request(noise, peak_fits, t),
-                        transit_fit=_transit_fit_request(transit_fit, peak_fits, t, power_kwargs))
+                        detrend=detrend, detrend_mask=detrend_mask, peaks=peaks, peak_fits=bool(peak_fits),
+                        phase_scan=phase_scan, stages=stages)
 
 
 def _peaks_request(peaks, separation, ratios, min_power, models=False, peak_fits=False):
@@ -730,16 +739,40 @@ def _peaks_request(peaks, separation, ratios, min_power, models=False, peak_fits
     return request
 
 
-def _with_duration(peaks, duration):
-    """The device's peak records plus `duration`: table.duration[row], NaN where the row is -1."""
-    out = numpy.zeros(peaks.shape, dtype=peaks.dtype.descr + [("duration", "f8")])
-    for k in peaks.dtype.names:
-        out[k] = peaks[k]
+def _block(raw, names, sources=None):
+    """A group of peak fields of its own: a structured array of raw's shape with the float64 fields `names`, the leading ones
+    filled from raw's fields (or from its fields `sources`) in order; what is left is the caller's to fill."""
+    out = numpy.zeros(raw.shape, dtype=[(k, "f8") for k in names])
+    for k, source in zip(names, raw.dtype.names if sources is None else sources):
+        out[k] = raw[source]
+    return out
+
+
+def _joined(records, *blocks):
+    """`records` (None: nothing) and the blocks side by side in one structured array: the dtypes concatenated, the result
+    allocated once and every field filled once.  One part alone is returned as it is."""
+    parts = [part for part in (records,) + blocks if part is not None]
+    if len(parts) == 1:
+        return parts[0]
+    out = numpy.zeros(parts[0].shape, dtype=[field for part in parts for field in part.dtype.descr])
+    for part in parts:
+        for k in part.dtype.names:
+            out[k] = part[k]
+    return out
+
+
+def _duration_block(peaks, duration):
+    """`duration` of the device's peak records: table.duration[row], NaN where the row is -1."""
+    out = numpy.full(peaks.shape, numpy.nan, dtype=[("duration", "f8")])
     known = peaks["row"] >= 0
-    out["duration"] = numpy.nan
     if duration is not None:
         out["duration"][known] = numpy.asarray(duration, dtype=numpy.float64)[peaks["row"][known]]
     return out
+
+
+def _with_duration(peaks, duration):
+    """The device's peak records plus `duration` (_duration_block)."""
+    return _joined(peaks, _duration_block(peaks, duration))
 
 
 def peak_fit_fields():
@@ -749,18 +782,19 @@ def peak_fit_fields():
     return ("T0", "status") + tuple(TRANSIT_STATS_FIELDS) + ("rp_rs",)
 
 
-def _with_fits(peaks, fits, factor):
-    """The peaks (with duration) plus the device's fit records and rp_rs: rp_rs_from_depth(1 - depth) of the candidate's
-    depth, formed as the summary's (numpy's scalar ** 0.5), NaN where nothing was fitted."""
-    out = numpy.zeros(peaks.shape, dtype=peaks.dtype.descr + [(k, "f8") for k in peak_fit_fields()])
-    for k in peaks.dtype.names:
-        out[k] = peaks[k]
-    for k in fits.dtype.names:
-        out[k] = fits[k]
+def _fits_block(peaks, fits, factor):
+    """The device's fit records and rp_rs: rp_rs_from_depth(1 - depth) of the candidate's depth, formed as the summary's
+    (numpy's scalar ** 0.5), NaN where nothing was fitted."""
+    out = _block(fits, peak_fit_fields())
     fit = fits["status"] == 0
     out["rp_rs"] = numpy.nan
     out["rp_rs"][fit] = [x ** (1 / 2) for x in (1 - peaks["depth"][fit]) * factor]
     return out
+
+
+def _with_fits(peaks, fits, factor):
+    """The peaks (with duration) plus their fits (_fits_block)."""
+    return _joined(peaks, _fits_block(peaks, fits, factor))
 
 
 def _phase_scan_request(phase_scan, peak_fits, max_bins, min_count):
@@ -785,18 +819,11 @@ def phase_scan_fields():
 def _with_scans(records, scans):
     """`records` (None, or the peaks with their fits) plus the device's scan records and the two significances,
     (depth - scan_mean) / scan_std: NaN without a scatter, +-inf or NaN where the scatter is zero."""
-    names = phase_scan_fields()
-    base = [] if records is None else records.dtype.descr
-    out = numpy.zeros(scans.shape, dtype=base + [(k, "f8") for k in names])
-    if records is not None:
-        for k in records.dtype.names:
-            out[k] = records[k]
-    for k, source in zip(names, scans.dtype.names):
-        out[k] = scans[source]
+    out = _block(scans, phase_scan_fields())
     with numpy.errstate(all="ignore"):
         out["secondary_significance"] = (scans["secondary_depth"] - scans["scan_mean"]) / scans["scan_std"]
         out["primary_significance"] = (scans["primary_depth"] - scans["scan_mean"]) / scans["scan_std"]
-    return out
+    return _joined(records, out)
 
 
 def phase_scan(t, flux_batch, period, T0, duration, curve=None, max_bins=4096, min_count=3, context=None, device=None):
@@ -869,21 +896,21 @@ def find_peaks(power, periods, k, separation=0.02, ratios=HARMONICS, min_power=N
     return peaks, n_peaks
 
 
+# what a peak stage sees of one device's slice of the batch (or, behind the join, of the whole batch): the plan inputs, the rows
+# that were searched, whether a dy_batch was given, the slice itself, its peak, fit and scan records (scans None without a
+# phase scan) and the most epochs a period of the grid can have
+_PeakSlice = collections.namedtuple("_PeakSlice", ("inp", "y_rows", "dy_rows", "weighted", "rows", "peaks", "fits", "scans",
+                                                   "max_epochs"))
+
+
 def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=None, devices=None, with_arrays=False,
                  statistics=False, per_transit=False, models=False, spectra=False, detrend=None, peaks=None,
-                 peak_fits=False, phase_scan=None, transit_times=None, shape_fit=None, sine_test=None, ephemeris_match=None,
-                 views=None, event_vetting=None, centroids=None, noise=None, detrend_mask=None, transit_fit=None):
+                 peak_fits=False, phase_scan=None, detrend_mask=None, stages=None):
     """power_batch; spectra=True (power_results) also returns SR and power_raw [n_curves, n_periods] behind the arrays;
     peaks: None or a checked request (_peaks_request); peak_fits: with peaks, their T0 fits and statistics; phase_scan: None or a checked
-    request (_phase_scan_request), with peak_fits, the fits' phase scans; transit_times: None or a checked request
-    (_transit_times_request), with peak_fits, the fits' transit times; shape_fit: None or a checked request
-    (_shape_fit_request), with peak_fits, the fits' shape fits; sine_test: None or a checked request (_sine_test_request),
-    with peak_fits, the fits' sine tests; ephemeris_match: None or a checked request (_ephemeris_match_request), with
-    peak_fits, the match of the fitted peaks across the curves; views: None or a checked request (_views_request), with
-    peak_fits, the fits' folded views; event_vetting: None or a checked request (_event_vetting_request), with peak_fits, the
-    fits' event vetting; centroids: None or a checked request (_centroid_request), with peak_fits, the fits' centroid tests;
-    noise: None or a checked request (_noise_request), with peak_fits, the curves' noise profiles; transit_fit: None or a
-    checked request (_transit_fit_request), with peak_fits, the fits' limb-darkened transit fits."""
+    request (_phase_scan_request), with peak_fits, the fits' phase scans; stages: None, or a dict from the name of an entry
+    of _PEAK_STAGES to its checked request (absent or None: not asked for), with peak_fits, the follow-ups of the fits."""
+    stages = [(stage, stages[stage.name]) for stage in _PEAK_STAGES if stages and stages.get(stage.name) is not None]
     models = bool(models)
     per_transit = bool(per_transit or models)
     statistics = bool(statistics or per_transit)
@@ -910,54 +937,27 @@ def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=Non
     if peak_fits:
         kw.update(peak_fits=(fill_factor, root, root_count, max_epochs), phase_scan=phase_scan)
 
-    if transit_times is not None or event_vetting is not None:
-        from ._lib import TIMES_MAX_EPOCHS
-        tt_epochs = min(max_epochs, TIMES_MAX_EPOCHS)
-    if centroids is not None:
-        from ._lib import CENTROID_MAX_EPOCHS
-        cen_epochs = min(max_epochs, CENTROID_MAX_EPOCHS)
+    def follow_ups(ctx, scope, part, rows):
+        # (the same context, the same rows: the candidates are the peaks the search fitted)
+        env = _PeakSlice(inp, y_rows[rows], dy_rows[rows], dy_batch is not None, rows, part["peaks"], part["peak_fits"],
+                         part.get("phase_scans"), max_epochs)
+        for stage, request in stages:
+            if stage.scope == scope:
+                part.update(stage.run(ctx, env, request))
 
     def call(ctx, lo, hi):
         part = ctx._power_batch(inp["t"], y_rows[lo:hi], dy_rows[lo:hi], inp["periods"], inp["table"], inp["params"],
                                 int(kernel), **kw)
-        if transit_times is not None:
-            # (the same context, the same rows: the candidates are the peaks the search fitted)
-            part["tt_ephemeris"], part["tt_times"] = _peak_transit_times(
-                ctx, inp, y_rows[lo:hi], dy_rows[lo:hi], part["peaks"], part["peak_fits"], transit_times, tt_epochs)
-        if shape_fit is not None:
-            part["shape_fits"] = _peak_shape_fits(ctx, inp, y_rows[lo:hi], dy_rows[lo:hi], part["peaks"], part["peak_fits"],
-                                                  shape_fit)
-        if sine_test is not None:
-            # (the weights are normalised, so the search's dy / mean(dy) serve; without dy_batch they are uniform)
-            part["sine_tests"], part["sine_harmonics"] = _peak_sine_tests(
-                ctx, inp, y_rows[lo:hi], None if dy_batch is None else dy_rows[lo:hi], part["peaks"], part["peak_fits"], sine_test)
-        if views is not None:
-            (part["views_records"], part["views_global"], part["views_global_count"], part["views_local"],
-             part["views_local_count"]) = _peak_views(ctx, inp, y_rows[lo:hi], part["peaks"], part["peak_fits"],
-                                                      part["phase_scans"] if phase_scan is not None else None, views)
-        if event_vetting is not None:
-            part["ev_summaries"], part["ev_events"] = _peak_event_vetting(
-                ctx, inp, y_rows[lo:hi], dy_rows[lo:hi], part["peaks"], part["peak_fits"], event_vetting, tt_epochs)
-        if centroids is not None:
-            # (the centroid rows of the curves this device searched, beside their flux rows)
-            part["centroid_tests"] = _peak_centroid_tests(ctx, inp, y_rows[lo:hi], centroids["cx"][lo:hi], centroids["cy"][lo:hi],
-                                                          part["peaks"], part["peak_fits"], centroids, cen_epochs)
-        if noise is not None:
-            # (the same context, the same rows: the profile of what was searched)
-            part["noise_curves"], part["noise_count"], part["noise_robust"], part["noise_rms"] = ctx.noise_profile(
-                inp["t"], y_rows[lo:hi], noise["widths"], noise["span_max"], noise["pair_span"], NOISE_CLIP, NOISE_CLIP,
-                NOISE_MIN_COUNT)
-        if transit_fit is not None:
-            part["transit_fits"] = _peak_transit_fits(ctx, inp, y_rows[lo:hi], dy_rows[lo:hi], part["peaks"],
-                                                      part["peak_fits"], transit_fit)
+        if stages:
+            follow_ups(ctx, "slice", part, slice(lo, hi))
         return part
 
     out = _run_batch(devices, device, context, len(y_rows), call)
-    if ephemeris_match is not None:
+    if any(stage.scope == "batch" for stage, _ in stages):
         # (across the curves, so behind the join: one call on one device, as the SysRem step)
         ctx, lock = _first_context(context, device, devices, len(y_rows))
         with lock:
-            out["matches"] = _peak_matches(ctx, inp, out["peaks"], out["peak_fits"], ephemeris_match)
+            follow_ups(ctx, "batch", out, slice(0, len(y_rows)))
     raw = out["summary"]
     names = list(raw.dtype.names) + ["duration"]
     fields = [(k, raw.dtype[k]) for k in raw.dtype.names] + [("duration", "f8")]
@@ -1000,42 +1000,17 @@ def _power_batch(t, flux_batch, dy_batch, power_kwargs, context=None, device=Non
         m["folded_dy"][no_fit] = numpy.nan
         result += (m,)
     if peaks is not None:
-        records = _with_duration(out["peaks"], inp["table"].duration)
+        blocks = [_duration_block(out["peaks"], inp["table"].duration)]
         if peak_fits:
             from .stats import limb_darkening_factor
-            records = _with_fits(records, out["peak_fits"], limb_darkening_factor(inp["limb_dark"], inp["u"]))
+            blocks.append(_fits_block(out["peaks"], out["peak_fits"], limb_darkening_factor(inp["limb_dark"], inp["u"])))
             if phase_scan is not None:
-                records = _with_scans(records, out["phase_scans"])
+                blocks.append(_with_scans(None, out["phase_scans"]))
+        records = _joined(out["peaks"], *blocks)
         found = dict(peaks=records, n_peaks=out["n_peaks"])
-        if transit_times is not None:
-            found["peaks"] = _with_ephemeris(records, out["tt_ephemeris"])
-            found["transit_times"] = _with_oc(out["tt_ephemeris"], out["tt_times"])
-        if shape_fit is not None:
-            found["peaks"] = _with_shapes(found["peaks"], out["shape_fits"], found["peaks"]["period"])
-        if sine_test is not None:
-            found["peaks"] = _with_sines(found["peaks"], out["sine_tests"], out["sine_harmonics"])
-        if ephemeris_match is not None:
-            found["peaks"] = _with_matches(found["peaks"], out["matches"])
-        if views is not None:
-            found["peaks"] = _with_views(found["peaks"], out["views_records"])
-            found["views"] = _views_dict(out["views_global"].reshape((-1,) + out["views_global"].shape[2:]),
-                                         out["views_global_count"].reshape((-1,) + out["views_global_count"].shape[2:]),
-                                         out["views_local"].reshape((-1,) + out["views_local"].shape[2:]),
-                                         out["views_local_count"].reshape((-1,) + out["views_local_count"].shape[2:]),
-                                         lead=out["views_records"].shape)
-        if event_vetting is not None:
-            found["peaks"] = _with_events(found["peaks"], out["ev_summaries"])
-            found["events"] = out["ev_events"]
-        if centroids is not None:
-            found["peaks"] = _with_centroids(found["peaks"], out["centroid_tests"])
-        if noise is not None:
-            found["noise"] = dict(widths=noise["widths"], curves=out["noise_curves"], count=out["noise_count"],
-                                  robust=out["noise_robust"], rms=out["noise_rms"],
-                                  beta=_noise_beta(out["noise_robust"], noise["widths"], out["noise_curves"]["sigma"]))
-            found["peaks"] = _with_noise(found["peaks"], found["noise"], noise["cadence"])
-        if transit_fit is not None:
-            found["peaks"] = _with_transit_fits(found["peaks"], out["transit_fits"], found["peaks"]["period"],
-                                                found["peaks"]["T0"])
+        for stage, request in stages:
+            found.update(stage.extras(out, request))
+        found["peaks"] = _joined(records, *(stage.block(out, request, records) for stage, request in stages))
         result += (found,)
     if spectra:
         result += (out["SR"], out["power_raw"])
@@ -1374,34 +1349,51 @@ def _with_oc(ephemeris, times):
 
 def _with_ephemeris(records, ephemeris):
     """The peaks (with their fits) plus the tt_ fields of the device's ephemeris records."""
-    out = numpy.zeros(records.shape, dtype=records.dtype.descr + [(k, "f8") for k, _ in TRANSIT_TIMES_PEAK_FIELDS])
-    for k in records.dtype.names:
-        out[k] = records[k]
-    for k, source in TRANSIT_TIMES_PEAK_FIELDS:
-        out[k] = ephemeris[source]
-    return out
+    return _joined(records, _block(ephemeris, *zip(*TRANSIT_TIMES_PEAK_FIELDS)))
 
 
-def _peak_transit_times(ctx, inp, y_rows, dy_rows, peaks, fits, request, max_epochs):
-    """(ephemeris [n_curves, K], times [n_curves, K, max_epochs]) of the peaks of a slice of the batch, on ctx.  Every peak
-    is a candidate, so the device writes the whole table in place and nothing is filled or scattered on the host: a peak
-    whose fit status is not 0 goes in without an ephemeris (period and T0 NaN, the first row, reach 1) and comes back as
-    the statement has it, status 1 and NaN in every other field."""
-    from .template import reference_transit
-    search, min_ses = request
+def _peak_candidates(peaks, fits, keep=None):
+    """(period, T0, duration, curve, fitted) of the peaks of a slice of the batch as candidates, flat over [n_curves * K]:
+    the period of the peak and T0 and duration_days of its fit record where the fit status is 0 (and `keep`, where one is
+    given, holds), NaN elsewhere -- every peak is a candidate, so the device writes a whole table in place, and one without
+    an ephemeris comes back as its statement has it, status 1 and NaN in every other field; curve = the peak's curve."""
     n_curves, k = fits.shape
     fitted = (fits["status"] == 0).reshape(-1)
+    if keep is not None:
+        fitted = fitted & keep
     period = numpy.where(fitted, peaks["period"].reshape(-1), numpy.nan)
     T0 = numpy.where(fitted, fits["T0"].reshape(-1), numpy.nan)
-    row, reach = numpy.zeros(n_curves * k, dtype=numpy.int64), numpy.ones(n_curves * k, dtype=numpy.int64)
+    duration = numpy.where(fitted, fits["duration_days"].reshape(-1), numpy.nan)
+    return period, T0, duration, numpy.repeat(numpy.arange(n_curves), k), fitted
+
+
+def _peak_rows(inp, period, duration, fitted, rows_of, fill=()):
+    """(widths, shapes, span_max, per) of the fitted candidates: the rows rows_of(t, period, duration) gives them
+    (transit_time_rows, event_vetting_rows) with every row's template, and `per`, its per-candidate arrays over ALL
+    candidates -- row 0, reach 1 and then `fill` where nothing was fitted."""
+    from .template import reference_transit
+    per = [numpy.zeros(len(fitted), dtype=numpy.int64), numpy.ones(len(fitted), dtype=numpy.int64)]
+    per += [numpy.full(len(fitted), value) for value in fill]
     widths, span_max = numpy.array([3], dtype=numpy.int64), [0.0]        # (no fitted peak: one row nobody reads)
     if fitted.any():
-        widths, span_max, row[fitted], reach[fitted] = transit_time_rows(
-            inp["t"], period[fitted], fits["duration_days"].reshape(-1)[fitted], search)
+        widths, span_max, *found = rows_of(inp["t"], period[fitted], duration[fitted])
+        for target, values in zip(per, found):
+            target[fitted] = values
     shapes = [1.0 - numpy.asarray(reference_transit(int(L), **inp["shape"])) for L in widths]
-    eph, times = ctx.transit_times(inp["t"], y_rows, dy_rows, period, T0, row, reach, widths, shapes, span_max,
-                                   curve=numpy.repeat(numpy.arange(n_curves), k), min_ses=min_ses, max_epochs=int(max_epochs))
-    return eph.reshape(n_curves, k), times.reshape(n_curves, k, int(max_epochs))
+    return widths, shapes, span_max, per
+
+
+def _peak_transit_times(ctx, env, request):
+    """tt_ephemeris [n_curves, K] and tt_times [n_curves, K, max_epochs] of the peaks of a slice of the batch, on ctx."""
+    from ._lib import TIMES_MAX_EPOCHS
+    search, min_ses = request
+    max_epochs = min(env.max_epochs, TIMES_MAX_EPOCHS)
+    period, T0, duration, curve, fitted = _peak_candidates(env.peaks, env.fits)
+    widths, shapes, span_max, (row, reach) = _peak_rows(
+        env.inp, period, duration, fitted, lambda t, P, d: transit_time_rows(t, P, d, search))
+    eph, times = ctx.transit_times(env.inp["t"], env.y_rows, env.dy_rows, period, T0, row, reach, widths, shapes, span_max,
+                                   curve=curve, min_ses=min_ses, max_epochs=int(max_epochs))
+    return dict(tt_ephemeris=eph.reshape(env.fits.shape), tt_times=times.reshape(env.fits.shape + (int(max_epochs),)))
 
 
 def transit_times(t, flux_batch, period, T0, duration, curve=None, dy_batch=None, search=1.0, min_ses=3.0,
@@ -1452,14 +1444,7 @@ def transit_times(t, flux_batch, period, T0, duration, curve=None, dy_batch=None
     oc = time - (T0_fit + epoch * period_fit); NaN past a candidate's n_epochs."""
     search, min_ses, gap_tolerance, depth_min, max_epochs = _transit_times_options(search, min_ses, gap_tolerance,
                                                                                    transit_depth_min, max_epochs)
-    t = numpy.asarray(t, dtype=numpy.float64)
-    if numpy.ndim(flux_batch) == 1:
-        flux_batch = numpy.asarray(flux_batch)[None, :]
-        dy_batch = None if dy_batch is None else numpy.asarray(dy_batch)[None, :]
-    if numpy.ndim(flux_batch) != 2 or t.ndim != 1 or numpy.shape(flux_batch)[1] != len(t):
-        raise ValueError("flux_batch must be [n] or [n_curves, n] over the time stamps t [n]")
-    if not numpy.all(numpy.isfinite(t)) or not numpy.all(t[1:] >= t[:-1]):
-        raise ValueError("transit times: t must be finite and non-decreasing")
+    t, flux_batch, dy_batch = _candidate_rows("transit times", t, flux_batch, dy_batch)
     try:
         period, T0, duration = (numpy.atleast_1d(numpy.asarray(v, dtype=numpy.float64)) for v in (period, T0, duration))
     except (TypeError, ValueError):
@@ -1482,13 +1467,9 @@ def transit_times(t, flux_batch, period, T0, duration, curve=None, dy_batch=None
         counts = _epoch_counts(t, period, T0)
         counts = counts[(counts >= 1.0) & (counts <= TIMES_MAX_EPOCHS)]
         max_epochs = int(counts.max()) if len(counts) else 1
-    flux_batch = _detrended(t, flux_batch, detrend, context, device, None, dy_batch)
-    kwargs = dict(template_kwargs)
-    kwargs.setdefault("oversampling_factor", 1)      # (the period grid of the plan inputs is not used: the coarsest will do)
-    inp, y_rows, dy_rows = _batch_inputs(t, flux_batch, dy_batch, kwargs)
+    inp, y_rows, dy_rows, ctx = _candidate_inputs(t, flux_batch, dy_batch, detrend, context, device, template_kwargs)
     from .template import reference_transit
     shapes = [1.0 - numpy.asarray(reference_transit(int(L), **inp["shape"])) for L in widths]
-    ctx = context if context is not None else _search.default_context(device)
     eph, times = ctx.transit_times(inp["t"], y_rows, dy_rows, period, T0, row, reach, widths, shapes, span_max, curve=curve,
                                    depth_min=depth_min, min_ses=min_ses, max_epochs=max_epochs)
     return eph, _with_oc(eph, times)
@@ -1575,39 +1556,23 @@ def event_vetting_rows(t, period, duration, search=1.0, chase_window=EVENT_VETTI
 
 def _with_events(records, summaries):
     """The peaks (with whatever they carry) plus the ev_ fields of the device's event summaries."""
-    names = event_summary_fields()
-    out = numpy.zeros(records.shape, dtype=records.dtype.descr + [("ev_" + k, "f8") for k in names])
-    for k in records.dtype.names:
-        out[k] = records[k]
-    for k in names:
-        out["ev_" + k] = summaries[k]
-    return out
+    return _joined(records, _block(summaries, ["ev_" + k for k in event_summary_fields()]))
 
 
-def _peak_event_vetting(ctx, inp, y_rows, dy_rows, peaks, fits, request, max_epochs):
-    """(summaries [n_curves, K], events [n_curves, K, max_epochs]) of the peaks of a slice of the batch, on ctx.  Every peak
-    is a candidate, as in _peak_transit_times: a peak whose fit status is not 0 goes in without an ephemeris and comes back
-    as the statement has it, status 1 and NaN in every other field."""
-    from .template import reference_transit
-    n_curves, k = fits.shape
-    fitted = (fits["status"] == 0).reshape(-1)
-    period = numpy.where(fitted, peaks["period"].reshape(-1), numpy.nan)
-    T0 = numpy.where(fitted, fits["T0"].reshape(-1), numpy.nan)
-    row, reach = numpy.zeros(n_curves * k, dtype=numpy.int64), numpy.ones(n_curves * k, dtype=numpy.int64)
-    chase_reach, guard = numpy.zeros(n_curves * k, dtype=numpy.int64), numpy.zeros(n_curves * k, dtype=numpy.int64)
-    chase_span = numpy.ones(n_curves * k)
-    widths, span_max = numpy.array([3], dtype=numpy.int64), [0.0]        # (no fitted peak: one row nobody reads)
-    if fitted.any():
-        (widths, span_max, row[fitted], reach[fitted], chase_reach[fitted], guard[fitted],
-         chase_span[fitted]) = event_vetting_rows(inp["t"], period[fitted], fits["duration_days"].reshape(-1)[fitted],
-                                                  request["search"], request["chase_window"], request["guard"])
-    shapes = [1.0 - numpy.asarray(reference_transit(int(L), **inp["shape"])) for L in widths]
-    out, events = ctx.event_vetting(inp["t"], y_rows, dy_rows, period, T0, row, reach, chase_reach, guard, chase_span, widths,
-                                    shapes, span_max, curve=numpy.repeat(numpy.arange(n_curves), k),
-                                    min_ses=request["min_ses"], chase_fraction=request["chase_fraction"],
-                                    chase_min=request["chase_min"], point_fraction=request["point_fraction"],
-                                    step_fraction=request["step_fraction"], max_epochs=int(max_epochs))
-    return out.reshape(n_curves, k), events.reshape(n_curves, k, int(max_epochs))
+def _peak_event_vetting(ctx, env, request):
+    """ev_summaries [n_curves, K] and ev_events [n_curves, K, max_epochs] of the peaks of a slice of the batch, on ctx."""
+    from ._lib import TIMES_MAX_EPOCHS
+    max_epochs = min(env.max_epochs, TIMES_MAX_EPOCHS)
+    period, T0, duration, curve, fitted = _peak_candidates(env.peaks, env.fits)
+    widths, shapes, span_max, (row, reach, chase_reach, guard, chase_span) = _peak_rows(
+        env.inp, period, duration, fitted,
+        lambda t, P, d: event_vetting_rows(t, P, d, request["search"], request["chase_window"], request["guard"]), (0, 0, 1.0))
+    out, events = ctx.event_vetting(env.inp["t"], env.y_rows, env.dy_rows, period, T0, row, reach, chase_reach, guard,
+                                    chase_span, widths, shapes, span_max, curve=curve, min_ses=request["min_ses"],
+                                    chase_fraction=request["chase_fraction"], chase_min=request["chase_min"],
+                                    point_fraction=request["point_fraction"], step_fraction=request["step_fraction"],
+                                    max_epochs=int(max_epochs))
+    return dict(ev_summaries=out.reshape(env.fits.shape), ev_events=events.reshape(env.fits.shape + (int(max_epochs),)))
 
 
 def event_vetting(t, flux_batch, period, T0, duration, curve=None, dy_batch=None, search=1.0,
@@ -1652,14 +1617,7 @@ def event_vetting(t, flux_batch, period, T0, duration, curve=None, dy_batch=None
     max_epochs] with the fields event_fields(); NaN past a candidate's n_epochs."""
     o = _event_vetting_options(search, chase_window, guard, min_ses, chase_fraction, chase_min, point_fraction, step_fraction,
                                gap_tolerance, transit_depth_min, max_epochs)
-    t = numpy.asarray(t, dtype=numpy.float64)
-    if numpy.ndim(flux_batch) == 1:
-        flux_batch = numpy.asarray(flux_batch)[None, :]
-        dy_batch = None if dy_batch is None else numpy.asarray(dy_batch)[None, :]
-    if numpy.ndim(flux_batch) != 2 or t.ndim != 1 or numpy.shape(flux_batch)[1] != len(t):
-        raise ValueError("flux_batch must be [n] or [n_curves, n] over the time stamps t [n]")
-    if not numpy.all(numpy.isfinite(t)) or not numpy.all(t[1:] >= t[:-1]):
-        raise ValueError("event vetting: t must be finite and non-decreasing")
+    t, flux_batch, dy_batch = _candidate_rows("event vetting", t, flux_batch, dy_batch)
     try:
         period, T0, duration = (numpy.atleast_1d(numpy.asarray(v, dtype=numpy.float64)) for v in (period, T0, duration))
     except (TypeError, ValueError):
@@ -1687,13 +1645,9 @@ def event_vetting(t, flux_batch, period, T0, duration, curve=None, dy_batch=None
         counts = _epoch_counts(t, period, T0)
         counts = counts[(counts >= 1.0) & (counts <= TIMES_MAX_EPOCHS)]
         max_epochs = int(counts.max()) if len(counts) else 1
-    flux_batch = _detrended(t, flux_batch, detrend, context, device, None, dy_batch)
-    kwargs = dict(template_kwargs)
-    kwargs.setdefault("oversampling_factor", 1)      # (the period grid of the plan inputs is not used: the coarsest will do)
-    inp, y_rows, dy_rows = _batch_inputs(t, flux_batch, dy_batch, kwargs)
+    inp, y_rows, dy_rows, ctx = _candidate_inputs(t, flux_batch, dy_batch, detrend, context, device, template_kwargs)
     from .template import reference_transit
     shapes = [1.0 - numpy.asarray(reference_transit(int(L), **inp["shape"])) for L in widths]
-    ctx = context if context is not None else _search.default_context(device)
     return ctx.event_vetting(inp["t"], y_rows, dy_rows, period, T0, row, reach, chase_reach, guards, chase_span, widths, shapes,
                              span_max, curve=curve, depth_min=o["depth_min"], min_ses=o["min_ses"],
                              chase_fraction=o["chase_fraction"], chase_min=o["chase_min"], point_fraction=o["point_fraction"],
@@ -1761,33 +1715,20 @@ def _shape_fit_request(shape_fit, peak_fits, window, min_count):
 def _with_shapes(records, shapes, period):
     """`records` (None, or the peaks with their fits) plus the device's shape records, shape_delta_chi2 and the geometry of
     the best trapezoid at `period`."""
-    names = shape_fit_fields()
-    base = [] if records is None else records.dtype.descr
-    out = numpy.zeros(shapes.shape, dtype=base + [(k, "f8") for k in names])
-    if records is not None:
-        for k in records.dtype.names:
-            out[k] = records[k]
-    for k, source in zip(names, shapes.dtype.names):
-        out[k] = shapes[source]
+    out = _block(shapes, shape_fit_fields())
     out["shape_delta_chi2"] = shapes["ses"] * shapes["ses"] - shapes["ses_vee"] * shapes["ses_vee"]
     out["shape_impact"], out["shape_a_rs"], out["shape_rho_star"] = transit_geometry(
         period, shapes["depth"], shapes["duration"], shapes["ingress"])
-    return out
+    return _joined(records, out)
 
 
-def _peak_shape_fits(ctx, inp, y_rows, dy_rows, peaks, fits, request):
-    """The shape records [n_curves, K] of the peaks of a slice of the batch, on ctx.  Every peak is a candidate, so the device
-    writes the whole table in place: a peak whose fit status is not 0 goes in as (NaN, NaN, NaN) and comes back as the
-    statement has it, status 1 and NaN in every other field."""
+def _peak_shape_fits(ctx, env, request):
+    """shape_fits [n_curves, K]: the shape records of the peaks of a slice of the batch, on ctx."""
     window, min_count = request
-    n_curves, k = fits.shape
-    fitted = (fits["status"] == 0).reshape(-1)
-    period = numpy.where(fitted, peaks["period"].reshape(-1), numpy.nan)
-    T0 = numpy.where(fitted, fits["T0"].reshape(-1), numpy.nan)
-    duration = numpy.where(fitted, fits["duration_days"].reshape(-1), numpy.nan)
-    out = ctx.shape_fit(inp["t"], y_rows, dy_rows, period, T0, duration, SHAPE_FIT_RATIOS, SHAPE_FIT_INGRESS,
-                        SHAPE_FIT_SHIFTS, curve=numpy.repeat(numpy.arange(n_curves), k), window=window, min_count=min_count)
-    return out.reshape(n_curves, k)
+    period, T0, duration, curve, _ = _peak_candidates(env.peaks, env.fits)
+    out = ctx.shape_fit(env.inp["t"], env.y_rows, env.dy_rows, period, T0, duration, SHAPE_FIT_RATIOS, SHAPE_FIT_INGRESS,
+                        SHAPE_FIT_SHIFTS, curve=curve, window=window, min_count=min_count)
+    return dict(shape_fits=out.reshape(env.fits.shape))
 
 
 def shape_fit(t, flux_batch, period, T0, duration, curve=None, dy_batch=None, ratios=None, ingress=None, shifts=None,
@@ -1834,20 +1775,9 @@ def shape_fit(t, flux_batch, period, T0, duration, curve=None, dy_batch=None, ra
     ratio, ingress, shift, window, min_count, depth_min = shape_fit_tables(
         SHAPE_FIT_RATIOS if ratios is None else ratios, SHAPE_FIT_INGRESS if ingress is None else ingress,
         SHAPE_FIT_SHIFTS if shifts is None else shifts, window, min_count, transit_depth_min)
-    t = numpy.asarray(t, dtype=numpy.float64)
-    if numpy.ndim(flux_batch) == 1:
-        flux_batch = numpy.asarray(flux_batch)[None, :]
-        dy_batch = None if dy_batch is None else numpy.asarray(dy_batch)[None, :]
-    if numpy.ndim(flux_batch) != 2 or t.ndim != 1 or numpy.shape(flux_batch)[1] != len(t):
-        raise ValueError("flux_batch must be [n] or [n_curves, n] over the time stamps t [n]")
-    if not numpy.all(numpy.isfinite(t)) or not numpy.all(t[1:] >= t[:-1]):
-        raise ValueError("shape fit: t must be finite and non-decreasing")
+    t, flux_batch, dy_batch = _candidate_rows("shape fit", t, flux_batch, dy_batch)
     period, T0, duration, curve = shape_fit_candidates(period, T0, duration, curve, numpy.shape(flux_batch)[0])
-    flux_batch = _detrended(t, flux_batch, detrend, context, device, None, dy_batch)
-    kwargs = dict(power_kwargs)
-    kwargs.setdefault("oversampling_factor", 1)      # (the period grid of the plan inputs is not used: the coarsest will do)
-    inp, y_rows, dy_rows = _batch_inputs(t, flux_batch, dy_batch, kwargs)
-    ctx = context if context is not None else _search.default_context(device)
+    inp, y_rows, dy_rows, ctx = _candidate_inputs(t, flux_batch, dy_batch, detrend, context, device, power_kwargs)
     out = ctx.shape_fit(inp["t"], y_rows, dy_rows, period, T0, duration, ratio, ingress, shift, curve=curve, window=window,
                         min_count=min_count, depth_min=depth_min)
     return _with_shapes(None, out, period)
@@ -1972,17 +1902,10 @@ def _seed_rows(k_rows, depth):
 
 def _with_transit_fits(records, fits, period, T0):
     """`records` (None, or the peaks with their fits) plus the device's transit-fit records, fit_T0 and the geometry."""
-    names = transit_fit_fields()
-    base = [] if records is None else records.dtype.descr
-    out = numpy.zeros(fits.shape, dtype=base + [(k, "f8") for k in names])
-    if records is not None:
-        for k in records.dtype.names:
-            out[k] = records[k]
-    for k, source in zip(names, fits.dtype.names):
-        out[k] = fits[source]
+    out = _block(fits, transit_fit_fields())
     out["fit_T0"] = numpy.asarray(T0, dtype=numpy.float64) + fits["shift"]
     out["fit_a_rs"], out["fit_inc"], out["fit_rho_star"] = transit_fit_geometry(period, fits["k"], fits["b"], fits["duration"])
-    return out
+    return _joined(records, out)
 
 
 def _transit_fit_request(transit_fit, peak_fits, t, power_kwargs):
@@ -2005,25 +1928,19 @@ def _transit_fit_request(transit_fit, peak_fits, t, power_kwargs):
 
 
 def _peak_transit_fits(ctx, inp, y_rows, dy_rows, peaks, fits, request):
-    """The transit-fit records [n_curves, K] of the peaks of a slice of the batch, on ctx.  Every peak is a candidate: one
-    whose fit status is not 0 goes in as (NaN, NaN, NaN) and comes back as the statement has it, status 1 -- and so does a
-    peak whose duration is too short for the window to hold the widest, farthest shifted model plus half an exposure (the
-    entry refuses such a candidate, and the durations are known only behind the search)."""
-    n_curves, k = fits.shape
-    fitted = (fits["status"] == 0).reshape(-1)
+    """The transit-fit records [n_curves, K] of the peaks of a slice of the batch, on ctx.  A peak whose duration is too
+    short for the window to hold the widest, farthest shifted model plus half an exposure is no candidate either (the entry
+    refuses such a candidate, and the durations are known only behind the search)."""
     reach = 0.5 * float(request["ratio"][-1]) + max(abs(float(request["shift"][0])), abs(float(request["shift"][-1])))
     with numpy.errstate(all="ignore"):
         d = fits["duration_days"].reshape(-1)
-        fitted = fitted & (request["window"] * d >= reach * d + float(numpy.max(numpy.fabs(request["sub"]))))
-    period = numpy.where(fitted, peaks["period"].reshape(-1), numpy.nan)
-    T0 = numpy.where(fitted, fits["T0"].reshape(-1), numpy.nan)
-    duration = numpy.where(fitted, fits["duration_days"].reshape(-1), numpy.nan)
+        holds = request["window"] * d >= reach * d + float(numpy.max(numpy.fabs(request["sub"])))
+    period, T0, duration, curve, fitted = _peak_candidates(peaks, fits, holds)
     rows = _seed_rows(request["k_rows"], numpy.where(fitted, 1.0 - peaks["depth"].reshape(-1), numpy.nan))
     out = ctx.transit_fit(inp["t"], y_rows, dy_rows, period, T0, duration, rows, request["k_rows"], request["profile"],
-                          request["impact"], request["ratio"], request["shift"], request["sub"],
-                          curve=numpy.repeat(numpy.arange(n_curves), k), window=request["window"],
-                          min_count=request["min_count"], delta=request["delta"])
-    return out.reshape(n_curves, k)
+                          request["impact"], request["ratio"], request["shift"], request["sub"], curve=curve,
+                          window=request["window"], min_count=request["min_count"], delta=request["delta"])
+    return out.reshape(fits.shape)
 
 
 def transit_fit(t, flux_batch, period, T0, duration, depth, curve=None, dy_batch=None, impacts=None, ratios=None, shifts=None,
@@ -2061,30 +1978,19 @@ def transit_fit(t, flux_batch, period, T0, duration, depth, curve=None, dy_batch
     fit (NaN where it has none)."""
     from ._lib import shape_fit_candidates, transit_fit_window_holds
     setup = _transit_fit_setup(t, impacts, ratios, shifts, exposure, n_sub, window, min_count, delta, profile, template_kwargs)
-    t = numpy.asarray(t, dtype=numpy.float64)
-    if numpy.ndim(flux_batch) == 1:
-        flux_batch = numpy.asarray(flux_batch)[None, :]
-        dy_batch = None if dy_batch is None else numpy.asarray(dy_batch)[None, :]
-    if numpy.ndim(flux_batch) != 2 or t.ndim != 1 or numpy.shape(flux_batch)[1] != len(t):
-        raise ValueError("flux_batch must be [n] or [n_curves, n] over the time stamps t [n]")
-    if not numpy.all(numpy.isfinite(t)) or not numpy.all(t[1:] >= t[:-1]):
-        raise ValueError("transit fit: t must be finite and non-decreasing")
+    t, flux_batch, dy_batch = _candidate_rows("transit fit", t, flux_batch, dy_batch)
+    period, T0, duration, curve = shape_fit_candidates(period, T0, duration, curve, numpy.shape(flux_batch)[0], "transit fit")
     try:
-        period, T0, duration, curve = shape_fit_candidates(period, T0, duration, curve, numpy.shape(flux_batch)[0])
         depth = numpy.ascontiguousarray(numpy.atleast_1d(numpy.asarray(depth, dtype=numpy.float64)))
     except (TypeError, ValueError) as e:
-        raise ValueError(str(e).replace("shape fit:", "transit fit:"))
+        raise ValueError(str(e))
     if depth.shape != period.shape:
         raise ValueError("transit fit: depth must hold one value a candidate")
     if not transit_fit_window_holds(duration, setup["ratio"], setup["shift"], setup["sub"], setup["window"]):
         raise ValueError("transit fit: window %r does not hold the widest, farthest shifted model plus half an exposure for "
                          "the shortest duration" % (setup["window"],))
     rows = _seed_rows(setup["k_rows"], depth)
-    flux_batch = _detrended(t, flux_batch, detrend, context, device, None, dy_batch)
-    kwargs = dict(template_kwargs)
-    kwargs.setdefault("oversampling_factor", 1)      # (the period grid of the plan inputs is not used: the coarsest will do)
-    inp, y_rows, dy_rows = _batch_inputs(t, flux_batch, dy_batch, kwargs)
-    ctx = context if context is not None else _search.default_context(device)
+    inp, y_rows, dy_rows, ctx = _candidate_inputs(t, flux_batch, dy_batch, detrend, context, device, template_kwargs)
     out = ctx.transit_fit(inp["t"], y_rows, dy_rows, period, T0, duration, rows, setup["k_rows"], setup["profile"],
                           setup["impact"], setup["ratio"], setup["shift"], setup["sub"], curve=curve, window=setup["window"],
                           min_count=setup["min_count"], delta=setup["delta"])
@@ -2159,33 +2065,22 @@ def _centroid_request(centroids, peak_fits, flux_shape, window, min_in, min_out)
 def _with_centroids(records, tests):
     """`records` (None, or the peaks with their fits) plus the device's centroid records and what centroid_offsets forms of
     them."""
-    names = centroid_fields()
-    base = [] if records is None else records.dtype.descr
-    out = numpy.zeros(tests.shape, dtype=base + [(k, "f8") for k in names])
-    if records is not None:
-        for k in records.dtype.names:
-            out[k] = records[k]
-    for k, source in zip(names, tests.dtype.names):
-        out[k] = tests[source]
+    out = _block(tests, centroid_fields())
     (out["cen_shift"], out["cen_significance"], out["cen_offset_x"], out["cen_offset_y"], out["cen_offset"],
      out["cen_offset_err"]) = centroid_offsets(tests["depth"], tests["depth_err"], tests["shift_x"], tests["shift_x_err"],
                                                tests["shift_y"], tests["shift_y_err"])
-    return out
+    return _joined(records, out)
 
 
-def _peak_centroid_tests(ctx, inp, y_rows, cx_rows, cy_rows, peaks, fits, request, max_epochs):
-    """The centroid records [n_curves, K] of the peaks of a slice of the batch, on ctx.  Every peak is a candidate, so the
-    device writes the whole table in place: a peak whose fit status is not 0 goes in as (NaN, NaN, NaN) and comes back as the
-    statement has it, status 1 and NaN in every other field."""
-    n_curves, k = fits.shape
-    fitted = (fits["status"] == 0).reshape(-1)
-    period = numpy.where(fitted, peaks["period"].reshape(-1), numpy.nan)
-    T0 = numpy.where(fitted, fits["T0"].reshape(-1), numpy.nan)
-    duration = numpy.where(fitted, fits["duration_days"].reshape(-1), numpy.nan)
-    out = ctx.centroid_test(inp["t"], y_rows, cx_rows, cy_rows, period, T0, duration, _centroid_shape(inp),
-                            curve=numpy.repeat(numpy.arange(n_curves), k), window=request["window"],
-                            min_in=request["min_in"], min_out=request["min_out"], max_epochs=max_epochs)
-    return out.reshape(n_curves, k)
+def _peak_centroid_tests(ctx, env, request):
+    """centroid_tests [n_curves, K]: the centroid records of the peaks of a slice of the batch, on ctx, from the flux rows
+    it searched and the centroid rows of the same curves."""
+    from ._lib import CENTROID_MAX_EPOCHS
+    period, T0, duration, curve, _ = _peak_candidates(env.peaks, env.fits)
+    out = ctx.centroid_test(env.inp["t"], env.y_rows, request["cx"][env.rows], request["cy"][env.rows], period, T0, duration,
+                            _centroid_shape(env.inp), curve=curve, window=request["window"], min_in=request["min_in"],
+                            min_out=request["min_out"], max_epochs=min(env.max_epochs, CENTROID_MAX_EPOCHS))
+    return dict(centroid_tests=out.reshape(env.fits.shape))
 
 
 def centroid_epochs(t, period):
@@ -2246,25 +2141,12 @@ def centroid_test(t, flux_batch, cx_batch, cy_batch, period, T0, duration, curve
     cen_chi2_y, and cen_shift, cen_significance, cen_offset_x, cen_offset_y, cen_offset, cen_offset_err (NaN where
     cen_depth is not > 0)."""
     from ._lib import centroid_options, centroid_rows, shape_fit_candidates
-    t = numpy.asarray(t, dtype=numpy.float64)
-    if numpy.ndim(flux_batch) == 1:
-        flux_batch = numpy.asarray(flux_batch)[None, :]
-    if numpy.ndim(flux_batch) != 2 or t.ndim != 1 or numpy.shape(flux_batch)[1] != len(t):
-        raise ValueError("flux_batch must be [n] or [n_curves, n] over the time stamps t [n]")
-    if not numpy.all(numpy.isfinite(t)) or not numpy.all(t[1:] >= t[:-1]):
-        raise ValueError("centroid test: t must be finite and non-decreasing")
+    t, flux_batch, _ = _candidate_rows("centroid test", t, flux_batch)
     cx_rows, cy_rows = centroid_rows(cx_batch, cy_batch, numpy.shape(flux_batch))
-    try:
-        period, T0, duration, curve = shape_fit_candidates(period, T0, duration, curve, numpy.shape(flux_batch)[0])
-    except ValueError as e:
-        raise ValueError(str(e).replace("shape fit", "centroid test"))
+    period, T0, duration, curve = shape_fit_candidates(period, T0, duration, curve, numpy.shape(flux_batch)[0], "centroid test")
     window, min_in, min_out, max_epochs = centroid_options(window, min_in, min_out,
                                                            centroid_epochs(t, period) if max_epochs is None else max_epochs)
-    flux_batch = _detrended(t, flux_batch, detrend, context, device, None, None)
-    kwargs = dict(power_kwargs)
-    kwargs.setdefault("oversampling_factor", 1)      # (the period grid of the plan inputs is not used: the coarsest will do)
-    inp, y_rows, _ = _batch_inputs(t, flux_batch, None, kwargs)
-    ctx = context if context is not None else _search.default_context(device)
+    inp, y_rows, _, ctx = _candidate_inputs(t, flux_batch, None, detrend, context, device, power_kwargs)
     out = ctx.centroid_test(inp["t"], y_rows, cx_rows, cy_rows, period, T0, duration, _centroid_shape(inp), curve=curve,
                             window=window, min_in=min_in, min_out=min_out, max_epochs=max_epochs)
     return _with_centroids(None, out)
@@ -2366,31 +2248,29 @@ def _views_request(views, peak_fits, n_global, n_local, local_durations, local_w
     return folded_views_tables(n_global, n_local, local_durations, local_width)
 
 
-def _peak_views(ctx, inp, y_rows, peaks, fits, scans, request):
-    """The views of the peaks of a slice of the batch, on ctx: the records [n_curves, K] and the four arrays of the device,
-    [n_curves, K, ...].  Every peak is a candidate: one whose fit status is not 0 goes in as NaN and comes back with status 1,
-    NaN and 0.  scans (None: no secondary view) are the slice's phase-scan records."""
+def _peak_views(ctx, env, request):
+    """The views of the peaks of a slice of the batch, on ctx: views_records [n_curves, K] and the four arrays of the
+    device, [n_curves, K, ...].  Without phase scans there is no secondary view."""
     n_global, n_local, k, width = request
-    n_curves, K = fits.shape
-    fitted = (fits["status"] == 0).reshape(-1)
-    period = numpy.where(fitted, peaks["period"].reshape(-1), numpy.nan)
-    T0 = numpy.where(fitted, fits["T0"].reshape(-1), numpy.nan)
-    duration = numpy.where(fitted, fits["duration_days"].reshape(-1), numpy.nan)
-    phi = None if scans is None else numpy.where(fitted, scans["secondary_phase"].reshape(-1), numpy.nan)
-    out = ctx.folded_views(inp["t"], y_rows, period, T0, duration, curve=numpy.repeat(numpy.arange(n_curves), K),
-                           secondary_phase=phi, n_global=n_global, n_local=n_local, local_durations=k, local_width=width)
-    return tuple(v.reshape((n_curves, K) + v.shape[1:]) for v in out)
+    period, T0, duration, curve, fitted = _peak_candidates(env.peaks, env.fits)
+    phi = None if env.scans is None else numpy.where(fitted, env.scans["secondary_phase"].reshape(-1), numpy.nan)
+    out = ctx.folded_views(env.inp["t"], env.y_rows, period, T0, duration, curve=curve, secondary_phase=phi,
+                           n_global=n_global, n_local=n_local, local_durations=k, local_width=width)
+    names = ("views_records", "views_global", "views_global_count", "views_local", "views_local_count")
+    return {name: v.reshape(env.fits.shape + v.shape[1:]) for name, v in zip(names, out)}
+
+
+def _peak_views_dict(out, request):
+    """The `views` entry of the peaks dict from the joined arrays of _peak_views."""
+    flat = (out[k].reshape((-1,) + out[k].shape[2:]) for k in ("views_global", "views_global_count", "views_local",
+                                                               "views_local_count"))
+    return dict(views=_views_dict(*flat, lead=out["views_records"].shape))
 
 
 def _with_views(records, views):
     """The peaks plus views_status and the five views_n_* member counts of the device's view records."""
-    names = [("views_status", "status")] + [("views_" + k, k) for k in folded_view_fields()[2:]]
-    out = numpy.zeros(records.shape, dtype=records.dtype.descr + [(k, "f8") for k, _ in names])
-    for k in records.dtype.names:
-        out[k] = records[k]
-    for k, source in names:
-        out[k] = views[source]
-    return out
+    fields = folded_view_fields()
+    return _joined(records, _block(views, ["views_status"] + ["views_" + k for k in fields[2:]], ("status",) + fields[2:]))
 
 
 # ---- variability periodogram and sine test -----------------------------------------------------------------------------------
@@ -2489,32 +2369,23 @@ def _with_sines(records, sines, harmonics):
     """`records` (None, or the peaks with their fits) plus the device's sine records and harmonic records."""
     from ._lib import SINE_FIELDS, SINE_HARMONIC_FIELDS
     nH = harmonics.shape[-1]
-    base = [] if records is None else records.dtype.descr
-    out = numpy.zeros(sines.shape, dtype=base + [("sine_" + k, "f8") for k in SINE_FIELDS]
+    out = numpy.zeros(sines.shape, dtype=[("sine_" + k, "f8") for k in SINE_FIELDS]
                       + [("sine_" + k, "f8", (nH,)) for k in SINE_HARMONIC_FIELDS])
-    if records is not None:
-        for k in records.dtype.names:
-            out[k] = records[k]
     for k in SINE_FIELDS:
         out["sine_" + k] = sines[k]
     for k in SINE_HARMONIC_FIELDS:
         out["sine_" + k] = harmonics[k]
-    return out
+    return _joined(records, out)
 
 
-def _peak_sine_tests(ctx, inp, y_rows, dy_rows, peaks, fits, request):
-    """The sine records [n_curves, K] and harmonic records [n_curves, K, n_harmonics] of the peaks of a slice of the batch,
-    on ctx.  Every peak is a candidate: a peak whose fit status is not 0 goes in as (NaN, NaN, NaN) and comes back as the
-    statement has it, status 1 and NaN in every other field."""
+def _peak_sine_tests(ctx, env, request):
+    """sine_tests [n_curves, K] and sine_harmonics [n_curves, K, n_harmonics] of the peaks of a slice of the batch, on ctx.
+    The weights are normalised, so the search's dy / mean(dy) serve; without a dy_batch they are uniform."""
     mask, harmonics = request
-    n_curves, k = fits.shape
-    fitted = (fits["status"] == 0).reshape(-1)
-    period = numpy.where(fitted, peaks["period"].reshape(-1), numpy.nan)
-    T0 = numpy.where(fitted, fits["T0"].reshape(-1), numpy.nan)
-    duration = numpy.where(fitted, fits["duration_days"].reshape(-1), numpy.nan)
-    out, out_h = ctx.sine_test(inp["t"], y_rows, period, curve=numpy.repeat(numpy.arange(n_curves), k), dy=dy_rows, T0=T0,
+    period, T0, duration, curve, _ = _peak_candidates(env.peaks, env.fits)
+    out, out_h = ctx.sine_test(env.inp["t"], env.y_rows, period, curve=curve, dy=env.dy_rows if env.weighted else None, T0=T0,
                                duration=duration, mask=mask, harmonics=harmonics)
-    return out.reshape(n_curves, k), out_h.reshape(n_curves, k, len(harmonics))
+    return dict(sine_tests=out.reshape(env.fits.shape), sine_harmonics=out_h.reshape(env.fits.shape + (len(harmonics),)))
 
 
 def sine_test(t, flux_batch, period, curve=None, dy_batch=None, T0=None, duration=None, mask=1.5, harmonics=(0.5, 1.0, 2.0),
@@ -2581,18 +2452,18 @@ def _ephemeris_match_request(ephemeris_match, peak_fits, drift, epoch, max_ratio
     return a["drift_tolerance"], a["epoch_tolerance"], a["max_ratio"]
 
 
-def _peak_matches(ctx, inp, peaks, fits, request):
-    """The match records of the fitted peaks of the whole batch, on ctx: (records MATCH_DTYPE [M], the candidates' flat
-    indices c K + r into [n_curves, K], the shape).  A candidate is a peak of fit status 0: star = its curve, its period, T0
-    and duration_days of its fit, strength = 1 - depth; span = max t - min t."""
+def _peak_matches(ctx, env, request):
+    """matches: the match records of the fitted peaks of the whole batch, on ctx, as (records MATCH_DTYPE [M], the
+    candidates' flat indices c K + r into [n_curves, K], the shape).  A candidate is a peak of fit status 0: star = its
+    curve, its period, T0 and duration_days of its fit, strength = 1 - depth; span = max t - min t."""
     drift, epoch, max_ratio = request
-    n_curves, k = fits.shape
+    peaks, fits, t = env.peaks, env.fits, env.inp["t"]
+    k = fits.shape[1]
     at = numpy.flatnonzero((fits["status"] == 0).reshape(-1))
-    t = inp["t"]
     records = ctx.ephemeris_match(at // k, peaks["period"].reshape(-1)[at], fits["T0"].reshape(-1)[at],
                                   fits["duration_days"].reshape(-1)[at], 1 - peaks["depth"].reshape(-1)[at],
                                   numpy.max(t) - numpy.min(t), drift, epoch, max_ratio)
-    return records, at, (n_curves, k)
+    return dict(matches=(records, at, fits.shape))
 
 
 def _with_matches(records, matches):
@@ -2602,9 +2473,7 @@ def _with_matches(records, matches):
     found, at, shape = matches
     k = shape[1]
     names = ephemeris_match_peak_fields()
-    out = numpy.zeros(shape, dtype=records.dtype.descr + [(n, "i8" if n in ("match_curve", "match_rank") else "f8") for n in names])
-    for n in records.dtype.names:
-        out[n] = records[n]
+    out = numpy.zeros(shape, dtype=[(n, "i8" if n in ("match_curve", "match_rank") else "f8") for n in names])
     flat = out.reshape(-1)
     for n in names:
         flat[n] = -1 if n in ("match_curve", "match_rank") else numpy.nan
@@ -2616,7 +2485,7 @@ def _with_matches(records, matches):
     target = at[numpy.where(there, best, 0)]
     flat["match_curve"][at] = numpy.where(there, target // k, -1)
     flat["match_rank"][at] = numpy.where(there, target % k, -1)
-    return out
+    return _joined(records, out)
 
 
 def ephemeris_match(star, period, T0, duration, strength, span, drift_tolerance=0.5, epoch_tolerance=0.5, max_ratio=3,
@@ -2671,7 +2540,6 @@ def ephemeris_groups(records):
     return root
 
 
-# ---- injection-recovery ---------------------------------------------------------------------------------------------------
 # ---- the per-star noise profile ------------------------------------------------------------------------------------------------
 # the 14 pulse durations (hours) of Kepler's rms CDPP table
 KEPLER_PULSE_HOURS = (1.5, 2.0, 2.5, 3.0, 3.5, 4.5, 5.0, 6.0, 7.5, 9.0, 10.5, 12.0, 12.5, 15.0)
@@ -2820,13 +2688,11 @@ def noise_width_index(duration_days, cadence, widths):
     return numpy.where(numpy.isfinite(x), index, -1)
 
 
-def _with_noise(records, profile, cadence):
-    """The peaks plus noise_width (the profile width nearest duration_days / cadence, the smaller one on a tie), noise_sigma
-    (robust at that width) and noise_mes = depth_mean * sqrt(transit_count) / noise_sigma; NaN, and noise_width -1, where
-    status != 0 or noise_sigma is NaN."""
-    out = numpy.zeros(records.shape, dtype=records.dtype.descr + [("noise_width", "f8"), ("noise_sigma", "f8"), ("noise_mes", "f8")])
-    for k in records.dtype.names:
-        out[k] = records[k]
+def _noise_block(records, profile, cadence):
+    """noise_width (the profile width nearest duration_days / cadence, the smaller one on a tie), noise_sigma (robust at that
+    width) and noise_mes = depth_mean * sqrt(transit_count) / noise_sigma of the peaks `records`; NaN, and noise_width -1,
+    where status != 0 or noise_sigma is NaN."""
+    out = numpy.zeros(records.shape, dtype=[("noise_width", "f8"), ("noise_sigma", "f8"), ("noise_mes", "f8")])
     index = noise_width_index(records["duration_days"], cadence, profile["widths"])
     curve = numpy.arange(records.shape[0])[:, None]
     sigma = numpy.where(index >= 0, profile["robust"][curve, numpy.maximum(index, 0)], numpy.nan)
@@ -2839,6 +2705,82 @@ def _with_noise(records, profile, cadence):
     return out
 
 
+def _with_noise(records, profile, cadence):
+    """The peaks plus noise_width, noise_sigma and noise_mes (_noise_block)."""
+    return _joined(records, _noise_block(records, profile, cadence))
+
+
+def _peak_noise(ctx, env, request):
+    """noise_curves, noise_count, noise_robust and noise_rms of a slice of the batch, on ctx: the profile of the rows that
+    were searched."""
+    names = ("noise_curves", "noise_count", "noise_robust", "noise_rms")
+    return dict(zip(names, ctx.noise_profile(env.inp["t"], env.y_rows, request["widths"], request["span_max"],
+                                             request["pair_span"], NOISE_CLIP, NOISE_CLIP, NOISE_MIN_COUNT)))
+
+
+def _peak_noise_dict(out, request):
+    """The `noise` entry of the peaks dict: what noise_profile returns, from the joined arrays of _peak_noise."""
+    return dict(noise=dict(widths=request["widths"], curves=out["noise_curves"], count=out["noise_count"],
+                           robust=out["noise_robust"], rms=out["noise_rms"],
+                           beta=_noise_beta(out["noise_robust"], request["widths"], out["noise_curves"]["sigma"])))
+
+
+# ---- the peak stages: every follow-up of power_batch(peaks=K, peak_fits=True), in the order of their field groups in `peaks` ----
+# name: the power_batch keyword and the key of _power_batch's `stages`; keywords: the power_batch arguments `request` takes,
+# in order; request: None, or the checked request; scope: "slice" -- run(ctx, env,
+# request) for every device's slice inside its call, env a _PeakSlice -- or "batch" -- once behind the join, on the first
+# context under its lock; run returns the stage's arrays by name, which are joined across the slices; block(out, request,
+# records): the stage's own fields [n_curves, K] from the joined arrays `out`, records being the peaks with their fits (and
+# scans); extras(out, request): what the stage adds to the peaks dict.
+_PeakStage = collections.namedtuple("_PeakStage", ("name", "keywords", "request", "scope", "run", "block", "extras"))
+
+
+def _no_extras(out, request):
+    return {}
+
+
+_PEAK_STAGES = (
+    _PeakStage("transit_times", ("transit_times", "peak_fits", "transit_times_search", "transit_times_min_ses"),
+               _transit_times_request, "slice", _peak_transit_times,
+               lambda out, request, records: _with_ephemeris(None, out["tt_ephemeris"]),
+               lambda out, request: dict(transit_times=_with_oc(out["tt_ephemeris"], out["tt_times"]))),
+    _PeakStage("shape_fit", ("shape_fit", "peak_fits", "shape_fit_window", "shape_fit_min_count"),
+               _shape_fit_request, "slice", _peak_shape_fits,
+               lambda out, request, records: _with_shapes(None, out["shape_fits"], records["period"]), _no_extras),
+    _PeakStage("sine_test", ("sine_test", "peak_fits", "sine_test_mask", "sine_test_harmonics"),
+               _sine_test_request, "slice", _peak_sine_tests,
+               lambda out, request, records: _with_sines(None, out["sine_tests"], out["sine_harmonics"]), _no_extras),
+    _PeakStage("ephemeris_match", ("ephemeris_match", "peak_fits", "ephemeris_match_drift", "ephemeris_match_epoch",
+                                   "ephemeris_match_max_ratio"),
+               _ephemeris_match_request, "batch", _peak_matches,
+               lambda out, request, records: _with_matches(None, out["matches"]), _no_extras),
+    _PeakStage("views", ("views", "peak_fits", "views_global_bins", "views_local_bins", "views_local_durations",
+                         "views_local_width"),
+               _views_request, "slice", _peak_views,
+               lambda out, request, records: _with_views(None, out["views_records"]), _peak_views_dict),
+    _PeakStage("event_vetting", ("event_vetting", "peak_fits", "event_vetting_search", "event_vetting_chase_window",
+                                 "event_vetting_guard", "event_vetting_min_ses", "event_vetting_chase_fraction",
+                                 "event_vetting_chase_min", "event_vetting_point_fraction", "event_vetting_step_fraction"),
+               _event_vetting_request, "slice", _peak_event_vetting,
+               lambda out, request, records: _with_events(None, out["ev_summaries"]),
+               lambda out, request: dict(events=out["ev_events"])),
+    _PeakStage("centroids", ("centroids", "peak_fits", "flux_batch", "centroid_window", "centroid_min_in", "centroid_min_out"),
+               lambda centroids, peak_fits, flux_batch, *options: _centroid_request(centroids, peak_fits,
+                                                                                   numpy.shape(flux_batch), *options),
+               "slice", _peak_centroid_tests,
+               lambda out, request, records: _with_centroids(None, out["centroid_tests"]), _no_extras),
+    _PeakStage("noise", ("noise", "peak_fits", "t"), _noise_request, "slice", _peak_noise,
+               lambda out, request, records: _noise_block(records, dict(widths=request["widths"], robust=out["noise_robust"]),
+                                                          request["cadence"]), _peak_noise_dict),
+    _PeakStage("transit_fit", ("transit_fit", "peak_fits", "t", "power_kwargs"), _transit_fit_request, "slice",
+               lambda ctx, env, request: dict(transit_fits=_peak_transit_fits(ctx, env.inp, env.y_rows, env.dy_rows, env.peaks,
+                                                                              env.fits, request)),
+               lambda out, request, records: _with_transit_fits(None, out["transit_fits"], records["period"], records["T0"]),
+               _no_extras),
+)
+
+
+# ---- injection-recovery ---------------------------------------------------------------------------------------------------
 INJECTION_FIELDS = ("T0", "period", "rp_rs", "a", "inc")
 INJECTION_LAWS = ("quadratic", "linear", "uniform")
 
