@@ -41,7 +41,7 @@ extern "C" {
  * tls_debug_peak_phase_scans), (7: tls_sysrem), (7: tls_single_transits), (7: tls_transit_times),
  * (7: tls_shape_fit), (7: tls_nudft, tls_lomb_scargle, tls_sine_test); 8: every entry that takes `root, n_root` takes a
  * second table, `root, root_count, n_root`), (8: tls_ephemeris_match), (8: tls_folded_views),
- * (8: tls_event_vetting), (8: tls_centroid_test), (8: tls_noise_profile), (8: tls_transit_fit). */
+ * (8: tls_event_vetting), (8: tls_centroid_test), (8: tls_noise_profile), (8: tls_transit_fit), (8: tls_remove_transits). */
 #define TLS_AMD_ABI_VERSION 8
 
 #define TLS_OK 0
@@ -1276,6 +1276,36 @@ int tls_transit_fit(tls_ctx *ctx, const double *t, const double *y, const double
                     int64_t M, const double *impact, int64_t n_b, const double *ratio, int64_t n_t, const double *shift,
                     int64_t n_s, const double *sub, int64_t n_sub, double window, int64_t min_count, double delta,
                     tls_transit_fit_record *out_records /* [n_fits] */);
+
+/* The multi-planet search of survey mode: the fitted transits of a batch divided out, so that the next tls_power_batch on
+ * the quotient finds the planet under the one found.  The time stamps stay shared -- no point is deleted.  Candidate f
+ * (curve[f] in [0, n_curves), or curve NULL: candidate f belongs to curve f) carries period[f] and T0[f] of a peak and
+ * row[f], amplitude[f], b[f], duration[f], shift[f] of its tls_transit_fit_record (row, amplitude, b, duration, shift), with
+ * the k_rows, profile and sub that fit was made with.  Its constants, one IEEE double operation a step, no contraction:
+ *   e1 = 1.0 + k_rows[row];  e2 = e1 * e1;  sM = M / e1;  bb = b * b;  cc = e2 - bb;  rh = 1.0 / (0.5 * duration)
+ * It takes part (out_status[f] = 0) iff period, T0, amplitude, b, duration and shift are finite, period > 0, duration > 0,
+ * amplitude > 0, b >= 0, bb < e2 and amplitude * (the largest profile[row][m]) < 1.0; any other is skipped (out_status[f] =
+ * 1) and changes nothing.  For every point i of a curve, the candidates of that curve that take part in ascending f:
+ *   x = (t[i] - T0) / period;  k = floor(x + 0.5);  tau = (x - k) * period
+ *   acc = 0.0;  for s = 0 .. S - 1:  ts = tau + sub[s];  v = (ts - shift) * rh;  vv = v * v;  zz = bb + cc * vv
+ *     sample = 0.0 unless zz < e2, else  z = sqrt(zz);  q = z * sM;  m = min(floor(q), M - 1);  fr = q - m
+ *     sample = p[m] + (p[m + 1] - p[m]) * fr;  acc = acc + sample
+ *   mval = acc / S;  where mval > 0:  mod = 1.0 - amplitude * mval;  y[i] = y[i] / mod;  model[i] = model[i] * mod
+ * model starts at 1.0; a point no candidate touches comes back bit for bit.  These are the sub-samples of tls_transit_fit,
+ * operation for operation, so mval at a fit's members is that fit's own, and the result equals the Python statement in
+ * tests/remove_transits_spec.py bit for bit.  out_rows [n_curves][n] (may be y itself), out_model [n_curves][n] (may be NULL),
+ * out_status [n_fits].  Needs no plan and leaves a prepared plan as it is.  n_fits == 0 copies the rows.  The rows are
+ * processed in slabs, so device memory stays bounded for any n_curves.  TLS_E_ARG, before any device work and with the
+ * outputs untouched, for a curve[f] outside [0, n_curves), a row[f] outside [0, n_k), n outside [1, 1e8], negative counts,
+ * n_k outside [1, TLS_TRANSIT_FIT_MAX_ROWS], M outside [1, TLS_TRANSIT_FIT_MAX_M], n_sub outside [1, TLS_TRANSIT_FIT_MAX_SUB],
+ * a k_rows that is not finite, non-decreasing and > 0, a sub or profile that is not finite, and a t that is not finite and
+ * non-decreasing.  y is taken as it is. */
+int tls_remove_transits(tls_ctx *ctx, const double *t, const double *y, int64_t n, int64_t n_curves, const int64_t *curve,
+                        const double *period, const double *T0, const int64_t *row, const double *amplitude, const double *b,
+                        const double *duration, const double *shift, int64_t n_fits, const double *k_rows,
+                        const double *profile, int64_t n_k, int64_t M, const double *sub, int64_t n_sub,
+                        double *out_rows /* [n_curves][n] */, double *out_model /* [n_curves][n], may be NULL */,
+                        double *out_status /* [n_fits] */);
 
 /* ---- host-only planning (no GPU needed) ------------------------------------------ */
 /* Trial cells (duration x T0 positions) each period will enumerate: the data-independent

@@ -118,6 +118,7 @@ SYMBOLS = (
     "tls_ephemeris_match", "tls_folded_views", "tls_event_vetting", "tls_centroid_test", "tls_noise_profile",
     "tls_transit_fit",
     "tls_transit_mask", "tls_biweight_detrend_masked", "tls_prewhiten_masked",
+    "tls_remove_transits",
     "tls_comm_unique_id", "tls_comm_init", "tls_comm_destroy", "tls_comm_info", "tls_comm_allgather_results", "tls_comm_allgather_device", "tls_comm_fetch_gathered",
     "tls_comm_stage_results", "tls_comm_allgather_staged", "tls_comm_fetch_staged",
     "tls_comm_barrier", "tls_comm_max",
@@ -1336,6 +1337,10 @@ def load():
     lib.tls_prewhiten_masked.argtypes = [vp, _c_double_p, _c_double_p, _c_double_p, u8p, i64, i64, _c_double_p, i64, i64, i64, dbl,
                                          _c_double_p, _c_double_p, ctypes.c_void_p, _c_int64_p, _c_double_p, _c_double_p,
                                          _c_double_p]
+    lib.tls_remove_transits.restype = ci
+    lib.tls_remove_transits.argtypes = [vp, _c_double_p, _c_double_p, i64, i64, _c_int64_p, _c_double_p, _c_double_p, _c_int64_p,
+                                        _c_double_p, _c_double_p, _c_double_p, _c_double_p, i64, _c_double_p, _c_double_p, i64,
+                                        i64, _c_double_p, i64, _c_double_p, _c_double_p, _c_double_p]
     lib.tls_noise_profile.restype = ci
     lib.tls_noise_profile.argtypes = [vp, _c_double_p, _c_double_p, i64, i64, _c_int64_p, _c_double_p, i64, dbl, dbl, dbl, i64,
                                       ctypes.c_void_p, _c_int64_p, _c_double_p, _c_double_p]
@@ -1556,6 +1561,68 @@ def transit_mask_arguments(t, period, T0, duration, curve=None, n_curves=None, f
     if isinstance(factor, (bool, numpy.bool_)) or not isinstance(factor, numbers.Real) or not (0.0 < float(factor) < numpy.inf):
         raise ValueError("transit mask: factor must be finite and > 0, got %r" % (factor,))
     return dict(t=t, period=period, T0=T0, duration=duration, curve=curve, n_curves=n_curves, factor=float(factor))
+
+
+REMOVE_TRANSITS_FIELDS = ("period", "T0", "fit_row", "fit_amplitude", "fit_b", "fit_duration", "fit_shift")
+
+
+def remove_transits_arguments(t, y, period, T0, row, amplitude, b, duration, shift, k_rows, profile, sub, curve=None):
+    """What tls_remove_transits takes, checked as it checks them and packed for it -- a dict with t [n] (n in [1, 1e8], finite
+    and non-decreasing), y [n_curves, n] (one row [n] serves one curve), period, T0, amplitude, b, duration, shift [n_fits]
+    (any values: a candidate that cannot take part is skipped), row [n_fits] whole numbers in [0, nK) (integers, or the doubles
+    of a transit-fit record; a NaN row belongs to a candidate that is skipped and is sent as row 0), curve [n_fits] int64 in
+    [0, n_curves) (None: candidate f belongs to curve f) and k_rows, profile, sub as transit_fit_tables checks them.
+    ValueError otherwise.  GPU-free."""
+    what = "remove transits: "
+    try:
+        tables = transit_fit_tables(k_rows, profile, [0.0], [1.0], [0.0], sub)
+    except ValueError as e:
+        raise ValueError(str(e).replace("transit fit: ", what))
+    k_rows, profile, sub = tables[0], tables[1], tables[5]
+    try:
+        t = numpy.ascontiguousarray(numpy.asarray(t, dtype=numpy.float64))
+        y = numpy.asarray(y, dtype=numpy.float64)
+        columns = [numpy.ascontiguousarray(numpy.atleast_1d(numpy.asarray(v, dtype=numpy.float64)))
+                   for v in (period, T0, amplitude, b, duration, shift)]
+    except (TypeError, ValueError):
+        raise ValueError(what + "t, y and the candidates' columns must hold numbers")
+    if y.ndim == 1:
+        y = y[None, :]
+    if t.ndim != 1 or y.ndim != 2 or y.shape[1] != len(t) or not 1 <= len(t) <= 100000000:
+        raise ValueError(what + "y must be [n] or [n_curves, n] over the time stamps t [n] with n in [1, 1e8], got %s over %s"
+                         % (y.shape, t.shape))
+    if not numpy.all(numpy.isfinite(t)) or not numpy.all(t[1:] >= t[:-1]):
+        raise ValueError(what + "t must be finite and non-decreasing")
+    n_fits = len(columns[0])
+    if any(v.ndim != 1 or len(v) != n_fits for v in columns):
+        raise ValueError(what + "period, T0, amplitude, b, duration and shift must have one shape [n_fits], got %s"
+                         % ([v.shape for v in columns],))
+    rows = numpy.atleast_1d(numpy.asarray(row))
+    if rows.shape != (n_fits,) or (n_fits and rows.dtype.kind not in "iuf"):
+        raise ValueError(what + "row must hold one row in [0, %d) a candidate" % len(k_rows))
+    if rows.dtype.kind == "f":
+        with numpy.errstate(all="ignore"):
+            known = numpy.isfinite(rows)
+            if not numpy.all(rows[known] == numpy.floor(rows[known])) or not numpy.all(numpy.abs(rows[known]) < 2.0 ** 31):
+                raise ValueError(what + "row must hold one row in [0, %d) a candidate" % len(k_rows))
+            columns[2] = numpy.where(known, columns[2], numpy.nan)       # (no row: no candidate)
+            rows = numpy.where(known, rows, 0.0)
+    rows = numpy.ascontiguousarray(rows, dtype=numpy.int64)
+    if n_fits and (rows.min() < 0 or rows.max() >= len(k_rows)):
+        raise ValueError(what + "row must hold one row in [0, %d) a candidate" % len(k_rows))
+    if curve is None:
+        if n_fits > y.shape[0]:
+            raise ValueError(what + "curve out of range [0, n_curves = %d)" % y.shape[0])
+    else:
+        curve = numpy.asarray(curve)
+        if curve.shape != (n_fits,) or (n_fits and curve.dtype.kind not in "iu"):
+            raise ValueError(what + "curve must hold %d integers, got shape %s dtype %s" % (n_fits, curve.shape, curve.dtype))
+        curve = numpy.ascontiguousarray(curve, dtype=numpy.int64)
+        if n_fits and not (0 <= curve.min() and curve.max() < y.shape[0]):
+            raise ValueError(what + "curve out of range [0, n_curves = %d)" % y.shape[0])
+    names = ("period", "T0", "amplitude", "b", "duration", "shift")
+    return dict(dict(zip(names, (numpy.ascontiguousarray(v) for v in columns))), t=t, y=numpy.ascontiguousarray(y), row=rows,
+                curve=curve, k_rows=k_rows, profile=profile, sub=sub)
 
 
 def _sysrem_integer(name, value, low, high, what):
@@ -2484,6 +2551,29 @@ class Context(object):
         if numpy.ndim(y) == 1:
             flat, trend = flat[0], None if trend is None else trend[0]
         out = (flat,) + ((trend,) if return_trend else ()) + ((info,) if return_terms or debug else ())
+        return out[0] if len(out) == 1 else out
+
+    def remove_transits(self, t, y, period, T0, row, amplitude, b, duration, shift, k_rows, profile, sub, curve=None,
+                        return_model=False, return_status=False):
+        """The rows y [n_curves, n] (or one row) over t [n] with the fitted transits of the candidates divided out
+        (tls_remove_transits; the statement: include/tls_amd.h, tests/remove_transits_spec.py): candidate f carries period[f]
+        and T0[f] of a peak and row[f], amplitude[f], b[f], duration[f], shift[f] of its transit-fit record on the curve
+        curve[f] (None: one candidate a curve, in order), with the k_rows, profile and sub of that fit.  rows[, model][, status
+        float64 [n_fits]: 0 divided out, 1 skipped].  ValueError for what remove_transits_arguments refuses."""
+        a = remove_transits_arguments(t, y, period, T0, row, amplitude, b, duration, shift, k_rows, profile, sub, curve)
+        n_c, n = a["y"].shape
+        n_fits = len(a["period"])
+        rows = numpy.empty_like(a["y"])
+        model = numpy.empty_like(a["y"]) if return_model else None
+        status = numpy.zeros(n_fits)
+        self._check(self._lib.tls_remove_transits(
+            self._h, _dp(a["t"]), _dp(a["y"]), n, n_c, None if a["curve"] is None else _ip(a["curve"]), _dp(a["period"]),
+            _dp(a["T0"]), _ip(a["row"]), _dp(a["amplitude"]), _dp(a["b"]), _dp(a["duration"]), _dp(a["shift"]), n_fits,
+            _dp(a["k_rows"]), _dp(a["profile"]), len(a["k_rows"]), a["profile"].shape[1] - 1, _dp(a["sub"]), len(a["sub"]),
+            _dp(rows), None if model is None else _dp(model), _dp(status)))
+        if numpy.ndim(y) == 1:
+            rows, model = rows[0], None if model is None else model[0]
+        out = (rows,) + ((model,) if return_model else ()) + ((status,) if return_status else ())
         return out[0] if len(out) == 1 else out
 
     def debug_null_words(self, n, n_rows, seed, first_trial=0, block=None):

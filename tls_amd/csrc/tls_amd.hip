@@ -251,7 +251,8 @@ struct tls_ctx {
     DevBuf<double> d_detrend;       // tls_medfilt_detrend, tls_biweight_detrend: rows | flat rows | trend rows of one slab
     DevBuf<int> d_windows;          // tls_biweight_detrend: lo [n] | hi [n], the window of every point
     // tls_transit_mask: t | period | T0 | duration of the candidates grouped by curve | their offsets [n_curves + 1] (64-bit
-    // words); tls_biweight_detrend_masked: t
+    // words); tls_biweight_detrend_masked: t; tls_remove_transits: t | the grouped candidates with their constants | their
+    // offsets | profile | sub; of one slab: rows | models
     DevBuf<double> d_protect;
     // tls_transit_mask: the mask rows of one slab; tls_biweight_detrend_masked: mask | open marks | status rows of one slab;
     // tls_prewhiten_masked: the mask rows of one slab
@@ -2793,6 +2794,124 @@ int tls_transit_mask(tls_ctx* ctx, const double* t, int64_t n, const int64_t* cu
         ctx->last_kernel = "tls_transit_mask";
         TLS_HIP(ctx, hipMemcpyAsync(out_mask + c0 * nn, ctx->d_protect_bytes.ptr, curves * nn, hipMemcpyDeviceToHost, main_stream(ctx)));
         // (the next slab overwrites the device rows, and the sorted candidates live on this stack)
+        TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));
+    }
+    return TLS_OK;
+}
+
+// ---- the fitted transits of a batch divided out (tls_remove.hip.h, DESIGN.md "Multi-planet search")
+static_assert(sizeof(tlsdev::RemoveCandidate) == tlsdev::kRemoveWords * 8, "a grouped candidate is kRemoveWords doubles");
+
+int tls_remove_transits(tls_ctx* ctx, const double* t, const double* y, int64_t n, int64_t n_curves, const int64_t* curve,
+                        const double* period, const double* T0, const int64_t* row, const double* amplitude, const double* b,
+                        const double* duration, const double* shift, int64_t n_fits, const double* k_rows, const double* profile,
+                        int64_t n_k, int64_t M, const double* sub, int64_t n_sub, double* out_rows, double* out_model,
+                        double* out_status) {
+#pragma clang fp contract(off)
+    if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
+    const std::string what = "remove transits";
+    if (n_fits < 0 || n_curves < 0 || n < 0) return fail(ctx, TLS_E_ARG, what + ": negative count");
+    if (n_k < 1) return fail(ctx, TLS_E_ARG, what + ": every table needs an entry");
+    if (n_k > TLS_TRANSIT_FIT_MAX_ROWS) return fail(ctx, TLS_E_ARG, what + ": more than 4096 profile rows");
+    if (M < 1 || M > TLS_TRANSIT_FIT_MAX_M) return fail(ctx, TLS_E_ARG, what + ": M out of range [1, 4096]");
+    if (n_sub < 1 || n_sub > TLS_TRANSIT_FIT_MAX_SUB) return fail(ctx, TLS_E_ARG, what + ": n_sub out of range [1, 16]");
+    if (!k_rows || !profile || !sub) return fail(ctx, TLS_E_ARG, what + ": null argument");
+    for (int64_t i = 0; i < n_k; ++i)
+        if (!std::isfinite(k_rows[i]) || (i > 0 && k_rows[i] < k_rows[i - 1]))
+            return fail(ctx, TLS_E_ARG, what + ": the tables must be finite and non-decreasing");
+    if (!(k_rows[0] > 0.0)) return fail(ctx, TLS_E_ARG, what + ": every k_rows must be > 0");
+    for (int64_t s = 0; s < n_sub; ++s)
+        if (!std::isfinite(sub[s])) return fail(ctx, TLS_E_ARG, what + ": sub must be finite");
+    for (int64_t i = 0; i < n_k * (M + 1); ++i)
+        if (!std::isfinite(profile[i])) return fail(ctx, TLS_E_ARG, what + ": the profile must be finite");
+    if (n_fits > 0 && (!period || !T0 || !row || !amplitude || !b || !duration || !shift || !out_status))
+        return fail(ctx, TLS_E_ARG, what + ": null argument");
+    if (n_curves > 0 && (!t || !y || !out_rows)) return fail(ctx, TLS_E_ARG, what + ": null argument");
+    int rc;
+    if (n_curves > 0 || n_fits > 0) {
+        if ((rc = check_batch(ctx, what, n, 100000000, "[1, 1e8]", n_fits, n_curves))) return rc;
+        if (n_curves > 0 && (rc = check_time_stamps(ctx, what, t, n))) return rc;
+    }
+    if ((rc = check_curves(ctx, what, curve, n_fits, n_curves, [&](int64_t f) {
+            if (row[f] < 0 || row[f] >= n_k) return fail(ctx, TLS_E_ARG, what + ": row out of range [0, n_k)");
+            return (int)TLS_OK;
+        })))
+        return rc;
+    if (n_curves == 0) return TLS_OK;
+    const size_t nc = (size_t)n_curves, nn = (size_t)n, row_words = (size_t)M + 1;
+    // the candidates that take part, with their constants, grouped by curve in their order (a stable counting sort)
+    std::vector<tlsdev::RemoveCandidate> made((size_t)n_fits);
+    std::vector<long long> offset(nc + 1, 0);
+    for (int64_t f = 0; f < n_fits; ++f) {
+        const double P = period[f], A = amplitude[f], bf = b[f], T = duration[f];
+        const double* p = profile + (size_t)row[f] * row_words;
+        double deepest = p[0];
+        for (size_t m = 1; m < row_words; ++m) deepest = std::max(deepest, p[m]);
+        const double e1 = 1.0 + k_rows[row[f]];
+        const double e2 = e1 * e1;
+        const double sM = (double)M / e1;
+        const double bb = bf * bf;
+        const double cc = e2 - bb;
+        const double hT = 0.5 * T;
+        const double rh = 1.0 / hT;
+        const double dip = A * deepest;
+        const bool takes_part = std::isfinite(P) && std::isfinite(T0[f]) && std::isfinite(A) && std::isfinite(bf) && std::isfinite(T)
+                                && std::isfinite(shift[f]) && P > 0.0 && T > 0.0 && A > 0.0 && bf >= 0.0 && bb < e2 && dip < 1.0;
+        out_status[f] = takes_part ? 0.0 : 1.0;
+        made[(size_t)f] = tlsdev::RemoveCandidate{P, T0[f], A, shift[f], bb, cc, rh, e2, sM, (double)row[f]};
+        if (takes_part) ++offset[(size_t)(curve ? curve[f] : f) + 1];
+    }
+    for (size_t c = 0; c < nc; ++c) offset[c + 1] += offset[c];
+    const size_t m = (size_t)offset[nc];
+    if (m == 0) {                                    // nothing to divide out: the rows as they are
+        if (out_rows != y) std::memcpy(out_rows, y, nc * nn * 8);
+        if (out_model) std::fill(out_model, out_model + nc * nn, 1.0);
+        return TLS_OK;
+    }
+    std::vector<tlsdev::RemoveCandidate> sorted(m);
+    {
+        std::vector<long long> at(offset.begin(), offset.end() - 1);
+        for (int64_t f = 0; f < n_fits; ++f)
+            if (out_status[f] == 0.0) sorted[(size_t)at[(size_t)(curve ? curve[f] : f)]++] = made[(size_t)f];
+    }
+    TLS_HIP(ctx, hipSetDevice(ctx->device));
+    static_assert(sizeof(long long) == sizeof(double), "the offsets lie in a buffer of doubles");
+    // curves per launch: at most 256 MB of rows and models
+    const size_t slab = std::max<size_t>(1, std::min<size_t>(nc, ((size_t)256 << 20) / (16 * nn)));
+    const size_t words = tlsdev::kRemoveWords, table = (size_t)n_k * row_words;
+    // t | the grouped candidates | their offsets | profile | sub; of one slab: rows | models -- all of it written here or by
+    // the kernel in front of every read
+    TLS_HIP(ctx, ctx->d_protect.reserve(nn + words * m + nc + 1 + table + (size_t)n_sub + 2 * slab * nn));
+    double* d_t = ctx->d_protect.ptr;
+    double* d_cand = d_t + nn;
+    long long* d_offset = reinterpret_cast<long long*>(d_cand + words * m);
+    double* d_profile = d_cand + words * m + nc + 1;
+    double* d_sub = d_profile + table;
+    double* d_rows = d_sub + n_sub;
+    double* d_model = d_rows + slab * nn;
+    if ((rc = ensure_check_counters(ctx))) return rc;
+    const size_t lds = row_words * 8;
+    TLS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(tlsdev::tls_remove_transits_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_cand, sorted.data(), words * m * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_offset, offset.data(), (nc + 1) * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_profile, profile, table * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_sub, sub, (size_t)n_sub * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    for (size_t c0 = 0; c0 < nc; c0 += slab) {
+        const size_t curves = std::min(slab, nc - c0);
+        tlsdev::RemoveArgs a;
+        a.t = d_t; a.cand = reinterpret_cast<const tlsdev::RemoveCandidate*>(d_cand); a.offset = d_offset + c0;
+        a.profile = d_profile; a.sub = d_sub; a.rows = d_rows; a.model = out_model ? d_model : nullptr; a.check = ctx->d_check.ptr;
+        a.n = (long long)n; a.tiles_per_curve = (long long)((nn + tlsdev::kRemoveThreads - 1) / tlsdev::kRemoveThreads);
+        a.tiles = (long long)curves * a.tiles_per_curve; a.nK = (int)n_k; a.M = (int)M; a.S = (int)n_sub;
+        TLS_HIP(ctx, hipMemcpyAsync(d_rows, y + c0 * nn, curves * nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+        const unsigned blocks = (unsigned)std::min<long long>(a.tiles, 65536);
+        hipLaunchKernelGGL(tlsdev::tls_remove_transits_kernel, dim3(blocks), dim3(tlsdev::kRemoveThreads), lds, main_stream(ctx), a);
+        TLS_HIP(ctx, hipGetLastError());
+        ctx->last_kernel = "tls_remove_transits";
+        TLS_HIP(ctx, hipMemcpyAsync(out_rows + c0 * nn, d_rows, curves * nn * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+        if (out_model) TLS_HIP(ctx, hipMemcpyAsync(out_model + c0 * nn, d_model, curves * nn * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+        // (the next slab overwrites the device rows, and the grouped candidates live on this stack)
         TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));
     }
     return TLS_OK;

@@ -4442,6 +4442,8 @@ __global__ void __launch_bounds__(512) tls_transit_models(const ModelsArgs a) {
 // survey-mode trapezoid shape fit (tls_shape_fit)
 #include "tls_shape.hip.h"
 #include "tls_transit_fit.hip.h"
+// survey-mode multi-planet search: the fitted transits of a batch divided out (tls_remove_transits)
+#include "tls_remove.hip.h"
 // survey-mode centroid-shift test of a candidate (tls_centroid_test)
 #include "tls_centroid.hip.h"
 // survey-mode folded, median-binned views of a candidate (tls_folded_views)

@@ -1123,6 +1123,230 @@ def power_batch_protected(t, flux_batch, detrend, sde_min, factor=1.5, n_peaks=1
     return result, dict(protected=protected, mask=mask, summary=summary)
 
 
+# ---- multi-planet search: the fitted transits divided out, the quotient searched again ------------------------------------
+def remove_transits(t, flux_batch, planets, curve=None, exposure=None, n_sub=5, profile=None, return_model=False,
+                    return_status=False, context=None, device=None, devices=None, **template_kwargs):
+    """flux_batch [n_curves, n] (or one row [n]) over the shared, ascending time stamps t with the fitted transits of
+    `planets` divided out, on the device (tls_remove_transits): the limb-darkened, exposure-integrated model transit_fit fits
+    is evaluated at EVERY point of the planet's curve, y = y / (1 - A * mval) wherever the model dips (flux is multiplicative),
+    and every other point comes back bit for bit.  No point is deleted, so the rows keep their shared time stamps and the
+    next search is an ordinary power_batch on the result -- the planet under the one found (power_batch_multi is that flow
+    in one call).  The statement is in tests/remove_transits_spec.py and include/tls_amd.h, and the device equals it bit for
+    bit.
+
+    planets: a structured array with the fields period, T0, fit_row, fit_amplitude, fit_b, fit_duration, fit_shift -- a
+    `peaks` array of power_batch(..., transit_fit=True) or what transit_fit returns with period and T0 beside it.  curve
+    [n_fits]: the curve of every planet, flattened; None: planets [n_curves, K] are the planets of curve 0, 1, ... row by row,
+    planets [n_fits] one a curve, in order.  The planets of a curve are divided out in their order.  A planet takes part
+    (status 0) iff its seven values are finite, period, fit_duration and fit_amplitude > 0, fit_b in [0, 1 + k_rows[fit_row])
+    and fit_amplitude times the deepest entry of its profile row < 1; any other is skipped (status 1) -- the NaN records of
+    an unfitted peak among them.
+
+    exposure, n_sub, profile and the template keywords (u, limb_dark, transit_template) mean what they mean for transit_fit,
+    and must be the fit's own for the model to be the fitted one.  ValueError, before any device work, for what
+    _lib.remove_transits_arguments and the set-up of transit_fit refuse.
+
+    Returns rows[, model][, status]: rows and model (the product of the factors 1 - A * mval, 1.0 elsewhere) in flux_batch's
+    shape, status float64 in planets' shape."""
+    from ._lib import REMOVE_TRANSITS_FIELDS, remove_transits_arguments
+    what = "remove transits: "
+    one_row = numpy.ndim(flux_batch) == 1
+    t, flux_batch, _ = _candidate_rows("remove transits", t, flux_batch)
+    try:
+        setup = _transit_fit_setup(t, None, None, None, exposure, n_sub, 1.0, 3, 1.0, profile, template_kwargs)
+    except ValueError as e:
+        raise ValueError(str(e).replace("transit fit: ", what))
+    planets = numpy.asarray(planets)
+    if planets.dtype.names is None or any(k not in planets.dtype.names for k in REMOVE_TRANSITS_FIELDS):
+        raise ValueError(what + "planets must be a structured array with the fields %s" % (REMOVE_TRANSITS_FIELDS,))
+    n_curves = numpy.shape(flux_batch)[0]
+    if curve is None:
+        if planets.ndim == 2 and planets.shape[0] == n_curves:
+            curve = numpy.repeat(numpy.arange(n_curves, dtype=numpy.int64), planets.shape[1])
+        elif planets.ndim != 1 or planets.shape[0] > n_curves:
+            raise ValueError(what + "without curve, planets must be [n_curves, K] or hold at most one a curve, got shape %s "
+                             "for %d curves" % (planets.shape, n_curves))
+    elif numpy.shape(curve) != (planets.size,):
+        raise ValueError(what + "curve must hold one index a planet, flattened: %d, got shape %s"
+                         % (planets.size, numpy.shape(curve)))
+    flat = planets.reshape(-1)
+    a = remove_transits_arguments(t, flux_batch, flat["period"], flat["T0"], flat["fit_row"], flat["fit_amplitude"],
+                                  flat["fit_b"], flat["fit_duration"], flat["fit_shift"], setup["k_rows"], setup["profile"],
+                                  setup["sub"], curve)
+    of_curve = numpy.arange(len(flat), dtype=numpy.int64) if a["curve"] is None else a["curve"]
+    names = ("period", "T0", "row", "amplitude", "b", "duration", "shift")
+
+    def call(ctx, lo, hi):
+        mine = numpy.nonzero((of_curve >= lo) & (of_curve < hi))[0]
+        out = ctx.remove_transits(a["t"], a["y"][lo:hi], *(a[k][mine] for k in names), a["k_rows"], a["profile"], a["sub"],
+                                  curve=of_curve[mine] - lo, return_model=return_model, return_status=True)
+        return dict(rows=out[0], model=out[1] if return_model else None, status=out[-1], index=mine)
+
+    out = _run_batch(devices, device, context, n_curves, call)
+    status = numpy.zeros(len(flat))
+    status[out["index"]] = out["status"]
+    rows, model = out["rows"], out["model"]
+    if one_row:
+        rows, model = rows[0], None if model is None else model[0]
+    result = (rows,) + ((model,) if return_model else ()) + ((status.reshape(planets.shape),) if return_status else ())
+    return result[0] if len(result) == 1 else result
+
+
+def is_repeat(period, earlier, separation=0.02, ratios=HARMONICS):
+    """Whether `period` (any shape) repeats the planet found at `earlier` days: the closeness test of the peak selection
+    (find_peaks) against the earlier period and its multiples by `ratios` -- fabs(period - r * earlier) <= separation *
+    (r * earlier) for r = 1 or an r of ratios, c = r * earlier, w = separation * c and period - c one IEEE double operation
+    each.  A NaN repeats nothing."""
+    period = numpy.asarray(period, dtype=numpy.float64)
+    out = numpy.zeros(period.shape, dtype=bool)
+    with numpy.errstate(invalid="ignore", over="ignore"):
+        for r in (1.0,) + tuple(float(x) for x in ratios):
+            c = numpy.float64(r) * numpy.float64(earlier)
+            w = numpy.float64(separation) * c
+            out |= numpy.fabs(period - c) <= w
+    return out
+
+
+# power_batch_multi's pass_status
+PLANET_ACCEPTED, PLANET_NOT_REACHED, PLANET_BELOW_SDE, PLANET_NO_FIT, PLANET_REPEAT = 0, 1, 2, 3, 4
+_SUMMARY_RENAMED = ("period", "T0", "depth", "duration")     # summary fields a peak record has too: summary_period, ...
+
+
+def multi_planet_fields(summary_dtype, peaks_dtype):
+    """The fields [(name, dtype)] of power_batch_multi's planets array: pass_status, the pass's summary fields (period, T0,
+    depth and duration as summary_period, ..., the peak record holds fields of those names) and the fields of its peak
+    record."""
+    fields = [("pass_status", "i8")]
+    fields += [("summary_" + k if k in _SUMMARY_RENAMED else k, summary_dtype[k]) for k in summary_dtype.names]
+    return fields + [(k, peaks_dtype[k]) for k in peaks_dtype.names]
+
+
+def power_batch_multi(t, flux_batch, sde_min, n_planets=3, detrend=None, protect_factor=None, transit_fit=True,
+                      return_rows=False, **power_batch_kwargs):
+    """The multi-planet search in one call: search, divide the fitted transit out of the RAW rows, search the quotient.  A
+    second planet under a deep first one never shows in the first periodogram, so no peak list (peaks=K) returns it; with the
+    first one divided out it is the pick of the next pass.
+
+        pass 0:     power_batch(t, rows, detrend=detrend, peaks=1, peak_fits=True, transit_fit=transit_fit, ...), every curve
+        after every pass, a curve's pick (its peak of rank 0) is ACCEPTED iff its SDE >= sde_min, its peak status and its
+                    fit_status are 0, and its period is no repeat (is_repeat with peak_separation and peak_ratios) of an
+                    earlier accepted planet of that curve
+        pass j + 1: only the curves with an accepted pick that hold fewer than n_planets go on: power_batch as above on
+                    remove_transits(RAW rows of those curves, all their accepted planets in the order found) -- from the raw
+                    rows every time, with the same detrend, so no pass detrends a quotient of a detrended row
+
+    sde_min has no default: sde_threshold (from null_sde's table) chooses it.  n_planets in [1, 8].  transit_fit is True or
+    the dict power_batch takes (the fit is what is divided out, so it cannot be off).  protect_factor (None: off): the
+    detrend_mask of pass j + 1 is transit_mask of the accepted planets (period, T0, duration_days), that many durations
+    wide, so the detrending fits around the transits already found; power_batch's refusal of a median-filter step with a mask
+    stands.  power_batch_kwargs: dy_batch, context, device, devices, peak_separation, peak_ratios, peak_min_power and the
+    search's own keywords, passed on unchanged (dy_batch row by row); any other keyword of power_batch raises ValueError --
+    the rows of return_rows=True go through power_batch for anything else.  ValueError before any device work for a bad
+    argument.
+
+    Returns (planets, info).  planets: a structured array [n_curves, n_planets], entry [c, j] being pass j of curve c --
+    pass_status (0 accepted and divided out, 1 not reached, 2 below sde_min, 3 no fit, 4 a repeat) and, where the pass ran,
+    its summary fields and its peak record with the fit_ fields (multi_planet_fields; NaN and -1 where it did not run).  The
+    accepted entries of a row serve as remove_transits' planets.  info: a dict with `n_found` [n_curves], `searched` (the
+    index array of the curves every pass searched, pass by pass) and with return_rows=True `rows`, flux_batch with every
+    accepted planet divided out."""
+    if isinstance(sde_min, (bool, numpy.bool_)) or not isinstance(sde_min, numbers.Real) or numpy.isnan(sde_min):
+        raise ValueError("power_batch_multi: sde_min must be a number, got %r" % (sde_min,))
+    if isinstance(n_planets, (bool, numpy.bool_)) or not isinstance(n_planets, numbers.Integral) or not 1 <= int(n_planets) <= 8:
+        raise ValueError("power_batch_multi: n_planets must be an integer in [1, 8], got %r" % (n_planets,))
+    n_planets = int(n_planets)
+    if protect_factor is not None:
+        if isinstance(protect_factor, (bool, numpy.bool_)) or not isinstance(protect_factor, numbers.Real) \
+                or not (0.0 < float(protect_factor) < numpy.inf):
+            raise ValueError("power_batch_multi: protect_factor must be None or finite and > 0, got %r" % (protect_factor,))
+        for step in _detrend_steps(detrend):
+            if not isinstance(step, (Biweight, SysRem, Prewhiten)):
+                raise ValueError("power_batch_multi: the median filter (detrend=%r) has no masked form; use Biweight or "
+                                 "Prewhiten steps with protect_factor" % (step,))
+    if transit_fit is None or transit_fit is False:
+        raise ValueError("power_batch_multi: transit_fit must be True or a dict: the fitted transit is what is divided out")
+    keep = {"dy_batch", "context", "device", "devices", "peak_separation", "peak_ratios", "peak_min_power"}
+    named = {k for k, p in inspect.signature(power_batch).parameters.items() if p.kind is p.POSITIONAL_OR_KEYWORD}
+    for k in power_batch_kwargs:
+        if k in named and k not in keep:
+            raise ValueError("power_batch_multi: %s is not passed on to the passes; call power_batch on the rows of "
+                             "return_rows=True" % k)
+    search = {k: v for k, v in power_batch_kwargs.items() if k not in named}
+    rest = {k: v for k, v in power_batch_kwargs.items() if k in keep and k != "dy_batch"}
+    where = {k: power_batch_kwargs.get(k) for k in ("context", "device", "devices")}
+    separation, ratios = power_batch_kwargs.get("peak_separation", 0.02), power_batch_kwargs.get("peak_ratios", HARMONICS)
+    _peaks_request(1, separation, ratios, power_batch_kwargs.get("peak_min_power"), False, True)
+    raw = numpy.asarray(flux_batch, dtype=numpy.float64)
+    if raw.ndim != 2 or raw.shape[1] != len(t) or len(raw) < 1:
+        raise ValueError("flux_batch must have shape [n_curves, len(t)]")
+    dy_batch = power_batch_kwargs.get("dy_batch")
+    if dy_batch is not None:
+        dy_batch = numpy.asarray(dy_batch, dtype=numpy.float64)
+        if dy_batch.shape != raw.shape:
+            raise ValueError("dy_batch must have the shape of flux_batch")
+    setup = _transit_fit_request(transit_fit, True, t, search)
+    # (the passes and remove_transits share ONE profile table: formed once, and the model divided out is the fitted one)
+    fit_options = dict({} if transit_fit is True else transit_fit, profile=(setup["k_rows"], setup["profile"]))
+    removal = dict(where, profile=(setup["k_rows"], setup["profile"]), exposure=fit_options.get("exposure"),
+                   n_sub=fit_options.get("n_sub", 5))
+    n_curves = len(raw)
+    planets, n_found, searched = None, numpy.zeros(n_curves, dtype=numpy.int64), []
+    active = numpy.arange(n_curves)
+    for j in range(n_planets):
+        if len(active) == 0:
+            break
+        rows, mask = raw[active], None
+        if j:
+            found = planets[active, :j]
+            rows = remove_transits(t, rows, found, **removal)
+            if protect_factor is not None:
+                mask = _first_mask(t, found, len(active), j, protect_factor, where)
+        out = power_batch(t, rows, dy_batch=None if dy_batch is None else dy_batch[active], detrend=detrend, detrend_mask=mask,
+                          peaks=1, peak_fits=True, transit_fit=fit_options, **dict(rest, **search))
+        summary, peaks = out[0], out[-1]["peaks"][:, 0]
+        if planets is None:
+            planets = numpy.zeros((n_curves, n_planets), dtype=multi_planet_fields(summary.dtype, peaks.dtype))
+            for k in planets.dtype.names:
+                planets[k] = numpy.nan if planets.dtype[k].kind == "f" else -1
+            planets["pass_status"] = PLANET_NOT_REACHED
+        for k in summary.dtype.names:
+            planets["summary_" + k if k in _SUMMARY_RENAMED else k][active, j] = summary[k]
+        for k in peaks.dtype.names:
+            planets[k][active, j] = peaks[k]
+        with numpy.errstate(invalid="ignore"):
+            status = numpy.where(summary["SDE"] >= sde_min, PLANET_ACCEPTED, PLANET_BELOW_SDE)
+            status[(status == PLANET_ACCEPTED) & ((peaks["status"] != 0) | (peaks["fit_status"] != 0))] = PLANET_NO_FIT
+        for e in range(j):                           # (every earlier entry of a curve that goes on is an accepted planet)
+            for at, c in enumerate(active):
+                if status[at] == PLANET_ACCEPTED and is_repeat(peaks["period"][at], planets["period"][c, e], separation, ratios):
+                    status[at] = PLANET_REPEAT
+        planets["pass_status"][active, j] = status
+        searched.append(active)
+        n_found[active] += status == PLANET_ACCEPTED
+        active = active[status == PLANET_ACCEPTED]
+    info = dict(n_found=n_found, searched=searched)
+    if return_rows:
+        info["rows"] = remove_transits(t, raw, _accepted_only(planets), **removal)
+    return planets, info
+
+
+def _first_mask(t, found, n_active, j, factor, where):
+    """transit_mask of the accepted planets `found` [n_active, j] on the first device of where["devices"]."""
+    from ._lib import transit_mask_arguments
+    a = transit_mask_arguments(t, found["period"].reshape(-1), found["T0"].reshape(-1), found["duration_days"].reshape(-1),
+                               numpy.repeat(numpy.arange(n_active), j), n_active, factor)
+    ctx, lock = _first_context(where["context"], where["device"], where["devices"], n_active)
+    with lock:
+        return ctx.transit_mask(a["t"], a["period"], a["T0"], a["duration"], a["curve"], a["n_curves"], a["factor"])
+
+
+def _accepted_only(planets):
+    """planets with the amplitude of every entry that was not accepted set to NaN: remove_transits skips those."""
+    out = planets.copy()
+    out["fit_amplitude"][out["pass_status"] != PLANET_ACCEPTED] = numpy.nan
+    return out
+
+
 def search_batch(t, flux_batch, dy_batch=None, context=None, device=None, devices=None, detrend=None, detrend_mask=None,
                  **power_kwargs):
     """Search every light curve of `flux_batch` (shape [n_curves, n_points]) on the grids that
