@@ -202,7 +202,8 @@ int tls_debug_poison_lds(tls_ctx *ctx, uint32_t word);
  * tls_search_batch call (a stall in one group -- a transfer, a wait, a T0-fit launch -- shows here; bench.py prints the
  * largest and the median).  Returns the number of groups; out may be NULL. */
 int tls_debug_batch_group_ms(const tls_ctx *ctx, double *out, int64_t capacity);
-/* developer instrumentation: bytes of device memory the context holds, in all and in the final T0 fit's HBM scratch */
+/* developer instrumentation: bytes of device memory the context holds, in all (every device buffer it owns) and in the final
+ * T0 fit's HBM scratch */
 int tls_debug_device_bytes(const tls_ctx *ctx, int64_t *total, int64_t *t0_fit_scratch);
 /* developer instrumentation: the table of folded orders of the held plan (four-slot kernel; switch perm_table) -- its size
  * in bytes as the held plan uses it (0: the plan has none; the buffer behind it only grows and is counted by tls_debug_device_bytes) and whether a launch has filled it (1) or the next four-slot launch will (0); plan_reuses

@@ -1,5 +1,5 @@
 """The coverage of tests/test_stage_memory.py, checked without a GPU: every device buffer of a context is either smeared by
-tls_debug_poison_lds or kept for a reason stated here, every Context method that launches a stage kernel has a case, and the
+tls_debug_poison_lds (its kind where it is declared is scratch) or kept for a reason stated here (state), every Context method that launches a stage kernel has a case, and the
 pairs of cases lie on the two sides of the constants that separate their memory paths.  A stage added without a case, or a
 buffer added without a decision, fails here."""
 import ast
@@ -59,27 +59,36 @@ def _without_comments(text):
     return re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
 
 
-def declared_buffers():
-    """Every DevBuf<...> member of struct tls_ctx, the BatchSlot members apart."""
+def _registered():
+    """{member: kind} of every DevBuf<...> member of struct tls_ctx, the BatchSlot members apart: each is constructed against
+    the context's pool with its own name and its kind, where it is declared."""
     text = _without_comments(open(SOURCE).read())
     body = _braces(text, text.index("struct tls_ctx {"))
     slot = _braces(body, body.index("struct BatchSlot"))
     assert "DevBuf<" in slot
     body = body.replace(slot, "")
-    names = []
+    found = {}
     for members in re.findall(r"DevBuf<[^>]+>\s+([^;]+);", body):
-        names += [m.strip() for m in members.split(",")]
-    assert all(re.fullmatch(r"d_\w+", n) for n in names), names
-    assert len(names) == len(set(names)) and len(names) > 50
-    return set(names)
+        parts = re.findall(r'(\w+)\{pool, "(\w+)", (kScratch|kState)\}', members)
+        assert len(parts) == members.count("{") == members.count("}") == members.count("},") + 1, members   # no bare member
+        for member, name, kind in parts:
+            assert member == name and member not in found, member
+            found[member] = kind
+    assert all(re.fullmatch(r"d_\w+", n) for n in found), sorted(found)
+    assert len(found) > 50
+    return found
+
+
+def declared_buffers():
+    return set(_registered())
 
 
 def smeared_buffers():
+    """tls_debug_poison_lds walks the context's pool and smears the buffers of kind scratch, and those alone."""
     text = _without_comments(open(SOURCE).read())
     body = _braces(text, text.index("int tls_debug_poison_lds(tls_ctx* ctx, uint32_t word)"))
-    names = re.findall(r"smear\(ctx->(\w+)\)", body)
-    assert len(names) == len(set(names)), "a buffer is smeared twice"
-    return set(names)
+    assert "ctx->pool.first" in body and "b->kind == kScratch" in body and "ctx->d_" not in body
+    return {name for name, kind in _registered().items() if kind == "kScratch"}
 
 
 def test_every_device_buffer_is_smeared_or_kept_for_a_reason():

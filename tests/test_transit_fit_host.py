@@ -329,7 +329,7 @@ def test_header_binding_and_library_declare_the_entry():
     assert "tls_transit_fit.hip.h" in re.search(r"^HDR = (.*)$", makefile, flags=re.M).group(1)
     assert hasattr(_lib.Context, "transit_fit") and callable(_lib.transit_fit_arguments)
     source = open(os.path.join(REPO, "tls_amd", "csrc", "tls_amd.hip")).read()
-    assert "smear(ctx->d_transit)" in source
+    assert 'd_transit{pool, "d_transit", kScratch}' in source     # (scratch: what tls_debug_poison_lds smears)
 
 
 GOOD = dict(t=T, y=numpy.ones(500), dy=numpy.ones(500), period=[1.0, 2.0], T0=[1.1, 1.2], duration=[0.1, 0.2], row_first=[0, 8],

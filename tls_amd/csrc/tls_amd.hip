@@ -26,6 +26,11 @@
 #include "tls_kernels.hip.h"
 #include "tls_plan.hip.h"
 #include "tls_candidate_slabs.h"
+#include "tls_arena.h"
+
+// every DevBuf is device memory of the HIP runtime (a hipError_t travels as the int it is)
+int tlsmem::device_alloc(void** out, size_t bytes) { return (int)hipMalloc(out, bytes); }
+int tlsmem::device_free(void* p) { return (int)hipFree(p); }
 
 using namespace tlsplan;
 
@@ -40,19 +45,10 @@ constexpr size_t kEventRing = 64;   // launch-timing event pairs kept per contex
 
 std::string g_create_error;  // tls_last_error(NULL)
 
-template <typename T>
-struct DevBuf {
-    T* ptr = nullptr;
-    size_t cap = 0;  // elements
-    hipError_t reserve(size_t n_elem) {
-        if (n_elem <= cap) return hipSuccess;
-        if (ptr) { hipError_t e = hipFree(ptr); ptr = nullptr; cap = 0; if (e != hipSuccess) return e; }
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&ptr), std::max<size_t>(n_elem, 1) * sizeof(T));
-        if (e == hipSuccess) cap = n_elem;
-        return e;
-    }
-    void release() { if (ptr) (void)hipFree(ptr); ptr = nullptr; cap = 0; }
-};
+using tlsmem::Arena;
+using tlsmem::BufPool;
+using tlsmem::DevBuf;
+constexpr tlsmem::Kind kScratch = tlsmem::Kind::scratch, kState = tlsmem::Kind::state;
 
 // a typed window into the context's one plan allocation (d_plan): same `.ptr` as a DevBuf, not owned
 template <typename T>
@@ -148,9 +144,14 @@ struct PlanKey {
 // Lane B of a context (tls_ctx::lane_b; DESIGN.md section 4, "Launch lanes"): a second stream and a second set of exactly
 // what an overlappable four-slot launch writes, and of the flux.  Allocated at lane B's first use.
 struct LaneB {
+    explicit LaneB(BufPool& owner) : pool(owner) {}
+    BufPool& pool;                        // the context's
     hipStream_t stream = nullptr;
-    DevBuf<unsigned int> d_squeue, d_lists, d_perm;
-    DevBuf<double> d_out, d_y;            // [chi2 | row | depth | counters[4]]; the flux
+    DevBuf<unsigned int> d_squeue{pool, "lane_b.d_squeue", kState};   // state: a queue whose zero state between launches is the kernels' own invariant
+    // (smeared on the joined stream, which lane B's next command waits for)
+    DevBuf<unsigned int> d_lists{pool, "lane_b.d_lists", kScratch}, d_perm{pool, "lane_b.d_perm", kScratch};
+    // [chi2 | row | depth | counters[4]]; the flux.  State: results a later call may trust; the flux the next launch reads
+    DevBuf<double> d_out{pool, "lane_b.d_out", kState}, d_y{pool, "lane_b.d_y", kState};
     unsigned char* h_stage = nullptr; size_t h_stage_cap = 0;   // pinned: the flux on its way to d_y
     hipEvent_t ev_stage = nullptr; bool stage_pending = false;   // ... and its last upload
     hipEvent_t ev_done = nullptr;         // behind the last command on `stream` (launch or upload)
@@ -162,6 +163,10 @@ struct LaneB {
 
 struct tls_ctx {
     int device = 0;
+    // Every device buffer of the context is constructed against this pool (lane B's and the batch slots' too), with its name
+    // and kind (DESIGN.md "Device memory"): tls_ctx_destroy, tls_debug_device_bytes and tls_debug_poison_lds walk the pool.
+    // scratch: the next call uploads or writes all that it reads from the buffer; state: the one-line reason beside it.
+    BufPool pool;
     // Lane A's stream: the context's one stream for everything but a lane-B launch and its flux.  Every use outside the
     // lane path goes through main_stream(ctx), which first orders the stream behind lane B (join) -- hence the name no
     // other code spells.
@@ -172,7 +177,7 @@ struct tls_ctx {
     // exactly what such a launch writes (queue words, live-unit lists with the band list, stashed orders, results) and of
     // the flux --, so that search i+1 starts on the compute units search i has already left.  Lane B's buffers are
     // allocated at its first use (a context that never overlaps holds none of them).
-    LaneB lane_b;
+    LaneB lane_b{pool};
     hipEvent_t ev_state = nullptr;            // lane A's state a lane-B command must see: uploads, the filling launch, consumers
     bool state_dirty = true;                  // lane A's stream got a command other than an overlapped launch since ev_state's record
     int lanes = TLS_LANES_DEFAULT;            // developer switch `lanes` (0: every launch on lane A); not part of the plan key
@@ -191,7 +196,7 @@ struct tls_ctx {
     // device-resident plan
     // ONE allocation holds every plan array (views below); it is filled from ONE pinned staging buffer by ONE
     // asynchronous copy, and tls_prepare does not wait for it
-    DevBuf<unsigned char> d_plan;
+    DevBuf<unsigned char> d_plan{pool, "d_plan", kState};   // state: the plan
     View<double> d_t, d_y, d_w, d_periods, d_q, d_q2, d_g;
     View<int> d_order;
     View<tlsdev::PeriodRows> d_rows;
@@ -201,7 +206,7 @@ struct tls_ctx {
     hipEvent_t ev_stage = nullptr; bool stage_pending = false;  // its last upload
     // results: [chi2 | row | depth | counters[4]] in one allocation, fetched by one copy into pinned memory.  d_out is
     // lane A's allocation; the views denote the results of the LATEST launch, whichever lane it took (point_results)
-    DevBuf<double> d_out;
+    DevBuf<double> d_out{pool, "d_out", kState};   // state: results a later call may trust (tls_spectra without chi2)
     View<double> d_latest;
     View<double> d_chi2, d_depth;
     View<long long> d_row;
@@ -212,93 +217,89 @@ struct tls_ctx {
     int64_t plan_reuses = 0;   // tls_prepare calls answered from the held plan
     std::vector<double> batch_group_ms;   // wall time of every group of 32 light curves of the last tls_power_batch / tls_search_batch (tls_debug_batch_group_ms)
     std::vector<double> batch_group_wait_ms;   // ... of which the group's one wait for the device (tls_power_batch)
-    DevBuf<double> d_scratch, d_pack, d_gather, d_scalar, d_stage;
-    DevBuf<unsigned long long> d_phase, d_check;
-    DevBuf<unsigned int> d_queue, d_squeue, d_lists, d_perm, d_pqueues;   // d_pqueues: tls_power_batch's T0-fit queues   // d_squeue: the search kernel's self-rewinding queue
-    DevBuf<double> d_curve_S0, d_curve_w0;   // survey batches
+    DevBuf<double> d_scratch{pool, "d_scratch", kScratch}, d_pack{pool, "d_pack", kScratch}, d_scalar{pool, "d_scalar", kScratch};
+    // state: the staged / gathered results of the comm calls, which a later call may trust
+    DevBuf<double> d_gather{pool, "d_gather", kState}, d_stage{pool, "d_stage", kState};
+    // state: queues and counters whose zero state between launches is the kernels' own invariant
+    DevBuf<unsigned long long> d_phase{pool, "d_phase", kState}, d_check{pool, "d_check", kState};
+    DevBuf<unsigned int> d_queue{pool, "d_queue", kState};
+    DevBuf<unsigned int> d_squeue{pool, "d_squeue", kState};     // the search kernel's self-rewinding queue
+    DevBuf<unsigned int> d_pqueues{pool, "d_pqueues", kState};   // tls_power_batch's T0-fit queues
+    DevBuf<unsigned int> d_lists{pool, "d_lists", kScratch}, d_perm{pool, "d_perm", kScratch};
+    // state: inputs of the survey batches
+    DevBuf<double> d_curve_S0{pool, "d_curve_S0", kState}, d_curve_w0{pool, "d_curve_w0", kState};
     // The four-slot kernel's table of folded orders: one row per period of the plan (tlsdev::slim_perm_row entries).  The
     // order is numpy's stable argsort of fold_phase(t, period) -- the flux, the weights and the noise do not enter it --, so
     // it lives as long as the plan key: the plan's first four-slot launch stores it, every later one reads it.
-    DevBuf<unsigned short> d_perm_table;     // (grows like every DevBuf and is kept: plans of different period counts alternate on a context)
+    // state: it belongs to the plan (grows like every DevBuf and is kept: plans of different period counts alternate on a context)
+    DevBuf<unsigned short> d_perm_table{pool, "d_perm_table", kState};
     size_t perm_table_entries = 0;           // entries of it the held plan uses; 0: the plan has no table
     bool perm_filled = false;                // a launch that stored every row has been enqueued (stream order does the rest)
     // survey batches: two slots of device + pinned host buffers, a second stream for the transfers
     struct BatchSlot {
-        DevBuf<double> d_y, d_w, d_S0, d_w0, d_chi2, d_depth;
-        DevBuf<long long> d_row;
+        explicit BatchSlot(BufPool& owner) : pool(owner) {}
+        BufPool& pool;                                   // the context's
+        // state: the inputs and results of the survey batches
+        DevBuf<double> d_y{pool, "slot.d_y", kState}, d_w{pool, "slot.d_w", kState}, d_S0{pool, "slot.d_S0", kState},
+            d_w0{pool, "slot.d_w0", kState}, d_chi2{pool, "slot.d_chi2", kState}, d_depth{pool, "slot.d_depth", kState};
+        DevBuf<long long> d_row{pool, "slot.d_row", kState};
         double* h_in = nullptr; size_t h_in_cap = 0;     // pinned: y | w | S0 | w0 of one group
         double* h_out = nullptr; size_t h_out_cap = 0;   // pinned: chi2 | row | depth of one group
         hipEvent_t ev_in = nullptr, ev_kernel = nullptr, ev_out = nullptr;
-    } slot[2];
+    } slot[2] = {BatchSlot(pool), BatchSlot(pool)};
     hipStream_t copy_stream = nullptr;
     // enqueue() reads these when set (a batch slot); otherwise the context's own buffers
     const double* over_y = nullptr; const double* over_w = nullptr;
     const double* over_S0 = nullptr; const double* over_w0 = nullptr;
     double* over_chi2 = nullptr; long long* over_row = nullptr; double* over_depth = nullptr;
     int batch_curves = 1;                    // light curves the next launch searches (tls_search_batch)
-    DevBuf<double> d_ft, d_fy, d_fsig, d_fep, d_fres, d_fscratch;  // final T0 fit
-    DevBuf<double> d_pink;          // tls_pink_noise: data | terms | running sums
-    DevBuf<double> d_frot;          // ... its rotation path: per fit flux | phases | quotients of the base order, state
-    DevBuf<int> d_frperm;           // ... and the base order itself
-    DevBuf<double> d_spec;                                         // SDE spectra: SR | power_raw | power | sde[2] | chi2 copy
-    DevBuf<double> d_tstats;        // tls_power_batch_stats: row durations | the two root tables | per-curve scratch of one group
-    DevBuf<int> d_tranges;          // ... and every epoch's chunk start | stop | offset
-    DevBuf<double> d_models;        // tls_power_batch_models: template curve | per-curve scratch of one group | results of one group
-    DevBuf<double> d_inject;        // tls_inject_transits: t | base rows | injected rows | constants of one slab
-    DevBuf<unsigned long long> d_inject_count;   // ... and its points in contact per injection
-    DevBuf<double> d_null;          // tls_null_rows: source rows | sigma | rows of one slab
-    DevBuf<unsigned long long> d_null_words;     // tls_debug_null_words: the words of one slab
-    DevBuf<double> d_detrend;       // tls_medfilt_detrend, tls_biweight_detrend: rows | flat rows | trend rows of one slab
-    DevBuf<int> d_windows;          // tls_biweight_detrend: lo [n] | hi [n], the window of every point
-    // tls_transit_mask: t | period | T0 | duration of the candidates grouped by curve | their offsets [n_curves + 1] (64-bit
-    // words); tls_biweight_detrend_masked: t; tls_remove_transits: t | the grouped candidates with their constants | their
-    // offsets | profile | sub; of one slab: rows | models
-    DevBuf<double> d_protect;
-    // tls_transit_mask: the mask rows of one slab; tls_biweight_detrend_masked: mask | open marks | status rows of one slab;
-    // tls_prewhiten_masked: the mask rows of one slab
-    DevBuf<unsigned char> d_protect_bytes;
-    // tls_sysrem: y | x | flat | dy | w (without dy: one weight a row) [| trend] | m | c [K] rows | a [K] | chunk partials
-    DevBuf<double> d_sysrem;
-    DevBuf<unsigned long long> d_sysrem_state;   // ... and its state words (tlsdev::kSysremState)
-    DevBuf<double> d_peaks;         // tls_find_peaks: periods | records of one slab | power [| chi2 | depth | row] rows of one slab
-    DevBuf<unsigned long long> d_peak_mask;      // ... and tls_power_batch_peaks: a row's alive mask where the LDS does not hold it
-    // the peak-fit stage (tls_power_batch_peak_fits), one slab of fits: picks | per-transit rows | signals | fit parameters |
-    // n_epochs | curve of fit; trial epochs; residuals; the statistics kernel's scratch and its chunk ranges
-    DevBuf<double> d_pfit, d_pfep, d_pfres, d_pfstats;
-    DevBuf<int> d_pfranges;
-    DevBuf<double> d_scan;          // tls_phase_scan: t | y rows | period | T0 | duration | records | curve of fit
-    // tls_single_transits: t | rows | taps | of one slab: y | dy | ses | depth | events | n_events | row
-    DevBuf<double> d_single;
-    // The per-candidate stages (run_candidate_slabs): of one slab the curve rows [cs][n] -- in front of them the pairs
-    // [cs][n] where the pairs kernel runs, at the 16-byte aligned start --, then the per-candidate arrays [sl] with the packed
-    // int columns [sl] each last (padded to a whole double); behind the semicolon what every slab of the call shares.
-    // tls_transit_times: of one slab: pairs | y | dy | records | times | period | T0 | slot, row, reach; t | rows | taps | slopes
-    DevBuf<double> d_times;
-    // tls_event_vetting: of one slab: pairs | held (N, D) | y | dy | summaries | events | period | T0 | chase_span | slot, row,
-    // reach, chase, guard; t | rows | taps
-    DevBuf<double> d_vetting;
-    // tls_shape_fit: of one slab: pairs | y | dy | records | period | T0 | duration | slot; t | ratio | ingress | shift | scratch
-    DevBuf<double> d_shape;
-    // tls_transit_fit: of one slab: pairs | y | dy | records | period | T0 | duration | slot | row_first; t | k_rows | profile |
-    // impact | ratio | shift | sub | scratch
-    DevBuf<double> d_transit;
-    // tls_centroid_test: of one slab: y | cx | cy | records | period | T0 | duration | slot; t | shape | scratch
-    DevBuf<double> d_centroid;
-    // tls_folded_views: of one slab: y | records | period | T0 | duration | secondary | global and local medians | slot | global
-    // and local counts; t | scratch
-    DevBuf<double> d_views;
-    // tls_nudft / tls_lomb_scargle: the sums of one slab first (16-byte aligned pairs), then its rows and tables
-    // tls_sine_test: of one slab: y | dy | records | harmonic records | sums | period | T0 | duration | slot; t | harmonics
-    DevBuf<double> d_gls;
-    // tls_ephemeris_match: star | period | T0 | duration | strength | records | partial records of every chunk
-    DevBuf<double> d_match;
-    // tls_noise_profile: t | span_max | widths; of one slab: rows | d | records | count | robust | rms | clip counts | and for
-    // rows that do not fit the LDS the window means and validity words of every (curve, width)
-    DevBuf<double> d_noise;
+    // the final T0 fit
+    DevBuf<double> d_ft{pool, "d_ft", kScratch}, d_fy{pool, "d_fy", kScratch}, d_fsig{pool, "d_fsig", kScratch}, d_fep{pool, "d_fep", kScratch},
+        d_fres{pool, "d_fres", kScratch}, d_fscratch{pool, "d_fscratch", kScratch};
+    DevBuf<double> d_pink{pool, "d_pink", kScratch};          // tls_pink_noise
+    DevBuf<double> d_frot{pool, "d_frot", kScratch};          // the T0 fit's rotation path: per fit flux, phases, quotients of the base order, state
+    DevBuf<int> d_frperm{pool, "d_frperm", kScratch};         // ... and the base order itself
+    DevBuf<double> d_spec{pool, "d_spec", kScratch};          // the SDE spectra and what tls_power_batch copies out of a group
+    DevBuf<double> d_tstats{pool, "d_tstats", kScratch};      // tls_power_batch_stats: the tables and the per-curve scratch of one group
+    DevBuf<int> d_tranges{pool, "d_tranges", kScratch};       // ... and every epoch's chunk start | stop | offset
+    DevBuf<double> d_models{pool, "d_models", kScratch};      // tls_power_batch_models
+    DevBuf<double> d_inject{pool, "d_inject", kScratch};      // tls_inject_transits
+    DevBuf<unsigned long long> d_inject_count{pool, "d_inject_count", kScratch};   // ... and its points in contact per injection
+    DevBuf<double> d_null{pool, "d_null", kScratch};          // tls_null_rows
+    DevBuf<unsigned long long> d_null_words{pool, "d_null_words", kScratch};       // tls_debug_null_words: the words of one slab
+    DevBuf<double> d_detrend{pool, "d_detrend", kScratch};    // tls_medfilt_detrend, tls_biweight_detrend: the rows of one slab
+    DevBuf<int> d_windows{pool, "d_windows", kScratch};       // tls_biweight_detrend: the window of every point
+    // tls_transit_mask, tls_biweight_detrend_masked, tls_remove_transits: time stamps, grouped candidates, rows of one slab
+    DevBuf<double> d_protect{pool, "d_protect", kScratch};
+    // ... and their mask rows of one slab (tls_prewhiten_masked's too)
+    DevBuf<unsigned char> d_protect_bytes{pool, "d_protect_bytes", kScratch};
+    DevBuf<double> d_sysrem{pool, "d_sysrem", kScratch};      // tls_sysrem
+    // ... and its state words (tlsdev::kSysremState).  State: counters whose zero state between launches is the kernels' own invariant
+    DevBuf<unsigned long long> d_sysrem_state{pool, "d_sysrem_state", kState};
+    DevBuf<double> d_peaks{pool, "d_peaks", kScratch};        // tls_find_peaks
+    DevBuf<unsigned long long> d_peak_mask{pool, "d_peak_mask", kScratch};   // ... and tls_power_batch_peaks: a row's alive mask where the LDS does not hold it
+    // the peak-fit stage (tls_power_batch_peak_fits), one slab of fits: inputs and fit records; trial epochs; residuals; the
+    // statistics kernel's scratch and its chunk ranges
+    DevBuf<double> d_pfit{pool, "d_pfit", kScratch}, d_pfep{pool, "d_pfep", kScratch}, d_pfres{pool, "d_pfres", kScratch},
+        d_pfstats{pool, "d_pfstats", kScratch};
+    DevBuf<int> d_pfranges{pool, "d_pfranges", kScratch};
+    DevBuf<double> d_scan{pool, "d_scan", kScratch};          // tls_phase_scan
+    DevBuf<double> d_single{pool, "d_single", kScratch};      // tls_single_transits
+    // the per-candidate stages (run_candidate_slabs): one slab's curve rows and per-candidate arrays, then what every slab shares
+    DevBuf<double> d_times{pool, "d_times", kScratch};        // tls_transit_times
+    DevBuf<double> d_vetting{pool, "d_vetting", kScratch};    // tls_event_vetting
+    DevBuf<double> d_shape{pool, "d_shape", kScratch};        // tls_shape_fit
+    DevBuf<double> d_transit{pool, "d_transit", kScratch};    // tls_transit_fit
+    DevBuf<double> d_centroid{pool, "d_centroid", kScratch};  // tls_centroid_test
+    DevBuf<double> d_views{pool, "d_views", kScratch};        // tls_folded_views
+    DevBuf<double> d_gls{pool, "d_gls", kScratch};            // tls_nudft, tls_lomb_scargle, tls_sine_test, prewhiten
+    DevBuf<double> d_match{pool, "d_match", kScratch};        // tls_ephemeris_match
+    DevBuf<double> d_noise{pool, "d_noise", kScratch};        // tls_noise_profile
     // two-role slab path (series in HBM, one light curve; SearchPlan::split)
     View<unsigned int> d_tile_prefix;        // [n_periods + 1] tiles in front of work item w (queue order)
-    DevBuf<double> d_partials;               // [split_max_items][3] a tile's winner
-    DevBuf<unsigned int> d_tiles_done;       // [split_batch] tiles of the period that are done (zero between launches)
+    DevBuf<double> d_partials{pool, "d_partials", kScratch};  // [split_max_items][3] a tile's winner
+    // [split_batch] tiles of the period that are done.  State: zero between launches is the kernels' own invariant
+    DevBuf<unsigned int> d_tiles_done{pool, "d_tiles_done", kState};
     std::vector<tlsdev::WidthEntry> host_widths;  // kept for tls_update_flux's pruning decision
     Switches opt;                     // the context's switches (tls_set_options / tls_debug_set_switch; initially the process's TLS_* environment)
 
@@ -310,9 +311,10 @@ struct tls_ctx {
     double S0 = 0, w0 = 1, depth_min = 0;
     double y_abs_max = 1.0;   // largest |flux| of the light curve(s) of the next launch: bounds the prefix sum (fast mode's eps)
     double e_abs_max = INFINITY;   // largest |1 - flux| of the same (inf: a sample outside [0.5, 2]): admits the fp32 screen
-    DevBuf<float> d_split;    // fp32 screen: low halves of the folded samples, one region per workgroup
-    DevBuf<double> d_park;    // fp32 screen: parked cells, kParkCap per workgroup
-    DevBuf<double> d_band;    // slab variant, fast mode: band_prefix of the launches (two slots, like h_band)
+    DevBuf<float> d_split{pool, "d_split", kScratch};    // fp32 screen: low halves of the folded samples, one region per workgroup
+    DevBuf<double> d_park{pool, "d_park", kScratch};     // fp32 screen: parked cells, kParkCap per workgroup
+    // slab variant, fast mode: band_prefix of the launches (two slots, like h_band).  State: the host caches it by sigma
+    DevBuf<double> d_band{pool, "d_band", kState};
     double* d_band_now = nullptr;   // the slot the next launch reads
     double* h_band = nullptr; size_t h_band_cap = 0;   // pinned: two slots of (n_widths + 1) doubles
     hipEvent_t ev_band[2] = {nullptr, nullptr}; bool band_used[2] = {false, false}; int band_slot = 0;
@@ -344,7 +346,7 @@ int fail(tls_ctx* ctx, int code, const std::string& msg) {
 
 #define TLS_HIP(ctx, call)                                                              \
     do {                                                                                \
-        hipError_t e_ = (call);                                                         \
+        hipError_t e_ = static_cast<hipError_t>(call);                                                \
         if (e_ != hipSuccess)                                                           \
             return fail(ctx, TLS_E_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
     } while (0)
@@ -914,10 +916,10 @@ int enqueue(tls_ctx* ctx, bool count_work, bool phase_clock = false, double* deb
     switch (kernel_pick) {
     case Kernel::ResidentScreen: {
         const size_t region = (size_t)plan.M + 1 + (size_t)plan.region_pad;
-        hipError_t er = ctx->d_split.reserve((size_t)plan.blocks * region);
+        hipError_t er = static_cast<hipError_t>(ctx->d_split.reserve((size_t)plan.blocks * region));
         if (er != hipSuccess) { --ctx->ev_used; return fail(ctx, TLS_E_HIP, std::string("fp32 screen scratch: ") + hipGetErrorString(er)); }
         a.split_lo = ctx->d_split.ptr;
-        er = ctx->d_park.reserve((size_t)plan.blocks * tlsdev::kParkCap * 2);   // (a ParkedCell is two doubles wide)
+        er = static_cast<hipError_t>(ctx->d_park.reserve((size_t)plan.blocks * tlsdev::kParkCap * 2));   // (a ParkedCell is two doubles wide)
         if (er != hipSuccess) { --ctx->ev_used; return fail(ctx, TLS_E_HIP, std::string("fp32 screen scratch: ") + hipGetErrorString(er)); }
         a.park_cells = ctx->d_park.ptr;
         e = launch_variant<true, true, unsigned short, false, false, true>(ctx, a, plan.blocks);
@@ -1117,27 +1119,26 @@ int reserve_post_search(tls_ctx* ctx, int64_t group, int64_t n_periods, int64_t 
     b.max_len = std::max<int64_t>(max_len, 1);
     b.spec_stride = 3 * np;
     b.group = group;
-    TLS_HIP(ctx, ctx->d_spec.reserve(g * b.spec_stride + 2 * g + 8 * g + g + stats_words * g + peaks_words * g + fits_words * g + scans_words * g));
-    b.sde = ctx->d_spec.ptr + g * b.spec_stride;
-    b.pick = b.sde + 2 * g;
-    b.T0 = b.pick + 8 * g;
-    b.stats = stats_words ? b.T0 + g : nullptr;
-    b.per_transit = stats_words ? b.stats + (size_t)tlsdev::kTransitStats * g : nullptr;
-    if (peaks_words) {
-        const bool rows_copied = stats_copied == stats_words;
-        b.peaks = b.T0 + g + (rows_copied ? stats_words : (size_t)tlsdev::kTransitStats) * g;
-        if (fits_words) b.fits = b.peaks + peaks_words * g;
-        if (scans_words) b.scans = b.fits + fits_words * g;
-        if (stats_words && !rows_copied) b.per_transit = b.peaks + (peaks_words + fits_words + scans_words) * g;
-    }
+    // the per-transit rows follow the records where they are copied out with them (or where there are no peaks); else they
+    // stay behind everything that is copied
+    const size_t record_words = stats_words ? (size_t)tlsdev::kTransitStats : 0, row_words = stats_words - record_words;
+    const bool rows_last = peaks_words && stats_copied != stats_words;
+    double* spectra;   // (enqueue_post_search reads them from d_spec's start)
+    Arena L;
+    L.add(spectra, g * b.spec_stride);  L.add(b.sde, 2 * g);  L.add(b.pick, 8 * g);  L.add(b.T0, g);
+    L.add(b.stats, record_words * g);
+    if (!rows_last) L.add(b.per_transit, row_words * g);
+    L.add(b.peaks, peaks_words * g);  L.add(b.fits, fits_words * g);  L.add(b.scans, scans_words * g);
+    if (rows_last) L.add(b.per_transit, row_words * g);
+    TLS_HIP(ctx, L.bind(ctx->d_spec));
     b.fit_stride = (size_t)n;
     TLS_HIP(ctx, ctx->d_fep.reserve(g * b.fit_stride));
     TLS_HIP(ctx, ctx->d_fres.reserve(g * b.fit_stride));
-    // signals | n_epochs (ints) | fit parameters (T0FitParams, 24 B each)
-    TLS_HIP(ctx, ctx->d_fsig.reserve(g * (size_t)b.max_len + g + 3 * g));
-    b.n_epochs = reinterpret_cast<int*>(ctx->d_fsig.ptr + g * (size_t)b.max_len);
-    b.fit = reinterpret_cast<tlsdev::T0FitParams*>(ctx->d_fsig.ptr + g * (size_t)b.max_len + g);
-    static_assert(sizeof(tlsdev::T0FitParams) == 24, "three doubles of device scratch per fit");
+    double* signals;   // (read from d_fsig's start)
+    Arena F;
+    F.add(signals, g * (size_t)b.max_len);  F.add(b.n_epochs, 2 * g);   // (a double's room a curve)
+    F.add(b.fit, g);
+    TLS_HIP(ctx, F.bind(ctx->d_fsig));
     return TLS_OK;
 }
 
@@ -1201,11 +1202,11 @@ struct StatsBufs { double *row_duration = nullptr, *root = nullptr, *root_count 
 // device inputs of a request (uploaded once per call) and the O(group x n) scratch of one group
 int reserve_transit_stats(tls_ctx* ctx, const StatsRequest& sr, int64_t group, int64_t n, StatsBufs& sb) {
     sb.scratch_stride = 4 * (size_t)n + 1;   // flux_ootr | concat(odd, even) | pink terms | running sums
-    const size_t ins = (size_t)sr.n_rows + 2 * (size_t)sr.n_root;
-    TLS_HIP(ctx, ctx->d_tstats.reserve(ins + (size_t)group * sb.scratch_stride));
+    Arena L;
+    L.add(sb.row_duration, (size_t)sr.n_rows);  L.add(sb.root, (size_t)sr.n_root);  L.add(sb.root_count, (size_t)sr.n_root);
+    L.add(sb.scratch, (size_t)group * sb.scratch_stride);
+    TLS_HIP(ctx, L.bind(ctx->d_tstats));
     TLS_HIP(ctx, ctx->d_tranges.reserve((size_t)group * 3 * (size_t)sr.max_epochs));
-    sb.row_duration = ctx->d_tstats.ptr; sb.root = sb.row_duration + sr.n_rows; sb.root_count = sb.root + sr.n_root;
-    sb.scratch = sb.root_count + sr.n_root;
     sb.ranges = ctx->d_tranges.ptr;
     TLS_HIP(ctx, hipMemcpyAsync(sb.row_duration, sr.row_duration, (size_t)sr.n_rows * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     TLS_HIP(ctx, hipMemcpyAsync(sb.root, sr.root, (size_t)sr.n_root * 8, hipMemcpyHostToDevice, main_stream(ctx)));
@@ -1303,8 +1304,10 @@ int reserve_transit_models(tls_ctx* ctx, const ModelsRequest& mr, int64_t group,
     mb.scratch_stride = (mb.resident ? 0 : 3 * (size_t)n) + 2 * (size_t)tlsdev::kModelsOversample * (size_t)n;
     mb.out_stride = mr.stride(n);
     const size_t g = (size_t)group, curve = 2 * (size_t)mr.curve_n;
-    TLS_HIP(ctx, ctx->d_models.reserve(curve + g * mb.scratch_stride + g * mb.out_stride));
-    mb.curve = ctx->d_models.ptr; mb.scratch = mb.curve + curve; mb.out = mb.scratch + g * mb.scratch_stride;
+    Arena L;
+    L.add(mb.curve, curve);   // times | values
+    L.add(mb.scratch, g * mb.scratch_stride);  L.add(mb.out, g * mb.out_stride);
+    TLS_HIP(ctx, L.bind(ctx->d_models));
     TLS_HIP(ctx, hipMemcpyAsync(mb.curve, mr.curve_t, (size_t)mr.curve_n * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     TLS_HIP(ctx, hipMemcpyAsync(mb.curve + mr.curve_n, mr.curve_f, (size_t)mr.curve_n * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     return TLS_OK;
@@ -1501,15 +1504,15 @@ int reserve_peak_fits(tls_ctx* ctx, int64_t fits_total, int64_t n, int64_t max_l
     fb.fit_stride = (size_t)n;
     fb.scratch_stride = 4 * (size_t)n + 1;
     const size_t s = (size_t)fb.slab, rows = (size_t)tlsdev::kPerTransitRows * (size_t)max_epochs;
-    TLS_HIP(ctx, ctx->d_pfit.reserve(8 * s + rows * s + (size_t)fb.max_len * s + 3 * s + s + s));
+    Arena L;
+    L.add(fb.pick, 8 * s);  L.add(fb.per_transit, rows * s);  L.add(fb.signal, (size_t)fb.max_len * s);  L.add(fb.fit, s);
+    L.add(fb.n_epochs, 2 * s);   // (a double's room a fit, this and the next)
+    L.add(fb.curve, 2 * s);
+    TLS_HIP(ctx, L.bind(ctx->d_pfit));
     TLS_HIP(ctx, ctx->d_pfep.reserve(s * fb.fit_stride));
     TLS_HIP(ctx, ctx->d_pfres.reserve(s * fb.fit_stride));
     TLS_HIP(ctx, ctx->d_pfstats.reserve(s * fb.scratch_stride));
     TLS_HIP(ctx, ctx->d_pfranges.reserve(s * 3 * (size_t)max_epochs));
-    fb.pick = ctx->d_pfit.ptr; fb.per_transit = fb.pick + 8 * s; fb.signal = fb.per_transit + rows * s;
-    fb.fit = reinterpret_cast<tlsdev::T0FitParams*>(fb.signal + (size_t)fb.max_len * s);
-    fb.n_epochs = reinterpret_cast<int*>(fb.signal + (size_t)fb.max_len * s + 3 * s);
-    fb.curve = reinterpret_cast<int*>(fb.signal + (size_t)fb.max_len * s + 4 * s);
     fb.epochs = ctx->d_pfep.ptr; fb.residuals = ctx->d_pfres.ptr; fb.scratch = ctx->d_pfstats.ptr; fb.ranges = ctx->d_pfranges.ptr;
     return TLS_OK;
 }
@@ -1963,42 +1966,21 @@ void tls_ctx_destroy(tls_ctx* ctx) {
     if (ctx->comm) (void)ncclCommDestroy(ctx->comm);
     if (ctx->lane_b.stream) (void)hipStreamSynchronize(ctx->lane_b.stream);
     if (ctx->lane_a_stream) (void)hipStreamSynchronize(ctx->lane_a_stream);
+    ctx->pool.release_all();   // every device buffer of the context, lane B's and the batch slots' included
     {
         auto& lb = ctx->lane_b;
-        lb.d_squeue.release(); lb.d_lists.release(); lb.d_perm.release(); lb.d_out.release(); lb.d_y.release();
         if (lb.h_stage) (void)hipHostFree(lb.h_stage);
         if (lb.ev_stage) (void)hipEventDestroy(lb.ev_stage);
         if (lb.ev_done) (void)hipEventDestroy(lb.ev_done);
         if (lb.stream) (void)hipStreamDestroy(lb.stream);
     }
     if (ctx->ev_state) (void)hipEventDestroy(ctx->ev_state);
-    ctx->d_plan.release(); ctx->d_out.release();
     if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
     if (ctx->h_out) (void)hipHostFree(ctx->h_out);
     if (ctx->ev_stage) (void)hipEventDestroy(ctx->ev_stage);
-    ctx->d_scratch.release(); ctx->d_pack.release();
-    ctx->d_gather.release(); ctx->d_scalar.release(); ctx->d_stage.release();
-    ctx->d_partials.release(); ctx->d_tiles_done.release(); ctx->d_check.release(); ctx->d_spec.release(); ctx->d_queue.release(); ctx->d_squeue.release(); ctx->d_pqueues.release(); ctx->d_phase.release(); ctx->d_lists.release(); ctx->d_perm.release(); ctx->d_perm_table.release(); ctx->d_curve_S0.release(); ctx->d_curve_w0.release();
-    ctx->d_ft.release(); ctx->d_fy.release(); ctx->d_fsig.release(); ctx->d_fep.release(); ctx->d_fres.release(); ctx->d_fscratch.release(); ctx->d_frot.release(); ctx->d_frperm.release(); ctx->d_pink.release();
-    ctx->d_tstats.release(); ctx->d_tranges.release(); ctx->d_models.release(); ctx->d_inject.release(); ctx->d_inject_count.release();
-    ctx->d_null.release(); ctx->d_null_words.release(); ctx->d_detrend.release(); ctx->d_windows.release(); ctx->d_sysrem.release(); ctx->d_sysrem_state.release(); ctx->d_peaks.release(); ctx->d_peak_mask.release();
-    ctx->d_pfit.release(); ctx->d_pfep.release(); ctx->d_pfres.release(); ctx->d_pfstats.release(); ctx->d_pfranges.release();
-    ctx->d_scan.release();
-    ctx->d_single.release();
-    ctx->d_times.release();
-    ctx->d_vetting.release();
-    ctx->d_shape.release();
-    ctx->d_transit.release();
-    ctx->d_centroid.release();
-    ctx->d_views.release();
-    ctx->d_gls.release();
-    ctx->d_match.release();
-    ctx->d_noise.release();
-    ctx->d_split.release(); ctx->d_park.release(); ctx->d_band.release();
     if (ctx->h_band) (void)hipHostFree(ctx->h_band);
     for (auto& ev : ctx->ev_band) if (ev) (void)hipEventDestroy(ev);
     for (auto& sl : ctx->slot) {
-        sl.d_y.release(); sl.d_w.release(); sl.d_S0.release(); sl.d_w0.release(); sl.d_chi2.release(); sl.d_depth.release(); sl.d_row.release();
         if (sl.h_in) (void)hipHostFree(sl.h_in);
         if (sl.h_out) (void)hipHostFree(sl.h_out);
         if (sl.ev_in) (void)hipEventDestroy(sl.ev_in);
@@ -2337,9 +2319,10 @@ int tls_pink_noise(tls_ctx* ctx, const double* data, int64_t n, int64_t width, d
     if (!(root_width > 0.0)) return fail(ctx, TLS_E_ARG, "pink noise: root_width must be width ** 0.5");
     TLS_HIP(ctx, hipSetDevice(ctx->device));
     const int64_t n_windows = n - width + 1;
-    // data | terms | running sums (n_windows + 1)
-    TLS_HIP(ctx, ctx->d_pink.reserve((size_t)n + 2 * (size_t)n_windows + 1));
-    double* d_data = ctx->d_pink.ptr; double* d_terms = d_data + n; double* d_sums = d_terms + n_windows;
+    double *d_data, *d_terms, *d_sums;
+    Arena L;
+    L.add(d_data, (size_t)n);  L.add(d_terms, (size_t)n_windows);  L.add(d_sums, (size_t)n_windows + 1);   // running sums
+    TLS_HIP(ctx, L.bind(ctx->d_pink));
     TLS_HIP(ctx, hipMemcpyAsync(d_data, data, (size_t)n * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     hipLaunchKernelGGL(tlsdev::tls_pink_terms, dim3((unsigned)((n_windows + 255) / 256)), dim3(256), 0, main_stream(ctx),
                        (const double*)d_data, (int)n_windows, (int)width, root_width, d_terms);
@@ -2380,13 +2363,12 @@ int tls_inject_transits(tls_ctx* ctx, const double* t, int64_t n, const double* 
     const size_t nn = (size_t)n;
     const int64_t slab = std::max<int64_t>(1, std::min<int64_t>({n_inj, (int64_t)65535, (int64_t)((256u << 20) / (8 * nn))}));
     const size_t base_len = flux_rows == 1 ? nn : (size_t)slab * nn;
-    // t | base rows | injected rows | constants
-    TLS_HIP(ctx, ctx->d_inject.reserve(nn + base_len + (size_t)slab * nn + 6 * (size_t)slab));
+    double *d_t, *d_base, *d_out, *d_consts;
+    Arena L;
+    L.add(d_t, nn);  L.add(d_base, base_len);  L.add(d_out, (size_t)slab * nn);   // the injected rows of one slab
+    L.add(d_consts, 6 * (size_t)slab);   // ... and their constants (tls_injection)
+    TLS_HIP(ctx, L.bind(ctx->d_inject));
     TLS_HIP(ctx, ctx->d_inject_count.reserve((size_t)slab));
-    double* d_t = ctx->d_inject.ptr;
-    double* d_base = d_t + nn;
-    double* d_out = d_base + base_len;
-    double* d_consts = d_out + (size_t)slab * nn;
     TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     if (flux_rows == 1) TLS_HIP(ctx, hipMemcpyAsync(d_base, flux, nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     for (int64_t k0 = 0; k0 < n_inj; k0 += slab) {
@@ -2467,11 +2449,10 @@ int tls_null_rows(tls_ctx* ctx, int64_t n, int64_t n_rows, uint64_t seed, int64_
     const int64_t slab = null_slab(n_rows, 8 * nn);
     const size_t src_len = mode == 1 ? (size_t)n_src * nn : 0;
     const size_t sigma_len = mode == 0 ? (size_t)n_sigma : 0;
-    // source rows | sigma | rows of one slab
-    TLS_HIP(ctx, ctx->d_null.reserve(src_len + sigma_len + (size_t)slab * nn));
-    double* d_src = ctx->d_null.ptr;
-    double* d_sigma = d_src + src_len;
-    double* d_out = d_sigma + sigma_len;
+    double *d_src, *d_sigma, *d_out;
+    Arena L;
+    L.add(d_src, src_len);  L.add(d_sigma, sigma_len);  L.add(d_out, (size_t)slab * nn);   // the rows of one slab
+    TLS_HIP(ctx, L.bind(ctx->d_null));
     if (src_len) TLS_HIP(ctx, hipMemcpyAsync(d_src, src, src_len * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     if (sigma_len) TLS_HIP(ctx, hipMemcpyAsync(d_sigma, sigma, sigma_len * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     for (int64_t k0 = 0; k0 < n_rows; k0 += slab) {
@@ -2553,12 +2534,10 @@ int tls_medfilt_detrend(tls_ctx* ctx, const double* y, int64_t n, int64_t n_rows
     TLS_HIP(ctx, hipSetDevice(ctx->device));
     // rows per launch: at most 256 MB of rows (as the injection and null slabs), and gridDim.y within its limit
     const int64_t slab = std::max<int64_t>(1, std::min<int64_t>({n_rows, (int64_t)65535, (int64_t)((256u << 20) / (8 * nn))}));
-    const int parts = out_trend ? 3 : 2;
-    // rows | flat rows [| trend rows]
-    TLS_HIP(ctx, ctx->d_detrend.reserve((size_t)parts * (size_t)slab * nn));
-    double* d_y = ctx->d_detrend.ptr;
-    double* d_flat = d_y + (size_t)slab * nn;
-    double* d_trend = out_trend ? d_flat + (size_t)slab * nn : nullptr;
+    double *d_y, *d_flat, *d_trend;
+    Arena L;
+    L.add(d_y, (size_t)slab * nn);  L.add(d_flat, (size_t)slab * nn);  L.add(d_trend, out_trend ? (size_t)slab * nn : 0);
+    TLS_HIP(ctx, L.bind(ctx->d_detrend));
     const int P = detrend_span(n, kernel);
     const int T = P - (int)(kernel - 1);
     const size_t lds = (size_t)P * (sizeof(unsigned long long) + sizeof(unsigned int));
@@ -2649,22 +2628,26 @@ static int biweight_detrend(tls_ctx* ctx, const double* t, const double* y, bool
     TLS_HIP(ctx, hipSetDevice(ctx->device));
     // rows per launch: at most 256 MB of rows (as the median filter's slabs), and gridDim.y within its limit
     const int64_t slab = std::max<int64_t>(1, std::min<int64_t>({n_rows, (int64_t)65535, (int64_t)((256u << 20) / (8 * nn))}));
-    const int parts = out_trend || masked ? 3 : 2;   // (the masked call interpolates between trend values: it always forms them)
-    TLS_HIP(ctx, ctx->d_detrend.reserve((size_t)parts * (size_t)slab * nn));
-    TLS_HIP(ctx, ctx->d_windows.reserve(2 * nn));
-    double* d_y = ctx->d_detrend.ptr;
-    double* d_flat = d_y + (size_t)slab * nn;
-    double* d_trend = parts == 3 ? d_flat + (size_t)slab * nn : nullptr;
+    double *d_y, *d_flat, *d_trend;
+    Arena L;
+    L.add(d_y, (size_t)slab * nn);  L.add(d_flat, (size_t)slab * nn);
+    L.add(d_trend, out_trend || masked ? (size_t)slab * nn : 0);   // (the masked call interpolates between trend values: it always forms them)
+    TLS_HIP(ctx, L.bind(ctx->d_detrend));
+    int *d_lo, *d_hi;   // the window of every point
+    Arena W;
+    W.add(d_lo, nn);  W.add(d_hi, nn);
+    TLS_HIP(ctx, W.bind(ctx->d_windows));
     // the masked call: the time stamps; the mask rows, the masked pass's marks and the status rows of a slab
     unsigned char *d_mask = nullptr, *d_open = nullptr, *d_status = nullptr;
     if (masked) {
         TLS_HIP(ctx, ctx->d_protect.reserve(nn));
-        TLS_HIP(ctx, ctx->d_protect_bytes.reserve(3 * (size_t)slab * nn));
-        d_mask = ctx->d_protect_bytes.ptr; d_open = d_mask + (size_t)slab * nn; d_status = d_open + (size_t)slab * nn;
+        Arena M;
+        M.add(d_mask, (size_t)slab * nn);  M.add(d_open, (size_t)slab * nn);  M.add(d_status, (size_t)slab * nn);
+        TLS_HIP(ctx, M.bind(ctx->d_protect_bytes));
         TLS_HIP(ctx, hipMemcpyAsync(ctx->d_protect.ptr, t, nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     }
-    TLS_HIP(ctx, hipMemcpyAsync(ctx->d_windows.ptr, lo.data(), nn * sizeof(int), hipMemcpyHostToDevice, main_stream(ctx)));
-    TLS_HIP(ctx, hipMemcpyAsync(ctx->d_windows.ptr + nn, hi.data(), nn * sizeof(int), hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_lo, lo.data(), nn * sizeof(int), hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_hi, hi.data(), nn * sizeof(int), hipMemcpyHostToDevice, main_stream(ctx)));
     int T = 0, P = 0, smax = 0;
     biweight_plan(lo, hi, wmax, &T, &P, &smax);
     const size_t lds = (size_t)P * (sizeof(unsigned long long) + sizeof(unsigned int)) + (size_t)smax * sizeof(double);
@@ -2680,7 +2663,7 @@ static int biweight_detrend(tls_ctx* ctx, const double* t, const double* y, bool
     tlsdev::BiweightMaskedArgs a;   // (the plain kernel takes its base, BiweightArgs)
     a.mask = d_mask; a.status = d_open; a.min_points = (int)min_points;
     a.y = d_y; a.flat = d_flat; a.trend = d_trend; a.check = nullptr;
-    a.lo = ctx->d_windows.ptr; a.hi = ctx->d_windows.ptr + nn;
+    a.lo = d_lo; a.hi = d_hi;
     a.n = (long long)n; a.tile = T; a.span = P; a.smax = smax;
 #ifdef TLS_DEBUG_CHECKS
     if (int rc = ensure_check_counters(ctx)) return rc;
@@ -2772,14 +2755,15 @@ int tls_transit_mask(tls_ctx* ctx, const double* t, int64_t n, const int64_t* cu
         }
     }
     TLS_HIP(ctx, hipSetDevice(ctx->device));
-    static_assert(sizeof(long long) == sizeof(double), "the offsets lie in a buffer of doubles");
     // curves per launch: at most 256 MB of flags
     const size_t slab = std::max<size_t>(1, std::min<size_t>(nc, ((size_t)256 << 20) / nn));
-    TLS_HIP(ctx, ctx->d_protect.reserve(nn + 3 * m + nc + 1));
-    TLS_HIP(ctx, ctx->d_protect_bytes.reserve(slab * nn));
-    double* d_t = ctx->d_protect.ptr;
-    double* d_cand = d_t + nn;
-    long long* d_offset = reinterpret_cast<long long*>(d_cand + 3 * m);
+    double *d_t, *d_cand;
+    long long* d_offset;
+    Arena L;
+    L.add(d_t, nn);  L.add(d_cand, 3 * m);   // period | T0 | duration of the candidates grouped by curve
+    L.add(d_offset, nc + 1);
+    TLS_HIP(ctx, L.bind(ctx->d_protect));
+    TLS_HIP(ctx, ctx->d_protect_bytes.reserve(slab * nn));   // the mask rows of one slab
     TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     if (m) TLS_HIP(ctx, hipMemcpyAsync(d_cand, sorted.data(), 3 * m * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     TLS_HIP(ctx, hipMemcpyAsync(d_offset, offset.data(), (nc + 1) * 8, hipMemcpyHostToDevice, main_stream(ctx)));
@@ -2875,32 +2859,31 @@ int tls_remove_transits(tls_ctx* ctx, const double* t, const double* y, int64_t 
             if (out_status[f] == 0.0) sorted[(size_t)at[(size_t)(curve ? curve[f] : f)]++] = made[(size_t)f];
     }
     TLS_HIP(ctx, hipSetDevice(ctx->device));
-    static_assert(sizeof(long long) == sizeof(double), "the offsets lie in a buffer of doubles");
     // curves per launch: at most 256 MB of rows and models
     const size_t slab = std::max<size_t>(1, std::min<size_t>(nc, ((size_t)256 << 20) / (16 * nn)));
-    const size_t words = tlsdev::kRemoveWords, table = (size_t)n_k * row_words;
-    // t | the grouped candidates | their offsets | profile | sub; of one slab: rows | models -- all of it written here or by
-    // the kernel in front of every read
-    TLS_HIP(ctx, ctx->d_protect.reserve(nn + words * m + nc + 1 + table + (size_t)n_sub + 2 * slab * nn));
-    double* d_t = ctx->d_protect.ptr;
-    double* d_cand = d_t + nn;
-    long long* d_offset = reinterpret_cast<long long*>(d_cand + words * m);
-    double* d_profile = d_cand + words * m + nc + 1;
-    double* d_sub = d_profile + table;
-    double* d_rows = d_sub + n_sub;
-    double* d_model = d_rows + slab * nn;
+    const size_t table = (size_t)n_k * row_words;
+    // all of it written here or by the kernel in front of every read
+    double *d_t, *d_profile, *d_sub, *d_rows, *d_model;
+    tlsdev::RemoveCandidate* d_cand;
+    long long* d_offset;
+    Arena L;
+    L.add(d_t, nn);  L.add(d_cand, m);   // the grouped candidates
+    L.add(d_offset, nc + 1);  L.add(d_profile, table);  L.add(d_sub, (size_t)n_sub);
+    L.add(d_rows, slab * nn);    // of one slab: rows | models
+    L.add(d_model, slab * nn);
+    TLS_HIP(ctx, L.bind(ctx->d_protect));
     if ((rc = ensure_check_counters(ctx))) return rc;
     const size_t lds = row_words * 8;
     TLS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(tlsdev::tls_remove_transits_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
-    TLS_HIP(ctx, hipMemcpyAsync(d_cand, sorted.data(), words * m * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_cand, sorted.data(), m * sizeof(tlsdev::RemoveCandidate), hipMemcpyHostToDevice, main_stream(ctx)));
     TLS_HIP(ctx, hipMemcpyAsync(d_offset, offset.data(), (nc + 1) * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     TLS_HIP(ctx, hipMemcpyAsync(d_profile, profile, table * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     TLS_HIP(ctx, hipMemcpyAsync(d_sub, sub, (size_t)n_sub * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     for (size_t c0 = 0; c0 < nc; c0 += slab) {
         const size_t curves = std::min(slab, nc - c0);
         tlsdev::RemoveArgs a;
-        a.t = d_t; a.cand = reinterpret_cast<const tlsdev::RemoveCandidate*>(d_cand); a.offset = d_offset + c0;
+        a.t = d_t; a.cand = d_cand; a.offset = d_offset + c0;
         a.profile = d_profile; a.sub = d_sub; a.rows = d_rows; a.model = out_model ? d_model : nullptr; a.check = ctx->d_check.ptr;
         a.n = (long long)n; a.tiles_per_curve = (long long)((nn + tlsdev::kRemoveThreads - 1) / tlsdev::kRemoveThreads);
         a.tiles = (long long)curves * a.tiles_per_curve; a.nK = (int)n_k; a.M = (int)M; a.S = (int)n_sub;
@@ -2941,19 +2924,17 @@ int tls_sysrem(tls_ctx* ctx, const double* y, const double* dy, int64_t n, int64
                 return fail(ctx, TLS_E_ARG, "sysrem: dy of row " + std::to_string(q / nn) + " has a non-finite or non-positive value");
     TLS_HIP(ctx, hipSetDevice(ctx->device));
     const size_t chunks = (R + TLS_SYSREM_ROW_CHUNK - 1) / TLS_SYSREM_ROW_CHUNK;
-    const size_t matrices = 3 + (dy ? 2 : 0) + (out_trend ? 1 : 0);
-    TLS_HIP(ctx, ctx->d_sysrem.reserve(matrices * cells + (dy ? 1 : 2) * R + K * R + K * nn + 2 * chunks * nn));
     TLS_HIP(ctx, ctx->d_sysrem_state.reserve(tlsdev::kSysremState));
-    double* at = ctx->d_sysrem.ptr;
-    auto take = [&](size_t count) { double* p = at; at += count; return p; };
-    double* d_y = take(cells);
+    double *d_y, *d_dy;
     tlsdev::SysremArgs a;
-    a.y = d_y; a.x = take(cells); a.flat = take(cells);
-    double* d_dy = dy ? take(cells) : nullptr;
-    a.dy = d_dy; a.w = dy ? take(cells) : take(R);   // (without dy: one weight a row)
-    a.trend = out_trend ? take(cells) : nullptr;
-    a.m = take(R);
-    a.c = take(K * R); a.a = take(K * nn); a.pnum = take(chunks * nn); a.pden = take(chunks * nn);
+    Arena L;
+    L.add(d_y, cells);  L.add(a.x, cells);  L.add(a.flat, cells);  L.add(d_dy, dy ? cells : 0);
+    L.add(a.w, dy ? cells : R);   // (without dy: one weight a row)
+    L.add(a.trend, out_trend ? cells : 0);  L.add(a.m, R);  L.add(a.c, K * R);  L.add(a.a, K * nn);
+    L.add(a.pnum, chunks * nn);   // chunk partials
+    L.add(a.pden, chunks * nn);
+    TLS_HIP(ctx, L.bind(ctx->d_sysrem));
+    a.y = d_y; a.dy = d_dy;
     a.state = ctx->d_sysrem_state.ptr; a.check = nullptr;
     a.n = (long long)n; a.rows = (long long)n_rows; a.chunks = (long long)chunks;
     a.tol = tol; a.n_components = (int)n_components; a.k = 0; a.iter = 0;
@@ -3017,15 +2998,14 @@ int tls_spectra(tls_ctx* ctx, const double* chi2, int64_t n, int64_t kernel, dou
     if (!chi2) n = ctx->plan.n_periods;
     if (kernel % 2 == 0) kernel += 1;                                   // stats.py:115-117
     const size_t nn = (size_t)n;
-    TLS_HIP(ctx, ctx->d_spec.reserve(4 * nn + 2));
-    double* d_in = ctx->d_chi2.ptr;
-    if (chi2) {
-        d_in = ctx->d_spec.ptr + 3 * nn + 2;
-        TLS_HIP(ctx, hipMemcpyAsync(d_in, chi2, nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
-    }
     tlsdev::SpectraArgs a;
-    a.chi2 = d_in; a.SR = ctx->d_spec.ptr; a.power_raw = ctx->d_spec.ptr + nn; a.power = ctx->d_spec.ptr + 2 * nn;
-    a.sde = ctx->d_spec.ptr + 3 * nn; a.n = (int)n; a.kernel = (int)kernel; a.detrend = n > 2 * kernel ? 1 : 0;
+    double* d_copy;   // the caller's chi2
+    Arena L;
+    L.add(a.SR, nn);  L.add(a.power_raw, nn);  L.add(a.power, nn);  L.add(a.sde, 2);  L.add(d_copy, nn);
+    TLS_HIP(ctx, L.bind(ctx->d_spec));
+    if (chi2) TLS_HIP(ctx, hipMemcpyAsync(d_copy, chi2, nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    a.chi2 = chi2 ? d_copy : ctx->d_chi2.ptr;
+    a.n = (int)n; a.kernel = (int)kernel; a.detrend = n > 2 * kernel ? 1 : 0;
     a.chi2_stride = 0; a.out_stride = 0; a.sde_stride = 0;
     hipLaunchKernelGGL(tlsdev::tls_spectra_head, dim3(1), dim3(1024), 0, main_stream(ctx), a);
     if (a.detrend) {
@@ -3056,7 +3036,8 @@ int tls_debug_folded(tls_ctx* ctx, double* out, int64_t capacity) {
     if (capacity < need) return fail(ctx, TLS_E_ARG, "tls_debug_folded: out holds fewer than n_periods * n doubles");
     if (need == 0) return TLS_OK;
     TLS_HIP(ctx, hipSetDevice(ctx->device));
-    DevBuf<double> d_out;
+    BufPool local;   // (freed at scope exit, on every path)
+    DevBuf<double> d_out(local, "d_out", kScratch);
     TLS_HIP(ctx, d_out.reserve((size_t)need));
     int rc = enqueue(ctx, false, false, d_out.ptr);
     if (rc == TLS_OK) {
@@ -3066,7 +3047,6 @@ int tls_debug_folded(tls_ctx* ctx, double* out, int64_t capacity) {
         if (e != hipSuccess) rc = fail(ctx, TLS_E_HIP, hipGetErrorString(e));
     }
     if (rc != TLS_OK) (void)hipStreamSynchronize(main_stream(ctx));
-    d_out.release();   // (on every path)
     return rc;
 }
 
@@ -3079,7 +3059,8 @@ int tls_debug_prefix(tls_ctx* ctx, double* out, int64_t capacity, int64_t* row_l
     if (capacity < need) return fail(ctx, TLS_E_ARG, "tls_debug_prefix: out holds fewer than n_periods * row_length doubles");
     if (need == 0) return TLS_OK;
     TLS_HIP(ctx, hipSetDevice(ctx->device));
-    DevBuf<double> d_out;
+    BufPool local;   // (freed at scope exit, on every path)
+    DevBuf<double> d_out(local, "d_out", kScratch);
     TLS_HIP(ctx, d_out.reserve((size_t)need));
     int rc = enqueue(ctx, false, false, nullptr, d_out.ptr);
     if (rc == TLS_OK) {
@@ -3089,7 +3070,6 @@ int tls_debug_prefix(tls_ctx* ctx, double* out, int64_t capacity, int64_t* row_l
         if (e != hipSuccess) rc = fail(ctx, TLS_E_HIP, hipGetErrorString(e));
     }
     if (rc != TLS_OK) (void)hipStreamSynchronize(main_stream(ctx));
-    d_out.release();   // (on every path)
     return rc;
 }
 
@@ -3099,7 +3079,8 @@ int tls_debug_period_cycles(tls_ctx* ctx, uint64_t* cycles, int64_t capacity) {
     if (capacity < ctx->plan.n_periods) return fail(ctx, TLS_E_ARG, "tls_debug_period_cycles: out holds fewer than n_periods entries");
     if (ctx->plan.n_periods == 0) return TLS_OK;
     TLS_HIP(ctx, hipSetDevice(ctx->device));
-    DevBuf<unsigned long long> d_out;
+    BufPool local;   // (freed at scope exit, on every path)
+    DevBuf<unsigned long long> d_out(local, "d_out", kScratch);
     TLS_HIP(ctx, d_out.reserve((size_t)ctx->plan.n_periods));
     hipError_t e = hipMemsetAsync(d_out.ptr, 0, (size_t)ctx->plan.n_periods * 8, main_stream(ctx));
     int rc = e == hipSuccess ? enqueue(ctx, false, false, nullptr, nullptr, d_out.ptr) : fail(ctx, TLS_E_HIP, hipGetErrorString(e));
@@ -3110,7 +3091,6 @@ int tls_debug_period_cycles(tls_ctx* ctx, uint64_t* cycles, int64_t capacity) {
     } else {
         (void)hipStreamSynchronize(main_stream(ctx));
     }
-    d_out.release();
     return rc;
 }
 
@@ -3118,7 +3098,8 @@ int tls_debug_cumsum(tls_ctx* ctx, const double* f, int64_t count, double* out, 
     if (!ctx || !f || !out || count < 0 || count > 100000000) return fail(ctx, TLS_E_ARG, "bad argument");
     if (threads < 64 || threads > 1024 || threads % 64) return fail(ctx, TLS_E_ARG, "threads must be a multiple of 64 in [64, 1024]");
     TLS_HIP(ctx, hipSetDevice(ctx->device));
-    DevBuf<double> d_f, d_out;
+    BufPool local;   // (freed at scope exit, on every path)
+    DevBuf<double> d_f(local, "d_f", kScratch), d_out(local, "d_out", kScratch);
     TLS_HIP(ctx, d_f.reserve((size_t)count));
     TLS_HIP(ctx, d_out.reserve((size_t)count + 1));
     if (count) TLS_HIP(ctx, hipMemcpyAsync(d_f.ptr, f, (size_t)count * 8, hipMemcpyHostToDevice, main_stream(ctx)));
@@ -3131,7 +3112,6 @@ int tls_debug_cumsum(tls_ctx* ctx, const double* f, int64_t count, double* out, 
     TLS_HIP(ctx, hipGetLastError());
     TLS_HIP(ctx, hipMemcpyAsync(out, d_out.ptr, ((size_t)count + 1) * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
     TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));
-    d_f.release(); d_out.release();
     return TLS_OK;
 }
 
@@ -3164,72 +3144,11 @@ int tls_debug_poison_lds(tls_ctx* ctx, uint32_t word) {
     hipLaunchKernelGGL(tls_poison_lds_kernel, dim3((unsigned)(4 * ctx->n_cu)), dim3(1024), 160 * 1024, main_stream(ctx), (unsigned int)word,
                        static_cast<unsigned int*>(nullptr));
     TLS_HIP(ctx, hipGetLastError());
-    // ... and the per-workgroup scratch in HBM (slabs, live-unit lists, stashed orders, the screen's and the sorts' scratch, the
-    // T0 fit's slabs), the post-search chain's arrays and every survey stage's buffer: all ones -- NaNs as doubles -- as fresh
-    // device memory may be.  Every buffer below is one whose next call uploads or writes all that it reads from it.
-    // Not smeared, because what they hold between calls is state by design:
-    //   d_plan, d_perm_table, d_band      the plan, its table of folded orders, and the band prefix the host caches by sigma
-    //   d_out, d_stage, d_gather          the results a later call may trust (tls_spectra without chi2, the staged / gathered
-    //                                     results of the comm calls)
-    //   d_queue, d_squeue, d_pqueues, d_tiles_done, d_check, d_phase, d_sysrem_state
-    //                                     queues and counters whose zero state between launches is the kernels' own invariant
-    //   d_curve_S0, d_curve_w0 and the batch slots (slot[].d_*)
-    //                                     the inputs and results of the survey batches
-    auto smear = [&](auto& buf) -> hipError_t {
-        return buf.ptr && buf.cap ? hipMemsetAsync(buf.ptr, 0xFF, buf.cap * sizeof(*buf.ptr), main_stream(ctx)) : hipSuccess;
-    };
-    TLS_HIP(ctx, smear(ctx->d_scratch));
-    TLS_HIP(ctx, smear(ctx->d_lists));
-    TLS_HIP(ctx, smear(ctx->d_perm));
-    TLS_HIP(ctx, smear(ctx->lane_b.d_lists));   // (lane B's: on the joined stream, which its next command waits for)
-    TLS_HIP(ctx, smear(ctx->lane_b.d_perm));
-    TLS_HIP(ctx, smear(ctx->d_split));
-    TLS_HIP(ctx, smear(ctx->d_park));
-    TLS_HIP(ctx, smear(ctx->d_partials));
-    TLS_HIP(ctx, smear(ctx->d_pack));
-    TLS_HIP(ctx, smear(ctx->d_scalar));
-    // the final T0 fit and the post-search chain
-    TLS_HIP(ctx, smear(ctx->d_ft));
-    TLS_HIP(ctx, smear(ctx->d_fy));
-    TLS_HIP(ctx, smear(ctx->d_fsig));
-    TLS_HIP(ctx, smear(ctx->d_fep));
-    TLS_HIP(ctx, smear(ctx->d_fres));
-    TLS_HIP(ctx, smear(ctx->d_fscratch));
-    TLS_HIP(ctx, smear(ctx->d_frot));
-    TLS_HIP(ctx, smear(ctx->d_frperm));
-    TLS_HIP(ctx, smear(ctx->d_pink));
-    TLS_HIP(ctx, smear(ctx->d_spec));
-    TLS_HIP(ctx, smear(ctx->d_tstats));
-    TLS_HIP(ctx, smear(ctx->d_tranges));
-    TLS_HIP(ctx, smear(ctx->d_models));
-    TLS_HIP(ctx, smear(ctx->d_peaks));
-    TLS_HIP(ctx, smear(ctx->d_peak_mask));
-    TLS_HIP(ctx, smear(ctx->d_pfit));
-    TLS_HIP(ctx, smear(ctx->d_pfep));
-    TLS_HIP(ctx, smear(ctx->d_pfres));
-    TLS_HIP(ctx, smear(ctx->d_pfstats));
-    TLS_HIP(ctx, smear(ctx->d_pfranges));
-    // the survey stages
-    TLS_HIP(ctx, smear(ctx->d_inject));
-    TLS_HIP(ctx, smear(ctx->d_inject_count));
-    TLS_HIP(ctx, smear(ctx->d_null));
-    TLS_HIP(ctx, smear(ctx->d_null_words));
-    TLS_HIP(ctx, smear(ctx->d_detrend));
-    TLS_HIP(ctx, smear(ctx->d_windows));
-    TLS_HIP(ctx, smear(ctx->d_protect));
-    TLS_HIP(ctx, smear(ctx->d_protect_bytes));
-    TLS_HIP(ctx, smear(ctx->d_sysrem));
-    TLS_HIP(ctx, smear(ctx->d_scan));
-    TLS_HIP(ctx, smear(ctx->d_single));
-    TLS_HIP(ctx, smear(ctx->d_times));
-    TLS_HIP(ctx, smear(ctx->d_vetting));
-    TLS_HIP(ctx, smear(ctx->d_shape));
-    TLS_HIP(ctx, smear(ctx->d_transit));
-    TLS_HIP(ctx, smear(ctx->d_centroid));
-    TLS_HIP(ctx, smear(ctx->d_views));
-    TLS_HIP(ctx, smear(ctx->d_gls));
-    TLS_HIP(ctx, smear(ctx->d_match));
-    TLS_HIP(ctx, smear(ctx->d_noise));
+    // ... and every scratch buffer of the context (the per-workgroup scratch in HBM, the T0 fit's slabs, the post-search
+    // chain's arrays, every survey stage's buffer): all ones -- NaNs as doubles -- as fresh device memory may be.  What a
+    // state buffer holds between calls is state by design; the reason stands beside each in tls_ctx.
+    for (const tlsmem::PoolBuf* b = ctx->pool.first; b; b = b->next)
+        if (b->kind == kScratch && b->base() && b->cap) TLS_HIP(ctx, hipMemsetAsync(b->base(), 0xFF, b->bytes(), main_stream(ctx)));
     return TLS_OK;
 }
 
@@ -3485,35 +3404,7 @@ int tls_debug_peak_phase_scans(tls_ctx* ctx, const double* y, int64_t n_curves, 
 
 int tls_debug_device_bytes(const tls_ctx* ctx, int64_t* total, int64_t* t0_fit_scratch) {
     if (!ctx || !total || !t0_fit_scratch) return TLS_E_ARG;
-    size_t sum = 0;
-    auto add = [&](const auto& b) { sum += b.cap * sizeof(*b.ptr); };
-    add(ctx->d_plan); add(ctx->d_out);
-    add(ctx->lane_b.d_squeue); add(ctx->lane_b.d_lists); add(ctx->lane_b.d_perm); add(ctx->lane_b.d_out); add(ctx->lane_b.d_y);
-    add(ctx->d_scratch); add(ctx->d_pack); add(ctx->d_gather); add(ctx->d_scalar); add(ctx->d_stage);
-    add(ctx->d_phase); add(ctx->d_check);
-    add(ctx->d_queue); add(ctx->d_squeue); add(ctx->d_lists); add(ctx->d_perm); add(ctx->d_perm_table); add(ctx->d_pqueues);
-    add(ctx->d_curve_S0); add(ctx->d_curve_w0);
-    for (const auto& sl : ctx->slot) {
-        add(sl.d_y); add(sl.d_w); add(sl.d_S0); add(sl.d_w0); add(sl.d_chi2); add(sl.d_depth); add(sl.d_row);
-    }
-    add(ctx->d_ft); add(ctx->d_fy); add(ctx->d_fsig); add(ctx->d_fep); add(ctx->d_fres); add(ctx->d_fscratch);
-    add(ctx->d_pink); add(ctx->d_frot); add(ctx->d_frperm); add(ctx->d_spec); add(ctx->d_tstats); add(ctx->d_tranges); add(ctx->d_models);
-    add(ctx->d_peaks); add(ctx->d_peak_mask);
-    add(ctx->d_pfit); add(ctx->d_pfep); add(ctx->d_pfres); add(ctx->d_pfstats); add(ctx->d_pfranges);
-    add(ctx->d_scan);
-    add(ctx->d_single);
-    add(ctx->d_times);
-    add(ctx->d_vetting);
-    add(ctx->d_shape);
-    add(ctx->d_transit);
-    add(ctx->d_centroid);
-    add(ctx->d_views);
-    add(ctx->d_gls);
-    add(ctx->d_match);
-    add(ctx->d_noise);
-    add(ctx->d_partials); add(ctx->d_tiles_done);
-    add(ctx->d_split); add(ctx->d_park); add(ctx->d_band);
-    *total = (int64_t)sum;
+    *total = (int64_t)ctx->pool.bytes();
     *t0_fit_scratch = (int64_t)(ctx->d_fscratch.cap * sizeof(double));
     return TLS_OK;
 }
@@ -3911,15 +3802,14 @@ int tls_phase_scan(tls_ctx* ctx, const double* t, const double* y, int64_t n, in
     }
     TLS_HIP(ctx, hipSetDevice(ctx->device));
     const size_t nn = (size_t)n, rows = (size_t)n_curves, fits = (size_t)n_fits, words = (size_t)tlsdev::kPhaseWords;
-    // t | y rows | period | T0 | duration | records | curve of fit (the whole batch at once: DESIGN.md "Phase scan")
-    TLS_HIP(ctx, ctx->d_scan.reserve(nn + rows * nn + 3 * fits + words * fits + (fits + 1) / 2));
-    double* d_t = ctx->d_scan.ptr;
-    double* d_y = d_t + nn;
-    double* d_period = d_y + rows * nn;
-    double* d_T0 = d_period + fits;
-    double* d_duration = d_T0 + fits;
-    double* d_out = d_duration + fits;
-    int* d_curve = reinterpret_cast<int*>(d_out + words * fits);
+    // (the whole batch at once: DESIGN.md "Phase scan")
+    double *d_t, *d_y, *d_period, *d_T0, *d_duration, *d_out;
+    int* d_curve;
+    Arena L;
+    L.add(d_t, nn);  L.add(d_y, rows * nn);  L.add(d_period, fits);  L.add(d_T0, fits);  L.add(d_duration, fits);
+    L.add(d_out, words * fits);   // records
+    L.add(d_curve, fits);         // curve of fit
+    TLS_HIP(ctx, L.bind(ctx->d_scan));
     TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     TLS_HIP(ctx, hipMemcpyAsync(d_y, y, rows * nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     TLS_HIP(ctx, hipMemcpyAsync(d_period, period, fits * 8, hipMemcpyHostToDevice, main_stream(ctx)));
@@ -3941,7 +3831,6 @@ int tls_phase_scan(tls_ctx* ctx, const double* t, const double* y, int64_t n, in
 // and the selection kernel, one workgroup a curve, slab by slab; the planes stay in the context's scratch unless asked for
 static_assert(sizeof(tls_single_event) == tlsdev::kSingleEventWords * 8, "tls_single_event is the kernel's record");
 static_assert(TLS_SINGLE_MAX_WIDTH == tlsdev::kSingleMaxWidth && TLS_SINGLE_MAX_K == tlsdev::kSingleMaxK, "the header's limits");
-static_assert(sizeof(tlsdev::SingleRow) == 16, "two doubles a row");
 
 int tls_single_transits(tls_ctx* ctx, const double* t, const double* y, const double* dy, int64_t n, int64_t n_curves,
                         const double* shape_values, const int64_t* shape_offset, const int64_t* width, const double* span_max,
@@ -3967,18 +3856,16 @@ int tls_single_transits(tls_ctx* ctx, const double* t, const double* y, const do
     // curves per launch: at most 256 MB of rows and planes (as the detrending slabs), 36 bytes a point
     const int64_t slab = std::max<int64_t>(1, std::min<int64_t>({n_curves, (int64_t)65535, (int64_t)((256u << 20) / (36 * nn))}));
     const size_t sl = (size_t)slab;
-    // t | rows | taps | of one slab: y | dy | ses | depth | events | n_events | row
-    TLS_HIP(ctx, ctx->d_single.reserve(nn + 2 * (size_t)n_rows + 2 * n_taps + 4 * sl * nn + sl * words + sl + (sl * nn + 1) / 2));
-    double* d_t = ctx->d_single.ptr;
-    tlsdev::SingleRow* d_rows = reinterpret_cast<tlsdev::SingleRow*>(d_t + nn);
-    double* d_taps = d_t + nn + 2 * (size_t)n_rows;
-    double* d_y = d_taps + 2 * n_taps;
-    double* d_dy = d_y + sl * nn;
-    double* d_ses = d_dy + sl * nn;
-    double* d_depth = d_ses + sl * nn;
-    double* d_events = d_depth + sl * nn;
-    long long* d_n_events = reinterpret_cast<long long*>(d_events + sl * words);
-    int* d_row = reinterpret_cast<int*>(d_events + sl * words + sl);
+    double *d_t, *d_taps, *d_y, *d_dy, *d_ses, *d_depth, *d_events;
+    tlsdev::SingleRow* d_rows;
+    long long* d_n_events;
+    int* d_row;
+    Arena L;
+    L.add(d_t, nn);  L.add(d_rows, (size_t)n_rows);  L.add(d_taps, 2 * n_taps);
+    L.add(d_y, sl * nn);          // of one slab, from here on
+    L.add(d_dy, sl * nn);  L.add(d_ses, sl * nn);  L.add(d_depth, sl * nn);  L.add(d_events, sl * words);
+    L.add(d_n_events, sl);  L.add(d_row, sl * nn);
+    TLS_HIP(ctx, L.bind(ctx->d_single));
     if ((rc = ensure_check_counters(ctx))) return rc;
     tlsdev::SingleArgs a;
     a.t = d_t; a.y = d_y; a.dy = d_dy; a.rows = d_rows; a.taps = d_taps;
@@ -4064,21 +3951,17 @@ int tls_transit_times(tls_ctx* ctx, const double* t, const double* y, const doub
     const size_t budget = 256u << 20;
     const size_t cs = std::max<size_t>(1, std::min<size_t>({(size_t)n_curves, 1024, budget / (32 * nn)}));
     const size_t sl = std::max<size_t>(1, std::min<size_t>({(size_t)n_fits, 1024, budget / (8 * time_words)}));
-    // of one slab: pairs | y | dy | records | times | period | T0 | slot, row, reach;  t | rows | taps | slopes
-    TLS_HIP(ctx, ctx->d_times.reserve(4 * cs * nn + sl * (eph_words + time_words + 2) + (3 * sl + 1) / 2
-                                      + nn + 2 * (size_t)n_rows + 5 * n_taps));
-    double2* d_pairs = reinterpret_cast<double2*>(ctx->d_times.ptr);           // (the allocation's start: 16-byte aligned)
-    double* d_y = ctx->d_times.ptr + 2 * cs * nn;
-    double* d_dy = d_y + cs * nn;
-    double* d_out = d_dy + cs * nn;
-    double* d_out_times = d_out + sl * eph_words;
-    double* d_period = d_out_times + sl * time_words;
-    double* d_T0 = d_period + sl;
-    int* d_ints = reinterpret_cast<int*>(d_T0 + sl);
-    double* d_t = d_T0 + sl + (3 * sl + 1) / 2;
-    tlsdev::SingleRow* d_rows = reinterpret_cast<tlsdev::SingleRow*>(d_t + nn);
-    double* d_taps = d_t + nn + 2 * (size_t)n_rows;
-    double* d_slopes = d_taps + 2 * n_taps;
+    double2* d_pairs;
+    double *d_y, *d_dy, *d_out, *d_out_times, *d_period, *d_T0, *d_t, *d_taps, *d_slopes;
+    int* d_ints;
+    tlsdev::SingleRow* d_rows;
+    Arena L;
+    L.add(d_pairs, cs * nn);            // of one slab, down to the int columns
+    L.add(d_y, cs * nn);  L.add(d_dy, cs * nn);  L.add(d_out, sl * eph_words);  L.add(d_out_times, sl * time_words);
+    L.add(d_period, sl);  L.add(d_T0, sl);  L.add(d_ints, 3 * sl);   // slot | row | reach
+    L.add(d_t, nn);                     // what every slab shares, from here on
+    L.add(d_rows, (size_t)n_rows);  L.add(d_taps, 2 * n_taps);  L.add(d_slopes, 3 * n_taps);
+    TLS_HIP(ctx, L.bind(ctx->d_times));
     if ((rc = ensure_check_counters(ctx))) return rc;
     tlsdev::TimesPairsArgs p;
     p.y = d_y; p.dy = d_dy; p.pairs = d_pairs;
@@ -4164,23 +4047,19 @@ int tls_event_vetting(tls_ctx* ctx, const double* t, const double* y, const doub
     const size_t budget = 256u << 20;
     const size_t cs = std::max<size_t>(1, std::min<size_t>({(size_t)n_curves, 1024, budget / (32 * nn)}));
     const size_t sl = std::max<size_t>(1, std::min<size_t>({(size_t)n_fits, 1024, budget / (8 * (event_words + 2 * me))}));
-    // of one slab: pairs | held | y | dy | summaries | events | period | T0 | chase_span | slot, row, reach, chase, guard;
-    // t | rows | taps
-    TLS_HIP(ctx, ctx->d_vetting.reserve(4 * cs * nn + sl * (2 * me + sum_words + event_words + 3) + (5 * sl + 1) / 2
-                                        + nn + 2 * (size_t)n_rows + 2 * n_taps));
-    double2* d_pairs = reinterpret_cast<double2*>(ctx->d_vetting.ptr);         // (the allocation's start: 16-byte aligned)
-    double2* d_held = d_pairs + cs * nn;
-    double* d_y = ctx->d_vetting.ptr + 2 * cs * nn + 2 * sl * me;
-    double* d_dy = d_y + cs * nn;
-    double* d_out = d_dy + cs * nn;
-    double* d_out_events = d_out + sl * sum_words;
-    double* d_period = d_out_events + sl * event_words;
-    double* d_T0 = d_period + sl;
-    double* d_span = d_T0 + sl;
-    int* d_ints = reinterpret_cast<int*>(d_span + sl);
-    double* d_t = d_span + sl + (5 * sl + 1) / 2;
-    tlsdev::SingleRow* d_rows = reinterpret_cast<tlsdev::SingleRow*>(d_t + nn);
-    double* d_taps = d_t + nn + 2 * (size_t)n_rows;
+    double2 *d_pairs, *d_held;
+    double *d_y, *d_dy, *d_out, *d_out_events, *d_period, *d_T0, *d_span, *d_t, *d_taps;
+    int* d_ints;
+    tlsdev::SingleRow* d_rows;
+    Arena L;
+    L.add(d_pairs, cs * nn);            // of one slab, down to the int columns
+    L.add(d_held, sl * me);             // held (N, D)
+    L.add(d_y, cs * nn);  L.add(d_dy, cs * nn);  L.add(d_out, sl * sum_words);  L.add(d_out_events, sl * event_words);
+    L.add(d_period, sl);  L.add(d_T0, sl);  L.add(d_span, sl);
+    L.add(d_ints, 5 * sl);              // slot | row | reach | chase | guard
+    L.add(d_t, nn);                     // what every slab shares, from here on
+    L.add(d_rows, (size_t)n_rows);  L.add(d_taps, 2 * n_taps);
+    TLS_HIP(ctx, L.bind(ctx->d_vetting));
     if ((rc = ensure_check_counters(ctx))) return rc;
     tlsdev::TimesPairsArgs p;
     p.y = d_y; p.dy = d_dy; p.pairs = d_pairs;
@@ -4250,28 +4129,23 @@ int tls_shape_fit(tls_ctx* ctx, const double* t, const double* y, const double* 
         || (rc = check_time_stamps(ctx, "shape fit", t, n)) || (rc = check_curves(ctx, "shape fit", curve, n_fits, n_curves)))
         return rc;
     TLS_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t nn = (size_t)n, words = tlsdev::kShapeWords, tables = (size_t)(nT + nQ + nS);
+    const size_t nn = (size_t)n, words = tlsdev::kShapeWords;
     // a slab: at most 1024 candidates on at most 1024 curves, 256 MB of curves (32 bytes a point); the workgroups of a launch:
     // at most 1024, 256 MB of member scratch (24 bytes a point each)
     const size_t budget = 256u << 20;
     const size_t cs = std::max<size_t>(1, std::min<size_t>({(size_t)n_curves, 1024, budget / (32 * nn)}));
     const size_t sl = std::min<size_t>((size_t)n_fits, 1024);
     const size_t groups = std::max<size_t>(1, std::min<size_t>({sl, (size_t)tlsdev::kShapeMaxGroups, budget / (24 * nn)}));
-    // of one slab: pairs | y | dy | records | period | T0 | duration | slot;  t | ratio | ingress | shift | scratch
-    TLS_HIP(ctx, ctx->d_shape.reserve(4 * cs * nn + sl * (words + 3) + (sl + 1) / 2 + nn + tables + 3 * groups * nn));
-    double2* d_pairs = reinterpret_cast<double2*>(ctx->d_shape.ptr);           // (the allocation's start: 16-byte aligned)
-    double* d_y = ctx->d_shape.ptr + 2 * cs * nn;
-    double* d_dy = d_y + cs * nn;
-    double* d_out = d_dy + cs * nn;
-    double* d_period = d_out + sl * words;
-    double* d_T0 = d_period + sl;
-    double* d_duration = d_T0 + sl;
-    int* d_slot = reinterpret_cast<int*>(d_duration + sl);
-    double* d_t = d_duration + sl + (sl + 1) / 2;
-    double* d_ratio = d_t + nn;
-    double* d_ingress = d_ratio + nT;
-    double* d_shift = d_ingress + nQ;
-    double* d_scratch = d_shift + nS;
+    double2* d_pairs;
+    double *d_y, *d_dy, *d_out, *d_period, *d_T0, *d_duration, *d_t, *d_ratio, *d_ingress, *d_shift, *d_scratch;
+    int* d_slot;
+    Arena L;
+    L.add(d_pairs, cs * nn);            // of one slab, down to the slots
+    L.add(d_y, cs * nn);  L.add(d_dy, cs * nn);  L.add(d_out, sl * words);  L.add(d_period, sl);  L.add(d_T0, sl);
+    L.add(d_duration, sl);  L.add(d_slot, sl);
+    L.add(d_t, nn);                     // what every slab shares, from here on
+    L.add(d_ratio, (size_t)nT);  L.add(d_ingress, (size_t)nQ);  L.add(d_shift, (size_t)nS);  L.add(d_scratch, 3 * groups * nn);
+    TLS_HIP(ctx, L.bind(ctx->d_shape));
     if ((rc = ensure_check_counters(ctx))) return rc;
     tlsdev::TimesPairsArgs p;
     p.y = d_y; p.dy = d_dy; p.pairs = d_pairs;
@@ -4358,31 +4232,24 @@ int tls_transit_fit(tls_ctx* ctx, const double* t, const double* y, const double
         return rc;
     TLS_HIP(ctx, hipSetDevice(ctx->device));
     const size_t nn = (size_t)n, words = tlsdev::kTransitWords, units = (size_t)(n_b * n_t * n_s);
-    const size_t rows = (size_t)n_k, row_words = (size_t)M + 1, tables = rows + rows * row_words + (size_t)(n_b + n_t + n_s + n_sub);
+    const size_t rows = (size_t)n_k, row_words = (size_t)M + 1;
     // a slab: at most 512 candidates on at most 512 curves, 256 MB of curves (32 bytes a point); the workgroups of a launch:
     // at most 512, 256 MB of scratch (24 bytes a point and 16 bytes a unit each)
     const size_t budget = 256u << 20, stretch = 3 * nn + 2 * units;
     const size_t cs = std::max<size_t>(1, std::min<size_t>({(size_t)n_curves, (size_t)tlsdev::kTransitSlab, budget / (32 * nn)}));
     const size_t sl = std::min<size_t>((size_t)n_fits, (size_t)tlsdev::kTransitSlab);
     const size_t groups = std::max<size_t>(1, std::min<size_t>(sl, budget / (8 * stretch)));
-    // of one slab: pairs | y | dy | records | period | T0 | duration | slot, row_first;  t | the tables | scratch
-    TLS_HIP(ctx, ctx->d_transit.reserve(4 * cs * nn + sl * (words + 3) + sl + nn + tables + groups * stretch));
-    double2* d_pairs = reinterpret_cast<double2*>(ctx->d_transit.ptr);         // (the allocation's start: 16-byte aligned)
-    double* d_y = ctx->d_transit.ptr + 2 * cs * nn;
-    double* d_dy = d_y + cs * nn;
-    double* d_out = d_dy + cs * nn;
-    double* d_period = d_out + sl * words;
-    double* d_T0 = d_period + sl;
-    double* d_duration = d_T0 + sl;
-    int* d_ints = reinterpret_cast<int*>(d_duration + sl);                     // slot [sl] | row_first [sl]
-    double* d_t = d_duration + sl + sl;
-    double* d_k = d_t + nn;
-    double* d_profile = d_k + rows;
-    double* d_impact = d_profile + rows * row_words;
-    double* d_ratio = d_impact + n_b;
-    double* d_shift = d_ratio + n_t;
-    double* d_sub = d_shift + n_s;
-    double* d_scratch = d_sub + n_sub;
+    double2* d_pairs;
+    double *d_y, *d_dy, *d_out, *d_period, *d_T0, *d_duration, *d_t, *d_k, *d_profile, *d_impact, *d_ratio, *d_shift, *d_sub, *d_scratch;
+    int* d_ints;
+    Arena L;
+    L.add(d_pairs, cs * nn);            // of one slab, down to the int columns
+    L.add(d_y, cs * nn);  L.add(d_dy, cs * nn);  L.add(d_out, sl * words);  L.add(d_period, sl);  L.add(d_T0, sl);
+    L.add(d_duration, sl);  L.add(d_ints, 2 * sl);   // slot | row_first
+    L.add(d_t, nn);                     // what every slab shares, from here on
+    L.add(d_k, rows);  L.add(d_profile, rows * row_words);  L.add(d_impact, (size_t)n_b);  L.add(d_ratio, (size_t)n_t);
+    L.add(d_shift, (size_t)n_s);  L.add(d_sub, (size_t)n_sub);  L.add(d_scratch, groups * stretch);
+    TLS_HIP(ctx, L.bind(ctx->d_transit));
     if ((rc = ensure_check_counters(ctx))) return rc;
     tlsdev::TimesPairsArgs p;
     p.y = d_y; p.dy = d_dy; p.pairs = d_pairs;
@@ -4452,19 +4319,16 @@ int tls_centroid_test(tls_ctx* ctx, const double* t, const double* y, const doub
     const size_t stretch = max_epochs > tlsdev::kCentroidLdsEpochs
         ? (size_t)(max_epochs - tlsdev::kCentroidLdsEpochs) * tlsdev::kCentroidEpochWords : 0;
     const size_t groups = std::max<size_t>(1, std::min<size_t>({sl, (size_t)tlsdev::kCentroidMaxGroups, stretch ? budget / (8 * stretch) : sl}));
-    // of one slab: y | cx | cy | records | period | T0 | duration | slot;  t | shape | scratch
-    TLS_HIP(ctx, ctx->d_centroid.reserve(3 * cs * nn + sl * (words + 3) + (sl + 1) / 2 + nn + ll + groups * stretch));
-    double* d_y = ctx->d_centroid.ptr;
-    double* d_cx = d_y + cs * nn;
-    double* d_cy = d_cx + cs * nn;
-    double* d_out = d_cy + cs * nn;
-    double* d_period = d_out + sl * words;
-    double* d_T0 = d_period + sl;
-    double* d_duration = d_T0 + sl;
-    int* d_slot = reinterpret_cast<int*>(d_duration + sl);
-    double* d_t = d_duration + sl + (sl + 1) / 2;
-    double* d_b = d_t + nn;
-    double* d_scratch = d_b + ll;
+    double *d_y, *d_cx, *d_cy, *d_out, *d_period, *d_T0, *d_duration, *d_t, *d_b, *d_scratch;
+    int* d_slot;
+    Arena A;
+    A.add(d_y, cs * nn);                // of one slab, down to the slots
+    A.add(d_cx, cs * nn);  A.add(d_cy, cs * nn);  A.add(d_out, sl * words);  A.add(d_period, sl);  A.add(d_T0, sl);
+    A.add(d_duration, sl);  A.add(d_slot, sl);
+    A.add(d_t, nn);                     // what every slab shares, from here on
+    A.add(d_b, ll);                     // the shape
+    A.add(d_scratch, groups * stretch);
+    TLS_HIP(ctx, A.bind(ctx->d_centroid));
     if ((rc = ensure_check_counters(ctx))) return rc;
     tlsdev::CentroidArgs a;
     a.t = d_t; a.y = d_y; a.cx = d_cx; a.cy = d_cy; a.slot = d_slot; a.period = d_period; a.T0 = d_T0; a.duration = d_duration;
@@ -4521,23 +4385,16 @@ int tls_folded_views(tls_ctx* ctx, const double* t, const double* y, int64_t n, 
     const size_t sl = std::min<size_t>({(size_t)n_fits, (size_t)tlsdev::kViewsSlab, std::max<size_t>(1, budget / (12 * (ng + nl)))});
     const size_t stretch = n > tlsdev::kViewsLdsPoints ? tlsdev::views_scratch_words(nn) : 0;
     const size_t groups = std::max<size_t>(1, std::min<size_t>({sl, (size_t)tlsdev::kViewsMaxGroups, stretch ? budget / (8 * stretch) : sl}));
-    const size_t ints = (sl * (1 + ng + nl) + 1) / 2;        // slot | global counts | local counts, in doubles
-    // of one slab: y | records | period | T0 | duration | secondary | global and local medians | slot | global and local
-    // counts;  t | scratch
-    TLS_HIP(ctx, ctx->d_views.reserve(cs * nn + sl * (words + 4 + ng + nl) + ints + nn + groups * stretch));
-    double* d_y = ctx->d_views.ptr;
-    double* d_out = d_y + cs * nn;
-    double* d_period = d_out + sl * words;
-    double* d_T0 = d_period + sl;
-    double* d_duration = d_T0 + sl;
-    double* d_secondary = d_duration + sl;
-    double* d_gmed = d_secondary + sl;
-    double* d_lmed = d_gmed + sl * ng;
-    int* d_slot = reinterpret_cast<int*>(d_lmed + sl * nl);
-    int* d_gcnt = d_slot + sl;
-    int* d_lcnt = d_gcnt + sl * ng;
-    double* d_t = d_lmed + sl * nl + ints;
-    double* d_scratch = d_t + nn;
+    double *d_y, *d_out, *d_period, *d_T0, *d_duration, *d_secondary, *d_gmed, *d_lmed, *d_t, *d_scratch;
+    int *d_slot, *d_gcnt, *d_lcnt;
+    Arena L;
+    L.add(d_y, cs * nn);                // of one slab, down to the counts
+    L.add(d_out, sl * words);  L.add(d_period, sl);  L.add(d_T0, sl);  L.add(d_duration, sl);
+    L.add(d_secondary, sl);             // (held whether or not the call gives secondary phases: the slab's size does not depend on it)
+    L.add(d_gmed, sl * ng);  L.add(d_lmed, sl * nl);  L.add(d_slot, sl);  L.add(d_gcnt, sl * ng);  L.add(d_lcnt, sl * nl);
+    L.add(d_t, nn);                     // what every slab shares, from here on
+    L.add(d_scratch, groups * stretch);
+    TLS_HIP(ctx, L.bind(ctx->d_views));
     if ((rc = ensure_check_counters(ctx))) return rc;
     tlsdev::ViewsArgs a;
     a.t = d_t; a.y = d_y; a.slot = d_slot; a.period = d_period; a.T0 = d_T0; a.duration = d_duration;
@@ -4617,12 +4474,13 @@ int tls_nudft(tls_ctx* ctx, const double* rows, int64_t n_rows, int64_t n, const
     TLS_HIP(ctx, hipSetDevice(ctx->device));
     const size_t nn = (size_t)n, nf = (size_t)n_freq;
     const int64_t slab = gls_slab(n_rows, n, n_freq);
-    // sums [slab][F] pairs | rows [slab][n] | t | f
-    TLS_HIP(ctx, ctx->d_gls.reserve(2 * (size_t)slab * nf + (size_t)slab * nn + nn + nf));
-    double2* d_out = reinterpret_cast<double2*>(ctx->d_gls.ptr);
-    double* d_rows = ctx->d_gls.ptr + 2 * (size_t)slab * nf;
-    double* d_t = d_rows + (size_t)slab * nn;
-    double* d_f = d_t + nn;
+    double2* d_out;
+    double *d_rows, *d_t, *d_f;
+    Arena L;
+    L.add(d_out, (size_t)slab * nf);    // the sums of one slab
+    L.add(d_rows, (size_t)slab * nn);   // ... and its rows
+    L.add(d_t, nn);  L.add(d_f, nf);
+    TLS_HIP(ctx, L.bind(ctx->d_gls));
     TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     TLS_HIP(ctx, hipMemcpyAsync(d_f, frequencies, nf * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     for (int64_t k0 = 0; k0 < n_rows; k0 += slab) {
@@ -4657,27 +4515,20 @@ int tls_lomb_scargle(tls_ctx* ctx, const double* t, const double* y, const doubl
     const size_t nn = (size_t)n, nf = (size_t)n_freq;
     const int64_t slab = gls_slab(n_curves, n, n_freq);
     const size_t sl = (size_t)slab, wl = dy ? sl : 1, words = k ? pk.words() : 0;
-    // (YC, YS) | (C, S) | (C2, S2) pairs; power | amplitude | phase; y | dy | a | w rows; mean | variance; t | f | 2 f | 1 / f; peaks
-    TLS_HIP(ctx, ctx->d_gls.reserve(2 * sl * nf + 4 * wl * nf + 3 * sl * nf + (dy ? 3 : 2) * sl * nn + wl * nn + 2 * sl + nn + 3 * nf
-                                    + sl * words));
+    double2 *d_yc, *d_cs, *d_cs2;
+    double *d_power, *d_amplitude, *d_phase, *d_y, *d_dy, *d_a, *d_w, *d_mean, *d_var, *d_t, *d_f, *d_f2, *d_periods, *d_peaks;
+    Arena L;
+    L.add(d_yc, sl * nf);               // (YC, YS)
+    L.add(d_cs, wl * nf);               // (C, S)
+    L.add(d_cs2, wl * nf);              // (C2, S2)
+    L.add(d_power, sl * nf);  L.add(d_amplitude, sl * nf);  L.add(d_phase, sl * nf);  L.add(d_y, sl * nn);
+    L.add(d_dy, dy ? sl * nn : 0);  L.add(d_a, sl * nn);   // the rows the transform reads
+    L.add(d_w, wl * nn);                // ... and their weights
+    L.add(d_mean, sl);  L.add(d_var, sl);  L.add(d_t, nn);  L.add(d_f, nf);  L.add(d_f2, nf);   // 2 f
+    L.add(d_periods, nf);               // 1 / f
+    L.add(d_peaks, sl * words);
+    TLS_HIP(ctx, L.bind(ctx->d_gls));
     if (k && (rc = reserve_peak_mask(ctx, slab, n_freq))) return rc;
-    double2* d_yc = reinterpret_cast<double2*>(ctx->d_gls.ptr);
-    double2* d_cs = d_yc + sl * nf;
-    double2* d_cs2 = d_cs + wl * nf;
-    double* d_power = reinterpret_cast<double*>(d_cs2 + wl * nf);
-    double* d_amplitude = d_power + sl * nf;
-    double* d_phase = d_amplitude + sl * nf;
-    double* d_y = d_phase + sl * nf;
-    double* d_dy = dy ? d_y + sl * nn : nullptr;
-    double* d_a = d_y + (dy ? 2 : 1) * sl * nn;
-    double* d_w = d_a + sl * nn;
-    double* d_mean = d_w + wl * nn;
-    double* d_var = d_mean + sl;
-    double* d_t = d_var + sl;
-    double* d_f = d_t + nn;
-    double* d_f2 = d_f + nf;
-    double* d_periods = d_f2 + nf;
-    double* d_peaks = d_periods + nf;
     std::vector<double> twice(nf), periods(nf), h_peaks(sl * words);
     for (size_t i = 0; i < nf; ++i) { twice[i] = 2.0 * frequencies[i]; periods[i] = 1.0 / frequencies[i]; }
     TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
@@ -4768,20 +4619,15 @@ int tls_sine_test(tls_ctx* ctx, const double* t, const double* y, const double* 
     // a slab: at most 1024 candidates on at most 1024 curves, 256 MB of curves
     const size_t cs = std::max<size_t>(1, std::min<size_t>({(size_t)n_curves, 1024, (256u << 20) / (16 * nn)}));
     const size_t sl = std::min<size_t>((size_t)n_fits, 1024);
-    const size_t per_fit = tlsdev::kSineWords + nH * (tlsdev::kSineHarmonicWords + 6);
-    // of one slab: y | dy | records | harmonic records | sums | period | T0 | duration | slot;  t | harmonics
-    TLS_HIP(ctx, ctx->d_gls.reserve(2 * cs * nn + sl * (per_fit + 3) + (sl + 1) / 2 + nn + nH));
-    double* d_y = ctx->d_gls.ptr;
-    double* d_dy = d_y + cs * nn;
-    double* d_out = d_dy + cs * nn;
-    double* d_out_h = d_out + sl * tlsdev::kSineWords;
-    double* d_sums = d_out_h + sl * nH * tlsdev::kSineHarmonicWords;
-    double* d_period = d_sums + sl * nH * 6;
-    double* d_T0 = d_period + sl;
-    double* d_duration = d_T0 + sl;
-    int* d_slot = reinterpret_cast<int*>(d_duration + sl);
-    double* d_t = d_duration + sl + (sl + 1) / 2;
-    double* d_harmonics = d_t + nn;
+    double *d_y, *d_dy, *d_out, *d_out_h, *d_sums, *d_period, *d_T0, *d_duration, *d_t, *d_harmonics;
+    int* d_slot;
+    Arena L;
+    L.add(d_y, cs * nn);                // of one slab, down to the slots
+    L.add(d_dy, cs * nn);  L.add(d_out, sl * tlsdev::kSineWords);  L.add(d_out_h, sl * nH * tlsdev::kSineHarmonicWords);
+    L.add(d_sums, sl * nH * 6);  L.add(d_period, sl);  L.add(d_T0, sl);  L.add(d_duration, sl);  L.add(d_slot, sl);
+    L.add(d_t, nn);                     // what every slab shares, from here on
+    L.add(d_harmonics, nH);
+    TLS_HIP(ctx, L.bind(ctx->d_gls));
     tlsdev::SineArgs a;
     a.t = d_t; a.y = d_y; a.dy = dy ? d_dy : nullptr; a.slot = d_slot; a.period = d_period;
     a.T0 = T0 ? d_T0 : nullptr; a.duration = T0 ? d_duration : nullptr; a.harmonics = d_harmonics;
@@ -4834,36 +4680,24 @@ static int prewhiten(tls_ctx* ctx, const double* t, const double* y, const doubl
     const size_t wl = own ? sl : 1;
     if (masked) TLS_HIP(ctx, ctx->d_protect_bytes.reserve(sl * nn));
     const unsigned char* d_mask = masked ? ctx->d_protect_bytes.ptr : nullptr;
-    // (YC, YS) | (C, S) | (C2, S2) pairs; power | amplitude | phase; y | r | dy | a (flat at the end) | w | trend; mean_0 | mean |
-    // variance | status; terms | sums; t | f | 2 f; n_iterations | counts | active; steps
-    const size_t ints = (sl + 1) / 2;
-    TLS_HIP(ctx, ctx->d_gls.reserve(2 * sl * nf + 4 * wl * nf + 3 * sl * nf + (dy ? 5 : 4) * sl * nn + wl * nn + 4 * sl
-                                    + sl * KH * (words + 6) + nn + 2 * nf + sl + K + ints + (out_steps ? (KH + 1) * sl * nn : 0)));
-    double2* d_yc = reinterpret_cast<double2*>(ctx->d_gls.ptr);
-    double2* d_cs = d_yc + sl * nf;
-    double2* d_cs2 = d_cs + wl * nf;
-    double* d_power = reinterpret_cast<double*>(d_cs2 + wl * nf);
-    double* d_amplitude = d_power + sl * nf;
-    double* d_phase = d_amplitude + sl * nf;
-    double* d_y = d_phase + sl * nf;
-    double* d_r = d_y + sl * nn;
-    double* d_dy = dy ? d_r + sl * nn : nullptr;
-    double* d_a = d_r + (dy ? 2 : 1) * sl * nn;
-    double* d_w = d_a + sl * nn;
-    double* d_trend = d_w + wl * nn;
-    double* d_mean0 = d_trend + sl * nn;
-    double* d_mean = d_mean0 + sl;
-    double* d_var = d_mean + sl;
-    double* d_status = d_var + sl;
-    double* d_terms = d_status + sl;
-    double* d_sums = d_terms + sl * KH * words;
-    double* d_t = d_sums + sl * KH * 6;
-    double* d_f = d_t + nn;
-    double* d_f2 = d_f + nf;
-    long long* d_iterations = reinterpret_cast<long long*>(d_f2 + nf);
-    unsigned long long* d_counts = reinterpret_cast<unsigned long long*>(d_iterations + sl);
-    int* d_active = reinterpret_cast<int*>(d_counts + K);
-    double* d_steps = out_steps ? reinterpret_cast<double*>(d_counts + K) + ints : nullptr;
+    double2 *d_yc, *d_cs, *d_cs2;
+    double *d_power, *d_amplitude, *d_phase, *d_y, *d_r, *d_dy, *d_a, *d_w, *d_trend, *d_mean0, *d_mean, *d_var, *d_status, *d_terms,
+        *d_sums, *d_t, *d_f, *d_f2, *d_steps;
+    long long* d_iterations;
+    unsigned long long* d_counts;
+    int* d_active;
+    Arena L;
+    L.add(d_yc, sl * nf);               // (YC, YS)
+    L.add(d_cs, wl * nf);               // (C, S)
+    L.add(d_cs2, wl * nf);              // (C2, S2)
+    L.add(d_power, sl * nf);  L.add(d_amplitude, sl * nf);  L.add(d_phase, sl * nf);  L.add(d_y, sl * nn);  L.add(d_r, sl * nn);
+    L.add(d_dy, dy ? sl * nn : 0);  L.add(d_a, sl * nn);   // (flat at the end)
+    L.add(d_w, wl * nn);  L.add(d_trend, sl * nn);  L.add(d_mean0, sl);  L.add(d_mean, sl);  L.add(d_var, sl);
+    L.add(d_status, sl);  L.add(d_terms, sl * KH * words);  L.add(d_sums, sl * KH * 6);  L.add(d_t, nn);  L.add(d_f, nf);
+    L.add(d_f2, nf);                    // 2 f
+    L.add(d_iterations, sl);  L.add(d_counts, K);   // (behind the iterations: one memset clears both)
+    L.add(d_active, sl);  L.add(d_steps, out_steps ? (KH + 1) * sl * nn : 0);
+    TLS_HIP(ctx, L.bind(ctx->d_gls));
     const bool lds = n <= tlsdev::kPrewhitenLdsPoints;
     const size_t lds_bytes = tlsdev::prewhiten_lds_bytes((int)n, lds);
     auto step_kernel = lds ? tlsdev::tls_prewhiten_step_kernel<true> : tlsdev::tls_prewhiten_step_kernel<false>;
@@ -4995,24 +4829,23 @@ int tls_ephemeris_match(tls_ctx* ctx, const int64_t* star, const double* period,
     const size_t nn = (size_t)n, words = (size_t)tlsdev::kMatchWords;
     const int tiles = (int)((n + tlsdev::kMatchTile - 1) / tlsdev::kMatchTile);
     const int chunks = tlsdev::match_chunks(tiles);
-    const size_t partial_words = sizeof(tlsdev::MatchPartial) / 8;
-    TLS_HIP(ctx, ctx->d_match.reserve(5 * nn + words * nn + partial_words * (size_t)chunks * nn));
-    double* d_star = ctx->d_match.ptr;
-    double* d_period = d_star + nn;
-    double* d_T0 = d_period + nn;
-    double* d_duration = d_T0 + nn;
-    double* d_strength = d_duration + nn;
-    double* d_out = d_strength + nn;
-    double* d_partial = d_out + words * nn;
+    long long* d_star;
+    double *d_period, *d_T0, *d_duration, *d_strength, *d_out;
+    tlsdev::MatchPartial* d_partial;
+    Arena L;
+    L.add(d_star, nn);  L.add(d_period, nn);  L.add(d_T0, nn);  L.add(d_duration, nn);  L.add(d_strength, nn);
+    L.add(d_out, words * nn);                 // records
+    L.add(d_partial, (size_t)chunks * nn);    // ... and the partial records of every chunk
+    TLS_HIP(ctx, L.bind(ctx->d_match));
     TLS_HIP(ctx, hipMemcpyAsync(d_star, star, nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     TLS_HIP(ctx, hipMemcpyAsync(d_period, period, nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     TLS_HIP(ctx, hipMemcpyAsync(d_T0, T0, nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     TLS_HIP(ctx, hipMemcpyAsync(d_duration, duration, nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     TLS_HIP(ctx, hipMemcpyAsync(d_strength, strength, nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     tlsdev::MatchArgs a;
-    a.star = reinterpret_cast<const long long*>(d_star);
+    a.star = d_star;
     a.period = d_period; a.T0 = d_T0; a.duration = d_duration; a.strength = d_strength;
-    a.partial = reinterpret_cast<tlsdev::MatchPartial*>(d_partial); a.out = d_out;
+    a.partial = d_partial; a.out = d_out;
     a.span = span; a.drift_tolerance = drift_tolerance; a.epoch_tolerance = epoch_tolerance; a.max_ratio = (double)max_ratio;
     a.n = (int)n; a.tiles = tiles; a.chunks = chunks;
     hipLaunchKernelGGL(tlsdev::tls_match_pairs_kernel, dim3((unsigned)tiles, (unsigned)chunks), dim3(tlsdev::kMatchTile), 0,
@@ -5073,22 +4906,19 @@ int tls_noise_profile(tls_ctx* ctx, const double* t, const double* y, int64_t n,
     if (!lds) slab = std::min<int64_t>(slab, (int64_t)((256u << 20) / (8 * nn * W)));
     slab = std::max<int64_t>(1, slab);
     const size_t S = (size_t)slab;
-    const size_t width_words = (W + 1) / 2;                        // int32 widths in doubles
-    const size_t bad_words = (S * (nn + 1) + 1) / 2;               // uint32 counts in doubles
-    const size_t scratch_words = lds ? 0 : S * W * (nn + mask_words);
-    TLS_HIP(ctx, ctx->d_noise.reserve(nn + W + width_words + 2 * S * nn + S * tlsdev::kNoiseWords + 3 * S * W + bad_words + scratch_words));
-    double* d_t = ctx->d_noise.ptr;
-    double* d_span = d_t + nn;
-    double* d_widths = d_span + W;
-    double* d_y = d_widths + width_words;
-    double* d_d = d_y + S * nn;
-    double* d_records = d_d + S * nn;
-    double* d_count = d_records + S * tlsdev::kNoiseWords;
-    double* d_robust = d_count + S * W;
-    double* d_rms = d_robust + S * W;
-    double* d_bad = d_rms + S * W;
-    double* d_v = d_bad + bad_words;
-    double* d_mask = d_v + S * W * nn;
+    double *d_t, *d_span, *d_y, *d_d, *d_records, *d_robust, *d_rms, *d_v;
+    int* d_widths;
+    long long* d_count;
+    unsigned int* d_bad;
+    unsigned long long* d_mask;
+    Arena L;
+    L.add(d_t, nn);  L.add(d_span, W);  L.add(d_widths, W);
+    L.add(d_y, S * nn);                       // of one slab, from here on
+    L.add(d_d, S * nn);  L.add(d_records, S * tlsdev::kNoiseWords);  L.add(d_count, S * W);  L.add(d_robust, S * W);
+    L.add(d_rms, S * W);  L.add(d_bad, S * (nn + 1));   // clip counts
+    // for rows that do not fit the LDS: the window means and validity words of every (curve, width)
+    L.add(d_v, lds ? 0 : S * W * nn);  L.add(d_mask, lds ? 0 : S * W * mask_words);
+    TLS_HIP(ctx, L.bind(ctx->d_noise));
     std::vector<int> w32((size_t)n_widths);
     for (size_t k = 0; k < W; ++k) w32[k] = (int)widths[k];
     if (t) TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
@@ -5100,10 +4930,10 @@ int tls_noise_profile(tls_ctx* ctx, const double* t, const double* y, int64_t n,
     TLS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(curve_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)curve_lds));
     TLS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(width_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)width_lds));
     tlsdev::NoiseArgs a;
-    a.t = t ? d_t : nullptr; a.y = d_y; a.d = d_d; a.bad = reinterpret_cast<unsigned int*>(d_bad); a.records = d_records;
-    a.widths = reinterpret_cast<const int*>(d_widths); a.span_max = d_span;
-    a.v = lds ? nullptr : d_v; a.mask = lds ? nullptr : reinterpret_cast<unsigned long long*>(d_mask);
-    a.count = reinterpret_cast<long long*>(d_count); a.robust = d_robust; a.rms = d_rms; a.check = nullptr;
+    a.t = t ? d_t : nullptr; a.y = d_y; a.d = d_d; a.bad = d_bad; a.records = d_records;
+    a.widths = d_widths; a.span_max = d_span;
+    a.v = d_v; a.mask = d_mask;
+    a.count = d_count; a.robust = d_robust; a.rms = d_rms; a.check = nullptr;
     a.pair_span = pair_span; a.clip_upper = clip_upper; a.clip_lower = clip_lower;
     a.n = (int)n; a.W = (int)n_widths; a.min_count = (int)std::min<int64_t>(min_count, (int64_t)INT32_MAX);
 #ifdef TLS_DEBUG_CHECKS
@@ -5150,17 +4980,15 @@ int tls_find_peaks(tls_ctx* ctx, const double* power, const double* chi2, const 
     const size_t parts = 1 + (chi2 ? 1 : 0) + (row ? 1 : 0) + (depth ? 1 : 0);
     // rows per launch: at most 256 MB of rows (as the detrending slabs)
     const int64_t slab = std::max<int64_t>(1, std::min<int64_t>({n_rows, (int64_t)65535, (int64_t)((256u << 20) / (8 * np * parts))}));
-    // periods | records of one slab | power [| chi2 | depth | row] rows of one slab
-    TLS_HIP(ctx, ctx->d_peaks.reserve(np + (size_t)slab * words + parts * (size_t)slab * np));
+    double *d_periods, *d_out, *d_power, *d_chi2, *d_depth;
+    long long* d_row;
+    Arena L;
+    L.add(d_periods, np);  L.add(d_out, (size_t)slab * words);   // the records of one slab
+    L.add(d_power, (size_t)slab * np);              // ... and its rows
+    L.add(d_chi2, chi2 ? (size_t)slab * np : 0);  L.add(d_depth, depth ? (size_t)slab * np : 0);
+    L.add(d_row, row ? (size_t)slab * np : 0);
+    TLS_HIP(ctx, L.bind(ctx->d_peaks));
     if ((rc = reserve_peak_mask(ctx, slab, n_periods))) return rc;
-    double* d_periods = ctx->d_peaks.ptr;
-    double* d_out = d_periods + np;
-    double* d_power = d_out + (size_t)slab * words;
-    double* d_next = d_power + (size_t)slab * np;
-    double* d_chi2 = nullptr; double* d_depth = nullptr; long long* d_row = nullptr;
-    if (chi2) { d_chi2 = d_next; d_next += (size_t)slab * np; }
-    if (depth) { d_depth = d_next; d_next += (size_t)slab * np; }
-    if (row) d_row = reinterpret_cast<long long*>(d_next);
     std::vector<double> h((size_t)slab * words);
     TLS_HIP(ctx, hipMemcpyAsync(d_periods, periods, np * 8, hipMemcpyHostToDevice, main_stream(ctx)));
     for (int64_t k0 = 0; k0 < n_rows; k0 += slab) {
