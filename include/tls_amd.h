@@ -41,7 +41,8 @@ extern "C" {
  * tls_debug_peak_phase_scans), (7: tls_sysrem), (7: tls_single_transits), (7: tls_transit_times),
  * (7: tls_shape_fit), (7: tls_nudft, tls_lomb_scargle, tls_sine_test); 8: every entry that takes `root, n_root` takes a
  * second table, `root, root_count, n_root`), (8: tls_ephemeris_match), (8: tls_folded_views),
- * (8: tls_event_vetting), (8: tls_centroid_test), (8: tls_noise_profile), (8: tls_transit_fit), (8: tls_remove_transits). */
+ * (8: tls_event_vetting), (8: tls_centroid_test), (8: tls_noise_profile), (8: tls_transit_fit), (8: tls_remove_transits),
+ * (8: tls_event_periods). */
 #define TLS_AMD_ABI_VERSION 8
 
 #define TLS_OK 0
@@ -780,6 +781,75 @@ int tls_transit_times(tls_ctx *ctx, const double *t, const double *y, const doub
                       int64_t n_fits, const double *shape_values, const int64_t *shape_offset, const int64_t *width,
                       const double *span_max, int64_t n_rows, double depth_min, double min_ses, int64_t max_epochs,
                       tls_ephemeris *out /* [n_fits] */, tls_transit_time *out_times /* [n_fits][max_epochs] */);
+
+/* ---- survey mode: the period aliases of two- and few-transit events ---------------------------------------------------- */
+/* Two single-transit events of a star (two sectors a year apart, a campaign with a gap) have no periodogram peak, but they fix
+ * the period up to the aliases P_k = (t_b - t_a) / k, and the data decide among them: an alias is ruled out when one of its
+ * other epochs falls on good data that show no dip, allowed when they all fall in gaps, confirmed when another one shows a dip.
+ * For a curve (y [n], dy [n] over the ascending, finite t [n]) and the rows of tls_transit_times (L, b, span_max), a pair is
+ * (ca < cb sample indices, row r, reach S >= 1, offset >= 0 days):
+ *   w = 1.0 / (dy * dy);  xw = (1.0 - y) * w;  bb[j] = b[j]*b[j];  h = (L-1)/2
+ *   window(c):  lo = c - h;  hi = lo + L - 1;  invalid if lo < 0 or hi > n-1 or not (t[hi] - t[lo] <= span_max)
+ *               N = 0; D = 0; for j ascending:  N = N + xw[lo+j]*b[j];  D = D + w[lo+j]*bb[j]
+ *   look(tc):   j = first index with t[j] >= tc (n-1 if there is none)
+ *               if j > 0 and tc - t[j-1] <= t[j] - tc:  j = j - 1                      tls_transit_times' nearest sample
+ *               for s = -S .. S ascending:  c = j + s
+ *                   skip if c < 0 or c > n-1, or window(c) is invalid
+ *                   skip if not (fabs(t[c] - tc) <= offset)                             a centre at the edge of a gap covers no epoch inside it
+ *                   skip if not (D > 0);  q = N / sqrt(D)                               signed, NO depth_min test: a missing dip must count
+ *                   hold (q, N, D) if nothing is held or q > held q                     the first shift wins ties
+ *               nothing held: the epoch is uncovered
+ *   ta = t[ca];  tb = t[cb];  dT = tb - ta;  status 1 unless dT > 0                     dT is reported, the rest is NaN
+ *   A = look(ta);  B = look(tb);  status 2 unless both are covered and N_A + N_B > 0    dT; pair_mes, pair_depth where both are covered
+ *   pN = N_A + N_B;  pD = D_A + D_B;  pair_depth = pN / pD;  pair_mes = pN / sqrt(pD)
+ *   k_hi = floor(dT / period_min);  n_aliases = k_hi;  status 3 if k_hi < 1             n_evaluated = n_allowed = 0, no alias
+ *   n_evaluated = min(k_hi, max_aliases)
+ *   alias k = 1 .. n_evaluated:
+ *       P = dT / k;  e_first = ceil((t[0] - ta) / P);  e_last = floor((t[n-1] - ta) / P);  n_epochs = (e_last - e_first) + 1.0
+ *       SN = 0; SD = 0; n_covered = 0; n_seen = 0; worst_sigma = NaN; worst_epoch = NaN
+ *       for e = e_first + i, i = 0 .. n_epochs-1:
+ *           tc = ta + e * P;  look(tc);  uncovered: next epoch
+ *           n_covered += 1;  SN = SN + N;  SD = SD + D;  if q >= min_ses:  n_seen += 1
+ *           if e != 0 and e != k:  z = (pair_depth - N / D) * sqrt(D)                   how far the epoch falls short of the pair's depth
+ *               if worst_sigma is NaN or z > worst_sigma:  worst_sigma = z;  worst_epoch = e
+ *       mes = SN / sqrt(SD);  depth = SN / SD
+ *   allowed(k) = not (worst_sigma > veto_sigma)                                         NaN: no other covered epoch, allowed
+ *   best = the allowed alias with the largest non-NaN mes (the smallest k on ties, i.e. the longest period)
+ *   longest / shortest = the smallest / largest allowed k;  n_allowed = their count
+ * Everything that cannot be formed is NaN.  Every step is one IEEE double operation and every sum runs in the stated order:
+ * both records equal the Python statement in tests/event_periods_spec.py bit for bit.  All fields are doubles. */
+#define TLS_ALIAS_MAX 4096
+typedef struct tls_event_pair {
+    double status;                 /* 0 aliases were looked at; 1 dT <= 0; 2 an event is uncovered or the pair shows no dip; 3 no alias >= period_min */
+    double dT;                     /* t[cb] - t[ca] */
+    double n_aliases, n_evaluated; /* k_hi; min(k_hi, max_aliases) */
+    double n_allowed;
+    double pair_mes, pair_depth;   /* of the two events together */
+    double best_k, best_period, best_mes, best_n_covered, best_n_seen;
+    double longest_k, longest_period;
+    double shortest_k, shortest_period;
+} tls_event_pair;
+typedef struct tls_event_alias {
+    double period;                 /* dT / k at rank k - 1; NaN in every field at ranks past n_evaluated */
+    double n_epochs, n_covered;    /* epochs inside the series; those a window covers */
+    double n_seen;                 /* covered epochs with q >= min_ses */
+    double mes, depth;             /* over the covered epochs */
+    double worst_sigma, worst_epoch;   /* the largest shortfall of a covered epoch other than the pair's own, and its epoch */
+} tls_event_alias;
+/* n_pairs pairs (curve[f], index_a[f], index_b[f], row[f], reach[f], offset[f]) on the curves of y, dy [n_curves][n] over the
+ * shared time stamps t [n]; the rows as tls_single_transits takes them.  out [n_pairs], out_aliases [n_pairs][max_aliases] (may
+ * be NULL).  Needs no plan and no search, and leaves a prepared plan as it is.  n_pairs == 0 is a no-op.  Pairs are processed in
+ * slabs, so device memory stays bounded for any n_pairs.  TLS_E_ARG, before any device work and with the outputs untouched, for
+ * what tls_transit_times refuses for t, the rows, curve, row and reach, n outside [1, 2^20], an index outside [0, n) or
+ * index_a >= index_b, a non-finite or negative offset, a period_min that is not finite and > 0 or has
+ * (t[n-1] - t[0]) / period_min + 2 > TLS_TIMES_MAX_EPOCHS, max_aliases outside [1, TLS_ALIAS_MAX], and a NaN min_ses or
+ * veto_sigma (+inf is legal: no veto).  y and dy are taken as they are (dy > 0). */
+int tls_event_periods(tls_ctx *ctx, const double *t, const double *y, const double *dy, int64_t n, int64_t n_curves,
+                      const int64_t *curve, const int64_t *index_a, const int64_t *index_b, const int64_t *row,
+                      const int64_t *reach, const double *offset, int64_t n_pairs, const double *shape_values,
+                      const int64_t *shape_offset, const int64_t *width, const double *span_max, int64_t n_rows,
+                      double period_min, int64_t max_aliases, double min_ses, double veto_sigma,
+                      tls_event_pair *out /* [n_pairs] */, tls_event_alias *out_aliases /* [n_pairs][max_aliases], or NULL */);
 
 /* Per-transit event vetting: the tests of a candidate's INDIVIDUAL events (after the Kepler Robovetter's individual transit
  * metrics, Thompson et al. 2018, A.3.7) -- is an event unique in its neighbourhood, does it rest on one sample, does the flux

@@ -51,6 +51,13 @@ TIMES_MAX_REACH = 4096
 TIMES_MAX_EPOCHS = 65536
 TIMES_MAX_POINTS = 1 << 30   # tls_times.hip.h kTimesMaxPoints
 EVENTS_MAX_CHASE = 8192      # include/tls_amd.h TLS_EVENTS_MAX_CHASE: the widest chase reach of a candidate of tls_event_vetting
+# include/tls_amd.h TLS_ALIAS_MAX: the most aliases of a pair of tls_event_periods; tls_aliases.hip.h kAliasTile (the centres of a
+# workgroup of the plane kernel), kAliasLdsPoints (a longer series is read from device memory, not from the LDS) and
+# kAliasMaxPoints
+ALIAS_MAX = 4096
+ALIAS_TILE = 256
+ALIAS_LDS_POINTS = 6400
+ALIAS_MAX_POINTS = 1 << 20
 # include/tls_amd.h TLS_SHAPE_MAX_UNITS: the most (duration, ingress, shift) units of tls_shape_fit; tls_shape.hip.h
 # kShapeMaxPoints and kShapeLdsMembers (the members of a candidate the LDS holds; more are staged through it in tiles)
 SHAPE_MAX_UNITS = 65536
@@ -118,7 +125,7 @@ SYMBOLS = (
     "tls_ephemeris_match", "tls_folded_views", "tls_event_vetting", "tls_centroid_test", "tls_noise_profile",
     "tls_transit_fit",
     "tls_transit_mask", "tls_biweight_detrend_masked", "tls_prewhiten_masked",
-    "tls_remove_transits",
+    "tls_remove_transits", "tls_event_periods",
     "tls_comm_unique_id", "tls_comm_init", "tls_comm_destroy", "tls_comm_info", "tls_comm_allgather_results", "tls_comm_allgather_device", "tls_comm_fetch_gathered",
     "tls_comm_stage_results", "tls_comm_allgather_staged", "tls_comm_fetch_staged",
     "tls_comm_barrier", "tls_comm_max",
@@ -551,6 +558,80 @@ def transit_times_arguments(t, y, dy, period, T0, row, reach, widths, shapes, sp
     for k in ("k", "separation"):
         del a[k]
     a.update(ints, period=period, T0=T0, depth_min=depth_min, min_ses=min_ses, max_epochs=max_epochs)
+    return a
+
+
+# tls_event_pair and tls_event_alias (include/tls_amd.h): the period aliases of a pair of events, 16 doubles, and one alias,
+# 8 doubles
+EVENT_PAIR_FIELDS = ("status", "dT", "n_aliases", "n_evaluated", "n_allowed", "pair_mes", "pair_depth", "best_k", "best_period",
+                     "best_mes", "best_n_covered", "best_n_seen", "longest_k", "longest_period", "shortest_k",
+                     "shortest_period")
+EVENT_ALIAS_FIELDS = ("period", "n_epochs", "n_covered", "n_seen", "mes", "depth", "worst_sigma", "worst_epoch")
+
+
+class EventPair(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_double) for k in EVENT_PAIR_FIELDS]
+
+
+class EventAlias(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_double) for k in EVENT_ALIAS_FIELDS]
+
+
+EVENT_PAIR_DTYPE = numpy.dtype([(k, "f8") for k in EVENT_PAIR_FIELDS])
+EVENT_ALIAS_DTYPE = numpy.dtype([(k, "f8") for k in EVENT_ALIAS_FIELDS])
+
+
+def event_periods_options(period_min, max_aliases=256, min_ses=3.0, veto_sigma=3.0):
+    """(period_min, max_aliases, min_ses, veto_sigma) as tls_event_periods takes them, checked as it checks them: period_min
+    finite and > 0, max_aliases an integer in [1, ALIAS_MAX], min_ses and veto_sigma numbers and no NaN (veto_sigma +inf: no
+    veto); ValueError otherwise."""
+    if isinstance(period_min, (bool, numpy.bool_)) or not isinstance(period_min, numbers.Real) \
+            or not (0.0 < float(period_min) < numpy.inf):
+        raise ValueError("event periods: period_min must be finite and > 0, got %r" % (period_min,))
+    if isinstance(max_aliases, (bool, numpy.bool_)) or not isinstance(max_aliases, numbers.Integral) \
+            or not 1 <= int(max_aliases) <= ALIAS_MAX:
+        raise ValueError("event periods: max_aliases must be an integer in [1, %d], got %r" % (ALIAS_MAX, max_aliases))
+    for name, v in (("min_ses", min_ses), ("veto_sigma", veto_sigma)):
+        if isinstance(v, (bool, numpy.bool_)) or not isinstance(v, numbers.Real) or numpy.isnan(v):
+            raise ValueError("event periods: %s must be a number and no NaN, got %r" % (name, v))
+    return float(period_min), int(max_aliases), float(min_ses), float(veto_sigma)
+
+
+def event_periods_arguments(t, y, dy, curve, index_a, index_b, row, reach, offset, widths, shapes, span_max, period_min,
+                            max_aliases=256, min_ses=3.0, veto_sigma=3.0):
+    """What tls_event_periods takes, checked as it checks them and packed for it -- the dict of single_arguments for t, y, dy
+    and the rows (n up to ALIAS_MAX_POINTS), plus curve, index_a, index_b, row and reach [n_pairs] (int64; curve in
+    [0, n_curves), 0 <= index_a < index_b < n, row in [0, n_rows), reach in [1, TIMES_MAX_REACH]), offset [n_pairs] (float64,
+    finite and >= 0 days) and period_min, max_aliases, min_ses, veto_sigma (event_periods_options; (t[n-1] - t[0]) / period_min
+    + 2 is at most TIMES_MAX_EPOCHS).  ValueError otherwise.  GPU-free."""
+    what = "event periods"
+    period_min, max_aliases, min_ses, veto_sigma = event_periods_options(period_min, max_aliases, min_ses, veto_sigma)
+    a = single_arguments(t, y, dy, widths, shapes, span_max, what=what, max_points=ALIAS_MAX_POINTS)
+    n, n_curves = len(a["t"]), len(a["y"])
+    if not (a["t"][-1] - a["t"][0]) / period_min + 2.0 <= TIMES_MAX_EPOCHS:
+        raise ValueError("%s: period_min %r gives an alias more than %d epochs over %r days"
+                         % (what, period_min, TIMES_MAX_EPOCHS, a["t"][-1] - a["t"][0]))
+    curve = numpy.atleast_1d(numpy.asarray(curve))
+    ints = {}
+    for name, v, lo, hi in (("curve", curve, 0, n_curves - 1), ("index_a", index_a, 0, n - 1), ("index_b", index_b, 0, n - 1),
+                            ("row", row, 0, len(a["width"]) - 1), ("reach", reach, 1, TIMES_MAX_REACH)):
+        v = numpy.atleast_1d(numpy.asarray(v))
+        if v.ndim != 1 or v.shape != curve.shape or (v.size and v.dtype.kind not in "iu"):
+            raise ValueError("%s: %s must hold one integer a pair" % (what, name))
+        if v.size and (v.min() < lo or v.max() > hi):
+            raise ValueError("%s: %s out of range [%d, %d]" % (what, name, lo, hi))
+        ints[name] = numpy.ascontiguousarray(v, dtype=numpy.int64)
+    if not numpy.all(ints["index_a"] < ints["index_b"]):
+        raise ValueError("%s: index_a must lie in front of index_b" % what)
+    try:
+        offset = numpy.ascontiguousarray(numpy.atleast_1d(numpy.asarray(offset, dtype=numpy.float64)))
+    except (TypeError, ValueError):
+        raise ValueError("%s: offset must be numbers" % what)
+    if offset.shape != curve.shape or not numpy.all(numpy.isfinite(offset) & (offset >= 0.0)):
+        raise ValueError("%s: offset must hold one finite value >= 0 a pair" % what)
+    for k in ("k", "separation", "depth_min", "min_ses"):
+        del a[k]
+    a.update(ints, offset=offset, period_min=period_min, max_aliases=max_aliases, min_ses=min_ses, veto_sigma=veto_sigma)
     return a
 
 
@@ -1291,6 +1372,10 @@ def load():
     lib.tls_transit_times.argtypes = [vp, _c_double_p, _c_double_p, _c_double_p, i64, i64, _c_int64_p, _c_double_p, _c_double_p,
                                       _c_int64_p, _c_int64_p, i64, _c_double_p, _c_int64_p, _c_int64_p, _c_double_p, i64, dbl,
                                       dbl, i64, ctypes.c_void_p, ctypes.c_void_p]
+    lib.tls_event_periods.restype = ci
+    lib.tls_event_periods.argtypes = [vp, _c_double_p, _c_double_p, _c_double_p, i64, i64, _c_int64_p, _c_int64_p, _c_int64_p,
+                                      _c_int64_p, _c_int64_p, _c_double_p, i64, _c_double_p, _c_int64_p, _c_int64_p, _c_double_p,
+                                      i64, dbl, i64, dbl, dbl, ctypes.c_void_p, ctypes.c_void_p]
     lib.tls_event_vetting.restype = ci
     lib.tls_event_vetting.argtypes = [vp, _c_double_p, _c_double_p, _c_double_p, i64, i64, _c_int64_p, _c_double_p, _c_double_p,
                                       _c_int64_p, _c_int64_p, _c_int64_p, _c_int64_p, _c_double_p, i64, _c_double_p, _c_int64_p,
@@ -2454,6 +2539,27 @@ class Context(object):
             self._h, _ip(a["star"]), _dp(a["period"]), _dp(a["T0"]), _dp(a["duration"]), _dp(a["strength"]), len(a["star"]),
             a["span"], a["drift_tolerance"], a["epoch_tolerance"], a["max_ratio"], out.ctypes.data_as(ctypes.c_void_p)))
         return out
+
+    def event_periods(self, t, y, dy, curve, index_a, index_b, row, reach, offset, widths, shapes, span_max, period_min,
+                      max_aliases=256, min_ses=3.0, veto_sigma=3.0, with_aliases=True):
+        """The period aliases (tls_event_periods; the statement: include/tls_amd.h, tests/event_periods_spec.py) of the event
+        pairs (curve[f], index_a[f] < index_b[f], row[f], reach[f], offset[f] in days) on the curves of y, dy [n_curves, n] (or
+        one row) over t [n], for the rows (widths[r], shapes[r], span_max[r]): (EVENT_PAIR_DTYPE [n_pairs], EVENT_ALIAS_DTYPE
+        [n_pairs, max_aliases], or None without with_aliases).  ValueError for what event_periods_arguments refuses."""
+        a = event_periods_arguments(t, y, dy, curve, index_a, index_b, row, reach, offset, widths, shapes, span_max, period_min,
+                                    max_aliases, min_ses, veto_sigma)
+        n_c, n = a["y"].shape
+        n_pairs = len(a["curve"])
+        pairs = numpy.zeros(n_pairs, dtype=EVENT_PAIR_DTYPE)
+        aliases = numpy.zeros((n_pairs, a["max_aliases"]), dtype=EVENT_ALIAS_DTYPE) if with_aliases else None
+        assert EVENT_PAIR_DTYPE.itemsize == ctypes.sizeof(EventPair) and EVENT_ALIAS_DTYPE.itemsize == ctypes.sizeof(EventAlias)
+        self._check(self._lib.tls_event_periods(
+            self._h, _dp(a["t"]), _dp(a["y"]), _dp(a["dy"]), n, n_c, _ip(a["curve"]), _ip(a["index_a"]), _ip(a["index_b"]),
+            _ip(a["row"]), _ip(a["reach"]), _dp(a["offset"]), n_pairs, _dp(a["shape_values"]), _ip(a["shape_offset"]),
+            _ip(a["width"]), _dp(a["span_max"]), len(a["width"]), a["period_min"], a["max_aliases"], a["min_ses"],
+            a["veto_sigma"], pairs.ctypes.data_as(ctypes.c_void_p),
+            None if aliases is None else aliases.ctypes.data_as(ctypes.c_void_p)))
+        return pairs, aliases
 
     def noise_profile(self, t, y, widths, span_max, pair_span, clip_upper=5.0, clip_lower=5.0, min_count=3):
         """The noise profiles (tls_noise_profile; the statement: include/tls_amd.h, tests/noise_profile_spec.py) of the curves

@@ -295,6 +295,7 @@ struct tls_ctx {
     DevBuf<double> d_gls{pool, "d_gls", kScratch};            // tls_nudft, tls_lomb_scargle, tls_sine_test, prewhiten
     DevBuf<double> d_match{pool, "d_match", kScratch};        // tls_ephemeris_match
     DevBuf<double> d_noise{pool, "d_noise", kScratch};        // tls_noise_profile
+    DevBuf<double> d_aliases{pool, "d_aliases", kScratch};    // tls_event_periods
     // two-role slab path (series in HBM, one light curve; SearchPlan::split)
     View<unsigned int> d_tile_prefix;        // [n_periods + 1] tiles in front of work item w (queue order)
     DevBuf<double> d_partials{pool, "d_partials", kScratch};  // [split_max_items][3] a tile's winner
@@ -3992,6 +3993,132 @@ int tls_transit_times(tls_ctx* ctx, const double* t, const double* y, const doub
         [&](const SlabView& s) {
             TLS_HIP(ctx, hipMemcpyAsync(out + s.f0, d_out, s.fits * eph_words * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
             TLS_HIP(ctx, hipMemcpyAsync(out_times + (size_t)s.f0 * me, d_out_times, s.fits * time_words * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+            return TLS_OK;
+        });
+}
+
+// ---- period aliases of event pairs (tls_aliases.hip.h, DESIGN.md "Event periods"): the pairs kernel of the transit times over
+// the curves a slab of event pairs reads, the (N, D) plane of every (curve, row) group of the slab, then one workgroup an
+// event pair, slab by slab
+static_assert(sizeof(tls_event_pair) == tlsdev::kAliasPairWords * 8, "tls_event_pair is the kernel's record");
+static_assert(sizeof(tls_event_alias) == tlsdev::kAliasWords * 8, "tls_event_alias is the kernel's record");
+static_assert(TLS_ALIAS_MAX == tlsdev::kAliasMax, "the header's limit");
+
+int tls_event_periods(tls_ctx* ctx, const double* t, const double* y, const double* dy, int64_t n, int64_t n_curves,
+                      const int64_t* curve, const int64_t* index_a, const int64_t* index_b, const int64_t* row,
+                      const int64_t* reach, const double* offset, int64_t n_pairs, const double* shape_values,
+                      const int64_t* shape_offset, const int64_t* width, const double* span_max, int64_t n_rows,
+                      double period_min, int64_t max_aliases, double min_ses, double veto_sigma, tls_event_pair* out,
+                      tls_event_alias* out_aliases) {
+    if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
+    const std::string what = "event periods";
+    if (n_pairs < 0 || n_curves < 0 || n_rows < 0 || n < 0) return fail(ctx, TLS_E_ARG, what + ": negative count");
+    if (max_aliases < 1 || max_aliases > TLS_ALIAS_MAX) return fail(ctx, TLS_E_ARG, what + ": max_aliases out of range [1, 4096]");
+    if (!(std::isfinite(period_min) && period_min > 0.0)) return fail(ctx, TLS_E_ARG, what + ": period_min must be finite and > 0");
+    if (std::isnan(min_ses) || std::isnan(veto_sigma)) return fail(ctx, TLS_E_ARG, what + ": min_ses or veto_sigma is NaN");
+    if (n_pairs == 0) return TLS_OK;
+    RowTables tb;
+    int rc = build_row_tables(ctx, what, "null argument", shape_values, shape_offset, width, span_max, n_rows, false, tb);
+    if (rc) return rc;
+    if (!t || !y || !dy || !curve || !index_a || !index_b || !row || !reach || !offset || !out) return fail(ctx, TLS_E_ARG, "null argument");
+    if ((rc = check_batch(ctx, what, n, tlsdev::kAliasMaxPoints, "[1, 2^20]", n_pairs, n_curves)) || (rc = check_time_stamps(ctx, what, t, n)))
+        return rc;
+    if (!((t[n - 1] - t[0]) / period_min + 2.0 <= (double)TLS_TIMES_MAX_EPOCHS))
+        return fail(ctx, TLS_E_ARG, what + ": period_min gives an alias more than 65536 epochs");
+    int max_width = 0;
+    if ((rc = check_curves(ctx, what, curve, n_pairs, n_curves, [&](int64_t f) {
+            if (row[f] < 0 || row[f] >= n_rows) return fail(ctx, TLS_E_ARG, what + ": row out of range [0, n_rows)");
+            if (reach[f] < 1 || reach[f] > TLS_TIMES_MAX_REACH) return fail(ctx, TLS_E_ARG, what + ": reach out of range [1, 4096]");
+            if (index_a[f] < 0 || index_b[f] >= n || index_a[f] >= index_b[f])
+                return fail(ctx, TLS_E_ARG, what + ": the event indices must be 0 <= index_a < index_b < n");
+            if (!(std::isfinite(offset[f]) && offset[f] >= 0.0)) return fail(ctx, TLS_E_ARG, what + ": offset must be finite and >= 0");
+            max_width = std::max(max_width, (int)width[row[f]]);
+            return TLS_OK;
+        })))
+        return rc;
+    TLS_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t nn = (size_t)n, ma = (size_t)max_aliases, n_taps = tb.n_taps;
+    const size_t pair_words = tlsdev::kAliasPairWords, alias_words = out_aliases ? (size_t)tlsdev::kAliasWords * ma : 0;
+    // a slab: at most 1024 pairs on at most 1024 curves; 256 MB of curves (32 bytes a point), of planes (16 bytes a point and
+    // group, a group an event pair at most) and of alias records
+    const size_t budget = 256u << 20;
+    const size_t cs = std::max<size_t>(1, std::min<size_t>({(size_t)n_curves, 1024, budget / (32 * nn)}));
+    const size_t sl = std::max<size_t>(1, std::min<size_t>({(size_t)n_pairs, 1024, budget / (16 * nn), budget / (64 * ma)}));
+    double2 *d_pairs, *d_plane;
+    double *d_y, *d_dy, *d_out, *d_out_aliases, *d_offset, *d_t, *d_taps;
+    int *d_ints, *d_groups;
+    tlsdev::SingleRow* d_rows;
+    Arena L;
+    L.add(d_pairs, cs * nn);            // of one slab, down to the group columns
+    L.add(d_plane, sl * nn);
+    L.add(d_y, cs * nn);  L.add(d_dy, cs * nn);  L.add(d_out, sl * pair_words);  L.add(d_out_aliases, sl * alias_words);
+    L.add(d_offset, sl);  L.add(d_ints, 5 * sl);     // slot | row | reach | index_a | index_b
+    L.add(d_groups, 3 * sl);                         // every pair's group | every group's slot | every group's row
+    L.add(d_t, nn);                     // what every slab shares, from here on
+    L.add(d_rows, (size_t)n_rows);  L.add(d_taps, 2 * n_taps);
+    TLS_HIP(ctx, L.bind(ctx->d_aliases));
+    if ((rc = ensure_check_counters(ctx))) return rc;
+    tlsdev::TimesPairsArgs p;
+    p.y = d_y; p.dy = d_dy; p.pairs = d_pairs;
+    tlsdev::AliasPlaneArgs pl;
+    pl.t = d_t; pl.pairs = d_pairs; pl.rows = d_rows; pl.taps = d_taps; pl.group_slot = d_groups + sl; pl.group_row = d_groups + 2 * sl;
+    pl.plane = d_plane; pl.check = ctx->d_check.ptr; pl.n = (int)n;
+    tlsdev::AliasArgs a;
+    a.t = d_t; a.plane = d_plane; a.group = d_groups; a.reach = d_ints + 2 * sl; a.index_a = d_ints + 3 * sl; a.index_b = d_ints + 4 * sl;
+    a.offset = d_offset; a.out = d_out; a.out_aliases = d_out_aliases; a.check = ctx->d_check.ptr;
+    a.period_min = period_min; a.min_ses = min_ses; a.veto_sigma = veto_sigma; a.n = (int)n; a.max_aliases = (int)max_aliases;
+    const size_t plane_lds = tlsdev::alias_plane_lds_bytes(max_width), alias_lds = tlsdev::alias_lds_bytes((int)n);
+    auto plane_kernel = tlsdev::tls_alias_plane_kernel;
+    auto alias_kernel = alias_lds ? tlsdev::tls_event_aliases_kernel<true> : tlsdev::tls_event_aliases_kernel<false>;
+    TLS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(plane_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plane_lds));
+    if (alias_lds)
+        TLS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(alias_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         tlsdev::kAliasLdsPoints * 24));
+    TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_rows, tb.rows.data(), (size_t)n_rows * sizeof(tlsdev::SingleRow), hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_taps, tb.taps.data(), 2 * n_taps * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    const unsigned tiles = (unsigned)((nn + tlsdev::kAliasTile - 1) / tlsdev::kAliasTile);
+    // the (slot, row) groups of a slab: its pairs in a stable sort by (slot, row), a new group where either changes
+    std::vector<int> h_slot(sl), h_groups(3 * sl), order(sl);
+    tlsslab::Slab again;
+    const SlabStage stage{"event periods", "tls_event_periods", curve, n_pairs, nn, cs, sl,
+                          {{d_y, y}, {d_dy, dy}}, {{d_offset, offset}}, d_ints, 5};
+    return run_candidate_slabs(ctx, stage,
+        [&](int64_t f, int* at) {
+            at[sl] = (int)row[f];
+            at[2 * sl] = (int)reach[f];
+            at[3 * sl] = (int)index_a[f];
+            at[4 * sl] = (int)index_b[f];
+            return (size_t)0;
+        },
+        [&](const SlabView& s) {
+            tlsslab::next_slab(curve, n_pairs, s.f0, cs, sl, h_slot.data(), again);   // (the slab's slots once more)
+            for (size_t i = 0; i < s.fits; ++i) order[i] = (int)i;
+            std::stable_sort(order.begin(), order.begin() + (ptrdiff_t)s.fits, [&](int u, int v) {
+                const int64_t ru = row[s.f0 + u], rv = row[s.f0 + v];
+                return h_slot[(size_t)u] != h_slot[(size_t)v] ? h_slot[(size_t)u] < h_slot[(size_t)v] : ru < rv;
+            });
+            size_t groups = 0;
+            for (size_t k = 0; k < s.fits; ++k) {
+                const int i = order[k];
+                const int r = (int)row[s.f0 + i];
+                if (k == 0 || h_groups[sl + groups - 1] != h_slot[(size_t)i] || h_groups[2 * sl + groups - 1] != r) {
+                    h_groups[sl + groups] = h_slot[(size_t)i];
+                    h_groups[2 * sl + groups] = r;
+                    ++groups;
+                }
+                h_groups[(size_t)i] = (int)groups - 1;
+            }
+            if (hipMemcpyAsync(d_groups, h_groups.data(), 3 * sl * sizeof(int), hipMemcpyHostToDevice, main_stream(ctx)) != hipSuccess) return;
+            if (!launch_times_pairs(ctx, p, s.curves, nn)) return;
+            hipLaunchKernelGGL(plane_kernel, dim3(tiles, (unsigned)groups), dim3(tlsdev::kAliasThreads), plane_lds, main_stream(ctx), pl);
+            if (hipPeekAtLastError() != hipSuccess) return;
+            hipLaunchKernelGGL(alias_kernel, dim3((unsigned)s.fits), dim3(tlsdev::kAliasThreads), alias_lds, main_stream(ctx), a);
+        },
+        [&](const SlabView& s) {
+            TLS_HIP(ctx, hipMemcpyAsync(out + s.f0, d_out, s.fits * pair_words * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+            if (out_aliases)
+                TLS_HIP(ctx, hipMemcpyAsync(out_aliases + (size_t)s.f0 * ma, d_out_aliases, s.fits * alias_words * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
             return TLS_OK;
         });
 }

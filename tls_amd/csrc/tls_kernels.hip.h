@@ -90,7 +90,8 @@ enum CheckCode {
     kChkBiweight = 10,     // tls_biweight_detrend: a span over its LDS, or an LDS index outside the staged slots
     kChkSysrem = 11,       // tls_sysrem: a row, a chunk or a component count outside the call's
     kChkSingle = 12,       // tls_single_transits: a window outside the staged slots, or a taken centre, row or window outside the series
-    kChkTimes = 13,        // tls_transit_times, tls_event_vetting: a reach or a width outside the entry's limits, or a picked window outside the series
+    kChkTimes = 13,        // tls_transit_times, tls_event_vetting, tls_event_periods: a reach, a width, an event index or an epoch
+                           // count outside the entry's limits, or a picked window outside the series or the staged slots
     kChkShape = 14,        // tls_shape_fit: a member's rank or a unit's table index outside its limits; tls_centroid_test: a
                            // shape or an epoch count outside the entry's limits, or an epoch's head outside the series
     kChkViews = 15,        // tls_folded_views: a bin's range outside its part, a member outside the series, or no single middle member
@@ -4437,6 +4438,8 @@ __global__ void __launch_bounds__(512) tls_transit_models(const ModelsArgs a) {
 #include "tls_single.hip.h"
 // survey-mode transit times and refitted ephemeris (tls_transit_times)
 #include "tls_times.hip.h"
+// survey-mode period aliases of a pair of single-transit events (tls_event_periods), on tls_times.hip.h's pairs
+#include "tls_aliases.hip.h"
 // survey-mode per-transit event vetting (tls_event_vetting), on tls_times.hip.h's pairs and chunks
 #include "tls_events.hip.h"
 // survey-mode trapezoid shape fit (tls_shape_fit)

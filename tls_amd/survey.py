@@ -1699,6 +1699,211 @@ def transit_times(t, flux_batch, period, T0, duration, curve=None, dy_batch=None
     return eph, _with_oc(eph, times)
 
 
+# ---- the period aliases of two- and few-transit events ---------------------------------------------------------------------
+def event_pair_fields():
+    """The fields of an event pair's record, in order: those of tls_event_pair."""
+    from ._lib import EVENT_PAIR_FIELDS
+    return tuple(EVENT_PAIR_FIELDS)
+
+
+def event_alias_fields():
+    """The fields of one alias of an event pair, in order: those of tls_event_alias."""
+    from ._lib import EVENT_ALIAS_FIELDS
+    return tuple(EVENT_ALIAS_FIELDS)
+
+
+def _ratio(name, value, what="event pairs"):
+    if isinstance(value, (bool, numpy.bool_)) or not isinstance(value, numbers.Real) or not (1.0 <= float(value) < numpy.inf):
+        raise ValueError("%s: %s must be finite and >= 1, got %r" % (what, name, value))
+    return float(value)
+
+
+def event_pairs(events, n_events, min_ses=7.0, depth_ratio=2.0, width_ratio=2.0, max_pairs=8):
+    """The pairs of single-transit events that may be two transits of one planet, on the host: per curve of `events`
+    [n_curves, k] (the records of single_transits, n_events [n_curves] of them valid) every two events a, b with
+    index_a < index_b that both reach min_ses and whose depths and widths agree within the ratios (larger / smaller <=
+    depth_ratio, width_ratio), at most max_pairs a curve by descending ses_a^2 + ses_b^2 (the earlier pair on ties).  The row of
+    a pair is that of its stronger event (a on ties).  Returns (curve, index_a, index_b, row), int64 [n_pairs], curve
+    ascending.  ValueError for ratios below 1, a NaN min_ses, max_pairs < 1 and records without the fields index, ses, depth,
+    width and row."""
+    depth_ratio, width_ratio = _ratio("depth_ratio", depth_ratio), _ratio("width_ratio", width_ratio)
+    if isinstance(min_ses, (bool, numpy.bool_)) or not isinstance(min_ses, numbers.Real) or numpy.isnan(min_ses):
+        raise ValueError("event pairs: min_ses must be a number and no NaN, got %r" % (min_ses,))
+    if isinstance(max_pairs, (bool, numpy.bool_)) or not isinstance(max_pairs, numbers.Integral) or int(max_pairs) < 1:
+        raise ValueError("event pairs: max_pairs must be an integer >= 1, got %r" % (max_pairs,))
+    events = numpy.asarray(events)
+    if events.dtype.names is None or not {"index", "ses", "depth", "width", "row"} <= set(events.dtype.names):
+        raise ValueError("event pairs: events must be the records of single_transits")
+    if events.ndim == 1:
+        events = events[None, :]
+    n_events = numpy.atleast_1d(numpy.asarray(n_events))
+    if events.ndim != 2 or n_events.shape != (len(events),) or (n_events.size and (n_events.min() < 0
+                                                                                     or n_events.max() > events.shape[1])):
+        raise ValueError("event pairs: events must be [n_curves, k] with n_events [n_curves] in [0, k]")
+    found = []
+    for c in range(len(events)):
+        ev = events[c, :int(n_events[c])]
+        ev = ev[ev["ses"] >= float(min_ses)]
+        ev = ev[numpy.argsort(ev["index"], kind="stable")]
+        rows = []
+        for i in range(len(ev)):
+            for j in range(i + 1, len(ev)):
+                a, b = ev[i], ev[j]
+                if not a["index"] < b["index"]:
+                    continue
+                d = sorted((float(a["depth"]), float(b["depth"])))
+                w = sorted((float(a["width"]), float(b["width"])))
+                if not (d[0] > 0.0 and d[1] <= depth_ratio * d[0] and w[1] <= width_ratio * w[0]):
+                    continue
+                strength = float(a["ses"]) ** 2 + float(b["ses"]) ** 2
+                rows.append((-strength, int(a["index"]), int(b["index"]), int(a["row"] if a["ses"] >= b["ses"] else b["row"])))
+        rows.sort()
+        found += [(c,) + r[1:] for r in rows[:int(max_pairs)]]
+    out = numpy.array(found, dtype=numpy.int64).reshape(-1, 4)
+    return out[:, 0].copy(), out[:, 1].copy(), out[:, 2].copy(), out[:, 3].copy()
+
+
+def event_period_reach(widths, row, dt):
+    """(reach, offset) of event_periods' defaults for pairs on the rows `row` of `widths`: reach_f = max(1, min(L_f // 4,
+    4096)) samples and offset_f = (reach_f + 0.5) * dt days."""
+    from ._lib import TIMES_MAX_REACH
+    L = numpy.asarray(widths, dtype=numpy.int64)[numpy.asarray(row, dtype=numpy.int64)]
+    reach = numpy.maximum(1, numpy.minimum(L // 4, TIMES_MAX_REACH)).astype(numpy.int64)
+    return reach, (reach + 0.5) * float(dt)
+
+
+def event_periods(t, flux_batch, events=None, n_events=None, pairs=None, dy_batch=None, period_min=None, max_aliases=256,
+                  reach=None, min_ses=3.0, veto_sigma=3.0, widths=None, gap_tolerance=0.5, with_aliases=True, detrend=None,
+                  context=None, device=None, devices=None, **template_kwargs):
+    """The periods two or a few single-transit events of a star allow, on the device (tls_event_periods).  Two events -- two
+    TESS sectors a year apart, a K2 campaign with a gap, a 40-day planet in a 90-day window -- have no periodogram peak, but they
+    fix the period up to the aliases P_k = (t_b - t_a) / k, and the data decide among them: an alias is ruled out when one of
+    its other epochs falls on good data that show no dip, allowed when they all fall in gaps, and confirmed when another epoch
+    shows a dip.  This is the table of allowed periods a duo-transit follow-up starts from.
+
+    The pairs are `pairs` = (curve, index_a, index_b, row) -- sample indices index_a < index_b on light curve curve of
+    flux_batch [n_curves, n] (or one row), row an index into `widths` --, or event_pairs(events, n_events) of the records of
+    single_transits, or, with neither, those of single_transits on the same detrended rows (the rows are detrended once).  The
+    rows are single_transits': with dt = median(diff(t)), row r is (L_r = widths[r], b_r = 1 - template.reference_transit(L_r,
+    **shape), span_max = (L_r - 1) * dt * (1 + gap_tolerance)); widths=None takes single_transit_widths(t), so the rows of
+    single_transits' events fit.  reach (None: max(1, min(L // 4, 4096)) of the pair's row; an integer, or one a pair) is how far
+    a dip may lie from an epoch, in samples, offset = (reach + 0.5) * dt, and period_min=None is 4 times the longest row's
+    duration.
+
+        look(tc): among the centres within reach of the sample nearest tc and within offset of tc whose window is whole and runs
+            over no gap, the one of the largest q = N / sqrt(D) (N = sum xw b, D = sum w b^2; signed, no depth threshold: a
+            missing dip must count); no such centre: the epoch is uncovered
+        the pair: both events covered and N_a + N_b > 0;  pair_depth = (N_a + N_b) / (D_a + D_b)
+        alias k = 1 .. min(floor(dT / period_min), max_aliases):  P = dT / k;  over its epochs inside the series:
+            n_covered, n_seen (q >= min_ses), mes = sum N / sqrt(sum D), depth = sum N / sum D
+            worst_sigma = the largest (pair_depth - N / D) sqrt(D) over the covered epochs other than the pair's own
+        allowed(k) = not (worst_sigma > veto_sigma): an alias without another covered epoch is allowed
+        best = the allowed alias of the largest mes; longest / shortest = the allowed aliases of the smallest / largest k
+
+    Pair status: 0 its aliases were looked at; 1 the two events share a time stamp; 2 an event is uncovered (its window runs over
+    a gap or an end) or the two show no dip; 3 no alias is as long as period_min.  Each step is one IEEE double operation and
+    every sum runs in index order, so the result is bit-equal to the Python statement in tests/event_periods_spec.py.
+    ValueError, before any device work (the detrending included), for period_min not finite and > 0, max_aliases outside
+    [1, 4096], a NaN min_ses or veto_sigma (inf: no veto), a bad reach, gap_tolerance or widths and `pairs` out of range; the rows
+    (and the events of a call without pairs) are checked behind the detrending steps, before the call's own device work.  detrend= takes the steps and tuples of
+    search_batch; devices=[...] deals the pairs out by their curves.
+
+    Returns (pairs, aliases): a structured array [n_pairs] with curve, index_a, index_b, row, reach, offset and the fields
+    event_pair_fields(), and one [n_pairs, max_aliases] with k, allowed and the fields event_alias_fields() (NaN, not allowed,
+    past n_evaluated); aliases is None with with_aliases=False."""
+    from ._lib import TIMES_MAX_REACH, event_periods_options, single_widths
+    from .template import reference_transit
+    _, max_aliases, min_ses, veto_sigma = event_periods_options(1.0 if period_min is None else period_min, max_aliases,
+                                                                 min_ses, veto_sigma)
+    if isinstance(gap_tolerance, bool) or not (0.0 <= float(gap_tolerance) < numpy.inf):
+        raise ValueError("event periods: gap_tolerance must be finite and >= 0, got %r" % (gap_tolerance,))
+    if widths is not None:
+        widths = single_widths(widths, "event periods")
+    if reach is not None:
+        reach = numpy.asarray(reach)
+        if reach.dtype.kind not in "iu" or reach.ndim > 1 or (reach.size and (reach.min() < 1 or reach.max() > TIMES_MAX_REACH)):
+            raise ValueError("event periods: reach must be integers in [1, %d]" % TIMES_MAX_REACH)
+    if pairs is not None and (events is not None or n_events is not None):
+        raise ValueError("event periods: give pairs or events, not both")
+    if (events is None) != (n_events is None):
+        raise ValueError("event periods: events and n_events come together")
+    t, flux_batch, dy_batch = _candidate_rows("event periods", t, flux_batch, dy_batch)
+    if widths is None:
+        widths = single_transit_widths(t)
+    n_curves = numpy.shape(flux_batch)[0]
+
+    def checked(pairs):
+        if isinstance(pairs, dict):
+            pairs = tuple(pairs[k] for k in ("curve", "index_a", "index_b", "row"))
+        if len(pairs) != 4:
+            raise ValueError("event periods: pairs must be (curve, index_a, index_b, row)")
+        curve, index_a, index_b, row = (numpy.atleast_1d(numpy.asarray(v)) for v in pairs)
+        for name, v, hi in (("curve", curve, n_curves), ("index_a", index_a, len(t)), ("index_b", index_b, len(t)),
+                            ("row", row, len(widths))):
+            if v.ndim != 1 or v.shape != curve.shape or (v.size and (v.dtype.kind not in "iu" or v.min() < 0 or v.max() >= hi)):
+                raise ValueError("event periods: %s must hold one index in [0, %d) a pair" % (name, hi))
+        if not numpy.all(index_a < index_b):
+            raise ValueError("event periods: index_a must lie in front of index_b")
+        if reach is not None and reach.ndim == 1 and reach.shape != curve.shape:
+            raise ValueError("event periods: reach must be one integer, or one a pair")
+        return tuple(v.astype(numpy.int64) for v in (curve, index_a, index_b, row))
+
+    if pairs is not None:
+        pairs = checked(pairs)                       # (what the caller gave is checked in front of the detrending)
+    flux_batch = _detrended(t, flux_batch, detrend, context, device, devices, dy_batch)
+    if pairs is None:
+        if events is None:
+            events, n_events = single_transits(t, flux_batch, dy_batch, widths=widths, gap_tolerance=gap_tolerance,
+                                               context=context, device=device, devices=devices, **template_kwargs)
+        pairs = checked(event_pairs(events, n_events))
+    curve, index_a, index_b, row = pairs
+    kwargs = dict(template_kwargs)
+    kwargs.setdefault("oversampling_factor", 1)      # (the period grid of the plan inputs is not used: the coarsest will do)
+    inp, y_rows, dy_rows = _batch_inputs(t, flux_batch, dy_batch, kwargs)
+    dt = float(numpy.median(numpy.diff(inp["t"]))) if len(inp["t"]) > 1 else 0.0
+    shapes = [1.0 - numpy.asarray(reference_transit(int(L), **inp["shape"])) for L in widths]
+    span_max = [(int(L) - 1) * dt * (1 + float(gap_tolerance)) for L in widths]
+    default_reach, _ = event_period_reach(widths, row, dt)
+    if reach is None:
+        reach = default_reach
+    else:
+        reach = numpy.broadcast_to(reach, curve.shape).astype(numpy.int64)
+    offset = (reach + 0.5) * dt
+    if period_min is None:
+        period_min = 4.0 * float(numpy.max(widths)) * dt
+    period_min = event_periods_options(period_min)[0]
+
+    def call(ctx, lo, hi):
+        where = numpy.flatnonzero((curve >= lo) & (curve < hi))
+        rec, table = ctx.event_periods(inp["t"], y_rows[lo:hi], dy_rows[lo:hi], curve[where] - lo, index_a[where],
+                                       index_b[where], row[where], reach[where], offset[where], widths, shapes, span_max,
+                                       period_min, max_aliases, min_ses, veto_sigma, with_aliases=with_aliases)
+        return dict(where=where, pairs=rec, aliases=table)
+
+    out = _run_batch(devices, device, context, n_curves, call)
+    from ._lib import EVENT_ALIAS_DTYPE, EVENT_PAIR_DTYPE
+    back = numpy.empty(len(curve), dtype=numpy.int64)
+    back[out["where"]] = numpy.arange(len(curve))
+    raw = out["pairs"][back]
+    records = numpy.zeros(len(curve), dtype=[(k, "i8") for k in ("curve", "index_a", "index_b", "row", "reach")]
+                          + [("offset", "f8")] + EVENT_PAIR_DTYPE.descr)
+    for name, v in (("curve", curve), ("index_a", index_a), ("index_b", index_b), ("row", row), ("reach", reach),
+                    ("offset", offset)):
+        records[name] = v
+    for name in raw.dtype.names:
+        records[name] = raw[name]
+    if not with_aliases:
+        return records, None
+    table = out["aliases"][back]
+    aliases = numpy.zeros(table.shape, dtype=[("k", "i8"), ("allowed", "?")] + EVENT_ALIAS_DTYPE.descr)
+    aliases["k"] = numpy.arange(1, table.shape[1] + 1)[None, :]
+    with numpy.errstate(invalid="ignore"):
+        aliases["allowed"] = (aliases["k"] <= raw["n_evaluated"][:, None]) & ~(table["worst_sigma"] > veto_sigma)
+    for name in table.dtype.names:
+        aliases[name] = table[name]
+    return records, aliases
+
+
 # ---- per-transit event vetting ---------------------------------------------------------------------------------------------
 EVENT_VETTING_CHASE_WINDOW = 0.1
 EVENT_VETTING_GUARD = 1.5
