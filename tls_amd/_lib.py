@@ -5,12 +5,13 @@ raised as RuntimeError with the library's message.  No torch, no fallback: if th
 shared library is missing, or no GPU is usable, the error surfaces here.
 """
 import ctypes
-import numbers
 import operator
 import os
 import weakref
 
 import numpy
+
+from . import _checks
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # Developer switch for A/B timing of two builds of the same source (tls_amd/csrc/Makefile `variant`, `debug`): another
@@ -260,14 +261,12 @@ PHASE_SCANNED, PHASE_NOTHING = 0, 1
 def phase_scan_arguments(max_bins, min_count):
     """(max_bins, min_count) as the phase scan takes them, checked as tls_phase_scan checks them: max_bins an integer in
     [PHASE_SCAN_MIN_BINS, PHASE_SCAN_MAX_BINS], min_count an integer >= 1; ValueError otherwise."""
+    what = "phase scan"
     for name, v in (("max_bins", max_bins), ("min_count", min_count)):
-        if isinstance(v, bool) or not isinstance(v, numbers.Integral):
-            raise ValueError("phase scan: %s must be an integer, got %r" % (name, v))
-    if not PHASE_SCAN_MIN_BINS <= int(max_bins) <= PHASE_SCAN_MAX_BINS:
-        raise ValueError("phase scan: max_bins must be in [%d, %d], got %r" % (PHASE_SCAN_MIN_BINS, PHASE_SCAN_MAX_BINS, max_bins))
-    if not 1 <= int(min_count) < 2 ** 31:
-        raise ValueError("phase scan: min_count must be at least 1, got %r" % (min_count,))
-    return int(max_bins), int(min_count)
+        _checks.integer(what, name, v)
+    return (_checks.integer(what, "max_bins", max_bins, PHASE_SCAN_MIN_BINS, PHASE_SCAN_MAX_BINS,
+                            "must be in [%d, %d]" % (PHASE_SCAN_MIN_BINS, PHASE_SCAN_MAX_BINS)),
+            _checks.integer(what, "min_count", min_count, 1, 2 ** 31 - 1, "must be at least 1"))
 
 
 # tls_match_record (include/tls_amd.h): the ephemeris match of one candidate, 10 doubles
@@ -302,16 +301,11 @@ def ephemeris_match_arguments(star, period, T0, duration, strength, span, drift_
     otherwise.  GPU-free."""
     what = "ephemeris match"
     for name, v in (("span", span), ("drift_tolerance", drift_tolerance), ("epoch_tolerance", epoch_tolerance)):
-        if isinstance(v, (bool, numpy.bool_)) or not isinstance(v, numbers.Real):
-            raise ValueError("%s: %s must be a number, got %r" % (what, name, v))
-    if not 0.0 < float(span) < numpy.inf:
-        raise ValueError("%s: span must be finite and > 0, got %r" % (what, span))
-    for name, v in (("drift_tolerance", drift_tolerance), ("epoch_tolerance", epoch_tolerance)):
-        if not 0.0 <= float(v) < numpy.inf:
-            raise ValueError("%s: %s must be finite and >= 0, got %r" % (what, name, v))
-    if isinstance(max_ratio, (bool, numpy.bool_)) or not isinstance(max_ratio, numbers.Integral) \
-            or not 1 <= int(max_ratio) <= MATCH_MAX_RATIO:
-        raise ValueError("%s: max_ratio must be an integer in [1, %d], got %r" % (what, MATCH_MAX_RATIO, max_ratio))
+        _checks.real(what, name, v)
+    span = _checks.finite_positive(what, "span", span)
+    drift_tolerance = _checks.finite_at_least(what, "drift_tolerance", drift_tolerance)
+    epoch_tolerance = _checks.finite_at_least(what, "epoch_tolerance", epoch_tolerance)
+    max_ratio = _checks.integer(what, "max_ratio", max_ratio, 1, MATCH_MAX_RATIO)
     star = numpy.atleast_1d(numpy.asarray(star))
     if star.size and star.dtype.kind not in "iu":
         raise ValueError("%s: star must hold integers" % what)
@@ -325,8 +319,8 @@ def ephemeris_match_arguments(star, period, T0, duration, strength, span, drift_
         raise ValueError("%s: star, period, T0, duration and strength must all be [M]" % what)
     if len(star) > MATCH_MAX_CANDIDATES:
         raise ValueError("%s: at most %d candidates, got %d" % (what, MATCH_MAX_CANDIDATES, len(star)))
-    return dict(star=star, period=period, T0=T0, duration=duration, strength=strength, span=float(span),
-                drift_tolerance=float(drift_tolerance), epoch_tolerance=float(epoch_tolerance), max_ratio=int(max_ratio))
+    return dict(star=star, period=period, T0=T0, duration=duration, strength=strength, span=span,
+                drift_tolerance=drift_tolerance, epoch_tolerance=epoch_tolerance, max_ratio=max_ratio)
 
 
 # tls_noise_curve (include/tls_amd.h): the per-curve part of a noise profile, 6 doubles
@@ -354,17 +348,13 @@ def noise_arguments(t, y, widths, span_max, pair_span, clip_upper=5.0, clip_lowe
         t = None if t is None else numpy.ascontiguousarray(numpy.asarray(t, dtype=numpy.float64))
     except (TypeError, ValueError):
         raise ValueError("%s: the light curves and t must hold numbers" % what)
-    if y.ndim == 1:
-        y = y[None, :]
-    if y.ndim != 2 or (t is not None and (t.ndim != 1 or y.shape[1] != len(t))):
-        raise ValueError("%s: flux must be [n] or [n_curves, n] over the time stamps t [n]" % what)
+    y, _ = _checks.row_shapes(what, t, y, names="flux")
     n = y.shape[1]
     if not 3 <= n <= NOISE_MAX_POINTS:
         raise ValueError("%s: n must lie in [3, %d], got %d" % (what, NOISE_MAX_POINTS, n))
-    if t is not None and (not numpy.all(numpy.isfinite(t)) or not numpy.all(t[1:] >= t[:-1])):
-        raise ValueError("%s: t must be finite and ascending" % what)
-    if y.size and not numpy.all(numpy.isfinite(y)):
-        raise ValueError("%s: the flux has a NaN or an infinite value" % what)
+    if t is not None:
+        _checks.time_values(what, t, "ascending")
+    y, _ = _checks.row_values(what, y, noun="the flux")
     raw = numpy.atleast_1d(numpy.asarray(widths))
     if raw.ndim != 1 or not 1 <= len(raw) <= NOISE_MAX_WIDTHS:
         raise ValueError("%s: widths must be [W] with W in [1, %d]" % (what, NOISE_MAX_WIDTHS))
@@ -382,13 +372,11 @@ def noise_arguments(t, y, widths, span_max, pair_span, clip_upper=5.0, clip_lowe
         raise ValueError("%s: span_max must hold numbers" % what)
     if span.shape != w.shape or not numpy.all(span >= 0.0):
         raise ValueError("%s: span_max must hold one value >= 0 a width" % what)
-    for name, v in (("pair_span", pair_span), ("clip_upper", clip_upper), ("clip_lower", clip_lower)):
-        if isinstance(v, (bool, numpy.bool_)) or not isinstance(v, numbers.Real) or not float(v) >= 0.0:
-            raise ValueError("%s: %s must be a number >= 0, got %r" % (what, name, v))
-    if isinstance(min_count, (bool, numpy.bool_)) or not isinstance(min_count, numbers.Integral) or not 1 <= int(min_count) < 2 ** 31:
-        raise ValueError("%s: min_count must be an integer >= 1, got %r" % (what, min_count))
-    return dict(t=t, y=numpy.ascontiguousarray(y), widths=w, span_max=span, pair_span=float(pair_span),
-                clip_upper=float(clip_upper), clip_lower=float(clip_lower), min_count=int(min_count))
+    pair_span, clip_upper, clip_lower = (_checks.not_negative(what, name, v) for name, v in (
+        ("pair_span", pair_span), ("clip_upper", clip_upper), ("clip_lower", clip_lower)))
+    min_count = _checks.integer(what, "min_count", min_count, 1, 2 ** 31 - 1, "must be an integer >= 1")
+    return dict(t=t, y=y, widths=w, span_max=span, pair_span=pair_span, clip_upper=clip_upper, clip_lower=clip_lower,
+                min_count=min_count)
 
 
 # tls_single_event (include/tls_amd.h): one single-transit event, 8 doubles
@@ -404,12 +392,8 @@ SINGLE_EVENT_DTYPE = numpy.dtype([(k, "f8") for k in SINGLE_EVENT_FIELDS])
 
 def _single_number(name, value, low=0.0, what="single transits"):
     """value as a float, finite and >= low; ValueError otherwise (a bool or a non-number included)."""
-    if isinstance(value, (bool, numpy.bool_)) or not isinstance(value, numbers.Real):
-        raise ValueError("%s: %s must be a number, got %r" % (what, name, value))
-    v = float(value)
-    if not (low <= v < numpy.inf):
-        raise ValueError("%s: %s must be finite and >= %g, got %r" % (what, name, low, value))
-    return v
+    _checks.real(what, name, value)
+    return _checks.finite_at_least(what, name, value, low)
 
 
 def single_widths(widths, what="single transits"):
@@ -435,15 +419,11 @@ def single_options(depth_min=0.0, k=8, min_ses=0.0, separation=0.5):
     """(depth_min, k, min_ses, separation) as tls_single_transits takes them, checked as it checks them: depth_min and
     separation finite and >= 0, k an integer in [1, SINGLE_MAX_K], min_ses no NaN (None: -inf, no threshold); ValueError
     otherwise."""
-    if isinstance(k, (bool, numpy.bool_)) or not isinstance(k, numbers.Integral) or not 1 <= int(k) <= SINGLE_MAX_K:
-        raise ValueError("single transits: k must be an integer in [1, %d], got %r" % (SINGLE_MAX_K, k))
+    k = _checks.integer("single transits", "k", k, 1, SINGLE_MAX_K)
     depth_min = _single_number("depth_min", depth_min)
     separation = _single_number("separation", separation)
-    if min_ses is None:
-        min_ses = -numpy.inf
-    if isinstance(min_ses, (bool, numpy.bool_)) or not isinstance(min_ses, numbers.Real) or numpy.isnan(min_ses):
-        raise ValueError("single transits: min_ses must be a number and no NaN, got %r" % (min_ses,))
-    return depth_min, int(k), float(min_ses), separation
+    min_ses = _checks.no_nan("single transits", "min_ses", -numpy.inf if min_ses is None else min_ses)
+    return depth_min, k, min_ses, separation
 
 
 def single_arguments(t, y, dy, widths, shapes, span_max, depth_min=0.0, k=8, min_ses=0.0, separation=0.5,
@@ -456,22 +436,8 @@ def single_arguments(t, y, dy, widths, shapes, span_max, depth_min=0.0, k=8, min
     and separation are finite and >= 0; k is an integer in [1, SINGLE_MAX_K]; min_ses is no NaN (None: -inf, no threshold).
     ValueError otherwise.  GPU-free.  tls_transit_times takes the same t, y, dy and rows: `what` heads the messages and
     max_points is the entry's limit of n."""
-    t = numpy.asarray(t, dtype=numpy.float64)
-    if t.ndim != 1 or not 1 <= len(t) <= max_points:
-        raise ValueError("%s: t must have shape [n] with n in [1, %d], got %s" % (what, max_points, t.shape))
-    if not numpy.all(numpy.isfinite(t)) or not numpy.all(t[1:] >= t[:-1]):
-        raise ValueError("%s: t must be finite and non-decreasing" % what)
-    y, dy = numpy.asarray(y, dtype=numpy.float64), numpy.asarray(dy, dtype=numpy.float64)
-    if y.ndim == 1:
-        y = y[None, :]
-    if dy.ndim == 1:
-        dy = dy[None, :]
-    if y.ndim != 2 or y.shape[1] != len(t) or dy.shape != y.shape:
-        raise ValueError("%s: y and dy must be [n] or [n_curves, n] over the time stamps t [n]" % what)
-    if y.size and not numpy.all(numpy.isfinite(y)):
-        raise ValueError("%s: y has a NaN or an infinite value" % what)
-    if dy.size and not (dy.min() > 0.0 and dy.max() < numpy.inf):
-        raise ValueError("%s: dy has a NaN, infinite or non-positive value" % what)
+    t = _checks.times(what, t, max_points)
+    y, dy = _checks.rows(what, t, y, dy)
     width = single_widths(widths, what)
     if len(shapes) != len(width):
         raise ValueError("%s: %d shapes for %d widths" % (what, len(shapes), len(width)))
@@ -485,7 +451,7 @@ def single_arguments(t, y, dy, widths, shapes, span_max, depth_min=0.0, k=8, min
     depth_min, k, min_ses, separation = single_options(depth_min, k, min_ses, separation)
     offset = numpy.zeros(len(width), dtype=numpy.int64)
     offset[1:] = numpy.cumsum(width)[:-1]
-    return dict(t=numpy.ascontiguousarray(t), y=numpy.ascontiguousarray(y), dy=numpy.ascontiguousarray(dy), width=width,
+    return dict(t=t, y=y, dy=dy, width=width,
                 shape_values=numpy.ascontiguousarray(numpy.concatenate(rows)), shape_offset=offset,
                 span_max=numpy.ascontiguousarray(span), depth_min=depth_min, k=k, min_ses=min_ses,
                 separation=separation)
@@ -510,51 +476,31 @@ EPHEMERIS_DTYPE = numpy.dtype([(k, "f8") for k in EPHEMERIS_FIELDS])
 TRANSIT_TIME_DTYPE = numpy.dtype([(k, "f8") for k in TRANSIT_TIME_FIELDS])
 
 
-def transit_times_options(depth_min=0.0, min_ses=3.0, max_epochs=1):
+def transit_times_options(depth_min=0.0, min_ses=3.0, max_epochs=1, what="transit times"):
     """(depth_min, min_ses, max_epochs) as tls_transit_times takes them, checked as it checks them: depth_min finite and
-    >= 0, min_ses a number and no NaN, max_epochs an integer in [1, TIMES_MAX_EPOCHS]; ValueError otherwise."""
-    if isinstance(depth_min, (bool, numpy.bool_)) or not isinstance(depth_min, numbers.Real) \
-            or not (0.0 <= float(depth_min) < numpy.inf):
-        raise ValueError("transit times: depth_min must be finite and >= 0, got %r" % (depth_min,))
-    if isinstance(min_ses, (bool, numpy.bool_)) or not isinstance(min_ses, numbers.Real) or numpy.isnan(min_ses):
-        raise ValueError("transit times: min_ses must be a number and no NaN, got %r" % (min_ses,))
-    if isinstance(max_epochs, (bool, numpy.bool_)) or not isinstance(max_epochs, numbers.Integral) \
-            or not 1 <= int(max_epochs) <= TIMES_MAX_EPOCHS:
-        raise ValueError("transit times: max_epochs must be an integer in [1, %d], got %r" % (TIMES_MAX_EPOCHS, max_epochs))
-    return float(depth_min), float(min_ses), int(max_epochs)
+    >= 0, min_ses a number and no NaN, max_epochs an integer in [1, TIMES_MAX_EPOCHS]; ValueError otherwise, headed `what`."""
+    return (_checks.finite_at_least(what, "depth_min", depth_min), _checks.no_nan(what, "min_ses", min_ses),
+            _checks.integer(what, "max_epochs", max_epochs, 1, TIMES_MAX_EPOCHS))
 
 
 def transit_times_arguments(t, y, dy, period, T0, row, reach, widths, shapes, span_max, curve=None, depth_min=0.0,
-                            min_ses=3.0, max_epochs=1):
+                            min_ses=3.0, max_epochs=1, what="transit times"):
     """What tls_transit_times takes, checked as it checks them and packed for it -- the dict of single_arguments for t, y,
-    dy and the rows (width, shape_values, shape_offset, span_max: checked as single_arguments checks them, n up to
-    TIMES_MAX_POINTS), plus period, T0
-    [n_fits] (float64, any value: the device gives a candidate without an ephemeris status 1), curve (None: one candidate a
-    curve, in order), row and reach [n_fits] (int64; curve in [0, n_curves), row in [0, n_rows), reach in
-    [1, TIMES_MAX_REACH]), depth_min, min_ses, max_epochs (transit_times_options).  ValueError otherwise.  GPU-free."""
-    depth_min, min_ses, max_epochs = transit_times_options(depth_min, min_ses, max_epochs)
-    a = single_arguments(t, y, dy, widths, shapes, span_max, depth_min, what="transit times", max_points=TIMES_MAX_POINTS)
-    try:
-        period, T0 = (numpy.ascontiguousarray(numpy.atleast_1d(numpy.asarray(v, dtype=numpy.float64))) for v in (period, T0))
-    except (TypeError, ValueError):
-        raise ValueError("transit times: period and T0 must be numbers")
-    if period.ndim != 1 or period.shape != T0.shape:
-        raise ValueError("transit times: period and T0 must be [n_fits]")
+    dy and the rows (width, shape_values, shape_offset, span_max: n up to TIMES_MAX_POINTS), plus period, T0 [n_fits]
+    (float64, any value: the device gives a candidate without an ephemeris status 1), curve (None: one candidate a curve,
+    in order), row and reach [n_fits] (int64; curve in [0, n_curves), row in [0, n_rows), reach in [1, TIMES_MAX_REACH]),
+    depth_min, min_ses, max_epochs (transit_times_options).  ValueError otherwise, headed `what`: tls_event_vetting takes
+    the same.  GPU-free."""
+    depth_min, min_ses, max_epochs = transit_times_options(depth_min, min_ses, max_epochs, what)
+    a = single_arguments(t, y, dy, widths, shapes, span_max, depth_min, what=what, max_points=TIMES_MAX_POINTS)
+    period, T0 = _checks.columns(what, "period and T0", (period, T0))
     n_fits, n_curves = len(period), len(a["y"])
     if curve is None:
         if n_fits != n_curves:
-            raise ValueError("transit times: curve=None takes one candidate a light curve: %d candidates, %d curves"
-                             % (n_fits, n_curves))
+            raise _checks.one_a_curve(what, n_fits, n_curves)
         curve = numpy.arange(n_curves)
-    ints = {}
-    for name, v, lo, hi in (("curve", curve, 0, n_curves - 1), ("row", row, 0, len(a["width"]) - 1),
-                            ("reach", reach, 1, TIMES_MAX_REACH)):
-        v = numpy.atleast_1d(numpy.asarray(v))
-        if v.shape != period.shape or (v.size and v.dtype.kind not in "iu"):
-            raise ValueError("transit times: %s must hold one integer a candidate" % name)
-        if v.size and (v.min() < lo or v.max() > hi):
-            raise ValueError("transit times: %s out of range [%d, %d]" % (name, lo, hi))
-        ints[name] = numpy.ascontiguousarray(v, dtype=numpy.int64)
+    ints = _checks.integer_columns(what, period.shape, (("curve", curve, 0, n_curves - 1), ("row", row, 0, len(a["width"]) - 1),
+                                                        ("reach", reach, 1, TIMES_MAX_REACH)))
     for k in ("k", "separation"):
         del a[k]
     a.update(ints, period=period, T0=T0, depth_min=depth_min, min_ses=min_ses, max_epochs=max_epochs)
@@ -585,16 +531,10 @@ def event_periods_options(period_min, max_aliases=256, min_ses=3.0, veto_sigma=3
     """(period_min, max_aliases, min_ses, veto_sigma) as tls_event_periods takes them, checked as it checks them: period_min
     finite and > 0, max_aliases an integer in [1, ALIAS_MAX], min_ses and veto_sigma numbers and no NaN (veto_sigma +inf: no
     veto); ValueError otherwise."""
-    if isinstance(period_min, (bool, numpy.bool_)) or not isinstance(period_min, numbers.Real) \
-            or not (0.0 < float(period_min) < numpy.inf):
-        raise ValueError("event periods: period_min must be finite and > 0, got %r" % (period_min,))
-    if isinstance(max_aliases, (bool, numpy.bool_)) or not isinstance(max_aliases, numbers.Integral) \
-            or not 1 <= int(max_aliases) <= ALIAS_MAX:
-        raise ValueError("event periods: max_aliases must be an integer in [1, %d], got %r" % (ALIAS_MAX, max_aliases))
-    for name, v in (("min_ses", min_ses), ("veto_sigma", veto_sigma)):
-        if isinstance(v, (bool, numpy.bool_)) or not isinstance(v, numbers.Real) or numpy.isnan(v):
-            raise ValueError("event periods: %s must be a number and no NaN, got %r" % (name, v))
-    return float(period_min), int(max_aliases), float(min_ses), float(veto_sigma)
+    what = "event periods"
+    return (_checks.finite_positive(what, "period_min", period_min),
+            _checks.integer(what, "max_aliases", max_aliases, 1, ALIAS_MAX),
+            _checks.no_nan(what, "min_ses", min_ses), _checks.no_nan(what, "veto_sigma", veto_sigma))
 
 
 def event_periods_arguments(t, y, dy, curve, index_a, index_b, row, reach, offset, widths, shapes, span_max, period_min,
@@ -611,24 +551,13 @@ def event_periods_arguments(t, y, dy, curve, index_a, index_b, row, reach, offse
     if not (a["t"][-1] - a["t"][0]) / period_min + 2.0 <= TIMES_MAX_EPOCHS:
         raise ValueError("%s: period_min %r gives an alias more than %d epochs over %r days"
                          % (what, period_min, TIMES_MAX_EPOCHS, a["t"][-1] - a["t"][0]))
-    curve = numpy.atleast_1d(numpy.asarray(curve))
-    ints = {}
-    for name, v, lo, hi in (("curve", curve, 0, n_curves - 1), ("index_a", index_a, 0, n - 1), ("index_b", index_b, 0, n - 1),
-                            ("row", row, 0, len(a["width"]) - 1), ("reach", reach, 1, TIMES_MAX_REACH)):
-        v = numpy.atleast_1d(numpy.asarray(v))
-        if v.ndim != 1 or v.shape != curve.shape or (v.size and v.dtype.kind not in "iu"):
-            raise ValueError("%s: %s must hold one integer a pair" % (what, name))
-        if v.size and (v.min() < lo or v.max() > hi):
-            raise ValueError("%s: %s out of range [%d, %d]" % (what, name, lo, hi))
-        ints[name] = numpy.ascontiguousarray(v, dtype=numpy.int64)
+    shape = numpy.atleast_1d(numpy.asarray(curve)).shape
+    ints = _checks.integer_columns(what, shape, (
+        ("curve", curve, 0, n_curves - 1), ("index_a", index_a, 0, n - 1), ("index_b", index_b, 0, n - 1),
+        ("row", row, 0, len(a["width"]) - 1), ("reach", reach, 1, TIMES_MAX_REACH)), "pair")
     if not numpy.all(ints["index_a"] < ints["index_b"]):
         raise ValueError("%s: index_a must lie in front of index_b" % what)
-    try:
-        offset = numpy.ascontiguousarray(numpy.atleast_1d(numpy.asarray(offset, dtype=numpy.float64)))
-    except (TypeError, ValueError):
-        raise ValueError("%s: offset must be numbers" % what)
-    if offset.shape != curve.shape or not numpy.all(numpy.isfinite(offset) & (offset >= 0.0)):
-        raise ValueError("%s: offset must hold one finite value >= 0 a pair" % what)
+    offset = _checks.float_column(what, "offset", offset, shape, "pair", not_numbers="must be numbers")
     for k in ("k", "separation", "depth_min", "min_ses"):
         del a[k]
     a.update(ints, offset=offset, period_min=period_min, max_aliases=max_aliases, min_ses=min_ses, veto_sigma=veto_sigma)
@@ -658,15 +587,11 @@ EVENT_RECORD_DTYPE = numpy.dtype([(k, "f8") for k in EVENT_RECORD_FIELDS])
 def event_vetting_options(chase_fraction=0.6, chase_min=0.5, point_fraction=0.5, step_fraction=0.5):
     """(chase_fraction, chase_min, point_fraction, step_fraction) as tls_event_vetting takes them, checked as it checks them:
     numbers, chase_fraction in (0, 1], chase_min in [0, 1], point_fraction and step_fraction > 0; ValueError otherwise."""
-    out = []
-    for name, v, ok, text in (("chase_fraction", chase_fraction, lambda x: 0.0 < x <= 1.0, "in (0, 1]"),
-                              ("chase_min", chase_min, lambda x: 0.0 <= x <= 1.0, "in [0, 1]"),
-                              ("point_fraction", point_fraction, lambda x: x > 0.0, "> 0"),
-                              ("step_fraction", step_fraction, lambda x: x > 0.0, "> 0")):
-        if isinstance(v, (bool, numpy.bool_)) or not isinstance(v, numbers.Real) or not ok(float(v)):
-            raise ValueError("event vetting: %s must be a number %s, got %r" % (name, text, v))
-        out.append(float(v))
-    return tuple(out)
+    what = "event vetting"
+    return (_checks.within(what, "chase_fraction", chase_fraction, 0.0, 1.0, low_open=True),
+            _checks.within(what, "chase_min", chase_min, 0.0, 1.0),
+            _checks.positive(what, "point_fraction", point_fraction),
+            _checks.positive(what, "step_fraction", step_fraction))
 
 
 def event_vetting_arguments(t, y, dy, period, T0, row, reach, chase_reach, guard, chase_span, widths, shapes, span_max,
@@ -677,25 +602,13 @@ def event_vetting_arguments(t, y, dy, period, T0, row, reach, chase_reach, guard
     guard >= 0), chase_span [n_fits] (float64, finite and > 0) and the four parameters (event_vetting_options).  ValueError
     otherwise.  GPU-free."""
     options = event_vetting_options(chase_fraction, chase_min, point_fraction, step_fraction)
-    try:
-        a = transit_times_arguments(t, y, dy, period, T0, row, reach, widths, shapes, span_max, curve, depth_min, min_ses,
-                                    max_epochs)
-    except ValueError as e:
-        raise ValueError(str(e).replace("transit times", "event vetting"))
+    what = "event vetting"
+    a = transit_times_arguments(t, y, dy, period, T0, row, reach, widths, shapes, span_max, curve, depth_min, min_ses,
+                                max_epochs, what)
     shape = a["period"].shape
-    for name, v, hi in (("chase_reach", chase_reach, EVENTS_MAX_CHASE), ("guard", guard, None)):
-        v = numpy.atleast_1d(numpy.asarray(v))
-        if v.shape != shape or (v.size and v.dtype.kind not in "iu"):
-            raise ValueError("event vetting: %s must hold one integer a candidate" % name)
-        if v.size and (v.min() < 0 or (hi is not None and v.max() > hi)):
-            raise ValueError("event vetting: %s out of range [0, %s]" % (name, "2^63)" if hi is None else "%d" % hi))
-        a[name] = numpy.ascontiguousarray(v, dtype=numpy.int64)
-    try:
-        span = numpy.ascontiguousarray(numpy.atleast_1d(numpy.asarray(chase_span, dtype=numpy.float64)))
-    except (TypeError, ValueError):
-        raise ValueError("event vetting: chase_span must hold numbers")
-    if span.shape != shape or not numpy.all(numpy.isfinite(span) & (span > 0.0)):
-        raise ValueError("event vetting: chase_span must hold one finite value > 0 a candidate")
+    a.update(_checks.integer_columns(what, shape, (("chase_reach", chase_reach, 0, EVENTS_MAX_CHASE),
+                                                   ("guard", guard, 0, None))))
+    span = _checks.float_column(what, "chase_span", chase_span, shape, "candidate", above=">")
     a.update(chase_span=span, chase_fraction=options[0], chase_min=options[1], point_fraction=options[2],
              step_fraction=options[3])
     return a
@@ -718,18 +631,9 @@ def shape_fit_tables(ratios, ingress, shifts, window=2.0, min_count=3, depth_min
     table 1-D, not empty, finite and non-decreasing; every ratio > 0; ingress[0] == 0.0 and ingress[-1] == 0.5; between 1 and
     SHAPE_MAX_UNITS units; window finite and at least 0.5 * max(ratio) + max|shift| (the model must lie inside the window);
     min_count an integer >= 1; depth_min finite and >= 0.  ValueError otherwise."""
-    tables = []
-    for name, v in (("ratios", ratios), ("ingress", ingress), ("shifts", shifts)):
-        try:
-            v = numpy.ascontiguousarray(numpy.asarray(v, dtype=numpy.float64))
-        except (TypeError, ValueError):
-            raise ValueError("shape fit: %s must hold numbers" % name)
-        if v.ndim != 1 or len(v) < 1:
-            raise ValueError("shape fit: %s must be a table [k] with k >= 1, got shape %s" % (name, v.shape))
-        if not numpy.all(numpy.isfinite(v)) or not numpy.all(v[1:] >= v[:-1]):
-            raise ValueError("shape fit: %s must be finite and ascending" % name)
-        tables.append(v)
-    ratio, ingress, shift = tables
+    what = "shape fit"
+    ratio, ingress, shift = (_checks.table(what, name, v)
+                             for name, v in (("ratios", ratios), ("ingress", ingress), ("shifts", shifts)))
     if not ratio[0] > 0.0:
         raise ValueError("shape fit: every ratio must be > 0, got %r" % ratio[0])
     if ingress[0] != 0.0 or ingress[-1] != 0.5:
@@ -737,70 +641,36 @@ def shape_fit_tables(ratios, ingress, shifts, window=2.0, min_count=3, depth_min
     units = len(ratio) * len(ingress) * len(shift)
     if not 1 <= units <= SHAPE_MAX_UNITS:
         raise ValueError("shape fit: %d units, outside [1, %d]" % (units, SHAPE_MAX_UNITS))
-    if isinstance(window, (bool, numpy.bool_)) or not isinstance(window, numbers.Real) or not numpy.isfinite(window):
-        raise ValueError("shape fit: window must be finite, got %r" % (window,))
-    least = 0.5 * float(ratio[-1]) + max(abs(float(shift[0])), abs(float(shift[-1])))
-    if not float(window) >= least:
-        raise ValueError("shape fit: window %r is below 0.5 * max(ratio) + max|shift| = %r: the model must lie inside it"
-                         % (window, least))
-    if isinstance(min_count, (bool, numpy.bool_)) or not isinstance(min_count, numbers.Integral) or int(min_count) < 1:
-        raise ValueError("shape fit: min_count must be an integer >= 1, got %r" % (min_count,))
-    if isinstance(depth_min, (bool, numpy.bool_)) or not isinstance(depth_min, numbers.Real) \
-            or not (0.0 <= float(depth_min) < numpy.inf):
-        raise ValueError("shape fit: transit_depth_min must be finite and >= 0, got %r" % (depth_min,))
-    return ratio, ingress, shift, float(window), int(min_count), float(depth_min)
+    window = _checks.fit_window(what, window, ratio, shift)
+    return (ratio, ingress, shift, window, _checks.integer(what, "min_count", min_count, 1),
+            _checks.finite_at_least(what, "transit_depth_min", depth_min))
 
 
 def shape_fit_candidates(period, T0, duration, curve, n_curves, what="shape fit"):
     """(period, T0, duration [n_fits] float64, curve [n_fits] int64) of tls_shape_fit, checked: numbers of one 1-D shape (any
     value: the device gives a candidate without an ephemeris status 1), curve (None: one candidate a curve, in order) integers
     in [0, n_curves).  ValueError otherwise, headed `what`."""
-    try:
-        period, T0, duration = (numpy.ascontiguousarray(numpy.atleast_1d(numpy.asarray(v, dtype=numpy.float64)))
-                                for v in (period, T0, duration))
-    except (TypeError, ValueError):
-        raise ValueError("%s: period, T0 and duration must be numbers" % what)
-    if period.ndim != 1 or not period.shape == T0.shape == duration.shape:
-        raise ValueError("%s: period, T0 and duration must be [n_fits]" % what)
-    if curve is None:
-        if len(period) != n_curves:
-            raise ValueError("%s: curve=None takes one candidate a light curve: %d candidates, %d curves"
-                             % (what, len(period), n_curves))
-        curve = numpy.arange(n_curves)
-    curve = numpy.atleast_1d(numpy.asarray(curve))
-    if curve.shape != period.shape or (curve.size and (curve.dtype.kind not in "iu" or curve.min() < 0
-                                                        or curve.max() >= n_curves)):
-        raise ValueError("%s: curve must hold one index in [0, %d) a candidate" % (what, n_curves))
-    return period, T0, duration, numpy.ascontiguousarray(curve, dtype=numpy.int64)
+    return tuple(_checks.candidates(what, period, T0, duration, curve, n_curves))
+
+
+def candidate_series(what, t, y, dy, period, T0, duration, curve, max_points):
+    """The light curves and candidates of a per-candidate stage, checked: a dict with t [n] (1-D, n in [1, max_points],
+    finite and non-decreasing), y and dy [n_curves, n] (y finite, dy finite and > 0) and period, T0, duration, curve
+    [n_fits] (shape_fit_candidates).  ValueError otherwise, headed `what`."""
+    t = _checks.times(what, t, max_points)
+    y, dy = _checks.rows(what, t, y, dy)
+    period, T0, duration, curve = _checks.candidates(what, period, T0, duration, curve, len(y))
+    return dict(t=t, y=y, dy=dy, period=period, T0=T0, duration=duration, curve=curve)
 
 
 def shape_fit_arguments(t, y, dy, period, T0, duration, ratios, ingress, shifts, curve=None, window=2.0, min_count=3,
                         depth_min=0.0):
-    """What tls_shape_fit takes, checked as it checks them and packed for it -- a dict with t [n] (1-D, n in
-    [1, SHAPE_MAX_POINTS], finite and non-decreasing), y and dy [n_curves, n] (y finite, dy finite and > 0), period, T0,
-    duration, curve [n_fits] (shape_fit_candidates), ratio, ingress, shift, window, min_count, depth_min
-    (shape_fit_tables).  ValueError otherwise.  GPU-free."""
+    """What tls_shape_fit takes, checked as it checks them and packed for it -- a dict with t [n] (n up to
+    SHAPE_MAX_POINTS), y and dy [n_curves, n], period, T0, duration, curve [n_fits] (candidate_series), ratio, ingress,
+    shift, window, min_count, depth_min (shape_fit_tables).  ValueError otherwise.  GPU-free."""
     ratio, ingress, shift, window, min_count, depth_min = shape_fit_tables(ratios, ingress, shifts, window, min_count, depth_min)
-    t = numpy.asarray(t, dtype=numpy.float64)
-    if t.ndim != 1 or not 1 <= len(t) <= SHAPE_MAX_POINTS:
-        raise ValueError("shape fit: t must have shape [n] with n in [1, %d], got %s" % (SHAPE_MAX_POINTS, t.shape))
-    if not numpy.all(numpy.isfinite(t)) or not numpy.all(t[1:] >= t[:-1]):
-        raise ValueError("shape fit: t must be finite and non-decreasing")
-    y, dy = numpy.asarray(y, dtype=numpy.float64), numpy.asarray(dy, dtype=numpy.float64)
-    if y.ndim == 1:
-        y = y[None, :]
-    if dy.ndim == 1:
-        dy = dy[None, :]
-    if y.ndim != 2 or y.shape[1] != len(t) or dy.shape != y.shape:
-        raise ValueError("shape fit: y and dy must be [n] or [n_curves, n] over the time stamps t [n]")
-    if y.size and not numpy.all(numpy.isfinite(y)):
-        raise ValueError("shape fit: y has a NaN or an infinite value")
-    if dy.size and not (dy.min() > 0.0 and dy.max() < numpy.inf):
-        raise ValueError("shape fit: dy has a NaN, infinite or non-positive value")
-    period, T0, duration, curve = shape_fit_candidates(period, T0, duration, curve, len(y))
-    return dict(t=numpy.ascontiguousarray(t), y=numpy.ascontiguousarray(y), dy=numpy.ascontiguousarray(dy), period=period,
-                T0=T0, duration=duration, curve=curve, ratio=ratio, ingress=ingress, shift=shift, window=window,
-                min_count=min_count, depth_min=depth_min)
+    return dict(candidate_series("shape fit", t, y, dy, period, T0, duration, curve, SHAPE_MAX_POINTS), ratio=ratio,
+                ingress=ingress, shift=shift, window=window, min_count=min_count, depth_min=depth_min)
 
 
 # tls_transit_fit_record (include/tls_amd.h): a candidate's limb-darkened transit fit, 24 doubles; the limits of
@@ -822,55 +692,39 @@ class TransitFitRecord(ctypes.Structure):
 TRANSIT_FIT_DTYPE = numpy.dtype([(k, "f8") for k in TRANSIT_FIT_FIELDS])
 
 
-def transit_fit_tables(k_rows, profile, impacts, ratios, shifts, sub, window=1.0, min_count=3, delta=1.0):
+def transit_fit_tables(k_rows, profile, impacts, ratios, shifts, sub, window=1.0, min_count=3, delta=1.0, what="transit fit"):
     """(k_rows, profile, impact, ratio, shift, sub, window, min_count, delta) as tls_transit_fit takes them, checked as it
     checks them: k_rows [nK] finite, ascending and > 0, nK <= TRANSIT_FIT_MAX_ROWS; profile [nK, M + 1] finite with M in
     [1, TRANSIT_FIT_MAX_M]; impacts, ratios, shifts 1-D, not empty, finite and ascending, impacts in [0, 1), ratios > 0, at
     most TRANSIT_FIT_MAX_UNITS units; sub [S] finite, S in [1, TRANSIT_FIT_MAX_SUB]; window finite and at least
-    0.5 * max(ratio) + max|shift|; min_count an integer >= 1; delta finite and >= 0.  ValueError otherwise."""
-    tables = []
-    for name, v in (("k_rows", k_rows), ("impacts", impacts), ("ratios", ratios), ("shifts", shifts), ("sub", sub)):
-        try:
-            v = numpy.ascontiguousarray(numpy.asarray(v, dtype=numpy.float64))
-        except (TypeError, ValueError):
-            raise ValueError("transit fit: %s must hold numbers" % name)
-        if v.ndim != 1 or len(v) < 1:
-            raise ValueError("transit fit: %s must be a table [k] with k >= 1, got shape %s" % (name, v.shape))
-        if not numpy.all(numpy.isfinite(v)) or (name != "sub" and not numpy.all(v[1:] >= v[:-1])):
-            raise ValueError("transit fit: %s must be finite%s" % (name, "" if name == "sub" else " and ascending"))
-        tables.append(v)
-    k_rows, impact, ratio, shift, sub = tables
+    0.5 * max(ratio) + max|shift|; min_count an integer >= 1; delta finite and >= 0.  ValueError otherwise, headed `what`:
+    tls_remove_transits takes the same k_rows, profile and sub."""
+    k_rows, impact, ratio, shift = (_checks.table(what, name, v) for name, v in (
+        ("k_rows", k_rows), ("impacts", impacts), ("ratios", ratios), ("shifts", shifts)))
+    sub = _checks.table(what, "sub", sub, ascending=False)
     if not k_rows[0] > 0.0 or len(k_rows) > TRANSIT_FIT_MAX_ROWS:
-        raise ValueError("transit fit: k_rows must hold at most %d values > 0" % TRANSIT_FIT_MAX_ROWS)
+        raise _checks.refusal(what, "k_rows must hold at most %d values > 0" % TRANSIT_FIT_MAX_ROWS)
     try:
         profile = numpy.ascontiguousarray(numpy.asarray(profile, dtype=numpy.float64))
     except (TypeError, ValueError):
-        raise ValueError("transit fit: profile must hold numbers")
+        raise _checks.refusal(what, "profile must hold numbers")
     if profile.ndim != 2 or profile.shape[0] != len(k_rows) or not 1 <= profile.shape[1] - 1 <= TRANSIT_FIT_MAX_M:
-        raise ValueError("transit fit: profile must be [len(k_rows), M + 1] with M in [1, %d], got shape %s"
-                         % (TRANSIT_FIT_MAX_M, profile.shape))
+        raise _checks.refusal(what, "profile must be [len(k_rows), M + 1] with M in [1, %d], got shape %s"
+                              % (TRANSIT_FIT_MAX_M, profile.shape))
     if not numpy.all(numpy.isfinite(profile)):
-        raise ValueError("transit fit: profile must be finite")
+        raise _checks.refusal(what, "profile must be finite")
     if not (impact[0] >= 0.0 and impact[-1] < 1.0):
-        raise ValueError("transit fit: every impact must be in [0, 1)")
+        raise _checks.refusal(what, "every impact must be in [0, 1)")
     if not ratio[0] > 0.0:
-        raise ValueError("transit fit: every ratio must be > 0, got %r" % ratio[0])
+        raise _checks.refusal(what, "every ratio must be > 0, got %r" % ratio[0])
     if len(sub) > TRANSIT_FIT_MAX_SUB:
-        raise ValueError("transit fit: n_sub %d outside [1, %d]" % (len(sub), TRANSIT_FIT_MAX_SUB))
+        raise _checks.refusal(what, "n_sub %d outside [1, %d]" % (len(sub), TRANSIT_FIT_MAX_SUB))
     units = len(impact) * len(ratio) * len(shift)
     if not 1 <= units <= TRANSIT_FIT_MAX_UNITS:
-        raise ValueError("transit fit: %d units, outside [1, %d]" % (units, TRANSIT_FIT_MAX_UNITS))
-    if isinstance(window, (bool, numpy.bool_)) or not isinstance(window, numbers.Real) or not numpy.isfinite(window):
-        raise ValueError("transit fit: window must be finite, got %r" % (window,))
-    least = 0.5 * float(ratio[-1]) + max(abs(float(shift[0])), abs(float(shift[-1])))
-    if not float(window) >= least:
-        raise ValueError("transit fit: window %r is below 0.5 * max(ratio) + max|shift| = %r: the model must lie inside it"
-                         % (window, least))
-    if isinstance(min_count, (bool, numpy.bool_)) or not isinstance(min_count, numbers.Integral) or int(min_count) < 1:
-        raise ValueError("transit fit: min_count must be an integer >= 1, got %r" % (min_count,))
-    if isinstance(delta, (bool, numpy.bool_)) or not isinstance(delta, numbers.Real) or not (0.0 <= float(delta) < numpy.inf):
-        raise ValueError("transit fit: delta must be finite and >= 0, got %r" % (delta,))
-    return k_rows, profile, impact, ratio, shift, sub, float(window), int(min_count), float(delta)
+        raise _checks.refusal(what, "%d units, outside [1, %d]" % (units, TRANSIT_FIT_MAX_UNITS))
+    window = _checks.fit_window(what, window, ratio, shift)
+    return (k_rows, profile, impact, ratio, shift, sub, window, _checks.integer(what, "min_count", min_count, 1),
+            _checks.finite_at_least(what, "delta", delta))
 
 
 def transit_fit_window_holds(duration, ratio, shift, sub, window):
@@ -887,24 +741,18 @@ def transit_fit_window_holds(duration, ratio, shift, sub, window):
 def transit_fit_arguments(t, y, dy, period, T0, duration, row_first, k_rows, profile, impacts, ratios, shifts, sub, curve=None,
                           window=1.0, min_count=3, delta=1.0):
     """What tls_transit_fit takes, checked as it checks them and packed for it -- a dict with t [n], y and dy [n_curves, n],
-    period, T0, duration, curve [n_fits] (as shape_fit_arguments has them), row_first [n_fits] int64 in [0, nK), and k_rows,
-    profile, impact, ratio, shift, sub, window, min_count, delta (transit_fit_tables).  ValueError otherwise.  GPU-free."""
+    period, T0, duration, curve [n_fits] (candidate_series, n up to SHAPE_MAX_POINTS), row_first [n_fits] int64 in [0, nK),
+    and k_rows, profile, impact, ratio, shift, sub, window, min_count, delta (transit_fit_tables).  ValueError otherwise.
+    GPU-free."""
     k_rows, profile, impact, ratio, shift, sub, window, min_count, delta = transit_fit_tables(
         k_rows, profile, impacts, ratios, shifts, sub, window, min_count, delta)
-    try:
-        a = shape_fit_arguments(t, y, dy, period, T0, duration, [1.0], [0.0, 0.5], [0.0], curve)
-    except ValueError as e:
-        raise ValueError(str(e).replace("shape fit:", "transit fit:"))
-    rows = numpy.atleast_1d(numpy.asarray(row_first))
-    if rows.shape != a["period"].shape or (rows.size and (rows.dtype.kind not in "iu" or rows.min() < 0
-                                                            or rows.max() >= len(k_rows))):
-        raise ValueError("transit fit: row_first must hold one row in [0, %d) a candidate" % len(k_rows))
+    a = candidate_series("transit fit", t, y, dy, period, T0, duration, curve, SHAPE_MAX_POINTS)
+    rows = _checks.indices("transit fit", "row_first", row_first, a["period"].shape, len(k_rows), "row")
     if not transit_fit_window_holds(a["duration"], ratio, shift, sub, window):
         raise ValueError("transit fit: window %r does not hold the widest, farthest shifted model plus half an exposure for "
                          "the shortest duration" % (window,))
-    return dict(t=a["t"], y=a["y"], dy=a["dy"], period=a["period"], T0=a["T0"], duration=a["duration"], curve=a["curve"],
-                row_first=numpy.ascontiguousarray(rows, dtype=numpy.int64), k_rows=k_rows, profile=profile, impact=impact,
-                ratio=ratio, shift=shift, sub=sub, window=window, min_count=min_count, delta=delta)
+    return dict(a, row_first=rows, k_rows=k_rows, profile=profile, impact=impact, ratio=ratio, shift=shift, sub=sub,
+                window=window, min_count=min_count, delta=delta)
 
 
 # tls_centroid_record (include/tls_amd.h): a candidate's centroid-shift test, 16 doubles
@@ -922,15 +770,9 @@ CENTROID_DTYPE = numpy.dtype([(k, "f8") for k in CENTROID_FIELDS])
 def centroid_options(window=3.0, min_in=1, min_out=3, max_epochs=CENTROID_MAX_EPOCHS):
     """(window, min_in, min_out, max_epochs) as tls_centroid_test takes them, checked as it checks them: window a finite
     number >= 1; min_in and min_out integers >= 1; max_epochs an integer in [1, CENTROID_MAX_EPOCHS].  ValueError otherwise."""
-    if isinstance(window, (bool, numpy.bool_)) or not isinstance(window, numbers.Real) or not (1.0 <= float(window) < numpy.inf):
-        raise ValueError("centroid test: window must be finite and >= 1, got %r" % (window,))
-    for name, v in (("min_in", min_in), ("min_out", min_out)):
-        if isinstance(v, (bool, numpy.bool_)) or not isinstance(v, numbers.Integral) or int(v) < 1:
-            raise ValueError("centroid test: %s must be an integer >= 1, got %r" % (name, v))
-    if isinstance(max_epochs, (bool, numpy.bool_)) or not isinstance(max_epochs, numbers.Integral) \
-            or not 1 <= int(max_epochs) <= CENTROID_MAX_EPOCHS:
-        raise ValueError("centroid test: max_epochs must be an integer in [1, %d], got %r" % (CENTROID_MAX_EPOCHS, max_epochs))
-    return float(window), int(min_in), int(min_out), int(max_epochs)
+    what = "centroid test"
+    return (_checks.finite_at_least(what, "window", window, 1.0), _checks.integer(what, "min_in", min_in, 1),
+            _checks.integer(what, "min_out", min_out, 1), _checks.integer(what, "max_epochs", max_epochs, 1, CENTROID_MAX_EPOCHS))
 
 
 def centroid_rows(cx, cy, shape):
@@ -965,23 +807,12 @@ def centroid_arguments(t, y, cx, cy, period, T0, duration, shape, curve=None, wi
         raise ValueError("centroid test: the shape must be [L] with L in [2, %d], got %s" % (CENTROID_MAX_SHAPE, shape.shape))
     if not numpy.all(numpy.isfinite(shape)):
         raise ValueError("centroid test: the shape must be finite")
-    t = numpy.asarray(t, dtype=numpy.float64)
-    if t.ndim != 1 or not 1 <= len(t) <= CENTROID_MAX_POINTS:
-        raise ValueError("centroid test: t must have shape [n] with n in [1, %d], got %s" % (CENTROID_MAX_POINTS, t.shape))
-    if not numpy.all(numpy.isfinite(t)) or not numpy.all(t[1:] >= t[:-1]):
-        raise ValueError("centroid test: t must be finite and non-decreasing")
-    y = numpy.asarray(y, dtype=numpy.float64)
-    if y.ndim == 1:
-        y = y[None, :]
-    if y.ndim != 2 or y.shape[1] != len(t):
-        raise ValueError("centroid test: y must be [n] or [n_curves, n] over the time stamps t [n]")
-    if y.size and not numpy.all(numpy.isfinite(y)):
-        raise ValueError("centroid test: y has a NaN or an infinite value")
+    t = _checks.times("centroid test", t, CENTROID_MAX_POINTS)
+    y = _checks.flux_rows("centroid test", t, y)
     cx, cy = centroid_rows(cx, cy, y.shape)
-    period, T0, duration, curve = shape_fit_candidates(period, T0, duration, curve, len(y), "centroid test")
-    return dict(t=numpy.ascontiguousarray(t), y=numpy.ascontiguousarray(y), cx=cx, cy=cy, period=period, T0=T0,
-                duration=duration, curve=curve, shape=shape, window=window, min_in=min_in, min_out=min_out,
-                max_epochs=max_epochs)
+    period, T0, duration, curve = _checks.candidates("centroid test", period, T0, duration, curve, len(y))
+    return dict(t=t, y=y, cx=cx, cy=cy, period=period, T0=T0, duration=duration, curve=curve, shape=shape, window=window,
+                min_in=min_in, min_out=min_out, max_epochs=max_epochs)
 
 
 # tls_views_record (include/tls_amd.h): a candidate's folded views, 7 doubles; the local views in the order of the arrays
@@ -1000,16 +831,15 @@ def folded_views_tables(n_global=2001, n_local=201, local_durations=4.0, local_w
     """(n_global, n_local, local_durations, local_width) as tls_folded_views takes them, checked as it checks them: the bin
     counts integers in [2, VIEWS_MAX_BINS]; local_durations finite and > 0; local_width finite, > 0 and at most
     2 * local_durations (a bin no wider than the view).  ValueError otherwise."""
-    for name, v in (("n_global", n_global), ("n_local", n_local)):
-        if isinstance(v, (bool, numpy.bool_)) or not isinstance(v, numbers.Integral) or not 2 <= int(v) <= VIEWS_MAX_BINS:
-            raise ValueError("folded views: %s must be an integer in [2, %d], got %r" % (name, VIEWS_MAX_BINS, v))
+    what = "folded views"
+    n_global = _checks.integer(what, "n_global", n_global, 2, VIEWS_MAX_BINS)
+    n_local = _checks.integer(what, "n_local", n_local, 2, VIEWS_MAX_BINS)
     for name, v in (("local_durations", local_durations), ("local_width", local_width)):
-        if isinstance(v, (bool, numpy.bool_)) or not isinstance(v, numbers.Real) or not (0.0 < float(v) < numpy.inf):
-            raise ValueError("folded views: %s must be finite and > 0, got %r" % (name, v))
+        _checks.finite_positive(what, name, v)
     if float(local_width) > 2.0 * float(local_durations):
         raise ValueError("folded views: local_width %r is wider than the view, 2 * local_durations = %r"
                          % (local_width, 2.0 * float(local_durations)))
-    return int(n_global), int(n_local), float(local_durations), float(local_width)
+    return n_global, n_local, float(local_durations), float(local_width)
 
 
 def folded_views_arguments(t, y, period, T0, duration, curve=None, secondary_phase=None, n_global=2001, n_local=201,
@@ -1019,27 +849,14 @@ def folded_views_arguments(t, y, period, T0, duration, curve=None, secondary_pha
     (shape_fit_candidates: any value, curve in [0, n_curves)), secondary_phase [n_fits] or None, and the four table
     parameters (folded_views_tables).  ValueError otherwise.  GPU-free."""
     n_global, n_local, k, width = folded_views_tables(n_global, n_local, local_durations, local_width)
-    t = numpy.asarray(t, dtype=numpy.float64)
-    if t.ndim != 1 or not 1 <= len(t) <= VIEWS_MAX_POINTS:
-        raise ValueError("folded views: t must have shape [n] with n in [1, %d], got %s" % (VIEWS_MAX_POINTS, t.shape))
-    if not numpy.all(numpy.isfinite(t)) or not numpy.all(t[1:] >= t[:-1]):
-        raise ValueError("folded views: t must be finite and non-decreasing")
-    y = numpy.asarray(y, dtype=numpy.float64)
-    if y.ndim == 1:
-        y = y[None, :]
-    if y.ndim != 2 or y.shape[1] != len(t):
-        raise ValueError("folded views: y must be [n] or [n_curves, n] over the time stamps t [n]")
-    if y.size and not numpy.all(numpy.isfinite(y)):
-        raise ValueError("folded views: y has a NaN or an infinite value")
-    period, T0, duration, curve = shape_fit_candidates(period, T0, duration, curve, len(y), "folded views")
+    t = _checks.times("folded views", t, VIEWS_MAX_POINTS)
+    y = _checks.flux_rows("folded views", t, y)
+    period, T0, duration, curve = _checks.candidates("folded views", period, T0, duration, curve, len(y))
     if secondary_phase is not None:
-        try:
-            secondary_phase = numpy.ascontiguousarray(numpy.atleast_1d(numpy.asarray(secondary_phase, dtype=numpy.float64)))
-        except (TypeError, ValueError):
-            raise ValueError("folded views: secondary_phase must hold numbers")
+        secondary_phase, = _checks.floats("folded views", [secondary_phase], "secondary_phase must hold numbers")
         if secondary_phase.shape != period.shape:
             raise ValueError("folded views: secondary_phase must be [n_fits], one phase a candidate")
-    return dict(t=numpy.ascontiguousarray(t), y=numpy.ascontiguousarray(y), period=period, T0=T0, duration=duration,
+    return dict(t=t, y=y, period=period, T0=T0, duration=duration,
                 curve=curve, secondary_phase=secondary_phase, n_global=n_global, n_local=n_local, local_durations=k,
                 local_width=width)
 
@@ -1070,10 +887,7 @@ def gls_axes(t, frequencies, n_min=3):
         f = numpy.ascontiguousarray(numpy.atleast_1d(numpy.asarray(frequencies, dtype=numpy.float64)))
     except (TypeError, ValueError):
         raise ValueError("periodogram: t and frequencies must hold numbers")
-    if t.ndim != 1 or not n_min <= len(t) <= GLS_MAX_POINTS:
-        raise ValueError("periodogram: t must have shape [n] with n in [%d, %d], got %s" % (n_min, GLS_MAX_POINTS, t.shape))
-    if not numpy.all(numpy.isfinite(t)) or not numpy.all(t[1:] >= t[:-1]):
-        raise ValueError("periodogram: t must be finite and ascending")
+    t = _checks.times("periodogram", t, GLS_MAX_POINTS, n_min, "ascending")
     if f.ndim != 1 or not 1 <= len(f) <= GLS_MAX_FREQUENCIES:
         raise ValueError("periodogram: frequencies must have shape [F] with F in [1, %d], got %s" % (GLS_MAX_FREQUENCIES, f.shape))
     if not numpy.all(numpy.isfinite(f) & (f > 0.0)):
@@ -1089,17 +903,10 @@ def gls_rows(t, y, dy, what="periodogram"):
         dy = None if dy is None else numpy.asarray(dy, dtype=numpy.float64)
     except (TypeError, ValueError):
         raise ValueError("%s: the light curves must hold numbers" % what)
-    if y.ndim == 1:
-        y = y[None, :]
-        if dy is not None and dy.ndim == 1:
-            dy = dy[None, :]
-    if y.ndim != 2 or y.shape[1] != len(t) or (dy is not None and dy.shape != y.shape):
-        raise ValueError("%s: flux and dy must be [n] or [n_curves, n] over the time stamps t [n]" % what)
-    if y.size and not numpy.all(numpy.isfinite(y)):
-        raise ValueError("%s: the flux has a NaN or an infinite value" % what)
-    if dy is not None and dy.size and not (dy.min() > 0.0 and dy.max() < numpy.inf):
-        raise ValueError("%s: dy has a NaN, infinite or non-positive value" % what)
-    return numpy.ascontiguousarray(y), None if dy is None else numpy.ascontiguousarray(dy)
+    len(t)      # (the rows lie over an array t: None, which row_shapes takes for "any n", stays the TypeError it was)
+    if y.ndim != 1 and dy is not None and dy.ndim == 1:     # (a dy [n] goes with a y [n] only)
+        raise _checks.over_t(what, "flux and dy")
+    return _checks.row_values(what, *_checks.row_shapes(what, t, y, dy, "flux and dy"), noun="the flux")
 
 
 def lomb_scargle_arguments(t, y, dy, frequencies, peaks=None, separation=0.02):
@@ -1132,17 +939,10 @@ def prewhiten_arguments(t, y, dy, frequencies, n_terms=3, harmonics=1, min_power
     [0, 1]).  ValueError otherwise.  GPU-free."""
     t, f = gls_axes(t, frequencies, 3)
     y, dy = gls_rows(t, y, dy, "prewhiten")
-
-    def integer(name, value, high):
-        if isinstance(value, (bool, numpy.bool_)) or not isinstance(value, numbers.Integral) or not 1 <= int(value) <= high:
-            raise ValueError("prewhiten: %s must be an integer in [1, %d], got %r" % (name, high, value))
-        return int(value)
-
-    k = integer("n_terms", n_terms, PREWHITEN_MAX_TERMS)
-    h = integer("harmonics", harmonics, SINE_MAX_HARMONICS)
-    if isinstance(min_power, (bool, numpy.bool_)) or not isinstance(min_power, numbers.Real) or not (0.0 <= float(min_power) <= 1.0):
-        raise ValueError("prewhiten: min_power must lie in [0, 1], got %r" % (min_power,))
-    return dict(t=t, frequencies=f, y=y, dy=dy, n_terms=k, harmonics=h, min_power=float(min_power))
+    k = _checks.integer("prewhiten", "n_terms", n_terms, 1, PREWHITEN_MAX_TERMS)
+    h = _checks.integer("prewhiten", "harmonics", harmonics, 1, SINE_MAX_HARMONICS)
+    min_power = _checks.within("prewhiten", "min_power", min_power, 0.0, 1.0, text="must lie in [0, 1]")
+    return dict(t=t, frequencies=f, y=y, dy=dy, n_terms=k, harmonics=h, min_power=min_power)
 
 
 def sine_test_arguments(t, y, dy, period, T0, duration, curve, mask, harmonics):
@@ -1154,10 +954,7 @@ def sine_test_arguments(t, y, dy, period, T0, duration, curve, mask, harmonics):
         t = numpy.ascontiguousarray(numpy.asarray(t, dtype=numpy.float64))
     except (TypeError, ValueError):
         raise ValueError("sine test: t must hold numbers")
-    if t.ndim != 1 or not 1 <= len(t) <= GLS_MAX_POINTS:
-        raise ValueError("sine test: t must have shape [n] with n in [1, %d], got %s" % (GLS_MAX_POINTS, t.shape))
-    if not numpy.all(numpy.isfinite(t)) or not numpy.all(t[1:] >= t[:-1]):
-        raise ValueError("sine test: t must be finite and ascending")
+    t = _checks.times("sine test", t, GLS_MAX_POINTS, order="ascending")
     y, dy = gls_rows(t, y, dy, "sine test")
     if (T0 is None) != (duration is None):
         raise ValueError("sine test: T0 and duration come together")
@@ -1168,31 +965,20 @@ def sine_test_arguments(t, y, dy, period, T0, duration, curve, mask, harmonics):
         harmonics = numpy.ascontiguousarray(numpy.atleast_1d(numpy.asarray(harmonics, dtype=numpy.float64)))
     except (TypeError, ValueError):
         raise ValueError("sine test: period, T0, duration and harmonics must be numbers")
-    if period.ndim != 1 or (T0 is not None and not period.shape == T0.shape == duration.shape):
-        raise ValueError("sine test: period, T0 and duration must be [n_fits]")
+    _checks.columns("sine test", "period, T0 and duration", (period,) if T0 is None else (period, T0, duration))
     if harmonics.ndim != 1 or not 1 <= len(harmonics) <= SINE_MAX_HARMONICS \
             or not numpy.all(numpy.isfinite(harmonics) & (harmonics > 0.0)):
         raise ValueError("sine test: harmonics must be 1 to %d finite values > 0" % SINE_MAX_HARMONICS)
-    if isinstance(mask, (bool, numpy.bool_)) or not isinstance(mask, numbers.Real) or not (0.0 <= float(mask) < numpy.inf):
-        raise ValueError("sine test: mask must be finite and >= 0, got %r" % (mask,))
-    if curve is None:
-        if len(period) != len(y):
-            raise ValueError("sine test: curve=None takes one candidate a light curve: %d candidates, %d curves"
-                             % (len(period), len(y)))
-        curve = numpy.arange(len(y))
-    curve = numpy.atleast_1d(numpy.asarray(curve))
-    if curve.shape != period.shape or (curve.size and (curve.dtype.kind not in "iu" or curve.min() < 0 or curve.max() >= len(y))):
-        raise ValueError("sine test: curve must hold one index in [0, %d) a candidate" % len(y))
-    return dict(t=t, y=y, dy=dy, period=period, T0=T0, duration=duration, curve=numpy.ascontiguousarray(curve, dtype=numpy.int64),
-                mask=float(mask), harmonics=harmonics)
+    mask = _checks.finite_at_least("sine test", "mask", mask)
+    curve = _checks.curves("sine test", curve, len(period), len(y))
+    return dict(t=t, y=y, dy=dy, period=period, T0=T0, duration=duration, curve=curve, mask=mask, harmonics=harmonics)
 
 
 def peaks_arguments(k, separation, ratios, min_power):
     """(k, separation, ratios, min_power) as the peak selection takes them, checked as tls_find_peaks checks them: k an
     integer in [1, PEAKS_MAX_K]; separation finite and in [0, 1); at most PEAKS_MAX_RATIOS ratios, each finite and > 0;
     min_power not NaN (None: -inf, no threshold).  ValueError otherwise."""
-    if isinstance(k, bool) or not isinstance(k, numbers.Integral) or not 1 <= int(k) <= PEAKS_MAX_K:
-        raise ValueError("peaks: k must be an integer in [1, %d], got %r" % (PEAKS_MAX_K, k))
+    k = _checks.integer("peaks", "k", k, 1, PEAKS_MAX_K)
     try:
         sep = float(separation)
         rat = numpy.array([] if ratios is None else ratios, dtype=numpy.float64).reshape(-1)
@@ -1207,7 +993,7 @@ def peaks_arguments(k, separation, ratios, min_power):
         raise ValueError("peaks: every ratio must be finite and > 0")
     if numpy.isnan(low):
         raise ValueError("peaks: min_power is NaN")
-    return int(k), sep, numpy.ascontiguousarray(rat), low
+    return k, sep, numpy.ascontiguousarray(rat), low
 
 
 INJECTION_FIELDS = ("tp", "period", "rp", "a", "sin_inc", "omega")
@@ -1511,20 +1297,14 @@ def medfilt_arguments(y, kernel):
     if rows.ndim != 2 or not 1 <= rows.shape[1] <= 100000000:
         raise ValueError("flux must have shape [n] or [n_rows, n] with n in [1, 1e8], got %s" % (numpy.shape(y),))
     k = medfilt_kernel(kernel, rows.shape[1])
-    # (min and max propagate a NaN, which then fails both comparisons)
-    if rows.size and not (rows.min() > 0.0 and rows.max() < numpy.inf):
-        raise ValueError("flux has a NaN, infinite or non-positive value: the median filter needs flux > 0")
+    _checks.positive_values(None, rows, "flux", "the median filter")
     return numpy.ascontiguousarray(rows), k
 
 
 def _days(name, value, allow_inf):
     """value as a float, > 0 and finite (or +inf where allow_inf); ValueError otherwise (a bool or a non-number included)."""
-    if isinstance(value, (bool, numpy.bool_)) or not isinstance(value, numbers.Real):
-        raise ValueError("%s must be a number of days, got %r" % (name, value))
-    v = float(value)
-    if not (v > 0.0 and (v < numpy.inf or allow_inf)):
-        raise ValueError("%s must be %s, got %r" % (name, "> 0" if allow_inf else "finite and > 0", value))
-    return v
+    _checks.real(None, name, value, "must be a number of days")
+    return _checks.positive(None, name, value, "must be > 0") if allow_inf else _checks.finite_positive(None, name, value)
 
 
 def biweight_windows(t, window_length, break_tolerance):
@@ -1535,12 +1315,7 @@ def biweight_windows(t, window_length, break_tolerance):
     a window of more than BIWEIGHT_MAX_WINDOW points."""
     wl = _days("window_length", window_length, False)
     bt = _days("break_tolerance", break_tolerance, True)
-    t = numpy.asarray(t, dtype=numpy.float64)
-    if t.ndim != 1 or not 1 <= len(t) <= 100000000:
-        raise ValueError("t must have shape [n] with n in [1, 1e8], got %s" % (t.shape,))
-    if not numpy.all(numpy.isfinite(t)) or not numpy.all(t[1:] >= t[:-1]):
-        raise ValueError("t must be finite and non-decreasing")
-    t = numpy.ascontiguousarray(t)
+    t = _checks.times(None, t, _checks.MAX_ROW_POINTS)
     n = len(t)
     idx = numpy.arange(n)
     brk = numpy.ones(n, dtype=bool)
@@ -1579,9 +1354,7 @@ def biweight_arguments(t, y, window_length, break_tolerance):
         rows = rows[None, :]
     if rows.ndim != 2 or rows.shape[1] != len(t):
         raise ValueError("flux must have shape [n] or [n_rows, n] with n = len(t) = %d, got %s" % (len(t), numpy.shape(y)))
-    # (min and max propagate a NaN, which then fails both comparisons)
-    if rows.size and not (rows.min() > 0.0 and rows.max() < numpy.inf):
-        raise ValueError("flux has a NaN, infinite or non-positive value: the biweight filter needs flux > 0")
+    _checks.positive_values(None, rows, "flux", "the biweight filter")
     return t, numpy.ascontiguousarray(rows), wl, bt
 
 
@@ -1599,9 +1372,7 @@ def detrend_mask_rows(mask, shape, what="mask"):
 
 
 def _min_points(min_points):
-    if isinstance(min_points, (bool, numpy.bool_)) or not isinstance(min_points, numbers.Integral) or not 1 <= int(min_points) < 2 ** 31:
-        raise ValueError("min_points must be an integer >= 1, got %r" % (min_points,))
-    return int(min_points)
+    return _checks.integer(None, "min_points", min_points, 1, 2 ** 31 - 1, "must be an integer >= 1")
 
 
 def biweight_masked_arguments(t, y, mask, window_length, break_tolerance, min_points=3):
@@ -1623,10 +1394,7 @@ def transit_mask_arguments(t, period, T0, duration, curve=None, n_curves=None, f
                                 for v in (period, T0, duration))
     except (TypeError, ValueError):
         raise ValueError("transit mask: t, period, T0 and duration must hold numbers")
-    if t.ndim != 1 or not 1 <= len(t) <= 100000000:
-        raise ValueError("transit mask: t must have shape [n] with n in [1, 1e8], got %s" % (t.shape,))
-    if not numpy.all(numpy.isfinite(t)):
-        raise ValueError("transit mask: t must be finite")
+    t = _checks.times("transit mask", t, _checks.MAX_ROW_POINTS, order=None)
     if period.ndim != 1 or not period.shape == T0.shape == duration.shape:
         raise ValueError("transit mask: period, T0 and duration must have one shape [m], got %s, %s, %s"
                          % (period.shape, T0.shape, duration.shape))
@@ -1638,14 +1406,11 @@ def transit_mask_arguments(t, period, T0, duration, curve=None, n_curves=None, f
         curve = numpy.ascontiguousarray(curve, dtype=numpy.int64)
     if n_curves is None:
         n_curves = m if curve is None else (int(curve.max()) + 1 if m else 0)
-    if isinstance(n_curves, (bool, numpy.bool_)) or not isinstance(n_curves, numbers.Integral) or n_curves < 0:
-        raise ValueError("transit mask: n_curves must be an integer >= 0, got %r" % (n_curves,))
-    n_curves = int(n_curves)
+    n_curves = _checks.integer("transit mask", "n_curves", n_curves, 0)
     if (curve is None and m > n_curves) or (curve is not None and m and not (0 <= curve.min() and curve.max() < n_curves)):
         raise ValueError("transit mask: curve out of range [0, n_curves = %d)" % n_curves)
-    if isinstance(factor, (bool, numpy.bool_)) or not isinstance(factor, numbers.Real) or not (0.0 < float(factor) < numpy.inf):
-        raise ValueError("transit mask: factor must be finite and > 0, got %r" % (factor,))
-    return dict(t=t, period=period, T0=T0, duration=duration, curve=curve, n_curves=n_curves, factor=float(factor))
+    factor = _checks.finite_positive("transit mask", "factor", factor)
+    return dict(t=t, period=period, T0=T0, duration=duration, curve=curve, n_curves=n_curves, factor=factor)
 
 
 REMOVE_TRANSITS_FIELDS = ("period", "T0", "fit_row", "fit_amplitude", "fit_b", "fit_duration", "fit_shift")
@@ -1658,53 +1423,47 @@ def remove_transits_arguments(t, y, period, T0, row, amplitude, b, duration, shi
     of a transit-fit record; a NaN row belongs to a candidate that is skipped and is sent as row 0), curve [n_fits] int64 in
     [0, n_curves) (None: candidate f belongs to curve f) and k_rows, profile, sub as transit_fit_tables checks them.
     ValueError otherwise.  GPU-free."""
-    what = "remove transits: "
-    try:
-        tables = transit_fit_tables(k_rows, profile, [0.0], [1.0], [0.0], sub)
-    except ValueError as e:
-        raise ValueError(str(e).replace("transit fit: ", what))
+    what = "remove transits"
+    tables = transit_fit_tables(k_rows, profile, [0.0], [1.0], [0.0], sub, what=what)
     k_rows, profile, sub = tables[0], tables[1], tables[5]
+    no_numbers = "t, y and the candidates' columns must hold numbers"
     try:
         t = numpy.ascontiguousarray(numpy.asarray(t, dtype=numpy.float64))
         y = numpy.asarray(y, dtype=numpy.float64)
-        columns = [numpy.ascontiguousarray(numpy.atleast_1d(numpy.asarray(v, dtype=numpy.float64)))
-                   for v in (period, T0, amplitude, b, duration, shift)]
     except (TypeError, ValueError):
-        raise ValueError(what + "t, y and the candidates' columns must hold numbers")
+        raise _checks.refusal(what, no_numbers)
+    columns = _checks.floats(what, (period, T0, amplitude, b, duration, shift), no_numbers)
     if y.ndim == 1:
         y = y[None, :]
-    if t.ndim != 1 or y.ndim != 2 or y.shape[1] != len(t) or not 1 <= len(t) <= 100000000:
-        raise ValueError(what + "y must be [n] or [n_curves, n] over the time stamps t [n] with n in [1, 1e8], got %s over %s"
-                         % (y.shape, t.shape))
-    if not numpy.all(numpy.isfinite(t)) or not numpy.all(t[1:] >= t[:-1]):
-        raise ValueError(what + "t must be finite and non-decreasing")
+    if t.ndim != 1 or y.ndim != 2 or y.shape[1] != len(t) or not 1 <= len(t) <= _checks.MAX_ROW_POINTS:
+        raise _checks.over_t(what, "y", " with n in [1, 1e8], got %s over %s" % (y.shape, t.shape))
+    _checks.time_values(what, t)
     n_fits = len(columns[0])
     if any(v.ndim != 1 or len(v) != n_fits for v in columns):
-        raise ValueError(what + "period, T0, amplitude, b, duration and shift must have one shape [n_fits], got %s"
-                         % ([v.shape for v in columns],))
+        raise _checks.refusal(what, "period, T0, amplitude, b, duration and shift must have one shape [n_fits], got %s"
+                              % ([v.shape for v in columns],))
+    no_row = _checks.refusal(what, "row must hold one row in [0, %d) a candidate" % len(k_rows))
     rows = numpy.atleast_1d(numpy.asarray(row))
     if rows.shape != (n_fits,) or (n_fits and rows.dtype.kind not in "iuf"):
-        raise ValueError(what + "row must hold one row in [0, %d) a candidate" % len(k_rows))
+        raise no_row
     if rows.dtype.kind == "f":
         with numpy.errstate(all="ignore"):
             known = numpy.isfinite(rows)
             if not numpy.all(rows[known] == numpy.floor(rows[known])) or not numpy.all(numpy.abs(rows[known]) < 2.0 ** 31):
-                raise ValueError(what + "row must hold one row in [0, %d) a candidate" % len(k_rows))
+                raise no_row
             columns[2] = numpy.where(known, columns[2], numpy.nan)       # (no row: no candidate)
             rows = numpy.where(known, rows, 0.0)
     rows = numpy.ascontiguousarray(rows, dtype=numpy.int64)
     if n_fits and (rows.min() < 0 or rows.max() >= len(k_rows)):
-        raise ValueError(what + "row must hold one row in [0, %d) a candidate" % len(k_rows))
-    if curve is None:
-        if n_fits > y.shape[0]:
-            raise ValueError(what + "curve out of range [0, n_curves = %d)" % y.shape[0])
-    else:
+        raise no_row
+    if curve is not None:
         curve = numpy.asarray(curve)
         if curve.shape != (n_fits,) or (n_fits and curve.dtype.kind not in "iu"):
-            raise ValueError(what + "curve must hold %d integers, got shape %s dtype %s" % (n_fits, curve.shape, curve.dtype))
+            raise _checks.refusal(what, "curve must hold %d integers, got shape %s dtype %s" % (n_fits, curve.shape, curve.dtype))
         curve = numpy.ascontiguousarray(curve, dtype=numpy.int64)
-        if n_fits and not (0 <= curve.min() and curve.max() < y.shape[0]):
-            raise ValueError(what + "curve out of range [0, n_curves = %d)" % y.shape[0])
+    in_range = n_fits <= y.shape[0] if curve is None else not n_fits or (0 <= curve.min() and curve.max() < y.shape[0])
+    if not in_range:
+        raise _checks.refusal(what, "curve out of range [0, n_curves = %d)" % y.shape[0])
     names = ("period", "T0", "amplitude", "b", "duration", "shift")
     return dict(dict(zip(names, (numpy.ascontiguousarray(v) for v in columns))), t=t, y=numpy.ascontiguousarray(y), row=rows,
                 curve=curve, k_rows=k_rows, profile=profile, sub=sub)
@@ -1712,15 +1471,7 @@ def remove_transits_arguments(t, y, period, T0, row, amplitude, b, duration, shi
 
 def _sysrem_integer(name, value, low, high, what):
     """value as an int in [low, high]; ValueError otherwise (a bool or a non-integer included)."""
-    if isinstance(value, (bool, numpy.bool_)):
-        raise ValueError("%s must be an integer, got %r" % (name, value))
-    try:
-        v = operator.index(value)
-    except TypeError:
-        raise ValueError("%s must be an integer, got %r" % (name, value))
-    if not low <= v <= high:
-        raise ValueError("%s must be in [%d, %s], got %d" % (name, low, what, v))
-    return v
+    return _checks.index(None, name, value, low, high, what)
 
 
 def sysrem_arguments(y, n_components=1, dy=None, max_iter=50, tol=1e-6):
@@ -1735,20 +1486,13 @@ def sysrem_arguments(y, n_components=1, dy=None, max_iter=50, tol=1e-6):
     k = _sysrem_integer("n_components", n_components, 1, min(SYSREM_MAX_COMPONENTS, rows.shape[0] - 1),
                         "min(SYSREM_MAX_COMPONENTS = %d, n_rows - 1 = %d)" % (SYSREM_MAX_COMPONENTS, rows.shape[0] - 1))
     iters = _sysrem_integer("max_iter", max_iter, 1, SYSREM_MAX_ITER, "SYSREM_MAX_ITER = %d" % SYSREM_MAX_ITER)
-    if isinstance(tol, (bool, numpy.bool_)) or not isinstance(tol, numbers.Real):
-        raise ValueError("tol must be a number, got %r" % (tol,))
-    tol = float(tol)
-    if not 0.0 <= tol < numpy.inf:
-        raise ValueError("tol must be finite and >= 0, got %r" % (tol,))
-    # (min and max propagate a NaN, which then fails both comparisons)
-    if not (rows.min() > 0.0 and rows.max() < numpy.inf):
-        raise ValueError("flux has a NaN, infinite or non-positive value: SysRem needs flux > 0")
+    tol = _checks.finite_at_least(None, "tol", _checks.real(None, "tol", tol))
+    _checks.positive_values(None, rows, "flux", "SysRem")
     if dy is not None:
         dy = numpy.asarray(dy, dtype=numpy.float64)
         if dy.shape != rows.shape:
             raise ValueError("dy must be None or have the shape of flux %s, got %s" % (rows.shape, dy.shape))
-        if not (dy.min() > 0.0 and dy.max() < numpy.inf):
-            raise ValueError("dy has a NaN, infinite or non-positive value: SysRem needs dy > 0")
+        _checks.positive_values(None, dy, "dy", "SysRem")
         dy = numpy.ascontiguousarray(dy)
     return numpy.ascontiguousarray(rows), dy, k, iters, tol
 
@@ -2292,12 +2036,11 @@ class Context(object):
         t = _f8(t)
         rows = numpy.ascontiguousarray(numpy.atleast_2d(numpy.asarray(y, dtype=numpy.float64)))
         if t.ndim != 1 or rows.ndim != 2 or rows.shape[1] != len(t) or len(t) < 1:
-            raise ValueError("y must be [n] or [n_curves, n] over the time stamps t [n]")
-        if not numpy.all(numpy.isfinite(t)):
-            raise ValueError("phase scan: the time stamps must be finite")
+            raise _checks.over_t(None, "y")
+        _checks.time_values("phase scan", t, None, "the time stamps")
+        # (numbers or numpy's own error, as ever; the shapes as every stage checks them)
         period, T0, duration = (_f8(numpy.atleast_1d(numpy.asarray(a, dtype=numpy.float64))) for a in (period, T0, duration))
-        if period.ndim != 1 or not period.shape == T0.shape == duration.shape:
-            raise ValueError("period, T0 and duration must be [n_fits]")
+        _checks.columns(None, "period, T0 and duration", (period, T0, duration))
         if curve is None:
             if len(period) != len(rows):
                 raise ValueError("curve=None takes one fit a light curve: %d fits, %d curves" % (len(period), len(rows)))

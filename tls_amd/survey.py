@@ -15,6 +15,7 @@ import operator
 
 import numpy
 
+from . import _checks
 from . import search as _search
 from .planning import search_inputs
 
@@ -523,9 +524,8 @@ def _candidate_rows(what, t, flux_batch, dy_batch=None):
         flux_batch = numpy.asarray(flux_batch)[None, :]
         dy_batch = None if dy_batch is None else numpy.asarray(dy_batch)[None, :]
     if numpy.ndim(flux_batch) != 2 or t.ndim != 1 or numpy.shape(flux_batch)[1] != len(t):
-        raise ValueError("flux_batch must be [n] or [n_curves, n] over the time stamps t [n]")
-    if not numpy.all(numpy.isfinite(t)) or not numpy.all(t[1:] >= t[:-1]):
-        raise ValueError("%s: t must be finite and non-decreasing" % what)
+        raise _checks.over_t(None, "flux_batch")
+    _checks.time_values(what, t)
     return t, flux_batch, dy_batch
 
 
@@ -856,7 +856,7 @@ def phase_scan(t, flux_batch, period, T0, duration, curve=None, max_bins=4096, m
     from ._lib import phase_scan_arguments
     max_bins, min_count = phase_scan_arguments(max_bins, min_count)
     if numpy.ndim(flux_batch) not in (1, 2) or numpy.ndim(t) != 1 or numpy.shape(flux_batch)[-1] != numpy.size(t):
-        raise ValueError("flux_batch must be [n] or [n_curves, n] over the time stamps t [n]")
+        raise _checks.over_t(None, "flux_batch")
     ctx = context if context is not None else _search.default_context(device)
     return _with_scans(None, ctx.phase_scan(t, flux_batch, period, T0, duration, curve=curve, max_bins=max_bins,
                                             min_count=min_count))
@@ -1092,10 +1092,8 @@ def power_batch_protected(t, flux_batch, detrend, sde_min, factor=1.5, n_peaks=1
 
     Returns (pass 2's result, info): info is a dict with `protected` [n_curves] bool (SDE of pass 1 >= sde_min), `mask`
     (uint8 [n_curves, n]) and `summary` (pass 1's)."""
-    if isinstance(factor, (bool, numpy.bool_)) or not isinstance(factor, numbers.Real) or not (0.0 < float(factor) < numpy.inf):
-        raise ValueError("power_batch_protected: factor must be finite and > 0, got %r" % (factor,))
-    if isinstance(sde_min, (bool, numpy.bool_)) or not isinstance(sde_min, numbers.Real) or numpy.isnan(sde_min):
-        raise ValueError("power_batch_protected: sde_min must be a number, got %r" % (sde_min,))
+    _checks.finite_positive("power_batch_protected", "factor", factor)
+    _checks.no_nan("power_batch_protected", "sde_min", sde_min, "must be a number")
     if "detrend_mask" in power_batch_kwargs:
         raise ValueError("power_batch_protected forms detrend_mask itself")
     for step in _detrend_steps(detrend):
@@ -1152,10 +1150,7 @@ def remove_transits(t, flux_batch, planets, curve=None, exposure=None, n_sub=5, 
     what = "remove transits: "
     one_row = numpy.ndim(flux_batch) == 1
     t, flux_batch, _ = _candidate_rows("remove transits", t, flux_batch)
-    try:
-        setup = _transit_fit_setup(t, None, None, None, exposure, n_sub, 1.0, 3, 1.0, profile, template_kwargs)
-    except ValueError as e:
-        raise ValueError(str(e).replace("transit fit: ", what))
+    setup = _transit_fit_setup(t, None, None, None, exposure, n_sub, 1.0, 3, 1.0, profile, template_kwargs, "remove transits")
     planets = numpy.asarray(planets)
     if planets.dtype.names is None or any(k not in planets.dtype.names for k in REMOVE_TRANSITS_FIELDS):
         raise ValueError(what + "planets must be a structured array with the fields %s" % (REMOVE_TRANSITS_FIELDS,))
@@ -1250,15 +1245,10 @@ def power_batch_multi(t, flux_batch, sde_min, n_planets=3, detrend=None, protect
     accepted entries of a row serve as remove_transits' planets.  info: a dict with `n_found` [n_curves], `searched` (the
     index array of the curves every pass searched, pass by pass) and with return_rows=True `rows`, flux_batch with every
     accepted planet divided out."""
-    if isinstance(sde_min, (bool, numpy.bool_)) or not isinstance(sde_min, numbers.Real) or numpy.isnan(sde_min):
-        raise ValueError("power_batch_multi: sde_min must be a number, got %r" % (sde_min,))
-    if isinstance(n_planets, (bool, numpy.bool_)) or not isinstance(n_planets, numbers.Integral) or not 1 <= int(n_planets) <= 8:
-        raise ValueError("power_batch_multi: n_planets must be an integer in [1, 8], got %r" % (n_planets,))
-    n_planets = int(n_planets)
+    _checks.no_nan("power_batch_multi", "sde_min", sde_min, "must be a number")
+    n_planets = _checks.integer("power_batch_multi", "n_planets", n_planets, 1, 8)
     if protect_factor is not None:
-        if isinstance(protect_factor, (bool, numpy.bool_)) or not isinstance(protect_factor, numbers.Real) \
-                or not (0.0 < float(protect_factor) < numpy.inf):
-            raise ValueError("power_batch_multi: protect_factor must be None or finite and > 0, got %r" % (protect_factor,))
+        _checks.finite_positive("power_batch_multi", "protect_factor", protect_factor, "must be None or finite and > 0")
         for step in _detrend_steps(detrend):
             if not isinstance(step, (Biweight, SysRem, Prewhiten)):
                 raise ValueError("power_batch_multi: the median filter (detrend=%r) has no masked form; use Biweight or "
@@ -1494,18 +1484,15 @@ def transit_time_fields():
 
 
 def _transit_times_options(search, min_ses, gap_tolerance=TRANSIT_TIMES_GAP_TOLERANCE, transit_depth_min=0.0,
-                           max_epochs=None):
+                           max_epochs=None, what="transit times"):
     """(search, min_ses, gap_tolerance, depth_min, max_epochs) of transit_times, checked: search and gap_tolerance numbers,
     search finite and > 0, gap_tolerance finite and >= 0; the others as _lib.transit_times_options checks them (max_epochs
-    None stays None).  ValueError otherwise."""
-    import numbers
+    None stays None).  ValueError otherwise, headed `what`."""
     from ._lib import transit_times_options
-    for name, v, low in (("search", search, False), ("gap_tolerance", gap_tolerance, True)):
-        if isinstance(v, (bool, numpy.bool_)) or not isinstance(v, numbers.Real) \
-                or not ((0.0 <= float(v) if low else 0.0 < float(v)) and float(v) < numpy.inf):
-            raise ValueError("transit times: %s must be finite and %s 0, got %r" % (name, ">=" if low else ">", v))
-    depth_min, min_ses, epochs = transit_times_options(transit_depth_min, min_ses, 1 if max_epochs is None else max_epochs)
-    return float(search), min_ses, float(gap_tolerance), depth_min, None if max_epochs is None else epochs
+    search = _checks.finite_positive(what, "search", search)
+    gap_tolerance = _checks.finite_at_least(what, "gap_tolerance", gap_tolerance)
+    depth_min, min_ses, epochs = transit_times_options(transit_depth_min, min_ses, 1 if max_epochs is None else max_epochs, what)
+    return search, min_ses, gap_tolerance, depth_min, None if max_epochs is None else epochs
 
 
 def _transit_times_request(transit_times, peak_fits, search, min_ses):
@@ -1518,24 +1505,24 @@ def _transit_times_request(transit_times, peak_fits, search, min_ses):
     return _transit_times_options(search, min_ses)[:2]
 
 
-def transit_time_rows(t, period, duration, search=1.0, gap_tolerance=TRANSIT_TIMES_GAP_TOLERANCE):
+def transit_time_rows(t, period, duration, search=1.0, gap_tolerance=TRANSIT_TIMES_GAP_TOLERANCE, what="transit times"):
     """(widths, span_max, row, reach) of transit_times for candidates of `period` and `duration` [n_fits] (days) on the
     time stamps t: with dt = median(diff(t)), L_f = clip(int(round(duration_f / dt)), 3, min(4096, n)); widths are the sorted
     distinct L_f, row[f] the index of L_f among them, span_max[r] = (L_r - 1) * dt * (1 + gap_tolerance), and
     reach_f = max(1, min(int(search * L_f), (int(P_f / dt) - 1) // 2, 4096)) -- two epochs never share a centre (a period that
-    is not finite and > 0 gets reach 1: the device reports status 1).  ValueError for fewer than 3 time stamps, a cadence or
-    a duration that is not finite and > 0."""
+    is not finite and > 0 gets reach 1: the device reports status 1).  ValueError, headed `what`, for fewer than 3 time
+    stamps, a cadence or a duration that is not finite and > 0."""
     from ._lib import SINGLE_MAX_WIDTH, SINGLE_MIN_WIDTH, TIMES_MAX_REACH
     t = numpy.asarray(t, dtype=numpy.float64)
     if t.ndim != 1 or len(t) < SINGLE_MIN_WIDTH:
-        raise ValueError("transit times: t must hold at least %d time stamps" % SINGLE_MIN_WIDTH)
+        raise _checks.refusal(what, "t must hold at least %d time stamps" % SINGLE_MIN_WIDTH)
     dt = float(numpy.median(numpy.diff(t)))
     if not (0.0 < dt < numpy.inf):
-        raise ValueError("transit times: the median cadence of t must be finite and > 0, got %r" % dt)
+        raise _checks.refusal(what, "the median cadence of t must be finite and > 0, got %r" % dt)
     period = numpy.atleast_1d(numpy.asarray(period, dtype=numpy.float64))
     duration = numpy.atleast_1d(numpy.asarray(duration, dtype=numpy.float64))
     if duration.size and not numpy.all((duration > 0.0) & (duration < numpy.inf)):
-        raise ValueError("transit times: every duration must be finite and > 0 days")
+        raise _checks.refusal(what, "every duration must be finite and > 0 days")
     top = min(SINGLE_MAX_WIDTH, len(t))
     L = numpy.array([min(max(int(round(float(d) / dt)), SINGLE_MIN_WIDTH), top) for d in duration], dtype=numpy.int64)
     widths = numpy.unique(L)
@@ -1555,6 +1542,15 @@ def _epoch_counts(t, period, T0):
     with numpy.errstate(all="ignore"):
         count = (numpy.floor((t[-1] - T0) / period) - numpy.ceil((t[0] - T0) / period)) + 1.0
     return numpy.where(numpy.isfinite(period) & numpy.isfinite(T0) & (period > 0.0), count, numpy.nan)
+
+
+def _most_epochs(t, period, T0):
+    """The default max_epochs of transit_times and event_vetting: the largest epoch count among the candidates that have
+    between 1 and TIMES_MAX_EPOCHS epochs inside the series; 1 without such a candidate."""
+    from ._lib import TIMES_MAX_EPOCHS
+    counts = _epoch_counts(t, period, T0)
+    counts = counts[(counts >= 1.0) & (counts <= TIMES_MAX_EPOCHS)]
+    return int(counts.max()) if len(counts) else 1
 
 
 def _with_oc(ephemeris, times):
@@ -1669,28 +1665,10 @@ def transit_times(t, flux_batch, period, T0, duration, curve=None, dy_batch=None
     search, min_ses, gap_tolerance, depth_min, max_epochs = _transit_times_options(search, min_ses, gap_tolerance,
                                                                                    transit_depth_min, max_epochs)
     t, flux_batch, dy_batch = _candidate_rows("transit times", t, flux_batch, dy_batch)
-    try:
-        period, T0, duration = (numpy.atleast_1d(numpy.asarray(v, dtype=numpy.float64)) for v in (period, T0, duration))
-    except (TypeError, ValueError):
-        raise ValueError("transit times: period, T0 and duration must be numbers")
-    if period.ndim != 1 or not period.shape == T0.shape == duration.shape:
-        raise ValueError("transit times: period, T0 and duration must be [n_fits]")
-    n_curves = numpy.shape(flux_batch)[0]
-    if curve is None:
-        if len(period) != n_curves:
-            raise ValueError("transit times: curve=None takes one candidate a light curve: %d candidates, %d curves"
-                             % (len(period), n_curves))
-        curve = numpy.arange(n_curves)
-    curve = numpy.atleast_1d(numpy.asarray(curve))
-    if curve.shape != period.shape or (curve.size and (curve.dtype.kind not in "iu" or curve.min() < 0
-                                                        or curve.max() >= n_curves)):
-        raise ValueError("transit times: curve must hold one index in [0, %d) a candidate" % n_curves)
+    period, T0, duration, curve = _checks.candidates("transit times", period, T0, duration, curve, numpy.shape(flux_batch)[0])
     widths, span_max, row, reach = transit_time_rows(t, period, duration, search, gap_tolerance)
     if max_epochs is None:
-        from ._lib import TIMES_MAX_EPOCHS
-        counts = _epoch_counts(t, period, T0)
-        counts = counts[(counts >= 1.0) & (counts <= TIMES_MAX_EPOCHS)]
-        max_epochs = int(counts.max()) if len(counts) else 1
+        max_epochs = _most_epochs(t, period, T0)
     inp, y_rows, dy_rows, ctx = _candidate_inputs(t, flux_batch, dy_batch, detrend, context, device, template_kwargs)
     from .template import reference_transit
     shapes = [1.0 - numpy.asarray(reference_transit(int(L), **inp["shape"])) for L in widths]
@@ -1713,9 +1691,7 @@ def event_alias_fields():
 
 
 def _ratio(name, value, what="event pairs"):
-    if isinstance(value, (bool, numpy.bool_)) or not isinstance(value, numbers.Real) or not (1.0 <= float(value) < numpy.inf):
-        raise ValueError("%s: %s must be finite and >= 1, got %r" % (what, name, value))
-    return float(value)
+    return _checks.finite_at_least(what, name, value, 1.0)
 
 
 def event_pairs(events, n_events, min_ses=7.0, depth_ratio=2.0, width_ratio=2.0, max_pairs=8):
@@ -1727,10 +1703,8 @@ def event_pairs(events, n_events, min_ses=7.0, depth_ratio=2.0, width_ratio=2.0,
     ascending.  ValueError for ratios below 1, a NaN min_ses, max_pairs < 1 and records without the fields index, ses, depth,
     width and row."""
     depth_ratio, width_ratio = _ratio("depth_ratio", depth_ratio), _ratio("width_ratio", width_ratio)
-    if isinstance(min_ses, (bool, numpy.bool_)) or not isinstance(min_ses, numbers.Real) or numpy.isnan(min_ses):
-        raise ValueError("event pairs: min_ses must be a number and no NaN, got %r" % (min_ses,))
-    if isinstance(max_pairs, (bool, numpy.bool_)) or not isinstance(max_pairs, numbers.Integral) or int(max_pairs) < 1:
-        raise ValueError("event pairs: max_pairs must be an integer >= 1, got %r" % (max_pairs,))
+    _checks.no_nan("event pairs", "min_ses", min_ses)
+    _checks.integer("event pairs", "max_pairs", max_pairs, 1)
     events = numpy.asarray(events)
     if events.dtype.names is None or not {"index", "ses", "depth", "width", "row"} <= set(events.dtype.names):
         raise ValueError("event pairs: events must be the records of single_transits")
@@ -1928,20 +1902,14 @@ def _event_vetting_options(search, chase_window, guard, min_ses, chase_fraction,
     """The options of event_vetting, checked, as a dict: search, min_ses, gap_tolerance, depth_min and max_epochs as
     _transit_times_options checks them (its messages headed "event vetting"); chase_window a number, finite and > 0; guard a
     number, finite and >= 0; the four parameters as _lib.event_vetting_options checks them.  ValueError otherwise."""
-    import numbers
     from ._lib import event_vetting_options
-    try:
-        search, min_ses, gap_tolerance, depth_min, max_epochs = _transit_times_options(search, min_ses, gap_tolerance,
-                                                                                       transit_depth_min, max_epochs)
-    except ValueError as e:
-        raise ValueError(str(e).replace("transit times", "event vetting"))
-    for name, v, low in (("chase_window", chase_window, False), ("guard", guard, True)):
-        if isinstance(v, (bool, numpy.bool_)) or not isinstance(v, numbers.Real) \
-                or not ((0.0 <= float(v) if low else 0.0 < float(v)) and float(v) < numpy.inf):
-            raise ValueError("event vetting: %s must be finite and %s 0, got %r" % (name, ">=" if low else ">", v))
+    search, min_ses, gap_tolerance, depth_min, max_epochs = _transit_times_options(
+        search, min_ses, gap_tolerance, transit_depth_min, max_epochs, "event vetting")
+    chase_window = _checks.finite_positive("event vetting", "chase_window", chase_window)
+    guard = _checks.finite_at_least("event vetting", "guard", guard)
     chase_fraction, chase_min, point_fraction, step_fraction = event_vetting_options(chase_fraction, chase_min, point_fraction,
                                                                                      step_fraction)
-    return dict(search=search, chase_window=float(chase_window), guard=float(guard), min_ses=min_ses,
+    return dict(search=search, chase_window=chase_window, guard=guard, min_ses=min_ses,
                 chase_fraction=chase_fraction, chase_min=chase_min, point_fraction=point_fraction,
                 step_fraction=step_fraction, gap_tolerance=gap_tolerance, depth_min=depth_min, max_epochs=max_epochs)
 
@@ -1959,7 +1927,7 @@ def _event_vetting_request(event_vetting, peak_fits, search, chase_window, guard
 
 
 def event_vetting_rows(t, period, duration, search=1.0, chase_window=EVENT_VETTING_CHASE_WINDOW, guard=EVENT_VETTING_GUARD,
-                       gap_tolerance=TRANSIT_TIMES_GAP_TOLERANCE):
+                       gap_tolerance=TRANSIT_TIMES_GAP_TOLERANCE, what="transit times"):
     """(widths, span_max, row, reach, chase_reach, guard, chase_span) of event_vetting for candidates of `period` and
     `duration` [n_fits] (days) on the time stamps t: the four arrays of transit_time_rows, and with dt = median(diff(t)) and
     L_f the candidate's width, chase_reach_f = min(int(chase_window * P_f / dt), 8192) samples, guard_f = int(guard * L_f)
@@ -1967,7 +1935,7 @@ def event_vetting_rows(t, period, duration, search=1.0, chase_window=EVENT_VETTI
     chase_window * P: `chases` keeps its meaning as a fraction of the period, and the windows beyond the cap are not looked
     at.  A period that is not finite and > 0 gets chase_reach 0 and chase_span 1 (the device reports status 1)."""
     from ._lib import EVENTS_MAX_CHASE
-    widths, span_max, row, reach = transit_time_rows(t, period, duration, search, gap_tolerance)
+    widths, span_max, row, reach = transit_time_rows(t, period, duration, search, gap_tolerance, what)
     dt = float(numpy.median(numpy.diff(numpy.asarray(t, dtype=numpy.float64))))
     period = numpy.atleast_1d(numpy.asarray(period, dtype=numpy.float64))
     chase_reach = numpy.zeros(len(period), dtype=numpy.int64)
@@ -2047,33 +2015,10 @@ def event_vetting(t, flux_batch, period, T0, duration, curve=None, dy_batch=None
     o = _event_vetting_options(search, chase_window, guard, min_ses, chase_fraction, chase_min, point_fraction, step_fraction,
                                gap_tolerance, transit_depth_min, max_epochs)
     t, flux_batch, dy_batch = _candidate_rows("event vetting", t, flux_batch, dy_batch)
-    try:
-        period, T0, duration = (numpy.atleast_1d(numpy.asarray(v, dtype=numpy.float64)) for v in (period, T0, duration))
-    except (TypeError, ValueError):
-        raise ValueError("event vetting: period, T0 and duration must be numbers")
-    if period.ndim != 1 or not period.shape == T0.shape == duration.shape:
-        raise ValueError("event vetting: period, T0 and duration must be [n_fits]")
-    n_curves = numpy.shape(flux_batch)[0]
-    if curve is None:
-        if len(period) != n_curves:
-            raise ValueError("event vetting: curve=None takes one candidate a light curve: %d candidates, %d curves"
-                             % (len(period), n_curves))
-        curve = numpy.arange(n_curves)
-    curve = numpy.atleast_1d(numpy.asarray(curve))
-    if curve.shape != period.shape or (curve.size and (curve.dtype.kind not in "iu" or curve.min() < 0
-                                                        or curve.max() >= n_curves)):
-        raise ValueError("event vetting: curve must hold one index in [0, %d) a candidate" % n_curves)
-    try:
-        widths, span_max, row, reach, chase_reach, guards, chase_span = event_vetting_rows(
-            t, period, duration, o["search"], o["chase_window"], o["guard"], o["gap_tolerance"])
-    except ValueError as e:
-        raise ValueError(str(e).replace("transit times", "event vetting"))
-    max_epochs = o["max_epochs"]
-    if max_epochs is None:
-        from ._lib import TIMES_MAX_EPOCHS
-        counts = _epoch_counts(t, period, T0)
-        counts = counts[(counts >= 1.0) & (counts <= TIMES_MAX_EPOCHS)]
-        max_epochs = int(counts.max()) if len(counts) else 1
+    period, T0, duration, curve = _checks.candidates("event vetting", period, T0, duration, curve, numpy.shape(flux_batch)[0])
+    widths, span_max, row, reach, chase_reach, guards, chase_span = event_vetting_rows(
+        t, period, duration, o["search"], o["chase_window"], o["guard"], o["gap_tolerance"], "event vetting")
+    max_epochs = _most_epochs(t, period, T0) if o["max_epochs"] is None else o["max_epochs"]
     inp, y_rows, dy_rows, ctx = _candidate_inputs(t, flux_batch, dy_batch, detrend, context, device, template_kwargs)
     from .template import reference_transit
     shapes = [1.0 - numpy.asarray(reference_transit(int(L), **inp["shape"])) for L in widths]
@@ -2226,16 +2171,19 @@ def transit_profile(k_rows=None, M=1024, **template_kwargs):
     profile[j][m] = 1 - F((1 + k_rows[j]) m / M; k_rows[j]) and profile[j][M] = 0, F being transit_model.quadratic_ld_flux for
     the quadratic, linear and uniform laws and transit_model.numerical_ld_flux for the others.  Default rows:
     numpy.geomspace(0.01, 0.5, 81).  Formed on the host, so the device stage is the same for every law."""
+    return _transit_profile("transit fit", k_rows, M, **template_kwargs)
+
+
+def _transit_profile(what, k_rows=None, M=1024, **template_kwargs):
+    """transit_profile, its messages headed `what`."""
     import warnings
     from . import transit_model, validate
     from ._lib import TRANSIT_FIT_MAX_M
     k_rows = numpy.array(TRANSIT_FIT_K_ROWS if k_rows is None else k_rows, dtype=numpy.float64)
     if k_rows.ndim != 1 or len(k_rows) < 1 or not numpy.all(numpy.isfinite(k_rows)) or not k_rows[0] > 0.0 \
             or not numpy.all(k_rows[1:] >= k_rows[:-1]):
-        raise ValueError("transit fit: k_rows must be a finite, ascending table of values > 0")
-    if isinstance(M, (bool, numpy.bool_)) or not isinstance(M, numbers.Integral) or not 1 <= int(M) <= TRANSIT_FIT_MAX_M:
-        raise ValueError("transit fit: M must be an integer in [1, %d], got %r" % (TRANSIT_FIT_MAX_M, M))
-    M = int(M)
+        raise _checks.refusal(what, "k_rows must be a finite, ascending table of values > 0")
+    M = _checks.integer(what, "M", M, 1, TRANSIT_FIT_MAX_M)
 
     class _Template(object):
         pass
@@ -2261,7 +2209,7 @@ def transit_profile(k_rows=None, M=1024, **template_kwargs):
         profile[j] = 1.0 - flux
         profile[j, M] = 0.0
     if not numpy.all(numpy.isfinite(profile)):
-        raise ValueError("transit fit: the profile of %r with u = %r is not finite" % (law, u))
+        raise _checks.refusal(what, "the profile of %r with u = %r is not finite" % (law, u))
     return k_rows, profile
 
 
@@ -2296,29 +2244,28 @@ def transit_fit_geometry(period, k, b, T14):
     return numpy.where(good, a_rs, numpy.nan), numpy.where(good, inc, numpy.nan), numpy.where(good, rho, numpy.nan)
 
 
-def _transit_fit_setup(t, impacts, ratios, shifts, exposure, n_sub, window, min_count, delta, profile, template_kwargs):
+def _transit_fit_setup(t, impacts, ratios, shifts, exposure, n_sub, window, min_count, delta, profile, template_kwargs,
+                       what="transit fit"):
     """The checked tables of a transit fit: a dict with k_rows, profile, impact, ratio, shift, sub, window, min_count, delta.
-    exposure None: the median cadence of t; 0: no smearing."""
+    exposure None: the median cadence of t; 0: no smearing.  `what` heads the messages: remove_transits sets up the same."""
     from ._lib import TRANSIT_FIT_MAX_SUB, transit_fit_tables
-    if isinstance(n_sub, (bool, numpy.bool_)) or not isinstance(n_sub, numbers.Integral) or not 1 <= int(n_sub) <= TRANSIT_FIT_MAX_SUB:
-        raise ValueError("transit fit: n_sub must be an integer in [1, %d], got %r" % (TRANSIT_FIT_MAX_SUB, n_sub))
+    _checks.integer(what, "n_sub", n_sub, 1, TRANSIT_FIT_MAX_SUB)
     if exposure is None:
         t = numpy.asarray(t, dtype=numpy.float64)
         exposure = float(numpy.median(numpy.diff(t))) if t.ndim == 1 and len(t) > 1 else 0.0
-    if isinstance(exposure, (bool, numpy.bool_)) or not isinstance(exposure, numbers.Real) or not (0.0 <= float(exposure) < numpy.inf):
-        raise ValueError("transit fit: exposure must be finite and >= 0 (days), got %r" % (exposure,))
+    _checks.finite_at_least(what, "exposure", exposure, text="must be finite and >= 0 (days)")
     S = int(n_sub) if float(exposure) > 0.0 else 1
     sub = float(exposure) * ((2.0 * numpy.arange(S) + 1.0) / (2.0 * S) - 0.5) if S > 1 else numpy.zeros(1)
     if profile is None:
-        profile = transit_profile(**template_kwargs)
+        profile = _transit_profile(what, **template_kwargs)
     try:
         k_rows, table = profile
     except (TypeError, ValueError):
-        raise ValueError("transit fit: profile must be the pair (k_rows, profile) of transit_profile")
+        raise _checks.refusal(what, "profile must be the pair (k_rows, profile) of transit_profile")
     names = ("k_rows", "profile", "impact", "ratio", "shift", "sub", "window", "min_count", "delta")
     return dict(zip(names, transit_fit_tables(
         k_rows, table, TRANSIT_FIT_IMPACTS if impacts is None else impacts, TRANSIT_FIT_RATIOS if ratios is None else ratios,
-        TRANSIT_FIT_SHIFTS if shifts is None else shifts, sub, window, min_count, delta)))
+        TRANSIT_FIT_SHIFTS if shifts is None else shifts, sub, window, min_count, delta, what)))
 
 
 def _seed_rows(k_rows, depth):
@@ -3020,8 +2967,7 @@ def noise_widths(t, hours=KEPLER_PULSE_HOURS):
 def _noise_spans(t, widths, gap_tolerance):
     """(span_max [W], pair_span) of noise_profile: (w - 1 + gap_tolerance) * cadence for every width and
     (1 + gap_tolerance) * cadence, the adjacency limit of the point-to-point sigma; all inf without t."""
-    if isinstance(gap_tolerance, (bool, numpy.bool_)) or not isinstance(gap_tolerance, numbers.Real) or not 0.0 <= float(gap_tolerance) < numpy.inf:
-        raise ValueError("noise profile: gap_tolerance must be finite and >= 0, got %r" % (gap_tolerance,))
+    _checks.finite_at_least("noise profile", "gap_tolerance", gap_tolerance)
     try:
         count = len(numpy.atleast_1d(numpy.asarray(widths)))
         steps = [numpy.float64(int(w) - 1) for w in numpy.atleast_1d(numpy.asarray(widths))]
