@@ -42,7 +42,7 @@ extern "C" {
  * (7: tls_shape_fit), (7: tls_nudft, tls_lomb_scargle, tls_sine_test); 8: every entry that takes `root, n_root` takes a
  * second table, `root, root_count, n_root`), (8: tls_ephemeris_match), (8: tls_folded_views),
  * (8: tls_event_vetting), (8: tls_centroid_test), (8: tls_noise_profile), (8: tls_transit_fit), (8: tls_remove_transits),
- * (8: tls_event_periods). */
+ * (8: tls_event_periods), (8: tls_decorrelate). */
 #define TLS_AMD_ABI_VERSION 8
 
 #define TLS_OK 0
@@ -1284,6 +1284,61 @@ typedef struct tls_noise_curve {
 int tls_noise_profile(tls_ctx *ctx, const double *t, const double *y, int64_t n, int64_t n_curves, const int64_t *widths,
                       const double *span_max, int64_t n_widths, double pair_span, double clip_upper, double clip_lower,
                       int64_t min_count, tls_noise_curve *out_curves, int64_t *out_count, double *out_robust, double *out_rms);
+
+/* ---- survey mode: regression detrending against centroids and basis vectors -------------------------------------------- */
+/* A weighted, robust linear least-squares fit of every light curve against series that are known to drive its systematics: the
+ * columns shared [n_shared][n] every curve takes (cotrending basis vectors, SysRem profiles of another ensemble) and then the
+ * columns own [n_curves][n_own][n] of the curve itself (monomials of its centroids); m = n_shared + n_own in
+ * [1, TLS_DECOR_MAX_TERMS]; the mean is always free.  y [n_curves][n]; dy (or NULL) gives w = 1.0 / (dy * dy), else w = 1.0;
+ * mask (or NULL) [n_curves][n], != 0: protected.  segments [n_segments + 1] ascends strictly from 0 to n; every
+ * (curve, segment) is fitted on its own.  F starts as the unprotected points of the segment; clip rounds run = 0.  Every sum
+ * runs over the points of F in ascending index from +0.0:
+ *   fit:
+ *     A  W = sum w * 1.0;  Sy = sum w * y;  Sk = sum w * x_k;  mu = Sy / W;  mean_k = Sk / W
+ *        F empty: status 1 with these sums over the whole segment
+ *     B  d = x_k - mean_k;  Vk = sum (w * d) * d;  scale_k = sqrt(Vk / W)
+ *        column k is live if 0 < scale_k < inf, else dropped (bit k of `dropped`)
+ *        |F| < live + 2: status 1
+ *     C  z = y / mu - 1.0;  u_k = (x_k - mean_k) / scale_k (live), 0.0 (dropped)
+ *        G_kl = sum (w * u_k) * u_l for l <= k;  G_kk = G_kk + ridge * W;  b_k = sum (w * u_k) * z
+ *     D  Cholesky in place, j ascending over the live columns:
+ *            s = G_jj;  for k < j live, ascending:  s = s - L_jk * L_jk
+ *            not (s > TLS_DECOR_PIVOT * G_jj): column j is collinear with those before it: dropped (bit j), no longer live
+ *            L_jj = sqrt(s);  for i > j live, ascending:  q = G_ij;  for k < j live, ascending:  q = q - L_ik * L_jk;  L_ij = q / L_jj
+ *        forward, j ascending live:  s = b_j;  for k < j live, ascending:  s = s - L_jk * v_k;  v_j = s / L_jj
+ *        back, j descending live:    s = v_j;  for k > j live, ascending:  s = s - L_kj * c_k;  c_j = s / L_jj
+ *        c_k = 0.0 for a dropped column
+ *     E  p = 0.0;  for k live, ascending:  p = p + c_k * u_k;  r = z - p  (every point of the segment)
+ *        Q = sum (w * r) * r;  sigma = sqrt(Q / W)
+ *   clip, only while rounds < n_iter:  up = sigma_upper * sigma;  down = -(sigma_lower * sigma)
+ *        a member of F leaves if r > up or r < down (inf switches a side off);  rounds = rounds + 1;  if any left: fit again
+ *   status 1 (at any fit): every c_k = 0.0, no column live or dropped, mean_k = 0.0, scale_k = 1.0, sigma = NaN
+ *   trend = mu * (1.0 + p);  flat = y / trend at EVERY point of the segment, protected and clipped ones included
+ *   status 2 (a trend value of the segment is not finite or not > 0): trend = mu, flat = y / mu; the rest of the record stays
+ * Every step is one IEEE double operation, so the results equal the Python statement in tests/decorrelate_spec.py bit for bit.
+ * A mask of zeros gives the bits of a call without one.  coef / scale are the coefficients in the units of the raw columns. */
+#define TLS_DECOR_MAX_TERMS 16
+#define TLS_DECOR_MAX_ITER 16
+#define TLS_DECOR_PIVOT 1e-10
+#define TLS_DECOR_LDS_POINTS 32768   /* a segment of at most this many points keeps F in the LDS, a longer one in device memory */
+typedef struct tls_decor_fit {
+    double status;                 /* 0 fitted; 1 too few points; 2 fitted, but the trend left (0, inf): trend = mu */
+    double dropped;                /* bit k: column k is constant on F or collinear with the columns before it */
+    double n_fit, n_clipped;       /* |F| at the end; the points the clip removed */
+    double rounds;                 /* clip rounds run */
+    double mu, sigma;
+    double n_live;                 /* the columns of the final fit */
+} tls_decor_fit;
+/* out_flat, out_trend (may be NULL) [n_curves][n]; out_fit [n_curves][n_segments]; out_coef, out_mean, out_scale (each may be
+ * NULL) [n_curves][n_segments][m].  The shared columns go to the device once a call; curves are processed in slabs, so device
+ * memory stays bounded.  Needs no plan and no search, and leaves a prepared plan as it is.  n_curves == 0 is a no-op.
+ * TLS_E_ARG, before any device work and with the outputs untouched, unless n is in [1, 1e8], m in [1, TLS_DECOR_MAX_TERMS],
+ * n_segments in [1, n] with segments ascending strictly from 0 to n, ridge finite and >= 0, n_iter in [0, TLS_DECOR_MAX_ITER],
+ * both sigmas > 0 (inf allowed, no NaN), y and dy finite and > 0, and every column finite. */
+int tls_decorrelate(tls_ctx *ctx, const double *y, const double *dy, const uint8_t *mask, int64_t n, int64_t n_curves,
+                    const double *shared, int64_t n_shared, const double *own, int64_t n_own, const int64_t *segments,
+                    int64_t n_segments, double ridge, int64_t n_iter, double sigma_upper, double sigma_lower, double *out_flat,
+                    double *out_trend, tls_decor_fit *out_fit, double *out_coef, double *out_mean, double *out_scale);
 
 /* The limb-darkened transit fit: the planet's size, impact parameter and T14 from the dip itself, with the exposure time in
  * the model.  A straight chord at constant speed crosses a limb-darkened disc: the separation is z^2 = b^2 + ((1 + k)^2 - b^2)

@@ -246,3 +246,42 @@ def fit_window(what, window, ratio, shift):
     if not float(window) >= least:
         raise refusal(what, "window %r is below 0.5 * max(ratio) + max|shift| = %r: the model must lie inside it" % (window, least))
     return float(window)
+
+
+# ---- decorrelation ---------------------------------------------------------------------------------------------------------
+def regressors(what, shared, own, n_curves, n, max_terms, single=False):
+    """(shared [n_shared, n], own [n_curves, n_own, n]) as contiguous float64, a None becoming an array without columns: at
+    least one of the two given, every value finite, n_shared + n_own in [1, max_terms].  One shared series may be [n]; with
+    `single` (the flux was one row) own is [n_own, n] or one series [n]."""
+    if shared is None and own is None:
+        raise refusal(what, "at least one of own and shared must be given")
+    try:
+        shared = numpy.zeros((0, n)) if shared is None else numpy.asarray(shared, dtype=numpy.float64)
+        own = numpy.zeros((n_curves, 0, n)) if own is None else numpy.asarray(own, dtype=numpy.float64)
+    except (TypeError, ValueError):
+        raise refusal(what, "own and shared must hold numbers")
+    if shared.ndim == 1:
+        shared = shared[None, :]
+    if shared.ndim != 2 or shared.shape[1] != n:
+        raise refusal(what, "shared must be [n_shared, n] with n = %d, got %s" % (n, shared.shape))
+    if single and own.ndim in (1, 2):
+        own = own.reshape((1, -1, own.shape[-1]))
+    if own.ndim != 3 or own.shape[0] != n_curves or own.shape[2] != n:
+        raise refusal(what, "own must be [n_curves, n_own, n] = [%d, n_own, %d]%s, got %s"
+                      % (n_curves, n, " or [n_own, n] for one row" if single else "", own.shape))
+    m = shared.shape[0] + own.shape[1]
+    if not 1 <= m <= max_terms:
+        raise refusal(what, "n_shared + n_own must lie in [1, %d], got %d + %d" % (max_terms, shared.shape[0], own.shape[1]))
+    if not (numpy.all(numpy.isfinite(shared)) and numpy.all(numpy.isfinite(own))):
+        raise refusal(what, "own and shared must be finite")
+    return numpy.ascontiguousarray(shared), numpy.ascontiguousarray(own)
+
+
+def segments(what, values, n):
+    """values as contiguous int64 [n_seg + 1]: integers ascending strictly from 0 to n; None: the one segment [0, n]."""
+    if values is None:
+        return numpy.array([0, n], dtype=numpy.int64)
+    v = numpy.asarray(values)
+    if v.ndim != 1 or len(v) < 2 or v.dtype.kind not in "iu" or v[0] != 0 or v[-1] != n or not numpy.all(v[1:] > v[:-1]):
+        raise refusal(what, "segments must hold integers ascending strictly from 0 to n = %d, got %r" % (n, values))
+    return numpy.ascontiguousarray(v, dtype=numpy.int64)

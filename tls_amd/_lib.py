@@ -110,6 +110,12 @@ NOISE_MAX_WIDTHS = 64
 NOISE_MAX_POINTS = 1 << 22
 NOISE_LDS_POINTS = 8192
 NOISE_THREADS = 256
+# include/tls_amd.h TLS_DECOR_*: the most columns and clip rounds of tls_decorrelate, the pivot below which a column counts as
+# collinear, and the points of a segment whose membership mask the LDS holds (a longer one keeps it in device scratch)
+DECOR_MAX_TERMS = 16
+DECOR_MAX_ITER = 16
+DECOR_PIVOT = 1e-10
+DECOR_LDS_POINTS = 32768
 PEAKS_LDS_PERIODS = 1 << 20   # tls_peaks.hip.h kPeaksLdsPeriods: a longer grid keeps its alive mask in device memory, not in LDS
 
 # every symbol include/tls_amd.h declares (tests check the export list against the header)
@@ -126,7 +132,7 @@ SYMBOLS = (
     "tls_ephemeris_match", "tls_folded_views", "tls_event_vetting", "tls_centroid_test", "tls_noise_profile",
     "tls_transit_fit",
     "tls_transit_mask", "tls_biweight_detrend_masked", "tls_prewhiten_masked",
-    "tls_remove_transits", "tls_event_periods",
+    "tls_remove_transits", "tls_event_periods", "tls_decorrelate",
     "tls_comm_unique_id", "tls_comm_init", "tls_comm_destroy", "tls_comm_info", "tls_comm_allgather_results", "tls_comm_allgather_device", "tls_comm_fetch_gathered",
     "tls_comm_stage_results", "tls_comm_allgather_staged", "tls_comm_fetch_staged",
     "tls_comm_barrier", "tls_comm_max",
@@ -1215,6 +1221,10 @@ def load():
     lib.tls_noise_profile.restype = ci
     lib.tls_noise_profile.argtypes = [vp, _c_double_p, _c_double_p, i64, i64, _c_int64_p, _c_double_p, i64, dbl, dbl, dbl, i64,
                                       ctypes.c_void_p, _c_int64_p, _c_double_p, _c_double_p]
+    lib.tls_decorrelate.restype = ci
+    lib.tls_decorrelate.argtypes = [vp, _c_double_p, _c_double_p, u8p, i64, i64, _c_double_p, i64, _c_double_p, i64, _c_int64_p,
+                                    i64, dbl, i64, dbl, dbl, _c_double_p, _c_double_p, ctypes.c_void_p, _c_double_p, _c_double_p,
+                                    _c_double_p]
     lib.tls_debug_peak_phase_scans.restype = ci
     lib.tls_debug_peak_phase_scans.argtypes = [vp, _c_double_p, i64, ctypes.c_void_p, _c_int64_p, i64, _c_double_p, _c_double_p,
                                                i64, dbl, _c_double_p, _c_double_p, i64, i64, ctypes.c_void_p, i64, i64,
@@ -1495,6 +1505,49 @@ def sysrem_arguments(y, n_components=1, dy=None, max_iter=50, tol=1e-6):
         _checks.positive_values(None, dy, "dy", "SysRem")
         dy = numpy.ascontiguousarray(dy)
     return numpy.ascontiguousarray(rows), dy, k, iters, tol
+
+
+# tls_decor_fit of include/tls_amd.h, in order: all doubles
+DECOR_FIELDS = ("status", "dropped", "n_fit", "n_clipped", "rounds", "mu", "sigma", "n_live")
+
+
+class DecorFit(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_double) for k in DECOR_FIELDS]
+
+
+DECOR_DTYPE = numpy.dtype([(k, "f8") for k in DECOR_FIELDS])
+
+
+def decorrelate_arguments(y, own=None, shared=None, dy=None, mask=None, segments=None, ridge=0.0, n_iter=3, sigma_upper=5.0,
+                          sigma_lower=5.0):
+    """What tls_decorrelate takes, checked as it checks them: a dict with y (float64 [n_curves, n], finite and > 0; one row
+    becomes [1, n]), dy (None, or y's shape, finite and > 0), mask (None, or uint8 rows of y's shape: detrend_mask_rows),
+    shared [n_shared, n] and own [n_curves, n_own, n] (finite, at least one given, n_shared + n_own in [1, DECOR_MAX_TERMS];
+    for one row own may be [n_own, n]), segments (int64, ascending strictly from 0 to n; None: [0, n]), ridge (finite, >= 0),
+    n_iter (an integer in [0, DECOR_MAX_ITER]) and sigma_upper, sigma_lower (> 0, inf allowed, no NaN).  ValueError otherwise.
+    GPU-free."""
+    what = "decorrelation"
+    try:
+        y = numpy.asarray(y, dtype=numpy.float64)
+        dy = None if dy is None else numpy.asarray(dy, dtype=numpy.float64)
+    except (TypeError, ValueError):
+        raise _checks.refusal(what, "the light curves and dy must hold numbers")
+    single = y.ndim == 1
+    y, dy = _checks.row_shapes(what, None, y, dy, names="flux" if dy is None else "flux and dy")
+    n_c, n = y.shape
+    if not 1 <= n <= _checks.MAX_ROW_POINTS:
+        raise _checks.refusal(what, "n must lie in [1, 1e8], got %d" % n)
+    _checks.positive_values(what, y, "flux", "decorrelation")
+    if dy is not None:
+        _checks.positive_values(what, dy, "dy", "decorrelation")
+    shared, own = _checks.regressors(what, shared, own, n_c, n, DECOR_MAX_TERMS, single)
+    return {"y": numpy.ascontiguousarray(y), "dy": None if dy is None else numpy.ascontiguousarray(dy),
+            "mask": None if mask is None else detrend_mask_rows(mask, y.shape), "shared": shared, "own": own,
+            "segments": _checks.segments(what, segments, n),
+            "ridge": _checks.finite_at_least(what, "ridge", ridge),
+            "n_iter": _checks.integer(what, "n_iter", n_iter, 0, DECOR_MAX_ITER),
+            "sigma_upper": _checks.positive(what, "sigma_upper", sigma_upper),
+            "sigma_lower": _checks.positive(what, "sigma_lower", sigma_lower), "single": single}
 
 
 def _f8(a):
@@ -2423,6 +2476,40 @@ class Context(object):
         if numpy.ndim(y) == 1:
             rows, model = rows[0], None if model is None else model[0]
         out = (rows,) + ((model,) if return_model else ()) + ((status,) if return_status else ())
+        return out[0] if len(out) == 1 else out
+
+    def decorrelate(self, y, own=None, shared=None, dy=None, mask=None, segments=None, ridge=0.0, n_iter=3, sigma_upper=5.0,
+                    sigma_lower=5.0, return_trend=False, return_fit=False):
+        """Regression detrending (tls_decorrelate; the statement: include/tls_amd.h, tests/decorrelate_spec.py) of the curves
+        y [n_curves, n] (or one row) against the columns shared [n_shared, n] and own [n_curves, n_own, n], every
+        (curve, segment) fitted on its own with up to n_iter clip rounds: flat; then trend with return_trend=True; then, with
+        return_fit=True, a dict with record (DECOR_DTYPE [n_curves, n_seg]), coef, mean and scale [n_curves, n_seg, m],
+        coefficients (coef / scale: in the units of the raw columns, 0.0 for a column that is not in the fit) and segments.
+        ValueError for what decorrelate_arguments refuses."""
+        a = decorrelate_arguments(y, own, shared, dy, mask, segments, ridge, n_iter, sigma_upper, sigma_lower)
+        n_c, n = a["y"].shape
+        n_shared, n_own = a["shared"].shape[0], a["own"].shape[1]
+        m, S = n_shared + n_own, len(a["segments"]) - 1
+        flat = numpy.empty_like(a["y"])
+        trend = numpy.empty_like(a["y"]) if return_trend else None
+        record = numpy.zeros((n_c, S), dtype=DECOR_DTYPE)
+        coef, mean, scale = (numpy.zeros((n_c, S, m)) if return_fit else None for _ in range(3))
+        assert DECOR_DTYPE.itemsize == ctypes.sizeof(DecorFit)
+        u8p = ctypes.POINTER(ctypes.c_uint8)
+        self._check(self._lib.tls_decorrelate(
+            self._h, _dp(a["y"]), None if a["dy"] is None else _dp(a["dy"]),
+            None if a["mask"] is None else a["mask"].ctypes.data_as(u8p), n, n_c, _dp(a["shared"]) if n_shared else None, n_shared,
+            _dp(a["own"]) if n_own else None, n_own, _ip(a["segments"]), S, a["ridge"], a["n_iter"], a["sigma_upper"],
+            a["sigma_lower"], _dp(flat), None if trend is None else _dp(trend), record.ctypes.data_as(ctypes.c_void_p),
+            None if coef is None else _dp(coef), None if mean is None else _dp(mean), None if scale is None else _dp(scale)))
+        if a["single"]:
+            flat, trend = flat[0], None if trend is None else trend[0]
+        out = (flat,) + ((trend,) if return_trend else ())
+        if return_fit:
+            with numpy.errstate(all="ignore"):
+                raw = numpy.where(coef != 0.0, coef / scale, 0.0)
+            out += ({"record": record, "coef": coef, "mean": mean, "scale": scale, "coefficients": raw,
+                     "segments": a["segments"]},)
         return out[0] if len(out) == 1 else out
 
     def debug_null_words(self, n, n_rows, seed, first_trial=0, block=None):

@@ -296,6 +296,7 @@ struct tls_ctx {
     DevBuf<double> d_match{pool, "d_match", kScratch};        // tls_ephemeris_match
     DevBuf<double> d_noise{pool, "d_noise", kScratch};        // tls_noise_profile
     DevBuf<double> d_aliases{pool, "d_aliases", kScratch};    // tls_event_periods
+    DevBuf<double> d_decor{pool, "d_decor", kScratch};        // tls_decorrelate
     // two-role slab path (series in HBM, one light curve; SearchPlan::split)
     View<unsigned int> d_tile_prefix;        // [n_periods + 1] tiles in front of work item w (queue order)
     DevBuf<double> d_partials{pool, "d_partials", kScratch};  // [split_max_items][3] a tile's winner
@@ -5086,6 +5087,98 @@ int tls_noise_profile(tls_ctx* ctx, const double* t, const double* y, int64_t n,
         TLS_HIP(ctx, hipMemcpyAsync(out_robust + (size_t)k0 * W, d_robust, rows * W * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
         TLS_HIP(ctx, hipMemcpyAsync(out_rms + (size_t)k0 * W, d_rms, rows * W * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
         TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));       // (the next slab overwrites the device buffers; w32 lives until here)
+    }
+    return TLS_OK;
+}
+
+// ---- decorrelation (tls_decorrelate.hip.h, DESIGN.md "Decorrelation"): one workgroup a (curve, segment); the shared columns
+// and the segment bounds go up once a call, the rows slab by slab
+static_assert(sizeof(tls_decor_fit) == tlsdev::kDecorWords * 8, "tls_decor_fit is the kernel's record");
+static_assert(TLS_DECOR_MAX_TERMS == tlsdev::kDecorMaxTerms && TLS_DECOR_MAX_ITER == tlsdev::kDecorMaxIter &&
+              TLS_DECOR_LDS_POINTS == tlsdev::kDecorLdsPoints, "the header's limits");
+
+int tls_decorrelate(tls_ctx* ctx, const double* y, const double* dy, const uint8_t* mask, int64_t n, int64_t n_curves,
+                    const double* shared, int64_t n_shared, const double* own, int64_t n_own, const int64_t* segments,
+                    int64_t n_segments, double ridge, int64_t n_iter, double sigma_upper, double sigma_lower, double* out_flat,
+                    double* out_trend, tls_decor_fit* out_fit, double* out_coef, double* out_mean, double* out_scale) {
+    if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
+    if (n < 1 || n > 100000000) return fail(ctx, TLS_E_ARG, "decorrelation: n out of range [1, 1e8]");
+    if (n_curves < 0) return fail(ctx, TLS_E_ARG, "decorrelation: n_curves < 0");
+    if (n_shared < 0 || n_own < 0 || n_shared + n_own < 1 || n_shared > TLS_DECOR_MAX_TERMS || n_own > TLS_DECOR_MAX_TERMS ||
+        n_shared + n_own > TLS_DECOR_MAX_TERMS)
+        return fail(ctx, TLS_E_ARG, "decorrelation: n_shared + n_own out of range [1, 16]");
+    if (n_segments < 1 || n_segments > n) return fail(ctx, TLS_E_ARG, "decorrelation: n_segments out of range [1, n]");
+    if (!segments) return fail(ctx, TLS_E_ARG, "null argument");
+    for (int64_t s = 0; s <= n_segments; ++s)
+        if ((s == 0 && segments[0] != 0) || (s > 0 && segments[s] <= segments[s - 1]) || (s == n_segments && segments[s] != n))
+            return fail(ctx, TLS_E_ARG, "decorrelation: segments must ascend strictly from 0 to n");
+    if (!(std::isfinite(ridge) && ridge >= 0.0)) return fail(ctx, TLS_E_ARG, "decorrelation: ridge must be finite and >= 0");
+    if (n_iter < 0 || n_iter > TLS_DECOR_MAX_ITER) return fail(ctx, TLS_E_ARG, "decorrelation: n_iter out of range [0, 16]");
+    if (!(sigma_upper > 0.0) || !(sigma_lower > 0.0)) return fail(ctx, TLS_E_ARG, "decorrelation: the sigmas must be > 0");
+    if (n_curves == 0) return TLS_OK;
+    if (!y || !out_flat || !out_fit || (n_shared && !shared) || (n_own && !own)) return fail(ctx, TLS_E_ARG, "null argument");
+    const size_t nn = (size_t)n, m = (size_t)(n_shared + n_own), S = (size_t)n_segments;
+    if ((uint64_t)n_curves > (uint64_t)(SIZE_MAX / 8) / ((uint64_t)n * (uint64_t)(n_own + 1)))
+        return fail(ctx, TLS_E_ARG, "decorrelation: rows too large");
+    for (size_t q = 0; q < (size_t)n_curves * nn; ++q) {
+        if (!(std::isfinite(y[q]) && y[q] > 0.0))
+            return fail(ctx, TLS_E_ARG, "decorrelation: row " + std::to_string(q / nn) + " has a non-finite or non-positive value");
+        if (dy && !(std::isfinite(dy[q]) && dy[q] > 0.0))
+            return fail(ctx, TLS_E_ARG, "decorrelation: dy of row " + std::to_string(q / nn) + " has a non-finite or non-positive value");
+    }
+    for (size_t q = 0; q < (size_t)n_shared * nn; ++q)
+        if (!std::isfinite(shared[q])) return fail(ctx, TLS_E_ARG, "decorrelation: shared has a non-finite value");
+    for (size_t q = 0; q < (size_t)n_curves * (size_t)n_own * nn; ++q)
+        if (!std::isfinite(own[q])) return fail(ctx, TLS_E_ARG, "decorrelation: own has a non-finite value");
+    TLS_HIP(ctx, hipSetDevice(ctx->device));
+    int64_t longest = 0;
+    for (int64_t s = 0; s < n_segments; ++s) longest = std::max(longest, segments[s + 1] - segments[s]);
+    const size_t member_words = longest > tlsdev::kDecorLdsPoints ? (size_t)((longest + 31) / 32) : 0;
+    // curves per launch: at most 256 MB of rows and columns, and the grid within 2^31 - 1 workgroups
+    const size_t row_bytes = nn * (8 * (3 + (dy ? 1 : 0) + (size_t)n_own) + (mask ? 1 : 0));
+    const int64_t slab = std::max<int64_t>(1, std::min<int64_t>({n_curves, (int64_t)((256u << 20) / row_bytes), (int64_t)(0x7fffffff / S)}));
+    const size_t B = (size_t)slab;
+    double *d_shared, *d_y, *d_dy, *d_own, *d_flat, *d_trend, *d_record, *d_coef, *d_mean, *d_scale;
+    long long* d_segments;
+    unsigned int* d_members;
+    unsigned char* d_mask;
+    Arena L;
+    L.add(d_shared, (size_t)n_shared * nn);  L.add(d_segments, S + 1);          // of the call
+    L.add(d_y, B * nn);                                                          // of one slab, from here on
+    L.add(d_dy, dy ? B * nn : 0);  L.add(d_own, B * (size_t)n_own * nn);  L.add(d_flat, B * nn);  L.add(d_trend, B * nn);
+    L.add(d_record, B * S * tlsdev::kDecorWords);  L.add(d_coef, B * S * m);  L.add(d_mean, B * S * m);  L.add(d_scale, B * S * m);
+    L.add(d_members, B * S * member_words);  L.add(d_mask, mask ? B * nn : 0);
+    TLS_HIP(ctx, L.bind(ctx->d_decor));
+    std::vector<long long> seg(S + 1);
+    for (size_t s = 0; s <= S; ++s) seg[s] = (long long)segments[s];
+    if (n_shared) TLS_HIP(ctx, hipMemcpyAsync(d_shared, shared, (size_t)n_shared * nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_segments, seg.data(), (S + 1) * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    tlsdev::DecorArgs a;
+    a.y = d_y; a.dy = d_dy; a.mask = d_mask; a.shared = d_shared; a.own = d_own; a.segments = d_segments;
+    a.flat = d_flat; a.trend = d_trend; a.record = d_record; a.coef = d_coef; a.mean = d_mean; a.scale = d_scale;
+    a.members = d_members; a.n = (long long)n; a.member_words = (long long)member_words;
+    a.ridge = ridge; a.sigma_upper = sigma_upper; a.sigma_lower = sigma_lower;
+    a.n_shared = (int)n_shared; a.n_own = (int)n_own; a.S = (int)n_segments; a.n_iter = (int)n_iter;
+    for (int64_t k0 = 0; k0 < n_curves; k0 += slab) {
+        const size_t rows = (size_t)std::min<int64_t>(slab, n_curves - k0), at = (size_t)k0;
+        TLS_HIP(ctx, hipMemcpyAsync(d_y, y + at * nn, rows * nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+        if (dy) TLS_HIP(ctx, hipMemcpyAsync(d_dy, dy + at * nn, rows * nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+        if (mask) TLS_HIP(ctx, hipMemcpyAsync(d_mask, mask + at * nn, rows * nn, hipMemcpyHostToDevice, main_stream(ctx)));
+        if (n_own) TLS_HIP(ctx, hipMemcpyAsync(d_own, own + at * (size_t)n_own * nn, rows * (size_t)n_own * nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+        hipLaunchKernelGGL(tlsdev::tls_decorrelate_kernel, dim3((unsigned)(rows * S)), dim3(tlsdev::kDecorThreads), 0, main_stream(ctx), a);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(main_stream(ctx));
+            return fail(ctx, TLS_E_HIP, std::string("decorrelation launch: ") + hipGetErrorString(e));
+        }
+        ctx->last_kernel = "tls_decorrelate";
+        TLS_HIP(ctx, hipMemcpyAsync(out_flat + at * nn, d_flat, rows * nn * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+        if (out_trend) TLS_HIP(ctx, hipMemcpyAsync(out_trend + at * nn, d_trend, rows * nn * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+        TLS_HIP(ctx, hipMemcpyAsync(out_fit + at * S, d_record, rows * S * tlsdev::kDecorWords * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+        if (out_coef) TLS_HIP(ctx, hipMemcpyAsync(out_coef + at * S * m, d_coef, rows * S * m * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+        if (out_mean) TLS_HIP(ctx, hipMemcpyAsync(out_mean + at * S * m, d_mean, rows * S * m * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+        if (out_scale) TLS_HIP(ctx, hipMemcpyAsync(out_scale + at * S * m, d_scale, rows * S * m * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+        TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));       // (the next slab overwrites the device buffers; seg lives until here)
     }
     return TLS_OK;
 }

@@ -4461,5 +4461,7 @@ __global__ void __launch_bounds__(512) tls_transit_models(const ModelsArgs a) {
 #include "tls_match.hip.h"
 // survey-mode per-star noise profile (tls_noise_profile)
 #include "tls_noise.hip.h"
+// survey-mode regression detrending against shared and per-curve series (tls_decorrelate)
+#include "tls_decorrelate.hip.h"
 
 }  // namespace tlsdev

@@ -431,15 +431,132 @@ def prewhiten_batch(t, flux_batch, n_terms=3, harmonics=1, min_power=None, frequ
     return res[0] if len(res) == 1 else res
 
 
+# ---- detrending: regression against centroids and basis vectors on the device -----------------------------------------------
+class Decorrelate(collections.namedtuple("Decorrelate", ("own", "shared", "segments", "ridge", "n_iter", "sigma_upper",
+                                                         "sigma_lower"))):
+    """detrend=Decorrelate(own=None, shared=None, segments=None, ridge=0.0, n_iter=3, sigma_upper=5.0, sigma_lower=5.0) on
+    the survey calls: every row regressed on its own columns own [n_curves, n_own, n] (centroid_regressors) and on the shared
+    columns shared [n_shared, n] (basis vectors) and divided by the fit (decorrelate_batch), weighted with dy_batch where one
+    is given and with detrend_mask as its mask.  An immutable value; its fields are checked where it is used."""
+    __slots__ = ()
+
+    def __new__(cls, own=None, shared=None, segments=None, ridge=0.0, n_iter=3, sigma_upper=5.0, sigma_lower=5.0):
+        return super(Decorrelate, cls).__new__(cls, own, shared, segments, ridge, n_iter, sigma_upper, sigma_lower)
+
+
+def decorrelate_fields():
+    """The fields of a decorrelation record, in order (tls_decor_fit of include/tls_amd.h): what
+    decorrelate_batch(..., return_fit=True) returns as `record` for every (curve, segment)."""
+    from ._lib import DECOR_FIELDS
+    return DECOR_FIELDS
+
+
+def centroid_regressors(cx_batch, cy_batch, order=2):
+    """The columns a centroid regression takes as `own`: [n_curves, n_terms, n] (one row [n]: [n_terms, n]) monomials
+    x^a y^b with 1 <= a + b <= order of x = cx - median(cx) and y = cy - median(cy), each row's own medians.  The terms run
+    by total degree, and within a degree from the highest power of x down: x, y | x^2, x y, y^2 | x^3, x^2 y, x y^2, y^3;
+    order (1, 2 or 3) gives 2, 5 or 9 of them.  ValueError unless cx_batch and cy_batch are finite and of one shape [n] or
+    [n_curves, n].  Host only."""
+    order = _checks.integer("centroid regressors", "order", order, 1, 3)
+    try:
+        cx, cy = numpy.asarray(cx_batch, dtype=numpy.float64), numpy.asarray(cy_batch, dtype=numpy.float64)
+    except (TypeError, ValueError):
+        raise _checks.refusal("centroid regressors", "cx_batch and cy_batch must hold numbers")
+    if cx.ndim not in (1, 2) or cx.shape != cy.shape or cx.shape[-1] < 1:
+        raise _checks.refusal("centroid regressors", "cx_batch and cy_batch must share one shape [n] or [n_curves, n], got %s "
+                              "and %s" % (cx.shape, cy.shape))
+    if not (numpy.all(numpy.isfinite(cx)) and numpy.all(numpy.isfinite(cy))):
+        raise _checks.refusal("centroid regressors", "cx_batch and cy_batch must be finite")
+    x = cx - numpy.median(cx, axis=-1, keepdims=True)
+    y = cy - numpy.median(cy, axis=-1, keepdims=True)
+    terms = [x ** a * y ** (d - a) for d in range(1, order + 1) for a in range(d, -1, -1)]
+    return numpy.ascontiguousarray(numpy.stack(terms, axis=-2))
+
+
+def decorrelate_segments(t, break_tolerance=0.5, window_length=None):
+    """The index boundaries decorrelate_batch takes as `segments` (int64, from 0 to len(t)): a new segment starts behind every
+    gap t[i] - t[i - 1] > break_tolerance; with a window_length every segment of span D = t[last] - t[first] is further cut
+    into k = ceil(D / window_length) parts of equal duration D / k (part i starts at the first stamp >= t[first] + i D / k;
+    a part without a stamp is left out).  ValueError unless t is [n], n >= 1, finite and non-decreasing, break_tolerance is
+    a number > 0 and window_length is None or finite and > 0.  Host only."""
+    what = "decorrelation segments"
+    t = _checks.times(what, t, _checks.MAX_ROW_POINTS)
+    _checks.positive(what, "break_tolerance", break_tolerance)
+    if window_length is not None:
+        window_length = _checks.finite_positive(what, "window_length", window_length, "must be None or finite and > 0")
+    n = len(t)
+    starts = numpy.concatenate([[0], 1 + numpy.flatnonzero(t[1:] - t[:-1] > break_tolerance), [n]])
+    edges = []
+    for a, b in zip(starts[:-1], starts[1:]):
+        edges.append(int(a))
+        span = t[b - 1] - t[a]
+        if window_length is not None and span > window_length:
+            k = int(numpy.ceil(span / window_length))
+            cuts = a + numpy.searchsorted(t[a:b], t[a] + numpy.arange(1, k) * (span / k), side="left")
+            edges.extend(int(c) for c in cuts)
+    return numpy.unique(numpy.array(edges + [n], dtype=numpy.int64))
+
+
+def decorrelate_batch(flux_batch, own=None, shared=None, dy_batch=None, mask=None, segments=None, ridge=0.0, n_iter=3,
+                      sigma_upper=5.0, sigma_lower=5.0, return_trend=False, return_fit=False, context=None, device=None,
+                      devices=None):
+    """flat = flux / trend for every row of flux_batch [n_curves, n] (one row [n] is accepted, with own [n_own, n]), with
+    trend a weighted, robust linear least-squares fit of the row against series that are KNOWN to drive its systematics
+    (tls_decorrelate): the regression of K2SFF, K2SC and EVEREST on the centroids, and of the Kepler / TESS pipelines on
+    their cotrending basis vectors.  The K2 roll moves the photocentre over the pixel sensitivity in a six-hour sawtooth as
+    long as a transit, with a shape of its own for every star: no per-row window (detrend_batch, biweight_batch) can follow
+    it without flattening the transit and no rank-1 term (sysrem_batch) describes it; a polynomial in the centroids does.
+
+    The columns of a row are shared [n_shared, n] (every row takes them: basis vectors, or the profiles
+    sysrem_batch(return_components=True) returned for another ensemble) and then its own, own [n_curves, n_own, n]
+    (centroid_regressors); at least one of the two, and n_shared + n_own in [1, DECOR_MAX_TERMS = 16].  The mean is always
+    free.  segments (decorrelate_segments; None: one segment) are index boundaries from 0 to n shared by all rows: every
+    (row, segment) is fitted on its own.  The fit: z = flux / mu - 1 against the standardised columns by the normal equations
+    (ridge * sum(w) added to the diagonal) and a Cholesky factorisation that drops a constant column and one collinear with
+    those before it (pivot <= DECOR_PIVOT = 1e-10 of its diagonal entry); then up to n_iter (in [0, DECOR_MAX_ITER = 16])
+    rounds in which the points with a residual above sigma_upper or below -sigma_lower weighted rms leave the fit and it is
+    repeated (inf switches a side off).  dy_batch gives the weights 1 / dy^2 (None: 1).  mask ([n_curves, n] uint8 or bool,
+    != 0: protected; transit_mask) keeps points out of the fit; trend and flat cover EVERY point, protected and clipped ones
+    included, and a mask of zeros changes no bit.  The exact steps are in include/tls_amd.h and tests/decorrelate_spec.py;
+    each is one IEEE double operation and every sum runs left to right, so the result equals the Python statement bit for bit.
+    The arguments are checked before any device work (ValueError).
+
+    devices=[...] deals the rows out, with their own, dy and mask rows beside them; every device gets shared.  Returns
+    flat[, trend][, fit]: fit is a dict with `record` ([n_curves, n_seg] of decorrelate_fields(): status 0 fitted, 1 too few
+    points (trend = mu), 2 the trend left (0, inf) (trend = mu); dropped, a bit a dropped column; n_fit, n_clipped, rounds, mu,
+    sigma, n_live), `coef`, `mean` and `scale` [n_curves, n_seg, m] of the standardised columns, `coefficients` = coef / scale
+    in the units of the raw columns, and `segments`."""
+    from ._lib import decorrelate_arguments
+    a = decorrelate_arguments(flux_batch, own, shared, dy_batch, mask, segments, ridge, n_iter, sigma_upper, sigma_lower)
+
+    def call(ctx, lo, hi):
+        flat, trend, fit = ctx.decorrelate(
+            a["y"][lo:hi], a["own"][lo:hi] if a["own"].shape[1] else None, a["shared"] if len(a["shared"]) else None,
+            None if a["dy"] is None else a["dy"][lo:hi], None if a["mask"] is None else a["mask"][lo:hi], a["segments"],
+            a["ridge"], a["n_iter"], a["sigma_upper"], a["sigma_lower"], return_trend=True, return_fit=True)
+        del fit["segments"]
+        return dict(flat=flat, trend=trend, **fit)
+
+    out = _run_batch(devices, device, context, len(a["y"]), call)
+    flat, trend = out["flat"], out["trend"]
+    fit = {k: out[k] for k in ("record", "coef", "mean", "scale", "coefficients")}
+    fit["segments"] = a["segments"]
+    if a["single"]:
+        flat, trend = flat[0], trend[0]
+        fit = {k: (v if k == "segments" else v[0]) for k, v in fit.items()}
+    res = (flat,) + ((trend,) if return_trend else ()) + ((fit,) if return_fit else ())
+    return res[0] if len(res) == 1 else res
+
+
 def _detrend_steps(detrend):
     """The steps of a detrend= argument, left to right: () for None, the one step of an int, a Biweight, a SysRem or a
-    Prewhiten, and the elements of a tuple or list of those."""
+    Prewhiten or a Decorrelate, and the elements of a tuple or list of those."""
     if detrend is None:
         return ()
-    if isinstance(detrend, (Biweight, SysRem, Prewhiten)) or not isinstance(detrend, (tuple, list)):
+    if isinstance(detrend, (Biweight, SysRem, Prewhiten, Decorrelate)) or not isinstance(detrend, (tuple, list)):
         return (detrend,)
     for step in detrend:
-        if step is None or (isinstance(step, (tuple, list)) and not isinstance(step, (Biweight, SysRem, Prewhiten))):
+        if step is None or (isinstance(step, (tuple, list)) and not isinstance(step, (Biweight, SysRem, Prewhiten, Decorrelate))):
             raise ValueError("a step of detrend must be a kernel size, a Biweight or a SysRem, got %r" % (step,))
     return tuple(detrend)
 
@@ -449,6 +566,25 @@ def _no_ensemble_step(detrend, caller):
     if any(isinstance(step, SysRem) for step in _detrend_steps(detrend)):
         raise ValueError("%s forms its rows from ONE star, so a fit across the rows is meaningless there: detrend=SysRem "
                          "belongs on search_batch, power_batch and power_results" % caller)
+
+
+def _no_regression_step(detrend, caller):
+    """ValueError for a Decorrelate among the steps of detrend, in the calls that form their rows on the device from ONE
+    star: a step's own columns belong to the rows of a batch the caller holds."""
+    if any(isinstance(step, Decorrelate) for step in _detrend_steps(detrend)):
+        raise ValueError("%s forms its rows on the device from ONE star and has no columns for them: detrend=Decorrelate "
+                         "belongs on search_batch, power_batch, power_results and lomb_scargle; decorrelate the star's flux "
+                         "with decorrelate_batch first" % caller)
+
+
+def _detrend_of_rows(detrend, rows):
+    """detrend as the curves `rows` (an index array) of the batch it was written for take it: every Decorrelate with the own
+    columns of those curves, every other step as it is."""
+    if not any(isinstance(step, Decorrelate) and step.own is not None for step in _detrend_steps(detrend)):
+        return detrend
+    steps = tuple(step._replace(own=numpy.asarray(step.own)[rows]) if isinstance(step, Decorrelate) and step.own is not None
+                  else step for step in _detrend_steps(detrend))
+    return steps[0] if isinstance(detrend, Decorrelate) else steps
 
 
 def _first_context(context, device, devices, n_curves):
@@ -464,8 +600,9 @@ def _detrended(t, flux_batch, detrend, context, device, devices, dy_batch=None, 
     """flux_batch as it is (detrend None), or taken through the steps of detrend left to right on the call's devices for
     [n_curves, len(t)]: biweight_batch for a Biweight, the whole batch through SysRem on the first device (weighted with
     dy_batch where one is given) for a SysRem, prewhiten_batch (on variability_frequencies(t) cut to the step's range, weighted
-    with dy_batch where one is given) for a Prewhiten, detrend_batch(flux_batch, step) otherwise.  detrend_mask ([n_curves,
-    len(t)], uint8 or bool) goes to every Biweight and Prewhiten step as its mask; a SysRem step runs unmasked, a median-filter
+    with dy_batch where one is given) for a Prewhiten, decorrelate_batch (weighted with dy_batch where one is given) for a
+    Decorrelate, detrend_batch(flux_batch, step) otherwise.  detrend_mask ([n_curves, len(t)], uint8 or bool) goes to every
+    Biweight, Prewhiten and Decorrelate step as its mask; a SysRem step runs unmasked, a median-filter
     step with a mask is a ValueError (before any step runs)."""
     steps = _detrend_steps(detrend)
     if detrend_mask is not None:
@@ -474,7 +611,7 @@ def _detrended(t, flux_batch, detrend, context, device, devices, dy_batch=None, 
             raise ValueError("flux_batch must have shape [n_curves, len(t)]")
         detrend_mask = detrend_mask_rows(detrend_mask, numpy.shape(flux_batch), "detrend_mask")
         for step in steps:
-            if not isinstance(step, (Biweight, SysRem, Prewhiten)):
+            if not isinstance(step, (Biweight, SysRem, Prewhiten, Decorrelate)):
                 raise ValueError("detrend_mask: the median filter (detrend=%r) is defined by its sample count and zero padding "
                                  "and has no masked form; use Biweight or Prewhiten steps with a mask" % (step,))
     if not steps:
@@ -495,6 +632,10 @@ def _detrended(t, flux_batch, detrend, context, device, devices, dy_batch=None, 
             grid, k, h, low = _prewhiten_step(t, step, len(t))
             flux_batch = prewhiten_batch(t, flux_batch, k, h, low, frequencies=grid, dy_batch=dy_batch, context=context,
                                          device=device, devices=devices, mask=detrend_mask)
+        elif isinstance(step, Decorrelate):
+            flux_batch = decorrelate_batch(flux_batch, step.own, step.shared, dy_batch, detrend_mask, step.segments, step.ridge,
+                                           step.n_iter, step.sigma_upper, step.sigma_lower, context=context, device=device,
+                                           devices=devices)
         else:
             flux_batch = detrend_batch(flux_batch, step, context=context, device=device, devices=devices)
     return flux_batch
@@ -1097,7 +1238,7 @@ def power_batch_protected(t, flux_batch, detrend, sde_min, factor=1.5, n_peaks=1
     if "detrend_mask" in power_batch_kwargs:
         raise ValueError("power_batch_protected forms detrend_mask itself")
     for step in _detrend_steps(detrend):
-        if not isinstance(step, (Biweight, SysRem, Prewhiten)):
+        if not isinstance(step, (Biweight, SysRem, Prewhiten, Decorrelate)):
             raise ValueError("power_batch_protected: the median filter (detrend=%r) has no masked form; use Biweight or "
                              "Prewhiten steps" % (step,))
     _peaks_request(n_peaks, power_batch_kwargs.get("peak_separation", 0.02), power_batch_kwargs.get("peak_ratios", HARMONICS),
@@ -1250,7 +1391,7 @@ def power_batch_multi(t, flux_batch, sde_min, n_planets=3, detrend=None, protect
     if protect_factor is not None:
         _checks.finite_positive("power_batch_multi", "protect_factor", protect_factor, "must be None or finite and > 0")
         for step in _detrend_steps(detrend):
-            if not isinstance(step, (Biweight, SysRem, Prewhiten)):
+            if not isinstance(step, (Biweight, SysRem, Prewhiten, Decorrelate)):
                 raise ValueError("power_batch_multi: the median filter (detrend=%r) has no masked form; use Biweight or "
                                  "Prewhiten steps with protect_factor" % (step,))
     if transit_fit is None or transit_fit is False:
@@ -1291,8 +1432,9 @@ def power_batch_multi(t, flux_batch, sde_min, n_planets=3, detrend=None, protect
             rows = remove_transits(t, rows, found, **removal)
             if protect_factor is not None:
                 mask = _first_mask(t, found, len(active), j, protect_factor, where)
-        out = power_batch(t, rows, dy_batch=None if dy_batch is None else dy_batch[active], detrend=detrend, detrend_mask=mask,
-                          peaks=1, peak_fits=True, transit_fit=fit_options, **dict(rest, **search))
+        out = power_batch(t, rows, dy_batch=None if dy_batch is None else dy_batch[active],
+                          detrend=_detrend_of_rows(detrend, active), detrend_mask=mask, peaks=1, peak_fits=True,
+                          transit_fit=fit_options, **dict(rest, **search))
         summary, peaks = out[0], out[-1]["peaks"][:, 0]
         if planets is None:
             planets = numpy.zeros((n_curves, n_planets), dtype=multi_planet_fields(summary.dtype, peaks.dtype))
@@ -3331,7 +3473,8 @@ def injection_recovery(t, flux, injections, dy=None, inject_u=None, inject_limb_
     the filter the data pass through, and completeness counts what the filter absorbs.  rows are then the detrended rows;
     n_in_transit and the classification are unchanged, and dy is passed through as it is.  detrend=Biweight(window_length,
     break_tolerance) does the same with the time-windowed biweight (tls_biweight_detrend, biweight_batch), and a tuple of
-    such steps applies them left to right.  A SysRem raises ValueError: the rows all come from ONE star.
+    such steps applies them left to right.  A SysRem raises ValueError: the rows all come from ONE star; so does a Decorrelate, whose
+    columns belong to rows the caller holds (decorrelate the star's flux with decorrelate_batch first).
 
     Returns (recovery, summary[, rows]): recovery a structured array -- the injected fields, T14, n_in_transit (points
     with z < 1 + rp_rs: 0 where every transit falls into a gap), period_match, epoch_offset, recovered -- and summary
@@ -3357,6 +3500,7 @@ def injection_recovery(t, flux, injections, dy=None, inject_u=None, inject_limb_
     classify_recovery(table[:0], numpy.zeros(0, dtype=[("period", "f8"), ("T0", "f8"), ("SDE", "f8"), ("no_fit", "i8")]),
                       None, sde_threshold, period_tolerance, aliases, epoch_tolerance)
     _no_ensemble_step(detrend, "injection_recovery")
+    _no_regression_step(detrend, "injection_recovery")
     for step in _detrend_steps(detrend):
         if isinstance(step, Biweight):
             from ._lib import biweight_arguments
@@ -3507,7 +3651,8 @@ def null_sde(t, n_trials, sigma=None, source=None, block=None, seed=0, first_tri
     source rows, filtered after resampling as the data are.  A row still depends on (seed, R) alone; rows are then the
     detrended rows, and dy is passed through as it is.  detrend=Biweight(window_length, break_tolerance) does the same with
     the time-windowed biweight (tls_biweight_detrend, biweight_batch), and a tuple of such steps applies them left to
-    right.  A SysRem raises ValueError: the rows all come from ONE star.
+    right.  A SysRem raises ValueError: the rows all come from ONE star; so does a Decorrelate, whose
+    columns belong to rows the caller holds (decorrelate the star's flux with decorrelate_batch first).
 
     Returns summary, or (summary, rows [n_trials, n]) with return_rows=True."""
     t, mode, sigma, source, block, seed, first_trial = _null_arguments(t, n_trials, sigma, source, block, seed, first_trial)
@@ -3522,6 +3667,7 @@ def null_sde(t, n_trials, sigma=None, source=None, block=None, seed=0, first_tri
     if statistics and not numpy.all(t[1:] >= t[:-1]):
         raise ValueError("statistics=True needs ascending time stamps t")
     _no_ensemble_step(detrend, "null_sde")
+    _no_regression_step(detrend, "null_sde")
     for step in _detrend_steps(detrend):
         if isinstance(step, Biweight):
             from ._lib import biweight_windows
