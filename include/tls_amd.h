@@ -42,7 +42,7 @@ extern "C" {
  * (7: tls_shape_fit), (7: tls_nudft, tls_lomb_scargle, tls_sine_test); 8: every entry that takes `root, n_root` takes a
  * second table, `root, root_count, n_root`), (8: tls_ephemeris_match), (8: tls_folded_views),
  * (8: tls_event_vetting), (8: tls_centroid_test), (8: tls_noise_profile), (8: tls_transit_fit), (8: tls_remove_transits),
- * (8: tls_event_periods), (8: tls_decorrelate). */
+ * (8: tls_event_periods), (8: tls_decorrelate), (8: tls_spline_detrend). */
 #define TLS_AMD_ABI_VERSION 8
 
 #define TLS_OK 0
@@ -1339,6 +1339,83 @@ int tls_decorrelate(tls_ctx *ctx, const double *y, const double *dy, const uint8
                     const double *shared, int64_t n_shared, const double *own, int64_t n_own, const int64_t *segments,
                     int64_t n_segments, double ridge, int64_t n_iter, double sigma_upper, double sigma_lower, double *out_flat,
                     double *out_trend, tls_decor_fit *out_fit, double *out_coef, double *out_mean, double *out_scale);
+
+/* ---- survey mode: robust B-spline detrending with a BIC-chosen knot spacing ------------------------------------------------ */
+/* Penalised least squares on a uniform cubic B-spline in every gap-free segment of the shared time stamps t [n] (finite,
+ * non-decreasing), with iterative sigma clipping of the residuals and, where several knot spacings are given, the spacing of
+ * the least Bayesian information criterion for every curve: the "Kepler spline" of Vanderburg & Johnson (2014).  y [n_rows][n];
+ * dy (or NULL) gives w = 1.0 / (dy * dy), else w = 1.0; mask (or NULL) [n_rows][n], != 0: protected, never a member of a fit.
+ * A new segment starts behind every gap t[j] - t[j-1] > break_tolerance.  A (curve, segment, spacing) with the points a .. b,
+ * L of them, T = t[b] - t[a]:
+ *   knots   T == 0: q = 0, m = 0, status 1.  Else q = max(1, ceil(T / spacing)), h = T / q, m = q + 3 coefficients.
+ *   place   x = (t[i] - t[a]) / h;  j = min(int(x), q - 1);  u = x - j            (the last point: u = 1 in the last interval)
+ *   basis   u2 = u * u;  u3 = u2 * u;  o = 1.0 - u;  o2 = o * o;  o3 = o2 * o
+ *           b0 = o3 / 6.0;  b1 = ((3.0 * u3 - 6.0 * u2) + 4.0) / 6.0;  b2 = (((-(3.0 * u3) + 3.0 * u2) + 3.0 * u) + 1.0) / 6.0
+ *           b3 = u3 / 6.0;  point i touches the coefficients j .. j + 3
+ *   F       the members: at first the unprotected points;  rounds = dropped = 0;  sigma = NaN
+ *   fit:    nF = |F|;  nF == 0, or the last member's time stamp is not > the first one's: status 1, leave the loop
+ *      A    W = sum_F w in index order from +0.0
+ *           interval j, its members (a contiguous index range, t ascends) in ascending index, every sum from +0.0:
+ *               wb_k = w * b_k;  S_j[k][l] += wb_k * b_l  (k <= l, ten sums);  R_j[k] += wb_k * y  (four)
+ *           A[c][c + d] (d = 0 .. 3, c + d < m) = 0.0 + the S_j[c - j][c + d - j] of j = max(0, c + d - 3) .. min(c, q - 1), ascending
+ *           g[c] = 0.0 + the R_j[c - j] of j = max(0, c - 3) .. min(c, q - 1), ascending
+ *           pw = W / q;  lam = penalty * pw;  A[c][c + d] = A[c][c + d] + lam * P[c][c + d], d = 0 .. 2, P = D2^T D2 of the
+ *           second differences of the m coefficients (whole numbers): positive definite with penalty > 0 as soon as F holds two
+ *           distinct time stamps, whatever intervals are empty
+ *      B    Cholesky inside the band, j ascending:  s = A[j][j];  for k = max(0, j - 3) .. j - 1:  s = s - L[j][k] * L[j][k]
+ *               not (s > TLS_SPLINE_PIVOT * A[j][j]): status 2, leave the loop;  L[j][j] = sqrt(s)
+ *               for i = j + 1 .. min(j + 3, m - 1):  v = A[j][i];  for k = max(0, i - 3) .. j - 1:  v = v - L[i][k] * L[j][k]
+ *                   L[i][j] = v / L[j][j]
+ *           forward, j ascending:  s = g[j];  for k = max(0, j - 3) .. j - 1:  s = s - L[j][k] * z[k];  z[j] = s / L[j][j]
+ *           back, j descending:    s = z[j];  for k = j + 1 .. min(j + 3, m - 1):  s = s - L[k][j] * c[k];  c[j] = s / L[j][j]
+ *      C    trend at EVERY point:  p = c[j] * b0;  p = p + c[j+1] * b1;  p = p + c[j+2] * b2;  p = p + c[j+3] * b3
+ *           a value not in (0, inf): status 2, leave the loop;  else status 0
+ *   clip    rounds == n_iter: leave.  r = y - trend over F;  med = median(r);  sigma = 1.4826 * median(|r - med|), the median
+ *           of an even count being (lower + upper) / 2;  sigma == 0: leave
+ *           up = sigma_upper * sigma;  down = -(sigma_lower * sigma);  out: the members with r > up or r < down
+ *           rounds = rounds + 1;  nobody out: leave;  nF - |out| < 2: leave, the round is not applied
+ *           F = F without out;  dropped = dropped + |out|;  fit again
+ *   status 1, 2:  trend = (sum w * y) / (sum w) over F in index order, over all the points of the segment where F is empty
+ *   flat = y / trend at every point;  weight = sum_F w (0.0: no member);  r = y - trend;  ssr = sum_F (w * r) * r
+ * The choice, for every curve (one spacing: the same record, choice 0):
+ *   d = y[i+1] - y[i] of the neighbours of one segment that are both unprotected; none: sigma_pp = NaN
+ *   sigma_pp = (1.4826 * median(|d - median(d)|)) / sqrt(2)
+ *   spacing s over its segments of status 0, in order, from 0:  K = sum coefficients;  N = sum kept;  Q = sum ssr;  V = sum weight
+ *   bic[s] = K * log(N) + (Q / (V / N)) / (sigma_pp * sigma_pp);  the first index of the least finite one wins
+ *   sigma_pp not > 0, or no bic finite: the first spacing, flag = 1
+ * Every step but log is one IEEE double operation without contraction, so flat, trend and the segment records equal the Python
+ * statement in tests/spline_spec.py bit for bit, and bic within the ulp of log.  One spacing gives the bits of that spacing in
+ * a list in which it wins; a mask of zeros gives the bits of a call without one. */
+#define TLS_SPLINE_MAX_SPACINGS 16
+#define TLS_SPLINE_MAX_ITER 16
+#define TLS_SPLINE_MAX_COEF 512      /* the most coefficients of one segment: the band the LDS holds */
+#define TLS_SPLINE_LDS_POINTS 5120   /* a call whose longest segment has at most this many points keeps the segment in the LDS */
+#define TLS_SPLINE_PIVOT 1e-10
+typedef struct tls_spline_segment {
+    double status;                 /* 0 fitted; 1 fewer than two members with distinct time stamps; 2 a pivot failed or the
+                                      trend left (0, inf): for 1 and 2 the trend is the weighted mean */
+    double intervals, coefficients;/* q and m (0: T == 0) */
+    double points, kept;           /* L, and |F| at the end */
+    double rounds, dropped;        /* clip rounds run, points they removed */
+    double sigma;                  /* of the last round (NaN: none) */
+    double ssr, weight;            /* sum_F (w r) r, sum_F w */
+} tls_spline_segment;
+typedef struct tls_spline_curve {
+    double choice;                 /* index of the chosen spacing */
+    double sigma_pp;
+    double flag;                   /* 1: no BIC could be formed, the first spacing was taken */
+    double bic[TLS_SPLINE_MAX_SPACINGS];   /* NaN behind n_spacings */
+} tls_spline_curve;
+/* out_flat, out_trend (may be NULL) [n_rows][n]; out_segment_records [n_rows][n_segments] for the segments of t in order;
+ * out_curve_records [n_rows].  Needs no plan and no search, and leaves a prepared plan as it is.  n_rows == 0 is a no-op.
+ * TLS_E_ARG, before any device work and with the outputs untouched, unless n is in [1, 1e8], t is finite and non-decreasing,
+ * n_spacings is in [1, TLS_SPLINE_MAX_SPACINGS] with every spacing finite and > 0, break_tolerance > 0 (inf allowed), penalty
+ * finite and >= 0, n_iter in [0, TLS_SPLINE_MAX_ITER], both sigmas > 0 (inf allowed, no NaN), y and dy finite and > 0, and no
+ * segment at any spacing has more than TLS_SPLINE_MAX_COEF coefficients. */
+int tls_spline_detrend(tls_ctx *ctx, const double *t, const double *y, const double *dy, const uint8_t *mask, int64_t n,
+                       int64_t n_rows, const double *spacings, int64_t n_spacings, double break_tolerance, double penalty,
+                       int64_t n_iter, double sigma_upper, double sigma_lower, double *out_flat, double *out_trend,
+                       tls_spline_segment *out_segment_records, tls_spline_curve *out_curve_records);
 
 /* The limb-darkened transit fit: the planet's size, impact parameter and T14 from the dip itself, with the exposure time in
  * the model.  A straight chord at constant speed crosses a limb-darkened disc: the separation is z^2 = b^2 + ((1 + k)^2 - b^2)

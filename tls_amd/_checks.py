@@ -285,3 +285,33 @@ def segments(what, values, n):
     if v.ndim != 1 or len(v) < 2 or v.dtype.kind not in "iu" or v[0] != 0 or v[-1] != n or not numpy.all(v[1:] > v[:-1]):
         raise refusal(what, "segments must hold integers ascending strictly from 0 to n = %d, got %r" % (n, values))
     return numpy.ascontiguousarray(v, dtype=numpy.int64)
+
+
+# ---- spline detrending -----------------------------------------------------------------------------------------------------
+def spacings(what, values, most):
+    """(values as contiguous float64 [k], single): one number or a sequence of 1 .. `most` numbers, each finite and > 0;
+    `single` says it was one number."""
+    single = numpy.ndim(values) == 0
+    try:
+        v = numpy.atleast_1d(numpy.asarray(values, dtype=numpy.float64))
+    except (TypeError, ValueError):
+        raise refusal(what, "knot_spacing must be a number or a sequence of numbers, got %r" % (values,))
+    if isinstance(values, (bool, numpy.bool_)) or v.ndim != 1 or not 1 <= len(v) <= most:
+        raise refusal(what, "knot_spacing must be a number or a sequence of 1 to %d numbers, got %r" % (most, values))
+    if not numpy.all(numpy.isfinite(v) & (v > 0.0)):
+        raise refusal(what, "every knot spacing must be finite and > 0, got %r" % (values,))
+    return numpy.ascontiguousarray(v), single
+
+
+def knot_segments(what, t, break_tolerance, spacing, max_coef):
+    """The index boundaries [n_seg + 1] (int64) of the segments of t, a new one behind every gap t[j] - t[j-1] >
+    break_tolerance; refuses a segment that takes more than max_coef coefficients at one of the spacings, q + 3 with
+    q = max(1, ceil(span / spacing))."""
+    starts = numpy.concatenate([[0], 1 + numpy.flatnonzero(t[1:] - t[:-1] > break_tolerance), [len(t)]]).astype(numpy.int64)
+    span = t[starts[1:] - 1] - t[starts[:-1]]
+    with numpy.errstate(all="ignore"):
+        most = numpy.maximum(1.0, numpy.ceil(span.max() / spacing.min())) + 3.0
+    if not most <= max_coef:
+        raise refusal(what, "a segment of %g d takes %g coefficients at a knot spacing of %g d, more than SPLINE_MAX_COEF = %d"
+                      % (span.max(), most, spacing.min(), max_coef))
+    return numpy.ascontiguousarray(starts)

@@ -116,6 +116,14 @@ DECOR_MAX_TERMS = 16
 DECOR_MAX_ITER = 16
 DECOR_PIVOT = 1e-10
 DECOR_LDS_POINTS = 32768
+# include/tls_amd.h TLS_SPLINE_*: the most knot spacings and clip rounds of tls_spline_detrend, the most coefficients of one
+# segment (the band the LDS holds), the points of the longest segment a call keeps in the LDS (a longer one runs on device
+# scratch), and the pivot below which the band counts as singular
+SPLINE_MAX_SPACINGS = 16
+SPLINE_MAX_ITER = 16
+SPLINE_MAX_COEF = 512
+SPLINE_LDS_POINTS = 5120
+SPLINE_PIVOT = 1e-10
 PEAKS_LDS_PERIODS = 1 << 20   # tls_peaks.hip.h kPeaksLdsPeriods: a longer grid keeps its alive mask in device memory, not in LDS
 
 # every symbol include/tls_amd.h declares (tests check the export list against the header)
@@ -132,7 +140,7 @@ SYMBOLS = (
     "tls_ephemeris_match", "tls_folded_views", "tls_event_vetting", "tls_centroid_test", "tls_noise_profile",
     "tls_transit_fit",
     "tls_transit_mask", "tls_biweight_detrend_masked", "tls_prewhiten_masked",
-    "tls_remove_transits", "tls_event_periods", "tls_decorrelate",
+    "tls_remove_transits", "tls_event_periods", "tls_decorrelate", "tls_spline_detrend",
     "tls_comm_unique_id", "tls_comm_init", "tls_comm_destroy", "tls_comm_info", "tls_comm_allgather_results", "tls_comm_allgather_device", "tls_comm_fetch_gathered",
     "tls_comm_stage_results", "tls_comm_allgather_staged", "tls_comm_fetch_staged",
     "tls_comm_barrier", "tls_comm_max",
@@ -1225,6 +1233,9 @@ def load():
     lib.tls_decorrelate.argtypes = [vp, _c_double_p, _c_double_p, u8p, i64, i64, _c_double_p, i64, _c_double_p, i64, _c_int64_p,
                                     i64, dbl, i64, dbl, dbl, _c_double_p, _c_double_p, ctypes.c_void_p, _c_double_p, _c_double_p,
                                     _c_double_p]
+    lib.tls_spline_detrend.restype = ci
+    lib.tls_spline_detrend.argtypes = [vp, _c_double_p, _c_double_p, _c_double_p, u8p, i64, i64, _c_double_p, i64, dbl, dbl, i64, dbl,
+                                       dbl, _c_double_p, _c_double_p, ctypes.c_void_p, ctypes.c_void_p]
     lib.tls_debug_peak_phase_scans.restype = ci
     lib.tls_debug_peak_phase_scans.argtypes = [vp, _c_double_p, i64, ctypes.c_void_p, _c_int64_p, i64, _c_double_p, _c_double_p,
                                                i64, dbl, _c_double_p, _c_double_p, i64, i64, ctypes.c_void_p, i64, i64,
@@ -1548,6 +1559,46 @@ def decorrelate_arguments(y, own=None, shared=None, dy=None, mask=None, segments
             "n_iter": _checks.integer(what, "n_iter", n_iter, 0, DECOR_MAX_ITER),
             "sigma_upper": _checks.positive(what, "sigma_upper", sigma_upper),
             "sigma_lower": _checks.positive(what, "sigma_lower", sigma_lower), "single": single}
+
+
+# tls_spline_segment and tls_spline_curve of include/tls_amd.h, in order: all doubles
+SPLINE_SEGMENT_FIELDS = ("status", "intervals", "coefficients", "points", "kept", "rounds", "dropped", "sigma", "ssr", "weight")
+SPLINE_CURVE_FIELDS = ("choice", "sigma_pp", "flag", "bic")
+SPLINE_SEGMENT_DTYPE = numpy.dtype([(k, "f8") for k in SPLINE_SEGMENT_FIELDS])
+SPLINE_CURVE_DTYPE = numpy.dtype([(k, "f8") for k in SPLINE_CURVE_FIELDS[:3]] + [("bic", "f8", (SPLINE_MAX_SPACINGS,))])
+
+
+def spline_arguments(t, y, knot_spacing=0.75, break_tolerance=0.5, penalty=1e-3, n_iter=5, sigma_upper=3.0, sigma_lower=3.0,
+                     dy=None, mask=None):
+    """What tls_spline_detrend takes, checked as it checks them: a dict with t (float64 [n], finite and non-decreasing), y
+    (float64 [n_curves, n] over t, finite and > 0; one row becomes [1, n]), dy (None, or y's shape, finite and > 0), mask
+    (None, or uint8 rows of y's shape: detrend_mask_rows), spacings (float64 [k], k in [1, SPLINE_MAX_SPACINGS], each finite
+    and > 0), break_tolerance (> 0, inf allowed), penalty (finite, >= 0), n_iter (an integer in [0, SPLINE_MAX_ITER]),
+    sigma_upper and sigma_lower (> 0, inf allowed, no NaN), segments (int64 [n_seg + 1]: a new segment behind every gap >
+    break_tolerance; none may take more than SPLINE_MAX_COEF coefficients at any spacing), single (y was one row) and
+    one_spacing (knot_spacing was one number).  ValueError otherwise.  GPU-free."""
+    what = "spline detrending"
+    t = _checks.times(what, t, _checks.MAX_ROW_POINTS)
+    try:
+        y = numpy.asarray(y, dtype=numpy.float64)
+        dy = None if dy is None else numpy.asarray(dy, dtype=numpy.float64)
+    except (TypeError, ValueError):
+        raise _checks.refusal(what, "the light curves and dy must hold numbers")
+    single = y.ndim == 1
+    y, dy = _checks.row_shapes(what, t, y, dy, names="flux" if dy is None else "flux and dy")
+    _checks.positive_values(what, y, "flux", "spline detrending")
+    if dy is not None:
+        _checks.positive_values(what, dy, "dy", "spline detrending")
+    spacing, one = _checks.spacings(what, knot_spacing, SPLINE_MAX_SPACINGS)
+    bt = _checks.positive(what, "break_tolerance", break_tolerance)
+    out = {"t": t, "y": numpy.ascontiguousarray(y), "dy": None if dy is None else numpy.ascontiguousarray(dy),
+           "mask": None if mask is None else detrend_mask_rows(mask, y.shape), "spacings": spacing, "break_tolerance": bt,
+           "penalty": _checks.finite_at_least(what, "penalty", penalty),
+           "n_iter": _checks.integer(what, "n_iter", n_iter, 0, SPLINE_MAX_ITER),
+           "sigma_upper": _checks.positive(what, "sigma_upper", sigma_upper),
+           "sigma_lower": _checks.positive(what, "sigma_lower", sigma_lower), "single": single, "one_spacing": one}
+    out["segments"] = _checks.knot_segments(what, t, bt, spacing, SPLINE_MAX_COEF)
+    return out
 
 
 def _f8(a):
@@ -2510,6 +2561,33 @@ class Context(object):
                 raw = numpy.where(coef != 0.0, coef / scale, 0.0)
             out += ({"record": record, "coef": coef, "mean": mean, "scale": scale, "coefficients": raw,
                      "segments": a["segments"]},)
+        return out[0] if len(out) == 1 else out
+
+    def spline_detrend(self, t, y, knot_spacing=0.75, break_tolerance=0.5, penalty=1e-3, n_iter=5, sigma_upper=3.0,
+                       sigma_lower=3.0, dy=None, mask=None, return_trend=False, return_fit=False):
+        """Robust B-spline detrending (tls_spline_detrend; the statement: include/tls_amd.h, tests/spline_spec.py) of the curves
+        y [n_curves, n] (or one row) over t: flat; then trend with return_trend=True; then, with return_fit=True, a dict with
+        segment (SPLINE_SEGMENT_DTYPE [n_curves, n_seg]), curve (SPLINE_CURVE_DTYPE [n_curves]), segments (the index
+        boundaries) and spacings.  ValueError for what spline_arguments refuses."""
+        a = spline_arguments(t, y, knot_spacing, break_tolerance, penalty, n_iter, sigma_upper, sigma_lower, dy, mask)
+        n_c, n = a["y"].shape
+        G = len(a["segments"]) - 1
+        flat = numpy.empty_like(a["y"])
+        trend = numpy.empty_like(a["y"]) if return_trend else None
+        segment = numpy.zeros((n_c, G), dtype=SPLINE_SEGMENT_DTYPE)
+        curve = numpy.zeros(n_c, dtype=SPLINE_CURVE_DTYPE)
+        assert SPLINE_SEGMENT_DTYPE.itemsize == 8 * len(SPLINE_SEGMENT_FIELDS) and SPLINE_CURVE_DTYPE.itemsize == 8 * (3 + SPLINE_MAX_SPACINGS)
+        u8p = ctypes.POINTER(ctypes.c_uint8)
+        self._check(self._lib.tls_spline_detrend(
+            self._h, _dp(a["t"]), _dp(a["y"]), None if a["dy"] is None else _dp(a["dy"]),
+            None if a["mask"] is None else a["mask"].ctypes.data_as(u8p), n, n_c, _dp(a["spacings"]), len(a["spacings"]),
+            a["break_tolerance"], a["penalty"], a["n_iter"], a["sigma_upper"], a["sigma_lower"], _dp(flat),
+            None if trend is None else _dp(trend), segment.ctypes.data_as(ctypes.c_void_p), curve.ctypes.data_as(ctypes.c_void_p)))
+        if a["single"]:
+            flat, trend = flat[0], None if trend is None else trend[0]
+        out = (flat,) + ((trend,) if return_trend else ())
+        if return_fit:
+            out += ({"segment": segment, "curve": curve, "segments": a["segments"], "spacings": a["spacings"]},)
         return out[0] if len(out) == 1 else out
 
     def debug_null_words(self, n, n_rows, seed, first_trial=0, block=None):

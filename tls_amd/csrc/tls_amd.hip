@@ -297,6 +297,7 @@ struct tls_ctx {
     DevBuf<double> d_noise{pool, "d_noise", kScratch};        // tls_noise_profile
     DevBuf<double> d_aliases{pool, "d_aliases", kScratch};    // tls_event_periods
     DevBuf<double> d_decor{pool, "d_decor", kScratch};        // tls_decorrelate
+    DevBuf<double> d_spline{pool, "d_spline", kScratch};      // tls_spline_detrend
     // two-role slab path (series in HBM, one light curve; SearchPlan::split)
     View<unsigned int> d_tile_prefix;        // [n_periods + 1] tiles in front of work item w (queue order)
     DevBuf<double> d_partials{pool, "d_partials", kScratch};  // [split_max_items][3] a tile's winner
@@ -5179,6 +5180,153 @@ int tls_decorrelate(tls_ctx* ctx, const double* y, const double* dy, const uint8
         if (out_mean) TLS_HIP(ctx, hipMemcpyAsync(out_mean + at * S * m, d_mean, rows * S * m * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
         if (out_scale) TLS_HIP(ctx, hipMemcpyAsync(out_scale + at * S * m, d_scale, rows * S * m * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
         TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));       // (the next slab overwrites the device buffers; seg lives until here)
+    }
+    return TLS_OK;
+}
+
+// ---- spline detrending (tls_spline.hip.h, DESIGN.md "Spline detrending"): one workgroup a (segment, spacing, curve).  The
+// host forms the segments of t and q and h of every (spacing, segment); with several spacings a records-only launch, the pick
+// and a launch at the picked spacing follow one another on the stream, with one spacing the fit and the pick.
+static_assert(sizeof(tls_spline_segment) == tlsdev::kSplineSegWords * 8 && sizeof(tls_spline_curve) == tlsdev::kSplineCurveWords * 8,
+              "the header's records are the kernels'");
+static_assert(TLS_SPLINE_MAX_SPACINGS == tlsdev::kSplineMaxSpacings && TLS_SPLINE_MAX_ITER == tlsdev::kSplineMaxIter &&
+              TLS_SPLINE_MAX_COEF == tlsdev::kSplineMaxCoef && TLS_SPLINE_LDS_POINTS == tlsdev::kSplineLdsPoints,
+              "the header's limits");
+static_assert(tlsdev::spline_lds_bytes(tlsdev::kSplineMaxCoef, tlsdev::kSplineLdsPoints, true) <= 160 * 1024, "the LDS of a workgroup");
+
+int tls_spline_detrend(tls_ctx* ctx, const double* t, const double* y, const double* dy, const uint8_t* mask, int64_t n,
+                       int64_t n_rows, const double* spacings, int64_t n_spacings, double break_tolerance, double penalty,
+                       int64_t n_iter, double sigma_upper, double sigma_lower, double* out_flat, double* out_trend,
+                       tls_spline_segment* out_segment_records, tls_spline_curve* out_curve_records) {
+    if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
+    if (n < 1 || n > 100000000) return fail(ctx, TLS_E_ARG, "spline detrending: n out of range [1, 1e8]");
+    if (n_rows < 0) return fail(ctx, TLS_E_ARG, "spline detrending: n_rows < 0");
+    if (n_spacings < 1 || n_spacings > TLS_SPLINE_MAX_SPACINGS) return fail(ctx, TLS_E_ARG, "spline detrending: n_spacings out of range [1, 16]");
+    if (!t || !spacings) return fail(ctx, TLS_E_ARG, "null argument");
+    for (int64_t s = 0; s < n_spacings; ++s)
+        if (!(std::isfinite(spacings[s]) && spacings[s] > 0.0)) return fail(ctx, TLS_E_ARG, "spline detrending: every knot spacing must be finite and > 0");
+    if (!(break_tolerance > 0.0)) return fail(ctx, TLS_E_ARG, "spline detrending: break_tolerance must be > 0");
+    if (!(std::isfinite(penalty) && penalty >= 0.0)) return fail(ctx, TLS_E_ARG, "spline detrending: penalty must be finite and >= 0");
+    if (n_iter < 0 || n_iter > TLS_SPLINE_MAX_ITER) return fail(ctx, TLS_E_ARG, "spline detrending: n_iter out of range [0, 16]");
+    if (!(sigma_upper > 0.0) || !(sigma_lower > 0.0)) return fail(ctx, TLS_E_ARG, "spline detrending: the sigmas must be > 0");
+    const size_t nn = (size_t)n, S = (size_t)n_spacings;
+    for (size_t i = 0; i < nn; ++i)
+        if (!std::isfinite(t[i]) || (i > 0 && t[i] < t[i - 1])) return fail(ctx, TLS_E_ARG, "spline detrending: t must be finite and non-decreasing");
+    // the segments, and q and h of every (spacing, segment)
+    std::vector<long long> seg(1, 0);
+    for (size_t i = 1; i < nn; ++i)
+        if (t[i] - t[i - 1] > break_tolerance) seg.push_back((long long)i);
+    seg.push_back((long long)n);
+    const size_t G = seg.size() - 1;
+    std::vector<int> qs(S * G);
+    std::vector<double> hs(S * G);
+    int m_max = 0;
+    long long longest = 0;
+    for (size_t g = 0; g < G; ++g) {
+        longest = std::max(longest, seg[g + 1] - seg[g]);
+        const double T = t[seg[g + 1] - 1] - t[seg[g]];
+        for (size_t s = 0; s < S; ++s) {
+            int q = 0;
+            double h = (double)NAN;
+            if (T != 0.0) {
+                const double want = std::ceil(T / spacings[s]);
+                if (!(want <= (double)(TLS_SPLINE_MAX_COEF - 3)))
+                    return fail(ctx, TLS_E_ARG, "spline detrending: a segment has more than " + std::to_string(TLS_SPLINE_MAX_COEF) + " coefficients");
+                q = std::max(1, (int)want);
+                h = T / (double)q;
+                m_max = std::max(m_max, q + 3);
+            }
+            qs[s * G + g] = q;
+            hs[s * G + g] = h;
+        }
+    }
+    if (n_rows == 0) return TLS_OK;
+    if (!y || !out_flat || !out_segment_records || !out_curve_records) return fail(ctx, TLS_E_ARG, "null argument");
+    if ((uint64_t)n_rows > (uint64_t)(SIZE_MAX / 8) / ((uint64_t)n * (uint64_t)(S + 2)))
+        return fail(ctx, TLS_E_ARG, "spline detrending: rows too large");
+    for (size_t k = 0; k < (size_t)n_rows * nn; ++k) {
+        if (!(std::isfinite(y[k]) && y[k] > 0.0))
+            return fail(ctx, TLS_E_ARG, "spline detrending: row " + std::to_string(k / nn) + " has a non-finite or non-positive value");
+        if (dy && !(std::isfinite(dy[k]) && dy[k] > 0.0))
+            return fail(ctx, TLS_E_ARG, "spline detrending: dy of row " + std::to_string(k / nn) + " has a non-finite or non-positive value");
+    }
+    TLS_HIP(ctx, hipSetDevice(ctx->device));
+    const bool lds = longest <= tlsdev::kSplineLdsPoints;
+    const int mcap = std::max(4, (m_max + 1) & ~1), pcap = lds ? (int)((longest + 1) & ~1LL) : 0;
+    const size_t lds_bytes = tlsdev::spline_lds_bytes(mcap, pcap, lds);
+    // curves per launch: gridDim.z within its limit, at most 256 MB of rows and at most 256 MB of the long segments' scratch
+    const size_t row_bytes = nn * (8 * (3 + (dy ? 1 : 0)) + (mask ? 1 : 0)), scratch_bytes = lds ? 0 : nn * 17 * S;
+    int64_t slab = std::min<int64_t>({n_rows, (int64_t)65535, (int64_t)((256u << 20) / row_bytes)});
+    if (!lds) slab = std::min<int64_t>(slab, (int64_t)((256u << 20) / scratch_bytes));
+    slab = std::max<int64_t>(1, slab);
+    const size_t B = (size_t)slab;
+    double *d_t, *d_h, *d_y, *d_dy, *d_flat, *d_trend, *d_tried, *d_records, *d_curves, *d_gw, *d_gr;
+    long long* d_seg;
+    int* d_q;
+    unsigned char *d_mask, *d_gmember;
+    Arena L;
+    L.add(d_t, nn);  L.add(d_seg, G + 1);  L.add(d_h, S * G);  L.add(d_q, S * G);                     // of the call
+    L.add(d_y, B * nn);  L.add(d_dy, dy ? B * nn : 0);  L.add(d_flat, B * nn);  L.add(d_trend, B * nn);       // of one slab, from here on
+    L.add(d_tried, S > 1 ? B * S * G * tlsdev::kSplineSegWords : 0);  L.add(d_records, B * G * tlsdev::kSplineSegWords);
+    L.add(d_curves, B * tlsdev::kSplineCurveWords);
+    L.add(d_gw, lds ? 0 : B * S * nn);  L.add(d_gr, lds ? 0 : B * S * nn);                                  // the long segments' scratch
+    L.add(d_mask, mask ? B * nn : 0);  L.add(d_gmember, lds ? 0 : B * S * nn);
+    TLS_HIP(ctx, L.bind(ctx->d_spline));
+    TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_seg, seg.data(), (G + 1) * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_h, hs.data(), S * G * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_q, qs.data(), S * G * 4, hipMemcpyHostToDevice, main_stream(ctx)));
+    auto fit_kernel = lds ? tlsdev::tls_spline_fit_kernel<true> : tlsdev::tls_spline_fit_kernel<false>;
+    TLS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(fit_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+    tlsdev::SplineArgs a;
+    a.t = d_t; a.y = d_y; a.dy = d_dy; a.mask = d_mask; a.seg = d_seg; a.q = d_q; a.h = d_h;
+    a.gw = d_gw; a.gr = d_gr; a.gmember = d_gmember; a.check = nullptr;
+    a.penalty = penalty; a.sigma_upper = sigma_upper; a.sigma_lower = sigma_lower;
+    a.n = (long long)n; a.G = (int)G; a.n_iter = (int)n_iter; a.mcap = mcap; a.pcap = pcap;
+    tlsdev::SplinePickArgs p;
+    p.t = d_t; p.y = d_y; p.mask = d_mask; p.curves = d_curves; p.check = nullptr;
+    p.break_tolerance = break_tolerance; p.n = (int)n; p.G = (int)G; p.S = (int)S;
+#ifdef TLS_DEBUG_CHECKS
+    if (int rc = ensure_check_counters(ctx)) return rc;
+    a.check = ctx->d_check.ptr;
+    p.check = ctx->d_check.ptr;
+#endif
+    for (int64_t k0 = 0; k0 < n_rows; k0 += slab) {
+        const size_t rows = (size_t)std::min<int64_t>(slab, n_rows - k0), at = (size_t)k0;
+        TLS_HIP(ctx, hipMemcpyAsync(d_y, y + at * nn, rows * nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+        if (dy) TLS_HIP(ctx, hipMemcpyAsync(d_dy, dy + at * nn, rows * nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+        if (mask) TLS_HIP(ctx, hipMemcpyAsync(d_mask, mask + at * nn, rows * nn, hipMemcpyHostToDevice, main_stream(ctx)));
+        hipError_t e = hipSuccess;
+        if (S > 1) {                                 // every spacing, the records alone; then the pick
+            a.choice = nullptr; a.flat = nullptr; a.trend = nullptr; a.records = d_tried; a.S = (int)S;
+            hipLaunchKernelGGL(fit_kernel, dim3((unsigned)G, (unsigned)S, (unsigned)rows), dim3(tlsdev::kSplineThreads), lds_bytes, main_stream(ctx), a);
+            e = hipGetLastError();
+            if (e == hipSuccess) {
+                p.records = d_tried;
+                hipLaunchKernelGGL(tlsdev::tls_spline_pick_kernel, dim3((unsigned)rows), dim3(tlsdev::kSplineThreads), 0, main_stream(ctx), p);
+                e = hipGetLastError();
+            }
+        }
+        if (e == hipSuccess) {                       // the fit that goes out: at the picked spacing, or at the only one
+            a.choice = S > 1 ? d_curves : nullptr; a.flat = d_flat; a.trend = d_trend; a.records = d_records; a.S = 1;
+            hipLaunchKernelGGL(fit_kernel, dim3((unsigned)G, 1u, (unsigned)rows), dim3(tlsdev::kSplineThreads), lds_bytes, main_stream(ctx), a);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess && S == 1) {
+            p.records = d_records;
+            hipLaunchKernelGGL(tlsdev::tls_spline_pick_kernel, dim3((unsigned)rows), dim3(tlsdev::kSplineThreads), 0, main_stream(ctx), p);
+            e = hipGetLastError();
+        }
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(main_stream(ctx));
+            return fail(ctx, TLS_E_HIP, std::string("spline detrending launch: ") + hipGetErrorString(e));
+        }
+        ctx->last_kernel = "tls_spline_detrend";
+        TLS_HIP(ctx, hipMemcpyAsync(out_flat + at * nn, d_flat, rows * nn * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+        if (out_trend) TLS_HIP(ctx, hipMemcpyAsync(out_trend + at * nn, d_trend, rows * nn * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+        TLS_HIP(ctx, hipMemcpyAsync(out_segment_records + at * G, d_records, rows * G * tlsdev::kSplineSegWords * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+        TLS_HIP(ctx, hipMemcpyAsync(out_curve_records + at, d_curves, rows * tlsdev::kSplineCurveWords * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+        TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));       // (the next slab overwrites the device buffers; seg, qs and hs live until here)
     }
     return TLS_OK;
 }

@@ -95,7 +95,8 @@ enum CheckCode {
     kChkShape = 14,        // tls_shape_fit: a member's rank or a unit's table index outside its limits; tls_centroid_test: a
                            // shape or an epoch count outside the entry's limits, or an epoch's head outside the series
     kChkViews = 15,        // tls_folded_views: a bin's range outside its part, a member outside the series, or no single middle member
-    kChkNoise = 16,        // tls_noise_profile: a width or a window outside the row, a rank outside its bins, or a count above its windows
+    kChkNoise = 16,        // tls_noise_profile: a width or a window outside the row, a rank outside its bins, or a count above its windows;
+                           // tls_spline_detrend: an interval, a member range or a band row outside the segment's, or a segment over its LDS
 };
 
 constexpr int kWave = 64;
@@ -4463,5 +4464,7 @@ __global__ void __launch_bounds__(512) tls_transit_models(const ModelsArgs a) {
 #include "tls_noise.hip.h"
 // survey-mode regression detrending against shared and per-curve series (tls_decorrelate)
 #include "tls_decorrelate.hip.h"
+// survey-mode robust B-spline detrending with a BIC-chosen knot spacing (tls_spline_detrend)
+#include "tls_spline.hip.h"
 
 }  // namespace tlsdev

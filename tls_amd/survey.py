@@ -548,15 +548,106 @@ def decorrelate_batch(flux_batch, own=None, shared=None, dy_batch=None, mask=Non
     return res[0] if len(res) == 1 else res
 
 
+# ---- detrending: a robust B-spline with a BIC-chosen knot spacing on the device ----------------------------------------------
+class Spline(collections.namedtuple("Spline", ("knot_spacing", "break_tolerance", "penalty", "n_iter", "sigma_upper",
+                                               "sigma_lower"))):
+    """detrend=Spline(knot_spacing=0.75, break_tolerance=0.5, penalty=1e-3, n_iter=5, sigma_upper=3.0, sigma_lower=3.0) on the
+    survey calls: a penalised cubic B-spline fitted robustly to every gap-free segment of every row and divided out
+    (spline_batch), weighted with dy_batch where one is given and with detrend_mask as its mask.  knot_spacing may be a
+    sequence: every row then takes the spacing of its own least BIC.  An immutable value; its fields are checked where it is
+    used."""
+    __slots__ = ()
+
+    def __new__(cls, knot_spacing=0.75, break_tolerance=0.5, penalty=1e-3, n_iter=5, sigma_upper=3.0, sigma_lower=3.0):
+        return super(Spline, cls).__new__(cls, knot_spacing, break_tolerance, penalty, n_iter, sigma_upper, sigma_lower)
+
+
+def spline_fields():
+    """(the fields of a segment record, the fields of a curve record) of spline_batch(..., return_fit=True), in order
+    (tls_spline_segment and tls_spline_curve of include/tls_amd.h); `bic` holds SPLINE_MAX_SPACINGS values."""
+    from ._lib import SPLINE_CURVE_FIELDS, SPLINE_SEGMENT_FIELDS
+    return SPLINE_SEGMENT_FIELDS, SPLINE_CURVE_FIELDS
+
+
+def spline_spacings(t, shortest=0.5, longest=20.0, count=8):
+    """The logarithmic ladder of knot spacings of Shallue & Vanderburg (2018): `count` values from `shortest` to `longest`
+    days, the longest cut to the span of t.  ValueError unless t is finite and non-decreasing, 0 < shortest <= longest < inf
+    and count is an integer in [1, SPLINE_MAX_SPACINGS].  Host only."""
+    from ._lib import SPLINE_MAX_SPACINGS
+    what = "spline spacings"
+    t = _checks.times(what, t, _checks.MAX_ROW_POINTS)
+    shortest = _checks.finite_positive(what, "shortest", shortest)
+    longest = _checks.finite_positive(what, "longest", longest)
+    if longest < shortest:
+        raise _checks.refusal(what, "longest must be >= shortest, got %r < %r" % (longest, shortest))
+    count = _checks.integer(what, "count", count, 1, SPLINE_MAX_SPACINGS)
+    span = float(t[-1] - t[0])
+    if span > shortest:
+        longest = min(longest, span)
+    return numpy.logspace(numpy.log10(shortest), numpy.log10(longest), count)
+
+
+def spline_batch(t, flux_batch, knot_spacing=0.75, break_tolerance=0.5, penalty=1e-3, n_iter=5, sigma_upper=3.0, sigma_lower=3.0,
+                 dy_batch=None, mask=None, return_trend=False, return_fit=False, context=None, device=None, devices=None):
+    """flat = flux / trend for every row of flux_batch ([n] or [n_curves, n], at the shared time stamps t), with trend a cubic
+    B-spline on uniform knots fitted to every gap-free segment by penalised, iteratively sigma-clipped least squares, on the
+    device (tls_spline_detrend): the "Kepler spline" of Vanderburg & Johnson (2014) and Shallue & Vanderburg (2018), the
+    detrender of the TESS Quick-Look Pipeline, wotan's pspline / rspline.  A smooth basis over the whole segment follows a
+    star that rotates in a few days without being shortened until it eats the transit, which a sliding window cannot.
+
+    A new segment starts behind every gap t[j] - t[j-1] > break_tolerance (days; inf: never).  A segment of span T takes
+    q = max(1, ceil(T / knot_spacing)) equal intervals and q + 3 coefficients (at most SPLINE_MAX_COEF = 512).  The normal
+    equations are banded (half-bandwidth 3); penalty * (sum w / q) times the squared second differences of the coefficients is
+    added, so that empty intervals (a short gap, a masked transit) leave the system positive definite; a banded Cholesky
+    solves it.  Then up to n_iter (in [0, SPLINE_MAX_ITER = 16]) clip rounds: sigma = 1.4826 MAD of the members' residuals,
+    members above sigma_upper sigma or below -sigma_lower sigma leave (inf switches a side off), and the segment is fitted
+    again, until a round drops nobody or would leave fewer than two members.  dy_batch gives the weights 1 / dy^2 (None: 1).
+    mask ([n_curves, n] uint8 or bool, != 0: protected; transit_mask) keeps points out of every fit; trend and flat cover EVERY
+    point, and a mask of zeros changes no bit.  A segment without two members at distinct time stamps (status 1), or whose
+    band has no pivot or whose trend leaves (0, inf) (status 2), gets the weighted mean as its trend, so the trend is always
+    finite and > 0.
+
+    knot_spacing may be a sequence of at most SPLINE_MAX_SPACINGS = 16 (spline_spacings): every row then gets the spacing
+    whose fit has the least Bayesian information criterion K log(N) + SSR / sigma_pp^2, with K the coefficients, N the
+    members left, SSR the weighted residual sum over the mean weight and sigma_pp the point-to-point scatter of the row.  The
+    exact steps are in include/tls_amd.h and tests/spline_spec.py; each but the BIC's log is one IEEE double operation in a
+    stated order, so flat, trend and the segment records equal the Python statement bit for bit.  The arguments are checked
+    before any device work (ValueError).
+
+    devices=[...] deals the rows out, with their dy and mask rows.  Returns flat[, trend][, fit]: fit is a dict with `segment`
+    ([n_curves, n_seg] of spline_fields()[0]: status, intervals, coefficients, points, kept, rounds, dropped, sigma, ssr,
+    weight), `curve` ([n_curves] of spline_fields()[1]: choice, sigma_pp, flag, bic [16]), `segments` (index boundaries) and
+    `spacings`."""
+    from ._lib import spline_arguments
+    a = spline_arguments(t, flux_batch, knot_spacing, break_tolerance, penalty, n_iter, sigma_upper, sigma_lower, dy_batch, mask)
+    spacing = float(a["spacings"][0]) if a["one_spacing"] else a["spacings"]
+
+    def call(ctx, lo, hi):
+        flat, trend, fit = ctx.spline_detrend(
+            a["t"], a["y"][lo:hi], spacing, a["break_tolerance"], a["penalty"], a["n_iter"], a["sigma_upper"], a["sigma_lower"],
+            None if a["dy"] is None else a["dy"][lo:hi], None if a["mask"] is None else a["mask"][lo:hi], return_trend=True,
+            return_fit=True)
+        return dict(flat=flat, trend=trend, segment=fit["segment"], curve=fit["curve"])
+
+    out = _run_batch(devices, device, context, len(a["y"]), call)
+    flat, trend = out["flat"], out["trend"]
+    fit = {"segment": out["segment"], "curve": out["curve"], "segments": a["segments"], "spacings": a["spacings"]}
+    if a["single"]:
+        flat, trend = flat[0], trend[0]
+        fit["segment"], fit["curve"] = fit["segment"][0], fit["curve"][0]
+    res = (flat,) + ((trend,) if return_trend else ()) + ((fit,) if return_fit else ())
+    return res[0] if len(res) == 1 else res
+
+
 def _detrend_steps(detrend):
     """The steps of a detrend= argument, left to right: () for None, the one step of an int, a Biweight, a SysRem or a
-    Prewhiten or a Decorrelate, and the elements of a tuple or list of those."""
+    Prewhiten, a Decorrelate or a Spline, and the elements of a tuple or list of those."""
     if detrend is None:
         return ()
-    if isinstance(detrend, (Biweight, SysRem, Prewhiten, Decorrelate)) or not isinstance(detrend, (tuple, list)):
+    if isinstance(detrend, (Biweight, SysRem, Prewhiten, Decorrelate, Spline)) or not isinstance(detrend, (tuple, list)):
         return (detrend,)
     for step in detrend:
-        if step is None or (isinstance(step, (tuple, list)) and not isinstance(step, (Biweight, SysRem, Prewhiten, Decorrelate))):
+        if step is None or (isinstance(step, (tuple, list)) and not isinstance(step, (Biweight, SysRem, Prewhiten, Decorrelate, Spline))):
             raise ValueError("a step of detrend must be a kernel size, a Biweight or a SysRem, got %r" % (step,))
     return tuple(detrend)
 
@@ -601,8 +692,9 @@ def _detrended(t, flux_batch, detrend, context, device, devices, dy_batch=None, 
     [n_curves, len(t)]: biweight_batch for a Biweight, the whole batch through SysRem on the first device (weighted with
     dy_batch where one is given) for a SysRem, prewhiten_batch (on variability_frequencies(t) cut to the step's range, weighted
     with dy_batch where one is given) for a Prewhiten, decorrelate_batch (weighted with dy_batch where one is given) for a
-    Decorrelate, detrend_batch(flux_batch, step) otherwise.  detrend_mask ([n_curves, len(t)], uint8 or bool) goes to every
-    Biweight, Prewhiten and Decorrelate step as its mask; a SysRem step runs unmasked, a median-filter
+    Decorrelate, spline_batch (weighted likewise) for a Spline, detrend_batch(flux_batch, step) otherwise.  detrend_mask
+    ([n_curves, len(t)], uint8 or bool) goes to every Biweight, Prewhiten, Decorrelate and Spline step as its mask; a SysRem step
+    runs unmasked, a median-filter
     step with a mask is a ValueError (before any step runs)."""
     steps = _detrend_steps(detrend)
     if detrend_mask is not None:
@@ -611,7 +703,7 @@ def _detrended(t, flux_batch, detrend, context, device, devices, dy_batch=None, 
             raise ValueError("flux_batch must have shape [n_curves, len(t)]")
         detrend_mask = detrend_mask_rows(detrend_mask, numpy.shape(flux_batch), "detrend_mask")
         for step in steps:
-            if not isinstance(step, (Biweight, SysRem, Prewhiten, Decorrelate)):
+            if not isinstance(step, (Biweight, SysRem, Prewhiten, Decorrelate, Spline)):
                 raise ValueError("detrend_mask: the median filter (detrend=%r) is defined by its sample count and zero padding "
                                  "and has no masked form; use Biweight or Prewhiten steps with a mask" % (step,))
     if not steps:
@@ -636,6 +728,10 @@ def _detrended(t, flux_batch, detrend, context, device, devices, dy_batch=None, 
             flux_batch = decorrelate_batch(flux_batch, step.own, step.shared, dy_batch, detrend_mask, step.segments, step.ridge,
                                            step.n_iter, step.sigma_upper, step.sigma_lower, context=context, device=device,
                                            devices=devices)
+        elif isinstance(step, Spline):
+            flux_batch = spline_batch(t, flux_batch, step.knot_spacing, step.break_tolerance, step.penalty, step.n_iter,
+                                      step.sigma_upper, step.sigma_lower, dy_batch, detrend_mask, context=context, device=device,
+                                      devices=devices)
         else:
             flux_batch = detrend_batch(flux_batch, step, context=context, device=device, devices=devices)
     return flux_batch
@@ -643,7 +739,7 @@ def _detrended(t, flux_batch, detrend, context, device, devices, dy_batch=None, 
 
 def _detrend_rows(ctx, t, rows, detrend):
     """rows as they are (detrend None), or taken through the per-row steps of detrend on ctx: the biweight for a Biweight,
-    pre-whitening with uniform weights for a Prewhiten, the
+    pre-whitening with uniform weights for a Prewhiten, the spline with uniform weights and no mask for a Spline, the
     median filter of kernel size step otherwise (the rows formed on the device by injection_recovery and null_sde, chunk by
     chunk)."""
     for step in _detrend_steps(detrend):
@@ -652,6 +748,8 @@ def _detrend_rows(ctx, t, rows, detrend):
         elif isinstance(step, Prewhiten):
             grid, k, h, low = _prewhiten_step(t, step, len(t))
             rows = ctx.prewhiten(t, rows, grid, k, h, low)
+        elif isinstance(step, Spline):
+            rows = ctx.spline_detrend(t, rows, *step)
         else:
             rows = ctx.medfilt_detrend(rows, step)
     return rows
@@ -1238,7 +1336,7 @@ def power_batch_protected(t, flux_batch, detrend, sde_min, factor=1.5, n_peaks=1
     if "detrend_mask" in power_batch_kwargs:
         raise ValueError("power_batch_protected forms detrend_mask itself")
     for step in _detrend_steps(detrend):
-        if not isinstance(step, (Biweight, SysRem, Prewhiten, Decorrelate)):
+        if not isinstance(step, (Biweight, SysRem, Prewhiten, Decorrelate, Spline)):
             raise ValueError("power_batch_protected: the median filter (detrend=%r) has no masked form; use Biweight or "
                              "Prewhiten steps" % (step,))
     _peaks_request(n_peaks, power_batch_kwargs.get("peak_separation", 0.02), power_batch_kwargs.get("peak_ratios", HARMONICS),
@@ -1391,7 +1489,7 @@ def power_batch_multi(t, flux_batch, sde_min, n_planets=3, detrend=None, protect
     if protect_factor is not None:
         _checks.finite_positive("power_batch_multi", "protect_factor", protect_factor, "must be None or finite and > 0")
         for step in _detrend_steps(detrend):
-            if not isinstance(step, (Biweight, SysRem, Prewhiten, Decorrelate)):
+            if not isinstance(step, (Biweight, SysRem, Prewhiten, Decorrelate, Spline)):
                 raise ValueError("power_batch_multi: the median filter (detrend=%r) has no masked form; use Biweight or "
                                  "Prewhiten steps with protect_factor" % (step,))
     if transit_fit is None or transit_fit is False:
@@ -3509,6 +3607,9 @@ def injection_recovery(t, flux, injections, dy=None, inject_u=None, inject_limb_
             from ._lib import prewhiten_arguments
             grid, k, h, low = _prewhiten_step(t, step, n)
             prewhiten_arguments(t, flux, None, grid, k, h, low)
+        elif isinstance(step, Spline):
+            from ._lib import spline_arguments
+            spline_arguments(t, flux, *step)
         else:
             from ._lib import medfilt_arguments
             medfilt_arguments(flux, step)
@@ -3676,6 +3777,9 @@ def null_sde(t, n_trials, sigma=None, source=None, block=None, seed=0, first_tri
             from ._lib import prewhiten_arguments
             grid, k, h, low = _prewhiten_step(t, step, n)
             prewhiten_arguments(t, numpy.ones(n), None, grid, k, h, low)
+        elif isinstance(step, Spline):
+            from ._lib import spline_arguments
+            spline_arguments(t, numpy.ones(n), *step)
         else:
             from ._lib import medfilt_kernel
             medfilt_kernel(step, n)
