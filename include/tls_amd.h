@@ -42,7 +42,7 @@ extern "C" {
  * (7: tls_shape_fit), (7: tls_nudft, tls_lomb_scargle, tls_sine_test); 8: every entry that takes `root, n_root` takes a
  * second table, `root, root_count, n_root`), (8: tls_ephemeris_match), (8: tls_folded_views),
  * (8: tls_event_vetting), (8: tls_centroid_test), (8: tls_noise_profile), (8: tls_transit_fit), (8: tls_remove_transits),
- * (8: tls_event_periods), (8: tls_decorrelate), (8: tls_spline_detrend). */
+ * (8: tls_event_periods), (8: tls_decorrelate), (8: tls_spline_detrend), (8: tls_clean_rows). */
 #define TLS_AMD_ABI_VERSION 8
 
 #define TLS_OK 0
@@ -1416,6 +1416,58 @@ int tls_spline_detrend(tls_ctx *ctx, const double *t, const double *y, const dou
                        int64_t n_rows, const double *spacings, int64_t n_spacings, double break_tolerance, double penalty,
                        int64_t n_iter, double sigma_upper, double sigma_lower, double *out_flat, double *out_trend,
                        tls_spline_segment *out_segment_records, tls_spline_curve *out_curve_records);
+
+/* ---- survey mode: missing points and outliers flagged and repaired -------------------------------------------------------- */
+/* The cleaning stage in front of every other one: the bad points of every curve are flagged and replaced with defined values,
+ * so that a batch whose stars have their own missing cadences, flares and single-sample glitches keeps its shared time stamps.
+ * t [n] finite and non-decreasing; y [n_rows][n] MAY hold NaN, +-inf, zero and negative values; bad (or NULL) [n_rows][n],
+ * != 0: the caller's quality flag.  window_length > 0 in days gives a sliding centre, 0.0 the row's median.
+ *   flags   uint8 a point: 1 missing, not (isfinite(y) and y > 0); 2 the caller's bad; 4 high outlier; 8 low outlier.  A point
+ *           is valid while its flags are 0.
+ *   windows the biweight's: a new segment starts behind every gap t[j] - t[j-1] > break_tolerance; the window of i is the
+ *           points of its segment with |t[j] - t[i]| <= 0.5 * window_length (at most TLS_BIWEIGHT_MAX_WINDOW).
+ *   median  the middle value, or (a + b) / 2.0 of the two middle ones.
+ *   round   up to n_iter of them, none when both sigmas are inf:
+ *     1  window_length 0: centre = median of the row's valid points, every valid point has a residual.  Else the centre of a
+ *        valid point is the median of the valid points of its window OTHER THAN ITSELF; with fewer than min_points of those
+ *        the point has no residual this round and the clip cannot flag it.
+ *     2  r_i = y_i - centre_i
+ *     3  fewer than two points with a residual: the rounds end, this one is not counted.  Over the points with a residual:
+ *        c0 = median(r);  sigma = 1.4826 * median(|r_i - c0|);  rounds = rounds + 1;  the record's center = the row's median
+ *        (window_length 0) or c0, its sigma = sigma
+ *     4  not (sigma > 0): the rounds end
+ *     5  d_i = r_i - c0;  high: d_i > sigma_upper * sigma;  low candidate: d_i < -(sigma_lower * sigma)
+ *     6  a run: a maximal set of low candidates that are neighbours in the sequence of the round's valid points of one
+ *        segment -- an invalid point is stepped over; a valid point that is no candidate (without a residual, high) and a
+ *        segment boundary end a run.  The candidates of a run of at most max_run are flagged low: a transit, a run of many
+ *        samples, is left alone, and a missing sample inside it does not split it.
+ *     7  nobody flagged: the rounds end.  Fewer than two valid points would be left: the round is not applied, the rounds end.
+ *        Else flags |= 4 (high), |= 8 (low).
+ *   repair  a point with flags != 0, a < i < b its nearest valid points inside its segment:
+ *           both: y_a where t_b == t_a, else y_a + (y_b - y_a) * ((t_i - t_a) / (t_b - t_a));  one: that neighbour's value;
+ *           none: the median of the row's valid points (status |= 1);  a row without a valid point: all 1.0 (status = 2)
+ * Valid points pass through with their bits; the output is finite and > 0.  Every step is one IEEE double operation without
+ * contraction and the medians are selections, so rows, flags and records equal the Python statement in tests/clean_spec.py
+ * bit for bit.  bad of zeros gives the bits of no bad. */
+#define TLS_CLEAN_MAX_ITER 16
+#define TLS_CLEAN_LDS_POINTS 8192    /* a row of at most this many points keeps a round's residuals in the LDS */
+typedef struct tls_clean_record {
+    double status;                 /* 0; |= 1 a segment was filled from the row's median; 2 no valid point in the row */
+    double n_missing, n_bad;       /* points with flag 1, with flag 2 */
+    double n_high, n_low;          /* points with flag 4, with flag 8 */
+    double n_filled;               /* points with any flag */
+    double longest_run;            /* the longest stretch of consecutive filled indices */
+    double rounds;                 /* clip rounds that formed a sigma */
+    double center, sigma;          /* of the last such round (NaN: none) */
+} tls_clean_record;
+/* out_rows [n_rows][n]; out_flags (may be NULL) [n_rows][n]; out_records [n_rows].  Needs no plan and no search, and leaves a
+ * prepared plan as it is.  n_rows == 0 is a no-op.  TLS_E_ARG, before any device work and with the outputs untouched, unless n
+ * is in [1, 1e8], t is finite and non-decreasing, window_length is finite and >= 0, break_tolerance > 0 (inf allowed), both
+ * sigmas > 0 (inf allowed, no NaN), max_run >= 1, n_iter in [0, TLS_CLEAN_MAX_ITER], min_points >= 1 and no window holds more
+ * than TLS_BIWEIGHT_MAX_WINDOW points. */
+int tls_clean_rows(tls_ctx *ctx, const double *t, const double *y, const uint8_t *bad, int64_t n, int64_t n_rows,
+                   double window_length, double break_tolerance, double sigma_upper, double sigma_lower, int64_t max_run,
+                   int64_t n_iter, int64_t min_points, double *out_rows, uint8_t *out_flags, tls_clean_record *out_records);
 
 /* The limb-darkened transit fit: the planet's size, impact parameter and T14 from the dip itself, with the exposure time in
  * the model.  A straight chord at constant speed crosses a limb-darkened disc: the separation is z^2 = b^2 + ((1 + k)^2 - b^2)

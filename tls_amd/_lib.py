@@ -124,6 +124,10 @@ SPLINE_MAX_ITER = 16
 SPLINE_MAX_COEF = 512
 SPLINE_LDS_POINTS = 5120
 SPLINE_PIVOT = 1e-10
+# include/tls_amd.h TLS_CLEAN_*: the most clip rounds of tls_clean_rows, and the points of a row whose residuals a round keeps
+# in the LDS (the noise profile's selection: NOISE_LDS_POINTS; a longer row runs on device memory)
+CLEAN_MAX_ITER = 16
+CLEAN_LDS_POINTS = 8192
 PEAKS_LDS_PERIODS = 1 << 20   # tls_peaks.hip.h kPeaksLdsPeriods: a longer grid keeps its alive mask in device memory, not in LDS
 
 # every symbol include/tls_amd.h declares (tests check the export list against the header)
@@ -140,7 +144,7 @@ SYMBOLS = (
     "tls_ephemeris_match", "tls_folded_views", "tls_event_vetting", "tls_centroid_test", "tls_noise_profile",
     "tls_transit_fit",
     "tls_transit_mask", "tls_biweight_detrend_masked", "tls_prewhiten_masked",
-    "tls_remove_transits", "tls_event_periods", "tls_decorrelate", "tls_spline_detrend",
+    "tls_remove_transits", "tls_event_periods", "tls_decorrelate", "tls_spline_detrend", "tls_clean_rows",
     "tls_comm_unique_id", "tls_comm_init", "tls_comm_destroy", "tls_comm_info", "tls_comm_allgather_results", "tls_comm_allgather_device", "tls_comm_fetch_gathered",
     "tls_comm_stage_results", "tls_comm_allgather_staged", "tls_comm_fetch_staged",
     "tls_comm_barrier", "tls_comm_max",
@@ -1236,6 +1240,9 @@ def load():
     lib.tls_spline_detrend.restype = ci
     lib.tls_spline_detrend.argtypes = [vp, _c_double_p, _c_double_p, _c_double_p, u8p, i64, i64, _c_double_p, i64, dbl, dbl, i64, dbl,
                                        dbl, _c_double_p, _c_double_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.tls_clean_rows.restype = ci
+    lib.tls_clean_rows.argtypes = [vp, _c_double_p, _c_double_p, u8p, i64, i64, dbl, dbl, dbl, dbl, i64, i64, i64, _c_double_p, u8p,
+                                   ctypes.c_void_p]
     lib.tls_debug_peak_phase_scans.restype = ci
     lib.tls_debug_peak_phase_scans.argtypes = [vp, _c_double_p, i64, ctypes.c_void_p, _c_int64_p, i64, _c_double_p, _c_double_p,
                                                i64, dbl, _c_double_p, _c_double_p, i64, i64, ctypes.c_void_p, i64, i64,
@@ -1599,6 +1606,43 @@ def spline_arguments(t, y, knot_spacing=0.75, break_tolerance=0.5, penalty=1e-3,
            "sigma_lower": _checks.positive(what, "sigma_lower", sigma_lower), "single": single, "one_spacing": one}
     out["segments"] = _checks.knot_segments(what, t, bt, spacing, SPLINE_MAX_COEF)
     return out
+
+
+# tls_clean_record of include/tls_amd.h, in order: all doubles
+CLEAN_FIELDS = ("status", "n_missing", "n_bad", "n_high", "n_low", "n_filled", "longest_run", "rounds", "center", "sigma")
+CLEAN_DTYPE = numpy.dtype([(k, "f8") for k in CLEAN_FIELDS])
+
+
+def clean_arguments(t, y, window_length=None, break_tolerance=0.5, sigma_upper=4.0, sigma_lower=float("inf"), max_run=1, n_iter=3,
+                    min_points=3, bad=None):
+    """What tls_clean_rows takes, checked as it checks them: a dict with t (float64 [n], finite and non-decreasing), y (float64
+    [n_curves, n] over t; ANY values, NaN and infinities included; one row becomes [1, n]), bad (None, or uint8 rows of y's
+    shape: detrend_mask_rows), window_length (None: the row's median; else finite and > 0, no window over BIWEIGHT_MAX_WINDOW
+    points), break_tolerance (> 0, inf allowed), sigma_upper and sigma_lower (> 0, inf allowed, no NaN), max_run (an integer
+    >= 1), n_iter (an integer in [0, CLEAN_MAX_ITER]), min_points (an integer >= 1) and single (y was one row).  ValueError
+    otherwise.  GPU-free."""
+    what = "cleaning"
+    t = _checks.times(what, t, _checks.MAX_ROW_POINTS)
+    try:
+        y = numpy.asarray(y, dtype=numpy.float64)
+    except (TypeError, ValueError):
+        raise _checks.refusal(what, "the light curves must hold numbers")
+    single = y.ndim == 1
+    y, _ = _checks.row_shapes(what, t, y, names="flux")
+    bt = _checks.positive(what, "break_tolerance", break_tolerance)
+    if window_length is not None:
+        window_length = _checks.finite_positive(what, "window_length", window_length, "must be None or finite and > 0")
+        try:
+            biweight_windows(t, window_length, bt)
+        except ValueError as e:
+            raise _checks.refusal(what, str(e))
+    return {"t": t, "y": numpy.ascontiguousarray(y), "bad": None if bad is None else detrend_mask_rows(bad, y.shape, "bad"),
+            "window_length": window_length, "break_tolerance": bt,
+            "sigma_upper": _checks.positive(what, "sigma_upper", sigma_upper),
+            "sigma_lower": _checks.positive(what, "sigma_lower", sigma_lower),
+            "max_run": _checks.integer(what, "max_run", max_run, 1, 2 ** 62),
+            "n_iter": _checks.integer(what, "n_iter", n_iter, 0, CLEAN_MAX_ITER),
+            "min_points": _checks.integer(what, "min_points", min_points, 1, 2 ** 31 - 1), "single": single}
 
 
 def _f8(a):
@@ -2588,6 +2632,29 @@ class Context(object):
         out = (flat,) + ((trend,) if return_trend else ())
         if return_fit:
             out += ({"segment": segment, "curve": curve, "segments": a["segments"], "spacings": a["spacings"]},)
+        return out[0] if len(out) == 1 else out
+
+    def clean_rows(self, t, y, window_length=None, break_tolerance=0.5, sigma_upper=4.0, sigma_lower=float("inf"), max_run=1,
+                   n_iter=3, min_points=3, bad=None, return_flags=False, return_record=False):
+        """The cleaning stage (tls_clean_rows; the statement: include/tls_amd.h, tests/clean_spec.py) of the curves y
+        [n_curves, n] (or one row) over t, which may hold NaN, infinities and values <= 0: the repaired rows; then, with
+        return_flags=True, the flags (uint8: 1 missing, 2 the caller's bad, 4 high, 8 low); then, with return_record=True, the
+        records (CLEAN_DTYPE [n_curves]).  ValueError for what clean_arguments refuses."""
+        a = clean_arguments(t, y, window_length, break_tolerance, sigma_upper, sigma_lower, max_run, n_iter, min_points, bad)
+        n_c, n = a["y"].shape
+        rows = numpy.empty_like(a["y"])
+        flags = numpy.empty((n_c, n), dtype=numpy.uint8)
+        record = numpy.zeros(n_c, dtype=CLEAN_DTYPE)
+        assert CLEAN_DTYPE.itemsize == 8 * len(CLEAN_FIELDS)
+        u8p = ctypes.POINTER(ctypes.c_uint8)
+        self._check(self._lib.tls_clean_rows(
+            self._h, _dp(a["t"]), _dp(a["y"]), None if a["bad"] is None else a["bad"].ctypes.data_as(u8p), n, n_c,
+            0.0 if a["window_length"] is None else a["window_length"], a["break_tolerance"], a["sigma_upper"], a["sigma_lower"],
+            a["max_run"], a["n_iter"], a["min_points"], _dp(rows), flags.ctypes.data_as(u8p),
+            record.ctypes.data_as(ctypes.c_void_p)))
+        if a["single"]:
+            rows, flags, record = rows[0], flags[0], record[0]
+        out = (rows,) + ((flags,) if return_flags else ()) + ((record,) if return_record else ())
         return out[0] if len(out) == 1 else out
 
     def debug_null_words(self, n, n_rows, seed, first_trial=0, block=None):

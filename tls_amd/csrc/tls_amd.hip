@@ -298,6 +298,7 @@ struct tls_ctx {
     DevBuf<double> d_aliases{pool, "d_aliases", kScratch};    // tls_event_periods
     DevBuf<double> d_decor{pool, "d_decor", kScratch};        // tls_decorrelate
     DevBuf<double> d_spline{pool, "d_spline", kScratch};      // tls_spline_detrend
+    DevBuf<double> d_clean{pool, "d_clean", kScratch};        // tls_clean_rows
     // two-role slab path (series in HBM, one light curve; SearchPlan::split)
     View<unsigned int> d_tile_prefix;        // [n_periods + 1] tiles in front of work item w (queue order)
     DevBuf<double> d_partials{pool, "d_partials", kScratch};  // [split_max_items][3] a tile's winner
@@ -5180,6 +5181,145 @@ int tls_decorrelate(tls_ctx* ctx, const double* y, const double* dy, const uint8
         if (out_mean) TLS_HIP(ctx, hipMemcpyAsync(out_mean + at * S * m, d_mean, rows * S * m * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
         if (out_scale) TLS_HIP(ctx, hipMemcpyAsync(out_scale + at * S * m, d_scale, rows * S * m * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
         TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));       // (the next slab overwrites the device buffers; seg lives until here)
+    }
+    return TLS_OK;
+}
+
+// ---- cleaning (tls_clean.hip.h, DESIGN.md "Cleaning"): flags, rounds of a robust clip, repair.  The host forms the segments
+// and (for a sliding centre) the biweight's windows and tiles once a call; a round is the tile pass (a sliding centre only) and
+// the per-row kernel, and the host reads one count a round: the rows still running.
+static_assert(sizeof(tls_clean_record) == tlsdev::kCleanWords * 8, "the header's record is the kernels'");
+static_assert(TLS_CLEAN_MAX_ITER == tlsdev::kCleanMaxIter && TLS_CLEAN_LDS_POINTS == tlsdev::kNoiseLdsPoints, "the header's limits");
+static_assert(tlsdev::clean_row_lds_bytes(tlsdev::kNoiseLdsPoints, true) <= 160 * 1024, "the LDS of a workgroup");
+static_assert(tlsdev::clean_tile_lds_bytes(tlsdev::kDetrendMaxSpan, tlsdev::kDetrendMaxSpan) <= 160 * 1024, "the LDS of a workgroup");
+
+int tls_clean_rows(tls_ctx* ctx, const double* t, const double* y, const uint8_t* bad, int64_t n, int64_t n_rows,
+                   double window_length, double break_tolerance, double sigma_upper, double sigma_lower, int64_t max_run,
+                   int64_t n_iter, int64_t min_points, double* out_rows, uint8_t* out_flags, tls_clean_record* out_records) {
+    if (!ctx) return fail(nullptr, TLS_E_ARG, "null context");
+    if (n < 1 || n > 100000000) return fail(ctx, TLS_E_ARG, "cleaning: n out of range [1, 1e8]");
+    if (n_rows < 0) return fail(ctx, TLS_E_ARG, "cleaning: n_rows < 0");
+    if (!(std::isfinite(window_length) && window_length >= 0.0))
+        return fail(ctx, TLS_E_ARG, "cleaning: window_length must be finite and > 0, or 0 for the row's median");
+    if (!(break_tolerance > 0.0)) return fail(ctx, TLS_E_ARG, "cleaning: break_tolerance must be > 0");
+    if (!(sigma_upper > 0.0) || !(sigma_lower > 0.0)) return fail(ctx, TLS_E_ARG, "cleaning: the sigmas must be > 0");
+    if (max_run < 1) return fail(ctx, TLS_E_ARG, "cleaning: max_run must be >= 1");
+    if (n_iter < 0 || n_iter > TLS_CLEAN_MAX_ITER) return fail(ctx, TLS_E_ARG, "cleaning: n_iter out of range [0, 16]");
+    if (min_points < 1 || min_points > INT32_MAX) return fail(ctx, TLS_E_ARG, "cleaning: min_points must be >= 1");
+    if (!t) return fail(ctx, TLS_E_ARG, "null argument");
+    for (int64_t i = 0; i < n; ++i)
+        if (!std::isfinite(t[i]) || (i > 0 && !(t[i] >= t[i - 1])))
+            return fail(ctx, TLS_E_ARG, "cleaning: t must be finite and non-decreasing (index " + std::to_string(i) + ")");
+    const size_t nn = (size_t)n;
+    const bool sliding = window_length > 0.0;
+    // the segments, and the biweight's windows: [lo_i, hi_i) inside i's segment, |t[j] - t[i]| <= window_length / 2
+    std::vector<int> seg(nn), lo, hi;
+    for (int64_t i = 0, s = 0; i < n; ++i) {
+        if (i > 0 && t[i] - t[i - 1] > break_tolerance) ++s;
+        seg[(size_t)i] = (int)s;
+    }
+    int64_t wmax = 0;
+    if (sliding) {
+        lo.resize(nn);
+        hi.resize(nn);
+        const double half = 0.5 * window_length;
+        int64_t start = 0, wlo = 0, whi = 0;
+        for (int64_t i = 0; i < n; ++i) {
+            if (i > 0 && t[i] - t[i - 1] > break_tolerance) start = i;
+            wlo = std::max(wlo, start);
+            while (std::fabs(t[wlo] - t[i]) > half) ++wlo;
+            whi = std::max(whi, i + 1);
+            while (whi < n && !(t[whi] - t[whi - 1] > break_tolerance) && std::fabs(t[whi] - t[i]) <= half) ++whi;
+            lo[(size_t)i] = (int)wlo;
+            hi[(size_t)i] = (int)whi;
+            wmax = std::max(wmax, whi - wlo);
+        }
+        if (wmax > TLS_BIWEIGHT_MAX_WINDOW)
+            return fail(ctx, TLS_E_ARG, "cleaning: a window holds " + std::to_string(wmax) + " points, more than " +
+                                            std::to_string(TLS_BIWEIGHT_MAX_WINDOW));
+    }
+    if (n_rows == 0) return TLS_OK;
+    if (!y || !out_rows || !out_records) return fail(ctx, TLS_E_ARG, "null argument");
+    if ((uint64_t)n_rows > (uint64_t)(SIZE_MAX / 32) / (uint64_t)n) return fail(ctx, TLS_E_ARG, "cleaning: rows too large");
+    TLS_HIP(ctx, hipSetDevice(ctx->device));
+    const bool rounds_wanted = n_iter > 0 && !(std::isinf(sigma_upper) && std::isinf(sigma_lower));
+    const bool lds = n <= tlsdev::kNoiseLdsPoints;
+    // rows per launch: the grid's limit, and at most 256 MB of rows, residuals, flags and codes
+    const int64_t slab = std::max<int64_t>(1, std::min<int64_t>({n_rows, (int64_t)65535, (int64_t)((256u << 20) / (27 * nn))}));
+    const size_t B = (size_t)slab;
+    double *d_t, *d_y, *d_r, *d_out, *d_records;
+    unsigned long long* d_counts;
+    int *d_seg, *d_lo, *d_hi;
+    unsigned int* d_run;
+    unsigned char *d_bad, *d_flags, *d_code;
+    Arena L;
+    L.add(d_t, nn);  L.add(d_counts, (size_t)TLS_CLEAN_MAX_ITER);                                           // of the call
+    L.add(d_y, B * nn);  L.add(d_r, B * nn);  L.add(d_out, B * nn);  L.add(d_records, B * tlsdev::kCleanWords);   // of one slab, from here on
+    L.add(d_seg, nn);  L.add(d_lo, sliding ? nn : 0);  L.add(d_hi, sliding ? nn : 0);  L.add(d_run, B);
+    L.add(d_bad, bad ? B * nn : 0);  L.add(d_flags, B * nn);  L.add(d_code, lds ? 0 : B * nn);
+    TLS_HIP(ctx, L.bind(ctx->d_clean));
+    TLS_HIP(ctx, hipMemcpyAsync(d_t, t, nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+    TLS_HIP(ctx, hipMemcpyAsync(d_seg, seg.data(), nn * sizeof(int), hipMemcpyHostToDevice, main_stream(ctx)));
+    int T = 0, P = 0, smax = 0;
+    size_t tile_lds = 0;
+    if (sliding) {
+        TLS_HIP(ctx, hipMemcpyAsync(d_lo, lo.data(), nn * sizeof(int), hipMemcpyHostToDevice, main_stream(ctx)));
+        TLS_HIP(ctx, hipMemcpyAsync(d_hi, hi.data(), nn * sizeof(int), hipMemcpyHostToDevice, main_stream(ctx)));
+        biweight_plan(lo, hi, wmax, &T, &P, &smax);
+        tile_lds = tlsdev::clean_tile_lds_bytes(P, smax);
+        TLS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(tlsdev::tls_clean_tile), hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_lds));
+    }
+    auto row_kernel = lds ? tlsdev::tls_clean_row_kernel<true> : tlsdev::tls_clean_row_kernel<false>;
+    const size_t row_lds = tlsdev::clean_row_lds_bytes((int)n, lds);
+    TLS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(row_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)row_lds));
+    tlsdev::CleanArgs a;
+    a.t = d_t; a.seg = d_seg; a.y = d_y; a.bad = d_bad; a.flags = d_flags; a.r = d_r; a.code = d_code; a.out = d_out;
+    a.records = d_records; a.run = d_run; a.counts = d_counts; a.check = nullptr; a.lo = sliding ? d_lo : nullptr;
+    a.hi = sliding ? d_hi : nullptr; a.sigma_upper = sigma_upper; a.sigma_lower = sigma_lower; a.max_run = (long long)max_run;
+    a.n = (long long)n; a.n_iter = (int)n_iter; a.min_points = (int)min_points; a.round = 0; a.rounds_wanted = rounds_wanted ? 1 : 0;
+    a.tile = T; a.span = P; a.smax = smax;
+#ifdef TLS_DEBUG_CHECKS
+    if (int rc = ensure_check_counters(ctx)) return rc;
+    a.check = ctx->d_check.ptr;
+#endif
+    auto launched = [&](const char* what) -> int {
+        const hipError_t e = hipGetLastError();
+        if (e == hipSuccess) return TLS_OK;
+        (void)hipStreamSynchronize(main_stream(ctx));
+        return fail(ctx, TLS_E_HIP, std::string("cleaning ") + what + " launch: " + hipGetErrorString(e));
+    };
+    const unsigned tiles = sliding ? (unsigned)((n + T - 1) / T) : 0u;
+    for (int64_t k0 = 0; k0 < n_rows; k0 += slab) {
+        const size_t rows = (size_t)std::min<int64_t>(slab, n_rows - k0), at = (size_t)k0 * nn;
+        TLS_HIP(ctx, hipMemcpyAsync(d_y, y + at, rows * nn * 8, hipMemcpyHostToDevice, main_stream(ctx)));
+        if (bad) TLS_HIP(ctx, hipMemcpyAsync(d_bad, bad + at, rows * nn, hipMemcpyHostToDevice, main_stream(ctx)));
+        TLS_HIP(ctx, hipMemsetAsync(d_counts, 0, TLS_CLEAN_MAX_ITER * 8, main_stream(ctx)));
+        a.count = (long long)rows * (long long)n;
+        const unsigned blocks = (unsigned)std::min<long long>((a.count + tlsdev::kDetrendThreads - 1) / tlsdev::kDetrendThreads, 65536);
+        hipLaunchKernelGGL(tlsdev::tls_clean_init, dim3(blocks), dim3(tlsdev::kDetrendThreads), 0, main_stream(ctx), a);
+        if (int rc = launched("init")) return rc;
+        for (int64_t k = 0; rounds_wanted && k < n_iter; ++k) {
+            a.round = (int)k;
+            if (sliding) {
+                hipLaunchKernelGGL(tlsdev::tls_clean_tile, dim3(tiles, (unsigned)rows), dim3(tlsdev::kDetrendThreads), tile_lds, main_stream(ctx), a);
+                if (int rc = launched("tile")) return rc;
+            }
+            hipLaunchKernelGGL(row_kernel, dim3((unsigned)rows), dim3(tlsdev::kNoiseThreads), row_lds, main_stream(ctx), a);
+            if (int rc = launched("row")) return rc;
+            if (k + 1 < n_iter) {
+                unsigned long long going = 0;
+                TLS_HIP(ctx, hipMemcpyAsync(&going, d_counts + k, 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+                TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));
+                if (going == 0) break;
+            }
+        }
+        hipLaunchKernelGGL(tlsdev::tls_clean_repair_kernel, dim3((unsigned)rows), dim3(tlsdev::kNoiseThreads), 0, main_stream(ctx), a);
+        if (int rc = launched("repair")) return rc;
+        ctx->last_kernel = "tls_clean_rows";
+        TLS_HIP(ctx, hipMemcpyAsync(out_rows + at, d_out, rows * nn * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+        if (out_flags) TLS_HIP(ctx, hipMemcpyAsync(out_flags + at, d_flags, rows * nn, hipMemcpyDeviceToHost, main_stream(ctx)));
+        TLS_HIP(ctx, hipMemcpyAsync(out_records + k0, d_records, rows * tlsdev::kCleanWords * 8, hipMemcpyDeviceToHost, main_stream(ctx)));
+        TLS_HIP(ctx, hipStreamSynchronize(main_stream(ctx)));       // (the next slab overwrites the device buffers; seg, lo and hi live until here)
     }
     return TLS_OK;
 }

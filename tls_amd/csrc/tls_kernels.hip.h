@@ -96,7 +96,8 @@ enum CheckCode {
                            // shape or an epoch count outside the entry's limits, or an epoch's head outside the series
     kChkViews = 15,        // tls_folded_views: a bin's range outside its part, a member outside the series, or no single middle member
     kChkNoise = 16,        // tls_noise_profile: a width or a window outside the row, a rank outside its bins, or a count above its windows;
-                           // tls_spline_detrend: an interval, a member range or a band row outside the segment's, or a segment over its LDS
+                           // tls_spline_detrend: an interval, a member range or a band row outside the segment's, or a segment over its LDS;
+                           // tls_clean_rows: a count above the row's, or a neighbour outside it (its tiles count under kChkBiweight)
 };
 
 constexpr int kWave = 64;
@@ -4466,5 +4467,7 @@ __global__ void __launch_bounds__(512) tls_transit_models(const ModelsArgs a) {
 #include "tls_decorrelate.hip.h"
 // survey-mode robust B-spline detrending with a BIC-chosen knot spacing (tls_spline_detrend)
 #include "tls_spline.hip.h"
+// survey-mode cleaning: missing points and outliers flagged and repaired (tls_clean_rows)
+#include "tls_clean.hip.h"
 
 }  // namespace tlsdev

@@ -639,15 +639,170 @@ def spline_batch(t, flux_batch, knot_spacing=0.75, break_tolerance=0.5, penalty=
     return res[0] if len(res) == 1 else res
 
 
+# ---- cleaning: missing points and outliers flagged and repaired on the device -----------------------------------------------
+class Clean(collections.namedtuple("Clean", ("window_length", "sigma_upper", "sigma_lower", "max_run", "n_iter", "min_points",
+                                             "break_tolerance"))):
+    """detrend=Clean(window_length=None, sigma_upper=4.0, sigma_lower=inf, max_run=1, n_iter=3, min_points=3,
+    break_tolerance=0.5) on the survey calls: the bad points of every row flagged and repaired (clean_batch), the repaired rows
+    handed on.  As the FIRST step it admits rows with NaN, infinite and non-positive values, which every other call and step
+    refuses.  It hands on no flags: later steps see the repaired rows and the caller's detrend_mask alone, and with
+    detrend_mask it runs unmasked, as SysRem does.  For stars with trends: (Clean(sigma_upper=inf), <detrender>,
+    Clean(None, 4.0)) -- repair, flatten, clip.  An immutable value; its fields are checked where it is used."""
+    __slots__ = ()
+
+    def __new__(cls, window_length=None, sigma_upper=4.0, sigma_lower=float("inf"), max_run=1, n_iter=3, min_points=3,
+                break_tolerance=0.5):
+        return super(Clean, cls).__new__(cls, window_length, sigma_upper, sigma_lower, max_run, n_iter, min_points,
+                                         break_tolerance)
+
+
+def _clean_step(step):
+    """The keywords of clean_batch and Context.clean_rows of a Clean step."""
+    return dict(window_length=step.window_length, break_tolerance=step.break_tolerance, sigma_upper=step.sigma_upper,
+                sigma_lower=step.sigma_lower, max_run=step.max_run, n_iter=step.n_iter, min_points=step.min_points)
+
+
+def clean_fields():
+    """The fields of a record of clean_batch(..., return_record=True), in order (tls_clean_record of include/tls_amd.h)."""
+    from ._lib import CLEAN_FIELDS
+    return CLEAN_FIELDS
+
+
+def clean_batch(t, flux_batch, window_length=None, break_tolerance=0.5, sigma_upper=4.0, sigma_lower=float("inf"), max_run=1,
+                n_iter=3, min_points=3, bad=None, return_flags=False, return_record=False, context=None, device=None,
+                devices=None):
+    """The rows of flux_batch ([n] or [n_curves, n], at the shared time stamps t) with their bad points flagged and replaced
+    with defined values, on the device (tls_clean_rows): the counterpart of the reference's cleaned_array and of a sigma clip
+    that keeps every row on the shared time stamps, so that everything downstream keeps its plans.  flux_batch MAY hold NaN,
+    infinities, zeros and negative values; bad ([n_curves, n] uint8 or bool, != 0) is the caller's quality flag.
+
+    Flags (uint8 a point): 1 missing, not (isfinite(y) and y > 0), cleaned_array's conditions; 2 the caller's bad; 4 high
+    outlier; 8 low outlier.  A point is valid while its flags are 0.  Up to n_iter (in [0, CLEAN_MAX_ITER = 16]) clip rounds
+    run, none when both sigmas are inf.  A round forms a centre for every valid point -- window_length None: the median of the
+    row's valid points; else the median of the valid points of its window OTHER THAN ITSELF (the biweight's windows: inside
+    the segment, a new one behind every gap > break_tolerance days, within half a window_length; with fewer than min_points
+    such members the point has no residual and cannot be flagged) -- the residuals r, c0 = median(r) and sigma = 1.4826
+    median(|r - c0|).  Points with r - c0 > sigma_upper sigma are flagged high.  Points with r - c0 < -sigma_lower sigma are
+    low candidates, and a candidate is flagged low only when its run -- the candidates that are neighbours among the valid
+    points of one segment -- holds at most max_run of them: a single-sample glitch goes, a transit of many samples stays, and
+    a missing sample inside a transit does not split it.  The rounds end after one that flags nothing; a round that would
+    leave fewer than two valid points is not applied.  inf switches a side off (sigma_lower's default: a dip is what a
+    search looks for).
+
+    Repair: a flagged point between two valid points of its segment is interpolated linearly in time; with one valid
+    neighbour it takes that value; a segment without a valid point takes the row's median of valid points; a row without one
+    becomes all 1.0.  Valid points keep their bits, and the result is finite and > 0.  The exact steps are in
+    include/tls_amd.h and tests/clean_spec.py; each is one IEEE double operation and the medians are selections, so rows,
+    flags and records equal the Python statement bit for bit.
+
+    A sliding centre on an UNDETRENDED fast rotator eats the shoulders of its transits (the centre lags the curvature there;
+    DESIGN.md "Cleaning" has the counts): repair first, flatten, and clip the flattened rows --
+    detrend=(Clean(sigma_upper=inf), <detrender>, Clean(None, 4.0)).  An interpolated point carries no noise: a row whose
+    transits are mostly missing gains no depth, but its SDE is that of a slightly quieter row.
+
+    devices=[...] deals the rows out, with their bad rows.  The arguments are checked before any device work (ValueError).
+    Returns rows[, flags][, record]: record is a structured array [n_curves] of clean_fields() -- status (|= 1: a segment
+    was filled from the row's median; 2: no valid point), n_missing, n_bad, n_high, n_low, n_filled, longest_run (consecutive
+    filled indices), rounds, center and sigma of the last round (NaN: none)."""
+    from ._lib import clean_arguments
+    a = clean_arguments(t, flux_batch, window_length, break_tolerance, sigma_upper, sigma_lower, max_run, n_iter, min_points, bad)
+
+    def call(ctx, lo, hi):
+        rows, flags, record = ctx.clean_rows(
+            a["t"], a["y"][lo:hi], a["window_length"], a["break_tolerance"], a["sigma_upper"], a["sigma_lower"], a["max_run"],
+            a["n_iter"], a["min_points"], None if a["bad"] is None else a["bad"][lo:hi], return_flags=True, return_record=True)
+        return dict(rows=rows, flags=flags, record=record)
+
+    out = _run_batch(devices, device, context, len(a["y"]), call)
+    rows, flags, record = out["rows"], out["flags"], out["record"]
+    if a["single"]:
+        rows, flags, record = rows[0], flags[0], record[0]
+    res = (rows,) + ((flags,) if return_flags else ()) + ((record,) if return_record else ())
+    return res[0] if len(res) == 1 else res
+
+
+def align_rows(times, fluxes, t, tolerance=None):
+    """Per-star series snapped onto a shared grid, on the host: the way from "my stars have their own time stamps and gaps" to
+    clean_batch and power_batch.  times and fluxes: one (t_k, y_k) a star, t_k sorted (non-decreasing) and finite, y_k of its
+    length (NaN allowed); t [n]: the shared grid, finite and strictly ascending.  Every sample goes to the nearest grid stamp
+    if that lies within `tolerance` days (default: half the median step of t; the lower index wins a tie), else it is
+    dropped.  A grid point takes the mean of its samples -- their sum in index order from 0.0, over their count -- and NaN
+    where it has none.
+
+    The time error: the samples are searched AT THE GRID'S time stamps.  Stars of one field share cadence numbers but not
+    barycentric times: across a TESS camera the correction spreads by about 100 s, against a cadence of 120 s to 1800 s, across
+    a Kepler module far less.  offset_mean is each star's mean t_sample - t_grid over the samples kept -- add it to a T0 found
+    on the grid -- and offset_max the largest |t_sample - t_grid|, the error left in a single point.
+
+    Returns (flux_batch [n_stars, n] with NaN where a star has no sample, n_dropped [n_stars] int64, offset_mean [n_stars],
+    offset_max [n_stars]; NaN offsets for a star without a sample kept).  ValueError for shapes that disagree, a grid that is
+    not finite and strictly ascending, time stamps of a star that are not finite and sorted, and a tolerance that is not
+    finite and >= 0."""
+    what = "align_rows"
+    t = _checks.times(what, t, _checks.MAX_ROW_POINTS)
+    n = len(t)
+    if n > 1 and not numpy.all(t[1:] > t[:-1]):
+        raise _checks.refusal(what, "the grid t must ascend strictly")
+    if tolerance is None:
+        tolerance = 0.5 * float(numpy.median(numpy.diff(t))) if n > 1 else 0.0
+    tolerance = _checks.finite_at_least(what, "tolerance", tolerance)
+    try:
+        n_stars = len(times)
+        same = n_stars == len(fluxes)
+    except TypeError:
+        raise _checks.refusal(what, "times and fluxes must be sequences with one entry a star")
+    if not same:
+        raise _checks.refusal(what, "times and fluxes must have one entry a star each, got %d and %d" % (n_stars, len(fluxes)))
+    out = numpy.full((n_stars, n), numpy.nan)
+    n_dropped = numpy.zeros(n_stars, dtype=numpy.int64)
+    offset_mean, offset_max = numpy.full(n_stars, numpy.nan), numpy.full(n_stars, numpy.nan)
+    for k in range(n_stars):
+        tk = numpy.asarray(times[k], dtype=numpy.float64)
+        yk = numpy.asarray(fluxes[k], dtype=numpy.float64)
+        if tk.ndim != 1 or yk.shape != tk.shape:
+            raise _checks.refusal(what, "star %d: time stamps and flux must be 1-d and of one length" % k)
+        if not numpy.all(numpy.isfinite(tk)) or not numpy.all(tk[1:] >= tk[:-1]):
+            raise _checks.refusal(what, "star %d: the time stamps must be finite and sorted" % k)
+        if len(tk) == 0:
+            continue
+        right = numpy.clip(numpy.searchsorted(t, tk, side="left"), 0, n - 1)
+        left = numpy.maximum(right - 1, 0)
+        at = numpy.where(numpy.abs(tk - t[left]) <= numpy.abs(t[right] - tk), left, right)   # (the lower index wins a tie)
+        off = tk - t[at]
+        keep = numpy.abs(off) <= tolerance
+        n_dropped[k] = int((~keep).sum())
+        if not keep.any():
+            continue
+        at, off, y = at[keep], off[keep], yk[keep]
+        total, count = numpy.zeros(n), numpy.zeros(n)
+        numpy.add.at(total, at, y)                   # (unbuffered: a grid point's samples are added in index order)
+        numpy.add.at(count, at, 1.0)
+        hit = count > 0
+        out[k, hit] = total[hit] / count[hit]
+        offset_mean[k] = float(off.mean())
+        offset_max[k] = float(numpy.abs(off).max())
+    return out, n_dropped, offset_mean, offset_max
+
+
+def _clean_first(t, flux_batch, detrend, context, device, devices):
+    """(rows, the steps left) of the calls that check their rows before they detrend them: a Clean at the head of detrend is
+    run here, so that the check sees the repaired rows; anything else comes back as it is."""
+    steps = _detrend_steps(detrend)
+    if not steps or not isinstance(steps[0], Clean):
+        return flux_batch, detrend
+    rows = clean_batch(t, flux_batch, context=context, device=device, devices=devices, **_clean_step(steps[0]))
+    return rows, (steps[1:] or None)
+
+
 def _detrend_steps(detrend):
     """The steps of a detrend= argument, left to right: () for None, the one step of an int, a Biweight, a SysRem or a
-    Prewhiten, a Decorrelate or a Spline, and the elements of a tuple or list of those."""
+    Prewhiten, a Decorrelate, a Spline or a Clean, and the elements of a tuple or list of those."""
     if detrend is None:
         return ()
-    if isinstance(detrend, (Biweight, SysRem, Prewhiten, Decorrelate, Spline)) or not isinstance(detrend, (tuple, list)):
+    if isinstance(detrend, (Biweight, SysRem, Prewhiten, Decorrelate, Spline, Clean)) or not isinstance(detrend, (tuple, list)):
         return (detrend,)
     for step in detrend:
-        if step is None or (isinstance(step, (tuple, list)) and not isinstance(step, (Biweight, SysRem, Prewhiten, Decorrelate, Spline))):
+        if step is None or (isinstance(step, (tuple, list)) and not isinstance(step, (Biweight, SysRem, Prewhiten, Decorrelate, Spline, Clean))):
             raise ValueError("a step of detrend must be a kernel size, a Biweight or a SysRem, got %r" % (step,))
     return tuple(detrend)
 
@@ -694,7 +849,7 @@ def _detrended(t, flux_batch, detrend, context, device, devices, dy_batch=None, 
     with dy_batch where one is given) for a Prewhiten, decorrelate_batch (weighted with dy_batch where one is given) for a
     Decorrelate, spline_batch (weighted likewise) for a Spline, detrend_batch(flux_batch, step) otherwise.  detrend_mask
     ([n_curves, len(t)], uint8 or bool) goes to every Biweight, Prewhiten, Decorrelate and Spline step as its mask; a SysRem step
-    runs unmasked, a median-filter
+    and a Clean step (clean_batch: the repaired rows go on, the flags do not) run unmasked, a median-filter
     step with a mask is a ValueError (before any step runs)."""
     steps = _detrend_steps(detrend)
     if detrend_mask is not None:
@@ -703,7 +858,7 @@ def _detrended(t, flux_batch, detrend, context, device, devices, dy_batch=None, 
             raise ValueError("flux_batch must have shape [n_curves, len(t)]")
         detrend_mask = detrend_mask_rows(detrend_mask, numpy.shape(flux_batch), "detrend_mask")
         for step in steps:
-            if not isinstance(step, (Biweight, SysRem, Prewhiten, Decorrelate, Spline)):
+            if not isinstance(step, (Biweight, SysRem, Prewhiten, Decorrelate, Spline, Clean)):
                 raise ValueError("detrend_mask: the median filter (detrend=%r) is defined by its sample count and zero padding "
                                  "and has no masked form; use Biweight or Prewhiten steps with a mask" % (step,))
     if not steps:
@@ -732,6 +887,8 @@ def _detrended(t, flux_batch, detrend, context, device, devices, dy_batch=None, 
             flux_batch = spline_batch(t, flux_batch, step.knot_spacing, step.break_tolerance, step.penalty, step.n_iter,
                                       step.sigma_upper, step.sigma_lower, dy_batch, detrend_mask, context=context, device=device,
                                       devices=devices)
+        elif isinstance(step, Clean):                # (unmasked, and its flags are no mask for the steps behind it)
+            flux_batch = clean_batch(t, flux_batch, context=context, device=device, devices=devices, **_clean_step(step))
         else:
             flux_batch = detrend_batch(flux_batch, step, context=context, device=device, devices=devices)
     return flux_batch
@@ -740,6 +897,7 @@ def _detrended(t, flux_batch, detrend, context, device, devices, dy_batch=None, 
 def _detrend_rows(ctx, t, rows, detrend):
     """rows as they are (detrend None), or taken through the per-row steps of detrend on ctx: the biweight for a Biweight,
     pre-whitening with uniform weights for a Prewhiten, the spline with uniform weights and no mask for a Spline, the
+    cleaning stage for a Clean, the
     median filter of kernel size step otherwise (the rows formed on the device by injection_recovery and null_sde, chunk by
     chunk)."""
     for step in _detrend_steps(detrend):
@@ -750,6 +908,8 @@ def _detrend_rows(ctx, t, rows, detrend):
             rows = ctx.prewhiten(t, rows, grid, k, h, low)
         elif isinstance(step, Spline):
             rows = ctx.spline_detrend(t, rows, *step)
+        elif isinstance(step, Clean):
+            rows = ctx.clean_rows(t, rows, **_clean_step(step))
         else:
             rows = ctx.medfilt_detrend(rows, step)
     return rows
@@ -1336,7 +1496,7 @@ def power_batch_protected(t, flux_batch, detrend, sde_min, factor=1.5, n_peaks=1
     if "detrend_mask" in power_batch_kwargs:
         raise ValueError("power_batch_protected forms detrend_mask itself")
     for step in _detrend_steps(detrend):
-        if not isinstance(step, (Biweight, SysRem, Prewhiten, Decorrelate, Spline)):
+        if not isinstance(step, (Biweight, SysRem, Prewhiten, Decorrelate, Spline, Clean)):
             raise ValueError("power_batch_protected: the median filter (detrend=%r) has no masked form; use Biweight or "
                              "Prewhiten steps" % (step,))
     _peaks_request(n_peaks, power_batch_kwargs.get("peak_separation", 0.02), power_batch_kwargs.get("peak_ratios", HARMONICS),
@@ -1489,7 +1649,7 @@ def power_batch_multi(t, flux_batch, sde_min, n_planets=3, detrend=None, protect
     if protect_factor is not None:
         _checks.finite_positive("power_batch_multi", "protect_factor", protect_factor, "must be None or finite and > 0")
         for step in _detrend_steps(detrend):
-            if not isinstance(step, (Biweight, SysRem, Prewhiten, Decorrelate, Spline)):
+            if not isinstance(step, (Biweight, SysRem, Prewhiten, Decorrelate, Spline, Clean)):
                 raise ValueError("power_batch_multi: the median filter (detrend=%r) has no masked form; use Biweight or "
                                  "Prewhiten steps with protect_factor" % (step,))
     if transit_fit is None or transit_fit is False:
@@ -1508,6 +1668,8 @@ def power_batch_multi(t, flux_batch, sde_min, n_planets=3, detrend=None, protect
     raw = numpy.asarray(flux_batch, dtype=numpy.float64)
     if raw.ndim != 2 or raw.shape[1] != len(t) or len(raw) < 1:
         raise ValueError("flux_batch must have shape [n_curves, len(t)]")
+    # (a Clean at the head of detrend repairs the raw rows ONCE: the fitted transits are divided out of the repaired rows)
+    raw, detrend = _clean_first(t, raw, detrend, where["context"], where["device"], where["devices"])
     dy_batch = power_batch_kwargs.get("dy_batch")
     if dy_batch is not None:
         dy_batch = numpy.asarray(dy_batch, dtype=numpy.float64)
@@ -2947,6 +3109,8 @@ def lomb_scargle(t, flux_batch, frequencies=None, dy_batch=None, peaks=None, wit
     if frequencies is None:
         frequencies = variability_frequencies(t)
     one = numpy.ndim(flux_batch) == 1
+    if numpy.ndim(flux_batch) == 2:                  # (a Clean at the head of detrend repairs the rows before they are checked)
+        flux_batch, detrend = _clean_first(t, flux_batch, detrend, context, device, devices)
     a = lomb_scargle_arguments(t, flux_batch, dy_batch, frequencies, peaks, peak_separation)
     rows = _detrended(a["t"], a["y"], detrend, context, device, devices, a["dy"], detrend_mask)
 
@@ -3599,20 +3763,25 @@ def injection_recovery(t, flux, injections, dy=None, inject_u=None, inject_limb_
                       None, sde_threshold, period_tolerance, aliases, epoch_tolerance)
     _no_ensemble_step(detrend, "injection_recovery")
     _no_regression_step(detrend, "injection_recovery")
+    # (behind a Clean at the head the later steps see repaired rows: their checks take rows of ones of flux's shape)
+    probe = numpy.ones(flux.shape) if isinstance((_detrend_steps(detrend) or (None,))[0], Clean) else flux
     for step in _detrend_steps(detrend):
         if isinstance(step, Biweight):
             from ._lib import biweight_arguments
-            biweight_arguments(t, flux, step.window_length, step.break_tolerance)
+            biweight_arguments(t, probe, step.window_length, step.break_tolerance)
         elif isinstance(step, Prewhiten):
             from ._lib import prewhiten_arguments
             grid, k, h, low = _prewhiten_step(t, step, n)
-            prewhiten_arguments(t, flux, None, grid, k, h, low)
+            prewhiten_arguments(t, probe, None, grid, k, h, low)
         elif isinstance(step, Spline):
             from ._lib import spline_arguments
-            spline_arguments(t, flux, *step)
+            spline_arguments(t, probe, *step)
+        elif isinstance(step, Clean):
+            from ._lib import clean_arguments
+            clean_arguments(t, flux, **_clean_step(step))
         else:
             from ._lib import medfilt_arguments
-            medfilt_arguments(flux, step)
+            medfilt_arguments(probe, step)
     consts = injection_constants(table)
 
     def form(ctx, lo, hi):
@@ -3780,6 +3949,9 @@ def null_sde(t, n_trials, sigma=None, source=None, block=None, seed=0, first_tri
         elif isinstance(step, Spline):
             from ._lib import spline_arguments
             spline_arguments(t, numpy.ones(n), *step)
+        elif isinstance(step, Clean):
+            from ._lib import clean_arguments
+            clean_arguments(t, numpy.ones(n), **_clean_step(step))
         else:
             from ._lib import medfilt_kernel
             medfilt_kernel(step, n)
